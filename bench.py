@@ -2,6 +2,8 @@
 
     python bench.py --gpus N --steps K --warmup W          (N > 1: the parent starts N rank processes itself, one per GPU, before any GPU call;
                                                             under `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` it is a rank)
+    python bench.py ... --dump-outputs DIR                 (after the timed steps: the last step's outputs as DIR/<name>.npy, float32, seeded inputs —
+                                                            two builds compared output for output)
 
 Model (BASELINE.json configs[1..3], "cfg2" / "cfg3" / "cfg4"): TemporalModel(1 layer, embed_dim 256, 8 heads, max_len 2024, scale_ratio 8, 3 field
 groups, AdaLN, SEA exchange), synthetic cylinder_flow-shaped encoded fields x ~ N(0,1) [B, 2024, 3, 256] with one scalar condition per step,
@@ -248,6 +250,32 @@ def _timed(step, n_steps, warmup, dist, dev):
     return elapsed, r
 
 
+DUMP_BYTES = 64 << 20           # --dump-outputs: all arrays of one run together
+DUMP_ELEMS_PER_ARRAY = 4 << 20  # larger outputs are written as a fixed, seeded sample of this many elements
+
+
+def _host_copy(t, sample_seed=0):
+    """A device output as a float32 CPU tensor, flattened to a fixed sample of DUMP_ELEMS_PER_ARRAY elements when it is larger (the same sorted
+    indices for the same numel in every run: torch.randint under a fixed seed, duplicates dropped)."""
+    t = t.detach().float()
+    if t.numel() > DUMP_ELEMS_PER_ARRAY:
+        idx = torch.randint(t.numel(), (DUMP_ELEMS_PER_ARRAY,), generator=torch.Generator().manual_seed(sample_seed)).unique()
+        t = t.reshape(-1)[idx.to(t.device)]
+    return t.cpu()
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs DIR: each {name: CPU tensor} as DIR/<name>.npy in float32."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.numel() * 4 for a in arrays.values())
+    assert total <= DUMP_BYTES, f"--dump-outputs: {total} bytes over the {DUMP_BYTES}-byte budget"
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a.numpy().astype(np.float32, copy=False))
+    log(f"dumped {', '.join(f'{k} {tuple(v.shape)}' for k, v in arrays.items())} to {out_dir}")
+
+
 def _launch_time_ms(rec, reps=20):
     """Average duration of one launch of a record: `reps` back-to-back launches between two HIP events recorded on the launch stream — captured in one
     graph (no dispatch gap between them: the figure rocprofv3's per-kernel average agrees with) when no process group is alive; with one alive the
@@ -417,15 +445,18 @@ def leg_rollout(args, dist, dev, rank, world, steps, warmup, B):
         assert torch.isfinite(out).all()
     ms = elapsed / steps * 1e3
     gflop = algorithmic_gflop(B, T, F, E, H, D, S, L)
+    dumps = {"rollout_out": _host_copy(out)} if args.dump_outputs else None   # the last timed step's forward output (--dump-outputs)
 
     def again():
         """The same W warm-up + K timed steps once more (run_rank calls it behind the other legs of a default run, when the device has been busy for seconds)."""
         with torch.no_grad():
             el, o = _timed(step, steps, warmup, dist, dev)
             assert torch.isfinite(o).all()
+            if dumps is not None:
+                dumps["rollout_out"] = _host_copy(o)
         return el
 
-    return {"value": world * B * steps / elapsed, "unit": "trajectory-steps/s", "ms_per_step": ms, "steps": steps, "_again": again,
+    return {"value": world * B * steps / elapsed, "unit": "trajectory-steps/s", "ms_per_step": ms, "steps": steps, "_again": again, "_dumps": dumps,
             "workload": f"cfg2: cylinder_flow temporal model E={E} H={H} F={F} L={L} adaln, forward-only rollout step at T={T} (recompute mode), B={B} per GPU",
             "replay": "hip-graph" if use_graph else "plain (one native call per step: sea_run_list)", "order": "per-launch timing pass, then W warm-up + K timed steps",
             "model_algorithmic_gflop_per_step": gflop,
@@ -462,9 +493,11 @@ def leg_train(args, dist, dev, rank, world, steps, warmup, B):
     log(f"train leg: cfg3/cfg4 fwd+bwd+AdamW, B={B} per GPU, world {world}, {steps} timed steps")
     elapsed, loss = _timed(lambda: eng.train_step(x, tgt, ib, opt), steps, warmup, dist, dev)
     assert torch.isfinite(loss).all()
+    # --dump-outputs: what the last timed step gave its caller — the loss, and the parameters its AdamW step updated in place (the live prefix of the flat buffer)
+    dumps = {"train_loss": _host_copy(loss.reshape(1)), "train_params": _host_copy(eng.params.flat32[:eng.params.n_live])} if args.dump_outputs else None
     ms = elapsed / steps * 1e3
     gflop = 3 * algorithmic_gflop(B, T, F, E, H, D, S, L)
-    out = {"allreduce_calls_per_step": int(getattr(eng, "last_allreduce_calls", 0)), "value": world * B * steps / elapsed, "unit": "trajectory-steps/s", "train_steps_per_s": steps / elapsed, "ms_per_step": ms, "steps": steps,
+    out = {"_dumps": dumps, "allreduce_calls_per_step": int(getattr(eng, "last_allreduce_calls", 0)), "value": world * B * steps / elapsed, "unit": "trajectory-steps/s", "train_steps_per_s": steps / elapsed, "ms_per_step": ms, "steps": steps,
            "workload": f"cfg{'3' if world == 1 else '4'}: cylinder_flow temporal model E={E} H={H} F={F} L={L} adaln, fwd+bwd+AdamW (teacher-forced, T={T}), B={B} per GPU, "
                        f"global batch {world * B}",
            "parallelism": f"dp{world}: replicated model, batch split by rank, the flat gradient all-reduced once per step (RCCL; every element once, in up to three slices "
@@ -690,6 +723,11 @@ def run_rank(args):
             r["ms_per_step"], r["value"] = el / r["steps"] * 1e3, world * (args.batch or 1) * r["steps"] / el
             r["model_mfma_frac"] = r["model_algorithmic_gflop_per_step"] / (r["ms_per_step"] * 1e-3) / 1e3 / PEAK_BF16_TFLOPS
             r["order"] = "per-launch timing pass, W + K steps (from idle), the other legs, then W warm-up + K timed steps again (device busy): the line's value"
+    dumps = {}
+    for k in ("rollout", "train"):
+        dumps.update(res.get(k, {}).pop("_dumps", None) or {})
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, dumps)
     if rank == 0:
         h = res[headline]
         hk = h["cfg2_2024_steps"] if headline == "kv" else h
@@ -798,6 +836,10 @@ def main():
     ap.add_argument("--mode", default="all", choices=["all", "rollout", "train", "kv", "shipped", "decode", "encode"],
                     help="all: every leg in one line (default); rollout / train / kv: one leg; decode / encode: the spatial decoder / encoder legs "
                          "(SURVEY.md §8f ranks 1 and 2)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float32; arrays over "
+                         f"{DUMP_ELEMS_PER_ARRAY} elements as a fixed seeded sample; {DUMP_BYTES >> 20} MB at most): the rollout forward's output, the train "
+                         "step's loss and updated parameters, the decode / encode legs' outputs; the inputs are seeded, the same in every run")
     args = ap.parse_args()
     if args.mode == "decode":
         return main_decode(args)
@@ -916,6 +958,8 @@ def main_decode(args):
             "roofline": {"kernel": "decode.layer2 over the needed columns (gemm_grouped)", "bound": "hbm", "achieved": alg_bytes / (k_ms * 1e-3) / 1e9, "peak": 8000.0, "unit": "GB/s",
                          "frac": alg_bytes / (k_ms * 1e-3) / 1e9 / 8000.0, "traffic": None, "launch_ms": k_ms, "launch_gflop": flops / 1e9,
                          "mfma_tflops": flops / (k_ms * 1e-3) / 1e12}}
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"decode_fields": _host_copy(out)})
     print(json.dumps(line))
 
 
@@ -977,6 +1021,8 @@ def main_encode(args):
             "roofline": {"kernel": "encode.layer1 (gemm_grouped, GELU epilogue; one chunk)", "bound": "hbm", "achieved": alg_bytes / (k_ms * 1e-3) / 1e9, "peak": 8000.0,
                          "unit": "GB/s", "frac": alg_bytes / (k_ms * 1e-3) / 1e9 / 8000.0, "traffic": None, "launch_ms": k_ms, "launch_gflop": flops / 1e9,
                          "mfma_tflops": flops / (k_ms * 1e-3) / 1e12}}
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"encode_z": _host_copy(z)})
     print(json.dumps(line))
 
 

@@ -481,6 +481,27 @@ def eval_case():
     shutil.rmtree(tmp, ignore_errors=True)
 
 
+def config_cases():
+    """The reference's config dicts (configs/<case>.py: get_config_temporal / get_config_spatial) as JSON; credential values are not stored."""
+    import importlib.util
+    import json
+
+    print("reference_configs")
+    out = {}
+    for case in ("cylinder_flow", "multiphase_flow"):
+        spec = importlib.util.spec_from_file_location("ref_cfg_" + case, os.path.join(REF, "configs", case + ".py"))
+        mod = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(mod)
+        for kind in ("temporal", "spatial"):
+            cfg = getattr(mod, "get_config_" + kind)()
+            out[f"{case}/{kind}"] = {k: (None if "KEY" in k.upper() else v) for k, v in cfg.items()}
+    path = os.path.join(HERE, "reference_configs.json")
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(f"  wrote reference_configs.json  {os.path.getsize(path) / 1024:.1f} KiB")
+
+
 def OrderedDictMerge(a, b):
     out = dict(a)
     out.update(b)
@@ -506,6 +527,7 @@ def main():
         "encode": encode_cases,
         "unpatch": unpatch_cases,
         "dataset": dataset_cases,
+        "configs": config_cases,
     }
     # ablation variants of the exchange / info-bottleneck: forward only
     cases["model_addition_adaln_f3"] = lambda: model_case("model_addition_adaln_f3", OracleConfig(2, 64, 4, 80, 8, 0, 3, 2, True, "adaln", "addition"), 2, 33)

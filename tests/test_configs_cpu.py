@@ -1,6 +1,7 @@
-"""Config mirrors (reference configs/cylinder_flow.py:73-162, configs/multiphase_flow.py:73-162): key / value equality with the imported
-reference dicts in the build container; the shipped temporal-model values pinned literally everywhere else."""
-import importlib.util
+"""Config mirrors (reference configs/cylinder_flow.py:73-162, configs/multiphase_flow.py:73-162): key / value equality with the reference's
+dicts, stored as tests/golden/reference_configs.json by tests/golden/make_fixtures.py (credential values not stored); the shipped temporal-model
+values pinned literally."""
+import json
 import os
 
 import pytest
@@ -8,7 +9,8 @@ import pytest
 from sea_amd.configs import get_config
 from sea_amd.configs import cylinder_flow, multiphase_flow
 
-REF = "/root/reference/configs"
+from tests.conftest import GOLDEN
+
 MODEL_KEYS = ('num_layers', 'embed_dim', 'n_heads', 'block_size', 'scale_ratio', 'src_len', 'num_fields', 'down_proj', 'dropout', 'exchange_mode',
               'pos_encoding_mode', 'ib_scale_mode', 'ib_addition_mode', 'ib_mlp_layers', 'ib_num', 'add_info_after_cross', 'LN_type')
 
@@ -25,16 +27,11 @@ def test_shipped_temporal_values():
     assert get_config('cylinder_flow', 'temporal') == cyl and get_config('multiphase_flow', 'spatial') == multiphase_flow.get_config_spatial()
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="the reference tree exists only in the build container")
 @pytest.mark.parametrize("case", ["cylinder_flow", "multiphase_flow"])
 @pytest.mark.parametrize("kind", ["temporal", "spatial"])
 def test_keys_and_values_equal_reference(case, kind):
-    import sys
-    sys.dont_write_bytecode = True
-    spec = importlib.util.spec_from_file_location("ref_cfg_" + case, f"{REF}/{case}.py")
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    ref = getattr(mod, "get_config_" + kind)()
+    with open(os.path.join(GOLDEN, "reference_configs.json")) as f:
+        ref = json.load(f)[f"{case}/{kind}"]
     mine = get_config(case, kind)
     for k, v in ref.items():
         if 'KEY' in k.upper() or k == 'use_wandb':   # credentials are never mirrored; wandb is not part of this build
