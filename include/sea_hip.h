@@ -41,7 +41,7 @@ enum {
 int sea_abi_version(void);
 const char* sea_last_error(void);
 /* sizeof of every ABI struct in declaration order (SeaGemmGroup, SeaQkvGroup, SeaQkvCommon, SeaAttnProblem,
- * SeaAttnParams, SeaNormGroup, SeaSiluGroup, SeaIbParams, ..., SeaLaunchRec, SeaGemmNormGroup, SeaExchangeTail, SeaMlpGroup, SeaMlp2Group, SeaKvNorm, SeaKvField, SeaKvPair, SeaKvLayer, SeaKvGlobal, SeaStepPatch, SeaRowChain, SeaAdalnGroup, SeaAdalnQkv, SeaSplitkGroup last): lets a binding verify its layout.  Host only. */
+ * SeaAttnParams, SeaNormGroup, SeaSiluGroup, SeaIbParams, ..., SeaLaunchRec, SeaGemmNormGroup, SeaExchangeTail, SeaMlpGroup, SeaMlp2Group, SeaKvNorm, SeaKvField, SeaKvPair, SeaKvLayer, SeaKvGlobal, SeaStepPatch, SeaRowChain, SeaAdalnGroup, SeaAdalnQkv, SeaSplitkGroup, SeaEncBlock last): lets a binding verify its layout.  Host only. */
 int sea_struct_sizes(int* out, int cap);
 /* Number of compute units / name of device 0's architecture as HIP reports them (diagnostics for bench.py). */
 int sea_device_info(int* cu_count, char* arch, int arch_len);
@@ -844,6 +844,59 @@ void sea_kv_debug_stamps(unsigned long long* buf);
  * Returns 0 when both maps are as documented in cdna_hip_programming.md §3.
  */
 int sea_selftest_mfma(void);
+
+
+/* ------------------------------------------------------------------------------------------------------------
+ * One EncoderBlock of the spatial encoder (reference models/base_blocks.py:123-139: x += MHA(LN(x)); x += MLP_x4(LN(x)), weight-only
+ * LayerNorms, un-masked attention without rotary embedding, projection without bias, MLP = Linear, LayerNorm + GELU, Linear), fused per snapshot:
+ * one workgroup owns the P rows of one snapshot and runs every phase of the block; rows m = snapshot * P + patch.
+ *
+ * sea_encoder_block_fwd: Zout = block(Zin).  ONE launch per block.
+ * sea_encoder_block_bwd: from dZout, recomputes the block's forward from Zin and writes dZin (f32) plus the activation-dtype operands of ONE
+ *   sea_wgrad_grouped launch that yields every parameter gradient of the block (Linear: dY | X pairs; LayerNorm weights / bias: the column sums of
+ *   u1, u2, u3w, u3b, i.e. the db of a wgrad group).  The backward of a block is therefore two launches.
+ * Supported: dtype SEA_BF16, W in {32, 64}, H = 8 (head dim W / 8), S = 4 W, 1 <= P <= 128 — anything else returns SEA_EUNSUPPORTED (-3)
+ * and the caller composes the block from the other entry points.  Weights are act [out, in] (nn.Linear layout); wqkv = [q; k; v] rows, bqkv f32 [3W].
+ * ws: f32 workspace of >= sea_encoder_block_ws_floats(B, P, W) floats, private to the call.
+ */
+typedef struct {
+    const float* Zin;   /* f32 [M, W] block input */
+    float* Zout;        /* f32 [M, W] block output (forward) */
+    const void* wqkv;   /* act [3W, W] */
+    const float* bqkv;  /* f32 [3W] */
+    const void* wo;     /* act [W, W] */
+    const void* w1;     /* act [S, W] */
+    const float* b1;    /* f32 [S] */
+    const float* lnw;   /* f32 [S] */
+    const float* lnb;   /* f32 [S] */
+    const void* w2;     /* act [W, S] */
+    const float* b2;    /* f32 [W] */
+    const float* g1;    /* f32 [W] ln_exp1_1.weight */
+    const float* g2;    /* f32 [W] ln_exp1_2.weight */
+    const float* dZout; /* f32 [M, W] (backward) */
+    float* dZin;        /* f32 [M, W] (backward; may not alias dZout) */
+    /* backward outputs, act, contiguous rows: the wgrad operands */
+    void* n1;    /* [M, W]  LN1 output: X of q / k / v */
+    void* dqkv;  /* [M, 3W] dY of q | k | v */
+    void* att;   /* [M, W]  attention output: X of the projection */
+    void* dz1;   /* [M, W]  dY of the projection */
+    void* n2;    /* [M, W]  X of fc1 */
+    void* dh;    /* [M, S]  dY of fc1 */
+    void* hg;    /* [M, S]  X of fc2 */
+    void* dz2;   /* [M, W]  dY of fc2 */
+    void* u1;    /* [M, W]  column sums = d ln_exp1_1.weight */
+    void* u2;    /* [M, W]  column sums = d ln_exp1_2.weight */
+    void* u3w;   /* [M, S]  column sums = d mlp LayerNorm weight */
+    void* u3b;   /* [M, S]  column sums = d mlp LayerNorm bias */
+    float* ws;
+    int64_t ws_floats;
+    int32_t B, P, W, H;
+    float eps;
+    int32_t pad_;
+} SeaEncBlock;
+int64_t sea_encoder_block_ws_floats(int B, int P, int W);
+int sea_encoder_block_fwd(const SeaEncBlock* params, int dtype, void* stream);
+int sea_encoder_block_bwd(const SeaEncBlock* params, int dtype, void* stream);
 
 #ifdef __cplusplus
 }

@@ -164,6 +164,12 @@ class SeaAdalnGroup(C.Structure):
 MAX_SPLITK_GROUPS = 8
 
 
+class SeaEncBlock(C.Structure):
+    _fields_ = [(n, _vp) for n in ("Zin", "Zout", "wqkv", "bqkv", "wo", "w1", "b1", "lnw", "lnb", "w2", "b2", "g1", "g2", "dZout", "dZin",
+                                   "n1", "dqkv", "att", "dz1", "n2", "dh", "hg", "dz2", "u1", "u2", "u3w", "u3b", "ws")] + \
+                [("ws_floats", _i64), ("B", _i32), ("P", _i32), ("W", _i32), ("H", _i32), ("eps", _f32), ("pad_", _i32)]
+
+
 class SeaSplitkGroup(C.Structure):
     _fields_ = [("P", _vp), ("bias", _vp), ("R", _vp), ("C32", _vp), ("Cact", _vp), ("p_stride", _i64), ("S", _i32), ("M", _i32), ("N", _i32), ("ldp", _i32),
                 ("ldr", _i32), ("ldc32", _i32), ("ldcact", _i32), ("bias_scale", _f32)]
@@ -306,6 +312,11 @@ def lib() -> C.CDLL:
     L.sea_adaln_qkv.restype = C.c_int
     L.sea_splitk_finish.argtypes = [C.POINTER(SeaSplitkGroup), C.c_int, C.c_int, _vp]
     L.sea_splitk_finish.restype = C.c_int
+    L.sea_encoder_block_ws_floats.argtypes = [C.c_int, C.c_int, C.c_int]
+    L.sea_encoder_block_ws_floats.restype = _i64
+    for name in ("sea_encoder_block_fwd", "sea_encoder_block_bwd"):
+        getattr(L, name).argtypes = [C.POINTER(SeaEncBlock), C.c_int, _vp]
+        getattr(L, name).restype = C.c_int
     L.sea_run_list.argtypes = [C.POINTER(SeaLaunchRec), C.c_int, _vp]
     L.sea_run_list.restype = C.c_int
     L.sea_run_list_steps.argtypes = [C.POINTER(SeaLaunchRec), C.c_int, C.POINTER(SeaStepPatch), C.c_int, C.c_int, C.c_int, _vp]
@@ -334,7 +345,7 @@ def lib() -> C.CDLL:
 
 ABI_STRUCTS = (SeaGemmGroup, SeaQkvGroup, SeaQkvCommon, SeaAttnProblem, SeaAttnParams, SeaNormGroup, SeaSiluGroup,
                SeaIbParams, SeaWgradGroup, SeaNormBwdGroup, SeaSiluBwdGroup, SeaIbBwdParams, SeaAttnBwdProblem, SeaAttnBwdParams,
-               SeaDropout, SeaLaunchRec, SeaGemmNormGroup, SeaExchangeTail, SeaMlpGroup, SeaMlp2Group, SeaKvNorm, SeaKvField, SeaKvPair, SeaKvLayer, SeaKvGlobal, SeaStepPatch, SeaRowChain, SeaAdalnGroup, SeaAdalnQkv, SeaSplitkGroup)
+               SeaDropout, SeaLaunchRec, SeaGemmNormGroup, SeaExchangeTail, SeaMlpGroup, SeaMlp2Group, SeaKvNorm, SeaKvField, SeaKvPair, SeaKvLayer, SeaKvGlobal, SeaStepPatch, SeaRowChain, SeaAdalnGroup, SeaAdalnQkv, SeaSplitkGroup, SeaEncBlock)
 
 EXPORTED_SYMBOLS = (
     "sea_abi_version", "sea_last_error", "sea_struct_sizes", "sea_device_info", "sea_gemm_grouped", "sea_qkv_rope_grouped",
@@ -343,6 +354,7 @@ EXPORTED_SYMBOLS = (
     "sea_wgrad_grouped", "sea_transpose_weights", "sea_rownorm_bwd", "sea_silu_outer_bwd", "sea_ib_bwd",
     "sea_attention_bwd", "sea_dropout_mask", "sea_run_list", "sea_run_list_steps", "sea_unpatchify", "sea_gemm_rownorm", "sea_exchange_tail", "sea_patchify", "sea_silu_outer_ib", "sea_mlp_fc1_ln_gelu", "sea_mlp_fc2_proj_norm", "sea_kv_rollout", "sea_kv_arena_words", "sea_kv_debug_stamps",
     "sea_gemm_fewrows", "sea_qkv_rope_fewrows", "sea_row_chain", "sea_row_chain_riders", "sea_gemm_adaln", "sea_mlp_block", "sea_adaln_qkv", "sea_splitk_finish",
+    "sea_encoder_block_ws_floats", "sea_encoder_block_fwd", "sea_encoder_block_bwd",
 )
 
 

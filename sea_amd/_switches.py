@@ -10,6 +10,8 @@
                                            norm=0                Linear + row norm as two launches  xtail=0            a field's exchange tail as three launches
                                            xtail_max_rows=N      ... from N rows up                  fold_ib=0          the info-bottleneck add as a launch of its own
                                            silu=0|1              generated GEMM operand off / on    mlp1 / mlpnorm / mlp2=0|1   the fused MLP halves off / forced
+                                           enc=composed|fused    spatial encoder training: every EncoderBlock composed from the generic launches (default, measured
+                                                                   faster) or as the fused sea_encoder_block_fwd / _bwd (bf16, width 32 or 64; other shapes always compose)
   SEA_KV          key=value,...          KV-cache rollout: fast=0 (generic step plan), hoist=0 (condition work per step), gemv=0 (step plan without the few-row launches of gemv.hip),
                                            loop=python (step loop in Python),
                                            force_err=1 (test hook: the persistent launch "reports" a hand-off that gave up)

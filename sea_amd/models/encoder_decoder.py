@@ -8,11 +8,12 @@ constructor, sub-module and parameter names, run as a fixed sequence of libsea_h
 MLPs (GELU epilogue; the sinusoidal patch positions ride as the residual operand of the second Linear), and per EncoderBlock:
 weight-only LayerNorm, fused q/k/v projection written in the attention layouts, un-masked flash attention (the causal kernel with the whole
 row visible), projection + residual, LayerNorm, Linear, LayerNorm + GELU, Linear + residual.  `SpatialModel` ties encoder and decoder
-together as the reference does.  Training of the spatial model is out of scope.
+together as the reference does; under grad its forward is the training path of sea_amd/spatial_train.py (forward with saved activations and a
+hand-written backward), with grad disabled it is the inference path above, unchanged.
 """
 from __future__ import annotations
 
-from typing import List, Sequence
+from typing import List, Optional, Sequence
 
 import torch
 import torch.nn as nn
@@ -304,16 +305,22 @@ class PointwiseEncode(nn.Module):
 
 class SpatialModel(nn.Module):
     """SpatialModel(field_groups, n_inp, MLP_hidden, num_layers, embed_dim, n_heads, max_len, src_len, dropout=0.1, variational=False): encoder +
-    decoder under the reference's attribute names `encode` / `decode` (models/encoder_decoder.py:148-176), inference only; the variational encoder
-    (`Encode`, sampling) is not provided."""
+    decoder under the reference's attribute names `encode` / `decode` (models/encoder_decoder.py:148-176); the variational encoder
+    (`Encode`, sampling) is not provided.
+
+    In train() mode with grad enabled (and parameters requiring grad) forward() is the training forward of sea_amd/spatial_train.py: `loss.backward()` fills
+    p.grad of every parameter (gradients accumulate until zero_grad()), and initialize_optimizer returns the fused AdamW over the flat parameter
+    buffer the engine keeps.  Under torch.no_grad() or in eval() mode forward() runs the inference launches of PointwiseEncode.forward / Decode.forward."""
 
     def __init__(self, field_groups, n_inp, MLP_hidden, num_layers, embed_dim, n_heads, max_len, src_len, dropout=0.1, variational=False):
         super().__init__()
         if variational:
             raise NotImplementedError("sea_amd.SpatialModel: the variational encoder is outside the accelerated path (both shipped configs use variational=False)")
         self.variational = False
+        self.dropout_p = float(dropout)
         self.encode = PointwiseEncode(field_groups, n_inp, MLP_hidden, num_layers, embed_dim, n_heads, max_len, src_len, dropout)
         self.decode = Decode(field_groups, n_inp, MLP_hidden, embed_dim, dropout)
+        object.__setattr__(self, "_engine", None)
 
     def set_compute_dtype(self, dtype) -> "SpatialModel":
         self.encode.set_compute_dtype(dtype)
@@ -325,7 +332,47 @@ class SpatialModel(nn.Module):
         x[x == pad_idx] = 0.0
         return x
 
+    # ------------------------------------------------------------------ training (sea_amd/spatial_train.py)
+    def _apply(self, fn, *args, **kwargs):
+        # .to()/.cuda()/.cpu() re-create parameter storage: drop the engine (and its flat buffers); it is rebuilt lazily
+        object.__setattr__(self, "_engine", None)
+        return super()._apply(fn, *args, **kwargs)
+
+    def engine(self, device: Optional[torch.device] = None):
+        from ..spatial_train import SpatialEngine
+
+        if self._engine is None:
+            dev = device if device is not None else next(self.parameters()).device
+            if dev.type != "cuda":
+                raise RuntimeError("sea_amd.SpatialModel: parameters are on the CPU; training runs on the MI355X only (model.to('cuda'))")
+            object.__setattr__(self, "_engine", SpatialEngine(self, dev))
+        return self._engine
+
+    def _grad_anchor(self) -> torch.Tensor:
+        """A leaf that requires grad, so that autograd calls the hand-written backward."""
+        a = getattr(self, "_anchor", None)
+        if a is None or a.device != next(self.parameters()).device:
+            a = torch.zeros(1, device=next(self.parameters()).device, requires_grad=True)
+            object.__setattr__(self, "_anchor", a)
+        return a
+
+    def _live_params(self):
+        eng = self._engine
+        cache = getattr(self, "_live_cache", None)
+        if cache is None or cache[0] is not eng:
+            named = dict(self.named_parameters())
+            cache = (eng, [named[n] for n in eng.params.live_names])
+            object.__setattr__(self, "_live_cache", cache)
+        return cache[1]
+
     def forward(self, x):
         x = self.generate_padding_mask(x)
-        return self.decode(self.encode(x))
+        if self.training and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            if self.dropout_p > 0.0:
+                raise NotImplementedError(f"sea_amd.SpatialModel: training with dropout {self.dropout_p} is not implemented (the shipped spatial configs "
+                                          "use dropout 0.0)")
+            N.require_gpu(x, "SpatialModel input")
+            from ..spatial_train import spatial_forward_with_grad
 
+            return spatial_forward_with_grad(self, self.engine(x.device), x)
+        return self.decode(self.encode(x))

@@ -667,3 +667,52 @@ def mlp_fc1_ln_gelu(groups: Sequence[Dict], eps: float = 1e-5, dtype: torch.dtyp
             _mat(d[k], k)
         fill_mlp_group(g, d.get("A"), d["W1"], d["b1"], d["lnw"], d["lnb"], d["Hg"], d.get("norm"))
     N.check(N.lib().sea_mlp_fc1_ln_gelu(arr, len(groups), eps, N.dtype_code(dtype), N.stream_ptr()), "sea_mlp_fc1_ln_gelu")
+
+
+# ------------------------------------------------------------------------------------------------ fused EncoderBlock (encoder_block.hip)
+def encoder_block_supported(dtype: torch.dtype, W: int, H: int, P: int) -> bool:
+    """The shapes sea_encoder_block_fwd / _bwd instantiate: bf16, W in {32, 64}, H = 8, P <= 128 (S = 4 W by construction)."""
+    return dtype == torch.bfloat16 and W in (32, 64) and H == 8 and 1 <= P <= 128
+
+
+def encoder_block_ws_floats(B: int, P: int, W: int) -> int:
+    return int(N.lib().sea_encoder_block_ws_floats(B, P, W))
+
+
+_ENC_BLOCK_FIELDS = ("Zin", "Zout", "wqkv", "bqkv", "wo", "w1", "b1", "lnw", "lnb", "w2", "b2", "g1", "g2", "dZout", "dZin",
+                     "n1", "dqkv", "att", "dz1", "n2", "dh", "hg", "dz2", "u1", "u2", "u3w", "u3b")
+
+
+def _encoder_block(fn_name: str, t: Dict, B: int, P: int, W: int, H: int, ws: torch.Tensor, eps: float, dtype: torch.dtype) -> None:
+    """t: tensors by SeaEncBlock field name (include/sea_hip.h); every given tensor must be contiguous on the GPU."""
+    st = N.SeaEncBlock()
+    for k in _ENC_BLOCK_FIELDS:
+        v = t.get(k)
+        if v is not None:
+            N.require_gpu(v, k)
+            if not v.is_contiguous():
+                raise ValueError(f"{fn_name}: {k} must be contiguous")
+            setattr(st, k, v.data_ptr())
+    N.require_gpu(ws, "ws")
+    st.ws, st.ws_floats = ws.data_ptr(), ws.numel()
+    st.B, st.P, st.W, st.H, st.eps = B, P, W, H, eps
+    from . import ptrcheck
+
+    if ptrcheck.always():
+        from types import SimpleNamespace
+
+        ranges = ptrcheck.Ranges()
+        for k, v in list(t.items()) + [("ws", ws)]:
+            ranges.add_tensor(v, k)
+        ptrcheck.check_records([SimpleNamespace(fn=fn_name, args=(), keep=st, name=fn_name)], ranges, 2 if dtype == torch.bfloat16 else 4, fn_name)
+    N.check(getattr(N.lib(), fn_name)(C.byref(st), N.dtype_code(dtype), N.stream_ptr()), fn_name)
+
+
+def encoder_block_fwd(t: Dict, B: int, P: int, W: int, H: int, ws: torch.Tensor, eps: float = 1e-5, dtype: torch.dtype = torch.bfloat16) -> None:
+    """Zout = EncoderBlock(Zin), one launch.  t: Zin, Zout and the block's weights (wqkv act [3W, W], bqkv, wo, w1, b1, lnw, lnb, w2, b2, g1, g2)."""
+    _encoder_block("sea_encoder_block_fwd", t, B, P, W, H, ws, eps, dtype)
+
+
+def encoder_block_bwd(t: Dict, B: int, P: int, W: int, H: int, ws: torch.Tensor, eps: float = 1e-5, dtype: torch.dtype = torch.bfloat16) -> None:
+    """dZin from dZout (the block's forward recomputed from Zin) plus the wgrad operands n1, dqkv, att, dz1, n2, dh, hg, dz2, u1, u2, u3w, u3b."""
+    _encoder_block("sea_encoder_block_bwd", t, B, P, W, H, ws, eps, dtype)

@@ -115,6 +115,20 @@ def _extents(st, esz: int) -> Iterable[Tuple[str, int, int]]:
             yield "Yact", st.Yact, ((st.M - 1) * st.ldyact + (st.d if st.X else 2 * st.d)) * esz
         if st.Y32:
             yield "Y32", st.Y32, ((st.M - 1) * st.ldy32 + st.d) * f32
+    elif isinstance(st, N.SeaEncBlock):
+        M, W = st.B * st.P, st.W
+        S = 4 * W
+        for name, n in (("Zin", M * W), ("bqkv", 3 * W), ("b1", S), ("lnw", S), ("lnb", S), ("b2", W), ("g1", W), ("g2", W), ("ws", st.ws_floats)):
+            yield name, getattr(st, name), n * f32
+        for name, n in (("wqkv", 3 * W * W), ("wo", W * W), ("w1", S * W), ("w2", W * S)):
+            yield name, getattr(st, name), n * esz
+        for name in ("Zout", "dZout", "dZin"):
+            if getattr(st, name):
+                yield name, getattr(st, name), M * W * f32
+        for name, n in (("n1", W), ("dqkv", 3 * W), ("att", W), ("dz1", W), ("n2", W), ("dh", S), ("hg", S), ("dz2", W), ("u1", W), ("u2", W),
+                        ("u3w", S), ("u3b", S)):
+            if getattr(st, name):
+                yield name, getattr(st, name), M * n * esz
     elif isinstance(st, N.SeaSplitkGroup):
         yield "P", st.P, ((st.S - 1) * st.p_stride + (st.M - 1) * st.ldp + st.N) * f32
         if st.bias:

@@ -1,6 +1,6 @@
 """Host-side mirror of the hot-path half of the reference's utils/train_utils.py.
 
-Mirrored (same names and argument meaning): initialize_optimizer (:33-39), relativeMSE (:112-116),
+Mirrored (same names and argument meaning): initialize_optimizer (:33-39), calculate_R2 (:42-48), relativeMSE (:112-116),
 relativeMSE_with_time (:124-150), autoregressive_validation (:154-184), full_autoregressive_evaluation (:186-212, the
 encoded half; decoding through the spatial autoencoder, CSV and plots are out of scope — SURVEY.md §2), the
 error-tracker duck type (:50-110).  `rollout` is the loop both evaluation functions share (:202-209), with the
@@ -37,6 +37,14 @@ def relativeMSE(predictions: torch.Tensor, truth: torch.Tensor, dim: int = -1) -
 def relativeMSE_with_time(predictions: torch.Tensor, truth: torch.Tensor, dim=2) -> torch.Tensor:
     """Same ratio, summed over `dim` (reference :124-150)."""
     return relativeMSE(predictions, truth, dim=dim)
+
+
+def calculate_R2(prediction: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+    """1 - sum((p - y)^2) / sum((y - mean(y))^2) over all elements (reference :42-48); a 0-d tensor on the inputs' device."""
+    prediction, labels = prediction.reshape(-1), labels.reshape(-1)
+    residual = torch.sum((prediction - labels) ** 2)
+    total = torch.sum((labels - torch.mean(labels)) ** 2)
+    return 1 - residual / total
 
 
 class SeaMSELoss(torch.nn.Module):
