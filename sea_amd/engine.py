@@ -33,6 +33,11 @@ _QKV = re.compile(r"^(.*\.)(k|q|v)\.(weight|bias)$")
 _QKV_RANK = {("q", "weight"): 0, ("k", "weight"): 1, ("v", "weight"): 2, ("q", "bias"): 3, ("k", "bias"): 4, ("v", "bias"): 5}
 
 
+# Plan-only keys of a group dict (Plan._bind): the byte offset of a struct field into the caller's x / out / dout tensor, patched at bind time
+_BIND_KEYS = {"X_is_x": ("_x_patches", "X"), "R_is_x": ("_x_patches", "R"), "Xin_is_x": ("_x_patches", "Xin"), "Y_is_out": ("_out_patches", "Y32"),
+              "dY_is_dout": ("_dout_patches", "dY")}
+
+
 def _round_up(x: int, m: int) -> int:
     return (x + m - 1) // m * m
 
@@ -318,6 +323,35 @@ class Plan:
         self._cur.append(_Rec(None, [], "join", None, lane))
 
     # ------------------------------------------------------------------ record builders
+    def _bind(self, g, d: dict) -> dict:
+        """d without its plan-only keys (_BIND_KEYS), each registered as a bind-time patch of struct g; a generated operand (`silu`), an
+        info-bottleneck addend (`ib`) and dropout (`drop`) register g for the condition pointer and the per-step seed."""
+        d = dict(d)
+        for key, (patches, field) in _BIND_KEYS.items():
+            off = d.pop(key, None)
+            if off is not None:
+                getattr(self, patches).append((g, field, off))
+        if d.get("silu") is not None:
+            self._c_patches.append((g, "silu_c"))
+        if d.get("ib") is not None:
+            self._c_patches.append((g, "ib_c"))
+        if d.get("drop") is not None:
+            self._drop_structs.append(g)
+        return d
+
+    def _array(self, struct, groups: List[dict], fill):
+        """One launch's struct array: fill(g, **d) per group dict (see _bind)."""
+        arr = (struct * len(groups))()
+        for g, d in zip(arr, groups):
+            fill(g, **self._bind(g, d))
+        return arr
+
+    def _grouped(self, fn, struct, groups: List[dict], limit: int, fill, name: str, *tail) -> None:
+        """Launches fn(arr, n, *tail) over the groups, at most `limit` per launch."""
+        for s in range(0, len(groups), limit):
+            arr = self._array(struct, groups[s:s + limit], fill)
+            self._cur.append(self._rec(fn, [arr, len(arr), *tail], name, arr))
+
     def _gemm_splitk(self, chunk: List[dict], name: str) -> bool:
         """Split-K form of a launch of skinny-M Linear layers with a very long contraction (the MLP of configs/multiphase_flow.py:112-141 at M = B T = 796: fc2 forward and
         fc1's data gradient, 2048 x 16384): at 128 x 128 tiles such a launch is 224 workgroups each walking K = 16384 alone; four K-quarters as groups of ONE
@@ -338,68 +372,30 @@ class Plan:
             tiles += ((Mg + 127) // 128) * ((Ng + 127) // 128)
         if tiles >= 384:
             return False
-        parts, fin = [], (N.SeaSplitkGroup * len(chunk))()
-        for f_, d in zip(fin, chunk):
+        parts, fin = [], []
+        for d in chunk:
             A, W = d["A"], d["W"]
-            Mg, Ng, ks = A.shape[0], W.shape[0], W.shape[1] // S
-            P = self._buf(S, Mg, Ng, dtype=torch.float32)
+            ks = W.shape[1] // S
+            P = self._buf(S, A.shape[0], W.shape[0], dtype=torch.float32)
             for q in range(S):
                 parts.append(dict(A=A[:, q * ks:(q + 1) * ks], W=W[:, q * ks:(q + 1) * ks], C32=P[q]))
-            R, C32, Cact, bias = d.get("R"), d.get("C32"), d.get("Cact"), d.get("bias")
-            f_.P, f_.p_stride, f_.S, f_.M, f_.N, f_.ldp = P.data_ptr(), P.stride(0), S, Mg, Ng, P.stride(1)
-            f_.bias, f_.bias_scale = N.ptr(bias), d.get("bias_scale", 1.0)
-            f_.R, f_.ldr = N.ptr(R), (R.stride(0) if R is not None else 0)
-            f_.C32, f_.ldc32 = N.ptr(C32), (C32.stride(0) if C32 is not None else 0)
-            f_.Cact, f_.ldcact = N.ptr(Cact), (Cact.stride(0) if Cact is not None else 0)
-        arr = (N.SeaGemmGroup * len(parts))()
-        for g, d in zip(arr, parts):
-            _fill_gemm(g, **d)
+            fin.append(dict(P=P, bias=d.get("bias"), bias_scale=d.get("bias_scale", 1.0), R=d.get("R"), C32=d.get("C32"), Cact=d.get("Cact")))
         L = N.lib()
-        self._cur.append(self._rec(L.sea_gemm_grouped, [arr, len(parts), self.code], name + ".splitk", arr))
-        self._cur.append(self._rec(L.sea_splitk_finish, [fin, len(chunk), self.code], name, fin))
+        self._grouped(L.sea_gemm_grouped, N.SeaGemmGroup, parts, N.MAX_GROUPS, ops.fill_gemm_group, name + ".splitk", self.code)
+        self._grouped(L.sea_splitk_finish, N.SeaSplitkGroup, fin, N.MAX_SPLITK_GROUPS, ops.fill_splitk_group, name, self.code)
         return True
 
     def _gemm(self, groups: List[dict], name: str) -> None:
-        L = N.lib()
+        """Group dicts: the arguments of ops.fill_gemm_group, plus `R_is_x`; a dropout's seed (drop[0]) is re-keyed every step (set_dropout_seed)."""
         for s in range(0, len(groups), N.MAX_GROUPS):
             chunk = groups[s:s + N.MAX_GROUPS]
-            if self._gemm_splitk(chunk, name):
-                continue
-            arr = (N.SeaGemmGroup * len(chunk))()
-            for g, d in zip(arr, chunk):
-                _fill_gemm(g, **d)
-            self._cur.append(self._rec(L.sea_gemm_grouped, [arr, len(chunk), self.code], name, arr))
-            for g, d in zip(arr, chunk):
-                if d.get("silu") is not None:
-                    self._c_patches.append((g, "silu_c"))
-                if d.get("R_is_x") is not None:
-                    self._x_patches.append((g, "R", d["R_is_x"]))
-                if d.get("drop") is not None:
-                    self._drop_structs.append(g)
+            if not self._gemm_splitk(chunk, name):
+                self._grouped(N.lib().sea_gemm_grouped, N.SeaGemmGroup, chunk, N.MAX_GROUPS, ops.fill_gemm_group, name, self.code)
 
     def _norm(self, groups: List[dict], d: int, name: str, x_is_act=False, gelu=False) -> None:
-        L = N.lib()
-        for s in range(0, len(groups), N.MAX_NORM_GROUPS):
-            chunk = groups[s:s + N.MAX_NORM_GROUPS]
-            arr = (N.SeaNormGroup * len(chunk))()
-            for g, gd in zip(arr, chunk):
-                X = gd["X"]
-                g.X, g.ldx = X.data_ptr(), gd.get("ldx", X.stride(0) if X.dim() == 2 else 0)
-                mod = gd.get("mod")
-                g.mod, g.ldmod = N.ptr(mod), (mod.stride(0) if mod is not None else 0)
-                g.gamma, g.beta = gd["gamma"].data_ptr(), N.ptr(gd.get("beta"))
-                y32, yact = gd.get("Y32"), gd.get("Yact")
-                g.Y32, g.ldy32 = N.ptr(y32), gd.get("ldy32", y32.stride(0) if y32 is not None else 0)
-                g.Yact, g.ldyact = N.ptr(yact), (yact.stride(0) if yact is not None else 0)
-                g.mean, g.rstd = N.ptr(gd.get("mean")), N.ptr(gd.get("rstd"))
-                add, xout = gd.get("addend"), gd.get("Xout")
-                g.addend, g.ldadd = N.ptr(add), (add.stride(0) if add is not None else 0)
-                g.Xout, g.ldxout = N.ptr(xout), (xout.stride(0) if xout is not None else 0)
-                if gd.get("X_is_x") is not None:
-                    self._x_patches.append((g, "X", gd["X_is_x"]))
-                if gd.get("Y_is_out") is not None:
-                    self._out_patches.append((g, "Y32", gd["Y_is_out"]))
-            self._cur.append(self._rec(L.sea_rownorm, [arr, len(chunk), self.M, d, int(x_is_act), int(gelu), 1e-5, self.code], name, arr))
+        """Group dicts: those of ops.fill_norm_group, plus `X_is_x` and `Y_is_out`."""
+        self._grouped(N.lib().sea_rownorm, N.SeaNormGroup, groups, N.MAX_NORM_GROUPS, lambda g, **gd: ops.fill_norm_group(g, gd), name,
+                      self.M, d, int(x_is_act), int(gelu), 1e-5, self.code)
 
     def _norm_specs(self, specs, n: int):
         """SeaNormGroup array of the `pre` specs of a few-row launch (None entries: no norm for that group), with the bind-time patches of _norm."""
@@ -407,68 +403,37 @@ class Plan:
             return None
         arr = (N.SeaNormGroup * n)()
         for g, sp in zip(arr, specs):
-            if sp is None:
-                continue
-            ops.fill_norm_group(g, sp)
-            if sp.get("X_is_x") is not None:
-                self._x_patches.append((g, "X", sp["X_is_x"]))
+            if sp is not None:
+                ops.fill_norm_group(g, self._bind(g, sp))
         return arr
 
     def _gemm_few(self, groups: List[dict], name: str, pre=None, pre_act: bool = False, pre_gelu: bool = False) -> None:
         """sea_gemm_fewrows (step plans at the shipped widths): group dicts as _gemm; pre[i]: the _norm group dict (or None) of the row norm in front of the layer.
         Groups with pre[i] carry no A."""
-        L = N.lib()
         n = len(groups)
         assert n <= N.FEW_MAX_GROUPS
-        arr = (N.SeaGemmGroup * n)()
-        for g, d in zip(arr, groups):
-            d = dict(d)
-            if d.get("A") is None:
-                d["A"] = d["W"]   # shapes only; the operand comes from pre[i]
-                _fill_gemm(g, **d)
-                g.A, g.lda, g.M = None, 0, self.M
-            else:
-                _fill_gemm(g, **d)
-            if d.get("R_is_x") is not None:
-                self._x_patches.append((g, "R", d["R_is_x"]))
+        arr = self._array(N.SeaGemmGroup, groups, lambda g, A=None, **d: ops.fill_gemm_group(g, A, M=self.M, **d))
         pa = self._norm_specs(pre, n)
-        self._cur.append(self._rec(L.sea_gemm_fewrows, [arr, pa, n, int(pre_act), int(pre_gelu), 1e-5, self.code], name, (arr, pa)))
+        self._cur.append(self._rec(N.lib().sea_gemm_fewrows, [arr, pa, n, int(pre_act), int(pre_gelu), 1e-5, self.code], name, (arr, pa)))
+
+    def _qkv_common(self, rope: torch.Tensor, hd: int):
+        """The SeaQkvCommon of a launch of this plan, its position updated per step (set_position)."""
+        common = N.SeaQkvCommon(rope.data_ptr(), self.H, hd, self.T, self.pos0, self.cap, ops.q_scale(hd))
+        self._pos_structs.append(common)
+        return common
 
     def _qkv_few(self, groups: List[dict], rope: torch.Tensor, hd: int, name: str, pre=None) -> None:
         """sea_qkv_rope_fewrows: group dicts as _qkv; pre[i]: the _norm group dict of the row norm in front of the projection (or None)."""
-        L = N.lib()
         n = len(groups)
         assert n <= N.FEW_MAX_GROUPS
-        arr = (N.SeaQkvGroup * n)()
-        for g, d in zip(arr, groups):
-            A, W = d.get("A"), d["W"]
-            g.A, g.lda = (A.data_ptr(), A.stride(0)) if A is not None else (None, 0)
-            g.W, g.bias = W.data_ptr(), d["bias"].data_ptr()
-            g.Qout, g.Kout, g.Vtout, g.Vout = N.ptr(d.get("Q")), N.ptr(d.get("K")), N.ptr(d.get("Vt")), N.ptr(d.get("V"))
-            g.ldw = W.stride(0)
-            g.M, g.N, g.K, g.col0 = self.M, W.shape[0], W.shape[1], d["col0"]
+        arr = self._array(N.SeaQkvGroup, groups, lambda g, A=None, **d: ops.fill_qkv_group(g, A, M=self.M, **d))
         pa = self._norm_specs(pre, n)
-        common = N.SeaQkvCommon(rope.data_ptr(), self.H, hd, self.T, self.pos0, self.cap, ops.q_scale(hd))
-        self._pos_structs.append(common)
-        self._cur.append(self._rec(L.sea_qkv_rope_fewrows, [arr, pa, n, C.byref(common), 1e-5, self.code], name, (arr, pa, common)))
+        common = self._qkv_common(rope, hd)
+        self._cur.append(self._rec(N.lib().sea_qkv_rope_fewrows, [arr, pa, n, C.byref(common), 1e-5, self.code], name, (arr, pa, common)))
 
     def _gemm_norm(self, groups: List[dict], name: str) -> None:
-        """Linear + row normalisation in one launch (sea_gemm_rownorm): group dicts as _gemm (A, W, bias) plus the _norm keys
-        (mod, gamma, beta, Yact, Y32/ldy32/Y_is_out)."""
-        L = N.lib()
-        for s in range(0, len(groups), N.MAX_GEMM_NORM_GROUPS):
-            chunk = groups[s:s + N.MAX_GEMM_NORM_GROUPS]
-            arr = (N.SeaGemmNormGroup * len(chunk))()
-            for g, d in zip(arr, chunk):
-                ops.fill_gemm_norm_group(g, d["A"], d["W"], d["gamma"], bias=d.get("bias"), R=d.get("R"), C32=d.get("C32"), mod=d.get("mod"),
-                                         beta=d.get("beta"), Y32=d.get("Y32"), Yact=d.get("Yact"), mean=d.get("mean"), rstd=d.get("rstd"),
-                                         ldy32=d.get("ldy32"), n_seg=d.get("n_seg", 1),
-                                         a_seg_stride=d.get("a_seg_stride", 0), bias_scale=d.get("bias_scale", 1.0), Cact=d.get("Cact"), ib=d.get("ib"))
-                if d.get("Y_is_out") is not None:
-                    self._out_patches.append((g, "Y32", d["Y_is_out"]))
-                if d.get("ib") is not None:
-                    self._c_patches.append((g, "ib_c"))
-            self._cur.append(self._rec(L.sea_gemm_rownorm, [arr, len(chunk), 1e-5, self.code], name, arr))
+        """Linear + row normalisation in one launch (sea_gemm_rownorm): group dicts as ops.fill_gemm_norm_group, plus `Y_is_out`."""
+        self._grouped(N.lib().sea_gemm_rownorm, N.SeaGemmNormGroup, groups, N.MAX_GEMM_NORM_GROUPS, ops.fill_gemm_norm_group, name, 1e-5, self.code)
 
     def _xtail(self, att, Wp, Wup, bup, bias_scale, X, down, name: str) -> None:
         """One field's exchange tail in one launch (sea_exchange_tail): projections + GELU, up-projection of their sum + residual, and — `down` —
@@ -480,33 +445,15 @@ class Plan:
     def _adaln(self, groups: List[dict], name: str) -> None:
         """AdaLN as the epilogue of cond_mlp.2's GEMM, and plain cond_mlp.2 groups, in one launch (sea_gemm_adaln): dicts as ops.fill_adaln_group, plus `X_is_x`
         (byte offset into the caller's tensor: the rows of the first layer are read from it, strided) and `Y_is_out`."""
-        for s in range(0, len(groups), N.MAX_ADALN_GROUPS):
-            chunk = groups[s:s + N.MAX_ADALN_GROUPS]
-            arr = (N.SeaAdalnGroup * len(chunk))()
-            for g, d in zip(arr, chunk):
-                d = dict(d)
-                x_off, o_off = d.pop("X_is_x", None), d.pop("Y_is_out", None)
-                ops.fill_adaln_group(g, **d)
-                if x_off is not None:
-                    self._x_patches.append((g, "X", x_off))
-                if o_off is not None:
-                    self._out_patches.append((g, "Y32", o_off))
-            self._cur.append(self._rec(N.lib().sea_gemm_adaln, [arr, len(chunk), 1e-5, self.code], name, arr))
+        self._grouped(N.lib().sea_gemm_adaln, N.SeaAdalnGroup, groups, N.MAX_ADALN_GROUPS, ops.fill_adaln_group, name, 1e-5, self.code)
 
     def _chain(self, groups: List[dict], rope: torch.Tensor, hd: int, name: str) -> None:
         """A row-local chain between two attention launches (sea_row_chain): group dicts as ops.fill_row_chain, plus `Xin_is_x` (byte offset into the caller's
         tensor: the residual rows of the first layer are read from it, strided)."""
         for s in range(0, len(groups), N.CHAIN_MAX_GROUPS):
             chunk = groups[s:s + N.CHAIN_MAX_GROUPS]
-            arr = (N.SeaRowChain * len(chunk))()
-            for g, d in zip(arr, chunk):
-                d = dict(d)
-                x_off = d.pop("Xin_is_x", None)
-                ops.fill_row_chain(g, **d)
-                if x_off is not None:
-                    self._x_patches.append((g, "Xin", x_off))
-            common = N.SeaQkvCommon(rope.data_ptr(), self.H, hd, self.T, self.pos0, self.cap, ops.q_scale(hd))
-            self._pos_structs.append(common)
+            arr = self._array(N.SeaRowChain, chunk, ops.fill_row_chain)
+            common = self._qkv_common(rope, hd)
             rd = self._take_riders(len(chunk), max(g.M for g in arr)) if s == 0 else None
             if rd is None:
                 self._cur.append(self._rec(N.lib().sea_row_chain, [arr, len(chunk), C.byref(common), 1e-5, self.code], name, (arr, common)))
@@ -549,34 +496,21 @@ class Plan:
         return arr, len(arr), done, take, ibp
 
     def _qkv(self, groups: List[dict], rope: torch.Tensor, hd: int, name: str) -> None:
-        L = N.lib()
-        arr = (N.SeaQkvGroup * len(groups))()
-        for g, d in zip(arr, groups):
-            A, W = d["A"], d["W"]
-            g.A, g.W, g.bias = A.data_ptr(), W.data_ptr(), d["bias"].data_ptr()
-            g.Qout, g.Kout, g.Vtout, g.Vout = N.ptr(d.get("Q")), N.ptr(d.get("K")), N.ptr(d.get("Vt")), N.ptr(d.get("V"))
-            g.lda, g.ldw = A.stride(0), W.stride(0)
-            g.M, g.N, g.K, g.col0 = self.M, W.shape[0], W.shape[1], d["col0"]
-        common = N.SeaQkvCommon(rope.data_ptr(), self.H, hd, self.T, self.pos0, self.cap, ops.q_scale(hd))
-        self._pos_structs.append(common)
-        self._cur.append(self._rec(L.sea_qkv_rope_grouped, [arr, len(groups), C.byref(common), self.code], name, (arr, common)))
+        """Group dicts: the arguments of ops.fill_qkv_group."""
+        arr = self._array(N.SeaQkvGroup, groups, lambda g, **d: ops.fill_qkv_group(g, M=self.M, **d))
+        common = self._qkv_common(rope, hd)
+        self._cur.append(self._rec(N.lib().sea_qkv_rope_grouped, [arr, len(groups), C.byref(common), self.code], name, (arr, common)))
 
     def _attn(self, problems: List[dict], hd: int, ldo: int, name: str, drop=None, src_len: Optional[int] = None) -> None:
-        L = N.lib()
+        """drop: (thr, first stream); the seed is re-keyed every step (set_dropout_seed)."""
         for s in range(0, len(problems), N.MAX_ATTN_PROBLEMS):
-            chunk = problems[s:s + N.MAX_ATTN_PROBLEMS]
             P = N.SeaAttnParams()
-            P.n_problems = len(chunk)
-            if drop is not None:  # (thr, first stream of this launch)
-                P.drop.thr, P.drop.stream = drop[0], drop[1] + s
+            ops.fill_attn_params(P, problems[s:s + N.MAX_ATTN_PROBLEMS], self.B, self.H, hd, self.T, self.pos0 + self.T, self.cap, self.pos0,
+                                 (self.eng.model.src_len if src_len is None else src_len), ldo, drop=((0, drop[1] + s, drop[0]) if drop is not None else None))
+            if drop is not None:
                 self._drop_structs.append(P)
-            for i, d in enumerate(chunk):
-                P.p[i].Q, P.p[i].K, P.p[i].Vt, P.p[i].O = d["Q"].data_ptr(), d["K"].data_ptr(), d["Vt"].data_ptr(), d["O"].data_ptr()
-                P.p[i].LSE = N.ptr(d.get("LSE"))
-            P.B, P.H, P.hd, P.Tq, P.Tk, P.cap = self.B, self.H, hd, self.T, self.pos0 + self.T, self.cap
-            P.q_pos0, P.src_len, P.ldo = self.pos0, (self.eng.model.src_len if src_len is None else src_len), ldo
             self._pos_structs.append(P)
-            self._cur.append(self._rec(L.sea_attention_fwd, [C.byref(P), self.code], name, P))
+            self._cur.append(self._rec(N.lib().sea_attention_fwd, [C.byref(P), self.code], name, P))
 
     def _cond_mods(self, split: bool = False, riders: bool = False) -> Dict[str, torch.Tensor]:
         """AdaLN condition MLPs for the WHOLE model: silu launch + grouped GEMM (cond_mlp.2); returns prefix -> [M, 2d] (w | b).
@@ -607,6 +541,18 @@ class Plan:
         gen_a = self._gen_a(first + rest)
         ib_todo = list(getattr(self, "_ib_fold", []))   # (layer prefix, ibuf): info-bottleneck MLPs evaluated by extra row passes of the first silu launch
         self._rider_arr, self._rider_ib = None, None
+
+        def silu_launch(chunk, tag):   # sea_silu_outer_ib: the hidden rows of `chunk` (dicts as ops.fill_silu_group) and the info-bottleneck rows still to do
+            arr = self._array(N.SeaSiluGroup, chunk, ops.fill_silu_group) if chunk else None
+            ibs, n_ib = None, len(ib_todo)
+            if ib_todo:
+                ibs = (N.SeaIbParams * n_ib)()
+                for ibp, (lpre, ibuf) in zip(ibs, ib_todo):
+                    ops.fill_ib_params(ibp, [ibuf], None, **self._ib_layer(lpre))
+                ib_todo.clear()
+            rec = self._rec(L.sea_silu_outer_ib, [arr, len(chunk), None, M, self.code, ibs, n_ib], tag, (arr, ibs) if chunk else (ibs,))
+            self._c_patches.append((rec.args, 2))
+            self._cur.append(rec)
         if riders:
             # the silu launch as it is (hidden rows of every module + the information-bottleneck rows); cond_mlp.2 of AdaLN_0 and ln_cross of the (only) layer in
             # front; cond_mlp.2 of every other module as rider tiles of the chain launches
@@ -626,37 +572,22 @@ class Plan:
                 if self._front_chain and ((pre_, d) in first or (self._front3 and "ln_cross." in pre_)):
                     continue   # generated inside sea_adaln_qkv
                 hids[pre_] = self._buf(M, 2 * d)
-                silu_groups.append((P.f32_vec(pre_ + "cond_mlp.0.weight", 2 * d), P.f32_vec(pre_ + "cond_mlp.0.bias"), hids[pre_]))
+                silu_groups.append(dict(w1=P.f32_vec(pre_ + "cond_mlp.0.weight", 2 * d), b1=P.f32_vec(pre_ + "cond_mlp.0.bias"), Hid=hids[pre_]))
             self._front_rows = None
             if self._front3:   # the silu / ib rows as row riders of sea_adaln_qkv (emitted by _build)
                 sarr = (N.SeaSiluGroup * max(len(silu_groups), 1))()
-                for g, (w1, b1, hid) in zip(sarr, silu_groups):
-                    g.w1, g.b1, g.Hid, g.K2, g.ld = w1.data_ptr(), b1.data_ptr(), hid.data_ptr(), hid.shape[1], hid.stride(0)
+                for g, gd in zip(sarr, silu_groups):
+                    ops.fill_silu_group(g, **gd)
                 ibp = None
                 if ib_todo:
                     ibp = N.SeaIbParams()
                     lpre, ibuf = ib_todo[0]
-                    ibp.X[0], ibp.n_fields, ibp.ldx = ibuf.data_ptr(), 1, ibuf.stride(0)
-                    self._fill_ib(ibp, lpre)
+                    ops.fill_ib_params(ibp, [ibuf], None, **self._ib_layer(lpre))
                     ib_todo.clear()
                 self._front_rows = (sarr, len(silu_groups), ibp)
                 silu_groups = []
             for s_ in range(0, len(silu_groups), N.MAX_SILU_GROUPS):
-                chunk = silu_groups[s_:s_ + N.MAX_SILU_GROUPS]
-                sarr = (N.SeaSiluGroup * len(chunk))()
-                for g, (w1, b1, hid) in zip(sarr, chunk):
-                    g.w1, g.b1, g.Hid, g.K2, g.ld = w1.data_ptr(), b1.data_ptr(), hid.data_ptr(), hid.shape[1], hid.stride(0)
-                ibs, n_ib = None, 0
-                if ib_todo:
-                    n_ib = len(ib_todo)
-                    ibs = (N.SeaIbParams * n_ib)()
-                    for ibp, (lpre, ibuf) in zip(ibs, ib_todo):
-                        ibp.X[0], ibp.n_fields, ibp.ldx = ibuf.data_ptr(), 1, ibuf.stride(0)
-                        self._fill_ib(ibp, lpre)
-                    ib_todo.clear()
-                rec = self._rec(L.sea_silu_outer_ib, [sarr, len(chunk), None, M, self.code, ibs, n_ib], "adaln.silu", (sarr, ibs))
-                self._c_patches.append((rec.args, 2))
-                self._cur.append(rec)
+                silu_launch(silu_groups[s_:s_ + N.MAX_SILU_GROUPS], "adaln.silu")
             # cond_mlp.2 of the front modules: AdaLN_0's as the GEMM whose epilogue IS the normalisation (sea_gemm_adaln: no modulation matrix, no norm launch),
             # ln_cross's as plain groups of the same launch — emitted by _build where the AdaLN_0 launch used to be.  SEA_PLAN=adaln_gemm=0 keeps GEMM + norm launch.
             if _switches.plan("adaln_gemm", "1") != "0":
@@ -664,56 +595,32 @@ class Plan:
             else:
                 self._adaln_front = None
                 self._gemm([dict(A=hids[pre_], W=P.act(pre_ + "cond_mlp.2.weight"), bias=P.f32_vec(pre_ + "cond_mlp.2.bias"), Cact=mods[pre_]) for pre_, _ in front], "adaln.cond_gemm.front")
-            arr = (N.SeaGemmGroup * len(later))()
-            for g, (pre_, d) in zip(arr, later):
-                _fill_gemm(g, A=hids[pre_], W=P.act(pre_ + "cond_mlp.2.weight"), bias=P.f32_vec(pre_ + "cond_mlp.2.bias"), Cact=mods[pre_])
-            self._rider_arr = arr
+            self._rider_arr = self._array(N.SeaGemmGroup, [dict(A=hids[pre_], W=P.act(pre_ + "cond_mlp.2.weight"), bias=P.f32_vec(pre_ + "cond_mlp.2.bias"),
+                                                                Cact=mods[pre_]) for pre_, _ in later], ops.fill_gemm_group)
             self._rider_tiles = sum(((M + 127) // 128) * ((2 * d + 127) // 128) for _, d in later)
-            self._keep.append((arr, self._rider_ib))
+            self._keep.append((self._rider_arr, self._rider_ib))
             return mods
 
         def emit(inst, tag):
             silu_groups, gemm_groups = [], []
             if gen_a:
                 if ib_todo:   # no silu rows to ride on: the information-bottleneck rows as a launch of their own (added by the norm pass in front of the MLP)
-                    n_ib = len(ib_todo)
-                    ibs = (N.SeaIbParams * n_ib)()
-                    for ibp, (lpre, ibuf) in zip(ibs, ib_todo):
-                        ibp.X[0], ibp.n_fields, ibp.ldx = ibuf.data_ptr(), 1, ibuf.stride(0)
-                        self._fill_ib(ibp, lpre)
-                    ib_todo.clear()
-                    rec = self._rec(L.sea_silu_outer_ib, [None, 0, None, M, self.code, ibs, n_ib], "ib.rows", (ibs,))
-                    self._c_patches.append((rec.args, 2))
-                    self._cur.append(rec)
+                    silu_launch([], "ib.rows")
                 for pre, d in inst:
                     mod = self._buf(M, 2 * d)
                     mods[pre] = mod
                     gemm_groups.append(dict(A=None, M=M, W=P.act(pre + "cond_mlp.2.weight"), bias=P.f32_vec(pre + "cond_mlp.2.bias"), Cact=mod,
-                                            silu=(P.f32_vec(pre + "cond_mlp.0.weight", 2 * d), P.f32_vec(pre + "cond_mlp.0.bias"))))
+                                            silu=dict(w1=P.f32_vec(pre + "cond_mlp.0.weight", 2 * d), b1=P.f32_vec(pre + "cond_mlp.0.bias"))))
                 self._gemm(gemm_groups, "adaln.cond_gemm" + tag)
                 return
             for pre, d in inst:
                 hid = self._buf(M, 2 * d)
                 mod = self._buf(M, 2 * d)
                 mods[pre] = mod
-                silu_groups.append((P.f32_vec(pre + "cond_mlp.0.weight", 2 * d), P.f32_vec(pre + "cond_mlp.0.bias"), hid))
+                silu_groups.append(dict(w1=P.f32_vec(pre + "cond_mlp.0.weight", 2 * d), b1=P.f32_vec(pre + "cond_mlp.0.bias"), Hid=hid))
                 gemm_groups.append(dict(A=hid, W=P.act(pre + "cond_mlp.2.weight"), bias=P.f32_vec(pre + "cond_mlp.2.bias"), Cact=mod))
             for s in range(0, len(silu_groups), N.MAX_SILU_GROUPS):
-                chunk = silu_groups[s:s + N.MAX_SILU_GROUPS]
-                arr = (N.SeaSiluGroup * len(chunk))()
-                for g, (w1, b1, hid) in zip(arr, chunk):
-                    g.w1, g.b1, g.Hid, g.K2, g.ld = w1.data_ptr(), b1.data_ptr(), hid.data_ptr(), hid.shape[1], hid.stride(0)
-                ibs, n_ib = None, 0
-                if ib_todo:
-                    n_ib = len(ib_todo)
-                    ibs = (N.SeaIbParams * n_ib)()
-                    for ibp, (lpre, ibuf) in zip(ibs, ib_todo):
-                        ibp.X[0], ibp.n_fields, ibp.ldx = ibuf.data_ptr(), 1, ibuf.stride(0)
-                        self._fill_ib(ibp, lpre)
-                    ib_todo.clear()
-                rec = self._rec(L.sea_silu_outer_ib, [arr, len(chunk), None, M, self.code, ibs, n_ib], "adaln.silu" + tag, (arr, ibs))
-                self._c_patches.append((rec.args, 2))
-                self._cur.append(rec)
+                silu_launch(silu_groups[s:s + N.MAX_SILU_GROUPS], "adaln.silu" + tag)
             self._gemm(gemm_groups, "adaln.cond_gemm" + tag)
 
         # Long launches (B = 8): AdaLN_0 of the first layer, its condition MLP and the self-attention's q / k / v as ONE launch too (sea_adaln_qkv without riders, emitted by
@@ -897,24 +804,20 @@ class Plan:
                     front3 = getattr(self, "_front3", False)
                     arr = (N.SeaAdalnQkv * F)()
                     for g_, i in zip(arr, range(F)):
-                        mp = f"{pre}ln.exp.{i}.0."
+                        mp, lc = f"{pre}ln.exp.{i}.0.", f"{pre}ln_cross.{i}."
+                        third = dict(w1=P.f32_vec(lc + "cond_mlp.0.weight", 2 * D), b1=P.f32_vec(lc + "cond_mlp.0.bias"), W=af[lc][1], bias=af[lc][2],
+                                     out=mods[lc]) if front3 else None   # ln_cross_i's modulation as the launch's third layer
                         ops.fill_adaln_qkv(g_, X=xr[i], cond=None, w1=P.f32_vec(mp + "cond_mlp.0.weight", 2 * E), b1=P.f32_vec(mp + "cond_mlp.0.bias"), W2c=af[mp][1], b2c=af[mp][2],
                                            gamma=P.f32_vec(mp + "weight"), beta=P.f32_vec(mp + "bias"), Wqkv=P.act(f"{pre}attn.self.{i}.q.weight", 3 * E),
-                                           bqkv=P.f32_vec(f"{pre}attn.self.{i}.q.bias", 3 * E), Q=Qs[i], K=Ks[l][i], Vt=Vs[l][i], ldx=(FE if first else None))
+                                           bqkv=P.f32_vec(f"{pre}attn.self.{i}.q.bias", 3 * E), Q=Qs[i], K=Ks[l][i], Vt=Vs[l][i], ldx=(FE if first else None), third=third)
                         g_.M = M
                         self._c_patches.append((g_, "cond"))
                         if first:
                             self._x_patches.append((g_, "X", i * Eo * 4))
-                        if front3:   # ln_cross_i's modulation as the launch's third layer
-                            lc = f"{pre}ln_cross.{i}."
-                            W3 = af[lc][1]
-                            g_.w13, g_.b13 = P.f32_vec(lc + "cond_mlp.0.weight", 2 * D).data_ptr(), P.f32_vec(lc + "cond_mlp.0.bias").data_ptr()
-                            g_.W3, g_.ldw3, g_.b3, g_.N3 = W3.data_ptr(), W3.stride(0), N.ptr(af[lc][2]), 2 * D
-                            g_.mod3, g_.ldmod3 = mods[lc].data_ptr(), mods[lc].stride(0)
                     rg = [] if front3 else [(key, v) for key, v in af.items() if "ln_cross." in key]
                     rarr = (N.SeaGemmGroup * max(len(rg), 1))()
                     for g_, (key, (hid_, W_, b_)) in zip(rarr, rg):
-                        _fill_gemm(g_, A=hid_, W=W_, bias=b_, Cact=mods[key])
+                        ops.fill_gemm_group(g_, hid_, W_, b_, Cact=mods[key])
                     common = N.SeaQkvCommon(rope_s.data_ptr(), self.H, hd_s, self.T, self.pos0, self.cap, ops.q_scale(hd_s))
                     self._pos_structs.append(common)
                     sarr, n_s, ibp = self._front_rows if front3 else (None, 0, None)
@@ -1237,29 +1140,23 @@ class Plan:
                     lnb=P.f32_vec(pre + "ib.layers.1.bias"), w2=P.f32(pre + "ib.layers.3.weight"), b2=P.f32_vec(pre + "ib.layers.3.bias"),
                     h=self.eng.model.ib_hidden)
 
-    def _fill_ib(self, ib, pre: str) -> None:
-        """The layer parameters of SeaIbParams for the block's ib_scale_mode (models/temporal.py:103-109)."""
+    def _ib_layer(self, pre: str) -> dict:
+        """ops.fill_ib_params's layer arguments for the block's ib_scale_mode (models/temporal.py:103-109), on this plan's rows."""
         P, mode = self.eng.params, self.eng.ib_mode
-        ib.mode, ib.M, ib.E = mode, self.M, self.ib_dim
         if mode == 0:
-            q = self._ib_params(pre)
-            ib.w1, ib.b1, ib.lnw, ib.lnb, ib.w2, ib.b2 = (q[k].data_ptr() for k in ("w1", "b1", "lnw", "lnb", "w2", "b2"))
-            ib.h = q["h"]
+            w = {k: v for k, v in self._ib_params(pre).items() if k != "h"}
         elif mode == 1:   # nn.Linear(1, E): weight [E, 1], bias [E]
-            ib.w1, ib.b1, ib.h = P.f32_vec(pre + "ib.weight").data_ptr(), P.f32_vec(pre + "ib.bias").data_ptr(), 1
+            w = dict(w1=P.f32_vec(pre + "ib.weight"), b1=P.f32_vec(pre + "ib.bias"))
         else:             # GaussianFourierProjection: W [1, E/2]
-            ib.w1, ib.h = P.f32(pre + "ib.W").data_ptr(), 1
+            w = dict(w1=P.f32(pre + "ib.W"))
+        return dict(w, mode=mode, M=self.M, E=self.ib_dim)
 
     def _ib(self, pre: str, xr: List[torch.Tensor], drop=None) -> None:
-        P = self.eng.params
+        """drop: (thr, first stream); the seed is re-keyed every step (set_dropout_seed)."""
         ib = N.SeaIbParams()
+        ops.fill_ib_params(ib, xr, None, drop=((0, drop[1], drop[0]) if drop is not None else None), **self._ib_layer(pre))
         if drop is not None:
-            ib.drop.thr, ib.drop.stream = drop
             self._drop_structs.append(ib)
-        for i, x in enumerate(xr):
-            ib.X[i] = x.data_ptr()
-        ib.n_fields, ib.ldx = len(xr), xr[0].stride(0)
-        self._fill_ib(ib, pre)
         self._c_patches.append((ib, "c"))
         self._cur.append(self._rec(N.lib().sea_ib_add, [C.byref(ib)], "ib_add", ib))
 
@@ -1577,31 +1474,6 @@ class Plan:
             for k in range(n):
                 tot[k] += evs[k].elapsed_time(evs[k + 1])
         return [(r.name, t / iters) for r, t in zip(recs, tot)]
-
-
-def _fill_gemm(g, A, W, bias=None, R=None, C32=None, Cact=None, n_seg=1, a_seg_stride=0, act=0, bias_scale=1.0, ldr=None,
-               R_is_x=None, Z=None, ldc32=None, drop=None, silu=None, M=None) -> None:
-    if drop is not None:  # (thr, stream, mode); the seed is patched every step
-        g.drop.thr, g.drop.stream, g.drop.mode = drop
-    if silu is not None:  # generated A operand: (w1 [K] f32, b1 [K] f32); the condition pointer is patched at bind time; rows = M
-        g.A, g.W, g.lda = None, W.data_ptr(), 0
-        g.silu_w1, g.silu_b1 = silu[0].data_ptr(), silu[1].data_ptr()
-        g.Z, g.ldz, g.bias, g.R, g.C32, g.Cact = None, 0, N.ptr(bias), None, N.ptr(C32), N.ptr(Cact)
-        g.a_seg_stride, g.ldw, g.ldr = 0, W.stride(0), 0
-        g.ldc32 = C32.stride(0) if C32 is not None else 0
-        g.ldcact = Cact.stride(0) if Cact is not None else 0
-        g.M, g.N, g.K, g.n_seg, g.act, g.bias_scale = M, W.shape[0], W.shape[1], 1, 0, bias_scale
-        return
-    g.A, g.W = A.data_ptr(), W.data_ptr()
-    g.Z, g.ldz = N.ptr(Z), (Z.stride(0) if Z is not None else 0)
-    g.bias, g.R, g.C32, g.Cact = N.ptr(bias), N.ptr(R), N.ptr(C32), N.ptr(Cact)
-    g.a_seg_stride = a_seg_stride
-    g.lda, g.ldw = A.stride(-2), W.stride(0)
-    g.ldr = (ldr if ldr is not None else R.stride(0)) if R is not None else 0
-    g.ldc32 = (ldc32 if ldc32 is not None else C32.stride(0)) if C32 is not None else 0
-    g.ldcact = Cact.stride(0) if Cact is not None else 0
-    g.M, g.N, g.K = A.shape[-2], W.shape[0], W.shape[1]
-    g.n_seg, g.act, g.bias_scale = n_seg, act, bias_scale
 
 
 def blk_pe(eng: "TemporalEngine", layer: int) -> torch.Tensor:

@@ -1,8 +1,10 @@
 """Tensor-level wrappers over the C ABI (include/sea_hip.h).
 
-Each function fills the ABI structs from torch tensors (device memory owned by PyTorch) and launches on the current
-stream.  They are the un-fused building blocks used by the module mirrors in sea_amd/models/base_blocks.py and by the
-operator tests; sea_amd/engine.py pre-builds the same structs once per plan for the whole-model path.
+Each ABI struct has ONE filler here (fill_*): it writes the struct's fields from torch tensors (device memory owned by PyTorch)
+and plain values, and validates nothing.  The eager wrappers check their operands, call the fillers and launch on the current
+stream: they are the un-fused building blocks used by the module mirrors in sea_amd/models/base_blocks.py, by the spatial
+autoencoder's training step and by the operator tests.  The plans (sea_amd/engine.py, train_engine.py, kv_engine.py) call the
+same fillers once per plan for the whole-model path.
 """
 from __future__ import annotations
 
@@ -22,31 +24,30 @@ def _mat(t: torch.Tensor, name: str) -> torch.Tensor:
 
 
 def fill_gemm_group(g: N.SeaGemmGroup, A, W, bias=None, R=None, C32=None, Cact=None, n_seg=1, a_seg_stride=0, act=0,
-                    bias_scale=1.0, M=None, N_=None, K=None, Z=None, silu=None, drop=None) -> None:
-    if silu is not None:   # generated A operand: dict(c f32 [M], w1 f32 [K], b1 f32 [K]) — A[m, k] = silu(w1[k] c[m] + b1[k])
-        g.silu_c, g.silu_w1, g.silu_b1 = silu["c"].data_ptr(), silu["w1"].data_ptr(), silu["b1"].data_ptr()
-        g.A, g.lda, g.W, g.ldw = None, 0, W.data_ptr(), W.stride(0)
-        g.bias, g.R, g.C32, g.Cact, g.Z = N.ptr(bias), None, N.ptr(C32), N.ptr(Cact), None
-        g.ldc32 = C32.stride(0) if C32 is not None else 0
-        g.ldcact = Cact.stride(0) if Cact is not None else 0
-        g.M, g.N, g.K, g.n_seg, g.act, g.bias_scale = silu["c"].numel(), W.shape[0], W.shape[1], 1, 0, bias_scale
-        return
-    g.A, g.W = A.data_ptr(), W.data_ptr()
+                    bias_scale=1.0, M=None, N_=None, K=None, Z=None, silu=None, drop=None, ldr=None, ldc32=None) -> None:
+    """A: the rows are its last two axes; None with M given (a few-row launch's norm prologue supplies them) or with `silu`.  ldr / ldc32: row strides
+    of R / C32 other than their own (a strided view of the caller's tensor)."""
+    if silu is not None:   # generated A operand: dict(c f32 [M] — None: patched at bind time, M given —, w1 f32 [K], b1 f32 [K]): A[m, k] = silu(w1[k] c[m] + b1[k])
+        c = silu.get("c")
+        g.silu_c, g.silu_w1, g.silu_b1 = N.ptr(c), silu["w1"].data_ptr(), silu["b1"].data_ptr()
+        A, R, Z, n_seg, a_seg_stride, act = None, None, None, 1, 0, 0
+        M = c.numel() if M is None else M
+    g.A, g.lda = (A.data_ptr(), A.stride(-2)) if A is not None else (None, 0)
+    g.W, g.ldw = W.data_ptr(), W.stride(0)
     g.bias = N.ptr(bias)
     g.R, g.C32, g.Cact = N.ptr(R), N.ptr(C32), N.ptr(Cact)
     g.Z, g.ldz = N.ptr(Z), (Z.stride(0) if Z is not None else 0)
     g.a_seg_stride = a_seg_stride
-    g.lda, g.ldw = A.stride(0), W.stride(0)
-    g.ldr = R.stride(0) if R is not None else 0
-    g.ldc32 = C32.stride(0) if C32 is not None else 0
+    g.ldr = (ldr if ldr is not None else R.stride(0)) if R is not None else 0
+    g.ldc32 = (ldc32 if ldc32 is not None else C32.stride(0)) if C32 is not None else 0
     g.ldcact = Cact.stride(0) if Cact is not None else 0
-    g.M = A.shape[0] if M is None else M
+    g.M = A.shape[-2] if M is None else M
     g.N = W.shape[0] if N_ is None else N_
     g.K = W.shape[1] if K is None else K
     g.n_seg = n_seg
     g.act = act
     g.bias_scale = bias_scale
-    if drop is not None:   # (seed, stream, thr, mode): counter-based dropout of the epilogue (include/sea_hip.h, SeaDropout)
+    if drop is not None:   # (seed, stream, thr, mode): counter-based dropout of the epilogue (include/sea_hip.h, SeaDropout); a plan's seed is re-keyed every step
         g.drop.seed, g.drop.stream, g.drop.thr, g.drop.mode = drop
 
 
@@ -84,6 +85,15 @@ def q_scale(hd: int) -> float:
     return float(hd) ** -0.5 * LOG2E
 
 
+def fill_qkv_group(g: N.SeaQkvGroup, A, W, bias=None, Q=None, K=None, Vt=None, V=None, col0=0, M=None) -> None:
+    """A act [M, K] (None in a few-row launch with a norm prologue: M given), W act [N, K], the attention operands Q / K / Vt / V (sea_hip.h, SeaQkvGroup)."""
+    g.A, g.lda = (A.data_ptr(), A.stride(0)) if A is not None else (None, 0)
+    g.W, g.ldw, g.bias = W.data_ptr(), W.stride(0), N.ptr(bias)
+    g.Qout, g.Kout, g.Vtout, g.Vout = N.ptr(Q), N.ptr(K), N.ptr(Vt), N.ptr(V)
+    g.M, g.N, g.K = (A.shape[0] if M is None else M), W.shape[0], W.shape[1]
+    g.col0 = col0
+
+
 def qkv_rope_grouped(groups: Sequence[Dict], rope: torch.Tensor, H: int, hd: int, T: int, pos0: int, cap: int,
                      q_scale: float, dtype: torch.dtype) -> None:
     """groups: dicts with A [M,K], W [N,K], bias f32 [N], col0, Q/K/Vt output tensors (see sea_hip.h)."""
@@ -93,12 +103,7 @@ def qkv_rope_grouped(groups: Sequence[Dict], rope: torch.Tensor, H: int, hd: int
         A, W = _mat(d["A"], "A"), _mat(d["W"], "W")
         if A.dtype != dtype or W.dtype != dtype:
             raise ValueError(f"qkv group {i}: dtype mismatch")
-        g = arr[i]
-        g.A, g.W, g.bias = A.data_ptr(), W.data_ptr(), N.ptr(d.get("bias"))
-        g.Qout, g.Kout, g.Vtout, g.Vout = N.ptr(d.get("Q")), N.ptr(d.get("K")), N.ptr(d.get("Vt")), N.ptr(d.get("V"))
-        g.lda, g.ldw = A.stride(0), W.stride(0)
-        g.M, g.N, g.K = A.shape[0], W.shape[0], W.shape[1]
-        g.col0 = d.get("col0", 0)
+        fill_qkv_group(arr[i], A, W, d.get("bias"), d.get("Q"), d.get("K"), d.get("Vt"), d.get("V"), d.get("col0", 0))
     N.require_gpu(rope, "rope")
     assert rope.dtype == torch.float32 and rope.is_contiguous() and rope.shape[-1] == 2 and rope.shape[-2] == hd // 2
     assert rope.shape[0] >= pos0 + T, "rope table shorter than pos0 + T"
@@ -106,12 +111,21 @@ def qkv_rope_grouped(groups: Sequence[Dict], rope: torch.Tensor, H: int, hd: int
     N.check(N.lib().sea_qkv_rope_grouped(arr, n, C.byref(common), N.dtype_code(dtype), N.stream_ptr()), "sea_qkv_rope_grouped")
 
 
+def fill_attn_params(P: N.SeaAttnParams, problems: Sequence[Dict], B: int, H: int, hd: int, Tq: int, Tk: int, cap: int, q_pos0: int, src_len: int, ldo: int,
+                     drop=None) -> None:
+    """problems: dicts with Q, K, Vt, O, optional LSE (see attention_fwd); drop = (seed, first stream, thr): problem i on stream + i."""
+    P.n_problems = len(problems)
+    for p, d in zip(P.p, problems):
+        p.Q, p.K, p.Vt, p.O, p.LSE = d["Q"].data_ptr(), d["K"].data_ptr(), d["Vt"].data_ptr(), d["O"].data_ptr(), N.ptr(d.get("LSE"))
+    P.B, P.H, P.hd, P.Tq, P.Tk, P.cap, P.q_pos0, P.src_len, P.ldo = B, H, hd, Tq, Tk, cap, q_pos0, src_len, ldo
+    if drop is not None:   # dropout of the attention probabilities
+        P.drop.seed, P.drop.stream, P.drop.thr = drop
+
+
 def attention_fwd(problems: Sequence[Dict], B: int, H: int, hd: int, Tq: int, Tk: int, cap: int, q_pos0: int,
                   src_len: int, dtype: torch.dtype, drop=None) -> None:
     """problems: dicts with Q [B,H,Tq,hd], K [B,H,cap,hd], Vt [B,H,hd,cap], O [B,Tq,H*hd] (row stride = O.stride(1)),
     optional LSE f32 [B,H,Tq]."""
-    P = N.SeaAttnParams()
-    P.n_problems = len(problems)
     ldo = None
     for i, d in enumerate(problems):
         for k in ("Q", "K", "Vt", "O"):
@@ -122,11 +136,8 @@ def attention_fwd(problems: Sequence[Dict], B: int, H: int, hd: int, Tq: int, Tk
         assert O.dim() == 3 and O.stride(2) == 1 and O.stride(0) == Tq * O.stride(1)
         ldo = O.stride(1) if ldo is None else ldo
         assert O.stride(1) == ldo
-        P.p[i].Q, P.p[i].K, P.p[i].Vt, P.p[i].O = d["Q"].data_ptr(), d["K"].data_ptr(), d["Vt"].data_ptr(), O.data_ptr()
-        P.p[i].LSE = N.ptr(d.get("LSE"))
-    P.B, P.H, P.hd, P.Tq, P.Tk, P.cap, P.q_pos0, P.src_len, P.ldo = B, H, hd, Tq, Tk, cap, q_pos0, src_len, ldo
-    if drop is not None:   # (seed, first stream, thr): dropout of the attention probabilities, problem i on stream + i
-        P.drop.seed, P.drop.stream, P.drop.thr = drop
+    P = N.SeaAttnParams()
+    fill_attn_params(P, problems, B, H, hd, Tq, Tk, cap, q_pos0, src_len, ldo, drop)   # drop: (seed, first stream, thr)
     N.check(N.lib().sea_attention_fwd(C.byref(P), N.dtype_code(dtype), N.stream_ptr()), "sea_attention_fwd")
 
 
@@ -184,12 +195,8 @@ def gemm_fewrows(groups: Sequence[Dict], dtype: torch.dtype, pre=None, pre_x_is_
     for i, d in enumerate(groups):
         W = _mat(d["W"], "W")
         A = d.get("A")
-        if A is None:
-            X = pre[i]["X"]
-            fill_gemm_group(arr[i], W, W, d.get("bias"), d.get("R"), d.get("C32"), d.get("Cact"), act=d.get("act", 0), bias_scale=d.get("bias_scale", 1.0), M=X.shape[0], Z=d.get("Z"))
-            arr[i].A, arr[i].lda = None, 0
-        else:
-            fill_gemm_group(arr[i], _mat(A, "A"), W, d.get("bias"), d.get("R"), d.get("C32"), d.get("Cact"), act=d.get("act", 0), bias_scale=d.get("bias_scale", 1.0), Z=d.get("Z"))
+        fill_gemm_group(arr[i], (_mat(A, "A") if A is not None else None), W, d.get("bias"), d.get("R"), d.get("C32"), d.get("Cact"), act=d.get("act", 0),
+                        bias_scale=d.get("bias_scale", 1.0), M=(pre[i]["X"].shape[0] if A is None else None), Z=d.get("Z"))
     N.check(N.lib().sea_gemm_fewrows(arr, _norm_array(pre, n), n, int(pre_x_is_act), int(pre_gelu), eps, N.dtype_code(dtype), N.stream_ptr()), "sea_gemm_fewrows")
 
 
@@ -199,14 +206,9 @@ def qkv_rope_fewrows(groups: Sequence[Dict], rope: torch.Tensor, H: int, hd: int
     n = len(groups)
     arr = (N.SeaQkvGroup * n)()
     for i, d in enumerate(groups):
-        W = _mat(d["W"], "W")
-        g = arr[i]
         A = d.get("A")
-        g.A, g.lda = (N.ptr(A), A.stride(0)) if A is not None else (None, 0)
-        g.W, g.bias, g.ldw = W.data_ptr(), N.ptr(d.get("bias")), W.stride(0)
-        g.Qout, g.Kout, g.Vtout, g.Vout = N.ptr(d.get("Q")), N.ptr(d.get("K")), N.ptr(d.get("Vt")), N.ptr(d.get("V"))
-        g.M, g.N, g.K = (A.shape[0] if A is not None else pre[i]["X"].shape[0]), W.shape[0], W.shape[1]
-        g.col0 = d.get("col0", 0)
+        fill_qkv_group(arr[i], A, _mat(d["W"], "W"), d.get("bias"), d.get("Q"), d.get("K"), d.get("Vt"), d.get("V"), d.get("col0", 0),
+                       M=(None if A is not None else pre[i]["X"].shape[0]))
     common = N.SeaQkvCommon(rope.data_ptr(), H, hd, T, pos0, cap, q_scale)
     N.check(N.lib().sea_qkv_rope_fewrows(arr, _norm_array(pre, n), n, C.byref(common), eps, N.dtype_code(dtype), N.stream_ptr()), "sea_qkv_rope_fewrows")
 
@@ -353,7 +355,7 @@ def adaln_qkv(groups: Sequence[Dict], rope: torch.Tensor, H: int, hd: int, T: in
     if silu:
         sarr = (N.SeaSiluGroup * len(silu))()
         for g, gd in zip(sarr, silu):
-            g.w1, g.b1, g.Hid, g.K2, g.ld = gd["w1"].data_ptr(), gd["b1"].data_ptr(), gd["Hid"].data_ptr(), gd["Hid"].shape[1], gd["Hid"].stride(0)
+            fill_silu_group(g, gd["w1"], gd["b1"], gd["Hid"])
     N.check(N.lib().sea_adaln_qkv(arr, len(groups), C.byref(c), rarr, len(riders), sarr, len(silu), (silu_c.data_ptr() if silu_c is not None else None),
                                   (silu_c.numel() if silu_c is not None else 0), None, eps, N.dtype_code(dtype), N.stream_ptr()), "sea_adaln_qkv")
 
@@ -413,37 +415,50 @@ def row_chain(groups: Sequence[Dict], rope: Optional[torch.Tensor] = None, H: in
     N.check(N.lib().sea_row_chain(P, len(groups), C.byref(common) if common is not None else None, eps, N.dtype_code(dtype), N.stream_ptr()), "sea_row_chain")
 
 
+def fill_silu_group(g: N.SeaSiluGroup, w1, b1, Hid) -> None:
+    """Hid act [M, K2] = silu(w1[k] c[m] + b1[k]); w1, b1 f32 [K2]."""
+    g.w1, g.b1, g.Hid, g.K2, g.ld = w1.data_ptr(), b1.data_ptr(), Hid.data_ptr(), Hid.shape[1], Hid.stride(0)
+
+
 def silu_outer(groups: Sequence[Dict], c: torch.Tensor, M: int, dtype: torch.dtype) -> None:
     """groups: dicts with w1 f32 [K2], b1 f32 [K2], Hid act [M,K2]."""
     n = len(groups)
     arr = (N.SeaSiluGroup * n)()
-    for i, gd in enumerate(groups):
-        g = arr[i]
-        H = _mat(gd["Hid"], "Hid")
-        g.w1, g.b1, g.Hid, g.K2, g.ld = gd["w1"].data_ptr(), gd["b1"].data_ptr(), H.data_ptr(), H.shape[1], H.stride(0)
+    for g, gd in zip(arr, groups):
+        fill_silu_group(g, gd["w1"], gd["b1"], _mat(gd["Hid"], "Hid"))
     N.require_gpu(c, "c")
     assert c.dtype == torch.float32 and c.is_contiguous() and c.numel() == M
     N.check(N.lib().sea_silu_outer(arr, n, c.data_ptr(), M, N.dtype_code(dtype), N.stream_ptr()), "sea_silu_outer")
 
 
+def fill_ib_params(P: N.SeaIbParams, xs: Sequence[torch.Tensor], c, w1, b1=None, lnw=None, lnb=None, w2=None, b2=None, mode: int = 0, M=None, E=None,
+                   drop=None) -> None:
+    """xs: f32 [M, E] matrices of equal row stride (M, E: their shape unless given); c f32 [M] (None: patched at bind time).  The layer by ib mode
+    (models/temporal.py:103-109): 0 the MLP (w1, b1, lnw, lnb f32 [h], w2 f32 [E, h], b2 f32 [E]); 1 nn.Linear(1, E) (w1 = weight [E, 1], b1 = bias);
+    2 GaussianFourierProjection (w1 = W [1, E/2]).  drop = (seed, first stream, thr): dropout of the layer's output, field i on stream + i."""
+    for i, x in enumerate(xs):
+        P.X[i] = x.data_ptr()
+    P.n_fields, P.ldx = len(xs), xs[0].stride(0)
+    P.mode, P.M, P.E = mode, (xs[0].shape[0] if M is None else M), (xs[0].shape[1] if E is None else E)
+    P.c, P.w1, P.b1, P.lnw, P.lnb, P.w2, P.b2 = N.ptr(c), w1.data_ptr(), N.ptr(b1), N.ptr(lnw), N.ptr(lnb), N.ptr(w2), N.ptr(b2)
+    P.h = w1.numel() if mode == 0 else 1
+    if drop is not None:
+        P.drop.seed, P.drop.stream, P.drop.thr = drop
+
+
 def ib_add(xs: Sequence[torch.Tensor], c: torch.Tensor, w1, b1, lnw, lnb, w2, b2, drop=None) -> None:
     """xs: f32 [M,E] matrices (equal row stride) updated in place: x += W2 gelu(LN(w1 c + b1)) + b2; drop = (seed, first stream, thr): dropout of the MLP output,
     field i on stream + i."""
-    P = N.SeaIbParams()
-    if drop is not None:
-        P.drop.seed, P.drop.stream, P.drop.thr = drop
     M, E = xs[0].shape
-    for i, x in enumerate(xs):
+    for x in xs:
         _mat(x, "x")
         assert x.dtype == torch.float32 and x.shape == (M, E) and x.stride(0) == xs[0].stride(0)
-        P.X[i] = x.data_ptr()
-    P.n_fields, P.ldx = len(xs), xs[0].stride(0)
     for t in (c, w1, b1, lnw, lnb, w2, b2):
         N.require_gpu(t, "ib parameter")
         assert t.dtype == torch.float32 and t.is_contiguous()
-    P.c, P.w1, P.b1, P.lnw, P.lnb, P.w2, P.b2 = (t.data_ptr() for t in (c, w1, b1, lnw, lnb, w2, b2))
-    P.M, P.E, P.h = M, E, w1.numel()
-    assert c.numel() == M and w2.shape == (E, P.h)
+    assert c.numel() == M and w2.shape == (E, w1.numel())
+    P = N.SeaIbParams()
+    fill_ib_params(P, xs, c, w1, b1, lnw, lnb, w2, b2, drop=drop)
     N.check(N.lib().sea_ib_add(C.byref(P), N.stream_ptr()), "sea_ib_add")
 
 
@@ -456,6 +471,13 @@ def convert(src: torch.Tensor, dst: torch.Tensor) -> None:
 
 
 # ------------------------------------------------------------------------------------------------ backward wrappers
+def fill_wgrad_group(g: N.SeaWgradGroup, dY, X, dW, db=None, M=None) -> None:
+    """dW f32 [N, K] (+)= dY^T X over M rows (those of dY unless given); db f32 [N] (+)= the column sums of dY."""
+    g.dY, g.X, g.dW, g.db = dY.data_ptr(), X.data_ptr(), dW.data_ptr(), N.ptr(db)
+    g.lddy, g.ldx, g.lddw = dY.stride(0), X.stride(0), dW.stride(0)
+    g.M, g.N, g.K = (dY.shape[0] if M is None else M), dW.shape[0], dW.shape[1]
+
+
 def wgrad_grouped(groups: Sequence[Dict], dtype: torch.dtype) -> None:
     """groups: dicts with dY act [M,N], X act [M,K], dW f32 [N,K] (accumulated), optional db f32 [N] (accumulated)."""
     n = len(groups)
@@ -463,11 +485,26 @@ def wgrad_grouped(groups: Sequence[Dict], dtype: torch.dtype) -> None:
     for g, d in zip(arr, groups):
         dY, X, dW = _mat(d["dY"], "dY"), _mat(d["X"], "X"), _mat(d["dW"], "dW")
         assert dY.dtype == dtype and X.dtype == dtype and dW.dtype == torch.float32
-        g.dY, g.X, g.dW, g.db = dY.data_ptr(), X.data_ptr(), dW.data_ptr(), N.ptr(d.get("db"))
-        g.lddy, g.ldx, g.lddw = dY.stride(0), X.stride(0), dW.stride(0)
-        g.M, g.N, g.K = dY.shape[0], dY.shape[1], X.shape[1]
-        assert X.shape[0] == g.M and dW.shape == (g.N, g.K)
+        assert X.shape[0] == dY.shape[0] and dW.shape == (dY.shape[1], X.shape[1])
+        fill_wgrad_group(g, dY, X, dW, d.get("db"))
     N.check(N.lib().sea_wgrad_grouped(arr, n, N.dtype_code(dtype), N.stream_ptr()), "sea_wgrad_grouped")
+
+
+def fill_norm_bwd_group(g: N.SeaNormBwdGroup, gd: Dict) -> None:
+    """gd: dY, X (row strides lddy / ldx when given: a strided view of the caller's tensor), optional mod / dmod, gamma, optional beta, the forward's
+    mean / rstd, dX32 and / or dXact, optional dgamma / dbeta (include/sea_hip.h, SeaNormBwdGroup)."""
+    dY, X = gd["dY"], gd["X"]
+    g.dY, g.lddy = dY.data_ptr(), gd.get("lddy", dY.stride(0))
+    g.X, g.ldx = X.data_ptr(), gd.get("ldx", X.stride(0))
+    mod, dmod = gd.get("mod"), gd.get("dmod")
+    g.mod, g.ldmod = N.ptr(mod), (mod.stride(0) if mod is not None else 0)
+    g.dmod, g.lddmod = N.ptr(dmod), (dmod.stride(0) if dmod is not None else 0)
+    g.gamma, g.beta = gd["gamma"].data_ptr(), N.ptr(gd.get("beta"))
+    g.mean, g.rstd = gd["mean"].data_ptr(), gd["rstd"].data_ptr()
+    dx32, dxa = gd.get("dX32"), gd.get("dXact")
+    g.dX32, g.lddx32 = N.ptr(dx32), (dx32.stride(0) if dx32 is not None else 0)
+    g.dXact, g.lddxact = N.ptr(dxa), (dxa.stride(0) if dxa is not None else 0)
+    g.dgamma, g.dbeta = N.ptr(gd.get("dgamma")), N.ptr(gd.get("dbeta"))
 
 
 def rownorm_bwd(groups: Sequence[Dict], M: int, d: int, dy_is_act: bool, x_is_act: bool, gelu: bool, accumulate: bool,
@@ -475,47 +512,54 @@ def rownorm_bwd(groups: Sequence[Dict], M: int, d: int, dy_is_act: bool, x_is_ac
     n = len(groups)
     arr = (N.SeaNormBwdGroup * n)()
     for g, gd in zip(arr, groups):
-        dY, X = _mat(gd["dY"], "dY"), _mat(gd["X"], "X")
-        g.dY, g.lddy, g.X, g.ldx = dY.data_ptr(), dY.stride(0), X.data_ptr(), X.stride(0)
-        mod, dmod = gd.get("mod"), gd.get("dmod")
-        g.mod, g.ldmod = N.ptr(mod), (mod.stride(0) if mod is not None else 0)
-        g.dmod, g.lddmod = N.ptr(dmod), (dmod.stride(0) if dmod is not None else 0)
-        g.gamma, g.beta = gd["gamma"].data_ptr(), N.ptr(gd.get("beta"))
-        g.mean, g.rstd = gd["mean"].data_ptr(), gd["rstd"].data_ptr()
-        dx32, dxa = gd.get("dX32"), gd.get("dXact")
-        g.dX32, g.lddx32 = N.ptr(dx32), (dx32.stride(0) if dx32 is not None else 0)
-        g.dXact, g.lddxact = N.ptr(dxa), (dxa.stride(0) if dxa is not None else 0)
-        g.dgamma, g.dbeta = N.ptr(gd.get("dgamma")), N.ptr(gd.get("dbeta"))
+        _mat(gd["dY"], "dY")
+        _mat(gd["X"], "X")
+        fill_norm_bwd_group(g, gd)
     N.check(N.lib().sea_rownorm_bwd(arr, n, M, d, int(dy_is_act), int(x_is_act), int(gelu), int(accumulate), N.dtype_code(dtype),
                                     N.ptr(ws), 0 if ws is None else ws.numel(), N.stream_ptr()), "sea_rownorm_bwd")
+
+
+def fill_silu_bwd_group(g: N.SeaSiluBwdGroup, dHid, w1, b1, dw1, db1) -> None:
+    """dw1 / db1 f32 [K2] (+)= the gradient of silu_outer's w1 / b1 from dHid act [M, K2]."""
+    g.dHid, g.w1, g.b1, g.dw1, g.db1 = dHid.data_ptr(), w1.data_ptr(), b1.data_ptr(), dw1.data_ptr(), db1.data_ptr()
+    g.K2, g.ld = dHid.shape[1], dHid.stride(0)
 
 
 def silu_outer_bwd(groups: Sequence[Dict], c: torch.Tensor, M: int, dtype: torch.dtype, ws: Optional[torch.Tensor] = None) -> None:
     n = len(groups)
     arr = (N.SeaSiluBwdGroup * n)()
     for g, gd in zip(arr, groups):
-        dH = _mat(gd["dHid"], "dHid")
-        g.dHid, g.w1, g.b1, g.dw1, g.db1 = dH.data_ptr(), gd["w1"].data_ptr(), gd["b1"].data_ptr(), gd["dw1"].data_ptr(), gd["db1"].data_ptr()
-        g.K2, g.ld = dH.shape[1], dH.stride(0)
+        fill_silu_bwd_group(g, _mat(gd["dHid"], "dHid"), gd["w1"], gd["b1"], gd["dw1"], gd["db1"])
     N.check(N.lib().sea_silu_outer_bwd(arr, n, c.data_ptr(), M, N.dtype_code(dtype), N.ptr(ws), 0 if ws is None else ws.numel(),
                                        N.stream_ptr()), "sea_silu_outer_bwd")
+
+
+def fill_ib_bwd_params(P: N.SeaIbBwdParams, dxs: Sequence[torch.Tensor], c, w1=None, b1=None, lnw=None, lnb=None, w2=None, dw1=None, db1=None, dlnw=None,
+                       dlnb=None, dw2=None, db2=None, ws=None, dhid=None, mode: int = 0, M=None, E=None, drop=None) -> None:
+    """dxs: f32 [M, E] gradients of the rows fill_ib_params's layer was added to (M, E: their shape unless given); c f32 [M] (None: patched at bind time).
+    mode 0 (the MLP): its parameters and their f32 gradients (accumulated); ws / dhid select the column-block form (see ib_bwd); drop as fill_ib_params's.
+    mode 1 (nn.Linear(1, E)): dw1 / db1 only."""
+    for i, x in enumerate(dxs):
+        P.dX[i] = x.data_ptr()
+    P.n_fields, P.ldx = len(dxs), dxs[0].stride(0)
+    P.mode, P.M, P.E = mode, (dxs[0].shape[0] if M is None else M), (dxs[0].shape[1] if E is None else E)
+    P.c, P.w1, P.b1, P.lnw, P.lnb, P.w2 = N.ptr(c), N.ptr(w1), N.ptr(b1), N.ptr(lnw), N.ptr(lnb), N.ptr(w2)
+    P.dw1, P.db1, P.dlnw, P.dlnb, P.dw2, P.db2 = N.ptr(dw1), N.ptr(db1), N.ptr(dlnw), N.ptr(dlnb), N.ptr(dw2), N.ptr(db2)
+    P.h = w1.numel() if mode == 0 else 0
+    if ws is not None and dhid is not None:
+        P.ws, P.ws_floats, P.dhid = ws.data_ptr(), ws.numel(), dhid.data_ptr()
+    if drop is not None:
+        P.drop.seed, P.drop.stream, P.drop.thr = drop
 
 
 def ib_bwd(dxs: Sequence[torch.Tensor], c, w1, b1, lnw, lnb, w2, dw1, db1, dlnw, dlnb, dw2, db2, ws: Optional[torch.Tensor] = None,
            dhid: Optional[torch.Tensor] = None) -> None:
     """ws (f32, >= E (1 + h) floats per row split) and dhid (f32 [M, 8], zero on entry) select the column-block form (h <= 8)."""
-    P = N.SeaIbBwdParams()
-    M, E = dxs[0].shape
-    if ws is not None and dhid is not None:
-        P.ws, P.ws_floats, P.dhid = ws.data_ptr(), ws.numel(), dhid.data_ptr()
-    for i, x in enumerate(dxs):
+    for x in dxs:
         _mat(x, "dx")
         assert x.dtype == torch.float32 and x.stride(0) == dxs[0].stride(0)
-        P.dX[i] = x.data_ptr()
-    P.n_fields, P.ldx = len(dxs), dxs[0].stride(0)
-    P.c, P.w1, P.b1, P.lnw, P.lnb, P.w2 = (t.data_ptr() for t in (c, w1, b1, lnw, lnb, w2))
-    P.dw1, P.db1, P.dlnw, P.dlnb, P.dw2, P.db2 = (t.data_ptr() for t in (dw1, db1, dlnw, dlnb, dw2, db2))
-    P.M, P.E, P.h = M, E, w1.numel()
+    P = N.SeaIbBwdParams()
+    fill_ib_bwd_params(P, dxs, c, w1, b1, lnw, lnb, w2, dw1, db1, dlnw, dlnb, dw2, db2, ws, dhid)
     N.check(N.lib().sea_ib_bwd(C.byref(P), N.stream_ptr()), "sea_ib_bwd")
 
 
@@ -527,16 +571,11 @@ def transpose_weights(src_flat: torch.Tensor, dst_flat: torch.Tensor, desc: torc
                                           tile_start.data_ptr(), n, total, N.stream_ptr()), "sea_transpose_weights")
 
 
-def attention_bwd(problems: Sequence[Dict], rope: torch.Tensor, B: int, H: int, hd: int, Tq: int, Tk: int, cap: int, q_pos0: int,
-                  src_len: int, q_scale: float, dtype: torch.dtype) -> None:
-    """problems: dicts with Q, K, V (row-major), O, dO [B,Tq,H*hd], LSE, delta f32 [B,H,Tq], dQ/dK/dV act [B*T, >= H*hd]."""
-    P = N.SeaAttnBwdParams()
+def fill_attn_bwd_params(P: N.SeaAttnBwdParams, problems: Sequence[Dict], rope, B: int, H: int, hd: int, Tq: int, Tk: int, cap: int, q_pos0: int, src_len: int,
+                         q_scale: float, drop=None) -> None:
+    """problems: dicts as attention_bwd's (the row strides are those of the first problem's O, dO, dQ, dK, dV); drop as fill_attn_params's."""
     P.n_problems = len(problems)
-    for i, d in enumerate(problems):
-        q = P.p[i]
-        for k in ("Q", "K", "V", "O", "dO", "dQ", "dK", "dV"):
-            N.require_gpu(d[k], k)
-            assert d[k].dtype == dtype, k
+    for q, d in zip(P.p, problems):
         q.Q, q.K, q.V, q.O, q.dO = (d[k].data_ptr() for k in ("Q", "K", "V", "O", "dO"))
         q.LSE, q.delta = d["LSE"].data_ptr(), d["delta"].data_ptr()
         q.dQ, q.dK, q.dV = d["dQ"].data_ptr(), d["dK"].data_ptr(), d["dV"].data_ptr()
@@ -546,6 +585,19 @@ def attention_bwd(problems: Sequence[Dict], rope: torch.Tensor, B: int, H: int, 
     P.ldo, P.lddo = d0["O"].stride(-2), d0["dO"].stride(-2)
     P.lddq, P.lddk, P.lddv = d0["dQ"].stride(-2), d0["dK"].stride(-2), d0["dV"].stride(-2)
     P.q_scale = q_scale
+    if drop is not None:
+        P.drop.seed, P.drop.stream, P.drop.thr = drop
+
+
+def attention_bwd(problems: Sequence[Dict], rope: torch.Tensor, B: int, H: int, hd: int, Tq: int, Tk: int, cap: int, q_pos0: int,
+                  src_len: int, q_scale: float, dtype: torch.dtype) -> None:
+    """problems: dicts with Q, K, V (row-major), O, dO [B,Tq,H*hd], LSE, delta f32 [B,H,Tq], dQ/dK/dV act [B*T, >= H*hd]."""
+    for d in problems:
+        for k in ("Q", "K", "V", "O", "dO", "dQ", "dK", "dV"):
+            N.require_gpu(d[k], k)
+            assert d[k].dtype == dtype, k
+    P = N.SeaAttnBwdParams()
+    fill_attn_bwd_params(P, problems, rope, B, H, hd, Tq, Tk, cap, q_pos0, src_len, q_scale)
     N.check(N.lib().sea_attention_bwd(C.byref(P), N.dtype_code(dtype), N.stream_ptr()), "sea_attention_bwd")
 
 
@@ -588,16 +640,20 @@ def patchify(fields: torch.Tensor, index_map: torch.Tensor, scale: torch.Tensor,
     return out
 
 
+def fill_splitk_group(g: N.SeaSplitkGroup, P, bias=None, bias_scale=1.0, R=None, C32=None, Cact=None) -> None:
+    """P f32 [S, M, N]: the partial products; out = sum_s P[s] + bias * bias_scale + R into C32 and / or Cact."""
+    g.P, g.p_stride, g.S, g.M, g.N, g.ldp = P.data_ptr(), P.stride(0), P.shape[0], P.shape[1], P.shape[2], P.stride(1)
+    g.bias, g.bias_scale = N.ptr(bias), bias_scale
+    g.R, g.ldr = N.ptr(R), (R.stride(0) if R is not None else 0)
+    g.C32, g.ldc32 = N.ptr(C32), (C32.stride(0) if C32 is not None else 0)
+    g.Cact, g.ldcact = N.ptr(Cact), (Cact.stride(0) if Cact is not None else 0)
+
+
 def splitk_finish(groups: Sequence[Dict], dtype: torch.dtype) -> None:
     """sea_splitk_finish: out = sum_s P[s] + bias * bias_scale + R; dicts with P f32 [S, M, N], optional bias / bias_scale / R, outputs C32 and / or Cact."""
     arr = (N.SeaSplitkGroup * len(groups))()
     for g, d in zip(arr, groups):
-        P, R, C32, Cact = d["P"], d.get("R"), d.get("C32"), d.get("Cact")
-        g.P, g.p_stride, g.S, g.M, g.N, g.ldp = P.data_ptr(), P.stride(0), P.shape[0], P.shape[1], P.shape[2], P.stride(1)
-        g.bias, g.bias_scale = N.ptr(d.get("bias")), d.get("bias_scale", 1.0)
-        g.R, g.ldr = N.ptr(R), (R.stride(0) if R is not None else 0)
-        g.C32, g.ldc32 = N.ptr(C32), (C32.stride(0) if C32 is not None else 0)
-        g.Cact, g.ldcact = N.ptr(Cact), (Cact.stride(0) if Cact is not None else 0)
+        fill_splitk_group(g, d["P"], d.get("bias"), d.get("bias_scale", 1.0), d.get("R"), d.get("C32"), d.get("Cact"))
     N.check(N.lib().sea_splitk_finish(arr, len(groups), N.dtype_code(dtype), N.stream_ptr()), "sea_splitk_finish")
 
 

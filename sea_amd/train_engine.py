@@ -54,79 +54,40 @@ class TrainPlan(Plan):
 
     # ------------------------------------------------------------------ record builders (backward)
     def _wgrad(self, groups: List[dict], name: str, sole: bool = False) -> None:
-        """`sole`: this launch is the ONLY contribution to its dW tensors in a backward (the field MLP's matrices): when the gradient buffer is known to hold
-        zeros (engine.backward sets SeaWgradGroup.overwrite per run from grads_dirty) the kernel may store instead of adding atomically."""
-        L = N.lib()
-        for s in range(0, len(groups), N.MAX_WGRAD_GROUPS):
-            chunk = groups[s:s + N.MAX_WGRAD_GROUPS]
-            arr = (N.SeaWgradGroup * len(chunk))()
-            for g, d in zip(arr, chunk):
-                dY, X, dW = d["dY"], d["X"], d["dW"]
-                g.dY, g.X, g.dW, g.db = dY.data_ptr(), X.data_ptr(), dW.data_ptr(), N.ptr(d.get("db"))
-                g.lddy, g.ldx, g.lddw = dY.stride(0), X.stride(0), dW.stride(0)
-                g.M, g.N, g.K = self.M, dW.shape[0], dW.shape[1]
-                assert dY.shape[1] == g.N and X.shape[1] == g.K, (name, dY.shape, X.shape, dW.shape)
-                if sole:
-                    self.__dict__.setdefault("_sole_wgrads", []).append(g)
-            self._cur.append(_Rec(L.sea_wgrad_grouped, [arr, len(chunk), self.code], name, arr))
+        """Group dicts: the arguments of ops.fill_wgrad_group.  `sole`: this launch is the ONLY contribution to its dW tensors in a backward (the field MLP's
+        matrices): when the gradient buffer is known to hold zeros (engine.backward sets SeaWgradGroup.overwrite per run from grads_dirty) the kernel may store
+        instead of adding atomically."""
+        def fill(g, dY, X, dW, db=None):
+            assert dY.shape[1] == dW.shape[0] and X.shape[1] == dW.shape[1], (name, dY.shape, X.shape, dW.shape)
+            ops.fill_wgrad_group(g, dY, X, dW, db, M=self.M)
+            if sole:
+                self.__dict__.setdefault("_sole_wgrads", []).append(g)
+        self._grouped(N.lib().sea_wgrad_grouped, N.SeaWgradGroup, groups, N.MAX_WGRAD_GROUPS, fill, name, self.code)
 
     def _norm_bwd(self, groups: List[dict], d: int, name: str, dy_is_act: bool, x_is_act: bool, gelu: bool, accumulate: bool) -> None:
-        L = N.lib()
+        """Group dicts: those of ops.fill_norm_bwd_group, plus `X_is_x` and `dY_is_dout`."""
         for s in range(0, len(groups), N.MAX_NORM_BWD_GROUPS):
-            chunk = groups[s:s + N.MAX_NORM_BWD_GROUPS]
-            arr = (N.SeaNormBwdGroup * len(chunk))()
-            for g, gd in zip(arr, chunk):
-                dY, X = gd["dY"], gd["X"]
-                g.dY, g.lddy = dY.data_ptr(), gd.get("lddy", dY.stride(0))
-                g.X, g.ldx = X.data_ptr(), gd.get("ldx", X.stride(0))
-                mod, dmod = gd.get("mod"), gd.get("dmod")
-                g.mod, g.ldmod = N.ptr(mod), (mod.stride(0) if mod is not None else 0)
-                g.dmod, g.lddmod = N.ptr(dmod), (dmod.stride(0) if dmod is not None else 0)
-                g.gamma, g.beta = gd["gamma"].data_ptr(), N.ptr(gd.get("beta"))
-                g.mean, g.rstd = gd["mean"].data_ptr(), gd["rstd"].data_ptr()
-                dx32, dxa = gd.get("dX32"), gd.get("dXact")
-                g.dX32, g.lddx32 = N.ptr(dx32), (dx32.stride(0) if dx32 is not None else 0)
-                g.dXact, g.lddxact = N.ptr(dxa), (dxa.stride(0) if dxa is not None else 0)
-                g.dgamma, g.dbeta = N.ptr(gd.get("dgamma")), N.ptr(gd.get("dbeta"))
-                if gd.get("X_is_x") is not None:
-                    self._x_patches.append((g, "X", gd["X_is_x"]))
-                if gd.get("dY_is_dout") is not None:
-                    self._dout_patches.append((g, "dY", gd["dY_is_dout"]))
-            ws = self._colsum_ws(len(chunk) * min((self.M + 3) // 4, 512) * 2 * d)
-            self._cur.append(_Rec(L.sea_rownorm_bwd, [arr, len(chunk), self.M, d, int(dy_is_act), int(x_is_act), int(gelu), int(accumulate),
-                                                      self.code, ws.data_ptr(), ws.numel()], name, arr))
+            arr = self._array(N.SeaNormBwdGroup, groups[s:s + N.MAX_NORM_BWD_GROUPS], lambda g, **gd: ops.fill_norm_bwd_group(g, gd))
+            ws = self._colsum_ws(len(arr) * min((self.M + 3) // 4, 512) * 2 * d)
+            self._cur.append(self._rec(N.lib().sea_rownorm_bwd, [arr, len(arr), self.M, d, int(dy_is_act), int(x_is_act), int(gelu), int(accumulate),
+                                                                 self.code, ws.data_ptr(), ws.numel()], name, arr))
 
     def _attn_bwd(self, problems: List[dict], hd: int, rope: torch.Tensor, name: str, drop=None, src_len: Optional[int] = None) -> None:
-        L = N.lib()
+        """drop: (thr, first stream) as _attn's."""
         P = N.SeaAttnBwdParams()
-        P.n_problems = len(problems)
+        # q_scale: what the QKV epilogue put on q (the kernel undoes it, and the log2 units of the scores)
+        ops.fill_attn_bwd_params(P, problems, rope, self.B, self.H, hd, self.T, self.T, self.cap, 0, (self.eng.model.src_len if src_len is None else src_len),
+                                 ops.q_scale(hd), drop=((0, drop[1], drop[0]) if drop is not None else None))
         if drop is not None:
-            P.drop.thr, P.drop.stream = drop
             self._drop_structs.append(P)
-        for i, d in enumerate(problems):
-            q = P.p[i]
-            q.Q, q.K, q.V, q.O, q.dO = (d[k].data_ptr() for k in ("Q", "K", "V", "O", "dO"))
-            q.LSE, q.delta = d["LSE"].data_ptr(), d["delta"].data_ptr()
-            q.dQ, q.dK, q.dV = d["dQ"].data_ptr(), d["dK"].data_ptr(), d["dV"].data_ptr()
-        d0 = problems[0]
-        P.rope = rope.data_ptr()
-        P.B, P.H, P.hd, P.Tq, P.Tk, P.cap, P.q_pos0, P.src_len = self.B, self.H, hd, self.T, self.T, self.cap, 0, (self.eng.model.src_len if src_len is None else src_len)
-        P.ldo, P.lddo = d0["O"].stride(0), d0["dO"].stride(0)
-        P.lddq, P.lddk, P.lddv = d0["dQ"].stride(0), d0["dK"].stride(0), d0["dV"].stride(0)
-        P.q_scale = ops.q_scale(hd)   # what the QKV epilogue put on q (the kernel undoes it, and the log2 units of the scores)
-        self._cur.append(_Rec(L.sea_attention_bwd, [C.byref(P), self.code], name, P))
+        self._cur.append(self._rec(N.lib().sea_attention_bwd, [C.byref(P), self.code], name, P))
 
     def _silu_bwd(self, groups: List[dict], name: str) -> None:
-        L = N.lib()
+        """Group dicts: the arguments of ops.fill_silu_bwd_group."""
         for s in range(0, len(groups), N.MAX_SILU_BWD_GROUPS):
-            chunk = groups[s:s + N.MAX_SILU_BWD_GROUPS]
-            arr = (N.SeaSiluBwdGroup * len(chunk))()
-            for g, d in zip(arr, chunk):
-                dH = d["dHid"]
-                g.dHid, g.w1, g.b1, g.dw1, g.db1 = dH.data_ptr(), d["w1"].data_ptr(), d["b1"].data_ptr(), d["dw1"].data_ptr(), d["db1"].data_ptr()
-                g.K2, g.ld = dH.shape[1], dH.stride(0)
-            ws = self._colsum_ws(len(chunk) * min((self.M + 3) // 4, 256) * 2 * max(d["dHid"].shape[1] for d in chunk))
-            rec = _Rec(L.sea_silu_outer_bwd, [arr, len(chunk), None, self.M, self.code, ws.data_ptr(), ws.numel()], name, arr)
+            arr = self._array(N.SeaSiluBwdGroup, groups[s:s + N.MAX_SILU_BWD_GROUPS], ops.fill_silu_bwd_group)
+            ws = self._colsum_ws(len(arr) * min((self.M + 3) // 4, 256) * 2 * max(g.K2 for g in arr))
+            rec = self._rec(N.lib().sea_silu_outer_bwd, [arr, len(arr), None, self.M, self.code, ws.data_ptr(), ws.numel()], name, arr)
             self._c_patches.append((rec.args, 2))
             self._cur.append(rec)
 
@@ -197,30 +158,25 @@ class TrainPlan(Plan):
         P, G, mode = self.eng.params, self.eng.grad_view, self.eng.ib_mode
         if mode == 2:      # GaussianFourierProjection: its matrix is fixed (requires_grad=False in the reference): nothing to accumulate
             return
-        ib = N.SeaIbBwdParams()
-        for i, x in enumerate(dxs):
-            ib.dX[i] = x.data_ptr()
-        ib.n_fields, ib.ldx = len(dxs), dxs[0].stride(0)
-        ib.M, ib.E, ib.mode = self.M, self.ib_dim, mode
         if mode == 1:      # nn.Linear(1, E): weight [E, 1], bias [E]
-            ib.dw1, ib.db1 = G(pre + "ib.weight").data_ptr(), G(pre + "ib.bias").data_ptr()
+            w = dict(dw1=G(pre + "ib.weight"), db1=G(pre + "ib.bias"))
         else:
-            if drop is not None:
-                ib.drop.thr, ib.drop.stream = drop
-                self._drop_structs.append(ib)
             names = ("ib.layers.0.weight", "ib.layers.0.bias", "ib.layers.1.weight", "ib.layers.1.bias", "ib.layers.3.weight")
-            ib.w1, ib.b1, ib.lnw, ib.lnb, ib.w2 = (P.f32(pre + n).data_ptr() for n in names)
-            ib.dw1, ib.db1, ib.dlnw, ib.dlnb, ib.dw2 = (G(pre + n).data_ptr() for n in names)
-            ib.db2 = G(pre + "ib.layers.3.bias").data_ptr()
-            ib.h = self.eng.model.ib_hidden
-            if ib.h <= 8:   # the column-block form (bwd.hip): partial sums per row split, d hidden per row (zeroed once: the launch leaves it zero)
+            w = dict(zip(("w1", "b1", "lnw", "lnb", "w2"), (P.f32(pre + n) for n in names)))
+            w.update(zip(("dw1", "db1", "dlnw", "dlnb", "dw2"), (G(pre + n) for n in names)), db2=G(pre + "ib.layers.3.bias"))
+            h = self.eng.model.ib_hidden
+            if h <= 8:   # the column-block form (bwd.hip): partial sums per row split, d hidden per row (zeroed once: the launch leaves it zero)
                 n_cb = (self.ib_dim + 255) // 256
                 rs = max(1, min((1024 + n_cb - 1) // n_cb, (self.M + 15) // 16))
-                ws = self._buf(rs * self.ib_dim * (1 + ib.h), dtype=torch.float32)
-                dhid = self._buf(self.M, 8, dtype=torch.float32, zero=True)
-                ib.ws, ib.ws_floats, ib.dhid = ws.data_ptr(), ws.numel(), dhid.data_ptr()
+                w.update(ws=self._buf(rs * self.ib_dim * (1 + h), dtype=torch.float32), dhid=self._buf(self.M, 8, dtype=torch.float32, zero=True))
+            if drop is not None:   # (thr, first stream) as _ib's
+                w["drop"] = (0, drop[1], drop[0])
+        ib = N.SeaIbBwdParams()
+        ops.fill_ib_bwd_params(ib, dxs, None, mode=mode, M=self.M, E=self.ib_dim, **w)
+        if "drop" in w:
+            self._drop_structs.append(ib)
         self._c_patches.append((ib, "c"))
-        self._cur.append(_Rec(N.lib().sea_ib_bwd, [C.byref(ib)], "bwd.ib", ib))
+        self._cur.append(self._rec(N.lib().sea_ib_bwd, [C.byref(ib)], "bwd.ib", ib))
 
     def _convert(self, src32: torch.Tensor, dst: torch.Tensor, name: str) -> None:
         self._cur.append(_Rec(N.lib().sea_convert_f32_to_act, [src32.data_ptr(), src32.stride(0), dst.data_ptr(), dst.stride(0), src32.shape[0],
@@ -268,14 +224,11 @@ class TrainPlan(Plan):
             silu_groups, gemm_groups = [], []
             for pre, d in prefixes:
                 hid[pre], mods[pre] = buf(M, 2 * d), buf(M, 2 * d)
-                silu_groups.append((P.f32_vec(pre + "cond_mlp.0.weight", 2 * d), P.f32_vec(pre + "cond_mlp.0.bias"), hid[pre]))
+                silu_groups.append(dict(w1=P.f32_vec(pre + "cond_mlp.0.weight", 2 * d), b1=P.f32_vec(pre + "cond_mlp.0.bias"), Hid=hid[pre]))
                 gemm_groups.append(dict(A=hid[pre], W=P.act(pre + "cond_mlp.2.weight"), bias=P.f32_vec(pre + "cond_mlp.2.bias"), Cact=mods[pre]))
             for s in range(0, len(silu_groups), N.MAX_SILU_GROUPS):
-                chunk = silu_groups[s:s + N.MAX_SILU_GROUPS]
-                arr = (N.SeaSiluGroup * len(chunk))()
-                for g, (w1, b1, hb) in zip(arr, chunk):
-                    g.w1, g.b1, g.Hid, g.K2, g.ld = w1.data_ptr(), b1.data_ptr(), hb.data_ptr(), hb.shape[1], hb.stride(0)
-                rec = _Rec(L.sea_silu_outer, [arr, len(chunk), None, M, self.code], "adaln.silu", arr)
+                arr = self._array(N.SeaSiluGroup, silu_groups[s:s + N.MAX_SILU_GROUPS], ops.fill_silu_group)
+                rec = _Rec(L.sea_silu_outer, [arr, len(arr), None, M, self.code], "adaln.silu", arr)
                 self._c_patches.append((rec.args, 2))
                 self._cur.append(rec)
             self._gemm(gemm_groups, "adaln.cond_gemm")
@@ -393,7 +346,7 @@ class TrainPlan(Plan):
                                D, "pool.norm")
                 # (PositionalEncoding ends in nn.Dropout, models/base_blocks.py:370-372: the position-encoded rows themselves are dropped — mode 3 of the epilogue)
                 sv["pe_drop"] = self._streams(F) if thr else None
-                self._gemm([dict(A=nrm[j], W=eng.eye(D), R=pe_t, Cact=big[:, j * D:(j + 1) * D], drop=((thr, sv["pe_drop"] + j, 3) if thr else None))
+                self._gemm([dict(A=nrm[j], W=eng.eye(D), R=pe_t, Cact=big[:, j * D:(j + 1) * D], drop=((0, sv["pe_drop"] + j, thr, 3) if thr else None))
                             for j in range(F)], "pool.pe_add")
                 sv["hp_pre"], sv["hp"], sv["pool"] = buf(M, 2 * D), buf(M, 2 * D), buf(M, D)
                 self._gemm([dict(A=big[:, :FD], W=P.act(f"{pre}pool_update.0.weight"), bias=P.f32_vec(f"{pre}pool_update.0.bias"), Cact=sv["hp"], Z=sv["hp_pre"],
@@ -487,7 +440,7 @@ class TrainPlan(Plan):
                              Yact=sv["hg"][i], mean=sv["sth"][i][0], rstd=sv["sth"][i][1]) for i in range(F)], S, "mlp.ln_gelu", x_is_act=True, gelu=True)
             sv["mlp_drop"] = self._streams(F) if thr else None
             self._gemm([dict(A=sv["hg"][i], W=P.act(f"{pre}mlp.{i}.layers.3.weight"), bias=P.f32_vec(f"{pre}mlp.{i}.layers.3.bias"), R=sv["xr"][i],
-                             Cact=sv["xa4"][i], drop=((thr, sv["mlp_drop"] + i, 1) if thr else None)) for i in range(F)], "mlp.fc2")
+                             Cact=sv["xa4"][i], drop=((0, sv["mlp_drop"] + i, thr, 1) if thr else None)) for i in range(F)], "mlp.fc2")
             self._gemm([dict(A=sv["xa4"][i], W=P.act(f"{pre}proj.{i}.weight"), bias=P.f32_vec(f"{pre}proj.{i}.bias"), C32=sv["x5"][i])
                         for i in range(F)], "proj")
             x_prev = sv["x5"]
@@ -547,7 +500,7 @@ class TrainPlan(Plan):
             self._wgrad([dict(dY=gao[i], X=sv["xa4"][i], dW=G2(f"{pre}proj.{i}.weight"), db=Gv(f"{pre}proj.{i}.bias")) for i in range(F)], "bwd.proj.wgrad")
             # (MLP-output dropout: the residual path C32 stays whole, the copy feeding fc2's backward is masked)
             self._gemm([dict(A=gao[i], W=P.actT(f"{pre}proj.{i}.weight"), C32=dx[i], Cact=gb[i],
-                             drop=((thr, sv["mlp_drop"] + i, 2) if thr else None)) for i in range(F)], "bwd.proj.dgrad")
+                             drop=((0, sv["mlp_drop"] + i, thr, 2) if thr else None)) for i in range(F)], "bwd.proj.dgrad")
             # ---- fc2:   x4 = x3 + hg W2^T + b2                 (gb = d x4)
             self._wgrad([dict(dY=gb[i], X=sv["hg"][i], dW=G2(f"{pre}mlp.{i}.layers.3.weight"), db=Gv(f"{pre}mlp.{i}.layers.3.bias")) for i in range(F)],
                         "bwd.fc2.wgrad", sole=True)
@@ -616,7 +569,7 @@ class TrainPlan(Plan):
                 self._wgrad([dict(dY=dhp, X=big[:, :FD], dW=G2(f"{pre}pool_update.0.weight"), db=Gv(f"{pre}pool_update.0.bias"))], "bwd.pool.update0.wgrad")
                 w0t = P.actT(f"{pre}pool_update.0.weight")          # [F D, 2 D]: rows j D .. (j+1) D map d hp onto d n_j
                 # the last of the three contributions to d (dropped rows): with dropout the gradient of the rows BEFORE the mask is mask * (the sum)
-                self._gemm([dict(A=dhp, W=w0t[j * D:(j + 1) * D], R=dnd[j], C32=dnd[j], drop=((thr, sv["pe_drop"] + j, 3) if thr else None))
+                self._gemm([dict(A=dhp, W=w0t[j * D:(j + 1) * D], R=dnd[j], C32=dnd[j], drop=((0, sv["pe_drop"] + j, thr, 3) if thr else None))
                             for j in range(F)], "bwd.pool.update0.dgrad")
                 ddn = [buf(M, D) for _ in range(F)]
                 self._norm_bwd([dict(dY=dnd[j], X=sv["dn"][j], mean=sv["stc"][j][0], rstd=sv["stc"][j][1], dXact=ddn[j], **bpar(f"{pre}ln_cross.{j}.", D))
