@@ -146,6 +146,8 @@ int sea_qkv_rope_grouped(const SeaQkvGroup* groups, int n_groups, const SeaQkvCo
  * masked_fill(tril(diagonal=src_len) == 0, -inf), softmax, @ v, merge heads — without materialising [T, T].
  * Scores are taken in LOG2 units: P = 2^(Q K^T - rowmax) / rowsum, i.e. Q must carry hd^-1/2 * log2(e) (SeaQkvCommon.q_scale).
  * Query row i (absolute position q_pos0 + i) attends keys j <= q_pos0 + i + src_len, j < Tk.
+ * hd: any multiple of 8 in 8..256 (powers of two run kernels of their own width; any other width a kernel of width round_up(hd, 32) that masks
+ * the columns past hd); cap % 8 == 0.  Anything else returns -1 ("unsupported head dim").
  *   O   : act [B, Tq, H*hd] row stride ldo
  *   LSE : f32 [B, H, Tq] BASE-2 log-sum-exp of the scores, log2(sum_j 2^(S_ij)) (for the backward pass), may be NULL
  */
@@ -493,6 +495,7 @@ int sea_rownorm_bwd(const SeaNormBwdGroup* groups, int n_groups, int M, int d, i
 
 /* Backward of sea_attention_fwd + the rotary embedding of sea_qkv_rope_grouped (flash-style: P is recomputed from Q, K and the
  * forward's LSE).  For each problem, from dO (gradient of the attention output, [B, Tq, H*hd] row stride lddo):
+ * hd: the forward's set, any multiple of 8 in 8..256.
  *   dQ [B*Tq, H*hd] (row stride lddq), dK, dV [B*Tk, H*hd] (lddk, lddv) = gradients with respect to the OUTPUTS of the q / k / v
  *   Linear layers (RoPE and the q scale are undone in the epilogue), i.e. the dY operands of sea_wgrad_grouped / the dgrad GEMM.
  * V is the row-major copy written by sea_qkv_rope_grouped (Vout); delta (f32 [B, H, Tq]) is workspace.  Deterministic.

@@ -12,7 +12,9 @@
 // NB blocks of a chunk lane group g holds the EPC = 4*NB CONSECUTIVE keys g*EPC .. g*EPC+EPC-1: exactly the
 // B-operand fragment (k = g*EPC + j) of the O^T product — P goes from accumulator to operand with a pack, no
 // shuffle, no LDS.
-// Head dims 8..128 (multiples of 8); contraction padded with zero lanes when hd < CK (hd = 16 bf16, hd = 8).
+// Head dims: every multiple of 8 in 8..256.  The powers of two have kernels of their own width (HD = hd, contraction padded with zero lanes when
+// hd < CK: hd = 16 bf16, hd = 8).  Any other width runs a MASKED kernel of compute width HD = round_up(hd, 32): the real hd (P.hd) is the row stride
+// of every global operand, key rows carry zero columns hd .. HD-1 in LDS (written once), V^T rows and O^T rows at or past hd are never loaded or stored.
 #include "sea_common.hpp"
 
 template <typename T, int HD>
@@ -66,9 +68,10 @@ struct AttnFwdLds {
 };
 
 // one 64-row query tile `qt` of (trajectory, head) pair `bh` of problem `zp`
-template <typename T, int HD, int SPLIT, bool DROP>
+template <typename T, int HD, int SPLIT, bool DROP, bool MASKED>
 __device__ __forceinline__ void attention_fwd_tile(const SeaAttnParams& P, char* smem_all, const int qt, const int bh, const int zp) {
     using C = AttnCfg<T, HD>;
+    const int hd = MASKED ? P.hd : HD;   // the real head dim (a multiple of 8, <= HD): the row stride of every global operand
     constexpr int NBUF = AttnFwdLds<T, HD, SPLIT>::NBUF;
     const int grp = SPLIT > 1 ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 8)) : 0;  // wave-uniform
     char* smem = smem_all + grp * NBUF * C::LDS_BYTES;
@@ -77,9 +80,9 @@ __device__ __forceinline__ void attention_fwd_tile(const SeaAttnParams& P, char*
     const int r = lane & 15, g = lane >> 4;
     const int b = bh / P.H, h = bh - b * P.H;
     const SeaAttnProblem& pr = P.p[zp];
-    const T* Qg = static_cast<const T*>(pr.Q) + (int64_t)bh * P.Tq * HD;
-    const T* Kg = static_cast<const T*>(pr.K) + (int64_t)bh * P.cap * HD;
-    const T* Vg = static_cast<const T*>(pr.Vt) + (int64_t)bh * HD * P.cap;
+    const T* Qg = static_cast<const T*>(pr.Q) + (int64_t)bh * P.Tq * hd;
+    const T* Kg = static_cast<const T*>(pr.K) + (int64_t)bh * P.cap * hd;
+    const T* Vg = static_cast<const T*>(pr.Vt) + (int64_t)bh * hd * P.cap;
     const int Tq = P.Tq, Tk = P.Tk, cap = P.cap;
 
     const int q_row0 = qt * 64 + wave * 16;
@@ -92,7 +95,7 @@ __device__ __forceinline__ void attention_fwd_tile(const SeaAttnParams& P, char*
 #pragma unroll
     for (int c = 0; c < C::NCH; ++c) {
         const int d0 = c * C::CK + g * C::EPC;
-        qf[c] = d0 < HD ? *reinterpret_cast<const uint4*>(Qg + (int64_t)q_ld * HD + d0) : make_uint4(0, 0, 0, 0);
+        qf[c] = d0 < hd ? *reinterpret_cast<const uint4*>(Qg + (int64_t)q_ld * hd + d0) : make_uint4(0, 0, 0, 0);   // (hd % 8 == 0: a chunk is all in or all out)
     }
 
     f32x4 oacc[C::NDB];
@@ -119,7 +122,7 @@ __device__ __forceinline__ void attention_fwd_tile(const SeaAttnParams& P, char*
 
     // ---- K/V tile staging through registers (issue-early / write-late, cdna_hip_programming.md T14): the global loads of
     // tile kt+1 are issued before the MFMAs of tile kt and written to the OTHER LDS buffer after them; one barrier per tile.
-    constexpr int K_CPR = HD / C::EPC;                       // 16-byte chunks per key row
+    constexpr int K_CPR = HD / C::EPC;                       // 16-byte chunks per key row (MASKED: those at columns >= hd are neither loaded nor stored)
     constexpr int V_CPR = 64 / C::EPC;                       // 16-byte chunks per d row of the V^T tile
     constexpr int NKR = (64 * K_CPR + 255) / 256;            // chunks per thread
     constexpr int NVR = (HD * V_CPR + 255) / 256;
@@ -131,20 +134,20 @@ __device__ __forceinline__ void attention_fwd_tile(const SeaAttnParams& P, char*
     for (int u = 0; u < NKR; ++u) {
         const int idx = tid + u * 256;
         const int rr = idx / K_CPR, cc = idx - rr * K_CPR;
-        k_row[u] = idx < 64 * K_CPR ? rr : -1;
-        k_goff[u] = rr * HD + cc * C::EPC;
+        k_row[u] = idx < 64 * K_CPR && cc * C::EPC < hd ? rr : -1;
+        k_goff[u] = rr * hd + cc * C::EPC;
         k_soff[u] = rr * C::K_STRIDE + cc * 16;
     }
 #pragma unroll
     for (int u = 0; u < NVR; ++u) {
         const int idx = tid + u * 256;
         const int d = idx / V_CPR, cc = idx - d * V_CPR;
-        v_key[u] = idx < HD * V_CPR ? cc * C::EPC : -1;
+        v_key[u] = idx < hd * V_CPR ? cc * C::EPC : -1;   // (d rows hd .. HD-1: neither loaded nor stored)
         v_goff[u] = (int64_t)d * cap + cc * C::EPC;
         v_soff[u] = d * C::V_STRIDE + cc * 16;
     }
     auto load_tile = [&](int kt) {
-        const T* Kt = Kg + (int64_t)kt * 64 * HD;
+        const T* Kt = Kg + (int64_t)kt * 64 * hd;
         const T* Vt = Vg + kt * 64;
         if ((kt + 1) * 64 <= Tk) {  // block-uniform fast path: the whole tile is inside the key range
 #pragma unroll
@@ -313,7 +316,7 @@ __device__ __forceinline__ void attention_fwd_tile(const SeaAttnParams& P, char*
 #pragma unroll
             for (int d = 0; d < C::NDB; ++d) {
                 uint4 a = make_uint4(0, 0, 0, 0);
-                if (d * 16 + r < HD) a = *reinterpret_cast<const uint4*>(sV + v_frag_off + d * 16 * C::V_STRIDE + kc * C::CK * (int)sizeof(T));
+                if (d * 16 + r < hd) a = *reinterpret_cast<const uint4*>(sV + v_frag_off + d * 16 * C::V_STRIDE + kc * C::CK * (int)sizeof(T));
                 mma16<T>(a, pf[kc], oacc[d]);
             }
         }
@@ -326,6 +329,14 @@ __device__ __forceinline__ void attention_fwd_tile(const SeaAttnParams& P, char*
             const int buf = i / (64 * (PADB / 16)), rem = i - buf * 64 * (PADB / 16);
             const int row = rem / (PADB / 16), cc = rem - row * (PADB / 16);
             *reinterpret_cast<uint4*>(smem + buf * C::LDS_BYTES + row * C::K_STRIDE + C::K_ROW + cc * 16) = make_uint4(0, 0, 0, 0);
+        }
+    }
+    if constexpr (MASKED) {   // the same for columns hd .. HD-1 of the masked widths, in every buffer of this group (none when hd == HD)
+        const int pch = (HD - hd) * (int)sizeof(T) / 16;
+        for (int i = tid; i < NBUF * 64 * pch; i += 256) {
+            const int buf = i / (64 * pch), rem = i - buf * 64 * pch;
+            const int row = rem / pch, cc = rem - row * pch;
+            *reinterpret_cast<uint4*>(smem + buf * C::LDS_BYTES + row * C::K_STRIDE + hd * (int)sizeof(T) + cc * 16) = make_uint4(0, 0, 0, 0);
         }
     }
     // group g walks tiles g, g + SPLIT, ...; every thread of the workgroup executes every barrier
@@ -397,11 +408,11 @@ __device__ __forceinline__ void attention_fwd_tile(const SeaAttnParams& P, char*
     }
     const float inv = 1.0f / l;
     if (q_idx < Tq) {
-        T* Og = static_cast<T*>(pr.O) + ((int64_t)b * Tq + q_idx) * P.ldo + h * HD;
+        T* Og = static_cast<T*>(pr.O) + ((int64_t)b * Tq + q_idx) * P.ldo + h * hd;
 #pragma unroll
         for (int d = 0; d < C::NDB; ++d) {
             const int d0 = d * 16 + g * 4;
-            if (d0 < HD) store4(Og + d0, oacc[d][0] * inv, oacc[d][1] * inv, oacc[d][2] * inv, oacc[d][3] * inv);
+            if (d0 < hd) store4(Og + d0, oacc[d][0] * inv, oacc[d][1] * inv, oacc[d][2] * inv, oacc[d][3] * inv);
         }
         if (pr.LSE != nullptr && g == 0) pr.LSE[(int64_t)bh * Tq + q_idx] = ref + __log2f(l);   // log2 units, like the scores (the backward recomputes P = 2^(S - LSE))
     }
@@ -412,7 +423,8 @@ __device__ __forceinline__ void attention_fwd_tile(const SeaAttnParams& P, char*
 // 8 XCDs in turn) owns the (trajectory, head) pairs x, x + 8, ... and walks them pair-major: the 16 workgroups of a pair run together and the K / V^T rows they
 // stream (0.26 MB per pair at head dim 32) stay in that XCD's L2.  The plain order (tile-major over all pairs) has every XCD stream 24 pairs' rows at once:
 // PMC at cfg3's self launch 631 MB read for 99 MB of operands, 6.5 TB/s over its 96 us — the launch ran at the rate of the fabric.
-template <typename T, int HD, int SPLIT, bool DROP>
+// MASKED: the compute width HD is above the real head dim P.hd (attention_fwd_tile); the power-of-two widths are never masked.
+template <typename T, int HD, int SPLIT, bool DROP, bool MASKED = false>
 __global__ __launch_bounds__(256 * SPLIT, (attn_min_waves<T, HD, DROP>())) void attention_fwd_kernel(const SeaAttnParams P, const int paired) {
     __shared__ __attribute__((aligned(16))) char smem_all[AttnFwdLds<T, HD, SPLIT>::BYTES];
     const int n_qt = (P.Tq + 63) / 64;
@@ -429,9 +441,9 @@ __global__ __launch_bounds__(256 * SPLIT, (attn_min_waves<T, HD, DROP>())) void 
     } else {
         decode_attn_block(tile_, bh, zp);
     }
-    attention_fwd_tile<T, HD, SPLIT, DROP>(P, smem_all, n_qt - 1 - tile_, bh, zp);  // heaviest (latest) query tiles first
+    attention_fwd_tile<T, HD, SPLIT, DROP, MASKED>(P, smem_all, n_qt - 1 - tile_, bh, zp);  // heaviest (latest) query tiles first
     if constexpr (PAIRABLE) {
-        if (paired && tile_ != n_qt - 1 - tile_) attention_fwd_tile<T, HD, SPLIT, DROP>(P, smem_all, tile_, bh, zp);   // (every wave has passed the tile loop's last barrier)
+        if (paired && tile_ != n_qt - 1 - tile_) attention_fwd_tile<T, HD, SPLIT, DROP, MASKED>(P, smem_all, tile_, bh, zp);   // (every wave has passed the tile loop's last barrier)
     }
 }
 
@@ -755,13 +767,17 @@ static bool launch_attention_row(const SeaAttnParams& P, hipStream_t s) {
     return true;
 }
 
+// compute width of a head dim: itself for the powers of two, else round_up(hd, 32) (a masked kernel)
+static inline int attn_compute_width(int hd) { return (hd & (hd - 1)) == 0 ? hd : (hd + 31) & ~31; }
+
 template <typename T, int SPLIT, bool DROP>
 static int launch_attention_s(const SeaAttnParams& P, hipStream_t s) {
     dim3 grid((P.Tq + 63) / 64, P.B * P.H, P.n_problems);
     const dim3 block(256 * SPLIT);
-    // long launches at head dims >= 32: paired causal tiles in the XCD-local order (attention_fwd_kernel).  SEA_TUNE=attn_paired=0|1 forces (read per call).
+    // long launches at compute widths 32 / 64: paired causal tiles in the XCD-local order (attention_fwd_kernel).  SEA_TUNE=attn_paired=0|1 forces (read per call).
     const int forced = sea_tune("attn_paired", -1);
-    const int paired = SPLIT == 1 && P.hd >= 32 && P.hd <= 64 && (forced >= 0 ? forced : (long)grid.x * grid.y * grid.z >= 4096);
+    const int hdp = attn_compute_width(P.hd);
+    const int paired = SPLIT == 1 && hdp >= 32 && hdp <= 64 && (forced >= 0 ? forced : (long)grid.x * grid.y * grid.z >= 4096);
     if (paired) grid.x = (grid.x + 1) / 2;
     switch (P.hd) {
         case 8: attention_fwd_kernel<T, 8, SPLIT, DROP><<<grid, block, 0, s>>>(P, paired); break;
@@ -770,7 +786,18 @@ static int launch_attention_s(const SeaAttnParams& P, hipStream_t s) {
         case 64: attention_fwd_kernel<T, 64, SPLIT, DROP><<<grid, block, 0, s>>>(P, paired); break;
         case 128: attention_fwd_kernel<T, 128, 1, DROP><<<grid, dim3(256), 0, s>>>(P, paired); break;  // LDS: one group only
         case 256: attention_fwd_kernel<T, 256, 1, DROP><<<grid, dim3(256), 0, s>>>(P, paired); break;  // the shipped multiphase dims (embed_dim 2048 / 8 heads); f32: single LDS buffer
-        default: return -1;
+        default:   // masked widths: the wave-group layout of the power of two at or above the compute width (SPLIT up to 64, one group above)
+            switch (hdp) {
+                case 32: attention_fwd_kernel<T, 32, SPLIT, DROP, true><<<grid, block, 0, s>>>(P, paired); break;
+                case 64: attention_fwd_kernel<T, 64, SPLIT, DROP, true><<<grid, block, 0, s>>>(P, paired); break;
+                case 96: attention_fwd_kernel<T, 96, 1, DROP, true><<<grid, dim3(256), 0, s>>>(P, paired); break;
+                case 128: attention_fwd_kernel<T, 128, 1, DROP, true><<<grid, dim3(256), 0, s>>>(P, paired); break;
+                case 160: attention_fwd_kernel<T, 160, 1, DROP, true><<<grid, dim3(256), 0, s>>>(P, paired); break;
+                case 192: attention_fwd_kernel<T, 192, 1, DROP, true><<<grid, dim3(256), 0, s>>>(P, paired); break;
+                case 224: attention_fwd_kernel<T, 224, 1, DROP, true><<<grid, dim3(256), 0, s>>>(P, paired); break;
+                case 256: attention_fwd_kernel<T, 256, 1, DROP, true><<<grid, dim3(256), 0, s>>>(P, paired); break;
+                default: return -1;
+            }
     }
     return 0;
 }
@@ -784,7 +811,7 @@ static int launch_attention(const SeaAttnParams& P, hipStream_t s) {
     // at most two workgroups per CU: four wave groups per query tile (measured at cfg2: cross-attention 18.3 -> 17.3 us; with 768
     // workgroups the 1024-thread workgroups no longer co-reside and it is slower, 21.7 -> 24.7 us)
     static const int split4 = sea_tune("attn_split4", -1);  // tuning aid: 0 off, 1 on
-    if (split && (split4 == 1 || (split4 < 0 && blocks <= 512)) && P.hd <= 32 && P.drop.thr == 0) {
+    if (split && (split4 == 1 || (split4 < 0 && blocks <= 512)) && (P.hd == 8 || P.hd == 16 || P.hd == 32) && P.drop.thr == 0) {
         const dim3 grid((P.Tq + 63) / 64, P.B * P.H, P.n_problems), block(1024);
         if (P.hd == 32) attention_fwd_kernel<T, 32, 4, false><<<grid, block, 0, s>>>(P, 0);
         else if (P.hd == 16) attention_fwd_kernel<T, 16, 4, false><<<grid, block, 0, s>>>(P, 0);
@@ -802,7 +829,7 @@ extern "C" int sea_attention_fwd(const SeaAttnParams* params, int dtype, void* s
     SEA_REQUIRE(P.n_problems >= 1 && P.n_problems <= SEA_MAX_ATTN_PROBLEMS, "sea_attention_fwd: n_problems=%d", P.n_problems);
     SEA_REQUIRE(P.B >= 1 && P.H >= 1 && P.Tq >= 1 && P.Tk >= 1 && P.cap >= P.Tk && P.q_pos0 >= 0 && P.src_len >= 0,
                 "sea_attention_fwd: bad sizes B=%d H=%d Tq=%d Tk=%d cap=%d q_pos0=%d src_len=%d", P.B, P.H, P.Tq, P.Tk, P.cap, P.q_pos0, P.src_len);
-    SEA_REQUIRE(P.hd == 8 || P.hd == 16 || P.hd == 32 || P.hd == 64 || P.hd == 128 || P.hd == 256, "sea_attention_fwd: unsupported head dim %d (8..256, powers of two)", P.hd);
+    SEA_REQUIRE(P.hd >= 8 && P.hd <= 256 && P.hd % 8 == 0, "sea_attention_fwd: unsupported head dim %d (a multiple of 8 in 8..256)", P.hd);
     SEA_REQUIRE(P.cap % 8 == 0, "sea_attention_fwd: cap=%d must be a multiple of 8", P.cap);
     SEA_REQUIRE(P.drop.thr >= 0 && P.drop.thr <= 255, "sea_attention_fwd: bad dropout threshold %d", P.drop.thr);
     SEA_REQUIRE(P.ldo >= P.H * P.hd && P.ldo % 4 == 0, "sea_attention_fwd: bad ldo=%d", P.ldo);

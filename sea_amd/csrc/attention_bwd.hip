@@ -11,6 +11,10 @@
 // are assigned to keys/queries so that a lane ends up with EPC consecutive ones).  Products that contract over the tile's
 // ROW index read the row-major LDS tile through transposed fragments (ds_read_b64_tr_b16 for bf16).
 // The epilogues undo RoPE (and the q scale) and write gradients of the q/k/v projections' outputs in [M, H*hd] layout.
+// Head dims: every multiple of 8 in 8..256, as in the forward.  A width that is not a power of two runs a MASKED kernel of compute width
+// HD = round_up(hd, 32): the real hd (P.hd) is the row stride of every global operand, the stagers write columns 0 .. hd-1 of a tile row and columns
+// hd .. HD-1 are zeros written once, so the contractions over d add zeros and the transposed reads of a pad column only ever feed a gradient row at
+// or past hd, which is not stored.
 #include "sea_common.hpp"
 
 typedef short s16x4b __attribute__((ext_vector_type(4)));
@@ -65,18 +69,22 @@ __device__ __forceinline__ uint4 pack_frag(const f32x4& lo, const f32x4& hi) {
     }
 }
 
-// stage a [64 rows][HD] row-major tile (rows row0.. of a [n_rows, HD] matrix with row stride ld elements) through registers
-template <typename T, int HD>
+// stage a [64 rows][hd] row-major tile (rows row0.. of a [n_rows, hd] matrix with row stride ld elements) through registers.  The chunk layout is that of
+// the compute width HD; MASKED: the chunks at columns >= hd are neither loaded nor stored
+template <typename T, int HD, bool MASKED = false>
 struct TileStager {
     using C = BwdCfg<T, HD>;
     uint4 r[C::NR];
+    int hd_;
+    __device__ __forceinline__ explicit TileStager(int hd) : hd_(hd) {}
+    __device__ __forceinline__ bool in(int idx, int cc) const { return idx < 64 * C::CPR && (!MASKED || cc * C::EPC < hd_); }
     __device__ __forceinline__ void load(const T* base, int64_t ld, int row0, int n_rows, int tid) {
 #pragma unroll
         for (int u = 0; u < C::NR; ++u) {
             const int idx = tid + u * 256;
             const int rr = idx / C::CPR, cc = idx - rr * C::CPR;
             r[u] = make_uint4(0, 0, 0, 0);
-            if (idx < 64 * C::CPR && row0 + rr < n_rows) r[u] = *reinterpret_cast<const uint4*>(base + (int64_t)(row0 + rr) * ld + cc * C::EPC);
+            if (in(idx, cc) && row0 + rr < n_rows) r[u] = *reinterpret_cast<const uint4*>(base + (int64_t)(row0 + rr) * ld + cc * C::EPC);
         }
     }
     __device__ __forceinline__ void store(char* tile, int tid) const {
@@ -84,7 +92,7 @@ struct TileStager {
         for (int u = 0; u < C::NR; ++u) {
             const int idx = tid + u * 256;
             const int rr = idx / C::CPR, cc = idx - rr * C::CPR;
-            if (idx < 64 * C::CPR) *reinterpret_cast<uint4*>(tile + rr * C::PITCH + cc * 16) = r[u];
+            if (in(idx, cc)) *reinterpret_cast<uint4*>(tile + rr * C::PITCH + cc * 16) = r[u];
         }
     }
 };
@@ -102,6 +110,17 @@ __device__ __forceinline__ void zero_tile_padding(char* base, int n_tiles, int t
             const int row = rem / CH, cc = rem - row * CH;
             *reinterpret_cast<uint4*>(base + t * C::TILE + row * C::PITCH + HD * (int)sizeof(T) + cc * 16) = make_uint4(0, 0, 0, 0);
         }
+    }
+}
+// ... and columns hd .. PCOLS-1 of a masked width (PCOLS = HD there; nothing to do when hd == HD)
+template <typename T, int HD>
+__device__ __forceinline__ void zero_tile_padding_masked(char* base, int n_tiles, int tid, int hd) {
+    using C = BwdCfg<T, HD>;
+    const int ch = (C::PCOLS - hd) * (int)sizeof(T) / 16;
+    for (int i = tid; i < n_tiles * 64 * ch; i += 256) {
+        const int t = i / (64 * ch), rem = i - t * 64 * ch;
+        const int row = rem / ch, cc = rem - row * ch;
+        *reinterpret_cast<uint4*>(base + t * C::TILE + row * C::PITCH + hd * (int)sizeof(T) + cc * 16) = make_uint4(0, 0, 0, 0);
     }
 }
 
@@ -138,21 +157,22 @@ __device__ __forceinline__ void decode_attn_block_bwd(int& tile, int& bh, int& z
 template <typename T, int HD>
 constexpr int attn_bwd_min_waves() { return (sizeof(T) == 2 && HD <= 32) ? SEA_ATTNB_WPE : 1; }
 
-template <typename T, int HD, bool DROP>
+template <typename T, int HD, bool DROP, bool MASKED>
 __device__ __forceinline__ void attn_bwd_dq_tile(const SeaAttnBwdParams& P, char* smem, const int qt, const int bh, const int zp) {
     using C = BwdCfg<T, HD>;
+    const int hd = MASKED ? P.hd : HD;   // the real head dim (a multiple of 8, <= HD)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, g = lane >> 4;
     const int b = bh / P.H, h = bh - b * P.H;
     const SeaAttnBwdProblem& pr = P.p[zp];
     const int Tq = P.Tq, Tk = P.Tk;
-    const T* Qg = static_cast<const T*>(pr.Q) + (int64_t)bh * Tq * HD;
-    const T* Kg = static_cast<const T*>(pr.K) + (int64_t)bh * P.cap * HD;
-    const T* Vg = static_cast<const T*>(pr.V) + (int64_t)bh * P.cap * HD;
+    const T* Qg = static_cast<const T*>(pr.Q) + (int64_t)bh * Tq * hd;
+    const T* Kg = static_cast<const T*>(pr.K) + (int64_t)bh * P.cap * hd;
+    const T* Vg = static_cast<const T*>(pr.V) + (int64_t)bh * P.cap * hd;
     const int q_row0 = qt * 64 + wave * 16, q_idx = q_row0 + r, q_ld = q_idx < Tq ? q_idx : Tq - 1;
     const uint32_t drop_stream = (P.drop.stream + zp) * (uint32_t)(P.B * P.H) + (uint32_t)bh;
     const float drop_sc = P.drop.thr > 0 ? drop_scale(P.drop.thr) : 1.f;
-    const T* Og = static_cast<const T*>(pr.O) + ((int64_t)b * Tq + q_ld) * P.ldo + h * HD;
-    const T* dOg = static_cast<const T*>(pr.dO) + ((int64_t)b * Tq + q_ld) * P.lddo + h * HD;
+    const T* Og = static_cast<const T*>(pr.O) + ((int64_t)b * Tq + q_ld) * P.ldo + h * hd;
+    const T* dOg = static_cast<const T*>(pr.dO) + ((int64_t)b * Tq + q_ld) * P.lddo + h * hd;
 
     uint4 qf[C::NCH], dof[C::NCH];
     float delta = 0.f;
@@ -161,8 +181,8 @@ __device__ __forceinline__ void attn_bwd_dq_tile(const SeaAttnBwdParams& P, char
         const int d0 = c * C::CK + g * C::EPC;
         qf[c] = make_uint4(0, 0, 0, 0);
         dof[c] = make_uint4(0, 0, 0, 0);
-        if (d0 < HD) {
-            qf[c] = *reinterpret_cast<const uint4*>(Qg + (int64_t)q_ld * HD + d0);
+        if (d0 < hd) {
+            qf[c] = *reinterpret_cast<const uint4*>(Qg + (int64_t)q_ld * hd + d0);
             dof[c] = *reinterpret_cast<const uint4*>(dOg + d0);
             T ov[C::EPC], dv[C::EPC];
             *reinterpret_cast<uint4*>(ov) = *reinterpret_cast<const uint4*>(Og + d0);
@@ -241,9 +261,10 @@ __device__ __forceinline__ void attn_bwd_dq_tile(const SeaAttnBwdParams& P, char
     };
 
     zero_tile_padding<T, HD>(smem, 2 * C::NBUF, tid);
-    TileStager<T, HD> stK, stV;
-    stK.load(Kg, HD, 0, Tk, tid);
-    stV.load(Vg, HD, 0, Tk, tid);
+    if constexpr (MASKED) zero_tile_padding_masked<T, HD>(smem, 2 * C::NBUF, tid, hd);
+    TileStager<T, HD, MASKED> stK(hd), stV(hd);
+    stK.load(Kg, hd, 0, Tk, tid);
+    stV.load(Vg, hd, 0, Tk, tid);
     stK.store(smem, tid);
     stV.store(smem + C::TILE, tid);
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): pre-loop register loads are complete, so the per-tile MFMAs do not wait on the prefetch (see attention.hip)
@@ -253,8 +274,8 @@ __device__ __forceinline__ void attn_bwd_dq_tile(const SeaAttnBwdParams& P, char
         const char* sV = sK + C::TILE;
         const bool more = kt + 1 < n_kt;
         if (more) {
-            stK.load(Kg, HD, (kt + 1) * 64, Tk, tid);
-            stV.load(Vg, HD, (kt + 1) * 64, Tk, tid);
+            stK.load(Kg, hd, (kt + 1) * 64, Tk, tid);
+            stV.load(Vg, hd, (kt + 1) * 64, Tk, tid);
         }
         if (kt * 64 <= wave_last) {
             if (kt * 64 + 63 <= wave_first && kt * 64 + 63 < Tk) tile(sK, sV, kt, std::false_type{});
@@ -269,12 +290,12 @@ __device__ __forceinline__ void attn_bwd_dq_tile(const SeaAttnBwdParams& P, char
         __syncthreads();
     }
     if (q_idx < Tq) {
-        T* out = static_cast<T*>(pr.dQ) + ((int64_t)b * Tq + q_idx) * P.lddq + h * HD;
-        const float2* rope = reinterpret_cast<const float2*>(P.rope) + (int64_t)(P.q_pos0 + q_idx) * (HD / 2);
+        T* out = static_cast<T*>(pr.dQ) + ((int64_t)b * Tq + q_idx) * P.lddq + h * hd;
+        const float2* rope = reinterpret_cast<const float2*>(P.rope) + (int64_t)(P.q_pos0 + q_idx) * (hd / 2);
 #pragma unroll
         for (int d = 0; d < C::NDB; ++d) {
             const int d0 = d * 16 + g * 4;
-            if (d0 < HD) {
+            if (d0 < hd) {
                 float v[4] = {dq[d][0], dq[d][1], dq[d][2], dq[d][3]};
                 unrope(v[0], v[1], rope[d0 >> 1]);
                 unrope(v[2], v[3], rope[(d0 >> 1) + 1]);
@@ -285,31 +306,32 @@ __device__ __forceinline__ void attn_bwd_dq_tile(const SeaAttnBwdParams& P, char
     }
 }
 
-template <typename T, int HD, bool DROP>
+template <typename T, int HD, bool DROP, bool MASKED = false>
 __global__ __launch_bounds__(256, (attn_bwd_min_waves<T, HD>())) void attn_bwd_dq_kernel(const SeaAttnBwdParams P, const int mode) {
     using C = BwdCfg<T, HD>;
     __shared__ __attribute__((aligned(16))) char smem[C::NBUF * 2 * C::TILE];  // NBUF buffers x (K tile, V tile)
     int tile_, bh, zp;
     decode_attn_block_bwd(tile_, bh, zp, mode);
     const int n_qt = (P.Tq + 63) / 64;
-    attn_bwd_dq_tile<T, HD, DROP>(P, smem, n_qt - 1 - tile_, bh, zp);  // heaviest query tiles first
+    attn_bwd_dq_tile<T, HD, DROP, MASKED>(P, smem, n_qt - 1 - tile_, bh, zp);  // heaviest query tiles first
     // ATTNB_PAIRED (grid.x = ceil(n_qt / 2)): then the light partner (every wave has passed the tile loop's last barrier: the buffers are free)
-    if ((mode & ATTNB_PAIRED) && tile_ != n_qt - 1 - tile_) attn_bwd_dq_tile<T, HD, DROP>(P, smem, tile_, bh, zp);
+    if ((mode & ATTNB_PAIRED) && tile_ != n_qt - 1 - tile_) attn_bwd_dq_tile<T, HD, DROP, MASKED>(P, smem, tile_, bh, zp);
 }
 
 // ---------------------------------------------------------------------------------------------- dK, dV
-template <typename T, int HD, bool DROP>
+template <typename T, int HD, bool DROP, bool MASKED>
 __device__ __forceinline__ void attn_bwd_dkv_tile(const SeaAttnBwdParams& P, char* smem, const int kb, const int bh, const int zp) {
     using C = BwdCfg<T, HD>;
+    const int hd = MASKED ? P.hd : HD;   // the real head dim (a multiple of 8, <= HD)
     constexpr int VEC_OFF = C::NBUF * 2 * C::TILE;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, g = lane >> 4;
     const int b = bh / P.H, h = bh - b * P.H;
     const SeaAttnBwdProblem& pr = P.p[zp];
     const int Tq = P.Tq, Tk = P.Tk;
-    const T* Qg = static_cast<const T*>(pr.Q) + (int64_t)bh * Tq * HD;
-    const T* Kg = static_cast<const T*>(pr.K) + (int64_t)bh * P.cap * HD;
-    const T* Vg = static_cast<const T*>(pr.V) + (int64_t)bh * P.cap * HD;
-    const T* dOg = static_cast<const T*>(pr.dO) + (int64_t)b * Tq * P.lddo + h * HD;
+    const T* Qg = static_cast<const T*>(pr.Q) + (int64_t)bh * Tq * hd;
+    const T* Kg = static_cast<const T*>(pr.K) + (int64_t)bh * P.cap * hd;
+    const T* Vg = static_cast<const T*>(pr.V) + (int64_t)bh * P.cap * hd;
+    const T* dOg = static_cast<const T*>(pr.dO) + (int64_t)b * Tq * P.lddo + h * hd;
     const float* lse_g = pr.LSE + (int64_t)bh * Tq;
     const float* del_g = pr.delta + (int64_t)bh * Tq;
     const int k_row0 = kb * 64 + wave * 16, k_idx = k_row0 + r, k_ld = k_idx < Tk ? k_idx : Tk - 1;
@@ -320,8 +342,15 @@ __device__ __forceinline__ void attn_bwd_dkv_tile(const SeaAttnBwdParams& P, cha
 #pragma unroll
     for (int c = 0; c < C::NCH; ++c) {
         const int d0 = c * C::CK + g * C::EPC;
-        kf[c] = d0 < HD ? *reinterpret_cast<const uint4*>(Kg + (int64_t)k_ld * HD + d0) : make_uint4(0, 0, 0, 0);
-        vf[c] = d0 < HD ? *reinterpret_cast<const uint4*>(Vg + (int64_t)k_ld * HD + d0) : make_uint4(0, 0, 0, 0);
+        if constexpr (MASKED) {   // clamped address, then a select: the branch form makes hipcc (ROCm 7.2) crash on the f32 head dim 256 kernel
+            const int dc = d0 < hd ? d0 : hd - C::EPC;
+            kf[c] = *reinterpret_cast<const uint4*>(Kg + (int64_t)k_ld * hd + dc);
+            vf[c] = *reinterpret_cast<const uint4*>(Vg + (int64_t)k_ld * hd + dc);
+            if (d0 >= hd) kf[c] = vf[c] = make_uint4(0, 0, 0, 0);
+        } else {
+            kf[c] = d0 < HD ? *reinterpret_cast<const uint4*>(Kg + (int64_t)k_ld * HD + d0) : make_uint4(0, 0, 0, 0);
+            vf[c] = d0 < HD ? *reinterpret_cast<const uint4*>(Vg + (int64_t)k_ld * HD + d0) : make_uint4(0, 0, 0, 0);
+        }
     }
     f32x4 dk[C::NDB], dv[C::NDB];
 #pragma unroll
@@ -395,7 +424,7 @@ __device__ __forceinline__ void attn_bwd_dkv_tile(const SeaAttnBwdParams& P, cha
         }
     };
 
-    TileStager<T, HD> stQ, stO;
+    TileStager<T, HD, MASKED> stQ(hd), stO(hd);
     float r_lse = 0.f, r_del = 0.f;
     auto load_vec = [&](int qt) {
         if (tid < 64) {
@@ -412,8 +441,9 @@ __device__ __forceinline__ void attn_bwd_dkv_tile(const SeaAttnBwdParams& P, cha
         }
     };
     zero_tile_padding<T, HD>(smem, 2 * C::NBUF, tid);
+    if constexpr (MASKED) zero_tile_padding_masked<T, HD>(smem, 2 * C::NBUF, tid, hd);
     if (qt0 < n_qt) {
-        stQ.load(Qg, HD, qt0 * 64, Tq, tid);
+        stQ.load(Qg, hd, qt0 * 64, Tq, tid);
         stO.load(dOg, P.lddo, qt0 * 64, Tq, tid);
         load_vec(qt0);
         stQ.store(smem, tid);
@@ -429,7 +459,7 @@ __device__ __forceinline__ void attn_bwd_dkv_tile(const SeaAttnBwdParams& P, cha
         const float* sL = reinterpret_cast<const float*>(smem + VEC_OFF) + bi * 128;
         const bool more = qt + 1 < n_qt;
         if (more && C::NBUF == 2) {
-            stQ.load(Qg, HD, (qt + 1) * 64, Tq, tid);
+            stQ.load(Qg, hd, (qt + 1) * 64, Tq, tid);
             stO.load(dOg, P.lddo, (qt + 1) * 64, Tq, tid);
             load_vec(qt + 1);
         }
@@ -443,7 +473,7 @@ __device__ __forceinline__ void attn_bwd_dkv_tile(const SeaAttnBwdParams& P, cha
             // (this form also loads the next pair only now: with dK, dV and the K / V fragments of a 256-wide f32 head in registers there is no room
             // for two tiles in flight — it is the parity path of the shipped multiphase width, not a fast one)
             if (more) {
-                stQ.load(Qg, HD, (qt + 1) * 64, Tq, tid);
+                stQ.load(Qg, hd, (qt + 1) * 64, Tq, tid);
                 stO.load(dOg, P.lddo, (qt + 1) * 64, Tq, tid);
                 load_vec(qt + 1);
             }
@@ -457,13 +487,13 @@ __device__ __forceinline__ void attn_bwd_dkv_tile(const SeaAttnBwdParams& P, cha
         __syncthreads();
     }
     if (k_idx < Tk) {
-        T* outk = static_cast<T*>(pr.dK) + ((int64_t)b * Tk + k_idx) * P.lddk + h * HD;
-        T* outv = static_cast<T*>(pr.dV) + ((int64_t)b * Tk + k_idx) * P.lddv + h * HD;
-        const float2* rope = reinterpret_cast<const float2*>(P.rope) + (int64_t)k_idx * (HD / 2);
+        T* outk = static_cast<T*>(pr.dK) + ((int64_t)b * Tk + k_idx) * P.lddk + h * hd;
+        T* outv = static_cast<T*>(pr.dV) + ((int64_t)b * Tk + k_idx) * P.lddv + h * hd;
+        const float2* rope = reinterpret_cast<const float2*>(P.rope) + (int64_t)k_idx * (hd / 2);
 #pragma unroll
         for (int d = 0; d < C::NDB; ++d) {
             const int d0 = d * 16 + g * 4;
-            if (d0 < HD) {
+            if (d0 < hd) {
                 float v[4] = {dk[d][0], dk[d][1], dk[d][2], dk[d][3]};
                 unrope(v[0], v[1], rope[d0 >> 1]);
                 unrope(v[2], v[3], rope[(d0 >> 1) + 1]);
@@ -474,22 +504,22 @@ __device__ __forceinline__ void attn_bwd_dkv_tile(const SeaAttnBwdParams& P, cha
     }
 }
 
-template <typename T, int HD, bool DROP>
+template <typename T, int HD, bool DROP, bool MASKED = false>
 __global__ __launch_bounds__(256, (attn_bwd_min_waves<T, HD>())) void attn_bwd_dkv_kernel(const SeaAttnBwdParams P, const int mode) {
     using C = BwdCfg<T, HD>;
     constexpr int VEC_OFF = C::NBUF * 2 * C::TILE;
     __shared__ __attribute__((aligned(16))) char smem[VEC_OFF + 2 * 2 * 64 * 4];  // NBUF x (Q tile, dO tile) + 2 x (lse, delta)
     int kb, bh, zp;  // key tile: the first key tiles are seen by the most queries -> ascending order is heaviest-first
     decode_attn_block_bwd(kb, bh, zp, mode);
-    attn_bwd_dkv_tile<T, HD, DROP>(P, smem, kb, bh, zp);
+    attn_bwd_dkv_tile<T, HD, DROP, MASKED>(P, smem, kb, bh, zp);
     if (mode & ATTNB_PAIRED) {   // grid.x = ceil(n_kt / 2): then the light partner tile
         const int n_kt = (P.Tk + 63) / 64;
         __syncthreads();         // (a tile with no visible query tile never enters the loop and its barriers)
-        if (kb != n_kt - 1 - kb) attn_bwd_dkv_tile<T, HD, DROP>(P, smem, n_kt - 1 - kb, bh, zp);
+        if (kb != n_kt - 1 - kb) attn_bwd_dkv_tile<T, HD, DROP, MASKED>(P, smem, n_kt - 1 - kb, bh, zp);
     }
 }
 
-template <typename T, int HD>
+template <typename T, int HD, bool MASKED = false>
 static void launch_bwd(const SeaAttnBwdParams& P, hipStream_t s) {
     const dim3 block(256), gq((P.Tq + 63) / 64, P.B * P.H, P.n_problems), gk((P.Tk + 63) / 64, P.B * P.H, P.n_problems);
     // paired tiles + XCD-local pair-major order for launches of at least 4096 workgroups at head dims >= 32 (SEA_TUNE=attnb_mode=0..3 forces the mode bits).
@@ -504,11 +534,11 @@ static void launch_bwd(const SeaAttnBwdParams& P, hipStream_t s) {
     if (mq & ATTNB_PAIRED) gq2.x = (gq.x + 1) / 2;
     if (mk & ATTNB_PAIRED) gk2.x = (gk.x + 1) / 2;
     if (P.drop.thr > 0) {
-        attn_bwd_dq_kernel<T, HD, true><<<gq2, block, pad, s>>>(P, mq);
-        attn_bwd_dkv_kernel<T, HD, true><<<gk2, block, pad, s>>>(P, mk);
+        attn_bwd_dq_kernel<T, HD, true, MASKED><<<gq2, block, pad, s>>>(P, mq);
+        attn_bwd_dkv_kernel<T, HD, true, MASKED><<<gk2, block, pad, s>>>(P, mk);
     } else {
-        attn_bwd_dq_kernel<T, HD, false><<<gq2, block, pad, s>>>(P, mq);
-        attn_bwd_dkv_kernel<T, HD, false><<<gk2, block, pad, s>>>(P, mk);
+        attn_bwd_dq_kernel<T, HD, false, MASKED><<<gq2, block, pad, s>>>(P, mq);
+        attn_bwd_dkv_kernel<T, HD, false, MASKED><<<gk2, block, pad, s>>>(P, mk);
     }
 }
 
@@ -521,7 +551,18 @@ static int dispatch_bwd(const SeaAttnBwdParams& P, hipStream_t s) {
         case 64: launch_bwd<T, 64>(P, s); break;
         case 128: launch_bwd<T, 128>(P, s); break;
         case 256: launch_bwd<T, 256>(P, s); break;   // the shipped multiphase dims (embed_dim 2048 / 8 heads); f32: one LDS buffer pair (BwdCfg::NBUF)
-        default: return -1;
+        default:   // masked widths: compute width round_up(hd, 32)
+            switch ((P.hd + 31) & ~31) {
+                case 32: launch_bwd<T, 32, true>(P, s); break;
+                case 64: launch_bwd<T, 64, true>(P, s); break;
+                case 96: launch_bwd<T, 96, true>(P, s); break;
+                case 128: launch_bwd<T, 128, true>(P, s); break;
+                case 160: launch_bwd<T, 160, true>(P, s); break;
+                case 192: launch_bwd<T, 192, true>(P, s); break;
+                case 224: launch_bwd<T, 224, true>(P, s); break;
+                case 256: launch_bwd<T, 256, true>(P, s); break;
+                default: return -1;
+            }
     }
     return 0;
 }
@@ -533,7 +574,7 @@ extern "C" int sea_attention_bwd(const SeaAttnBwdParams* params, int dtype, void
     SEA_REQUIRE(P.n_problems >= 1 && P.n_problems <= SEA_MAX_ATTN_PROBLEMS, "sea_attention_bwd: n_problems=%d", P.n_problems);
     SEA_REQUIRE(P.B >= 1 && P.H >= 1 && P.Tq >= 1 && P.Tk >= 1 && P.cap >= P.Tk && P.q_pos0 >= 0 && P.src_len >= 0 && P.rope,
                 "sea_attention_bwd: bad sizes B=%d H=%d Tq=%d Tk=%d cap=%d", P.B, P.H, P.Tq, P.Tk, P.cap);
-    SEA_REQUIRE(P.hd == 8 || P.hd == 16 || P.hd == 32 || P.hd == 64 || P.hd == 128 || P.hd == 256, "sea_attention_bwd: unsupported head dim %d (8 .. 256, powers of two)", P.hd);
+    SEA_REQUIRE(P.hd >= 8 && P.hd <= 256 && P.hd % 8 == 0, "sea_attention_bwd: unsupported head dim %d (a multiple of 8 in 8 .. 256)", P.hd);
     const int epc = dtype == SEA_BF16 ? 8 : 4;
     SEA_REQUIRE(P.ldo % epc == 0 && P.lddo % epc == 0 && P.lddq % 4 == 0 && P.lddk % 4 == 0 && P.lddv % 4 == 0, "sea_attention_bwd: bad strides");
     SEA_REQUIRE((long)P.B * P.H <= 65535, "sea_attention_bwd: B*H too large for grid.y");

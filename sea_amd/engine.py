@@ -1501,8 +1501,8 @@ class TemporalEngine:
                                       "reference's own forward fails: its attention modules are built for rows that are already widened, models/temporal.py:48,74-76,126-139)")
         E, H, D = m.internal_embed_dim, m.n_heads, m.down_dim
         for hd, what in ((E // H, "self"),) + (((D // H, "cross"),) if m.exchange_mode in ("sea", "pool") else ()):
-            if hd not in (8, 16, 32, 64, 128, 256) or hd * H != (E if what == "self" else D):
-                raise NotImplementedError(f"sea_amd: unsupported {what}-attention head dim {hd} (supported: 8, 16, 32, 64, 128, 256)")
+            if hd % 8 or not 8 <= hd <= 256 or hd * H != (E if what == "self" else D):   # (the attention kernels' set: sea_attention_fwd / _bwd)
+                raise NotImplementedError(f"sea_amd: unsupported {what}-attention head dim {(E if what == 'self' else D) / H:g} (supported: multiples of 8 from 8 to 256)")
         if m.src_len < 0:
             raise NotImplementedError("sea_amd: src_len must be >= 0")
         if self.ib_mode == 0 and m.ib_hidden > 64:
