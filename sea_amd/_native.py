@@ -379,6 +379,17 @@ def require_gpu(t: torch.Tensor, name: str = "tensor") -> None:
             "(no CPU fallback — the CPU oracle lives under oracle/ for tests only)")
 
 
+def require_same_operand(out: torch.Tensor, target: torch.Tensor, what: str, f32: bool = False) -> None:
+    """A loss reads `out.numel()` elements of the target through its raw pointer: refuse, before any launch, a target of another shape or
+    device, or (f32=True: the caller converts nothing) of a dtype other than float32."""
+    if target.shape != out.shape:
+        raise ValueError(f"sea_amd: {what}: target shape {tuple(target.shape)} does not match output shape {tuple(out.shape)}")
+    if target.device != out.device:
+        raise ValueError(f"sea_amd: {what}: target is on {target.device}, output on {out.device}")
+    if f32 and target.dtype != torch.float32:
+        raise ValueError(f"sea_amd: {what}: target dtype {target.dtype} must be torch.float32 (output shape {tuple(out.shape)})")
+
+
 def stream_ptr() -> int:
     return torch.cuda.current_stream().cuda_stream
 

@@ -43,6 +43,7 @@ class MSELossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, output, target):
         N.require_gpu(output, "output")
+        N.require_same_operand(output, target, "SeaMSELoss")
         out = output.contiguous().float()
         tgt = target.contiguous().float()
         dout = torch.empty_like(out)

@@ -36,6 +36,7 @@ int sea_cu_count();   // CUs of the current device (core.hip)
     } while (0)
 
 static inline bool sea_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+static inline bool sea_aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 
 // ------------------------------------------------------------------------------------------------ dtype traits
 // One "fragment" is 16 bytes per lane along the contraction dimension: 8 bf16 or 4 f32.

@@ -1655,7 +1655,8 @@ class TemporalEngine:
         self.grads_dirty = True
 
     def mse_loss_and_grad(self, out: torch.Tensor, target: torch.Tensor, grad_scale: float = 1.0):
-        """loss = mean((out - target)^2) and dout = grad_scale * d loss / d out in one kernel pass."""
+        """loss = mean((out - target)^2) and dout = grad_scale * d loss / d out in one kernel pass.  `target`: out's shape, float32."""
+        N.require_same_operand(out, target, "mse_loss_and_grad", f32=True)
         if self._loss_ws is None or self._loss_ws[0].numel() != out.numel():
             self._loss_ws = (torch.empty_like(out), torch.zeros(1, device=self.device), torch.empty(1024, device=self.device))
         dout, loss, partial = self._loss_ws

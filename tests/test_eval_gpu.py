@@ -15,7 +15,8 @@ from tests.test_model_gpu import build, gpu
 pytestmark = pytest.mark.gpu
 
 
-def _eval_setup(tmp_path, dtype="fp32"):
+def _eval_setup(tmp_path, dtype="fp32", n_points=None):
+    """n_points: keep only the first n_points mesh points of the fixture (a ragged mesh; the fixture's own z / enc then no longer apply)."""
     from sea_amd.utils.data_processors import MeshProcessor, ProcessData, TemporalDataset
     from sea_amd.utils.train_utils import transform_processed_data
 
@@ -36,10 +37,13 @@ def _eval_setup(tmp_path, dtype="fp32"):
                   k=None, pad_id=-1, pad_field_value=0, MLP_hidden_spatial=hidden, num_layers_spatial=layers, embed_dim_spatial=D, n_heads_spatial=Hs,
                   block_size_spatial=64, dropout_spatial=0.0, variational_spatial=False, src_len_spatial=0, encoder_decoder_path=sd, spatial_batch_size=1000,
                   random_seed=42, SEA_isolate=True, SEA_mixed=False, case_name="synth", run_name="fixture", dtype_spatial=dtype)
-    fields = gpu(g["fields"])                                                      # [tr, T+1, N, F]
-    mp_ = MeshProcessor(config, gpu(g["xy"]))
+    fields, xy = gpu(g["fields"]), gpu(g["xy"])                                   # [tr, T+1, N, F], [2, N]
+    if n_points is not None:
+        fields, xy = fields[:, :, :n_points].contiguous(), xy[:, :n_points].contiguous()
+    mp_ = MeshProcessor(config, xy)
     _, scaled = mp_.patchify_and_scale(fields.reshape(tr * (T + 1), fields.shape[2], fields.shape[3]), train_indices=np.arange(1))
-    assert scaled.shape[2] == n_inp and torch.equal(scaled.cpu(), torch.from_numpy(g["scaled"]))   # no scaling in the shipped configs: a pure gather
+    if n_points is None:
+        assert scaled.shape[2] == n_inp and torch.equal(scaled.cpu(), torch.from_numpy(g["scaled"]))   # no scaling in the shipped configs: a pure gather
     proc = ProcessData(n_inp, config)
     z = proc.initialize_and_process_data(scaled.permute(0, 1, 3, 2).contiguous())
     P = (m_ - 1) * (n_ - 1)
@@ -80,6 +84,30 @@ def test_temporal_test_verb_bf16_within_stated_tolerance(tmp_path):
     res = full_autoregressive_evaluation(model, loader, SeaMSELoss(), torch.device("cuda"), proc, mp_, config, 0, plot_traj=False)
     assert abs(res["encoded_rel_mse"] - float(g["encoded_rel_mse"])) < 0.1 * float(g["encoded_rel_mse"])
     assert abs(res["decoded_rel_mse"] - float(g["decoded_rel_mse"])) < 0.1 * float(g["decoded_rel_mse"])
+
+
+@pytest.mark.parametrize("n_points", [417, 418, 419])
+def test_temporal_test_verb_on_ragged_mesh(tmp_path, n_points):
+    """A mesh whose point count is not a multiple of 4: the evaluation takes relativeMSE over the points (dim=2) of the decoded fields.  It returns
+    finite numbers, and decoded_rel_mse is the fp64 formula applied to the same decoded fields, taken from the mesh processor outside the loop."""
+    from oracle.sea_oracle import relative_mse
+    from sea_amd.utils.train_utils import SeaMSELoss, full_autoregressive_evaluation, inverse_transform_processed_data, rollout
+
+    g, config, mp_, proc, z, enc, loader = _eval_setup(tmp_path, n_points=n_points)
+    model = build(cfg_from_meta(g["cfg"]), "fp32")
+    config["rollout_mode"] = model.rollout_mode = "kv"
+    res = full_autoregressive_evaluation(model, loader, SeaMSELoss(), torch.device("cuda"), proc, mp_, config, 0, plot_traj=False)
+    assert np.isfinite(res["encoded_rel_mse"]) and np.isfinite(res["decoded_rel_mse"])
+    data, target, original, ib = loader[0]
+    tr, T = target.shape[0], target.shape[1]
+    with torch.no_grad():
+        pred = rollout(model, data[:, 0:1].contiguous(), ib, T, mode="kv")
+        zz = inverse_transform_processed_data(pred, tr, T, (config["m"] - 1) * (config["n"] - 1), len(config["field_groups"]))
+        fields = mp_.decode_and_unpatch(proc.decoder(), zz)
+    fields = fields.reshape(tr, T, fields.shape[1], fields.shape[2])
+    assert fields.shape[2] == n_points
+    want = float(relative_mse(fields.double(), original.double(), dim=2).mean(dim=0).mean())
+    assert abs(res["decoded_rel_mse"] - want) <= 1e-5 * want, (res["decoded_rel_mse"], want)
 
 
 @pytest.mark.parametrize("name", ["rollout8_adaln_f3", "rollout100_ln_f2"])

@@ -1241,6 +1241,40 @@ def test_convert():
     assert torch.equal(dst, src[:, 64:128].to(torch.bfloat16))
 
 
+def test_convert_bf16_rounding_ties_specials_and_grid_stride():
+    """fp32 -> bf16 bitwise equal to torch's round-to-nearest-even: ties with even and odd upper halves, +-0, +-inf, values at and past the bf16
+    maximum; a NaN stays a NaN.  Subnormal inputs become a zero of their sign: the library is built with fp32 denormals flushed (build.py FLAGS),
+    where torch keeps them as bf16 subnormals.  A strided source of rows * cols / 4 > 2048 * 256 items, so the grid-stride loop runs."""
+    from sea_amd import ops
+
+    rows, cols = 300_000, 8
+    g = torch.Generator(device="cpu")
+    g.manual_seed(181)
+    bits = torch.randint(-(1 << 31), (1 << 31) - 1, (rows * cols,), generator=g, dtype=torch.int64).to(torch.int32)
+    ties = (torch.randint(0, 1 << 16, (rows * cols // 2,), generator=g, dtype=torch.int32) << 16) | 0x8000
+    bits[0::2] = ties
+    special = torch.tensor([0x00000000, 0x80000000, 0x7F800000, 0xFF800000, 0x7FC00000, 0xFFC00000, 0x7F800001,
+                            0x00000001, 0x80000001, 0x00008000, 0x00018000, 0x007FFFFF, 0x807FFFFF, 0x00400000,
+                            0x7F7F0000, 0x7F7F7FFF, 0x7F7F8000, 0x7F7FFFFF, 0xFF7F8000, 0x3F808000, 0x3F818000, 0x3F80FFFF], dtype=torch.int64).to(torch.int32)
+    bits[1:2 * special.numel():2] = special
+    vals = bits.view(torch.float32).reshape(rows, cols)
+    src = torch.full((rows, 16), 7.0)
+    src[:, 4:12] = vals
+    src = src.to(dev())[:, 4:12]                                # lds = 16, 16 bytes in
+    dst = torch.zeros(rows, cols, device=dev(), dtype=torch.bfloat16)
+    ops.convert(src, dst)
+    want = src.to(torch.bfloat16)
+    sub = (src != 0) & (src.abs() < torch.finfo(torch.float32).tiny)
+    want[sub] = torch.where(torch.signbit(src[sub]), -0.0, 0.0).to(torch.bfloat16)
+    assert int(sub.sum()) >= 6
+    nan = torch.isnan(want)
+    assert torch.equal(torch.isnan(dst), nan)                  # NaN payload and sign are not compared: torch writes the canonical +NaN
+    got_bits, want_bits = dst.view(torch.int16), want.view(torch.int16)
+    bad = (got_bits != want_bits) & ~nan
+    assert not bad.any(), [(hex(int(b) & 0xFFFFFFFF), hex(int(x) & 0xFFFF), hex(int(y) & 0xFFFF))
+                           for b, x, y in zip(bits.reshape(rows, cols)[bad.cpu()][:8], got_bits[bad][:8], want_bits[bad][:8])]
+
+
 def test_bad_arguments_raise():
     from sea_amd import ops
 
