@@ -571,6 +571,25 @@ typedef struct {
 int sea_ib_bwd(const SeaIbBwdParams* params, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Condition gradients (the gradient of the loss with respect to the per-row condition c [M], fp32).  Both ADD into dc; neither uses a float atomic
+ * on dc: per-workgroup partials and a fixed-order finish (AdaLN), one wave per row with a fixed-order wave sum (information bottleneck), so dc is
+ * bitwise repeatable whenever its operands are.  (Of the operands a training plan passes in, dhid of sea_ib_bwd's column-block form is accumulated
+ * atomically when E > 256 — it feeds the PARAMETER gradients only; sea_ib_bwd_dc recomputes d hidden itself.)
+ *
+ * sea_silu_outer_bwd_dc: sea_silu_outer_bwd (the same dw1 / db1) plus dc[m] += sum_groups sum_j dpre[m, j] w1[j], from the same single read of dHid.
+ *   ws: >= sea_silu_outer_bwd_dc_ws_floats(groups, n_groups, M) floats = ncb * M (dc partials, ncb = sum_groups ceil(K2 / 256)) + n_groups * 2 * max K2
+ *   (column-sum partials of one row split; more row splits run when more is given).  Limits as sea_silu_outer_bwd: K2 <= 2048, SEA_MAX_SILU_BWD_GROUPS.
+ * sea_ib_bwd_dc: dc[m] += d(loss)/d(c[m]) through the layer of params->mode, from dib = sum_f dX_f (mode 0: with the forward's dropout masks):
+ *   mode 0 'mlp' (h <= 64): back through W2, GELU and LN_h, dc += sum_k dpre[m, k] w1[k];  mode 1 'linear': dc += sum_e w1[e] dib[m, e];
+ *   mode 2 'fourier': dc += 2 pi sum_e W[e] (cos theta_e dib[m, e] - sin theta_e dib[m, E/2 + e]), theta_e = 2 pi c W[e] in fp32 as the forward forms it.
+ *   With params->dw1 set (modes 0 / 1) the same call first produces the parameter gradients exactly as sea_ib_bwd does (mode 2 has none: dw1 must be NULL).
+ * Bad sizes or pointers return -1 before anything is launched. */
+int64_t sea_silu_outer_bwd_dc_ws_floats(const SeaSiluBwdGroup* groups, int n_groups, int M);
+int sea_silu_outer_bwd_dc(const SeaSiluBwdGroup* groups, int n_groups, const float* c, float* dc, int M, int dtype, float* ws, int64_t ws_floats,
+                          void* stream);
+int sea_ib_bwd_dc(const SeaIbBwdParams* params, float* dc, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * AdaLN whose modulation never reaches memory (bf16 compute): the normalisation is the epilogue of cond_mlp.2's GEMM.
  *     [w | b] = A[M, K] . W[2d, K]^T + bias            A = silu(cond_mlp.0(c)) rows (sea_silu_outer), W = cond_mlp.2.weight (scale rows 0..d-1, shift rows d..2d-1)
  *     y       = xhat * (gamma + 1 + w) + (beta + b),   xhat = (X - mean) / sqrt(var_biased + eps) over the d columns of a row of X

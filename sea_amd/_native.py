@@ -282,6 +282,10 @@ def lib() -> C.CDLL:
     L.sea_rownorm_bwd.argtypes = [C.POINTER(SeaNormBwdGroup), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _i64, _vp]
     L.sea_silu_outer_bwd.argtypes = [C.POINTER(SeaSiluBwdGroup), C.c_int, _vp, C.c_int, C.c_int, _vp, _i64, _vp]
     L.sea_ib_bwd.argtypes = [C.POINTER(SeaIbBwdParams), _vp]
+    L.sea_silu_outer_bwd_dc.argtypes = [C.POINTER(SeaSiluBwdGroup), C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, _i64, _vp]
+    L.sea_silu_outer_bwd_dc_ws_floats.argtypes = [C.POINTER(SeaSiluBwdGroup), C.c_int, C.c_int]
+    L.sea_silu_outer_bwd_dc_ws_floats.restype = _i64
+    L.sea_ib_bwd_dc.argtypes = [C.POINTER(SeaIbBwdParams), _vp, _vp]
     L.sea_attention_bwd.argtypes = [C.POINTER(SeaAttnBwdParams), C.c_int, _vp]
     L.sea_dropout_mask.argtypes = [_vp, _i64, _i64, C.c_uint32, C.c_uint32, _i32, _vp]
     L.sea_dropout_mask.restype = C.c_int
@@ -327,7 +331,8 @@ def lib() -> C.CDLL:
     L.sea_kv_arena_words.restype = C.c_int64
     L.sea_kv_debug_stamps.argtypes = [_vp]
     L.sea_kv_debug_stamps.restype = None
-    for name in ("sea_attention_bwd", "sea_wgrad_grouped", "sea_transpose_weights", "sea_rownorm_bwd", "sea_silu_outer_bwd", "sea_ib_bwd"):
+    for name in ("sea_attention_bwd", "sea_wgrad_grouped", "sea_transpose_weights", "sea_rownorm_bwd", "sea_silu_outer_bwd", "sea_ib_bwd",
+                 "sea_silu_outer_bwd_dc", "sea_ib_bwd_dc"):
         getattr(L, name).restype = C.c_int
     L.sea_mse_fwd_bwd.argtypes = [_vp, _vp, _vp, _vp, _vp, C.c_int, _i64, C.c_float, _vp]
     L.sea_relative_mse.argtypes = [_vp, _vp, _vp, _i64, C.c_int, _vp]
@@ -355,6 +360,7 @@ EXPORTED_SYMBOLS = (
     "sea_attention_bwd", "sea_dropout_mask", "sea_run_list", "sea_run_list_steps", "sea_unpatchify", "sea_gemm_rownorm", "sea_exchange_tail", "sea_patchify", "sea_silu_outer_ib", "sea_mlp_fc1_ln_gelu", "sea_mlp_fc2_proj_norm", "sea_kv_rollout", "sea_kv_arena_words", "sea_kv_debug_stamps",
     "sea_gemm_fewrows", "sea_qkv_rope_fewrows", "sea_row_chain", "sea_row_chain_riders", "sea_gemm_adaln", "sea_mlp_block", "sea_adaln_qkv", "sea_splitk_finish",
     "sea_encoder_block_ws_floats", "sea_encoder_block_fwd", "sea_encoder_block_bwd",
+    "sea_silu_outer_bwd_dc", "sea_silu_outer_bwd_dc_ws_floats", "sea_ib_bwd_dc",
 )
 
 

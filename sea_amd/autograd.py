@@ -10,9 +10,14 @@ from . import _native as N
 class _TemporalFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, anchor, x, ib, model, eng):
-        out, plan = eng.forward_train(x, ib)
+        # input gradients are produced by launches of their own (a training plan of its own per (want_dx, want_dc)): only what autograd will ask for
+        want_dx, want_dc = bool(ctx.needs_input_grad[1]), bool(ctx.needs_input_grad[2])
+        if want_dc and ib.numel() != x.shape[0] * x.shape[1]:
+            raise ValueError(f"sea_amd: the condition gradient needs one condition value per row (B * T = {x.shape[0] * x.shape[1]}), got shape {tuple(ib.shape)}")
+        out, plan = eng.forward_train(x, ib, want_dx, want_dc)
         ctx.plan, ctx.eng, ctx.model = plan, eng, model
         ctx.generation = plan.generation   # the saved activations live in the plan's workspace: a later forward of the same shape replaces them
+        ctx.want, ctx.x_shape, ctx.ib_shape = (want_dx, want_dc), x.shape, ib.shape
         return out
 
     @staticmethod
@@ -23,14 +28,30 @@ class _TemporalFn(torch.autograd.Function):
                                "same shape (one activation set per (batch, length) is kept): run backward() before the next forward, or run the other "
                                "forward under torch.no_grad()")
         live = model._live_params()
-        # torch semantics: gradients accumulate until zero_grad().  A step that starts from p.grad is None starts from zero.
-        if eng.grads_dirty and live and live[0].grad is None:
+        frozen = not any(p.requires_grad for p in model.parameters())
+        saved = None
+        if frozen:
+            # only the inputs want gradients: the launch list still accumulates parameter gradients into the engine's buffer, so .grad views already
+            # attached to it keep their values (restored below), and no .grad is attached.  A buffer left holding them unattached is zeroed by the next
+            # step that attaches (grads_dirty, below).
+            if live and live[0].grad is not None:
+                saved = (eng.grads.clone(), eng.grads_dirty)
+        elif eng.grads_dirty and live and live[0].grad is None:
+            # torch semantics: gradients accumulate until zero_grad().  A step that starts from p.grad is None starts from zero.
             eng.zero_grads()
-        eng.backward(ctx.plan, dout.contiguous().float())
-        for name, p in zip(eng.params.live_names, live):
-            if p.grad is None:
-                p.grad = eng.grad_view(name)
-        return None, None, None, None, None
+        want_dx, want_dc = ctx.want
+        dev = dout.device
+        dx = torch.empty(ctx.x_shape, device=dev, dtype=torch.float32) if want_dx else None
+        dc = torch.zeros(ctx.plan.M, device=dev, dtype=torch.float32) if want_dc else None
+        eng.backward(ctx.plan, dout.contiguous().float(), dx=dx, dc=dc)
+        if saved is not None:
+            eng.grads.copy_(saved[0])
+            eng.grads_dirty = saved[1]
+        if not frozen:
+            for name, p in zip(eng.params.live_names, live):
+                if p.grad is None:
+                    p.grad = eng.grad_view(name)
+        return None, dx, (dc.view(ctx.ib_shape) if want_dc else None), None, None
 
 
 def temporal_forward_with_grad(model, eng, x, ib):

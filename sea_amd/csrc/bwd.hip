@@ -4,6 +4,8 @@
 //   sea_rownorm_bwd        backward of sea_rownorm (AdaLN / LayerNorm / LayerNorm+GELU)
 //   sea_silu_outer_bwd     backward of sea_silu_outer
 //   sea_ib_bwd             parameter gradients of the information-bottleneck MLP
+//   sea_silu_outer_bwd_dc  sea_silu_outer_bwd that also adds the condition gradient dc (AdaLN condition MLPs)
+//   sea_ib_bwd_dc          condition gradient of the information-bottleneck layer (all three ib_scale_modes), with its parameter gradients
 #include "sea_common.hpp"
 #include <stdlib.h>
 
@@ -1029,9 +1031,12 @@ struct SiluColsLaunch {
     int M, rows_per;
     float* ws;      // [n_groups][gridDim.y][2 * maxk]
     int maxk;
+    float* dcp;     // DC: [column block][M] this block's share of d(loss)/d(condition) per row (sea_silu_outer_bwd_dc)
 };
 
-template <typename T>
+// DC: each row's dc partial over the workgroup's 256 columns, sum_j dpre_j w1_j, is a wave sum of the same dpre values the column sums take — the
+// dHid rows are read once for both.  Every (column block, row) partial is stored exactly once; silu_dc_finish_kernel adds them in column-block order.
+template <typename T, bool DC>
 __global__ __launch_bounds__(256) void silu_outer_bwd_cols_kernel(const SiluColsLaunch L) {
     __shared__ float red[3][8][64];
     int gi = 0;
@@ -1059,6 +1064,7 @@ __global__ __launch_bounds__(256) void silu_outer_bwd_cols_kernel(const SiluCols
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const bool live = act && row + 4 * u < r1;
+            float sdc = 0.f;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const float pre = w[e] * cv[u] + bb[e];
@@ -1066,6 +1072,11 @@ __global__ __launch_bounds__(256) void silu_outer_bwd_cols_kernel(const SiluCols
                 const float dpre = live ? dv[u][e] * sg * (1.0f + pre * (1.0f - sg)) : 0.f;
                 aw[e] += dpre * cv[u];
                 ab[e] += dpre;
+                if constexpr (DC) sdc += dpre * w[e];
+            }
+            if constexpr (DC) {
+                sdc = wave_sum(sdc);
+                if (lane == 0 && row + 4 * u < r1) L.dcp[(int64_t)blockIdx.x * L.M + row + 4 * u] = sdc;
             }
         }
     }
@@ -1097,6 +1108,49 @@ __global__ __launch_bounds__(256) void silu_outer_bwd_cols_kernel(const SiluCols
     }
 }
 
+// The column-block form and its column-sum finish.  dcp != nullptr: the DC kernel, its per-(column block, row) partials in dcp [ncb][M].  Returns false
+// (nothing launched) when the workspace holds less than one row split.
+static bool silu_bwd_cols(const SeaSiluBwdGroup* groups, int n_groups, const float* c, int M, int dtype, float* ws, int64_t ws_floats, int maxk, float* dcp,
+                          hipStream_t s) {
+    SiluColsLaunch Q;
+    memset(&Q, 0, sizeof(Q));
+    int ncb = 0;
+    for (int i = 0; i < n_groups; ++i) {
+        Q.g[i] = groups[i];
+        Q.cb_start[i] = ncb;
+        ncb += (groups[i].K2 + 255) / 256;
+    }
+    Q.cb_start[n_groups] = ncb;
+    Q.n_groups = n_groups; Q.c = c; Q.M = M; Q.maxk = maxk; Q.dcp = dcp;
+    // row splits: about four workgroups per CU in all, at least 16 rows (one trip of a workgroup) per split, and what the workspace holds
+    int rs = (1024 + ncb - 1) / ncb;
+    const int rs_rows = (M + 15) / 16;
+    rs = rs > rs_rows ? rs_rows : rs;
+    const int64_t rs_ws = ws_floats / ((int64_t)n_groups * 2 * maxk);
+    rs = rs > rs_ws ? (int)rs_ws : rs;
+    if (rs < 1) return false;
+    Q.rows_per = (M + rs - 1) / rs;
+    rs = (M + Q.rows_per - 1) / Q.rows_per;
+    Q.ws = ws;
+    if (dcp != nullptr) {
+        if (dtype == SEA_BF16) silu_outer_bwd_cols_kernel<__bf16, true><<<dim3(ncb, rs), dim3(256), 0, s>>>(Q);
+        else silu_outer_bwd_cols_kernel<float, true><<<dim3(ncb, rs), dim3(256), 0, s>>>(Q);
+    } else {
+        if (dtype == SEA_BF16) silu_outer_bwd_cols_kernel<__bf16, false><<<dim3(ncb, rs), dim3(256), 0, s>>>(Q);
+        else silu_outer_bwd_cols_kernel<float, false><<<dim3(ncb, rs), dim3(256), 0, s>>>(Q);
+    }
+    ColsumFinish F;
+    memset(&F, 0, sizeof(F));
+    for (int i = 0; i < n_groups; ++i) {
+        F.out_a[i] = groups[i].dw1;
+        F.out_b[i] = groups[i].db1;
+        F.width[i] = groups[i].K2;
+    }
+    F.ws = ws; F.nblk = rs; F.stride = 2 * maxk;
+    colsum_finish_kernel<<<dim3((2 * maxk + 255) / 256, n_groups, rs < 16 ? rs : 16), dim3(256), 0, s>>>(F);
+    return true;
+}
+
 extern "C" int sea_silu_outer_bwd(const SeaSiluBwdGroup* groups, int n_groups, const float* c, int M, int dtype, float* ws, int64_t ws_floats,
                                   void* stream) {
     SEA_REQUIRE(groups && c && n_groups >= 1 && n_groups <= SEA_MAX_SILU_BWD_GROUPS && M >= 1, "sea_silu_outer_bwd: bad arguments");
@@ -1113,41 +1167,9 @@ extern "C" int sea_silu_outer_bwd(const SeaSiluBwdGroup* groups, int n_groups, c
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
     static const int cols_form = sea_tune("silubwd_cols", 1);   // tuning aid: 0 = the one-wave-per-row kernel
-    if (cols_form && ws != nullptr) {
-        SiluColsLaunch Q;
-        memset(&Q, 0, sizeof(Q));
-        int ncb = 0;
-        for (int i = 0; i < n_groups; ++i) {
-            Q.g[i] = groups[i];
-            Q.cb_start[i] = ncb;
-            ncb += (groups[i].K2 + 255) / 256;
-        }
-        Q.cb_start[n_groups] = ncb;
-        Q.n_groups = n_groups; Q.c = c; Q.M = M; Q.maxk = maxk;
-        // row splits: about four workgroups per CU in all, at least 16 rows (one trip of a workgroup) per split, and what the workspace holds
-        int rs = (1024 + ncb - 1) / ncb;
-        const int rs_rows = (M + 15) / 16;
-        rs = rs > rs_rows ? rs_rows : rs;
-        const int64_t rs_ws = ws_floats / ((int64_t)n_groups * 2 * maxk);
-        rs = rs > rs_ws ? (int)rs_ws : rs;
-        if (rs >= 1) {
-            Q.rows_per = (M + rs - 1) / rs;
-            rs = (M + Q.rows_per - 1) / Q.rows_per;
-            Q.ws = ws;
-            if (dtype == SEA_BF16) silu_outer_bwd_cols_kernel<__bf16><<<dim3(ncb, rs), dim3(256), 0, s>>>(Q);
-            else silu_outer_bwd_cols_kernel<float><<<dim3(ncb, rs), dim3(256), 0, s>>>(Q);
-            ColsumFinish F;
-            memset(&F, 0, sizeof(F));
-            for (int i = 0; i < n_groups; ++i) {
-                F.out_a[i] = groups[i].dw1;
-                F.out_b[i] = groups[i].db1;
-                F.width[i] = groups[i].K2;
-            }
-            F.ws = ws; F.nblk = rs; F.stride = 2 * maxk;
-            colsum_finish_kernel<<<dim3((2 * maxk + 255) / 256, n_groups, rs < 16 ? rs : 16), dim3(256), 0, s>>>(F);
-            SEA_CHECK_LAUNCH("sea_silu_outer_bwd");
-            return SEA_OK;
-        }
+    if (cols_form && ws != nullptr && silu_bwd_cols(groups, n_groups, c, M, dtype, ws, ws_floats, maxk, nullptr, s)) {
+        SEA_CHECK_LAUNCH("sea_silu_outer_bwd");
+        return SEA_OK;
     }
     L.c = c; L.M = M;
     int nblk = (M + 3) / 4;
@@ -1187,6 +1209,49 @@ extern "C" int sea_silu_outer_bwd(const SeaSiluBwdGroup* groups, int n_groups, c
         colsum_finish_kernel<<<dim3((2 * maxk + 255) / 256, n_groups, 16), dim3(256), 0, s>>>(F);
     }
     SEA_CHECK_LAUNCH("sea_silu_outer_bwd");
+    return SEA_OK;
+}
+
+// dc[m] += sum over the column blocks of dcp[cb][m], in column-block order: one thread per row, no atomics (bitwise repeatable).
+__global__ __launch_bounds__(256) void silu_dc_finish_kernel(const float* __restrict__ dcp, int ncb, int M, float* __restrict__ dc) {
+    const int m = blockIdx.x * 256 + threadIdx.x;
+    if (m >= M) return;
+    float acc = 0.f;
+    for (int cb = 0; cb < ncb; ++cb) acc += dcp[(int64_t)cb * M + m];
+    dc[m] += acc;
+}
+
+extern "C" int64_t sea_silu_outer_bwd_dc_ws_floats(const SeaSiluBwdGroup* groups, int n_groups, int M) {
+    if (!groups || n_groups < 1 || n_groups > SEA_MAX_SILU_BWD_GROUPS || M < 1) return -1;
+    int64_t ncb = 0, maxk = 0;
+    for (int i = 0; i < n_groups; ++i) {
+        ncb += (groups[i].K2 + 255) / 256;
+        maxk = groups[i].K2 > maxk ? groups[i].K2 : maxk;
+    }
+    return ncb * M + (int64_t)n_groups * 2 * maxk;
+}
+
+extern "C" int sea_silu_outer_bwd_dc(const SeaSiluBwdGroup* groups, int n_groups, const float* c, float* dc, int M, int dtype, float* ws, int64_t ws_floats,
+                                     void* stream) {
+    SEA_REQUIRE(groups && c && dc && ws && n_groups >= 1 && n_groups <= SEA_MAX_SILU_BWD_GROUPS && M >= 1, "sea_silu_outer_bwd_dc: bad arguments");
+    SEA_REQUIRE(dtype == SEA_F32 || dtype == SEA_BF16, "sea_silu_outer_bwd_dc: bad dtype %d", dtype);
+    int maxk = 0, ncb = 0;
+    for (int i = 0; i < n_groups; ++i) {
+        const SeaSiluBwdGroup& G = groups[i];
+        SEA_REQUIRE(G.dHid && G.w1 && G.b1 && G.dw1 && G.db1 && G.K2 >= 4 && G.K2 % 4 == 0 && G.K2 <= 2048 && G.ld >= G.K2 && G.ld % 4 == 0, "sea_silu_outer_bwd_dc[%d]: bad group", i);
+        SEA_REQUIRE(sea_aligned16(G.dHid) && sea_aligned16(G.w1) && sea_aligned16(G.b1), "sea_silu_outer_bwd_dc[%d]: pointers must be 16-byte aligned", i);
+        maxk = G.K2 > maxk ? G.K2 : maxk;
+        ncb += (G.K2 + 255) / 256;
+    }
+    const int64_t need = sea_silu_outer_bwd_dc_ws_floats(groups, n_groups, M);
+    SEA_REQUIRE(ws_floats >= need, "sea_silu_outer_bwd_dc: workspace of %lld floats, %lld needed", (long long)ws_floats, (long long)need);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    float* dcp = ws;   // [ncb][M] partials, then the column-sum partials
+    if (!silu_bwd_cols(groups, n_groups, c, M, dtype, ws + (int64_t)ncb * M, ws_floats - (int64_t)ncb * M, maxk, dcp, s)) {
+        SEA_REQUIRE(false, "sea_silu_outer_bwd_dc: workspace too small");
+    }
+    silu_dc_finish_kernel<<<dim3((M + 255) / 256), dim3(256), 0, s>>>(dcp, ncb, M, dc);
+    SEA_CHECK_LAUNCH("sea_silu_outer_bwd_dc");
     return SEA_OK;
 }
 
@@ -1669,5 +1734,122 @@ extern "C" int sea_ib_bwd(const SeaIbBwdParams* params, void* stream) {
     else if (P.h <= 8 && P.E <= 1024) ib_bwd_fast_kernel<4><<<dim3(nblk), dim3(256), lds, s>>>(P);
     else ib_bwd_kernel<<<dim3(nblk), dim3(256), lds, s>>>(P);
     SEA_CHECK_LAUNCH("sea_ib_bwd");
+    return SEA_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ condition gradient of the information-bottleneck layer
+// dc[m] += d(loss)/d(c[m]) through ib(c), dib = sum_f dX_f (each field's dropout mask applied as the forward drew it; mode 0 only).  One wave per row, no
+// atomics: the row's value is a fixed-order wave sum added by lane 0 (bitwise repeatable).
+//   mode 0: back through W2, GELU and LN_h to the pre-norm hidden (h <= 64: lane k holds unit k; d hidden_k in chunks of 8 dot products over the row),
+//           then dc = sum_k dpre_k w1_k
+//   mode 1: dc = sum_e w1_e dib_e
+//   mode 2: theta_e = 2 pi c W_e (fp32, as ib_simple4 forms it), dc = sum_e 2 pi W_e (cos theta_e dib_e - sin theta_e dib_{E/2 + e})
+template <int MODE>
+__global__ __launch_bounds__(256) void ib_dc_kernel(const SeaIbBwdParams P, float* __restrict__ dc) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int row = blockIdx.x * 4 + wave; row < P.M; row += 4 * gridDim.x) {
+        const float cv = P.c[row];
+        const int64_t ro = (int64_t)row * P.ldx;
+        float s = 0.f;
+        if constexpr (MODE == 1) {
+            for (int e = lane; e < P.E; e += 64) {
+                float g = 0.f;
+                for (int f = 0; f < P.n_fields; ++f) g += P.dX[f][ro + e];
+                s += P.w1[e] * g;
+            }
+        } else if constexpr (MODE == 2) {
+            const int half = P.E >> 1;
+            for (int e = lane; e < half; e += 64) {
+                float dS = 0.f, dC = 0.f;
+                for (int f = 0; f < P.n_fields; ++f) {
+                    dS += P.dX[f][ro + e];
+                    dC += P.dX[f][ro + half + e];
+                }
+                const float w = P.w1[e];
+                const float a = cv * w * 2.0f * 3.14159274101257324f;
+                s += w * (cosf(a) * dS - sinf(a) * dC);
+            }
+            s *= 2.0f * 3.14159274101257324f;
+        } else {
+            const int h = P.h, E = P.E;
+            const bool act = lane < h;
+            const float w1 = act ? P.w1[lane] : 0.f, lw = act ? P.lnw[lane] : 0.f;
+            const float pre = act ? w1 * cv + P.b1[lane] : 0.f;
+            const float mean = wave_sum(pre) / (float)h;
+            const float cen = act ? pre - mean : 0.f;
+            const float var = wave_sum(cen * cen) / (float)h;
+            const float rstd = 1.0f / sqrtf(var + 1e-5f);
+            const float xh = cen * rstd;
+            const float u = xh * lw + (act ? P.lnb[lane] : 0.f);
+            const float dsc = P.drop.thr > 0 ? drop_scale(P.drop.thr) : 1.f;
+            float dhid = 0.f;
+            for (int k0 = 0; k0 < h; k0 += 8) {
+                float part[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) part[j] = 0.f;
+                for (int e0 = lane * 4; e0 < E; e0 += 256) {
+                    float dib[4] = {0.f, 0.f, 0.f, 0.f};
+                    for (int f = 0; f < P.n_fields; ++f) {
+                        float v[4];
+                        load4(P.dX[f] + ro + e0, v);
+                        if (P.drop.thr > 0) {
+                            const uint32_t wd = drop_word(P.drop.seed, P.drop.stream + f, (uint32_t)row, (uint32_t)(e0 >> 2));
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) v[e] *= drop_factor(wd, e, P.drop.thr, dsc);
+                        }
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) dib[e] += v[e];
+                    }
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const float* w2 = P.w2 + (int64_t)(e0 + e) * h + k0;
+#pragma unroll
+                        for (int j = 0; j < 8; ++j)
+                            if (k0 + j < h) part[j] += dib[e] * w2[j];
+                    }
+                }
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const float t = wave_sum(part[j]);
+                    if (lane == k0 + j) dhid = t;
+                }
+            }
+            const float du = act ? dhid * gelu_erf_grad(u) : 0.f;
+            const float dxh = du * lw;
+            const float c1 = wave_sum(dxh) / (float)h;
+            const float c2 = wave_sum(dxh * xh) / (float)h;
+            const float dpre = act ? rstd * (dxh - c1 - xh * c2) : 0.f;
+            s = dpre * w1;
+        }
+        s = wave_sum(s);
+        if (lane == 0) dc[row] += s;
+    }
+}
+
+extern "C" int sea_ib_bwd_dc(const SeaIbBwdParams* params, float* dc, void* stream) {
+    SEA_REQUIRE(params != nullptr && dc != nullptr, "sea_ib_bwd_dc: null params or dc");
+    const SeaIbBwdParams& P = *params;
+    SEA_REQUIRE(P.mode >= 0 && P.mode <= 2, "sea_ib_bwd_dc: mode %d", P.mode);
+    SEA_REQUIRE(P.n_fields >= 1 && P.n_fields <= 8 && P.M >= 1 && P.E >= 1 && P.ldx >= P.E && P.c && P.w1, "sea_ib_bwd_dc: bad arguments");
+    for (int f = 0; f < P.n_fields; ++f) SEA_REQUIRE(P.dX[f] != nullptr, "sea_ib_bwd_dc: dX[%d] null", f);
+    if (P.mode == 0) {
+        SEA_REQUIRE(P.E >= 4 && P.E % 4 == 0 && P.ldx % 4 == 0 && P.h >= 1 && P.h <= 64 && P.b1 && P.lnw && P.lnb && P.w2, "sea_ib_bwd_dc (mlp): bad sizes / null pointer");
+        for (int f = 0; f < P.n_fields; ++f) SEA_REQUIRE(sea_aligned16(P.dX[f]), "sea_ib_bwd_dc (mlp): dX[%d] misaligned", f);
+    } else if (P.mode == 2) {
+        SEA_REQUIRE(P.E % 2 == 0 && P.dw1 == nullptr, "sea_ib_bwd_dc (fourier): E must be even; the projection is fixed (no dw1)");
+    }
+    SEA_REQUIRE(P.mode == 0 || P.drop.thr == 0, "sea_ib_bwd_dc: dropout is on the 'mlp' layer's output only");
+    const bool params_too = P.dw1 != nullptr;
+    if (params_too) {   // the parameter gradients first (their own checks refuse bad pointers before anything is launched)
+        const int rc = sea_ib_bwd(params, stream);
+        if (rc != SEA_OK) return rc;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int nblk = (P.M + 3) / 4;
+    if (nblk > 1024) nblk = 1024;
+    if (P.mode == 0) ib_dc_kernel<0><<<dim3(nblk), dim3(256), 0, s>>>(P, dc);
+    else if (P.mode == 1) ib_dc_kernel<1><<<dim3(nblk), dim3(256), 0, s>>>(P, dc);
+    else ib_dc_kernel<2><<<dim3(nblk), dim3(256), 0, s>>>(P, dc);
+    SEA_CHECK_LAUNCH("sea_ib_bwd_dc");
     return SEA_OK;
 }

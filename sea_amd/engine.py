@@ -1244,6 +1244,8 @@ class Plan:
         for t, label in zip(getattr(self, "_bound_tensors", ()) or (), ("x", "condition", "out")):
             R.add_tensor(t, "bound " + label)
         R.add_tensor(getattr(self, "_bound_dout", None), "bound dout")
+        for t in getattr(self, "_bound_input_grads", None) or ():
+            R.add_tensor(t, "bound input gradient")
         for t in (eng._loss_ws or ()):
             R.add_tensor(t, "loss workspace")
         for t in owners:
@@ -1588,7 +1590,8 @@ class TemporalEngine:
             self.grads.zero_()
         self.grads_dirty = False
 
-    def train_plan(self, B: int, T: int):
+    def train_plan(self, B: int, T: int, want_dx: bool = False, want_dc: bool = False):
+        """want_dx / want_dc: the backward also writes d loss / d x and d loss / d condition (TrainPlan.bind_input_grads); a plan of its own."""
         from .train_engine import TrainPlan
 
         m = self.model
@@ -1596,12 +1599,12 @@ class TemporalEngine:
         if thr > 255:
             raise ValueError("dropout probability too close to 1")
         dp = self.dp_overlap()
-        key = (B, T, thr, dp)
+        key = (B, T, thr, dp, bool(want_dx), bool(want_dc))
         p = self._train_plans.get(key)
         if p is None:
             if T > m.max_len:
                 raise ValueError(f"sequence length {T} exceeds max_len {m.max_len}")
-            p = TrainPlan(self, B, T, drop_thr=thr, dp=dp)
+            p = TrainPlan(self, B, T, drop_thr=thr, dp=dp, want_dx=want_dx, want_dc=want_dc)
             self._train_plans[key] = p
         return p
 
@@ -1624,14 +1627,14 @@ class TemporalEngine:
             self._dp_overlap = (world, bool(int(want.item())))
         return self._dp_overlap[1]
 
-    def forward_train(self, x: torch.Tensor, ib: torch.Tensor):
-        """Forward that keeps the activations the backward needs.  Returns (out, plan)."""
+    def forward_train(self, x: torch.Tensor, ib: torch.Tensor, want_dx: bool = False, want_dc: bool = False):
+        """Forward that keeps the activations the backward needs.  Returns (out, plan).  want_dx / want_dc: see train_plan."""
         B, T, F, E = x.shape
         x, ib = x.contiguous(), ib.contiguous()
         out = torch.empty_like(x)
         self.params.sync()
         self.params.sync_transposed()
-        p = self.train_plan(B, T)
+        p = self.train_plan(B, T, want_dx, want_dc)
         p.bind(x, ib, out)
         p.held = (x, ib)  # the backward list reads the inputs again: keep them alive until the next forward
         p.generation = getattr(p, "generation", 0) + 1   # identifies the activation set now in the plan's workspace (autograd.py checks it)
@@ -1642,14 +1645,19 @@ class TemporalEngine:
         p.run()
         return out, p
 
-    def backward(self, plan, dout: torch.Tensor, on_bucket=None) -> None:
+    def backward(self, plan, dout: torch.Tensor, on_bucket=None, dx: Optional[torch.Tensor] = None, dc: Optional[torch.Tensor] = None) -> None:
         """Accumulate d loss / d parameters into self.grads from dout = d loss / d out ([B,T,F,E] fp32, contiguous).  `on_bucket(lo, hi)`: called
-        as soon as self.grads[lo:hi] is final (TrainPlan.grad_buckets), while later launches are still being issued."""
+        as soon as self.grads[lo:hi] is final (TrainPlan.grad_buckets), while later launches are still being issued.  A plan built with want_dx /
+        want_dc also stores d loss / d x into dx ([B,T,F,E] fp32, contiguous) and ADDS d loss / d condition into dc ([B*T] fp32, zeroed by the caller)."""
         assert dout.is_contiguous() and dout.dtype == torch.float32
+        for t, shape in ((dx, dout.shape), (dc, (plan.M,))):
+            assert t is None or (t.is_contiguous() and t.dtype == torch.float32 and t.numel() == torch.Size(shape).numel() and t.device == dout.device)
         plan.bind_dout(dout.data_ptr())
+        plan.bind_input_grads(N.ptr(dx), N.ptr(dc))
         plan._bound_dout = dout          # held until the next backward: the launch list knows it by address only
+        plan._bound_input_grads = (dx, dc)
         if ptrcheck.always():
-            plan.audit(owners=(dout,))
+            plan.audit(owners=tuple(t for t in (dout, dx, dc) if t is not None))
         plan.set_grads_fresh(not self.grads_dirty)   # a backward into zeros (the usual step) lets the big weight-gradient launches store instead of add
         plan.run_backward(on_bucket)
         self.grads_dirty = True

@@ -354,7 +354,8 @@ class TemporalModel(nn.Module):
         if not x.is_cuda:
             raise RuntimeError("sea_amd.TemporalModel.forward: input is on the CPU; this path has no CPU fallback")
         eng = self.engine(x.device)
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+        # the grad path: whenever autograd has something to differentiate — a parameter, the input rows or the condition (autograd.py)
+        if torch.is_grad_enabled() and (any(p.requires_grad for p in self.parameters()) or x.requires_grad or x_additional_info.requires_grad):
             from ..autograd import temporal_forward_with_grad
 
             return temporal_forward_with_grad(self, eng, x, x_additional_info)

@@ -534,6 +534,21 @@ def silu_outer_bwd(groups: Sequence[Dict], c: torch.Tensor, M: int, dtype: torch
                                        N.stream_ptr()), "sea_silu_outer_bwd")
 
 
+def silu_outer_bwd_dc(groups: Sequence[Dict], c: torch.Tensor, dc: torch.Tensor, M: int, dtype: torch.dtype, ws: Optional[torch.Tensor] = None) -> None:
+    """silu_outer_bwd (the same dw1 / db1) that also adds the condition gradient into dc f32 [M] (sea_silu_outer_bwd_dc).  ws: f32 workspace, sized here
+    when not given."""
+    n = len(groups)
+    arr = (N.SeaSiluBwdGroup * n)()
+    for g, gd in zip(arr, groups):
+        fill_silu_bwd_group(g, _mat(gd["dHid"], "dHid"), gd["w1"], gd["b1"], gd["dw1"], gd["db1"])
+    if ws is None:   # the dc partials and the column sums of as many row splits as the column form runs (TrainPlan._silu_bwd sizes it the same way)
+        ncb = sum((g.K2 + 255) // 256 for g in arr)
+        rs = max(1, min((1024 + ncb - 1) // ncb, (M + 15) // 16))
+        ws = torch.empty(ncb * M + n * rs * 2 * max(g.K2 for g in arr), device=c.device, dtype=torch.float32)
+    N.check(N.lib().sea_silu_outer_bwd_dc(arr, n, c.data_ptr(), dc.data_ptr(), M, N.dtype_code(dtype), ws.data_ptr(), ws.numel(), N.stream_ptr()),
+            "sea_silu_outer_bwd_dc")
+
+
 def fill_ib_bwd_params(P: N.SeaIbBwdParams, dxs: Sequence[torch.Tensor], c, w1=None, b1=None, lnw=None, lnb=None, w2=None, dw1=None, db1=None, dlnw=None,
                        dlnb=None, dw2=None, db2=None, ws=None, dhid=None, mode: int = 0, M=None, E=None, drop=None) -> None:
     """dxs: f32 [M, E] gradients of the rows fill_ib_params's layer was added to (M, E: their shape unless given); c f32 [M] (None: patched at bind time).
@@ -561,6 +576,17 @@ def ib_bwd(dxs: Sequence[torch.Tensor], c, w1, b1, lnw, lnb, w2, dw1, db1, dlnw,
     P = N.SeaIbBwdParams()
     fill_ib_bwd_params(P, dxs, c, w1, b1, lnw, lnb, w2, dw1, db1, dlnw, dlnb, dw2, db2, ws, dhid)
     N.check(N.lib().sea_ib_bwd(C.byref(P), N.stream_ptr()), "sea_ib_bwd")
+
+
+def ib_bwd_dc(dxs: Sequence[torch.Tensor], c: torch.Tensor, dc: torch.Tensor, mode: int = 0, drop=None, **layer) -> None:
+    """dc f32 [M] += the condition gradient of the information-bottleneck layer of `mode` (sea_ib_bwd_dc); `layer`: fill_ib_bwd_params's parameter
+    and gradient keywords (with dw1 given, modes 0 / 1 also accumulate the parameter gradients, as ib_bwd)."""
+    for x in dxs:
+        _mat(x, "dx")
+        assert x.dtype == torch.float32 and x.stride(0) == dxs[0].stride(0)
+    P = N.SeaIbBwdParams()
+    fill_ib_bwd_params(P, dxs, c, mode=mode, drop=drop, **layer)
+    N.check(N.lib().sea_ib_bwd_dc(C.byref(P), dc.data_ptr(), N.stream_ptr()), "sea_ib_bwd_dc")
 
 
 def transpose_weights(src_flat: torch.Tensor, dst_flat: torch.Tensor, desc: torch.Tensor, tile_start: torch.Tensor) -> None:

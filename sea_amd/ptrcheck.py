@@ -218,6 +218,26 @@ def _walk_structs(obj) -> Iterator[C.Structure]:
             yield from _walk_structs(e)
 
 
+def _raw_extents(r, esz: int) -> Iterable[Tuple[str, int, int]]:
+    """(argument, address, bytes) of the operands a launch takes as raw addresses in its argument list, where the arguments state their extent: the
+    strided copies (sea_convert_f32_to_act, the input-gradient output dx among them) and the condition gradient dc [M] fp32."""
+    name, a = getattr(r.fn, "__name__", ""), r.args
+    if name == "sea_convert_f32_to_act":
+        rows, cols = a[4], a[5]
+        if isinstance(a[0], int):
+            yield "src", a[0], ((rows - 1) * a[1] + cols) * 4
+        if isinstance(a[2], int):
+            yield "dst", a[2], ((rows - 1) * a[3] + cols) * (4 if a[6] == N.SEA_F32 else esz)
+    elif name == "sea_silu_outer_bwd_dc":
+        for label, k in (("c", 2), ("dc", 3)):
+            if isinstance(a[k], int):
+                yield label, a[k], a[4] * 4
+        if isinstance(a[6], int):
+            yield "ws", a[6], a[7] * 4
+    elif name == "sea_ib_bwd_dc" and isinstance(a[1], int) and isinstance(r.keep, N.SeaIbBwdParams):
+        yield "dc", a[1], r.keep.M * 4
+
+
 def check_records(records, ranges: Ranges, esz: int, what: str) -> int:
     """Audit every launch record; raises RuntimeError naming the record, field and address of the first violation.  Returns the number of pointers seen."""
     n = 0
@@ -242,6 +262,11 @@ def check_records(records, ranges: Ranges, esz: int, what: str) -> int:
                     if hit is not None and nbytes > 0 and p + nbytes > hit[1]:
                         raise RuntimeError(f"sea_amd pointer audit ({what}): launch '{r.name}': {type(st).__name__}.{field} = {p:#x} + {nbytes} bytes runs "
                                            f"{p + nbytes - hit[1]} bytes past the end of its buffer ({hit[2]})")
+        for field, p, nbytes in _raw_extents(r, esz):
+            hit = ranges.find(p)
+            if hit is not None and nbytes > 0 and p + nbytes > hit[1]:
+                raise RuntimeError(f"sea_amd pointer audit ({what}): launch '{r.name}': argument {field} = {p:#x} + {nbytes} bytes runs "
+                                   f"{p + nbytes - hit[1]} bytes past the end of its buffer ({hit[2]})")
         # raw integer addresses kept in the Python argument list (sea_convert_f32_to_act, the silu launch's condition pointer)
         for a in r.args:
             if isinstance(a, int) and a >= (1 << 32) and ranges.find(a) is None and r.fn is not None and r.name not in ("",):

@@ -21,9 +21,14 @@ from .engine import Plan, _Rec, blk_pe
 
 
 class TrainPlan(Plan):
-    def __init__(self, eng, B: int, T: int, drop_thr: int = 0, dp: bool = False):
+    def __init__(self, eng, B: int, T: int, drop_thr: int = 0, dp: bool = False, want_dx: bool = False, want_dc: bool = False):
         self.drop_thr = drop_thr
         self.dp = bool(dp)   # data-parallel layout of the backward (the condition MLPs' backward per phase, two early slices): decided ONCE per engine (TemporalEngine.dp_overlap)
+        # input gradients (autograd.py): d loss / d x [B, T, F, Eo] and d loss / d condition [M], both fp32, written into caller buffers bound per backward
+        # (bind_input_grads).  Without them the backward list is exactly the parameter-gradient list.
+        self.want_dx, self.want_dc = bool(want_dx), bool(want_dc)
+        self._dx_patches: List[Tuple[list, int, int]] = []   # (record args, index, byte offset from the dx base)
+        self._dc_patches: List[Tuple[list, int]] = []        # (record args, index) receiving the dc pointer
         self._next_stream = 0
         self.bwd: List[_Rec] = []
         self._buckets = None
@@ -86,6 +91,17 @@ class TrainPlan(Plan):
         """Group dicts: the arguments of ops.fill_silu_bwd_group."""
         for s in range(0, len(groups), N.MAX_SILU_BWD_GROUPS):
             arr = self._array(N.SeaSiluBwdGroup, groups[s:s + N.MAX_SILU_BWD_GROUPS], ops.fill_silu_bwd_group)
+            if self.want_dc:
+                # the same parameter gradients plus dc, from one read of dHid: a workspace of its own (dc partials per column block and row, and the
+                # column-sum partials of as many row splits as the column form runs: sea_silu_outer_bwd_dc)
+                ncb = sum((g.K2 + 255) // 256 for g in arr)
+                rs = max(1, min((1024 + ncb - 1) // ncb, (self.M + 15) // 16))
+                ws = self._buf(ncb * self.M + len(arr) * rs * 2 * max(g.K2 for g in arr), dtype=torch.float32)
+                rec = self._rec(N.lib().sea_silu_outer_bwd_dc, [arr, len(arr), None, None, self.M, self.code, ws.data_ptr(), ws.numel()], name + ".dc", arr)
+                self._c_patches.append((rec.args, 2))
+                self._dc_patches.append((rec.args, 3))
+                self._cur.append(rec)
+                continue
             ws = self._colsum_ws(len(arr) * min((self.M + 3) // 4, 256) * 2 * max(g.K2 for g in arr))
             rec = self._rec(N.lib().sea_silu_outer_bwd, [arr, len(arr), None, self.M, self.code, ws.data_ptr(), ws.numel()], name, arr)
             self._c_patches.append((rec.args, 2))
@@ -157,9 +173,15 @@ class TrainPlan(Plan):
     def _ib_bwd(self, pre: str, dxs: List[torch.Tensor], drop=None) -> None:
         P, G, mode = self.eng.params, self.eng.grad_view, self.eng.ib_mode
         if mode == 2:      # GaussianFourierProjection: its matrix is fixed (requires_grad=False in the reference): nothing to accumulate
+            if self.want_dc:   # ... but the condition gradient passes through it
+                ib = N.SeaIbBwdParams()
+                ops.fill_ib_bwd_params(ib, dxs, None, w1=P.f32(pre + "ib.W"), mode=2, M=self.M, E=self.ib_dim)
+                self._ib_dc_rec(ib)
             return
         if mode == 1:      # nn.Linear(1, E): weight [E, 1], bias [E]
             w = dict(dw1=G(pre + "ib.weight"), db1=G(pre + "ib.bias"))
+            if self.want_dc:   # (the condition gradient reads the weight itself)
+                w["w1"] = P.f32_vec(pre + "ib.weight")
         else:
             names = ("ib.layers.0.weight", "ib.layers.0.bias", "ib.layers.1.weight", "ib.layers.1.bias", "ib.layers.3.weight")
             w = dict(zip(("w1", "b1", "lnw", "lnb", "w2"), (P.f32(pre + n) for n in names)))
@@ -175,8 +197,17 @@ class TrainPlan(Plan):
         ops.fill_ib_bwd_params(ib, dxs, None, mode=mode, M=self.M, E=self.ib_dim, **w)
         if "drop" in w:
             self._drop_structs.append(ib)
+        if self.want_dc:   # the same parameter gradients, then dc (sea_ib_bwd_dc)
+            self._ib_dc_rec(ib)
+            return
         self._c_patches.append((ib, "c"))
         self._cur.append(self._rec(N.lib().sea_ib_bwd, [C.byref(ib)], "bwd.ib", ib))
+
+    def _ib_dc_rec(self, ib) -> None:
+        self._c_patches.append((ib, "c"))
+        rec = self._rec(N.lib().sea_ib_bwd_dc, [C.byref(ib), None], "bwd.ib.dc", ib)
+        self._dc_patches.append((rec.args, 1))
+        self._cur.append(rec)
 
     def _convert(self, src32: torch.Tensor, dst: torch.Tensor, name: str) -> None:
         self._cur.append(_Rec(N.lib().sea_convert_f32_to_act, [src32.data_ptr(), src32.stride(0), dst.data_ptr(), dst.stride(0), src32.shape[0],
@@ -678,6 +709,13 @@ class TrainPlan(Plan):
         # have emitted them per phase above: nothing is left here)
         if adaln:
             cond_backward()
+        if self.want_dx:
+            # d loss / d x: layer 0's residual gradient (its first Eo columns: 'concat' widens the rows by the info-bottleneck columns), per field into
+            # the caller's [B, T, F, Eo] fp32 buffer
+            for i in range(F):
+                rec = self._rec(L.sea_convert_f32_to_act, [dx[i].data_ptr(), E, None, FE, M, Eo, N.SEA_F32], "bwd.dx.out")
+                self._dx_patches.append((rec.args, 2, i * Eo * 4))
+                self._cur.append(rec)
         self._cur = self.records
         self.saved = Sv
 
@@ -685,6 +723,14 @@ class TrainPlan(Plan):
     def bind_dout(self, dout_ptr: int) -> None:
         for tgt, field, off in self._dout_patches:
             setattr(tgt, field, dout_ptr + off)
+
+    def bind_input_grads(self, dx_ptr: Optional[int], dc_ptr: Optional[int]) -> None:
+        """Point the input-gradient launches at the caller's dx [B, T, F, Eo] fp32 and dc [M] fp32 (dc is ADDED to: zero it first)."""
+        assert (dx_ptr is not None) == self.want_dx and (dc_ptr is not None) == self.want_dc, "input-gradient buffers do not match the plan"
+        for args, k, off in self._dx_patches:
+            args[k] = dx_ptr + off
+        for args, k in self._dc_patches:
+            args[k] = dc_ptr
 
     def grad_buckets(self):
         """[(number of backward records after which the slice is final, flat start, flat end)] in backward order.  The flat buffers are laid out by gradient
