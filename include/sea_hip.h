@@ -41,7 +41,7 @@ enum {
 int sea_abi_version(void);
 const char* sea_last_error(void);
 /* sizeof of every ABI struct in declaration order (SeaGemmGroup, SeaQkvGroup, SeaQkvCommon, SeaAttnProblem,
- * SeaAttnParams, SeaNormGroup, SeaSiluGroup, SeaIbParams, ..., SeaLaunchRec, SeaGemmNormGroup, SeaExchangeTail, SeaMlpGroup, SeaMlp2Group, SeaKvNorm, SeaKvField, SeaKvPair, SeaKvLayer, SeaKvGlobal, SeaStepPatch, SeaRowChain, SeaAdalnGroup, SeaAdalnQkv, SeaSplitkGroup, SeaEncBlock last): lets a binding verify its layout.  Host only. */
+ * SeaAttnParams, SeaNormGroup, SeaSiluGroup, SeaIbParams, ..., SeaLaunchRec, SeaGemmNormGroup, SeaExchangeTail, SeaMlpGroup, SeaMlp2Group, SeaKvNorm, SeaKvField, SeaKvPair, SeaKvLayer, SeaKvGlobal, SeaStepPatch, SeaRowChain, SeaAdalnGroup, SeaAdalnQkv, SeaSplitkGroup, SeaEncBlock, SeaKvFill last): lets a binding verify its layout.  Host only. */
 int sea_struct_sizes(int* out, int cap);
 /* Number of compute units / name of device 0's architecture as HIP reports them (diagnostics for bench.py). */
 int sea_device_info(int* cu_count, char* arch, int arch_len);
@@ -804,7 +804,7 @@ int sea_patchify(const float* in, const int32_t* index_map, const float* scale, 
  * Supported: exchange_mode 'sea' (exchange = 1, F >= 2) or 'simple' (exchange = 0), LN_type adaln / ln, any info-bottleneck mode (the caller
  * evaluates the term for all steps), src_len = 0, E <= 512, head dims 8 / 16 / 32 / 64, widths whose 16-byte chunk count is a power of two <= 64
  * or 128 / 256 / 512.
- * What depends on the condition only is evaluated by the CALLER for all steps before the call: SeaKvNorm.mod = act [n_rows, 2 d] (row (pos) * B + b:
+ * What depends on the condition only is evaluated by the CALLER for all steps before the call: SeaKvNorm.mod = act [n_rows, 2 d] (row k * B + b of step k:
  * AdaLN's cond_mlp output, models/base_blocks.py:337-344; NULL for LN_type 'ln'), SeaKvLayer.ib = f32 [n_rows, E] (the info-bottleneck term,
  * models/temporal.py:103-114; NULL for ib_addition_mode 'none').
  * Caches are act [B, H, cap, hd] for keys AND values (row-major values: an append is one row).  Workspaces are f32, sized in elements:
@@ -859,6 +859,27 @@ typedef struct {
 int sea_kv_rollout(const SeaKvGlobal* G, const SeaKvLayer* layers, int pos0, int n_steps, uint32_t tag0, int dtype, void* stream);
 /* Words of `handoff` the persistent form of sea_kv_rollout needs for these sizes (host only). */
 int64_t sea_kv_arena_words(const SeaKvGlobal* G);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * KV-cache prefill from a multi-step context (the reference rolls out from a known prefix by recomputing the full forward over it every step,
+ * utils/train_utils.py:202-209): the full-context forward over the k context rows leaves every attention module's keys K [B, H, cap_src, hd] and
+ * values V^T [B, H, hd, cap_src] for positions 0 .. k-1 in its own buffers; ONE launch moves them into the decode caches, so that the exact KV
+ * decode continues from position k.  Per table entry, positions 0 .. n_pos-1 of every (b, h):
+ *   K -> Kd [B, H, cap_dst, hd];
+ *   Vt -> Vd, either as [B, H, cap_dst, hd] rows (v_rows = 1: sea_kv_rollout's caches, transposed through LDS tiles) or as [B, H, hd, cap_dst]
+ *   (v_rows = 0: the generic step plan's caches, only the capacity stride changes).
+ * Positions >= n_pos of a destination are never touched.  Requirements: hd a multiple of 8 in [8, 256]; 1 <= n_pos <= cap_src, cap_dst; cap_src and
+ * cap_dst multiples of 8; every pointer 16-byte aligned.  One launch per SEA_KV_FILL_MAX entries (the table travels in the kernel arguments).
+ */
+#define SEA_KV_FILL_MAX 32
+typedef struct {
+    const void* K;     /* act [B, H, cap_src, hd] */
+    const void* Vt;    /* act [B, H, hd, cap_src] */
+    void* Kd;          /* act [B, H, cap_dst, hd] */
+    void* Vd;          /* act [B, H, cap_dst, hd] (v_rows = 1) or [B, H, hd, cap_dst] (v_rows = 0) */
+    int32_t B, H, hd, n_pos, cap_src, cap_dst, v_rows, pad_;
+} SeaKvFill;
+int sea_kv_cache_fill(const SeaKvFill* entries, int n, int dtype, void* stream);
 /* Tuning aid: register a device buffer of n_steps * 64 8-byte words that the persistent form fills with 100 MHz clock stamps of its hand-offs
  * (tools/kv_persist_timeline.py); NULL switches it off. */
 void sea_kv_debug_stamps(unsigned long long* buf);

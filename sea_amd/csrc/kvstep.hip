@@ -586,6 +586,7 @@ struct KvArgs {
     SeaKvLayer L;
     SeaKvGlobal G;
     int32_t pos;         // position of this step's row in the caches / trajectory
+    int32_t step;        // index of this step within the call (pos - pos0): its rows of the condition buffers are step * B + b
     int32_t layer;
     uint32_t tag;        // unique per (step, layer) launch of the tails kernel
     int32_t last_layer;
@@ -619,7 +620,7 @@ __global__ __launch_bounds__(512) void kv_self_kernel(const KvArgs A) {
     float* part = red + 32;
     float* prob = part + 8 * HD;
     const SeaKvField& Fd = A.L.f[i];
-    const int64_t crow = (int64_t)pos * B + b;
+    const int64_t crow = (int64_t)A.step * B + b;
     const int64_t bh = (int64_t)b * H + h;
     T* Kc = static_cast<T*>(Fd.Ks) + bh * cap * HD;
     T* Vc = static_cast<T*>(Fd.Vs) + bh * cap * HD;
@@ -664,7 +665,7 @@ __global__ __launch_bounds__(512) void kv_oproj_kernel(const KvArgs A) {
     float* red = y + 3 * E;
     const SeaKvField& Fd = A.L.f[i];
     const bool ex = A.G.exchange != 0;
-    const int64_t crow = (int64_t)A.pos * B + b, ro = ((int64_t)b * F + i);
+    const int64_t crow = (int64_t)A.step * B + b, ro = ((int64_t)b * F + i);
     MRegs<MCfg<T, KE>::KS, tiles_per_wave(KE, 8)> rwo;
     MRegs<MCfg<T, KE>::KS, tiles_per_wave(KD, 8)> rwd;
     pre_issue<KE, T, tiles_per_wave(KE, 8)>(rwo, static_cast<const T*>(Fd.Wo), E, E, IdentityRow(), tid, nth);
@@ -794,7 +795,7 @@ __device__ __forceinline__ void tail_body(const KvArgs& A, float* sm, int b) {
     T* xsT = reinterpret_cast<T*>(y + E);
     float* red = y + 2 * E;
     const SeaKvField& Fd = A.L.f[I];
-    const int64_t crow = (int64_t)pos * B + b, ro = (int64_t)b * NF + I;
+    const int64_t crow = (int64_t)A.step * B + b, ro = (int64_t)b * NF + I;
     // ---- requested before the first wait: the projections of every pair, the k / v weights of the first two updated sources
     MRegs<MCfg<T, KD>::KS, NT_D> rp[NF - 1];
     MRegs<MCfg<T, KD>::KS, NT_2D> rkv[NNEW > 2 ? 2 : (NNEW > 0 ? NNEW : 1)];
@@ -983,7 +984,7 @@ __global__ __launch_bounds__(256) void kv_fc1_kernel(const KvArgs A) {
     float* hs = ns + 2 * E;
     float* red = hs + ROWS;
     const SeaKvField& Fd = A.L.f[i];
-    const int64_t crow = (int64_t)A.pos * B + b, ro = (int64_t)b * F + i;
+    const int64_t crow = (int64_t)A.step * B + b, ro = (int64_t)b * F + i;
     const int nr_ = r0 + ROWS <= S ? ROWS : S - r0;
     const T* W = static_cast<const T*>(Fd.W1) + (int64_t)r0 * E;
     MRegs<MCfg<T, KE>::KS, 1> rw;
@@ -1055,7 +1056,7 @@ __global__ __launch_bounds__(512) void kv_proj_kernel(const KvArgs A) {
     T* xsT = reinterpret_cast<T*>(y + E);
     float* red = y + 2 * E;
     const SeaKvField& Fd = A.L.f[i];
-    const int64_t crow = (int64_t)A.pos * B + b, ro = (int64_t)b * F + i;
+    const int64_t crow = (int64_t)A.step * B + b, ro = (int64_t)b * F + i;
     MRegs<MCfg<T, KE>::KS, tiles_per_wave(KE, 8)> rw;
     pre_issue<KE, T, tiles_per_wave(KE, 8)>(rw, static_cast<const T*>(Fd.Wproj), E, E, IdentityRow(), tid, nth);
     if (tid < E) {
@@ -1191,7 +1192,7 @@ __device__ __forceinline__ void role_self(const KvPersist& A, float* sm, int i, 
     for (int s = 0; s < A.n_steps; ++s) {
         const int pos = A.pos0 + s;
         const uint32_t tag = A.tag0 + (uint32_t)s;
-        const int64_t crow = pos;
+        const int64_t crow = s;
         NormRegs<1> nr;
         norm_issue<T, 1>(nr, E, Fd.ln0, crow, tid, nth);
         HeadRegs hr;
@@ -1241,7 +1242,7 @@ __device__ __forceinline__ void role_oproj(const KvPersist& A, float* sm, int i)
     for (int s = 0; s < A.n_steps; ++s) {
         const int pos = A.pos0 + s;
         const uint32_t tag = A.tag0 + (uint32_t)s;
-        const int64_t crow = pos;
+        const int64_t crow = s;
         NormRegs<1> nr;
         if (ex) norm_issue<T, 1>(nr, D, Fd.ln_cross, crow, tid, nth);
         const float* ibp = (A.L.ib != nullptr && !A.G.ib_after_cross) ? A.L.ib + crow * E : nullptr;
@@ -1381,7 +1382,7 @@ __device__ __forceinline__ void role_tail(const KvPersist& A, float* sm) {
     for (int st = 0; st < A.n_steps; ++st) {
         const int pos = A.pos0 + st;
         const uint32_t tag = A.tag0 + (uint32_t)st;
-        const int64_t crow = pos;
+        const int64_t crow = st;
         NormRegs<1> nr;
         if constexpr (HAS_DOWN) norm_issue<T, 1>(nr, D, Fd.ln_cross, crow, tid, nth);
         float gsum = 0.f;
@@ -1553,7 +1554,7 @@ __device__ __forceinline__ void role_fc(const KvPersist& A, float* sm, int i, in
     for (int s = 0; s < A.n_steps; ++s) {
         const int pos = A.pos0 + s;
         const uint32_t tag = A.tag0 + (uint32_t)s;
-        const int64_t crow = pos;
+        const int64_t crow = s;
         NormRegs<1> nr;
         norm_issue<T, 1>(nr, E, Fd.ln2, crow, tid, nth);
         const float* ibp = (A.L.ib != nullptr && A.G.ib_after_cross) ? A.L.ib + crow * E : nullptr;
@@ -1604,7 +1605,7 @@ __device__ __forceinline__ void role_proj(const KvPersist& A, float* sm, int i) 
         const int pos = A.pos0 + s;
         const uint32_t tag = A.tag0 + (uint32_t)s;
         NormRegs<1> nr;
-        norm_issue<T, 1>(nr, E, A.G.final_ln[i], (int64_t)pos, tid, nth);
+        norm_issue<T, 1>(nr, E, A.G.final_ln[i], (int64_t)s, tid, nth);
         if (tid < E) {
             const float v = gr_get(A.gx3 + i * E + tid, tag, ec);
             xs[tid] = v;
@@ -1687,6 +1688,7 @@ static int run_steps(const SeaKvGlobal& G, const SeaKvLayer* layers, int pos0, i
             A.L = layers[l];
             A.G = G;
             A.pos = pos;
+            A.step = k;
             A.layer = l;
             A.tag = tag0 + (uint32_t)(k * Ln + l);
             A.last_layer = l == Ln - 1;
@@ -1824,6 +1826,87 @@ static bool run_persistent(const SeaKvGlobal& G, const SeaKvLayer* layers, int p
     }
 }
 
+// ------------------------------------------------------------------------------------------------ cache prefill (sea_kv_cache_fill)
+// A workgroup per (entry, b * H + h, 64-position tile): the tile's key rows are one contiguous span in source and destination (only the capacity
+// stride differs), copied 16 bytes per lane; the values either keep the V^T layout (hd rows of 64 positions, 16 bytes per lane, the partial chunk of
+// the last tile element by element) or are transposed to rows through an LDS tile of 64 value columns x 64 positions (raw element bits, so that the
+// copy is exact): both the V^T reads and the row writes coalesce.
+constexpr int FILL_TILE = 64;
+struct FillLaunch {
+    SeaKvFill e[SEA_KV_FILL_MAX];
+    int32_t wg0[SEA_KV_FILL_MAX + 1];   // first workgroup of each entry (prefix sum of B H ceil(n_pos / 64))
+    int32_t n;
+};
+
+template <typename T>
+__global__ __launch_bounds__(256) void kv_fill_kernel(const FillLaunch L) {
+    using Bits = typename std::conditional<sizeof(T) == 2, uint16_t, uint32_t>::type;
+    constexpr int EPV = 16 / (int)sizeof(T);                 // elements per 16-byte chunk
+    __shared__ uint32_t tile[FILL_TILE * (FILL_TILE + 1)];   // [value column][position], one word of padding per column
+    int e = 0;
+    while (e + 1 < L.n && (int)blockIdx.x >= L.wg0[e + 1]) ++e;
+    const SeaKvFill& F = L.e[e];
+    const int tiles = (F.n_pos + FILL_TILE - 1) / FILL_TILE;
+    const int w = (int)blockIdx.x - L.wg0[e];
+    const int64_t bh = w / tiles;
+    const int p0 = (w - (int)bh * tiles) * FILL_TILE;
+    const int np = min(FILL_TILE, F.n_pos - p0);             // positions of this tile
+    const int hd = F.hd, tid = threadIdx.x;
+    // keys: rows p0 .. p0 + np - 1 are np * hd contiguous elements on both sides (hd * sizeof(T) is a multiple of 16)
+    {
+        const uint4* src = reinterpret_cast<const uint4*>(static_cast<const T*>(F.K) + (bh * F.cap_src + p0) * hd);
+        uint4* dst = reinterpret_cast<uint4*>(static_cast<T*>(F.Kd) + (bh * F.cap_dst + p0) * hd);
+        const int n16 = np * hd / EPV;
+        for (int c = tid; c < n16; c += 256) dst[c] = src[c];
+    }
+    const Bits* vs = reinterpret_cast<const Bits*>(F.Vt) + bh * hd * F.cap_src + p0;   // + d * cap_src: value column d of this tile
+    const int cpr = (np + EPV - 1) / EPV;                                              // 16-byte chunks per column (the last one may be partial)
+    if (!F.v_rows) {
+        Bits* vd = reinterpret_cast<Bits*>(F.Vd) + bh * hd * F.cap_dst + p0;
+        for (int it = tid; it < hd * cpr; it += 256) {
+            const int d = it / cpr, c = it - d * cpr;
+            const Bits* s = vs + (int64_t)d * F.cap_src + c * EPV;
+            Bits* t = vd + (int64_t)d * F.cap_dst + c * EPV;
+            if ((c + 1) * EPV <= np) {
+                *reinterpret_cast<uint4*>(t) = *reinterpret_cast<const uint4*>(s);
+            } else {
+                for (int u = 0; u < np - c * EPV; ++u) t[u] = s[u];
+            }
+        }
+        return;
+    }
+    Bits* vd = reinterpret_cast<Bits*>(F.Vd) + (bh * F.cap_dst + p0) * hd;                 // + p * hd + d
+    for (int d0 = 0; d0 < hd; d0 += FILL_TILE) {
+        const int dw = min(FILL_TILE, hd - d0);                                            // a multiple of 8
+        for (int it = tid; it < dw * cpr; it += 256) {                                     // V^T rows -> tile[d][p]
+            const int dl = it / cpr, c = it - dl * cpr;
+            const Bits* s = vs + (int64_t)(d0 + dl) * F.cap_src + c * EPV;
+            uint32_t* t = tile + dl * (FILL_TILE + 1) + c * EPV;
+            if ((c + 1) * EPV <= np) {
+                const uint4 v = *reinterpret_cast<const uint4*>(s);
+                Bits b[EPV];
+                __builtin_memcpy(b, &v, 16);
+#pragma unroll
+                for (int u = 0; u < EPV; ++u) t[u] = b[u];
+            } else {
+                for (int u = 0; u < np - c * EPV; ++u) t[u] = s[u];
+            }
+        }
+        __syncthreads();
+        const int cpp = dw / EPV;                                                          // 16-byte chunks of a value row in this column block
+        for (int it = tid; it < np * cpp; it += 256) {                                     // tile[d][p] -> value rows
+            const int p = it / cpp, c = it - p * cpp;
+            Bits b[EPV];
+#pragma unroll
+            for (int u = 0; u < EPV; ++u) b[u] = (Bits)tile[(c * EPV + u) * (FILL_TILE + 1) + p];
+            uint4 v;
+            __builtin_memcpy(&v, b, 16);
+            *reinterpret_cast<uint4*>(vd + (int64_t)p * hd + d0 + c * EPV) = v;
+        }
+        __syncthreads();
+    }
+}
+
 template <typename T>
 static int run_steps_t(const SeaKvGlobal& G, const SeaKvLayer* layers, int pos0, int n_steps, uint32_t tag0, hipStream_t s) {
     switch (pre_width(G)) {
@@ -1862,5 +1945,39 @@ extern "C" int sea_kv_rollout(const SeaKvGlobal* G, const SeaKvLayer* layers, in
     if (dtype == SEA_BF16) run_steps_t<__bf16>(*G, layers, pos0, n_steps, tag0, s);
     else run_steps_t<float>(*G, layers, pos0, n_steps, tag0, s);
     SEA_CHECK_LAUNCH("sea_kv_rollout");
+    return SEA_OK;
+}
+
+extern "C" int sea_kv_cache_fill(const SeaKvFill* entries, int n, int dtype, void* stream) {
+    SEA_REQUIRE(entries != nullptr && n >= 1, "sea_kv_cache_fill: bad arguments (entries=%p n=%d)", (const void*)entries, n);
+    SEA_REQUIRE(dtype == SEA_F32 || dtype == SEA_BF16, "sea_kv_cache_fill: bad dtype %d", dtype);
+    int64_t wg_all = 0;
+    for (int i = 0; i < n; ++i) {
+        const SeaKvFill& F = entries[i];
+        SEA_REQUIRE(F.K && F.Vt && F.Kd && F.Vd && sea_aligned16(F.K) && sea_aligned16(F.Vt) && sea_aligned16(F.Kd) && sea_aligned16(F.Vd),
+                    "sea_kv_cache_fill: entry %d: null or misaligned (16 bytes) pointer", i);
+        SEA_REQUIRE(F.B >= 1 && F.H >= 1 && F.hd >= 8 && F.hd <= 256 && F.hd % 8 == 0 && F.n_pos >= 1 && F.n_pos <= F.cap_src && F.n_pos <= F.cap_dst &&
+                        F.cap_src % 8 == 0 && F.cap_dst % 8 == 0 && (F.v_rows == 0 || F.v_rows == 1),
+                    "sea_kv_cache_fill: entry %d: bad sizes (B=%d H=%d hd=%d n_pos=%d cap_src=%d cap_dst=%d v_rows=%d)", i, F.B, F.H, F.hd, F.n_pos, F.cap_src,
+                    F.cap_dst, F.v_rows);
+        wg_all += (int64_t)F.B * F.H * ((F.n_pos + FILL_TILE - 1) / FILL_TILE);
+    }
+    SEA_REQUIRE(wg_all < ((int64_t)1 << 31), "sea_kv_cache_fill: %lld workgroups", (long long)wg_all);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    for (int e0 = 0; e0 < n; e0 += SEA_KV_FILL_MAX) {
+        FillLaunch L;
+        L.n = n - e0 < SEA_KV_FILL_MAX ? n - e0 : SEA_KV_FILL_MAX;
+        int64_t wg = 0;
+        for (int i = 0; i < L.n; ++i) {
+            const SeaKvFill& F = entries[e0 + i];
+            L.e[i] = F;
+            L.wg0[i] = (int32_t)wg;
+            wg += (int64_t)F.B * F.H * ((F.n_pos + FILL_TILE - 1) / FILL_TILE);
+        }
+        L.wg0[L.n] = (int32_t)wg;
+        if (dtype == SEA_BF16) kv_fill_kernel<__bf16><<<dim3((unsigned)wg), dim3(256), 0, s>>>(L);
+        else kv_fill_kernel<float><<<dim3((unsigned)wg), dim3(256), 0, s>>>(L);
+        SEA_CHECK_LAUNCH("sea_kv_cache_fill");
+    }
     return SEA_OK;
 }

@@ -85,6 +85,17 @@ def grad_phase(model, name: str) -> int:
     return (L - 1 - l) * 3 + sub
 
 
+def _kv_pairs(src: dict, dst: dict):
+    """((K, V^T) of plan `src`, (K, V^T) of plan `dst`) for every self-attention module and cross-attention pair of the model (Plan.kv)."""
+    for l in range(len(src["Ks"])):
+        for i in range(len(src["Ks"][l])):
+            yield (src["Ks"][l][i], src["Vs"][l][i]), (dst["Ks"][l][i], dst["Vs"][l][i])
+            if src["Kc"] is not None:
+                for j in range(len(src["Kc"][l][i])):
+                    if j != i:
+                        yield (src["Kc"][l][i][j], src["Vc"][l][i][j]), (dst["Kc"][l][i][j], dst["Vc"][l][i][j])
+
+
 class FlatParams:
     """One contiguous fp32 buffer holding every parameter of the model (+ the activation-dtype shadow)."""
 
@@ -745,6 +756,9 @@ class Plan:
         hbuf = [self._buf(M, S + pad)[:, :S] for _ in range(F)]
         hg = [self._buf(M, S + pad)[:, :S] for _ in range(F)]
         self.ws = dict(xr=xr, xa=xa, n_e=n_e, att_e=att_e, hbuf=hbuf, hg=hg)
+        # the keys / values of every self-attention module and cross-attention pair, per layer: the full-context plan leaves positions 0 .. T-1 here, the
+        # source of a context rollout's cache prefill (kv_engine.CacheFill); a step plan's are the caches themselves
+        self.kv = dict(Ks=Ks, Vs=Vs, Kc=(Kc if xmode == "sea" else None), Vc=(Vc if xmode == "sea" else None))
 
         xm = [self._buf(M, E) for _ in range(F)] if lanes else xa
         first = True  # the residual stream still lives in the caller's x [B,T,F,E]
@@ -1297,10 +1311,10 @@ class Plan:
             else:
                 s.q_pos0, s.Tk = pos0, pos0 + self.T
 
-    def step_patch_table(self, x_base: int, x_stride: int, c_base: int, c_stride: int, out_base: int, out_stride: int):
+    def step_patch_table(self, x_base: int, x_stride: int, c_base: int, c_stride: int, out_base: int, out_stride: int, pos0: int = 0):
         """The per-step edits of a KV-cache rollout (set_position + bind_ptrs) as a SeaStepPatch array for sea_run_list_steps: step s reads its rows at
-        x_base + s * x_stride, its condition values at c_base + s * c_stride, writes its rows at out_base + s * out_stride and sits at position s of the
-        caches.  None when the plan has no native launch list."""
+        x_base + s * x_stride, its condition values at c_base + s * c_stride, writes its rows at out_base + s * out_stride and sits at position pos0 + s of
+        the caches.  None when the plan has no native launch list."""
         if self._clist is None:
             return None
         arr, _, relink = self._clist
@@ -1316,10 +1330,10 @@ class Plan:
 
         for st in self._pos_structs:
             if isinstance(st, N.SeaQkvCommon):
-                rows.append((field_addr(st, "pos0"), 0, 0, 1))
+                rows.append((field_addr(st, "pos0"), 0, pos0, 1))
             else:
-                rows.append((field_addr(st, "q_pos0"), 0, 0, 1))
-                rows.append((field_addr(st, "Tk"), 0, self.T, 1))
+                rows.append((field_addr(st, "q_pos0"), 0, pos0, 1))
+                rows.append((field_addr(st, "Tk"), 0, pos0 + self.T, 1))
         for tgt, field, off in self._x_patches:
             rows.append((field_addr(tgt, field), 1, x_base + off, x_stride))
         for tgt, field, off in self._out_patches:
@@ -1333,15 +1347,15 @@ class Plan:
             t.addr, t.kind, t.base, t.stride = a_, k_, b_, s_
         return tab, len(rows)
 
-    def run_steps(self, n_steps: int, x_base: int, x_stride: int, c_base: int, c_stride: int, out_base: int, out_stride: int) -> bool:
-        """n_steps consecutive KV-cache steps from position 0 in ONE native call (sea_run_list_steps); False when the plan has no native list."""
-        pt = self.step_patch_table(x_base, x_stride, c_base, c_stride, out_base, out_stride)
+    def run_steps(self, n_steps: int, x_base: int, x_stride: int, c_base: int, c_stride: int, out_base: int, out_stride: int, pos0: int = 0) -> bool:
+        """n_steps consecutive KV-cache steps from position pos0 in ONE native call (sea_run_list_steps); False when the plan has no native list."""
+        pt = self.step_patch_table(x_base, x_stride, c_base, c_stride, out_base, out_stride, pos0)
         if pt is None:
             return False
-        assert n_steps <= self.cap
+        assert pos0 + n_steps <= self.cap
         rc = N.lib().sea_run_list_steps(self._clist[0], self._clist[1], pt[0], pt[1], 0, n_steps, N.stream_ptr())
         self._bound = (None, None, None)   # the structs now hold the last step's pointers / position
-        self.pos0 = n_steps - 1 if n_steps > 0 else self.pos0
+        self.pos0 = pos0 + n_steps - 1 if n_steps > 0 else self.pos0
         if rc != 0:
             N.check(rc, "KV-cache rollout (sea_run_list_steps)")
         return True
@@ -1737,18 +1751,19 @@ class TemporalEngine:
 
     def rollout_kv(self, x0: torch.Tensor, ib: torch.Tensor, n_steps: int) -> torch.Tensor:
         """Exact KV-cache rollout (the loop of utils/train_utils.py:202-209 without recomputing the prefix): step s feeds the row
-        at position s, appends its K/V to the per-layer caches and attends over positions <= s.  x0 [B,1,F,E], ib [B,>=n_steps,1]
-        -> [B, n_steps, F, E].  The trajectory is kept time-major [n_steps+1, B, F, E] so that every step reads and writes
+        at position s, appends its K/V to the per-layer caches and attends over positions <= s.  x0 [B,k,F,E] holds the known states at positions
+        0 .. k-1, ib [B,>=k+n_steps-1,1] -> the predictions of positions k .. k+n_steps-1 [B, n_steps, F, E].  k > 1: one full-context forward over the
+        context (the prefill) predicts position k and leaves the keys / values of positions 0 .. k-1, which one sea_kv_cache_fill launch moves into the
+        caches; the decode continues from position k.  The trajectory is kept time-major [steps+1, B, F, E] so that every step reads and writes
         contiguous [B, F, E] slabs with no copies."""
-        B, one, F, E = x0.shape
-        assert one == 1 and ib.shape[0] == B and ib.shape[1] >= n_steps
-        if n_steps > self.model.max_len:
-            raise ValueError(f"rollout of {n_steps} steps exceeds max_len {self.model.max_len}")
+        from . import kv_engine
+
+        B, k, F, E = x0.shape
+        kv_engine.check_context(self.model, x0, ib, n_steps)
         if self.model.src_len > 0:
             # the reference masks with tril(diagonal=src_len) (models/base_blocks.py:173, 265): in its recompute loop the rows already produced re-attend
             # to the src_len rows appended after them, so their K/V and everything downstream change from step to step — a cache is not exact
             raise NotImplementedError("sea_amd: the KV-cache rollout is exact only for src_len == 0; use the recompute rollout (rollout(..., mode='recompute'))")
-        from . import kv_engine
         if kv_engine.supported(self, B):
             # small models: seven launches per layer and step, condition-only work batched over all steps up front (sea_kv_rollout)
             kf = self._kv_fast.get(B)
@@ -1756,9 +1771,18 @@ class TemporalEngine:
                 kf = self._kv_fast[B] = kv_engine.KvFast(self, B)
             return kf.rollout(x0, ib, n_steps)
         self.params.sync()
+        first = 0 if k == 1 else k                        # position of the step loop's first step (k > 1: the prefill predicts position k)
+        full = None
+        if k > 1:
+            if n_steps == 0:
+                return torch.empty(B, 0, F, E, device=self.device, dtype=torch.float32)
+            pred, full = kv_engine.prefill(self, x0, ib)
+            n_steps -= 1
+            if n_steps == 0:
+                return pred.unsqueeze(1).contiguous()
         traj = torch.empty(n_steps + 1, B, F, E, device=self.device, dtype=torch.float32)
-        traj[0].copy_(x0[:, 0])
-        cond = ib[:, :n_steps, 0].t().contiguous()  # [n_steps, B]
+        traj[0].copy_(x0[:, 0] if k == 1 else pred)
+        cond = ib[:, first:first + n_steps, 0].t().contiguous()  # [n_steps, B]
         # What depends on the condition only (the AdaLN modulations of every module, the info-bottleneck term) is evaluated for ALL steps by one batched
         # pass before the loop — the full-context plan's own silu / grouped-GEMM / ib launches on n_steps * B rows — instead of once per step on B rows:
         # at the shipped cylinder width (embed_dim 1024) that is two launches and 31 % of the weight bytes of every step.  SEA_KV=hoist=0: per step.
@@ -1774,18 +1798,22 @@ class TemporalEngine:
                 cp.audit(owners=(cond,))
             cp.run()
         p = self.plan(B, 1, "step", cond=cp)
+        if full is not None:   # the context's keys / values -> the step plan's caches (positions 0 .. k-1)
+            kv_engine.cache_fill_for(p, full, lambda: kv_engine.CacheFill(
+                full, [dict(K=src[0], Vt=src[1], Kd=dst[0], Vd=dst[1]) for src, dst in _kv_pairs(full.kv, p.kv)],
+                [t for _, dst in _kv_pairs(full.kv, p.kv) for t in dst], False, f"step plan B={B}")).run()
         slab = B * F * E * 4
         base, cbase = traj.data_ptr(), cond.data_ptr()
         if not p._audited or ptrcheck.always():   # the step plan is bound by raw address: audit it once against the buffers it will walk
-            p.set_position(0)
+            p.set_position(first)
             p.bind_ptrs(base, cbase, base + slab)
             p.set_hoisted_step(0)
             p.audit(owners=(traj, cond))
         # the step loop in native code (the plan's launch list + a table of the per-step edits); SEA_KV=loop=python: one Python round trip per step
-        if _switches.kv("loop", "native") == "python" or not p.run_steps(n_steps, base, slab, cbase, B * 4, base + slab, slab):
+        if _switches.kv("loop", "native") == "python" or not p.run_steps(n_steps, base, slab, cbase, B * 4, base + slab, slab, first):
             for s in range(n_steps):
-                p.set_position(s)
+                p.set_position(first + s)
                 p.bind_ptrs(base + s * slab, cbase + s * B * 4, base + (s + 1) * slab)
                 p.set_hoisted_step(s)
                 p.run()
-        return traj[1:].permute(1, 0, 2, 3).contiguous()
+        return (traj[1:] if k == 1 else traj).permute(1, 0, 2, 3).contiguous()

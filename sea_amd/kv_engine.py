@@ -17,8 +17,9 @@ import torch
 
 from . import _native as N
 from . import _switches
+from . import ops
 from . import ptrcheck
-from .engine import Plan, _round_up
+from .engine import Plan, _Rec, _round_up
 
 
 class CondPlan(Plan):
@@ -48,6 +49,66 @@ def cond_plan_for(eng, M: int) -> CondPlan:
         cache.clear()
         cp = cache[M] = CondPlan(eng, M)
     return cp
+
+
+def check_context(model, x0: torch.Tensor, ib: torch.Tensor, n_steps: int) -> int:
+    """The context length k of a rollout from x0 [B, k, F, E] with conditions ib [B, >= k + n_steps - 1, 1]; ValueError (before anything is launched)
+    for an empty context, too few conditions or a last position past max_len."""
+    B, k = x0.shape[0], x0.shape[1]
+    if k < 1:
+        raise ValueError("rollout: the context x0 [B, k, F, E] needs k >= 1 known states")
+    if n_steps < 0:
+        raise ValueError(f"rollout: n_steps = {n_steps} < 0")
+    if n_steps > 0 and k + n_steps - 1 > model.max_len:
+        raise ValueError(f"rollout: context of {k} states + {n_steps} steps reaches position {k + n_steps - 2}: k + n_steps - 1 = {k + n_steps - 1} "
+                         f"exceeds max_len {model.max_len}")
+    need = k + n_steps - 1 if n_steps > 0 else 0
+    if ib.shape[0] != B or ib.shape[1] < need:
+        raise ValueError(f"rollout: ib {tuple(ib.shape)} is too short: a context of {k} states and {n_steps} steps needs [B={B}, >= k + n_steps - 1 = {need}, 1] "
+                         "conditions (one per position 0 .. k + n_steps - 2)")
+    return k
+
+
+def prefill(eng, x0: torch.Tensor, ib: torch.Tensor):
+    """The full-context forward over the k context rows (the engine's own plan for (B, k)): returns (prediction for position k [B, F, E] fp32, the plan,
+    whose per-layer K / V^T buffers now hold positions 0 .. k-1 of every attention module)."""
+    B, k = x0.shape[0], x0.shape[1]
+    out = eng.forward(x0, ib[:, :k])
+    return out[:, k - 1], eng.plan(B, k, "full")
+
+
+class CacheFill:
+    """One sea_kv_cache_fill launch (include/sea_hip.h) from a full-context plan's K / V^T buffers into the caches of a decode; built, and audited by
+    sea_amd/ptrcheck.py, once per (full-context plan, destination) — both keep their buffers for their lifetime."""
+
+    def __init__(self, full: Plan, entries: List[dict], owners, v_rows: bool, what: str):
+        self.full, self.owners, self.what = full, list(owners), what
+        self.dtype = full.dt
+        self.arr = (N.SeaKvFill * len(entries))()
+        for g, d in zip(self.arr, entries):
+            ops.fill_kv_fill(g, n_pos=full.T, v_rows=v_rows, **d)
+        self.rec = _Rec(N.lib().sea_kv_cache_fill, [self.arr, len(entries), N.dtype_code(self.dtype)], "kv.cache_fill", self.arr)
+        self.audit()
+
+    def audit(self) -> int:
+        R = self.full._known_ranges()
+        for t in self.owners:
+            R.add_tensor(t, "decode cache")
+        return ptrcheck.check_records([self.rec], R, 4 if self.dtype == torch.float32 else 2, f"CacheFill {self.what} k={self.full.T}")
+
+    def run(self) -> None:
+        if ptrcheck.always():
+            self.audit()
+        N.check(N.lib().sea_kv_cache_fill(self.arr, len(self.arr), N.dtype_code(self.dtype), N.stream_ptr()), "sea_kv_cache_fill")
+
+
+def cache_fill_for(holder, full: Plan, build) -> CacheFill:
+    """The CacheFill of `holder` (a decode's cache owner) from plan `full`: build() makes it on first use."""
+    cache = holder.__dict__.setdefault("_fills", {})
+    cf = cache.get(id(full))
+    if cf is None or cf.full is not full:
+        cf = cache[id(full)] = build()
+    return cf
 
 
 def _chunks_ok(K: int, epc: int) -> bool:
@@ -155,16 +216,48 @@ class KvFast:
         nm.beta = P.f32_vec(pre + "bias").data_ptr() if self.adaln else None
         self._norms.append((nm, pre))
 
+    def _fill(self, full: Plan) -> CacheFill:
+        """sea_kv_cache_fill entries of every self-attention module and cross-attention pair: V^T of the full-context plan -> value rows."""
+        def build():
+            kv, entries, owners = full.kv, [], []
+            for l in range(self.L):
+                Ly = self.layers[l]
+                for i in range(self.F):
+                    entries.append(dict(K=kv["Ks"][l][i], Vt=kv["Vs"][l][i], Kd=self._cache(Ly.f[i].Ks), Vd=self._cache(Ly.f[i].Vs)))
+                    if self.exchange:
+                        for j in range(self.F):
+                            if j != i:
+                                entries.append(dict(K=kv["Kc"][l][i][j], Vt=kv["Vc"][l][i][j], Kd=self._cache(Ly.p[i][j].Kc), Vd=self._cache(Ly.p[i][j].Vc)))
+            owners = [d[k] for d in entries for k in ("Kd", "Vd")]
+            return CacheFill(full, entries, owners, True, f"KvFast B={self.B}")
+        return cache_fill_for(self, full, build)
+
+    def _cache(self, ptr: int) -> torch.Tensor:
+        return next(t for t in self._keep if t.data_ptr() == ptr)
+
     def rollout(self, x0: torch.Tensor, ib: torch.Tensor, n_steps: int) -> torch.Tensor:
-        """x0 [B, 1, F, E], ib [B, >= n_steps, 1] -> [B, n_steps, F, E] (fp32)."""
+        """x0 [B, k, F, E] (the known states at positions 0 .. k-1), ib [B, >= k + n_steps - 1, 1] -> [B, n_steps, F, E] (fp32): the predictions of
+        positions k .. k + n_steps - 1.  k > 1: the full-context forward over the context predicts position k and leaves the keys / values of positions
+        0 .. k-1, which one sea_kv_cache_fill launch moves into the caches; the decode then runs from position k (sea_kv_rollout's pos0)."""
         B, F, E = self.B, self.F, self.E
+        k = x0.shape[1]
         eng = self.eng
         eng.params.sync()
-        traj = torch.empty(n_steps + 1, B, F, E, device=eng.device, dtype=torch.float32)
-        traj[0].copy_(x0[:, 0])
-        if n_steps == 0:
-            return traj[1:].permute(1, 0, 2, 3).contiguous()
-        cond = ib[:, :n_steps, 0].t().contiguous().float()     # [n_steps, B]: row pos * B + b
+        first = 0 if k == 1 else k           # position of the decode's first step
+        n_dec = n_steps if k == 1 else n_steps - 1
+        traj = torch.empty(first + n_dec + 1, B, F, E, device=eng.device, dtype=torch.float32)   # indexed by absolute position; rows < first are never read
+        out_from = 1 if k == 1 else k
+        if k == 1:
+            traj[0].copy_(x0[:, 0])
+        elif n_steps > 0:
+            pred, full = prefill(eng, x0, ib)
+            traj[k].copy_(pred)
+            if n_dec > 0:
+                self._fill(full).run()
+        if n_dec <= 0:
+            return traj[out_from:].permute(1, 0, 2, 3).contiguous()
+        n_steps = n_dec
+        cond = ib[:, first:first + n_steps, 0].t().contiguous().float()     # [n_steps, B]: row step * B + b
         M = n_steps * B
         cp: Optional[CondPlan] = None
         if self.adaln or self.has_ib:
@@ -185,16 +278,16 @@ class KvFast:
             self.layers[l].ib = cp.ibufs[l].data_ptr() if (cp is not None and self.has_ib) else None
         self.G.traj = traj.data_ptr()
         for attempt in (0, 1):
-            rc = N.lib().sea_kv_rollout(C.byref(self.G), self.layers, 0, n_steps, self._tag, N.dtype_code(eng.act_dtype), N.stream_ptr())
+            rc = N.lib().sea_kv_rollout(C.byref(self.G), self.layers, first, n_steps, self._tag, N.dtype_code(eng.act_dtype), N.stream_ptr())
             N.check(rc, "sea_kv_rollout")
             self._tag = (self._tag + n_steps * self.L) & 0xFFFFFFFF or 1
-            out = traj[1:].permute(1, 0, 2, 3).contiguous()
+            out = traj[out_from:].permute(1, 0, 2, 3).contiguous()
             if attempt == 0 and _switches.kv("force_err") == "1" and self.G.handoff_words > B * F * max(self.D, 1):
                 self.err.fill_(1)           # test hook: behave as if a hand-off wait of the persistent launch had given up (tests/test_kv_fast_gpu.py)
             if int(self.err.item()) == 0:   # (synchronises)
                 return out
             # A hand-off wait gave up: the persistent form needs all its workgroups on the chip at once, which another process on the same GPU can
-            # deny.  Nothing is lost but time — every spin is bounded, the trajectory is recomputed from position 0 — so fall back once, for good, to
+            # deny.  Nothing is lost but time — every spin is bounded, the trajectory is recomputed from the decode's first position — so fall back once, for good, to
             # the seven launches per step (their only hand-off is between workgroups of one 3-workgroup launch).
             self.err.zero_()
             if attempt == 0 and self.G.handoff_words > B * F * max(self.D, 1):

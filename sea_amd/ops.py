@@ -798,3 +798,25 @@ def encoder_block_fwd(t: Dict, B: int, P: int, W: int, H: int, ws: torch.Tensor,
 def encoder_block_bwd(t: Dict, B: int, P: int, W: int, H: int, ws: torch.Tensor, eps: float = 1e-5, dtype: torch.dtype = torch.bfloat16) -> None:
     """dZin from dZout (the block's forward recomputed from Zin) plus the wgrad operands n1, dqkv, att, dz1, n2, dh, hg, dz2, u1, u2, u3w, u3b."""
     _encoder_block("sea_encoder_block_bwd", t, B, P, W, H, ws, eps, dtype)
+
+
+def fill_kv_fill(g: N.SeaKvFill, K, Vt, Kd, Vd, n_pos: int, v_rows: bool) -> None:
+    """One entry of sea_kv_cache_fill: K [B, H, cap_src, hd] and Vt [B, H, hd, cap_src] (a full-context plan's buffers) -> Kd [B, H, cap_dst, hd] and
+    Vd ([B, H, cap_dst, hd] with v_rows, else [B, H, hd, cap_dst]), positions 0 .. n_pos - 1."""
+    B, H, cap_src, hd = K.shape
+    g.K, g.Vt, g.Kd, g.Vd = K.data_ptr(), Vt.data_ptr(), Kd.data_ptr(), Vd.data_ptr()
+    g.B, g.H, g.hd, g.n_pos, g.cap_src, g.cap_dst, g.v_rows = B, H, hd, n_pos, cap_src, Kd.shape[2], int(bool(v_rows))
+
+
+def kv_cache_fill(entries: Sequence[Dict], dtype: torch.dtype) -> None:
+    """sea_kv_cache_fill over entries dict(K, Vt, Kd, Vd, n_pos, v_rows) (fill_kv_fill's arguments): one launch per N.KV_FILL_MAX entries."""
+    for d in entries:
+        for name in ("K", "Vt", "Kd", "Vd"):
+            t = d[name]
+            N.require_gpu(t, name)
+            if t.dim() != 4 or not t.is_contiguous() or t.dtype != dtype:
+                raise ValueError(f"kv_cache_fill: {name} must be a contiguous 4-D {dtype} tensor, got {tuple(t.shape)} {t.dtype}")
+    arr = (N.SeaKvFill * max(len(entries), 1))()
+    for g, d in zip(arr, entries):
+        fill_kv_fill(g, **d)
+    N.check(N.lib().sea_kv_cache_fill(arr, len(entries), N.dtype_code(dtype), N.stream_ptr()), "sea_kv_cache_fill")

@@ -186,6 +186,13 @@ def _extents(st, esz: int) -> Iterable[Tuple[str, int, int]]:
         yield "Hg", st.Hg, ((st.M - 1) * st.ldh + st.S) * esz
         for k in ("b1", "lnw", "lnb"):
             yield k, getattr(st, k), st.S * f32
+    elif isinstance(st, N.SeaKvFill):
+        bh = st.B * st.H
+        last_src, last_dst = (bh - 1) * st.cap_src * st.hd, (bh - 1) * st.cap_dst * st.hd   # first element of the last (b, h) slab
+        yield "K", st.K, (last_src + st.n_pos * st.hd) * esz
+        yield "Vt", st.Vt, (last_src + (st.hd - 1) * st.cap_src + st.n_pos) * esz
+        yield "Kd", st.Kd, (last_dst + st.n_pos * st.hd) * esz
+        yield "Vd", st.Vd, (last_dst + (st.n_pos * st.hd if st.v_rows else (st.hd - 1) * st.cap_dst + st.n_pos)) * esz
     elif isinstance(st, N.SeaMlp2Group):
         yield "Hg", st.Hg, ((st.M - 1) * st.ldh + st.S) * esz
         yield "W2", st.W2, ((st.E - 1) * st.ldw2 + st.S) * esz

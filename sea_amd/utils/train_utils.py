@@ -75,14 +75,20 @@ _KV_FALLBACK_WARNED: set = set()
 
 
 def rollout(model, x0: torch.Tensor, ib: torch.Tensor, n_steps: int, mode: str = "kv") -> torch.Tensor:
-    """Autoregressive rollout (reference :202-209): start from step 0 (x0 [B,1,F,E]), predict n_steps steps with
-    conditions ib[:, :n_steps].  Returns the predictions [B, n_steps, F, E].
+    """Autoregressive rollout (reference :202-209) from a known history: x0 [B,k,F,E] holds the states at positions 0 .. k-1 (k >= 1; the
+    reference starts from k = 1), ib [B, >= k+n_steps-1, 1] one condition per position 0 .. k+n_steps-2.  Returns the n_steps predictions of
+    positions k .. k+n_steps-1 [B, n_steps, F, E].
 
     mode='recompute' — what the reference does: the full forward over the growing prefix every step (O(N^2) token-forwards);
     mode='kv'        — exact incremental decode with per-layer K/V caches (the model is strictly causal and
-                        prefix-consistent), O(N) token-forwards.
+                        prefix-consistent), O(N) token-forwards; a context of k > 1 states is prefilled by one
+                        full-context forward (engine.rollout_kv).
+    ValueError, before anything runs: k = 0, k + n_steps - 1 > max_len, or fewer than k + n_steps - 1 conditions.
     """
     assert mode in ("recompute", "kv")
+    from ..kv_engine import check_context
+
+    k = check_context(model, x0, ib, n_steps)
     if mode == "kv" and (getattr(model, "src_len", 0) > 0 or getattr(model, "exchange_mode", "sea") == "pool"
                          or str(getattr(model, "ib_addition_mode", "add")).lower() == "attention"):
         # a cache is exact only for strictly causal attention (src_len == 0, no un-masked info-bottleneck attention) and absolute positions (not 'pool'):
@@ -102,9 +108,9 @@ def rollout(model, x0: torch.Tensor, ib: torch.Tensor, n_steps: int, mode: str =
             if mode == "recompute":
                 a = x0
                 for i in range(n_steps):
-                    out = model(a, ib[:, : i + 1])
+                    out = model(a, ib[:, : k + i])
                     a = torch.cat((a, out[:, -1:]), dim=1)
-                return a[:, 1:]
+                return a[:, k:]
             return model.engine(x0.device).rollout_kv(x0.float(), ib.float(), n_steps)
     finally:
         model.train(was_training)
