@@ -5,11 +5,19 @@
   SEA_DP_OVERLAP  0                      data-parallel step: ONE gradient all-reduce after the backward instead of slices under it
   SEA_DP_REHEARSE 1                      a process group of ONE rank issues the data-parallel step's collectives instead of skipping them (sea_amd/parallel.py:
                                            how the RCCL path runs on a one-GPU box: tests/test_parallel_gpu.py, `SEA_DP_REHEARSE=1 python bench.py --mode train`)
-  SEA_PLAN        key=value,...          forms of the launch plans (what the tests force to compare every form with the default one):
-                                           lanes=none|cond|all   parallel graph branches          graph_lanes=0      a captured graph replays its lanes in record order
-                                           norm=0                Linear + row norm as two launches  xtail=0            a field's exchange tail as three launches
-                                           xtail_max_rows=N      ... from N rows up                  fold_ib=0          the info-bottleneck add as a launch of its own
-                                           silu=0|1              generated GEMM operand off / on    mlp1 / mlpnorm / mlp2=0|1   the fused MLP halves off / forced
+  SEA_PLAN        key=value,...          forms of the launch plans (what the tests force to compare every form with the default one).  Every key but the last two is read in ONE
+                                         place, plan_forms.resolve_forms, once per plan build; the measurements behind the defaults are the comments of plan_forms.PlanForms:
+                                           lanes=none|cond|all   parallel graph branches            norm=0                Linear + row norm as two launches
+                                           xtail=0               a field's exchange tail as three launches               xtail_max_rows=N      ... from N rows up
+                                           chain=0               the 18-launch plan instead of the row chains            chain_max_rows=N      row chains up to N rows (4096)
+                                           riders=0              whole-model condition launches instead of riders        rider_caps=a:b:c      rider tiles per chain launch (tuning aid)
+                                           front=0               silu + sea_gemm_adaln + QKV instead of sea_adaln_qkv    front3=0              ... keeps the silu launch
+                                           front_big=1           sea_adaln_qkv at long launches too                      adaln_gemm=0          cond_mlp.2 GEMM + norm launch in front
+                                           silu=0|1              generated GEMM operand off / on    fold_ib=0             the info-bottleneck add as a launch of its own
+                                           fold_ib_gen=1         ... folded at long launches too    mlp1 / mlpnorm / mlp2=0|1   the fused MLP halves off / forced
+                                           mlpblock=0            the field MLP as two launches      projnorm=0            the last proj and the final norm as two launches
+                                           splitk=0              no split-K form of skinny GEMMs with a long contraction
+                                           graph_lanes=0         a captured graph replays its lanes in record order (engine.forward_graphed)
                                            enc=composed|fused    spatial encoder training: every EncoderBlock composed from the generic launches (default, measured
                                                                    faster) or as the fused sea_encoder_block_fwd / _bwd (bf16, width 32 or 64; other shapes always compose)
   SEA_KV          key=value,...          KV-cache rollout: fast=0 (generic step plan), hoist=0 (condition work per step), gemv=0 (step plan without the few-row launches of gemv.hip),
@@ -26,7 +34,8 @@ import os
 from typing import Dict, Optional
 
 
-def _parse(var: str) -> Dict[str, str]:
+def parse(var: str) -> Dict[str, str]:
+    """Every key=value token of a switch variable (plan_forms.resolve_forms reads SEA_PLAN / SEA_KV through this, once per plan build)."""
     out: Dict[str, str] = {}
     for tok in os.environ.get(var, "").split(","):
         if "=" in tok:
@@ -37,8 +46,8 @@ def _parse(var: str) -> Dict[str, str]:
 
 def plan(key: str, default: Optional[str] = None) -> Optional[str]:
     """SEA_PLAN token (read at every plan build: tests change it between builds)."""
-    return _parse("SEA_PLAN").get(key, default)
+    return parse("SEA_PLAN").get(key, default)
 
 
 def kv(key: str, default: Optional[str] = None) -> Optional[str]:
-    return _parse("SEA_KV").get(key, default)
+    return parse("SEA_KV").get(key, default)

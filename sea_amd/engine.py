@@ -28,6 +28,7 @@ from . import _native as N
 from . import _switches
 from . import ops
 from . import ptrcheck
+from .plan_forms import INFERENCE, resolve_forms
 
 _QKV = re.compile(r"^(.*\.)(k|q|v)\.(weight|bias)$")
 _QKV_RANK = {("q", "weight"): 0, ("k", "weight"): 1, ("v", "weight"): 2, ("q", "bias"): 3, ("k", "bias"): 4, ("v", "bias"): 5}
@@ -229,8 +230,36 @@ class _Rec:
         self.fn, self.args, self.name, self.keep, self.lane = fn, list(args), name, keep, lane
 
 
+class _Riders:
+    """The rider work of a plan's chain launches (sea_row_chain_riders): cond_mlp.2 of the modules the field MLP and the final norm read, as 128 x 128 tiles of one
+    grouped GEMM handed out to the `hosts` chain launches that may carry riders (the one behind the self-attention and the tails of the fields that are not
+    last: their results are read by the MLP)."""
+
+    def __init__(self, arr, tiles: int, hosts: int, caps: Optional[Tuple[int, ...]]):
+        self.arr, self.tiles, self.done = arr, tiles, 0
+        self.hosts_total = self.hosts_left = hosts
+        self.caps, self.host_no = caps, 0     # PlanForms.rider_caps: tiles for the first, second, third host instead of equal shares
+
+    def take(self):
+        """The share of the next chain launch, (group array, groups, first tile, tiles): as many tiles of the rider GEMM as its idle CUs take in about the launch's
+        own duration (a chain workgroup owns a CU; two tile rounds under the three-field launch behind the self-attention, one under a field's tail) — equal
+        shares, the last host takes what is left.  None when nothing is left."""
+        left = self.tiles - self.done
+        if left <= 0:
+            return None
+        if self.caps is not None:
+            take = min(left, self.caps[self.host_no] if self.host_no < len(self.caps) else 0)
+            self.host_no += 1
+        else:
+            take = left if self.hosts_left <= 1 else min(left, (self.tiles + self.hosts_total - 1) // self.hosts_total)
+            self.hosts_left -= 1
+        t0, self.done = self.done, self.done + take
+        return self.arr, len(self.arr), t0, take
+
+
 class Plan:
     """Launch list for one (B, T, mode) of TemporalModel.forward."""
+    kind = INFERENCE   # what plan_forms.resolve_forms decides for: the subclasses (TrainPlan, CondPlan) turn the inference-only forms off
 
     def __init__(self, eng: "TemporalEngine", B: int, T: int, mode: str = "full", save_for_backward: bool = False, cond=None):
         assert mode in ("full", "step")
@@ -269,6 +298,10 @@ class Plan:
         self._lane = 0                    # lane the record builders tag new records with
         self._lane_streams: Dict[int, torch.cuda.Stream] = {}
         self._zero_ib: Optional[torch.Tensor] = None   # 'concat': the zeros the info-bottleneck columns are reset to
+        self.forms = resolve_forms(m, B, T, mode, self.dt, self.kind, hoisted=cond is not None, hoisted_ib=cond is not None and len(cond.ibufs) == self.L)
+        self._mods: Dict[str, torch.Tensor] = {}        # AdaLN modulations, prefix -> [M, 2d] (_cond_mods)
+        self._riders: Optional[_Riders] = None          # rider work of the chain launches (forms.riders)
+        self._front = None                              # rider plans: (cond_mlp.2 operands of the front modules, row riders of the one-launch front), see _cond_mods
         self._build()
         self._find_hoisted()
         self._clist = None          # (SeaLaunchRec array, [(rec index, field, args list, args index)]) for sea_run_list
@@ -369,7 +402,7 @@ class Plan:
         sea_gemm_grouped launch (fp32 partial matrices, two workgroups per CU on the two-stage ring) + sea_splitk_finish: 161 -> 128 + 10 us (tools/skinny_probe.py).
         bf16, plain epilogue (bias / residual / outputs only).  SEA_PLAN=splitk=0 keeps the single launch."""
         S = 4
-        if self.dt != torch.bfloat16 or _switches.plan("splitk", "1") == "0" or len(chunk) * S > N.MAX_GROUPS or len(chunk) > N.MAX_SPLITK_GROUPS:
+        if self.dt != torch.bfloat16 or not self.forms.splitk or len(chunk) * S > N.MAX_GROUPS or len(chunk) > N.MAX_SPLITK_GROUPS:
             return False
         tiles = 0
         for d in chunk:
@@ -465,46 +498,12 @@ class Plan:
             chunk = groups[s:s + N.CHAIN_MAX_GROUPS]
             arr = self._array(N.SeaRowChain, chunk, ops.fill_row_chain)
             common = self._qkv_common(rope, hd)
-            rd = self._take_riders(len(chunk), max(g.M for g in arr)) if s == 0 else None
+            rd = self._riders.take() if s == 0 and self._riders is not None else None
             if rd is None:
                 self._cur.append(self._rec(N.lib().sea_row_chain, [arr, len(chunk), C.byref(common), 1e-5, self.code], name, (arr, common)))
             else:
-                rarr, n_r, t0, nt, ibp = rd
-                self._cur.append(self._rec(N.lib().sea_row_chain_riders, [arr, len(chunk), C.byref(common), rarr, n_r, t0, nt, (C.byref(ibp) if ibp is not None else None), 1e-5, self.code],
-                                           name, (arr, common, rarr, ibp)))
-
-    def _take_riders(self, n_groups: int, m_rows: int, last: bool = False):
-        """The share of the rider work (sea_row_chain_riders) the next chain launch carries: as many 128 x 128 tiles of the rider GEMM as its idle CUs take in about the
-        launch's own duration (a chain workgroup owns a CU; two tile rounds under the three-field launch behind the self-attention, one under a field's tail), the
-        information-bottleneck rows with the first host.  None when nothing is left."""
-        arr = getattr(self, "_rider_arr", None)
-        if arr is None:
-            return None
-        done = getattr(self, "_rider_done", 0)
-        ibp = self._rider_ib if not getattr(self, "_rider_ib_done", False) else None
-        left = self._rider_tiles - done
-        if left <= 0 and ibp is None:
-            return None
-        # measured at cfg2 (tools/chain_probe.py replay, SEA_PLAN=rider_caps): 128:128:128 tiles under the three hosts 0.2153 ms per step, 192:96:96 0.2178,
-        # 256:64:64 0.2201, 384:0:0 0.2233, 0:192:192 0.2250, no riders 0.2214 — equal shares (a rider tile, alone on its CU beside 127-192 chain
-        # workgroups, takes ~9 us; the hosts last 24 / 16 / 12 us)
-        hosts_total = getattr(self, "_rider_hosts_total", 1)
-        cap = (self._rider_tiles + hosts_total - 1) // hosts_total
-        caps = _switches.plan("rider_caps", "")   # tuning aid: "a:b:c" = tiles for the first, second, third host
-        if caps:
-            lst = [int(v) for v in caps.split(":")]
-            k = getattr(self, "_rider_host_no", 0)
-            self._rider_host_no = k + 1
-            cap = lst[k] if k < len(lst) else 0
-            take = min(left, cap)
-            self._rider_done = done + take
-            self._rider_ib_done = True
-            return arr, len(arr), done, take, ibp
-        take = left if (last or self._rider_hosts_left <= 1) else min(left, cap)
-        self._rider_hosts_left -= 1
-        self._rider_done = done + take
-        self._rider_ib_done = True
-        return arr, len(arr), done, take, ibp
+                rarr, n_r, t0, nt = rd   # (the launch's information-bottleneck rider is not used: those rows ride in the silu launch / the one-launch front)
+                self._cur.append(self._rec(N.lib().sea_row_chain_riders, [arr, len(chunk), C.byref(common), rarr, n_r, t0, nt, None, 1e-5, self.code], name, (arr, common, rarr, None)))
 
     def _qkv(self, groups: List[dict], rope: torch.Tensor, hd: int, name: str) -> None:
         """Group dicts: the arguments of ops.fill_qkv_group."""
@@ -523,11 +522,12 @@ class Plan:
             self._pos_structs.append(P)
             self._cur.append(self._rec(N.lib().sea_attention_fwd, [C.byref(P), self.code], name, P))
 
-    def _cond_mods(self, split: bool = False, riders: bool = False) -> Dict[str, torch.Tensor]:
+    def _cond_mods(self, ib_fold=()) -> Dict[str, torch.Tensor]:
         """AdaLN condition MLPs for the WHOLE model: silu launch + grouped GEMM (cond_mlp.2); returns prefix -> [M, 2d] (w | b).
-        `split`: the modules the first launch of the layer needs (AdaLN_0 of layer 0) go first on the main stream, all the others run
-        on lane 1 beside the self-attention and are joined by the caller (self._join(1)) before their first use."""
-        P, F, E, D, M, L = self.eng.params, self.F, self.E, self.D, self.M, N.lib()
+        forms.split_cond: the modules the first launch of the layer needs (AdaLN_0 of layer 0) go first on the main stream, all the others run
+        on lane 1 beside the self-attention and are joined by the caller (self._join(1)) before their first use.
+        `ib_fold`: (layer prefix, ibuf) — info-bottleneck MLPs evaluated by extra row passes of the first silu launch."""
+        P, F, E, D, M, L, fm = self.eng.params, self.F, self.E, self.D, self.M, N.lib(), self.forms
         mods: Dict[str, torch.Tensor] = {}
         if not self.adaln:
             return mods
@@ -545,13 +545,7 @@ class Plan:
         for i in range(F):
             rest.append((f"ln.{i}.", self.Eo))
 
-        # cond_mlp.0 + SiLU evaluated inside the GEMM of cond_mlp.2 (generated A operand): no hidden matrix, no silu launch.  Inference plans
-        # only (the weight gradient of cond_mlp.2 reads the hidden matrix).  The operand is recomputed by every column tile of a row panel (4x at
-        # N = 512), VALU work that pays only once the hidden matrix's HBM round trip is the larger cost: measured 0.2685 against 0.2671 ms at cfg2
-        # (M = 2024: not used), 1.215 against 1.241 ms at B = 8 (used).  SEA_PLAN=silu=1|0 forces.
-        gen_a = self._gen_a(first + rest)
-        ib_todo = list(getattr(self, "_ib_fold", []))   # (layer prefix, ibuf): info-bottleneck MLPs evaluated by extra row passes of the first silu launch
-        self._rider_arr, self._rider_ib = None, None
+        ib_todo = list(ib_fold)
 
         def silu_launch(chunk, tag):   # sea_silu_outer_ib: the hidden rows of `chunk` (dicts as ops.fill_silu_group) and the info-bottleneck rows still to do
             arr = self._array(N.SeaSiluGroup, chunk, ops.fill_silu_group) if chunk else None
@@ -564,28 +558,20 @@ class Plan:
             rec = self._rec(L.sea_silu_outer_ib, [arr, len(chunk), None, M, self.code, ibs, n_ib], tag, (arr, ibs) if chunk else (ibs,))
             self._c_patches.append((rec.args, 2))
             self._cur.append(rec)
-        if riders:
+        if fm.riders:
             # the silu launch as it is (hidden rows of every module + the information-bottleneck rows); cond_mlp.2 of AdaLN_0 and ln_cross of the (only) layer in
             # front; cond_mlp.2 of every other module as rider tiles of the chain launches
             front = first + [(pre_, d) for pre_, d in rest if "ln_cross." in pre_]
             later = [(pre_, d) for pre_, d in rest if (pre_, d) not in front]
-            # The front of the block as ONE launch (sea_adaln_qkv, round 4): the condition MLP of AdaLN_0 with its hidden rows generated in the launch, AdaLN_0 and the
-            # self-attention's q / k / v + rotary epilogue — no hidden rows, no modulation matrix and no normalised rows of these modules in memory, no QKV launch;
-            # cond_mlp.2 of ln_cross rides on the CUs it leaves idle.  SEA_PLAN=front=0 keeps silu + sea_gemm_adaln + QKV.
-            self._front_chain = (_switches.plan("front", "1") != "0" and _switches.plan("adaln_gemm", "1") != "0" and ops.adaln_qkv_supported(self.dt, E, self.H)
-                                 and F <= N.MAX_AQKV_GROUPS and not self.concat)
-            # ... and with D = 128 the ln_cross modulation of a field is that launch's third layer (hidden rows generated in the launch, 2 D = 256 columns), the hidden
-            # rows of the modules further down and the information-bottleneck rows its row riders: no silu launch at all.  SEA_PLAN=front3=0 keeps the silu launch.
-            self._front3 = self._front_chain and D == 128 and len(later) <= N.AQKV_MAX_SILU and len(ib_todo) <= 1 and _switches.plan("front3", "1") != "0"
             silu_groups, hids = [], {}
             for pre_, d in front + later:
                 mods[pre_] = self._buf(M, 2 * d)
-                if self._front_chain and ((pre_, d) in first or (self._front3 and "ln_cross." in pre_)):
+                if fm.front_chain and ((pre_, d) in first or (fm.front3 and "ln_cross." in pre_)):
                     continue   # generated inside sea_adaln_qkv
                 hids[pre_] = self._buf(M, 2 * d)
                 silu_groups.append(dict(w1=P.f32_vec(pre_ + "cond_mlp.0.weight", 2 * d), b1=P.f32_vec(pre_ + "cond_mlp.0.bias"), Hid=hids[pre_]))
-            self._front_rows = None
-            if self._front3:   # the silu / ib rows as row riders of sea_adaln_qkv (emitted by _build)
+            front_rows = None
+            if fm.front3:   # the silu / ib rows as row riders of sea_adaln_qkv (emitted by _build)
                 sarr = (N.SeaSiluGroup * max(len(silu_groups), 1))()
                 for g, gd in zip(sarr, silu_groups):
                     ops.fill_silu_group(g, **gd)
@@ -595,26 +581,24 @@ class Plan:
                     lpre, ibuf = ib_todo[0]
                     ops.fill_ib_params(ibp, [ibuf], None, **self._ib_layer(lpre))
                     ib_todo.clear()
-                self._front_rows = (sarr, len(silu_groups), ibp)
+                front_rows = (sarr, len(silu_groups), ibp)
                 silu_groups = []
             for s_ in range(0, len(silu_groups), N.MAX_SILU_GROUPS):
                 silu_launch(silu_groups[s_:s_ + N.MAX_SILU_GROUPS], "adaln.silu")
-            # cond_mlp.2 of the front modules: AdaLN_0's as the GEMM whose epilogue IS the normalisation (sea_gemm_adaln: no modulation matrix, no norm launch),
-            # ln_cross's as plain groups of the same launch — emitted by _build where the AdaLN_0 launch used to be.  SEA_PLAN=adaln_gemm=0 keeps GEMM + norm launch.
-            if _switches.plan("adaln_gemm", "1") != "0":
-                self._adaln_front = {pre_: (hids.get(pre_), P.act(pre_ + "cond_mlp.2.weight"), P.f32_vec(pre_ + "cond_mlp.2.bias")) for pre_, _ in front}
+            # cond_mlp.2 of the front modules: emitted by _build where the AdaLN_0 launch used to be (forms.adaln_front), else as a GEMM here
+            if fm.adaln_front:
+                self._front = ({pre_: hids.get(pre_) for pre_, _ in front}, front_rows)
             else:
-                self._adaln_front = None
                 self._gemm([dict(A=hids[pre_], W=P.act(pre_ + "cond_mlp.2.weight"), bias=P.f32_vec(pre_ + "cond_mlp.2.bias"), Cact=mods[pre_]) for pre_, _ in front], "adaln.cond_gemm.front")
-            self._rider_arr = self._array(N.SeaGemmGroup, [dict(A=hids[pre_], W=P.act(pre_ + "cond_mlp.2.weight"), bias=P.f32_vec(pre_ + "cond_mlp.2.bias"),
-                                                                Cact=mods[pre_]) for pre_, _ in later], ops.fill_gemm_group)
-            self._rider_tiles = sum(((M + 127) // 128) * ((2 * d + 127) // 128) for _, d in later)
-            self._keep.append((self._rider_arr, self._rider_ib))
+            arr = self._array(N.SeaGemmGroup, [dict(A=hids[pre_], W=P.act(pre_ + "cond_mlp.2.weight"), bias=P.f32_vec(pre_ + "cond_mlp.2.bias"),
+                                                    Cact=mods[pre_]) for pre_, _ in later], ops.fill_gemm_group)
+            self._riders = _Riders(arr, sum(((M + 127) // 128) * ((2 * d + 127) // 128) for _, d in later), F, fm.rider_caps)
+            self._keep.append(arr)
             return mods
 
         def emit(inst, tag):
             silu_groups, gemm_groups = [], []
-            if gen_a:
+            if fm.gen_a:
                 if ib_todo:   # no silu rows to ride on: the information-bottleneck rows as a launch of their own (added by the norm pass in front of the MLP)
                     silu_launch([], "ib.rows")
                 for pre, d in inst:
@@ -634,14 +618,9 @@ class Plan:
                 silu_launch(silu_groups[s:s + N.MAX_SILU_GROUPS], "adaln.silu" + tag)
             self._gemm(gemm_groups, "adaln.cond_gemm" + tag)
 
-        # Long launches (B = 8): AdaLN_0 of the first layer, its condition MLP and the self-attention's q / k / v as ONE launch too (sea_adaln_qkv without riders, emitted by
-        # _build) — opt-in (SEA_PLAN=front_big=1): measured at B = 8 the launch takes 171 us against 67 (condition GEMM) + 31 (norm) + 60 (QKV) as tiled launches, the forward
-        # 1.070 against 1.047 ms: with several rounds of workgroups the tiled GEMMs keep three workgroups per CU busy, the row-owning workgroup one.
-        self._front_big = (type(self) is Plan and self.mode == "full" and _switches.plan("front_big", "0") == "1" and ops.adaln_qkv_supported(self.dt, E, self.H) and F <= N.MAX_AQKV_GROUPS
-                           and not self.concat and M >= 1024)
-        if self._front_big:
+        if fm.front_big:   # AdaLN_0 of the first layer and its condition MLP are part of the one-launch front (emitted by _build)
             first = []
-        if not split:
+        if not fm.split_cond:
             emit(first + rest, "")
             return mods
         if first:
@@ -651,88 +630,29 @@ class Plan:
         self._end_lane()
         return mods
 
-    def _gen_a(self, inst) -> bool:
-        """AdaLN condition MLPs with the generated GEMM operand (no silu launch)?  Long launches only, see _cond_mods."""
-        want = _switches.plan("silu", "auto")
-        return type(self) is Plan and all(2 * d <= 1024 for _, d in inst) and (want == "1" or (want == "auto" and self.M >= 8192))
-
     # ------------------------------------------------------------------ the plan
     def _build(self) -> None:
         eng, P = self.eng, self.eng.params
         F, E, D, S, M, B, T, H = self.F, self.E, self.D, self.S, self.M, self.B, self.T, self.H
-        dt, L = self.dt, N.lib()
+        L = N.lib()
         hd_s, hd_c = E // H, D // H
         cap = self.cap
         f32 = torch.float32
 
-        # Optional lanes (parallel graph branches) for independent work — SEA_PLAN=lanes: "cond" = the condition MLPs the first launch does
-        # not need, "all" = also every finished field's MLP beside the remaining exchange stages.  At one trajectory the
-        # cross-branch dependencies of a captured HIP graph cost more than the overlap gains; from 8192 rows up the condition lane pays (1 %).
         xmode = eng.model.exchange_mode                                   # 'sea' | 'addition' | 'simple' (models/temporal.py:314-324)
         has_ib = eng.model.ib_addition_mode.lower() == "add"              # 'none': _add_info returns x (models/temporal.py:113-114)
         ib_attn = eng.model.ib_addition_mode.lower() == "attention"       # x_i += cross_attn_ib_i(x_i, ib rows) (models/temporal.py:117-118)
-        mode = _switches.plan("lanes", "auto") if type(self) is Plan and xmode == "sea" and has_ib else "none"
-        if mode == "auto":   # with the current 21-launch plan: cfg2 0.252 ms none / 0.284 cond / 0.358 all; B=8 1.166 none / 1.154 cond / 1.245 all
-            mode = "cond" if self.M >= 8192 else "none"
-        lanes = mode == "all" and F >= 2 and eng.model.add_info_after_cross
-        split_cond = mode in ("cond", "all") and self.adaln
-        # Linear + the row norm that follows it in one launch (sea_gemm_rownorm) where a tile can span the whole output row: cross_down + ln_cross,
-        # the last layer's proj + the model's final norm.  SEA_PLAN=norm=0 keeps the two-launch form (A/B measurements).
-        fuse_norm = self._fuse_norm = type(self) is Plan and _switches.plan("norm", "1") != "0"
-        # the info-bottleneck add without a launch of its own: its MLP depends on the condition only, so it is EVALUATED by extra row passes of the silu
-        # launch (into ibuf) and ADDED by the AdaLN_2 pass that follows it anyway (SeaNormGroup.addend).  Needs the silu launch (adaln, short launches)
-        # and the add after the exchange; SEA_PLAN=fold_ib=0 keeps sea_ib_add.
-        # The row-local chains between the attention launches as ONE launch each (sea_row_chain, round 4): self-attention out-projection + residual ->
-        # cross_down + ln_cross -> every q of the field and the k / v of the pairs that read its PRE-exchange rows; per field, its exchange tail ->
-        # cross_down + ln_cross of the updated rows -> the k / v of the pairs that read them.  No cross-attention QKV launch, no out-projection launch, no
-        # down + norm launch: 18 launches -> 14 at cfg2.  bf16, the widths the kernel instantiates, at most 3 fields (the segments' weights share an LDS
-        # half), short launches (a workgroup owns most of a CU's LDS: beyond a round or two of workgroups the tiled launches win; SEA_PLAN=chain_max_rows).
-        # SEA_PLAN=chain=0 keeps the 18-launch plan (the reference form of tests/test_model_gpu.py::test_optional_plans_match_default_plan).
-        chain = self._chain_plan = (type(self) is Plan and self.mode == "full" and xmode == "sea" and 1 < F <= 3 and fuse_norm and not lanes and not self.concat
-                                    and _switches.plan("chain", "1") != "0" and _switches.plan("xtail", "1") != "0" and ops.row_chain_supported(dt, D, E, F - 1, D // H)
-                                    and M <= int(_switches.plan("chain_max_rows", "4096")))
-        # ... and with them RIDERS (sea_row_chain_riders): the AdaLN condition MLPs are functions of the condition alone, and only AdaLN_0 / ln_cross of the first
-        # layer are needed in front of the first attention — the modules the field MLP and the final norm read (62 % of the condition GEMM's work at cfg2)
-        # and the information-bottleneck rows are computed by extra workgroups of the chain launches, on the CUs those leave idle (127-192 workgroups on 256
-        # CUs): the condition GEMM in front of the step covers 6 of the 12 modules.  One layer, AdaLN, the ib add behind the exchange.
-        # SEA_PLAN=riders=0 keeps the whole-model condition launches.
-        riders = self._riders = (chain and self.adaln and self.L == 1 and not split_cond and _switches.plan("riders", "1") != "0"
-                                 and (not has_ib or (eng.model.add_info_after_cross and E <= 2048)) and not ib_attn and F + F <= N.CHAIN_MAX_RIDERS)
-        # the condition GEMMs generate their operand (long launches): no silu launch for the ib rows to ride on.  SEA_PLAN=fold_ib_gen=1 gives them a launch of
-        # their own (sea_silu_outer_ib without silu rows) and folds the add into the norm pass — measured at B = 8: 29 + 40 us against 30 (ib_add) + 30 (norm): not the default
-        gen_all = self._gen_a([(None, E), (None, D)])
-        fold_ib = (type(self) is Plan and has_ib and eng.model.add_info_after_cross and self.adaln and not lanes
-                   and self.L <= N.MAX_SILU_IB and E <= 2048 and _switches.plan("fold_ib", "1") != "0"
-                   and (riders or (gen_all and _switches.plan("fold_ib_gen", "0") != "0") or (not gen_all and not split_cond)))
-        hoist_ib = self._cond_src is not None and has_ib and eng.model.add_info_after_cross and len(self._cond_src.ibufs) == self.L and E <= 2048
-        if hoist_ib:       # the info-bottleneck rows of all steps exist already: added by the norm pass in front of the MLP (AdaLN or LayerNorm alike)
-            fold_ib = True
+        fm = self.forms                                                   # which launches the plan consists of: decided in plan_forms.resolve_forms
+        lanes, chain, few, fold_ib = fm.lanes, fm.chain, fm.few, fm.fold_ib
+        if fm.hoist_ib:    # the info-bottleneck rows of all steps exist already: added by the norm pass in front of the MLP (AdaLN or LayerNorm alike)
             ibufs = [t[:M] for t in self._cond_src.ibufs]
-            self._ib_fold = []
         else:
             ibufs = [self._buf(M, E, dtype=f32) for _ in range(self.L)] if fold_ib else None
-            self._ib_fold = [(f"blocks.{l}.", ibufs[l]) for l in range(self.L)] if fold_ib else []
-        mods = self._cond_mods(split=split_cond, riders=riders)
-        cond_joined = not split_cond
-
-        def norm_params(pre, d):
-            if self.adaln:
-                return dict(mod=mods[pre], gamma=P.f32_vec(pre + "weight"), beta=P.f32_vec(pre + "bias"))
-            return dict(gamma=P.f32_vec(pre + "weight"))
-
-        # the exchange tail of a field (projections + GELU, up-projection + residual, down-projection + norm) as ONE launch: bf16, the widths the
-        # kernel instantiates, short launches (SEA_PLAN=xtail=0 keeps the three-launch form; SEA_PLAN=xtail_max_rows bounds M)
-        fuse_xtail = (fuse_norm and not lanes and xmode == "sea" and F > 1 and _switches.plan("xtail", "1") != "0"
-                      and ops.exchange_tail_supported(dt, D, E, F - 1) and M <= int(_switches.plan("xtail_max_rows", "1000000000")))   # measured: cfg2 0.281 -> 0.254 ms, B = 2 0.414 -> 0.404, B = 4 0.679 -> 0.675, B = 8 a tie (1.191)
+        mods = self._mods = self._cond_mods([(f"blocks.{l}.", ibufs[l]) for l in range(self.L)] if fm.ib_rows_here else ())
+        cond_joined = not fm.split_cond
         rope_s, rope_c = eng.rope_self, eng.rope_cross
         Eo, concat = self.Eo, self.concat
         FE = F * Eo                                             # row stride of the caller's [B, T, F, Eo] tensors
-        # KV-cache step at the shipped widths (one row per trajectory and field, embed_dim 1024 / 2048): the Linear layers as sea_gemm_fewrows /
-        # sea_qkv_rope_fewrows launches with the row norms in front of them folded in (gemv.hip) — 18 launches instead of 22.  SEA_KV=gemv=0 keeps the generic launches.
-        few = self._few = (type(self) is Plan and self.mode == "step" and T == 1 and xmode == "sea" and not concat and not ib_attn
-                           and _switches.kv("gemv", "1") != "0" and 2 * (F - 1) <= N.FEW_MAX_GROUPS and F <= N.FEW_MAX_GROUPS
-                           and ops.fewrows_supported(dt, M, [E], qkv=True, pre=True) and ops.fewrows_supported(dt, M, [S])
-                           and (F == 1 or ops.fewrows_supported(dt, M, [D], qkv=True, pre=True)))
         xr = [self._buf(M, E, dtype=f32) for _ in range(F)]     # fp32 residual stream
         xa = [self._buf(M, E) for _ in range(F)]                # act-dtype copy (GEMM A operand)
         n_e = [self._buf(M, E) for _ in range(F)]               # normalised rows, dim E
@@ -750,9 +670,7 @@ class Plan:
             Vc = [[[self._buf(B, H, hd_c, cap, zero=True) for _ in range(F)] for _ in range(F)] for _ in range(self.L)]
             att_c = [self._buf(M, D) for _ in range(max(F - 1, 1))]
             gp = self._buf(max(F - 1, 1), M, D)
-        # hidden rows of the MLP: S is a power of two (4 KiB rows at cfg2) — a 32-row workgroup's stores, and the next launch's 32-row operand tiles, would sit
-        # at one 4 KiB stride and crowd a few memory channels; 128 B of padding per row spreads them (fc1 + LN + GELU 27.0 -> 25.4 us stand-alone)
-        pad = 64 if (type(self) is Plan and S % 1024 == 0) else 0
+        pad = fm.hidden_pad   # (a power-of-two row stride would crowd a few memory channels)
         hbuf = [self._buf(M, S + pad)[:, :S] for _ in range(F)]
         hg = [self._buf(M, S + pad)[:, :S] for _ in range(F)]
         self.ws = dict(xr=xr, xa=xa, n_e=n_e, att_e=att_e, hbuf=hbuf, hg=hg)
@@ -786,77 +704,39 @@ class Plan:
             if not eng.model.add_info_after_cross and ib_attn:
                 self._ib_attn(pre, xr)
             # -- self attention: x_i += proj(attn(AdaLN_0(x_i)))
-            groups = []
-            one_launch_front = l == 0 and not few and (getattr(self, "_front_big", False) or (getattr(self, "_adaln_front", None) and getattr(self, "_front_chain", False)))
-            for i in range(F if not one_launch_front else 0):   # (the one-launch front reads the module's parameters itself: its modulation matrix does not exist)
-                g = dict(**norm_params(f"{pre}ln.exp.{i}.0.", E)) if few else dict(Yact=n_e[i], **norm_params(f"{pre}ln.exp.{i}.0.", E))
-                if first:
-                    g.update(X=xr[i], ldx=FE, X_is_x=i * Eo * 4)
-                else:
-                    g.update(X=xr[i])
-                groups.append(g)
-            if few:   # AdaLN_0 / LayerNorm as the prologue of the projection
-                self._qkv_few([dict(W=P.act(f"{pre}attn.self.{i}.q.weight", 3 * E), bias=P.f32_vec(f"{pre}attn.self.{i}.q.bias", 3 * E),
-                                    col0=0, Q=Qs[i], K=Ks[l][i], Vt=Vs[l][i]) for i in range(F)], rope_s, hd_s, "self.qkv_rope", pre=groups)
+            def norm0():   # AdaLN_0 / LayerNorm of every field (`few`: as the prologue of the projection, no output rows)
+                groups = []
+                for i in range(F):
+                    g = dict(**self._norm_params(f"{pre}ln.exp.{i}.0.")) if few else dict(Yact=n_e[i], **self._norm_params(f"{pre}ln.exp.{i}.0."))
+                    if first:
+                        g.update(X=xr[i], ldx=FE, X_is_x=i * Eo * 4)
+                    else:
+                        g.update(X=xr[i])
+                    groups.append(g)
+                return groups
+            qkv_groups = [dict(W=P.act(f"{pre}attn.self.{i}.q.weight", 3 * E), bias=P.f32_vec(f"{pre}attn.self.{i}.q.bias", 3 * E),
+                               col0=0, Q=Qs[i], K=Ks[l][i], Vt=Vs[l][i]) for i in range(F)]
+            if few:
+                self._qkv_few(qkv_groups, rope_s, hd_s, "self.qkv_rope", pre=norm0())
+            elif l == 0 and fm.one_launch_front:   # (reads the module's parameters itself: its modulation matrix does not exist)
+                self._front_launch(pre, first, xr, Qs, Ks[l], Vs[l])
             else:
-                af = getattr(self, "_adaln_front", None) if l == 0 else None
-                if l == 0 and not af and getattr(self, "_front_big", False) and not few:
-                    arr = (N.SeaAdalnQkv * F)()
-                    for g_, i in zip(arr, range(F)):
-                        mp = f"{pre}ln.exp.{i}.0."
-                        ops.fill_adaln_qkv(g_, X=xr[i], cond=None, w1=P.f32_vec(mp + "cond_mlp.0.weight", 2 * E), b1=P.f32_vec(mp + "cond_mlp.0.bias"), W2c=P.act(mp + "cond_mlp.2.weight"),
-                                           b2c=P.f32_vec(mp + "cond_mlp.2.bias"), gamma=P.f32_vec(mp + "weight"), beta=P.f32_vec(mp + "bias"), Wqkv=P.act(f"{pre}attn.self.{i}.q.weight", 3 * E),
-                                           bqkv=P.f32_vec(f"{pre}attn.self.{i}.q.bias", 3 * E), Q=Qs[i], K=Ks[l][i], Vt=Vs[l][i], ldx=(FE if first else None))
-                        g_.M = M
-                        self._c_patches.append((g_, "cond"))
-                        if first:
-                            self._x_patches.append((g_, "X", i * Eo * 4))
-                    common = N.SeaQkvCommon(rope_s.data_ptr(), self.H, hd_s, self.T, self.pos0, self.cap, ops.q_scale(hd_s))
-                    self._pos_structs.append(common)
-                    self._cur.append(self._rec(L.sea_adaln_qkv, [arr, F, C.byref(common), None, 0, None, 0, None, 0, None, 1e-5, self.code], "self.cond_adaln0_qkv_rope", (arr, common, None, None, None)))
-                elif af and getattr(self, "_front_chain", False):
-                    front3 = getattr(self, "_front3", False)
-                    arr = (N.SeaAdalnQkv * F)()
-                    for g_, i in zip(arr, range(F)):
-                        mp, lc = f"{pre}ln.exp.{i}.0.", f"{pre}ln_cross.{i}."
-                        third = dict(w1=P.f32_vec(lc + "cond_mlp.0.weight", 2 * D), b1=P.f32_vec(lc + "cond_mlp.0.bias"), W=af[lc][1], bias=af[lc][2],
-                                     out=mods[lc]) if front3 else None   # ln_cross_i's modulation as the launch's third layer
-                        ops.fill_adaln_qkv(g_, X=xr[i], cond=None, w1=P.f32_vec(mp + "cond_mlp.0.weight", 2 * E), b1=P.f32_vec(mp + "cond_mlp.0.bias"), W2c=af[mp][1], b2c=af[mp][2],
-                                           gamma=P.f32_vec(mp + "weight"), beta=P.f32_vec(mp + "bias"), Wqkv=P.act(f"{pre}attn.self.{i}.q.weight", 3 * E),
-                                           bqkv=P.f32_vec(f"{pre}attn.self.{i}.q.bias", 3 * E), Q=Qs[i], K=Ks[l][i], Vt=Vs[l][i], ldx=(FE if first else None), third=third)
-                        g_.M = M
-                        self._c_patches.append((g_, "cond"))
-                        if first:
-                            self._x_patches.append((g_, "X", i * Eo * 4))
-                    rg = [] if front3 else [(key, v) for key, v in af.items() if "ln_cross." in key]
-                    rarr = (N.SeaGemmGroup * max(len(rg), 1))()
-                    for g_, (key, (hid_, W_, b_)) in zip(rarr, rg):
-                        ops.fill_gemm_group(g_, hid_, W_, b_, Cact=mods[key])
-                    common = N.SeaQkvCommon(rope_s.data_ptr(), self.H, hd_s, self.T, self.pos0, self.cap, ops.q_scale(hd_s))
-                    self._pos_structs.append(common)
-                    sarr, n_s, ibp = self._front_rows if front3 else (None, 0, None)
-                    rec = self._rec(L.sea_adaln_qkv, [arr, F, C.byref(common), (rarr if rg else None), len(rg), (sarr if n_s else None), n_s, None, (M if (n_s or ibp is not None) else 0),
-                                                      (C.byref(ibp) if ibp is not None else None), 1e-5, self.code], "self.cond_adaln0_qkv_rope", (arr, common, rarr, sarr, ibp))
-                    if n_s or ibp is not None:
-                        self._c_patches.append((rec.args, 7))
-                    self._cur.append(rec)
-                elif af:
+                if l == 0 and fm.adaln_front:
+                    hid = self._front[0]
                     ag = []
                     for i in range(F):
-                        hid_, W_, b_ = af[f"{pre}ln.exp.{i}.0."]
-                        g = dict(A=hid_, W=W_, bias=b_, X=xr[i], gamma=P.f32_vec(f"{pre}ln.exp.{i}.0.weight"), beta=P.f32_vec(f"{pre}ln.exp.{i}.0.bias"), Yact=n_e[i])
+                        mp = f"{pre}ln.exp.{i}.0."
+                        g = dict(A=hid[mp], W=P.act(mp + "cond_mlp.2.weight"), bias=P.f32_vec(mp + "cond_mlp.2.bias"), X=xr[i], gamma=P.f32_vec(mp + "weight"), beta=P.f32_vec(mp + "bias"), Yact=n_e[i])
                         if first:
                             g.update(ldx=FE, X_is_x=i * Eo * 4)
                         ag.append(g)
-                    for key, (hid_, W_, b_) in af.items():
+                    for key, hid_ in hid.items():
                         if "ln_cross." in key:
-                            ag.append(dict(A=hid_, W=W_, bias=b_, Yact=mods[key]))
+                            ag.append(dict(A=hid_, W=P.act(key + "cond_mlp.2.weight"), bias=P.f32_vec(key + "cond_mlp.2.bias"), Yact=mods[key]))
                     self._adaln(ag, "self.cond_adaln0")
                 else:
-                    self._norm(groups, E, "self.adaln0")
-                if not ((af and getattr(self, "_front_chain", False)) or (l == 0 and not af and getattr(self, "_front_big", False) and not few)):
-                    self._qkv([dict(A=n_e[i], W=P.act(f"{pre}attn.self.{i}.q.weight", 3 * E), bias=P.f32_vec(f"{pre}attn.self.{i}.q.bias", 3 * E),
-                                    col0=0, Q=Qs[i], K=Ks[l][i], Vt=Vs[l][i]) for i in range(F)], rope_s, hd_s, "self.qkv_rope")
+                    self._norm(norm0(), E, "self.adaln0")
+                self._qkv([dict(A=n_e[i], **g) for i, g in enumerate(qkv_groups)], rope_s, hd_s, "self.qkv_rope")
             self._attn([dict(Q=Qs[i], K=Ks[l][i], Vt=Vs[l][i], O=att_e[i]) for i in range(F)], hd_s, E, "self.attention")
             groups = []
             for i in range(F):
@@ -867,7 +747,6 @@ class Plan:
                     g.update(R=xr[i])
                 groups.append(g)
             if chain:
-                self._rider_hosts_left = self._rider_hosts_total = F   # (SEA_PLAN=rider_caps overrides) chain launches of this layer that may carry riders: this one and the tails of the fields that are not last (their results are read by the MLP)
                 # out-projection + residual, cross_down + ln_cross of the PRE-exchange rows, and from those normalised rows (never stored): q_ij for every
                 # j != i, and k / v of the pairs (a, i), a < i — field a runs its cross-attention before field i is updated (models/temporal.py:187-192)
                 groups = []
@@ -880,7 +759,7 @@ class Plan:
                         ca = f"{pre}cross_attn.{a}.{i}."
                         proj.append(dict(W=P.act(ca + "k.weight", 2 * D), bias=P.f32_vec(ca + "k.bias", 2 * D), col0=D, K=Kc[l][a][i], Vt=Vc[l][a][i]))
                     g = dict(a2=att_e[i], W2=P.act(f"{pre}attn.self.{i}.projection.weight"), Xin=xr[i], X=xr[i], proj=proj,
-                             down=dict(W=P.act(f"{pre}cross_down.{i}.weight"), bias=P.f32_vec(f"{pre}cross_down.{i}.bias"), **norm_params(f"{pre}ln_cross.{i}.", D)))
+                             down=dict(W=P.act(f"{pre}cross_down.{i}.weight"), bias=P.f32_vec(f"{pre}cross_down.{i}.bias"), **self._norm_params(f"{pre}ln_cross.{i}.")))
                     if first:
                         g.update(ldxin=FE, Xin_is_x=i * Eo * 4)
                     groups.append(g)
@@ -895,13 +774,7 @@ class Plan:
                 # -- 'addition' exchange (models/temporal.py:291-301; Jacobi: every field read at its pre-exchange value): down-projection + norm of all
                 # fields in one launch, s = GELU(sum_j n_j) as an identity-weight GEMM over F segments, x_i += cross_up_i(s) in one grouped launch
                 ndall = self._buf(F, M, D)
-                if fuse_norm and D <= 256 and D % 16 == 0:
-                    self._gemm_norm([dict(A=xa[j], W=P.act(f"{pre}cross_down.{j}.weight"), bias=P.f32_vec(f"{pre}cross_down.{j}.bias"), Yact=ndall[j],
-                                          **norm_params(f"{pre}ln_cross.{j}.", D)) for j in range(F)], "add.down_norm")
-                else:
-                    self._gemm([dict(A=xa[j], W=P.act(f"{pre}cross_down.{j}.weight"), bias=P.f32_vec(f"{pre}cross_down.{j}.bias"), C32=dn[j])
-                                for j in range(F)], "add.down")
-                    self._norm([dict(X=dn[j], Yact=ndall[j], **norm_params(f"{pre}ln_cross.{j}.", D)) for j in range(F)], D, "add.norm")
+                self._down_norm(pre, range(F), xa, dn, ndall, "add")
                 sg = self._buf(M, D)
                 self._gemm([dict(A=ndall[0], W=eng.eye(D), n_seg=F, a_seg_stride=M * D, Cact=sg, act=1)], "add.sum_gelu")
                 self._gemm([dict(A=sg, W=P.act(f"{pre}cross_up.{i}.weight"), bias=P.f32_vec(f"{pre}cross_up.{i}.bias"), R=xr[i], C32=xr[i])
@@ -915,13 +788,7 @@ class Plan:
                 nrm = [self._buf(M, D) for _ in range(F)]
                 pe_t = self._buf(M, D, dtype=f32)
                 pe_t.copy_(blk_pe(eng, l)[:T].repeat(B, 1))
-                if fuse_norm and D <= 256 and D % 16 == 0:
-                    self._gemm_norm([dict(A=xa[j], W=P.act(f"{pre}cross_down.{j}.weight"), bias=P.f32_vec(f"{pre}cross_down.{j}.bias"), Yact=nrm[j],
-                                          **norm_params(f"{pre}ln_cross.{j}.", D)) for j in range(F)], "pool.down_norm")
-                else:
-                    self._gemm([dict(A=xa[j], W=P.act(f"{pre}cross_down.{j}.weight"), bias=P.f32_vec(f"{pre}cross_down.{j}.bias"), C32=dn[j])
-                                for j in range(F)], "pool.down")
-                    self._norm([dict(X=dn[j], Yact=nrm[j], **norm_params(f"{pre}ln_cross.{j}.", D)) for j in range(F)], D, "pool.norm")
+                self._down_norm(pre, range(F), xa, dn, nrm, "pool")
                 self._gemm([dict(A=nrm[j], W=eng.eye(D), R=pe_t, Cact=big[:, j * D:(j + 1) * D]) for j in range(F)], "pool.pe_add")
                 hp, pool = self._buf(M, 2 * D), self._buf(M, D)
                 self._gemm([dict(A=big[:, :FD], W=P.act(f"{pre}pool_update.0.weight"), bias=P.f32_vec(f"{pre}pool_update.0.bias"), Cact=hp, act=1)], "pool.update0")
@@ -953,9 +820,9 @@ class Plan:
                     for s, j in enumerate(others):
                         ca = f"{pre}cross_attn.{i}.{j}."
                         qkv_groups.append(dict(W=P.act(ca + "q.weight"), bias=P.f32_vec(ca + "q.bias"), col0=0, Q=Qc[s]))
-                        qkv_pre.append(dict(X=dn[i], **norm_params(f"{pre}ln_cross.{i}.", D)))
+                        qkv_pre.append(dict(X=dn[i], **self._norm_params(f"{pre}ln_cross.{i}.")))
                         qkv_groups.append(dict(W=P.act(ca + "k.weight", 2 * D), bias=P.f32_vec(ca + "k.bias", 2 * D), col0=D, K=Kc[l][i][j], Vt=Vc[l][i][j]))
-                        qkv_pre.append(dict(X=dn[j], **norm_params(f"{pre}ln_cross.{j}.", D)))
+                        qkv_pre.append(dict(X=dn[j], **self._norm_params(f"{pre}ln_cross.{j}.")))
                         probs.append(dict(Q=Qc[s], K=Kc[l][i][j], Vt=Vc[l][i][j], O=att_c[s]))
                         proj_groups.append(dict(A=att_c[s], W=P.act(ca + "projection.weight"), Cact=gp[s], act=1))
                     self._qkv_few(qkv_groups, rope_c, hd_c, f"cross{i}.qkv_rope", pre=qkv_pre)
@@ -977,18 +844,12 @@ class Plan:
                         proj.append(dict(W=P.act(ca + "k.weight", 2 * D), bias=P.f32_vec(ca + "k.bias", 2 * D), col0=D, K=Kc[l][b_][i], Vt=Vc[l][b_][i]))
                     down = None
                     if i < F - 1:
-                        down = dict(W=P.act(f"{pre}cross_down.{i}.weight"), bias=P.f32_vec(f"{pre}cross_down.{i}.bias"), **norm_params(f"{pre}ln_cross.{i}.", D))
+                        down = dict(W=P.act(f"{pre}cross_down.{i}.weight"), bias=P.f32_vec(f"{pre}cross_down.{i}.bias"), **self._norm_params(f"{pre}ln_cross.{i}."))
                     self._chain([dict(att=[att_c[s_] for s_ in range(len(others))], Wp=[P.act(f"{pre}cross_attn.{i}.{j}.projection.weight") for j in others],
                                       W2=P.act(f"{pre}cross_up.{i}.weight"), b2=P.f32_vec(f"{pre}cross_up.{i}.bias"), bias_scale=float(F - 1), Xin=xr[i], X=xr[i],
                                       down=down, proj=proj)], rope_c, hd_c, f"cross{i}.tail")
             elif F > 1 and xmode == "sea":
-                if fuse_norm and D <= 256 and D % 16 == 0:
-                    self._gemm_norm([dict(A=xa[j], W=P.act(f"{pre}cross_down.{j}.weight"), bias=P.f32_vec(f"{pre}cross_down.{j}.bias"), Yact=nd_old[j],
-                                          **norm_params(f"{pre}ln_cross.{j}.", D)) for j in range(F)], "cross.down_norm_old")
-                else:
-                    self._gemm([dict(A=xa[j], W=P.act(f"{pre}cross_down.{j}.weight"), bias=P.f32_vec(f"{pre}cross_down.{j}.bias"), C32=dn[j])
-                                for j in range(F)], "cross.down_old")
-                    self._norm([dict(X=dn[j], Yact=nd_old[j], **norm_params(f"{pre}ln_cross.{j}.", D)) for j in range(F)], D, "cross.norm_old")
+                self._down_norm(pre, range(F), xa, dn, nd_old, "cross", "_old")
                 for i in range(F):
                     others = [j for j in range(F) if j != i]
                     qkv_groups, probs, proj_groups = [], [], []
@@ -1002,13 +863,13 @@ class Plan:
                         proj_groups.append(dict(A=att_c[s], W=P.act(ca + "projection.weight"), Cact=gp[s], act=1))
                     self._qkv(qkv_groups, rope_c, hd_c, f"cross{i}.qkv_rope")
                     self._attn(probs, hd_c, D, f"cross{i}.attention")
-                    if fuse_xtail:
+                    if fm.xtail:
                         # everything between this field's cross-attention and the next field's: projections + GELU, up-projection of the sum + residual,
                         # down-projection + ln_cross of the updated field, in one launch (a workgroup carries 16 rows through the three layers)
                         down = None
                         if i < F - 1:
                             down = dict(W=P.act(f"{pre}cross_down.{i}.weight"), bias=P.f32_vec(f"{pre}cross_down.{i}.bias"), Yact=nd_new[i],
-                                        **norm_params(f"{pre}ln_cross.{i}.", D))
+                                        **self._norm_params(f"{pre}ln_cross.{i}."))
                         self._xtail([att_c[s] for s in range(len(others))], [P.act(f"{pre}cross_attn.{i}.{j}.projection.weight") for j in others],
                                     P.act(f"{pre}cross_up.{i}.weight"), P.f32_vec(f"{pre}cross_up.{i}.bias"), float(F - 1), xr[i], down, f"cross{i}.tail")
                         continue
@@ -1024,16 +885,11 @@ class Plan:
                         if i < F - 1:
                             self._fork(2 + i)
                         self._ib(pre, [xr[i]])
-                        self._mlp_proj(pre, [i], xr, xm, n_e, hbuf, hg, mods, last, tag=f".f{i}")
+                        self._mlp_proj(pre, [i], xr, xm, n_e, hbuf, hg, last, tag=f".f{i}")
                         if i < F - 1:
                             self._end_lane()
-                    if i < F - 1 and fuse_norm and D <= 256 and D % 16 == 0:
-                        self._gemm_norm([dict(A=xa[i], W=P.act(f"{pre}cross_down.{i}.weight"), bias=P.f32_vec(f"{pre}cross_down.{i}.bias"), Yact=nd_new[i],
-                                              **norm_params(f"{pre}ln_cross.{i}.", D))], f"cross{i}.down_norm_new")
-                    elif i < F - 1:
-                        self._gemm([dict(A=xa[i], W=P.act(f"{pre}cross_down.{i}.weight"), bias=P.f32_vec(f"{pre}cross_down.{i}.bias"), C32=dn[i])],
-                                   f"cross{i}.down_new")
-                        self._norm([dict(X=dn[i], Yact=nd_new[i], **norm_params(f"{pre}ln_cross.{i}.", D))], D, f"cross{i}.norm_new")
+                    if i < F - 1:
+                        self._down_norm(pre, [i], xa, dn, nd_new, f"cross{i}", "_new")
             if lanes:
                 for i in range(F - 1):
                     self._join(2 + i)
@@ -1042,76 +898,100 @@ class Plan:
                 self._ib(pre, xr)
             if eng.model.add_info_after_cross and ib_attn:
                 self._ib_attn(pre, xr)
-            self._mlp_proj(pre, list(range(F)), xr, xa, n_e, hbuf, hg, mods, last, addend=(ibufs[l] if fold_ib else None), few=few)
+            self._mlp_proj(pre, list(range(F)), xr, xa, n_e, hbuf, hg, last, addend=(ibufs[l] if fold_ib else None))
 
-    def _mlp_proj(self, pre, fields, xr, xm, n_e, hbuf, hg, mods, final_norm, tag="", addend=None, few=False) -> bool:
+    def _norm_params(self, pre: str) -> dict:
+        """The gains of the row norm `pre` (AdaLN: with the module's modulation rows) as arguments of ops.fill_norm_group and its kin."""
+        P = self.eng.params
+        if self.adaln:
+            return dict(mod=self._mods[pre], gamma=P.f32_vec(pre + "weight"), beta=P.f32_vec(pre + "bias"))
+        return dict(gamma=P.f32_vec(pre + "weight"))
+
+    def _down_norm(self, pre, fields, xa, dn, Y, stem: str, suffix: str = "") -> None:
+        """Y_j = ln_cross_j(cross_down_j(xa_j)) for the listed fields: one sea_gemm_rownorm launch (forms.down_norm), else GEMM (into dn_j) + row norm."""
+        P = self.eng.params
+        lin = lambda j: dict(A=xa[j], W=P.act(f"{pre}cross_down.{j}.weight"), bias=P.f32_vec(f"{pre}cross_down.{j}.bias"))  # noqa: E731
+        if self.forms.down_norm:
+            self._gemm_norm([dict(Yact=Y[j], **lin(j), **self._norm_params(f"{pre}ln_cross.{j}.")) for j in fields], f"{stem}.down_norm{suffix}")
+        else:
+            self._gemm([dict(C32=dn[j], **lin(j)) for j in fields], f"{stem}.down{suffix}")
+            self._norm([dict(X=dn[j], Yact=Y[j], **self._norm_params(f"{pre}ln_cross.{j}.")) for j in fields], self.D, f"{stem}.norm{suffix}")
+
+    def _front_launch(self, pre, first, xr, Qs, Ks, Vs) -> None:
+        """The front of the first block as ONE launch (sea_adaln_qkv): the condition MLP of AdaLN_0 with its hidden rows generated in the launch, AdaLN_0 and the
+        self-attention's q / k / v + rotary epilogue.  A rider plan's (forms.front_chain) also carries cond_mlp.2 of ln_cross: as plain GEMM groups on the CUs the
+        launch leaves idle, or — forms.front3 — as every field's third layer, the silu / information-bottleneck rows of _cond_mods then being its row riders."""
+        P, F, E, D, M, Eo, fm = self.eng.params, self.F, self.E, self.D, self.M, self.Eo, self.forms
+        hid, rows = self._front if fm.front_chain else (None, None)
+        arr = (N.SeaAdalnQkv * F)()
+        for g_, i in zip(arr, range(F)):
+            mp, lc = f"{pre}ln.exp.{i}.0.", f"{pre}ln_cross.{i}."
+            third = dict(w1=P.f32_vec(lc + "cond_mlp.0.weight", 2 * D), b1=P.f32_vec(lc + "cond_mlp.0.bias"), W=P.act(lc + "cond_mlp.2.weight"), bias=P.f32_vec(lc + "cond_mlp.2.bias"),
+                         out=self._mods[lc]) if fm.front3 else None   # ln_cross_i's modulation as the launch's third layer
+            ops.fill_adaln_qkv(g_, X=xr[i], cond=None, w1=P.f32_vec(mp + "cond_mlp.0.weight", 2 * E), b1=P.f32_vec(mp + "cond_mlp.0.bias"), W2c=P.act(mp + "cond_mlp.2.weight"),
+                               b2c=P.f32_vec(mp + "cond_mlp.2.bias"), gamma=P.f32_vec(mp + "weight"), beta=P.f32_vec(mp + "bias"), Wqkv=P.act(f"{pre}attn.self.{i}.q.weight", 3 * E),
+                               bqkv=P.f32_vec(f"{pre}attn.self.{i}.q.bias", 3 * E), Q=Qs[i], K=Ks[i], Vt=Vs[i], ldx=(F * Eo if first else None), third=third)
+            g_.M = M
+            self._c_patches.append((g_, "cond"))
+            if first:
+                self._x_patches.append((g_, "X", i * Eo * 4))
+        rg = [key for key in hid if "ln_cross." in key] if fm.front_chain and not fm.front3 else []   # plain rider groups
+        rarr = (N.SeaGemmGroup * max(len(rg), 1))() if fm.front_chain else None
+        for g_, key in zip(rarr or (), rg):
+            ops.fill_gemm_group(g_, hid[key], P.act(key + "cond_mlp.2.weight"), P.f32_vec(key + "cond_mlp.2.bias"), Cact=self._mods[key])
+        common = self._qkv_common(self.eng.rope_self, E // self.H)
+        sarr, n_s, ibp = rows if rows is not None else (None, 0, None)   # row riders
+        rec = self._rec(N.lib().sea_adaln_qkv, [arr, F, C.byref(common), (rarr if rg else None), len(rg), (sarr if n_s else None), n_s, None, (M if (n_s or ibp is not None) else 0),
+                                                (C.byref(ibp) if ibp is not None else None), 1e-5, self.code], "self.cond_adaln0_qkv_rope", (arr, common, rarr, sarr, ibp))
+        if n_s or ibp is not None:
+            self._c_patches.append((rec.args, 7))
+        self._cur.append(rec)
+
+    def _mlp_proj(self, pre, fields, xr, xm, n_e, hbuf, hg, final_norm, tag="", addend=None) -> bool:
         """x_i += W2 gelu(LN(W1 AdaLN_2(x_i))) ; x_i = proj_i(x_i) for the listed fields (models/temporal.py:143-146), optionally followed
         by the model's final per-field norm written straight into out (models/temporal.py:412-415)."""
         P, E, S, Eo, FE = self.eng.params, self.E, self.S, self.Eo, self.F * self.Eo
         xo = xr if Eo == E else [t[:, :Eo] for t in xr]   # the proj output / the next block's input rows ('concat': the first Eo columns of the widened rows)
 
-        def norm_params(p_, d):
-            if self.adaln:
-                return dict(mod=mods[p_], gamma=P.f32_vec(p_ + "weight"), beta=P.f32_vec(p_ + "bias"))
-            return dict(gamma=P.f32_vec(p_ + "weight"))
-
-        if few:
+        fm = self.forms
+        if fm.few:
             # KV-cache step at the shipped widths: [ib add + AdaLN_2 / LayerNorm] fc1 | [LayerNorm + GELU] fc2 + residual | proj | final norm.
             # x + ib goes to rows of its own (xq): the prologue runs in every workgroup of fc1, so it must not update the rows it reads
             xq = [self._buf(self.M, E, dtype=torch.float32) for _ in fields] if addend is not None else None
             res = xq if addend is not None else [xr[i] for i in fields]
-            pre_n = [dict(X=xr[i], **(dict(addend=addend, Xout=xq[k]) if addend is not None else {}), **norm_params(f"{pre}ln.exp.{i}.2.", E)) for k, i in enumerate(fields)]
+            pre_n = [dict(X=xr[i], **(dict(addend=addend, Xout=xq[k]) if addend is not None else {}), **self._norm_params(f"{pre}ln.exp.{i}.2.")) for k, i in enumerate(fields)]
             self._gemm_few([dict(W=P.act(f"{pre}mlp.{i}.layers.0.weight"), bias=P.f32_vec(f"{pre}mlp.{i}.layers.0.bias"), Cact=hbuf[i]) for i in fields], "mlp.fc1" + tag, pre=pre_n)
             ln_h = [dict(X=hbuf[i], gamma=P.f32_vec(f"{pre}mlp.{i}.layers.1.weight"), beta=P.f32_vec(f"{pre}mlp.{i}.layers.1.bias")) for i in fields]
-            fold_ln = S <= 8192   # LayerNorm + GELU of the hidden rows as the prologue of fc2 while re-reading the row and its gains / shifts per workgroup stays below the weight stream
+            fold_ln = fm.few_fold_ln   # LayerNorm + GELU of the hidden rows as the prologue of fc2
             if not fold_ln:
                 self._norm([dict(Yact=hg[i], **g_) for i, g_ in zip(fields, ln_h)], S, "mlp.ln_gelu" + tag, x_is_act=True, gelu=True)
             self._gemm_few([dict(A=(None if fold_ln else hg[i]), W=P.act(f"{pre}mlp.{i}.layers.3.weight"), bias=P.f32_vec(f"{pre}mlp.{i}.layers.3.bias"), R=res[k], Cact=xm[i])
                             for k, i in enumerate(fields)], "mlp.fc2" + tag, pre=(ln_h if fold_ln else None), pre_act=fold_ln, pre_gelu=fold_ln)
             self._gemm_few([dict(A=xm[i], W=P.act(f"{pre}proj.{i}.weight"), bias=P.f32_vec(f"{pre}proj.{i}.bias"), C32=xo[i]) for i in fields], "proj" + tag)
             if final_norm:
-                self._norm([dict(X=xo[i], Y32=xo[i], ldy32=FE, Y_is_out=i * Eo * 4, **norm_params(f"ln.{i}.", Eo)) for i in fields], Eo, "final.norm" + tag)
+                self._norm([dict(X=xo[i], Y32=xo[i], ldy32=FE, Y_is_out=i * Eo * 4, **self._norm_params(f"ln.{i}.")) for i in fields], Eo, "final.norm" + tag)
             return final_norm
-        # Linear + nn.LayerNorm + GELU in one launch where the kernel is instantiated (bf16; SEA_PLAN=mlp1=0 keeps the two launches, =1 forces
-        # the one launch).  Every workgroup of that kernel streams the whole of W1, so it needs enough 32-row tiles to pay: with the few rows
-        # of a KV-cache step the two launches are faster (0.143 vs 0.163 ms per step at cfg2), hence the row threshold.
-        want = _switches.plan("mlp1", "auto")
-        fused = (type(self) is Plan and want != "0" and (want == "1" or self.M >= 1024) and ops.mlp_fc1_supported(self.dt, E, S) and len(fields) <= N.MAX_MLP_GROUPS)
-        # ... and the row pass in front of it (info-bottleneck add + AdaLN_2 / LayerNorm) as that launch's prologue: a workgroup owns its 32 rows from the
-        # fp32 residual stream to the activated hidden rows.  Measured (graph replay): cfg2 0.2472 -> 0.2440 ms (the launch itself 27.4 -> 31.2-32.2 us: its
-        # loads sit in front of the weight stream; the row pass it replaces is 7.8 us), B = 8 1.127 -> 1.138 ms (142 -> 171 us per launch against a 32 us row
-        # pass that runs at HBM speed) — used for short launches only.  SEA_PLAN=mlpnorm=0 / 1 forces.
-        wn = _switches.plan("mlpnorm", "auto")
-        norm_in = fused and (wn == "1" or (wn == "auto" and self.M <= 4096))
+        fused, norm_in = fm.mlp_fc1, fm.mlp_norm_in   # fc1 + LayerNorm + GELU as one launch; ... with the row pass in front of it as its prologue
         extra = (lambda i: dict(addend=addend, Xout=xr[i])) if addend is not None else (lambda i: {})   # x_i += ib rides in this pass
-        # The two fused launches as ONE (sea_mlp_block: the activated hidden rows stay in the owning workgroup's registers; no hg matrix, one launch boundary less, the
-        # x + ib rows are not written back — the block's residual is formed from x and ib again).  Short launches, where both halves are fused.  SEA_PLAN=mlpblock=0 keeps two launches.
-        # Long launches too (B = 8, M = 16192: 262 us against ib_add 30 + AdaLN_2 30 + fc1 + LN + GELU 160 + fc2 88 + proj + norm 55), there always with the norm
-        # prologue: the row pass it replaces and the hidden rows it keeps to itself are 0.6 GB of traffic.
-        w2 = _switches.plan("mlp2", "auto")
-        two = (type(self) is Plan and (w2 == "1" or (w2 == "auto" and 1024 <= self.M)) and ops.mlp_fc1_supported(self.dt, E, S) and Eo == E and len(fields) <= N.MAX_MLP_GROUPS)
-        if fused and two and _switches.plan("mlpblock", "1") != "0":
-            norm_in = norm_in or (self.M > 4096 and wn != "0")
+        if not norm_in:
+            self._norm([dict(X=xr[i], Yact=n_e[i], **extra(i), **self._norm_params(f"{pre}ln.exp.{i}.2.")) for i in fields], E, ("mlp.ib_adaln2" if addend is not None else "mlp.adaln2") + tag)
+        if fm.mlp_block:   # the whole field MLP + proj (+ final norm) as ONE launch (sea_mlp_block)
             a1, a2 = (N.SeaMlpGroup * len(fields))(), (N.SeaMlp2Group * len(fields))()
-            if not norm_in:
-                self._norm([dict(X=xr[i], Yact=n_e[i], **extra(i), **norm_params(f"{pre}ln.exp.{i}.2.", E)) for i in fields], E, ("mlp.ib_adaln2" if addend is not None else "mlp.adaln2") + tag)
             for g1, g2, i in zip(a1, a2, fields):
-                nrm = dict(X32=xr[i], **(dict(addend=addend) if addend is not None else {}), **norm_params(f"{pre}ln.exp.{i}.2.", E)) if norm_in else None
+                nrm = dict(X32=xr[i], **(dict(addend=addend) if addend is not None else {}), **self._norm_params(f"{pre}ln.exp.{i}.2.")) if norm_in else None
                 ops.fill_mlp_group(g1, None if norm_in else n_e[i], P.act(f"{pre}mlp.{i}.layers.0.weight"), P.f32_vec(f"{pre}mlp.{i}.layers.0.bias"),
                                    P.f32_vec(f"{pre}mlp.{i}.layers.1.weight"), P.f32_vec(f"{pre}mlp.{i}.layers.1.bias"), None, nrm)
-                fin = norm_params(f"ln.{i}.", E) if final_norm else {}
+                fin = self._norm_params(f"ln.{i}.") if final_norm else {}
                 ops.fill_mlp2_group(g2, None, P.act(f"{pre}mlp.{i}.layers.3.weight"), P.f32_vec(f"{pre}mlp.{i}.layers.3.bias"), (None if norm_in else xr[i]),
                                     P.act(f"{pre}proj.{i}.weight"), P.f32_vec(f"{pre}proj.{i}.bias"), Y32=xr[i], ldy32=(FE if final_norm else None), M=g1.M, **fin)
                 if final_norm:
                     self._out_patches.append((g2, "Y32", i * E * 4))
             self._cur.append(self._rec(N.lib().sea_mlp_block, [a1, a2, len(fields), 1e-5, self.code], ("mlp.block_norm" if final_norm else "mlp.block") + tag, (a1, a2)))
             return final_norm
-        if not norm_in:
-            self._norm([dict(X=xr[i], Yact=n_e[i], **extra(i), **norm_params(f"{pre}ln.exp.{i}.2.", E)) for i in fields], E, ("mlp.ib_adaln2" if addend is not None else "mlp.adaln2") + tag)
         if fused:
             arr = (N.SeaMlpGroup * len(fields))()
             for g_, i in zip(arr, fields):
-                nrm = dict(X32=xr[i], **extra(i), **norm_params(f"{pre}ln.exp.{i}.2.", E)) if norm_in else None
+                nrm = dict(X32=xr[i], **extra(i), **self._norm_params(f"{pre}ln.exp.{i}.2.")) if norm_in else None
                 ops.fill_mlp_group(g_, None if norm_in else n_e[i], P.act(f"{pre}mlp.{i}.layers.0.weight"), P.f32_vec(f"{pre}mlp.{i}.layers.0.bias"),
                                    P.f32_vec(f"{pre}mlp.{i}.layers.1.weight"), P.f32_vec(f"{pre}mlp.{i}.layers.1.bias"), hg[i], nrm)
             self._cur.append(self._rec(N.lib().sea_mlp_fc1_ln_gelu, [arr, len(fields), 1e-5, self.code], "mlp.fc1_ln_gelu" + tag, arr))   # (with or without the norm prologue: one name for the profiles)
@@ -1120,15 +1000,10 @@ class Plan:
                         for i in fields], "mlp.fc1" + tag)
             self._norm([dict(X=hbuf[i], gamma=P.f32_vec(f"{pre}mlp.{i}.layers.1.weight"), beta=P.f32_vec(f"{pre}mlp.{i}.layers.1.bias"), Yact=hg[i])
                         for i in fields], S, "mlp.ln_gelu" + tag, x_is_act=True, gelu=True)
-        # fc2 + residual, proj and — after the last layer — the model's final norm in one launch where the kernel is instantiated (the same shapes as the
-        # fc1 kernel): a workgroup owns 32 complete rows through both Linear layers.  Measured (plain replay, same box): cfg2 0.2373 -> 0.2358 ms (the launch
-        # 30.8 us against 19.8 + 7.1 + 5.6 with two boundaries less: a 32-row workgroup per CU streams W2 at a third of the rate three co-resident 64 x 64
-        # tiles do), B = 8 1.108 -> 1.18 ms (200 us against 76 + 21 + 31) — short launches only.  SEA_PLAN=mlp2=0 / 1 forces.
-        w2 = _switches.plan("mlp2", "auto")
-        if (type(self) is Plan and (w2 == "1" or (w2 == "auto" and 1024 <= self.M <= 4096)) and ops.mlp_fc1_supported(self.dt, E, S) and Eo == E and len(fields) <= N.MAX_MLP_GROUPS):
+        if fm.mlp_fc2_proj:   # fc2 + residual, proj and — after the last layer — the model's final norm in one launch (sea_mlp_fc2_proj_norm)
             arr = (N.SeaMlp2Group * len(fields))()
             for g_, i in zip(arr, fields):
-                nrm = norm_params(f"ln.{i}.", E) if final_norm else {}
+                nrm = self._norm_params(f"ln.{i}.") if final_norm else {}
                 ops.fill_mlp2_group(g_, hg[i], P.act(f"{pre}mlp.{i}.layers.3.weight"), P.f32_vec(f"{pre}mlp.{i}.layers.3.bias"), xr[i],
                                     P.act(f"{pre}proj.{i}.weight"), P.f32_vec(f"{pre}proj.{i}.bias"), Y32=xr[i], ldy32=(FE if final_norm else None), **nrm)
                 if final_norm:
@@ -1137,15 +1012,13 @@ class Plan:
             return final_norm
         self._gemm([dict(A=hg[i], W=P.act(f"{pre}mlp.{i}.layers.3.weight"), bias=P.f32_vec(f"{pre}mlp.{i}.layers.3.bias"), R=xr[i], Cact=xm[i])
                     for i in fields], "mlp.fc2" + tag)
-        # the last layer's proj + the model's final norm in one launch (sea_gemm_rownorm: a tile spans the whole output row): at B = 8 two launches of 23 + 31 us
-        # (the norm re-reads the rows the proj has just written: 100 MB) -> one.  SEA_PLAN=norm=0 / projnorm=0 keep the two launches.
-        if final_norm and getattr(self, "_fuse_norm", False) and type(self) is Plan and Eo <= 256 and Eo % 16 == 0 and Eo == E and _switches.plan("projnorm", "1") != "0":
+        if final_norm and fm.proj_norm:   # the last layer's proj + the model's final norm in one launch (sea_gemm_rownorm)
             self._gemm_norm([dict(A=xm[i], W=P.act(f"{pre}proj.{i}.weight"), bias=P.f32_vec(f"{pre}proj.{i}.bias"), Y32=xo[i], ldy32=FE, Y_is_out=i * Eo * 4,
-                                  **norm_params(f"ln.{i}.", Eo)) for i in fields], "proj_norm" + tag)
+                                  **self._norm_params(f"ln.{i}.")) for i in fields], "proj_norm" + tag)
             return final_norm
         self._gemm([dict(A=xm[i], W=P.act(f"{pre}proj.{i}.weight"), bias=P.f32_vec(f"{pre}proj.{i}.bias"), C32=xo[i]) for i in fields], "proj" + tag)
         if final_norm:
-            self._norm([dict(X=xo[i], Y32=xo[i], ldy32=FE, Y_is_out=i * Eo * 4, **norm_params(f"ln.{i}.", Eo)) for i in fields], Eo, "final.norm" + tag)
+            self._norm([dict(X=xo[i], Y32=xo[i], ldy32=FE, Y_is_out=i * Eo * 4, **self._norm_params(f"ln.{i}.")) for i in fields], Eo, "final.norm" + tag)
         return final_norm
 
     def _ib_params(self, pre: str) -> dict:
@@ -1497,13 +1370,18 @@ def blk_pe(eng: "TemporalEngine", layer: int) -> torch.Tensor:
     return eng.model.blocks[layer].pos_encoder.pe[0].to(device=eng.device, dtype=torch.float32)
 
 
+def _require_gpu(device: torch.device) -> None:
+    """The engine's device guard (a seam: tests/test_plan_forms_cpu.py builds plans in host memory past it; nothing can RUN there)."""
+    if device.type != "cuda":
+        raise RuntimeError("sea_amd: TemporalModel runs only on an MI355X (no CPU fallback)")
+
+
 class TemporalEngine:
     """Owns the flat parameter buffers of one TemporalModel on one GPU and the plans built over them."""
 
     def __init__(self, model: torch.nn.Module, device: torch.device, act_dtype: torch.dtype):
         N.lib()
-        if device.type != "cuda":
-            raise RuntimeError("sea_amd: TemporalModel runs only on an MI355X (no CPU fallback)")
+        _require_gpu(device)
         m = model
         self.ib_mode = {"mlp": 0, "linear": 1, "fourier": 2}.get(m.ib_scale_mode.lower(), -1)
         if (m.exchange_mode not in ("sea", "addition", "simple", "pool") or self.ib_mode < 0 or m.ib_addition_mode.lower() not in ("add", "none", "attention", "concat")

@@ -20,11 +20,13 @@ from . import _switches
 from . import ops
 from . import ptrcheck
 from .engine import Plan, _Rec, _round_up
+from .plan_forms import CONDITION
 
 
 class CondPlan(Plan):
     """Launch list that evaluates, for M = n_steps * B condition rows: mods[prefix] = cond_mlp output [M, 2d] (act dtype) of every AdaLN module and
     ibufs[l] = the info-bottleneck term [M, E] (fp32, accumulated into a zeroed buffer) of every layer."""
+    kind = CONDITION
 
     def __init__(self, eng, M: int):
         self.mods: Dict[str, torch.Tensor] = {}
@@ -33,7 +35,7 @@ class CondPlan(Plan):
 
     def _build(self) -> None:
         m = self.eng.model
-        self.mods = self._cond_mods(split=False)
+        self.mods = self._cond_mods()
         if m.ib_addition_mode.lower() == "add":
             for l in range(self.L):
                 ibuf = self._buf(self.M, self.E, dtype=torch.float32, zero=True)

@@ -15,12 +15,14 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from . import _native as N
-from . import _switches
 from . import ops
 from .engine import Plan, _Rec, blk_pe
+from .plan_forms import TRAINING
 
 
 class TrainPlan(Plan):
+    kind = TRAINING
+
     def __init__(self, eng, B: int, T: int, drop_thr: int = 0, dp: bool = False, want_dx: bool = False, want_dc: bool = False):
         self.drop_thr = drop_thr
         self.dp = bool(dp)   # data-parallel layout of the backward (the condition MLPs' backward per phase, two early slices): decided ONCE per engine (TemporalEngine.dp_overlap)
@@ -264,10 +266,8 @@ class TrainPlan(Plan):
                 self._cur.append(rec)
             self._gemm(gemm_groups, "adaln.cond_gemm")
 
-        def npar(pre):
-            if self.adaln:
-                return dict(mod=mods[pre], gamma=P.f32_vec(pre + "weight"), beta=P.f32_vec(pre + "bias"))
-            return dict(gamma=P.f32_vec(pre + "weight"))
+        self._mods = mods
+        npar = self._norm_params
 
         def stats():
             return buf(M, dtype=f32), buf(M, dtype=f32)
@@ -345,7 +345,7 @@ class TrainPlan(Plan):
                 sv["nd"] = buf(F, M, D)
                 sv["stc"] = [stats() for _ in range(F)]
                 sv["s_pre"], sv["sg"] = buf(M, D), buf(M, D)
-                if _switches.plan("norm", "1") != "0" and D <= 256 and D % 16 == 0:
+                if self.forms.down_norm:
                     self._gemm_norm([dict(A=sv["xa1"][j], W=P.act(f"{pre}cross_down.{j}.weight"), bias=P.f32_vec(f"{pre}cross_down.{j}.bias"), C32=sv["dn"][j],
                                           Yact=sv["nd"][j], mean=sv["stc"][j][0], rstd=sv["stc"][j][1], **npar(f"{pre}ln_cross.{j}.")) for j in range(F)], "add.down_norm")
                 else:
@@ -367,7 +367,7 @@ class TrainPlan(Plan):
                 big = sv["big"] = buf(M, 2 * FD)
                 pe_t = buf(M, D, dtype=f32)
                 pe_t.copy_(blk_pe(eng, l)[:T].repeat(B, 1))
-                if _switches.plan("norm", "1") != "0" and D <= 256 and D % 16 == 0:
+                if self.forms.down_norm:
                     self._gemm_norm([dict(A=sv["xa1"][j], W=P.act(f"{pre}cross_down.{j}.weight"), bias=P.f32_vec(f"{pre}cross_down.{j}.bias"), C32=sv["dn"][j],
                                           Yact=nrm[j], mean=sv["stc"][j][0], rstd=sv["stc"][j][1], **npar(f"{pre}ln_cross.{j}.")) for j in range(F)], "pool.down_norm")
                 else:
@@ -409,7 +409,7 @@ class TrainPlan(Plan):
                 sv["stc_new"] = [stats() for _ in range(F)]
                 sv["xa2"] = [buf(M, E) for _ in range(F)]
                 # cross_down + ln_cross in one launch (sea_gemm_rownorm); the pre-normalisation rows and the statistics are kept for the backward
-                fuse_dn = _switches.plan("norm", "1") != "0" and D <= 256 and D % 16 == 0
+                fuse_dn = self.forms.down_norm
                 if fuse_dn:
                     self._gemm_norm([dict(A=sv["xa1"][j], W=P.act(f"{pre}cross_down.{j}.weight"), bias=P.f32_vec(f"{pre}cross_down.{j}.bias"), C32=sv["dn_old"][j],
                                           Yact=sv["nd_old"][j], mean=sv["stc_old"][j][0], rstd=sv["stc_old"][j][1], **npar(f"{pre}ln_cross.{j}."))

@@ -114,7 +114,7 @@ def test_fewrow_decode_from_context_bf16(monkeypatch):
     cfg = O.OracleConfig(1, 1024, 8, 48, 8, 0, 2, 2, True, "adaln")
     m = check_context_cases(cfg, 1, "bf16", monkeypatch, "", ks=(2, 9), n=3, fast=False)
     p = next(p for key, p in m.engine()._plans.items() if key[:3] == (1, 1, "step"))
-    assert p._few
+    assert p.forms.few
     assert not kv_engine.supported(m.engine(), 1)
 
 

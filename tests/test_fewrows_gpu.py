@@ -194,7 +194,7 @@ def test_step_plan_of_fewrow_launches_equals_generic_step_plan_and_oracle(cfg_ar
     monkeypatch.setenv("SEA_KV", "gemv=1")
     a = rollout(m, x0, ibg, n, mode="kv")
     plans = [p for k, p in eng._plans.items() if k[:3] == (B, 1, "step")]
-    assert len(plans) == 1 and plans[0]._few
+    assert len(plans) == 1 and plans[0].forms.few
     names = [r.name for r in plans[0].records]
     assert not any("adaln" in nm or "norm_old" in nm or "norm_new" in nm or nm == "mlp.ln_gelu" for nm in names), names
     assert any(r.fn is eng_lib().sea_gemm_fewrows for r in plans[0].records) and any(r.fn is eng_lib().sea_qkv_rope_fewrows for r in plans[0].records)
@@ -205,7 +205,7 @@ def test_step_plan_of_fewrow_launches_equals_generic_step_plan_and_oracle(cfg_ar
     monkeypatch.setenv("SEA_KV", "gemv=0")
     b = rollout(m, x0, ibg, n, mode="kv")
     plans = [p for k, p in eng._plans.items() if k[:3] == (B, 1, "step")]
-    assert len(plans) == 1 and not plans[0]._few and len(plans[0].records) > n_few
+    assert len(plans) == 1 and not plans[0].forms.few and len(plans[0].records) > n_few
     e_ab, e_a, e_b = rel_l2(a.cpu().numpy(), b.cpu().numpy()), rel_l2(a.cpu().numpy(), ref), rel_l2(b.cpu().numpy(), ref)
     print(f"few-row step plan {n_few} launches vs generic {len(plans[0].records)}: rel-L2 between them {e_ab:.3e}; vs oracle {e_a:.3e} / {e_b:.3e}")
     assert e_ab < 2e-2 and e_a < 3e-2 and e_b < 3e-2
@@ -233,7 +233,7 @@ def test_fewrow_step_plan_without_the_hoisted_condition_work(cfg_args, B, monkey
     monkeypatch.setenv("SEA_KV", "hoist=0")
     b = rollout(m, x0, ibg, n, mode="kv")
     plans = [p for k, p in eng._plans.items() if k[:3] == (B, 1, "step")]
-    assert len(plans) == 1 and plans[0]._few and not plans[0]._hoisted
+    assert len(plans) == 1 and plans[0].forms.few and not plans[0]._hoisted
     assert rel_l2(a.cpu().numpy(), b.cpu().numpy()) < 2e-2
 
 

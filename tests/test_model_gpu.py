@@ -516,7 +516,7 @@ def test_shipped_multiphase_dims_forward(dtype, tol):
 @pytest.mark.parametrize("F,B,T", [(3, 2, 70), (2, 1, 130), (3, 1, 300)])
 def test_rider_plan_matches_the_plans_it_replaces(F, B, T, monkeypatch):
     """One-layer AdaLN models in bf16 run round 4's rider plan: the condition GEMM in front covers AdaLN_0 + ln_cross only, the row chains (sea_row_chain_riders)
-    carry cond_mlp.2 of the modules the field MLP / final norm read as RIDER tiles on the CUs they leave idle (engine.Plan._take_riders).  Against the oracle, against the same model with SEA_PLAN=riders=0 (whole-model silu + condition launches: same arithmetic ->
+    carry cond_mlp.2 of the modules the field MLP / final norm read as RIDER tiles on the CUs they leave idle (engine._Riders.take).  Against the oracle, against the same model with SEA_PLAN=riders=0 (whole-model silu + condition launches: same arithmetic ->
     bitwise) and with SEA_PLAN=chain=0 (round 3's launches); rows cross a trajectory boundary (B = 2) and a partial last tile (T = 70, 130, 300)."""
     cfg = O.OracleConfig(1, 128, 4, 320, 8, 0, F, 2, True, "adaln")
     x, _, ib = recipe_inputs(B, T, cfg, seed=9)
