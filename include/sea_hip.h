@@ -41,7 +41,7 @@ enum {
 int sea_abi_version(void);
 const char* sea_last_error(void);
 /* sizeof of every ABI struct in declaration order (SeaGemmGroup, SeaQkvGroup, SeaQkvCommon, SeaAttnProblem,
- * SeaAttnParams, SeaNormGroup, SeaSiluGroup, SeaIbParams, ..., SeaLaunchRec, SeaGemmNormGroup, SeaExchangeTail, SeaMlpGroup, SeaMlp2Group, SeaKvNorm, SeaKvField, SeaKvPair, SeaKvLayer, SeaKvGlobal, SeaStepPatch, SeaRowChain, SeaAdalnGroup, SeaAdalnQkv, SeaSplitkGroup, SeaEncBlock, SeaKvFill last): lets a binding verify its layout.  Host only. */
+ * SeaAttnParams, SeaNormGroup, SeaSiluGroup, SeaIbParams, ..., SeaLaunchRec, SeaGemmNormGroup, SeaExchangeTail, SeaMlpGroup, SeaMlp2Group, SeaKvNorm, SeaKvField, SeaKvPair, SeaKvLayer, SeaKvGlobal, SeaStepPatch, SeaRowChain, SeaAdalnGroup, SeaAdalnQkv, SeaSplitkGroup, SeaEncBlock, SeaKvFill, SeaKvFork last): lets a binding verify its layout.  Host only. */
 int sea_struct_sizes(int* out, int cap);
 /* Number of compute units / name of device 0's architecture as HIP reports them (diagnostics for bench.py). */
 int sea_device_info(int* cu_count, char* arch, int arch_len);
@@ -880,6 +880,26 @@ typedef struct {
     int32_t B, H, hd, n_pos, cap_src, cap_dst, v_rows, pad_;
 } SeaKvFill;
 int sea_kv_cache_fill(const SeaKvFill* entries, int n, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * KV-cache fork: a rollout session that branches into n_rep what-if continuations per trajectory copies the cache positions it has filled so far
+ * into the caches of a session of B_src * n_rep trajectories instead of prefilling the repeated history again.  Per table entry, ONE cache tensor:
+ * positions 0 .. n_pos-1 of every head of source row b go to destination rows b * n_rep + j, j = 0 .. n_rep-1 (row b * n_rep + j is branch j of b).
+ * Source and destination have the same layout:
+ *   transposed = 0: [B, H, cap, hd] rows (every key cache, the value rows of sea_kv_rollout): n_pos * hd contiguous elements per (b, h);
+ *   transposed = 1: [B, H, hd, cap] (V^T of the generic step plan): hd runs of n_pos elements per (b, h), the last 16-byte chunk of a run may be partial.
+ * Every 16-byte line of the source is read once and written n_rep times; the copy is exact (raw bits).  Positions >= n_pos of the destination are
+ * never touched.  Requirements: B_src, H, n_rep >= 1 (n_rep = 1: a plain copy); hd a multiple of 8 in [8, 256]; 1 <= n_pos <= cap_src, cap_dst; cap_src
+ * and cap_dst multiples of 8, independent of each other; both pointers 16-byte aligned; source and destination do not overlap.  One launch per
+ * SEA_KV_FORK_MAX entries (the table travels in the kernel arguments).  Returns -1, with the entry named in sea_last_error(), otherwise.
+ */
+#define SEA_KV_FORK_MAX 32
+typedef struct {
+    const void* src;   /* act [B_src, H, cap_src, hd] (transposed = 0) or [B_src, H, hd, cap_src] (transposed = 1) */
+    void* dst;         /* act [B_src * n_rep, H, cap_dst, hd] or [B_src * n_rep, H, hd, cap_dst] */
+    int32_t B_src, H, hd, n_pos, cap_src, cap_dst, n_rep, transposed;
+} SeaKvFork;
+int sea_kv_cache_fork(const SeaKvFork* entries, int n, int dtype, void* stream);
 /* Tuning aid: register a device buffer of n_steps * 64 8-byte words that the persistent form fills with 100 MHz clock stamps of its hand-offs
  * (tools/kv_persist_timeline.py); NULL switches it off. */
 void sea_kv_debug_stamps(unsigned long long* buf);

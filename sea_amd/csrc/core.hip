@@ -46,7 +46,7 @@ extern "C" int sea_struct_sizes(int* out, int cap) {
                          (int)sizeof(SeaAttnBwdProblem), (int)sizeof(SeaAttnBwdParams), (int)sizeof(SeaDropout), (int)sizeof(SeaLaunchRec),
                          (int)sizeof(SeaGemmNormGroup), (int)sizeof(SeaExchangeTail), (int)sizeof(SeaMlpGroup), (int)sizeof(SeaMlp2Group), (int)sizeof(SeaKvNorm), (int)sizeof(SeaKvField),
                          (int)sizeof(SeaKvPair), (int)sizeof(SeaKvLayer), (int)sizeof(SeaKvGlobal), (int)sizeof(SeaStepPatch), (int)sizeof(SeaRowChain), (int)sizeof(SeaAdalnGroup), (int)sizeof(SeaAdalnQkv), (int)sizeof(SeaSplitkGroup), (int)sizeof(SeaEncBlock),
-                         (int)sizeof(SeaKvFill)};
+                         (int)sizeof(SeaKvFill), (int)sizeof(SeaKvFork)};
     const int n = (int)(sizeof(sizes) / sizeof(sizes[0]));
     for (int i = 0; i < n && i < cap; ++i) out[i] = sizes[i];
     return n;

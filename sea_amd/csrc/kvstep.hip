@@ -1907,6 +1907,74 @@ __global__ __launch_bounds__(256) void kv_fill_kernel(const FillLaunch L) {
     }
 }
 
+// ------------------------------------------------------------------------------------------------ cache fork (sea_kv_cache_fork)
+// Both layouts are "`rows` runs of `run` elements per (b, h)": one run of n_pos * hd elements for [B, H, cap, hd] rows, hd runs of n_pos elements a
+// capacity apart for [B, H, hd, cap]; every run starts 16-byte aligned (capacities and hd are multiples of 8).  An item is one 16-byte chunk of a
+// run; a workgroup owns 1024 consecutive items of one (entry, b, h), four per lane a wave-width apart, so that a wave reads 1 KiB of consecutive
+// source bytes per load: it issues its four loads, then writes each line to the n_rep destination rows.  Only the last chunk of a run can be partial
+// (V^T with n_pos not a multiple of the chunk): that one is written element by element.
+constexpr int FORK_ITEMS = 1024;
+struct ForkLaunch {
+    SeaKvFork e[SEA_KV_FORK_MAX];
+    int32_t wg0[SEA_KV_FORK_MAX + 1];   // first workgroup of each entry (prefix sum of B_src H ceil(items / 1024))
+    int32_t n;
+};
+
+static inline int64_t fork_items(const SeaKvFork& F, int epv) {
+    return F.transposed ? (int64_t)F.hd * ((F.n_pos + epv - 1) / epv) : (int64_t)F.n_pos * F.hd / epv;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void kv_fork_kernel(const ForkLaunch L) {
+    using Bits = typename std::conditional<sizeof(T) == 2, uint16_t, uint32_t>::type;
+    constexpr int EPV = 16 / (int)sizeof(T);   // elements per 16-byte chunk
+    constexpr int PER = FORK_ITEMS / 256;
+    int e = 0;
+    while (e + 1 < L.n && (int)blockIdx.x >= L.wg0[e + 1]) ++e;
+    const SeaKvFork& F = L.e[e];
+    const int run = F.transposed ? F.n_pos : F.n_pos * F.hd;
+    const int cpr = (run + EPV - 1) / EPV;                       // chunks per run
+    const int items = (F.transposed ? F.hd : 1) * cpr;
+    const int tiles = (items + FORK_ITEMS - 1) / FORK_ITEMS;
+    const int w = (int)blockIdx.x - L.wg0[e];
+    const int bh = w / tiles;
+    const int it0 = (w - bh * tiles) * FORK_ITEMS + (int)threadIdx.x;
+    const int b = bh / F.H, h = bh - b * F.H;
+    const int64_t slab_s = (int64_t)F.cap_src * F.hd, slab_d = (int64_t)F.cap_dst * F.hd;
+    const Bits* src = static_cast<const Bits*>(F.src) + bh * slab_s;
+    Bits* dst = static_cast<Bits*>(F.dst) + ((int64_t)b * F.n_rep * F.H + h) * slab_d;   // branch j: + j * H * slab_d
+    const int64_t rep = (int64_t)F.H * slab_d;
+    // Every item loads its whole 16-byte chunk unconditionally (a lane without an item re-reads the last one; a partial last chunk of a V^T run ends
+    // inside the capacity row, which is a multiple of the chunk), so the four lines stay in registers and all four loads are in flight before
+    // the first store; `cnt` alone gates the stores.
+    uint4 v[PER];
+    int dof[PER], cnt[PER];                                      // element offset inside the destination (b, h) slab; elements to write (0: no item)
+#pragma unroll
+    for (int u = 0; u < PER; ++u) {
+        const int it = it0 + u * 256;
+        const int itc = min(it, items - 1);
+        const int d = itc / cpr, c = itc - d * cpr;              // (d = 0 in the row layout)
+        dof[u] = d * F.cap_dst + c * EPV;
+        cnt[u] = it < items ? min(EPV, run - c * EPV) : 0;
+        v[u] = *reinterpret_cast<const uint4*>(src + d * F.cap_src + c * EPV);
+    }
+#pragma unroll
+    for (int u = 0; u < PER; ++u) {
+        Bits* t = dst + dof[u];
+        if (cnt[u] == EPV) {
+            for (int j = 0; j < F.n_rep; ++j, t += rep) *reinterpret_cast<uint4*>(t) = v[u];
+        } else if (cnt[u] > 0) {
+            Bits b[EPV];
+            __builtin_memcpy(b, &v[u], 16);
+            for (int j = 0; j < F.n_rep; ++j, t += rep) {
+#pragma unroll
+                for (int x = 0; x < EPV; ++x)
+                    if (x < cnt[u]) t[x] = b[x];
+            }
+        }
+    }
+}
+
 template <typename T>
 static int run_steps_t(const SeaKvGlobal& G, const SeaKvLayer* layers, int pos0, int n_steps, uint32_t tag0, hipStream_t s) {
     switch (pre_width(G)) {
@@ -1978,6 +2046,42 @@ extern "C" int sea_kv_cache_fill(const SeaKvFill* entries, int n, int dtype, voi
         if (dtype == SEA_BF16) kv_fill_kernel<__bf16><<<dim3((unsigned)wg), dim3(256), 0, s>>>(L);
         else kv_fill_kernel<float><<<dim3((unsigned)wg), dim3(256), 0, s>>>(L);
         SEA_CHECK_LAUNCH("sea_kv_cache_fill");
+    }
+    return SEA_OK;
+}
+
+extern "C" int sea_kv_cache_fork(const SeaKvFork* entries, int n, int dtype, void* stream) {
+    SEA_REQUIRE(entries != nullptr && n >= 1, "sea_kv_cache_fork: bad arguments (entries=%p n=%d)", (const void*)entries, n);
+    SEA_REQUIRE(dtype == SEA_F32 || dtype == SEA_BF16, "sea_kv_cache_fork: bad dtype %d", dtype);
+    const int epv = dtype == SEA_BF16 ? 8 : 4;
+    int64_t wg_all = 0;
+    for (int i = 0; i < n; ++i) {
+        const SeaKvFork& F = entries[i];
+        SEA_REQUIRE(F.src && F.dst && sea_aligned16(F.src) && sea_aligned16(F.dst), "sea_kv_cache_fork: entry %d: null or misaligned (16 bytes) pointer", i);
+        SEA_REQUIRE(F.B_src >= 1 && F.H >= 1 && F.n_rep >= 1 && F.hd >= 8 && F.hd <= 256 && F.hd % 8 == 0 && F.n_pos >= 1 && F.n_pos <= F.cap_src &&
+                        F.n_pos <= F.cap_dst && F.cap_src % 8 == 0 && F.cap_dst % 8 == 0 && (F.transposed == 0 || F.transposed == 1) &&
+                        (int64_t)F.cap_src * F.hd < ((int64_t)1 << 31) && (int64_t)F.cap_dst * F.hd < ((int64_t)1 << 31) &&
+                        (int64_t)F.B_src * F.n_rep < ((int64_t)1 << 31),
+                    "sea_kv_cache_fork: entry %d: bad sizes (B_src=%d H=%d hd=%d n_pos=%d cap_src=%d cap_dst=%d n_rep=%d transposed=%d)", i, F.B_src, F.H, F.hd,
+                    F.n_pos, F.cap_src, F.cap_dst, F.n_rep, F.transposed);
+        wg_all += (int64_t)F.B_src * F.H * ((fork_items(F, epv) + FORK_ITEMS - 1) / FORK_ITEMS);
+    }
+    SEA_REQUIRE(wg_all < ((int64_t)1 << 31), "sea_kv_cache_fork: %lld workgroups", (long long)wg_all);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    for (int e0 = 0; e0 < n; e0 += SEA_KV_FORK_MAX) {
+        ForkLaunch L;
+        L.n = n - e0 < SEA_KV_FORK_MAX ? n - e0 : SEA_KV_FORK_MAX;
+        int64_t wg = 0;
+        for (int i = 0; i < L.n; ++i) {
+            const SeaKvFork& F = entries[e0 + i];
+            L.e[i] = F;
+            L.wg0[i] = (int32_t)wg;
+            wg += (int64_t)F.B_src * F.H * ((fork_items(F, epv) + FORK_ITEMS - 1) / FORK_ITEMS);
+        }
+        L.wg0[L.n] = (int32_t)wg;
+        if (dtype == SEA_BF16) kv_fork_kernel<__bf16><<<dim3((unsigned)wg), dim3(256), 0, s>>>(L);
+        else kv_fork_kernel<float><<<dim3((unsigned)wg), dim3(256), 0, s>>>(L);
+        SEA_CHECK_LAUNCH("sea_kv_cache_fork");
     }
     return SEA_OK;
 }

@@ -39,6 +39,14 @@ _BIND_KEYS = {"X_is_x": ("_x_patches", "X"), "R_is_x": ("_x_patches", "R"), "Xin
               "dY_is_dout": ("_dout_patches", "dY")}
 
 
+# what the KV-cache rollout refuses (TemporalEngine.plan / rollout_kv, and a rollout session before it is opened: rollout_session.check_open)
+KV_NO_POOL = ("sea_amd: the KV-cache rollout does not cover exchange_mode='pool' (its sinusoidal positions are relative to the window); "
+              "use the recompute rollout")
+KV_NO_IB_ATTENTION = ("sea_amd: the KV-cache rollout does not cover ib_addition_mode='attention' (every row attends to the info-bottleneck rows "
+                      "of ALL positions of the window, later ones included: rows already produced change as the window grows); use the recompute rollout")
+KV_NO_SRC_LEN = "sea_amd: the KV-cache rollout is exact only for src_len == 0; use the recompute rollout (rollout(..., mode='recompute'))"
+
+
 def _round_up(x: int, m: int) -> int:
     return (x + m - 1) // m * m
 
@@ -1439,11 +1447,9 @@ class TemporalEngine:
 
     def plan(self, B: int, T: int, mode: str = "full", cond=None) -> Plan:
         if mode == "step" and self.model.exchange_mode == "pool":
-            raise NotImplementedError("sea_amd: the KV-cache rollout does not cover exchange_mode='pool' (its sinusoidal positions are relative to the window); "
-                                      "use the recompute rollout")
+            raise NotImplementedError(KV_NO_POOL)
         if mode == "step" and self.model.ib_addition_mode.lower() == "attention":
-            raise NotImplementedError("sea_amd: the KV-cache rollout does not cover ib_addition_mode='attention' (every row attends to the info-bottleneck rows "
-                                      "of ALL positions of the window, later ones included: rows already produced change as the window grows); use the recompute rollout")
+            raise NotImplementedError(KV_NO_IB_ATTENTION)
         key = (B, T, mode) if cond is None else (B, T, mode, id(cond))
         p = self._plans.get(key)
         if p is None:
@@ -1641,7 +1647,7 @@ class TemporalEngine:
         if self.model.src_len > 0:
             # the reference masks with tril(diagonal=src_len) (models/base_blocks.py:173, 265): in its recompute loop the rows already produced re-attend
             # to the src_len rows appended after them, so their K/V and everything downstream change from step to step — a cache is not exact
-            raise NotImplementedError("sea_amd: the KV-cache rollout is exact only for src_len == 0; use the recompute rollout (rollout(..., mode='recompute'))")
+            raise NotImplementedError(KV_NO_SRC_LEN)
         if kv_engine.supported(self, B):
             # small models: seven launches per layer and step, condition-only work batched over all steps up front (sea_kv_rollout)
             kf = self._kv_fast.get(B)
@@ -1695,3 +1701,11 @@ class TemporalEngine:
                 p.set_hoisted_step(s)
                 p.run()
         return (traj[1:] if k == 1 else traj).permute(1, 0, 2, 3).contiguous()
+
+    def open_rollout(self, x0: torch.Tensor, ib: torch.Tensor):
+        """A stateful KV-cache rollout (rollout_session.RolloutSession) from the known states x0 [B, k, F, E] and the conditions ib [B, k-1, 1] of
+        positions 0 .. k-2: the session owns its caches between calls (step / advance / rewind / fork)."""
+        from . import rollout_session
+
+        with torch.no_grad():   # gradients through a session are not covered: the history is taken by value
+            return rollout_session.RolloutSession(self, x0, ib)

@@ -820,3 +820,28 @@ def kv_cache_fill(entries: Sequence[Dict], dtype: torch.dtype) -> None:
     for g, d in zip(arr, entries):
         fill_kv_fill(g, **d)
     N.check(N.lib().sea_kv_cache_fill(arr, len(entries), N.dtype_code(dtype), N.stream_ptr()), "sea_kv_cache_fill")
+
+
+def fill_kv_fork(g: N.SeaKvFork, src, dst, n_pos: int, transposed: bool) -> None:
+    """One entry of sea_kv_cache_fork: positions 0 .. n_pos - 1 of src ([B_src, H, cap_src, hd], or [B_src, H, hd, cap_src] when `transposed`) into
+    dst of the same layout with B_src * n_rep rows: destination row b * n_rep + j receives source row b."""
+    Bs, H = src.shape[0], src.shape[1]
+    hd, cap_src, cap_dst = (src.shape[2], src.shape[3], dst.shape[3]) if transposed else (src.shape[3], src.shape[2], dst.shape[2])
+    if dst.shape[0] % Bs or dst.shape[1] != H or (dst.shape[2] if transposed else dst.shape[3]) != hd:
+        raise ValueError(f"kv_cache_fork: dst {tuple(dst.shape)} is not src {tuple(src.shape)} with a multiple of its rows")
+    g.src, g.dst = src.data_ptr(), dst.data_ptr()
+    g.B_src, g.H, g.hd, g.n_pos, g.cap_src, g.cap_dst, g.n_rep, g.transposed = Bs, H, hd, n_pos, cap_src, cap_dst, dst.shape[0] // Bs, int(bool(transposed))
+
+
+def kv_cache_fork(entries: Sequence[Dict], dtype: torch.dtype) -> None:
+    """sea_kv_cache_fork over entries dict(src, dst, n_pos, transposed) (fill_kv_fork's arguments): one launch per N.KV_FORK_MAX entries."""
+    for d in entries:
+        for name in ("src", "dst"):
+            t = d[name]
+            N.require_gpu(t, name)
+            if t.dim() != 4 or not t.is_contiguous() or t.dtype != dtype:
+                raise ValueError(f"kv_cache_fork: {name} must be a contiguous 4-D {dtype} tensor, got {tuple(t.shape)} {t.dtype}")
+    arr = (N.SeaKvFork * max(len(entries), 1))()
+    for g, d in zip(arr, entries):
+        fill_kv_fork(g, **d)
+    N.check(N.lib().sea_kv_cache_fork(arr, len(entries), N.dtype_code(dtype), N.stream_ptr()), "sea_kv_cache_fork")

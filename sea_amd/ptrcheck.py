@@ -193,6 +193,11 @@ def _extents(st, esz: int) -> Iterable[Tuple[str, int, int]]:
         yield "Vt", st.Vt, (last_src + (st.hd - 1) * st.cap_src + st.n_pos) * esz
         yield "Kd", st.Kd, (last_dst + st.n_pos * st.hd) * esz
         yield "Vd", st.Vd, (last_dst + (st.n_pos * st.hd if st.v_rows else (st.hd - 1) * st.cap_dst + st.n_pos)) * esz
+    elif isinstance(st, N.SeaKvFork):
+        run = (st.hd - 1) * st.cap_src + st.n_pos if st.transposed else st.n_pos * st.hd          # elements of the last (b, h) slab that are touched
+        run_d = (st.hd - 1) * st.cap_dst + st.n_pos if st.transposed else st.n_pos * st.hd
+        yield "src", st.src, ((st.B_src * st.H - 1) * st.cap_src * st.hd + run) * esz
+        yield "dst", st.dst, ((st.B_src * st.n_rep * st.H - 1) * st.cap_dst * st.hd + run_d) * esz
     elif isinstance(st, N.SeaMlp2Group):
         yield "Hg", st.Hg, ((st.M - 1) * st.ldh + st.S) * esz
         yield "W2", st.W2, ((st.E - 1) * st.ldw2 + st.S) * esz

@@ -116,6 +116,30 @@ def rollout(model, x0: torch.Tensor, ib: torch.Tensor, n_steps: int, mode: str =
         model.train(was_training)
 
 
+def open_rollout(model, x0: torch.Tensor, ib: torch.Tensor):
+    """A stateful KV-cache rollout (sea_amd/rollout_session.py) from a known history: x0 [B, k, F, E] holds the states of positions 0 .. k-1 (k >= 1),
+    ib [B, k-1, 1] the conditions of positions 0 .. k-2 (may be empty) — the condition of the newest state arrives with the first step, which is
+    what lets a controller or a coupled solver choose it after seeing that state.
+
+        s = open_rollout(model, x0, ib)
+        y = s.step(c)                 # c [B, 1] or [B] -> the next state [B, F, E]; s.step(c, state=z) first replaces the current state by z
+        ys = s.advance(conds)         # conds [B, n, 1] -> [B, n, F, E]: n steps in the native loop
+        s.position, s.states()        # index of the newest known state; the trajectory so far [B, position + 1, F, E]
+        s.rewind(p)                   # go back to position p
+        t = s.fork(n)                 # B * n independent trajectories (row b * n + j: branch j of b) that share the history so far
+        s.close()                     # or `with open_rollout(...) as s:`
+
+    open(...).advance(ib[:, k-1:k-1+n]) is the trajectory of rollout(model, x0, ib, n, mode='kv').  The session owns its caches: rollout(), model(x, ib)
+    and other sessions on the same model do not disturb it.  It reads the weights as they are at every call; after an optimizer step the caches are
+    stale — open a new session.  NotImplementedError for the models the KV-cache rollout does not cover (src_len > 0, exchange_mode='pool',
+    ib_addition_mode='attention': a session has no recompute fallback); ValueError, before anything runs, for a malformed history."""
+    from ..rollout_session import check_open
+
+    check_open(model, x0, ib)
+    with torch.no_grad():
+        return model.engine(x0.device).open_rollout(x0, ib)
+
+
 def autoregressive_validation(model, validationLoader, loss_fn, device):
     """Autoregressive validation on the first sample of the first batch (reference :154-184)."""
     model.eval()
