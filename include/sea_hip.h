@@ -900,6 +900,30 @@ typedef struct {
     int32_t B_src, H, hd, n_pos, cap_src, cap_dst, n_rep, transposed;
 } SeaKvFork;
 int sea_kv_cache_fork(const SeaKvFork* entries, int n, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * KV-cache gather: the other direction of the fork.  A rollout session that keeps, drops, repeats or reorders trajectories (ensemble resampling,
+ * beam / MPC pruning) copies the cache positions it has filled so far into the caches of a session of B_dst trajectories instead of prefilling the
+ * selected histories again.  Per table entry, ONE cache tensor: positions 0 .. n_pos-1 of every head of source row index[j] go to destination row j,
+ * j = 0 .. B_dst-1; a source row may appear several times or not at all.  Source and destination state their layouts separately:
+ *   0: [B, H, cap, hd] rows (every key cache, the value rows of sea_kv_rollout);  1: [B, H, hd, cap] (V^T of the generic step plan).
+ * Equal layouts are copied in 16-byte chunks as sea_kv_cache_fork does (the partial last chunk of a V^T run element by element); rows -> V^T and
+ * V^T -> rows go through an LDS tile of 64 positions x 64 value columns, 16 bytes per lane on both global sides.  The copy is exact (raw bits);
+ * positions >= n_pos of the destination are never touched.  The kernel reads `index` itself and skips a destination row whose index lies outside
+ * [0, B_src): a guard against reading outside the source, not an interface — callers validate the index.
+ * Requirements: B_src, B_dst, H >= 1; hd a multiple of 8 in [8, 256]; 1 <= n_pos <= cap_src, cap_dst; cap_src and cap_dst multiples of 8, independent
+ * of each other; the layout flags 0 or 1; all three pointers non-NULL, src and dst 16-byte aligned; source and destination do not overlap.  One launch
+ * per SEA_KV_GATHER_MAX entries (the table travels in the kernel arguments).  Returns -1, with the entry named in sea_last_error(), otherwise.
+ * (An addition to ABI version 8.  sea_struct_sizes() keeps its 33 entries, SeaKvFork last: sizeof(SeaKvGather) is 64.)
+ */
+#define SEA_KV_GATHER_MAX 32
+typedef struct {
+    const void* src;        /* act [B_src, H, cap_src, hd] (src_transposed = 0) or [B_src, H, hd, cap_src] (1) */
+    void* dst;              /* act [B_dst, H, cap_dst, hd] (dst_transposed = 0) or [B_dst, H, hd, cap_dst] (1) */
+    const int32_t* index;   /* device, B_dst entries, each in [0, B_src) */
+    int32_t B_src, B_dst, H, hd, n_pos, cap_src, cap_dst, src_transposed, dst_transposed, pad_;
+} SeaKvGather;
+int sea_kv_cache_gather(const SeaKvGather* entries, int n, int dtype, void* stream);
 /* Tuning aid: register a device buffer of n_steps * 64 8-byte words that the persistent form fills with 100 MHz clock stamps of its hand-offs
  * (tools/kv_persist_timeline.py); NULL switches it off. */
 void sea_kv_debug_stamps(unsigned long long* buf);

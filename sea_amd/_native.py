@@ -252,6 +252,15 @@ class SeaKvFork(C.Structure):
                 ("n_rep", _i32), ("transposed", _i32)]
 
 
+KV_GATHER_MAX = 32
+
+
+class SeaKvGather(C.Structure):
+    # (not in ABI_STRUCTS: sea_struct_sizes() keeps SeaKvFork as its last entry; tests/test_session_select_cpu.py checks this layout through the library)
+    _fields_ = [("src", _vp), ("dst", _vp), ("index", _vp), ("B_src", _i32), ("B_dst", _i32), ("H", _i32), ("hd", _i32), ("n_pos", _i32),
+                ("cap_src", _i32), ("cap_dst", _i32), ("src_transposed", _i32), ("dst_transposed", _i32), ("pad_", _i32)]
+
+
 MAX_WGRAD_GROUPS = 32
 MAX_NORM_BWD_GROUPS = 8
 MAX_SILU_BWD_GROUPS = 24
@@ -351,6 +360,8 @@ def lib() -> C.CDLL:
     L.sea_kv_cache_fill.restype = C.c_int
     L.sea_kv_cache_fork.argtypes = [C.POINTER(SeaKvFork), C.c_int, C.c_int, _vp]
     L.sea_kv_cache_fork.restype = C.c_int
+    L.sea_kv_cache_gather.argtypes = [C.POINTER(SeaKvGather), C.c_int, C.c_int, _vp]
+    L.sea_kv_cache_gather.restype = C.c_int
     for name in ("sea_attention_bwd", "sea_wgrad_grouped", "sea_transpose_weights", "sea_rownorm_bwd", "sea_silu_outer_bwd", "sea_ib_bwd",
                  "sea_silu_outer_bwd_dc", "sea_ib_bwd_dc"):
         getattr(L, name).restype = C.c_int
@@ -379,7 +390,7 @@ EXPORTED_SYMBOLS = (
     "sea_mse_fwd_bwd", "sea_relative_mse", "sea_adamw_flat",
     "sea_wgrad_grouped", "sea_transpose_weights", "sea_rownorm_bwd", "sea_silu_outer_bwd", "sea_ib_bwd",
     "sea_attention_bwd", "sea_dropout_mask", "sea_run_list", "sea_run_list_steps", "sea_unpatchify", "sea_gemm_rownorm", "sea_exchange_tail", "sea_patchify", "sea_silu_outer_ib", "sea_mlp_fc1_ln_gelu", "sea_mlp_fc2_proj_norm", "sea_kv_rollout", "sea_kv_arena_words", "sea_kv_debug_stamps",
-    "sea_kv_cache_fill", "sea_kv_cache_fork",
+    "sea_kv_cache_fill", "sea_kv_cache_fork", "sea_kv_cache_gather",
     "sea_gemm_fewrows", "sea_qkv_rope_fewrows", "sea_row_chain", "sea_row_chain_riders", "sea_gemm_adaln", "sea_mlp_block", "sea_adaln_qkv", "sea_splitk_finish",
     "sea_encoder_block_ws_floats", "sea_encoder_block_fwd", "sea_encoder_block_bwd",
     "sea_silu_outer_bwd_dc", "sea_silu_outer_bwd_dc_ws_floats", "sea_ib_bwd_dc",

@@ -1975,6 +1975,150 @@ __global__ __launch_bounds__(256) void kv_fork_kernel(const ForkLaunch L) {
     }
 }
 
+// ------------------------------------------------------------------------------------------------ cache gather (sea_kv_cache_gather)
+// Destination row j of an entry receives source row index[j].  A workgroup owns one (entry, j, h) and
+//   * same layout on both sides: 1024 consecutive 16-byte items of the runs, exactly as the fork kernel (four loads in flight per lane, then the stores;
+//     the partial last chunk of a V^T run element by element);
+//   * rows <-> V^T: one 64-position tile, taken 64 value columns at a time through tile[value column][position] (raw element bits, one word of padding
+//     per column) as kv_fill_kernel does: the side that is [.., hd, cap] moves 16-byte chunks of positions, the side that is [.., cap, hd] 16-byte chunks
+//     of value columns, so that both the global reads and the global writes of a wave cover whole lines.
+// The index is read by the kernel; a row whose index lies outside [0, B_src) is skipped as a whole (the workgroup leaves before its first barrier).
+static_assert(sizeof(SeaKvGather) == 64, "SeaKvGather layout (include/sea_hip.h, sea_amd/_native.py)");
+constexpr int GATHER_ITEMS = FORK_ITEMS;
+constexpr int GATHER_TILE = FILL_TILE;
+struct GatherLaunch {
+    SeaKvGather e[SEA_KV_GATHER_MAX];
+    int32_t wg0[SEA_KV_GATHER_MAX + 1];   // first workgroup of each entry (prefix sum of B_dst H tiles)
+    int32_t n;
+};
+
+// workgroups per (j, h) of an entry
+static inline int64_t gather_tiles(const SeaKvGather& F, int epv) {
+    if (F.src_transposed != F.dst_transposed) return (F.n_pos + GATHER_TILE - 1) / GATHER_TILE;
+    const int64_t items = F.src_transposed ? (int64_t)F.hd * ((F.n_pos + epv - 1) / epv) : (int64_t)F.n_pos * F.hd / epv;
+    return (items + GATHER_ITEMS - 1) / GATHER_ITEMS;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void kv_gather_kernel(const GatherLaunch L) {
+    using Bits = typename std::conditional<sizeof(T) == 2, uint16_t, uint32_t>::type;
+    constexpr int EPV = 16 / (int)sizeof(T);   // elements per 16-byte chunk
+    constexpr int PER = GATHER_ITEMS / 256;
+    __shared__ uint32_t tile[GATHER_TILE * (GATHER_TILE + 1)];   // [value column][position], one word of padding per column
+    int e = 0;
+    while (e + 1 < L.n && (int)blockIdx.x >= L.wg0[e + 1]) ++e;
+    const SeaKvGather& F = L.e[e];
+    const bool convert = F.src_transposed != F.dst_transposed;
+    const int hd = F.hd, tid = threadIdx.x;
+    const int run = F.src_transposed ? F.n_pos : F.n_pos * hd;               // (same layout) elements of a run
+    const int cpr_run = (run + EPV - 1) / EPV;                               // chunks per run
+    const int items = (F.src_transposed ? hd : 1) * cpr_run;
+    const int tiles = convert ? (F.n_pos + GATHER_TILE - 1) / GATHER_TILE : (items + GATHER_ITEMS - 1) / GATHER_ITEMS;
+    const int w = (int)blockIdx.x - L.wg0[e];
+    const int jh = w / tiles, t = w - jh * tiles;
+    const int j = jh / F.H, h = jh - j * F.H;
+    const int sb = F.index[j];
+    if (sb < 0 || sb >= F.B_src) return;                                     // a guard only (uniform over the workgroup): never read outside the source
+    const int64_t slab_s = (int64_t)F.cap_src * hd, slab_d = (int64_t)F.cap_dst * hd;
+    const Bits* src = static_cast<const Bits*>(F.src) + ((int64_t)sb * F.H + h) * slab_s;
+    Bits* dst = static_cast<Bits*>(F.dst) + (int64_t)jh * slab_d;
+    if (!convert) {
+        // as kv_fork_kernel: every item loads its whole chunk (a lane without an item re-reads the last one; a partial last chunk of a V^T run ends
+        // inside the capacity row), all loads are in flight before the first store, `cnt` alone gates the stores
+        const int it0 = t * GATHER_ITEMS + tid;
+        uint4 v[PER];
+        int dof[PER], cnt[PER];
+#pragma unroll
+        for (int u = 0; u < PER; ++u) {
+            const int it = it0 + u * 256;
+            const int itc = min(it, items - 1);
+            const int d = itc / cpr_run, c = itc - d * cpr_run;              // (d = 0 in the row layout)
+            dof[u] = d * F.cap_dst + c * EPV;
+            cnt[u] = it < items ? min(EPV, run - c * EPV) : 0;
+            v[u] = *reinterpret_cast<const uint4*>(src + d * F.cap_src + c * EPV);
+        }
+#pragma unroll
+        for (int u = 0; u < PER; ++u) {
+            Bits* q = dst + dof[u];
+            if (cnt[u] == EPV) {
+                *reinterpret_cast<uint4*>(q) = v[u];
+            } else if (cnt[u] > 0) {
+                Bits b[EPV];
+                __builtin_memcpy(b, &v[u], 16);
+#pragma unroll
+                for (int x = 0; x < EPV; ++x)
+                    if (x < cnt[u]) q[x] = b[x];
+            }
+        }
+        return;
+    }
+    const int p0 = t * GATHER_TILE;
+    const int np = min(GATHER_TILE, F.n_pos - p0);                           // positions of this tile
+    const int cpr = (np + EPV - 1) / EPV;                                    // 16-byte chunks of positions per value column (the last one may be partial)
+    for (int d0 = 0; d0 < hd; d0 += GATHER_TILE) {
+        const int dw = min(GATHER_TILE, hd - d0);                            // a multiple of 8
+        const int cpp = dw / EPV;                                            // 16-byte chunks of a value row in this column block
+        if (F.src_transposed) {                                              // V^T runs -> tile[d][p]
+            const Bits* vs = src + (int64_t)d0 * F.cap_src + p0;
+            for (int it = tid; it < dw * cpr; it += 256) {
+                const int dl = it / cpr, c = it - dl * cpr;
+                const Bits* s = vs + (int64_t)dl * F.cap_src + c * EPV;
+                uint32_t* q = tile + dl * (GATHER_TILE + 1) + c * EPV;
+                if ((c + 1) * EPV <= np) {
+                    const uint4 v = *reinterpret_cast<const uint4*>(s);
+                    Bits b[EPV];
+                    __builtin_memcpy(b, &v, 16);
+#pragma unroll
+                    for (int u = 0; u < EPV; ++u) q[u] = b[u];
+                } else {
+                    for (int u = 0; u < np - c * EPV; ++u) q[u] = s[u];
+                }
+            }
+        } else {                                                             // value rows -> tile[d][p]
+            const Bits* vs = src + (int64_t)p0 * hd + d0;
+            for (int it = tid; it < np * cpp; it += 256) {
+                const int p = it / cpp, c = it - p * cpp;
+                const uint4 v = *reinterpret_cast<const uint4*>(vs + (int64_t)p * hd + c * EPV);
+                Bits b[EPV];
+                __builtin_memcpy(b, &v, 16);
+#pragma unroll
+                for (int u = 0; u < EPV; ++u) tile[(c * EPV + u) * (GATHER_TILE + 1) + p] = b[u];
+            }
+        }
+        __syncthreads();
+        if (F.dst_transposed) {                                              // tile[d][p] -> V^T runs
+            Bits* vd = dst + (int64_t)d0 * F.cap_dst + p0;
+            for (int it = tid; it < dw * cpr; it += 256) {
+                const int dl = it / cpr, c = it - dl * cpr;
+                const uint32_t* s = tile + dl * (GATHER_TILE + 1) + c * EPV;
+                Bits* q = vd + (int64_t)dl * F.cap_dst + c * EPV;
+                if ((c + 1) * EPV <= np) {
+                    Bits b[EPV];
+#pragma unroll
+                    for (int u = 0; u < EPV; ++u) b[u] = (Bits)s[u];
+                    uint4 v;
+                    __builtin_memcpy(&v, b, 16);
+                    *reinterpret_cast<uint4*>(q) = v;
+                } else {
+                    for (int u = 0; u < np - c * EPV; ++u) q[u] = (Bits)s[u];
+                }
+            }
+        } else {                                                             // tile[d][p] -> value rows
+            Bits* vd = dst + (int64_t)p0 * hd + d0;
+            for (int it = tid; it < np * cpp; it += 256) {
+                const int p = it / cpp, c = it - p * cpp;
+                Bits b[EPV];
+#pragma unroll
+                for (int u = 0; u < EPV; ++u) b[u] = (Bits)tile[(c * EPV + u) * (GATHER_TILE + 1) + p];
+                uint4 v;
+                __builtin_memcpy(&v, b, 16);
+                *reinterpret_cast<uint4*>(vd + (int64_t)p * hd + c * EPV) = v;
+            }
+        }
+        __syncthreads();
+    }
+}
+
 template <typename T>
 static int run_steps_t(const SeaKvGlobal& G, const SeaKvLayer* layers, int pos0, int n_steps, uint32_t tag0, hipStream_t s) {
     switch (pre_width(G)) {
@@ -2082,6 +2226,47 @@ extern "C" int sea_kv_cache_fork(const SeaKvFork* entries, int n, int dtype, voi
         if (dtype == SEA_BF16) kv_fork_kernel<__bf16><<<dim3((unsigned)wg), dim3(256), 0, s>>>(L);
         else kv_fork_kernel<float><<<dim3((unsigned)wg), dim3(256), 0, s>>>(L);
         SEA_CHECK_LAUNCH("sea_kv_cache_fork");
+    }
+    return SEA_OK;
+}
+
+extern "C" int sea_kv_cache_gather(const SeaKvGather* entries, int n, int dtype, void* stream) {
+    SEA_REQUIRE(entries != nullptr && n >= 1, "sea_kv_cache_gather: bad arguments (entries=%p n=%d)", (const void*)entries, n);
+    SEA_REQUIRE(dtype == SEA_F32 || dtype == SEA_BF16, "sea_kv_cache_gather: bad dtype %d", dtype);
+    const int epv = dtype == SEA_BF16 ? 8 : 4;
+    const int64_t esz = dtype == SEA_BF16 ? 2 : 4;
+    int64_t wg_all = 0;
+    for (int i = 0; i < n; ++i) {
+        const SeaKvGather& F = entries[i];
+        SEA_REQUIRE(F.src && F.dst && F.index && sea_aligned16(F.src) && sea_aligned16(F.dst), "sea_kv_cache_gather: entry %d: null or misaligned (16 bytes) pointer", i);
+        SEA_REQUIRE(F.B_src >= 1 && F.B_dst >= 1 && F.H >= 1 && F.hd >= 8 && F.hd <= 256 && F.hd % 8 == 0 && F.n_pos >= 1 && F.n_pos <= F.cap_src &&
+                        F.n_pos <= F.cap_dst && F.cap_src % 8 == 0 && F.cap_dst % 8 == 0 && (F.src_transposed == 0 || F.src_transposed == 1) &&
+                        (F.dst_transposed == 0 || F.dst_transposed == 1) && (int64_t)F.cap_src * F.hd < ((int64_t)1 << 31) &&
+                        (int64_t)F.cap_dst * F.hd < ((int64_t)1 << 31) && (int64_t)F.B_src * F.H < ((int64_t)1 << 31) && (int64_t)F.B_dst * F.H < ((int64_t)1 << 31) &&
+                        (int64_t)F.B_src * F.H * ((int64_t)F.cap_src * F.hd) < ((int64_t)1 << 58) && (int64_t)F.B_dst * F.H * ((int64_t)F.cap_dst * F.hd) < ((int64_t)1 << 58),
+                    "sea_kv_cache_gather: entry %d: bad sizes (B_src=%d B_dst=%d H=%d hd=%d n_pos=%d cap_src=%d cap_dst=%d src_transposed=%d dst_transposed=%d)", i,
+                    F.B_src, F.B_dst, F.H, F.hd, F.n_pos, F.cap_src, F.cap_dst, F.src_transposed, F.dst_transposed);
+        const uintptr_t s0 = reinterpret_cast<uintptr_t>(F.src), d0 = reinterpret_cast<uintptr_t>(F.dst);
+        const uint64_t s_bytes = (uint64_t)F.B_src * F.H * F.cap_src * F.hd * esz, d_bytes = (uint64_t)F.B_dst * F.H * F.cap_dst * F.hd * esz;
+        SEA_REQUIRE(s0 + s_bytes <= d0 || d0 + d_bytes <= s0, "sea_kv_cache_gather: entry %d: source and destination overlap", i);
+        wg_all += (int64_t)F.B_dst * F.H * gather_tiles(F, epv);
+        SEA_REQUIRE(wg_all < ((int64_t)1 << 31), "sea_kv_cache_gather: %lld workgroups", (long long)wg_all);
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    for (int e0 = 0; e0 < n; e0 += SEA_KV_GATHER_MAX) {
+        GatherLaunch L;
+        L.n = n - e0 < SEA_KV_GATHER_MAX ? n - e0 : SEA_KV_GATHER_MAX;
+        int64_t wg = 0;
+        for (int i = 0; i < L.n; ++i) {
+            const SeaKvGather& F = entries[e0 + i];
+            L.e[i] = F;
+            L.wg0[i] = (int32_t)wg;
+            wg += (int64_t)F.B_dst * F.H * gather_tiles(F, epv);
+        }
+        L.wg0[L.n] = (int32_t)wg;
+        if (dtype == SEA_BF16) kv_gather_kernel<__bf16><<<dim3((unsigned)wg), dim3(256), 0, s>>>(L);
+        else kv_gather_kernel<float><<<dim3((unsigned)wg), dim3(256), 0, s>>>(L);
+        SEA_CHECK_LAUNCH("sea_kv_cache_gather");
     }
     return SEA_OK;
 }

@@ -845,3 +845,61 @@ def kv_cache_fork(entries: Sequence[Dict], dtype: torch.dtype) -> None:
     for g, d in zip(arr, entries):
         fill_kv_fork(g, **d)
     N.check(N.lib().sea_kv_cache_fork(arr, len(entries), N.dtype_code(dtype), N.stream_ptr()), "sea_kv_cache_fork")
+
+
+def fill_kv_gather(g: N.SeaKvGather, src, dst, index, n_pos: int, src_transposed: bool, dst_transposed: bool) -> None:
+    """One entry of sea_kv_cache_gather: positions 0 .. n_pos - 1 of row index[j] of src ([B_src, H, cap_src, hd], or [B_src, H, hd, cap_src] when
+    `src_transposed`) into row j of dst ([B_dst, H, cap_dst, hd], or [B_dst, H, hd, cap_dst] when `dst_transposed`); index: int32 [B_dst] on the device."""
+    Bs, H = src.shape[0], src.shape[1]
+    hd, cap_src = (src.shape[2], src.shape[3]) if src_transposed else (src.shape[3], src.shape[2])
+    hd_d, cap_dst = (dst.shape[2], dst.shape[3]) if dst_transposed else (dst.shape[3], dst.shape[2])
+    if dst.shape[1] != H or hd_d != hd:
+        raise ValueError(f"kv_cache_gather: dst {tuple(dst.shape)} (transposed={bool(dst_transposed)}) does not have the heads and head dimension of src "
+                         f"{tuple(src.shape)} (transposed={bool(src_transposed)})")
+    if index.dim() != 1 or index.dtype != torch.int32 or index.shape[0] != dst.shape[0]:
+        raise ValueError(f"kv_cache_gather: index {tuple(index.shape)} {index.dtype} must be int32 [B_dst = {dst.shape[0]}]")
+    g.src, g.dst, g.index = src.data_ptr(), dst.data_ptr(), index.data_ptr()
+    g.B_src, g.B_dst, g.H, g.hd, g.n_pos, g.cap_src, g.cap_dst = Bs, dst.shape[0], H, hd, n_pos, cap_src, cap_dst
+    g.src_transposed, g.dst_transposed = int(bool(src_transposed)), int(bool(dst_transposed))
+
+
+def check_gather_index(index, B_src: Sequence[int], B_dst: Sequence[int], what: str = "kv_cache_gather") -> list:
+    """The index of a gather as a list of ints: a 1-D, non-empty host sequence or CPU integer tensor whose values lie in [0, b) for every b of B_src and
+    whose length equals every entry of B_dst.  Raises ValueError; touches no device."""
+    if torch.is_tensor(index):
+        if index.is_cuda or index.dim() != 1 or index.dtype in (torch.bool,) or index.is_floating_point() or index.is_complex():
+            raise ValueError(f"{what}: index must be a 1-D integer tensor on the host, got {tuple(index.shape)} {index.dtype} on {index.device}")
+        idx = index.tolist()
+    else:
+        idx = list(index)
+        if any(isinstance(v, bool) or not isinstance(v, int) for v in idx):
+            raise ValueError(f"{what}: index must be a 1-D sequence of integers")
+    if not idx:
+        raise ValueError(f"{what}: index is empty")
+    for b in B_src:
+        if min(idx) < 0 or max(idx) >= b:
+            raise ValueError(f"{what}: index values must lie in [0, B_src = {b}), got {min(idx)} .. {max(idx)}")
+    for b in B_dst:
+        if b != len(idx):
+            raise ValueError(f"{what}: index has {len(idx)} entries for a destination of B_dst = {b} rows")
+    return idx
+
+
+def kv_cache_gather(entries: Sequence[Dict], index, dtype: torch.dtype) -> None:
+    """sea_kv_cache_gather over entries dict(src, dst, n_pos, src_transposed, dst_transposed): one launch per N.KV_GATHER_MAX entries.  `index` (a host
+    sequence or CPU integer tensor, one value per destination row) is checked against every entry before anything touches the device, then uploaded
+    once as the int32 tensor all entries share.  The only way from Python to the entry point."""
+    idx = check_gather_index(index, [d["src"].shape[0] for d in entries], [d["dst"].shape[0] for d in entries])
+    for d in entries:
+        for name in ("src", "dst"):
+            t = d[name]
+            N.require_gpu(t, name)
+            if t.dim() != 4 or not t.is_contiguous() or t.dtype != dtype:
+                raise ValueError(f"kv_cache_gather: {name} must be a contiguous 4-D {dtype} tensor, got {tuple(t.shape)} {t.dtype}")
+    if not entries:
+        raise ValueError("kv_cache_gather: no entries")
+    dev_index = torch.tensor(idx, dtype=torch.int32, device=entries[0]["src"].device)
+    arr = (N.SeaKvGather * len(entries))()
+    for g, d in zip(arr, entries):
+        fill_kv_gather(g, index=dev_index, **d)
+    N.check(N.lib().sea_kv_cache_gather(arr, len(entries), N.dtype_code(dtype), N.stream_ptr()), "sea_kv_cache_gather")

@@ -198,6 +198,12 @@ def _extents(st, esz: int) -> Iterable[Tuple[str, int, int]]:
         run_d = (st.hd - 1) * st.cap_dst + st.n_pos if st.transposed else st.n_pos * st.hd
         yield "src", st.src, ((st.B_src * st.H - 1) * st.cap_src * st.hd + run) * esz
         yield "dst", st.dst, ((st.B_src * st.n_rep * st.H - 1) * st.cap_dst * st.hd + run_d) * esz
+    elif isinstance(st, N.SeaKvGather):
+        run_s = (st.hd - 1) * st.cap_src + st.n_pos if st.src_transposed else st.n_pos * st.hd    # elements of the last (b, h) slab that are touched
+        run_d = (st.hd - 1) * st.cap_dst + st.n_pos if st.dst_transposed else st.n_pos * st.hd
+        yield "src", st.src, ((st.B_src * st.H - 1) * st.cap_src * st.hd + run_s) * esz
+        yield "dst", st.dst, ((st.B_dst * st.H - 1) * st.cap_dst * st.hd + run_d) * esz
+        yield "index", st.index, st.B_dst * 4
     elif isinstance(st, N.SeaMlp2Group):
         yield "Hg", st.Hg, ((st.M - 1) * st.ldh + st.S) * esz
         yield "W2", st.W2, ((st.E - 1) * st.ldw2 + st.S) * esz

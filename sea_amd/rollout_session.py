@@ -2,7 +2,8 @@
 condition up front and forget their caches when they return; a RolloutSession owns the caches between calls, so that the next condition can be chosen
 after the last state has been seen (closed loops, co-simulation), the fed-back state can be replaced (data assimilation), the rollout can go back
 (`rewind`) and many futures can branch off one shared history (`fork`: one sea_kv_cache_fork launch per 32 cache tensors instead of a prefill of the
-repeated history).
+repeated history) or be kept, dropped, repeated and reordered afterwards (`select`, `resample`: one sea_kv_cache_gather launch per 32 cache tensors, which
+also converts between the two value-cache layouts, instead of a prefill of the selected histories).
 
 Positions: `position` p is the index of the newest known state.  The caches hold the keys / values of positions < p; a step feeds position p — its
 state (stored, or replaced through `state=`) and its condition, which arrives with the step — and predicts position p + 1, exactly as the reference's
@@ -15,7 +16,7 @@ slabs), and per decode form
     the session's single-step condition plan; a longer `advance` points the plan's hoisted condition pointers at its own, larger condition plan.
 The single-step condition plan (M = B rows) lives as long as the session, the `advance` one is kept for one row count at a time.
 
-Gradients through a session are not covered: step / advance / fork run under torch.no_grad(), so a condition or state that requires grad is
+Gradients through a session are not covered: step / advance / fork / select / resample run under torch.no_grad(), so a condition or state that requires grad is
 taken by value and no autograd graph is kept alive by the session's buffers.
 
 Weights are read through the engine's flat buffers (`params.sync()` at every call): a weight changed in mid-session takes effect from the next step
@@ -82,6 +83,43 @@ class CacheFork:
         N.check(N.lib().sea_kv_cache_fork(self.arr, len(self.arr), N.dtype_code(self.dtype), N.stream_ptr()), "sea_kv_cache_fork")
 
 
+class CacheGather:
+    """The sea_kv_cache_gather launch (include/sea_hip.h) from one session's caches into those of a session whose trajectory j is the source's
+    trajectory index[j]; an entry converts between value rows and V^T where the two sessions decode from different layouts.  Audited by
+    sea_amd/ptrcheck.py against the cache tensors of both sessions and the index tensor (int32, on the device, shared by every entry)."""
+
+    def __init__(self, entries: List[dict], index: torch.Tensor, dtype: torch.dtype, what: str):
+        self.dtype, self.what, self.index = dtype, what, index
+        self.owners = [d[k] for d in entries for k in ("src", "dst")] + [index]
+        self.arr = (N.SeaKvGather * len(entries))()
+        for g, d in zip(self.arr, entries):
+            ops.fill_kv_gather(g, index=index, **d)
+        self.rec = _Rec(N.lib().sea_kv_cache_gather, [self.arr, len(entries), N.dtype_code(dtype)], "kv.cache_gather", self.arr)
+        self.audit()
+
+    def audit(self) -> int:
+        R = ptrcheck.Ranges()
+        for t in self.owners:
+            R.add_tensor(t, "session cache")
+        return ptrcheck.check_records([self.rec], R, 4 if self.dtype == torch.float32 else 2, f"CacheGather {self.what}")
+
+    def run(self) -> None:
+        N.check(N.lib().sea_kv_cache_gather(self.arr, len(self.arr), N.dtype_code(self.dtype), N.stream_ptr()), "sea_kv_cache_gather")
+
+
+def check_select(B: int, index) -> List[int]:
+    """The index of select / resample on a session of B trajectories as a list of ints: a 1-D list, tuple or integer tensor (host or device: a device
+    tensor is copied to the host here, which synchronises) of length >= 1 with values in [0, B), duplicates allowed.  Raises ValueError."""
+    what = "rollout session: select"
+    if torch.is_tensor(index):
+        if index.dim() != 1 or index.dtype == torch.bool or index.is_floating_point() or index.is_complex():
+            raise ValueError(f"{what}: index must be a 1-D integer tensor, got {tuple(index.shape)} {index.dtype}")
+        index = index.detach().cpu()
+    elif not isinstance(index, (list, tuple)):
+        raise ValueError(f"{what}: index must be a list, a tuple or an integer tensor, got {type(index).__name__}")
+    return ops.check_gather_index(index, [B], [], what)
+
+
 def _own(view: torch.Tensor) -> torch.Tensor:
     """A contiguous tensor of its own.  (`.contiguous()` is no copy where it finds nothing to move — a permuted view whose moved dimension has
     size 1, i.e. B = 1 or one step — and would hand out session storage that a later call overwrites.)"""
@@ -101,7 +139,7 @@ class RolloutSession:
         m = eng.model
         B, k = check_open(m, x0, ib)
         self.eng, self.B, self.F, self.E, self.max_len = eng, B, m.num_variables, m.embed_dim, m.max_len
-        self.forked_by = forked_by          # None: opened; 'copy' / 'prefill': how fork() filled this session's caches
+        self.forked_by = forked_by          # None: opened; 'copy' / 'prefill': how fork() filled this session's caches; 'gather': select()
         self._closed = False
         self._alloc()
         self.traj[:k].copy_(x0.to(device=eng.device, dtype=torch.float32).permute(1, 0, 2, 3))
@@ -357,6 +395,53 @@ class RolloutSession:
             CacheFork(entries, self.eng.act_dtype, f"B={self.B} x {n} at position {pos}").run()
         t.position = pos
         return t
+
+    def _gathered(self, idx: List[int]) -> "RolloutSession":
+        """A new session whose trajectory j is trajectory idx[j] of this one (idx already checked): states and conditions through index_select, the
+        cache positions below `position` through ONE sea_kv_cache_gather launch per 32 cache tensors, which also converts value rows <-> V^T where
+        the new batch decodes from the other layout."""
+        pos = self.position
+        t = RolloutSession.__new__(RolloutSession)
+        t.eng, t.B, t.F, t.E, t.max_len = self.eng, len(idx), self.F, self.E, self.max_len
+        t.forked_by, t._closed = "gather", False
+        t._alloc()
+        index = torch.tensor(idx, dtype=torch.int32, device=self.eng.device)
+        t.traj[:pos + 1].copy_(self.traj[:pos + 1].index_select(1, index))
+        if pos > 0:
+            t.conds[:pos].copy_(self.conds[:pos].index_select(1, index))
+            mine, theirs = self._caches(), t._caches()
+            assert len(mine) == len(theirs)
+            entries = [dict(src=a, dst=b, n_pos=pos, src_transposed=ta, dst_transposed=tb) for (a, ta), (b, tb) in zip(mine, theirs)]
+            CacheGather(entries, index, self.eng.act_dtype, f"B={self.B} -> {t.B} at position {pos}").run()
+        t.position = pos
+        return t
+
+    @torch.no_grad()
+    def select(self, index) -> "RolloutSession":
+        """A new, independent session of len(index) trajectories at the same position: trajectory j has the states, conditions and cache positions
+        below `position` of trajectory index[j] of this session, which is left untouched.  index: a 1-D list, tuple or integer tensor with values in
+        [0, B), duplicates allowed (a device tensor is brought to the host once for validation: select then synchronises).  The caches are copied by
+        sea_kv_cache_gather (`forked_by == 'gather'`), never prefilled: where the new batch decodes from the other cache layout (kv_engine.supported
+        of len(index) against this session's form) the same launch converts the value caches.  At position 0 nothing is launched."""
+        self._live()
+        return self._gathered(check_select(self.B, index))
+
+    @torch.no_grad()
+    def resample(self, index) -> None:
+        """select(index) in place, len(index) == B: trajectory j becomes a copy of what trajectory index[j] was.  The selection is built in fresh
+        buffers (copying in place would read rows it has already overwritten), the device is synchronised as in close(), then this session adopts
+        them and releases its old ones.  Position, B and the decode form are unchanged; an identity index copies."""
+        self._live()
+        idx = check_select(self.B, index)
+        if len(idx) != self.B:
+            raise ValueError(f"rollout session: resample needs one index per trajectory (B = {self.B}), got {len(idx)}")
+        t = self._gathered(idx)
+        assert t.fast == self.fast and t.B == self.B
+        torch.cuda.synchronize(self.eng.device)   # the gather, and launches still in flight, read the old buffers by raw address
+        forked_by = self.forked_by
+        self.__dict__.update(t.__dict__)
+        self.forked_by = forked_by
+        t._closed = True
 
     def close(self) -> None:
         """Release the session's buffers (caches, workspace, trajectory).  Every later use raises ValueError."""
