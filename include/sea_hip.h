@@ -924,6 +924,54 @@ typedef struct {
     int32_t B_src, B_dst, H, hd, n_pos, cap_src, cap_dst, src_transposed, dst_transposed, pad_;
 } SeaKvGather;
 int sea_kv_cache_gather(const SeaKvGather* entries, int n, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Field-space loss of the spatial decoder: the mean-squared error of the DECODED fields against patch targets and its gradient with respect to the
+ * decoder's hidden rows, in one launch for all field groups (plus a one-block finish).  Replaces, for a loss taken on decoded fields
+ * (F.mse_loss(Decode(z), target) over models/encoder_decoder.py:126-146), the second decoder Linear (sea_gemm_grouped into an [M, n_fields * Cp] fp32
+ * output), sea_mse_fwd_bwd over that output and the data-gradient GEMM back to the hidden rows — without the output or the residual ever existing
+ * in memory.  Per group, rows m = 0 .. M-1:
+ *     Y[m, j, c] = sum_s H[m, s] W2[j Cp + c, s] + bias[j Cp + c]        j < n_fields, c < C        (fp32 accumulation)
+ *     D[m, j, c] = valid(m, c) ? Y[m, j, c] - target[m, field0 + j, c] : 0
+ *     loss       = inv_n * sum over groups, m, j, c of D^2
+ *     dH[m, s]   = 2 grad_scale inv_n * sum_{j, c} D[m, j, c] W2[j Cp + c, s]   [* gelu_erf'(Z[m, s]) when Z != NULL]     (written in the act dtype)
+ * H: the hidden rows GELU(z W1^T) and W2: the padded second-layer shadow copy, as Decode.forward prepares them; field j of a group sits at rows
+ * [j Cp, j Cp + C) of W2, the pad rows are zero.  Z: the saved pre-activation of the first layer (sea_gemm_grouped act = 1 with Z kept): with it dH is
+ * the gradient of the PRE-activation, ready for the data-gradient GEMM against W1.  target element (m, f, c) is at target + m ld_row + f ld_field + c
+ * (what sea_patchify writes in layout "BPFC"); f = field0 + j counts over all groups in the decoder's output order; only c < C is ever read.
+ * valid(m, c) = c < C when counts == NULL, else c < counts[m % P] (device int32 [P], values in [0, C]: a cell's mesh points are a prefix of its
+ * row; the kernel clamps a value outside [0, C] — a guard, not an interface).  Invalid slots and the pad columns contribute neither loss nor
+ * gradient, whatever the target holds there (NaN included).  inv_n is the caller's 1 / (number of valid elements).
+ * The residual is rounded to the act dtype once between the two products; the loss is summed from the fp32 residual through `partial` (f32,
+ * n_partial_cap >= ceil(M / 64) * n_groups) in a fixed order and dH has one writer per element: two runs give the same bits.
+ * Requirements: dtype SEA_BF16 (SEA_F32 returns SEA_EUNSUPPORTED: the fp32 decoder composes the launches above); M >= 1; S a multiple of 8, at most
+ * 640 (above: SEA_EUNSUPPORTED); any S in that range — the contraction is padded by masking in the kernel, the shadow copies stay [.., S]; Cp a
+ * multiple of 32, 1 <= C <= Cp; P >= 1 and M % P == 0 when counts is given; ld_row, ld_field multiples of 4, target 16-byte aligned; per group all
+ * pointers but Z non-NULL and 16-byte aligned, ldh, ldw multiples of 8, every row stride >= S; 1 <= n_groups <= SEA_DECODE_MSE_MAX_GROUPS.
+ * Returns -1, with the entry point and the offending group named in sea_last_error(), otherwise; nothing touches a device before the checks pass.
+ * (An addition to ABI version 8.  sea_struct_sizes() keeps its 33 entries: sizeof(SeaDecodeMseGroup) is 64, sizeof(SeaDecodeMse) 80.)
+ */
+#define SEA_DECODE_MSE_MAX_GROUPS 16
+typedef struct {
+    const void* H;       /* act [M, S], row stride ldh */
+    const void* W2;      /* act [n_fields * Cp, S], row stride ldw */
+    const float* bias;   /* f32 [n_fields * Cp] */
+    void* dH;            /* act [M, S], row stride lddh (output) */
+    const void* Z;       /* act [M, S], row stride ldz, or NULL */
+    int32_t ldh, ldw, lddh, ldz;
+    int32_t n_fields;    /* fields of this group */
+    int32_t field0;      /* index of the group's first field in the target */
+} SeaDecodeMseGroup;
+typedef struct {
+    const float* target;
+    const int32_t* counts;   /* device int32 [P] or NULL */
+    float* loss;             /* f32 [1] (output) */
+    float* partial;          /* f32 [n_partial_cap] workspace */
+    int64_t ld_row, ld_field;
+    int32_t M, S, C, Cp, P, n_partial_cap;
+    float inv_n, grad_scale;
+} SeaDecodeMse;
+int sea_decode_mse(const SeaDecodeMseGroup* groups, int n_groups, const SeaDecodeMse* p, int dtype, void* stream);
 /* Tuning aid: register a device buffer of n_steps * 64 8-byte words that the persistent form fills with 100 MHz clock stamps of its hand-offs
  * (tools/kv_persist_timeline.py); NULL switches it off. */
 void sea_kv_debug_stamps(unsigned long long* buf);

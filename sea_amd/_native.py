@@ -261,6 +261,22 @@ class SeaKvGather(C.Structure):
                 ("cap_src", _i32), ("cap_dst", _i32), ("src_transposed", _i32), ("dst_transposed", _i32), ("pad_", _i32)]
 
 
+DECODE_MSE_MAX_GROUPS = 16
+DECODE_MSE_ROWS = 64       # rows per workgroup of sea_decode_mse: its partial workspace holds ceil(M / 64) * n_groups floats
+DECODE_MSE_MAX_S = 640
+
+
+class SeaDecodeMseGroup(C.Structure):
+    # (not in ABI_STRUCTS, like SeaKvGather; tests/test_decode_loss_cpu.py checks the layouts through the library's argument checks)
+    _fields_ = [("H", _vp), ("W2", _vp), ("bias", _vp), ("dH", _vp), ("Z", _vp), ("ldh", _i32), ("ldw", _i32), ("lddh", _i32), ("ldz", _i32),
+                ("n_fields", _i32), ("field0", _i32)]
+
+
+class SeaDecodeMse(C.Structure):
+    _fields_ = [("target", _vp), ("counts", _vp), ("loss", _vp), ("partial", _vp), ("ld_row", _i64), ("ld_field", _i64),
+                ("M", _i32), ("S", _i32), ("C", _i32), ("Cp", _i32), ("P", _i32), ("n_partial_cap", _i32), ("inv_n", _f32), ("grad_scale", _f32)]
+
+
 MAX_WGRAD_GROUPS = 32
 MAX_NORM_BWD_GROUPS = 8
 MAX_SILU_BWD_GROUPS = 24
@@ -362,6 +378,8 @@ def lib() -> C.CDLL:
     L.sea_kv_cache_fork.restype = C.c_int
     L.sea_kv_cache_gather.argtypes = [C.POINTER(SeaKvGather), C.c_int, C.c_int, _vp]
     L.sea_kv_cache_gather.restype = C.c_int
+    L.sea_decode_mse.argtypes = [C.POINTER(SeaDecodeMseGroup), C.c_int, C.POINTER(SeaDecodeMse), C.c_int, _vp]
+    L.sea_decode_mse.restype = C.c_int
     for name in ("sea_attention_bwd", "sea_wgrad_grouped", "sea_transpose_weights", "sea_rownorm_bwd", "sea_silu_outer_bwd", "sea_ib_bwd",
                  "sea_silu_outer_bwd_dc", "sea_ib_bwd_dc"):
         getattr(L, name).restype = C.c_int
@@ -390,7 +408,7 @@ EXPORTED_SYMBOLS = (
     "sea_mse_fwd_bwd", "sea_relative_mse", "sea_adamw_flat",
     "sea_wgrad_grouped", "sea_transpose_weights", "sea_rownorm_bwd", "sea_silu_outer_bwd", "sea_ib_bwd",
     "sea_attention_bwd", "sea_dropout_mask", "sea_run_list", "sea_run_list_steps", "sea_unpatchify", "sea_gemm_rownorm", "sea_exchange_tail", "sea_patchify", "sea_silu_outer_ib", "sea_mlp_fc1_ln_gelu", "sea_mlp_fc2_proj_norm", "sea_kv_rollout", "sea_kv_arena_words", "sea_kv_debug_stamps",
-    "sea_kv_cache_fill", "sea_kv_cache_fork", "sea_kv_cache_gather",
+    "sea_kv_cache_fill", "sea_kv_cache_fork", "sea_kv_cache_gather", "sea_decode_mse",
     "sea_gemm_fewrows", "sea_qkv_rope_fewrows", "sea_row_chain", "sea_row_chain_riders", "sea_gemm_adaln", "sea_mlp_block", "sea_adaln_qkv", "sea_splitk_finish",
     "sea_encoder_block_ws_floats", "sea_encoder_block_fwd", "sea_encoder_block_bwd",
     "sea_silu_outer_bwd_dc", "sea_silu_outer_bwd_dc_ws_floats", "sea_ib_bwd_dc",

@@ -1,0 +1,298 @@
+// Field-space loss of the spatial decoder (gfx950): sea_decode_mse.  The second decoder layer, the masked mean-squared error against the
+// patch targets and the data gradient back to the hidden rows in ONE launch (plus a one-block finish that sums the loss partials):
+//     Y = H W2^T + bias;   D = valid ? Y - target : 0;   loss = inv_n sum D^2;   dH = 2 grad_scale inv_n (D W2) [* GELU'(Z)]
+// Y and D are never stored: W2 is the operand of BOTH products (contracted over the hidden index s in the first, over the output column c in
+// the second), so a [rows, columns] tile lives only in the accumulator registers between two MFMA stages — the shape of a flash-attention
+// backward with W2 as K and V at once.
+//
+// Tiling.  A workgroup (4 waves) owns 64 rows of one field group, wave w the rows 16 w .. 16 w + 15.  Each wave keeps its rows of H as MFMA
+// fragments in registers (SP / 8 per lane) and its [16, SP] slice of dH as fp32 accumulators (SP / 4 per lane: 160 at SP = 640, which with the
+// 80 fragment registers and the staging set fits the 512-register file at one wave per SIMD).  The workgroup walks the 32-row tiles of W2
+// (32 output columns of one field; tiles that lie wholly in the pad columns [C, Cp) are skipped).  A tile is fetched once per workgroup — from
+// L2, every workgroup of the launch reads the same few hundred kB — into one of two LDS images [32][SP] with a pitch of 2 SP + 32 bytes, through
+// registers: the loads of tile t + 1 are issued before the MFMAs of tile t and stored after them, one barrier per tile.  Per tile and wave:
+//   stage 1  Y^T[c, m] = sum_s W2[c, s] H[m, s]: W2 rows are the A operand (ds_read_b128, row c = lane & 15), the H fragments the B operand.  Two
+//            16-column sub-tiles, two accumulators each (even / odd k-steps), start from the bias.  The result has the row m on the lane and four
+//            consecutive columns c = 4 g + r in its registers,
+//   between  which is how the target is read (one float4 per lane and sub-tile, each element exactly once, requested before stage 1), the residual
+//            masked (select, so that a NaN or a huge value in an invalid slot is neutral), squared into the lane's loss sum, and rounded to bf16 ONCE,
+//            as the composed path rounds dY when its GEMM reads it.  The 8 values are the A fragment of stage 2 with k-slot (g, j) = column
+//            4 g + j (j < 4) or 16 + 4 g + j - 4,
+//   stage 2  dH[m, s] += sum_c D[m, c] W2[c, s]: the SAME LDS image read column-wise — two ds_read_b64_tr_b16 per 16 hidden columns deliver rows
+//            4 g .. 4 g + 3 and 16 + 4 g .. 16 + 4 g + 3 of the tile for column s = 16 st + (lane & 15): the k-slots above.
+// The pitch of 8 dwords mod 64 banks keeps both read forms conflict-free (the 16 rows of a b128 read land on 16 distinct 16-byte bank groups, the 8
+// rows of a 32-lane half of a transposed read on 8 distinct 32-byte ones).
+//
+// The hidden width is padded to SP in {128, 256, 384, 512, 640} by MASKING in the kernel, not in the shadow copies: H fragments and LDS chunks at
+// s >= S are zero (S % 8 == 0: a 16-byte chunk is wholly inside or outside), k-steps and column tiles at or beyond S are skipped (uniform branches:
+// the transposed reads need every lane active), dH stores are guarded by s < S.  Rows >= M hold zero fragments and a zero column limit; they take
+// part in every barrier and cross-lane read and store nothing.
+//
+// Loss: lane sums -> wave -> workgroup in a fixed order, one partial per workgroup, summed by the finish block in a fixed order; dH has one
+// writer per element.  No atomics: two runs give the same bits.
+//
+// What bounds it: per tile a wave issues 4 SP / 32 MFMAs (16x16x32) and reads the tile twice from LDS; with four waves per CU the LDS array
+// (256 B / clk) is busy about as long as the matrix cores, so the launch sits near half the bf16 MFMA rate at best, and the 64-row block leaves one
+// wave per SIMD (DESIGN.md section 7 has the measurements).
+#include "sea_common.hpp"
+
+typedef short dm_s16x4 __attribute__((ext_vector_type(4)));
+
+struct DecodeMseLaunch {
+    SeaDecodeMseGroup g[SEA_DECODE_MSE_MAX_GROUPS];
+    SeaDecodeMse p;
+};
+
+constexpr int DM_ROWS = 64;   // rows per workgroup
+constexpr int DM_TC = 32;     // W2 rows (output columns) per tile
+constexpr int DM_PAD = 32;    // bytes added to an LDS row
+
+template <int SP>
+constexpr int dm_lds_bytes() { return 2 * DM_TC * (SP * 2 + DM_PAD) + 16; }
+
+// Tile t of a group (32 rows of W2: output columns [cb, cb + 32) of field j) into the thread's SP / 64 staging registers, chunks at s >= S zeroed; and on into an LDS image.
+template <int SP>
+__device__ __forceinline__ void dm_load_tile(uint4 (&wr)[SP / 64], const __bf16* W2, int ldw, int S, int Cp, int tpf, int t, int tid) {
+    constexpr int CPR = SP / 8;
+    const int j = t / tpf, cb = (t - j * tpf) * DM_TC;
+    const __bf16* src = W2 + (int64_t)(j * Cp + cb) * ldw;
+#pragma unroll
+    for (int u = 0; u < SP / 64; ++u) {
+        const int q = u * 256 + tid, r = q / CPR, ch = q - r * CPR;
+        wr[u] = ch * 8 < S ? *reinterpret_cast<const uint4*>(src + (int64_t)r * ldw + ch * 8) : make_uint4(0u, 0u, 0u, 0u);
+    }
+}
+template <int SP>
+__device__ __forceinline__ void dm_store_tile(const uint4 (&wr)[SP / 64], char* buf, int tid) {
+    constexpr int CPR = SP / 8, PITCH = SP * 2 + DM_PAD;
+#pragma unroll
+    for (int u = 0; u < SP / 64; ++u) {
+        const int q = u * 256 + tid, r = q / CPR, ch = q - r * CPR;
+        *reinterpret_cast<uint4*>(buf + r * PITCH + ch * 16) = wr[u];
+    }
+}
+
+template <int SP>
+__global__ __launch_bounds__(256) void decode_mse_kernel(const DecodeMseLaunch L) {
+    constexpr int KS = SP / 32;               // k-steps of stage 1
+    constexpr int ST = SP / 16;               // hidden-column tiles of stage 2
+    constexpr int PITCH = SP * 2 + DM_PAD;
+    constexpr int TILE = DM_TC * PITCH;
+    constexpr int CPR = SP / 8;               // 16-byte chunks per tile row
+    constexpr int NCH = DM_TC * CPR / 256;    // chunks per thread
+    static_assert(NCH * 256 == DM_TC * CPR, "whole chunks per thread");
+    extern __shared__ __attribute__((aligned(16))) char smem[];   // 2 tile images, then 4 floats of the loss reduction
+    float* red = reinterpret_cast<float*>(smem + 2 * TILE);
+
+    const SeaDecodeMseGroup& G = L.g[blockIdx.y];
+    const SeaDecodeMse& P = L.p;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, lg = lane >> 4;
+    const int M = P.M, S = P.S, C = P.C, Cp = P.Cp;
+    const int row0 = blockIdx.x * DM_ROWS + wave * 16;
+    const int m = row0 + li;   // the row this lane holds in the H fragments, in the stage-1 result and in the residual fragment
+    const __bf16* H = static_cast<const __bf16*>(G.H);
+    const __bf16* W2 = static_cast<const __bf16*>(G.W2);
+    const uint4 zero4 = make_uint4(0u, 0u, 0u, 0u);
+
+    // valid columns of this lane's row: [0, lim)
+    int lim = 0;
+    if (m < M) {
+        lim = C;
+        if (P.counts != nullptr) {
+            const int cnt = P.counts[m % P.P];
+            lim = cnt < 0 ? 0 : (cnt > C ? C : cnt);
+        }
+    }
+
+    uint4 hf[KS];
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+        const int s = ks * 32 + 8 * lg;
+        hf[ks] = (m < M && s < S) ? *reinterpret_cast<const uint4*>(H + (int64_t)m * G.ldh + s) : zero4;
+    }
+    f32x4 dh[ST];
+#pragma unroll
+    for (int st = 0; st < ST; ++st) dh[st] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    const int tpf = (C + DM_TC - 1) / DM_TC;   // tiles of a field that hold real columns
+    const int n_tiles = G.n_fields * tpf;
+    uint4 wr[NCH];
+    dm_load_tile<SP>(wr, W2, G.ldw, S, Cp, tpf, 0, tid);
+    dm_store_tile<SP>(wr, smem, tid);
+    __syncthreads();
+
+    float lsum = 0.f;
+    const float* trow = P.target + (int64_t)(m < M ? m : 0) * P.ld_row;
+    typedef dm_s16x4 __attribute__((address_space(3))) * lds_p;
+    for (int t = 0; t < n_tiles; ++t) {
+        const char* buf = smem + (t & 1) * TILE;
+        if (t + 1 < n_tiles) dm_load_tile<SP>(wr, W2, G.ldw, S, Cp, tpf, t + 1, tid);
+        const int j = t / tpf, cb = (t - j * tpf) * DM_TC;
+
+        // target of this lane's 2 x 4 columns (requested now, used after stage 1)
+        float tg[2][4];
+        const float* tf = trow + (int64_t)(G.field0 + j) * P.ld_field;
+#pragma unroll
+        for (int sub = 0; sub < 2; ++sub) {
+            const int c = cb + sub * 16 + 4 * lg;
+            tg[sub][0] = tg[sub][1] = tg[sub][2] = tg[sub][3] = 0.f;
+            if (c < lim) {
+                if (c + 4 <= C) {
+                    const float4 v = *reinterpret_cast<const float4*>(tf + c);
+                    tg[sub][0] = v.x; tg[sub][1] = v.y; tg[sub][2] = v.z; tg[sub][3] = v.w;
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        if (c + r < C) tg[sub][r] = tf[c + r];
+                }
+            }
+        }
+
+        // stage 1
+        f32x4 acc[2][2];
+#pragma unroll
+        for (int sub = 0; sub < 2; ++sub) {
+            const float4 b = *reinterpret_cast<const float4*>(G.bias + j * Cp + cb + sub * 16 + 4 * lg);
+            acc[sub][0] = f32x4{b.x, b.y, b.z, b.w};
+            acc[sub][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+            if (ks * 32 < S) {
+#pragma unroll
+                for (int sub = 0; sub < 2; ++sub) {
+                    const uint4 a = *reinterpret_cast<const uint4*>(buf + (sub * 16 + li) * PITCH + (ks * 4 + lg) * 16);
+                    mma16<__bf16>(a, hf[ks], acc[sub][ks & 1]);
+                }
+            }
+        }
+
+        // residual: masked, squared into the loss, rounded once
+        bf16x8 dfr;
+#pragma unroll
+        for (int sub = 0; sub < 2; ++sub) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int c = cb + sub * 16 + 4 * lg + r;
+                const float y = acc[sub][0][r] + acc[sub][1][r];
+                const float d = c < lim ? y - tg[sub][r] : 0.f;
+                lsum = fma1(d, d, lsum);
+                dfr[sub * 4 + r] = (__bf16)d;
+            }
+        }
+        const uint4 da = __builtin_bit_cast(uint4, dfr);
+
+        // stage 2
+        const char* tb = buf + (4 * lg + (li >> 2)) * PITCH + (4 * (li & 3)) * 2;
+#pragma unroll
+        for (int st = 0; st < ST; ++st) {
+            if (st * 16 < S) {
+                const dm_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(tb + st * 32));
+                const dm_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(tb + st * 32 + 16 * PITCH));
+                const uint2 l2 = __builtin_bit_cast(uint2, lo), h2 = __builtin_bit_cast(uint2, hi);
+                mma16<__bf16>(da, make_uint4(l2.x, l2.y, h2.x, h2.y), dh[st]);
+            }
+        }
+
+        if (t + 1 < n_tiles) dm_store_tile<SP>(wr, smem + ((t + 1) & 1) * TILE, tid);
+        __syncthreads();
+    }
+
+    // dH: register r of tile st is row 4 g + r of the wave, column 16 st + (lane & 15)
+    const float scale = 2.0f * P.grad_scale * P.inv_n;
+    __bf16* dH = static_cast<__bf16*>(G.dH);
+    const __bf16* Z = static_cast<const __bf16*>(G.Z);
+#pragma unroll
+    for (int st = 0; st < ST; ++st) {
+        const int s = st * 16 + li;
+        if (s < S) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int mr = row0 + 4 * lg + r;
+                if (mr < M) {
+                    float v = dh[st][r] * scale;
+                    if (Z != nullptr) v *= gelu_grad_for<__bf16>((float)Z[(int64_t)mr * G.ldz + s]);
+                    dH[(int64_t)mr * G.lddh + s] = (__bf16)v;
+                }
+            }
+        }
+    }
+
+    lsum = wave_sum(lsum);
+    if (lane == 0) red[wave] = lsum;
+    __syncthreads();
+    if (tid == 0) P.partial[blockIdx.y * gridDim.x + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// loss = inv_n * sum(partial), summed in a fixed order (one block)
+__global__ __launch_bounds__(256) void decode_mse_finish_kernel(const float* __restrict__ partial, int n_partial, float* __restrict__ loss, float inv_n) {
+    __shared__ float red[4];
+    float acc = 0.f;
+    for (int i = threadIdx.x; i < n_partial; i += 256) acc += partial[i];
+    acc = wave_sum(acc);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) loss[0] = ((red[0] + red[1]) + (red[2] + red[3])) * inv_n;
+}
+
+template <int SP>
+static int decode_mse_launch(const DecodeMseLaunch& L, dim3 grid, hipStream_t s) {
+    constexpr int lds = dm_lds_bytes<SP>();
+    static const hipError_t once = hipFuncSetAttribute(reinterpret_cast<const void*>(decode_mse_kernel<SP>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    (void)once;
+    decode_mse_kernel<SP><<<grid, dim3(256), lds, s>>>(L);
+    return 0;
+}
+
+extern "C" int sea_decode_mse(const SeaDecodeMseGroup* groups, int n_groups, const SeaDecodeMse* p, int dtype, void* stream) {
+    SEA_REQUIRE(groups != nullptr && p != nullptr, "sea_decode_mse: null argument table");
+    SEA_REQUIRE(n_groups >= 1 && n_groups <= SEA_DECODE_MSE_MAX_GROUPS, "sea_decode_mse: n_groups=%d outside 1..%d", n_groups, SEA_DECODE_MSE_MAX_GROUPS);
+    SEA_REQUIRE(dtype == SEA_F32 || dtype == SEA_BF16, "sea_decode_mse: bad dtype %d", dtype);
+    if (dtype != SEA_BF16) {
+        sea_set_error("sea_decode_mse: unsupported: bf16 only (the fp32 decoder composes sea_gemm_grouped and sea_mse_fwd_bwd)");
+        return SEA_EUNSUPPORTED;
+    }
+    const SeaDecodeMse& P = *p;
+    SEA_REQUIRE(P.target != nullptr && P.loss != nullptr && P.partial != nullptr, "sea_decode_mse: null target, loss or partial pointer");
+    SEA_REQUIRE(P.M >= 1, "sea_decode_mse: M=%d must be positive", P.M);
+    SEA_REQUIRE(P.S >= 8 && P.S % 8 == 0, "sea_decode_mse: S=%d must be a positive multiple of 8", P.S);
+    SEA_REQUIRE(P.Cp >= 32 && P.Cp % 32 == 0, "sea_decode_mse: Cp=%d must be a positive multiple of 32", P.Cp);
+    SEA_REQUIRE(P.C >= 1 && P.C <= P.Cp, "sea_decode_mse: C=%d must lie in 1..Cp=%d", P.C, P.Cp);
+    SEA_REQUIRE(P.P >= 1, "sea_decode_mse: P=%d must be positive", P.P);
+    SEA_REQUIRE(P.counts == nullptr || P.M % P.P == 0, "sea_decode_mse: M=%d is not a multiple of P=%d (counts given)", P.M, P.P);
+    SEA_REQUIRE(P.ld_row >= 0 && P.ld_row % 4 == 0 && P.ld_field >= 0 && P.ld_field % 4 == 0,
+                "sea_decode_mse: target strides ld_row=%lld, ld_field=%lld must be multiples of 4", (long long)P.ld_row, (long long)P.ld_field);
+    SEA_REQUIRE(sea_aligned16(P.target) && sea_aligned4(P.counts) && sea_aligned4(P.loss) && sea_aligned4(P.partial), "sea_decode_mse: misaligned target, counts, loss or partial pointer");
+    for (int g = 0; g < n_groups; ++g) {
+        const SeaDecodeMseGroup& G = groups[g];
+        SEA_REQUIRE(G.H != nullptr && G.W2 != nullptr && G.bias != nullptr && G.dH != nullptr, "sea_decode_mse: group %d: null pointer", g);
+        SEA_REQUIRE(sea_aligned16(G.H) && sea_aligned16(G.W2) && sea_aligned16(G.bias) && sea_aligned16(G.dH) && sea_aligned16(G.Z), "sea_decode_mse: group %d: pointers must be 16-byte aligned", g);
+        SEA_REQUIRE(G.ldh >= P.S && G.ldh % 8 == 0 && G.ldw >= P.S && G.ldw % 8 == 0 && G.lddh >= P.S && G.lddh % 2 == 0 && (G.Z == nullptr || G.ldz >= P.S),
+                    "sea_decode_mse: group %d: row strides ldh=%d ldw=%d lddh=%d ldz=%d must cover S=%d (ldh, ldw multiples of 8)", g, G.ldh, G.ldw, G.lddh, G.ldz, P.S);
+        SEA_REQUIRE(G.n_fields >= 1 && G.field0 >= 0, "sea_decode_mse: group %d: n_fields=%d, field0=%d", g, G.n_fields, G.field0);
+        SEA_REQUIRE((int64_t)G.n_fields * P.Cp <= 0x7fffffffLL / 2, "sea_decode_mse: group %d: too many output columns", g);
+    }
+    if (P.S > 640) {
+        sea_set_error("sea_decode_mse: unsupported: hidden width S=%d above 640", P.S);
+        return SEA_EUNSUPPORTED;
+    }
+    const int64_t row_blocks = ((int64_t)P.M + DM_ROWS - 1) / DM_ROWS;
+    SEA_REQUIRE(row_blocks * n_groups <= 0x7fffffffLL && row_blocks <= 0x7fffffffLL, "sea_decode_mse: too many rows");
+    SEA_REQUIRE((int64_t)P.n_partial_cap >= row_blocks * n_groups, "sea_decode_mse: partial workspace of %d floats is too small: %lld needed (ceil(M / 64) * n_groups)",
+                P.n_partial_cap, (long long)(row_blocks * n_groups));
+
+    DecodeMseLaunch L;
+    memset(&L, 0, sizeof(L));
+    for (int g = 0; g < n_groups; ++g) L.g[g] = groups[g];
+    L.p = P;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)row_blocks, (unsigned)n_groups);
+    if (P.S <= 128) decode_mse_launch<128>(L, grid, s);
+    else if (P.S <= 256) decode_mse_launch<256>(L, grid, s);
+    else if (P.S <= 384) decode_mse_launch<384>(L, grid, s);
+    else if (P.S <= 512) decode_mse_launch<512>(L, grid, s);
+    else decode_mse_launch<640>(L, grid, s);
+    decode_mse_finish_kernel<<<dim3(1), dim3(256), 0, s>>>(P.partial, (int)(row_blocks * n_groups), P.loss, P.inv_n);
+    SEA_CHECK_LAUNCH("sea_decode_mse");
+    return SEA_OK;
+}

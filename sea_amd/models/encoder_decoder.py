@@ -83,8 +83,9 @@ class Decode(nn.Module):
 
     def forward(self, z: torch.Tensor) -> torch.Tensor:
         N.require_gpu(z, "Decode input")
-        if z.requires_grad or (torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()) and False):
-            raise NotImplementedError("sea_amd.Decode: inference only")
+        if z.requires_grad and torch.is_grad_enabled():
+            self._require_frozen("forward")
+            return _DecodeFn.apply(z, self)
         B, P, G, D = z.shape
         assert G == self.num_groups and D == self.embed_dim, (z.shape, self.num_groups, self.embed_dim)
         dt = torch.float32 if self.compute_dtype == "fp32" else torch.bfloat16
@@ -108,6 +109,110 @@ class Decode(nn.Module):
         out = out.view(B, P, n_fields, Cp)
         return out if Cp == self.n_inp else out[..., :self.n_inp]   # a strided view: sea_unpatchify reads it in place
 
+    # ------------------------------------------------------------------ gradients to z (the decoder as a frozen observation operator)
+    def _require_frozen(self, what: str) -> None:
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            raise ValueError(f"sea_amd.Decode.{what}: gradients flow to z only, but a decoder parameter requires grad and would silently get none: call "
+                             "decoder.requires_grad_(False) to use the decoder as a frozen observation operator (training the decoder itself is "
+                             "SpatialModel's training path)")
+
+    def _act_dtype(self) -> torch.dtype:
+        return torch.float32 if self.compute_dtype == "fp32" else torch.bfloat16
+
+    def _weights_T(self, dt: torch.dtype):
+        """W1^T [D, S] and W2^T [S, n_fields * Cp] of every group in the activation dtype: the operands of the two data-gradient launches (kept under the
+        attribute the spatial training engine uses, refreshed with the shadow copies)."""
+        W1, W2 = self._weights(dt)
+        cur = getattr(self, "_shadow_T", None)
+        if cur is None or cur[0] is not self._shadow:
+            cur = (self._shadow, [w.t().contiguous() for w in W1], [w.t().contiguous() for w in W2])
+            self._shadow_T = cur
+        return cur[1], cur[2]
+
+    def _first_layer(self, z: torch.Tensor, dt: torch.dtype):
+        """forward()'s first grouped launch with the GELU pre-activation kept: (hidden rows, pre-activations), each a list of [M, MLP_hidden] per group."""
+        B, P, G, D = z.shape
+        assert G == self.num_groups and D == self.embed_dim, (z.shape, self.num_groups, self.embed_dim)
+        M = B * P
+        zf = z.detach().to(torch.float32).contiguous().view(M, G * D)
+        za = zf if dt == torch.float32 else torch.empty(M, G * D, device=z.device, dtype=dt)
+        if dt != torch.float32:
+            ops.convert(zf, za)
+        W1, _ = self._weights(dt)
+        hid = [torch.empty(M, self.MLP_hidden, device=z.device, dtype=dt) for _ in range(G)]
+        pre = [torch.empty(M, self.MLP_hidden, device=z.device, dtype=dt) for _ in range(G)]
+        ops.gemm_grouped([dict(A=za[:, g * D:(g + 1) * D], W=W1[g], Cact=hid[g], Z=pre[g], act=1) for g in range(G)], dt)
+        return hid, pre
+
+    def _input_grad(self, dpre: List[torch.Tensor], dt: torch.dtype) -> torch.Tensor:
+        """dz [M, G * D] f32 from the pre-activation gradients of the groups: one grouped data-gradient launch against W1^T."""
+        W1T, _ = self._weights_T(dt)
+        D = self.embed_dim
+        dz = torch.empty(dpre[0].shape[0], self.num_groups * D, device=dpre[0].device, dtype=torch.float32)
+        ops.gemm_grouped([dict(A=dpre[g], W=W1T[g], C32=dz[:, g * D:(g + 1) * D]) for g in range(self.num_groups)], dt)
+        return dz
+
+    def _valid_counts(self, counts, P: int, device: torch.device):
+        """(device int32 [P] or None, valid cells summed over the patches) for mse_loss; checked on the host, cached per counts object."""
+        if counts is None:
+            return None, P * self.n_inp
+        key = (id(counts), getattr(counts, "_version", None), P, device)
+        cur = getattr(self, "_counts_cache", None)
+        if cur is not None and cur[0] == key:
+            return cur[1], cur[2]
+        host = counts.detach().cpu() if torch.is_tensor(counts) else torch.as_tensor(list(counts))
+        if host.dim() != 1 or host.shape[0] != P or host.is_floating_point() or host.is_complex() or host.dtype == torch.bool:
+            raise ValueError(f"sea_amd.Decode.mse_loss: counts must be {P} integers (one per patch), got shape {tuple(host.shape)} {host.dtype}")
+        if int(host.min()) < 0 or int(host.max()) > self.n_inp:
+            raise ValueError(f"sea_amd.Decode.mse_loss: counts must lie in [0, n_inp = {self.n_inp}], got {int(host.min())} .. {int(host.max())}")
+        total = int(host.sum())
+        if total < 1:
+            raise ValueError("sea_amd.Decode.mse_loss: counts leave no valid element")
+        dev = host.to(device=device, dtype=torch.int32).contiguous()
+        self._counts_cache = (key, dev, total, counts)   # the object is kept so that its id is not reused
+        return dev, total
+
+    def mse_loss(self, z: torch.Tensor, target: torch.Tensor, counts=None, fused: Optional[bool] = None) -> torch.Tensor:
+        """Mean squared error of the decoded fields against `target` over the valid elements, as a 0-dim fp32 tensor; gradient flows to z only.
+        z [B, P, n_groups, embed_dim]; target float32 [B, P, n_fields, C] with C == n_inp or any wider row (e.g. c_out of patchify_and_scale: only the
+        first n_inp columns of a row are read); counts: None (every column of a cell is valid: the value equals F.mse_loss(decode(z), target)) or one
+        integer per patch in [0, n_inp] — the cell's mesh points are the first counts[p] slots of its rows, the rest is padding that contributes neither
+        loss nor gradient.  bf16 compute dtype: ONE fused launch (sea_decode_mse) between the two small-K ends — the decoded fields are never written;
+        fp32 compute dtype: forward() + the loss in eager launches.  `fused` forces either path (None: fused in bf16, except at the one measured size where
+        the composed path is faster: hidden width above 512, no counts, fewer than 16384 rows — the fused path there is leaner, not faster)."""
+        n_fields = sum(len(g) for g in self.field_groups)
+        C = self.n_inp
+        if z.dim() != 4 or z.shape[2] != self.num_groups or z.shape[3] != self.embed_dim:
+            raise ValueError(f"sea_amd.Decode.mse_loss: z must be [B, P, {self.num_groups}, {self.embed_dim}], got {tuple(z.shape)}")
+        B, P = z.shape[0], z.shape[1]
+        if target.dim() != 4 or tuple(target.shape[:3]) != (B, P, n_fields) or target.shape[3] < C:
+            raise ValueError(f"sea_amd.Decode.mse_loss: target must be [{B}, {P}, {n_fields}, >= {C}], got {tuple(target.shape)}")
+        if target.dtype != torch.float32 or target.device != z.device:
+            raise ValueError(f"sea_amd.Decode.mse_loss: target must be float32 on {z.device}, got {target.dtype} on {target.device}")
+        if target.requires_grad and torch.is_grad_enabled():
+            raise ValueError("sea_amd.Decode.mse_loss: the target must not require grad (gradients flow to z only)")
+        self._require_frozen("mse_loss")
+        dt = self._act_dtype()
+        if fused is None:
+            # measured (tools/decode_loss_bench.py, DESIGN.md section 7c): the fused launch is the faster path everywhere except at the padded hidden width 640 with
+            # every column valid and few rows (multiphase decoder, B = 1: 1.10 against 1.05 ms), where the composed path stays the default
+            fused = dt == torch.bfloat16 and not (counts is None and self.MLP_hidden > 512 and B * P < 16384)
+        if fused and dt != torch.bfloat16:
+            raise ValueError("sea_amd.Decode.mse_loss: the fused launch is bf16 only (set_compute_dtype('bf16'), or fused=False)")
+        cnt, per_snapshot = self._valid_counts(counts, P, z.device)
+        n_valid = B * n_fields * per_snapshot
+        N.require_gpu(z, "Decode.mse_loss input")
+        if fused:
+            return _DecodeMseFn.apply(z, self, target, cnt, n_valid)
+        y = self.forward(z)
+        t = target[..., :C]
+        if cnt is None:
+            from ..autograd import MSELossFn
+
+            return MSELossFn.apply(y, t)
+        valid = (torch.arange(C, device=z.device) < cnt[:, None]).view(1, P, 1, C)
+        d = torch.where(valid, y - t, torch.zeros((), device=z.device))
+        return (d * d).sum() / n_valid
 
     def forward_prefix(self, z: torch.Tensor, buckets) -> torch.Tensor:
         """The decoder for a consumer that only reads the first cells of a patch (MeshUnpatcher.decode_and_unpatch: a patch holds as many mesh points as its
@@ -144,6 +249,91 @@ class Decode(nn.Module):
         for s0 in range(0, len(groups), N.MAX_GROUPS):
             ops.gemm_grouped(groups[s0:s0 + N.MAX_GROUPS], dt)
         return out.view(P, B, n_fields, Cp).permute(1, 0, 2, 3)[..., :self.n_inp]
+
+
+class _DecodeFn(torch.autograd.Function):
+    """Decode.forward with a gradient to z: the launches of the inference forward (the first with the GELU pre-activation kept); the backward is two
+    grouped data-gradient launches of sea_gemm_grouped — against W2^T with GELU' of the saved pre-activation in the epilogue, then against W1^T."""
+
+    @staticmethod
+    def forward(ctx, z, dec):
+        dt = dec._act_dtype()
+        B, P, G, _ = z.shape
+        M = B * P
+        hid, pre = dec._first_layer(z, dt)
+        _, W2 = dec._weights(dt)
+        n_fields = sum(len(g) for g in dec.field_groups)
+        Cp = dec._n_inp_p
+        out = torch.empty(M, n_fields * Cp, device=z.device, dtype=torch.float32)
+        groups, off = [], 0
+        for g, grp in enumerate(dec.field_groups):
+            w = len(grp) * Cp
+            groups.append(dict(A=hid[g], W=W2[g], bias=dec._shadow[3][g], C32=out[:, off:off + w]))
+            off += w
+        ops.gemm_grouped(groups, dt)
+        ctx.dec, ctx.dt, ctx.zshape, ctx.zdtype = dec, dt, z.shape, z.dtype
+        ctx.save_for_backward(*pre)
+        out = out.view(B, P, n_fields, Cp)
+        return out if Cp == dec.n_inp else out[..., :dec.n_inp]
+
+    @staticmethod
+    def backward(ctx, dout):
+        dec, dt, pre = ctx.dec, ctx.dt, ctx.saved_tensors
+        B, P, G, _ = ctx.zshape
+        M, C, Cp = B * P, dec.n_inp, dec._n_inp_p
+        n_fields = sum(len(g) for g in dec.field_groups)
+        dev = dout.device
+        if Cp == C:
+            dpad = dout.to(torch.float32).contiguous().view(M, n_fields * Cp)
+        else:
+            dpad = torch.zeros(B, P, n_fields, Cp, device=dev, dtype=torch.float32)
+            dpad[..., :C] = dout
+            dpad = dpad.view(M, n_fields * Cp)
+        da = dpad
+        if dt != torch.float32:
+            da = torch.empty(M, n_fields * Cp, device=dev, dtype=dt)
+            ops.convert(dpad, da)
+        _, W2T = dec._weights_T(dt)
+        dpre = [torch.empty(M, dec.MLP_hidden, device=dev, dtype=dt) for _ in range(G)]
+        groups, off = [], 0
+        for g, grp in enumerate(dec.field_groups):
+            w = len(grp) * Cp
+            groups.append(dict(A=da[:, off:off + w], W=W2T[g], act=2, Z=pre[g], Cact=dpre[g]))
+            off += w
+        ops.gemm_grouped(groups, dt)
+        return dec._input_grad(dpre, dt).view(ctx.zshape).to(ctx.zdtype), None
+
+
+class _DecodeMseFn(torch.autograd.Function):
+    """Decode.mse_loss on the fused path: first layer (pre-activation kept), sea_decode_mse (second layer, masked MSE and the gradient of the
+    pre-activation in one launch; nothing of size [rows, columns] is allocated), data-gradient launch against W1^T.  Forward and backward are one
+    pass, as in MSELossFn: the backward scales the stored dz."""
+
+    @staticmethod
+    def forward(ctx, z, dec, target, counts, n_valid):
+        dt = torch.bfloat16
+        B, P, G, _ = z.shape
+        M = B * P
+        t3 = target.reshape(M, target.shape[2], target.shape[3])
+        if t3.stride(2) != 1 or t3.stride(0) % 4 or t3.stride(1) % 4 or t3.data_ptr() % 16:
+            # a contiguous target of an odd cell width, or the reference's [.., C, n_fields] layout seen through a permute: one row-aligned copy
+            src = t3[..., :dec.n_inp]
+            t3 = torch.zeros(M, src.shape[1], (dec.n_inp + 3) // 4 * 4, device=src.device, dtype=torch.float32)
+            t3[..., :dec.n_inp] = src
+        hid, pre = dec._first_layer(z, dt)
+        _, W2 = dec._weights(dt)
+        bias = dec._shadow[3]
+        dpre = [torch.empty(M, dec.MLP_hidden, device=z.device, dtype=dt) for _ in range(G)]
+        loss = ops.decode_mse([dict(H=hid[g], W2=W2[g], bias=bias[g], dH=dpre[g], Z=pre[g]) for g in range(G)], t3, dec.n_inp, dec._n_inp_p,
+                              1.0 / n_valid, counts=counts, n_patches=P, dtype=dt)
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(dec._input_grad(dpre, dt).view(z.shape).to(z.dtype))
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        (dz,) = ctx.saved_tensors
+        return dz * g, None, None, None, None
 
 
 def _round_up(x: int, m: int) -> int:

@@ -903,3 +903,79 @@ def kv_cache_gather(entries: Sequence[Dict], index, dtype: torch.dtype) -> None:
     for g, d in zip(arr, entries):
         fill_kv_gather(g, index=dev_index, **d)
     N.check(N.lib().sea_kv_cache_gather(arr, len(entries), N.dtype_code(dtype), N.stream_ptr()), "sea_kv_cache_gather")
+
+
+def fill_decode_mse(groups_arr, P: N.SeaDecodeMse, groups: Sequence[Dict], target, counts, n_patches: int, C_: int, Cp: int, inv_n: float, grad_scale: float,
+                    loss, partial) -> None:
+    """The argument table of sea_decode_mse.  groups: dicts H act [M, S], W2 act [n_fields * Cp, S], bias f32 [n_fields * Cp], dH act [M, S], optional
+    Z act [M, S]; group g's fields follow those of the groups before it in the target.  target: f32 [M, n_fields_total, >= C] with unit inner stride."""
+    field0 = 0
+    for g, d in zip(groups_arr, groups):
+        H, W2, Z = d["H"], d["W2"], d.get("Z")
+        g.H, g.W2, g.bias, g.dH, g.Z = H.data_ptr(), W2.data_ptr(), d["bias"].data_ptr(), d["dH"].data_ptr(), N.ptr(Z)
+        g.ldh, g.ldw, g.lddh, g.ldz = H.stride(0), W2.stride(0), d["dH"].stride(0), (Z.stride(0) if Z is not None else 0)
+        g.n_fields, g.field0 = W2.shape[0] // Cp, field0
+        field0 += g.n_fields
+    P.target, P.counts, P.loss, P.partial = target.data_ptr(), N.ptr(counts), loss.data_ptr(), partial.data_ptr()
+    P.ld_row, P.ld_field = target.stride(0), target.stride(1)
+    P.M, P.S, P.C, P.Cp, P.P, P.n_partial_cap = groups[0]["H"].shape[0], groups[0]["H"].shape[1], C_, Cp, n_patches, partial.numel()
+    P.inv_n, P.grad_scale = inv_n, grad_scale
+
+
+def decode_mse(groups: Sequence[Dict], target: torch.Tensor, C_: int, Cp: int, inv_n: float, counts: Optional[torch.Tensor] = None, n_patches: int = 1,
+               grad_scale: float = 1.0, dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
+    """sea_decode_mse: loss = inv_n * sum of the squared valid residuals of the decoder's second layer against `target`, and d loss / d H (times GELU'(Z)
+    where a group carries Z) written into each group's dH.  groups as fill_decode_mse; target f32 [M, n_fields_total, Cw >= C_] (any row and field
+    strides that are multiples of 4, unit inner stride, 16-byte-aligned base); counts: device int32 [n_patches] (row m belongs to patch m % n_patches)
+    or None.  Everything is checked on the host before the launch; returns the loss as an f32 tensor of one element."""
+    if dtype != torch.bfloat16:
+        raise ValueError(f"decode_mse: the fused launch is bf16 only, got {dtype}")
+    if not groups or len(groups) > N.DECODE_MSE_MAX_GROUPS:
+        raise ValueError(f"decode_mse: {len(groups)} groups; a launch carries 1 .. {N.DECODE_MSE_MAX_GROUPS}")
+    if Cp < 32 or Cp % 32 or not 1 <= C_ <= Cp:
+        raise ValueError(f"decode_mse: need Cp a multiple of 32 and 1 <= C <= Cp, got C = {C_}, Cp = {Cp}")
+    dev = target.device
+    M, S = tuple(groups[0]["H"].shape) if groups[0]["H"].dim() == 2 else (0, 0)
+    if M < 1 or S < 8 or S % 8 or S > N.DECODE_MSE_MAX_S:
+        raise ValueError(f"decode_mse: H must be [M >= 1, S] with S a multiple of 8 up to {N.DECODE_MSE_MAX_S}, got {tuple(groups[0]['H'].shape)}")
+    n_fields = 0
+    for i, d in enumerate(groups):
+        for name in ("H", "W2", "dH", "Z"):
+            t = d.get(name)
+            if t is None and name == "Z":
+                continue
+            if t.dim() != 2 or t.stride(1) != 1:
+                raise ValueError(f"decode_mse group {i}: {name}: need a 2-D tensor with unit inner stride, got shape {tuple(t.shape)} strides {t.stride()}")
+            if t.dtype != dtype or t.device != dev or t.shape[1] != S or (name != "W2" and t.shape[0] != M):
+                raise ValueError(f"decode_mse group {i}: {name} must be a {dtype} [{'n_fields * Cp' if name == 'W2' else M}, {S}] tensor on {dev}, got "
+                                 f"{tuple(t.shape)} {t.dtype} on {t.device}")
+            if t.stride(0) % 8 or t.data_ptr() % 16:
+                raise ValueError(f"decode_mse group {i}: {name} needs a row stride that is a multiple of 8 and a 16-byte-aligned base (stride {t.stride(0)})")
+        W2, b = d["W2"], d["bias"]
+        if W2.shape[0] < Cp or W2.shape[0] % Cp:
+            raise ValueError(f"decode_mse group {i}: W2 has {W2.shape[0]} rows, not a multiple of Cp = {Cp}")
+        if b.dtype != torch.float32 or b.dim() != 1 or b.shape[0] != W2.shape[0] or not b.is_contiguous() or b.device != dev or b.data_ptr() % 16:
+            raise ValueError(f"decode_mse group {i}: bias must be a contiguous, 16-byte-aligned float32 [{W2.shape[0]}] on {dev}, got {tuple(b.shape)} {b.dtype}")
+        n_fields += W2.shape[0] // Cp
+    if target.dtype != torch.float32 or target.dim() != 3 or target.shape[0] != M or target.shape[1] != n_fields or target.shape[2] < C_:
+        raise ValueError(f"decode_mse: target must be float32 [{M}, {n_fields}, >= {C_}], got {tuple(target.shape)} {target.dtype}")
+    if target.stride(2) != 1 or target.stride(0) % 4 or target.stride(1) % 4 or target.data_ptr() % 16:
+        raise ValueError(f"decode_mse: target needs unit inner stride, row and field strides that are multiples of 4 and a 16-byte-aligned base, got strides "
+                         f"{target.stride()} (pad the cell width to a multiple of 4: patchify_and_scale(..., c_out=))")
+    if n_patches < 1:
+        raise ValueError(f"decode_mse: n_patches = {n_patches} must be positive")
+    if counts is not None:
+        if counts.dtype != torch.int32 or counts.dim() != 1 or counts.shape[0] != n_patches or not counts.is_contiguous() or counts.device != dev:
+            raise ValueError(f"decode_mse: counts must be a contiguous int32 [{n_patches}] on {dev}, got {tuple(counts.shape)} {counts.dtype} on {counts.device}")
+        if M % n_patches:
+            raise ValueError(f"decode_mse: {M} rows are not a multiple of {n_patches} patches")
+    if not inv_n > 0.0:
+        raise ValueError(f"decode_mse: inv_n = {inv_n} must be positive")
+    N.require_gpu(target, "decode_mse target")   # every operand is on the target's device (checked above)
+    n_partial = (M + N.DECODE_MSE_ROWS - 1) // N.DECODE_MSE_ROWS * len(groups)
+    loss = torch.empty(1, device=dev, dtype=torch.float32)
+    partial = torch.empty(n_partial, device=dev, dtype=torch.float32)
+    arr, P = (N.SeaDecodeMseGroup * len(groups))(), N.SeaDecodeMse()
+    fill_decode_mse(arr, P, groups, target, counts, n_patches, C_, Cp, float(inv_n), float(grad_scale), loss, partial)
+    N.check(N.lib().sea_decode_mse(arr, len(groups), C.byref(P), N.dtype_code(dtype), N.stream_ptr()), "sea_decode_mse")
+    return loss

@@ -18,7 +18,7 @@ import torch
 
 from .. import parallel
 from ..models.temporal import TemporalModel
-from ..utils.train_utils import SeaMSELoss, full_autoregressive_evaluation, initialize_optimizer
+from ..utils.train_utils import FieldSpaceLoss, SeaMSELoss, full_autoregressive_evaluation, initialize_optimizer
 
 
 def get_model(config: Dict[str, Any], device: torch.device) -> Tuple[TemporalModel, torch.nn.Module, torch.optim.Optimizer]:
@@ -36,7 +36,21 @@ def get_model(config: Dict[str, Any], device: torch.device) -> Tuple[TemporalMod
     optimizer = initialize_optimizer(model, config)
     if config.get('variational', False):
         raise NotImplementedError("sea_amd: the variational loss belongs to the spatial autoencoder path (out of scope)")
-    return model, SeaMSELoss(), optimizer
+    return model, _loss_fn(config), optimizer
+
+
+def _loss_fn(config: Dict[str, Any]) -> torch.nn.Module:
+    """config.get('loss_space', 'latent'): 'latent' is the reference's MSE on the model output; 'field' the MSE of the decoded fields against the
+    original patch fields the loaders yield as their third item (FieldSpaceLoss) — it needs config['decoder'] (a frozen sea_amd Decode on the device),
+    config['n_patches'] and, for cells with padding, config['patch_counts']; config.get('field_layout', 'BPFC') names the layout of those fields."""
+    space = config.get('loss_space', 'latent')
+    if space == 'latent':
+        return SeaMSELoss()
+    if space != 'field':
+        raise ValueError(f"sea_amd.train: config['loss_space'] must be 'latent' or 'field', got {space!r}")
+    if 'decoder' not in config or 'n_patches' not in config:
+        raise ValueError("sea_amd.train: config['loss_space'] = 'field' needs config['decoder'] (the frozen spatial decoder) and config['n_patches']")
+    return FieldSpaceLoss(config['decoder'], config['n_patches'], config.get('patch_counts'), layout=config.get('field_layout', 'BPFC'))
 
 
 def _rank_device(device: torch.device, want: int) -> torch.device:
@@ -139,6 +153,7 @@ def train(config: Dict[str, Any], error_tracker):
         eng.params.sync_transposed(force=True)
     shard = world > 1 and not _loader_shards_itself(trainLoader)
     fused = bool(config.get('fused_step', True)) and isinstance(loss_fn, SeaMSELoss)
+    field_space = isinstance(loss_fn, FieldSpaceLoss)   # the unfused step, against the loaders' third item (the original patch fields)
     start = time.time()
     best_val = float('inf')
     best_rollout = float('inf')
@@ -150,7 +165,9 @@ def train(config: Dict[str, Any], error_tracker):
         model.train()
         loss_sum = torch.zeros((), device=device)  # accumulated on the device: one host sync per epoch, not per step
         n_batches = 0
-        for data, target, _, ib in trainLoader:
+        for data, target, original, ib in trainLoader:
+            if field_space:
+                target = original
             weight = 1.0
             if shard:
                 # rank r's trajectories of the global batch.  A batch that does not divide by the world size — the reference's loader has no drop_last
@@ -187,7 +204,9 @@ def train(config: Dict[str, Any], error_tracker):
             model.eval()
             val_sum, n_val = torch.zeros((), device=device), 0
             with torch.no_grad():
-                for v_data, v_target, _, v_ib in validationLoader:   # every rank validates on the whole loader: identical models give identical metrics
+                for v_data, v_target, v_original, v_ib in validationLoader:   # every rank validates on the whole loader: identical models give identical metrics
+                    if field_space:
+                        v_target = v_original
                     v_out = model(v_data.to(device), v_ib.to(device))
                     val_sum += loss_fn(v_out, v_target.to(device))
                     n_val += 1
@@ -195,7 +214,7 @@ def train(config: Dict[str, Any], error_tracker):
             val_metrics = {"Loss": val_loss}
             if epoch % full_eval_interval == 0:
                 # every rank evaluates (identical models: identical numbers, and the checkpoint decision below must agree); rank 0 alone writes the CSV
-                res = full_autoregressive_evaluation(model, validationLoader, loss_fn, device, processor, mesh_processor,
+                res = full_autoregressive_evaluation(model, validationLoader, (SeaMSELoss() if field_space else loss_fn), device, processor, mesh_processor,
                                                      (config if rank == 0 else {**config, 'save_dir': None}), epoch, plot_traj=False)
                 if res is not None:   # None: an empty validation loader
                     val_metrics["Full_Encoded_Rel_MSE"] = res['encoded_rel_mse']

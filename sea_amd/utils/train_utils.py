@@ -56,6 +56,38 @@ class SeaMSELoss(torch.nn.Module):
         return MSELossFn.apply(output, target)
 
 
+class FieldSpaceLoss(torch.nn.Module):
+    """Mean squared error of the DECODED fields: loss = FieldSpaceLoss(decoder, n_patches, counts)(out, target_fields).
+
+    out: the temporal model's output [B, T, n_groups, P * D]; target_fields: float32 patch fields [B, T, P, n_fields, C] (what
+    patchify_and_scale(..., layout="BPFC") writes; C >= the decoder's n_inp) or, with layout="BPCF", the reference's [B, T, P, C, n_fields].
+    The latent -> z re-layout of inverse_transform_processed_data / decode_rollout is applied as torch views, so autograd carries the gradient
+    back to the temporal model's hand-written backward; the loss itself is Decode.mse_loss (one fused launch in bf16; the decoded fields are
+    never written).  `decoder` is a frozen sea_amd Decode (decoder.requires_grad_(False)); it is not registered as a sub-module, so the loss
+    has no parameters.  counts: valid cells per patch (None: all), see Decode.mse_loss."""
+
+    def __init__(self, decoder, n_patches: int, counts=None, layout: str = "BPFC", fused=None):
+        super().__init__()
+        if layout not in ("BPFC", "BPCF"):
+            raise ValueError(f"FieldSpaceLoss: layout must be 'BPFC' or 'BPCF', got {layout!r}")
+        if int(n_patches) < 1:
+            raise ValueError(f"FieldSpaceLoss: n_patches = {n_patches} must be positive")
+        object.__setattr__(self, "decoder", decoder)
+        self.n_patches, self.counts, self.layout, self.fused = int(n_patches), counts, layout, fused
+
+    def forward(self, output: torch.Tensor, target_fields: torch.Tensor, layout=None) -> torch.Tensor:
+        layout = self.layout if layout is None else layout
+        if output.dim() != 4 or output.shape[-1] % self.n_patches:
+            raise ValueError(f"FieldSpaceLoss: output must be [B, T, n_groups, n_patches * D] with n_patches = {self.n_patches}, got {tuple(output.shape)}")
+        B, T, G, _ = output.shape
+        if target_fields.dim() != 5 or tuple(target_fields.shape[:3]) != (B, T, self.n_patches):
+            raise ValueError(f"FieldSpaceLoss: target fields must be [{B}, {T}, {self.n_patches}, ...] in layout {layout}, got {tuple(target_fields.shape)}")
+        z = inverse_transform_processed_data(output, B, T, self.n_patches, G)
+        tgt = target_fields if layout == "BPFC" else target_fields.permute(0, 1, 2, 4, 3)
+        tgt = tgt.reshape((B * T,) + tuple(tgt.shape[2:]))
+        return self.decoder.mse_loss(z, tgt, counts=self.counts, fused=self.fused)
+
+
 # ------------------------------------------------------------------------------------------------ optimizer
 def initialize_optimizer(model, config):
     """AdamW(lr=config['learning_rate'], betas=(0.9, 0.999), eps=1e-8, weight_decay=config.get('weight_decay', 0.0)) as one fused
