@@ -444,6 +444,48 @@ int sea_relative_mse(const float* pred, const float* truth, float* y, int64_t ro
 int sea_adamw_flat(float* p, const float* g, float* m, float* v, void* shadow, int shadow_dtype, int64_t n, float lr, float beta1,
                    float beta2, float eps, float weight_decay, int step, float grad_scale, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Gradient clipping by global norm and skipping of non-finite steps, decided on the device: what
+ * torch.nn.utils.clip_grad_norm_ + a host-side isfinite() test do with hundreds of ATen launches and a sync, as two
+ * short launches in front of the AdamW launch and no sync.  The two entry points are a PAIR: one sea_grad_norm_ctl per
+ * sea_adamw_flat_ctl, on the same stream, over the same g, n and grad_scale (the first counts the step the second applies).
+ *
+ * The step control block `ctl`: eight 32-bit words of device memory, 16-byte aligned, owned by the caller, zeroed (or
+ * word SEA_CTL_STEP set to the steps already taken) before the first call and carried from step to step:
+ */
+enum {
+    SEA_CTL_GRAD_NORM = 0,     /* f32  2-norm of grad_scale * g, the mean gradient AdamW consumes */
+    SEA_CTL_CLIP = 1,          /* f32  factor applied on top of grad_scale (0 on a skipped step) */
+    SEA_CTL_INV_BC1 = 2,       /* f32  1 / (1 - beta1^step) */
+    SEA_CTL_INV_SQRT_BC2 = 3,  /* f32  1 / sqrt(1 - beta2^step) */
+    SEA_CTL_APPLIED = 4,       /* i32  1: this step updates the parameters; 0: it is skipped */
+    SEA_CTL_STEP = 5,          /* i32  number of applied steps, this one included when applied */
+    SEA_CTL_SKIPPED = 6,       /* i32  running count of skipped steps */
+    SEA_CTL_CLIPPED = 7,       /* i32  running count of applied steps with clip < 1 */
+    SEA_CTL_WORDS = 8
+};
+
+/* total = sum g^2, every square and sum in fp64 (elements of 1e25 or 1e-30 neither overflow nor vanish, and the total is
+ * non-finite exactly when an element is), in a fixed order: partial[b] per workgroup (at most min(1024, n_partial_cap) of
+ * them), then one workgroup whose first thread, in fp64, writes the control block:
+ *     norm = |grad_scale| sqrt(total);  grad_norm = (float)norm;  finite = isfinite(grad_norm)
+ *     !finite && skip_nonfinite:  applied = 0, clip = 0, skipped += 1; step and the two bias corrections keep their values
+ *     otherwise:  applied = 1, step += 1, inv_bc1 / inv_sqrt_bc2 from the new step,
+ *                 clip = (max_norm > 0 && finite) ? min(1, max_norm / (norm + 1e-6)) : 1   (clip_grad_norm_'s formula),
+ *                 clipped += 1 when the stored fp32 clip < 1
+ * so with skip_nonfinite = 0 a non-finite norm is applied with clip = 1, as sea_adamw_flat would.  max_norm <= 0: no clipping
+ * (NaN is refused).  n % 4 == 0, n >= 4; g and ctl 16-byte aligned, partial 8-byte aligned; 0 <= beta < 1.
+ * g is read only; nothing but partial[0 .. min(workgroups, n_partial_cap)) and the eight control words is written. */
+int sea_grad_norm_ctl(const float* g, int64_t n, float grad_scale, float max_norm, int skip_nonfinite, float beta1, float beta2,
+                      double* partial, int n_partial_cap, int32_t* ctl, void* stream);
+
+/* sea_adamw_flat with g' = (grad_scale * clip) * g and the bias corrections read from the control block instead of computed
+ * from a host-side step number.  ctl[SEA_CTL_APPLIED] == 0: every workgroup returns before its first load; p, m, v and the
+ * shadow stay bitwise what they were.  g is not scaled in place: after the step it still holds the unclipped gradients.
+ * Constraints of sea_adamw_flat, and ctl 16-byte aligned. */
+int sea_adamw_flat_ctl(float* p, const float* g, float* m, float* v, void* shadow, int shadow_dtype, int64_t n, float lr, float beta1,
+                       float beta2, float eps, float weight_decay, float grad_scale, const int32_t* ctl, void* stream);
+
 /* ============================================================================================================
  * Backward pass.  The reference gets it from autograd (loss.backward(), train/train_temporal.py:257); here every
  * operator has a hand-written backward.  Data gradients of the Linear layers reuse sea_gemm_grouped with the W^T shadow

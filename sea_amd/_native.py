@@ -17,6 +17,8 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libsea_hip.so")
 SEA_F32, SEA_BF16 = 0, 1
 ABI_VERSION = 8   # include/sea_hip.h SEA_ABI_VERSION
 MAX_GROUPS = 16
+# the step control block of sea_grad_norm_ctl / sea_adamw_flat_ctl (include/sea_hip.h, SEA_CTL_*): word indices
+CTL_GRAD_NORM, CTL_CLIP, CTL_INV_BC1, CTL_INV_SQRT_BC2, CTL_APPLIED, CTL_STEP, CTL_SKIPPED, CTL_CLIPPED, CTL_WORDS = range(9)
 MAX_ATTN_PROBLEMS = 8
 MAX_NORM_GROUPS = 16
 MAX_SILU_GROUPS = 24
@@ -387,9 +389,12 @@ def lib() -> C.CDLL:
     L.sea_relative_mse.argtypes = [_vp, _vp, _vp, _i64, C.c_int, _vp]
     L.sea_adamw_flat.argtypes = [_vp, _vp, _vp, _vp, _vp, C.c_int, _i64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
                                  C.c_int, C.c_float, _vp]
+    L.sea_grad_norm_ctl.argtypes = [_vp, _i64, C.c_float, C.c_float, C.c_int, C.c_float, C.c_float, _vp, C.c_int, _vp, _vp]
+    L.sea_adamw_flat_ctl.argtypes = [_vp, _vp, _vp, _vp, _vp, C.c_int, _i64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
+                                     C.c_float, _vp, _vp]
     for name in ("sea_gemm_grouped", "sea_qkv_rope_grouped", "sea_attention_fwd", "sea_rownorm", "sea_silu_outer",
                  "sea_ib_add", "sea_convert_f32_to_act", "sea_device_info", "sea_mse_fwd_bwd", "sea_relative_mse",
-                 "sea_adamw_flat"):
+                 "sea_adamw_flat", "sea_grad_norm_ctl", "sea_adamw_flat_ctl"):
         getattr(L, name).restype = C.c_int
     if L.sea_abi_version() != ABI_VERSION:
         raise NativeLibraryError(f"{LIB_PATH}: ABI version {L.sea_abi_version()} != {ABI_VERSION}; rebuild (python -m sea_amd.build --force)")
@@ -405,7 +410,7 @@ ABI_STRUCTS = (SeaGemmGroup, SeaQkvGroup, SeaQkvCommon, SeaAttnProblem, SeaAttnP
 EXPORTED_SYMBOLS = (
     "sea_abi_version", "sea_last_error", "sea_struct_sizes", "sea_device_info", "sea_gemm_grouped", "sea_qkv_rope_grouped",
     "sea_attention_fwd", "sea_rownorm", "sea_silu_outer", "sea_ib_add", "sea_convert_f32_to_act", "sea_selftest_mfma",
-    "sea_mse_fwd_bwd", "sea_relative_mse", "sea_adamw_flat",
+    "sea_mse_fwd_bwd", "sea_relative_mse", "sea_adamw_flat", "sea_grad_norm_ctl", "sea_adamw_flat_ctl",
     "sea_wgrad_grouped", "sea_transpose_weights", "sea_rownorm_bwd", "sea_silu_outer_bwd", "sea_ib_bwd",
     "sea_attention_bwd", "sea_dropout_mask", "sea_run_list", "sea_run_list_steps", "sea_unpatchify", "sea_gemm_rownorm", "sea_exchange_tail", "sea_patchify", "sea_silu_outer_ib", "sea_mlp_fc1_ln_gelu", "sea_mlp_fc2_proj_norm", "sea_kv_rollout", "sea_kv_arena_words", "sea_kv_debug_stamps",
     "sea_kv_cache_fill", "sea_kv_cache_fork", "sea_kv_cache_gather", "sea_decode_mse",

@@ -1,5 +1,6 @@
 // Loss, metric and optimizer kernels of the SEA temporal train step (gfx950): sea_mse_fwd_bwd, sea_relative_mse,
-// sea_adamw_flat.  All HBM-bandwidth-bound streaming passes: 16-byte accesses, grid-stride, fp32 arithmetic.
+// sea_adamw_flat, and the clipped / skippable pair sea_grad_norm_ctl + sea_adamw_flat_ctl.  All HBM-bandwidth-bound streaming passes:
+// 16-byte accesses, grid-stride, fp32 arithmetic (the gradient norm accumulates in fp64).
 #include "sea_common.hpp"
 
 __device__ __forceinline__ float block_sum_256(float v, float* red) {
@@ -177,5 +178,158 @@ extern "C" int sea_adamw_flat(float* p, const float* g, float* m, float* v, void
         adamw_flat_kernel<float><<<dim3((unsigned)blocks), dim3(256), 0, s>>>(p, g, m, v, static_cast<float*>(shadow), n4, lr, beta1, beta2, eps, lr_wd,
                                                                              (float)(1.0 / bc1), (float)(1.0 / sqrt(bc2)), grad_scale);
     SEA_CHECK_LAUNCH("sea_adamw_flat");
+    return SEA_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- gradient norm -> step control block
+__device__ __forceinline__ double block_sum_256_f64(double v, double* red) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) red[wave] = v;
+    __syncthreads();
+    const double total = (red[0] + red[1]) + (red[2] + red[3]);
+    __syncthreads();
+    return total;
+}
+
+// pass 1: partial[b] = sum over the block's elements of g^2, every square and every sum in fp64: no fp32 square overflows (|g| = 1e25) or vanishes
+// (|g| = 1e-30), and the total is non-finite exactly when an element is.  One accumulator per float4 component (four independent FMA chains);
+// four 16-byte loads in flight per thread while a full round of the grid remains.  The order of a thread's terms is fixed.
+__global__ __launch_bounds__(256) void grad_norm_partial_kernel(const float* __restrict__ g, int64_t n4, double* __restrict__ partial) {
+    __shared__ double red[4];
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    const float4* g4 = reinterpret_cast<const float4*>(g);
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    for (; i + 3 * stride < n4; i += 4 * stride) {
+        const float4 a = g4[i], b = g4[i + stride], c = g4[i + 2 * stride], d = g4[i + 3 * stride];
+        const float x[16] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y, c.z, c.w, d.x, d.y, d.z, d.w};
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[e & 3] = fma((double)x[e], (double)x[e], acc[e & 3]);
+    }
+    for (; i < n4; i += stride) {
+        const float4 a = g4[i];
+        const float x[4] = {a.x, a.y, a.z, a.w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[e] = fma((double)x[e], (double)x[e], acc[e]);
+    }
+    const double total = block_sum_256_f64((acc[0] + acc[1]) + (acc[2] + acc[3]), red);
+    if (threadIdx.x == 0) partial[blockIdx.x] = total;
+}
+
+__device__ __forceinline__ double powi_f64(double b, int e) {   // b^e, e >= 1, by squaring: a few fp64 ulps, no libm call on the device
+    double r = 1.0;
+    for (; e > 0; e >>= 1, b *= b)
+        if (e & 1) r *= b;
+    return r;
+}
+
+// pass 2 (one block): the partials summed in a fixed order, then ONE thread decides the step and writes the control block (include/sea_hip.h)
+__global__ __launch_bounds__(256) void grad_norm_final_kernel(const double* __restrict__ partial, int n_partial, float grad_scale, float max_norm,
+                                                              int skip_nonfinite, float beta1, float beta2, int32_t* __restrict__ ctl) {
+    __shared__ double red[4];
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < n_partial; i += 256) acc += partial[i];
+    const double total = block_sum_256_f64(acc, red);
+    if (threadIdx.x != 0) return;
+    const double norm = fabs((double)grad_scale) * sqrt(total);
+    const float norm32 = (float)norm;
+    const bool finite = (__float_as_uint(norm32) & 0x7f800000u) != 0x7f800000u;   // the exponent field itself: no floating-point compare to reason about
+    ctl[SEA_CTL_GRAD_NORM] = __float_as_int(norm32);
+    if (!finite && skip_nonfinite) {   // the step is dropped: step and the bias corrections keep the last applied step's values
+        ctl[SEA_CTL_CLIP] = __float_as_int(0.f);
+        ctl[SEA_CTL_APPLIED] = 0;
+        ctl[SEA_CTL_SKIPPED] += 1;
+        return;
+    }
+    const int step = ctl[SEA_CTL_STEP] + 1;
+    const double bc1 = 1.0 - powi_f64((double)beta1, step), bc2 = 1.0 - powi_f64((double)beta2, step);
+    double clip = 1.0;
+    if (max_norm > 0.f && finite) clip = fmin(1.0, (double)max_norm / (norm + 1e-6));   // torch.nn.utils.clip_grad_norm_
+    const float clip32 = (float)clip;
+    ctl[SEA_CTL_CLIP] = __float_as_int(clip32);
+    ctl[SEA_CTL_INV_BC1] = __float_as_int((float)(1.0 / bc1));
+    ctl[SEA_CTL_INV_SQRT_BC2] = __float_as_int((float)(1.0 / sqrt(bc2)));
+    ctl[SEA_CTL_APPLIED] = 1;
+    ctl[SEA_CTL_STEP] = step;
+    if (clip32 < 1.f) ctl[SEA_CTL_CLIPPED] += 1;
+}
+
+extern "C" int sea_grad_norm_ctl(const float* g, int64_t n, float grad_scale, float max_norm, int skip_nonfinite, float beta1, float beta2,
+                                 double* partial, int n_partial_cap, int32_t* ctl, void* stream) {
+    SEA_REQUIRE(g && partial && ctl, "sea_grad_norm_ctl: null pointer");
+    SEA_REQUIRE(n >= 4 && n % 4 == 0, "sea_grad_norm_ctl: n=%lld must be a positive multiple of 4", (long long)n);
+    SEA_REQUIRE(sea_aligned16(g) && sea_aligned16(ctl) && (reinterpret_cast<uintptr_t>(partial) & 7u) == 0,
+                "sea_grad_norm_ctl: g and ctl must be 16-byte aligned, partial 8-byte aligned");
+    SEA_REQUIRE(n_partial_cap >= 1, "sea_grad_norm_ctl: partial workspace too small");
+    SEA_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f, "sea_grad_norm_ctl: betas (%g, %g) must lie in [0, 1)", (double)beta1, (double)beta2);
+    SEA_REQUIRE(max_norm == max_norm, "sea_grad_norm_ctl: max_norm is NaN (<= 0 means no clipping)");
+    const int64_t n4 = n / 4;
+    int64_t blocks = (n4 + 255) / 256;
+    if (blocks > 1024) blocks = 1024;
+    if (blocks > n_partial_cap) blocks = n_partial_cap;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    grad_norm_partial_kernel<<<dim3((unsigned)blocks), dim3(256), 0, s>>>(g, n4, partial);
+    grad_norm_final_kernel<<<dim3(1), dim3(256), 0, s>>>(partial, (int)blocks, grad_scale, max_norm, skip_nonfinite, beta1, beta2, ctl);
+    SEA_CHECK_LAUNCH("sea_grad_norm_ctl");
+    return SEA_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- AdamW steered by the control block
+// adamw_flat_kernel with grad_scale * clip, the two bias corrections and the applied flag read from the control block sea_grad_norm_ctl wrote on the
+// same stream (wave-uniform loads).  A copy, not a shared body: the launch of sea_adamw_flat stays the code it was.  A skipped step returns before
+// any load or store of p, m, v or the shadow.
+template <typename T>
+__global__ __launch_bounds__(256) void adamw_flat_ctl_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                             float* __restrict__ v, T* __restrict__ shadow, int64_t n4, float lr, float beta1,
+                                                             float beta2, float eps, float lr_wd, float grad_scale, const int32_t* __restrict__ ctl) {
+    if (ctl[SEA_CTL_APPLIED] == 0) return;
+    const float inv_bc1 = __int_as_float(ctl[SEA_CTL_INV_BC1]), inv_sqrt_bc2 = __int_as_float(ctl[SEA_CTL_INV_SQRT_BC2]);
+    const float gscale = mul1(grad_scale, __int_as_float(ctl[SEA_CTL_CLIP]));
+    // scalar-lane helpers pin the evaluation order, as in adamw_flat_kernel (b m + (1-b) g must not become g + b (m - g))
+    const float omb1 = 1.0f - beta1, omb2 = 1.0f - beta2, step_size = lr * inv_bc1;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+        float pp[4], gg[4], mm[4], vv[4];
+        load4(p + 4 * i, pp);
+        load4(g + 4 * i, gg);
+        load4(m + 4 * i, mm);
+        load4(v + 4 * i, vv);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float gr = mul1(gg[e], gscale);
+            if (lr_wd != 0.f) pp[e] = fma1(-lr_wd, pp[e], pp[e]);   // p - (lr*wd) p, as in adamw_flat_kernel
+            mm[e] = fma1(beta1, mm[e], mul1(omb1, gr));
+            vv[e] = fma1(beta2, vv[e], mul1(mul1(omb2, gr), gr));
+            // plain C from here (adamw_flat_kernel: the wait states after v_sqrt / v_rcp are inserted for compiled code only)
+            const float denom = sqrtf(vv[e]) * inv_sqrt_bc2 + eps;
+            pp[e] -= step_size * (mm[e] / denom);
+        }
+        store4(p + 4 * i, pp[0], pp[1], pp[2], pp[3]);
+        store4(m + 4 * i, mm[0], mm[1], mm[2], mm[3]);
+        store4(v + 4 * i, vv[0], vv[1], vv[2], vv[3]);
+        if (shadow != nullptr) store4(shadow + 4 * i, pp[0], pp[1], pp[2], pp[3]);
+    }
+}
+
+extern "C" int sea_adamw_flat_ctl(float* p, const float* g, float* m, float* v, void* shadow, int shadow_dtype, int64_t n, float lr, float beta1,
+                                  float beta2, float eps, float weight_decay, float grad_scale, const int32_t* ctl, void* stream) {
+    SEA_REQUIRE(p && g && m && v && ctl, "sea_adamw_flat_ctl: null pointer");
+    SEA_REQUIRE(n >= 4 && n % 4 == 0, "sea_adamw_flat_ctl: n=%lld must be a positive multiple of 4", (long long)n);
+    SEA_REQUIRE(sea_aligned16(p) && sea_aligned16(g) && sea_aligned16(m) && sea_aligned16(v) && sea_aligned16(shadow) && sea_aligned16(ctl),
+                "sea_adamw_flat_ctl: pointers must be 16-byte aligned");
+    SEA_REQUIRE(!shadow || shadow_dtype == SEA_BF16 || shadow_dtype == SEA_F32, "sea_adamw_flat_ctl: bad shadow dtype");
+    const int64_t n4 = n / 4;
+    int64_t blocks = (n4 + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const float lr_wd = (float)((double)lr * (double)weight_decay);
+    if (shadow != nullptr && shadow_dtype == SEA_BF16)
+        adamw_flat_ctl_kernel<__bf16><<<dim3((unsigned)blocks), dim3(256), 0, s>>>(p, g, m, v, static_cast<__bf16*>(shadow), n4, lr, beta1, beta2, eps,
+                                                                                  lr_wd, grad_scale, ctl);
+    else
+        adamw_flat_ctl_kernel<float><<<dim3((unsigned)blocks), dim3(256), 0, s>>>(p, g, m, v, static_cast<float*>(shadow), n4, lr, beta1, beta2, eps,
+                                                                                 lr_wd, grad_scale, ctl);
+    SEA_CHECK_LAUNCH("sea_adamw_flat_ctl");
     return SEA_OK;
 }

@@ -47,6 +47,10 @@ def train(config: Dict[str, Any], error_tracker):
     start_time = time.time()
     prev_error = float('inf')
     error_tracker.log_model(model, loss_fn, optimizer)
+    # clipping / skipping (config['max_grad_norm'], config['skip_nonfinite_steps']): the loop reads the loss on the host every step, and reads
+    # the step's control block with it; a skipped step counts for neither the loss nor R^2
+    controlled = bool(getattr(optimizer, 'controlled', False))
+    grad_norm, stats = 0.0, None
 
     for epoch in range(1, config['epoch_num'] + 1):
         model.train()
@@ -58,12 +62,23 @@ def train(config: Dict[str, Any], error_tracker):
             loss = loss_fn(outputs, data)
             loss.backward()
             optimizer.step()
+            if controlled:
+                stats = optimizer.step_stats()
+                if not stats["applied"]:
+                    continue
+                grad_norm = stats["grad_norm"]
             train_loss += loss.item()
             train_r2_sum += calculate_R2(outputs.detach(), data).item()
             n_batches += 1
-        train_loss /= n_batches
-        train_r2 = train_r2_sum / n_batches
-        error_tracker.record_error("train", epoch, {"Loss": train_loss, "Recon_Loss": train_loss, "R2": train_r2})
+        if controlled and n_batches == 0:   # no step of the epoch was applied: there is nothing to average
+            train_loss = train_r2 = float('nan')
+        else:
+            train_loss /= n_batches
+            train_r2 = train_r2_sum / n_batches
+        record = {"Loss": train_loss, "Recon_Loss": train_loss, "R2": train_r2}
+        if controlled and stats is not None:
+            record.update({"GradNorm": grad_norm, "SkippedSteps": stats["skipped_steps"], "ClippedSteps": stats["clipped_steps"]})
+        error_tracker.record_error("train", epoch, record)
 
         if epoch % config.get('validation_interval', 1) == 0 or epoch == config['epoch_num']:
             model.eval()

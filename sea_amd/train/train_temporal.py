@@ -16,6 +16,7 @@ from typing import Any, Dict, Tuple
 
 import torch
 
+from .. import _native as N
 from .. import parallel
 from ..models.temporal import TemporalModel
 from ..utils.train_utils import FieldSpaceLoss, SeaMSELoss, full_autoregressive_evaluation, initialize_optimizer
@@ -161,6 +162,11 @@ def train(config: Dict[str, Any], error_tracker):
     error_tracker.log_model(model, loss_fn, optimizer)
     full_eval_interval = config.get('full_eval_interval', 50)
     skipped_small = False
+    # clipping / skipping (config['max_grad_norm'], config['skip_nonfinite_steps']): whether a step was applied is known on the device only, so
+    # the epoch's loss is masked there and averaged over the applied steps; the counters come from the control block with the loss, once per epoch
+    controlled = bool(getattr(optimizer, 'controlled', False))
+    applied_before = optimizer.step_stats()["applied_steps"] if controlled else 0
+    grad_norm = torch.zeros((), device=device)   # the last APPLIED step's norm
     for epoch in range(1, config['epoch_num'] + 1):
         model.train()
         loss_sum = torch.zeros((), device=device)  # accumulated on the device: one host sync per epoch, not per step
@@ -188,6 +194,11 @@ def train(config: Dict[str, Any], error_tracker):
             data, target, ib = data.to(device), target.to(device), ib.to(device)
             if fused:
                 loss = model.engine(device).train_step(data.float(), target.float(), ib.float(), optimizer, loss_weight=weight)
+                if controlled:
+                    applied = optimizer.last_applied != 0
+                    loss_sum += torch.where(applied, loss.reshape(()) * weight, torch.zeros_like(loss_sum))
+                    grad_norm = torch.where(applied, optimizer.last_grad_norm, grad_norm)
+                    continue
                 loss_sum += loss.reshape(()) * weight
                 continue
             optimizer.zero_grad()
@@ -195,11 +206,25 @@ def train(config: Dict[str, Any], error_tracker):
             loss = loss_fn(outputs, target)
             (loss * weight if weight != 1.0 else loss).backward()
             optimizer.step()
+            if controlled:
+                applied = optimizer.last_applied != 0
+                loss_sum += torch.where(applied, loss.detach() * weight, torch.zeros_like(loss_sum))
+                grad_norm = torch.where(applied, optimizer.last_grad_norm, grad_norm)
+                continue
             loss_sum += loss.detach() * weight
         if scheduler is not None:
             scheduler.step()
-        train_loss = _mean_over_ranks(loss_sum, world).item() / max(n_batches, 1)
-        error_tracker.record_error("train", epoch, {"Loss": train_loss})
+        if controlled:
+            # ONE copy to the host: the loss sum and the norm ride with the control words (as their bit patterns)
+            words = torch.cat([torch.stack([_mean_over_ranks(loss_sum, world), grad_norm]).view(torch.int32), optimizer.step_control_words()]).cpu()
+            loss_host, norm_host = (float(t) for t in words[:2].view(torch.float32))
+            applied_now, skipped, clipped = (int(words[2 + i]) for i in (N.CTL_STEP, N.CTL_SKIPPED, N.CTL_CLIPPED))
+            n_applied, applied_before = applied_now - applied_before, applied_now
+            train_loss = loss_host / n_applied if n_applied else float('nan')   # no step of the epoch was applied: there is no loss to report
+            error_tracker.record_error("train", epoch, {"Loss": train_loss, "GradNorm": norm_host, "SkippedSteps": skipped, "ClippedSteps": clipped})
+        else:
+            train_loss = _mean_over_ranks(loss_sum, world).item() / max(n_batches, 1)
+            error_tracker.record_error("train", epoch, {"Loss": train_loss})
         if epoch % config.get('validation_interval', 1) == 0 or epoch == config['epoch_num']:
             model.eval()
             val_sum, n_val = torch.zeros((), device=device), 0

@@ -92,10 +92,13 @@ class FieldSpaceLoss(torch.nn.Module):
 def initialize_optimizer(model, config):
     """AdamW(lr=config['learning_rate'], betas=(0.9, 0.999), eps=1e-8, weight_decay=config.get('weight_decay', 0.0)) as one fused
     kernel over the model's flat parameter buffer (reference :33-39).  Returns (optimizer, scheduler) when
-    config['scheduler'] == 'linear', like the reference."""
+    config['scheduler'] == 'linear', like the reference.  Two optional keys beyond the reference's: config['max_grad_norm'] (clip the gradients
+    by their global 2-norm) and config['skip_nonfinite_steps'] (drop a step whose gradient norm is inf or NaN), both decided on the device
+    (sea_amd/optim.py)."""
     from ..optim import FlatAdamW
 
-    opt = FlatAdamW(model, lr=config['learning_rate'], betas=(0.9, 0.999), eps=1e-8, weight_decay=config.get('weight_decay', 0.0))
+    opt = FlatAdamW(model, lr=config['learning_rate'], betas=(0.9, 0.999), eps=1e-8, weight_decay=config.get('weight_decay', 0.0),
+                    max_grad_norm=config.get('max_grad_norm'), skip_nonfinite=config.get('skip_nonfinite_steps', False))
     if config.get('scheduler', None) == 'linear':
         sched = torch.optim.lr_scheduler.LinearLR(opt, start_factor=0.1, end_factor=1.0, total_iters=config['epoch_num'])
         return opt, sched
