@@ -1014,6 +1014,58 @@ typedef struct {
     float inv_n, grad_scale;
 } SeaDecodeMse;
 int sea_decode_mse(const SeaDecodeMseGroup* groups, int n_groups, const SeaDecodeMse* p, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Ensemble weighting: the squared error of the DECODED fields of every ensemble member against an observation, per member and per field, in one
+ * launch for all field groups (plus a short finish launch) — the likelihood term of a particle filter over rollout sessions (RolloutSession.fork /
+ * resample).  Replaces the second decoder Linear into an [M, n_fields * Cp] fp32 output and the reductions over it; neither the decoded fields nor
+ * the residual ever exist in memory.  It takes the SeaDecodeMseGroup operands H, W2, bias, ldh, ldw, n_fields, field0 as sea_decode_mse does (dH, Z,
+ * lddh, ldz are not read and may be NULL / 0).  Row m belongs to member m / P and patch m % P; the `members` consecutive members of one history share
+ * one observation, so the target row of m is trow(m) = ((m / P) / members) * P + m % P:
+ *     Y[m, j, c]               = sum_s H[m, s] W2[j Cp + c, s] + bias[j Cp + c]        j < n_fields, c < C        (fp32 accumulation)
+ *     sse[m / P, field0 + j]  += valid(m, c) ? (Y[m, j, c] - target[trow(m), field0 + j, c])^2 : 0
+ * target element (r, f, c) is at target + r ld_row + f ld_field + c; only c < C is ever read.  valid(m, c) = c < C when counts == NULL, else
+ * c < counts[m % P] (device int32 [P]; a value outside [0, C] is clamped — a guard, not an interface).  An invalid slot is neutral whatever the target
+ * holds there, NaN included.  The residual stays in fp32 (no second product consumes it).  sse: f32 [M / P, n_fields_total], every element written
+ * (not accumulated into): the groups' field ranges [field0, field0 + n_fields) must cover 0 .. n_fields_total-1 exactly once.
+ * work: f32 workspace of work_cap >= M * n_fields_total floats, private to the call: the main kernel writes the per-row, per-field sums there (the four
+ * lanes that hold a row's columns folded first), the finish launch sums the P rows of each member.  No atomics; every element has one writer and a
+ * fixed summation order: two runs give the same bits, and the result does not depend on `members` beyond the target row it selects.
+ * Requirements: those of sea_decode_mse — dtype SEA_BF16 (SEA_F32 returns SEA_EUNSUPPORTED); M >= 1; S a multiple of 8, at most 640 (above:
+ * SEA_EUNSUPPORTED), padded by masking; Cp a multiple of 32, 1 <= C <= Cp; ld_row, ld_field multiples of 4, target 16-byte aligned; per group H, W2,
+ * bias non-NULL and 16-byte aligned, ldh, ldw multiples of 8 and >= S; 1 <= n_groups <= SEA_DECODE_MSE_MAX_GROUPS — and P >= 1, members >= 1,
+ * M % (P * members) == 0, work_cap >= M * n_fields_total.
+ * Returns -1, with the entry point and the offending group named in sea_last_error(), otherwise; nothing touches a device before the checks pass.
+ * (An addition to ABI version 8.  sea_struct_sizes() keeps its 33 entries, SeaKvFork last: sizeof(SeaDecodeMemberSse) is 88.)
+ */
+typedef struct {
+    const float* target;     /* f32, rows of the observation: [M / (P * members) * P, n_fields_total, >= C] through ld_row, ld_field */
+    const int32_t* counts;   /* device int32 [P] or NULL */
+    float* sse;              /* f32 [M / P, n_fields_total] (output) */
+    float* work;             /* f32 [work_cap] workspace */
+    int64_t ld_row, ld_field, work_cap;
+    int32_t M, S, C, Cp, P, members, n_fields_total, pad_;
+} SeaDecodeMemberSse;
+int sea_decode_member_sse(const SeaDecodeMseGroup* groups, int n_groups, const SeaDecodeMemberSse* p, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Systematic resampling of an ensemble, gated by the effective sample size, in one launch: log-weights in, the int32 device index that
+ * sea_kv_cache_gather (RolloutSession.resample / select) takes out.  G histories with n members each, one workgroup per history, all sums in fp64.
+ * Per history g (member j is element g n + j):
+ *     a member is DEAD when its log-weight is NaN, +inf or -inf: its weight is 0 and it is never selected;
+ *     mx = max over the live members;  w_j = exp(logw_j - mx);  W = sum_j w_j;  c_i = sum_{k <= i} w_k;  ess = W^2 / sum_j w_j^2
+ *     no live member:                       index = identity (g n + j), logw_out = 0, ess = 0, resampled = -1
+ *     ess_frac < 0 or ess < ess_frac * n:   index[g n + j] = g n + min{ i : c_i > (j + u_g) / n * W } (clamped to the last live member),
+ *                                           logw_out = 0, resampled = 1
+ *     otherwise:                            index = identity, logw_out_j = logw_j - mx - log W (dead members: -inf), resampled = 0
+ * Indices never leave their history; within one they are non-decreasing and member i appears floor(n p_i) or ceil(n p_i) times (p_i = w_i / W).
+ * logw f32 [G n]; u f32 [G], offsets in [0, 1); index int32 [G n]; logw_out f32 [G n]; ess f32 [G]; resampled int32 [G] — all on the device, all
+ * non-NULL.  The cumulative sum has a fixed order (fp64, in LDS): two runs give the same bits.  The decision is taken on the device: nothing is read
+ * back.  Requirements: G >= 1; 1 <= n <= 4096 (above: SEA_EUNSUPPORTED); G n < 2^31; ess_frac not NaN.  Returns -1 with the entry point named in
+ * sea_last_error() otherwise, before any device is touched.  (An addition to ABI version 8; no new struct.)
+ */
+int sea_resample_systematic(const float* logw, const float* u, float ess_frac, int G, int n, int32_t* index, float* logw_out, float* ess, int32_t* resampled,
+                            void* stream);
 /* Tuning aid: register a device buffer of n_steps * 64 8-byte words that the persistent form fills with 100 MHz clock stamps of its hand-offs
  * (tools/kv_persist_timeline.py); NULL switches it off. */
 void sea_kv_debug_stamps(unsigned long long* buf);

@@ -279,6 +279,14 @@ class SeaDecodeMse(C.Structure):
                 ("M", _i32), ("S", _i32), ("C", _i32), ("Cp", _i32), ("P", _i32), ("n_partial_cap", _i32), ("inv_n", _f32), ("grad_scale", _f32)]
 
 
+class SeaDecodeMemberSse(C.Structure):
+    # sea_decode_member_sse (not in ABI_STRUCTS either; tests/test_ensemble_cpu.py checks the layout through the library's argument checks)
+    _fields_ = [("target", _vp), ("counts", _vp), ("sse", _vp), ("work", _vp), ("ld_row", _i64), ("ld_field", _i64), ("work_cap", _i64),
+                ("M", _i32), ("S", _i32), ("C", _i32), ("Cp", _i32), ("P", _i32), ("members", _i32), ("n_fields_total", _i32), ("pad_", _i32)]
+
+
+RESAMPLE_MAX_N = 4096      # members per history of sea_resample_systematic
+
 MAX_WGRAD_GROUPS = 32
 MAX_NORM_BWD_GROUPS = 8
 MAX_SILU_BWD_GROUPS = 24
@@ -382,6 +390,10 @@ def lib() -> C.CDLL:
     L.sea_kv_cache_gather.restype = C.c_int
     L.sea_decode_mse.argtypes = [C.POINTER(SeaDecodeMseGroup), C.c_int, C.POINTER(SeaDecodeMse), C.c_int, _vp]
     L.sea_decode_mse.restype = C.c_int
+    L.sea_decode_member_sse.argtypes = [C.POINTER(SeaDecodeMseGroup), C.c_int, C.POINTER(SeaDecodeMemberSse), C.c_int, _vp]
+    L.sea_decode_member_sse.restype = C.c_int
+    L.sea_resample_systematic.argtypes = [_vp, _vp, C.c_float, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]
+    L.sea_resample_systematic.restype = C.c_int
     for name in ("sea_attention_bwd", "sea_wgrad_grouped", "sea_transpose_weights", "sea_rownorm_bwd", "sea_silu_outer_bwd", "sea_ib_bwd",
                  "sea_silu_outer_bwd_dc", "sea_ib_bwd_dc"):
         getattr(L, name).restype = C.c_int
@@ -413,7 +425,7 @@ EXPORTED_SYMBOLS = (
     "sea_mse_fwd_bwd", "sea_relative_mse", "sea_adamw_flat", "sea_grad_norm_ctl", "sea_adamw_flat_ctl",
     "sea_wgrad_grouped", "sea_transpose_weights", "sea_rownorm_bwd", "sea_silu_outer_bwd", "sea_ib_bwd",
     "sea_attention_bwd", "sea_dropout_mask", "sea_run_list", "sea_run_list_steps", "sea_unpatchify", "sea_gemm_rownorm", "sea_exchange_tail", "sea_patchify", "sea_silu_outer_ib", "sea_mlp_fc1_ln_gelu", "sea_mlp_fc2_proj_norm", "sea_kv_rollout", "sea_kv_arena_words", "sea_kv_debug_stamps",
-    "sea_kv_cache_fill", "sea_kv_cache_fork", "sea_kv_cache_gather", "sea_decode_mse",
+    "sea_kv_cache_fill", "sea_kv_cache_fork", "sea_kv_cache_gather", "sea_decode_mse", "sea_decode_member_sse", "sea_resample_systematic",
     "sea_gemm_fewrows", "sea_qkv_rope_fewrows", "sea_row_chain", "sea_row_chain_riders", "sea_gemm_adaln", "sea_mlp_block", "sea_adaln_qkv", "sea_splitk_finish",
     "sea_encoder_block_ws_floats", "sea_encoder_block_fwd", "sea_encoder_block_bwd",
     "sea_silu_outer_bwd_dc", "sea_silu_outer_bwd_dc_ws_floats", "sea_ib_bwd_dc",

@@ -51,23 +51,24 @@ template <int SP>
 constexpr int dm_lds_bytes() { return 2 * DM_TC * (SP * 2 + DM_PAD) + 16; }
 
 // Tile t of a group (32 rows of W2: output columns [cb, cb + 32) of field j) into the thread's SP / 64 staging registers, chunks at s >= S zeroed; and on into an LDS image.
-template <int SP>
-__device__ __forceinline__ void dm_load_tile(uint4 (&wr)[SP / 64], const __bf16* W2, int ldw, int S, int Cp, int tpf, int t, int tid) {
+// (NT: threads of the workgroup; a thread carries DM_TC * (SP / 8) / NT chunks.)
+template <int SP, int NT = 256>
+__device__ __forceinline__ void dm_load_tile(uint4 (&wr)[SP * 4 / NT], const __bf16* W2, int ldw, int S, int Cp, int tpf, int t, int tid) {
     constexpr int CPR = SP / 8;
     const int j = t / tpf, cb = (t - j * tpf) * DM_TC;
     const __bf16* src = W2 + (int64_t)(j * Cp + cb) * ldw;
 #pragma unroll
-    for (int u = 0; u < SP / 64; ++u) {
-        const int q = u * 256 + tid, r = q / CPR, ch = q - r * CPR;
+    for (int u = 0; u < SP * 4 / NT; ++u) {
+        const int q = u * NT + tid, r = q / CPR, ch = q - r * CPR;
         wr[u] = ch * 8 < S ? *reinterpret_cast<const uint4*>(src + (int64_t)r * ldw + ch * 8) : make_uint4(0u, 0u, 0u, 0u);
     }
 }
-template <int SP>
-__device__ __forceinline__ void dm_store_tile(const uint4 (&wr)[SP / 64], char* buf, int tid) {
+template <int SP, int NT = 256>
+__device__ __forceinline__ void dm_store_tile(const uint4 (&wr)[SP * 4 / NT], char* buf, int tid) {
     constexpr int CPR = SP / 8, PITCH = SP * 2 + DM_PAD;
 #pragma unroll
-    for (int u = 0; u < SP / 64; ++u) {
-        const int q = u * 256 + tid, r = q / CPR, ch = q - r * CPR;
+    for (int u = 0; u < SP * 4 / NT; ++u) {
+        const int q = u * NT + tid, r = q / CPR, ch = q - r * CPR;
         *reinterpret_cast<uint4*>(buf + r * PITCH + ch * 16) = wr[u];
     }
 }
@@ -294,5 +295,237 @@ extern "C" int sea_decode_mse(const SeaDecodeMseGroup* groups, int n_groups, con
     else decode_mse_launch<640>(L, grid, s);
     decode_mse_finish_kernel<<<dim3(1), dim3(256), 0, s>>>(P.partial, (int)(row_blocks * n_groups), P.loss, P.inv_n);
     SEA_CHECK_LAUNCH("sea_decode_mse");
+    return SEA_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------------------------
+// sea_decode_member_sse: the per-member, per-field squared error of the decoded fields against an observation (ensemble weighting).  Stage 1 of
+// decode_mse_kernel — the same W2 tiles through the same two LDS images, the same H fragments in registers — with another epilogue and no stage 2:
+// the residual is squared in fp32 where it is produced and summed per ROW and FIELD.  A lane holds one row (m = row0 + lane & 15) and 8 of a tile's 32
+// columns; it adds its squares over the tiles of a field in a fixed order, the four lanes that share the row (lane >> 4) are folded by two butterfly
+// steps, and the lane group 0 writes work[m, field0 + j]: one writer per element.  A row tile may straddle members (P is arbitrary), so the P rows of a
+// member are summed by member_sse_finish_kernel — one wave per output element, lanes over the patches, a fixed butterfly — and not in the main kernel.
+// Without the dH accumulators a wave needs SP / 8 fragment registers and little else, so a workgroup is NW waves = 16 NW rows with NW in {4, 8}: at
+// NW = 8 every W2 tile is fetched from L2 and written to LDS half as often per row and two waves share a SIMD (at SP = 640 the two LDS images are
+// 84 kB: one workgroup per CU either way).  The entry point picks NW (measured: 128 rows above S = 512, 64 below; SEA_TUNE sse_rows=64|128 forces one; both give the same bits).
+struct MemberSseLaunch {
+    SeaDecodeMseGroup g[SEA_DECODE_MSE_MAX_GROUPS];
+    SeaDecodeMemberSse p;
+};
+
+template <int SP, int NW>
+__global__ __launch_bounds__(64 * NW) void decode_member_sse_kernel(const MemberSseLaunch L) {
+    constexpr int NT = 64 * NW;
+    constexpr int KS = SP / 32;
+    constexpr int PITCH = SP * 2 + DM_PAD;
+    constexpr int TILE = DM_TC * PITCH;
+    constexpr int NCH = SP * 4 / NT;
+    static_assert(NCH * NT == DM_TC * (SP / 8), "whole chunks per thread");
+    extern __shared__ __attribute__((aligned(16))) char smem[];   // 2 tile images
+
+    const SeaDecodeMseGroup& G = L.g[blockIdx.y];
+    const SeaDecodeMemberSse& P = L.p;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, lg = lane >> 4;
+    const int M = P.M, S = P.S, C = P.C, Cp = P.Cp;
+    const int row0 = blockIdx.x * (16 * NW) + wave * 16;
+    const int m = row0 + li;
+    const __bf16* H = static_cast<const __bf16*>(G.H);
+    const __bf16* W2 = static_cast<const __bf16*>(G.W2);
+    const uint4 zero4 = make_uint4(0u, 0u, 0u, 0u);
+
+    // valid columns of this lane's row: [0, lim); its row of the observation: the `members` consecutive members of a history share one
+    int lim = 0;
+    int64_t tr = 0;
+    if (m < M) {
+        const int mem = m / P.P, patch = m - mem * P.P;
+        lim = C;
+        if (P.counts != nullptr) {
+            const int cnt = P.counts[patch];
+            lim = cnt < 0 ? 0 : (cnt > C ? C : cnt);
+        }
+        tr = (int64_t)(mem / P.members) * P.P + patch;
+    }
+
+    uint4 hf[KS];
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+        const int s = ks * 32 + 8 * lg;
+        hf[ks] = (m < M && s < S) ? *reinterpret_cast<const uint4*>(H + (int64_t)m * G.ldh + s) : zero4;
+    }
+
+    const int tpf = (C + DM_TC - 1) / DM_TC;
+    const int n_tiles = G.n_fields * tpf;
+    uint4 wr[NCH];
+    dm_load_tile<SP, NT>(wr, W2, G.ldw, S, Cp, tpf, 0, tid);
+    dm_store_tile<SP, NT>(wr, smem, tid);
+    __syncthreads();
+
+    float fsum = 0.f;
+    const float* trow = P.target + tr * P.ld_row;
+    float* wrow = P.work + (int64_t)(m < M ? m : 0) * P.n_fields_total + G.field0;
+    int j = 0, tj = 0;   // field of tile t and the tile's index inside it
+    for (int t = 0; t < n_tiles; ++t) {
+        const char* buf = smem + (t & 1) * TILE;
+        if (t + 1 < n_tiles) dm_load_tile<SP, NT>(wr, W2, G.ldw, S, Cp, tpf, t + 1, tid);
+        const int cb = tj * DM_TC;
+
+        float tg[2][4];
+        const float* tf = trow + (int64_t)(G.field0 + j) * P.ld_field;
+#pragma unroll
+        for (int sub = 0; sub < 2; ++sub) {
+            const int c = cb + sub * 16 + 4 * lg;
+            tg[sub][0] = tg[sub][1] = tg[sub][2] = tg[sub][3] = 0.f;
+            if (c < lim) {
+                if (c + 4 <= C) {
+                    const float4 v = *reinterpret_cast<const float4*>(tf + c);
+                    tg[sub][0] = v.x; tg[sub][1] = v.y; tg[sub][2] = v.z; tg[sub][3] = v.w;
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        if (c + r < C) tg[sub][r] = tf[c + r];
+                }
+            }
+        }
+
+        f32x4 acc[2][2];
+#pragma unroll
+        for (int sub = 0; sub < 2; ++sub) {
+            const float4 b = *reinterpret_cast<const float4*>(G.bias + j * Cp + cb + sub * 16 + 4 * lg);
+            acc[sub][0] = f32x4{b.x, b.y, b.z, b.w};
+            acc[sub][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+            if (ks * 32 < S) {
+#pragma unroll
+                for (int sub = 0; sub < 2; ++sub) {
+                    const uint4 a = *reinterpret_cast<const uint4*>(buf + (sub * 16 + li) * PITCH + (ks * 4 + lg) * 16);
+                    mma16<__bf16>(a, hf[ks], acc[sub][ks & 1]);
+                }
+            }
+        }
+
+        // residual: masked (a select: NaN in an invalid slot is neutral), squared in fp32, never rounded
+#pragma unroll
+        for (int sub = 0; sub < 2; ++sub) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int c = cb + sub * 16 + 4 * lg + r;
+                const float y = acc[sub][0][r] + acc[sub][1][r];
+                const float d = c < lim ? y - tg[sub][r] : 0.f;
+                fsum = fma1(d, d, fsum);
+            }
+        }
+        if (++tj == tpf) {   // the field is complete (uniform over the workgroup): fold the row's four lanes, one writer
+            float v = fsum;
+            v += __shfl_xor(v, 16);
+            v += __shfl_xor(v, 32);
+            if (lg == 0 && m < M) wrow[j] = v;
+            fsum = 0.f;
+            tj = 0;
+            ++j;
+        }
+
+        if (t + 1 < n_tiles) dm_store_tile<SP, NT>(wr, smem + ((t + 1) & 1) * TILE, tid);
+        __syncthreads();
+    }
+}
+
+// sse[member, f] = sum over the member's P rows of work[row, f]: one wave per output element, lane l adds the rows l, l + 64, .. in order, then a fixed butterfly
+__global__ __launch_bounds__(256) void member_sse_finish_kernel(const float* __restrict__ work, float* __restrict__ sse, int64_t n_out, int P, int nft) {
+    const int lane = threadIdx.x & 63;
+    const int64_t o = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (o >= n_out) return;   // whole waves leave: no barrier follows
+    const int64_t mem = o / nft;
+    const int f = (int)(o - mem * nft);
+    const float* src = work + mem * P * nft + f;
+    float acc = 0.f;
+    for (int p = lane; p < P; p += 64) acc += src[(int64_t)p * nft];
+    acc = wave_sum(acc);
+    if (lane == 0) sse[o] = acc;
+}
+
+template <int SP, int NW>
+static void member_sse_launch(const MemberSseLaunch& L, int64_t M, int n_groups, hipStream_t s) {
+    constexpr int lds = 2 * DM_TC * (SP * 2 + DM_PAD);
+    static bool set_on[64] = {false};   // per device: SP = 640 needs 84 kB, above the 64 kB a kernel gets without the attribute
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = -1;
+    if (dev < 0 || !set_on[dev]) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(decode_member_sse_kernel<SP, NW>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        if (dev >= 0) set_on[dev] = true;
+    }
+    const dim3 grid((unsigned)((M + 16 * NW - 1) / (16 * NW)), (unsigned)n_groups);
+    decode_member_sse_kernel<SP, NW><<<grid, dim3(64 * NW), lds, s>>>(L);
+}
+
+template <int NW>
+static void member_sse_dispatch(const MemberSseLaunch& L, int n_groups, hipStream_t s) {
+    const int S = L.p.S;
+    const int64_t M = L.p.M;
+    if (S <= 128) member_sse_launch<128, NW>(L, M, n_groups, s);
+    else if (S <= 256) member_sse_launch<256, NW>(L, M, n_groups, s);
+    else if (S <= 384) member_sse_launch<384, NW>(L, M, n_groups, s);
+    else if (S <= 512) member_sse_launch<512, NW>(L, M, n_groups, s);
+    else member_sse_launch<640, NW>(L, M, n_groups, s);
+}
+
+extern "C" int sea_decode_member_sse(const SeaDecodeMseGroup* groups, int n_groups, const SeaDecodeMemberSse* p, int dtype, void* stream) {
+    SEA_REQUIRE(groups != nullptr && p != nullptr, "sea_decode_member_sse: null argument table");
+    SEA_REQUIRE(n_groups >= 1 && n_groups <= SEA_DECODE_MSE_MAX_GROUPS, "sea_decode_member_sse: n_groups=%d outside 1..%d", n_groups, SEA_DECODE_MSE_MAX_GROUPS);
+    SEA_REQUIRE(dtype == SEA_F32 || dtype == SEA_BF16, "sea_decode_member_sse: bad dtype %d", dtype);
+    if (dtype != SEA_BF16) {
+        sea_set_error("sea_decode_member_sse: unsupported: bf16 only (the fp32 decoder composes sea_gemm_grouped and reductions)");
+        return SEA_EUNSUPPORTED;
+    }
+    const SeaDecodeMemberSse& P = *p;
+    SEA_REQUIRE(P.target != nullptr && P.sse != nullptr && P.work != nullptr, "sea_decode_member_sse: null target, sse or work pointer");
+    SEA_REQUIRE(P.M >= 1, "sea_decode_member_sse: M=%d must be positive", P.M);
+    SEA_REQUIRE(P.S >= 8 && P.S % 8 == 0, "sea_decode_member_sse: S=%d must be a positive multiple of 8", P.S);
+    SEA_REQUIRE(P.Cp >= 32 && P.Cp % 32 == 0, "sea_decode_member_sse: Cp=%d must be a positive multiple of 32", P.Cp);
+    SEA_REQUIRE(P.C >= 1 && P.C <= P.Cp, "sea_decode_member_sse: C=%d must lie in 1..Cp=%d", P.C, P.Cp);
+    SEA_REQUIRE(P.P >= 1 && P.members >= 1, "sea_decode_member_sse: P=%d and members=%d must be positive", P.P, P.members);
+    SEA_REQUIRE((int64_t)P.M % ((int64_t)P.P * P.members) == 0, "sea_decode_member_sse: M=%d is not a multiple of P * members = %d * %d", P.M, P.P, P.members);
+    SEA_REQUIRE(P.n_fields_total >= 1, "sea_decode_member_sse: n_fields_total=%d must be positive", P.n_fields_total);
+    SEA_REQUIRE(P.work_cap >= (int64_t)P.M * P.n_fields_total, "sea_decode_member_sse: workspace of %lld floats is too small: %lld needed (M * n_fields_total)",
+                (long long)P.work_cap, (long long)((int64_t)P.M * P.n_fields_total));
+    SEA_REQUIRE(P.ld_row >= 0 && P.ld_row % 4 == 0 && P.ld_field >= 0 && P.ld_field % 4 == 0,
+                "sea_decode_member_sse: target strides ld_row=%lld, ld_field=%lld must be multiples of 4", (long long)P.ld_row, (long long)P.ld_field);
+    SEA_REQUIRE(sea_aligned16(P.target) && sea_aligned4(P.counts) && sea_aligned4(P.sse) && sea_aligned4(P.work), "sea_decode_member_sse: misaligned target, counts, sse or work pointer");
+    int64_t covered = 0;
+    for (int g = 0; g < n_groups; ++g) {
+        const SeaDecodeMseGroup& G = groups[g];
+        SEA_REQUIRE(G.H != nullptr && G.W2 != nullptr && G.bias != nullptr, "sea_decode_member_sse: group %d: null pointer", g);
+        SEA_REQUIRE(sea_aligned16(G.H) && sea_aligned16(G.W2) && sea_aligned16(G.bias), "sea_decode_member_sse: group %d: pointers must be 16-byte aligned", g);
+        SEA_REQUIRE(G.ldh >= P.S && G.ldh % 8 == 0 && G.ldw >= P.S && G.ldw % 8 == 0,
+                    "sea_decode_member_sse: group %d: row strides ldh=%d ldw=%d must cover S=%d and be multiples of 8", g, G.ldh, G.ldw, P.S);
+        SEA_REQUIRE(G.n_fields >= 1 && G.field0 >= 0 && (int64_t)G.field0 + G.n_fields <= P.n_fields_total,
+                    "sea_decode_member_sse: group %d: n_fields=%d, field0=%d outside the %d fields", g, G.n_fields, G.field0, P.n_fields_total);
+        SEA_REQUIRE((int64_t)G.n_fields * P.Cp <= 0x7fffffffLL / 2, "sea_decode_member_sse: group %d: too many output columns", g);
+        for (int h = 0; h < g; ++h)
+            SEA_REQUIRE(G.field0 >= groups[h].field0 + groups[h].n_fields || groups[h].field0 >= G.field0 + G.n_fields,
+                        "sea_decode_member_sse: group %d: its fields overlap those of group %d (every output element has one writer)", g, h);
+        covered += G.n_fields;
+    }
+    SEA_REQUIRE(covered == P.n_fields_total, "sea_decode_member_sse: the groups cover %lld of the %d fields (every field needs exactly one group)", (long long)covered, P.n_fields_total);
+    if (P.S > 640) {
+        sea_set_error("sea_decode_member_sse: unsupported: hidden width S=%d above 640", P.S);
+        return SEA_EUNSUPPORTED;
+    }
+    const int64_t n_out = (int64_t)(P.M / P.P) * P.n_fields_total;
+    SEA_REQUIRE(((int64_t)P.M + 63) / 64 <= 0x7fffffffLL && (n_out + 3) / 4 <= 0x7fffffffLL, "sea_decode_member_sse: too many rows");
+
+    MemberSseLaunch L;
+    memset(&L, 0, sizeof(L));
+    for (int g = 0; g < n_groups; ++g) L.g[g] = groups[g];
+    L.p = P;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // measured (tools/ensemble_bench.py): at SP = 640 the two LDS images leave one workgroup per CU and 128 rows are 1.4x faster;
+    // up to SP = 512 two workgroups fit and 64 rows are 3 - 9 % faster.  Read per call: the tool measures both forms in one process.
+    const int rows = sea_tune("sse_rows", P.S > 512 ? 128 : 64);
+    if (rows == 64) member_sse_dispatch<4>(L, n_groups, s);
+    else member_sse_dispatch<8>(L, n_groups, s);
+    member_sse_finish_kernel<<<dim3((unsigned)((n_out + 3) / 4)), dim3(256), 0, s>>>(P.work, P.sse, n_out, P.P, P.n_fields_total);
+    SEA_CHECK_LAUNCH("sea_decode_member_sse");
     return SEA_OK;
 }

@@ -152,22 +152,25 @@ class Decode(nn.Module):
         ops.gemm_grouped([dict(A=dpre[g], W=W1T[g], C32=dz[:, g * D:(g + 1) * D]) for g in range(self.num_groups)], dt)
         return dz
 
-    def _valid_counts(self, counts, P: int, device: torch.device):
-        """(device int32 [P] or None, valid cells summed over the patches) for mse_loss; checked on the host, cached per counts object."""
+    def _valid_counts(self, counts, P: int, device: torch.device, allow_empty: bool = False, what: str = "mse_loss"):
+        """(device int32 [P] or None, valid cells summed over the patches) for mse_loss and member_sse; checked on the host, cached per counts object.
+        allow_empty: counts that leave no valid element are accepted (a sum of squares over nothing is 0; a mean is undefined); what: the caller named in the messages."""
         if counts is None:
             return None, P * self.n_inp
         key = (id(counts), getattr(counts, "_version", None), P, device)
         cur = getattr(self, "_counts_cache", None)
         if cur is not None and cur[0] == key:
+            if cur[2] < 1 and not allow_empty:
+                raise ValueError(f"sea_amd.Decode.{what}: counts leave no valid element")
             return cur[1], cur[2]
         host = counts.detach().cpu() if torch.is_tensor(counts) else torch.as_tensor(list(counts))
         if host.dim() != 1 or host.shape[0] != P or host.is_floating_point() or host.is_complex() or host.dtype == torch.bool:
-            raise ValueError(f"sea_amd.Decode.mse_loss: counts must be {P} integers (one per patch), got shape {tuple(host.shape)} {host.dtype}")
+            raise ValueError(f"sea_amd.Decode.{what}: counts must be {P} integers (one per patch), got shape {tuple(host.shape)} {host.dtype}")
         if int(host.min()) < 0 or int(host.max()) > self.n_inp:
-            raise ValueError(f"sea_amd.Decode.mse_loss: counts must lie in [0, n_inp = {self.n_inp}], got {int(host.min())} .. {int(host.max())}")
+            raise ValueError(f"sea_amd.Decode.{what}: counts must lie in [0, n_inp = {self.n_inp}], got {int(host.min())} .. {int(host.max())}")
         total = int(host.sum())
-        if total < 1:
-            raise ValueError("sea_amd.Decode.mse_loss: counts leave no valid element")
+        if total < 1 and not allow_empty:
+            raise ValueError(f"sea_amd.Decode.{what}: counts leave no valid element")
         dev = host.to(device=device, dtype=torch.int32).contiguous()
         self._counts_cache = (key, dev, total, counts)   # the object is kept so that its id is not reused
         return dev, total
@@ -213,6 +216,62 @@ class Decode(nn.Module):
         valid = (torch.arange(C, device=z.device) < cnt[:, None]).view(1, P, 1, C)
         d = torch.where(valid, y - t, torch.zeros((), device=z.device))
         return (d * d).sum() / n_valid
+
+    def member_sse(self, z: torch.Tensor, target: torch.Tensor, counts=None, members: int = 1, fused: Optional[bool] = None) -> torch.Tensor:
+        """Squared error of the decoded fields of every ensemble member against an observation, summed over a member's patches and valid cells:
+        fp32 [Bm, n_fields], no autograd graph.  z [Bm, P, n_groups, embed_dim] holds `members` consecutive members per history (row b * members + j is
+        member j of history b, as RolloutSession.fork orders them); target float32 [Bm / members, P, n_fields, C >= n_inp] is one observation per
+        history; counts as in mse_loss (counts that leave no valid element are accepted here: every score is then 0).  bf16 compute dtype: the
+        first-layer launch plus ONE fused launch (sea_decode_member_sse) — the decoded fields are never written; fp32, or fused=False: forward() plus
+        torch reductions over its output (the composed path).  `fused` forces either path; None: fused in bf16 from 8192 rows (Bm * P) on, composed
+        below — measured (tools/ensemble_bench.py, DESIGN.md section 7d, 64 members x 64 patches): at 4096 rows the composed path is the faster one
+        (0.14 - 0.19 ms against 0.18 - 0.23 ms: the fused path's time there is its launches, not its kernel), except with the mesh's counts at the
+        cylinder decoder, where the fused path is ahead by 2 % (0.180 against 0.184 ms) — too little to make the rule depend on counts; at 16384 rows
+        the fused path is 2.1 - 3.1x faster; fused=True selects the leaner path (8 - 10 MB of extra memory against 229 MB at 4096 rows) at any size."""
+        n_fields = sum(len(g) for g in self.field_groups)
+        C = self.n_inp
+        if z.dim() != 4 or z.shape[2] != self.num_groups or z.shape[3] != self.embed_dim:
+            raise ValueError(f"sea_amd.Decode.member_sse: z must be [Bm, P, {self.num_groups}, {self.embed_dim}], got {tuple(z.shape)}")
+        Bm, P = z.shape[0], z.shape[1]
+        if not isinstance(members, int) or isinstance(members, bool) or members < 1 or Bm < 1 or Bm % members:
+            raise ValueError(f"sea_amd.Decode.member_sse: members = {members!r} must be a positive integer that divides the {Bm} rows of z")
+        B = Bm // members
+        if target.dim() != 4 or tuple(target.shape[:3]) != (B, P, n_fields) or target.shape[3] < C:
+            raise ValueError(f"sea_amd.Decode.member_sse: target must be [{B}, {P}, {n_fields}, >= {C}] (one observation per history of {members} members), "
+                             f"got {tuple(target.shape)}")
+        if target.dtype != torch.float32 or target.device != z.device:
+            raise ValueError(f"sea_amd.Decode.member_sse: target must be float32 on {z.device}, got {target.dtype} on {target.device}")
+        dt = self._act_dtype()
+        if fused is None:
+            fused = dt == torch.bfloat16 and Bm * P >= 8192
+        if fused and dt != torch.bfloat16:
+            raise ValueError("sea_amd.Decode.member_sse: the fused launch is bf16 only (set_compute_dtype('bf16'), or fused=False)")
+        cnt, _ = self._valid_counts(counts, P, z.device, allow_empty=True, what="member_sse")
+        N.require_gpu(z, "Decode.member_sse input")
+        with torch.no_grad():
+            if not fused:
+                y = self.forward(z.detach()).view(B, members, P, n_fields, C)
+                d = y - target.detach()[..., :C].unsqueeze(1)
+                if cnt is not None:
+                    valid = (torch.arange(C, device=z.device) < cnt[:, None]).view(1, 1, P, 1, C)
+                    d = torch.where(valid, d, torch.zeros((), device=z.device))
+                return (d * d).sum(dim=(2, 4)).view(Bm, n_fields)
+            M = Bm * P
+            t3 = target.detach().reshape(B * P, n_fields, target.shape[3])
+            if t3.stride(2) != 1 or t3.stride(0) % 4 or t3.stride(1) % 4 or t3.data_ptr() % 16:
+                # a contiguous observation of an odd cell width, or the reference's [.., C, n_fields] layout seen through a permute: one row-aligned copy
+                src = t3[..., :C]
+                t3 = torch.zeros(B * P, n_fields, (C + 3) // 4 * 4, device=src.device, dtype=torch.float32)
+                t3[..., :C] = src
+            G, D = self.num_groups, self.embed_dim
+            zf = z.detach().to(torch.float32).contiguous().view(M, G * D)
+            za = torch.empty(M, G * D, device=z.device, dtype=dt)
+            ops.convert(zf, za)
+            W1, W2 = self._weights(dt)
+            hid = [torch.empty(M, self.MLP_hidden, device=z.device, dtype=dt) for _ in range(G)]
+            ops.gemm_grouped([dict(A=za[:, g * D:(g + 1) * D], W=W1[g], Cact=hid[g], act=1) for g in range(G)], dt)
+            bias = self._shadow[3]
+            return ops.decode_member_sse([dict(H=hid[g], W2=W2[g], bias=bias[g]) for g in range(G)], t3, C, self._n_inp_p, P, members=members, counts=cnt, dtype=dt)
 
     def forward_prefix(self, z: torch.Tensor, buckets) -> torch.Tensor:
         """The decoder for a consumer that only reads the first cells of a patch (MeshUnpatcher.decode_and_unpatch: a patch holds as many mesh points as its

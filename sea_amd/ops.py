@@ -979,3 +979,100 @@ def decode_mse(groups: Sequence[Dict], target: torch.Tensor, C_: int, Cp: int, i
     fill_decode_mse(arr, P, groups, target, counts, n_patches, C_, Cp, float(inv_n), float(grad_scale), loss, partial)
     N.check(N.lib().sea_decode_mse(arr, len(groups), C.byref(P), N.dtype_code(dtype), N.stream_ptr()), "sea_decode_mse")
     return loss
+
+
+def fill_decode_member_sse(groups_arr, P: N.SeaDecodeMemberSse, groups: Sequence[Dict], target, counts, n_patches: int, members: int, C_: int, Cp: int,
+                           sse, work) -> None:
+    """The argument table of sea_decode_member_sse.  groups: dicts H act [M, S], W2 act [n_fields * Cp, S], bias f32 [n_fields * Cp] (no dH, no Z); group
+    g's fields follow those of the groups before it.  target: f32 [M / members, n_fields_total, >= C] with unit inner stride."""
+    field0 = 0
+    for g, d in zip(groups_arr, groups):
+        H, W2 = d["H"], d["W2"]
+        g.H, g.W2, g.bias, g.dH, g.Z = H.data_ptr(), W2.data_ptr(), d["bias"].data_ptr(), None, None
+        g.ldh, g.ldw, g.lddh, g.ldz = H.stride(0), W2.stride(0), 0, 0
+        g.n_fields, g.field0 = W2.shape[0] // Cp, field0
+        field0 += g.n_fields
+    P.target, P.counts, P.sse, P.work = target.data_ptr(), N.ptr(counts), sse.data_ptr(), work.data_ptr()
+    P.ld_row, P.ld_field, P.work_cap = target.stride(0), target.stride(1), work.numel()
+    P.M, P.S, P.C, P.Cp, P.P = groups[0]["H"].shape[0], groups[0]["H"].shape[1], C_, Cp, n_patches
+    P.members, P.n_fields_total = members, field0
+
+
+def decode_member_sse(groups: Sequence[Dict], target: torch.Tensor, C_: int, Cp: int, n_patches: int, members: int = 1, counts: Optional[torch.Tensor] = None,
+                      dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
+    """sea_decode_member_sse: the squared error of the decoder's second layer against `target` per member and field, f32 [M / n_patches, n_fields_total].
+    groups as fill_decode_member_sse; row m is patch m % n_patches of member m // n_patches, and the `members` consecutive members of one history read
+    the same target rows: target f32 [M / members, n_fields_total, Cw >= C_] (row and field strides multiples of 4, unit inner stride, 16-byte-aligned
+    base); counts: device int32 [n_patches] or None.  Everything is checked on the host before the launch."""
+    if dtype != torch.bfloat16:
+        raise ValueError(f"decode_member_sse: the fused launch is bf16 only, got {dtype}")
+    if not groups or len(groups) > N.DECODE_MSE_MAX_GROUPS:
+        raise ValueError(f"decode_member_sse: {len(groups)} groups; a launch carries 1 .. {N.DECODE_MSE_MAX_GROUPS}")
+    if Cp < 32 or Cp % 32 or not 1 <= C_ <= Cp:
+        raise ValueError(f"decode_member_sse: need Cp a multiple of 32 and 1 <= C <= Cp, got C = {C_}, Cp = {Cp}")
+    dev = target.device
+    M, S = tuple(groups[0]["H"].shape) if groups[0]["H"].dim() == 2 else (0, 0)
+    if M < 1 or S < 8 or S % 8 or S > N.DECODE_MSE_MAX_S:
+        raise ValueError(f"decode_member_sse: H must be [M >= 1, S] with S a multiple of 8 up to {N.DECODE_MSE_MAX_S}, got {tuple(groups[0]['H'].shape)}")
+    if n_patches < 1 or members < 1:
+        raise ValueError(f"decode_member_sse: n_patches = {n_patches} and members = {members} must be positive")
+    if M % (n_patches * members):
+        raise ValueError(f"decode_member_sse: {M} rows are not a multiple of n_patches * members = {n_patches} * {members}")
+    n_fields = 0
+    for i, d in enumerate(groups):
+        for name in ("H", "W2"):
+            t = d[name]
+            if t.dim() != 2 or t.stride(1) != 1:
+                raise ValueError(f"decode_member_sse group {i}: {name}: need a 2-D tensor with unit inner stride, got shape {tuple(t.shape)} strides {t.stride()}")
+            if t.dtype != dtype or t.device != dev or t.shape[1] != S or (name != "W2" and t.shape[0] != M):
+                raise ValueError(f"decode_member_sse group {i}: {name} must be a {dtype} [{'n_fields * Cp' if name == 'W2' else M}, {S}] tensor on {dev}, got "
+                                 f"{tuple(t.shape)} {t.dtype} on {t.device}")
+            if t.stride(0) % 8 or t.data_ptr() % 16:
+                raise ValueError(f"decode_member_sse group {i}: {name} needs a row stride that is a multiple of 8 and a 16-byte-aligned base (stride {t.stride(0)})")
+        W2, b = d["W2"], d["bias"]
+        if W2.shape[0] < Cp or W2.shape[0] % Cp:
+            raise ValueError(f"decode_member_sse group {i}: W2 has {W2.shape[0]} rows, not a multiple of Cp = {Cp}")
+        if b.dtype != torch.float32 or b.dim() != 1 or b.shape[0] != W2.shape[0] or not b.is_contiguous() or b.device != dev or b.data_ptr() % 16:
+            raise ValueError(f"decode_member_sse group {i}: bias must be a contiguous, 16-byte-aligned float32 [{W2.shape[0]}] on {dev}, got {tuple(b.shape)} {b.dtype}")
+        n_fields += W2.shape[0] // Cp
+    rows = M // members
+    if target.dtype != torch.float32 or target.dim() != 3 or target.shape[0] != rows or target.shape[1] != n_fields or target.shape[2] < C_:
+        raise ValueError(f"decode_member_sse: target must be float32 [{rows}, {n_fields}, >= {C_}], got {tuple(target.shape)} {target.dtype}")
+    if target.stride(2) != 1 or target.stride(0) % 4 or target.stride(1) % 4 or target.data_ptr() % 16:
+        raise ValueError(f"decode_member_sse: target needs unit inner stride, row and field strides that are multiples of 4 and a 16-byte-aligned base, got "
+                         f"strides {target.stride()} (pad the cell width to a multiple of 4: patchify_and_scale(..., c_out=))")
+    if counts is not None and (counts.dtype != torch.int32 or counts.dim() != 1 or counts.shape[0] != n_patches or not counts.is_contiguous() or counts.device != dev):
+        raise ValueError(f"decode_member_sse: counts must be a contiguous int32 [{n_patches}] on {dev}, got {tuple(counts.shape)} {counts.dtype} on {counts.device}")
+    N.require_gpu(target, "decode_member_sse target")   # every operand is on the target's device (checked above)
+    sse = torch.empty(M // n_patches, n_fields, device=dev, dtype=torch.float32)
+    work = torch.empty(M * n_fields, device=dev, dtype=torch.float32)
+    arr, P = (N.SeaDecodeMseGroup * len(groups))(), N.SeaDecodeMemberSse()
+    fill_decode_member_sse(arr, P, groups, target, counts, n_patches, members, C_, Cp, sse, work)
+    N.check(N.lib().sea_decode_member_sse(arr, len(groups), C.byref(P), N.dtype_code(dtype), N.stream_ptr()), "sea_decode_member_sse")
+    return sse
+
+
+def resample_systematic(logw: torch.Tensor, u: torch.Tensor, members: int, ess_frac: float = -1.0):
+    """sea_resample_systematic: logw f32 [G * members] (device, contiguous), u f32 [G] in [0, 1), ess_frac < 0: always resample, else only the histories
+    whose effective sample size is below ess_frac * members.  Returns (index int32 [G * members], logw_out f32 [G * members], ess f32 [G], resampled
+    int32 [G]) on the device; nothing is read back."""
+    n = int(members)
+    if n < 1 or n > N.RESAMPLE_MAX_N:
+        raise ValueError(f"resample_systematic: members = {members} outside 1 .. {N.RESAMPLE_MAX_N}")
+    if logw.dim() != 1 or logw.dtype != torch.float32 or not logw.is_contiguous() or logw.numel() < 1 or logw.numel() % n:
+        raise ValueError(f"resample_systematic: logw must be a contiguous float32 [G * {n}] tensor, got {tuple(logw.shape)} {logw.dtype}")
+    G = logw.numel() // n
+    if u.dim() != 1 or u.dtype != torch.float32 or u.shape[0] != G or not u.is_contiguous() or u.device != logw.device:
+        raise ValueError(f"resample_systematic: u must be a contiguous float32 [{G}] tensor on {logw.device}, got {tuple(u.shape)} {u.dtype} on {u.device}")
+    ess_frac = float(ess_frac)
+    if ess_frac != ess_frac:
+        raise ValueError("resample_systematic: ess_frac is NaN")
+    N.require_gpu(logw, "resample_systematic log-weights")
+    dev = logw.device
+    index = torch.empty(G * n, device=dev, dtype=torch.int32)
+    logw_out = torch.empty(G * n, device=dev, dtype=torch.float32)
+    ess = torch.empty(G, device=dev, dtype=torch.float32)
+    resampled = torch.empty(G, device=dev, dtype=torch.int32)
+    N.check(N.lib().sea_resample_systematic(logw.data_ptr(), u.data_ptr(), ess_frac, G, n, index.data_ptr(), logw_out.data_ptr(), ess.data_ptr(),
+                                            resampled.data_ptr(), N.stream_ptr()), "sea_resample_systematic")
+    return index, logw_out, ess, resampled

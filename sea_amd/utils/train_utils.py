@@ -88,6 +88,10 @@ class FieldSpaceLoss(torch.nn.Module):
         return self.decoder.mse_loss(z, tgt, counts=self.counts, fused=self.fused)
 
 
+# ------------------------------------------------------------------------------------------------ ensembles (sea_amd/ensemble.py)
+from ..ensemble import FieldLikelihood, systematic_resample  # noqa: E402,F401  (re-exported: the particle-filter steps around a RolloutSession)
+
+
 # ------------------------------------------------------------------------------------------------ optimizer
 def initialize_optimizer(model, config):
     """AdamW(lr=config['learning_rate'], betas=(0.9, 0.999), eps=1e-8, weight_decay=config.get('weight_decay', 0.0)) as one fused
