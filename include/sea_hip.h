@@ -1049,6 +1049,47 @@ typedef struct {
 int sea_decode_member_sse(const SeaDecodeMseGroup* groups, int n_groups, const SeaDecodeMemberSse* p, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * The forecast of an ensemble: the weighted mean and the weighted, centred variance of the DECODED fields over the members of every history, in one
+ * launch for all field groups (plus a short finish launch above 128 members).  The decoded member fields never exist in memory.  Operands H, W2,
+ * bias, ldh, ldw, n_fields, field0 of SeaDecodeMseGroup as in sea_decode_member_sse (dH, Z, lddh, ldz are not read); there is no target.  Row
+ * m = (b * members + j) * P + patch of H is member j of history b (the order of RolloutSession.fork); B = M / (P * members) histories.
+ *     y_j[b, patch, f, c]    = sum_s H[m, s] W2[(f - field0) Cp + c, s] + bias[(f - field0) Cp + c]           (fp32 accumulation; never stored)
+ *     mean[b, patch, f, c]   = sum_j w_j y_j / sum_j w_j                                                      over the LIVE members j
+ *     var[b, patch, f, c]    = var_scale[b] * sum_j w_j (y_j - mean)^2
+ * w: f32 [B * members], the weight of member j of history b at b * members + j, normalised per history by the caller (sum 1: the mean is then
+ * sum_j w_j y_j); NULL: 1 / members each.  A member with w <= 0 or NaN is DEAD: it is passed over by a select, not multiplied by 0 — its hidden row is
+ * not read, and NaN or Inf in it reaches no output.  A history without a live member gets mean = var = 0.  var_scale: f32 [B] or NULL (1) — the caller's
+ * correction factor, e.g. 1 / (1 - sum_j w_j^2) for the unbiased estimator.  counts: device int32 [P] or NULL; valid(patch, c) = c < counts[patch]
+ * (clamped to [0, C]; NULL: c < C).  mean, var: f32 [B * P, n_fields_total, ld], element (bp, f, c) at (bp * n_fields_total + f) * ld + c; EVERY element
+ * is written: invalid columns and the columns [C, ld) are exactly 0 in both, so a freshly allocated output holds nothing uninitialised.  Only the
+ * ceil(counts[patch] / 32) column tiles of a field that hold valid columns are computed.
+ * Numerics: every partial result is a triple (W, mean, M2) with M2 taken about the partial's own mean — a lane's four members about their mean, then
+ * Chan's pairwise update  M2 = M2_a + M2_b + W_a W_b / (W_a + W_b) (m_a - m_b)^2  over lane groups, the 8 waves of a workgroup (16 members each) and the
+ * 128-member chunks, in a fixed order.  Nothing is formed as E[y^2] - E[y]^2.  A history whose weight sits on one member returns that member's decoded
+ * row bit for bit and var == 0 exactly.  No atomics, one writer per output element: two runs give the same bits, and a history's result does not
+ * depend on the other histories of the call.
+ * work: f32 workspace, private to the call, read only when members > 128: work_cap >= ceil(members / 128) * (2 * B * P * n_fields_total * ld + B * P)
+ * floats (a partial mean and M2 per chunk and output element, a weight per chunk and output row); may be NULL up to 128 members.
+ * Requirements: dtype SEA_BF16 (SEA_F32 returns SEA_EUNSUPPORTED); M >= 1; S a multiple of 8, at most 640 (above: SEA_EUNSUPPORTED), padded by
+ * masking; Cp a multiple of 32, 1 <= C <= Cp; P >= 1, members >= 1, M % (P * members) == 0; ld >= C, ld % 4 == 0; mean, var 16-byte aligned; w,
+ * var_scale, counts, work 4-byte aligned; per group H, W2, bias non-NULL and 16-byte aligned, ldh, ldw multiples of 8 and >= S; the groups' field
+ * ranges cover 0 .. n_fields_total-1 exactly once; 1 <= n_groups <= SEA_DECODE_MSE_MAX_GROUPS.
+ * Returns -1, with the entry point and the offending group named in sea_last_error(), otherwise; nothing touches a device before the checks pass.
+ * (An addition to ABI version 8.  sea_struct_sizes() keeps its 33 entries, SeaKvFork last: sizeof(SeaDecodeMemberMoments) is 88.)
+ */
+typedef struct {
+    const float* w;           /* f32 [B * members] normalised weights, or NULL (1 / members) */
+    const float* var_scale;   /* f32 [B], or NULL (1) */
+    const int32_t* counts;    /* device int32 [P] or NULL */
+    float* mean;              /* f32 [B * P, n_fields_total, ld] (output) */
+    float* var;               /* f32 [B * P, n_fields_total, ld] (output) */
+    float* work;              /* f32 [work_cap] workspace (members > 128), or NULL */
+    int64_t work_cap;
+    int32_t M, S, C, Cp, P, members, n_fields_total, ld;
+} SeaDecodeMemberMoments;
+int sea_decode_member_moments(const SeaDecodeMseGroup* groups, int n_groups, const SeaDecodeMemberMoments* p, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Systematic resampling of an ensemble, gated by the effective sample size, in one launch: log-weights in, the int32 device index that
  * sea_kv_cache_gather (RolloutSession.resample / select) takes out.  G histories with n members each, one workgroup per history, all sums in fp64.
  * Per history g (member j is element g n + j):

@@ -285,6 +285,14 @@ class SeaDecodeMemberSse(C.Structure):
                 ("M", _i32), ("S", _i32), ("C", _i32), ("Cp", _i32), ("P", _i32), ("members", _i32), ("n_fields_total", _i32), ("pad_", _i32)]
 
 
+class SeaDecodeMemberMoments(C.Structure):
+    # sea_decode_member_moments (not in ABI_STRUCTS, like its siblings: sea_struct_sizes() keeps SeaKvFork as its last entry and the existing tests hold
+    # that table at 33 entries; tests/test_ensemble_moments_cpu.py checks the layout through the library's argument checks)
+    _fields_ = [("w", _vp), ("var_scale", _vp), ("counts", _vp), ("mean", _vp), ("var", _vp), ("work", _vp), ("work_cap", _i64),
+                ("M", _i32), ("S", _i32), ("C", _i32), ("Cp", _i32), ("P", _i32), ("members", _i32), ("n_fields_total", _i32), ("ld", _i32)]
+
+
+MEMBER_MOMENTS_CHUNK = 128   # members one workgroup of sea_decode_member_moments finishes; above it the launch needs its workspace
 RESAMPLE_MAX_N = 4096      # members per history of sea_resample_systematic
 
 MAX_WGRAD_GROUPS = 32
@@ -392,6 +400,8 @@ def lib() -> C.CDLL:
     L.sea_decode_mse.restype = C.c_int
     L.sea_decode_member_sse.argtypes = [C.POINTER(SeaDecodeMseGroup), C.c_int, C.POINTER(SeaDecodeMemberSse), C.c_int, _vp]
     L.sea_decode_member_sse.restype = C.c_int
+    L.sea_decode_member_moments.argtypes = [C.POINTER(SeaDecodeMseGroup), C.c_int, C.POINTER(SeaDecodeMemberMoments), C.c_int, _vp]
+    L.sea_decode_member_moments.restype = C.c_int
     L.sea_resample_systematic.argtypes = [_vp, _vp, C.c_float, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]
     L.sea_resample_systematic.restype = C.c_int
     for name in ("sea_attention_bwd", "sea_wgrad_grouped", "sea_transpose_weights", "sea_rownorm_bwd", "sea_silu_outer_bwd", "sea_ib_bwd",
@@ -425,7 +435,7 @@ EXPORTED_SYMBOLS = (
     "sea_mse_fwd_bwd", "sea_relative_mse", "sea_adamw_flat", "sea_grad_norm_ctl", "sea_adamw_flat_ctl",
     "sea_wgrad_grouped", "sea_transpose_weights", "sea_rownorm_bwd", "sea_silu_outer_bwd", "sea_ib_bwd",
     "sea_attention_bwd", "sea_dropout_mask", "sea_run_list", "sea_run_list_steps", "sea_unpatchify", "sea_gemm_rownorm", "sea_exchange_tail", "sea_patchify", "sea_silu_outer_ib", "sea_mlp_fc1_ln_gelu", "sea_mlp_fc2_proj_norm", "sea_kv_rollout", "sea_kv_arena_words", "sea_kv_debug_stamps",
-    "sea_kv_cache_fill", "sea_kv_cache_fork", "sea_kv_cache_gather", "sea_decode_mse", "sea_decode_member_sse", "sea_resample_systematic",
+    "sea_kv_cache_fill", "sea_kv_cache_fork", "sea_kv_cache_gather", "sea_decode_mse", "sea_decode_member_sse", "sea_decode_member_moments", "sea_resample_systematic",
     "sea_gemm_fewrows", "sea_qkv_rope_fewrows", "sea_row_chain", "sea_row_chain_riders", "sea_gemm_adaln", "sea_mlp_block", "sea_adaln_qkv", "sea_splitk_finish",
     "sea_encoder_block_ws_floats", "sea_encoder_block_fwd", "sea_encoder_block_bwd",
     "sea_silu_outer_bwd_dc", "sea_silu_outer_bwd_dc_ws_floats", "sea_ib_bwd_dc",

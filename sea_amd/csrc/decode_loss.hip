@@ -529,3 +529,378 @@ extern "C" int sea_decode_member_sse(const SeaDecodeMseGroup* groups, int n_grou
     SEA_CHECK_LAUNCH("sea_decode_member_sse");
     return SEA_OK;
 }
+
+// ------------------------------------------------------------------------------------------------------------------------------------------------
+// sea_decode_member_moments: the weighted mean and the weighted, centred variance of the decoded fields over the members of each history (the forecast
+// of an ensemble and its spread).  The second consumer of stage 1 above — the same W2 tiles through the same two LDS images, the same H fragments in
+// registers — but it reduces over ROWS (the members of one (history, patch)) instead of over columns, so the two MFMA operands are swapped:
+//   A = the H fragments: lane (li, lg) holds the hidden row of member j0 + li — rows are loaded per lane by index, so the gather
+//       m = (b members + j) P + patch costs nothing,
+//   B = the W2 tile from LDS, read exactly as member_sse reads its A operand (row sub 16 + li, chunk 4 ks + lg),
+// and the accumulator of lane (li, lg) holds COLUMN cb + sub 16 + li for the four MEMBERS j0 + 4 lg + r.  Four members are reduced in registers, the
+// four lane groups by two butterfly steps, the NW = 8 waves of a workgroup (consecutive 16-member blocks of the same (history, patch): 128 members)
+// through 4 kB of LDS by the wave whose turn it is, which also stores the tile's 32 columns of both outputs.  Ensembles above 128 members run one
+// workgroup per 128-member chunk, each writing its (W, mean, M2) to the workspace, and a short finish launch folds the chunks in ascending order.
+//
+// Numerics.  Every partial is a triple (W, mean, M2) with M2 = sum w (y - mean)^2 taken about the partial's OWN mean: a lane takes the mean of its
+// (up to) four live members about the first live value, then their centred squares; partials are merged by Chan's update
+//     mean = m_a + (m_b - m_a) W_b / W,   M2 = M2_a + M2_b + (m_a - m_b)^2 W_a W_b / W,   W = W_a + W_b
+// in a fixed tree (lane groups (0,1),(2,3); waves ((0,1),(2,3)),((4,5),(6,7)); chunks left to right).  The weights do not depend on the column, so the
+// two factors of every merge, f = W_b / W and k = W_a f, are computed once per launch and not per tile; an empty side gives f = 1, k = 0 or
+// f = 0, k = 0, with which the update returns the other side's bits (an empty partial is (0, 0, 0)).  Nothing is ever formed as E[y^2] - E[y]^2.
+// A member with w <= 0 (or NaN) is dead: its hidden row is not loaded, and its accumulator registers are passed over by SELECTS, so NaN or Inf in it
+// reaches nothing.  A history with one live member therefore returns that member's decoded row bit for bit and a variance of exactly 0.
+// Waves whose 16-member block lies beyond `members` issue no MFMAs: they help carry the W2 tiles and take their turns at the stores.
+// counts: a workgroup serves ONE patch, so the column limit is uniform: only the ceil(lim / 32) tiles of a field that hold valid columns are
+// fetched and multiplied; everything at or beyond them, up to ld, is zero-filled.  One writer per output element, no atomics: two runs give the same
+// bits, and a history's result does not depend on the other histories of the call.
+struct MemberMomentsLaunch {
+    SeaDecodeMseGroup g[SEA_DECODE_MSE_MAX_GROUPS];
+    SeaDecodeMemberMoments p;
+    int n_chunks;
+    float w_uniform;   // 1 / members, used when p.w == NULL
+};
+
+constexpr int MM_NW = 8;               // waves per workgroup
+constexpr int MM_CHUNK = 16 * MM_NW;   // members a workgroup finishes
+
+template <int SP>
+constexpr int mm_lds_bytes() { return 2 * DM_TC * (SP * 2 + DM_PAD) + 2 * MM_NW * DM_TC * 8 + MM_NW * 4; }
+
+// the two factors of Chan's update for partial weights Wa (left) and Wb (right)
+__device__ __forceinline__ void mm_factors(float Wa, float Wb, float& f, float& k) {
+    f = Wb > 0.f ? (Wa > 0.f ? Wb / (Wa + Wb) : 1.f) : 0.f;
+    k = Wa * f;
+}
+// (ma, qa) <- merge of the left partial (ma, qa) and the right one (mb, qb)
+__device__ __forceinline__ void mm_merge(float& ma, float& qa, float mb, float qb, float f, float k) {
+    const float d = add1(mb, -ma);
+    ma = fma1(d, f, ma);
+    qa = fma1(mul1(d, d), k, add1(qa, qb));
+}
+
+template <int SP>
+__global__ __launch_bounds__(64 * MM_NW) void decode_member_moments_kernel(const MemberMomentsLaunch L) {
+    constexpr int NW = MM_NW;
+    constexpr int NT = 64 * NW;
+    constexpr int KS = SP / 32;
+    constexpr int PITCH = SP * 2 + DM_PAD;
+    constexpr int TILE = DM_TC * PITCH;
+    constexpr int NCH = SP * 4 / NT;
+    static_assert(NCH * NT == DM_TC * (SP / 8), "whole chunks per thread");
+    extern __shared__ __attribute__((aligned(16))) char smem[];   // 2 tile images; (mean, M2) of 32 columns per wave, twice; the waves' weights
+    float2* red = reinterpret_cast<float2*>(smem + 2 * TILE);
+    float* wsum = reinterpret_cast<float*>(smem + 2 * TILE + 2 * NW * DM_TC * 8);
+
+    const SeaDecodeMseGroup& G = L.g[blockIdx.y];
+    const SeaDecodeMemberMoments& P = L.p;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, lg = lane >> 4;
+    const int S = P.S, C = P.C, Cp = P.Cp, members = P.members, ld = P.ld, nft = P.n_fields_total;
+    const int n_chunks = L.n_chunks;
+    const int bp = blockIdx.x / n_chunks, chunk = blockIdx.x - bp * n_chunks;
+    const int b = bp / P.P, patch = bp - b * P.P;
+    const __bf16* H = static_cast<const __bf16*>(G.H);
+    const __bf16* W2 = static_cast<const __bf16*>(G.W2);
+    const uint4 zero4 = make_uint4(0u, 0u, 0u, 0u);
+    const bool last = n_chunks == 1;   // this workgroup finishes its outputs; otherwise it writes a partial per chunk
+
+    int lim = C;   // valid columns of this patch: [0, lim) — uniform over the workgroup
+    if (P.counts != nullptr) {
+        const int cnt = P.counts[patch];
+        lim = cnt < 0 ? 0 : (cnt > C ? C : cnt);
+    }
+    const int tpf = (lim + DM_TC - 1) / DM_TC;   // tiles of a field that hold valid columns
+    const int64_t out0 = ((int64_t)bp * nft + G.field0) * ld;   // (bp, field0, 0) of both outputs
+    if (last && tpf * DM_TC < ld) {   // columns behind the tiles: exactly 0
+        const int z0 = tpf * DM_TC, zw = ld - z0;
+        for (int i = tid; i < G.n_fields * zw; i += NT) {
+            const int j = i / zw;
+            const int64_t o = out0 + (int64_t)j * ld + z0 + (i - j * zw);
+            P.mean[o] = 0.f;
+            P.var[o] = 0.f;
+        }
+    }
+    if (tpf == 0) return;   // uniform: before any barrier
+
+    // this wave's 16-member block; the weights of the lane's four accumulator rows and of its hidden row
+    const int j0 = chunk * MM_CHUNK + wave * 16;
+    const bool active = j0 < members;   // uniform over the wave
+    const float* wrow = P.w != nullptr ? P.w + (int64_t)b * members : nullptr;
+    float wl[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int jr = j0 + 4 * lg + r;
+        const float v = jr < members ? (wrow != nullptr ? wrow[jr] : L.w_uniform) : 0.f;
+        wl[r] = v > 0.f ? v : 0.f;   // negative or NaN: dead
+    }
+    const int jm = j0 + li;
+    const bool row_live = jm < members && (wrow != nullptr ? wrow[jm] : L.w_uniform) > 0.f;
+    const int64_t m = ((int64_t)b * members + (jm < members ? jm : 0)) * P.P + patch;
+
+    uint4 hf[KS];
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+        const int s = ks * 32 + 8 * lg;
+        hf[ks] = (row_live && s < S) ? *reinterpret_cast<const uint4*>(H + m * G.ldh + s) : zero4;
+    }
+
+    // merge factors of the two butterfly steps (the left side is the lower lane group)
+    const float Wl = add1(add1(wl[0], wl[1]), add1(wl[2], wl[3]));
+    const float inv_Wl = Wl > 0.f ? 1.0f / Wl : 0.f;
+    const bool left1 = (lane & 16) == 0, left2 = (lane & 32) == 0;
+    float f1, k1, f2, k2;
+    const float Wo1 = __shfl_xor(Wl, 16);
+    mm_factors(left1 ? Wl : Wo1, left1 ? Wo1 : Wl, f1, k1);
+    const float Wp = add1(left1 ? Wl : Wo1, left1 ? Wo1 : Wl);
+    const float Wo2 = __shfl_xor(Wp, 32);
+    mm_factors(left2 ? Wp : Wo2, left2 ? Wo2 : Wp, f2, k2);
+    const float Ww = add1(left2 ? Wp : Wo2, left2 ? Wo2 : Wp);   // the wave's weight: the same bits in every lane
+    if (lane == 0) wsum[wave] = Ww;
+    if (!active && lane < DM_TC) {   // an empty block stays (0, 0) in both images
+        red[wave * DM_TC + lane] = make_float2(0.f, 0.f);
+        red[(NW + wave) * DM_TC + lane] = make_float2(0.f, 0.f);
+    }
+
+    const int n_tiles = G.n_fields * tpf;
+    uint4 wr[NCH];
+    dm_load_tile<SP, NT>(wr, W2, G.ldw, S, Cp, tpf, 0, tid);
+    dm_store_tile<SP, NT>(wr, smem, tid);
+    __syncthreads();
+
+    // merge factors of the wave tree ((0,1),(2,3)),((4,5),(6,7))
+    float tf[NW - 1], tk[NW - 1];
+    float Wtot;
+    {
+        float w2[NW / 2], w4[NW / 4];
+#pragma unroll
+        for (int i = 0; i < NW / 2; ++i) {
+            mm_factors(wsum[2 * i], wsum[2 * i + 1], tf[i], tk[i]);
+            w2[i] = add1(wsum[2 * i], wsum[2 * i + 1]);
+        }
+#pragma unroll
+        for (int i = 0; i < NW / 4; ++i) {
+            mm_factors(w2[2 * i], w2[2 * i + 1], tf[NW / 2 + i], tk[NW / 2 + i]);
+            w4[i] = add1(w2[2 * i], w2[2 * i + 1]);
+        }
+        mm_factors(w4[0], w4[1], tf[NW - 2], tk[NW - 2]);
+        Wtot = add1(w4[0], w4[1]);
+    }
+    const int64_t n_el = (int64_t)(P.M / (P.P * members)) * P.P * nft * ld;   // elements of one output
+    if (!last && G.field0 == 0 && tid == 0) P.work[2 * n_chunks * n_el + (int64_t)bp * n_chunks + chunk] = Wtot;
+    const float vs = P.var_scale != nullptr ? P.var_scale[b] : 1.0f;
+    float* const o_mean = P.mean;
+    float* const o_var = P.var;
+    float* const o_work = P.work;
+
+    // the 32 columns of a finished tile: merge the waves' partials (lanes 0-31 and 32-63 both do), store the mean (lanes 0-31) and the variance (32-63)
+    auto emit = [=](int rb, int pj, int pcb) {
+        const int col = lane & 31;
+        float mm[NW], qq[NW];
+#pragma unroll
+        for (int w = 0; w < NW; ++w) {
+            const float2 v = red[(rb * NW + w) * DM_TC + col];
+            mm[w] = v.x;
+            qq[w] = v.y;
+        }
+#pragma unroll
+        for (int i = 0; i < NW / 2; ++i) mm_merge(mm[2 * i], qq[2 * i], mm[2 * i + 1], qq[2 * i + 1], tf[i], tk[i]);
+#pragma unroll
+        for (int i = 0; i < NW / 4; ++i) mm_merge(mm[4 * i], qq[4 * i], mm[4 * i + 2], qq[4 * i + 2], tf[NW / 2 + i], tk[NW / 2 + i]);
+        mm_merge(mm[0], qq[0], mm[4], qq[4], tf[NW - 2], tk[NW - 2]);
+        const int c = pcb + col;
+        if (c < ld) {
+            const int64_t o = out0 + (int64_t)pj * ld + c;
+            if (last) {
+                const float v = lane < 32 ? mm[0] : mul1(qq[0], vs);
+                (lane < 32 ? o_mean : o_var)[o] = c < lim ? v : 0.f;
+            } else {
+                o_work[(int64_t)(lane < 32 ? chunk : n_chunks + chunk) * n_el + o] = lane < 32 ? mm[0] : qq[0];
+            }
+        }
+    };
+
+    int j = 0, tj = 0;     // field of tile t and the tile's index inside it
+    int pj = 0, pcb = 0;   // the same of tile t - 1
+    for (int t = 0; t < n_tiles; ++t) {
+        const char* buf = smem + (t & 1) * TILE;
+        if (t + 1 < n_tiles) dm_load_tile<SP, NT>(wr, W2, G.ldw, S, Cp, tpf, t + 1, tid);
+        const int cb = tj * DM_TC;
+        if (t > 0 && wave == ((t - 1) & (NW - 1))) emit((t - 1) & 1, pj, pcb);
+
+        if (active) {
+            f32x4 acc[2][2];
+#pragma unroll
+            for (int sub = 0; sub < 2; ++sub) {
+                const float bv = G.bias[j * Cp + cb + sub * 16 + li];
+                acc[sub][0] = f32x4{bv, bv, bv, bv};
+                acc[sub][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {
+                if (ks * 32 < S) {
+#pragma unroll
+                    for (int sub = 0; sub < 2; ++sub) {
+                        const uint4 wv = *reinterpret_cast<const uint4*>(buf + (sub * 16 + li) * PITCH + (ks * 4 + lg) * 16);
+                        mma16<__bf16>(hf[ks], wv, acc[sub][ks & 1]);
+                    }
+                }
+            }
+#pragma unroll
+            for (int sub = 0; sub < 2; ++sub) {
+                float y[4];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) y[r] = acc[sub][0][r] + acc[sub][1][r];   // plain C++, as above: the first reader of an MFMA result must be an instruction the compiler sees (it places the wait states behind the MFMA; it cannot for inline assembly)
+                // the lane's four members: mean about the first live value, then the centred squares; a dead member is passed over by selects
+                float ref = 0.f;
+#pragma unroll
+                for (int r = 3; r >= 0; --r) ref = wl[r] > 0.f ? y[r] : ref;
+                float sw = 0.f;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) sw = wl[r] > 0.f ? fma1(wl[r], add1(y[r], -ref), sw) : sw;
+                float mean = fma1(sw, inv_Wl, ref);
+                float q = 0.f;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float d = add1(y[r], -mean);
+                    q = wl[r] > 0.f ? fma1(mul1(wl[r], d), d, q) : q;
+                }
+                // lane groups (0, 1), (2, 3), then the pairs
+                float mo = __shfl_xor(mean, 16), qo = __shfl_xor(q, 16);
+                float ma = left1 ? mean : mo, qa = left1 ? q : qo;
+                mm_merge(ma, qa, left1 ? mo : mean, left1 ? qo : q, f1, k1);
+                mo = __shfl_xor(ma, 32);
+                qo = __shfl_xor(qa, 32);
+                float mb = left2 ? ma : mo, qb = left2 ? qa : qo;
+                mm_merge(mb, qb, left2 ? mo : ma, left2 ? qo : qa, f2, k2);
+                if (lg == 0) red[((t & 1) * NW + wave) * DM_TC + sub * 16 + li] = make_float2(mb, qb);
+            }
+        }
+        pj = j;
+        pcb = cb;
+        if (++tj == tpf) {
+            tj = 0;
+            ++j;
+        }
+
+        if (t + 1 < n_tiles) dm_store_tile<SP, NT>(wr, smem + ((t + 1) & 1) * TILE, tid);
+        __syncthreads();
+    }
+    if (wave == ((n_tiles - 1) & (NW - 1))) emit((n_tiles - 1) & 1, pj, pcb);
+}
+
+// ensembles above 128 members: fold the chunks' partials (left to right) into the outputs; one thread per output element
+__global__ __launch_bounds__(256) void member_moments_finish_kernel(const float* __restrict__ work, int n_chunks, const int32_t* __restrict__ counts,
+                                                                    const float* __restrict__ var_scale, float* __restrict__ mean, float* __restrict__ var,
+                                                                    int64_t n_el, int P, int nft, int ld, int C) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= n_el) return;
+    const int c = (int)(e % ld);
+    const int64_t bp = e / ld / nft;
+    const int patch = (int)(bp % P);
+    int lim = C;
+    if (counts != nullptr) {
+        const int cnt = counts[patch];
+        lim = cnt < 0 ? 0 : (cnt > C ? C : cnt);
+    }
+    if (c >= lim) {
+        mean[e] = 0.f;
+        var[e] = 0.f;
+        return;
+    }
+    const float* wm = work;
+    const float* wq = work + n_chunks * n_el;
+    const float* ww = work + 2 * n_chunks * n_el + bp * n_chunks;
+    float W = ww[0], mu = wm[e], q = wq[e];
+    for (int k = 1; k < n_chunks; ++k) {
+        float f, kk;
+        mm_factors(W, ww[k], f, kk);
+        mm_merge(mu, q, wm[k * n_el + e], wq[k * n_el + e], f, kk);
+        W = add1(W, ww[k]);
+    }
+    mean[e] = mu;
+    var[e] = mul1(q, var_scale != nullptr ? var_scale[bp / P] : 1.0f);
+}
+
+template <int SP>
+static void member_moments_launch(const MemberMomentsLaunch& L, dim3 grid, hipStream_t s) {
+    constexpr int lds = mm_lds_bytes<SP>();
+    static bool set_on[64] = {false};   // per device: SP = 640 needs 88 kB, above the 64 kB a kernel gets without the attribute
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = -1;
+    if (dev < 0 || !set_on[dev]) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(decode_member_moments_kernel<SP>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        if (dev >= 0) set_on[dev] = true;
+    }
+    decode_member_moments_kernel<SP><<<grid, dim3(64 * MM_NW), lds, s>>>(L);
+}
+
+extern "C" int sea_decode_member_moments(const SeaDecodeMseGroup* groups, int n_groups, const SeaDecodeMemberMoments* p, int dtype, void* stream) {
+    SEA_REQUIRE(groups != nullptr && p != nullptr, "sea_decode_member_moments: null argument table");
+    SEA_REQUIRE(n_groups >= 1 && n_groups <= SEA_DECODE_MSE_MAX_GROUPS, "sea_decode_member_moments: n_groups=%d outside 1..%d", n_groups, SEA_DECODE_MSE_MAX_GROUPS);
+    SEA_REQUIRE(dtype == SEA_F32 || dtype == SEA_BF16, "sea_decode_member_moments: bad dtype %d", dtype);
+    if (dtype != SEA_BF16) {
+        sea_set_error("sea_decode_member_moments: unsupported: bf16 only (the fp32 decoder composes sea_gemm_grouped and reductions)");
+        return SEA_EUNSUPPORTED;
+    }
+    const SeaDecodeMemberMoments& P = *p;
+    SEA_REQUIRE(P.mean != nullptr && P.var != nullptr, "sea_decode_member_moments: null mean or var pointer");
+    SEA_REQUIRE(P.M >= 1, "sea_decode_member_moments: M=%d must be positive", P.M);
+    SEA_REQUIRE(P.S >= 8 && P.S % 8 == 0, "sea_decode_member_moments: S=%d must be a positive multiple of 8", P.S);
+    SEA_REQUIRE(P.Cp >= 32 && P.Cp % 32 == 0, "sea_decode_member_moments: Cp=%d must be a positive multiple of 32", P.Cp);
+    SEA_REQUIRE(P.C >= 1 && P.C <= P.Cp, "sea_decode_member_moments: C=%d must lie in 1..Cp=%d", P.C, P.Cp);
+    SEA_REQUIRE(P.P >= 1 && P.members >= 1, "sea_decode_member_moments: P=%d and members=%d must be positive", P.P, P.members);
+    SEA_REQUIRE((int64_t)P.M % ((int64_t)P.P * P.members) == 0, "sea_decode_member_moments: M=%d is not a multiple of P * members = %d * %d", P.M, P.P, P.members);
+    SEA_REQUIRE(P.n_fields_total >= 1, "sea_decode_member_moments: n_fields_total=%d must be positive", P.n_fields_total);
+    SEA_REQUIRE(P.ld >= P.C && P.ld % 4 == 0, "sea_decode_member_moments: output row stride ld=%d must cover C=%d and be a multiple of 4", P.ld, P.C);
+    SEA_REQUIRE(sea_aligned16(P.mean) && sea_aligned16(P.var) && sea_aligned4(P.w) && sea_aligned4(P.var_scale) && sea_aligned4(P.counts) && sea_aligned4(P.work),
+                "sea_decode_member_moments: misaligned mean, var (16 bytes), w, var_scale, counts or work (4 bytes) pointer");
+    int64_t covered = 0;
+    for (int g = 0; g < n_groups; ++g) {
+        const SeaDecodeMseGroup& G = groups[g];
+        SEA_REQUIRE(G.H != nullptr && G.W2 != nullptr && G.bias != nullptr, "sea_decode_member_moments: group %d: null pointer", g);
+        SEA_REQUIRE(sea_aligned16(G.H) && sea_aligned16(G.W2) && sea_aligned16(G.bias), "sea_decode_member_moments: group %d: pointers must be 16-byte aligned", g);
+        SEA_REQUIRE(G.ldh >= P.S && G.ldh % 8 == 0 && G.ldw >= P.S && G.ldw % 8 == 0,
+                    "sea_decode_member_moments: group %d: row strides ldh=%d ldw=%d must cover S=%d and be multiples of 8", g, G.ldh, G.ldw, P.S);
+        SEA_REQUIRE(G.n_fields >= 1 && G.field0 >= 0 && (int64_t)G.field0 + G.n_fields <= P.n_fields_total,
+                    "sea_decode_member_moments: group %d: n_fields=%d, field0=%d outside the %d fields", g, G.n_fields, G.field0, P.n_fields_total);
+        SEA_REQUIRE((int64_t)G.n_fields * P.Cp <= 0x7fffffffLL / 2, "sea_decode_member_moments: group %d: too many output columns", g);
+        for (int h = 0; h < g; ++h)
+            SEA_REQUIRE(G.field0 >= groups[h].field0 + groups[h].n_fields || groups[h].field0 >= G.field0 + G.n_fields,
+                        "sea_decode_member_moments: group %d: its fields overlap those of group %d (every output element has one writer)", g, h);
+        covered += G.n_fields;
+    }
+    SEA_REQUIRE(covered == P.n_fields_total, "sea_decode_member_moments: the groups cover %lld of the %d fields (every field needs exactly one group)", (long long)covered, P.n_fields_total);
+    if (P.S > 640) {
+        sea_set_error("sea_decode_member_moments: unsupported: hidden width S=%d above 640", P.S);
+        return SEA_EUNSUPPORTED;
+    }
+    const int64_t BP = (int64_t)P.M / P.members;   // (history, patch) pairs: rows of the outputs
+    const int64_t n_chunks = ((int64_t)P.members + MM_CHUNK - 1) / MM_CHUNK;
+    const int64_t n_el = BP * P.n_fields_total * P.ld;
+    SEA_REQUIRE(BP * n_chunks <= 0x7fffffffLL && (n_el + 255) / 256 <= 0x7fffffffLL, "sea_decode_member_moments: too many rows");
+    if (n_chunks > 1) {
+        const int64_t need = n_chunks * (2 * n_el + BP);
+        SEA_REQUIRE(P.work != nullptr && P.work_cap >= need,
+                    "sea_decode_member_moments: workspace of %lld floats is too small: %lld needed (ceil(members / 128) * (2 * outputs + M / members); members=%d above 128)",
+                    (long long)(P.work != nullptr ? P.work_cap : 0), (long long)need, P.members);
+    }
+
+    MemberMomentsLaunch L;
+    memset(&L, 0, sizeof(L));
+    for (int g = 0; g < n_groups; ++g) L.g[g] = groups[g];
+    L.p = P;
+    L.n_chunks = (int)n_chunks;
+    L.w_uniform = 1.0f / (float)P.members;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)(BP * n_chunks), (unsigned)n_groups);
+    if (P.S <= 128) member_moments_launch<128>(L, grid, s);
+    else if (P.S <= 256) member_moments_launch<256>(L, grid, s);
+    else if (P.S <= 384) member_moments_launch<384>(L, grid, s);
+    else if (P.S <= 512) member_moments_launch<512>(L, grid, s);
+    else member_moments_launch<640>(L, grid, s);
+    if (n_chunks > 1)
+        member_moments_finish_kernel<<<dim3((unsigned)((n_el + 255) / 256)), dim3(256), 0, s>>>(P.work, (int)n_chunks, P.counts, P.var_scale, P.mean, P.var, n_el, P.P,
+                                                                                                   P.n_fields_total, P.ld, P.C);
+    SEA_CHECK_LAUNCH("sea_decode_member_moments");
+    return SEA_OK;
+}

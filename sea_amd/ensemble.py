@@ -7,12 +7,15 @@ RolloutSession.resample takes.
     logw = like(y, obs)                                           # [B * n] log-weights: one fused launch over the decoder's second layer
     index, logw, ess, resampled = systematic_resample(logw, n, ess_threshold=0.5, prior=logw_prev)
     ens.resample(index)                                           # the int32 device index goes in as it is
+    mean, var = EnsembleFields(decoder, n_patches, members=n, counts=counts)(y, logw=logw)   # the forecast: posterior mean and spread of the decoded fields
 
 FieldLikelihood is Decode.member_sse behind the latent -> z re-layout of FieldSpaceLoss: from 8192 rows (members x patches) on, or with
 fused=True, one fused launch over the decoder's second layer (sea_decode_member_sse: the decoded fields are never written); below that, by
 measurement, the decoder's forward plus reductions (Decode.member_sse states the rule); systematic_resample is sea_resample_systematic: normalisation, cumulative sum, effective sample size, the decision whether to
 resample and the searches in one launch.  Neither function reads anything back from the device (no .item(), no .cpu()): the decision lives in the
-index itself (the identity where a history was not resampled) and in the returned `resampled` tensor.
+index itself (the identity where a history was not resampled) and in the returned `resampled` tensor.  EnsembleFields is the product of the
+ensemble: the weighted mean and the centred variance of the members' decoded fields (Decode.member_moments; fused: sea_decode_member_moments, the
+members' fields are never written), from the log-weights as they are — normalised with tensor ops, nothing read back.
 """
 from __future__ import annotations
 
@@ -83,6 +86,65 @@ class FieldLikelihood:
         tgt = obs if layout == "BPFC" else obs.permute(0, 1, 3, 2)
         sse = self.decoder.member_sse(z, tgt, counts=self.counts, members=self.members, fused=self.fused)
         return (sse * self._field_scale(sse.device)).sum(1)
+
+
+def normalised_weights(logw: torch.Tensor, members: int) -> torch.Tensor:
+    """Log-weights [B * members] (unnormalised, or a `logw_out` of systematic_resample) -> float32 weights [B * members] that sum to 1 per history, with
+    tensor ops only.  A NaN or infinite log-weight is a dead member: weight exactly 0; the maximum over the live members is subtracted first; a
+    history without a live member gets equal weights (what `resampled == -1` means in the resampler: the ensemble is kept as it is)."""
+    lw = logw.detach().reshape(-1, members).to(torch.float32)
+    live = torch.isfinite(lw)
+    mx = torch.where(live, lw, torch.full_like(lw, float("-inf"))).max(dim=1, keepdim=True).values
+    w = torch.where(live, (torch.where(live, lw, mx) - mx).exp(), torch.zeros_like(lw))
+    W = w.sum(dim=1, keepdim=True)
+    return torch.where(W > 0, w / W.clamp_min(torch.finfo(torch.float32).tiny), torch.full_like(w, 1.0 / members)).reshape(-1).contiguous()
+
+
+class EnsembleFields:
+    """The forecast of an ensemble: fields(y, logw=None, unbiased=False) -> (mean, var), the weighted mean and the centred variance of the members'
+    decoded fields, each fp32 [B, P, n_fields, n_inp] (layout "BPFC": views of n_inp_p-wide buffers that sea_unpatchify reads in place —
+    MeshUnpatcher.inverse_scale_and_unpatch(mean, layout="BPFC") and unpatch_spread(var.sqrt())) or, with layout="BPCF", permuted views in the
+    reference's [B, P, n_inp, n_fields].
+
+    y: what RolloutSession.step returns for B * members trajectories, [B * members, n_groups, P * D], member j of history b at row b * members + j;
+    logw: None (equal weights) or [B * members] log-weights on y's device, unnormalised or the `logw_out` of systematic_resample (normalised_weights
+    states the rules: dead members get weight 0 and are passed over — NaN in their states reaches nothing; a history without a live member gets equal
+    weights); nothing is read back.  unbiased: multiply var by 1 / (1 - sum_j w_j^2).  counts: valid cells per patch (None: all), as in
+    Decode.mse_loss; invalid cells are exactly 0 in both results.  fused: None (Decode.member_moments' rule), True (the fused launch at any size;
+    bf16 only) or False (the composed path).  `decoder` is a sea_amd Decode; no autograd graph is built."""
+
+    def __init__(self, decoder, n_patches: int, members: int, counts=None, layout: str = "BPFC", fused: Optional[bool] = None):
+        if layout not in ("BPFC", "BPCF"):
+            raise ValueError(f"EnsembleFields: layout must be 'BPFC' or 'BPCF', got {layout!r}")
+        if not isinstance(n_patches, int) or isinstance(n_patches, bool) or n_patches < 1:
+            raise ValueError(f"EnsembleFields: n_patches = {n_patches!r} must be a positive integer")
+        if not isinstance(members, int) or isinstance(members, bool) or members < 1:
+            raise ValueError(f"EnsembleFields: members = {members!r} must be a positive integer")
+        self.decoder, self.n_patches, self.members, self.counts, self.layout, self.fused = decoder, n_patches, members, counts, layout, fused
+
+    def __call__(self, y: torch.Tensor, logw: Optional[torch.Tensor] = None, unbiased: bool = False, layout: Optional[str] = None):
+        layout = self.layout if layout is None else layout
+        if layout not in ("BPFC", "BPCF"):
+            raise ValueError(f"EnsembleFields: layout must be 'BPFC' or 'BPCF', got {layout!r}")
+        P = self.n_patches
+        if y.dim() != 3 or y.shape[-1] % P or y.shape[0] < 1:
+            raise ValueError(f"EnsembleFields: y must be [B * members, n_groups, n_patches * D] with n_patches = {P}, got {tuple(y.shape)}")
+        Bm, G, E = y.shape
+        if Bm % self.members:
+            raise ValueError(f"EnsembleFields: the {Bm} trajectories of y are not a multiple of members = {self.members}")
+        if logw is not None:
+            if not torch.is_tensor(logw) or not logw.is_floating_point() or logw.numel() != Bm or logw.dim() not in (1, 2) \
+                    or (logw.dim() == 2 and logw.shape[1] != self.members):
+                raise ValueError(f"EnsembleFields: logw must be None or a floating-point [{Bm}] (or [{Bm // self.members}, {self.members}]) tensor of log-weights, got "
+                                 f"{tuple(logw.shape) if torch.is_tensor(logw) else type(logw).__name__}")
+            if logw.device != y.device:
+                raise ValueError(f"EnsembleFields: logw is on {logw.device}, y on {y.device}")
+        N.require_gpu(y, "EnsembleFields states")
+        z = y.reshape(Bm, G, P, E // P).permute(0, 2, 1, 3)          # the re-layout of FieldLikelihood
+        with torch.no_grad():
+            w = None if logw is None else normalised_weights(logw, self.members)
+            mean, var = self.decoder.member_moments(z, self.members, weights=w, counts=self.counts, unbiased=bool(unbiased), fused=self.fused)
+        return (mean, var) if layout == "BPFC" else (mean.permute(0, 1, 3, 2), var.permute(0, 1, 3, 2))
 
 
 def systematic_resample(logw: torch.Tensor, members: int, u: Optional[torch.Tensor] = None, ess_threshold: Optional[float] = None,

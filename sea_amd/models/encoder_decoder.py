@@ -273,6 +273,81 @@ class Decode(nn.Module):
             bias = self._shadow[3]
             return ops.decode_member_sse([dict(H=hid[g], W2=W2[g], bias=bias[g]) for g in range(G)], t3, C, self._n_inp_p, P, members=members, counts=cnt, dtype=dt)
 
+    def member_moments(self, z: torch.Tensor, members: int, weights: Optional[torch.Tensor] = None, counts=None, unbiased: bool = False,
+                       fused: Optional[bool] = None):
+        """The forecast of an ensemble: (mean, var) of the decoded fields over the `members` members of every history, each fp32 [B, P, n_fields, n_inp]
+        (a view of an n_inp_p-wide buffer, like forward()'s result: sea_unpatchify reads it in place); no autograd graph.  z [B * members, P, n_groups,
+        embed_dim] in fork() order (row b * members + j is member j of history b); weights: None (1 / members) or float32 [B * members] on z's device,
+        normalised per history (EnsembleFields builds them from log-weights); a member with weight 0 is dead: it is passed over, NaN in its latents
+        reaches nothing.  mean = sum_j w_j y_j, var = sum_j w_j (y_j - mean)^2, centred; unbiased=True multiplies var by 1 / (1 - sum_j w_j^2)
+        (members / (members - 1) for equal weights), computed with tensor ops; a history whose weight sits on one member gets variance 0, not Inf.
+        counts as in mse_loss (None, or valid cells per patch; all-zero counts are accepted): invalid cells and the pad columns are exactly 0 in both.
+        bf16 compute dtype: the first-layer launch plus ONE fused launch (sea_decode_member_moments) — the members' decoded fields are never written;
+        fp32, or fused=False: forward() plus torch reductions (mean, then centred squares; the composed path).  `fused` forces either path; None:
+        fused in bf16 from 4096 rows (B * members * P) on, composed below — measured (tools/ensemble_bench.py --moments,
+        profiles/ensemble_moments_bench.txt; 64 members x 64 patches, n_inp 1628): at 4096 rows, the smallest size measured,
+        the fused path is ahead at both decoders (cylinder 0.21 against 0.29 - 0.31 ms; multiphase 0.30 against 0.30 - 0.32 ms: level with every
+        column valid, 8 % ahead with the mesh's counts), at 16384 rows 2.5 - 5.0x faster, and it needs 10 - 53 MB of extra memory against 307 -
+        1229 MB.  Below 4096 rows nothing has been measured, so the composed path stays the default there."""
+        n_fields = sum(len(g) for g in self.field_groups)
+        C, Cp = self.n_inp, self._n_inp_p
+        if z.dim() != 4 or z.shape[2] != self.num_groups or z.shape[3] != self.embed_dim:
+            raise ValueError(f"sea_amd.Decode.member_moments: z must be [B * members, P, {self.num_groups}, {self.embed_dim}], got {tuple(z.shape)}")
+        Bm, P = z.shape[0], z.shape[1]
+        if not isinstance(members, int) or isinstance(members, bool) or members < 1 or Bm < 1 or Bm % members:
+            raise ValueError(f"sea_amd.Decode.member_moments: members = {members!r} must be a positive integer that divides the {Bm} rows of z")
+        B = Bm // members
+        if weights is not None:
+            if not torch.is_tensor(weights) or weights.dim() != 1 or weights.shape[0] != Bm:
+                raise ValueError(f"sea_amd.Decode.member_moments: weights must be None or a [{Bm}] tensor (one weight per member), got "
+                                 f"{tuple(weights.shape) if torch.is_tensor(weights) else type(weights).__name__}")
+            if weights.dtype != torch.float32 or weights.device != z.device:
+                raise ValueError(f"sea_amd.Decode.member_moments: weights must be float32 on {z.device}, got {weights.dtype} on {weights.device}")
+        dt = self._act_dtype()
+        if fused is None:
+            fused = dt == torch.bfloat16 and Bm * P >= 4096
+        if fused and dt != torch.bfloat16:
+            raise ValueError("sea_amd.Decode.member_moments: the fused launch is bf16 only (set_compute_dtype('bf16'), or fused=False)")
+        cnt, _ = self._valid_counts(counts, P, z.device, allow_empty=True, what="member_moments")
+        N.require_gpu(z, "Decode.member_moments input")
+        with torch.no_grad():
+            w = None if weights is None else weights.detach().contiguous()
+            scale = None
+            if unbiased:
+                s2 = torch.full((B,), 1.0 / members, device=z.device, dtype=torch.float32) if w is None else (w.view(B, members) ** 2).sum(1)
+                den = 1.0 - s2
+                scale = torch.where(den > 0, 1.0 / den.clamp_min(torch.finfo(torch.float32).tiny), torch.zeros_like(den)).contiguous()
+            if not fused:
+                y = self.forward(z.detach()).view(B, members, P, n_fields, C)
+                wb = (torch.full((B, members), 1.0 / members, device=z.device, dtype=torch.float32) if w is None else w.view(B, members)).view(B, members, 1, 1, 1)
+                live = wb > 0
+                zero = torch.zeros((), device=z.device)
+                W = torch.where(live, wb, zero).sum(1)
+                mean = (wb * torch.where(live, y, zero)).sum(1) / W.clamp_min(torch.finfo(torch.float32).tiny)
+                d = torch.where(live, y - mean.unsqueeze(1), zero)
+                var = (wb * d * d).sum(1)
+                if scale is not None:
+                    var = var * scale.view(B, 1, 1, 1)
+                if cnt is not None:
+                    valid = (torch.arange(C, device=z.device) < cnt[:, None]).view(1, P, 1, C)
+                    mean, var = torch.where(valid, mean, zero), torch.where(valid, var, zero)
+                out = torch.zeros(2, B, P, n_fields, Cp, device=z.device, dtype=torch.float32)
+                out[0, ..., :C], out[1, ..., :C] = mean, var
+                return (out[0], out[1]) if Cp == C else (out[0, ..., :C], out[1, ..., :C])
+            M = Bm * P
+            G, D = self.num_groups, self.embed_dim
+            zf = z.detach().to(torch.float32).contiguous().view(M, G * D)
+            za = torch.empty(M, G * D, device=z.device, dtype=dt)
+            ops.convert(zf, za)
+            W1, W2 = self._weights(dt)
+            hid = [torch.empty(M, self.MLP_hidden, device=z.device, dtype=dt) for _ in range(G)]
+            ops.gemm_grouped([dict(A=za[:, g * D:(g + 1) * D], W=W1[g], Cact=hid[g], act=1) for g in range(G)], dt)
+            bias = self._shadow[3]
+            mean, var = ops.decode_member_moments([dict(H=hid[g], W2=W2[g], bias=bias[g]) for g in range(G)], C, Cp, P, members=members, weights=w,
+                                                  var_scale=scale, counts=cnt, ld=Cp, dtype=dt)
+            mean, var = mean.view(B, P, n_fields, Cp), var.view(B, P, n_fields, Cp)
+            return (mean, var) if Cp == C else (mean[..., :C], var[..., :C])
+
     def forward_prefix(self, z: torch.Tensor, buckets) -> torch.Tensor:
         """The decoder for a consumer that only reads the first cells of a patch (MeshUnpatcher.decode_and_unpatch: a patch holds as many mesh points as its
         cell has, the rest of its n_inp columns is padding nobody reads — 71 % of the columns on the bench's wake-refined mesh).  z [B, P, n_groups,

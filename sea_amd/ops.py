@@ -1052,6 +1052,84 @@ def decode_member_sse(groups: Sequence[Dict], target: torch.Tensor, C_: int, Cp:
     return sse
 
 
+def fill_decode_member_moments(groups_arr, P: N.SeaDecodeMemberMoments, groups: Sequence[Dict], weights, var_scale, counts, n_patches: int, members: int, C_: int,
+                               Cp: int, mean, var, work) -> None:
+    """The argument table of sea_decode_member_moments.  groups: dicts H act [M, S], W2 act [n_fields * Cp, S], bias f32 [n_fields * Cp]; group g's fields
+    follow those of the groups before it.  mean, var: f32 [M / members, n_fields_total, ld] contiguous; work: f32 workspace or None."""
+    field0 = 0
+    for g, d in zip(groups_arr, groups):
+        H, W2 = d["H"], d["W2"]
+        g.H, g.W2, g.bias, g.dH, g.Z = H.data_ptr(), W2.data_ptr(), d["bias"].data_ptr(), None, None
+        g.ldh, g.ldw, g.lddh, g.ldz = H.stride(0), W2.stride(0), 0, 0
+        g.n_fields, g.field0 = W2.shape[0] // Cp, field0
+        field0 += g.n_fields
+    P.w, P.var_scale, P.counts, P.mean, P.var, P.work = N.ptr(weights), N.ptr(var_scale), N.ptr(counts), mean.data_ptr(), var.data_ptr(), N.ptr(work)
+    P.work_cap = 0 if work is None else work.numel()
+    P.M, P.S, P.C, P.Cp, P.P = groups[0]["H"].shape[0], groups[0]["H"].shape[1], C_, Cp, n_patches
+    P.members, P.n_fields_total, P.ld = members, field0, mean.shape[2]
+
+
+def decode_member_moments(groups: Sequence[Dict], C_: int, Cp: int, n_patches: int, members: int = 1, weights: Optional[torch.Tensor] = None,
+                          var_scale: Optional[torch.Tensor] = None, counts: Optional[torch.Tensor] = None, ld: Optional[int] = None,
+                          dtype: torch.dtype = torch.bfloat16):
+    """sea_decode_member_moments: (mean, var) of the decoder's second layer over the `members` consecutive members of every history, each f32
+    [M / members, n_fields_total, ld] (ld: row width of the outputs, default Cp; every element is written, invalid and pad columns as 0).  groups as
+    fill_decode_member_moments; row m is patch m % n_patches of member m // n_patches.  weights: f32 [M / n_patches] normalised per history, or None
+    (1 / members); var_scale: f32 [M / (n_patches * members)] or None; counts: device int32 [n_patches] or None.  Everything is checked on the host
+    before the launch."""
+    if dtype != torch.bfloat16:
+        raise ValueError(f"decode_member_moments: the fused launch is bf16 only, got {dtype}")
+    if not groups or len(groups) > N.DECODE_MSE_MAX_GROUPS:
+        raise ValueError(f"decode_member_moments: {len(groups)} groups; a launch carries 1 .. {N.DECODE_MSE_MAX_GROUPS}")
+    if Cp < 32 or Cp % 32 or not 1 <= C_ <= Cp:
+        raise ValueError(f"decode_member_moments: need Cp a multiple of 32 and 1 <= C <= Cp, got C = {C_}, Cp = {Cp}")
+    ld = Cp if ld is None else ld
+    if ld < C_ or ld % 4:
+        raise ValueError(f"decode_member_moments: ld = {ld} must be a multiple of 4 that covers C = {C_}")
+    dev = groups[0]["H"].device
+    M, S = tuple(groups[0]["H"].shape) if groups[0]["H"].dim() == 2 else (0, 0)
+    if M < 1 or S < 8 or S % 8 or S > N.DECODE_MSE_MAX_S:
+        raise ValueError(f"decode_member_moments: H must be [M >= 1, S] with S a multiple of 8 up to {N.DECODE_MSE_MAX_S}, got {tuple(groups[0]['H'].shape)}")
+    if n_patches < 1 or members < 1:
+        raise ValueError(f"decode_member_moments: n_patches = {n_patches} and members = {members} must be positive")
+    if M % (n_patches * members):
+        raise ValueError(f"decode_member_moments: {M} rows are not a multiple of n_patches * members = {n_patches} * {members}")
+    n_fields = 0
+    for i, d in enumerate(groups):
+        for name in ("H", "W2"):
+            t = d[name]
+            if t.dim() != 2 or t.stride(1) != 1:
+                raise ValueError(f"decode_member_moments group {i}: {name}: need a 2-D tensor with unit inner stride, got shape {tuple(t.shape)} strides {t.stride()}")
+            if t.dtype != dtype or t.device != dev or t.shape[1] != S or (name != "W2" and t.shape[0] != M):
+                raise ValueError(f"decode_member_moments group {i}: {name} must be a {dtype} [{'n_fields * Cp' if name == 'W2' else M}, {S}] tensor on {dev}, got "
+                                 f"{tuple(t.shape)} {t.dtype} on {t.device}")
+            if t.stride(0) % 8 or t.data_ptr() % 16:
+                raise ValueError(f"decode_member_moments group {i}: {name} needs a row stride that is a multiple of 8 and a 16-byte-aligned base (stride {t.stride(0)})")
+        W2, b = d["W2"], d["bias"]
+        if W2.shape[0] < Cp or W2.shape[0] % Cp:
+            raise ValueError(f"decode_member_moments group {i}: W2 has {W2.shape[0]} rows, not a multiple of Cp = {Cp}")
+        if b.dtype != torch.float32 or b.dim() != 1 or b.shape[0] != W2.shape[0] or not b.is_contiguous() or b.device != dev or b.data_ptr() % 16:
+            raise ValueError(f"decode_member_moments group {i}: bias must be a contiguous, 16-byte-aligned float32 [{W2.shape[0]}] on {dev}, got {tuple(b.shape)} {b.dtype}")
+        n_fields += W2.shape[0] // Cp
+    Bm, B = M // n_patches, M // (n_patches * members)
+    for name, t, n in (("weights", weights, Bm), ("var_scale", var_scale, B)):
+        if t is not None and (not torch.is_tensor(t) or t.dtype != torch.float32 or t.dim() != 1 or t.shape[0] != n or not t.is_contiguous() or t.device != dev):
+            raise ValueError(f"decode_member_moments: {name} must be a contiguous float32 [{n}] tensor on {dev}, got "
+                             f"{(tuple(t.shape), t.dtype, str(t.device)) if torch.is_tensor(t) else type(t).__name__}")
+    if counts is not None and (counts.dtype != torch.int32 or counts.dim() != 1 or counts.shape[0] != n_patches or not counts.is_contiguous() or counts.device != dev):
+        raise ValueError(f"decode_member_moments: counts must be a contiguous int32 [{n_patches}] on {dev}, got {tuple(counts.shape)} {counts.dtype} on {counts.device}")
+    N.require_gpu(groups[0]["H"], "decode_member_moments hidden rows")   # every operand is on their device (checked above)
+    rows = M // members
+    mean = torch.empty(rows, n_fields, ld, device=dev, dtype=torch.float32)
+    var = torch.empty(rows, n_fields, ld, device=dev, dtype=torch.float32)
+    n_chunks = (members + N.MEMBER_MOMENTS_CHUNK - 1) // N.MEMBER_MOMENTS_CHUNK
+    work = torch.empty(n_chunks * (2 * mean.numel() + rows), device=dev, dtype=torch.float32) if n_chunks > 1 else None
+    arr, P = (N.SeaDecodeMseGroup * len(groups))(), N.SeaDecodeMemberMoments()
+    fill_decode_member_moments(arr, P, groups, weights, var_scale, counts, n_patches, members, C_, Cp, mean, var, work)
+    N.check(N.lib().sea_decode_member_moments(arr, len(groups), C.byref(P), N.dtype_code(dtype), N.stream_ptr()), "sea_decode_member_moments")
+    return mean, var
+
+
 def resample_systematic(logw: torch.Tensor, u: torch.Tensor, members: int, ess_frac: float = -1.0):
     """sea_resample_systematic: logw f32 [G * members] (device, contiguous), u f32 [G] in [0, 1), ess_frac < 0: always resample, else only the histories
     whose effective sample size is below ess_frac * members.  Returns (index int32 [G * members], logw_out f32 [G * members], ess f32 [G], resampled

@@ -132,6 +132,16 @@ class MeshUnpatcher:
         return ops.unpatchify(scaled_fields.float(), layout, self.partitioner.padded_index_map, self._scale, self._shift, self.partitioner.x_coords.numel(),
                               point_slot=self.partitioner.point_slot if self.gather else None)
 
+    def unpatch_spread(self, std_fields: torch.Tensor, layout: str = "BPFC") -> torch.Tensor:
+        """A spread (standard deviation) of the scaled fields onto the mesh in physical units: the inverse scaling x -> a x + b turns a standard
+        deviation s into |a| s, so this is inverse_scale_and_unpatch's launch with |a| and a zero shift.  std_fields [T, P, F, C] (layout "BPFC":
+        Decode.member_moments' var.sqrt() in place) or the reference's [T, P, C, F] ("BPCF") -> [T, N, F]."""
+        N.require_gpu(std_fields, "std_fields")
+        if not hasattr(self, "_abs_scale"):
+            self._abs_scale, self._zero_shift = self._scale.abs(), torch.zeros_like(self._shift)
+        return ops.unpatchify(std_fields.float(), layout, self.partitioner.padded_index_map, self._abs_scale, self._zero_shift, self.partitioner.x_coords.numel(),
+                              point_slot=self.partitioner.point_slot if self.gather else None)
+
 
     # ------------------------------------------------------------------ decoder + un-patchify without the padding
     def _prefix_plan(self, max_buckets: int):
@@ -231,6 +241,13 @@ class MeshProcessor:
         if self._unpatcher is None:
             raise ValueError("call patchify_and_scale first (it builds the partition)")
         return self._unpatcher.inverse_scale_and_unpatch(scaled_fields.to(self.device), layout=layout)
+
+    def unpatch_spread(self, std_fields: torch.Tensor, layout: str = "BPFC") -> torch.Tensor:
+        """An ensemble spread (standard deviation of the scaled fields, [T, P, F, C] or with layout="BPCF" [T, P, C, F]) -> [T, N, F] in physical units
+        (MeshUnpatcher.unpatch_spread: |scale|, no shift)."""
+        if self._unpatcher is None:
+            raise ValueError("call patchify_and_scale first (it builds the partition)")
+        return self._unpatcher.unpatch_spread(std_fields.to(self.device), layout=layout)
 
     def decode_and_unpatch(self, decoder, z: torch.Tensor) -> torch.Tensor:
         """decoder(z) + inverse_scale_and_unpatch(..., layout="BPFC") in one go, the decoder run only over a cell's mesh points (MeshUnpatcher.decode_and_unpatch):

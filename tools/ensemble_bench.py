@@ -13,7 +13,12 @@
       composed scoring below 8192 rows) — against step -> decoder forward + reductions -> eager resampling -> resample, alternating, host clock,
       drained around every batch of cycles.
 
+  (m) --moments (this leg alone): ms per Decode.member_moments — fused (sea_decode_member_moments) against composed (forward() + torch reductions:
+      mean, then centred squares) — at the sizes, members and meshes of (a), equal weights, with the peak of allocated memory above its value
+      before the call and the fused launch's MFMA fraction over the column tiles it walks (with counts: ceil(count / 32) tiles per patch).
+
     python tools/ensemble_bench.py [--reps 7] [--out profiles/ensemble_bench.txt]
+    python tools/ensemble_bench.py --moments [--out profiles/ensemble_moments_bench.txt]
 """
 import argparse
 import json
@@ -125,6 +130,7 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--sizes", default="cylinder,multiphase")
     ap.add_argument("--parts", default="a,b,c")
+    ap.add_argument("--moments", action="store_true", help="measure Decode.member_moments (leg m) instead of the legs of --parts")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -142,7 +148,41 @@ def main():
         print(s, flush=True)
         lines.append(s)
 
-    parts = args.parts.split(",")
+    parts = ["m"] if args.moments else args.parts.split(",")
+    if "m" in parts:
+        emit(f"ensemble_bench (m): Decode.member_moments, {MEMBERS} members per history, P = {P}, fields {groups}, n_inp = {n_inp} (valid cells per patch "
+             f"{int(counts.min())} .. {int(counts.max())}, {float(counts.sum()) / (P * n_inp):.2f} of the slots), bf16, equal weights, device time, median of {args.reps} windows")
+        emit(f"{'size':<11}{'B':>3}{'rows':>7} {'counts':<7}{'fused ms':>10}{'composed ms':>13}{'comp/fused':>11}{'fused MB':>10}{'composed MB':>13}{'MFMA':>7}{'rel mean':>10}{'rel var':>10}")
+        recs = []
+        for name in args.sizes.split(","):
+            sz = SIZES[name]
+            torch.manual_seed(1)
+            dec = Decode(groups, n_inp, sz["hidden"], sz["D"]).requires_grad_(False).set_compute_dtype("bf16").to(dev)
+            for B in (1, 4):
+                Bm = B * MEMBERS
+                M = Bm * P
+                z = torch.randn(Bm, P, len(groups), sz["D"], device=dev)
+                for cnt in (None, counts):
+                    def fused():
+                        return dec.member_moments(z, MEMBERS, counts=cnt, fused=True)
+
+                    def composed():
+                        return dec.member_moments(z, MEMBERS, counts=cnt, fused=False)
+
+                    (tf, tc), spread = device_ms([fused, composed], args.reps)
+                    a, b = fused(), composed()
+                    err_m, err_v = float((a[0] - b[0]).norm() / b[0].norm()), float((a[1] - b[1]).norm() / b[1].norm())
+                    mem_f, mem_c = extra_bytes(fused), extra_bytes(composed)
+                    walked = (n_inp + 31) // 32 * 32 if cnt is None else float(((cnt.clamp(0, n_inp) + 31) // 32 * 32).float().mean())
+                    rec = dict(size=name, B=B, rows=M, counts=cnt is not None, fused_ms=tf, composed_ms=tc, spread_ms=spread, fused_extra_bytes=mem_f,
+                               composed_extra_bytes=mem_c, mfma_fraction=2.0 * M * walked * n_fields * sz["hidden"] / (tf * 1e-3) / BF16_PEAK,
+                               fused_vs_composed_rel_l2_mean=err_m, fused_vs_composed_rel_l2_var=err_v)
+                    recs.append(rec)
+                    emit(f"{name:<11}{B:>3}{M:>7} {'mesh' if rec['counts'] else 'all':<7}{tf:>10.4f}{tc:>13.4f}{tc / tf:>11.2f}{mem_f / 2**20:>10.2f}{mem_c / 2**20:>13.2f}"
+                         f"{rec['mfma_fraction']:>7.3f}{err_m:>10.1e}{err_v:>10.1e}")
+                del z
+                torch.cuda.empty_cache()
+        record["member_moments"] = recs
     if "a" in parts:
         emit(f"ensemble_bench (a): Decode.member_sse, {MEMBERS} members per history, P = {P}, fields {groups}, n_inp = {n_inp} (valid cells per patch "
              f"{int(counts.min())} .. {int(counts.max())}, {float(counts.sum()) / (P * n_inp):.2f} of the slots), bf16, device time, median of {args.reps} windows")
