@@ -321,6 +321,8 @@ def lib() -> C.CDLL:
         raise NativeLibraryError(f"cannot load {LIB_PATH}: {e}") from e
     L.sea_abi_version.restype = C.c_int
     L.sea_last_error.restype = C.c_char_p
+    L.sea_last_form.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.sea_last_form.restype = C.c_char_p
     L.sea_struct_sizes.argtypes = [C.POINTER(C.c_int), C.c_int]
     L.sea_struct_sizes.restype = C.c_int
     L.sea_device_info.argtypes = [C.POINTER(C.c_int), C.c_char_p, C.c_int]
@@ -430,7 +432,7 @@ ABI_STRUCTS = (SeaGemmGroup, SeaQkvGroup, SeaQkvCommon, SeaAttnProblem, SeaAttnP
                SeaKvFill, SeaKvFork)
 
 EXPORTED_SYMBOLS = (
-    "sea_abi_version", "sea_last_error", "sea_struct_sizes", "sea_device_info", "sea_gemm_grouped", "sea_qkv_rope_grouped",
+    "sea_abi_version", "sea_last_error", "sea_last_form", "sea_struct_sizes", "sea_device_info", "sea_gemm_grouped", "sea_qkv_rope_grouped",
     "sea_attention_fwd", "sea_rownorm", "sea_silu_outer", "sea_ib_add", "sea_convert_f32_to_act", "sea_selftest_mfma",
     "sea_mse_fwd_bwd", "sea_relative_mse", "sea_adamw_flat", "sea_grad_norm_ctl", "sea_adamw_flat_ctl",
     "sea_wgrad_grouped", "sea_transpose_weights", "sea_rownorm_bwd", "sea_silu_outer_bwd", "sea_ib_bwd",

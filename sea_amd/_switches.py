@@ -23,8 +23,14 @@
   SEA_KV          key=value,...          KV-cache rollout: fast=0 (generic step plan), hoist=0 (condition work per step), gemv=0 (step plan without the few-row launches of gemv.hip),
                                            loop=python (step loop in Python),
                                            force_err=1 (test hook: the persistent launch "reports" a hand-off that gave up)
-  SEA_TUNE        key=value,...          native tuning aids read by libsea_hip.so (sea_tune() in core.hip): kv_persist, kv_pre, gemm_norm_rows, gemm_tile, gemm256, gemm_ws (0 off, 2 also short launches), attn_split4, attn_paired,
-                                           attnb_mode (attention backward: 1 XCD-local order, 2 paired causal tiles, 3 both, 0 neither), ...
+  SEA_TUNE        key=value,...          native tuning aids read by libsea_hip.so (sea_tune() in core.hip: one getenv, which returns at once when the variable is unset).
+                                         Read at EVERY call, because the tests force one form after another in one process — a key held in a function-local static
+                                         is fixed by the first call of the process, long before the forcing test starts —: gemm_tile (64 | 128), gemm256 (0 | 1),
+                                         gemm_ws (0 off, 2 also short launches), gemm_norm_rows (16 | 64), attn_split4 (0 | 1), attn_paired, attnb_mode (attention
+                                         backward: 1 XCD-local order, 2 paired causal tiles, 3 both, 0 neither), chain_rows, kv_persist, kv_pre, sse_rows, wgrad_tile
+                                         (64 | 128 | 256), wgrad_stage.  Every other key (gemm_skinny, gemm_dma_*, gemm_n_major, gemm_norm_dma, attn_row, wgrad_target,
+                                         wgrad_xcd, normbwd_*, ...) is a measurement aid read once per process: set it before the first launch; no test may force
+                                         one (tests/test_tune_keys_cpu.py).  Which kernel a launch took: ops.last_form() (sea_last_form, include/sea_hip.h).
   SEA_EXTRA_FLAGS "..."                  extra hipcc flags for `python -m sea_amd.build` (A/B builds)
 (tests only: SEA_TEST_DP_BACKEND=nccl runs the data-parallel tests one rank per GPU over RCCL.)
 """

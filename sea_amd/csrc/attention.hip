@@ -799,23 +799,28 @@ static int launch_attention_s(const SeaAttnParams& P, hipStream_t s) {
                 default: return -1;
             }
     }
+    sea_note_form(SPLIT == 2 && hdp <= 64 ? "attn.split2" : "attn.split1", paired, 0);   // (compute widths above 64 run one wave group)
     return 0;
 }
 
 template <typename T>
 static int launch_attention(const SeaAttnParams& P, hipStream_t s) {
     // few workgroups per CU and a long key range: split the key tiles of a query tile over two wave groups
-    if (launch_attention_row<T>(P, s)) return 0;
+    if (launch_attention_row<T>(P, s)) {
+        sea_note_form("attn.row", 0, 0);
+        return 0;
+    }
     const long blocks = (long)((P.Tq + 63) / 64) * P.B * P.H * P.n_problems;
     const bool split = blocks <= 1024 && P.Tk >= 256;
     // at most two workgroups per CU: four wave groups per query tile (measured at cfg2: cross-attention 18.3 -> 17.3 us; with 768
     // workgroups the 1024-thread workgroups no longer co-reside and it is slower, 21.7 -> 24.7 us)
-    static const int split4 = sea_tune("attn_split4", -1);  // tuning aid: 0 off, 1 on
+    const int split4 = sea_tune("attn_split4", -1);  // 0 off, 1 on; read per call (tests force the forms in one process)
     if (split && (split4 == 1 || (split4 < 0 && blocks <= 512)) && (P.hd == 8 || P.hd == 16 || P.hd == 32) && P.drop.thr == 0) {
         const dim3 grid((P.Tq + 63) / 64, P.B * P.H, P.n_problems), block(1024);
         if (P.hd == 32) attention_fwd_kernel<T, 32, 4, false><<<grid, block, 0, s>>>(P, 0);
         else if (P.hd == 16) attention_fwd_kernel<T, 16, 4, false><<<grid, block, 0, s>>>(P, 0);
         else attention_fwd_kernel<T, 8, 4, false><<<grid, block, 0, s>>>(P, 0);
+        sea_note_form("attn.split4", 0, 0);
         return 0;
     }
     if (P.drop.thr > 0) return split ? launch_attention_s<T, 2, true>(P, s) : launch_attention_s<T, 1, true>(P, s);

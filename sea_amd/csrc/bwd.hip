@@ -302,7 +302,7 @@ extern "C" int sea_wgrad_grouped(const SeaWgradGroup* groups, int n_groups, int 
         big = big && G.N % 128 == 0 && G.K % 128 == 0;
         long_m = long_m && G.M >= 2048;
     }
-    static const int forced = sea_tune("wgrad_tile", 0);  // tuning aid
+    const int forced = sea_tune("wgrad_tile", 0);  // read per call (tests force the forms in one process)
     long tiles128 = 0;
     for (int i = 0; i < n_groups; ++i) tiles128 += (long)((groups[i].N + 127) / 128) * ((groups[i].K + 127) / 128);
     // few 128-tiles would mean many contraction splits, i.e. many atomic passes over the same outputs: measured at cfg3 the small
@@ -348,7 +348,7 @@ extern "C" int sea_wgrad_grouped(const SeaWgradGroup* groups, int n_groups, int 
             if (best_cost < 0 || cost < best_cost) best_cost = cost, best_splits = sp;
         }
     }
-    int total = 0;
+    int total = 0, splits_max = 0, any_store = 0;
     for (int i = 0; i < n_groups; ++i) {
         const SeaWgradGroup& G = groups[i];
         long want = best_splits;
@@ -358,6 +358,8 @@ extern "C" int sea_wgrad_grouped(const SeaWgradGroup* groups, int n_groups, int 
         splits = (G.M + rows - 1) / rows;
         L.g[i] = G;
         L.splits[i] = splits;
+        splits_max = splits > splits_max ? splits : splits_max;
+        any_store |= G.overwrite != 0 && splits == 1;
         L.rows_per_split[i] = rows;
         L.tile_start[i] = total;
         total += ((G.N + tn - 1) / tn) * ((G.K + tk - 1) / tk) * splits;
@@ -378,6 +380,7 @@ extern "C" int sea_wgrad_grouped(const SeaWgradGroup* groups, int n_groups, int 
     if (dtype == SEA_BF16) { if (tn == 256) LAUNCH_WG(__bf16, 256, 128, 64); else if (tn == 128) LAUNCH_WG(__bf16, 128, 128, 64); else LAUNCH_WG(__bf16, 64, 64, 32); }
     else { if (tn == 128) LAUNCH_WG(float, 128, 128, 64); else LAUNCH_WG(float, 64, 64, 32); }
 #undef LAUNCH_WG
+    sea_note_form(tn == 256 ? "wgrad.tile256" : (tn == 128 ? "wgrad.tile128" : "wgrad.tile64"), splits_max, any_store);
     SEA_CHECK_LAUNCH("sea_wgrad_grouped");
     return SEA_OK;
 }

@@ -23,6 +23,16 @@ int sea_tune(const char* key, int dflt) {
     return dflt;
 }
 
+// The last noted launch form of this thread: a pointer to a string literal and two ints — no formatting, no allocation on the launch path.
+static thread_local const char* g_form = "";
+static thread_local int g_form_a = 0, g_form_b = 0;
+
+void sea_note_form(const char* literal, int a, int b) {
+    g_form = literal;
+    g_form_a = a;
+    g_form_b = b;
+}
+
 // CUs of the CURRENT device (one process per GPU: rank r's device is not device 0), cached per device; 256 when the query fails
 int sea_cu_count() {
     static int cu_of[64] = {0};
@@ -37,6 +47,11 @@ int sea_cu_count() {
 
 extern "C" int sea_abi_version(void) { return SEA_ABI_VERSION; }
 extern "C" const char* sea_last_error(void) { return g_err; }
+extern "C" const char* sea_last_form(int* a, int* b) {
+    if (a) *a = g_form_a;
+    if (b) *b = g_form_b;
+    return g_form;
+}
 
 // sizeof of every ABI struct, in header order, so that a binding can verify its own layout (returns the count).
 extern "C" int sea_struct_sizes(int* out, int cap) {

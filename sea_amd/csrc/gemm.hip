@@ -413,7 +413,7 @@ static int pick_tile(long tiles128, bool dma, long kmax = 0) {
     // tile halves.  Measured crossovers on the cfg2/cfg3 shapes at B = 1, 2, 4, 8 (single-buffered register-staged main loop):
     // condition GEMM 672 tiles 31.8 us (64) vs 28.0 (128); fc1 768: 22.0 vs 21.2, 6144: 135 vs 118; qkv 288: 16.7 vs 19.5, 2304: 61 vs 59;
     // LDS-DMA main loop (fc2) 384: 70 vs 79, 768: 158 vs 127.
-    static const int forced = sea_tune("gemm_tile", 0);  // tuning aid
+    const int forced = sea_tune("gemm_tile", 0);  // read per call (tests force the forms in one process)
     if (forced == 64 || forced == 128) return forced;
     // very long contractions with the chip nearly filled by 128 x 128 tiles (the reference's multiphase MLP: M = 796, N = 2048, K = 16384 -> 224 tiles): the launch
     // runs at the rate of its L2 -> LDS operand traffic, (BM + BN) K per tile — 3.5 GB with 64 x 64 tiles, 1.9 GB with 128 x 128: mlp.fc2 291 -> 173 us,
@@ -474,6 +474,7 @@ extern "C" int sea_gemm_grouped(const SeaGemmGroup* groups, int n_groups, int dt
         S.n_groups = n_groups;
         if (long_k) gemm_skinny_long_kernel<<<dim3(blocks), dim3(512), 0, static_cast<hipStream_t>(stream)>>>(S);
         else gemm_skinny_kernel<<<dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream)>>>(S);
+        sea_note_form(long_k ? "gemm.skinny_long" : "gemm.skinny", 0, 0);
         SEA_CHECK_LAUNCH("sea_gemm_grouped");
         return SEA_OK;
     }
@@ -523,19 +524,21 @@ extern "C" int sea_gemm_grouped(const SeaGemmGroup* groups, int n_groups, int dt
     // short contractions (K = 256 / 512) of long plain launches: the weight-stationary streaming kernel (gemm_ws.hip: weights in registers, activation rows once
     // per 256 output columns, the tile's store under the next tile's MFMAs)
     if (dtype == SEA_BF16 && !silu && sea_gemm_ws_try(groups, n_groups, s)) {
+        sea_note_form("gemm.ws", 0, 0);
         SEA_CHECK_LAUNCH("sea_gemm_grouped");
         return SEA_OK;
     }
     // 256 x 256 tiles (gemm256.hip: a wave owns 128 x 64, 96 B/clk of fragment reads at the full MFMA rate instead of the 128 x 128 tile's 128) for launches that
     // give every CU at least one such tile and a half.  SEA_TUNE=gemm256=0|1 forces.
     {
-        static const int g256 = sea_tune("gemm256", -1);
+        const int g256 = sea_tune("gemm256", -1);  // read per call (tests force the forms in one process)
         long t256 = 0;
         for (int i = 0; i < n_groups; ++i) t256 += (long)((groups[i].M + 255) / 256) * ((groups[i].N + 255) / 256);
         // measured (tools/bench_ops.py, SEA_TUNE=gemm256=0|1): 4096^3 139 -> 118 us (1164 TFLOP/s); 9 x (16192, 512, 512) 128.5 -> 122 us; 3 x (16192, 256, 2048) 61.9 -> 58.7;
         // the multiphase fc1 shape 121.6 -> 115; but 3 x (16192, 2048, 256) 91 -> 96 (four K-tiles: the launch is its epilogue) — hence the contraction floor
         const bool deep = (t256 >= 384 && kmax_all >= 512) || (t256 >= 192 && kmax_all >= 2048);
         if (dtype == SEA_BF16 && !silu && (g256 == 1 || (g256 < 0 && deep)) && sea_gemm256_try(groups, n_groups, L.n_major, s)) {
+            sea_note_form("gemm.256", 0, 0);
             SEA_CHECK_LAUNCH("sea_gemm_grouped");
             return SEA_OK;
         }
@@ -584,6 +587,7 @@ extern "C" int sea_gemm_grouped(const SeaGemmGroup* groups, int n_groups, int dt
 #undef LAUNCH_GEMM_T
 #undef LAUNCH_GEMM_SILU
 #undef LAUNCH_GEMM
+    sea_note_form(tile == 128 ? "gemm.tile128" : "gemm.tile64", dma && !silu ? 1 : 0, dma && !silu ? L.dma_ns : 0);
     SEA_CHECK_LAUNCH("sea_gemm_grouped");
     return SEA_OK;
 }

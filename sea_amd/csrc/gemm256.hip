@@ -208,7 +208,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const Gemm256Launch L) {
 
 // Launches the big-tile kernel for groups sea_gemm_grouped has validated; returns false (nothing launched) when a group needs a feature it does not have.
 bool sea_gemm256_try(const SeaGemmGroup* groups, int n_groups, unsigned n_major, hipStream_t s) {
-    static const bool force_act = sea_tune("gemm256", -1) == 1;
+    const bool force_act = sea_tune("gemm256", -1) == 1;  // read per call (tests force the forms in one process)
     Gemm256Launch L;
     memset(&L, 0, sizeof(L));
     int total = 0;

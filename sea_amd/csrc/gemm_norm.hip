@@ -444,7 +444,7 @@ extern "C" int sea_gemm_rownorm(const SeaGemmNormGroup* groups, int n_groups, fl
         total += (G.M + 63) / 64;
     }
     // 16-row tiles while the 64-row launch would leave most CUs without a workgroup (measured at cfg2: see DESIGN.md); SEA_TUNE=gemm_norm_rows=16|64 forces
-    static const int forced = sea_tune("gemm_norm_rows", 0);
+    const int forced = sea_tune("gemm_norm_rows", 0);  // read per call (tests force the forms in one process)
     const bool small = forced == 16 || (forced != 64 && total <= 512);
     if (small) {
         total = 0;
@@ -502,6 +502,7 @@ extern "C" int sea_gemm_rownorm(const SeaGemmNormGroup* groups, int n_groups, fl
 #undef LAUNCH_GN_T
 #undef LAUNCH_GN16
 #undef LAUNCH_GN
+    sea_note_form(!small ? "gemm_norm.rows64" : (dma_nk > 0 ? "gemm_norm.rows16_dma" : "gemm_norm.rows16"), 0, 0);
     SEA_CHECK_LAUNCH("sea_gemm_rownorm");
     return SEA_OK;
 }

@@ -76,6 +76,14 @@ def gemm_grouped(groups: Sequence[Dict], dtype: torch.dtype) -> None:
     N.check(N.lib().sea_gemm_grouped(arr, n, N.dtype_code(dtype), N.stream_ptr()), "sea_gemm_grouped")
 
 
+def last_form():
+    """(form, a, b) of the calling thread's last noted launch — which kernel sea_gemm_grouped / sea_gemm_rownorm / sea_attention_fwd / sea_wgrad_grouped
+    took (include/sea_hip.h, sea_last_form); ("", 0, 0) before any.  For the tests that force a form."""
+    a, b = C.c_int(0), C.c_int(0)
+    name = N.lib().sea_last_form(C.byref(a), C.byref(b))
+    return (name.decode() if name else ""), a.value, b.value
+
+
 LOG2E = 1.4426950408889634
 
 
@@ -471,22 +479,25 @@ def convert(src: torch.Tensor, dst: torch.Tensor) -> None:
 
 
 # ------------------------------------------------------------------------------------------------ backward wrappers
-def fill_wgrad_group(g: N.SeaWgradGroup, dY, X, dW, db=None, M=None) -> None:
-    """dW f32 [N, K] (+)= dY^T X over M rows (those of dY unless given); db f32 [N] (+)= the column sums of dY."""
+def fill_wgrad_group(g: N.SeaWgradGroup, dY, X, dW, db=None, M=None, overwrite=0) -> None:
+    """dW f32 [N, K] (+)= dY^T X over M rows (those of dY unless given); db f32 [N] (+)= the column sums of dY.  overwrite = 1: dW holds zeros (or
+    nothing worth keeping) and this group is its only contribution — the kernel may store instead of adding when it does not split the contraction."""
+    g.overwrite = int(overwrite)
     g.dY, g.X, g.dW, g.db = dY.data_ptr(), X.data_ptr(), dW.data_ptr(), N.ptr(db)
     g.lddy, g.ldx, g.lddw = dY.stride(0), X.stride(0), dW.stride(0)
     g.M, g.N, g.K = (dY.shape[0] if M is None else M), dW.shape[0], dW.shape[1]
 
 
 def wgrad_grouped(groups: Sequence[Dict], dtype: torch.dtype) -> None:
-    """groups: dicts with dY act [M,N], X act [M,K], dW f32 [N,K] (accumulated), optional db f32 [N] (accumulated)."""
+    """groups: dicts with dY act [M,N], X act [M,K], dW f32 [N,K] (accumulated), optional db f32 [N] (accumulated), optional overwrite (0 | 1, default 0:
+    include/sea_hip.h, SeaWgradGroup)."""
     n = len(groups)
     arr = (N.SeaWgradGroup * n)()
     for g, d in zip(arr, groups):
         dY, X, dW = _mat(d["dY"], "dY"), _mat(d["X"], "X"), _mat(d["dW"], "dW")
         assert dY.dtype == dtype and X.dtype == dtype and dW.dtype == torch.float32
         assert X.shape[0] == dY.shape[0] and dW.shape == (dY.shape[1], X.shape[1])
-        fill_wgrad_group(g, dY, X, dW, d.get("db"))
+        fill_wgrad_group(g, dY, X, dW, d.get("db"), overwrite=d.get("overwrite", 0))
     N.check(N.lib().sea_wgrad_grouped(arr, n, N.dtype_code(dtype), N.stream_ptr()), "sea_wgrad_grouped")
 
 

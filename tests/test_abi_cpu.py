@@ -73,6 +73,16 @@ def test_validation_without_gpu(lib):
     assert b"sea_kv_rollout" in lib.sea_last_error()
 
 
+def test_last_form_is_empty_before_any_noted_launch(lib):
+    """sea_last_form: "" and zeros until a launcher has launched something (a refused call notes nothing); null out-pointers are allowed."""
+    from sea_amd import _native as N, ops
+
+    g = (N.SeaGemmGroup * 1)()
+    assert lib.sea_gemm_grouped(g, 1, 0, None) == -1
+    assert ops.last_form() == ("", 0, 0)
+    assert lib.sea_last_form(None, None) == b""
+
+
 def test_cpu_tensors_are_refused():
     import torch
     from sea_amd import ops

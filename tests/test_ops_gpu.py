@@ -62,7 +62,8 @@ def test_gemm_bias_residual(dtype, M, N_, K):
 def test_gemm256_coalesced_residual_epilogue(monkeypatch):
     """gemm256.hip's path for a bf16 output with a fp32 residual (the training forward's mlp.fc2: x + MLP(x)): the residual is added in the coalesced copy-out.  cfg3's
     shape at a sixth of its rows per group — ragged last row tile, strided residual (one field of [M, F E]), N below the 256-column tile in one group — against fp32
-    torch and against the 128 x 128 kernel."""
+    torch and against the tiled kernel the launcher takes without it (31 tiles of 256 x 256 are too few for the big tile by itself, 122 of 128 x 128 too few
+    for the 128 tile: the 64 tile).  Both forms are forced per call and asserted; test_forced_forms_gpu.py runs the other edges and the 128 tile."""
     from sea_amd import ops
 
     bf = torch.bfloat16
@@ -78,12 +79,14 @@ def test_gemm256_coalesced_residual_epilogue(monkeypatch):
         refs.append(A.float() @ W.float().t() + bias + R)
     monkeypatch.setenv("SEA_TUNE", "gemm256=1")
     ops.gemm_grouped(groups, bf)
+    assert ops.last_form()[0] == "gemm.256"
     torch.cuda.synchronize()
     first = [g["Cact"].clone() for g in groups]
     for c, ref in zip(first, refs):
         assert torch.isfinite(c.float()).all() and rel(c.float(), ref) < 6e-3
     monkeypatch.setenv("SEA_TUNE", "gemm256=0")
     ops.gemm_grouped(groups, bf)
+    assert ops.last_form()[0] == "gemm.tile64"
     torch.cuda.synchronize()
     for g, c in zip(groups, first):
         assert rel(g["Cact"].float(), c.float()) < 4e-3
@@ -440,6 +443,8 @@ def test_attention_prefill_paired_tiles(monkeypatch, dtype, hd, T, src_len, B, H
         O = torch.full((B, T, H * hd), float("nan"), device=dev(), dtype=dtype)
         LSE = torch.full((B, H, T), float("nan"), device=dev())
         ops.attention_fwd([dict(Q=Q, K=K, Vt=Vt, O=O, LSE=LSE)], B, H, hd, T, T, cap, 0, src_len, dtype)
+        # (attn_split4=0: short launches with at least 256 keys run two wave groups, never paired; the others one)
+        assert ops.last_form() == (("attn.split2", 0, 0) if (B * H * ((T + 63) // 64)) <= 1024 and T >= 256 else ("attn.split1", paired, 0))
         torch.cuda.synchronize()
         outs.append((O, LSE))
     Oref, lse_ref = attention_ref(Q, K, Vt, 0, src_len, T)
@@ -590,9 +595,9 @@ def test_gemm_rownorm_matches_gemm_then_rownorm(dtype, N_, K):
 @pytest.mark.parametrize("M", [203, 2500])
 def test_gemm_rownorm_segments_ib_addend(dtype, M):
     """The exchange tail of one field in one launch: x += cross_up(sum_j g_j) (segments, bias counted per segment, in-place residual),
-    the copy cross_down reads is written BEFORE the info-bottleneck addend, AdaLN_2 is taken after it.  M = 2500 runs the 64-row tiles
-    (forced through SEA_TUNE=gemm_norm_rows is not needed: the launch is longer than 512 row tiles only at M > 32768, so both shapes are forced by env in
-    test_gemm_rownorm_tile_shapes_agree)."""
+    the copy cross_down reads is written BEFORE the info-bottleneck addend, AdaLN_2 is taken after it.  Both row counts run the 16-row tiles (M = 2500 is 40
+    tiles of 64 rows: the launcher takes the 64-row kernel only above 512 of them); the 64-row kernel is forced, and every kernel's name asserted, in
+    test_forced_forms_gpu.py::test_gemm_rownorm_tile_shapes_agree."""
     from sea_amd import ops
 
     D, E, h, S = 128, 256, 8, 2
@@ -672,7 +677,7 @@ def test_row_chain_matches_the_separate_launches(D, E, B, T, form, rows, monkeyp
     from sea_amd import ops
 
     if rows:
-        monkeypatch.setenv("SEA_TUNE", f"chain_rows={rows}")   # (read once per process by the library: only the first forced value of a process takes effect)
+        monkeypatch.setenv("SEA_TUNE", f"chain_rows={rows}")   # (read per call by the library)
     dt = torch.bfloat16
     M, H = B * T, D // 16
     hd = D // H

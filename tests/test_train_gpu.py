@@ -347,3 +347,56 @@ def test_bf16_training_reduces_loss():
     eng = m.engine()
     losses = [eng.train_step(x, tgt, ib, opt).item() for _ in range(30)]
     assert losses[-1] < 0.7 * losses[0], losses[::5]
+
+
+def _doubled_gradients_agree(names, g1, g2, dtype):
+    """g2 = 2 g1 for every live parameter, by name, to the noise of the atomics' order; .k.bias (a mathematically zero gradient: see the comment in
+    test_fused_train_step_equals_autograd_path) absolutely, against the largest gradient norm in the model."""
+    top = max(float(g1[k].double().norm()) for k in names)
+    for k in names:
+        a, b = g2[k].double(), 2 * g1[k].double()
+        if k.endswith(".k.bias"):
+            assert float((a - b).norm()) <= 2e-5 * top, (dtype, k, float((a - b).norm()), top)
+        else:
+            assert float((a - b).norm()) <= 2e-5 * float(b.norm()), (dtype, k, float((a - b).norm() / b.norm()))
+
+
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+def test_second_backward_without_zeroing_adds(dtype):
+    """Gradient accumulation: a backward into a buffer that already holds a microbatch's gradients must ADD everywhere.  The field MLP's weight-gradient
+    launches store instead of adding when the buffer holds zeros (SeaWgradGroup.overwrite, set per run from grads_dirty): a flag left on would silently
+    discard the first microbatch's fc1 / fc2 gradients.  Through the engine and through the module surface (two loss.backward() without zero_grad())."""
+    from sea_amd.utils.train_utils import SeaMSELoss
+
+    cfg = O.OracleConfig(2, 128, 4, 96, 8, 0, 3, 2, True, "adaln")
+    x, tgt, ib = recipe_inputs(2, 70, cfg, seed=78)
+    x, tgt, ib = x.cuda(), tgt.cuda(), ib.cuda()
+    m = build(cfg, dtype).train()
+    eng = m.engine()
+    names = list(eng.params.live_names)
+
+    def fwd_bwd():
+        out, plan = eng.forward_train(x, ib)
+        _, dout = eng.mse_loss_and_grad(out, tgt)
+        eng.backward(plan, dout)
+        sole = plan.__dict__.get("_sole_wgrads", [])
+        assert len(sole) > 0
+        return [int(g.overwrite) for g in sole]
+
+    eng.zero_grads()
+    assert set(fwd_bwd()) == {1}
+    g1 = {k: eng.grad_view(k).clone() for k in names}
+    assert any(k.endswith(".k.bias") for k in names) and all(torch.isfinite(v).all() for v in g1.values())
+    eng.zero_grads()
+    assert set(fwd_bwd()) == {1}
+    assert set(fwd_bwd()) == {0}
+    _doubled_gradients_agree(names, g1, {k: eng.grad_view(k).clone() for k in names}, dtype)
+
+    m2 = build(cfg, dtype).train()
+    for _ in range(2):
+        SeaMSELoss()(m2(x, ib), tgt).backward()
+    named = dict(m2.named_parameters())
+    assert list(m2.engine().params.live_names) == names and all(named[k].grad is not None for k in names)
+    _doubled_gradients_agree(names, g1, {k: named[k].grad for k in names}, dtype)
+    sole = m2.engine().train_plan(2, 70).__dict__.get("_sole_wgrads", [])
+    assert len(sole) > 0 and {int(g.overwrite) for g in sole} == {0}
