@@ -1097,6 +1097,49 @@ typedef struct {
 int sea_decode_member_moments(const SeaDecodeMseGroup* groups, int n_groups, const SeaDecodeMemberMoments* p, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Ensemble weighting against SPARSE observations: K sensors, each reading one decoded field at one cell of one patch, shared by all histories of the
+ * call; the precision-weighted squared error of every member in one launch for all field groups (plus a short finish launch).  The host sorts the
+ * sensors by (group, patch, given order), pads every (group, observed patch) segment to a multiple of 32 entries and hands over the tables
+ * (sea_amd/ensemble.py, SensorSet); K_pad is the length of the sorted, padded list and Q the number of observed patches (the sorted union over all
+ * groups).  Operands H, W2, bias, ldh, ldw, n_fields of SeaDecodeMseGroup (dH, Z, lddh, ldz, field0 are not read).  H holds the hidden rows of the
+ * OBSERVED patches only, patch-major: row q * Bm + bm is member bm at observed patch q, [Q * Bm, S].  For sorted position k of group g in patch q
+ * (seg[g * (Q + 1) + q] <= k < seg[g * (Q + 1) + q + 1]), member bm of history b = bm / members:
+ *     y[bm, k]   = sum_s H_g[q * Bm + bm, s] W2_g[wrow[k], s] + bias_g[wrow[k]]                       (fp32 accumulation)
+ *     w          = live[k] != 0 and prec[b * ld_prec + k] > 0 ? prec[b * ld_prec + k] : 0              (prec == NULL: 1)
+ *     d          = w > 0 ? y[bm, k] - obs[b * ld_obs + k] : 0          (a select: without weight a sensor is neutral whatever obs holds, NaN and Inf included)
+ *     wsse[bm]   = sum_k (w d) d                                        (fp32)
+ *     pred[bm * K_pad + k] = y[bm, k]                                   (when pred != NULL; pad positions are written too — W2 row wrow[k] = 0, a defined value)
+ * obs, prec: f32 in sorted, padded order, one row per history (ld_prec == 0: one precision row for all histories); live: int32 [K_pad], 0 at the pad
+ * entries; wrow: int32 [K_pad], the W2 row (field - first field of the group) * Cp + cell of every entry — the PADDED column index — and 0 at the
+ * pad entries; seg: int32 [n_groups, Q + 1], every row ascending in steps that are multiples of 32 (an empty step: the group has no sensor in that
+ * patch).  The kernel TRUSTS wrow (0 <= wrow < n_fields * Cp of its group) and seg (0 <= seg <= K_pad): they are device data the entry point cannot
+ * read; the caller range-checks them on the host before the upload.  work: f32 workspace of work_cap >= Q * n_groups * Bm floats, private to the
+ * call: one partial per (patch, group, member), every one written (zeros for an empty segment), summed per member by the finish launch in ascending
+ * order.  No atomics, one writer per element: two runs give the same bits, and a member's score does not depend on `members`, on the number of
+ * histories or on the row tile the member falls into.
+ * Requirements: dtype SEA_BF16 (SEA_F32 returns SEA_EUNSUPPORTED); Bm >= 1, members >= 1, Bm % members == 0; S a multiple of 8, at most 640
+ * (above: SEA_EUNSUPPORTED), padded by masking; Cp a multiple of 32; K_pad a multiple of 32, >= 32; 1 <= Q <= 65535; ld_obs >= K_pad, a multiple of
+ * 4; ld_prec 0 or as ld_obs; obs, prec (nullable), pred (nullable) 16-byte aligned, live, wrow, seg, wsse, work non-NULL and 4-byte aligned; per
+ * group H, W2, bias non-NULL and 16-byte aligned, ldh, ldw multiples of 8 and >= S; 1 <= n_groups <= SEA_DECODE_MSE_MAX_GROUPS.
+ * Returns -1, with the entry point named in sea_last_error(), otherwise; nothing touches a device before the checks pass.
+ * One kernel form ("sensor_sse.rows64" in sea_last_form): 64 members per workgroup.
+ * (An addition to ABI version 8.  sea_struct_sizes() keeps its 33 entries, SeaKvFork last: sizeof(SeaDecodeSensorSse) is 112.)
+ */
+typedef struct {
+    const float* obs;        /* f32 [Bm / members, K_pad] through ld_obs, sorted and padded */
+    const float* prec;       /* f32 [K_pad] (ld_prec 0) or [Bm / members, K_pad] through ld_prec, or NULL (1) */
+    const int32_t* live;     /* int32 [K_pad]: 1 a sensor, 0 a pad entry */
+    const int32_t* wrow;     /* int32 [K_pad]: row of the group's W2 */
+    const int32_t* seg;      /* int32 [n_groups, Q + 1] */
+    float* wsse;             /* f32 [Bm] (output) */
+    float* pred;             /* f32 [Bm, K_pad] (output) or NULL */
+    float* work;             /* f32 [work_cap] workspace */
+    int64_t ld_obs, ld_prec, work_cap;
+    int32_t Bm, members, S, Cp, Q, K_pad;
+} SeaDecodeSensorSse;
+int sea_decode_sensor_sse(const SeaDecodeMseGroup* groups, int n_groups, const SeaDecodeSensorSse* p, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Systematic resampling of an ensemble, gated by the effective sample size, in one launch: log-weights in, the int32 device index that
  * sea_kv_cache_gather (RolloutSession.resample / select) takes out.  G histories with n members each, one workgroup per history, all sums in fp64.
  * Per history g (member j is element g n + j):

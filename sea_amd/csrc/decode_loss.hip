@@ -904,3 +904,220 @@ extern "C" int sea_decode_member_moments(const SeaDecodeMseGroup* groups, int n_
     SEA_CHECK_LAUNCH("sea_decode_member_moments");
     return SEA_OK;
 }
+
+// ------------------------------------------------------------------------------------------------------------------------------------------------
+// sea_decode_sensor_sse: the precision-weighted squared error of every ensemble member against SPARSE observations — K sensors, each reading one
+// decoded field at one cell of one patch (ensemble weighting from probes instead of a dense snapshot).  Stage 1 of decode_mse_kernel once more, with
+// two changes: the 32 W2 rows of a tile are GATHERED through an index table (wrow: the sensors of one (group, patch) segment, sorted and padded to a
+// multiple of 32 by the host), and the other operand holds only the hidden rows of the observed patches (H is patch-major: row q Bm + bm is member bm
+// at observed patch q).  Workgroup (x, y, z) serves the 64-member row tile x of observed patch y and group z; wave w the members 16 w .. 16 w + 15; a
+// lane holds one member (lane & 15) and 8 of a tile's 32 sensors (sorted positions 16 sub + 4 (lane >> 4) + r), as in decode_member_sse_kernel.  A
+// (group, patch) pair without sensors is an empty segment: its workgroup writes zeros and leaves before any barrier.
+// Epilogue, per sensor: w = live and prec > 0 ? prec : 0; d = w > 0 ? y - obs : 0 (selects: a sensor without weight is neutral whatever obs holds, NaN
+// and Inf included); sum += (w d) d in fp32.  The lane adds its 8 sensors per tile over the tiles in order, the four lanes of a member are folded by
+// two butterfly steps, lane group 0 writes work[(y G + z) Bm + bm]: one writer per element, no atomics.  sensor_sse_finish_kernel adds a member's Q G
+// partials in ascending order.  A 16-row tile may straddle histories, so every lane derives its own history b = bm / members for obs and prec.  A
+// member's arithmetic touches nothing of the other rows of its tile (an MFMA column is a dot product of its own operands), so its score does not
+// depend on the tile it falls into, on `members` or on the number of histories: the same bits.  With pred != NULL the decoded values are stored
+// too, at pred[bm K_pad + sorted position] (pad positions included: their W2 row is row 0 — a defined value the caller drops).
+// The kernel trusts wrow (rows of W2) and seg: the host builds and range-checks them (sea_amd/ensemble.py, SensorSet).
+struct SensorSseLaunch {
+    SeaDecodeMseGroup g[SEA_DECODE_MSE_MAX_GROUPS];
+    SeaDecodeSensorSse p;
+};
+
+// dm_load_tile with gathered rows: row i of the tile is W2 row rows[i]; the 16-byte chunks of a row stay contiguous
+template <int SP, int NT = 256>
+__device__ __forceinline__ void ds_load_tile_gathered(uint4 (&wr)[SP * 4 / NT], const __bf16* W2, int ldw, int S, const int32_t* __restrict__ rows, int tid) {
+    constexpr int CPR = SP / 8;
+#pragma unroll
+    for (int u = 0; u < SP * 4 / NT; ++u) {
+        const int q = u * NT + tid, r = q / CPR, ch = q - r * CPR;
+        wr[u] = ch * 8 < S ? *reinterpret_cast<const uint4*>(W2 + (int64_t)rows[r] * ldw + ch * 8) : make_uint4(0u, 0u, 0u, 0u);
+    }
+}
+
+template <int SP>
+__global__ __launch_bounds__(256) void decode_sensor_sse_kernel(const SensorSseLaunch L) {
+#pragma clang fp reassociate(off)   // the lane's sum runs over its sensors in the stated order
+    constexpr int NT = 256;
+    constexpr int KS = SP / 32;
+    constexpr int PITCH = SP * 2 + DM_PAD;
+    constexpr int TILE = DM_TC * PITCH;
+    constexpr int NCH = SP * 4 / NT;
+    static_assert(NCH * NT == DM_TC * (SP / 8), "whole chunks per thread");
+    extern __shared__ __attribute__((aligned(16))) char smem[];   // 2 tile images
+
+    const SeaDecodeMseGroup& G = L.g[blockIdx.z];
+    const SeaDecodeSensorSse& P = L.p;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, lg = lane >> 4;
+    const int Bm = P.Bm, S = P.S;
+    const int q = blockIdx.y, n_g = gridDim.z;
+    const int bm = blockIdx.x * DM_ROWS + wave * 16 + li;   // the member this lane holds
+    float* const wslot = P.work + ((int64_t)q * n_g + blockIdx.z) * Bm + (bm < Bm ? bm : 0);
+
+    const int seg0 = P.seg[(int64_t)blockIdx.z * (P.Q + 1) + q], seg1 = P.seg[(int64_t)blockIdx.z * (P.Q + 1) + q + 1];
+    const int n_tiles = (seg1 - seg0) / DM_TC;
+    if (n_tiles <= 0) {   // uniform over the workgroup, before any barrier: no sensor of this group in this patch
+        if (lg == 0 && bm < Bm) *wslot = 0.f;
+        return;
+    }
+
+    const __bf16* H = static_cast<const __bf16*>(G.H);
+    const __bf16* W2 = static_cast<const __bf16*>(G.W2);
+    const uint4 zero4 = make_uint4(0u, 0u, 0u, 0u);
+    uint4 hf[KS];
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+        const int s = ks * 32 + 8 * lg;
+        hf[ks] = (bm < Bm && s < S) ? *reinterpret_cast<const uint4*>(H + ((int64_t)q * Bm + bm) * G.ldh + s) : zero4;
+    }
+    const int b = bm < Bm ? bm / P.members : 0;   // the lane's history: a row beyond Bm reads history 0 and stores nothing
+    const float* orow = P.obs + (int64_t)b * P.ld_obs;
+    const float* prow = P.prec != nullptr ? P.prec + (int64_t)b * P.ld_prec : nullptr;
+    float* drow = P.pred != nullptr && bm < Bm ? P.pred + (int64_t)bm * P.K_pad : nullptr;
+
+    uint4 wr[NCH];
+    ds_load_tile_gathered<SP, NT>(wr, W2, G.ldw, S, P.wrow + seg0, tid);
+    dm_store_tile<SP, NT>(wr, smem, tid);
+    __syncthreads();
+
+    float fsum = 0.f;
+    for (int t = 0; t < n_tiles; ++t) {
+        const char* buf = smem + (t & 1) * TILE;
+        const int k0 = seg0 + t * DM_TC;   // sorted position of the tile's first sensor
+        if (t + 1 < n_tiles) ds_load_tile_gathered<SP, NT>(wr, W2, G.ldw, S, P.wrow + k0 + DM_TC, tid);
+
+        // observation, precision and the live mask of this lane's 2 x 4 sensors (requested now, used after the products); the bias through the row table
+        float ob[2][4], pw[2][4];
+        f32x4 acc[2][2];
+#pragma unroll
+        for (int sub = 0; sub < 2; ++sub) {
+            const int k = k0 + sub * 16 + 4 * lg;   // a multiple of 4: obs, prec and pred rows start 16-byte aligned (K_pad % 32 == 0, strides % 4 == 0)
+            const float4 o = *reinterpret_cast<const float4*>(orow + k);
+            ob[sub][0] = o.x; ob[sub][1] = o.y; ob[sub][2] = o.z; ob[sub][3] = o.w;
+            float4 pv = make_float4(1.f, 1.f, 1.f, 1.f);
+            if (prow != nullptr) pv = *reinterpret_cast<const float4*>(prow + k);
+            pw[sub][0] = pv.x; pw[sub][1] = pv.y; pw[sub][2] = pv.z; pw[sub][3] = pv.w;
+            f32x4 bv;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                pw[sub][r] = (P.live[k + r] != 0 && pw[sub][r] > 0.f) ? pw[sub][r] : 0.f;   // pad entries, zero, negative and NaN precisions: no weight
+                bv[r] = G.bias[P.wrow[k + r]];
+            }
+            acc[sub][0] = bv;
+            acc[sub][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+            if (ks * 32 < S) {
+#pragma unroll
+                for (int sub = 0; sub < 2; ++sub) {
+                    const uint4 a = *reinterpret_cast<const uint4*>(buf + (sub * 16 + li) * PITCH + (ks * 4 + lg) * 16);
+                    mma16<__bf16>(a, hf[ks], acc[sub][ks & 1]);
+                }
+            }
+        }
+
+#pragma unroll
+        for (int sub = 0; sub < 2; ++sub) {
+            float y[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                y[r] = acc[sub][0][r] + acc[sub][1][r];
+                const float w = pw[sub][r];
+                const float d = w > 0.f ? y[r] - ob[sub][r] : 0.f;
+                fsum = __builtin_fmaf(w * d, d, fsum);
+            }
+            if (drow != nullptr) *reinterpret_cast<float4*>(drow + k0 + sub * 16 + 4 * lg) = make_float4(y[0], y[1], y[2], y[3]);
+        }
+
+        if (t + 1 < n_tiles) dm_store_tile<SP, NT>(wr, smem + ((t + 1) & 1) * TILE, tid);
+        __syncthreads();
+    }
+
+    // fold the member's four lanes, one writer
+    float v = fsum;
+    v += __shfl_xor(v, 16);
+    v += __shfl_xor(v, 32);
+    if (lg == 0 && bm < Bm) *wslot = v;
+}
+
+// wsse[bm] = sum of the member's Q * G partials work[i Bm + bm], i ascending: a fixed order
+__global__ __launch_bounds__(256) void sensor_sse_finish_kernel(const float* __restrict__ work, float* __restrict__ wsse, int Bm, int n_part) {
+#pragma clang fp reassociate(off)   // the order IS the contract: with the file's -ffast-math the loop was vectorised into two partial sums when Bm == 1 — other bits than at Bm > 1
+    const int bm = blockIdx.x * 256 + threadIdx.x;
+    if (bm >= Bm) return;
+    float acc = 0.f;
+    for (int i = 0; i < n_part; ++i) acc += work[(int64_t)i * Bm + bm];
+    wsse[bm] = acc;
+}
+
+template <int SP>
+static void sensor_sse_launch(const SensorSseLaunch& L, dim3 grid, hipStream_t s) {
+    constexpr int lds = 2 * DM_TC * (SP * 2 + DM_PAD);
+    static bool set_on[64] = {false};   // per device: SP = 640 needs 84 kB, above the 64 kB a kernel gets without the attribute
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = -1;
+    if (dev < 0 || !set_on[dev]) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(decode_sensor_sse_kernel<SP>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        if (dev >= 0) set_on[dev] = true;
+    }
+    decode_sensor_sse_kernel<SP><<<grid, dim3(256), lds, s>>>(L);
+}
+
+extern "C" int sea_decode_sensor_sse(const SeaDecodeMseGroup* groups, int n_groups, const SeaDecodeSensorSse* p, int dtype, void* stream) {
+    SEA_REQUIRE(groups != nullptr && p != nullptr, "sea_decode_sensor_sse: null argument table");
+    SEA_REQUIRE(n_groups >= 1 && n_groups <= SEA_DECODE_MSE_MAX_GROUPS, "sea_decode_sensor_sse: n_groups=%d outside 1..%d", n_groups, SEA_DECODE_MSE_MAX_GROUPS);
+    SEA_REQUIRE(dtype == SEA_F32 || dtype == SEA_BF16, "sea_decode_sensor_sse: bad dtype %d", dtype);
+    if (dtype != SEA_BF16) {
+        sea_set_error("sea_decode_sensor_sse: unsupported: bf16 only (the fp32 decoder composes sea_gemm_grouped, a gather and reductions)");
+        return SEA_EUNSUPPORTED;
+    }
+    const SeaDecodeSensorSse& P = *p;
+    SEA_REQUIRE(P.obs != nullptr && P.live != nullptr && P.wrow != nullptr && P.seg != nullptr && P.wsse != nullptr && P.work != nullptr,
+                "sea_decode_sensor_sse: null obs, live, wrow, seg, wsse or work pointer");
+    SEA_REQUIRE(P.Bm >= 1 && P.members >= 1 && P.Bm % P.members == 0, "sea_decode_sensor_sse: Bm=%d must be a positive multiple of members=%d", P.Bm, P.members);
+    SEA_REQUIRE(P.S >= 8 && P.S % 8 == 0, "sea_decode_sensor_sse: S=%d must be a positive multiple of 8", P.S);
+    SEA_REQUIRE(P.Cp >= 32 && P.Cp % 32 == 0, "sea_decode_sensor_sse: Cp=%d must be a positive multiple of 32", P.Cp);
+    SEA_REQUIRE(P.K_pad >= 32 && P.K_pad % 32 == 0, "sea_decode_sensor_sse: K_pad=%d must be a positive multiple of 32", P.K_pad);
+    SEA_REQUIRE(P.Q >= 1 && P.Q <= 65535, "sea_decode_sensor_sse: Q=%d observed patches outside 1..65535", P.Q);
+    SEA_REQUIRE(P.ld_obs >= P.K_pad && P.ld_obs % 4 == 0, "sea_decode_sensor_sse: obs row stride ld_obs=%lld must cover K_pad=%d and be a multiple of 4", (long long)P.ld_obs, P.K_pad);
+    SEA_REQUIRE(P.prec == nullptr || P.ld_prec == 0 || (P.ld_prec >= P.K_pad && P.ld_prec % 4 == 0),
+                "sea_decode_sensor_sse: prec row stride ld_prec=%lld must be 0 (one row for all histories) or cover K_pad=%d and be a multiple of 4", (long long)P.ld_prec, P.K_pad);
+    SEA_REQUIRE(sea_aligned16(P.obs) && sea_aligned16(P.prec) && sea_aligned16(P.pred), "sea_decode_sensor_sse: obs, prec and pred must be 16-byte aligned");
+    SEA_REQUIRE(sea_aligned4(P.live) && sea_aligned4(P.wrow) && sea_aligned4(P.seg) && sea_aligned4(P.wsse) && sea_aligned4(P.work),
+                "sea_decode_sensor_sse: misaligned live, wrow, seg, wsse or work pointer");
+    for (int g = 0; g < n_groups; ++g) {
+        const SeaDecodeMseGroup& G = groups[g];
+        SEA_REQUIRE(G.H != nullptr && G.W2 != nullptr && G.bias != nullptr, "sea_decode_sensor_sse: group %d: null pointer", g);
+        SEA_REQUIRE(sea_aligned16(G.H) && sea_aligned16(G.W2) && sea_aligned16(G.bias), "sea_decode_sensor_sse: group %d: pointers must be 16-byte aligned", g);
+        SEA_REQUIRE(G.ldh >= P.S && G.ldh % 8 == 0 && G.ldw >= P.S && G.ldw % 8 == 0,
+                    "sea_decode_sensor_sse: group %d: row strides ldh=%d ldw=%d must cover S=%d and be multiples of 8", g, G.ldh, G.ldw, P.S);
+        SEA_REQUIRE(G.n_fields >= 1 && (int64_t)G.n_fields * P.Cp <= 0x7fffffffLL / 2, "sea_decode_sensor_sse: group %d: n_fields=%d", g, G.n_fields);
+    }
+    if (P.S > 640) {
+        sea_set_error("sea_decode_sensor_sse: unsupported: hidden width S=%d above 640", P.S);
+        return SEA_EUNSUPPORTED;
+    }
+    const int64_t row_blocks = ((int64_t)P.Bm + DM_ROWS - 1) / DM_ROWS;
+    const int64_t need = (int64_t)P.Q * n_groups * P.Bm;
+    SEA_REQUIRE(row_blocks <= 0x7fffffffLL && (int64_t)P.Q * P.Bm <= 0x7fffffffLL, "sea_decode_sensor_sse: too many rows");
+    SEA_REQUIRE(P.work_cap >= need, "sea_decode_sensor_sse: workspace of %lld floats is too small: %lld needed (Q * n_groups * Bm)", (long long)P.work_cap, (long long)need);
+
+    SensorSseLaunch L;
+    memset(&L, 0, sizeof(L));
+    for (int g = 0; g < n_groups; ++g) L.g[g] = groups[g];
+    L.p = P;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)row_blocks, (unsigned)P.Q, (unsigned)n_groups);
+    if (P.S <= 128) sensor_sse_launch<128>(L, grid, s);
+    else if (P.S <= 256) sensor_sse_launch<256>(L, grid, s);
+    else if (P.S <= 384) sensor_sse_launch<384>(L, grid, s);
+    else if (P.S <= 512) sensor_sse_launch<512>(L, grid, s);
+    else sensor_sse_launch<640>(L, grid, s);
+    sea_note_form("sensor_sse.rows64", 0, 0);
+    sensor_sse_finish_kernel<<<dim3((unsigned)((P.Bm + 255) / 256)), dim3(256), 0, s>>>(P.work, P.wsse, P.Bm, (int)((int64_t)P.Q * n_groups));
+    SEA_CHECK_LAUNCH("sea_decode_sensor_sse");
+    return SEA_OK;
+}

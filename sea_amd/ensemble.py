@@ -16,6 +16,14 @@ resample and the searches in one launch.  Neither function reads anything back f
 index itself (the identity where a history was not resampled) and in the returned `resampled` tensor.  EnsembleFields is the product of the
 ensemble: the weighted mean and the centred variance of the members' decoded fields (Decode.member_moments; fused: sea_decode_member_moments, the
 members' fields are never written), from the log-weights as they are — normalised with tensor ops, nothing read back.
+
+Sparse observations — K point sensors, each reading one field at one cell of one patch, with a precision per reading (0: missing) — take the place of
+the dense snapshot through SensorSet and SensorLikelihood:
+
+    sensors = unpatcher.sensor_set(decoder, points, fields)       # or SensorSet(decoder, n_patches, patch, cell, field): tables built and uploaded once
+    like = SensorLikelihood(decoder, n_patches, members=n, sensors=sensors, sigma=sensors.scale_sigma(sigma_phys))
+    logw = like(y, sensors.scale_values(readings), precision)     # [B * n]: Decode.sensor_sse — the first layer over the observed patches only, then ONE
+                                                                  # launch (sea_decode_sensor_sse) over the sensors' rows of the second layer
 """
 from __future__ import annotations
 
@@ -25,6 +33,11 @@ import torch
 
 from . import _native as N
 from . import ops
+
+try:   # numpy integers are accepted in sensor index sequences where numpy is installed
+    import numpy as _np
+except ImportError:   # pragma: no cover
+    _np = None
 
 
 class FieldLikelihood:
@@ -187,3 +200,260 @@ def systematic_resample(logw: torch.Tensor, members: int, u: Optional[torch.Tens
         if u is None:
             u = torch.rand(G, device=lw.device, dtype=torch.float32)
         return ops.resample_systematic(lw, u.contiguous(), members, frac)
+
+
+# ------------------------------------------------------------------------------------------------ sparse observations
+def _int_list(x, name: str, what: str):
+    """A 1-D sequence or tensor of integers as a list of Python ints; bool, float, empty, nested or ragged input is refused."""
+    if torch.is_tensor(x):
+        if x.dtype == torch.bool or x.is_floating_point() or x.is_complex() or x.dim() != 1 or x.numel() < 1:
+            raise ValueError(f"{what}: {name} must be a non-empty 1-D integer sequence or tensor, got a {tuple(x.shape)} {x.dtype} tensor")
+        return [int(v) for v in x.detach().cpu().tolist()]       # a tensor given on the device comes to the host once, here
+    try:
+        vals = list(x)
+    except TypeError:
+        raise ValueError(f"{what}: {name} must be a non-empty 1-D integer sequence or tensor, got {type(x).__name__}") from None
+    if not vals:
+        raise ValueError(f"{what}: {name} is empty")
+    out = []
+    for v in vals:
+        if torch.is_tensor(v) and v.dim() == 0 and v.dtype != torch.bool and not v.is_floating_point() and not v.is_complex():
+            v = int(v)
+        if isinstance(v, bool) or not isinstance(v, int):
+            if _np is None or not isinstance(v, _np.integer):
+                raise ValueError(f"{what}: {name} must hold integers only (no bool, float or nested sequence), got {type(v).__name__}")
+        out.append(int(v))
+    return out
+
+
+class SensorSet:
+    """K >= 1 point sensors shared by all histories of a call: sensor k reads decoded field field[k] at cell cell[k] of patch patch[k].
+
+    patch, cell, field: integer sequences or tensors of equal length (a device tensor comes to the host once, here), checked on the host:
+    0 <= patch < n_patches, 0 <= cell < decoder.n_inp, field one of the decoder's fields.  Duplicates are allowed (two instruments at one point).
+    The launch tables of sea_decode_sensor_sse are built here, once, and uploaded once per device (at construction for the decoder's device when
+    that is a GPU, otherwise at the first call on a device):
+      order   the sensors sorted by (group, patch, given order), every (group, observed patch) segment padded to a multiple of 32 entries: K_pad
+      perm    int32 [K_pad]: sorted position -> sensor (pad entries point at sensor 0)
+      wrow    int32 [K_pad]: the row of the group's second-layer weights, (position of the field in its group) * Cp + cell with Cp = the decoder's
+              PADDED cell width (pad entries: 0)
+      live    int32 [K_pad]: 1 a sensor, 0 a pad entry
+      Q       the observed patches: the sorted union over all groups (`patches`, int64 [Q] on the device)
+      seg     int32 [n_groups, Q + 1]: the CSR table of the segments in the sorted list (a (group, patch) pair without sensors: an empty segment)
+      inv     int64 [K]: sensor -> sorted position (un-permutes the predictions)
+    perm and wrow are range-checked before the upload: the kernel trusts them.  A set belongs to the decoder geometry it was built for (n_patches,
+    n_inp, padded width, field grouping); Decode.sensor_sse refuses another.  affine: None, or (scales [K], shifts [K]) — the forward scaling x * a + b of
+    every sensor's field into the decoder's scaled units, which scale_values / scale_sigma apply (they raise without it); points: None, or the K mesh
+    point ids the sensors sit at, kept for the caller.  MeshUnpatcher.sensor_set passes both."""
+
+    def __init__(self, decoder, n_patches: int, patch, cell, field, affine=None, points=None):
+        what = "SensorSet"
+        if not isinstance(n_patches, int) or isinstance(n_patches, bool) or n_patches < 1:
+            raise ValueError(f"{what}: n_patches = {n_patches!r} must be a positive integer")
+        patch, cell, field = _int_list(patch, "patch", what), _int_list(cell, "cell", what), _int_list(field, "field", what)
+        K = len(patch)
+        if len(cell) != K or len(field) != K:
+            raise ValueError(f"{what}: patch, cell and field must have equal lengths, got {K}, {len(cell)}, {len(field)}")
+        groups = tuple(tuple(int(f) for f in g) for g in decoder.field_groups)
+        where = {}                      # field id -> (group, position in the group, position in the decoder's output)
+        pos = 0
+        for g, grp in enumerate(groups):
+            for j, f in enumerate(grp):
+                where[f] = (g, j, pos)
+                pos += 1
+        C_, Cp = int(decoder.n_inp), int(decoder._n_inp_p)
+        for k in range(K):
+            if not 0 <= patch[k] < n_patches:
+                raise ValueError(f"{what}: sensor {k}: patch {patch[k]} outside 0 .. {n_patches - 1}")
+            if not 0 <= cell[k] < C_:
+                raise ValueError(f"{what}: sensor {k}: cell {cell[k]} outside 0 .. n_inp - 1 = {C_ - 1}")
+            if field[k] not in where:
+                raise ValueError(f"{what}: sensor {k}: field {field[k]} is not one of the decoder's fields {sorted(where)}")
+        self.n_patches, self.n_inp, self.Cp, self.groups, self.K = n_patches, C_, Cp, groups, K
+        self.patch, self.cell, self.field = patch, cell, field
+        self.out_field = [where[f][2] for f in field]            # the field's position in the decoder's output (and in a per-field sigma)
+        G, T = len(groups), N.SENSOR_TILE
+        buckets = {}
+        for k in range(K):
+            buckets.setdefault((where[field[k]][0], patch[k]), []).append(k)
+        self.patches = sorted(set(patch))
+        Q = len(self.patches)
+        if Q > N.SENSOR_MAX_PATCHES:
+            raise ValueError(f"{what}: {Q} observed patches; a set carries at most {N.SENSOR_MAX_PATCHES}")
+        perm, wrow, live, seg = [], [], [], []
+        for g in range(G):
+            row = []
+            for p in self.patches:
+                row.append(len(perm))
+                ks = buckets.get((g, p), [])
+                for k in ks:
+                    perm.append(k)
+                    wrow.append(where[field[k]][1] * Cp + cell[k])
+                    live.append(1)
+                pad = -len(ks) % T
+                perm += [0] * pad
+                wrow += [0] * pad
+                live += [0] * pad
+            row.append(len(perm))
+            seg.append(row)
+        self.K_pad, self.Q = len(perm), Q
+        inv = [0] * K
+        for s, (k, l) in enumerate(zip(perm, live)):
+            if l:
+                inv[k] = s
+        # the kernel trusts these: check them here
+        for g in range(G):
+            for qi in range(Q):
+                a, b = seg[g][qi], seg[g][qi + 1]
+                if not 0 <= a <= b <= self.K_pad or (b - a) % T:
+                    raise ValueError(f"{what}: internal error: segment ({g}, {qi}) = [{a}, {b}) is not a multiple of {T} inside 0 .. {self.K_pad}")
+                for s in range(a, b):
+                    if not 0 <= wrow[s] < len(groups[g]) * Cp or not 0 <= perm[s] < K:
+                        raise ValueError(f"{what}: internal error: entry {s}: W2 row {wrow[s]} or sensor {perm[s]} out of range")
+        if self.K_pad < T or self.K_pad >= 2 ** 31 or sum(live) != K:
+            raise ValueError(f"{what}: internal error: K_pad = {self.K_pad}, {sum(live)} live entries for {K} sensors")
+        self.perm, self.wrow, self.live, self.seg, self.inv = perm, wrow, live, seg, inv
+        self._dev = {}
+        if affine is not None and (len(affine) != 2 or len(affine[0]) != K or len(affine[1]) != K):
+            raise ValueError(f"{what}: affine must be a pair of {K} scales and {K} shifts (one per sensor)")
+        if points is not None and len(points) != K:
+            raise ValueError(f"{what}: points must name one mesh point per sensor ({K}), got {len(points)}")
+        self._affine = None if affine is None else ([float(v) for v in affine[0]], [float(v) for v in affine[1]])
+        self.points = None if points is None else [int(v) for v in points]
+        self._affine_dev = {}
+        dev = next(iter(decoder.parameters())).device
+        if dev.type == "cuda":
+            self.tables(dev)
+
+    def matches(self, decoder, n_patches: int) -> bool:
+        return (self.n_patches == n_patches and self.n_inp == int(decoder.n_inp) and self.Cp == int(decoder._n_inp_p)
+                and self.groups == tuple(tuple(int(f) for f in g) for g in decoder.field_groups))
+
+    def tables(self, device):
+        """The tables on `device` (uploaded once per device): a dict perm, wrow, live, seg (int32), patches, inv, patch, cell, out_field (int64)."""
+        device = torch.device(device)
+        t = self._dev.get(device)
+        if t is None:
+            i32 = lambda v: torch.tensor(v, dtype=torch.int32, device=device)   # noqa: E731
+            i64 = lambda v: torch.tensor(v, dtype=torch.int64, device=device)   # noqa: E731
+            t = dict(perm=i32(self.perm), wrow=i32(self.wrow), live=i32(self.live), seg=i32(self.seg), patches=i64(self.patches), inv=i64(self.inv),
+                     patch=i64(self.patch), cell=i64(self.cell), out_field=i64(self.out_field))
+            self._dev[device] = t
+        return t
+
+    def _coeffs(self, device):
+        if self._affine is None:
+            raise ValueError("SensorSet: this set was not built from a mesh (MeshUnpatcher.sensor_set): it has no field scaling")
+        device = torch.device(device)
+        t = self._affine_dev.get(device)
+        if t is None:
+            t = (torch.tensor(self._affine[0], dtype=torch.float32, device=device), torch.tensor(self._affine[1], dtype=torch.float32, device=device))
+            self._affine_dev[device] = t
+        return t
+
+    def scale_values(self, v: torch.Tensor) -> torch.Tensor:
+        """Physical sensor readings [..., K] -> the decoder's scaled units: v * a_f + b_f with the forward affine of sensor k's field, the coefficients
+        patchify_and_scale applies (float32)."""
+        if not torch.is_tensor(v) or v.dim() < 1 or v.shape[-1] != self.K:
+            raise ValueError(f"SensorSet.scale_values: need a tensor [..., {self.K}], got {tuple(v.shape) if torch.is_tensor(v) else type(v).__name__}")
+        a, b = self._coeffs(v.device)
+        return v.to(torch.float32) * a + b
+
+    def scale_sigma(self, s: torch.Tensor) -> torch.Tensor:
+        """Physical standard deviations [..., K] -> scaled units: s * |a_f|."""
+        if not torch.is_tensor(s) or s.dim() < 1 or s.shape[-1] != self.K:
+            raise ValueError(f"SensorSet.scale_sigma: need a tensor [..., {self.K}], got {tuple(s.shape) if torch.is_tensor(s) else type(s).__name__}")
+        a, _ = self._coeffs(s.device)
+        return s.to(torch.float32) * a.abs()
+
+
+class SensorLikelihood:
+    """Gaussian log-likelihood of sparse sensor readings, per ensemble member: like(y, obs, precision=None) -> log-weights [B * members] (f32, device),
+    ready for systematic_resample.
+
+    y: what RolloutSession.step returns for B * members trajectories, [B * members, n_groups, P * D] (member j of history b at row b * members + j);
+    obs: float32 [B, K] on y's device, the readings in the sensors' given order, in the decoder's scaled units (SensorSet.scale_values);
+    precision: None (1), or float32 [K] or [B, K] on y's device, finite and >= 0 — a weight per reading; 0 marks a missing reading: it is neutral
+    whatever obs holds there, NaN and Inf included.  A precision on the device is not read back (a negative or NaN entry there counts as 0); one on
+    the host is checked.  sigma: None (1), a positive number, n_fields numbers (one per field in the decoder's output order; taken so when K equals
+    n_fields) or K numbers (one per sensor), folded once into a per-sensor precision 1 / sigma^2 that multiplies the call's precision; a sigma given
+    on the device is read when the object is built.  logw = -0.5 * sum_k w_k (y_k - obs_k)^2 (Decode.sensor_sse).  fused: None (Decode.sensor_sse's
+    rule), True (the fused launch; bf16 only) or False (the composed path).  A call reads nothing back from the device and uploads nothing, once the
+    sensor set's tables and the folded sigma are on the device (the first call on a device uploads them).  `decoder` is a sea_amd Decode; no
+    autograd graph is built."""
+
+    def __init__(self, decoder, n_patches: int, members: int, sensors: SensorSet, sigma=None, fused: Optional[bool] = None):
+        if not isinstance(n_patches, int) or isinstance(n_patches, bool) or n_patches < 1:
+            raise ValueError(f"SensorLikelihood: n_patches = {n_patches!r} must be a positive integer")
+        if not isinstance(members, int) or isinstance(members, bool) or members < 1:
+            raise ValueError(f"SensorLikelihood: members = {members!r} must be a positive integer")
+        if not isinstance(sensors, SensorSet):
+            raise ValueError(f"SensorLikelihood: sensors must be a SensorSet, got {type(sensors).__name__}")
+        if not sensors.matches(decoder, n_patches):
+            raise ValueError("SensorLikelihood: the SensorSet was built for another decoder geometry (n_patches, n_inp, padded cell width or field grouping)")
+        self.decoder, self.n_patches, self.members, self.sensors, self.fused = decoder, n_patches, members, sensors, fused
+        n_fields, K = sum(len(g) for g in decoder.field_groups), sensors.K
+        if sigma is None:
+            self._prec_host = None
+        else:
+            s = torch.as_tensor(sigma, dtype=torch.float64).detach().cpu()   # a tensor given on the device comes to the host once, here
+            if s.dim() > 1 or (s.dim() == 1 and s.numel() not in (n_fields, K)):
+                raise ValueError(f"SensorLikelihood: sigma must be None, a number, {n_fields} numbers (one per field) or {K} numbers (one per sensor), "
+                                 f"got shape {tuple(s.shape)}")
+            if not bool(torch.isfinite(s).all()) or not bool((s > 0).all()):
+                raise ValueError(f"SensorLikelihood: sigma must be finite and positive, got {s.tolist()}")
+            p = 1.0 / (s * s)
+            if p.dim() == 0:
+                self._prec_host = [float(p)] * K
+            elif p.numel() == n_fields:
+                self._prec_host = [float(p[f]) for f in sensors.out_field]
+            else:
+                self._prec_host = [float(v) for v in p]
+        self._prec = {}
+        dev = next(iter(decoder.parameters())).device
+        if dev.type == "cuda":
+            self._sigma_precision(dev)
+
+    def _sigma_precision(self, device):
+        if self._prec_host is None:
+            return None
+        t = self._prec.get(device)
+        if t is None:
+            t = self._prec[device] = torch.tensor(self._prec_host, dtype=torch.float32, device=device)
+        return t
+
+    def __call__(self, y: torch.Tensor, obs: torch.Tensor, precision: Optional[torch.Tensor] = None) -> torch.Tensor:
+        P = self.n_patches
+        if not torch.is_tensor(y) or y.dim() != 3 or y.shape[-1] % P or y.shape[0] < 1:
+            raise ValueError(f"SensorLikelihood: y must be [B * members, n_groups, n_patches * D] with n_patches = {P}, got "
+                             f"{tuple(y.shape) if torch.is_tensor(y) else type(y).__name__}")
+        Bm, G, E = y.shape
+        if Bm % self.members:
+            raise ValueError(f"SensorLikelihood: the {Bm} trajectories of y are not a multiple of members = {self.members}")
+        z = y.reshape(Bm, G, P, E // P).permute(0, 2, 1, 3)          # the re-layout of FieldLikelihood
+        _check_sensor_operands("SensorLikelihood", obs, precision, Bm // self.members, self.sensors.K, y.device)
+        sp = self._sigma_precision(y.device) if y.is_cuda else None
+        if sp is not None:
+            precision = sp if precision is None else precision * sp
+        wsse = self.decoder.sensor_sse(z, self.sensors, obs, precision=precision, members=self.members, fused=self.fused)
+        return -0.5 * wsse
+
+
+def _check_sensor_operands(what: str, obs, precision, B: int, K: int, device) -> None:
+    """obs float32 [B, K] and precision None / float32 [K] / [B, K], both on `device`; a precision on the host is also checked for finite, non-negative values
+    (one on the device is not read back)."""
+    if not torch.is_tensor(obs) or obs.dim() != 2 or tuple(obs.shape) != (B, K):
+        raise ValueError(f"{what}: obs must be a [{B}, {K}] tensor (one row of readings per history, in the sensors' given order), got "
+                         f"{tuple(obs.shape) if torch.is_tensor(obs) else type(obs).__name__}")
+    if obs.dtype != torch.float32 or obs.device != device:
+        raise ValueError(f"{what}: obs must be float32 on {device}, got {obs.dtype} on {obs.device}")
+    if precision is not None:
+        if not torch.is_tensor(precision) or tuple(precision.shape) not in ((K,), (B, K)):
+            raise ValueError(f"{what}: precision must be None or a [{K}] or [{B}, {K}] tensor, got "
+                             f"{tuple(precision.shape) if torch.is_tensor(precision) else type(precision).__name__}")
+        if precision.dtype != torch.float32:
+            raise ValueError(f"{what}: precision must be float32, got {precision.dtype}")
+        if precision.device.type == "cpu" and (not bool(torch.isfinite(precision).all()) or not bool((precision >= 0).all())):
+            raise ValueError(f"{what}: precision must be finite and >= 0")
+        if precision.device != device:
+            raise ValueError(f"{what}: precision is on {precision.device}, the states on {device}")

@@ -273,6 +273,80 @@ class Decode(nn.Module):
             bias = self._shadow[3]
             return ops.decode_member_sse([dict(H=hid[g], W2=W2[g], bias=bias[g]) for g in range(G)], t3, C, self._n_inp_p, P, members=members, counts=cnt, dtype=dt)
 
+    def sensor_sse(self, z: torch.Tensor, sensors, obs: torch.Tensor, precision: Optional[torch.Tensor] = None, members: int = 1,
+                   fused: Optional[bool] = None, predictions: bool = False):
+        """Precision-weighted squared error of every ensemble member against SPARSE observations: fp32 [Bm], sum_k w_k (y_k - obs[b, k])^2 over the K
+        sensors of `sensors` (a sea_amd.ensemble.SensorSet built for this decoder: sensor k reads decoded field field[k] at cell cell[k] of patch
+        patch[k]); no autograd graph.  z [Bm, P, n_groups, embed_dim], member j of history b at row b * members + j; obs float32 [Bm / members, K] on
+        z's device in the sensors' given order; precision None (1) or float32 [K] or [Bm / members, K], finite and >= 0: a sensor with w == 0 is
+        neutral by a select whatever obs holds there, NaN and Inf included (a precision on the host is checked; one on the device is not read back —
+        a negative or NaN entry there counts as 0).  predictions=True: returns (wsse, pred) with pred fp32 [Bm, K], the decoded value of every member
+        at every sensor in the given order (the innovation is pred - obs).
+        bf16 compute dtype, fused: the z rows of the observed patches gathered patch-major, the first-layer launch over those Q * Bm rows only, ONE
+        fused launch (sea_decode_sensor_sse) and its finish launch — neither the decoded fields nor the unobserved patches' hidden rows exist; obs and
+        precision come into the sorted, padded order of the set by one index_select each.  fp32, or fused=False: forward(), a gather of its output at
+        the sensors, torch reductions (the composed path).  fused=None: the fused path in bf16 — it never does more arithmetic than the composed one
+        (K columns against every cell), and no measured size has the composed path ahead (tools/sensor_bench.py, profiles/sensor_bench.txt, DESIGN.md section 7f;
+        64 members x 64 patches, 16 - 4096 sensors: one history 0.10 - 0.12 ms fused against 0.12 - 0.14 ms composed, level within the windows' spread in two
+        rows; four histories 0.10 - 0.14 against 0.21 - 0.29 ms; 0.5 - 46 MB of extra memory against 84 - 348 MB).  A call with device inputs reads nothing back and
+        uploads nothing once the set's tables are on the device."""
+        from ..ensemble import SensorSet, _check_sensor_operands
+
+        if z.dim() != 4 or z.shape[2] != self.num_groups or z.shape[3] != self.embed_dim:
+            raise ValueError(f"sea_amd.Decode.sensor_sse: z must be [Bm, P, {self.num_groups}, {self.embed_dim}], got {tuple(z.shape)}")
+        Bm, P = z.shape[0], z.shape[1]
+        if not isinstance(members, int) or isinstance(members, bool) or members < 1 or Bm < 1 or Bm % members:
+            raise ValueError(f"sea_amd.Decode.sensor_sse: members = {members!r} must be a positive integer that divides the {Bm} rows of z")
+        B = Bm // members
+        if not isinstance(sensors, SensorSet):
+            raise ValueError(f"sea_amd.Decode.sensor_sse: sensors must be a SensorSet, got {type(sensors).__name__}")
+        if not sensors.matches(self, P):
+            raise ValueError(f"sea_amd.Decode.sensor_sse: the SensorSet was built for n_patches {sensors.n_patches}, n_inp {sensors.n_inp} (padded {sensors.Cp}), "
+                             f"field groups {sensors.groups}; this call has n_patches {P}, n_inp {self.n_inp} (padded {self._n_inp_p}), field groups {self.field_groups}")
+        K = sensors.K
+        _check_sensor_operands("sea_amd.Decode.sensor_sse", obs, precision, B, K, z.device)
+        dt = self._act_dtype()
+        if fused is None:
+            fused = dt == torch.bfloat16
+        if fused and dt != torch.bfloat16:
+            raise ValueError("sea_amd.Decode.sensor_sse: the fused launch is bf16 only (set_compute_dtype('bf16'), or fused=False)")
+        N.require_gpu(z, "Decode.sensor_sse input")
+        T = sensors.tables(z.device)
+        with torch.no_grad():
+            obs = obs.detach()
+            prec = None if precision is None else precision.detach()
+            if not fused:
+                y = self.forward(z.detach())                                              # [Bm, P, n_fields, C]
+                pred = y[:, T["patch"], T["out_field"], T["cell"]]                         # [Bm, K]
+                o = obs.unsqueeze(1).expand(B, members, K).reshape(Bm, K)
+                if prec is None:
+                    d = pred - o
+                    wsse = (d * d).sum(1)
+                else:
+                    w = prec.view(1, 1, K).expand(B, members, K) if prec.dim() == 1 else prec.unsqueeze(1).expand(B, members, K)
+                    w = w.reshape(Bm, K)
+                    zero = torch.zeros((), device=z.device)
+                    live = w > 0
+                    w = torch.where(live, w, zero)
+                    d = torch.where(live, pred - o, zero)
+                    wsse = (w * d * d).sum(1)
+                return (wsse, pred.contiguous()) if predictions else wsse
+            G, D, Q = self.num_groups, self.embed_dim, sensors.Q
+            zq = z.detach().index_select(1, T["patches"]).to(torch.float32).permute(1, 0, 2, 3).contiguous().view(Q * Bm, G * D)   # patch-major: row q * Bm + bm
+            za = torch.empty(Q * Bm, G * D, device=z.device, dtype=dt)
+            ops.convert(zq, za)
+            W1, W2 = self._weights(dt)
+            hid = [torch.empty(Q * Bm, self.MLP_hidden, device=z.device, dtype=dt) for _ in range(G)]
+            ops.gemm_grouped([dict(A=za[:, g * D:(g + 1) * D], W=W1[g], Cact=hid[g], act=1) for g in range(G)], dt)
+            bias = self._shadow[3]
+            obs_s = obs.index_select(1, T["perm"])                                         # [B, K_pad]: sorted, padded (a pad entry repeats sensor 0 and is not live)
+            prec_s = None if prec is None else prec.index_select(prec.dim() - 1, T["perm"])
+            out = ops.decode_sensor_sse([dict(H=hid[g], W2=W2[g], bias=bias[g]) for g in range(G)], obs_s, T["live"], T["wrow"], T["seg"], self._n_inp_p,
+                                        members=members, prec=prec_s, predictions=predictions, dtype=dt)
+            if not predictions:
+                return out
+            return out[0], out[1].index_select(1, T["inv"])
+
     def member_moments(self, z: torch.Tensor, members: int, weights: Optional[torch.Tensor] = None, counts=None, unbiased: bool = False,
                        fused: Optional[bool] = None):
         """The forecast of an ensemble: (mean, var) of the decoded fields over the `members` members of every history, each fp32 [B, P, n_fields, n_inp]

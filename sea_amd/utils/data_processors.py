@@ -108,18 +108,48 @@ class MeshUnpatcher:
         self._scale = torch.tensor(scale, device=dev, dtype=torch.float32)
         self._shift = torch.tensor(shift, device=dev, dtype=torch.float32)
 
+    def _forward_coefficients(self):
+        """(scale, shift) per field of the forward scaling x -> x * scale + shift (identity without scalers): what patchify_and_scale applies."""
+        F = sum(len(g) for g in self.field_groups)
+        scale, shift = [1.0] * F, [0.0] * F
+        for g, sc in zip(self.field_groups, self.scalers):
+            a, b = sc.forward_affine()
+            for f in g:
+                scale[f], shift[f] = a, b
+        return scale, shift
+
+    def sensor_set(self, decoder, points, fields):
+        """Point sensors on the mesh as a sea_amd.ensemble.SensorSet for `decoder`: sensor k reads field fields[k] at mesh point points[k] (integer
+        sequences or tensors of equal length).  The (patch, cell) of a point comes from the partitioner's point -> slot table (slot = patch * C +
+        cell; the table comes to the host once, here); a decoder whose n_inp is below the mesh's slots per patch is refused.  The decoder lives in scaled units, so the set carries scale_values(v) — the forward affine
+        of every sensor's field, the coefficients patchify_and_scale applies — and scale_sigma(s) = s * |a_f| for readings and standard deviations
+        in physical units."""
+        from ..ensemble import SensorSet, _int_list
+
+        pts = _int_list(points, "points", "sensor_set")
+        flds = _int_list(fields, "fields", "sensor_set")
+        if len(pts) != len(flds):
+            raise ValueError(f"sensor_set: points and fields must have equal lengths, got {len(pts)} and {len(flds)}")
+        slot = self.partitioner.point_slot.detach().cpu().tolist()
+        P, C = self.partitioner.padded_index_map.shape
+        if int(decoder.n_inp) < C:
+            raise ValueError(f"sensor_set: the decoder's cell width n_inp = {decoder.n_inp} is below the mesh's {C} slots per patch: it decodes another partition")
+        scale, shift = self._forward_coefficients()
+        for k, (pt, f) in enumerate(zip(pts, flds)):
+            if not 0 <= pt < len(slot):
+                raise ValueError(f"sensor_set: sensor {k}: mesh point {pt} outside 0 .. {len(slot) - 1}")
+            if not 0 <= f < len(scale):
+                raise ValueError(f"sensor_set: sensor {k}: field {f} outside the mesh's {len(scale)} fields")
+        return SensorSet(decoder, int(P), [slot[pt] // C for pt in pts], [slot[pt] % C for pt in pts], flds,
+                         affine=([scale[f] for f in flds], [shift[f] for f in flds]), points=pts)
+
     def patchify_and_scale(self, data: torch.Tensor, layout: str = "BPCF", c_out: Optional[int] = None) -> torch.Tensor:
         """The forward leg (reference MeshProcessor.patchify_and_scale, utils/data_processors.py:484-526, with fitted scalers): data [T, N, F] ->
         scaled, partitioned, padded fields [T, P, C, F] (layout "BPCF", the reference's) or [T, P, F, c_out] ("BPFC", what the encoder reads) in ONE
         launch of sea_patchify; padded slots hold pad_field_value, unscaled, as in the reference."""
         N.require_gpu(data, "data")
         if not hasattr(self, "_fscale"):
-            F = sum(len(g) for g in self.field_groups)
-            scale, shift = [1.0] * F, [0.0] * F
-            for g, sc in zip(self.field_groups, self.scalers):
-                a, b = sc.forward_affine()
-                for f in g:
-                    scale[f], shift[f] = a, b
+            scale, shift = self._forward_coefficients()
             dev = self.partitioner.device
             self._fscale = torch.tensor(scale, device=dev, dtype=torch.float32)
             self._fshift = torch.tensor(shift, device=dev, dtype=torch.float32)
@@ -248,6 +278,13 @@ class MeshProcessor:
         if self._unpatcher is None:
             raise ValueError("call patchify_and_scale first (it builds the partition)")
         return self._unpatcher.unpatch_spread(std_fields.to(self.device), layout=layout)
+
+    def sensor_set(self, decoder, points, fields):
+        """Point sensors on the mesh (mesh point ids and field ids) as a SensorSet for `decoder`, with scale_values / scale_sigma for readings in
+        physical units (MeshUnpatcher.sensor_set)."""
+        if self._unpatcher is None:
+            raise ValueError("call patchify_and_scale first (it builds the partition)")
+        return self._unpatcher.sensor_set(decoder, points, fields)
 
     def decode_and_unpatch(self, decoder, z: torch.Tensor) -> torch.Tensor:
         """decoder(z) + inverse_scale_and_unpatch(..., layout="BPFC") in one go, the decoder run only over a cell's mesh points (MeshUnpatcher.decode_and_unpatch):
