@@ -1140,6 +1140,49 @@ typedef struct {
 int sea_decode_sensor_sse(const SeaDecodeMseGroup* groups, int n_groups, const SeaDecodeSensorSse* p, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * The sparse-sensor score WITH its gradient to the hidden rows of the observed patches, in one launch for all field groups (plus the finish launch of
+ * sea_decode_sensor_sse): what nudging, 3D-Var corrections, gradient moves of resampled duplicates and sensor terms of a training loss need.  It
+ * replaces Decode.forward under autograd, a gather of K values and the backward of an [M, n_fields * Cp] output gradient that is zero outside K
+ * columns of the observed patches (reference models/encoder_decoder.py: the decoder MLP's second Linear and its backward, run over all P patches).
+ * Tables, obs, prec, live, wrow, seg, wsse, pred, work and the SeaDecodeMseGroup operands H, W2, bias, ldh, ldw, n_fields are those of
+ * sea_decode_sensor_sse; dH and lddh are OUTPUT; Z and ldz are nullable and read.  H, Z and dH are [Q * Bm, S], patch-major: row q * Bm + bm.  For sorted
+ * position k of group g in observed patch q, member bm of history b = bm / members:
+ *     y[bm, k]   = sum_s H_g[q * Bm + bm, s] W2_g[wrow[k], s] + bias_g[wrow[k]]                       (fp32 accumulation, as sea_decode_sensor_sse)
+ *     w          = live[k] != 0 and prec[b * ld_prec + k] > 0 ? prec[b * ld_prec + k] : 0              (prec == NULL: 1)
+ *     d          = w > 0 ? y[bm, k] - obs[b * ld_obs + k] : 0          (a select: NaN / Inf in obs is neutral without weight)
+ *     wsse[bm]   = sum_k (w d) d                                        (fp32; the same order as sea_decode_sensor_sse)
+ *     pred[bm * K_pad + k] = y[bm, k]                                   (when pred != NULL)
+ *     r          = act(w d)                                             (rounded ONCE between the two products, as sea_decode_mse rounds its residual)
+ *     dH_g[q * Bm + bm, s] = 2 grad_scale * sum_{k in segment (g, q), ascending} r[bm, k] W2_g[wrow[k], s]     [* gelu_erf'(Z_g[q * Bm + bm, s]) when Z != NULL]
+ * dH is written in the act dtype; EVERY element of rows [0, Q * Bm) by columns [0, S) is written, the rows of an empty (group, patch) segment as exact
+ * zeros.  One writer per dH element, no atomics, the tiles of a segment accumulated in ascending order: two runs give the same bits, and a member's dH
+ * rows and score do not depend on `members`, on the number of histories or on the row tile the member falls into.  wsse and pred equal what
+ * sea_decode_sensor_sse writes for the same operands bit for bit (the same accumulator layout, per-lane order, butterfly and finish launch).
+ * The kernel TRUSTS wrow and seg exactly as sea_decode_sensor_sse does: the caller range-checks them on the host before the upload (SensorSet).
+ * Requirements: those of sea_decode_sensor_sse — and per group dH non-NULL and 16-byte aligned, lddh a multiple of 8 and >= S; Z NULL, or 16-byte
+ * aligned with ldz a multiple of 8 and >= S; grad_scale finite.  SEA_F32 returns SEA_EUNSUPPORTED; so does S > 640.
+ * Returns -1, with the entry point and the offending group named in sea_last_error(), otherwise; nothing touches a device before the checks pass.
+ * One kernel form ("sensor_grad.rows64" in sea_last_form): 64 members per workgroup, 4 waves of 16 members, SP / 8 fragment registers and SP / 4 fp32
+ * dH accumulators per lane (sea_amd/csrc/decode_loss.hip).
+ * (An addition to ABI version 8.  sea_struct_sizes() keeps its 33 entries, SeaKvFork last: sizeof(SeaDecodeSensorGrad) is 120.)
+ */
+typedef struct {
+    const float* obs;        /* as SeaDecodeSensorSse */
+    const float* prec;
+    const int32_t* live;
+    const int32_t* wrow;
+    const int32_t* seg;
+    float* wsse;             /* f32 [Bm] (output) */
+    float* pred;             /* f32 [Bm, K_pad] (output) or NULL */
+    float* work;             /* f32 [work_cap] workspace, >= Q * n_groups * Bm */
+    int64_t ld_obs, ld_prec, work_cap;
+    int32_t Bm, members, S, Cp, Q, K_pad;
+    float grad_scale;        /* dH = 2 grad_scale * (...) */
+    int32_t pad_;
+} SeaDecodeSensorGrad;
+int sea_decode_sensor_grad(const SeaDecodeMseGroup* groups, int n_groups, const SeaDecodeSensorGrad* p, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Systematic resampling of an ensemble, gated by the effective sample size, in one launch: log-weights in, the int32 device index that
  * sea_kv_cache_gather (RolloutSession.resample / select) takes out.  G histories with n members each, one workgroup per history, all sums in fp64.
  * Per history g (member j is element g n + j):

@@ -1121,3 +1121,254 @@ extern "C" int sea_decode_sensor_sse(const SeaDecodeMseGroup* groups, int n_grou
     SEA_CHECK_LAUNCH("sea_decode_sensor_sse");
     return SEA_OK;
 }
+
+// ------------------------------------------------------------------------------------------------------------------------------------------------
+// sea_decode_sensor_grad: the sparse-sensor score WITH its gradient to the hidden rows of the observed patches — decode_sensor_sse_kernel (gathered W2
+// tiles, patch-major hidden rows, precision-weighted epilogue) crossed with the second MFMA stage of decode_mse_kernel.  The workgroup, the waves, the
+// H fragments, the two LDS images [32][SP] with the pitch of 2 SP + 32 bytes, the prefetch of tile t + 1 before the MFMAs of tile t and the one barrier
+// per tile are those of the two parents.  Per tile and wave:
+//   stage 1  exactly decode_sensor_sse_kernel's: the same accumulators (bias through the row table, even / odd k-steps), the same per-lane order of the
+//            sum, the same butterfly, the same work slot and the same finish launch — wsse and pred are that kernel's bits,
+//   between  r = bf16(w d), rounded ONCE: the lane's 2 x 4 weighted residuals are the A fragment of stage 2 with k-slot (g, j) = tile row 4 g + j or
+//            16 + 4 g + j - 4, as in decode_mse_kernel (a sensor without weight has w d = 0 by the select: its W2 row is multiplied by an exact zero),
+//   stage 2  dH[bm, s] += sum_k r[bm, k] W2[wrow[k], s]: the SAME gathered image read column-wise (two ds_read_b64_tr_b16 per 16 hidden columns).
+// A wave carries SP / 8 fragment registers and SP / 4 fp32 dH accumulators per lane, the budget of decode_mse_kernel (one wave per SIMD at SP = 640).
+// The tiles of a segment are accumulated in ascending order into registers and stored once: dH row q Bm + bm, columns [0, S), has one writer; the
+// workgroup of an EMPTY segment stores zeros there (and its zero partial) and then leaves, before any barrier.  A row of an MFMA result depends on its
+// own operand row only, so a member's dH rows and score do not depend on `members`, on the number of histories or on the row tile it falls into.
+// The kernel trusts wrow and seg exactly as decode_sensor_sse_kernel does.
+struct SensorGradLaunch {
+    SeaDecodeMseGroup g[SEA_DECODE_MSE_MAX_GROUPS];
+    SeaDecodeSensorGrad p;
+};
+
+template <int SP>
+__global__ __launch_bounds__(256) void decode_sensor_grad_kernel(const SensorGradLaunch L) {
+#pragma clang fp reassociate(off)   // the lane's sum runs over its sensors in the stated order
+    constexpr int NT = 256;
+    constexpr int KS = SP / 32;
+    constexpr int ST = SP / 16;
+    constexpr int PITCH = SP * 2 + DM_PAD;
+    constexpr int TILE = DM_TC * PITCH;
+    constexpr int NCH = SP * 4 / NT;
+    static_assert(NCH * NT == DM_TC * (SP / 8), "whole chunks per thread");
+    extern __shared__ __attribute__((aligned(16))) char smem[];   // 2 tile images
+
+    const SeaDecodeMseGroup& G = L.g[blockIdx.z];
+    const SeaDecodeSensorGrad& P = L.p;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, lg = lane >> 4;
+    const int Bm = P.Bm, S = P.S;
+    const int q = blockIdx.y, n_g = gridDim.z;
+    const int row0 = blockIdx.x * DM_ROWS + wave * 16;
+    const int bm = row0 + li;   // the member this lane holds in the H fragments, in the stage-1 result and in the residual fragment
+    float* const wslot = P.work + ((int64_t)q * n_g + blockIdx.z) * Bm + (bm < Bm ? bm : 0);
+    __bf16* dH = static_cast<__bf16*>(G.dH);
+
+    const int seg0 = P.seg[(int64_t)blockIdx.z * (P.Q + 1) + q], seg1 = P.seg[(int64_t)blockIdx.z * (P.Q + 1) + q + 1];
+    const int n_tiles = (seg1 - seg0) / DM_TC;
+    if (n_tiles <= 0) {   // uniform over the workgroup, before any barrier: no sensor of this group in this patch — zero rows, a zero partial
+        if (lg == 0 && bm < Bm) *wslot = 0.f;
+        const int mrows = Bm - blockIdx.x * DM_ROWS < DM_ROWS ? Bm - blockIdx.x * DM_ROWS : DM_ROWS;
+        const int cpr = S / 8;   // 16-byte chunks of a row (S % 8 == 0, lddh % 8 == 0, dH 16-byte aligned)
+        for (int i = tid; i < mrows * cpr; i += NT) {
+            const int r = i / cpr, ch = i - r * cpr;
+            *reinterpret_cast<uint4*>(dH + ((int64_t)q * Bm + blockIdx.x * DM_ROWS + r) * G.lddh + ch * 8) = make_uint4(0u, 0u, 0u, 0u);
+        }
+        return;
+    }
+
+    const __bf16* H = static_cast<const __bf16*>(G.H);
+    const __bf16* W2 = static_cast<const __bf16*>(G.W2);
+    const uint4 zero4 = make_uint4(0u, 0u, 0u, 0u);
+    uint4 hf[KS];
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+        const int s = ks * 32 + 8 * lg;
+        hf[ks] = (bm < Bm && s < S) ? *reinterpret_cast<const uint4*>(H + ((int64_t)q * Bm + bm) * G.ldh + s) : zero4;
+    }
+    f32x4 dh[ST];
+#pragma unroll
+    for (int st = 0; st < ST; ++st) dh[st] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int b = bm < Bm ? bm / P.members : 0;   // the lane's history: a row beyond Bm reads history 0 and stores nothing
+    const float* orow = P.obs + (int64_t)b * P.ld_obs;
+    const float* prow = P.prec != nullptr ? P.prec + (int64_t)b * P.ld_prec : nullptr;
+    float* drow = P.pred != nullptr && bm < Bm ? P.pred + (int64_t)bm * P.K_pad : nullptr;
+
+    uint4 wr[NCH];
+    ds_load_tile_gathered<SP, NT>(wr, W2, G.ldw, S, P.wrow + seg0, tid);
+    dm_store_tile<SP, NT>(wr, smem, tid);
+    __syncthreads();
+
+    float fsum = 0.f;
+    typedef dm_s16x4 __attribute__((address_space(3))) * lds_p;
+    for (int t = 0; t < n_tiles; ++t) {
+        const char* buf = smem + (t & 1) * TILE;
+        const int k0 = seg0 + t * DM_TC;   // sorted position of the tile's first sensor
+        if (t + 1 < n_tiles) ds_load_tile_gathered<SP, NT>(wr, W2, G.ldw, S, P.wrow + k0 + DM_TC, tid);
+
+        // stage 1, as decode_sensor_sse_kernel
+        float ob[2][4], pw[2][4];
+        f32x4 acc[2][2];
+#pragma unroll
+        for (int sub = 0; sub < 2; ++sub) {
+            const int k = k0 + sub * 16 + 4 * lg;
+            const float4 o = *reinterpret_cast<const float4*>(orow + k);
+            ob[sub][0] = o.x; ob[sub][1] = o.y; ob[sub][2] = o.z; ob[sub][3] = o.w;
+            float4 pv = make_float4(1.f, 1.f, 1.f, 1.f);
+            if (prow != nullptr) pv = *reinterpret_cast<const float4*>(prow + k);
+            pw[sub][0] = pv.x; pw[sub][1] = pv.y; pw[sub][2] = pv.z; pw[sub][3] = pv.w;
+            f32x4 bv;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                pw[sub][r] = (P.live[k + r] != 0 && pw[sub][r] > 0.f) ? pw[sub][r] : 0.f;
+                bv[r] = G.bias[P.wrow[k + r]];
+            }
+            acc[sub][0] = bv;
+            acc[sub][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+            if (ks * 32 < S) {
+#pragma unroll
+                for (int sub = 0; sub < 2; ++sub) {
+                    const uint4 a = *reinterpret_cast<const uint4*>(buf + (sub * 16 + li) * PITCH + (ks * 4 + lg) * 16);
+                    mma16<__bf16>(a, hf[ks], acc[sub][ks & 1]);
+                }
+            }
+        }
+
+        // score, predictions, and the weighted residual rounded once
+        bf16x8 dfr;
+#pragma unroll
+        for (int sub = 0; sub < 2; ++sub) {
+            float y[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                y[r] = acc[sub][0][r] + acc[sub][1][r];
+                const float w = pw[sub][r];
+                const float d = w > 0.f ? y[r] - ob[sub][r] : 0.f;
+                const float wd = w * d;
+                fsum = __builtin_fmaf(wd, d, fsum);
+                dfr[sub * 4 + r] = (__bf16)wd;
+            }
+            if (drow != nullptr) *reinterpret_cast<float4*>(drow + k0 + sub * 16 + 4 * lg) = make_float4(y[0], y[1], y[2], y[3]);
+        }
+        const uint4 da = __builtin_bit_cast(uint4, dfr);
+
+        // stage 2, as decode_mse_kernel
+        const char* tb = buf + (4 * lg + (li >> 2)) * PITCH + (4 * (li & 3)) * 2;
+#pragma unroll
+        for (int st = 0; st < ST; ++st) {
+            if (st * 16 < S) {
+                const dm_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(tb + st * 32));
+                const dm_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(tb + st * 32 + 16 * PITCH));
+                const uint2 l2 = __builtin_bit_cast(uint2, lo), h2 = __builtin_bit_cast(uint2, hi);
+                mma16<__bf16>(da, make_uint4(l2.x, l2.y, h2.x, h2.y), dh[st]);
+            }
+        }
+
+        if (t + 1 < n_tiles) dm_store_tile<SP, NT>(wr, smem + ((t + 1) & 1) * TILE, tid);
+        __syncthreads();
+    }
+
+    // dH: register r of tile st is member row0 + 4 g + r, column 16 st + (lane & 15)
+    const float scale = 2.0f * P.grad_scale;
+    const __bf16* Z = static_cast<const __bf16*>(G.Z);
+#pragma unroll
+    for (int st = 0; st < ST; ++st) {
+        const int s = st * 16 + li;
+        if (s < S) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int mr = row0 + 4 * lg + r;
+                if (mr < Bm) {
+                    const int64_t row = (int64_t)q * Bm + mr;
+                    float v = dh[st][r] * scale;
+                    if (Z != nullptr) v *= gelu_grad_for<__bf16>((float)Z[row * G.ldz + s]);
+                    dH[row * G.lddh + s] = (__bf16)v;
+                }
+            }
+        }
+    }
+
+    // fold the member's four lanes, one writer
+    float v = fsum;
+    v += __shfl_xor(v, 16);
+    v += __shfl_xor(v, 32);
+    if (lg == 0 && bm < Bm) *wslot = v;
+}
+
+template <int SP>
+static void sensor_grad_launch(const SensorGradLaunch& L, dim3 grid, hipStream_t s) {
+    constexpr int lds = 2 * DM_TC * (SP * 2 + DM_PAD);
+    static bool set_on[64] = {false};   // per device: SP = 640 needs 84 kB, above the 64 kB a kernel gets without the attribute
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = -1;
+    if (dev < 0 || !set_on[dev]) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(decode_sensor_grad_kernel<SP>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        if (dev >= 0) set_on[dev] = true;
+    }
+    decode_sensor_grad_kernel<SP><<<grid, dim3(256), lds, s>>>(L);
+}
+
+extern "C" int sea_decode_sensor_grad(const SeaDecodeMseGroup* groups, int n_groups, const SeaDecodeSensorGrad* p, int dtype, void* stream) {
+    SEA_REQUIRE(groups != nullptr && p != nullptr, "sea_decode_sensor_grad: null argument table");
+    SEA_REQUIRE(n_groups >= 1 && n_groups <= SEA_DECODE_MSE_MAX_GROUPS, "sea_decode_sensor_grad: n_groups=%d outside 1..%d", n_groups, SEA_DECODE_MSE_MAX_GROUPS);
+    SEA_REQUIRE(dtype == SEA_F32 || dtype == SEA_BF16, "sea_decode_sensor_grad: bad dtype %d", dtype);
+    if (dtype != SEA_BF16) {
+        sea_set_error("sea_decode_sensor_grad: unsupported: bf16 only (the fp32 decoder composes sea_gemm_grouped, a gather and reductions under autograd)");
+        return SEA_EUNSUPPORTED;
+    }
+    const SeaDecodeSensorGrad& P = *p;
+    SEA_REQUIRE(P.obs != nullptr && P.live != nullptr && P.wrow != nullptr && P.seg != nullptr && P.wsse != nullptr && P.work != nullptr,
+                "sea_decode_sensor_grad: null obs, live, wrow, seg, wsse or work pointer");
+    SEA_REQUIRE(P.Bm >= 1 && P.members >= 1 && P.Bm % P.members == 0, "sea_decode_sensor_grad: Bm=%d must be a positive multiple of members=%d", P.Bm, P.members);
+    SEA_REQUIRE(P.S >= 8 && P.S % 8 == 0, "sea_decode_sensor_grad: S=%d must be a positive multiple of 8", P.S);
+    SEA_REQUIRE(P.Cp >= 32 && P.Cp % 32 == 0, "sea_decode_sensor_grad: Cp=%d must be a positive multiple of 32", P.Cp);
+    SEA_REQUIRE(P.K_pad >= 32 && P.K_pad % 32 == 0, "sea_decode_sensor_grad: K_pad=%d must be a positive multiple of 32", P.K_pad);
+    SEA_REQUIRE(P.Q >= 1 && P.Q <= 65535, "sea_decode_sensor_grad: Q=%d observed patches outside 1..65535", P.Q);
+    SEA_REQUIRE(P.ld_obs >= P.K_pad && P.ld_obs % 4 == 0, "sea_decode_sensor_grad: obs row stride ld_obs=%lld must cover K_pad=%d and be a multiple of 4", (long long)P.ld_obs, P.K_pad);
+    SEA_REQUIRE(P.prec == nullptr || P.ld_prec == 0 || (P.ld_prec >= P.K_pad && P.ld_prec % 4 == 0),
+                "sea_decode_sensor_grad: prec row stride ld_prec=%lld must be 0 (one row for all histories) or cover K_pad=%d and be a multiple of 4", (long long)P.ld_prec, P.K_pad);
+    SEA_REQUIRE(sea_aligned16(P.obs) && sea_aligned16(P.prec) && sea_aligned16(P.pred), "sea_decode_sensor_grad: obs, prec and pred must be 16-byte aligned");
+    SEA_REQUIRE(sea_aligned4(P.live) && sea_aligned4(P.wrow) && sea_aligned4(P.seg) && sea_aligned4(P.wsse) && sea_aligned4(P.work),
+                "sea_decode_sensor_grad: misaligned live, wrow, seg, wsse or work pointer");
+    uint32_t gs_bits;
+    memcpy(&gs_bits, &P.grad_scale, sizeof(gs_bits));
+    SEA_REQUIRE((gs_bits & 0x7f800000u) != 0x7f800000u, "sea_decode_sensor_grad: grad_scale must be finite");   // the exponent field itself: no floating-point compare to reason about
+    for (int g = 0; g < n_groups; ++g) {
+        const SeaDecodeMseGroup& G = groups[g];
+        SEA_REQUIRE(G.H != nullptr && G.W2 != nullptr && G.bias != nullptr && G.dH != nullptr, "sea_decode_sensor_grad: group %d: null pointer (H, W2, bias or dH)", g);
+        SEA_REQUIRE(sea_aligned16(G.H) && sea_aligned16(G.W2) && sea_aligned16(G.bias) && sea_aligned16(G.dH) && sea_aligned16(G.Z),
+                    "sea_decode_sensor_grad: group %d: pointers must be 16-byte aligned", g);
+        SEA_REQUIRE(G.ldh >= P.S && G.ldh % 8 == 0 && G.ldw >= P.S && G.ldw % 8 == 0,
+                    "sea_decode_sensor_grad: group %d: row strides ldh=%d ldw=%d must cover S=%d and be multiples of 8", g, G.ldh, G.ldw, P.S);
+        SEA_REQUIRE(G.lddh >= P.S && G.lddh % 8 == 0 && (G.Z == nullptr || (G.ldz >= P.S && G.ldz % 8 == 0)),
+                    "sea_decode_sensor_grad: group %d: row strides lddh=%d ldz=%d must cover S=%d and be multiples of 8", g, G.lddh, G.ldz, P.S);
+        SEA_REQUIRE(G.n_fields >= 1 && (int64_t)G.n_fields * P.Cp <= 0x7fffffffLL / 2, "sea_decode_sensor_grad: group %d: n_fields=%d", g, G.n_fields);
+    }
+    if (P.S > 640) {
+        sea_set_error("sea_decode_sensor_grad: unsupported: hidden width S=%d above 640", P.S);
+        return SEA_EUNSUPPORTED;
+    }
+    const int64_t row_blocks = ((int64_t)P.Bm + DM_ROWS - 1) / DM_ROWS;
+    const int64_t need = (int64_t)P.Q * n_groups * P.Bm;
+    SEA_REQUIRE(row_blocks <= 0x7fffffffLL && (int64_t)P.Q * P.Bm <= 0x7fffffffLL, "sea_decode_sensor_grad: too many rows");
+    SEA_REQUIRE(P.work_cap >= need, "sea_decode_sensor_grad: workspace of %lld floats is too small: %lld needed (Q * n_groups * Bm)", (long long)P.work_cap, (long long)need);
+
+    SensorGradLaunch L;
+    memset(&L, 0, sizeof(L));
+    for (int g = 0; g < n_groups; ++g) L.g[g] = groups[g];
+    L.p = P;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)row_blocks, (unsigned)P.Q, (unsigned)n_groups);
+    if (P.S <= 128) sensor_grad_launch<128>(L, grid, s);
+    else if (P.S <= 256) sensor_grad_launch<256>(L, grid, s);
+    else if (P.S <= 384) sensor_grad_launch<384>(L, grid, s);
+    else if (P.S <= 512) sensor_grad_launch<512>(L, grid, s);
+    else sensor_grad_launch<640>(L, grid, s);
+    sea_note_form("sensor_grad.rows64", 0, 0);
+    sensor_sse_finish_kernel<<<dim3((unsigned)((P.Bm + 255) / 256)), dim3(256), 0, s>>>(P.work, P.wsse, P.Bm, (int)((int64_t)P.Q * n_groups));
+    SEA_CHECK_LAUNCH("sea_decode_sensor_grad");
+    return SEA_OK;
+}

@@ -24,9 +24,13 @@ the dense snapshot through SensorSet and SensorLikelihood:
     like = SensorLikelihood(decoder, n_patches, members=n, sensors=sensors, sigma=sensors.scale_sigma(sigma_phys))
     logw = like(y, sensors.scale_values(readings), precision)     # [B * n]: Decode.sensor_sse — the first layer over the observed patches only, then ONE
                                                                   # launch (sea_decode_sensor_sse) over the sensors' rows of the second layer
+    logw, dlogw_dy = like.score_and_grad(y, obs, precision)       # the same log-weights and the gradient of every member's own log-weight, in y's layout:
+                                                                  # Decode.sensor_loss's launches (sea_decode_sensor_grad), no autograd graph
+    y = ens.step(c_next, state=like.nudge(y, obs, precision, rate=0.25))   # one gradient step towards the readings as the corrected state
 """
 from __future__ import annotations
 
+import math
 from typing import Optional
 
 import torch
@@ -380,7 +384,8 @@ class SensorLikelihood:
     on the device is read when the object is built.  logw = -0.5 * sum_k w_k (y_k - obs_k)^2 (Decode.sensor_sse).  fused: None (Decode.sensor_sse's
     rule), True (the fused launch; bf16 only) or False (the composed path).  A call reads nothing back from the device and uploads nothing, once the
     sensor set's tables and the folded sigma are on the device (the first call on a device uploads them).  `decoder` is a sea_amd Decode; no
-    autograd graph is built."""
+    autograd graph is built.  score_and_grad(y, obs, precision) adds the gradient of every member's own log-weight with respect to its state, and
+    nudge(y, obs, precision, rate) takes one gradient step along it."""
 
     def __init__(self, decoder, n_patches: int, members: int, sensors: SensorSet, sigma=None, fused: Optional[bool] = None):
         if not isinstance(n_patches, int) or isinstance(n_patches, bool) or n_patches < 1:
@@ -437,6 +442,51 @@ class SensorLikelihood:
             precision = sp if precision is None else precision * sp
         wsse = self.decoder.sensor_sse(z, self.sensors, obs, precision=precision, members=self.members, fused=self.fused)
         return -0.5 * wsse
+
+
+    def score_and_grad(self, y: torch.Tensor, obs: torch.Tensor, precision: Optional[torch.Tensor] = None):
+        """(logw [Bm], dlogw_dy [Bm, n_groups, P * D] fp32): __call__'s log-weights (the same bits on the fused path) and the gradient of every member's
+        OWN log-weight with respect to its state, in y's layout (the inverse of the re-layout __call__ applies) — Decode.sensor_loss's one pass.  On the
+        fused path no graph is built; nothing is read back, and nothing is uploaded after the first call on a device."""
+        P = self.n_patches
+        if not torch.is_tensor(y) or y.dim() != 3 or y.shape[-1] % P or y.shape[0] < 1:
+            raise ValueError(f"SensorLikelihood: y must be [B * members, n_groups, n_patches * D] with n_patches = {P}, got "
+                             f"{tuple(y.shape) if torch.is_tensor(y) else type(y).__name__}")
+        Bm, G, E = y.shape
+        if Bm % self.members:
+            raise ValueError(f"SensorLikelihood: the {Bm} trajectories of y are not a multiple of members = {self.members}")
+        _check_sensor_operands("SensorLikelihood", obs, precision, Bm // self.members, self.sensors.K, y.device)
+        sp = self._sigma_precision(y.device) if y.is_cuda else None
+        if sp is not None:
+            precision = sp if precision is None else precision * sp
+        dec = self.decoder
+        fused = self.fused if self.fused is not None else dec._act_dtype() == torch.bfloat16
+        z = y.detach().reshape(Bm, G, P, E // P).permute(0, 2, 1, 3)
+        if fused:
+            if dec._act_dtype() != torch.bfloat16:
+                raise ValueError("SensorLikelihood: the fused launch is bf16 only (set_compute_dtype('bf16'), or fused=False)")
+            N.require_gpu(y, "SensorLikelihood.score_and_grad input")
+            wsse, _, dz = dec._sensor_grad_fused(z, self.sensors, obs.detach(), None if precision is None else precision.detach(), self.members, False, True)
+        else:
+            with torch.enable_grad():
+                zz = z.to(torch.float32).contiguous().requires_grad_(True)
+                wsse = dec.sensor_loss(zz, self.sensors, obs, precision=precision, members=self.members, fused=False)
+                (dz,) = torch.autograd.grad(wsse.sum(), zz)
+                wsse = wsse.detach()
+        return -0.5 * wsse, (-0.5 * dz.to(torch.float32)).permute(0, 2, 1, 3).reshape(Bm, G, E)
+
+    def nudge(self, y: torch.Tensor, obs: torch.Tensor, precision: Optional[torch.Tensor] = None, rate=1.0) -> torch.Tensor:
+        """y + rate * dlogw_dy, in y's dtype: one gradient step on every member's log-likelihood of the readings — a corrected state for
+        RolloutSession.step(c, state=...).  rate: a number, or a float32 [Bm] tensor on y's device (one step length per member)."""
+        if torch.is_tensor(rate):
+            if not torch.is_tensor(y) or rate.dim() != 1 or rate.shape[0] != y.shape[0] or rate.dtype != torch.float32 or rate.device != y.device:
+                raise ValueError(f"SensorLikelihood.nudge: a rate tensor must be float32 [{y.shape[0] if torch.is_tensor(y) else 'Bm'}] on the states' device, got "
+                                 f"{tuple(rate.shape)} {rate.dtype} on {rate.device}")
+            rate = rate.detach().view(-1, 1, 1)
+        elif isinstance(rate, bool) or not isinstance(rate, (int, float)) or not math.isfinite(rate):
+            raise ValueError(f"SensorLikelihood.nudge: rate must be a finite number or a float32 [Bm] tensor, got {rate!r}")
+        _, grad = self.score_and_grad(y, obs, precision)
+        return (y.detach().to(torch.float32) + rate * grad).to(y.dtype)
 
 
 def _check_sensor_operands(what: str, obs, precision, B: int, K: int, device) -> None:

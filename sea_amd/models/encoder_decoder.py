@@ -347,6 +347,95 @@ class Decode(nn.Module):
                 return out
             return out[0], out[1].index_select(1, T["inv"])
 
+    def sensor_loss(self, z: torch.Tensor, sensors, obs: torch.Tensor, precision: Optional[torch.Tensor] = None, members: int = 1,
+                    fused: Optional[bool] = None, predictions: bool = False):
+        """sensor_sse WITH a gradient to z: the precision-weighted squared error of every member against sparse observations, fp32 [Bm], as a
+        differentiable tensor — gradient flows to z only (the decoder is a frozen observation operator: a parameter that requires grad is refused; obs
+        and precision must not require grad).  Arguments as sensor_sse.  predictions=True: returns (wsse, pred) with pred fp32 [Bm, K], which carries
+        no gradient.  wsse[bm] depends on z[bm] alone, so d (sum_bm c_bm wsse[bm]) / dz[bm] = c_bm d wsse[bm] / dz[bm]: this is what nudging, a
+        3D-Var correction or a gradient move of resampled duplicates differentiates.
+        bf16 compute dtype, fused: the z rows of the observed patches gathered patch-major, the first-layer launch over those Q * Bm rows with the
+        pre-activation kept, ONE fused launch (sea_decode_sensor_grad: the score — sensor_sse's bits — and the gradient of the pre-activation, the
+        weighted residual rounded to bf16 once between the two products) and its finish launch, the data-gradient launch against W1^T over Q * Bm
+        rows, and one index_copy_ into a zeroed [Bm, P, n_groups, embed_dim]: the gradient at an unobserved patch, and at the slice of a group without
+        sensors in a patch, is exactly 0.  Forward and backward are one pass, as in mse_loss: the backward scales the stored dz by the upstream
+        gradient of every member.  fp32, or fused=False: forward() under autograd, a gather at the sensors and torch reductions (the composed path;
+        its backward runs over all P patches).  fused=None: the fused path in bf16 — it never does more arithmetic than the composed one, and no
+        measured size has the composed path ahead (tools/sensor_grad_bench.py, profiles/sensor_grad_bench.txt; 64 members x 64
+        patches, 16 - 4096 sensors over 4 - 64 patches, loss + backward: one history 0.23 - 0.29 ms fused against 0.40 - 0.68 ms composed, four
+        histories 0.23 - 0.33 against 0.83 - 0.97 ms, every row outside the windows' spread; 1.5 - 127 MB of extra memory against 206 - 846 MB; the
+        score alone, sensor_sse, takes 0.09 - 0.12 ms).  A call with device inputs reads nothing back and uploads nothing once the set's tables
+        are on the device."""
+        from ..ensemble import SensorSet, _check_sensor_operands
+
+        what = "sea_amd.Decode.sensor_loss"
+        if z.dim() != 4 or z.shape[2] != self.num_groups or z.shape[3] != self.embed_dim:
+            raise ValueError(f"{what}: z must be [Bm, P, {self.num_groups}, {self.embed_dim}], got {tuple(z.shape)}")
+        Bm, P = z.shape[0], z.shape[1]
+        if not isinstance(members, int) or isinstance(members, bool) or members < 1 or Bm < 1 or Bm % members:
+            raise ValueError(f"{what}: members = {members!r} must be a positive integer that divides the {Bm} rows of z")
+        B = Bm // members
+        if not isinstance(sensors, SensorSet):
+            raise ValueError(f"{what}: sensors must be a SensorSet, got {type(sensors).__name__}")
+        if not sensors.matches(self, P):
+            raise ValueError(f"{what}: the SensorSet was built for n_patches {sensors.n_patches}, n_inp {sensors.n_inp} (padded {sensors.Cp}), "
+                             f"field groups {sensors.groups}; this call has n_patches {P}, n_inp {self.n_inp} (padded {self._n_inp_p}), field groups {self.field_groups}")
+        K = sensors.K
+        _check_sensor_operands(what, obs, precision, B, K, z.device)
+        if torch.is_grad_enabled() and (obs.requires_grad or (precision is not None and precision.requires_grad)):
+            raise ValueError(f"{what}: obs and precision must not require grad (gradients flow to z only)")
+        self._require_frozen("sensor_loss")
+        dt = self._act_dtype()
+        if fused is None:
+            fused = dt == torch.bfloat16
+        if fused and dt != torch.bfloat16:
+            raise ValueError(f"{what}: the fused launch is bf16 only (set_compute_dtype('bf16'), or fused=False)")
+        N.require_gpu(z, "Decode.sensor_loss input")
+        obs = obs.detach()
+        prec = None if precision is None else precision.detach()
+        if fused:
+            out = _DecodeSensorFn.apply(z, self, sensors, obs, prec, members, predictions)
+            return (out[0], out[1]) if predictions else out
+        T = sensors.tables(z.device)
+        y = _DecodeFn.apply(z, self)                                                  # [Bm, P, n_fields, C]
+        pred = y[:, T["patch"], T["out_field"], T["cell"]]                             # [Bm, K]
+        o = obs.unsqueeze(1).expand(B, members, K).reshape(Bm, K)
+        if prec is None:
+            d = pred - o
+            wsse = (d * d).sum(1)
+        else:
+            w = prec.view(1, 1, K).expand(B, members, K) if prec.dim() == 1 else prec.unsqueeze(1).expand(B, members, K)
+            w = w.reshape(Bm, K)
+            zero = torch.zeros((), device=z.device)
+            live = w > 0
+            w = torch.where(live, w, zero)
+            d = torch.where(live, pred - o, zero)
+            wsse = (w * d * d).sum(1)
+        return (wsse, pred.detach().contiguous()) if predictions else wsse
+
+    def _sensor_grad_fused(self, z: torch.Tensor, sensors, obs: torch.Tensor, prec: Optional[torch.Tensor], members: int, predictions: bool, want_grad: bool):
+        """The fused bf16 launches of sensor_loss on checked arguments, without autograd: (wsse [Bm], pred [Bm, K] or None, dz f32 [Bm, P, G, D] or None)."""
+        dt = torch.bfloat16
+        with torch.no_grad():
+            Bm, P, G, D = z.shape
+            T, Q = sensors.tables(z.device), sensors.Q
+            zq = z.detach().index_select(1, T["patches"]).permute(1, 0, 2, 3)            # [Q, Bm, G, D] patch-major: row q * Bm + bm
+            hid, pre = self._first_layer(zq, dt)
+            _, W2 = self._weights(dt)
+            bias = self._shadow[3]
+            dpre = [torch.empty(Q * Bm, self.MLP_hidden, device=z.device, dtype=dt) for _ in range(G)]
+            obs_s = obs.index_select(1, T["perm"])                                         # [B, K_pad]: sorted, padded (a pad entry repeats sensor 0 and is not live)
+            prec_s = None if prec is None else prec.index_select(prec.dim() - 1, T["perm"])
+            wsse, pred = ops.decode_sensor_grad([dict(H=hid[g], W2=W2[g], bias=bias[g], dH=dpre[g], Z=pre[g]) for g in range(G)], obs_s, T["live"], T["wrow"],
+                                                T["seg"], self._n_inp_p, members=members, prec=prec_s, predictions=predictions, dtype=dt)
+            if pred is not None:
+                pred = pred.index_select(1, T["inv"])
+            dz = None
+            if want_grad:
+                dz = torch.zeros(Bm, P, G, D, device=z.device, dtype=torch.float32)
+                dz.index_copy_(1, T["patches"], self._input_grad(dpre, dt).view(Q, Bm, G, D).permute(1, 0, 2, 3))
+            return wsse, pred, dz
+
     def member_moments(self, z: torch.Tensor, members: int, weights: Optional[torch.Tensor] = None, counts=None, unbiased: bool = False,
                        fused: Optional[bool] = None):
         """The forecast of an ensemble: (mean, var) of the decoded fields over the `members` members of every history, each fp32 [B, P, n_fields, n_inp]
@@ -542,6 +631,27 @@ class _DecodeMseFn(torch.autograd.Function):
     def backward(ctx, g):
         (dz,) = ctx.saved_tensors
         return dz * g, None, None, None, None
+
+
+class _DecodeSensorFn(torch.autograd.Function):
+    """Decode.sensor_loss on the fused path (Decode._sensor_grad_fused): first layer over the observed patches' rows (pre-activation kept),
+    sea_decode_sensor_grad (score and pre-activation gradient in one launch), data-gradient launch against W1^T, one index_copy_ into the zeroed dz.
+    Forward and backward are one pass, as in _DecodeMseFn: wsse[bm] depends on z[bm] only, so the backward scales the stored dz per member."""
+
+    @staticmethod
+    def forward(ctx, z, dec, sensors, obs, prec, members, predictions):
+        wsse, pred, dz = dec._sensor_grad_fused(z, sensors, obs, prec, members, predictions, ctx.needs_input_grad[0])
+        if dz is not None:
+            ctx.save_for_backward(dz.to(z.dtype))
+        if not predictions:
+            return wsse
+        ctx.mark_non_differentiable(pred)
+        return wsse, pred
+
+    @staticmethod
+    def backward(ctx, g, *unused):
+        (dz,) = ctx.saved_tensors
+        return (dz * g.view(-1, 1, 1, 1)).to(dz.dtype), None, None, None, None, None, None
 
 
 def _round_up(x: int, m: int) -> int:

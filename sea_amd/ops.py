@@ -9,6 +9,7 @@ same fillers once per plan for the whole-model path.
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Dict, Optional, Sequence
 
 import torch
@@ -1142,6 +1143,95 @@ def decode_sensor_sse(groups: Sequence[Dict], obs: torch.Tensor, live: torch.Ten
     fill_decode_sensor_sse(arr, P, groups, obs, prec, live, wrow, seg, members, Cp, wsse, pred, work)
     N.check(N.lib().sea_decode_sensor_sse(arr, len(groups), C.byref(P), N.dtype_code(dtype), N.stream_ptr()), "sea_decode_sensor_sse")
     return (wsse, pred) if predictions else wsse
+
+
+def fill_decode_sensor_grad(groups_arr, P: N.SeaDecodeSensorGrad, groups: Sequence[Dict], obs, prec, live, wrow, seg, members: int, Cp: int, wsse, pred, work,
+                            grad_scale: float) -> None:
+    """The argument table of sea_decode_sensor_grad.  groups: dicts H act [Q * Bm, S] (patch-major: row q * Bm + bm), W2 act [n_fields * Cp, S], bias f32
+    [n_fields * Cp], dH act [Q * Bm, S] (output) and Z act [Q * Bm, S] or None (absent).  The rest as fill_decode_sensor_sse."""
+    field0 = 0
+    for g, d in zip(groups_arr, groups):
+        H, W2, dH, Z = d["H"], d["W2"], d["dH"], d.get("Z")
+        g.H, g.W2, g.bias, g.dH, g.Z = H.data_ptr(), W2.data_ptr(), d["bias"].data_ptr(), dH.data_ptr(), N.ptr(Z)
+        g.ldh, g.ldw, g.lddh, g.ldz = H.stride(0), W2.stride(0), dH.stride(0), (Z.stride(0) if Z is not None else 0)
+        g.n_fields, g.field0 = W2.shape[0] // Cp, field0
+        field0 += g.n_fields
+    P.obs, P.prec, P.live, P.wrow, P.seg = obs.data_ptr(), N.ptr(prec), live.data_ptr(), wrow.data_ptr(), seg.data_ptr()
+    P.wsse, P.pred, P.work = wsse.data_ptr(), N.ptr(pred), work.data_ptr()
+    P.ld_obs, P.ld_prec, P.work_cap = obs.stride(0), (prec.stride(0) if prec is not None and prec.dim() == 2 else 0), work.numel()
+    P.Bm, P.members, P.S, P.Cp, P.Q, P.K_pad = wsse.shape[0], members, groups[0]["H"].shape[1], Cp, seg.shape[1] - 1, live.shape[0]
+    P.grad_scale = grad_scale
+
+
+def decode_sensor_grad(groups: Sequence[Dict], obs: torch.Tensor, live: torch.Tensor, wrow: torch.Tensor, seg: torch.Tensor, Cp: int, members: int = 1,
+                       prec: Optional[torch.Tensor] = None, predictions: bool = False, grad_scale: float = 1.0, dtype: torch.dtype = torch.bfloat16):
+    """sea_decode_sensor_grad: decode_sensor_sse's score (the same bits) and, in the same launch, its gradient to the hidden rows: every group's dH act
+    [Q * Bm, S] is written IN PLACE with 2 grad_scale * (w d rounded to bf16) W2 [* gelu'(Z) where the group carries a Z], zeros at the rows of a
+    (group, patch) pair without sensors.  Returns (wsse f32 [Bm], pred f32 [Bm, K_pad] or None).  groups as fill_decode_sensor_grad; the tables and obs /
+    prec as decode_sensor_sse.  Everything is checked on the host before the launch."""
+    what = "decode_sensor_grad"
+    if dtype != torch.bfloat16:
+        raise ValueError(f"{what}: the fused launch is bf16 only, got {dtype}")
+    if not groups or len(groups) > N.DECODE_MSE_MAX_GROUPS:
+        raise ValueError(f"{what}: {len(groups)} groups; a launch carries 1 .. {N.DECODE_MSE_MAX_GROUPS}")
+    if Cp < 32 or Cp % 32:
+        raise ValueError(f"{what}: need Cp a multiple of 32, got Cp = {Cp}")
+    if isinstance(grad_scale, bool) or not isinstance(grad_scale, (int, float)) or not math.isfinite(grad_scale):
+        raise ValueError(f"{what}: grad_scale = {grad_scale!r} must be a finite number")
+    dev = obs.device
+    if seg.dim() != 2 or seg.shape[0] != len(groups) or seg.shape[1] < 2 or seg.dtype != torch.int32 or not seg.is_contiguous() or seg.device != dev:
+        raise ValueError(f"{what}: seg must be a contiguous int32 [{len(groups)}, Q + 1 >= 2] on {dev}, got {tuple(seg.shape)} {seg.dtype} on {seg.device}")
+    Q = seg.shape[1] - 1
+    if Q > N.SENSOR_MAX_PATCHES:
+        raise ValueError(f"{what}: {Q} observed patches; a launch carries 1 .. {N.SENSOR_MAX_PATCHES}")
+    for name, t in (("live", live), ("wrow", wrow)):
+        if t.dim() != 1 or t.dtype != torch.int32 or not t.is_contiguous() or t.device != dev or t.shape[0] != live.shape[0]:
+            raise ValueError(f"{what}: {name} must be a contiguous int32 [K_pad] on {dev}, got {tuple(t.shape)} {t.dtype} on {t.device}")
+    K_pad = live.shape[0]
+    if K_pad < N.SENSOR_TILE or K_pad % N.SENSOR_TILE:
+        raise ValueError(f"{what}: K_pad = {K_pad} must be a positive multiple of {N.SENSOR_TILE}")
+    R, S = tuple(groups[0]["H"].shape) if groups[0]["H"].dim() == 2 else (0, 0)
+    if R < 1 or R % Q or S < 8 or S % 8 or S > N.DECODE_MSE_MAX_S:
+        raise ValueError(f"{what}: H must be [Q * Bm, S] with Q = {Q} and S a multiple of 8 up to {N.DECODE_MSE_MAX_S}, got {tuple(groups[0]['H'].shape)}")
+    Bm = R // Q
+    if not isinstance(members, int) or members < 1 or Bm % members:
+        raise ValueError(f"{what}: members = {members!r} must be a positive integer that divides Bm = {Bm}")
+    B = Bm // members
+    for i, d in enumerate(groups):
+        for name in ("H", "W2", "dH", "Z"):
+            t = d.get(name)
+            if t is None and name == "Z":
+                continue
+            if t is None or t.dim() != 2 or t.stride(1) != 1:
+                raise ValueError(f"{what} group {i}: {name}: need a 2-D tensor with unit inner stride, got "
+                                 f"{'None' if t is None else f'shape {tuple(t.shape)} strides {t.stride()}'}")
+            if t.dtype != dtype or t.device != dev or t.shape[1] != S or (name != "W2" and t.shape[0] != R):
+                raise ValueError(f"{what} group {i}: {name} must be a {dtype} [{'n_fields * Cp' if name == 'W2' else R}, {S}] tensor on {dev}, got "
+                                 f"{tuple(t.shape)} {t.dtype} on {t.device}")
+            if t.stride(0) % 8 or t.stride(0) < S or t.data_ptr() % 16:
+                raise ValueError(f"{what} group {i}: {name} needs a row stride that is a multiple of 8 and covers S = {S}, and a 16-byte-aligned base (stride {t.stride(0)})")
+        W2, b = d["W2"], d["bias"]
+        if W2.shape[0] < Cp or W2.shape[0] % Cp:
+            raise ValueError(f"{what} group {i}: W2 has {W2.shape[0]} rows, not a multiple of Cp = {Cp}")
+        if b.dtype != torch.float32 or b.dim() != 1 or b.shape[0] != W2.shape[0] or not b.is_contiguous() or b.device != dev or b.data_ptr() % 16:
+            raise ValueError(f"{what} group {i}: bias must be a contiguous, 16-byte-aligned float32 [{W2.shape[0]}] on {dev}, got {tuple(b.shape)} {b.dtype}")
+    if obs.dtype != torch.float32 or obs.dim() != 2 or tuple(obs.shape) != (B, K_pad) or obs.stride(1) != 1 or obs.stride(0) % 4 or obs.stride(0) < K_pad \
+            or obs.data_ptr() % 16:
+        raise ValueError(f"{what}: obs must be a 16-byte-aligned float32 [{B}, {K_pad}] with unit inner stride and a row stride that is a multiple of 4, "
+                         f"got {tuple(obs.shape)} {obs.dtype} strides {obs.stride()}")
+    if prec is not None:
+        if prec.dtype != torch.float32 or prec.device != dev or tuple(prec.shape) not in ((K_pad,), (B, K_pad)) or prec.stride(-1) != 1 or prec.data_ptr() % 16 \
+                or (prec.dim() == 2 and (prec.stride(0) % 4 or prec.stride(0) < K_pad)):
+            raise ValueError(f"{what}: prec must be None or a 16-byte-aligned float32 [{K_pad}] or [{B}, {K_pad}] on {dev} with unit inner stride, got "
+                             f"{tuple(prec.shape)} {prec.dtype} strides {prec.stride()} on {prec.device}")
+    N.require_gpu(obs, f"{what} obs")   # every operand is on the observation's device (checked above)
+    wsse = torch.empty(Bm, device=dev, dtype=torch.float32)
+    pred = torch.empty(Bm, K_pad, device=dev, dtype=torch.float32) if predictions else None
+    work = torch.empty(Q * len(groups) * Bm, device=dev, dtype=torch.float32)
+    arr, P = (N.SeaDecodeMseGroup * len(groups))(), N.SeaDecodeSensorGrad()
+    fill_decode_sensor_grad(arr, P, groups, obs, prec, live, wrow, seg, members, Cp, wsse, pred, work, float(grad_scale))
+    N.check(N.lib().sea_decode_sensor_grad(arr, len(groups), C.byref(P), N.dtype_code(dtype), N.stream_ptr()), "sea_decode_sensor_grad")
+    return wsse, pred
 
 
 def fill_decode_member_moments(groups_arr, P: N.SeaDecodeMemberMoments, groups: Sequence[Dict], weights, var_scale, counts, n_patches: int, members: int, C_: int,
