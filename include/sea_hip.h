@@ -1200,6 +1200,60 @@ int sea_decode_sensor_grad(const SeaDecodeMseGroup* groups, int n_groups, const 
  */
 int sea_resample_systematic(const float* logw, const float* u, float ess_frac, int G, int n, int32_t* index, float* logw_out, float* ess, int32_t* resampled,
                             void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Ensemble Kalman analysis from sensor readings, in ensemble space, in two launches (the deterministic EnKF of Sakov & Oke 2008; no random numbers).
+ * B histories with N members each (member j of history b is row b N + j), K sensors, Ld analysis domains.  sea_enkf_transform turns the members'
+ * predictions into one [N, N] matrix D per (history, domain); sea_ensemble_mix applies it to the latent states.  Per history b and domain d:
+ *     w_k    = (prec_k > 0 ? prec_k : 0) * (taper[d, k] > 0 ? taper[d, k] : 0)     selects: a reading without weight is neutral whatever obs holds
+ *                                                                                  there, NaN and Inf included (prec NULL: 1; taper NULL: 1, Ld = 1)
+ *     ybar_k = mean_j pred[j, k]
+ *     S[j,k] = rho (pred[j, k] - ybar_k) sqrt(w_k / (N - 1))                       0 where w_k = 0, by a select
+ *     dl_k   = sqrt(w_k) (obs_k - ybar_k)                                          0 where w_k = 0, by a select
+ *     C = S S^T [N, N],  v = S dl [N],  W = (I + C)^-1                             fp64 throughout; I + C is SPD with eigenvalues >= 1: Cholesky
+ *                                                                                  without pivoting, then the inverse in LAPACK's potrf, trtri, lauum order
+ *     G = (W v) 1^T / sqrt(N - 1) - alpha (I - W)
+ *     D = (rho - 1) Pi + rho Pi G,  Pi = I - 1 1^T / N                             Pi G: G with every column's mean over i removed
+ * and the analysed state of member j is y[j] + sum_i D[i, j] y[i] per latent element: its member mean is xbar + K (obs - H xbar) and its anomalies
+ * are A - alpha K H A, K the ensemble Kalman gain of the rho-inflated forecast.  Without a live reading and with rho = 1, D is exactly 0.
+ * D f32 [B, Ld, N, N] and status int32 [B, Ld] are written in full: status = the number of live sensors (w_k > 0), or -1 when a live operand is not
+ * finite or a pivot is not a positive finite number — D is then all zeros for that problem (no update).  One workgroup per (domain, history), every
+ * sum in a fixed order given by (N, K) alone: two runs give the same bits, and a problem's bits do not depend on the other problems of the launch.
+ * Requirements: pred, obs, D, status non-NULL, 4-byte aligned; B in 1 .. 65535; N >= 2 (above 128: SEA_EUNSUPPORTED); K >= 1; Ld >= 1, Ld = 1 without
+ * a taper; ld_pred, ld_obs, ld_taper >= K; ld_prec = 0 (one row [K] for all histories) or >= K; rho finite and >= 1; alpha in [0, 1].  Returns -1 with
+ * the entry point named in sea_last_error() otherwise, before any device is touched.  Notes the form "enkf.transform" (a = the register block edge
+ * 1, 2, 4 or 8; b = the dynamic LDS bytes).  (An addition to ABI version 8; the struct is not in sea_struct_sizes().)
+ */
+typedef struct {
+    const float* pred;       /* f32 [B N, ld_pred]: pred[b N + j, k], the decoded value of member j at sensor k (Decode.sensor_sse's predictions) */
+    const float* obs;        /* f32 [B, ld_obs] */
+    const float* prec;       /* NULL (1), f32 [K] (ld_prec = 0) or f32 [B, ld_prec] */
+    const float* taper;      /* NULL (1; Ld = 1) or f32 [Ld, ld_taper] */
+    float* D;                /* f32 [B, Ld, N, N] */
+    int32_t* status;         /* int32 [B, Ld] */
+    int64_t ld_pred, ld_obs, ld_prec, ld_taper;
+    double rho, alpha;
+    int32_t B, N, K, Ld;
+} SeaEnkfTransform;          /* 112 bytes */
+int sea_enkf_transform(const SeaEnkfTransform* p, void* stream);
+
+/* out[b N + j, g, p, :] = y[b N + j, g, p, :] + sum_i D[b, dom(p), i, j] y[b N + i, g, p, :], dom(p) = 0 when Ld = 1 and p when Ld = P.
+ * y act [Bm, G, P Dl] (contiguous; what RolloutSession.step returns), D f32 [Bm / N, Ld, N, N]; the sum is accumulated in fp32 over i in ascending
+ * order, one writer per element.  inc (f32, same shape, may be NULL) receives the sum alone; out (act, may be NULL) receives y + inc rounded to the
+ * act dtype — exactly that: with D = 0, out has the bits of y.  At least one of out and inc is required; out must not overlap y.  Requirements:
+ * N >= 2 (above 128: SEA_EUNSUPPORTED), Bm a multiple of N with at most 65535 histories, G, P, Dl >= 1, Ld 1 or P.  Returns -1 with the entry point
+ * named in sea_last_error() otherwise, before any device is touched.  Notes the form "enkf.mix_bf16" / "enkf.mix_f32" (a = 1 with P domains).
+ * (An addition to ABI version 8; the struct is not in sea_struct_sizes().)
+ */
+typedef struct {
+    const void* y;
+    const float* D;
+    void* out;
+    float* inc;
+    int32_t Bm, N, G, P, Dl, Ld;
+} SeaEnsembleMix;            /* 56 bytes */
+int sea_ensemble_mix(const SeaEnsembleMix* p, int dtype, void* stream);
+
 /* Tuning aid: register a device buffer of n_steps * 64 8-byte words that the persistent form fills with 100 MHz clock stamps of its hand-offs
  * (tools/kv_persist_timeline.py); NULL switches it off. */
 void sea_kv_debug_stamps(unsigned long long* buf);

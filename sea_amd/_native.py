@@ -305,6 +305,19 @@ class SeaDecodeSensorGrad(C.Structure):
     _fields_ = SeaDecodeSensorSse._fields_ + [("grad_scale", _f32), ("pad_", _i32)]
 
 
+class SeaEnkfTransform(C.Structure):
+    # sea_enkf_transform (not in ABI_STRUCTS, like its siblings; tests/test_enkf_cpu.py checks the layout through the library's argument checks)
+    _fields_ = [("pred", _vp), ("obs", _vp), ("prec", _vp), ("taper", _vp), ("D", _vp), ("status", _vp),
+                ("ld_pred", _i64), ("ld_obs", _i64), ("ld_prec", _i64), ("ld_taper", _i64), ("rho", C.c_double), ("alpha", C.c_double),
+                ("B", _i32), ("N", _i32), ("K", _i32), ("Ld", _i32)]
+
+
+class SeaEnsembleMix(C.Structure):
+    # sea_ensemble_mix (not in ABI_STRUCTS either)
+    _fields_ = [("y", _vp), ("D", _vp), ("out", _vp), ("inc", _vp), ("Bm", _i32), ("N", _i32), ("G", _i32), ("P", _i32), ("Dl", _i32), ("Ld", _i32)]
+
+
+ENKF_MAX_N = 128             # members per history of sea_enkf_transform / sea_ensemble_mix
 SENSOR_TILE = 32             # sensors per W2 tile of sea_decode_sensor_sse: every (group, patch) segment of a SensorSet is padded to a multiple of it
 SENSOR_MAX_PATCHES = 65535   # observed patches one launch of sea_decode_sensor_sse carries (a grid dimension)
 MEMBER_MOMENTS_CHUNK = 128   # members one workgroup of sea_decode_member_moments finishes; above it the launch needs its workspace
@@ -425,6 +438,10 @@ def lib() -> C.CDLL:
     L.sea_decode_member_moments.restype = C.c_int
     L.sea_resample_systematic.argtypes = [_vp, _vp, C.c_float, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]
     L.sea_resample_systematic.restype = C.c_int
+    L.sea_enkf_transform.argtypes = [C.POINTER(SeaEnkfTransform), _vp]
+    L.sea_enkf_transform.restype = C.c_int
+    L.sea_ensemble_mix.argtypes = [C.POINTER(SeaEnsembleMix), C.c_int, _vp]
+    L.sea_ensemble_mix.restype = C.c_int
     for name in ("sea_attention_bwd", "sea_wgrad_grouped", "sea_transpose_weights", "sea_rownorm_bwd", "sea_silu_outer_bwd", "sea_ib_bwd",
                  "sea_silu_outer_bwd_dc", "sea_ib_bwd_dc"):
         getattr(L, name).restype = C.c_int
@@ -456,7 +473,7 @@ EXPORTED_SYMBOLS = (
     "sea_mse_fwd_bwd", "sea_relative_mse", "sea_adamw_flat", "sea_grad_norm_ctl", "sea_adamw_flat_ctl",
     "sea_wgrad_grouped", "sea_transpose_weights", "sea_rownorm_bwd", "sea_silu_outer_bwd", "sea_ib_bwd",
     "sea_attention_bwd", "sea_dropout_mask", "sea_run_list", "sea_run_list_steps", "sea_unpatchify", "sea_gemm_rownorm", "sea_exchange_tail", "sea_patchify", "sea_silu_outer_ib", "sea_mlp_fc1_ln_gelu", "sea_mlp_fc2_proj_norm", "sea_kv_rollout", "sea_kv_arena_words", "sea_kv_debug_stamps",
-    "sea_kv_cache_fill", "sea_kv_cache_fork", "sea_kv_cache_gather", "sea_decode_mse", "sea_decode_member_sse", "sea_decode_member_moments", "sea_decode_sensor_sse", "sea_decode_sensor_grad", "sea_resample_systematic",
+    "sea_kv_cache_fill", "sea_kv_cache_fork", "sea_kv_cache_gather", "sea_decode_mse", "sea_decode_member_sse", "sea_decode_member_moments", "sea_decode_sensor_sse", "sea_decode_sensor_grad", "sea_resample_systematic", "sea_enkf_transform", "sea_ensemble_mix",
     "sea_gemm_fewrows", "sea_qkv_rope_fewrows", "sea_row_chain", "sea_row_chain_riders", "sea_gemm_adaln", "sea_mlp_block", "sea_adaln_qkv", "sea_splitk_finish",
     "sea_encoder_block_ws_floats", "sea_encoder_block_fwd", "sea_encoder_block_bwd",
     "sea_silu_outer_bwd_dc", "sea_silu_outer_bwd_dc_ws_floats", "sea_ib_bwd_dc",

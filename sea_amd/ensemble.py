@@ -27,6 +27,12 @@ the dense snapshot through SensorSet and SensorLikelihood:
     logw, dlogw_dy = like.score_and_grad(y, obs, precision)       # the same log-weights and the gradient of every member's own log-weight, in y's layout:
                                                                   # Decode.sensor_loss's launches (sea_decode_sensor_grad), no autograd graph
     y = ens.step(c_next, state=like.nudge(y, obs, precision, rate=0.25))   # one gradient step towards the readings as the corrected state
+
+The ensemble Kalman analysis moves all members at once (SensorKalman: sea_enkf_transform + sea_ensemble_mix behind sensor_sse's predictions):
+
+    kalman = SensorKalman(decoder, n_patches, members=n, sensors=sensors, sigma=sensors.scale_sigma(sigma_phys), inflation=1.05,
+                          taper=unpatcher.sensor_taper(sensors, radius))      # taper=None: one analysis domain for all patches
+    y = ens.step(c_next, state=kalman.analyse(y, sensors.scale_values(readings), precision))
 """
 from __future__ import annotations
 
@@ -507,3 +513,171 @@ def _check_sensor_operands(what: str, obs, precision, B: int, K: int, device) ->
             raise ValueError(f"{what}: precision must be finite and >= 0")
         if precision.device != device:
             raise ValueError(f"{what}: precision is on {precision.device}, the states on {device}")
+
+
+# ------------------------------------------------------------------------------------------------ the ensemble Kalman analysis
+def gaspari_cohn(dist: torch.Tensor, radius) -> torch.Tensor:
+    """The fifth-order, compactly supported correlation function of Gaspari & Cohn (1999, eq. 4.10) as a localisation taper: 1 at distance 0,
+    monotonically down to exactly 0 at 2 * radius and beyond.  dist: a tensor of distances (any shape, any sign); radius: a positive number, the
+    half-width c of the function.  Returns a tensor of dist's shape (float32 unless dist is float64)."""
+    if not torch.is_tensor(dist) or dist.is_complex():
+        raise ValueError(f"gaspari_cohn: dist must be a real tensor of distances, got {type(dist).__name__}")
+    if isinstance(radius, bool) or not isinstance(radius, (int, float)) or not math.isfinite(radius) or radius <= 0:
+        raise ValueError(f"gaspari_cohn: radius = {radius!r} must be a positive finite number")
+    z = dist.to(torch.float64 if dist.dtype == torch.float64 else torch.float32).abs() / float(radius)
+    zi = z.clamp(max=1.0)                                             # each branch is evaluated inside its own interval only
+    zo = z.clamp(min=1.0, max=2.0)
+    inner = (((-0.25 * zi + 0.5) * zi + 0.625) * zi - 5.0 / 3.0) * zi * zi + 1.0
+    outer = ((((zo / 12.0 - 0.5) * zo + 0.625) * zo + 5.0 / 3.0) * zo - 5.0) * zo + 4.0 - 2.0 / (3.0 * zo)
+    return torch.where(z <= 1.0, inner, torch.where(z < 2.0, outer.clamp(min=0.0), torch.zeros_like(z)))
+
+
+def _composed_transform(pred, obs, prec, taper, members: int, rho: float, alpha: float):
+    """sea_enkf_transform's formulas (include/sea_hip.h) as fp64 torch ops on pred's device: (D f32 [B, Ld, N, N], status int32 [B, Ld]).  Needs
+    torch.linalg's Cholesky on that device."""
+    f64 = torch.float64
+    n = members
+    B, K = obs.shape
+    zero = torch.zeros((), device=pred.device, dtype=f64)
+    p = pred.to(f64).view(B, 1, n, K)
+    w = torch.ones(B, 1, K, device=pred.device, dtype=f64) if prec is None else prec.to(f64).expand(B, K).unsqueeze(1)
+    w = torch.where(w > 0, w, zero)
+    if taper is not None:
+        t = taper.to(f64).unsqueeze(0)                                 # [1, Ld, K]
+        w = w * torch.where(t > 0, t, zero)
+    live = w > 0                                                       # [B, Ld, K]
+    ybar = p.mean(dim=2)                                               # [B, 1, K]
+    S = torch.where(live.unsqueeze(2), rho * (p - ybar.unsqueeze(2)) * (w / (n - 1)).sqrt().unsqueeze(2), zero)     # [B, Ld, N, K]
+    dl = torch.where(live, w.sqrt() * (obs.to(f64).unsqueeze(1) - ybar), zero)                                       # [B, Ld, K]
+    C_ = S @ S.transpose(-1, -2)
+    v = (S @ dl.unsqueeze(-1)).squeeze(-1)
+    eye = torch.eye(n, device=pred.device, dtype=f64)
+    bad = ~(torch.isfinite(C_).all(-1).all(-1) & torch.isfinite(v).all(-1))                                          # [B, Ld]
+    Msafe = torch.where(bad[..., None, None], eye, eye + C_)
+    L, _ = torch.linalg.cholesky_ex(Msafe, check_errors=False)      # its info is not used: measured unreliable for large batches; a failed factor is not finite
+    bad = bad | ~torch.isfinite(L).all(-1).all(-1)
+    W = torch.cholesky_solve(eye.expand_as(Msafe).contiguous(), torch.where(bad[..., None, None], eye, L))
+    G = (W @ torch.where(bad[..., None], zero, v).unsqueeze(-1)) / math.sqrt(n - 1) - alpha * (eye - W)
+    Pi = eye - 1.0 / n
+    D = (rho - 1.0) * Pi + rho * (G - G.mean(dim=-2, keepdim=True))
+    D = torch.where(bad[..., None, None], zero, D)
+    count = live.sum(-1).to(torch.int32)
+    status = torch.where(bad, torch.full_like(count, -1), count)
+    return D.to(torch.float32).contiguous(), status
+
+
+def _composed_mix(y, D, n_patches: int):
+    """sea_ensemble_mix's increment with batched fp32 matrix products: f32, y's shape."""
+    B, Ld, n, _ = D.shape
+    Bm, G, E = y.shape
+    yf = y.to(torch.float32).view(B, n, G, n_patches, E // n_patches)
+    if Ld == 1:
+        return torch.bmm(D[:, 0].transpose(1, 2), yf.reshape(B, n, -1)).view(Bm, G, E)
+    yp = yf.permute(0, 3, 1, 2, 4).reshape(B, n_patches, n, -1)       # [B, P, N, G * Dl]
+    inc = torch.matmul(D.transpose(2, 3), yp)                          # [B, P, N, G * Dl]
+    return inc.view(B, n_patches, n, G, E // n_patches).permute(0, 2, 3, 1, 4).reshape(Bm, G, E)
+
+
+class SensorKalman:
+    """The ensemble Kalman analysis of an ensemble's latent states from sparse sensor readings — the deterministic EnKF of Sakov & Oke (2008) in
+    ensemble space, two launches behind the predictions: kalman.analyse(y, obs, precision=None) -> y_a in y's layout and dtype, a corrected state
+    for RolloutSession.step(c, state=y_a).  No random numbers, no step length to tune, and the ensemble keeps its N distinct members.
+
+    y: what RolloutSession.step returns for B * members trajectories, [B * members, n_groups, P * D]; obs, precision, sigma: exactly SensorLikelihood's
+    (readings float32 [B, K] in the decoder's scaled units; a precision 0 marks a missing reading — neutral whatever obs holds there).  The members'
+    predictions at the sensors come from Decode.sensor_sse(..., predictions=True) (the fused launch in bf16, the composed path in fp32); from them
+    sea_enkf_transform forms, per history and analysis domain, the [N, N] matrix D of include/sea_hip.h in fp64 (the mean moves by K (obs - H xbar),
+    the anomalies by -anomaly_gain K H A, K the Kalman gain of the forecast inflated by `inflation` >= 1), and sea_ensemble_mix applies
+    y_a[j] = y[j] + sum_i D[i, j] y[i] to every latent element.  taper: None — one domain: every patch takes the same D; or float32 [P, K] weights in
+    [0, 1] (MeshUnpatcher.sensor_taper) — patch p's latent slice is analysed by its own problem, whose precisions are multiplied by taper[p]
+    (LETKF-style domain localisation; a patch is the natural domain of a latent state stored per patch).  A taper on the host is uploaded once per
+    device.  transform(y, obs, precision) -> (D [B, Ld, N, N], status [B, Ld], pred [B * N, K]); status is the number of live readings of a problem,
+    or -1 where a live operand was not finite: that problem's D is 0 and its states pass through unchanged.  analyse(..., increment=True) also returns
+    the fp32 increment y_a - y before rounding.  fused: None or True — the two launches; False — the same formulas as fp64 torch ops on the device and
+    batched fp32 matrix products, for comparison (it needs torch.linalg's Cholesky on the device; the predictions are sensor_sse's either way).
+    fused=None is the measured rule (tools/enkf_bench.py, profiles/enkf_bench.txt): the two launches, except for ONE problem (one
+    history, one domain) with 4096 sensors or more, the only measured rows with the composed path ahead (a single workgroup then carries all the fp64
+    work of C = S S^T).  A call reads nothing back from
+    the device and uploads nothing after the first call on a device.  2 <= members <= 128.  `decoder` is a sea_amd Decode; no autograd graph is built."""
+
+    def __init__(self, decoder, n_patches: int, members: int, sensors: SensorSet, sigma=None, inflation: float = 1.0, anomaly_gain: float = 0.5,
+                 taper=None, fused: Optional[bool] = None):
+        if not isinstance(members, int) or isinstance(members, bool) or members < 2 or members > N.ENKF_MAX_N:
+            raise ValueError(f"SensorKalman: members = {members!r} must be an integer in 2 .. {N.ENKF_MAX_N}")
+        self._like = SensorLikelihood(decoder, n_patches, members, sensors, sigma=sigma)   # its checks, its folding of sigma
+        for name, v, lo, hi in (("inflation", inflation, 1.0, float("inf")), ("anomaly_gain", anomaly_gain, 0.0, 1.0)):
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or not lo <= v <= hi:
+                raise ValueError(f"SensorKalman: {name} = {v!r} must be a finite number in [{lo}, {hi}]")
+        self.decoder, self.n_patches, self.members, self.sensors, self.fused = decoder, n_patches, members, sensors, fused
+        self.inflation, self.anomaly_gain = float(inflation), float(anomaly_gain)
+        self._taper = {}
+        if taper is None:
+            self._taper_src = None
+        else:
+            t = taper if torch.is_tensor(taper) else torch.as_tensor(taper)
+            if t.dim() != 2 or tuple(t.shape) != (n_patches, sensors.K) or not t.is_floating_point():
+                raise ValueError(f"SensorKalman: taper must be None or a float32 [{n_patches}, {sensors.K}] array (one row of weights per patch), got "
+                                 f"{tuple(t.shape)} {t.dtype}")
+            t = t.detach().to(torch.float32).contiguous()
+            if t.device.type == "cpu" and (not bool(torch.isfinite(t).all()) or not bool(((t >= 0) & (t <= 1)).all())):
+                raise ValueError("SensorKalman: taper weights must lie in [0, 1]")
+            self._taper_src = t
+            self._taper[t.device] = t
+            dev = next(iter(decoder.parameters())).device
+            if dev.type == "cuda":
+                self._taper_on(dev)
+
+    def _taper_on(self, device):
+        if self._taper_src is None:
+            return None
+        t = self._taper.get(device)
+        if t is None:
+            t = self._taper[device] = self._taper_src.to(device)
+        return t
+
+    def _fused_for(self, histories: int) -> bool:
+        if self.fused is not None:
+            return bool(self.fused)
+        domains = 1 if self._taper_src is None else self.n_patches
+        return not (histories * domains == 1 and self.sensors.K >= 4096)
+
+    def _operands(self, y, obs, precision):
+        P, n = self.n_patches, self.members
+        if not torch.is_tensor(y) or y.dim() != 3 or y.shape[-1] % P or y.shape[0] < 1:
+            raise ValueError(f"SensorKalman: y must be [B * members, n_groups, n_patches * D] with n_patches = {P}, got "
+                             f"{tuple(y.shape) if torch.is_tensor(y) else type(y).__name__}")
+        Bm, G, E = y.shape
+        if Bm % n:
+            raise ValueError(f"SensorKalman: the {Bm} trajectories of y are not a multiple of members = {n}")
+        _check_sensor_operands("SensorKalman", obs, precision, Bm // n, self.sensors.K, y.device)
+        sp = self._like._sigma_precision(y.device) if y.is_cuda else None
+        if sp is not None:
+            precision = sp if precision is None else precision * sp
+        return y.detach(), obs.detach(), None if precision is None else precision.detach()
+
+    def transform(self, y: torch.Tensor, obs: torch.Tensor, precision: Optional[torch.Tensor] = None):
+        """(D f32 [B, Ld, N, N], status int32 [B, Ld], pred f32 [B * N, K]): the ensemble-space matrix of the analysis, the live readings per problem
+        (-1: no update) and the members' predictions at the sensors (the innovation of member j is pred[j] - obs)."""
+        y, obs, prec = self._operands(y, obs, precision)
+        Bm, G, E = y.shape
+        P, n = self.n_patches, self.members
+        z = y.reshape(Bm, G, P, E // P).permute(0, 2, 1, 3)          # the re-layout of SensorLikelihood
+        _, pred = self.decoder.sensor_sse(z, self.sensors, obs, precision=prec, members=n, predictions=True)
+        taper = self._taper_on(y.device)
+        with torch.no_grad():
+            if self._fused_for(obs.shape[0]):
+                D, status = ops.enkf_transform(pred, obs, n, prec=prec, taper=taper, rho=self.inflation, alpha=self.anomaly_gain)
+            else:
+                D, status = _composed_transform(pred, obs, prec, taper, n, self.inflation, self.anomaly_gain)
+        return D, status, pred
+
+    def analyse(self, y: torch.Tensor, obs: torch.Tensor, precision: Optional[torch.Tensor] = None, increment: bool = False):
+        """y_a in y's layout and dtype — or (y_a, increment f32) with increment=True — from one set of readings."""
+        D, _, _ = self.transform(y, obs, precision)
+        yc = y.detach().contiguous()
+        with torch.no_grad():
+            if self._fused_for(obs.shape[0]):
+                return ops.ensemble_mix(yc, D, self.n_patches, output=True, increment=bool(increment))
+            inc = _composed_mix(yc, D, self.n_patches)
+            out = (yc.to(torch.float32) + inc).to(y.dtype)
+        return (out, inc) if increment else out

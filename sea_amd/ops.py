@@ -1336,3 +1336,100 @@ def resample_systematic(logw: torch.Tensor, u: torch.Tensor, members: int, ess_f
     N.check(N.lib().sea_resample_systematic(logw.data_ptr(), u.data_ptr(), ess_frac, G, n, index.data_ptr(), logw_out.data_ptr(), ess.data_ptr(),
                                             resampled.data_ptr(), N.stream_ptr()), "sea_resample_systematic")
     return index, logw_out, ess, resampled
+
+
+def fill_enkf_transform(P: N.SeaEnkfTransform, pred, obs, prec, taper, members: int, rho: float, alpha: float, D, status) -> None:
+    """The argument table of sea_enkf_transform.  pred f32 [B * members, K], obs f32 [B, K], prec None / f32 [K] / [B, K], taper None / f32 [Ld, K] (unit inner
+    strides); D f32 [B, Ld, members, members] and status int32 [B, Ld], contiguous."""
+    P.pred, P.obs, P.prec, P.taper, P.D, P.status = pred.data_ptr(), obs.data_ptr(), N.ptr(prec), N.ptr(taper), D.data_ptr(), status.data_ptr()
+    P.ld_pred, P.ld_obs = pred.stride(0), obs.stride(0)
+    P.ld_prec = 0 if prec is None or prec.dim() == 1 else prec.stride(0)
+    P.ld_taper = 0 if taper is None else taper.stride(0)
+    P.rho, P.alpha = rho, alpha
+    P.B, P.N, P.K, P.Ld = obs.shape[0], members, obs.shape[1], D.shape[1]
+
+
+def enkf_transform(pred: torch.Tensor, obs: torch.Tensor, members: int, prec: Optional[torch.Tensor] = None, taper: Optional[torch.Tensor] = None,
+                   rho: float = 1.0, alpha: float = 0.5, out: Optional[torch.Tensor] = None):
+    """sea_enkf_transform: the ensemble-space matrix of the deterministic ensemble Kalman analysis (include/sea_hip.h states the formulas).  pred f32
+    [B * members, K] (the predictions of Decode.sensor_sse), obs f32 [B, K], prec None, f32 [K] or [B, K], taper None (one domain) or f32 [Ld, K]; rho >= 1
+    the inflation, alpha in [0, 1] the anomaly gain.  Returns (D f32 [B, Ld, members, members], status int32 [B, Ld]: the live sensors of the problem, or
+    -1 with D = 0 where a live operand was not finite) on the device; nothing is read back.  out: a D to write into."""
+    what = "enkf_transform"
+    n = members
+    if not isinstance(n, int) or isinstance(n, bool) or n < 2 or n > N.ENKF_MAX_N:
+        raise ValueError(f"{what}: members = {members!r} must be an integer in 2 .. {N.ENKF_MAX_N}")
+    if not torch.is_tensor(obs) or obs.dim() != 2 or obs.dtype != torch.float32 or obs.shape[0] < 1 or obs.shape[1] < 1 or obs.stride(1) != 1:
+        raise ValueError(f"{what}: obs must be a float32 [B, K] tensor with unit inner stride, got {tuple(obs.shape) if torch.is_tensor(obs) else type(obs).__name__}")
+    B, K = obs.shape
+    dev = obs.device
+    if not torch.is_tensor(pred) or pred.dtype != torch.float32 or tuple(pred.shape) != (B * n, K) or pred.stride(1) != 1 or pred.stride(0) < K or pred.device != dev:
+        raise ValueError(f"{what}: pred must be a float32 [{B * n}, {K}] tensor with unit inner stride on {dev}, got "
+                         f"{(tuple(pred.shape), pred.dtype, str(pred.device)) if torch.is_tensor(pred) else type(pred).__name__}")
+    if obs.stride(0) < K and B > 1:
+        raise ValueError(f"{what}: obs rows overlap (strides {obs.stride()})")
+    if prec is not None and (not torch.is_tensor(prec) or prec.dtype != torch.float32 or tuple(prec.shape) not in ((K,), (B, K)) or prec.stride(-1) != 1
+                             or prec.device != dev or (prec.dim() == 2 and B > 1 and prec.stride(0) < K)):
+        raise ValueError(f"{what}: prec must be None or a float32 [{K}] or [{B}, {K}] tensor with unit inner stride on {dev}, got "
+                         f"{(tuple(prec.shape), prec.dtype, str(prec.device)) if torch.is_tensor(prec) else type(prec).__name__}")
+    if prec is not None and prec.dim() == 2 and prec.stride(0) < K:   # one history whose row stride says nothing: the [K] form
+        prec = prec[0]
+    if taper is not None and (not torch.is_tensor(taper) or taper.dtype != torch.float32 or taper.dim() != 2 or taper.shape[0] < 1 or taper.shape[1] != K
+                              or not taper.is_contiguous() or taper.device != dev):
+        raise ValueError(f"{what}: taper must be None or a contiguous float32 [Ld, {K}] tensor on {dev}, got "
+                         f"{(tuple(taper.shape), taper.dtype, str(taper.device)) if torch.is_tensor(taper) else type(taper).__name__}")
+    rho, alpha = float(rho), float(alpha)
+    if not (1.0 <= rho < float("inf")) or not (0.0 <= alpha <= 1.0):
+        raise ValueError(f"{what}: need a finite inflation rho >= 1 and an anomaly gain alpha in [0, 1], got rho = {rho}, alpha = {alpha}")
+    Ld = 1 if taper is None else taper.shape[0]
+    if B > 65535:
+        raise ValueError(f"{what}: {B} histories; a launch carries up to 65535")
+    if out is not None and (not torch.is_tensor(out) or out.dtype != torch.float32 or tuple(out.shape) != (B, Ld, n, n) or not out.is_contiguous() or out.device != dev):
+        raise ValueError(f"{what}: out must be a contiguous float32 [{B}, {Ld}, {n}, {n}] tensor on {dev}")
+    N.require_gpu(obs, f"{what} obs")   # every operand is on the readings' device (checked above)
+    D = torch.empty(B, Ld, n, n, device=dev, dtype=torch.float32) if out is None else out
+    status = torch.empty(B, Ld, device=dev, dtype=torch.int32)
+    P = N.SeaEnkfTransform()
+    fill_enkf_transform(P, pred, obs, prec, taper, n, rho, alpha, D, status)
+    P.ld_obs = max(P.ld_obs, K)   # one history: its row stride is never used and may say anything
+    N.check(N.lib().sea_enkf_transform(C.byref(P), N.stream_ptr()), "sea_enkf_transform")
+    return D, status
+
+
+def fill_ensemble_mix(P: N.SeaEnsembleMix, y, D, out, inc, members: int, n_patches: int) -> None:
+    """The argument table of sea_ensemble_mix.  y act [Bm, G, n_patches * Dl] contiguous, D f32 [Bm / members, Ld, members, members] contiguous; out (y's
+    dtype) and inc (f32) in y's shape, contiguous, either may be None."""
+    P.y, P.D, P.out, P.inc = y.data_ptr(), D.data_ptr(), N.ptr(out), N.ptr(inc)
+    P.Bm, P.N, P.G, P.P, P.Dl, P.Ld = y.shape[0], members, y.shape[1], n_patches, y.shape[2] // n_patches, D.shape[1]
+
+
+def ensemble_mix(y: torch.Tensor, D: torch.Tensor, n_patches: int, output: bool = True, increment: bool = False):
+    """sea_ensemble_mix: out[b * n + j, g, p, :] = y[...] + sum_i D[b, dom(p), i, j] * y[b * n + i, g, p, :] with n = D.shape[-1] members per history and
+    dom(p) = 0 for D [B, 1, n, n], p for D [B, n_patches, n, n].  y [B * n, G, n_patches * Dl] float32 or bfloat16, contiguous.  Returns out (y's dtype;
+    a new tensor), the fp32 increment, or (out, increment), as `output` and `increment` ask; nothing is read back."""
+    what = "ensemble_mix"
+    if not output and not increment:
+        raise ValueError(f"{what}: neither the output nor the increment is asked for")
+    if not isinstance(n_patches, int) or isinstance(n_patches, bool) or n_patches < 1:
+        raise ValueError(f"{what}: n_patches = {n_patches!r} must be a positive integer")
+    if not torch.is_tensor(y) or y.dim() != 3 or y.dtype not in (torch.float32, torch.bfloat16) or not y.is_contiguous() or y.shape[0] < 1 or y.shape[1] < 1 \
+            or y.shape[2] < 1 or y.shape[2] % n_patches:
+        raise ValueError(f"{what}: y must be a contiguous float32 or bfloat16 [B * members, n_groups, {n_patches} * D] tensor, got "
+                         f"{(tuple(y.shape), y.dtype) if torch.is_tensor(y) else type(y).__name__}")
+    if not torch.is_tensor(D) or D.dim() != 4 or D.dtype != torch.float32 or not D.is_contiguous() or D.shape[2] != D.shape[3] or D.device != y.device:
+        raise ValueError(f"{what}: D must be a contiguous float32 [B, Ld, members, members] tensor on {y.device}, got "
+                         f"{(tuple(D.shape), D.dtype, str(D.device)) if torch.is_tensor(D) else type(D).__name__}")
+    n = D.shape[2]
+    if n < 2 or n > N.ENKF_MAX_N:
+        raise ValueError(f"{what}: members = {n} outside 2 .. {N.ENKF_MAX_N}")
+    if y.shape[0] != D.shape[0] * n:
+        raise ValueError(f"{what}: y holds {y.shape[0]} trajectories, D is for {D.shape[0]} histories of {n} members")
+    if D.shape[1] not in (1, n_patches):
+        raise ValueError(f"{what}: D has {D.shape[1]} domains; need 1 or n_patches = {n_patches}")
+    N.require_gpu(y, f"{what} states")
+    out = torch.empty_like(y) if output else None
+    inc = torch.empty(y.shape, device=y.device, dtype=torch.float32) if increment else None
+    P = N.SeaEnsembleMix()
+    fill_ensemble_mix(P, y, D, out, inc, n, n_patches)
+    N.check(N.lib().sea_ensemble_mix(C.byref(P), N.dtype_code(y.dtype), N.stream_ptr()), "sea_ensemble_mix")
+    return (out, inc) if output and increment else (out if output else inc)

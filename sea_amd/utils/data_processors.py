@@ -143,6 +143,25 @@ class MeshUnpatcher:
         return SensorSet(decoder, int(P), [slot[pt] // C for pt in pts], [slot[pt] % C for pt in pts], flds,
                          affine=([scale[f] for f in flds], [shift[f] for f in flds]), points=pts)
 
+    def sensor_taper(self, sensors, radius) -> torch.Tensor:
+        """Localisation weights for SensorKalman(taper=...): float32 [P, K] on the partitioner's device, gaspari_cohn(distance, radius) between every
+        patch's centroid — the mean of the partitioner's full_coords over the patch's valid slots — and every sensor's mesh point (the `points` a set
+        from sensor_set carries; a set built without points is refused).  A patch without a mesh point gets weight 0 everywhere."""
+        from ..ensemble import SensorSet, gaspari_cohn
+
+        if not isinstance(sensors, SensorSet) or sensors.points is None:
+            raise ValueError("sensor_taper: need a SensorSet built by sensor_set (it carries the sensors' mesh points)")
+        part = self.partitioner
+        idx = part.padded_index_map.long()
+        if sensors.n_patches != idx.shape[0] or max(sensors.points) >= part.full_coords.shape[0]:
+            raise ValueError(f"sensor_taper: the SensorSet was built for another mesh ({sensors.n_patches} patches; this one has {idx.shape[0]})")
+        valid = (idx != part.pad_id).to(part.full_coords.dtype)                                  # [P, C]
+        cnt = valid.sum(1, keepdim=True)
+        centroid = (part.full_coords[idx.clamp_min(0)] * valid[..., None]).sum(1) / cnt.clamp_min(1.0)   # [P, 2]
+        where = part.full_coords[torch.tensor(sensors.points, device=part.full_coords.device)]   # [K, 2]
+        dist = (centroid[:, None, :] - where[None, :, :]).square().sum(-1).sqrt()
+        return (gaspari_cohn(dist, radius) * (cnt > 0)).to(torch.float32).contiguous()
+
     def patchify_and_scale(self, data: torch.Tensor, layout: str = "BPCF", c_out: Optional[int] = None) -> torch.Tensor:
         """The forward leg (reference MeshProcessor.patchify_and_scale, utils/data_processors.py:484-526, with fitted scalers): data [T, N, F] ->
         scaled, partitioned, padded fields [T, P, C, F] (layout "BPCF", the reference's) or [T, P, F, c_out] ("BPFC", what the encoder reads) in ONE
@@ -285,6 +304,12 @@ class MeshProcessor:
         if self._unpatcher is None:
             raise ValueError("call patchify_and_scale first (it builds the partition)")
         return self._unpatcher.sensor_set(decoder, points, fields)
+
+    def sensor_taper(self, sensors, radius) -> torch.Tensor:
+        """Gaspari-Cohn localisation weights [P, K] between the patches' centroids and the sensors of a set from sensor_set (MeshUnpatcher.sensor_taper)."""
+        if self._unpatcher is None:
+            raise ValueError("call patchify_and_scale first (it builds the partition)")
+        return self._unpatcher.sensor_taper(sensors, radius)
 
     def decode_and_unpatch(self, decoder, z: torch.Tensor) -> torch.Tensor:
         """decoder(z) + inverse_scale_and_unpatch(..., layout="BPFC") in one go, the decoder run only over a cell's mesh points (MeshUnpatcher.decode_and_unpatch):
