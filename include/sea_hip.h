@@ -1254,6 +1254,62 @@ typedef struct {
 } SeaEnsembleMix;            /* 56 bytes */
 int sea_ensemble_mix(const SeaEnsembleMix* p, int dtype, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Verification of an ensemble against sensor readings, in two launches: CRPS, rank, PIT, mean and spread per (history, sensor), and per history
+ * the fp64 sums and the rank histogram that calibration is read from.  B histories with N members each (member j of history b is row b N + j), K
+ * sensors; pred, obs and prec as for sea_enkf_transform (the same selects).  Per history b, in fp64:
+ *     logw NULL: lw_j = 0.  A member with lw_j = -inf is DEAD: weight 0, not counted in ranks; every other member is live (L of them).
+ *     mx = max_j lw_j;  e_j = exp(lw_j - mx) (dead: 0);  W = sum_j e_j;  w_j = e_j / W;  q = sum_j w_j^2          (sums over j ascending)
+ *     c = unbiased ? 1 - q : 1                        (N / (N - 1) scaling for equal weights; c <= 0 — one member carries all weight — is handled by selects)
+ *     status[b] = L, or -1 when a lw_j is NaN or +inf or none is finite: all per-sensor floats of the history are then 0, its ranks -1, and it adds
+ *     nothing to sums and hist.
+ * Per sensor k of history b, with y = obs[b, k], x_j = pred[b N + j, k] over the live members, p = prec[b, k] (NULL: 1):
+ *     DEAD reading (not p > 0):  mean = spread = crps = pit = 0, rank = -1, whatever obs and pred hold there (NaN, Inf, 3e38 included)
+ *     BAD sensor (live, and y, p or a live member's x_j is not finite): the four floats are NaN, rank = -2; counted in sums[6], left out of every other sum
+ *     mean   = sum_j w_j x_j
+ *     spread = c > 0 ? sqrt(sum_j w_j (x_j - mean)^2 / c) : 0
+ *     crps   = sum_j w_j |x_j - y| - (c > 0 ? (1 / (2 c)) sum_i sum_j w_i w_j |x_i - x_j| : 0)                (unbiased: the fair CRPS)
+ *              the double sum is evaluated as 2 sum_i w_i (x_i - y) (2 Wb_i + w_i - 1), Wb_i = sum_j w_j [(x_j, j) < (x_i, i)] accumulated over j
+ *              ascending: the weight below member i under the total order (value, member index) — no sort, ties and zero weights included
+ *     pit    = sum_j w_j [x_j < y] + 0.5 sum_j w_j [x_j == y]
+ *     rank   = the number of live members with x_j < y                                                        (int32, 0 .. L)
+ * Per history, over its live, good sensors in ascending k, from the fp64 per-sensor values before they are rounded to fp32:
+ *     sums[b, 0..7] = count, sum crps, sum (y - mean)^2, sum spread^2, sum (y - mean)^2 / (spread^2 + 1 / p), sum (mean - y), count of bad sensors,
+ *                     sum 1 / p                        (f64)
+ *     hist[b, r]    = the number of those sensors with rank r, r = 0 .. N                                      (int64 [B, N + 1])
+ * accumulate = 1 adds a call's sums and hist into the existing ones (one writer per element); 0 overwrites them.  status is always overwritten.
+ * mean, spread, crps, pit f32 [B, ld_out] and rank int32 [B, ld_out] may each be NULL; every element [b, k < K] of the others is written.
+ * Launch 1: a workgroup per (tile of 16 sensors, history): the tile's predictions are staged in LDS as [sensor][member], a wave takes a sensor at a
+ * time with a member (two above 64 members) per lane, the lane sums are reduced by a fixed butterfly, thread k writes sensor k, and the tile's fp64
+ * partial sums (sensors ascending) and its partial histogram go to `work`.  Launch 2: a workgroup per history adds the tiles in ascending order.
+ * No atomics to global memory: two runs give the same bits; a history's outputs are those of a launch holding it alone; a sensor's own outputs do
+ * not depend on K, on its place in a tile or on the other sensors.
+ * Requirements: pred, obs, sums, hist, status, work non-NULL; f32 / int32 buffers 4-byte, sums, hist and work 8-byte aligned; B in 1 .. 65535;
+ * N >= 1 (above 128: SEA_EUNSUPPORTED); K >= 1; ld_pred, ld_obs, ld_out >= K; ld_prec = 0 (one row [K] for all histories) or >= K; unbiased and
+ * accumulate 0 or 1; work_bytes >= sea_ensemble_verify_ws_bytes(B, N, K) (the workspace is private to the call until it has run).  Returns -1 with
+ * the entry point named in sea_last_error() otherwise, before any device is touched.  Notes the form "verify" (a = members per lane, 1 or 2; b =
+ * the dynamic LDS bytes).  (An addition to ABI version 8; the struct is not in sea_struct_sizes().)
+ */
+typedef struct {
+    const float* pred;       /* f32 [B N, ld_pred] */
+    const float* obs;        /* f32 [B, ld_obs] */
+    const float* prec;       /* NULL (1), f32 [K] (ld_prec = 0) or f32 [B, ld_prec] */
+    const float* logw;       /* NULL (equal weights) or f32 [B N], unnormalised */
+    float* mean;             /* f32 [B, ld_out] or NULL */
+    float* spread;
+    float* crps;
+    float* pit;
+    int32_t* rank;           /* int32 [B, ld_out] or NULL */
+    double* sums;            /* f64 [B, 8] */
+    int64_t* hist;           /* int64 [B, N + 1] */
+    int32_t* status;         /* int32 [B] */
+    void* work;              /* work_bytes bytes */
+    int64_t ld_pred, ld_obs, ld_prec, ld_out, work_bytes;
+    int32_t B, N, K, unbiased, accumulate, pad_;
+} SeaEnsembleVerify;         /* 168 bytes */
+int64_t sea_ensemble_verify_ws_bytes(int B, int N, int K);   /* -1 for sizes the entry point refuses */
+int sea_ensemble_verify(const SeaEnsembleVerify* p, void* stream);
+
 /* Tuning aid: register a device buffer of n_steps * 64 8-byte words that the persistent form fills with 100 MHz clock stamps of its hand-offs
  * (tools/kv_persist_timeline.py); NULL switches it off. */
 void sea_kv_debug_stamps(unsigned long long* buf);

@@ -1,0 +1,331 @@
+// Verification of an ensemble against sensor readings (gfx950): sea_ensemble_verify.  From the members' predictions at K sensors, the readings, their
+// precisions and the members' log-weights: CRPS, PIT, rank, mean and spread per (history, sensor), and per history the fp64 sums and the rank
+// histogram (include/sea_hip.h states the formulas).  Two launches, both without atomics to global memory, spin-waits or any exchange between
+// workgroups; every loop bound is a kernel argument; every early exit is taken by the whole workgroup between barriers.
+//
+// verify_kernel<V>: one workgroup of 256 threads per (tile of 16 sensors, history); V = 1 up to 64 members, 2 above.
+//   1  the history's weights, in fp64: the log-weights go to LDS, every thread walks them in ascending order (broadcast reads) for the maximum, the
+//      sum of the exponentials and q = sum w^2 — the same bits in every thread and in every tile of the history.
+//   2  the tile's N x 16 block of pred is read along each member row (64-byte segments) and staged as [sensor][member | 1] fp32 (an odd row stride: the
+//      transposing stores and the per-sensor reads both stay off one bank).
+//   3  wave w takes sensors w, w + 4, ...: lane l holds member l (and l + 64), walks j = 0 .. N - 1 with broadcast LDS reads and accumulates the
+//      weight below its own member under the total order (value, member index); that gives the pair sum of the CRPS without a sort.  The lane
+//      terms are reduced by a fixed xor butterfly (the mean first: the spread is centred on it).  A dead reading is passed over by its wave.
+//   4  thread k of the tile finishes sensor k (the selects on c, the fp32 stores) and files its terms; threads 0 .. 7 add the tile's terms in
+//      ascending sensor order; the partial histogram is counted in LDS with integer adds (order-independent).  Both go to the workspace.
+// verify_finish_kernel: one workgroup per history adds the tiles' partials in ascending tile order into sums and hist (or onto them: accumulate);
+// the partial sums come through LDS 256 tiles at a time, so that their loads are in flight together and only the additions are serial.
+// What bounds it: per sensor a wave pays N broadcast reads, compares and fp64 adds per lane and two rounds of butterflies; a workgroup therefore
+// holds only 16 sensors, four per wave, and a few hundred sensors already spread over the chip; below that the two launches' latency.
+#include "sea_common.hpp"
+
+#include <math.h>
+
+constexpr int VF_THREADS = 256;
+constexpr int VF_MAX_N = 128;
+constexpr int VF_TILE = 16;    // sensors per workgroup: four per wave
+constexpr int VF_SUMS = 8;
+constexpr int VF_FIN_TILES = 256;   // tiles whose partial sums the finish kernel holds in LDS at a time
+constexpr int VF_WALK = 8;   // members whose LDS reads are issued together in the walk
+
+static inline int64_t vf_tile_words(int N) { return VF_SUMS + (N + 2) / 2; }   // 8-byte words per (history, tile): 8 sums, then N + 1 int32 bins
+
+__device__ __forceinline__ double vf_wave_sum(double v) {
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
+
+template <int V>
+__global__ __launch_bounds__(VF_THREADS) void verify_kernel(const SeaEnsembleVerify p, const int tiles, const int words) {
+#pragma clang fp reassociate(off)
+    extern __shared__ __attribute__((aligned(16))) float vf_stage[];   // [VF_TILE][N | 1]
+    __shared__ double lw_s[VF_MAX_N], w_s[VF_MAX_N];
+    __shared__ int live_s[VF_MAX_N];
+    __shared__ double r_mean[VF_TILE], r_var[VF_TILE], r_abs[VF_TILE], r_pair[VF_TILE], r_pit[VF_TILE];
+    __shared__ int r_rank[VF_TILE], r_state[VF_TILE];                  // state: 0 live and good, 1 dead, 2 bad
+    __shared__ double term_s[VF_SUMS][VF_TILE];
+    __shared__ int hist_s[VF_MAX_N + 1];
+    __shared__ float y_s[VF_TILE], pv_s[VF_TILE];                      // the tile's readings and precisions: no global load inside the sensor loop
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tile = blockIdx.x, b = blockIdx.y;
+    const int N = p.N, K = p.K, SLD = N | 1;
+    const int k0 = tile * VF_TILE;
+    const int kcn = K - k0 < VF_TILE ? K - k0 : VF_TILE;
+    const float* pred = p.pred + (int64_t)b * N * p.ld_pred;
+    const float* obs = p.obs + (int64_t)b * p.ld_obs;
+    const float* prec = p.prec != nullptr ? p.prec + (int64_t)b * p.ld_prec : nullptr;
+    const int64_t orow = (int64_t)b * p.ld_out;
+    double* wsum = reinterpret_cast<double*>(p.work) + ((int64_t)b * tiles + tile) * words;
+    int32_t* whist = reinterpret_cast<int32_t*>(wsum + VF_SUMS);
+
+    // 1: the weights of the history
+    int invalid = 0, alive = 0;
+    if (tid < N) {
+        const float lw = p.logw != nullptr ? p.logw[(int64_t)b * N + tid] : 0.f;
+        invalid = (lw != lw || lw == INFINITY) ? 1 : 0;
+        alive = (!invalid && lw != -INFINITY) ? 1 : 0;
+        lw_s[tid] = (double)lw;
+        live_s[tid] = alive;
+    }
+    for (int r = tid; r <= N; r += VF_THREADS) hist_s[r] = 0;
+    const int n_live = __syncthreads_count(alive);
+    invalid = __syncthreads_or(invalid);
+    if (invalid || n_live == 0) {   // uniform: the history is not scored
+        if (tid < kcn) {
+            if (p.mean != nullptr) p.mean[orow + k0 + tid] = 0.f;
+            if (p.spread != nullptr) p.spread[orow + k0 + tid] = 0.f;
+            if (p.crps != nullptr) p.crps[orow + k0 + tid] = 0.f;
+            if (p.pit != nullptr) p.pit[orow + k0 + tid] = 0.f;
+            if (p.rank != nullptr) p.rank[orow + k0 + tid] = -1;
+        }
+        if (tid < VF_SUMS) wsum[tid] = 0.0;
+        for (int r = tid; r <= N; r += VF_THREADS) whist[r] = 0;
+        if (tile == 0 && tid == 0) p.status[b] = -1;
+        return;
+    }
+    double mx = -INFINITY;
+    for (int j = 0; j < N; ++j) mx = lw_s[j] > mx ? lw_s[j] : mx;
+    if (tid < N) w_s[tid] = alive ? exp(lw_s[tid] - mx) : 0.0;
+    __syncthreads();
+    double W = 0.0;
+    for (int j = 0; j < N; ++j) W += w_s[j];
+    const double my_w = tid < N ? w_s[tid] / W : 0.0;
+    __syncthreads();   // every thread has read the exponentials
+    if (tid < N) w_s[tid] = my_w;
+
+    // 2: the tile's predictions, [sensor][member]
+    for (int e = tid; e < N * VF_TILE; e += VF_THREADS) {
+        const int j = e / VF_TILE, kc = e % VF_TILE;
+        if (kc < kcn) vf_stage[kc * SLD + j] = pred[(int64_t)j * p.ld_pred + k0 + kc];
+    }
+    if (tid < kcn) {
+        y_s[tid] = obs[k0 + tid];
+        pv_s[tid] = prec != nullptr ? prec[k0 + tid] : 1.f;
+    }
+    __syncthreads();
+    double q = 0.0;
+    for (int j = 0; j < N; ++j) q = fma(w_s[j], w_s[j], q);
+    const double c = p.unbiased ? 1.0 - q : 1.0;
+
+    // 3: a sensor per wave at a time
+    for (int kc = wave; kc < kcn; kc += 4) {
+        const float pv = pv_s[kc];
+        if (!(pv > 0.f)) {   // the same word in every lane: the wave passes a dead reading over, whatever obs and pred hold there
+            if (lane == 0) r_state[kc] = 1;
+            continue;
+        }
+        const float* row = vf_stage + kc * SLD;
+        const float yf = y_s[kc];
+        const double y = (double)yf;
+        float x[V];
+        double w[V], below[V];
+        bool lv[V];
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            const int i = lane + 64 * v;
+            const bool in = i < N;
+            x[v] = in ? row[i] : 0.f;
+            w[v] = in ? w_s[i] : 0.0;
+            lv[v] = in && live_s[i] != 0;
+            below[v] = 0.0;
+        }
+        // the walk, j ascending; eight members' reads are issued together, and the order test is written without short-circuits: no branch in the chain.
+        // A dead member's weight is 0: its value, NaN included, reaches nothing
+        int j = 0;
+        for (; j + VF_WALK <= N; j += VF_WALK) {
+            float xj[VF_WALK];
+            double wj[VF_WALK];
+#pragma unroll
+            for (int u = 0; u < VF_WALK; ++u) {
+                xj[u] = row[j + u];
+                wj[u] = w_s[j + u];
+            }
+#pragma unroll
+            for (int u = 0; u < VF_WALK; ++u)
+#pragma unroll
+                for (int v = 0; v < V; ++v) {
+                    const bool lower = (xj[u] < x[v]) | ((xj[u] == x[v]) & (j + u < lane + 64 * v));
+                    below[v] += lower ? wj[u] : 0.0;
+                }
+        }
+        for (; j < N; ++j) {
+            const float xj = row[j];
+            const double wj = w_s[j];
+#pragma unroll
+            for (int v = 0; v < V; ++v) {
+                const bool lower = (xj < x[v]) | ((xj == x[v]) & (j < lane + 64 * v));
+                below[v] += lower ? wj : 0.0;
+            }
+        }
+        double m = 0.0;
+        int bad = (isfinite(yf) && isfinite(pv)) ? 0 : 1, rk = 0;
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            m += lv[v] ? w[v] * (double)x[v] : 0.0;
+            bad |= (lv[v] && !isfinite(x[v])) ? 1 : 0;
+            rk += (lv[v] && x[v] < yf) ? 1 : 0;
+        }
+        const double mean = vf_wave_sum(m);
+        double var = 0.0, ab = 0.0, pr = 0.0, pt = 0.0;
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            const double xd = (double)x[v], d = xd - y, dm = xd - mean;
+            var += lv[v] ? w[v] * dm * dm : 0.0;
+            ab += lv[v] ? w[v] * fabs(d) : 0.0;
+            pr += lv[v] ? w[v] * d * (2.0 * below[v] + w[v] - 1.0) : 0.0;
+            pt += lv[v] ? w[v] * (x[v] < yf ? 1.0 : (x[v] == yf ? 0.5 : 0.0)) : 0.0;
+        }
+#pragma unroll
+        for (int m = 1; m < 64; m <<= 1) {   // six butterflies, stage by stage: their exchanges are in flight together; each sum has vf_wave_sum's order
+            const double o_var = __shfl_xor(var, m, 64), o_ab = __shfl_xor(ab, m, 64), o_pr = __shfl_xor(pr, m, 64), o_pt = __shfl_xor(pt, m, 64);
+            const int o_rk = __shfl_xor(rk, m, 64), o_bad = __shfl_xor(bad, m, 64);
+            var += o_var;
+            ab += o_ab;
+            pr += o_pr;
+            pt += o_pt;
+            rk += o_rk;
+            bad += o_bad;
+        }
+        if (lane == 0) {
+            r_mean[kc] = mean;
+            r_var[kc] = var;
+            r_abs[kc] = ab;
+            r_pair[kc] = pr;
+            r_pit[kc] = pt;
+            r_rank[kc] = rk;
+            r_state[kc] = bad ? 2 : 0;
+        }
+    }
+    __syncthreads();
+
+    // 4: thread k finishes sensor k
+    if (tid < VF_TILE) {
+        double t[VF_SUMS];
+#pragma unroll
+        for (int i = 0; i < VF_SUMS; ++i) t[i] = 0.0;
+        if (tid < kcn) {
+            const int state = r_state[tid];
+            float o_mean = 0.f, o_spread = 0.f, o_crps = 0.f, o_pit = 0.f;
+            int o_rank = -1;
+            if (state == 2) {
+                o_mean = o_spread = o_crps = o_pit = NAN;
+                o_rank = -2;
+                t[6] = 1.0;
+            } else if (state == 0) {
+                const double y = (double)y_s[tid];
+                const double rvar = 1.0 / (double)pv_s[tid];
+                const double mean = r_mean[tid];
+                const double sp2 = c > 0.0 ? r_var[tid] / c : 0.0;
+                const double crps = r_abs[tid] - (c > 0.0 ? r_pair[tid] / c : 0.0);
+                const double err = y - mean;
+                o_mean = (float)mean;
+                o_spread = (float)sqrt(sp2);
+                o_crps = (float)crps;
+                o_pit = (float)r_pit[tid];
+                o_rank = r_rank[tid];
+                t[0] = 1.0;
+                t[1] = crps;
+                t[2] = err * err;
+                t[3] = sp2;
+                t[4] = err * err / (sp2 + rvar);
+                t[5] = mean - y;
+                t[7] = rvar;
+                atomicAdd(&hist_s[o_rank], 1);   // LDS, integers: the order does not matter; 0 <= rank <= N
+            }
+            if (p.mean != nullptr) p.mean[orow + k0 + tid] = o_mean;
+            if (p.spread != nullptr) p.spread[orow + k0 + tid] = o_spread;
+            if (p.crps != nullptr) p.crps[orow + k0 + tid] = o_crps;
+            if (p.pit != nullptr) p.pit[orow + k0 + tid] = o_pit;
+            if (p.rank != nullptr) p.rank[orow + k0 + tid] = o_rank;
+        }
+#pragma unroll
+        for (int i = 0; i < VF_SUMS; ++i) term_s[i][tid] = t[i];
+    }
+    __syncthreads();
+    if (tid < VF_SUMS) {
+        double s = 0.0;
+        for (int k = 0; k < kcn; ++k) s += term_s[tid][k];
+        wsum[tid] = s;
+    }
+    for (int r = tid; r <= N; r += VF_THREADS) whist[r] = hist_s[r];
+    if (tile == 0 && tid == 0) p.status[b] = n_live;
+}
+
+__global__ __launch_bounds__(VF_THREADS) void verify_finish_kernel(const SeaEnsembleVerify p, const int tiles, const int words) {
+#pragma clang fp reassociate(off)
+    __shared__ double part[VF_FIN_TILES][VF_SUMS];   // a chunk of the tiles' partial sums: read together, then added in ascending tile order
+    const int tid = threadIdx.x, b = blockIdx.x, N = p.N;
+    const double* base = reinterpret_cast<const double*>(p.work) + (int64_t)b * tiles * words;
+    double acc = 0.0;
+    for (int t0 = 0; t0 < tiles; t0 += VF_FIN_TILES) {
+        const int n = tiles - t0 < VF_FIN_TILES ? tiles - t0 : VF_FIN_TILES;
+        for (int e = tid; e < n * VF_SUMS; e += VF_THREADS) part[e / VF_SUMS][e % VF_SUMS] = base[(int64_t)(t0 + e / VF_SUMS) * words + e % VF_SUMS];
+        __syncthreads();
+        if (tid < VF_SUMS)
+            for (int t = 0; t < n; ++t) acc += part[t][tid];
+        __syncthreads();   // the chunk has been consumed
+    }
+    if (tid < VF_SUMS) {
+        double* dst = p.sums + (int64_t)b * VF_SUMS + tid;
+        *dst = p.accumulate ? *dst + acc : acc;
+    }
+    for (int r = tid; r <= N; r += VF_THREADS) {
+        int64_t s = 0;
+#pragma unroll 8
+        for (int t = 0; t < tiles; ++t) s += reinterpret_cast<const int32_t*>(base + (int64_t)t * words + VF_SUMS)[r];   // integers: any order
+        int64_t* dst = p.hist + (int64_t)b * (N + 1) + r;
+        *dst = p.accumulate ? *dst + s : s;
+    }
+}
+
+static inline bool vf_aligned8(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 7u) == 0; }
+
+extern "C" int64_t sea_ensemble_verify_ws_bytes(int B, int N, int K) {
+    if (B < 1 || B > 65535 || N < 1 || N > VF_MAX_N || K < 1) return -1;
+    const int64_t tiles = ((int64_t)K + VF_TILE - 1) / VF_TILE;
+    return (int64_t)B * tiles * vf_tile_words(N) * 8;
+}
+
+template <int V>
+static void verify_launch(const SeaEnsembleVerify& p, int tiles, hipStream_t s) {
+    const int lds = VF_TILE * (p.N | 1) * (int)sizeof(float);
+    verify_kernel<V><<<dim3((unsigned)tiles, (unsigned)p.B), dim3(VF_THREADS), lds, s>>>(p, tiles, (int)vf_tile_words(p.N));
+    sea_note_form("verify", V, lds);
+}
+
+extern "C" int sea_ensemble_verify(const SeaEnsembleVerify* pp, void* stream) {
+    SEA_REQUIRE(pp != nullptr, "sea_ensemble_verify: null argument table");
+    const SeaEnsembleVerify& p = *pp;
+    SEA_REQUIRE(p.pred != nullptr && p.obs != nullptr && p.sums != nullptr && p.hist != nullptr && p.status != nullptr && p.work != nullptr,
+                "sea_ensemble_verify: null pointer (pred, obs, sums, hist, status and work are required; prec, logw and the per-sensor outputs may be NULL)");
+    SEA_REQUIRE(sea_aligned4(p.pred) && sea_aligned4(p.obs) && sea_aligned4(p.prec) && sea_aligned4(p.logw) && sea_aligned4(p.mean) && sea_aligned4(p.spread) &&
+                    sea_aligned4(p.crps) && sea_aligned4(p.pit) && sea_aligned4(p.rank) && sea_aligned4(p.status) && vf_aligned8(p.sums) && vf_aligned8(p.hist) &&
+                    vf_aligned8(p.work),
+                "sea_ensemble_verify: misaligned pointer (f32 and int32 buffers need 4 bytes; sums, hist and work 8)");
+    SEA_REQUIRE(p.B >= 1 && p.B <= 65535, "sea_ensemble_verify: B=%d histories outside 1 .. 65535", p.B);
+    SEA_REQUIRE(p.N >= 1, "sea_ensemble_verify: N=%d must be positive", p.N);
+    SEA_REQUIRE(p.K >= 1, "sea_ensemble_verify: K=%d must be positive", p.K);
+    SEA_REQUIRE(p.ld_pred >= p.K && p.ld_obs >= p.K, "sea_ensemble_verify: ld_pred=%lld and ld_obs=%lld must cover K=%d", (long long)p.ld_pred, (long long)p.ld_obs, p.K);
+    SEA_REQUIRE(p.prec == nullptr || p.ld_prec == 0 || p.ld_prec >= p.K, "sea_ensemble_verify: ld_prec=%lld must be 0 (one row for all histories) or cover K=%d",
+                (long long)p.ld_prec, p.K);
+    SEA_REQUIRE((p.mean == nullptr && p.spread == nullptr && p.crps == nullptr && p.pit == nullptr && p.rank == nullptr) || p.ld_out >= p.K,
+                "sea_ensemble_verify: ld_out=%lld must cover K=%d", (long long)p.ld_out, p.K);
+    SEA_REQUIRE((p.unbiased == 0 || p.unbiased == 1) && (p.accumulate == 0 || p.accumulate == 1), "sea_ensemble_verify: unbiased=%d and accumulate=%d must be 0 or 1",
+                p.unbiased, p.accumulate);
+    if (p.N > VF_MAX_N) {
+        sea_set_error("sea_ensemble_verify: unsupported: N=%d members above %d", p.N, VF_MAX_N);
+        return SEA_EUNSUPPORTED;
+    }
+    const int64_t need = sea_ensemble_verify_ws_bytes(p.B, p.N, p.K);
+    SEA_REQUIRE(p.work_bytes >= need, "sea_ensemble_verify: work_bytes=%lld below the %lld that sea_ensemble_verify_ws_bytes(B=%d, N=%d, K=%d) asks for",
+                (long long)p.work_bytes, (long long)need, p.B, p.N, p.K);
+    const int tiles = (int)(((int64_t)p.K + VF_TILE - 1) / VF_TILE);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (p.N <= 64) verify_launch<1>(p, tiles, s);
+    else verify_launch<2>(p, tiles, s);
+    verify_finish_kernel<<<dim3((unsigned)p.B), dim3(VF_THREADS), 0, s>>>(p, tiles, (int)vf_tile_words(p.N));
+    SEA_CHECK_LAUNCH("sea_ensemble_verify");
+    return SEA_OK;
+}

@@ -33,9 +33,17 @@ The ensemble Kalman analysis moves all members at once (SensorKalman: sea_enkf_t
     kalman = SensorKalman(decoder, n_patches, members=n, sensors=sensors, sigma=sensors.scale_sigma(sigma_phys), inflation=1.05,
                           taper=unpatcher.sensor_taper(sensors, radius))      # taper=None: one analysis domain for all patches
     y = ens.step(c_next, state=kalman.analyse(y, sensors.scale_values(readings), precision))
+
+Whether the ensemble is any good is read at the same sensors (SensorVerification: sea_ensemble_verify behind the same predictions):
+
+    verify = SensorVerification(decoder, n_patches, members=n, sensors=sensors, sigma=sensors.scale_sigma(sigma_phys))
+    D, status, pred = kalman.transform(y, obs, precision)
+    forecast = verify.from_predictions(pred, obs, precision, into=forecast)   # CRPS, PIT, rank, mean, spread per sensor; sums and rank histogram add up
+    forecast.spread_skill, forecast.suggested_inflation, forecast.hist         # [B] tensors and the histogram, on the device
 """
 from __future__ import annotations
 
+import dataclasses
 import math
 from typing import Optional
 
@@ -681,3 +689,206 @@ class SensorKalman:
             inc = _composed_mix(yc, D, self.n_patches)
             out = (yc.to(torch.float32) + inc).to(y.dtype)
         return (out, inc) if increment else out
+
+
+# ------------------------------------------------------------------------------------------------ verification at the sensors
+@dataclasses.dataclass(frozen=True)
+class EnsembleScores:
+    """What SensorVerification returns, all on the predictions' device.  Per (history, sensor), [B, K]: crps, pit, mean, spread (float32) and rank
+    (int32: live members below the reading; -1 a reading without weight, -2 a bad sensor — a live reading or a live member's prediction that is not
+    finite; its floats are NaN).  Per history: sums float64 [B, 8] (count of live good sensors, sum crps, sum (y - mean)^2, sum spread^2,
+    sum (y - mean)^2 / (spread^2 + 1 / precision), sum (mean - y), count of bad sensors, sum 1 / precision), hist int64 [B, members + 1] (the rank
+    histogram over the same sensors) and status int32 [B] (the live members; -1: the history's log-weights hold a NaN, +inf or no finite entry, and
+    it was not scored).  sums and hist add up over calls (into=).  The derived properties are float64 [B] tensor expressions of sums: nothing is read
+    back; a history without a live good sensor gives NaN."""
+    crps: torch.Tensor
+    pit: torch.Tensor
+    rank: torch.Tensor
+    mean: torch.Tensor
+    spread: torch.Tensor
+    sums: torch.Tensor
+    hist: torch.Tensor
+    status: torch.Tensor
+
+    @property
+    def count(self):
+        return self.sums[:, 0]
+
+    @property
+    def mean_crps(self):
+        return self.sums[:, 1] / self.sums[:, 0]
+
+    @property
+    def rmse(self):
+        """The root-mean-square error of the ensemble mean at the sensors."""
+        return (self.sums[:, 2] / self.sums[:, 0]).sqrt()
+
+    @property
+    def mean_spread(self):
+        """The root of the mean ensemble variance at the sensors (what the error of the mean is to be compared with)."""
+        return (self.sums[:, 3] / self.sums[:, 0]).sqrt()
+
+    @property
+    def spread_skill(self):
+        """mean_spread / rmse: below 1 the ensemble is under-dispersive (raise the inflation), above 1 over-dispersive."""
+        return (self.sums[:, 3] / self.sums[:, 2]).sqrt()
+
+    @property
+    def consistency(self):
+        """The mean of (y - mean)^2 / (spread^2 + 1 / precision): about 1 for a calibrated ensemble with honest observation errors."""
+        return self.sums[:, 4] / self.sums[:, 0]
+
+    @property
+    def bias(self):
+        """The mean of (ensemble mean - reading)."""
+        return self.sums[:, 5] / self.sums[:, 0]
+
+    @property
+    def suggested_inflation(self):
+        """sqrt(max(1, (sum (y - mean)^2 - sum 1 / precision) / sum spread^2)): the moment estimate of the inflation that would make the spread
+        consistent with the error of the mean (Wang & Bishop 2003; Desroziers et al. 2005)."""
+        return ((self.sums[:, 2] - self.sums[:, 7]) / self.sums[:, 3]).clamp_min(1.0).sqrt()
+
+
+def _composed_verify(pred, obs, prec, logw, members: int, unbiased: bool, out_dtype=torch.float32):
+    """sea_ensemble_verify's formulas (include/sea_hip.h) as fp64 torch ops on pred's device — a stable sort, a cumulative sum, gathers — for any
+    member count: a dict with ops.ensemble_verify's keys (out_dtype: the dtype of the per-sensor floats).  Nothing is read back."""
+    f64 = torch.float64
+    n = members
+    B, K = obs.shape
+    dev = pred.device
+    zero = torch.zeros((), device=dev, dtype=f64)
+    x = pred.to(f64).view(B, n, K)
+    y = obs.to(f64)
+    lw = torch.zeros(B, n, device=dev, dtype=f64) if logw is None else logw.to(f64).view(B, n)
+    invalid = (torch.isnan(lw) | (lw == float("inf"))).any(1) | ~torch.isfinite(lw).any(1)            # [B]
+    lw = torch.where(invalid.unsqueeze(1), zero, lw)
+    alive = lw != float("-inf")                                                                      # [B, N]
+    e = torch.where(alive, (lw - lw.max(dim=1, keepdim=True).values).exp(), zero)
+    w = e / e.sum(dim=1, keepdim=True)
+    c = 1.0 - (w * w).sum(dim=1, keepdim=True) if unbiased else torch.ones(B, 1, device=dev, dtype=f64)
+    pos = c > 0
+    c_safe = torch.where(pos, c, torch.ones_like(c))
+    p = torch.ones(B, K, device=dev, dtype=f64) if prec is None else prec.to(f64).expand(B, K)
+    live = (p > 0) & ~invalid.unsqueeze(1)                                                           # [B, K]
+    finite = torch.isfinite(y) & torch.isfinite(p) & (torch.isfinite(x) | ~alive.unsqueeze(2)).all(1)
+    bad = live & ~finite
+    good = live & finite
+    use = good.unsqueeze(1) & alive.unsqueeze(2)                                                     # [B, N, K]: what enters a sum
+    xs = torch.where(use, x, zero)
+    ys = torch.where(good, y, zero)
+    rvar = 1.0 / torch.where(good, p, torch.ones_like(p))
+    wv = torch.where(use, w.unsqueeze(2), zero)
+    mean = (wv * xs).sum(1)
+    sp2 = torch.where(pos, (wv * (xs - mean.unsqueeze(1)) ** 2).sum(1) / c_safe, zero)
+    d = xs - ys.unsqueeze(1)
+    order = torch.sort(xs, dim=1, stable=True).indices                                                # ties keep the member order
+    ws, ds = torch.gather(wv, 1, order), torch.gather(d, 1, order)
+    below = ws.cumsum(1) - ws
+    pair = (ws * ds * (2.0 * below + ws - 1.0)).sum(1)
+    crps = (wv * d.abs()).sum(1) - torch.where(pos, pair / c_safe, zero)
+    lt, eq = xs < ys.unsqueeze(1), xs == ys.unsqueeze(1)
+    pit = (wv * (lt.to(f64) + 0.5 * eq.to(f64))).sum(1)
+    rank = (lt & use).sum(1)
+    err = ys - mean
+    terms = torch.stack([good.to(f64), crps, err * err, sp2, err * err / (sp2 + rvar), mean - ys, zero.expand(B, K), rvar], dim=2)   # [B, K, 8]
+    sums = torch.where(good.unsqueeze(2), terms, zero).sum(1)
+    sums[:, 6] = bad.sum(1).to(f64)
+    hist = torch.zeros(B, n + 1, device=dev, dtype=torch.int64).scatter_add_(1, torch.where(good, rank, torch.zeros_like(rank)), good.to(torch.int64))
+    nan = torch.full((), float("nan"), device=dev, dtype=f64)
+    f32 = lambda t: torch.where(bad, nan, torch.where(good, t, zero)).to(out_dtype)   # noqa: E731
+    rank = torch.where(bad, torch.full_like(rank, -2), torch.where(good, rank, torch.full_like(rank, -1))).to(torch.int32)
+    status = torch.where(invalid, torch.full_like(invalid, -1, dtype=torch.int64), alive.sum(1)).to(torch.int32)
+    return dict(mean=f32(mean), spread=f32(sp2.sqrt()), crps=f32(crps), pit=f32(pit), rank=rank, sums=sums, hist=hist, status=status)
+
+
+class SensorVerification:
+    """Verification of an ensemble against sparse sensor readings — is the ensemble any good: verify(y, obs, precision=None, logw=None, into=None) ->
+    EnsembleScores.  Per (history, sensor) the continuous ranked probability score, the probability integral transform, the rank of the reading among
+    the members, the ensemble mean and spread; per history the fp64 sums behind rmse, mean_spread, spread_skill, consistency, bias, mean_crps and
+    suggested_inflation, and the rank histogram — what inflation, anomaly_gain, sigma and a taper radius of SensorKalman are tuned by.
+
+    y, obs, precision, sigma: exactly SensorLikelihood's (that object's checks and its folding of sigma into the precision; 1 / precision is the
+    reading's observation-error variance; precision 0 marks a missing reading — neutral whatever obs and the predictions hold there).  logw: None
+    (equal weights) or [B * members] (or [B, members]) unnormalised log-weights; a member with -inf is dead: weight 0, not ranked.  unbiased=True
+    divides the spread's and the CRPS's member-pair terms by 1 - sum w^2 (N / (N - 1) for equal weights: the fair CRPS).  The predictions come from
+    Decode.sensor_sse(..., predictions=True); from_predictions(pred, obs, ...) skips the decode — the pred that SensorKalman.transform returned is
+    scored as the forecast without decoding twice.  into: an earlier result; this call's sums and histogram are added onto ITS sums and hist (in
+    place), so a run aggregates its cycles without host work.  fused: True — the two launches of sea_ensemble_verify (include/sea_hip.h; up to 128
+    members, GPU tensors); False — the same formulas as fp64 torch ops (a sort, a cumulative sum, gathers), for comparison, for more than 128 members
+    and for CPU tensors through from_predictions.  fused=None is the measured rule (tools/verify_bench.py, profiles/verify_bench.txt, DESIGN.md
+    section 7i): the two launches up to 128 members — every measured row has them ahead of the composed path (64 members, 16 to 4096 sensors, one
+    and four histories, with and without log-weights: 0.035 - 0.050 ms against 0.76 - 1.00 ms per from_predictions call; 128 members at 256 and 4096
+    sensors: 0.047 - 0.093 against 0.69 - 0.87 ms); other member counts were not measured and follow the same rule.  A call reads nothing
+    back from the device and uploads nothing after the first call on a device.  `decoder` is a sea_amd Decode; no autograd graph is built."""
+
+    def __init__(self, decoder, n_patches: int, members: int, sensors: SensorSet, sigma=None, unbiased: bool = True, fused: Optional[bool] = None):
+        if not isinstance(members, int) or isinstance(members, bool) or members < 1:
+            raise ValueError(f"SensorVerification: members = {members!r} must be a positive integer")
+        if fused is not None and not isinstance(fused, bool):
+            raise ValueError(f"SensorVerification: fused = {fused!r} must be None, True or False")
+        if fused and members > N.VERIFY_MAX_N:
+            raise ValueError(f"SensorVerification: the fused launches carry up to {N.VERIFY_MAX_N} members, got {members} (fused=False, or None)")
+        self._like = SensorLikelihood(decoder, n_patches, members, sensors, sigma=sigma)   # its checks, its folding of sigma
+        self.decoder, self.n_patches, self.members, self.sensors, self.fused, self.unbiased = decoder, n_patches, members, sensors, fused, bool(unbiased)
+
+    def _fused_for(self, device) -> bool:
+        if self.fused is not None:
+            return bool(self.fused)
+        return self.members <= N.VERIFY_MAX_N and device.type == "cuda"
+
+    def _operands(self, obs, precision, logw, into, B: int, device):
+        n, K = self.members, self.sensors.K
+        _check_sensor_operands("SensorVerification", obs, precision, B, K, device)
+        sp = self._like._sigma_precision(device)
+        if sp is not None:
+            precision = sp if precision is None else precision * sp
+        if logw is not None:
+            if not torch.is_tensor(logw) or not logw.is_floating_point() or logw.numel() != B * n or logw.dim() not in (1, 2) \
+                    or (logw.dim() == 2 and logw.shape[1] != n) or logw.device != device:
+                raise ValueError(f"SensorVerification: logw must be None or a floating-point [{B * n}] (or [{B}, {n}]) tensor of log-weights on {device}, got "
+                                 f"{(tuple(logw.shape), str(logw.device)) if torch.is_tensor(logw) else type(logw).__name__}")
+            logw = logw.detach().reshape(-1).to(torch.float32).contiguous()
+        if into is not None:
+            if not isinstance(into, EnsembleScores) or tuple(into.sums.shape) != (B, N.VERIFY_SUMS) or tuple(into.hist.shape) != (B, n + 1) \
+                    or into.sums.device != device or into.sums.dtype != torch.float64 or into.hist.dtype != torch.int64 \
+                    or not into.sums.is_contiguous() or not into.hist.is_contiguous():
+                raise ValueError(f"SensorVerification: into must be an earlier EnsembleScores for {B} histories of {n} members on {device}")
+        return obs.detach(), None if precision is None else precision.detach(), logw
+
+    def _verify(self, pred, obs, prec, logw, into) -> EnsembleScores:
+        with torch.no_grad():
+            if self._fused_for(pred.device):
+                out = None if into is None else dict(sums=into.sums, hist=into.hist)
+                r = ops.ensemble_verify(pred, obs, self.members, prec=prec, logw=logw, unbiased=self.unbiased, accumulate=into is not None, out=out)
+            else:
+                r = _composed_verify(pred, obs, prec, logw, self.members, self.unbiased)
+                if into is not None:
+                    r["sums"], r["hist"] = into.sums.add_(r["sums"]), into.hist.add_(r["hist"])
+        return EnsembleScores(**r)
+
+    def from_predictions(self, pred: torch.Tensor, obs: torch.Tensor, precision: Optional[torch.Tensor] = None, logw: Optional[torch.Tensor] = None,
+                         into: Optional[EnsembleScores] = None) -> EnsembleScores:
+        """The scores of predictions that exist already: pred float32 [B * members, K] in the sensors' given order (Decode.sensor_sse's predictions, the
+        third result of SensorKalman.transform)."""
+        n, K = self.members, self.sensors.K
+        if not torch.is_tensor(pred) or pred.dim() != 2 or pred.dtype != torch.float32 or pred.shape[0] < 1 or pred.shape[0] % n or pred.shape[1] != K:
+            raise ValueError(f"SensorVerification: pred must be a float32 [B * {n}, {K}] tensor, got "
+                             f"{(tuple(pred.shape), pred.dtype) if torch.is_tensor(pred) else type(pred).__name__}")
+        obs, prec, logw = self._operands(obs, precision, logw, into, pred.shape[0] // n, pred.device)
+        pred = pred.detach()
+        return self._verify(pred if pred.stride(1) == 1 and pred.stride(0) >= K else pred.contiguous(), obs, prec, logw, into)
+
+    def __call__(self, y: torch.Tensor, obs: torch.Tensor, precision: Optional[torch.Tensor] = None, logw: Optional[torch.Tensor] = None,
+                 into: Optional[EnsembleScores] = None) -> EnsembleScores:
+        P, n = self.n_patches, self.members
+        if not torch.is_tensor(y) or y.dim() != 3 or y.shape[-1] % P or y.shape[0] < 1:
+            raise ValueError(f"SensorVerification: y must be [B * members, n_groups, n_patches * D] with n_patches = {P}, got "
+                             f"{tuple(y.shape) if torch.is_tensor(y) else type(y).__name__}")
+        Bm, G, E = y.shape
+        if Bm % n:
+            raise ValueError(f"SensorVerification: the {Bm} trajectories of y are not a multiple of members = {n}")
+        obs, prec, logw = self._operands(obs, precision, logw, into, Bm // n, y.device)
+        z = y.detach().reshape(Bm, G, P, E // P).permute(0, 2, 1, 3)          # the re-layout of SensorLikelihood
+        _, pred = self.decoder.sensor_sse(z, self.sensors, obs, precision=prec, members=n, predictions=True)
+        return self._verify(pred, obs, prec, logw, into)

@@ -1433,3 +1433,78 @@ def ensemble_mix(y: torch.Tensor, D: torch.Tensor, n_patches: int, output: bool 
     fill_ensemble_mix(P, y, D, out, inc, n, n_patches)
     N.check(N.lib().sea_ensemble_mix(C.byref(P), N.dtype_code(y.dtype), N.stream_ptr()), "sea_ensemble_mix")
     return (out, inc) if output and increment else (out if output else inc)
+
+
+VERIFY_OUTPUTS = ("mean", "spread", "crps", "pit", "rank", "sums", "hist", "status")
+
+
+def fill_ensemble_verify(P: N.SeaEnsembleVerify, pred, obs, prec, logw, members: int, unbiased: bool, accumulate: bool, mean, spread, crps, pit, rank,
+                         sums, hist, status, work) -> None:
+    """The argument table of sea_ensemble_verify.  pred f32 [B * members, K], obs f32 [B, K], prec None / f32 [K] / [B, K] (unit inner strides), logw None /
+    f32 [B * members] contiguous; mean, spread, crps, pit f32 and rank int32 [B, K] contiguous or None; sums f64 [B, 8], hist int64 [B, members + 1],
+    status int32 [B] contiguous; work: a uint8 workspace of at least sea_ensemble_verify_ws_bytes(B, members, K) bytes."""
+    P.pred, P.obs, P.prec, P.logw = pred.data_ptr(), obs.data_ptr(), N.ptr(prec), N.ptr(logw)
+    P.mean, P.spread, P.crps, P.pit, P.rank = N.ptr(mean), N.ptr(spread), N.ptr(crps), N.ptr(pit), N.ptr(rank)
+    P.sums, P.hist, P.status, P.work = sums.data_ptr(), hist.data_ptr(), status.data_ptr(), work.data_ptr()
+    P.ld_pred, P.ld_obs = pred.stride(0), obs.stride(0)
+    P.ld_prec = 0 if prec is None or prec.dim() == 1 else prec.stride(0)
+    P.ld_out = obs.shape[1]
+    P.work_bytes = work.numel() * work.element_size()
+    P.B, P.N, P.K, P.unbiased, P.accumulate, P.pad_ = obs.shape[0], members, obs.shape[1], int(bool(unbiased)), int(bool(accumulate)), 0
+
+
+def ensemble_verify(pred: torch.Tensor, obs: torch.Tensor, members: int, prec: Optional[torch.Tensor] = None, logw: Optional[torch.Tensor] = None,
+                    unbiased: bool = True, accumulate: bool = False, out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+    """sea_ensemble_verify: CRPS, PIT, rank, mean and spread of an ensemble at the sensors, and per history the fp64 sums and the rank histogram
+    (include/sea_hip.h states the formulas).  pred f32 [B * members, K] (the predictions of Decode.sensor_sse), obs f32 [B, K], prec None, f32 [K] or
+    [B, K] (a host-side one is checked for finite values >= 0; one on the device is not read back), logw None or f32 [B * members] unnormalised
+    log-weights.  Returns a dict: mean, spread, crps, pit f32 [B, K], rank int32 [B, K], sums f64 [B, 8], hist int64 [B, members + 1], status int32 [B] —
+    on the device; nothing is read back.  out: a dict of tensors to write into, by those names; accumulate=True adds this call's sums and histogram
+    onto out["sums"] and out["hist"], which are then required."""
+    what = "ensemble_verify"
+    n = members
+    if not isinstance(n, int) or isinstance(n, bool) or n < 1 or n > N.VERIFY_MAX_N:
+        raise ValueError(f"{what}: members = {members!r} must be an integer in 1 .. {N.VERIFY_MAX_N}")
+    if not torch.is_tensor(obs) or obs.dim() != 2 or obs.dtype != torch.float32 or obs.shape[0] < 1 or obs.shape[1] < 1 or obs.stride(1) != 1:
+        raise ValueError(f"{what}: obs must be a float32 [B, K] tensor with unit inner stride, got {tuple(obs.shape) if torch.is_tensor(obs) else type(obs).__name__}")
+    B, K = obs.shape
+    dev = obs.device
+    if not torch.is_tensor(pred) or pred.dtype != torch.float32 or tuple(pred.shape) != (B * n, K) or pred.stride(1) != 1 or (pred.stride(0) < K and B * n > 1) \
+            or pred.device != dev:
+        raise ValueError(f"{what}: pred must be a float32 [{B * n}, {K}] tensor with unit inner stride on {dev}, got "
+                         f"{(tuple(pred.shape), pred.dtype, str(pred.device)) if torch.is_tensor(pred) else type(pred).__name__}")
+    if obs.stride(0) < K and B > 1:
+        raise ValueError(f"{what}: obs rows overlap (strides {obs.stride()})")
+    if prec is not None and (not torch.is_tensor(prec) or prec.dtype != torch.float32 or tuple(prec.shape) not in ((K,), (B, K)) or prec.stride(-1) != 1
+                             or prec.device != dev or (prec.dim() == 2 and B > 1 and prec.stride(0) < K)):
+        raise ValueError(f"{what}: prec must be None or a float32 [{K}] or [{B}, {K}] tensor with unit inner stride on {dev}, got "
+                         f"{(tuple(prec.shape), prec.dtype, str(prec.device)) if torch.is_tensor(prec) else type(prec).__name__}")
+    if prec is not None and prec.device.type == "cpu" and (not bool(torch.isfinite(prec).all()) or not bool((prec >= 0).all())):
+        raise ValueError(f"{what}: prec must be finite and >= 0")
+    if prec is not None and prec.dim() == 2 and prec.stride(0) < K:   # one history whose row stride says nothing: the [K] form
+        prec = prec[0]
+    if logw is not None and (not torch.is_tensor(logw) or logw.dtype != torch.float32 or tuple(logw.shape) != (B * n,) or not logw.is_contiguous() or logw.device != dev):
+        raise ValueError(f"{what}: logw must be None or a contiguous float32 [{B * n}] tensor on {dev}, got "
+                         f"{(tuple(logw.shape), logw.dtype, str(logw.device)) if torch.is_tensor(logw) else type(logw).__name__}")
+    if B > 65535:
+        raise ValueError(f"{what}: {B} histories; a launch carries up to 65535")
+    shapes = {"mean": ((B, K), torch.float32), "spread": ((B, K), torch.float32), "crps": ((B, K), torch.float32), "pit": ((B, K), torch.float32),
+              "rank": ((B, K), torch.int32), "sums": ((B, N.VERIFY_SUMS), torch.float64), "hist": ((B, n + 1), torch.int64), "status": ((B,), torch.int32)}
+    out = {} if out is None else out
+    if not isinstance(out, dict) or any(k not in shapes for k in out):
+        raise ValueError(f"{what}: out must be a dict with keys among {VERIFY_OUTPUTS}")
+    for k, t in out.items():
+        shape, dt = shapes[k]
+        if not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"{what}: out[{k!r}] must be a contiguous {dt} {list(shape)} tensor on {dev}")
+    if accumulate and ("sums" not in out or "hist" not in out):
+        raise ValueError(f"{what}: accumulate=True adds onto out['sums'] and out['hist']: both are required")
+    N.require_gpu(obs, f"{what} obs")   # every operand is on the readings' device (checked above)
+    res = {k: out[k] if k in out else torch.empty(shapes[k][0], device=dev, dtype=shapes[k][1]) for k in VERIFY_OUTPUTS}
+    work = torch.empty(int(N.lib().sea_ensemble_verify_ws_bytes(B, n, K)), device=dev, dtype=torch.uint8)
+    P = N.SeaEnsembleVerify()
+    fill_ensemble_verify(P, pred, obs, prec, logw, n, unbiased, accumulate, res["mean"], res["spread"], res["crps"], res["pit"], res["rank"], res["sums"],
+                         res["hist"], res["status"], work)
+    P.ld_obs, P.ld_pred = max(P.ld_obs, K), max(P.ld_pred, K)   # a single row: its stride is never used and may say anything
+    N.check(N.lib().sea_ensemble_verify(C.byref(P), N.stream_ptr()), "sea_ensemble_verify")
+    return res
