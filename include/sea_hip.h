@@ -715,6 +715,19 @@ typedef struct {
     const float* b3;     /* f32 [N3] or NULL */
     void* mod3;          /* act [M, N3], row stride ldmod3 */
     int32_t ldw3, ldmod3;
+    /* optional condition memo (memo_stamps != NULL; NULL: none, every launch computes everything).  The modulation rows of a row are functions of cond[m] and the
+     * weights alone.  A workgroup (32 rows) whose rows all carry the stamp {bits of cond[m], *memo_epoch} skips cond_mlp.2 of AdaLN_0 and the third layer: it reads
+     * its AdaLN_0 modulation rows from memo_mods, and mod3 is left as it is.  Any other workgroup computes as without a memo, stores its modulation rows to
+     * memo_mods and, at its end, writes its stamps.  The caller keeps stamps (zeroed once), memo_mods and mod3 between launches and changes *memo_epoch (never
+     * to 0) whenever a weight of these modules changes.  memo_count: hits / misses are counted per workgroup where SEA_TUNE=memo_count=1. */
+    uint32_t* memo_stamps;        /* u32 [M][2] */
+    void* memo_mods;              /* act [M, 2E], row stride ldmemo: [scale | shift] of AdaLN_0 */
+    const uint32_t* memo_epoch;   /* u32 [1], device memory */
+    int32_t* memo_count;          /* i32 [2] (hits, misses) or NULL */
+    uint32_t* memo_rows;          /* u32 [n_silu + 1][silu_M][2] or NULL, read from group 0 only: the stamps of the launch's ROW RIDERS, one set per silu group and
+                                   * one (the last) for the information-bottleneck rows.  A row-rider workgroup (64 rows) whose rows all match exits: its hidden /
+                                   * information-bottleneck rows of an earlier launch are still in the caller's buffers.  Any other computes and stamps its rows. */
+    int32_t ldmemo, pad_;
 } SeaAdalnQkv;
 /* silu / silu_c / silu_M, ib (both optional): row riders — hidden rows silu(w1 * silu_c[m] + b1) of up to 8 other modules (sea_silu_outer's groups) and the
  * information-bottleneck rows (sea_silu_outer_ib's SeaIbParams), evaluated by extra workgroups for launches further down the step. */

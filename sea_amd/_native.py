@@ -184,7 +184,8 @@ AQKV_MAX_SILU = 8
 class SeaAdalnQkv(C.Structure):
     _fields_ = [("X", _vp), ("cond", _vp), ("w1", _vp), ("b1", _vp), ("W2c", _vp), ("b2c", _vp), ("gamma", _vp), ("beta", _vp), ("Wqkv", _vp), ("bqkv", _vp),
                 ("Q", _vp), ("K", _vp), ("Vt", _vp), ("ldx", _i32), ("ldw2c", _i32), ("ldw", _i32), ("M", _i32), ("E", _i32), ("N3", _i32),
-                ("w13", _vp), ("b13", _vp), ("W3", _vp), ("b3", _vp), ("mod3", _vp), ("ldw3", _i32), ("ldmod3", _i32)]
+                ("w13", _vp), ("b13", _vp), ("W3", _vp), ("b3", _vp), ("mod3", _vp), ("ldw3", _i32), ("ldmod3", _i32),
+                ("memo_stamps", _vp), ("memo_mods", _vp), ("memo_epoch", _vp), ("memo_count", _vp), ("memo_rows", _vp), ("ldmemo", _i32), ("pad_", _i32)]   # the condition memo (NULL: none)
 
 
 MAX_MLP_GROUPS = 8

@@ -15,6 +15,8 @@
 //   - layer B (K = E): wave w owns 96 of the 3E output columns, [Wq; Wk; Wv] through the same rings; the epilogue stages the rotated / scaled values in LDS in
 //     the attention layouts and the stores leave as whole rows (Q, K: 64 B of a (head, step) row per 4 lanes; V^T: 8 steps of a (head, dim) row per lane).
 // Riders: 128 x 128 tiles of plain GEMMs of later launches (cond_mlp.2 of ln_cross) run on the CUs this launch leaves idle, as in chain.hip.
+// Condition memo (SeaAdalnQkv.memo_*, optional): the modulation rows depend on cond[m] and the weights alone; a workgroup whose rows all carry the stamp
+// {bits of cond[m], weight epoch} skips layers A and C and takes its modulation rows from a table an earlier launch left, a row-rider workgroup exits.
 #include "gemm_tile.hpp"
 #include "ib_rows.hpp"
 #include <stdlib.h>
@@ -72,6 +74,8 @@ __device__ __forceinline__ f32x4 aq_mma_first(const uint4& a, const uint4& b) {
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
 }
 
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
 struct AqkvCfg {
     static constexpr int E = 256, KC = 2 * E, BM = 32, NW = 8;
     static constexpr int KTA = KC / 64, KTB = E / 64;               // K-tiles of the two layers
@@ -99,6 +103,35 @@ __global__ __launch_bounds__(512) void adaln_qkv_kernel(const AqkvLaunch L) {
     if ((int)blockIdx.x >= total + L.rider_n) {   // ---- row riders (block-uniform)
         const int x = (int)blockIdx.x - total - L.rider_n;
         const int lane_ = threadIdx.x & 63, wave_ = threadIdx.x >> 6;
+        // The condition memo of the row riders (group 0's memo_rows != NULL): what a rider workgroup writes is a function of its 64 conditions and the weights, and
+        // its output rows stay in the caller's buffers between launches.  When every row's stamp {condition bits, weight epoch} in the workgroup's OWN set (one per
+        // silu group, one for the information-bottleneck rows: a set shared between workgroups of one launch would let a late one read what an early one wrote)
+        // equals what it sees, the workgroup exits; any other computes all its rows as without a memo and stamps them.  One wave decides, through LDS and a barrier.
+        uint32_t* rst = L.g[0].memo_stamps != nullptr ? L.g[0].memo_rows : nullptr;
+        uint32_t r_c = 0, r_e = 0;
+        int r_row = -1;   // wave 0, lane l: row l of the workgroup's 64 (or -1 behind the last row)
+        if (rst != nullptr) {
+            const int per_g_ = (L.M_r + 63) >> 6;
+            const int set = x < L.silu_wgs ? x / per_g_ : L.n_silu;
+            const int b0 = (x < L.silu_wgs ? x - set * per_g_ : x - L.silu_wgs) * 64;
+            rst += (int64_t)set * L.M_r * 2;
+            int ok = 1;
+            if (wave_ == 0 && b0 + lane_ < L.M_r) {
+                r_row = b0 + lane_;
+                r_c = __float_as_uint(L.cond_r[r_row]);
+                r_e = *L.g[0].memo_epoch;
+                const uint2 st = reinterpret_cast<const uint2*>(rst)[r_row];
+                ok = st.x == r_c && st.y == r_e;
+            }
+            const int all_ok = __all(ok);
+            if (threadIdx.x == 0) *reinterpret_cast<int*>(smem) = all_ok;
+            __syncthreads();
+            const bool r_hit = __builtin_amdgcn_readfirstlane(*reinterpret_cast<const int*>(smem)) != 0;
+            if (L.g[0].memo_count != nullptr && threadIdx.x == 0) atomicAdd(L.g[0].memo_count + (r_hit ? 0 : 1), 1);
+            if (r_hit) return;
+            // (stamped here already: no launch reads a stamp it writes, and the rows are complete when the launch is)
+            if (r_row >= 0) reinterpret_cast<uint2*>(rst)[r_row] = make_uint2(r_c, r_e);
+        }
         if (x < L.silu_wgs) {   // 64 rows of one group: a wave takes 8 of them with its slice of w1 / b1 in registers (rowops.hip: silu_outer_kernel)
             const int per_g = (L.M_r + 63) >> 6;
             const int gy = x / per_g;
@@ -253,6 +286,14 @@ __global__ __launch_bounds__(512) void adaln_qkv_kernel(const AqkvLaunch L) {
             load4(G.b3 + 32 * wave + 16 + 4 * g, b3o[1]);
         }
     }
+    // ---- the condition memo (G.memo_stamps != NULL; NULL: none of it, the launch as it always was).  The modulation rows are functions of (cond[m], weights): a
+    // row whose stamp {bits of cond[m], weight epoch} equals what this launch sees has its rows in G.memo_mods (AdaLN_0) and G.mod3 (ln_cross) already.  When ALL 32
+    // rows of the workgroup match — a HIT — layers A and C are skipped: neither W2c nor W3 is streamed.  The stamps are read here and written at the workgroup's
+    // end (on a miss); no launch reads a stamp it writes itself, so the kernel boundary is all the ordering there is.
+    const bool memo = G.memo_stamps != nullptr;   // (a kernel argument: uniform)
+    bool hit = false;
+    uint32_t my_c = 0, my_e = 0;                  // lane l < 32 of every wave: the stamp of row m0 + l as this launch sees it (wave 0 writes them back)
+    u32x4 tq0 = {0u, 0u, 0u, 0u}, tq1 = tq0, tq2 = tq0, tq3 = tq0;   // this thread's 16 scale | 16 shift columns of row prow in the table: requested before the decision, used on a hit
     // ---- the hidden rows of the condition MLP, generated: thread = 8 contraction indices (chunk kc8 of the 64) of the 4 rows 4 wave .. 4 wave + 3
     {
         const int kc8 = lane;                                  // 64 chunks of 8 = KC
@@ -269,28 +310,56 @@ __global__ __launch_bounds__(512) void adaln_qkv_kernel(const AqkvLaunch L) {
             const int m = m0 + wave * 4 + i < M ? m0 + wave * 4 + i : M - 1;
             asm volatile("global_load_dword %0, %1, off" : "=v"(cvr[i]) : "v"(G.cond + m) : "memory");
         }
+        if (memo) {
+            // The decision comes BEFORE the first counted piece: nothing is in the rings yet, so the compiler's own waits for these loads drain nothing.
+            const int ml = m0 + (lane & 31);
+            const int mc = ml < M ? ml : M - 1;
+            my_c = __float_as_uint(G.cond[mc]);
+            const uint2 st = reinterpret_cast<const uint2*>(G.memo_stamps)[mc];
+            my_e = *G.memo_epoch;
+            const char* trow = static_cast<const char*>(G.memo_mods) + ((int64_t)mrow * G.ldmemo + pc0) * 2;
+            tq0 = *reinterpret_cast<const u32x4*>(trow);
+            tq1 = *reinterpret_cast<const u32x4*>(trow + 16);
+            tq2 = *reinterpret_cast<const u32x4*>(trow + E * 2);
+            tq3 = *reinterpret_cast<const u32x4*>(trow + E * 2 + 16);
+            // every load of the prologue has landed, the untracked ones too: on a hit their registers are free for other values.  (The table pieces are operands so
+            // that the compiler waits for them HERE on both paths: left pending on a miss, its wait would sit in the row pass and drain layer B's slots in flight.)
+            asm volatile("s_waitcnt vmcnt(0)" : "+v"(w1a), "+v"(w1b), "+v"(b1a), "+v"(b1b), "+v"(cvr[0]), "+v"(cvr[1]), "+v"(cvr[2]), "+v"(cvr[3]), "+v"(tq0), "+v"(tq1), "+v"(tq2), "+v"(tq3) : : "memory");
+            const int ok = ml >= M || (st.x == my_c && st.y == my_e);   // (rows behind the last one: nothing to compute)
+            const int all_ok = __all(ok);
+            // ONE wave decides, every wave reads its answer behind a barrier: the branch is block-uniform by construction.  The word sits in wave 0's ring slot 7,
+            // which nothing fills before the next barrier (a miss: slot_a(7) is issued by layer A's first iteration; a hit: the table rows go there behind it).
+            int* flag = reinterpret_cast<int*>(smem + C::RING_OFF + (C::RSA - 1) * C::SLOT);
+            if (tid == 0) *flag = all_ok;
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+            hit = __builtin_amdgcn_readfirstlane(*flag) != 0;
+            if (G.memo_count != nullptr && tid == 0) atomicAdd(G.memo_count + (hit ? 0 : 1), 1);
+        }
+        if (!hit) {   // (a miss, or no memo)
 #pragma unroll
-        for (int k = 0; k < C::RSA - 1; ++k) slot_a(k);
-        asm volatile("s_waitcnt vmcnt(%8)" : "+v"(w1a), "+v"(w1b), "+v"(b1a), "+v"(b1b), "+v"(cvr[0]), "+v"(cvr[1]), "+v"(cvr[2]), "+v"(cvr[3]) : "n"(2 * (AqkvCfg::RSA - 1)) : "memory");
-        const float w1[8] = {w1a[0], w1a[1], w1a[2], w1a[3], w1b[0], w1b[1], w1b[2], w1b[3]};
-        const float b1[8] = {b1a[0], b1a[1], b1a[2], b1a[3], b1b[0], b1b[1], b1b[2], b1b[3]};
-        const int kt = kc8 >> 3, ck = kc8 & 7;
+            for (int k = 0; k < C::RSA - 1; ++k) slot_a(k);
+            asm volatile("s_waitcnt vmcnt(%8)" : "+v"(w1a), "+v"(w1b), "+v"(b1a), "+v"(b1b), "+v"(cvr[0]), "+v"(cvr[1]), "+v"(cvr[2]), "+v"(cvr[3]) : "n"(2 * (AqkvCfg::RSA - 1)) : "memory");
+            const float w1[8] = {w1a[0], w1a[1], w1a[2], w1a[3], w1b[0], w1b[1], w1b[2], w1b[3]};
+            const float b1[8] = {b1a[0], b1a[1], b1a[2], b1a[3], b1b[0], b1b[1], b1b[2], b1b[3]};
+            const int kt = kc8 >> 3, ck = kc8 & 7;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int row = wave * 4 + i;
-            const float cv = cvr[i];
-            bf16x8 hv;
+            for (int i = 0; i < 4; ++i) {
+                const int row = wave * 4 + i;
+                const float cv = cvr[i];
+                bf16x8 hv;
 #pragma unroll
-            for (int e = 0; e < 8; ++e) hv[e] = (__bf16)silu_f(w1[e] * cv + b1[e]);
-            *reinterpret_cast<bf16x8*>(smem + kt * (BM * 128) + row * 128 + ((ck ^ (row & 7)) << 4)) = hv;
+                for (int e = 0; e < 8; ++e) hv[e] = (__bf16)silu_f(w1[e] * cv + b1[e]);
+                *reinterpret_cast<bf16x8*>(smem + kt * (BM * 128) + row * 128 + ((ck ^ (row & 7)) << 4)) = hv;
+            }
         }
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();   // the hidden rows are complete
+    __builtin_amdgcn_s_barrier();   // the hidden rows are complete (a hit: every wave has read the decision, so its word may be overwritten)
     stamp();   // 1: hidden rows generated
     // ================================================================================================ layer A: the modulation of this wave's 32 outputs
     f32x4 acc[2][4];
-    {
+    if (!hit) {
         uint4 af[2][2];
 #pragma unroll
         for (int k = 0; k < 4 * KTA; ++k) {
@@ -320,7 +389,7 @@ __global__ __launch_bounds__(512) void adaln_qkv_kernel(const AqkvLaunch L) {
         }
     }
     stamp();   // 2: layer A's loop
-    // Every value the compiler loaded itself at the start is "used" HERE, where the loop's last wait has emptied the memory queue anyway: its wait for a load sits
+    // Every value the compiler loaded itself at the start is "used" HERE, where the loop's last wait (a memo hit: the decision's) has emptied the memory queue anyway: its wait for a load sits
     // at the first use and counts only the loads it issued itself — at a first use further down it would drain the counted LDS-DMA pieces in flight there
     // (seen: 1.5 us in front of the row pass, whose x / gamma / beta had landed ten microseconds earlier).
 #pragma unroll
@@ -337,8 +406,16 @@ __global__ __launch_bounds__(512) void adaln_qkv_kernel(const AqkvLaunch L) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this wave's fragment reads are retired: its ring takes layer B's first slots
 #pragma unroll
     for (int k = 0; k < C::RSB - 1; ++k) slot_b(k);
-    // this wave's part of the modulation, + bias, as bf16 (the precision the two-launch form stores): row mb * 16 + r, columns [scale 32 | shift 32]
-    {
+    if (hit) {
+        // the modulation rows from the table, to the place and in the bf16 values layer A leaves them: columns pc0 .. pc0 + 15 are columns 16 (pl & 1) .. of the
+        // part of wave pl >> 1 (the row pass below reads exactly these four pieces back)
+        char* mp = smem + C::RING_OFF + (pl >> 1) * C::WAVE_RING + C::MOD_OFF + prow * 128 + (pl & 1) * 32;
+        *reinterpret_cast<u32x4*>(mp) = tq0;
+        *reinterpret_cast<u32x4*>(mp + 16) = tq1;
+        *reinterpret_cast<u32x4*>(mp + 64) = tq2;
+        *reinterpret_cast<u32x4*>(mp + 80) = tq3;
+    } else {
+        // this wave's part of the modulation, + bias, as bf16 (the precision the two-launch form stores): row mb * 16 + r, columns [scale 32 | shift 32]
         char* mp = smem + C::RING_OFF + wave * C::WAVE_RING + C::MOD_OFF;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -385,6 +462,13 @@ __global__ __launch_bounds__(512) void adaln_qkv_kernel(const AqkvLaunch L) {
         load8(reinterpret_cast<const T*>(mp + 16), *reinterpret_cast<float(*)[8]>(mw + 8));
         load8(reinterpret_cast<const T*>(mp + 64), *reinterpret_cast<float(*)[8]>(mb));
         load8(reinterpret_cast<const T*>(mp + 80), *reinterpret_cast<float(*)[8]>(mb + 8));
+        if (memo && !hit && rok) {   // a miss leaves the same bf16 values in the table for the next launches (stores only: a load here would drain layer B's slots in flight)
+            char* trow = static_cast<char*>(G.memo_mods) + ((int64_t)mrow * G.ldmemo + pc0) * 2;
+            *reinterpret_cast<uint4*>(trow) = *reinterpret_cast<const uint4*>(mp);
+            *reinterpret_cast<uint4*>(trow + 16) = *reinterpret_cast<const uint4*>(mp + 16);
+            *reinterpret_cast<uint4*>(trow + E * 2) = *reinterpret_cast<const uint4*>(mp + 64);
+            *reinterpret_cast<uint4*>(trow + E * 2 + 16) = *reinterpret_cast<const uint4*>(mp + 80);
+        }
 #pragma unroll
         for (int c = 0; c < 16; c += 8) {
             const int col = pc0 + c, kt = col >> 6, ck = (col & 63) >> 3;
@@ -404,8 +488,9 @@ __global__ __launch_bounds__(512) void adaln_qkv_kernel(const AqkvLaunch L) {
     }
     stamp();   // 4: row pass
     // layer C's operand: the hidden rows silu(w13 * c + b13) of the third matrix, K-tile kt into the spare 4 KiB of wave kt's ring region (the modulation parts
-    // the row pass has just read); consumed behind layer B's slots, after the barrier in front of slot 6 KTB
-    if (has3) {
+    // the row pass has just read); consumed behind layer B's slots, after the barrier in front of slot 6 KTB.  A memo hit skips the layer: mod3 in memory is right
+    const bool do3 = has3 && !hit;   // (block-uniform)
+    if (do3) {
         const int kc8 = tid & 31, kt = kc8 >> 3, ck = kc8 & 7;
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
@@ -424,7 +509,9 @@ __global__ __launch_bounds__(512) void adaln_qkv_kernel(const AqkvLaunch L) {
 #pragma unroll
         for (int k = 0; k < NTOT; ++k) {
             const int after_ = NTOT - 1 - k < C::RSB - 2 ? NTOT - 1 - k : C::RSB - 2;
+            const int after_b = 6 * KTB - 1 - k < C::RSB - 2 ? 6 * KTB - 1 - k : C::RSB - 2;   // ... when layer C's slots do not follow (a memo hit)
             if (k >= 6 * KTB) {   // ---- a slot of layer C
+                if (!do3) continue;
                 const int k3 = k - 6 * KTB, kt = k3 >> 1, j = k3 & 1;
                 aq_wait_n(after_);
                 if (k3 == 0) __builtin_amdgcn_s_barrier();   // every wave's share of the generated rows is in LDS (their writes were retired by the wait above)
@@ -452,10 +539,11 @@ __global__ __launch_bounds__(512) void adaln_qkv_kernel(const AqkvLaunch L) {
                 continue;
             }
             const int kt = k / 6, j = k - kt * 6;
-            aq_wait_n(after_);
+            if (do3 || after_b == after_) aq_wait_n(after_);
+            else aq_wait_n(after_b);
             if (k + C::RSB - 1 < NTOT) {
                 if (k + C::RSB - 1 < 6 * KTB) slot_b(k + C::RSB - 1);
-                else slot_c(k + C::RSB - 1);
+                else if (do3) slot_c(k + C::RSB - 1);
             }
             if (j == 0) {
 #pragma unroll
@@ -513,7 +601,7 @@ __global__ __launch_bounds__(512) void adaln_qkv_kernel(const AqkvLaunch L) {
             }
         }
     }
-    if (has3) {   // layer C's 32 columns of this wave, + bias, bf16, behind the staged q | k | v: [32 rows][K3 columns] at a pitch of + 16 bytes
+    if (do3) {   // layer C's 32 columns of this wave, + bias, bf16, behind the staged q | k | v: [32 rows][K3 columns] at a pitch of + 16 bytes
 #pragma unroll
         for (int j = 0; j < 2; ++j)
 #pragma unroll
@@ -577,7 +665,7 @@ __global__ __launch_bounds__(512) void adaln_qkv_kernel(const AqkvLaunch L) {
             }
         }
     }
-    if (has3) {   // the third layer's rows: 32 pieces of 16 bytes per row
+    if (do3) {   // the third layer's rows: 32 pieces of 16 bytes per row
         T* M3 = static_cast<T*>(G.mod3);
         for (int id = tid; id < BM * (C::K3 / 8); id += 512) {
             const int row = id >> 5, pc = id & 31;
@@ -586,6 +674,8 @@ __global__ __launch_bounds__(512) void adaln_qkv_kernel(const AqkvLaunch L) {
         }
     }
     stamp();   // 10: V^T stored (issued)
+    // a miss stamps its rows LAST (the probe exits above write none): the table rows and mod3 of this workgroup are then those of (cond[m], epoch)
+    if (memo && !hit && wave == 0 && lane < 32 && m0 + lane < M) reinterpret_cast<uint2*>(G.memo_stamps)[m0 + lane] = make_uint2(my_c, my_e);
 }
 
 extern "C" int sea_adaln_qkv(const SeaAdalnQkv* groups, int n_groups, const SeaQkvCommon* common, const SeaGemmGroup* riders, int n_riders, const SeaSiluGroup* silu, int n_silu,
@@ -600,6 +690,7 @@ extern "C" int sea_adaln_qkv(const SeaAdalnQkv* groups, int n_groups, const SeaQ
                 common->T, common->pos0, common->cap);
     AqkvLaunch L;
     memset(&L, 0, sizeof(L));
+    const bool memo_count = sea_tune("memo_count", 0) != 0;   // (read at every call: a test switches it on for one plan)
     int total = 0;
     for (int i = 0; i < n_groups; ++i) {
         const SeaAdalnQkv& G = groups[i];
@@ -615,7 +706,13 @@ extern "C" int sea_adaln_qkv(const SeaAdalnQkv* groups, int n_groups, const SeaQ
                             sea_aligned16(G.W3) && sea_aligned16(G.b3) && sea_aligned16(G.mod3),
                         "sea_adaln_qkv[%d]: third layer: null / misaligned pointer, bad stride, or N3 = %d != 256", i, G.N3);
         }
+        if (G.memo_stamps != nullptr) {
+            SEA_REQUIRE(G.memo_mods && G.memo_epoch && G.ldmemo % 8 == 0 && G.ldmemo >= 2 * E && sea_aligned16(G.memo_mods) && ((uintptr_t)G.memo_stamps & 7) == 0 &&
+                            ((uintptr_t)G.memo_epoch & 3) == 0 && ((uintptr_t)G.memo_count & 3) == 0 && ((uintptr_t)G.memo_rows & 7) == 0,
+                        "sea_adaln_qkv[%d]: condition memo: null / misaligned pointer or bad stride (ldmemo=%d)", i, G.ldmemo);
+        }
         L.g[i] = G;
+        if (!memo_count) L.g[i].memo_count = nullptr;
         L.tile_start[i] = total;
         total += (G.M + 31) / 32;
     }

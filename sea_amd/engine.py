@@ -105,6 +105,24 @@ def _kv_pairs(src: dict, dst: dict):
                         yield (src["Kc"][l][i][j], src["Vc"][l][i][j]), (dst["Kc"][l][i][j], dst["Vc"][l][i][j])
 
 
+class _WatchedParameter(torch.nn.Parameter):
+    """The class FlatParams gives the model's parameters: `p.data` hands out a tensor with a version counter of its own, so an in-place write through it
+    (`p.data.mul_(s)`, `p.data.copy_(w)`: the usual way to edit a weight) moves neither flat32._version nor p._version and nothing on the host could see
+    it.  Here every READ of `.data` is counted, process-wide; a FlatParams whose count is behind takes the weights as possibly changed: its next sync()
+    refreshes the shadow and moves the weight epoch on.  A read that wrote nothing costs one redundant conversion (in every engine of the process: the
+    parameter holds no reference to its store, so it pickles and copies like any other).  Nothing in this package reads `.data`."""
+    reads = 0
+
+    @property
+    def data(self):
+        _WatchedParameter.reads += 1
+        return torch.Tensor.data.__get__(self)
+
+    @data.setter
+    def data(self, value):
+        torch.Tensor.data.__set__(self, value)
+
+
 class FlatParams:
     """One contiguous fp32 buffer holding every parameter of the model (+ the activation-dtype shadow)."""
 
@@ -141,6 +159,9 @@ class FlatParams:
                 view = self.flat32[o:o + p.numel()].view(shp)
                 view.copy_(p.detach().to(device=device, dtype=torch.float32))
                 p.data = view  # the module's parameter now aliases the flat buffer
+                if type(p) is torch.nn.Parameter:
+                    p.__class__ = _WatchedParameter
+        self._data_reads = _WatchedParameter.reads   # reads of a parameter's `.data` seen by the last sync
         self.live_names = [n for _, n, _ in keyed if not is_dead(n)]
         self.phase_of = {n: grad_phase(model, n) for _, n, _ in keyed if not is_dead(n)}
         self.flat_act = self.flat32 if act_dtype == torch.float32 else torch.empty(self.n_total, device=device, dtype=act_dtype)
@@ -149,6 +170,9 @@ class FlatParams:
         self._t_total = 0
         self._synced_version = -1
         self._synced_T_version = -1
+        # the weight epoch of the condition memo (plan_forms.PlanForms.cond_memo): a DEVICE word the kernels read themselves — a captured graph bakes kernel
+        # arguments in, not what a pointer leads to.  Starts at 1: a zeroed stamp matches no epoch.  weights_changed() is its only writer
+        self.memo_epoch = torch.ones(1, device=device, dtype=torch.int32)
         self.sync()
 
     # -- views
@@ -223,10 +247,19 @@ class FlatParams:
         if self.act_dtype == torch.float32:
             return
         v = self.flat32._version
-        if force or v != self._synced_version:
+        if force or v != self._synced_version or self._data_reads != _WatchedParameter.reads:
+            self._data_reads = _WatchedParameter.reads
             N.check(N.lib().sea_convert_f32_to_act(self.flat32.data_ptr(), self.n_total, self.flat_act.data_ptr(), self.n_total, 1,
                                                    self.n_total, N.dtype_code(self.act_dtype), N.stream_ptr()), "weight shadow")
             self._synced_version = v
+            self.weights_changed()   # (the fp32 vectors the kernels read from flat32 itself moved the version too)
+
+    def weights_changed(self) -> None:
+        """Every writer of the activation shadow `flat_act` calls this behind its write, on the launch stream: sync() above when it converts, and the two AdamW
+        launches of optim.FlatAdamW.step, which write the shadow through raw pointers.  One tiny device write moves the weight epoch on; a row stamped under
+        an older epoch no longer matches (adaln_qkv.hip), so every memoised condition product is computed again from the new weights.  (The word wraps to 0,
+        the epoch of a zeroed stamp, after 2^32 updates.)"""
+        self.memo_epoch.add_(1)
 
 
 class _Rec:
@@ -310,6 +343,7 @@ class Plan:
         self._mods: Dict[str, torch.Tensor] = {}        # AdaLN modulations, prefix -> [M, 2d] (_cond_mods)
         self._riders: Optional[_Riders] = None          # rider work of the chain launches (forms.riders)
         self._front = None                              # rider plans: (cond_mlp.2 operands of the front modules, row riders of the one-launch front), see _cond_mods
+        self.memo_count: Optional[torch.Tensor] = None  # forms.cond_memo: int32 [2], hits / misses of the condition memo's workgroups (SEA_TUNE=memo_count=1)
         self._build()
         self._find_hoisted()
         self._clist = None          # (SeaLaunchRec array, [(rec index, field, args list, args index)]) for sea_run_list
@@ -931,14 +965,21 @@ class Plan:
         launch leaves idle, or — forms.front3 — as every field's third layer, the silu / information-bottleneck rows of _cond_mods then being its row riders."""
         P, F, E, D, M, Eo, fm = self.eng.params, self.F, self.E, self.D, self.M, self.Eo, self.forms
         hid, rows = self._front if fm.front_chain else (None, None)
+        if fm.cond_memo and self.memo_count is None:
+            self.memo_count = self._buf(2, dtype=torch.int32, zero=True)   # (hits, misses) in workgroups, counted where SEA_TUNE=memo_count=1
         arr = (N.SeaAdalnQkv * F)()
         for g_, i in zip(arr, range(F)):
             mp, lc = f"{pre}ln.exp.{i}.0.", f"{pre}ln_cross.{i}."
             third = dict(w1=P.f32_vec(lc + "cond_mlp.0.weight", 2 * D), b1=P.f32_vec(lc + "cond_mlp.0.bias"), W=P.act(lc + "cond_mlp.2.weight"), bias=P.f32_vec(lc + "cond_mlp.2.bias"),
                          out=self._mods[lc]) if fm.front3 else None   # ln_cross_i's modulation as the launch's third layer
+            # the condition memo: a stamp per row, zeroed once (epoch 0 matches nothing); the table is the [M, 2E] modulation buffer _cond_mods keeps for the module.
+            # Both, and the third layer's output, are written by this launch only and live as long as the plan: what a forward leaves is there for the next
+            memo = dict(stamps=self._buf(M, 2, dtype=torch.int32, zero=True), mods=self._mods[mp], epoch=P.memo_epoch, count=self.memo_count) if fm.cond_memo else None
+            if memo is not None and i == 0 and rows is not None:   # the row riders' stamps: a set per silu group and one for the information-bottleneck rows
+                memo["rows"] = self._buf(rows[1] + 1, M, 2, dtype=torch.int32, zero=True)
             ops.fill_adaln_qkv(g_, X=xr[i], cond=None, w1=P.f32_vec(mp + "cond_mlp.0.weight", 2 * E), b1=P.f32_vec(mp + "cond_mlp.0.bias"), W2c=P.act(mp + "cond_mlp.2.weight"),
                                b2c=P.f32_vec(mp + "cond_mlp.2.bias"), gamma=P.f32_vec(mp + "weight"), beta=P.f32_vec(mp + "bias"), Wqkv=P.act(f"{pre}attn.self.{i}.q.weight", 3 * E),
-                               bqkv=P.f32_vec(f"{pre}attn.self.{i}.q.bias", 3 * E), Q=Qs[i], K=Ks[i], Vt=Vs[i], ldx=(F * Eo if first else None), third=third)
+                               bqkv=P.f32_vec(f"{pre}attn.self.{i}.q.bias", 3 * E), Q=Qs[i], K=Ks[i], Vt=Vs[i], ldx=(F * Eo if first else None), third=third, memo=memo)
             g_.M = M
             self._c_patches.append((g_, "cond"))
             if first:
@@ -1128,7 +1169,7 @@ class Plan:
         for t in self._keep:
             R.add_tensor(t, "plan workspace")
         P = eng.params
-        for t, label in ((P.flat32, "flat32"), (P.flat_act, "flat_act"), (P.flat_actT, "flat_actT"), (eng.grads, "grads"), (eng.rope_self, "rope_self"),
+        for t, label in ((P.flat32, "flat32"), (P.flat_act, "flat_act"), (P.flat_actT, "flat_actT"), (P.memo_epoch, "weight epoch"), (eng.grads, "grads"), (eng.rope_self, "rope_self"),
                          (eng.rope_cross, "rope_cross"), (getattr(self, "_ws_colsum", None), "column-sum workspace"), (self._zero_ib, "zero rows")):
             R.add_tensor(t, label)
         for t in eng._eyes.values():
@@ -1411,6 +1452,10 @@ class TemporalEngine:
             raise NotImplementedError("sea_amd: info-bottleneck hidden width (scale_ratio) must be <= 64")
         self.model, self.device, self.act_dtype = model, device, act_dtype
         self.params = FlatParams(model, device, act_dtype)
+        # load_state_dict copies into the parameters, which alias flat32 but count their versions themselves (flat32._version does not move): the shadow is
+        # refreshed — and the condition memo's weight epoch moved on — right behind the load.  (A write through `p.data` moves no version at all:
+        # _WatchedParameter reports the read of `.data` instead.)
+        model.register_load_state_dict_post_hook(lambda module, incompatible: self.params.sync(force=True))
         blk = model.blocks[0]
         self.rope_self = torch.view_as_real(blk.attn["self"][0].freqs_cis.to(device)).contiguous()
         self.rope_cross = None

@@ -332,9 +332,16 @@ def adaln_qkv_supported(dtype: torch.dtype, E: int, H: int) -> bool:
     return dtype == torch.bfloat16 and E == 256 and H > 0 and E % H == 0 and E // H in (16, 32)
 
 
-def fill_adaln_qkv(g: N.SeaAdalnQkv, X, cond, w1, b1, W2c, b2c, gamma, beta, Wqkv, bqkv, Q, K, Vt, ldx=None, third=None) -> None:
+def fill_adaln_qkv(g: N.SeaAdalnQkv, X, cond, w1, b1, W2c, b2c, gamma, beta, Wqkv, bqkv, Q, K, Vt, ldx=None, third=None, memo=None) -> None:
     """One group of sea_adaln_qkv: X f32 [M, E] (row stride ldx), cond f32 [M], cond_mlp.0 (w1, b1 f32 [2E]), cond_mlp.2 (W2c act [2E, 2E], b2c), AdaLN_0's gamma / beta,
-    [Wq; Wk; Wv] act [3E, E] + bias, the attention operands Q [B,H,T,hd] / K [B,H,cap,hd] / Vt [B,H,hd,cap]."""
+    [Wq; Wk; Wv] act [3E, E] + bias, the attention operands Q [B,H,T,hd] / K [B,H,cap,hd] / Vt [B,H,hd,cap].  memo: dict(stamps int32 [M, 2] zeroed once, mods act
+    [M, 2E], epoch int32 [1], count int32 [2], rows int32 [n_silu + 1, M, 2] zeroed once: the row riders' stamps, group 0 only) — the condition memo, buffers the caller keeps between launches (None: no memo, the pointers stay NULL)."""
+    if memo is not None:
+        st, tab = memo["stamps"], memo["mods"]
+        if st.dtype != torch.int32 or tuple(st.shape) != (X.shape[0], 2) or not st.is_contiguous() or tab.shape[0] != X.shape[0] or tab.shape[1] != W2c.shape[0] or tab.stride(1) != 1:
+            raise ValueError(f"adaln_qkv memo: stamps {tuple(st.shape)} {st.dtype} / mods {tuple(tab.shape)} do not fit M = {X.shape[0]}, 2E = {W2c.shape[0]}")
+        g.memo_stamps, g.memo_mods, g.ldmemo = st.data_ptr(), tab.data_ptr(), tab.stride(0)
+        g.memo_epoch, g.memo_count, g.memo_rows = memo["epoch"].data_ptr(), N.ptr(memo.get("count")), N.ptr(memo.get("rows"))
     g.X, g.ldx, g.cond = X.data_ptr(), (ldx if ldx is not None else X.stride(0)), N.ptr(cond)
     g.w1, g.b1, g.W2c, g.ldw2c, g.b2c = w1.data_ptr(), b1.data_ptr(), W2c.data_ptr(), W2c.stride(0), N.ptr(b2c)
     g.gamma, g.beta, g.Wqkv, g.ldw, g.bqkv = gamma.data_ptr(), N.ptr(beta), Wqkv.data_ptr(), Wqkv.stride(0), N.ptr(bqkv)

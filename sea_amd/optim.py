@@ -161,6 +161,8 @@ class FlatAdamW(torch.optim.Optimizer):
                                          float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]),
                                          float(self.grad_scale), self._ctl.data_ptr(), N.stream_ptr()), "sea_adamw_flat_ctl")
             P._synced_version = P.flat32._version   # as below (a skipped step wrote nothing: the refresh is then redundant, not wrong)
+            if shadow is not None:
+                P.weights_changed()                 # (the kernel wrote the shadow through raw pointers: the condition memo's weight epoch moves on)
             P.sync_transposed(force=True)
             return loss
         self._step += 1
@@ -170,6 +172,8 @@ class FlatAdamW(torch.optim.Optimizer):
                                        float(self.grad_scale), N.stream_ptr()), "sea_adamw_flat")
         # the kernel wrote through raw pointers: mark both shadows as current for the row-major one, stale for the transposed one
         P._synced_version = P.flat32._version
+        if shadow is not None:
+            P.weights_changed()
         P.sync_transposed(force=True)
         return loss
 

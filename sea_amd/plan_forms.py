@@ -5,7 +5,7 @@ are hoisted, the SEA_PLAN / SEA_KV switches — to a `PlanForms`; it touches no 
 can be read off (and tested) without a GPU.  engine.Plan stores the result as `plan.forms`; the code that emits the launches only reads it."""
 from __future__ import annotations
 
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import Dict, Optional, Tuple
 
 import torch
@@ -106,6 +106,13 @@ class PlanForms:
     # (the norm re-reads the rows the proj has just written: 100 MB) -> one.  SEA_PLAN=norm=0 / projnorm=0 keep the two launches.
     proj_norm: bool
     splitk: bool         # SEA_PLAN=splitk=0 keeps the single launch where engine.Plan._gemm_splitk would split a long contraction
+    # The condition memo of the one-launch front: the AdaLN modulation rows are functions of one condition scalar per row and the weights, and
+    # in a rollout's recompute loop, a repeated window or a graph replay the conditions of (nearly) all rows are those of the forward before.  The plan keeps the
+    # AdaLN_0 modulation rows, a stamp {condition bits, weight epoch} per row and the ln_cross modulation between forwards; a workgroup of sea_adaln_qkv whose 32
+    # stamps match what it sees skips cond_mlp.2 of AdaLN_0 and of ln_cross (two thirds of the launch's weight stream).  Decided on the device, by value.
+    # Where front_chain and riders; SEA_PLAN=cond_memo=0 switches it off (the reference form of tests/test_cond_memo_gpu.py).  Not part of a PlanForms'
+    # equality: it changes no launch, only optional pointers of one.
+    cond_memo: bool = field(default=False, compare=False)
 
     @property
     def one_launch_front(self) -> bool:
@@ -176,4 +183,5 @@ def resolve_forms(model, B: int, T: int, mode: str, dt: torch.dtype, kind: str =
         hidden_pad=(64 if inference and S % 1024 == 0 else 0), front_chain=front_chain, front3=front3, adaln_front=adaln_front, front_big=front_big,
         mlp_fc1=mlp_fc1, mlp_norm_in=mlp_norm_in, mlp_block=mlp_block, mlp_fc2_proj=mlp_fc2_proj,
         down_norm=(fuse_norm if inference else kind == TRAINING and sw("norm", "1") != "0") and D <= 256 and D % 16 == 0,
-        proj_norm=fuse_norm and Eo <= 256 and Eo % 16 == 0 and Eo == E and sw("projnorm", "1") != "0", splitk=sw("splitk", "1") != "0")
+        proj_norm=fuse_norm and Eo <= 256 and Eo % 16 == 0 and Eo == E and sw("projnorm", "1") != "0", splitk=sw("splitk", "1") != "0",
+        cond_memo=front_chain and riders and sw("cond_memo", "1") != "0")

@@ -157,6 +157,14 @@ def _extents(st, esz: int) -> Iterable[Tuple[str, int, int]]:
             yield "b13", st.b13, st.N3 * f32
             yield "W3", st.W3, ((st.N3 - 1) * st.ldw3 + st.N3) * esz
             yield "mod3", st.mod3, ((st.M - 1) * st.ldmod3 + st.N3) * esz
+        if st.memo_stamps:   # the condition memo: a {condition bits, epoch} pair per row, the [M, 2E] table, the epoch word, the optional counters
+            yield "memo_stamps", st.memo_stamps, st.M * 8
+            yield "memo_mods", st.memo_mods, ((st.M - 1) * st.ldmemo + 2 * E) * esz
+            yield "memo_epoch", st.memo_epoch, 4
+            if st.memo_count:
+                yield "memo_count", st.memo_count, 8
+            if st.memo_rows:   # (at least the information-bottleneck set; the launch's silu group count is not in this struct)
+                yield "memo_rows", st.memo_rows, st.M * 8
     elif isinstance(st, N.SeaRowChain):
         K2 = st.D if st.n_seg > 0 else st.E
         for s_ in range(st.n_seg):
