@@ -43,9 +43,10 @@ const char* sea_last_error(void);
 /* The kernel form the calling thread's last noted launch took, for tests: a static string such as "gemm.tile64" ("" before any noted launch) and
  * two small integers whose meaning depends on the launcher (a / b may be NULL).  Noted by sea_gemm_grouped ("gemm.skinny", "gemm.skinny_long",
  * "gemm.ws", "gemm.256", "gemm.tile64", "gemm.tile128"; a = 1 if the LDS-DMA ring is taken, b = its stages), sea_gemm_rownorm ("gemm_norm.rows16",
- * "gemm_norm.rows16_dma", "gemm_norm.rows64"), sea_attention_fwd ("attn.row", "attn.split4", "attn.split2", "attn.split1"; a = 1 if paired) and
- * sea_wgrad_grouped ("wgrad.tile64", "wgrad.tile128", "wgrad.tile256"; a = the largest split count over the groups, b = 1 if any group takes the
- * plain store).  Host only.  (An addition to ABI version 8; no new struct.) */
+ * "gemm_norm.rows16_dma", "gemm_norm.rows64"), sea_attention_fwd ("attn.row", "attn.split4", "attn.split2", "attn.split1"; a = 1 if paired),
+ * sea_attention_bwd ("attn_bwd" at head dims 8 / 16 / 32 / 64 / 128 / 256, "attn_bwd.masked" at the other widths; a = the mode bits of the dQ kernel,
+ * b = those of the dK / dV kernel: 1 XCD-local order, 2 paired tiles) and sea_wgrad_grouped ("wgrad.tile64", "wgrad.tile128", "wgrad.tile256"; a = the
+ * largest split count over the groups, b = 1 if any group takes the plain store).  Host only.  (An addition to ABI version 8; no new struct.) */
 const char* sea_last_form(int* a, int* b);
 /* sizeof of every ABI struct in declaration order (SeaGemmGroup, SeaQkvGroup, SeaQkvCommon, SeaAttnProblem,
  * SeaAttnParams, SeaNormGroup, SeaSiluGroup, SeaIbParams, ..., SeaLaunchRec, SeaGemmNormGroup, SeaExchangeTail, SeaMlpGroup, SeaMlp2Group, SeaKvNorm, SeaKvField, SeaKvPair, SeaKvLayer, SeaKvGlobal, SeaStepPatch, SeaRowChain, SeaAdalnGroup, SeaAdalnQkv, SeaSplitkGroup, SeaEncBlock, SeaKvFill, SeaKvFork last): lets a binding verify its layout.  Host only. */

@@ -533,6 +533,7 @@ static void launch_bwd(const SeaAttnBwdParams& P, hipStream_t s) {
     dim3 gq2 = gq, gk2 = gk;
     if (mq & ATTNB_PAIRED) gq2.x = (gq.x + 1) / 2;
     if (mk & ATTNB_PAIRED) gk2.x = (gk.x + 1) / 2;
+    sea_note_form(MASKED ? "attn_bwd.masked" : "attn_bwd", mq, mk);   // a / b: the mode bits of the dQ / the dK, dV kernel
     if (P.drop.thr > 0) {
         attn_bwd_dq_kernel<T, HD, true, MASKED><<<gq2, block, pad, s>>>(P, mq);
         attn_bwd_dkv_kernel<T, HD, true, MASKED><<<gk2, block, pad, s>>>(P, mk);

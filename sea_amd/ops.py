@@ -78,8 +78,8 @@ def gemm_grouped(groups: Sequence[Dict], dtype: torch.dtype) -> None:
 
 
 def last_form():
-    """(form, a, b) of the calling thread's last noted launch — which kernel sea_gemm_grouped / sea_gemm_rownorm / sea_attention_fwd / sea_wgrad_grouped
-    took (include/sea_hip.h, sea_last_form); ("", 0, 0) before any.  For the tests that force a form."""
+    """(form, a, b) of the calling thread's last noted launch — which kernel sea_gemm_grouped / sea_gemm_rownorm / sea_attention_fwd / sea_attention_bwd /
+    sea_wgrad_grouped took (include/sea_hip.h, sea_last_form); ("", 0, 0) before any.  For the tests that force a form."""
     a, b = C.c_int(0), C.c_int(0)
     name = N.lib().sea_last_form(C.byref(a), C.byref(b))
     return (name.decode() if name else ""), a.value, b.value

@@ -9,7 +9,9 @@ Local bounds.  GEMM, GEMM + norm and weight-gradient outputs are rounded to bf16
 at most 2^-9 ||ref_row|| <= 2^-9 * 3 * rms row norm as long as no row is longer than 3 rms row norms — asserted on every reference (`spread`).  fp32
 outputs: 4 x the global fp32 tolerance.  A vector output (db, mean, rstd) is one row.  Attention rounds P and O, and the error of P is statistical: its
 bf16 bounds are 3 x what a torch restatement that rounds P and O where the kernel does gives for the same metric on these inputs (ATTN_LOCAL; `python
-tests/test_forced_forms_gpu.py` prints the measured values on the CPU); fp32 attention rounds nothing: 4 x the global fp32 tolerance."""
+tests/test_forced_forms_gpu.py` prints the measured values on the CPU); fp32 attention rounds nothing: 4 x the global fp32 tolerance.  The attention
+backward (dQ, dK, dV rows of one head, against fp64 autograd) follows the same rule: ATTNB_LOCAL from attention_bwd_emulated, which rounds the forward's O,
+the P and dS fragments and the three outputs."""
 import math
 
 import pytest
@@ -264,21 +266,22 @@ def test_gemm_rownorm_tile_shapes_agree(monkeypatch, dtype, N_, K):
 
 
 # ------------------------------------------------------------------------------------------------ sea_attention_fwd
-ATTN_SHAPES = [(257, 257, 0, 0), (330, 330, 0, 3), (5, 300, 295, 0)]   # (Tq, Tk, q_pos0, src_len): two wave groups need Tk >= 256
-ATTN_SHORT = [(200, 200, 0, 3)]                                        # fewer than 256 keys: one wave group
+ATTN_SHAPES = [(257, 257, 0, 0), (330, 330, 0, 3), (5, 300, 295, 0), (257, 257, 0, 264)]   # (Tq, Tk, q_pos0, src_len): two wave groups need Tk >= 256;
+ATTN_SHORT = [(200, 200, 0, 3), (200, 200, 0, 200)]   # fewer than 256 keys: one wave group               the last of each: src_len = cap, every key visible
 ATTN_ROW = [(1, 300, 299, 0), (1, 257, 100, 3), (1, 200, 199, 0)]      # Tq = 1 without LSE: the one-row kernels (keys limited by the causal rule or by Tk)
 ATTN_B, ATTN_H = 1, 3
 # Local bounds of the bf16 outputs = 3 x the largest value of the same metric for attention_ref64(round_p, round_o) (P and O rounded to bf16 where the kernel rounds them)
 # over every case of this file, measured on the CPU (python tests/test_forced_forms_gpu.py).  Measured: O 1.358e-2 for the tiled kernels (P and O rounded; the
-# early queries see few keys, so their rows are several rms row norms long), O 2.957e-3 for the row kernels (fp32 probabilities: O alone), LSE 2.806e-4.
+# early queries see few keys, so their rows are several rms row norms long), O 2.957e-3 for the row kernels (fp32 probabilities: O alone), LSE 2.806e-4.  (The shapes with every key visible and
+# the three problems of one launch stay below them: at most O 8.236e-3, LSE 2.733e-4.)
 ATTN_LOCAL = {"O": 3 * 1.358e-2, "O_row": 3 * 2.957e-3, "LSE": 3 * 2.806e-4}
 
 
-def attn_inputs(dtype, hd, Tq, Tk, q_pos0, src_len, device=None):
+def attn_inputs(dtype, hd, Tq, Tk, q_pos0, src_len, device=None, seed=0):
     cap = (Tk + 7) // 8 * 8
-    Q = rnd(ATTN_B, ATTN_H, Tq, hd, dtype=dtype, scale=hd ** -0.25, seed=3000 + hd + Tq, device=device)
-    K = rnd(ATTN_B, ATTN_H, cap, hd, dtype=dtype, scale=hd ** -0.25, seed=3001 + hd + Tq, device=device)
-    Vt = rnd(ATTN_B, ATTN_H, hd, cap, dtype=dtype, seed=3002 + hd + Tq, device=device)
+    Q = rnd(ATTN_B, ATTN_H, Tq, hd, dtype=dtype, scale=hd ** -0.25, seed=seed + 3000 + hd + Tq, device=device)
+    K = rnd(ATTN_B, ATTN_H, cap, hd, dtype=dtype, scale=hd ** -0.25, seed=seed + 3001 + hd + Tq, device=device)
+    Vt = rnd(ATTN_B, ATTN_H, hd, cap, dtype=dtype, seed=seed + 3002 + hd + Tq, device=device)
     return Q, K, Vt, cap
 
 
@@ -307,34 +310,29 @@ def attn_rows(O, hd):
     return O.reshape(-1, hd)
 
 
-def _attn_case(monkeypatch, tune, dtype, hd, shape, form, paired=None, lse=True):
-    from sea_amd import ops
-
+def _attn_problem(dtype, hd, shape, lse=True, seed=0):
+    """One problem dict (padding poisoned, outputs NaN) and the fp64 references of O and LSE."""
     Tq, Tk, q_pos0, src_len = shape
-    Q, K, Vt, cap = attn_inputs(dtype, hd, Tq, Tk, q_pos0, src_len)
+    Q, K, Vt, cap = attn_inputs(dtype, hd, Tq, Tk, q_pos0, src_len, seed=seed)
     Oref, Lref = attention_ref64(Q, K, Vt, q_pos0, src_len, Tk)
     K[:, :, Tk:] = float("nan")        # poison the padding: it must never leak into the result
     Vt[:, :, :, Tk:] = float("nan")
-    O = torch.full((ATTN_B, Tq, ATTN_H * hd), float("nan"), device=dev(), dtype=dtype)
-    p = dict(Q=Q, K=K, Vt=Vt, O=O)
+    p = dict(Q=Q, K=K, Vt=Vt, O=torch.full((ATTN_B, Tq, ATTN_H * hd), float("nan"), device=dev(), dtype=dtype))
     if lse:
         p["LSE"] = torch.full((ATTN_B, ATTN_H, Tq), float("nan"), device=dev())
-    force(monkeypatch, tune)
-    ops.attention_fwd([p], ATTN_B, ATTN_H, hd, Tq, Tk, cap, q_pos0, src_len, dtype)
-    got = ops.last_form()
-    torch.cuda.synchronize()
-    assert got[0] == form, (tune, hd, shape, got)
-    if paired is not None:
-        assert got[1] == paired, (tune, got)
+    return p, Oref, Lref, cap
+
+
+def _attn_check(p, Oref, Lref, dtype, hd, form, what):
     f32 = dtype == torch.float32
-    what = f"{form} [{tune}] hd={hd} {shape}"
+    O = p["O"]
     assert torch.isfinite(O.float()).all(), what
     eg, el = rel(O, Oref), rowerr(attn_rows(O, hd), attn_rows(Oref, hd))
     lo = 4 * 2e-5 if f32 else ATTN_LOCAL["O_row" if form == "attn.row" else "O"]
     print(f"{what} O: global {eg:.3e}  local {el:.3e} (< {lo:.2e})")
     assert eg < (2e-5 if f32 else 8e-3), (what, eg)
     assert el < lo, (what, el)
-    if lse:
+    if "LSE" in p:
         L = p["LSE"]
         assert torch.isfinite(L).all(), what
         eg, el = rel(L, Lref), rowerr(L.reshape(-1, 1), Lref.reshape(-1, 1))
@@ -342,7 +340,27 @@ def _attn_case(monkeypatch, tune, dtype, hd, shape, form, paired=None, lse=True)
         print(f"{what} LSE: global {eg:.3e}  local {el:.3e} (< {ll:.2e})")
         assert eg < (1e-5 if f32 else 1e-3), (what, eg)
         assert el < ll, (what, el)
-    return O, p.get("LSE")
+
+
+def _attn_case(monkeypatch, tune, dtype, hd, shape, form, paired=None, lse=True, n=1):
+    """n problems with different tensors in ONE launch under `tune`: the form, then every problem against its reference; returns [(O, LSE)] per problem
+    (the pair itself when n = 1)."""
+    from sea_amd import ops
+
+    Tq, Tk, q_pos0, src_len = shape
+    built = [_attn_problem(dtype, hd, shape, lse, seed=100 * i) for i in range(n)]
+    cap = built[0][3]
+    force(monkeypatch, tune)
+    ops.attention_fwd([b[0] for b in built], ATTN_B, ATTN_H, hd, Tq, Tk, cap, q_pos0, src_len, dtype)
+    got = ops.last_form()
+    torch.cuda.synchronize()
+    assert got[0] == form, (tune, hd, shape, got)
+    if paired is not None:
+        assert got[1] == paired, (tune, got)
+    for i, (p, Oref, Lref, _) in enumerate(built):
+        _attn_check(p, Oref, Lref, dtype, hd, form, f"{form} [{tune}] hd={hd} {shape}" + (f" problem {i} of {n}" if n > 1 else ""))
+    outs = [(p["O"], p.get("LSE")) for p, _, _, _ in built]
+    return outs[0] if n == 1 else outs
 
 
 @pytest.mark.parametrize("hd", [8, 16, 32])
@@ -373,11 +391,358 @@ def test_attention_one_wave_group_and_its_paired_order(monkeypatch, dtype, hd):
             assert torch.equal(plain[0], pair[0]) and torch.equal(plain[1], pair[1])
 
 
+@pytest.mark.parametrize("tune,hd,form", [(None, 32, "attn.split4"), ("attn_split4=0", 32, "attn.split2"), (None, 128, "attn.split1")])
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_attention_prefill_of_three_problems_in_one_launch(monkeypatch, dtype, tune, hd, form):
+    """Three problems with different tensors (grid.z = 3) at Tq = Tk = 257 in each tiled form (with at least 256 keys one wave group is what a compute
+    width above 64 runs): every problem against its own reference, and bitwise what the same problem gives when it is launched alone."""
+    shape = (257, 257, 0, 0)
+    together = _attn_case(monkeypatch, tune, dtype, hd, shape, form, paired=0, n=3)
+    for i, (O, L) in enumerate(together):
+        p, _, _, cap = _attn_problem(dtype, hd, shape, seed=100 * i)
+        from sea_amd import ops
+
+        ops.attention_fwd([p], ATTN_B, ATTN_H, hd, 257, 257, cap, 0, 0, dtype)
+        assert ops.last_form()[0] == form, (i, ops.last_form())
+        torch.cuda.synchronize()
+        assert torch.equal(O, p["O"]) and torch.equal(L, p["LSE"]), (form, i)
+
+
 @pytest.mark.parametrize("hd", [8, 16, 32, 64])
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_attention_row_form(monkeypatch, dtype, hd):
     for shape in ATTN_ROW:
         _attn_case(monkeypatch, None, dtype, hd, shape, "attn.row", lse=False)
+
+
+# ------------------------------------------------------------------------------------------------ sea_attention_bwd
+# (Tq, Tk, q_pos0, src_len) at 64 x 64 tiles and 16-row waves; src_len = CAP: every key visible, with the identity rotary table, as the training engine issues
+# its information-bottleneck and spatial-encoder attention
+CAP = "cap"
+ATTNB_EDGES = [(63, 63, 0, 0), (64, 64, 0, 0), (65, 65, 0, 0), (128, 128, 0, 0), (129, 129, 0, 1)]   # tile and wave edges
+ATTNB_SRC = [(80, 80, 0, 16), (130, 130, 0, 15)]                        # src_len one wave high: the unmasked-tile boundaries of both kernels
+ATTNB_FULL = [(64, 64, 0, CAP), (70, 70, 0, CAP), (130, 130, 0, CAP)]
+# a chunk at the end of a cache; a longer one; key tiles no query sees; queries past the last key; one element
+ATTNB_RECT = [(5, 77, 72, 0), (70, 200, 130, 0), (40, 200, 0, 0), (130, 70, 0, 0), (1, 1, 0, 0)]
+ATTNB_SHAPES = ATTNB_EDGES + ATTNB_SRC + ATTNB_FULL + ATTNB_RECT           # at head dims 16 and 32
+# a fifth entry x puts +c on q0[..., 0] and -c on k0[..., 0] with c^2 q_scale = x: every score lies near -x in log2 units.  At x = 144 the 2^(0 - LSE) of a
+# zero-filled tile row past Tk overflows fp32 — what `key < Tk` in the dQ kernel's tile mask is there for (without it inf * 0 makes the tile's dQ rows NaN).
+ATTNB_FAR = [(70, 70, 0, CAP, 144.0)]
+ATTNB_HD_SHAPES = [(65, 65, 0, 0), (130, 130, 0, CAP), (70, 200, 130, 0)]   # at every other head dim
+ATTNB_HDS = [8, 64, 128, 256, 24, 96]                                      # (24 and 96: the masked kernels, compute widths 32 and 96)
+ATTNB_MODE_SHAPES = [(65, 65, 0, 0), (129, 129, 0, 1), (130, 130, 0, CAP), (40, 200, 0, 0)]
+ATTNB_MODE_BH = [(1, 3), (2, 4)]                                           # B * H = 3: the XCD-local order falls back to the plain one; 8: it is taken
+ATTNB_MULTI_SHAPES = [(65, 65, 0, 0), (70, 70, 0, CAP)]                    # hd 16, three and SEA_MAX_ATTN_PROBLEMS (8) problems
+ATTNB_DROP = dict(hd=32, shape=(129, 129, 0, CAP), n=2, seed=4242, stream=11, thr=64)
+ATTNB_B, ATTNB_H = 1, 3
+LOG2E = 1.4426950408889634
+# Local bounds of the bf16 gradients = 3 x the largest value of the same metric for attention_bwd_emulated (the fp64 formulas, rounded to bf16 where the kernels
+# round: the O the forward stored, the P and dS fragments in front of the second MFMA, the three outputs) over every case of this section, the dropout case
+# apart, measured on the CPU (python tests/test_forced_forms_gpu.py).
+# Measured: dQ 2.728e-2 (hd 8, (70, 200, 130, 0)), dK 2.474e-2 and dV 2.474e-2 (both hd 16, (40, 200, 0, 0), B * H = 8: four key rows in five are zero, so a
+# row is long against the rms row norm); with dropout dQ 9.988e-3, dK 1.090e-2, dV 6.177e-3.
+ATTNB_LOCAL = {"dQ": 3 * 2.728e-2, "dK": 3 * 2.474e-2, "dV": 3 * 2.474e-2, "dQ_drop": 3 * 9.988e-3, "dK_drop": 3 * 1.090e-2, "dV_drop": 3 * 6.177e-3}
+
+
+def attnb_cases():
+    """Every (hd, shape, B, H, number of problems) of this section, the dropout case apart: what the tests launch and what ATTNB_LOCAL is measured over."""
+    cases = [(hd, sh, ATTNB_B, ATTNB_H, 1) for hd in (16, 32) for sh in ATTNB_SHAPES]
+    cases += [(hd, sh, ATTNB_B, ATTNB_H, 1) for hd in ATTNB_HDS for sh in ATTNB_HD_SHAPES]
+    cases += [(hd, sh, B, H, 1) for hd in (16, 32) for sh in ATTNB_MODE_SHAPES for B, H in ATTNB_MODE_BH if (B, H) != (ATTNB_B, ATTNB_H)]
+    cases += [(16, sh, ATTNB_B, ATTNB_H, n) for sh in ATTNB_MULTI_SHAPES for n in (3, 8)]
+    return cases
+
+
+def rope_table(hd, n, identity=False, device=None):
+    if identity:   # cos 1, sin 0
+        t = torch.stack((torch.ones(n, hd // 2), torch.zeros(n, hd // 2)), dim=-1)
+    else:
+        ang = torch.outer(torch.arange(n, dtype=torch.float32), 1.0 / (10000.0 ** (torch.arange(0, hd, 2).float() / hd)))
+        t = torch.stack((torch.cos(ang), torch.sin(ang)), dim=-1)
+    return t.contiguous().to(device if device is not None else dev())
+
+
+def rope64(x, table, pos0, inverse=False):
+    """x [B, T, H, hd] (fp64) rotated at positions pos0 .. pos0 + T - 1: (e', o') = (e c - o s, e s + o c); inverse: the transposed rotation."""
+    T = x.shape[1]
+    c, s = table[pos0:pos0 + T, :, 0].double()[None, :, None, :], table[pos0:pos0 + T, :, 1].double()[None, :, None, :]
+    if inverse:
+        s = -s
+    xe, xo = x[..., 0::2], x[..., 1::2]
+    return torch.stack((xe * c - xo * s, xe * s + xo * c), dim=-1).flatten(-2)
+
+
+def drop_mask_host(rows, cols, seed, stream, thr):
+    """keep * scale of SeaDropout (include/sea_hip.h) restated on the host, so that the emulation behind the dropout bounds runs without a device; the
+    dropout test asserts that sea_dropout_mask gives the same grid."""
+    import numpy as np
+
+    M = np.uint64(0xFFFFFFFF)
+
+    def fmix(x):
+        x = x ^ (x >> np.uint64(16))
+        x = (x * np.uint64(0x85EBCA6B)) & M
+        x = x ^ (x >> np.uint64(13))
+        x = (x * np.uint64(0xC2B2AE35)) & M
+        return x ^ (x >> np.uint64(16))
+
+    row = np.arange(rows, dtype=np.uint64)[:, None]
+    col = np.arange(cols, dtype=np.uint64)[None, :]
+    base = np.uint64((seed ^ ((stream * 0x9E3779B1) & 0xFFFFFFFF)) & 0xFFFFFFFF)
+    x = fmix((base + ((row * np.uint64(0x85EBCA77)) & M)) & M)
+    w = fmix(x ^ ((((col >> np.uint64(2)) * np.uint64(0xC2B2AE3D)) + np.uint64(0x27D4EB2F)) & M))
+    byte = (w >> (np.uint64(8) * (col & np.uint64(3)))) & np.uint64(0xFF)
+    return torch.from_numpy(np.where(byte >= np.uint64(thr), float(np.float32(256.0) / np.float32(256 - thr)), 0.0))   # the kernels' scale is an fp32 quotient
+
+
+def attnb_inputs(dtype, hd, shape, B, H, prob=0, device=None):
+    """The operands of one problem as the QKV epilogue would have written them (rotated, q scaled, rounded to the compute dtype), the fp64 pre-images q0 /
+    k0 / v0 [B, T, H, hd] the gradients are taken with respect to, dO, the rotary table and the resolved (cap, src_len)."""
+    Tq, Tk, q_pos0, src_len = shape[:4]
+    device = device if device is not None else dev()
+    cap = (Tk + 15) // 8 * 8                      # at least 8 padding rows
+    full = src_len == CAP
+    src_len = cap if full else src_len
+    seed = 5000 + 1000 * prob + 7 * hd + 13 * Tq + 3 * Tk + 31 * q_pos0 + 101 * B * H
+    table = rope_table(hd, max(q_pos0 + Tq, Tk), identity=full, device=device)
+    q0, k0, v0 = (rnd(B, T, H, hd, seed=seed + s, device=device).double() for s, T in ((1, Tq), (2, Tk), (3, Tk)))
+    scale2 = float(hd) ** -0.5 * LOG2E            # ops.q_scale(hd): the attention kernels score in log2 units
+    if len(shape) > 4:                            # (with the identity table: coordinate 0 is not rotated away)
+        assert full
+        q0[..., 0], k0[..., 0] = (shape[4] / scale2) ** 0.5, -(shape[4] / scale2) ** 0.5
+    return dict(q0=q0, k0=k0, v0=v0, table=table, cap=cap, src_len=src_len, scale2=scale2, B=B, H=H, hd=hd, Tq=Tq, Tk=Tk, q_pos0=q_pos0,
+                dO=rnd(B, Tq, H * hd, dtype=dtype, seed=seed + 4, device=device),
+                Q=(rope64(q0, table, q_pos0) * scale2).permute(0, 2, 1, 3).contiguous().to(dtype),
+                K=rope64(k0, table, 0).permute(0, 2, 1, 3).contiguous().to(dtype), V=v0.permute(0, 2, 1, 3).contiguous().to(dtype))
+
+
+def attnb_visible(inp):
+    """[Tq, Tk] bool: query i (at position q_pos0 + i) sees key j iff j <= q_pos0 + i + src_len."""
+    i = torch.arange(inp["Tq"], device=inp["Q"].device)[:, None] + inp["q_pos0"] + inp["src_len"]
+    return torch.arange(inp["Tk"], device=inp["Q"].device)[None, :] <= i
+
+
+def attention_bwd_ref64(inp, drop=None):
+    """fp64 autograd through rotary -> q_scale -> masked base-2 softmax (-> dropout factors `drop` [B, H, Tq, Tk]) -> P V, evaluated on the operands as
+    rounded to the compute dtype (straight-through: the values are the kernel's operands, the gradients flow to q0 / k0 / v0).  Returns the gradients with
+    respect to the un-rotated, un-scaled q, k, v ([B, T, H, hd]): what dQ, dK, dV hold."""
+    q, k, v = (inp[n].clone().requires_grad_(True) for n in ("q0", "k0", "v0"))
+    qr = (rope64(q, inp["table"], inp["q_pos0"]) * inp["scale2"]).permute(0, 2, 1, 3)
+    kr, vr = rope64(k, inp["table"], 0).permute(0, 2, 1, 3), v.permute(0, 2, 1, 3)
+    qr, kr, vr = (t + (inp[n].double() - t.detach()) for t, n in ((qr, "Q"), (kr, "K"), (vr, "V")))
+    S = (qr @ kr.transpose(-1, -2)).masked_fill(~attnb_visible(inp), float("-inf"))
+    P = torch.exp2(S - S.max(-1, keepdim=True).values.detach())
+    P = P / P.sum(-1, keepdim=True)
+    if drop is not None:
+        P = P * drop.double()
+    O = (P @ vr).transpose(1, 2).reshape(inp["B"], inp["Tq"], -1)
+    O.backward(inp["dO"].double())
+    return {"dQ": q.grad, "dK": k.grad, "dV": v.grad}
+
+
+def attention_bwd_emulated(inp, drop=None, rt=BF):
+    """The kernels' formulas in fp64 with a rounding to `rt` where the bf16 kernels round: the forward's P (before the row sum) and O, hence delta = sum O dO
+    of the ROUNDED O; the P (x dropout factor) and dS fragments in front of the second MFMA (pack_frag); the three outputs.  rt = None rounds nothing and
+    restates attention_bwd_ref64 without autograd (checked by this file's __main__)."""
+    r = (lambda t: t.to(rt).double()) if rt is not None else (lambda t: t)
+    B, H, hd, Tq, Tk = inp["B"], inp["H"], inp["hd"], inp["Tq"], inp["Tk"]
+    Q, K, V = inp["Q"].double(), inp["K"].double(), inp["V"].double()
+    dO = inp["dO"].double().view(B, Tq, H, hd).permute(0, 2, 1, 3)
+    D = drop.double() if drop is not None else 1.0
+    S = (Q @ K.transpose(-1, -2)).masked_fill(~attnb_visible(inp), float("-inf"))
+    mx = S.max(-1, keepdim=True).values
+    Pf = torch.exp2(S - mx)
+    l = r(Pf).sum(-1, keepdim=True)                 # the forward's row sum: of the rounded, un-dropped probabilities
+    O = r((r(Pf * D) @ V) / l)
+    lse = mx + torch.log2(l)
+    delta = (O * dO).sum(-1, keepdim=True)
+    P = torch.exp2(S - lse)
+    dS = P * ((dO @ V.transpose(-1, -2)) * D - delta)
+    pf, sf = r(P * D), r(dS)
+    dq = rope64((sf @ K).permute(0, 2, 1, 3), inp["table"], inp["q_pos0"], inverse=True) * (inp["scale2"] * LN2)
+    dk = rope64((sf.transpose(-1, -2) @ Q).permute(0, 2, 1, 3), inp["table"], 0, inverse=True) * LN2
+    dv = (pf.transpose(-1, -2) @ dO).permute(0, 2, 1, 3)
+    return {"dQ": r(dq), "dK": r(dk), "dV": r(dv)}
+
+
+def attnb_drop_factors(inp, prob, seed, stream0, thr):
+    """[B, H, Tq, Tk]: the kernels' mask of (problem, b, h) is stream (stream0 + problem) * B * H + b * H + h over the (query, key) grid."""
+    B, H = inp["B"], inp["H"]
+    return torch.stack([torch.stack([drop_mask_host(inp["Tq"], inp["Tk"], seed, (stream0 + prob) * B * H + b * H + h, thr) for h in range(H)])
+                        for b in range(B)]).to(inp["Q"].device)
+
+
+def _attnb_launch(monkeypatch, tune, dtype, inps, drop=None):
+    """One forward (for O and LSE, as in training) and one backward launch of the problems `inps` under `tune`: K / V padding rows [Tk, cap) NaN, O and dO column views of wider NaN-framed buffers (ldo = E + 24, lddo = E + 16), dQ in a NaN frame, dK | dV the halves of one
+    [B * Tk, 2 E] buffer, every output NaN before the launch.  Asserts the noted form; returns the problem dicts."""
+    import ctypes as C
+
+    from sea_amd import _native as N, ops
+
+    i0 = inps[0]
+    B, H, hd, Tq, Tk, cap, q_pos0, src_len = (i0[k] for k in ("B", "H", "hd", "Tq", "Tk", "cap", "q_pos0", "src_len"))
+    E, nan = H * hd, float("nan")
+    assert abs(ops.q_scale(hd) - i0["scale2"]) < 1e-15
+    probs = []
+    for inp in inps:
+        K, V = (torch.full((B, H, cap, hd), nan, device=dev(), dtype=dtype) for _ in range(2))
+        K[:, :, :Tk], V[:, :, :Tk] = inp["K"], inp["V"]
+        Obig = torch.full((B, Tq, E + 24), nan, device=dev(), dtype=dtype)
+        dObig = torch.full((B, Tq, E + 16), nan, device=dev(), dtype=dtype)
+        dObig[:, :, 8:8 + E] = inp["dO"]
+        dQbig, dQ = framed(B * Tq, E, dtype)
+        dKV = torch.full((B * Tk, 2 * E), nan, device=dev(), dtype=dtype)
+        probs.append(dict(Q=inp["Q"], K=K, V=V, Vt=V.transpose(2, 3).contiguous(), O=Obig[:, :, 8:8 + E], dO=dObig[:, :, 8:8 + E], Obig=Obig, dQbig=dQbig,
+                          LSE=torch.full((B, H, Tq), nan, device=dev()), delta=torch.full((B, H, Tq), nan, device=dev()), dQ=dQ, dK=dKV[:, :E], dV=dKV[:, E:]))
+    force(monkeypatch, tune)
+    ops.attention_fwd(probs, B, H, hd, Tq, Tk, cap, q_pos0, src_len, dtype, drop=drop)
+    if drop is None:
+        ops.attention_bwd(probs, i0["table"], B, H, hd, Tq, Tk, cap, q_pos0, src_len, i0["scale2"], dtype)
+    else:
+        P = N.SeaAttnBwdParams()
+        ops.fill_attn_bwd_params(P, probs, i0["table"], B, H, hd, Tq, Tk, cap, q_pos0, src_len, i0["scale2"], drop)
+        N.check(N.lib().sea_attention_bwd(C.byref(P), N.dtype_code(dtype), N.stream_ptr()), "sea_attention_bwd")
+    got = ops.last_form()
+    torch.cuda.synchronize()
+    mode = int(tune.split("=")[1]) if tune else 0      # these launches are far below the 4096 workgroups from which the launcher picks mode 3 itself
+    assert got == ("attn_bwd" if hd in (8, 16, 32, 64, 128, 256) else "attn_bwd.masked", mode, mode), (tune, hd, got)
+    return probs
+
+
+def _attnb_check(what, dtype, inp, p, ref, drop=False):
+    """Both checks of dQ, dK, dV of one problem, delta, the frames, exact zeros at keys no query sees."""
+    B, H, hd, Tq, Tk = inp["B"], inp["H"], inp["hd"], inp["Tq"], inp["Tk"]
+    f32 = dtype == torch.float32
+    t = 2e-5 if f32 else 2e-2
+    floor = 0.1 * float(inp["dO"].double().norm())
+    assert frame_untouched(p["dQbig"], H * hd), what
+    assert frame_untouched(p["Obig"].view(B * Tq, -1), H * hd), what
+    O, dO = p["O"].double(), p["dO"].double()
+    assert torch.isfinite(O).all() and torch.isfinite(p["LSE"]).all() and torch.isfinite(p["delta"]).all(), what
+    # delta = sum_d O dO of the stored O and dO: hd products (exact in fp32 for bf16 factors, one rounding for fp32 ones) summed in fp32 in some order:
+    # at most (hd + 1) 2^-24 sum |O dO| off; asserted at hd 2^-23
+    terms = (O * dO).view(B, Tq, H, hd).permute(0, 2, 1, 3)
+    ed = (p["delta"].double() - terms.sum(-1)).abs() - hd * 2.0 ** -23 * terms.abs().sum(-1)
+    assert float(ed.max()) <= 0, (what, "delta", float(ed.max()))
+    first_unseen = inp["q_pos0"] + Tq - 1 + inp["src_len"] + 1     # keys from here on are seen by no query
+    for name, T in (("dQ", Tq), ("dK", Tk), ("dV", Tk)):
+        out, r = p[name].reshape(B, T, H, hd), ref[name]
+        assert torch.isfinite(out.float()).all(), (what, name)
+        err, rn = float((out.double() - r).norm()), float(r.norm())
+        if rn == 0:    # Tq = Tk = 1: dQ = dK = 0 exactly — the floor of test_bwd_ops_gpu.py
+            print(f"{what} {name}: reference 0, error {err:.3e} (<= {t * floor:.2e})")
+            assert err <= t * floor, (what, name, err)
+            continue
+        lo = 4 * t if f32 else ATTNB_LOCAL[name + ("_drop" if drop else "")]
+        eg, el = err / rn, rowerr(out.reshape(-1, hd), r.reshape(-1, hd))
+        print(f"{what} {name}: global {eg:.3e} (< {t:.1e})  local {el:.3e} (< {lo:.2e})")
+        assert eg < t, (what, name, "global", eg)
+        assert el < lo, (what, name, "local", el)
+        if name != "dQ" and first_unseen < Tk:
+            assert bool((out[:, first_unseen:] == 0).all()) and bool((r[:, first_unseen:] == 0).all()), (what, name, "keys no query sees")
+
+
+_ATTNB_REF = {}
+
+
+def _attnb_ref(dtype, hd, shape, B, H, prob=0):
+    """(inputs, fp64 reference) of one problem, computed once per session and left unchanged."""
+    key = (dtype, hd, shape, B, H, prob)
+    if key not in _ATTNB_REF:
+        inp = attnb_inputs(dtype, hd, shape, B, H, prob)
+        _ATTNB_REF[key] = (inp, attention_bwd_ref64(inp))
+    return _ATTNB_REF[key]
+
+
+def _attnb_case(monkeypatch, tune, dtype, hd, shape, B=ATTNB_B, H=ATTNB_H, n=1):
+    """n problems in one launch under `tune`, each against its reference; returns [(dQ, dK, dV, delta)] per problem."""
+    built = [_attnb_ref(dtype, hd, shape, B, H, i) for i in range(n)]
+    probs = _attnb_launch(monkeypatch, tune, dtype, [b[0] for b in built])
+    for i, ((inp, ref), p) in enumerate(zip(built, probs)):
+        _attnb_check(f"attn_bwd [{tune}] hd={hd} {shape} B*H={B * H}" + (f" problem {i} of {n}" if n > 1 else ""), dtype, inp, p, ref)
+    return [(p["dQ"], p["dK"], p["dV"], p["delta"]) for p in probs]
+
+
+def _same(a, b):
+    return all(torch.equal(x, y) for x, y in zip(a, b))
+
+
+@pytest.mark.parametrize("hd", [16, 32])
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_attention_backward_tile_edges_and_geometries(monkeypatch, dtype, hd):
+    """The benchmark's head dims at every shape of the section: lengths on and beside the 64-row tile and the 16-row wave edges, src_len one wave high,
+    every key visible with the identity rotary table, Tq != Tk with q_pos0 > 0, key tiles no query sees, queries past the last key, one element."""
+    for shape in ATTNB_SHAPES:
+        _attnb_case(monkeypatch, None, dtype, hd, shape)
+
+
+@pytest.mark.parametrize("hd", [16, 32])
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_attention_backward_scores_far_below_zero_stay_finite(monkeypatch, dtype, hd):
+    """Every LSE below -128: 2^(0 - LSE) of a zero-filled tile row past Tk overflows before the mask zeroes it, and every output must still be finite.
+    (Finiteness only: the common component that pushes the scores down is 5 x as long as the rest of a key and multiplies every rounding of dS into
+    dQ, so the section's tolerances, made for well-conditioned operands, do not apply; fp32 measured 6e-5 on dQ.)"""
+    inp = attnb_inputs(dtype, hd, ATTNB_FAR[0], ATTNB_B, ATTNB_H)
+    p = _attnb_launch(monkeypatch, None, dtype, [inp])[0]
+    assert float(p["LSE"].max()) < -128
+    for k in ("O", "LSE", "delta", "dQ", "dK", "dV"):
+        assert torch.isfinite(p[k].float()).all(), k
+    assert frame_untouched(p["dQbig"], ATTNB_H * hd)
+
+
+@pytest.mark.parametrize("hd", ATTNB_HDS)
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_attention_backward_head_dims(monkeypatch, dtype, hd):
+    """Every other exact head dim and the masked widths 24 and 96 on a length beside a tile edge, on full visibility and on a chunk at the end of a cache."""
+    for shape in ATTNB_HD_SHAPES:
+        _attnb_case(monkeypatch, None, dtype, hd, shape)
+
+
+@pytest.mark.parametrize("B,H", ATTNB_MODE_BH)
+@pytest.mark.parametrize("hd", [16, 32])
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_attention_backward_forced_modes(monkeypatch, dtype, hd, B, H):
+    """attnb_mode 0 .. 3 (1: XCD-local order, taken at B * H = 8 and falling back at 3; 2: paired tiles — at (40, 200) the paired dK / dV tile sees no query
+    and skips its loop): the noted mode bits are the forced ones, every mode meets the reference and is bitwise mode 0 (no atomics)."""
+    for shape in ATTNB_MODE_SHAPES:
+        plain = _attnb_case(monkeypatch, "attnb_mode=0", dtype, hd, shape, B, H)
+        for mode in (1, 2, 3):
+            assert _same(plain[0], _attnb_case(monkeypatch, f"attnb_mode={mode}", dtype, hd, shape, B, H)[0]), (mode, shape)
+
+
+@pytest.mark.parametrize("n", [3, 8])
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_attention_backward_problems_of_one_launch(monkeypatch, dtype, n):
+    """Three and SEA_MAX_ATTN_PROBLEMS problems with different tensors in one launch (grid.z): each against its own reference, and bitwise what the same
+    problem gives when it is launched alone."""
+    for shape in ATTNB_MULTI_SHAPES:
+        together = _attnb_case(monkeypatch, None, dtype, 16, shape, n=n)
+        for i, outs in enumerate(together):
+            inp, _ = _attnb_ref(dtype, 16, shape, ATTNB_B, ATTNB_H, i)
+            alone = _attnb_launch(monkeypatch, None, dtype, [inp])[0]
+            assert _same(outs, (alone["dQ"], alone["dK"], alone["dV"], alone["delta"])), (shape, n, i)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_attention_backward_with_dropout(monkeypatch, dtype):
+    """Dropout of the probabilities (thr = 64, p = 0.25) on two problems with every key visible: the mask is sea_dropout_mask's (equal to its host
+    restatement, which the emulated bounds use); global and per-row checks as everywhere."""
+    from tests.test_dropout_gpu import mask
+
+    c = ATTNB_DROP
+    inps, refs = [], []
+    for i in range(c["n"]):
+        inp = attnb_inputs(dtype, c["hd"], c["shape"], ATTNB_B, ATTNB_H, i)
+        D = attnb_drop_factors(inp, i, c["seed"], c["stream"], c["thr"])
+        for h in range(ATTNB_H):   # the same elements kept; the scale to an fp32 ulp (the device's quotient 256 / (256 - thr) need not be correctly rounded)
+            m = mask(inp["Tq"], inp["Tk"], c["seed"], (c["stream"] + i) * ATTNB_B * ATTNB_H + h, c["thr"]).double()
+            assert torch.equal(m > 0, D[0, h] > 0), (i, h, int(((m > 0) != (D[0, h] > 0)).sum()))
+            assert float((m - D[0, h]).abs().max()) <= 2.0 ** -22, (i, h, float((m - D[0, h]).abs().max()))
+        inps.append(inp)
+        refs.append(attention_bwd_ref64(inp, D))
+    probs = _attnb_launch(monkeypatch, None, dtype, inps, drop=(c["seed"], c["stream"], c["thr"]))
+    for i, (inp, ref, p) in enumerate(zip(inps, refs, probs)):
+        _attnb_check(f"attn_bwd dropout thr={c['thr']} hd={c['hd']} {c['shape']} problem {i}", dtype, inp, p, ref, drop=True)
 
 
 # ------------------------------------------------------------------------------------------------ sea_wgrad_grouped
@@ -486,15 +851,41 @@ def test_wgrad_tile256(monkeypatch, overwrite):
 
 if __name__ == "__main__":   # the emulation behind ATTN_LOCAL, on the CPU
     worst = {"O": 0.0, "O_row": 0.0, "LSE": 0.0}
-    for hd in (8, 16, 32, 64):
-        for key, shapes in (("O", ATTN_SHAPES + ATTN_SHORT), ("O_row", ATTN_ROW)):
-            for Tq, Tk, q_pos0, src_len in shapes:
-                Q, K, Vt, _ = attn_inputs(BF, hd, Tq, Tk, q_pos0, src_len, device="cpu")
-                Oref, Lref = attention_ref64(Q, K, Vt, q_pos0, src_len, Tk)
-                Oe, Le = attention_ref64(Q, K, Vt, q_pos0, src_len, Tk, round_p=BF if key == "O" else None, round_o=BF)
-                eo, elv = rowerr(attn_rows(Oe, hd), attn_rows(Oref, hd)), rowerr(Le.reshape(-1, 1), Lref.reshape(-1, 1))
-                print(f"hd={hd} {(Tq, Tk, q_pos0, src_len)}: O local {eo:.3e}  LSE local {elv:.3e}  (global O {rel(Oe, Oref):.3e}, LSE {rel(Le, Lref):.3e})")
-                worst[key] = max(worst[key], eo)
-                if key == "O":
-                    worst["LSE"] = max(worst["LSE"], elv)
+    cases = [(hd, key, shape, 0) for hd in (8, 16, 32, 64) for key, shapes in (("O", ATTN_SHAPES + ATTN_SHORT), ("O_row", ATTN_ROW)) for shape in shapes]
+    cases += [(hd, "O", (257, 257, 0, 0), 100 * i) for hd in (32, 128) for i in range(3)]   # the three problems of one launch
+    for hd, key, (Tq, Tk, q_pos0, src_len), seed in cases:
+        Q, K, Vt, _ = attn_inputs(BF, hd, Tq, Tk, q_pos0, src_len, device="cpu", seed=seed)
+        Oref, Lref = attention_ref64(Q, K, Vt, q_pos0, src_len, Tk)
+        Oe, Le = attention_ref64(Q, K, Vt, q_pos0, src_len, Tk, round_p=BF if key == "O" else None, round_o=BF)
+        eo, elv = rowerr(attn_rows(Oe, hd), attn_rows(Oref, hd)), rowerr(Le.reshape(-1, 1), Lref.reshape(-1, 1))
+        print(f"hd={hd} {(Tq, Tk, q_pos0, src_len)} seed {seed}: O local {eo:.3e}  LSE local {elv:.3e}  (global O {rel(Oe, Oref):.3e}, LSE {rel(Le, Lref):.3e})")
+        worst[key] = max(worst[key], eo)
+        if key == "O":
+            worst["LSE"] = max(worst["LSE"], elv)
     print({k: f"{v:.3e}" for k, v in worst.items()})
+
+    # the emulation behind ATTNB_LOCAL; with no rounding it must restate the autograd reference
+    def emulate(what, inp, D, suffix):
+        ref, exact, emu = attention_bwd_ref64(inp, D), attention_bwd_emulated(inp, D, rt=None), attention_bwd_emulated(inp, D)
+        line = []
+        for name in ("dQ", "dK", "dV"):
+            assert float((exact[name] - ref[name]).norm()) <= 1e-12 * max(float(ref[name].norm()), 1.0), (what, name)
+            if float(ref[name].norm()) == 0:
+                line.append(f"{name} reference 0")
+                continue
+            e = rowerr(emu[name].reshape(-1, inp["hd"]), ref[name].reshape(-1, inp["hd"]))
+            line.append(f"{name} local {e:.3e} (global {rel(emu[name], ref[name]):.3e})")
+            if e > worstb[name + suffix][0]:
+                worstb[name + suffix] = (e, what)
+        print(f"{what}: " + "  ".join(line))
+
+    worstb = {k: (0.0, "") for k in ATTNB_LOCAL}
+    for hd, shape, B, H, n in attnb_cases():
+        for i in range(n):
+            emulate(f"attn_bwd hd={hd} {shape} B*H={B * H} problem {i} of {n}", attnb_inputs(BF, hd, shape, B, H, i, device="cpu"), None, "")
+    c = ATTNB_DROP
+    for i in range(c["n"]):
+        inp = attnb_inputs(BF, c["hd"], c["shape"], ATTNB_B, ATTNB_H, i, device="cpu")
+        emulate(f"attn_bwd dropout hd={c['hd']} {c['shape']} problem {i}", inp, attnb_drop_factors(inp, i, c["seed"], c["stream"], c["thr"]), "_drop")
+    for k, (v, what) in worstb.items():
+        print(f"ATTNB_LOCAL[{k!r}]: measured {v:.3e} ({what}); the constant is 3 * {ATTNB_LOCAL[k] / 3:.3e}")
