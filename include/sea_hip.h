@@ -1111,6 +1111,49 @@ typedef struct {
 int sea_decode_member_moments(const SeaDecodeMseGroup* groups, int n_groups, const SeaDecodeMemberMoments* p, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * The ensemble Kalman analysis from a DENSE observation of the decoded fields, part 1: per (history, patch) the N x N Gram matrix of the members'
+ * weighted decoded anomalies and its product with the innovation, in one launch for all field groups (looped inside the workgroup in ascending
+ * order).  Neither the members' decoded fields nor an [B N, K] prediction matrix ever exist in memory.  Operands H, W2, bias, ldh, ldw, n_fields,
+ * field0 of SeaDecodeMseGroup exactly as in sea_decode_member_moments; row m = (b * members + j) * P + p of H is member j of history b;
+ * B = M / (P * members); N = members.  Per history b and patch p:
+ *     y_j[f, c]     = sum_s H[m, s] W2[(f - field0) Cp + c, s] + bias[(f - field0) Cp + c]                   (fp32 accumulation; never stored)
+ *     w[f, c]       = valid(p, c) ? (pf[f] > 0 ? pf[f] : 0) * (prec != NULL ? (prec[b, p, f, c] > 0 ? prec[b, p, f, c] : 0) : 1) : 0
+ *                     selects: a NaN counts as 0; pf = prec_field (NULL: 1); valid(p, c) = c < counts[p] (clamped to [0, C]; NULL: c < C)
+ *     ybar[f, c]    = (1 / N) sum_j y_j[f, c]           a_j = y_j - ybar                                     (centred form, fixed member order, fp32)
+ *     gram[b,p,i,j] = sum_{w > 0} w a_i a_j                                                                  f64 [B, P, N, N], written in full, exactly symmetric
+ *     proj[b,p,j]   = sum_{w > 0} w a_j (obs[b, p, f, c] - ybar[f, c])                                       f64 [B, P, N]
+ *     count[b,p]    = #{(f, c): w > 0}, or -1 when obs or a member's value at such a cell, or a stored sum, is not finite       int32 [B, P]
+ * obs element (b P + p, f, c) is at obs + (b P + p) ld_row + f ld_field + c (the layout of SeaDecodeMemberSse.target); prec, when given, has the same
+ * layout through ld_prow, ld_pfield.  A cell without weight — an invalid slot, a pad column, prec or pf not positive — is neutral by a select whatever
+ * obs and prec hold there, NaN and Inf included; obs is not even read there.  Member rows beyond N inside a 16-row block contribute nothing.
+ * Numerics: the mean and the anomalies in fp32; sqrt(w) is put on both factors, so that a product commutes; products are summed in fp32 only inside one
+ * 32-column tile (the f32-input MFMA: an ordered fmaf chain); everything across tiles, fields and groups is added in fp64 in ascending (group, field,
+ * tile) order; proj is summed in fp64 per lane (16 column classes per member) and the classes are folded in ascending order.  Only the
+ * ceil(counts[p] / 32) tiles of a field that hold valid columns are walked; a patch without a valid column gets zeros and count 0.
+ * One workgroup per (history, patch), no atomics, one writer per element: two runs give the same bits, and a history's outputs do not depend on the
+ * other histories of the call.
+ * Requirements: dtype SEA_BF16 (SEA_F32: SEA_EUNSUPPORTED); M >= 1; S a multiple of 8, at most 640 (above: SEA_EUNSUPPORTED), padded by masking; Cp a
+ * multiple of 32, 1 <= C <= Cp; P >= 1; members >= 2 (above 128: SEA_EUNSUPPORTED); M % (P * members) == 0; ld_field, ld_pfield >= C; obs, prec,
+ * prec_field, counts, count 4-byte, gram and proj 8-byte aligned; per group H, W2, bias non-NULL and 16-byte aligned, ldh, ldw multiples of 8 and
+ * >= S; the groups' field ranges cover 0 .. n_fields_total-1 exactly once; 1 <= n_groups <= SEA_DECODE_MSE_MAX_GROUPS.
+ * Returns -1, with the entry point and the offending group named in sea_last_error(), otherwise; nothing touches a device before the checks pass.
+ * Notes the form "decode.member_gram" (a = the padded hidden width, b = the dynamic LDS bytes).
+ * (An addition to ABI version 8.  sea_struct_sizes() keeps its 33 entries, SeaKvFork last: sizeof(SeaDecodeMemberGram) is 120.)
+ */
+typedef struct {
+    const float* obs;          /* f32, rows of the observation: [B * P, n_fields_total, >= C] through ld_row, ld_field */
+    const float* prec_field;   /* f32 [n_fields_total], or NULL (1) */
+    const float* prec;         /* f32 map in obs's layout through ld_prow, ld_pfield, or NULL (1) */
+    const int32_t* counts;     /* device int32 [P] or NULL */
+    double* gram;              /* f64 [B, P, members, members] (output) */
+    double* proj;              /* f64 [B, P, members] (output) */
+    int32_t* count;            /* int32 [B, P] (output) */
+    int64_t ld_row, ld_field, ld_prow, ld_pfield;
+    int32_t M, S, C, Cp, P, members, n_fields_total, pad_;
+} SeaDecodeMemberGram;       /* 120 bytes */
+int sea_decode_member_gram(const SeaDecodeMseGroup* groups, int n_groups, const SeaDecodeMemberGram* p, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Ensemble weighting against SPARSE observations: K sensors, each reading one decoded field at one cell of one patch, shared by all histories of the
  * call; the precision-weighted squared error of every member in one launch for all field groups (plus a short finish launch).  The host sorts the
  * sensors by (group, patch, given order), pads every (group, observed patch) segment to a multiple of 32 entries and hands over the tables
@@ -1250,6 +1293,33 @@ typedef struct {
     int32_t B, N, K, Ld;
 } SeaEnkfTransform;          /* 112 bytes */
 int sea_enkf_transform(const SeaEnkfTransform* p, void* stream);
+
+/* The second form of the transform: the same analysis from Q partial Gram matrices per history — sea_decode_member_gram's gram, proj and count with
+ * Q = P, one partial per patch — and an optional f32 taper [Ld, ld_taper] over the partials (NULL: all ones, Ld = 1).  Per (history b, domain d), with
+ * t_q = taper[d, q] > 0 ? taper[d, q] : 0:
+ *     C = rho^2 / (N - 1) sum_q t_q gram[b, q]        v = rho / sqrt(N - 1) sum_q t_q proj[b, q]          q ascending, fp64
+ *     status = sum_{t_q > 0} count[b, q], or -1 if a contributing count is -1 or C, v or a pivot is not finite (then D = 0 for that problem alone)
+ * A partial with t_q = 0 or count 0 is passed over by the whole workgroup.  From I + C on, the analysis is sea_enkf_transform's, by the same code:
+ * potrf -> trtri -> lauum in one LDS image, then G and D; D f32 [B, Ld, N, N] and status int32 [B, Ld] are written in full.  By construction D equals
+ * sea_enkf_transform's D for "every valid cell is a sensor with precision w and taper T[d, patch(k)]".  Without a live cell and with rho = 1, D is
+ * exactly 0.  One workgroup per (domain, history); two runs give the same bits, and a problem's bits do not depend on the other problems.
+ * Requirements: gram, proj (8-byte aligned), count, D, status non-NULL; B in 1 .. 65535; N >= 2 (above 128: SEA_EUNSUPPORTED); Q >= 1; Ld >= 1, Ld = 1
+ * without a taper; ld_taper >= Q; rho finite and >= 1; alpha in [0, 1].  Returns -1 with the entry point named in sea_last_error() otherwise, before any
+ * device is touched.  Notes the form "enkf.transform_gram" (a = the register block edge, b = the dynamic LDS bytes).  (An addition to ABI version 8; the
+ * struct is not in sea_struct_sizes().)
+ */
+typedef struct {
+    const double* gram;      /* f64 [B, Q, N, N] */
+    const double* proj;      /* f64 [B, Q, N] */
+    const int32_t* count;    /* int32 [B, Q] */
+    const float* taper;      /* NULL (1; Ld = 1) or f32 [Ld, ld_taper] */
+    float* D;                /* f32 [B, Ld, N, N] */
+    int32_t* status;         /* int32 [B, Ld] */
+    int64_t ld_taper;
+    double rho, alpha;
+    int32_t B, N, Q, Ld;
+} SeaEnkfTransformGram;      /* 88 bytes */
+int sea_enkf_transform_gram(const SeaEnkfTransformGram* p, void* stream);
 
 /* out[b N + j, g, p, :] = y[b N + j, g, p, :] + sum_i D[b, dom(p), i, j] y[b N + i, g, p, :], dom(p) = 0 when Ld = 1 and p when Ld = P.
  * y act [Bm, G, P Dl] (contiguous; what RolloutSession.step returns), D f32 [Bm / N, Ld, N, N]; the sum is accumulated in fp32 over i in ascending

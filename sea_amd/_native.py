@@ -293,6 +293,13 @@ class SeaDecodeMemberMoments(C.Structure):
                 ("M", _i32), ("S", _i32), ("C", _i32), ("Cp", _i32), ("P", _i32), ("members", _i32), ("n_fields_total", _i32), ("ld", _i32)]
 
 
+class SeaDecodeMemberGram(C.Structure):
+    # sea_decode_member_gram (not in ABI_STRUCTS, like its siblings; tests/test_field_enkf_cpu.py checks the layout through the library's argument checks)
+    _fields_ = [("obs", _vp), ("prec_field", _vp), ("prec", _vp), ("counts", _vp), ("gram", _vp), ("proj", _vp), ("count", _vp),
+                ("ld_row", _i64), ("ld_field", _i64), ("ld_prow", _i64), ("ld_pfield", _i64),
+                ("M", _i32), ("S", _i32), ("C", _i32), ("Cp", _i32), ("P", _i32), ("members", _i32), ("n_fields_total", _i32), ("pad_", _i32)]
+
+
 class SeaDecodeSensorSse(C.Structure):
     # sea_decode_sensor_sse (not in ABI_STRUCTS, like its siblings; tests/test_sensor_cpu.py checks the layout through the library's argument checks)
     _fields_ = [("obs", _vp), ("prec", _vp), ("live", _vp), ("wrow", _vp), ("seg", _vp), ("wsse", _vp), ("pred", _vp), ("work", _vp),
@@ -311,6 +318,12 @@ class SeaEnkfTransform(C.Structure):
     _fields_ = [("pred", _vp), ("obs", _vp), ("prec", _vp), ("taper", _vp), ("D", _vp), ("status", _vp),
                 ("ld_pred", _i64), ("ld_obs", _i64), ("ld_prec", _i64), ("ld_taper", _i64), ("rho", C.c_double), ("alpha", C.c_double),
                 ("B", _i32), ("N", _i32), ("K", _i32), ("Ld", _i32)]
+
+
+class SeaEnkfTransformGram(C.Structure):
+    # sea_enkf_transform_gram (not in ABI_STRUCTS either; tests/test_field_enkf_cpu.py checks the layout through the library's argument checks)
+    _fields_ = [("gram", _vp), ("proj", _vp), ("count", _vp), ("taper", _vp), ("D", _vp), ("status", _vp), ("ld_taper", _i64),
+                ("rho", C.c_double), ("alpha", C.c_double), ("B", _i32), ("N", _i32), ("Q", _i32), ("Ld", _i32)]
 
 
 class SeaEnsembleMix(C.Structure):
@@ -451,6 +464,10 @@ def lib() -> C.CDLL:
     L.sea_resample_systematic.restype = C.c_int
     L.sea_enkf_transform.argtypes = [C.POINTER(SeaEnkfTransform), _vp]
     L.sea_enkf_transform.restype = C.c_int
+    L.sea_decode_member_gram.argtypes = [C.POINTER(SeaDecodeMseGroup), C.c_int, C.POINTER(SeaDecodeMemberGram), C.c_int, _vp]
+    L.sea_decode_member_gram.restype = C.c_int
+    L.sea_enkf_transform_gram.argtypes = [C.POINTER(SeaEnkfTransformGram), _vp]
+    L.sea_enkf_transform_gram.restype = C.c_int
     L.sea_ensemble_mix.argtypes = [C.POINTER(SeaEnsembleMix), C.c_int, _vp]
     L.sea_ensemble_mix.restype = C.c_int
     L.sea_ensemble_verify.argtypes = [C.POINTER(SeaEnsembleVerify), _vp]
@@ -488,7 +505,7 @@ EXPORTED_SYMBOLS = (
     "sea_mse_fwd_bwd", "sea_relative_mse", "sea_adamw_flat", "sea_grad_norm_ctl", "sea_adamw_flat_ctl",
     "sea_wgrad_grouped", "sea_transpose_weights", "sea_rownorm_bwd", "sea_silu_outer_bwd", "sea_ib_bwd",
     "sea_attention_bwd", "sea_dropout_mask", "sea_run_list", "sea_run_list_steps", "sea_unpatchify", "sea_gemm_rownorm", "sea_exchange_tail", "sea_patchify", "sea_silu_outer_ib", "sea_mlp_fc1_ln_gelu", "sea_mlp_fc2_proj_norm", "sea_kv_rollout", "sea_kv_arena_words", "sea_kv_debug_stamps",
-    "sea_kv_cache_fill", "sea_kv_cache_fork", "sea_kv_cache_gather", "sea_decode_mse", "sea_decode_member_sse", "sea_decode_member_moments", "sea_decode_sensor_sse", "sea_decode_sensor_grad", "sea_resample_systematic", "sea_enkf_transform", "sea_ensemble_mix", "sea_ensemble_verify", "sea_ensemble_verify_ws_bytes",
+    "sea_kv_cache_fill", "sea_kv_cache_fork", "sea_kv_cache_gather", "sea_decode_mse", "sea_decode_member_sse", "sea_decode_member_moments", "sea_decode_sensor_sse", "sea_decode_sensor_grad", "sea_resample_systematic", "sea_enkf_transform", "sea_enkf_transform_gram", "sea_decode_member_gram", "sea_ensemble_mix", "sea_ensemble_verify", "sea_ensemble_verify_ws_bytes",
     "sea_gemm_fewrows", "sea_qkv_rope_fewrows", "sea_row_chain", "sea_row_chain_riders", "sea_gemm_adaln", "sea_mlp_block", "sea_adaln_qkv", "sea_splitk_finish",
     "sea_encoder_block_ws_floats", "sea_encoder_block_fwd", "sea_encoder_block_bwd",
     "sea_silu_outer_bwd_dc", "sea_silu_outer_bwd_dc_ws_floats", "sea_ib_bwd_dc",

@@ -1372,3 +1372,357 @@ extern "C" int sea_decode_sensor_grad(const SeaDecodeMseGroup* groups, int n_gro
     SEA_CHECK_LAUNCH("sea_decode_sensor_grad");
     return SEA_OK;
 }
+
+// ------------------------------------------------------------------------------------------------------------------------------------------------
+// sea_decode_member_gram: what the ensemble Kalman analysis needs from a DENSE observation of the decoded fields — per (history, patch) the N x N Gram
+// matrix of the members' weighted decoded anomalies and its product with the innovation (include/sea_hip.h states the formulas).  The walk is
+// decode_member_moments_kernel's: one workgroup of 8 waves serves one (history, patch), wave w decodes the members 16 w .. 16 w + 15 tile by tile (32
+// columns of one field; stage 1 of decode_mse_kernel, the bias in the accumulator), and the decoded values never leave the chip.  The field groups are
+// looped INSIDE the workgroup in ascending order, so one launch finishes gram, proj and count.  Per tile:
+//   a  the wave's column sums over its live members (four per lane, two butterfly steps over the lane groups) go to LDS; after a barrier every lane adds
+//      the 8 waves' sums of its column in ascending order and scales by 1 / N: ybar, the same bits in every wave.  A member row at or beyond N is passed
+//      over by a select (its hidden row is zero, so its decoded "value" is the bias: it must not reach the mean, and its anomaly must be 0, not -ybar);
+//   b  the weight of the column w = valid ? max(pf, 0) max(prec, 0) : 0 by selects (a NaN compares false); the lane forms x_j = sqrt(w) (y_j - ybar) and
+//      e = sqrt(w) (obs - ybar) in fp32 — both exactly 0 where w is not positive, whatever obs, prec or the pad columns hold — adds x_j e to its four fp64
+//      proj sums, and writes x_j to an LDS image X[member][32 columns];
+//   c  G += X X^T over the tile's 32 columns with the f32-input MFMA (v_mfma_f32_16x16x4_f32: bit for bit an ordered fmaf chain, so the fp32 sum stays
+//      inside ONE tile, in two chains of four k-steps), each 16 x 16 block then added to fp64 accumulators in registers — everything across tiles,
+//      fields and groups is fp64, in ascending (group, field, tile) order.  Both operands of a block are rows of the same image and sqrt(w) sits on
+//      both sides, so the product commutes: block (i, j) and block (j, i) have the same bits, and only the blocks of a circulant half are computed:
+//      wave w owns (w, (w + d) mod NB) for d = 0 .. NB / 2 (at d = NB / 2 with NB even only the waves below d), 4 or 5 blocks at 128 members; the
+//      mirror block is stored from the same registers, the diagonal blocks are symmetric by the commuting fmaf chain.
+// count: wave 0 counts the columns with w > 0.  A live column whose obs or whose live member value is not finite, or a stored sum that is not finite,
+// sets count = -1.  No atomics, one writer per element (an off-diagonal block and its mirror have the one owner): two runs give the same bits, and
+// nothing of a (history, patch) depends on the others.  A patch without a valid column writes zeros and leaves before any barrier.
+struct MemberGramLaunch {
+    SeaDecodeMseGroup g[SEA_DECODE_MSE_MAX_GROUPS];
+    SeaDecodeMemberGram p;
+    int n_groups;
+    float inv_n;
+};
+
+constexpr int MG_NW = 8;        // waves per workgroup: 128 members
+constexpr int MG_XP = 36;       // floats per row of the anomaly image (32 columns + 4: 16-byte rows)
+constexpr int MG_MAXD = 5;      // circulant offsets a wave may own: d = 0 .. 4 at 8 blocks
+
+template <int SP>
+constexpr int mg_lds_bytes() { return 2 * DM_TC * (SP * 2 + DM_PAD) + MG_NW * DM_TC * 4 + 16 * MG_NW * MG_XP * 4; }
+
+template <int SP>
+__global__ __launch_bounds__(64 * MG_NW) void decode_member_gram_kernel(const MemberGramLaunch L) {
+#pragma clang fp reassociate(off)
+    constexpr int NW = MG_NW;
+    constexpr int NT = 64 * NW;
+    constexpr int KS = SP / 32;
+    constexpr int PITCH = SP * 2 + DM_PAD;
+    constexpr int TILE = DM_TC * PITCH;
+    constexpr int NCH = SP * 4 / NT;
+    constexpr int XP = MG_XP;
+    static_assert(NCH * NT == DM_TC * (SP / 8), "whole chunks per thread");
+    static_assert(16 * NW * XP * 4 >= NW * 16 * 16 * 8, "the proj fold fits the anomaly image");
+    extern __shared__ __attribute__((aligned(16))) char smem[];   // 2 tile images; the waves' column sums [NW][32]; the anomaly image [128][XP]
+    float* red = reinterpret_cast<float*>(smem + 2 * TILE);
+    float* Xs = reinterpret_cast<float*>(smem + 2 * TILE + NW * DM_TC * 4);
+
+    const SeaDecodeMemberGram& P = L.p;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), li = lane & 15, lg = lane >> 4;
+    const int S = P.S, C = P.C, Cp = P.Cp, N = P.members;
+    const int bp = blockIdx.x;
+    const int b = bp / P.P, patch = bp - b * P.P;
+    double* const o_gram = P.gram + (int64_t)bp * N * N;
+    double* const o_proj = P.proj + (int64_t)bp * N;
+
+    int lim = C;   // valid columns of this patch: [0, lim) — uniform over the workgroup
+    if (P.counts != nullptr) {
+        const int cnt = P.counts[patch];
+        lim = cnt < 0 ? 0 : (cnt > C ? C : cnt);
+    }
+    const int tpf = (lim + DM_TC - 1) / DM_TC;   // tiles of a field that hold valid columns
+    if (tpf == 0) {   // uniform: before any barrier
+        for (int i = tid; i < N * N; i += NT) o_gram[i] = 0.0;
+        if (tid < N) o_proj[tid] = 0.0;
+        if (tid == 0) P.count[bp] = 0;
+        return;
+    }
+
+    const int NB = (N + 15) >> 4;               // 16-member blocks
+    const int j0 = wave * 16;
+    const bool active = j0 < N;                 // uniform over the wave
+    const int nrow = N - (j0 + 4 * lg);         // the lane's accumulator rows r < nrow are members
+    const int jm = j0 + li;
+    const bool row_live = jm < N;
+    const int64_t m = ((int64_t)b * N + (row_live ? jm : 0)) * P.P + patch;
+
+    double gacc[MG_MAXD][4], pacc[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        pacc[r] = 0.0;
+#pragma unroll
+        for (int d = 0; d < MG_MAXD; ++d) gacc[d][r] = 0.0;
+    }
+    int bad = 0, ncell = 0;
+
+    for (int gi = 0; gi < L.n_groups; ++gi) {
+        const SeaDecodeMseGroup& G = L.g[gi];
+        const __bf16* H = static_cast<const __bf16*>(G.H);
+        const __bf16* W2 = static_cast<const __bf16*>(G.W2);
+        uint4 hf[KS];
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+            const int s = ks * 32 + 8 * lg;
+            // a row at or beyond N repeats member 0's: whatever it decodes to is passed over by the selects of b.  Whole k-steps below S load plainly (a
+            // uniform branch); the step that straddles S loads column 0 where s >= S and selects zeros (the tile image is zero there, but 0 * NaN is not)
+            if (ks * 32 + 32 <= S) {
+                hf[ks] = *reinterpret_cast<const uint4*>(H + m * G.ldh + s);
+            } else {
+                const uint4 v = *reinterpret_cast<const uint4*>(H + m * G.ldh + (s < S ? s : 0));
+                hf[ks] = s < S ? v : make_uint4(0u, 0u, 0u, 0u);
+            }
+        }
+        const int n_tiles = G.n_fields * tpf;
+        uint4 wr[NCH];
+        dm_load_tile<SP, NT>(wr, W2, G.ldw, S, Cp, tpf, 0, tid);
+        dm_store_tile<SP, NT>(wr, smem, tid);   // the group before this one ended on a barrier: image 0 is free
+        __syncthreads();
+
+        int j = 0, tj = 0;   // field of tile t inside the group and the tile's index inside the field
+        for (int t = 0; t < n_tiles; ++t) {
+            const char* buf = smem + (t & 1) * TILE;
+            const int cb = tj * DM_TC;
+            const int fg = G.field0 + j;
+
+            // a: decode, the wave's column sums
+            float y[2][4];
+            if (active) {
+                f32x4 acc[2][2];
+#pragma unroll
+                for (int sub = 0; sub < 2; ++sub) {
+                    const float bv = G.bias[j * Cp + cb + sub * 16 + li];
+                    acc[sub][0] = f32x4{bv, bv, bv, bv};
+                    acc[sub][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+                }
+#pragma unroll
+                for (int ks = 0; ks < KS; ++ks) {
+                    if (ks * 32 < S) {
+#pragma unroll
+                        for (int sub = 0; sub < 2; ++sub) {
+                            const uint4 wv = *reinterpret_cast<const uint4*>(buf + (sub * 16 + li) * PITCH + (ks * 4 + lg) * 16);
+                            mma16<__bf16>(hf[ks], wv, acc[sub][ks & 1]);
+                        }
+                    }
+                }
+#pragma unroll
+                for (int sub = 0; sub < 2; ++sub) {
+                    float sm = 0.f;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        y[sub][r] = acc[sub][0][r] + acc[sub][1][r];   // plain C++: the first reader of an MFMA result must be an instruction the compiler sees
+                        sm = (r < nrow) ? add1(sm, y[sub][r]) : sm;
+                    }
+                    sm = add1(sm, __shfl_xor(sm, 16));
+                    sm = add1(sm, __shfl_xor(sm, 32));
+                    if (lg == 0) red[wave * DM_TC + sub * 16 + li] = sm;
+                }
+            } else {
+#pragma unroll
+                for (int sub = 0; sub < 2; ++sub) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) y[sub][r] = 0.f;
+                }
+                if (lane < DM_TC) red[wave * DM_TC + lane] = 0.f;
+            }
+            __syncthreads();
+            if (t + 1 < n_tiles) dm_load_tile<SP, NT>(wr, W2, G.ldw, S, Cp, tpf, t + 1, tid);   // in flight behind b and c; not alive beside a's accumulators
+
+            // b: the mean, the weights, the anomalies
+#pragma unroll
+            for (int sub = 0; sub < 2; ++sub) {
+                const int cl = sub * 16 + li, c = cb + cl;
+                float ys = red[cl];
+#pragma unroll
+                for (int w = 1; w < NW; ++w) ys = add1(ys, red[w * DM_TC + cl]);
+                const float ybar = mul1(ys, L.inv_n);
+                float w = 0.f;
+                if (c < lim) {
+                    const float pf = P.prec_field != nullptr ? P.prec_field[fg] : 1.f;
+                    const float pm = P.prec != nullptr ? P.prec[(int64_t)bp * P.ld_prow + (int64_t)fg * P.ld_pfield + c] : 1.f;
+                    w = mul1(pf > 0.f ? pf : 0.f, pm > 0.f ? pm : 0.f);
+                }
+                const bool on = w > 0.f;   // false for NaN
+                const float ov = on ? P.obs[(int64_t)bp * P.ld_row + (int64_t)fg * P.ld_field + c] : 0.f;
+                const float sw = on ? sqrtf(w) : 0.f;
+                const float e = on ? mul1(sw, add1(ov, -ybar)) : 0.f;
+                if (on && !isfinite(e)) bad = 1;
+                if (on && wave == 0 && lg == 0) ++ncell;
+                if (active) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const float x = (on && (r < nrow)) ? mul1(sw, add1(y[sub][r], -ybar)) : 0.f;
+                        if (on && (r < nrow) && !isfinite(x)) bad = 1;
+                        pacc[r] = fma((double)x, (double)e, pacc[r]);
+                        Xs[(j0 + 4 * lg + r) * XP + cl] = x;
+                    }
+                }
+            }
+            __syncthreads();
+
+            // c: the blocks of X X^T this wave owns
+            if (wave < NB) {
+                const float4 a0 = *reinterpret_cast<const float4*>(Xs + (j0 + li) * XP + 8 * lg);
+                const float4 a1 = *reinterpret_cast<const float4*>(Xs + (j0 + li) * XP + 8 * lg + 4);
+#pragma unroll
+                for (int d = 0; d < MG_MAXD; ++d) {
+                    if (2 * d <= NB && (2 * d != NB || wave < d)) {   // uniform over the wave
+                        int bj = wave + d;
+                        bj = bj >= NB ? bj - NB : bj;
+                        const float4 b0 = *reinterpret_cast<const float4*>(Xs + (bj * 16 + li) * XP + 8 * lg);
+                        const float4 b1 = *reinterpret_cast<const float4*>(Xs + (bj * 16 + li) * XP + 8 * lg + 4);
+                        f32x4 c0 = f32x4{0.f, 0.f, 0.f, 0.f}, c1 = f32x4{0.f, 0.f, 0.f, 0.f};
+                        c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.x, b0.x, c0, 0, 0, 0);
+                        c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.x, b1.x, c1, 0, 0, 0);
+                        c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.y, b0.y, c0, 0, 0, 0);
+                        c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.y, b1.y, c1, 0, 0, 0);
+                        c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.z, b0.z, c0, 0, 0, 0);
+                        c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.z, b1.z, c1, 0, 0, 0);
+                        c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.w, b0.w, c0, 0, 0, 0);
+                        c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.w, b1.w, c1, 0, 0, 0);
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) gacc[d][r] += (double)c0[r] + (double)c1[r];
+                    }
+                    if constexpr (SP > 512) __builtin_amdgcn_sched_barrier(0);   // one block's fragments at a time: with all five hoisted the widest form spills
+                }
+            }
+            if (++tj == tpf) {
+                tj = 0;
+                ++j;
+            }
+            if (t + 1 < n_tiles) dm_store_tile<SP, NT>(wr, smem + ((t + 1) & 1) * TILE, tid);
+            __syncthreads();
+        }
+    }
+
+    // the blocks and their mirrors: row 16 wave + 4 lg + r, column 16 bj + li
+    if (wave < NB) {
+#pragma unroll
+        for (int d = 0; d < MG_MAXD; ++d) {
+            if (2 * d <= NB && (2 * d != NB || wave < d)) {
+                int bj = wave + d;
+                bj = bj >= NB ? bj - NB : bj;
+                const int col = bj * 16 + li;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int row = j0 + 4 * lg + r;
+                    if (row < N && col < N) {
+                        const double v = gacc[d][r];
+                        if (!isfinite(v)) bad = 1;
+                        o_gram[(int64_t)row * N + col] = v;
+                        if (d != 0) o_gram[(int64_t)col * N + row] = v;
+                    }
+                }
+            }
+        }
+    }
+    // proj: the 16 column lanes of a member in ascending order, through the anomaly image's memory (the loop above ended on a barrier)
+    double* ps = reinterpret_cast<double*>(Xs);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) ps[(j0 + 4 * lg + r) * 16 + li] = pacc[r];
+    int* cs = reinterpret_cast<int*>(red);
+    if (wave == 0 && lg == 0) cs[li] = ncell;
+    __syncthreads();
+    if (tid < N) {
+        double s = 0.0;
+        for (int i = 0; i < 16; ++i) s += ps[tid * 16 + i];
+        if (!isfinite(s)) bad = 1;
+        o_proj[tid] = s;
+    }
+    bad = __syncthreads_or(bad);
+    if (tid == 0) {
+        int n = 0;
+        for (int i = 0; i < 16; ++i) n += cs[i];
+        P.count[bp] = bad ? -1 : n;
+    }
+}
+
+template <int SP>
+static void member_gram_launch(const MemberGramLaunch& L, dim3 grid, hipStream_t s) {
+    constexpr int lds = mg_lds_bytes<SP>();
+    static bool set_on[64] = {false};   // per device: SP = 640 needs 103 kB, above the 64 kB a kernel gets without the attribute
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = -1;
+    if (dev < 0 || !set_on[dev]) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(decode_member_gram_kernel<SP>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        if (dev >= 0) set_on[dev] = true;
+    }
+    decode_member_gram_kernel<SP><<<grid, dim3(64 * MG_NW), lds, s>>>(L);
+    sea_note_form("decode.member_gram", SP, lds);
+}
+
+extern "C" int sea_decode_member_gram(const SeaDecodeMseGroup* groups, int n_groups, const SeaDecodeMemberGram* p, int dtype, void* stream) {
+    SEA_REQUIRE(groups != nullptr && p != nullptr, "sea_decode_member_gram: null argument table");
+    SEA_REQUIRE(n_groups >= 1 && n_groups <= SEA_DECODE_MSE_MAX_GROUPS, "sea_decode_member_gram: n_groups=%d outside 1..%d", n_groups, SEA_DECODE_MSE_MAX_GROUPS);
+    SEA_REQUIRE(dtype == SEA_F32 || dtype == SEA_BF16, "sea_decode_member_gram: bad dtype %d", dtype);
+    if (dtype != SEA_BF16) {
+        sea_set_error("sea_decode_member_gram: unsupported: bf16 only (the fp32 decoder composes sea_gemm_grouped and fp64 reductions)");
+        return SEA_EUNSUPPORTED;
+    }
+    const SeaDecodeMemberGram& P = *p;
+    SEA_REQUIRE(P.obs != nullptr && P.gram != nullptr && P.proj != nullptr && P.count != nullptr,
+                "sea_decode_member_gram: null pointer (obs, gram, proj and count are required; prec_field, prec and counts may be NULL)");
+    SEA_REQUIRE(P.M >= 1, "sea_decode_member_gram: M=%d must be positive", P.M);
+    SEA_REQUIRE(P.S >= 8 && P.S % 8 == 0, "sea_decode_member_gram: S=%d must be a positive multiple of 8", P.S);
+    SEA_REQUIRE(P.Cp >= 32 && P.Cp % 32 == 0, "sea_decode_member_gram: Cp=%d must be a positive multiple of 32", P.Cp);
+    SEA_REQUIRE(P.C >= 1 && P.C <= P.Cp, "sea_decode_member_gram: C=%d must lie in 1..Cp=%d", P.C, P.Cp);
+    SEA_REQUIRE(P.P >= 1, "sea_decode_member_gram: P=%d must be positive", P.P);
+    SEA_REQUIRE(P.members >= 2, "sea_decode_member_gram: members=%d: an analysis needs at least 2 members", P.members);
+    SEA_REQUIRE((int64_t)P.M % ((int64_t)P.P * P.members) == 0, "sea_decode_member_gram: M=%d is not a multiple of P * members = %d * %d", P.M, P.P, P.members);
+    SEA_REQUIRE(P.n_fields_total >= 1, "sea_decode_member_gram: n_fields_total=%d must be positive", P.n_fields_total);
+    SEA_REQUIRE(P.ld_field >= P.C && P.ld_row >= 0, "sea_decode_member_gram: obs strides ld_row=%lld, ld_field=%lld must cover C=%d", (long long)P.ld_row,
+                (long long)P.ld_field, P.C);
+    SEA_REQUIRE(P.prec == nullptr || (P.ld_pfield >= P.C && P.ld_prow >= 0), "sea_decode_member_gram: prec strides ld_prow=%lld, ld_pfield=%lld must cover C=%d",
+                (long long)P.ld_prow, (long long)P.ld_pfield, P.C);
+    SEA_REQUIRE(sea_aligned4(P.obs) && sea_aligned4(P.prec_field) && sea_aligned4(P.prec) && sea_aligned4(P.counts) && sea_aligned4(P.count) &&
+                    (reinterpret_cast<uintptr_t>(P.gram) & 7u) == 0 && (reinterpret_cast<uintptr_t>(P.proj) & 7u) == 0,
+                "sea_decode_member_gram: misaligned obs, prec_field, prec, counts, count (4 bytes), gram or proj (8 bytes) pointer");
+    int64_t covered = 0;
+    for (int g = 0; g < n_groups; ++g) {
+        const SeaDecodeMseGroup& G = groups[g];
+        SEA_REQUIRE(G.H != nullptr && G.W2 != nullptr && G.bias != nullptr, "sea_decode_member_gram: group %d: null pointer", g);
+        SEA_REQUIRE(sea_aligned16(G.H) && sea_aligned16(G.W2) && sea_aligned16(G.bias), "sea_decode_member_gram: group %d: pointers must be 16-byte aligned", g);
+        SEA_REQUIRE(G.ldh >= P.S && G.ldh % 8 == 0 && G.ldw >= P.S && G.ldw % 8 == 0,
+                    "sea_decode_member_gram: group %d: row strides ldh=%d ldw=%d must cover S=%d and be multiples of 8", g, G.ldh, G.ldw, P.S);
+        SEA_REQUIRE(G.n_fields >= 1 && G.field0 >= 0 && (int64_t)G.field0 + G.n_fields <= P.n_fields_total,
+                    "sea_decode_member_gram: group %d: n_fields=%d, field0=%d outside the %d fields", g, G.n_fields, G.field0, P.n_fields_total);
+        SEA_REQUIRE((int64_t)G.n_fields * P.Cp <= 0x7fffffffLL / 2, "sea_decode_member_gram: group %d: too many output columns", g);
+        for (int h = 0; h < g; ++h)
+            SEA_REQUIRE(G.field0 >= groups[h].field0 + groups[h].n_fields || groups[h].field0 >= G.field0 + G.n_fields,
+                        "sea_decode_member_gram: group %d: its fields overlap those of group %d (a cell is counted once)", g, h);
+        covered += G.n_fields;
+    }
+    SEA_REQUIRE(covered == P.n_fields_total, "sea_decode_member_gram: the groups cover %lld of the %d fields (every field needs exactly one group)", (long long)covered, P.n_fields_total);
+    if (P.S > 640) {
+        sea_set_error("sea_decode_member_gram: unsupported: hidden width S=%d above 640", P.S);
+        return SEA_EUNSUPPORTED;
+    }
+    if (P.members > 16 * MG_NW) {
+        sea_set_error("sea_decode_member_gram: unsupported: members=%d above %d", P.members, 16 * MG_NW);
+        return SEA_EUNSUPPORTED;
+    }
+    const int64_t BP = (int64_t)P.M / P.members;   // (history, patch) pairs
+    SEA_REQUIRE(BP <= 0x7fffffffLL, "sea_decode_member_gram: too many rows");
+
+    MemberGramLaunch L;
+    memset(&L, 0, sizeof(L));
+    for (int g = 0; g < n_groups; ++g) L.g[g] = groups[g];
+    L.p = P;
+    L.n_groups = n_groups;
+    L.inv_n = 1.0f / (float)P.members;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)BP);
+    if (P.S <= 128) member_gram_launch<128>(L, grid, s);
+    else if (P.S <= 256) member_gram_launch<256>(L, grid, s);
+    else if (P.S <= 384) member_gram_launch<384>(L, grid, s);
+    else if (P.S <= 512) member_gram_launch<512>(L, grid, s);
+    else member_gram_launch<640>(L, grid, s);
+    SEA_CHECK_LAUNCH("sea_decode_member_gram");
+    return SEA_OK;
+}

@@ -34,6 +34,12 @@ The ensemble Kalman analysis moves all members at once (SensorKalman: sea_enkf_t
                           taper=unpatcher.sensor_taper(sensors, radius))      # taper=None: one analysis domain for all patches
     y = ens.step(c_next, state=kalman.analyse(y, sensors.scale_values(readings), precision))
 
+A dense snapshot takes the same analysis through FieldKalman (sea_decode_member_gram + sea_enkf_transform_gram + sea_ensemble_mix: the members' decoded
+fields are reduced to one N x N Gram matrix per (history, patch) while they are decoded; a [P, P] taper between patch centroids localises):
+
+    kalman = FieldKalman(decoder, n_patches, members=n, counts=counts, sigma=sigma_cell, inflation=1.05, taper=unpatcher.patch_taper(radius))
+    y = ens.step(c_next, state=kalman.analyse(y, obs, precision))             # obs [B, P, n_fields, C]; precision: a map of obs's shape, 0 = missing
+
 Whether the ensemble is any good is read at the same sensors (SensorVerification: sea_ensemble_verify behind the same predictions):
 
     verify = SensorVerification(decoder, n_patches, members=n, sensors=sensors, sigma=sensors.scale_sigma(sigma_phys))
@@ -685,6 +691,195 @@ class SensorKalman:
         yc = y.detach().contiguous()
         with torch.no_grad():
             if self._fused_for(obs.shape[0]):
+                return ops.ensemble_mix(yc, D, self.n_patches, output=True, increment=bool(increment))
+            inc = _composed_mix(yc, D, self.n_patches)
+            out = (yc.to(torch.float32) + inc).to(y.dtype)
+        return (out, inc) if increment else out
+
+
+def _composed_transform_gram(gram, proj, count, taper, members: int, rho: float, alpha: float):
+    """sea_enkf_transform_gram's formulas (include/sea_hip.h) as fp64 torch ops on gram's device: (D f32 [B, Ld, N, N], status int32 [B, Ld])."""
+    f64 = torch.float64
+    n = members
+    B, Q = count.shape
+    zero = torch.zeros((), device=gram.device, dtype=f64)
+    t = torch.ones(1, Q, device=gram.device, dtype=f64) if taper is None else taper.to(f64)
+    t = torch.where(t > 0, t, zero)                                                                  # [Ld, Q]
+    use = (t > 0).unsqueeze(0) & (count != 0).unsqueeze(1)                                           # [B, Ld, Q]
+    tw = torch.where(use & (count > 0).unsqueeze(1), t.unsqueeze(0), zero)
+    ok = (count > 0)
+    g = torch.where(ok[..., None, None], gram, zero)
+    pr = torch.where(ok[..., None], proj, zero)
+    C_ = (rho * rho / (n - 1)) * torch.einsum("bdq,bqij->bdij", tw, g)
+    v = (rho / math.sqrt(n - 1)) * torch.einsum("bdq,bqi->bdi", tw, pr)
+    eye = torch.eye(n, device=gram.device, dtype=f64)
+    bad = (use & (count < 0).unsqueeze(1)).any(-1) | ~(torch.isfinite(C_).all(-1).all(-1) & torch.isfinite(v).all(-1))    # [B, Ld]
+    Msafe = torch.where(bad[..., None, None], eye, eye + C_)
+    L, _ = torch.linalg.cholesky_ex(Msafe, check_errors=False)
+    bad = bad | ~torch.isfinite(L).all(-1).all(-1)
+    W = torch.cholesky_solve(eye.expand_as(Msafe).contiguous(), torch.where(bad[..., None, None], eye, L))
+    G = (W @ torch.where(bad[..., None], zero, v).unsqueeze(-1)) / math.sqrt(n - 1) - alpha * (eye - W)
+    Pi = eye - 1.0 / n
+    D = (rho - 1.0) * Pi + rho * (G - G.mean(dim=-2, keepdim=True))
+    D = torch.where(bad[..., None, None], zero, D)
+    live = torch.where(use, count.unsqueeze(1).expand_as(use), torch.zeros_like(count).unsqueeze(1).expand_as(use)).sum(-1).to(torch.int32)
+    status = torch.where(bad, torch.full_like(live, -1), live)
+    return D.to(torch.float32).contiguous(), status
+
+
+class FieldKalman:
+    """The ensemble Kalman analysis of an ensemble's latent states from a DENSE snapshot of the decoded fields — a PIV frame, a coarse solver's field, a
+    reanalysis — by the deterministic EnKF of Sakov & Oke (2008) in ensemble space: kalman.analyse(y, obs, precision=None) -> y_a in y's layout and
+    dtype, a corrected state for RolloutSession.step(c, state=y_a).  All members move, none is duplicated; no random numbers.
+
+    y, obs, layout, counts and sigma mean what they mean in FieldLikelihood: y [B * members, n_groups, P * D] as RolloutSession.step returns it (member j
+    of history b at row b * members + j); obs float32 [B, P, n_fields, C >= n_inp] (layout "BPFC") or the reference's [B, P, C, n_fields] ("BPCF"), one
+    snapshot per history, in the decoder's scaled units; counts: valid cells per patch (None: all); sigma: None (1), a positive number or n_fields
+    positive numbers — the precision of a cell of field f is 1 / sigma_f^2.  precision: an optional float32 map in obs's layout and shape, >= 0, that
+    multiplies it; 0 marks a missing cell, neutral whatever obs holds there (NaN included).  A dense snapshot makes the ensemble-space matrix large:
+    choose sigma as the error of one CELL, not of a field.
+    Three launches behind the decoder's first layer: sea_decode_member_gram (per (history, patch) the N x N Gram matrix of the members' weighted decoded
+    anomalies and its product with the innovation; the members' fields and a [B * N, cells] prediction matrix never exist), sea_enkf_transform_gram
+    (the weighted sum of the patches' matrices per analysis domain, then SensorKalman's factorisation: D [B, Ld, N, N], include/sea_hip.h), and
+    sea_ensemble_mix (y_a[j] = y[j] + sum_i D[i, j] y[i]).  taper: None — one domain, every patch takes the same D; or a float [P, P] array in [0, 1]
+    (MeshUnpatcher.patch_taper) — patch p's latent slice is analysed by its own problem in which the cells of patch q weigh taper[p, q]; uploaded once
+    per device.  Because a domain's matrix is a weighted sum of patch matrices, localisation costs P small sums per domain, not a pass over the cells.
+    transform(y, obs, precision) -> (D, status): status int32 [B, Ld] is the number of live cells of a problem, or -1 where an operand of a contributing
+    patch was not finite: that problem's D is 0 and its states pass through unchanged.  analyse(..., increment=True) also returns the fp32 increment.
+    fused: True — the launches above (bf16 only); False — Decode.forward plus the same formulas as fp64 torch ops and batched fp32 products, for
+    comparison (it holds the members' decoded fields in float64 and needs torch.linalg's Cholesky on the device, whose factor at 128 members came back
+    wrong in one of three runs in the torch build this was developed on: DESIGN.md section 7j).  fused=None decides the DECODE (fused launch or
+    Decode.forward plus fp64 reductions, the only form in fp32) and always takes the transform and mix launches, which do not depend on the
+    decoder's dtype and are ahead of the torch formulas in every measured row (0.14 - 0.15 against 0.42 - 0.73 ms).  It is the measured rule
+    (tools/field_enkf_bench.py, profiles/field_enkf_bench.txt; 64 members x 64 patches, n_inp 1628, cylinder and multiphase
+    decoder, every column valid and the mesh's counts, device time per analyse call): one history, one domain 0.87 - 0.94 ms fused against 1.44 -
+    1.47 ms composed; one history, 64 domains 0.83 - 0.90 against 1.79 - 1.92 ms; four histories 0.85 - 0.96 against 4.15 - 4.28 ms; 7 launches against
+    152 - 168; 11 - 54 MB of extra memory against 0.5 - 2.5 GB; SensorKalman with every valid cell a sensor: 18.5 ms (90 000 cells) and 63.1 ms (312 576).
+    So: the fused decode in bf16 from 4096 rows (B * members * P) on — every measured row — and the composed decode below, where nothing was measured.
+    A call reads nothing back from the device and uploads nothing after the first call on a device.  2 <= members <= 128.  `decoder` is a sea_amd
+    Decode; no autograd graph is built."""
+
+    def __init__(self, decoder, n_patches: int, members: int, counts=None, layout: str = "BPFC", sigma=None, inflation: float = 1.0,
+                 anomaly_gain: float = 0.5, taper=None, fused: Optional[bool] = None):
+        if layout not in ("BPFC", "BPCF"):
+            raise ValueError(f"FieldKalman: layout must be 'BPFC' or 'BPCF', got {layout!r}")
+        if not isinstance(n_patches, int) or isinstance(n_patches, bool) or n_patches < 1:
+            raise ValueError(f"FieldKalman: n_patches = {n_patches!r} must be a positive integer")
+        if not isinstance(members, int) or isinstance(members, bool) or members < 2 or members > N.ENKF_MAX_N:
+            raise ValueError(f"FieldKalman: members = {members!r} must be an integer in 2 .. {N.ENKF_MAX_N}")
+        for name, v, lo, hi in (("inflation", inflation, 1.0, float("inf")), ("anomaly_gain", anomaly_gain, 0.0, 1.0)):
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or not lo <= v <= hi:
+                raise ValueError(f"FieldKalman: {name} = {v!r} must be a finite number in [{lo}, {hi}]")
+        if fused not in (None, True, False):
+            raise ValueError(f"FieldKalman: fused must be None, True or False, got {fused!r}")
+        self.decoder, self.n_patches, self.members, self.counts, self.layout, self.fused = decoder, n_patches, members, counts, layout, fused
+        self.inflation, self.anomaly_gain = float(inflation), float(anomaly_gain)
+        n_fields = sum(len(g) for g in decoder.field_groups)
+        if sigma is None:
+            self._prec_host = None
+        else:
+            s = torch.as_tensor(sigma, dtype=torch.float64).detach().cpu()   # a tensor given on the device comes to the host once, here
+            if s.dim() > 1 or (s.dim() == 1 and s.numel() != n_fields):
+                raise ValueError(f"FieldKalman: sigma must be None, a number or {n_fields} numbers (one per field), got shape {tuple(s.shape)}")
+            if not bool(torch.isfinite(s).all()) or not bool((s > 0).all()):
+                raise ValueError(f"FieldKalman: sigma must be finite and positive, got {s.tolist()}")
+            self._prec_host = [float(v) for v in (1.0 / (s * s)).expand(n_fields)]
+        self._prec = None
+        self._taper = {}
+        if taper is None:
+            self._taper_src = None
+        else:
+            t = taper if torch.is_tensor(taper) else torch.as_tensor(taper)
+            if t.dim() != 2 or tuple(t.shape) != (n_patches, n_patches) or not t.is_floating_point():
+                raise ValueError(f"FieldKalman: taper must be None or a float [{n_patches}, {n_patches}] array (row p: the weights of the patches in patch p's "
+                                 f"analysis), got {tuple(t.shape)} {t.dtype}")
+            t = t.detach().to(torch.float32).contiguous()
+            if t.device.type == "cpu" and (not bool(torch.isfinite(t).all()) or not bool(((t >= 0) & (t <= 1)).all())):
+                raise ValueError("FieldKalman: taper weights must lie in [0, 1]")
+            self._taper_src = t
+            self._taper[t.device] = t
+            dev = next(iter(decoder.parameters())).device
+            if dev.type == "cuda":
+                self._taper_on(dev)
+
+    def _taper_on(self, device):
+        if self._taper_src is None:
+            return None
+        t = self._taper.get(device)
+        if t is None:
+            t = self._taper[device] = self._taper_src.to(device)
+        return t
+
+    def _field_precision(self, device):
+        """1 / sigma_f^2 as an f32 [n_fields] tensor on the device (None without sigma), built once per device by fills."""
+        if self._prec_host is None:
+            return None
+        if self._prec is None or self._prec.device != device:
+            prec = torch.empty(len(self._prec_host), device=device, dtype=torch.float32)
+            for f, v in enumerate(self._prec_host):
+                prec[f].fill_(v)
+            self._prec = prec
+        return self._prec
+
+    def _fused_for(self, y) -> bool:
+        """Whether the decode and reduction run as the fused launch (sea_decode_member_gram)."""
+        if self.fused is not None:
+            return bool(self.fused)
+        return self.decoder._act_dtype() == torch.bfloat16 and y.shape[0] * self.n_patches >= 4096
+
+    def _native_tail(self) -> bool:
+        """Whether the transform and the mix run as sea_enkf_transform_gram and sea_ensemble_mix: always, except with fused=False (all torch ops, for
+        comparison).  The two launches take fp64 partials and fp32 or bf16 states whatever the decoder computed in."""
+        return self.fused is not False
+
+    def _operands(self, y, obs, precision):
+        P, n = self.n_patches, self.members
+        if not torch.is_tensor(y) or y.dim() != 3 or y.shape[-1] % P or y.shape[0] < 1:
+            raise ValueError(f"FieldKalman: y must be [B * members, n_groups, n_patches * D] with n_patches = {P}, got "
+                             f"{tuple(y.shape) if torch.is_tensor(y) else type(y).__name__}")
+        Bm = y.shape[0]
+        if Bm % n:
+            raise ValueError(f"FieldKalman: the {Bm} trajectories of y are not a multiple of members = {n}")
+        B = Bm // n
+        if not torch.is_tensor(obs) or obs.dim() != 4 or tuple(obs.shape[:2]) != (B, P):
+            raise ValueError(f"FieldKalman: the observation must be [{B}, {P}, ...] in layout {self.layout} (one snapshot per history), got "
+                             f"{tuple(obs.shape) if torch.is_tensor(obs) else type(obs).__name__}")
+        if obs.dtype != torch.float32 or obs.device != y.device:
+            raise ValueError(f"FieldKalman: obs must be float32 on {y.device}, got {obs.dtype} on {obs.device}")
+        if precision is not None:
+            if not torch.is_tensor(precision) or tuple(precision.shape) != tuple(obs.shape):
+                raise ValueError(f"FieldKalman: precision must be None or a map of obs's shape {tuple(obs.shape)}, got "
+                                 f"{tuple(precision.shape) if torch.is_tensor(precision) else type(precision).__name__}")
+            if precision.dtype != torch.float32:
+                raise ValueError(f"FieldKalman: precision must be float32, got {precision.dtype}")
+            if precision.device.type == "cpu" and (not bool(torch.isfinite(precision).all()) or not bool((precision >= 0).all())):
+                raise ValueError("FieldKalman: precision must be finite and >= 0")
+            if precision.device != y.device:
+                raise ValueError(f"FieldKalman: precision is on {precision.device}, the states on {y.device}")
+        N.require_gpu(y, "FieldKalman states")
+        perm = (lambda t: t) if self.layout == "BPFC" else (lambda t: t.permute(0, 1, 3, 2))
+        return y.detach(), perm(obs.detach()), None if precision is None else perm(precision.detach())
+
+    def transform(self, y: torch.Tensor, obs: torch.Tensor, precision: Optional[torch.Tensor] = None):
+        """(D f32 [B, Ld, N, N], status int32 [B, Ld]): the ensemble-space matrix of the analysis and the live cells per problem (-1: no update)."""
+        y, tgt, prec = self._operands(y, obs, precision)
+        Bm, G, E = y.shape
+        P, n = self.n_patches, self.members
+        fused = self._fused_for(y)
+        z = y.reshape(Bm, G, P, E // P).permute(0, 2, 1, 3)          # the re-layout of FieldLikelihood
+        gram, proj, count = self.decoder.member_gram(z, tgt, n, counts=self.counts, precision=prec, field_precision=self._field_precision(y.device), fused=fused)
+        taper = self._taper_on(y.device)
+        with torch.no_grad():
+            if self._native_tail():
+                return ops.enkf_transform_gram(gram, proj, count, taper=taper, rho=self.inflation, alpha=self.anomaly_gain)
+            return _composed_transform_gram(gram, proj, count, taper, n, self.inflation, self.anomaly_gain)
+
+    def analyse(self, y: torch.Tensor, obs: torch.Tensor, precision: Optional[torch.Tensor] = None, increment: bool = False):
+        """y_a in y's layout and dtype — or (y_a, increment f32) with increment=True — from one snapshot: the correct(y, observation) of a rollout."""
+        D, _ = self.transform(y, obs, precision)
+        yc = y.detach().contiguous()
+        with torch.no_grad():
+            if self._native_tail():
                 return ops.ensemble_mix(yc, D, self.n_patches, output=True, increment=bool(increment))
             inc = _composed_mix(yc, D, self.n_patches)
             out = (yc.to(torch.float32) + inc).to(y.dtype)

@@ -511,6 +511,97 @@ class Decode(nn.Module):
             mean, var = mean.view(B, P, n_fields, Cp), var.view(B, P, n_fields, Cp)
             return (mean, var) if Cp == C else (mean[..., :C], var[..., :C])
 
+    def member_gram(self, z: torch.Tensor, obs: torch.Tensor, members: int, counts=None, precision: Optional[torch.Tensor] = None,
+                    field_precision: Optional[torch.Tensor] = None, fused: Optional[bool] = None):
+        """What an ensemble Kalman analysis needs from a DENSE observation of the decoded fields: (gram, proj, count) per (history, patch) —
+        gram float64 [B, P, members, members] = sum over the live cells of w a_i a_j with a_j = y_j - mean_j y_j the decoded anomaly of member j, proj
+        float64 [B, P, members] = sum w a_j (obs - mean_j y_j), count int32 [B, P] the live cells, or -1 where obs or a member's value at a live
+        cell, or a sum, is not finite (include/sea_hip.h, sea_decode_member_gram, states the formulas); no autograd graph.  z [B * members, P,
+        n_groups, embed_dim] in fork() order; obs float32 [B, P, n_fields, C >= n_inp] on z's device, one snapshot per history; counts as in
+        mse_loss (all-zero counts are accepted); precision: None or a float32 map of obs's shape, >= 0, 0 marks a missing cell; field_precision: None
+        or float32 [n_fields] on z's device.  The weight of a cell is w = valid ? max(field_precision, 0) * max(precision, 0) : 0, by selects: a
+        cell without weight is neutral whatever obs and precision hold there, NaN included.  2 <= members <= 128.
+        bf16 compute dtype: the first-layer launch plus ONE fused launch (sea_decode_member_gram) — neither the members' decoded fields nor a
+        [B * members, cells] prediction matrix are ever written; fp32, or fused=False: forward() plus float64 torch ops with the same selects (the
+        composed path: it holds the members' fields in float64).  fused=None: the fused launch in bf16 from 4096 rows (B * members * P) on — measured
+        at 4096 and 16384 rows (tools/field_enkf_bench.py, profiles/field_enkf_bench.txt, DESIGN.md section 7j: 0.64 - 0.72 ms for this call; the
+        composed analysis it replaces takes 1.4 - 4.3 ms) — and the composed path below, where nothing has been measured."""
+        what = "sea_amd.Decode.member_gram"
+        n_fields = sum(len(g) for g in self.field_groups)
+        C, Cp = self.n_inp, self._n_inp_p
+        if not torch.is_tensor(z) or z.dim() != 4 or z.shape[2] != self.num_groups or z.shape[3] != self.embed_dim:
+            raise ValueError(f"{what}: z must be [B * members, P, {self.num_groups}, {self.embed_dim}], got {tuple(z.shape) if torch.is_tensor(z) else type(z).__name__}")
+        Bm, P = z.shape[0], z.shape[1]
+        if not isinstance(members, int) or isinstance(members, bool) or members < 2 or members > N.ENKF_MAX_N or Bm < 1 or Bm % members:
+            raise ValueError(f"{what}: members = {members!r} must be an integer in 2 .. {N.ENKF_MAX_N} that divides the {Bm} rows of z")
+        B = Bm // members
+        for name, t in (("obs", obs), ("precision", precision)):
+            if t is None and name == "precision":
+                continue
+            if not torch.is_tensor(t) or t.dim() != 4 or tuple(t.shape[:3]) != (B, P, n_fields) or t.shape[3] < C:
+                raise ValueError(f"{what}: {name} must be [{B}, {P}, {n_fields}, >= {C}] (one per history of {members} members), got "
+                                 f"{tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
+            if t.dtype != torch.float32 or t.device != z.device:
+                raise ValueError(f"{what}: {name} must be float32 on {z.device}, got {t.dtype} on {t.device}")
+        if precision is not None and precision.shape[3] != obs.shape[3]:
+            raise ValueError(f"{what}: precision must have obs's shape {tuple(obs.shape)}, got {tuple(precision.shape)}")
+        if field_precision is not None and (not torch.is_tensor(field_precision) or field_precision.dtype != torch.float32 or tuple(field_precision.shape) != (n_fields,)
+                                            or field_precision.device != z.device):
+            raise ValueError(f"{what}: field_precision must be None or a float32 [{n_fields}] tensor on {z.device}")
+        dt = self._act_dtype()
+        if fused is None:
+            fused = dt == torch.bfloat16 and Bm * P >= 4096
+        if fused and dt != torch.bfloat16:
+            raise ValueError(f"{what}: the fused launch is bf16 only (set_compute_dtype('bf16'), or fused=False)")
+        cnt, _ = self._valid_counts(counts, P, z.device, allow_empty=True, what="member_gram")
+        N.require_gpu(z, "Decode.member_gram input")
+        with torch.no_grad():
+            obs = obs.detach()
+            prec = None if precision is None else precision.detach()
+            pf = None if field_precision is None else field_precision.detach().contiguous()
+            if not fused:
+                f64 = torch.float64
+                zero = torch.zeros((), device=z.device, dtype=f64)
+                y = self.forward(z.detach()).view(B, members, P, n_fields, C).to(f64)
+                w = torch.ones(B, P, n_fields, C, device=z.device, dtype=f64)
+                if pf is not None:
+                    pf64 = pf.to(f64).view(1, 1, n_fields, 1)
+                    w = w * torch.where(pf64 > 0, pf64, zero)
+                if prec is not None:
+                    pm = prec[..., :C].to(f64)
+                    w = w * torch.where(pm > 0, pm, zero)
+                if cnt is not None:
+                    w = torch.where((torch.arange(C, device=z.device) < cnt[:, None]).view(1, P, 1, C), w, zero)
+                live = w > 0                                                         # false for NaN
+                sw = torch.where(live, w, zero).sqrt()
+                ybar = y.mean(dim=1)                                                 # [B, P, F, C]
+                X = torch.where(live.unsqueeze(1), (y - ybar.unsqueeze(1)) * sw.unsqueeze(1), zero)          # [B, n, P, F, C]
+                e = torch.where(live, sw * (obs[..., :C].to(f64) - ybar), zero)
+                Xp = X.permute(0, 2, 1, 3, 4).reshape(B, P, members, n_fields * C)
+                gram = Xp @ Xp.transpose(-1, -2)
+                gram = 0.5 * (gram + gram.transpose(-1, -2))
+                proj = (Xp @ e.reshape(B, P, n_fields * C, 1)).squeeze(-1)
+                count = live.sum(dim=(2, 3)).to(torch.int32)
+                bad = ~(torch.isfinite(X).all(-1).all(-1).all(1) & torch.isfinite(e).all(-1).all(-1)) \
+                    | ~(torch.isfinite(gram).all(-1).all(-1) & torch.isfinite(proj).all(-1))
+                return gram.contiguous(), proj.contiguous(), torch.where(bad, torch.full_like(count, -1), count)
+
+            def rows(t):   # [B * P, n_fields, width] with unit inner stride: a view where the layout allows it, else one copy of the first C columns
+                t3 = t.reshape(B * P, n_fields, t.shape[3])
+                return t3 if t3.stride(2) == 1 and t3.stride(1) >= C and t3.stride(0) >= 0 else t3[..., :C].contiguous()
+
+            M = Bm * P
+            G, D = self.num_groups, self.embed_dim
+            zf = z.detach().to(torch.float32).contiguous().view(M, G * D)
+            za = torch.empty(M, G * D, device=z.device, dtype=dt)
+            ops.convert(zf, za)
+            W1, W2 = self._weights(dt)
+            hid = [torch.empty(M, self.MLP_hidden, device=z.device, dtype=dt) for _ in range(G)]
+            ops.gemm_grouped([dict(A=za[:, g * D:(g + 1) * D], W=W1[g], Cact=hid[g], act=1) for g in range(G)], dt)
+            bias = self._shadow[3]
+            return ops.decode_member_gram([dict(H=hid[g], W2=W2[g], bias=bias[g]) for g in range(G)], rows(obs), C, Cp, P, members, prec_field=pf,
+                                          prec=None if prec is None else rows(prec), counts=cnt, dtype=dt)
+
     def forward_prefix(self, z: torch.Tensor, buckets) -> torch.Tensor:
         """The decoder for a consumer that only reads the first cells of a patch (MeshUnpatcher.decode_and_unpatch: a patch holds as many mesh points as its
         cell has, the rest of its n_inp columns is padding nobody reads — 71 % of the columns on the bench's wake-refined mesh).  z [B, P, n_groups,

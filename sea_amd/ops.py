@@ -1319,6 +1319,98 @@ def decode_member_moments(groups: Sequence[Dict], C_: int, Cp: int, n_patches: i
     return mean, var
 
 
+def fill_decode_member_gram(groups_arr, P: N.SeaDecodeMemberGram, groups: Sequence[Dict], obs, prec_field, prec, counts, n_patches: int, members: int, C_: int, Cp: int,
+                            gram, proj, count) -> None:
+    """The argument table of sea_decode_member_gram.  groups as fill_decode_member_moments; obs (and prec, when given) f32 [B * n_patches, n_fields_total,
+    >= C] with unit inner stride; prec_field f32 [n_fields_total] or None; gram f64 [B, n_patches, members, members], proj f64 [B, n_patches, members],
+    count int32 [B, n_patches], contiguous."""
+    field0 = 0
+    for g, d in zip(groups_arr, groups):
+        H, W2 = d["H"], d["W2"]
+        g.H, g.W2, g.bias, g.dH, g.Z = H.data_ptr(), W2.data_ptr(), d["bias"].data_ptr(), None, None
+        g.ldh, g.ldw, g.lddh, g.ldz = H.stride(0), W2.stride(0), 0, 0
+        g.n_fields, g.field0 = W2.shape[0] // Cp, field0
+        field0 += g.n_fields
+    P.obs, P.prec_field, P.prec, P.counts = obs.data_ptr(), N.ptr(prec_field), N.ptr(prec), N.ptr(counts)
+    P.gram, P.proj, P.count = gram.data_ptr(), proj.data_ptr(), count.data_ptr()
+    P.ld_row, P.ld_field = obs.stride(0), obs.stride(1)
+    P.ld_prow, P.ld_pfield = (0, 0) if prec is None else (prec.stride(0), prec.stride(1))
+    P.M, P.S, P.C, P.Cp, P.P = groups[0]["H"].shape[0], groups[0]["H"].shape[1], C_, Cp, n_patches
+    P.members, P.n_fields_total, P.pad_ = members, field0, 0
+
+
+def decode_member_gram(groups: Sequence[Dict], obs: torch.Tensor, C_: int, Cp: int, n_patches: int, members: int, prec_field: Optional[torch.Tensor] = None,
+                       prec: Optional[torch.Tensor] = None, counts: Optional[torch.Tensor] = None, dtype: torch.dtype = torch.bfloat16, out=None):
+    """sea_decode_member_gram: per (history, patch) the Gram matrix of the members' weighted decoded anomalies, its product with the innovation and the
+    number of live cells (include/sea_hip.h states the formulas): (gram f64 [B, n_patches, members, members], proj f64 [B, n_patches, members], count int32
+    [B, n_patches]) on the device; nothing is read back.  groups as fill_decode_member_moments (row m is patch m % n_patches of member m // n_patches);
+    obs f32 [B * n_patches, n_fields, >= C] with unit inner stride; prec None or a map of obs's shape; prec_field None or f32 [n_fields]; counts device
+    int32 [n_patches] or None; out: (gram, proj, count) tensors to write into (every element is written).  Everything is checked on the host before the
+    launch."""
+    what = "decode_member_gram"
+    if dtype != torch.bfloat16:
+        raise ValueError(f"{what}: the fused launch is bf16 only, got {dtype}")
+    if not groups or len(groups) > N.DECODE_MSE_MAX_GROUPS:
+        raise ValueError(f"{what}: {len(groups)} groups; a launch carries 1 .. {N.DECODE_MSE_MAX_GROUPS}")
+    if Cp < 32 or Cp % 32 or not 1 <= C_ <= Cp:
+        raise ValueError(f"{what}: need Cp a multiple of 32 and 1 <= C <= Cp, got C = {C_}, Cp = {Cp}")
+    dev = groups[0]["H"].device
+    M, S = tuple(groups[0]["H"].shape) if groups[0]["H"].dim() == 2 else (0, 0)
+    if M < 1 or S < 8 or S % 8 or S > N.DECODE_MSE_MAX_S:
+        raise ValueError(f"{what}: H must be [M >= 1, S] with S a multiple of 8 up to {N.DECODE_MSE_MAX_S}, got {tuple(groups[0]['H'].shape)}")
+    if not isinstance(members, int) or isinstance(members, bool) or members < 2 or members > N.ENKF_MAX_N:
+        raise ValueError(f"{what}: members = {members!r} must be an integer in 2 .. {N.ENKF_MAX_N}")
+    if n_patches < 1 or M % (n_patches * members):
+        raise ValueError(f"{what}: {M} rows are not a multiple of n_patches * members = {n_patches} * {members}")
+    n_fields = 0
+    for i, d in enumerate(groups):
+        for name in ("H", "W2"):
+            t = d[name]
+            if t.dim() != 2 or t.stride(1) != 1:
+                raise ValueError(f"{what} group {i}: {name}: need a 2-D tensor with unit inner stride, got shape {tuple(t.shape)} strides {t.stride()}")
+            if t.dtype != dtype or t.device != dev or t.shape[1] != S or (name != "W2" and t.shape[0] != M):
+                raise ValueError(f"{what} group {i}: {name} must be a {dtype} [{'n_fields * Cp' if name == 'W2' else M}, {S}] tensor on {dev}, got "
+                                 f"{tuple(t.shape)} {t.dtype} on {t.device}")
+            if t.stride(0) % 8 or t.data_ptr() % 16:
+                raise ValueError(f"{what} group {i}: {name} needs a row stride that is a multiple of 8 and a 16-byte-aligned base (stride {t.stride(0)})")
+        W2, b = d["W2"], d["bias"]
+        if W2.shape[0] < Cp or W2.shape[0] % Cp:
+            raise ValueError(f"{what} group {i}: W2 has {W2.shape[0]} rows, not a multiple of Cp = {Cp}")
+        if b.dtype != torch.float32 or b.dim() != 1 or b.shape[0] != W2.shape[0] or not b.is_contiguous() or b.device != dev or b.data_ptr() % 16:
+            raise ValueError(f"{what} group {i}: bias must be a contiguous, 16-byte-aligned float32 [{W2.shape[0]}] on {dev}, got {tuple(b.shape)} {b.dtype}")
+        n_fields += W2.shape[0] // Cp
+    B = M // (n_patches * members)
+    for name, t in (("obs", obs), ("prec", prec)):
+        if t is None and name == "prec":
+            continue
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or t.dim() != 3 or tuple(t.shape[:2]) != (B * n_patches, n_fields) or t.shape[2] < C_ or t.stride(2) != 1 \
+                or t.device != dev or t.stride(1) < C_ or (t.shape[0] > 1 and t.stride(0) < 0):
+            raise ValueError(f"{what}: {name} must be a float32 [{B * n_patches}, {n_fields}, >= {C_}] tensor with unit inner stride on {dev}, got "
+                             f"{(tuple(t.shape), t.dtype, t.stride(), str(t.device)) if torch.is_tensor(t) else type(t).__name__}")
+    if prec_field is not None and (not torch.is_tensor(prec_field) or prec_field.dtype != torch.float32 or tuple(prec_field.shape) != (n_fields,)
+                                   or not prec_field.is_contiguous() or prec_field.device != dev):
+        raise ValueError(f"{what}: prec_field must be None or a contiguous float32 [{n_fields}] tensor on {dev}")
+    if counts is not None and (counts.dtype != torch.int32 or counts.dim() != 1 or counts.shape[0] != n_patches or not counts.is_contiguous() or counts.device != dev):
+        raise ValueError(f"{what}: counts must be a contiguous int32 [{n_patches}] on {dev}, got {tuple(counts.shape)} {counts.dtype} on {counts.device}")
+    if out is not None:
+        shapes = ((B, n_patches, members, members), (B, n_patches, members), (B, n_patches))
+        if not isinstance(out, (tuple, list)) or len(out) != 3 or any(
+                not torch.is_tensor(t) or t.dtype != dt_ or tuple(t.shape) != sh or not t.is_contiguous() or t.device != dev
+                for t, sh, dt_ in zip(out, shapes, (torch.float64, torch.float64, torch.int32))):
+            raise ValueError(f"{what}: out must be contiguous (float64 {shapes[0]}, float64 {shapes[1]}, int32 {shapes[2]}) tensors on {dev}")
+    N.require_gpu(groups[0]["H"], f"{what} hidden rows")   # every operand is on their device (checked above)
+    if out is not None:
+        gram, proj, count = out
+    else:
+        gram = torch.empty(B, n_patches, members, members, device=dev, dtype=torch.float64)
+        proj = torch.empty(B, n_patches, members, device=dev, dtype=torch.float64)
+        count = torch.empty(B, n_patches, device=dev, dtype=torch.int32)
+    arr, P = (N.SeaDecodeMseGroup * len(groups))(), N.SeaDecodeMemberGram()
+    fill_decode_member_gram(arr, P, groups, obs, prec_field, prec, counts, n_patches, members, C_, Cp, gram, proj, count)
+    N.check(N.lib().sea_decode_member_gram(arr, len(groups), C.byref(P), N.dtype_code(dtype), N.stream_ptr()), "sea_decode_member_gram")
+    return gram, proj, count
+
+
 def resample_systematic(logw: torch.Tensor, u: torch.Tensor, members: int, ess_frac: float = -1.0):
     """sea_resample_systematic: logw f32 [G * members] (device, contiguous), u f32 [G] in [0, 1), ess_frac < 0: always resample, else only the histories
     whose effective sample size is below ess_frac * members.  Returns (index int32 [G * members], logw_out f32 [G * members], ess f32 [G], resampled
@@ -1400,6 +1492,55 @@ def enkf_transform(pred: torch.Tensor, obs: torch.Tensor, members: int, prec: Op
     fill_enkf_transform(P, pred, obs, prec, taper, n, rho, alpha, D, status)
     P.ld_obs = max(P.ld_obs, K)   # one history: its row stride is never used and may say anything
     N.check(N.lib().sea_enkf_transform(C.byref(P), N.stream_ptr()), "sea_enkf_transform")
+    return D, status
+
+
+def fill_enkf_transform_gram(P: N.SeaEnkfTransformGram, gram, proj, count, taper, rho: float, alpha: float, D, status) -> None:
+    """The argument table of sea_enkf_transform_gram.  gram f64 [B, Q, members, members], proj f64 [B, Q, members], count int32 [B, Q], taper None / f32
+    [Ld, Q] (unit inner stride); D f32 [B, Ld, members, members] and status int32 [B, Ld], contiguous."""
+    P.gram, P.proj, P.count, P.taper, P.D, P.status = gram.data_ptr(), proj.data_ptr(), count.data_ptr(), N.ptr(taper), D.data_ptr(), status.data_ptr()
+    P.ld_taper = 0 if taper is None else taper.stride(0)
+    P.rho, P.alpha = rho, alpha
+    P.B, P.N, P.Q, P.Ld = gram.shape[0], gram.shape[2], gram.shape[1], D.shape[1]
+
+
+def enkf_transform_gram(gram: torch.Tensor, proj: torch.Tensor, count: torch.Tensor, taper: Optional[torch.Tensor] = None, rho: float = 1.0, alpha: float = 0.5,
+                        out: Optional[torch.Tensor] = None):
+    """sea_enkf_transform_gram: the ensemble-space matrix of the deterministic ensemble Kalman analysis from Q partial Gram matrices per history
+    (decode_member_gram's outputs; include/sea_hip.h states the formulas).  gram f64 [B, Q, n, n], proj f64 [B, Q, n], count int32 [B, Q], contiguous;
+    taper None (one domain: every partial with weight 1) or f32 [Ld, Q]; rho >= 1 the inflation, alpha in [0, 1] the anomaly gain.  Returns (D f32 [B, Ld,
+    n, n], status int32 [B, Ld]: the live cells of the problem, or -1 with D = 0) on the device; nothing is read back.  out: a D to write into."""
+    what = "enkf_transform_gram"
+    if not torch.is_tensor(gram) or gram.dim() != 4 or gram.dtype != torch.float64 or not gram.is_contiguous() or gram.shape[2] != gram.shape[3] or gram.shape[0] < 1 \
+            or gram.shape[1] < 1:
+        raise ValueError(f"{what}: gram must be a contiguous float64 [B, Q, members, members] tensor, got "
+                         f"{(tuple(gram.shape), gram.dtype) if torch.is_tensor(gram) else type(gram).__name__}")
+    B, Q, n, _ = gram.shape
+    dev = gram.device
+    if n < 2 or n > N.ENKF_MAX_N:
+        raise ValueError(f"{what}: members = {n} outside 2 .. {N.ENKF_MAX_N}")
+    if not torch.is_tensor(proj) or proj.dtype != torch.float64 or tuple(proj.shape) != (B, Q, n) or not proj.is_contiguous() or proj.device != dev:
+        raise ValueError(f"{what}: proj must be a contiguous float64 [{B}, {Q}, {n}] tensor on {dev}")
+    if not torch.is_tensor(count) or count.dtype != torch.int32 or tuple(count.shape) != (B, Q) or not count.is_contiguous() or count.device != dev:
+        raise ValueError(f"{what}: count must be a contiguous int32 [{B}, {Q}] tensor on {dev}")
+    if taper is not None and (not torch.is_tensor(taper) or taper.dtype != torch.float32 or taper.dim() != 2 or taper.shape[0] < 1 or taper.shape[1] != Q
+                              or not taper.is_contiguous() or taper.device != dev):
+        raise ValueError(f"{what}: taper must be None or a contiguous float32 [Ld, {Q}] tensor on {dev}, got "
+                         f"{(tuple(taper.shape), taper.dtype, str(taper.device)) if torch.is_tensor(taper) else type(taper).__name__}")
+    rho, alpha = float(rho), float(alpha)
+    if not (1.0 <= rho < float("inf")) or not (0.0 <= alpha <= 1.0):
+        raise ValueError(f"{what}: need a finite inflation rho >= 1 and an anomaly gain alpha in [0, 1], got rho = {rho}, alpha = {alpha}")
+    Ld = 1 if taper is None else taper.shape[0]
+    if B > 65535:
+        raise ValueError(f"{what}: {B} histories; a launch carries up to 65535")
+    if out is not None and (not torch.is_tensor(out) or out.dtype != torch.float32 or tuple(out.shape) != (B, Ld, n, n) or not out.is_contiguous() or out.device != dev):
+        raise ValueError(f"{what}: out must be a contiguous float32 [{B}, {Ld}, {n}, {n}] tensor on {dev}")
+    N.require_gpu(gram, f"{what} gram")   # every operand is on its device (checked above)
+    D = torch.empty(B, Ld, n, n, device=dev, dtype=torch.float32) if out is None else out
+    status = torch.empty(B, Ld, device=dev, dtype=torch.int32)
+    P = N.SeaEnkfTransformGram()
+    fill_enkf_transform_gram(P, gram, proj, count, taper, rho, alpha, D, status)
+    N.check(N.lib().sea_enkf_transform_gram(C.byref(P), N.stream_ptr()), "sea_enkf_transform_gram")
     return D, status
 
 

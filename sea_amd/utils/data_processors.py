@@ -152,15 +152,31 @@ class MeshUnpatcher:
         if not isinstance(sensors, SensorSet) or sensors.points is None:
             raise ValueError("sensor_taper: need a SensorSet built by sensor_set (it carries the sensors' mesh points)")
         part = self.partitioner
-        idx = part.padded_index_map.long()
-        if sensors.n_patches != idx.shape[0] or max(sensors.points) >= part.full_coords.shape[0]:
-            raise ValueError(f"sensor_taper: the SensorSet was built for another mesh ({sensors.n_patches} patches; this one has {idx.shape[0]})")
-        valid = (idx != part.pad_id).to(part.full_coords.dtype)                                  # [P, C]
-        cnt = valid.sum(1, keepdim=True)
-        centroid = (part.full_coords[idx.clamp_min(0)] * valid[..., None]).sum(1) / cnt.clamp_min(1.0)   # [P, 2]
+        if sensors.n_patches != part.padded_index_map.shape[0] or max(sensors.points) >= part.full_coords.shape[0]:
+            raise ValueError(f"sensor_taper: the SensorSet was built for another mesh ({sensors.n_patches} patches; this one has {part.padded_index_map.shape[0]})")
+        centroid, cnt = self._patch_centroids()
         where = part.full_coords[torch.tensor(sensors.points, device=part.full_coords.device)]   # [K, 2]
         dist = (centroid[:, None, :] - where[None, :, :]).square().sum(-1).sqrt()
         return (gaspari_cohn(dist, radius) * (cnt > 0)).to(torch.float32).contiguous()
+
+    def _patch_centroids(self):
+        """(centroid [P, 2], cnt [P, 1]): the mean of the partitioner's full_coords over every patch's valid slots, and how many there are."""
+        part = self.partitioner
+        idx = part.padded_index_map.long()
+        valid = (idx != part.pad_id).to(part.full_coords.dtype)                                  # [P, C]
+        cnt = valid.sum(1, keepdim=True)
+        centroid = (part.full_coords[idx.clamp_min(0)] * valid[..., None]).sum(1) / cnt.clamp_min(1.0)   # [P, 2]
+        return centroid, cnt
+
+    def patch_taper(self, radius) -> torch.Tensor:
+        """Localisation weights for FieldKalman(taper=...): float32 [P, P] on the partitioner's device, gaspari_cohn(distance, radius) between the
+        centroids of patch p (the analysis domain: row) and patch q (whose cells are observed: column) — the centroids of sensor_taper.  A patch
+        without a mesh point gets weight 0 in its row and its column."""
+        from ..ensemble import gaspari_cohn
+
+        centroid, cnt = self._patch_centroids()
+        dist = (centroid[:, None, :] - centroid[None, :, :]).square().sum(-1).sqrt()
+        return (gaspari_cohn(dist, radius) * (cnt > 0) * (cnt > 0).view(1, -1)).to(torch.float32).contiguous()
 
     def patchify_and_scale(self, data: torch.Tensor, layout: str = "BPCF", c_out: Optional[int] = None) -> torch.Tensor:
         """The forward leg (reference MeshProcessor.patchify_and_scale, utils/data_processors.py:484-526, with fitted scalers): data [T, N, F] ->
@@ -310,6 +326,12 @@ class MeshProcessor:
         if self._unpatcher is None:
             raise ValueError("call patchify_and_scale first (it builds the partition)")
         return self._unpatcher.sensor_taper(sensors, radius)
+
+    def patch_taper(self, radius) -> torch.Tensor:
+        """Gaspari-Cohn localisation weights [P, P] between the patches' centroids, for FieldKalman(taper=...) (MeshUnpatcher.patch_taper)."""
+        if self._unpatcher is None:
+            raise ValueError("call patchify_and_scale first (it builds the partition)")
+        return self._unpatcher.patch_taper(radius)
 
     def decode_and_unpatch(self, decoder, z: torch.Tensor) -> torch.Tensor:
         """decoder(z) + inverse_scale_and_unpatch(..., layout="BPFC") in one go, the decoder run only over a cell's mesh points (MeshUnpatcher.decode_and_unpatch):
