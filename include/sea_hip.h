@@ -46,7 +46,12 @@ const char* sea_last_error(void);
  * "gemm_norm.rows16_dma", "gemm_norm.rows64"), sea_attention_fwd ("attn.row", "attn.split4", "attn.split2", "attn.split1"; a = 1 if paired),
  * sea_attention_bwd ("attn_bwd" at head dims 8 / 16 / 32 / 64 / 128 / 256, "attn_bwd.masked" at the other widths; a = the mode bits of the dQ kernel,
  * b = those of the dK / dV kernel: 1 XCD-local order, 2 paired tiles) and sea_wgrad_grouped ("wgrad.tile64", "wgrad.tile128", "wgrad.tile256"; a = the
- * largest split count over the groups, b = 1 if any group takes the plain store).  Host only.  (An addition to ABI version 8; no new struct.) */
+ * largest split count over the groups, b = 1 if any group takes the plain store), and by the row-owning launches: sea_mlp_fc1_ln_gelu / sea_mlp_fc2_proj_norm /
+ * sea_mlp_block ("mlp_fc1.rows32", "mlp_fc2.rows32", "mlp_block.rows32"; a = per_xcd of the XCD-local tile order, 0 in the plain order, b = workgroups launched),
+ * sea_gemm_adaln ("gemm_adaln.rows64", "gemm_adaln.rows128"; a = tiles), sea_exchange_tail ("xtail.rows16"; a = row tiles per group, b = segments),
+ * sea_row_chain / sea_row_chain_riders ("chain.rows16", "chain.rows32"; a = rider tiles run in this launch, b = information-bottleneck workgroups) and
+ * sea_adaln_qkv ("adaln_qkv.rows32", "adaln_qkv.rows32_mod3" with the third layer; a = rider tiles, b = row-rider workgroups).  Host only.  (An addition to
+ * ABI version 8; no new struct.) */
 const char* sea_last_form(int* a, int* b);
 /* sizeof of every ABI struct in declaration order (SeaGemmGroup, SeaQkvGroup, SeaQkvCommon, SeaAttnProblem,
  * SeaAttnParams, SeaNormGroup, SeaSiluGroup, SeaIbParams, ..., SeaLaunchRec, SeaGemmNormGroup, SeaExchangeTail, SeaMlpGroup, SeaMlp2Group, SeaKvNorm, SeaKvField, SeaKvPair, SeaKvLayer, SeaKvGlobal, SeaStepPatch, SeaRowChain, SeaAdalnGroup, SeaAdalnQkv, SeaSplitkGroup, SeaEncBlock, SeaKvFill, SeaKvFork last): lets a binding verify its layout.  Host only. */

@@ -773,5 +773,6 @@ extern "C" int sea_adaln_qkv(const SeaAdalnQkv* groups, int n_groups, const SeaQ
         adaln_qkv_kernel<false><<<grid, dim3(512), lds, static_cast<hipStream_t>(stream)>>>(L);
     }
     SEA_CHECK_LAUNCH("sea_adaln_qkv");
+    sea_note_form(has3 ? "adaln_qkv.rows32_mod3" : "adaln_qkv.rows32", rider_total, L.silu_wgs + L.ib_wgs);   // a: rider tiles; b: row-rider workgroups (silu + info-bottleneck)
     return SEA_OK;
 }

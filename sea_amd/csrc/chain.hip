@@ -750,5 +750,6 @@ static int row_chain_launch(const SeaRowChain* params, int n_groups, const SeaQk
     else { if (mi == 1) LAUNCH_CH(64, 128, 1); else LAUNCH_CH(64, 128, 2); }
 #undef LAUNCH_CH
     SEA_CHECK_LAUNCH("sea_row_chain");
+    sea_note_form(mi == 1 ? "chain.rows16" : "chain.rows32", L.rider_n, L.ib_wgs);   // a / b: rider tiles run in this launch, info-bottleneck workgroups
     return SEA_OK;
 }

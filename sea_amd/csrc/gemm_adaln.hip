@@ -234,5 +234,6 @@ extern "C" int sea_gemm_adaln(const SeaAdalnGroup* groups, int n_groups, float e
         gemm_adaln_kernel<__bf16, 64><<<dim3(total), dim3(256), lds, static_cast<hipStream_t>(stream)>>>(L);
     }
     SEA_CHECK_LAUNCH("sea_gemm_adaln");
+    sea_note_form(bm == 128 ? "gemm_adaln.rows128" : "gemm_adaln.rows64", total, 0);   // a: tiles launched
     return SEA_OK;
 }

@@ -554,5 +554,6 @@ extern "C" int sea_exchange_tail(const SeaExchangeTail* params, int n_groups, fl
     if (D == 128) LAUNCH_XT(128, 256); else LAUNCH_XT(64, 128);
 #undef LAUNCH_XT
     SEA_CHECK_LAUNCH("sea_exchange_tail");
+    sea_note_form("xtail.rows16", (int)grid.x, S0);   // a: row tiles per group; b: segments
     return SEA_OK;
 }

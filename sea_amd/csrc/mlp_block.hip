@@ -683,5 +683,6 @@ extern "C" int sea_mlp_block(const SeaMlpGroup* g1, const SeaMlp2Group* g2, int 
         mlp_block_kernel<2, 8><<<dim3(total), dim3(512), lds, s>>>(L);
     }
     SEA_CHECK_LAUNCH("sea_mlp_block");
+    sea_note_form("mlp_block.rows32", L.per_xcd, total);   // a: per_xcd (0: the plain tile order); b: workgroups launched
     return SEA_OK;
 }

@@ -606,6 +606,7 @@ extern "C" int sea_mlp_fc1_ln_gelu(const SeaMlpGroup* groups, int n_groups, floa
         mlp_fc1_ln_gelu_kernel<2, 8><<<dim3(total), dim3(512), lds0, s>>>(L);
     }
     SEA_CHECK_LAUNCH("sea_mlp_fc1_ln_gelu");
+    sea_note_form("mlp_fc1.rows32", L.per_xcd, total);   // a: per_xcd (0: the plain tile order); b: workgroups launched
     return SEA_OK;
 }
 
@@ -655,5 +656,6 @@ extern "C" int sea_mlp_fc2_proj_norm(const SeaMlp2Group* groups, int n_groups, f
         mlp_fc2_proj_norm_kernel<2, 16><<<dim3(total), dim3(512), lds, s>>>(L);
     }
     SEA_CHECK_LAUNCH("sea_mlp_fc2_proj_norm");
+    sea_note_form("mlp_fc2.rows32", L.per_xcd, total);   // a: per_xcd (0: the plain tile order); b: workgroups launched
     return SEA_OK;
 }

@@ -79,7 +79,8 @@ def gemm_grouped(groups: Sequence[Dict], dtype: torch.dtype) -> None:
 
 def last_form():
     """(form, a, b) of the calling thread's last noted launch — which kernel sea_gemm_grouped / sea_gemm_rownorm / sea_attention_fwd / sea_attention_bwd /
-    sea_wgrad_grouped took (include/sea_hip.h, sea_last_form); ("", 0, 0) before any.  For the tests that force a form."""
+    sea_wgrad_grouped and the row-owning launches (MLP, sea_gemm_adaln, sea_exchange_tail, sea_row_chain, sea_adaln_qkv) took (include/sea_hip.h, sea_last_form);
+    ("", 0, 0) before any.  For the tests that force a form."""
     a, b = C.c_int(0), C.c_int(0)
     name = N.lib().sea_last_form(C.byref(a), C.byref(b))
     return (name.decode() if name else ""), a.value, b.value
@@ -354,9 +355,10 @@ def fill_adaln_qkv(g: N.SeaAdalnQkv, X, cond, w1, b1, W2c, b2c, gamma, beta, Wqk
 
 
 def adaln_qkv(groups: Sequence[Dict], rope: torch.Tensor, H: int, hd: int, T: int, pos0: int, cap: int, q_scale: float, riders: Sequence[Dict] = (), silu: Sequence[Dict] = (),
-              silu_c: Optional[torch.Tensor] = None, eps: float = 1e-5, dtype: torch.dtype = torch.bfloat16) -> None:
+              silu_c: Optional[torch.Tensor] = None, eps: float = 1e-5, dtype: torch.dtype = torch.bfloat16, ib: Optional[Dict] = None) -> None:
     """sea_adaln_qkv: the front of a block in one launch (dict keys: the arguments of fill_adaln_qkv); `riders`: plain GEMM groups (A, W, bias, Cact) as sea_gemm_grouped's;
-    `silu`: row riders as sea_silu_outer's groups (w1, b1, Hid) evaluated on silu_c."""
+    `silu`: row riders as sea_silu_outer's groups (w1, b1, Hid) evaluated on silu_c; `ib`: the information-bottleneck row rider (the arguments of fill_ib_params: its
+    rows xs[0] are stored, evaluated on silu_c too)."""
     arr = (N.SeaAdalnQkv * len(groups))()
     for g, d in zip(arr, groups):
         fill_adaln_qkv(g, **d)
@@ -372,8 +374,13 @@ def adaln_qkv(groups: Sequence[Dict], rope: torch.Tensor, H: int, hd: int, T: in
         sarr = (N.SeaSiluGroup * len(silu))()
         for g, gd in zip(sarr, silu):
             fill_silu_group(g, gd["w1"], gd["b1"], gd["Hid"])
+    ibp = None
+    if ib is not None:
+        ibp = N.SeaIbParams()
+        fill_ib_params(ibp, **ib)
     N.check(N.lib().sea_adaln_qkv(arr, len(groups), C.byref(c), rarr, len(riders), sarr, len(silu), (silu_c.data_ptr() if silu_c is not None else None),
-                                  (silu_c.numel() if silu_c is not None else 0), None, eps, N.dtype_code(dtype), N.stream_ptr()), "sea_adaln_qkv")
+                                  (silu_c.numel() if silu_c is not None else 0), (C.byref(ibp) if ibp is not None else None), eps, N.dtype_code(dtype), N.stream_ptr()),
+            "sea_adaln_qkv")
 
 
 def row_chain_supported(dtype: torch.dtype, D: int, E: int, n_seg: int, hd: int) -> bool:
@@ -422,13 +429,34 @@ def fill_row_chain(P: N.SeaRowChain, W2, Xin, X, att: Sequence[torch.Tensor] = (
 
 
 def row_chain(groups: Sequence[Dict], rope: Optional[torch.Tensor] = None, H: int = 1, hd: int = 4, T: int = 1, pos0: int = 0, cap: int = 0, q_scale_: float = 1.0,
-              eps: float = 1e-5, dtype: torch.dtype = torch.bfloat16) -> None:
-    """sea_row_chain: the row-local chain between two attention launches for up to three groups (fields) of one shape (dict keys: the arguments of fill_row_chain)."""
+              eps: float = 1e-5, dtype: torch.dtype = torch.bfloat16, riders: Optional[Sequence[Dict]] = None, tile0: Optional[int] = None, n_tiles: Optional[int] = None,
+              ib: Optional[Dict] = None) -> None:
+    """sea_row_chain: the row-local chain between two attention launches for up to three groups (fields) of one shape (dict keys: the arguments of fill_row_chain).
+    With any of riders / tile0 / n_tiles / ib: sea_row_chain_riders — `riders`: plain GEMM groups (the arguments of fill_gemm_group: A, W, bias, Cact) cut into
+    128 x 128 tiles numbered group by group, of which this launch runs [tile0, tile0 + n_tiles) (all of them unless given); `ib`: the information-bottleneck
+    rows (the arguments of fill_ib_params: xs[0] is stored)."""
     P = (N.SeaRowChain * len(groups))()
     for p_, d in zip(P, groups):
         fill_row_chain(p_, **d)
     common = N.SeaQkvCommon(N.ptr(rope), H, hd, T, pos0, cap, q_scale_) if rope is not None else None
-    N.check(N.lib().sea_row_chain(P, len(groups), C.byref(common) if common is not None else None, eps, N.dtype_code(dtype), N.stream_ptr()), "sea_row_chain")
+    cref = C.byref(common) if common is not None else None
+    if riders is None and tile0 is None and n_tiles is None and ib is None:
+        N.check(N.lib().sea_row_chain(P, len(groups), cref, eps, N.dtype_code(dtype), N.stream_ptr()), "sea_row_chain")
+        return
+    riders = list(riders or ())
+    rarr = (N.SeaGemmGroup * len(riders))() if riders else None
+    total = 0
+    for g, d in zip(rarr or (), riders):
+        fill_gemm_group(g, **d)
+        total += ((g.M + 127) // 128) * ((g.N + 127) // 128)
+    tile0 = 0 if tile0 is None else tile0
+    n_tiles = total - tile0 if n_tiles is None else n_tiles
+    ibp = None
+    if ib is not None:
+        ibp = N.SeaIbParams()
+        fill_ib_params(ibp, **ib)
+    N.check(N.lib().sea_row_chain_riders(P, len(groups), cref, rarr, len(riders), tile0, n_tiles, (C.byref(ibp) if ibp is not None else None), eps, N.dtype_code(dtype),
+                                         N.stream_ptr()), "sea_row_chain_riders")
 
 
 def fill_silu_group(g: N.SeaSiluGroup, w1, b1, Hid) -> None:
