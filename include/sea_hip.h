@@ -1399,6 +1399,61 @@ typedef struct {
 int64_t sea_ensemble_verify_ws_bytes(int B, int N, int K);   /* -1 for sizes the entry point refuses */
 int sea_ensemble_verify(const SeaEnsembleVerify* p, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Verification of an ensemble against a DENSE observation of the decoded fields, in two launches: sea_ensemble_verify's scores with every cell of
+ * the mesh a reading, without the members' decoded fields or a prediction matrix ever existing in memory.  Operands H, W2, bias, ldh, ldw,
+ * n_fields, field0 of SeaDecodeMseGroup, and obs, prec_field, prec, counts with their strides, exactly as in sea_decode_member_gram; row
+ * m = (b * members + j) * P + p of H is member j of history b; B = M / (P * members); N = members; F = n_fields_total.  Per history b and patch p:
+ *     y_j[f, c] = sum_s H[m, s] W2[(f - field0) Cp + c, s] + bias[(f - field0) Cp + c]                       (fp32 accumulation; never stored)
+ *     w[f, c]   = valid(p, c) ? (pf[f] > 0 ? pf[f] : 0) * (prec != NULL ? (prec[b, p, f, c] > 0 ? prec[b, p, f, c] : 0) : 1) : 0    (an fp32 product)
+ *                 selects: a NaN counts as 0; pf = prec_field (NULL: 1); valid(p, c) = c < counts[p] (clamped to [0, C]; NULL: c < C)
+ * The history's weights, status[b] and c come from logw and unbiased as in sea_ensemble_verify.  A cell with w > 0 is a live reading with
+ * x_j = y_j[f, c] (compared as the f32 values they are), y = obs[b, p, f, c] and precision w; mean, spread, crps, pit and rank are
+ * sea_ensemble_verify's, evaluated by the same device code in fp64.  A cell without weight is DEAD: the four floats 0, rank -1, and obs is not read
+ * there.  A live cell whose y, w or a live member's value is not finite is BAD: the four floats NaN, rank -2.  A history whose log-weights are
+ * invalid (status -1) has all its maps 0, its ranks -1, and adds nothing to sums and hist.
+ *     mean, spread, crps, pit f32 and rank int32 [B, P, F, ld_out]: each may be NULL; EVERY element of the others is written, the columns from C
+ *                             (and from counts[p]) up to ld_out as dead cells
+ *     sums[b, f, 0..7]        sea_ensemble_verify's eight sums over the live, good cells of field f of history b, patches ascending, columns
+ *                             ascending inside a patch, from the fp64 per-cell values before any rounding (entry 3 adds spread^2)          (f64 [B, F, 8])
+ *     hist[b, f, r]           the number of those cells with rank r, r = 0 .. N                                                            (int64 [B, F, N + 1])
+ *     status[b]               the number of live members, or -1                                                                            (int32 [B])
+ * accumulate = 1 adds a call's sums and hist onto the existing ones; 0 overwrites them.  status is always overwritten.
+ * Launch 1: a workgroup of 8 waves per (history, patch, field, chunk of 512 columns) decodes 32 columns of its field at a time as
+ * sea_decode_member_gram does, stages the values in LDS as [column][member], a wave scores a column at a time with a member (two above 64) per lane,
+ * thread k stores column k, and the workgroup's partial sums (columns ascending) and partial histogram (integer LDS adds) go to `work`.  Launch 2: a
+ * workgroup per history adds the partials in ascending (patch, chunk) order.  No floating-point atomics: two runs give the same bits; a history's outputs are those of a call holding it alone; a
+ * cell's own outputs do not depend on the other cells of its patch.
+ * Requirements: dtype SEA_BF16 (SEA_F32: SEA_EUNSUPPORTED); M >= 1; S a multiple of 8, at most 640 (above: SEA_EUNSUPPORTED), padded by masking; Cp a
+ * multiple of 32, 1 <= C <= Cp; P >= 1; members >= 1 (above 128: SEA_EUNSUPPORTED); M % (P * members) == 0; at most 65535 histories and fields; ld_field,
+ * ld_pfield >= C, and ld_out >= C when a map is given; f32 and int32 buffers 4-byte, sums, hist and work 8-byte aligned; unbiased and accumulate 0 or
+ * 1; work_bytes >= sea_decode_member_verify_ws_bytes(B, P, F, members, Cp); per group H, W2, bias non-NULL and 16-byte aligned, ldh, ldw multiples of 8
+ * and >= S; the groups' field ranges cover 0 .. F-1 exactly once; 1 <= n_groups <= SEA_DECODE_MSE_MAX_GROUPS.  Returns -1, with the entry point and
+ * the offending group named in sea_last_error(), otherwise; nothing touches a device before the checks pass.
+ * Notes the form "decode.member_verify" (a = the padded hidden width, b = the dynamic LDS bytes).
+ * (An addition to ABI version 8.  The struct is not in sea_struct_sizes(): sizeof(SeaDecodeMemberVerify) is 200.)
+ */
+typedef struct {
+    const float* obs;          /* f32, rows of the observation: [B * P, F, >= C] through ld_row, ld_field */
+    const float* prec_field;   /* f32 [F], or NULL (1) */
+    const float* prec;         /* f32 map in obs's layout through ld_prow, ld_pfield, or NULL (1) */
+    const int32_t* counts;     /* device int32 [P] or NULL */
+    const float* logw;         /* NULL (equal weights) or f32 [B N], unnormalised */
+    float* mean;               /* f32 [B, P, F, ld_out] or NULL */
+    float* spread;
+    float* crps;
+    float* pit;
+    int32_t* rank;             /* int32 [B, P, F, ld_out] or NULL */
+    double* sums;              /* f64 [B, F, 8] */
+    int64_t* hist;             /* int64 [B, F, N + 1] */
+    int32_t* status;           /* int32 [B] */
+    void* work;                /* work_bytes bytes */
+    int64_t ld_row, ld_field, ld_prow, ld_pfield, ld_out, work_bytes;
+    int32_t M, S, C, Cp, P, members, n_fields_total, unbiased, accumulate, pad_;
+} SeaDecodeMemberVerify;     /* 200 bytes */
+int64_t sea_decode_member_verify_ws_bytes(int B, int P, int n_fields_total, int members, int Cp);   /* -1 for sizes the entry point refuses */
+int sea_decode_member_verify(const SeaDecodeMseGroup* groups, int n_groups, const SeaDecodeMemberVerify* p, int dtype, void* stream);
+
 /* Tuning aid: register a device buffer of n_steps * 64 8-byte words that the persistent form fills with 100 MHz clock stamps of its hand-offs
  * (tools/kv_persist_timeline.py); NULL switches it off. */
 void sea_kv_debug_stamps(unsigned long long* buf);

@@ -35,6 +35,7 @@
 // (256 B / clk) is busy about as long as the matrix cores, so the launch sits near half the bf16 MFMA rate at best, and the 64-row block leaves one
 // wave per SIMD (DESIGN.md section 7 has the measurements).
 #include "sea_common.hpp"
+#include "verify_score.hpp"   // sea_decode_member_verify scores a cell as verify_kernel scores a sensor
 
 typedef short dm_s16x4 __attribute__((ext_vector_type(4)));
 
@@ -1724,5 +1725,379 @@ extern "C" int sea_decode_member_gram(const SeaDecodeMseGroup* groups, int n_gro
     else if (P.S <= 512) member_gram_launch<512>(L, grid, s);
     else member_gram_launch<640>(L, grid, s);
     SEA_CHECK_LAUNCH("sea_decode_member_gram");
+    return SEA_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------------------------
+// sea_decode_member_verify: verification of an ensemble against a DENSE observation of the decoded fields — per cell the ensemble mean, spread, CRPS,
+// PIT and rank, per (history, field) the fp64 sums and the rank histogram (include/sea_hip.h states the formulas; they are sea_ensemble_verify's with a
+// cell for a sensor).  Launch 1 has decode_member_gram_kernel's walk, with one workgroup of 8 waves per (history, patch, FIELD, chunk of MV_CHUNK
+// tiles of the field) — grid.y is the field, grid.z the chunk: the sums are per field anyway, scoring and not decoding sets the time, and at one
+// history a workgroup per (history, patch) would leave three quarters of the chip idle behind a chain of n_fields * tiles scoring steps whose length
+// the fullest patch sets.  A chunk without a valid column leaves at once.  Wave w decodes the members 16 w .. 16 w + 15 tile by tile (32 columns
+// of the field).  Per tile:
+//   a  threads 0 .. 31 form the columns' weights (decode_member_gram_kernel's selects) and read obs where the weight is positive; the waves decode and
+//      write their values to an LDS image V[column][member] with a row of 129 floats (an odd stride: the lane-per-member reads of b are conflict-free
+//      and the walk's reads are broadcasts; the stores of a, four rows apart per lane group, pay a two-way conflict once per tile);
+//   b  wave w scores the columns w, w + 8, w + 16, w + 24 with vf_score_wave (verify_score.hpp: the arithmetic verify_kernel runs per sensor, in fp64,
+//      members compared as the f32 values they are); a dead column is passed over by its wave;
+//   c  thread k finishes column k (vf_finish_reading), stores the five maps — one writer per element, 128-byte segments — files the column's eight
+//      terms and counts its rank in the field's LDS histogram (integer adds); the next tile of W2 goes to its LDS image meanwhile;
+//   d  threads 0 .. 7 add the tile's terms in ascending column order onto the field's running fp64 sums; after the last tile the sums and the
+//      histogram go to `work` [(history, patch), chunk, field].
+// Three barriers per tile.  Columns at or beyond the walked tiles (whole tiles of invalid or pad columns) are filled as dead before the walk.
+// member_verify_finish_kernel: one workgroup per history adds the partials of each field in ascending (patch, chunk) order.
+// No floating-point atomics anywhere, no exchange between workgroups: two runs give the same bits, a history's outputs are those of a call holding it
+// alone, and a cell's own outputs depend on its column of V, its weight and its reading only.
+struct MemberVerifyLaunch {
+    SeaDecodeMseGroup g[SEA_DECODE_MSE_MAX_GROUPS];
+    SeaDecodeMemberVerify p;
+    int n_groups;
+    int words;   // 8-byte words per (history, patch, field) of the workspace
+};
+
+constexpr int MV_NW = 8;               // waves per workgroup: 128 members
+constexpr int MV_NT = 64 * MV_NW;
+constexpr int MV_VP = VF_MAX_N + 1;    // floats per column of the value image
+constexpr int MV_CHUNK = 16;           // tiles (of 32 columns) of a field that one workgroup scores
+
+static inline int mv_chunks(int Cp) { return (Cp / DM_TC + MV_CHUNK - 1) / MV_CHUNK; }
+
+static inline int64_t mv_words(int N) { return VF_SUMS + (N + 2) / 2; }   // 8 sums, then N + 1 int32 bins
+
+// LDS at SP = 640: 2 x 41984 (W2 images) + 16512 (V) dynamic, 6.6 kB static (weights, readings, terms, histogram): 107 kB of the CU's 160 kB
+template <int SP>
+constexpr int mv_lds_bytes() { return 2 * DM_TC * (SP * 2 + DM_PAD) + DM_TC * MV_VP * 4; }
+
+template <int SP, int V>
+__global__ __launch_bounds__(MV_NT) void decode_member_verify_kernel(const MemberVerifyLaunch L) {
+#pragma clang fp reassociate(off)
+    constexpr int NW = MV_NW;
+    constexpr int NT = MV_NT;
+    constexpr int KS = SP / 32;
+    constexpr int PITCH = SP * 2 + DM_PAD;
+    constexpr int TILE = DM_TC * PITCH;
+    constexpr int NCH = SP * 4 / NT;
+    constexpr int VP = MV_VP;
+    static_assert(NCH * NT == DM_TC * (SP / 8), "whole chunks per thread");
+    extern __shared__ __attribute__((aligned(16))) char smem[];   // 2 tile images; the value image [32][VP]
+    float* Vs = reinterpret_cast<float*>(smem + 2 * TILE);
+    __shared__ double lw_s[VF_MAX_N], w_s[VF_MAX_N];
+    __shared__ int live_s[VF_MAX_N];
+    __shared__ VfReading r_s[DM_TC];
+    __shared__ double term_s[VF_SUMS][DM_TC];
+    __shared__ int hist_s[VF_MAX_N + 1];
+    __shared__ float y_s[DM_TC], pv_s[DM_TC];
+
+    const SeaDecodeMemberVerify& P = L.p;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), li = lane & 15, lg = lane >> 4;
+    const int S = P.S, C = P.C, Cp = P.Cp, N = P.members, F = P.n_fields_total, words = L.words;
+    const int bp = blockIdx.x, fg = blockIdx.y, ck = blockIdx.z, Q = gridDim.z;   // the field and the chunk of its tiles this workgroup scores
+    const int b = bp / P.P, patch = bp - b * P.P;
+    const int64_t ld = P.ld_out;
+    const int64_t obase = ((int64_t)bp * F + fg) * ld;
+    double* const wsum = reinterpret_cast<double*>(P.work) + (((int64_t)bp * Q + ck) * F + fg) * words;
+    int32_t* const whist = reinterpret_cast<int32_t*>(wsum + VF_SUMS);
+
+    int lim = C;   // valid columns of this patch: [0, lim) — uniform over the workgroup
+    if (P.counts != nullptr) {
+        const int cnt = P.counts[patch];
+        lim = cnt < 0 ? 0 : (cnt > C ? C : cnt);
+    }
+    const int tpf = (lim + DM_TC - 1) / DM_TC;   // tiles of a field that hold valid columns
+    const int tb = ck * MV_CHUNK, te = tpf < tb + MV_CHUNK ? tpf : tb + MV_CHUNK;   // this workgroup's tiles: [tb, te)
+
+    // the weights of the history (verify_kernel's step 1)
+    int invalid = 0, alive = 0;
+    if (tid < N) {
+        const float lw = P.logw != nullptr ? P.logw[(int64_t)b * N + tid] : 0.f;
+        invalid = (lw != lw || lw == INFINITY) ? 1 : 0;
+        alive = (!invalid && lw != -INFINITY) ? 1 : 0;
+        lw_s[tid] = (double)lw;
+        live_s[tid] = alive;
+    }
+    for (int r = tid; r <= N; r += NT) hist_s[r] = 0;
+    const int n_live = __syncthreads_count(alive);
+    invalid = __syncthreads_or(invalid);
+    const bool unscored = invalid || n_live == 0;
+    if (patch == 0 && fg == 0 && ck == 0 && tid == 0) P.status[b] = unscored ? -1 : n_live;
+    if (ck == 0) {   // the columns no tile walks (all of them when the history is not scored or the patch has no valid column): dead
+        const int c0 = (unscored || tpf == 0) ? 0 : tpf * DM_TC;
+        for (int64_t c = c0 + tid; c < ld; c += NT) {
+            const int64_t at = obase + c;
+            if (P.mean != nullptr) P.mean[at] = 0.f;
+            if (P.spread != nullptr) P.spread[at] = 0.f;
+            if (P.crps != nullptr) P.crps[at] = 0.f;
+            if (P.pit != nullptr) P.pit[at] = 0.f;
+            if (P.rank != nullptr) P.rank[at] = -1;
+        }
+    }
+    if (unscored || te <= tb) {   // uniform: nothing to score in this chunk
+        for (int e = tid; e < words; e += NT) wsum[e] = 0.0;   // the sums, and the int32 bins: all bits zero
+        return;
+    }
+    double mx = -INFINITY;
+    for (int j = 0; j < N; ++j) mx = lw_s[j] > mx ? lw_s[j] : mx;
+    if (tid < N) w_s[tid] = alive ? exp(lw_s[tid] - mx) : 0.0;
+    __syncthreads();
+    double W = 0.0;
+    for (int j = 0; j < N; ++j) W += w_s[j];
+    const double my_w = tid < N ? w_s[tid] / W : 0.0;
+    __syncthreads();   // every thread has read the exponentials
+    if (tid < N) w_s[tid] = my_w;
+    __syncthreads();
+    double q = 0.0;
+    for (int j = 0; j < N; ++j) q = fma(w_s[j], w_s[j], q);
+    const double cq = P.unbiased ? 1.0 - q : 1.0;
+
+    const int j0 = wave * 16;
+    const bool active = j0 < N;                 // uniform over the wave
+    const int jm = j0 + li;
+    const int64_t m = ((int64_t)b * N + (jm < N ? jm : 0)) * P.P + patch;
+    double acc_sum = 0.0;                       // threads 0 .. 7: the field's running sums
+
+    int gsel = 0;   // the group that holds the field: the entry point has checked that exactly one does
+    for (int gi = 1; gi < L.n_groups; ++gi) gsel = (fg >= L.g[gi].field0 && fg < L.g[gi].field0 + L.g[gi].n_fields) ? gi : gsel;
+    {
+        const SeaDecodeMseGroup& G = L.g[gsel];
+        const int j = fg - G.field0;   // the field inside its group
+        const __bf16* H = static_cast<const __bf16*>(G.H);
+        const __bf16* W2 = static_cast<const __bf16*>(G.W2);
+        uint4 hf[KS];
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+            const int s = ks * 32 + 8 * lg;
+            // a row at or beyond N repeats member 0's: its values are stored to V and never read.  The k-step that straddles S loads column 0 where
+            // s >= S and selects zeros (the tile image is zero there, but 0 * NaN is not)
+            if (ks * 32 + 32 <= S) {
+                hf[ks] = *reinterpret_cast<const uint4*>(H + m * G.ldh + s);
+            } else {
+                const uint4 v = *reinterpret_cast<const uint4*>(H + m * G.ldh + (s < S ? s : 0));
+                hf[ks] = s < S ? v : make_uint4(0u, 0u, 0u, 0u);
+            }
+        }
+        const int n_tiles = te - tb, t0 = j * tpf + tb;   // this chunk's tiles among the group's
+        uint4 wr[NCH];
+        dm_load_tile<SP, NT>(wr, W2, G.ldw, S, Cp, tpf, t0, tid);
+        dm_store_tile<SP, NT>(wr, smem, tid);
+        __syncthreads();
+
+        for (int t = 0; t < n_tiles; ++t) {
+            const char* buf = smem + (t & 1) * TILE;
+            const int cb = (tb + t) * DM_TC;
+
+            // a: the columns' weights and readings; decode into the value image
+            if (tid < DM_TC) {
+                const int c = cb + tid;
+                float w = 0.f;
+                if (c < lim) {
+                    const float pf = P.prec_field != nullptr ? P.prec_field[fg] : 1.f;
+                    const float pm = P.prec != nullptr ? P.prec[(int64_t)bp * P.ld_prow + (int64_t)fg * P.ld_pfield + c] : 1.f;
+                    w = mul1(pf > 0.f ? pf : 0.f, pm > 0.f ? pm : 0.f);
+                }
+                const bool on = w > 0.f;   // false for NaN
+                pv_s[tid] = on ? w : 0.f;
+                y_s[tid] = on ? P.obs[(int64_t)bp * P.ld_row + (int64_t)fg * P.ld_field + c] : 0.f;
+            }
+            if (active) {
+                f32x4 acc[2][2];
+#pragma unroll
+                for (int sub = 0; sub < 2; ++sub) {
+                    const float bv = G.bias[j * Cp + cb + sub * 16 + li];
+                    acc[sub][0] = f32x4{bv, bv, bv, bv};
+                    acc[sub][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+                }
+#pragma unroll
+                for (int ks = 0; ks < KS; ++ks) {
+                    if (ks * 32 < S) {
+#pragma unroll
+                        for (int sub = 0; sub < 2; ++sub) {
+                            const uint4 wv = *reinterpret_cast<const uint4*>(buf + (sub * 16 + li) * PITCH + (ks * 4 + lg) * 16);
+                            mma16<__bf16>(hf[ks], wv, acc[sub][ks & 1]);
+                        }
+                    }
+                }
+#pragma unroll
+                for (int sub = 0; sub < 2; ++sub) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)   // plain C++: the first reader of an MFMA result must be an instruction the compiler sees
+                        Vs[(sub * 16 + li) * VP + j0 + 4 * lg + r] = acc[sub][0][r] + acc[sub][1][r];
+                }
+            }
+            __syncthreads();
+            if (t + 1 < n_tiles) dm_load_tile<SP, NT>(wr, W2, G.ldw, S, Cp, tpf, t0 + t + 1, tid);   // in flight behind b
+
+            // b: a column per wave at a time
+            for (int cl = wave; cl < DM_TC; cl += NW) {
+                const float pv = pv_s[cl];
+                if (!(pv > 0.f)) {   // the same word in every lane
+                    if (lane == 0) r_s[cl].state = 1;
+                    continue;
+                }
+                const VfReading r = vf_score_wave<V>(Vs + cl * VP, w_s, live_s, N, lane, y_s[cl], pv);
+                if (lane == 0) r_s[cl] = r;
+            }
+            __syncthreads();
+
+            // c: thread k finishes column k
+            if (tid < DM_TC) {
+                double tm[VF_SUMS];
+                const VfReading r = r_s[tid];
+                const VfOut o = vf_finish_reading(r, y_s[tid], pv_s[tid], cq, tm);
+                if (r.state == 0) atomicAdd(&hist_s[o.rank], 1);   // LDS, integers: the order does not matter; 0 <= rank <= N
+                const int c = cb + tid;
+                if (c < ld) {
+                    const int64_t at = obase + c;
+                    if (P.mean != nullptr) P.mean[at] = o.mean;
+                    if (P.spread != nullptr) P.spread[at] = o.spread;
+                    if (P.crps != nullptr) P.crps[at] = o.crps;
+                    if (P.pit != nullptr) P.pit[at] = o.pit;
+                    if (P.rank != nullptr) P.rank[at] = o.rank;
+                }
+#pragma unroll
+                for (int i = 0; i < VF_SUMS; ++i) term_s[i][tid] = tm[i];
+            }
+            if (t + 1 < n_tiles) dm_store_tile<SP, NT>(wr, smem + ((t + 1) & 1) * TILE, tid);
+            __syncthreads();
+
+            // d: the field's sums, columns ascending (the next tile's terms are filed two barriers ahead)
+            if (tid < VF_SUMS)
+                for (int k = 0; k < DM_TC; ++k) acc_sum += term_s[tid][k];
+        }
+    }
+    if (tid < VF_SUMS) wsum[tid] = acc_sum;
+    for (int r = tid; r <= N; r += NT) whist[r] = hist_s[r];   // every integer add lies behind the last tile's barrier
+}
+
+__global__ __launch_bounds__(256) void member_verify_finish_kernel(const SeaDecodeMemberVerify p, const int chunks, const int words) {
+#pragma clang fp reassociate(off)
+    const int tid = threadIdx.x, b = blockIdx.x, N = p.members, F = p.n_fields_total, Pn = p.P * chunks;   // (patch, chunk) partials per field
+    const double* base = reinterpret_cast<const double*>(p.work) + (int64_t)b * Pn * F * words;
+    for (int e = tid; e < F * VF_SUMS; e += 256) {
+        const int f = e / VF_SUMS, i = e - f * VF_SUMS;
+        double acc = 0.0;
+#pragma unroll 8
+        for (int pt = 0; pt < Pn; ++pt) acc += base[((int64_t)pt * F + f) * words + i];   // (patch, chunk) ascending
+        double* dst = p.sums + ((int64_t)b * F + f) * VF_SUMS + i;
+        *dst = p.accumulate ? *dst + acc : acc;
+    }
+    for (int e = tid; e < F * (N + 1); e += 256) {
+        const int f = e / (N + 1), r = e - f * (N + 1);
+        int64_t s = 0;
+#pragma unroll 8
+        for (int pt = 0; pt < Pn; ++pt) s += reinterpret_cast<const int32_t*>(base + ((int64_t)pt * F + f) * words + VF_SUMS)[r];   // integers: any order
+        int64_t* dst = p.hist + ((int64_t)b * F + f) * (N + 1) + r;
+        *dst = p.accumulate ? *dst + s : s;
+    }
+}
+
+template <int SP, int V>
+static void member_verify_launch(const MemberVerifyLaunch& L, dim3 grid, hipStream_t s) {
+    constexpr int lds = mv_lds_bytes<SP>();
+    static bool set_on[64] = {false};   // per device: the dynamic part is 100 kB at SP = 640, above the 64 kB a kernel gets without the attribute
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = -1;
+    if (dev < 0 || !set_on[dev]) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(decode_member_verify_kernel<SP, V>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        if (dev >= 0) set_on[dev] = true;
+    }
+    decode_member_verify_kernel<SP, V><<<grid, dim3(MV_NT), lds, s>>>(L);
+    sea_note_form("decode.member_verify", SP, lds);
+}
+
+template <int V>
+static void member_verify_dispatch(const MemberVerifyLaunch& L, dim3 grid, hipStream_t s) {
+    if (L.p.S <= 128) member_verify_launch<128, V>(L, grid, s);
+    else if (L.p.S <= 256) member_verify_launch<256, V>(L, grid, s);
+    else if (L.p.S <= 384) member_verify_launch<384, V>(L, grid, s);
+    else if (L.p.S <= 512) member_verify_launch<512, V>(L, grid, s);
+    else member_verify_launch<640, V>(L, grid, s);
+}
+
+extern "C" int64_t sea_decode_member_verify_ws_bytes(int B, int P, int n_fields_total, int members, int Cp) {
+    if (B < 1 || B > 65535 || P < 1 || n_fields_total < 1 || members < 1 || members > VF_MAX_N || Cp < 32 || Cp % 32) return -1;
+    return (int64_t)B * P * mv_chunks(Cp) * n_fields_total * mv_words(members) * 8;
+}
+
+extern "C" int sea_decode_member_verify(const SeaDecodeMseGroup* groups, int n_groups, const SeaDecodeMemberVerify* p, int dtype, void* stream) {
+    SEA_REQUIRE(groups != nullptr && p != nullptr, "sea_decode_member_verify: null argument table");
+    SEA_REQUIRE(n_groups >= 1 && n_groups <= SEA_DECODE_MSE_MAX_GROUPS, "sea_decode_member_verify: n_groups=%d outside 1..%d", n_groups, SEA_DECODE_MSE_MAX_GROUPS);
+    SEA_REQUIRE(dtype == SEA_F32 || dtype == SEA_BF16, "sea_decode_member_verify: bad dtype %d", dtype);
+    if (dtype != SEA_BF16) {
+        sea_set_error("sea_decode_member_verify: unsupported: bf16 only (the fp32 decoder composes the decode and sea_ensemble_verify's formulas)");
+        return SEA_EUNSUPPORTED;
+    }
+    const SeaDecodeMemberVerify& P = *p;
+    SEA_REQUIRE(P.obs != nullptr && P.sums != nullptr && P.hist != nullptr && P.status != nullptr && P.work != nullptr,
+                "sea_decode_member_verify: null pointer (obs, sums, hist, status and work are required; prec_field, prec, counts, logw and the maps may be NULL)");
+    SEA_REQUIRE(P.M >= 1, "sea_decode_member_verify: M=%d must be positive", P.M);
+    SEA_REQUIRE(P.S >= 8 && P.S % 8 == 0, "sea_decode_member_verify: S=%d must be a positive multiple of 8", P.S);
+    SEA_REQUIRE(P.Cp >= 32 && P.Cp % 32 == 0, "sea_decode_member_verify: Cp=%d must be a positive multiple of 32", P.Cp);
+    SEA_REQUIRE(P.C >= 1 && P.C <= P.Cp, "sea_decode_member_verify: C=%d must lie in 1..Cp=%d", P.C, P.Cp);
+    SEA_REQUIRE(P.P >= 1, "sea_decode_member_verify: P=%d must be positive", P.P);
+    SEA_REQUIRE(P.members >= 1, "sea_decode_member_verify: members=%d must be positive", P.members);
+    SEA_REQUIRE((int64_t)P.M % ((int64_t)P.P * P.members) == 0, "sea_decode_member_verify: M=%d is not a multiple of P * members = %d * %d", P.M, P.P, P.members);
+    SEA_REQUIRE(P.n_fields_total >= 1, "sea_decode_member_verify: n_fields_total=%d must be positive", P.n_fields_total);
+    SEA_REQUIRE(P.ld_field >= P.C && P.ld_row >= 0, "sea_decode_member_verify: obs strides ld_row=%lld, ld_field=%lld must cover C=%d", (long long)P.ld_row,
+                (long long)P.ld_field, P.C);
+    SEA_REQUIRE(P.prec == nullptr || (P.ld_pfield >= P.C && P.ld_prow >= 0), "sea_decode_member_verify: prec strides ld_prow=%lld, ld_pfield=%lld must cover C=%d",
+                (long long)P.ld_prow, (long long)P.ld_pfield, P.C);
+    SEA_REQUIRE((P.mean == nullptr && P.spread == nullptr && P.crps == nullptr && P.pit == nullptr && P.rank == nullptr) || P.ld_out >= P.C,
+                "sea_decode_member_verify: ld_out=%lld must cover C=%d", (long long)P.ld_out, P.C);
+    SEA_REQUIRE((P.unbiased == 0 || P.unbiased == 1) && (P.accumulate == 0 || P.accumulate == 1), "sea_decode_member_verify: unbiased=%d and accumulate=%d must be 0 or 1",
+                P.unbiased, P.accumulate);
+    SEA_REQUIRE(sea_aligned4(P.obs) && sea_aligned4(P.prec_field) && sea_aligned4(P.prec) && sea_aligned4(P.counts) && sea_aligned4(P.logw) && sea_aligned4(P.mean) &&
+                    sea_aligned4(P.spread) && sea_aligned4(P.crps) && sea_aligned4(P.pit) && sea_aligned4(P.rank) && sea_aligned4(P.status) &&
+                    (reinterpret_cast<uintptr_t>(P.sums) & 7u) == 0 && (reinterpret_cast<uintptr_t>(P.hist) & 7u) == 0 && (reinterpret_cast<uintptr_t>(P.work) & 7u) == 0,
+                "sea_decode_member_verify: misaligned pointer (f32 and int32 buffers need 4 bytes; sums, hist and work 8)");
+    int64_t covered = 0;
+    for (int g = 0; g < n_groups; ++g) {
+        const SeaDecodeMseGroup& G = groups[g];
+        SEA_REQUIRE(G.H != nullptr && G.W2 != nullptr && G.bias != nullptr, "sea_decode_member_verify: group %d: null pointer", g);
+        SEA_REQUIRE(sea_aligned16(G.H) && sea_aligned16(G.W2) && sea_aligned16(G.bias), "sea_decode_member_verify: group %d: pointers must be 16-byte aligned", g);
+        SEA_REQUIRE(G.ldh >= P.S && G.ldh % 8 == 0 && G.ldw >= P.S && G.ldw % 8 == 0,
+                    "sea_decode_member_verify: group %d: row strides ldh=%d ldw=%d must cover S=%d and be multiples of 8", g, G.ldh, G.ldw, P.S);
+        SEA_REQUIRE(G.n_fields >= 1 && G.field0 >= 0 && (int64_t)G.field0 + G.n_fields <= P.n_fields_total,
+                    "sea_decode_member_verify: group %d: n_fields=%d, field0=%d outside the %d fields", g, G.n_fields, G.field0, P.n_fields_total);
+        SEA_REQUIRE((int64_t)G.n_fields * P.Cp <= 0x7fffffffLL / 2, "sea_decode_member_verify: group %d: too many output columns", g);
+        for (int h = 0; h < g; ++h)
+            SEA_REQUIRE(G.field0 >= groups[h].field0 + groups[h].n_fields || groups[h].field0 >= G.field0 + G.n_fields,
+                        "sea_decode_member_verify: group %d: its fields overlap those of group %d (a cell is scored once)", g, h);
+        covered += G.n_fields;
+    }
+    SEA_REQUIRE(covered == P.n_fields_total, "sea_decode_member_verify: the groups cover %lld of the %d fields (every field needs exactly one group)", (long long)covered,
+                P.n_fields_total);
+    if (P.S > 640) {
+        sea_set_error("sea_decode_member_verify: unsupported: hidden width S=%d above 640", P.S);
+        return SEA_EUNSUPPORTED;
+    }
+    if (P.members > VF_MAX_N) {
+        sea_set_error("sea_decode_member_verify: unsupported: members=%d above %d", P.members, VF_MAX_N);
+        return SEA_EUNSUPPORTED;
+    }
+    const int64_t BP = (int64_t)P.M / P.members;   // (history, patch) pairs
+    const int64_t B = BP / P.P;
+    SEA_REQUIRE(BP <= 0x7fffffffLL && B <= 65535, "sea_decode_member_verify: %lld histories; a launch carries up to 65535", (long long)B);
+    SEA_REQUIRE((int64_t)P.n_fields_total * mv_words(P.members) <= 0x7fffffffLL && (int64_t)P.n_fields_total * (P.members + 1) <= 0x7fffffffLL,
+                "sea_decode_member_verify: too many fields");
+    const int64_t need = sea_decode_member_verify_ws_bytes((int)B, P.P, P.n_fields_total, P.members, P.Cp);
+    SEA_REQUIRE(P.work_bytes >= need,
+                "sea_decode_member_verify: work_bytes=%lld below the %lld that sea_decode_member_verify_ws_bytes(B=%d, P=%d, n_fields_total=%d, members=%d, Cp=%d) asks for",
+                (long long)P.work_bytes, (long long)need, (int)B, P.P, P.n_fields_total, P.members, P.Cp);
+    SEA_REQUIRE((int64_t)P.P * mv_chunks(P.Cp) <= 0x7fffffffLL && mv_chunks(P.Cp) <= 65535, "sea_decode_member_verify: Cp=%d has too many column chunks", P.Cp);
+
+    MemberVerifyLaunch L;
+    memset(&L, 0, sizeof(L));
+    for (int g = 0; g < n_groups; ++g) L.g[g] = groups[g];
+    L.p = P;
+    L.n_groups = n_groups;
+    L.words = (int)mv_words(P.members);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    SEA_REQUIRE(P.n_fields_total <= 65535, "sea_decode_member_verify: n_fields_total=%d above 65535 (a grid dimension)", P.n_fields_total);
+    const dim3 grid((unsigned)BP, (unsigned)P.n_fields_total, (unsigned)mv_chunks(P.Cp));
+    if (P.members <= 64) member_verify_dispatch<1>(L, grid, s);
+    else member_verify_dispatch<2>(L, grid, s);
+    member_verify_finish_kernel<<<dim3((unsigned)B), dim3(256), 0, s>>>(P, mv_chunks(P.Cp), L.words);
+    SEA_CHECK_LAUNCH("sea_decode_member_verify");
     return SEA_OK;
 }

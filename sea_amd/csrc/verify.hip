@@ -17,24 +17,13 @@
 // the partial sums come through LDS 256 tiles at a time, so that their loads are in flight together and only the additions are serial.
 // What bounds it: per sensor a wave pays N broadcast reads, compares and fp64 adds per lane and two rounds of butterflies; a workgroup therefore
 // holds only 16 sensors, four per wave, and a few hundred sensors already spread over the chip; below that the two launches' latency.
-#include "sea_common.hpp"
-
-#include <math.h>
+#include "verify_score.hpp"   // the per-reading arithmetic, shared with decode_member_verify_kernel (decode_loss.hip)
 
 constexpr int VF_THREADS = 256;
-constexpr int VF_MAX_N = 128;
 constexpr int VF_TILE = 16;    // sensors per workgroup: four per wave
-constexpr int VF_SUMS = 8;
 constexpr int VF_FIN_TILES = 256;   // tiles whose partial sums the finish kernel holds in LDS at a time
-constexpr int VF_WALK = 8;   // members whose LDS reads are issued together in the walk
 
 static inline int64_t vf_tile_words(int N) { return VF_SUMS + (N + 2) / 2; }   // 8-byte words per (history, tile): 8 sums, then N + 1 int32 bins
-
-__device__ __forceinline__ double vf_wave_sum(double v) {
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
 
 template <int V>
 __global__ __launch_bounds__(VF_THREADS) void verify_kernel(const SeaEnsembleVerify p, const int tiles, const int words) {
@@ -116,86 +105,15 @@ __global__ __launch_bounds__(VF_THREADS) void verify_kernel(const SeaEnsembleVer
             if (lane == 0) r_state[kc] = 1;
             continue;
         }
-        const float* row = vf_stage + kc * SLD;
-        const float yf = y_s[kc];
-        const double y = (double)yf;
-        float x[V];
-        double w[V], below[V];
-        bool lv[V];
-#pragma unroll
-        for (int v = 0; v < V; ++v) {
-            const int i = lane + 64 * v;
-            const bool in = i < N;
-            x[v] = in ? row[i] : 0.f;
-            w[v] = in ? w_s[i] : 0.0;
-            lv[v] = in && live_s[i] != 0;
-            below[v] = 0.0;
-        }
-        // the walk, j ascending; eight members' reads are issued together, and the order test is written without short-circuits: no branch in the chain.
-        // A dead member's weight is 0: its value, NaN included, reaches nothing
-        int j = 0;
-        for (; j + VF_WALK <= N; j += VF_WALK) {
-            float xj[VF_WALK];
-            double wj[VF_WALK];
-#pragma unroll
-            for (int u = 0; u < VF_WALK; ++u) {
-                xj[u] = row[j + u];
-                wj[u] = w_s[j + u];
-            }
-#pragma unroll
-            for (int u = 0; u < VF_WALK; ++u)
-#pragma unroll
-                for (int v = 0; v < V; ++v) {
-                    const bool lower = (xj[u] < x[v]) | ((xj[u] == x[v]) & (j + u < lane + 64 * v));
-                    below[v] += lower ? wj[u] : 0.0;
-                }
-        }
-        for (; j < N; ++j) {
-            const float xj = row[j];
-            const double wj = w_s[j];
-#pragma unroll
-            for (int v = 0; v < V; ++v) {
-                const bool lower = (xj < x[v]) | ((xj == x[v]) & (j < lane + 64 * v));
-                below[v] += lower ? wj : 0.0;
-            }
-        }
-        double m = 0.0;
-        int bad = (isfinite(yf) && isfinite(pv)) ? 0 : 1, rk = 0;
-#pragma unroll
-        for (int v = 0; v < V; ++v) {
-            m += lv[v] ? w[v] * (double)x[v] : 0.0;
-            bad |= (lv[v] && !isfinite(x[v])) ? 1 : 0;
-            rk += (lv[v] && x[v] < yf) ? 1 : 0;
-        }
-        const double mean = vf_wave_sum(m);
-        double var = 0.0, ab = 0.0, pr = 0.0, pt = 0.0;
-#pragma unroll
-        for (int v = 0; v < V; ++v) {
-            const double xd = (double)x[v], d = xd - y, dm = xd - mean;
-            var += lv[v] ? w[v] * dm * dm : 0.0;
-            ab += lv[v] ? w[v] * fabs(d) : 0.0;
-            pr += lv[v] ? w[v] * d * (2.0 * below[v] + w[v] - 1.0) : 0.0;
-            pt += lv[v] ? w[v] * (x[v] < yf ? 1.0 : (x[v] == yf ? 0.5 : 0.0)) : 0.0;
-        }
-#pragma unroll
-        for (int m = 1; m < 64; m <<= 1) {   // six butterflies, stage by stage: their exchanges are in flight together; each sum has vf_wave_sum's order
-            const double o_var = __shfl_xor(var, m, 64), o_ab = __shfl_xor(ab, m, 64), o_pr = __shfl_xor(pr, m, 64), o_pt = __shfl_xor(pt, m, 64);
-            const int o_rk = __shfl_xor(rk, m, 64), o_bad = __shfl_xor(bad, m, 64);
-            var += o_var;
-            ab += o_ab;
-            pr += o_pr;
-            pt += o_pt;
-            rk += o_rk;
-            bad += o_bad;
-        }
+        const VfReading r = vf_score_wave<V>(vf_stage + kc * SLD, w_s, live_s, N, lane, y_s[kc], pv);
         if (lane == 0) {
-            r_mean[kc] = mean;
-            r_var[kc] = var;
-            r_abs[kc] = ab;
-            r_pair[kc] = pr;
-            r_pit[kc] = pt;
-            r_rank[kc] = rk;
-            r_state[kc] = bad ? 2 : 0;
+            r_mean[kc] = r.mean;
+            r_var[kc] = r.var;
+            r_abs[kc] = r.ab;
+            r_pair[kc] = r.pair;
+            r_pit[kc] = r.pit;
+            r_rank[kc] = r.rank;
+            r_state[kc] = r.state;
         }
     }
     __syncthreads();
@@ -206,39 +124,21 @@ __global__ __launch_bounds__(VF_THREADS) void verify_kernel(const SeaEnsembleVer
 #pragma unroll
         for (int i = 0; i < VF_SUMS; ++i) t[i] = 0.0;
         if (tid < kcn) {
-            const int state = r_state[tid];
-            float o_mean = 0.f, o_spread = 0.f, o_crps = 0.f, o_pit = 0.f;
-            int o_rank = -1;
-            if (state == 2) {
-                o_mean = o_spread = o_crps = o_pit = NAN;
-                o_rank = -2;
-                t[6] = 1.0;
-            } else if (state == 0) {
-                const double y = (double)y_s[tid];
-                const double rvar = 1.0 / (double)pv_s[tid];
-                const double mean = r_mean[tid];
-                const double sp2 = c > 0.0 ? r_var[tid] / c : 0.0;
-                const double crps = r_abs[tid] - (c > 0.0 ? r_pair[tid] / c : 0.0);
-                const double err = y - mean;
-                o_mean = (float)mean;
-                o_spread = (float)sqrt(sp2);
-                o_crps = (float)crps;
-                o_pit = (float)r_pit[tid];
-                o_rank = r_rank[tid];
-                t[0] = 1.0;
-                t[1] = crps;
-                t[2] = err * err;
-                t[3] = sp2;
-                t[4] = err * err / (sp2 + rvar);
-                t[5] = mean - y;
-                t[7] = rvar;
-                atomicAdd(&hist_s[o_rank], 1);   // LDS, integers: the order does not matter; 0 <= rank <= N
-            }
-            if (p.mean != nullptr) p.mean[orow + k0 + tid] = o_mean;
-            if (p.spread != nullptr) p.spread[orow + k0 + tid] = o_spread;
-            if (p.crps != nullptr) p.crps[orow + k0 + tid] = o_crps;
-            if (p.pit != nullptr) p.pit[orow + k0 + tid] = o_pit;
-            if (p.rank != nullptr) p.rank[orow + k0 + tid] = o_rank;
+            VfReading r;
+            r.mean = r_mean[tid];
+            r.var = r_var[tid];
+            r.ab = r_abs[tid];
+            r.pair = r_pair[tid];
+            r.pit = r_pit[tid];
+            r.rank = r_rank[tid];
+            r.state = r_state[tid];
+            const VfOut o = vf_finish_reading(r, y_s[tid], pv_s[tid], c, t);
+            if (r.state == 0) atomicAdd(&hist_s[o.rank], 1);   // LDS, integers: the order does not matter; 0 <= rank <= N
+            if (p.mean != nullptr) p.mean[orow + k0 + tid] = o.mean;
+            if (p.spread != nullptr) p.spread[orow + k0 + tid] = o.spread;
+            if (p.crps != nullptr) p.crps[orow + k0 + tid] = o.crps;
+            if (p.pit != nullptr) p.pit[orow + k0 + tid] = o.pit;
+            if (p.rank != nullptr) p.rank[orow + k0 + tid] = o.rank;
         }
 #pragma unroll
         for (int i = 0; i < VF_SUMS; ++i) term_s[i][tid] = t[i];

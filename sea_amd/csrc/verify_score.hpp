@@ -1,0 +1,151 @@
+// The per-reading arithmetic of ensemble verification, shared by verify_kernel (verify.hip: a reading is a sensor) and decode_member_verify_kernel
+// (decode_loss.hip: a reading is a cell of the decoded field).  Both call the SAME two device functions, so a cell scored from the same member values,
+// reading, precision and weights has the same bits as a sensor.  include/sea_hip.h (sea_ensemble_verify) states the formulas.
+//   vf_score_wave<V>  one wave scores one reading: lane l holds member l (and l + 64 at V = 2), walks j = 0 .. N - 1 with broadcast LDS reads and
+//                     accumulates the weight below its own member under the total order (value, member index); the lane terms are reduced by a fixed
+//                     xor butterfly (the mean first: the spread is centred on it).  Every lane returns the same sums.
+//   vf_finish_reading one thread finishes one reading: the selects on c, the fp32 roundings, the eight terms of the per-history sums.
+#pragma once
+#include "sea_common.hpp"
+
+#include <math.h>
+
+constexpr int VF_MAX_N = 128;
+constexpr int VF_SUMS = 8;
+constexpr int VF_WALK = 8;   // members whose LDS reads are issued together in the walk
+
+__device__ __forceinline__ double vf_wave_sum(double v) {
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
+
+struct VfReading {   // what a wave leaves per reading; state: 0 live and good, 1 dead, 2 bad
+    double mean, var, ab, pair, pit;
+    int rank, state;
+};
+
+// row: the reading's member values [N] in LDS; w_s, live_s: the history's normalised weights and live flags [N] in LDS; yf, pv: the reading and its
+// precision (pv > 0: the caller passes dead readings over).  A dead member's weight is 0: its value, NaN included, reaches nothing.
+template <int V>
+__device__ __forceinline__ VfReading vf_score_wave(const float* row, const double* w_s, const int* live_s, const int N, const int lane, const float yf, const float pv) {
+#pragma clang fp reassociate(off)
+    const double y = (double)yf;
+    float x[V];
+    double w[V], below[V];
+    bool lv[V];
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+        const int i = lane + 64 * v;
+        const bool in = i < N;
+        x[v] = in ? row[i] : 0.f;
+        w[v] = in ? w_s[i] : 0.0;
+        lv[v] = in && live_s[i] != 0;
+        below[v] = 0.0;
+    }
+    // the walk, j ascending; eight members' reads are issued together, and the order test is written without short-circuits: no branch in the chain
+    int j = 0;
+    for (; j + VF_WALK <= N; j += VF_WALK) {
+        float xj[VF_WALK];
+        double wj[VF_WALK];
+#pragma unroll
+        for (int u = 0; u < VF_WALK; ++u) {
+            xj[u] = row[j + u];
+            wj[u] = w_s[j + u];
+        }
+#pragma unroll
+        for (int u = 0; u < VF_WALK; ++u)
+#pragma unroll
+            for (int v = 0; v < V; ++v) {
+                const bool lower = (xj[u] < x[v]) | ((xj[u] == x[v]) & (j + u < lane + 64 * v));
+                below[v] += lower ? wj[u] : 0.0;
+            }
+    }
+    for (; j < N; ++j) {
+        const float xj = row[j];
+        const double wj = w_s[j];
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            const bool lower = (xj < x[v]) | ((xj == x[v]) & (j < lane + 64 * v));
+            below[v] += lower ? wj : 0.0;
+        }
+    }
+    double m = 0.0;
+    int bad = (isfinite(yf) && isfinite(pv)) ? 0 : 1, rk = 0;
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+        m += lv[v] ? w[v] * (double)x[v] : 0.0;
+        bad |= (lv[v] && !isfinite(x[v])) ? 1 : 0;
+        rk += (lv[v] && x[v] < yf) ? 1 : 0;
+    }
+    const double mean = vf_wave_sum(m);
+    double var = 0.0, ab = 0.0, pr = 0.0, pt = 0.0;
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+        const double xd = (double)x[v], d = xd - y, dm = xd - mean;
+        var += lv[v] ? w[v] * dm * dm : 0.0;
+        ab += lv[v] ? w[v] * fabs(d) : 0.0;
+        pr += lv[v] ? w[v] * d * (2.0 * below[v] + w[v] - 1.0) : 0.0;
+        pt += lv[v] ? w[v] * (x[v] < yf ? 1.0 : (x[v] == yf ? 0.5 : 0.0)) : 0.0;
+    }
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) {   // six butterflies, stage by stage: their exchanges are in flight together; each sum has vf_wave_sum's order
+        const double o_var = __shfl_xor(var, m, 64), o_ab = __shfl_xor(ab, m, 64), o_pr = __shfl_xor(pr, m, 64), o_pt = __shfl_xor(pt, m, 64);
+        const int o_rk = __shfl_xor(rk, m, 64), o_bad = __shfl_xor(bad, m, 64);
+        var += o_var;
+        ab += o_ab;
+        pr += o_pr;
+        pt += o_pt;
+        rk += o_rk;
+        bad += o_bad;
+    }
+    VfReading r;
+    r.mean = mean;
+    r.var = var;
+    r.ab = ab;
+    r.pair = pr;
+    r.pit = pt;
+    r.rank = rk;
+    r.state = bad ? 2 : 0;
+    return r;
+}
+
+struct VfOut {
+    float mean, spread, crps, pit;
+    int rank;
+};
+
+// t: the reading's eight terms of the per-history sums (all 0 for a dead reading).  c = unbiased ? 1 - q : 1.
+__device__ __forceinline__ VfOut vf_finish_reading(const VfReading& r, const float yf, const float pv, const double c, double (&t)[VF_SUMS]) {
+#pragma clang fp reassociate(off)
+    VfOut o;
+    o.mean = o.spread = o.crps = o.pit = 0.f;
+    o.rank = -1;
+#pragma unroll
+    for (int i = 0; i < VF_SUMS; ++i) t[i] = 0.0;
+    if (r.state == 2) {
+        o.mean = o.spread = o.crps = o.pit = NAN;
+        o.rank = -2;
+        t[6] = 1.0;
+    } else if (r.state == 0) {
+        const double y = (double)yf;
+        const double rvar = 1.0 / (double)pv;
+        const double mean = r.mean;
+        const double sp2 = c > 0.0 ? r.var / c : 0.0;
+        const double crps = r.ab - (c > 0.0 ? r.pair / c : 0.0);
+        const double err = y - mean;
+        o.mean = (float)mean;
+        o.spread = (float)sqrt(sp2);
+        o.crps = (float)crps;
+        o.pit = (float)r.pit;
+        o.rank = r.rank;
+        t[0] = 1.0;
+        t[1] = crps;
+        t[2] = err * err;
+        t[3] = sp2;
+        t[4] = err * err / (sp2 + rvar);
+        t[5] = mean - y;
+        t[7] = rvar;
+    }
+    return o;
+}

@@ -46,6 +46,12 @@ Whether the ensemble is any good is read at the same sensors (SensorVerification
     D, status, pred = kalman.transform(y, obs, precision)
     forecast = verify.from_predictions(pred, obs, precision, into=forecast)   # CRPS, PIT, rank, mean, spread per sensor; sums and rank histogram add up
     forecast.spread_skill, forecast.suggested_inflation, forecast.hist         # [B] tensors and the histogram, on the device
+
+... or on the whole mesh against a dense snapshot (FieldVerification: sea_decode_member_verify, the members' fields never written):
+
+    verify = FieldVerification(decoder, n_patches, members=n, counts=counts, sigma=sigma_cell)
+    scores = verify(y, snapshot, precision, into=scores)                       # crps, pit, rank, mean, spread maps [B, P, n_fields, n_inp]
+    scores.spread_skill, scores.pooled().suggested_inflation                    # [B, n_fields] per field; pooled(): [B] over the mesh
 """
 from __future__ import annotations
 
@@ -727,7 +733,65 @@ def _composed_transform_gram(gram, proj, count, taper, members: int, rho: float,
     return D.to(torch.float32).contiguous(), status
 
 
-class FieldKalman:
+class _FieldObserver:
+    """What FieldKalman and FieldVerification share: the checks of (y, obs, precision) against a dense snapshot, the layout, and sigma folded into an f32
+    [n_fields] precision on the device.  _what names the class in the messages."""
+    _what = "FieldObserver"
+
+    def _set_sigma(self, sigma, n_fields: int) -> None:
+        if sigma is None:
+            self._prec_host = None
+        else:
+            s = torch.as_tensor(sigma, dtype=torch.float64).detach().cpu()   # a tensor given on the device comes to the host once, here
+            if s.dim() > 1 or (s.dim() == 1 and s.numel() != n_fields):
+                raise ValueError(f"{self._what}: sigma must be None, a number or {n_fields} numbers (one per field), got shape {tuple(s.shape)}")
+            if not bool(torch.isfinite(s).all()) or not bool((s > 0).all()):
+                raise ValueError(f"{self._what}: sigma must be finite and positive, got {s.tolist()}")
+            self._prec_host = [float(v) for v in (1.0 / (s * s)).expand(n_fields)]
+        self._prec = None
+
+    def _field_precision(self, device):
+        """1 / sigma_f^2 as an f32 [n_fields] tensor on the device (None without sigma), built once per device by fills."""
+        if self._prec_host is None:
+            return None
+        if self._prec is None or self._prec.device != device:
+            prec = torch.empty(len(self._prec_host), device=device, dtype=torch.float32)
+            for f, v in enumerate(self._prec_host):
+                prec[f].fill_(v)
+            self._prec = prec
+        return self._prec
+
+    def _operands(self, y, obs, precision, gpu: bool = True):
+        P, n, what = self.n_patches, self.members, self._what
+        if not torch.is_tensor(y) or y.dim() != 3 or y.shape[-1] % P or y.shape[0] < 1:
+            raise ValueError(f"{what}: y must be [B * members, n_groups, n_patches * D] with n_patches = {P}, got "
+                             f"{tuple(y.shape) if torch.is_tensor(y) else type(y).__name__}")
+        Bm = y.shape[0]
+        if Bm % n:
+            raise ValueError(f"{what}: the {Bm} trajectories of y are not a multiple of members = {n}")
+        B = Bm // n
+        if not torch.is_tensor(obs) or obs.dim() != 4 or tuple(obs.shape[:2]) != (B, P):
+            raise ValueError(f"{what}: the observation must be [{B}, {P}, ...] in layout {self.layout} (one snapshot per history), got "
+                             f"{tuple(obs.shape) if torch.is_tensor(obs) else type(obs).__name__}")
+        if obs.dtype != torch.float32 or obs.device != y.device:
+            raise ValueError(f"{what}: obs must be float32 on {y.device}, got {obs.dtype} on {obs.device}")
+        if precision is not None:
+            if not torch.is_tensor(precision) or tuple(precision.shape) != tuple(obs.shape):
+                raise ValueError(f"{what}: precision must be None or a map of obs's shape {tuple(obs.shape)}, got "
+                                 f"{tuple(precision.shape) if torch.is_tensor(precision) else type(precision).__name__}")
+            if precision.dtype != torch.float32:
+                raise ValueError(f"{what}: precision must be float32, got {precision.dtype}")
+            if precision.device.type == "cpu" and (not bool(torch.isfinite(precision).all()) or not bool((precision >= 0).all())):
+                raise ValueError(f"{what}: precision must be finite and >= 0")
+            if precision.device != y.device:
+                raise ValueError(f"{what}: precision is on {precision.device}, the states on {y.device}")
+        if gpu:
+            N.require_gpu(y, f"{what} states")
+        perm = (lambda t: t) if self.layout == "BPFC" else (lambda t: t.permute(0, 1, 3, 2))
+        return y.detach(), perm(obs.detach()), None if precision is None else perm(precision.detach())
+
+
+class FieldKalman(_FieldObserver):
     """The ensemble Kalman analysis of an ensemble's latent states from a DENSE snapshot of the decoded fields — a PIV frame, a coarse solver's field, a
     reanalysis — by the deterministic EnKF of Sakov & Oke (2008) in ensemble space: kalman.analyse(y, obs, precision=None) -> y_a in y's layout and
     dtype, a corrected state for RolloutSession.step(c, state=y_a).  All members move, none is duplicated; no random numbers.
@@ -759,6 +823,8 @@ class FieldKalman:
     A call reads nothing back from the device and uploads nothing after the first call on a device.  2 <= members <= 128.  `decoder` is a sea_amd
     Decode; no autograd graph is built."""
 
+    _what = "FieldKalman"
+
     def __init__(self, decoder, n_patches: int, members: int, counts=None, layout: str = "BPFC", sigma=None, inflation: float = 1.0,
                  anomaly_gain: float = 0.5, taper=None, fused: Optional[bool] = None):
         if layout not in ("BPFC", "BPCF"):
@@ -775,16 +841,7 @@ class FieldKalman:
         self.decoder, self.n_patches, self.members, self.counts, self.layout, self.fused = decoder, n_patches, members, counts, layout, fused
         self.inflation, self.anomaly_gain = float(inflation), float(anomaly_gain)
         n_fields = sum(len(g) for g in decoder.field_groups)
-        if sigma is None:
-            self._prec_host = None
-        else:
-            s = torch.as_tensor(sigma, dtype=torch.float64).detach().cpu()   # a tensor given on the device comes to the host once, here
-            if s.dim() > 1 or (s.dim() == 1 and s.numel() != n_fields):
-                raise ValueError(f"FieldKalman: sigma must be None, a number or {n_fields} numbers (one per field), got shape {tuple(s.shape)}")
-            if not bool(torch.isfinite(s).all()) or not bool((s > 0).all()):
-                raise ValueError(f"FieldKalman: sigma must be finite and positive, got {s.tolist()}")
-            self._prec_host = [float(v) for v in (1.0 / (s * s)).expand(n_fields)]
-        self._prec = None
+        self._set_sigma(sigma, n_fields)
         self._taper = {}
         if taper is None:
             self._taper_src = None
@@ -810,17 +867,6 @@ class FieldKalman:
             t = self._taper[device] = self._taper_src.to(device)
         return t
 
-    def _field_precision(self, device):
-        """1 / sigma_f^2 as an f32 [n_fields] tensor on the device (None without sigma), built once per device by fills."""
-        if self._prec_host is None:
-            return None
-        if self._prec is None or self._prec.device != device:
-            prec = torch.empty(len(self._prec_host), device=device, dtype=torch.float32)
-            for f, v in enumerate(self._prec_host):
-                prec[f].fill_(v)
-            self._prec = prec
-        return self._prec
-
     def _fused_for(self, y) -> bool:
         """Whether the decode and reduction run as the fused launch (sea_decode_member_gram)."""
         if self.fused is not None:
@@ -831,34 +877,6 @@ class FieldKalman:
         """Whether the transform and the mix run as sea_enkf_transform_gram and sea_ensemble_mix: always, except with fused=False (all torch ops, for
         comparison).  The two launches take fp64 partials and fp32 or bf16 states whatever the decoder computed in."""
         return self.fused is not False
-
-    def _operands(self, y, obs, precision):
-        P, n = self.n_patches, self.members
-        if not torch.is_tensor(y) or y.dim() != 3 or y.shape[-1] % P or y.shape[0] < 1:
-            raise ValueError(f"FieldKalman: y must be [B * members, n_groups, n_patches * D] with n_patches = {P}, got "
-                             f"{tuple(y.shape) if torch.is_tensor(y) else type(y).__name__}")
-        Bm = y.shape[0]
-        if Bm % n:
-            raise ValueError(f"FieldKalman: the {Bm} trajectories of y are not a multiple of members = {n}")
-        B = Bm // n
-        if not torch.is_tensor(obs) or obs.dim() != 4 or tuple(obs.shape[:2]) != (B, P):
-            raise ValueError(f"FieldKalman: the observation must be [{B}, {P}, ...] in layout {self.layout} (one snapshot per history), got "
-                             f"{tuple(obs.shape) if torch.is_tensor(obs) else type(obs).__name__}")
-        if obs.dtype != torch.float32 or obs.device != y.device:
-            raise ValueError(f"FieldKalman: obs must be float32 on {y.device}, got {obs.dtype} on {obs.device}")
-        if precision is not None:
-            if not torch.is_tensor(precision) or tuple(precision.shape) != tuple(obs.shape):
-                raise ValueError(f"FieldKalman: precision must be None or a map of obs's shape {tuple(obs.shape)}, got "
-                                 f"{tuple(precision.shape) if torch.is_tensor(precision) else type(precision).__name__}")
-            if precision.dtype != torch.float32:
-                raise ValueError(f"FieldKalman: precision must be float32, got {precision.dtype}")
-            if precision.device.type == "cpu" and (not bool(torch.isfinite(precision).all()) or not bool((precision >= 0).all())):
-                raise ValueError("FieldKalman: precision must be finite and >= 0")
-            if precision.device != y.device:
-                raise ValueError(f"FieldKalman: precision is on {precision.device}, the states on {y.device}")
-        N.require_gpu(y, "FieldKalman states")
-        perm = (lambda t: t) if self.layout == "BPFC" else (lambda t: t.permute(0, 1, 3, 2))
-        return y.detach(), perm(obs.detach()), None if precision is None else perm(precision.detach())
 
     def transform(self, y: torch.Tensor, obs: torch.Tensor, precision: Optional[torch.Tensor] = None):
         """(D f32 [B, Ld, N, N], status int32 [B, Ld]): the ensemble-space matrix of the analysis and the live cells per problem (-1: no update)."""
@@ -1087,3 +1105,157 @@ class SensorVerification:
         z = y.detach().reshape(Bm, G, P, E // P).permute(0, 2, 1, 3)          # the re-layout of SensorLikelihood
         _, pred = self.decoder.sensor_sse(z, self.sensors, obs, precision=prec, members=n, predictions=True)
         return self._verify(pred, obs, prec, logw, into)
+
+
+# ------------------------------------------------------------------------------------------------ verification on dense fields
+FIELD_MAPS = ("mean", "spread", "crps", "pit", "rank")
+FIELD_VERIFY_FUSED_MIN_ROWS = 4096   # fused=None: the fused launches from this many decoder rows (B * members * n_patches) on — the smallest measured size
+
+
+def _field_sums_property(fn):
+    return property(lambda self: fn(self.sums))
+
+
+@dataclasses.dataclass(frozen=True)
+class FieldScores:
+    """What FieldVerification returns, all on the states' device.  Per cell, [B, P, n_fields, n_inp] views: crps, pit, mean, spread (float32) and rank
+    (int32: live members below the observed value; -1 a cell without weight, -2 a bad cell — a live cell whose observation, weight or a live
+    member's value is not finite; its floats are NaN); None for a map that was not asked for.  Per (history, field): sums float64 [B, F, 8] and hist
+    int64 [B, F, members + 1] with EnsembleScores' entries, status int32 [B].  sums and hist add up over calls (into=).  The derived properties are
+    float64 [B, F] tensor expressions of sums: nothing is read back; a field without a live good cell gives NaN.  pooled() adds the fields up."""
+    crps: Optional[torch.Tensor]
+    pit: Optional[torch.Tensor]
+    rank: Optional[torch.Tensor]
+    mean: Optional[torch.Tensor]
+    spread: Optional[torch.Tensor]
+    sums: torch.Tensor
+    hist: torch.Tensor
+    status: torch.Tensor
+
+    count = _field_sums_property(lambda s: s[..., 0])
+    mean_crps = _field_sums_property(lambda s: s[..., 1] / s[..., 0])
+    rmse = _field_sums_property(lambda s: (s[..., 2] / s[..., 0]).sqrt())
+    mean_spread = _field_sums_property(lambda s: (s[..., 3] / s[..., 0]).sqrt())
+    spread_skill = _field_sums_property(lambda s: (s[..., 3] / s[..., 2]).sqrt())
+    consistency = _field_sums_property(lambda s: s[..., 4] / s[..., 0])
+    bias = _field_sums_property(lambda s: s[..., 5] / s[..., 0])
+    suggested_inflation = _field_sums_property(lambda s: ((s[..., 2] - s[..., 7]) / s[..., 3]).clamp_min(1.0).sqrt())
+
+    def pooled(self) -> EnsembleScores:
+        """The scores over all fields: an EnsembleScores whose sums [B, 8] and hist [B, members + 1] are this object's added over the fields (new
+        tensors), with the same maps and status — its derived properties are the mesh-wide rmse, spread_skill, suggested_inflation, ..."""
+        return EnsembleScores(crps=self.crps, pit=self.pit, rank=self.rank, mean=self.mean, spread=self.spread, sums=self.sums.sum(1), hist=self.hist.sum(1),
+                              status=self.status)
+
+
+def _field_cell_weights(shape, prec_field, prec, counts, device):
+    """w f32 [B, P, F, C] of sea_decode_member_verify: valid ? max(pf, 0) * max(prec, 0) : 0, by selects (a NaN counts as 0), the product in fp32."""
+    B, P, F, C_ = shape
+    zero = torch.zeros((), device=device, dtype=torch.float32)
+    w = torch.ones(B, P, F, C_, device=device, dtype=torch.float32)
+    if prec_field is not None:
+        pf = prec_field.to(torch.float32).view(1, 1, F, 1)
+        w = w * torch.where(pf > 0, pf, zero)
+    if prec is not None:
+        pm = prec[..., :C_].to(torch.float32)
+        w = w * torch.where(pm > 0, pm, zero)
+    if counts is not None:
+        w = torch.where((torch.arange(C_, device=device) < counts.to(device)[:, None]).view(1, P, 1, C_), w, zero)
+    return torch.where(w > 0, w, zero)   # false for NaN
+
+
+def _composed_field_verify(Y, obs, w, logw, members: int, unbiased: bool, maps=FIELD_MAPS, out_dtype=torch.float32):
+    """sea_decode_member_verify's outputs from decoded members, with every cell a sensor of _composed_verify and every (history, field) a history of
+    it: Y [B * members, P, F, C] (any float dtype, compared as given), obs [B, P, F, >= C], w [B, P, F, C] the cells' weights (0: dead), logw None or
+    [B * members].  Returns a dict: the maps asked for [B, P, F, C], sums [B, F, 8], hist [B, F, members + 1], status [B].  Nothing is read back."""
+    n = members
+    Bm, P, F, C_ = Y.shape
+    B = Bm // n
+    pred = Y.reshape(B, n, P, F, C_).permute(0, 3, 1, 2, 4).reshape(B * F * n, P * C_)
+    cells = lambda t: t[..., :C_].permute(0, 2, 1, 3).reshape(B * F, P * C_)   # noqa: E731
+    lw = None if logw is None else logw.reshape(B, 1, n).expand(B, F, n).reshape(-1)
+    r = _composed_verify(pred, cells(obs), cells(w), lw, n, unbiased, out_dtype=out_dtype)
+    res = {k: r[k].view(B, F, P, C_).permute(0, 2, 1, 3).contiguous() for k in FIELD_MAPS if k in maps}
+    res.update(sums=r["sums"].view(B, F, N.VERIFY_SUMS), hist=r["hist"].view(B, F, n + 1), status=r["status"].view(B, F)[:, 0].contiguous())
+    return res
+
+
+class FieldVerification(_FieldObserver):
+    """Verification of an ensemble against a DENSE snapshot of the decoded fields — SensorVerification's scores with every cell of the mesh a reading:
+    verify(y, obs, precision=None, logw=None, into=None, maps=...) -> FieldScores.  Per cell the continuous ranked probability score, the probability
+    integral transform, the rank of the observed value among the members, the ensemble mean and spread (maps on the mesh: MeshUnpatcher.unpatch_spread
+    for crps and spread, unpatch_map for pit and rank); per (history, field) the fp64 sums behind rmse, mean_spread, spread_skill, consistency, bias,
+    mean_crps and suggested_inflation, and the rank histogram — what inflation, anomaly_gain, sigma and a taper radius of FieldKalman are tuned by.
+
+    y, obs, layout, counts, sigma and precision mean what they mean in FieldKalman (its checks, its folding of sigma into a per-field precision): the
+    weight of a cell is precision / sigma_f^2, 1 / weight is the observation-error variance that `consistency` and `suggested_inflation` use, and a
+    cell without weight is neutral whatever obs holds there.  logw: None (equal weights) or [B * members] (or [B, members]) unnormalised log-weights;
+    a member with -inf is dead.  unbiased=True: the fair CRPS and the N / (N - 1) spread.  maps: the per-cell outputs to produce, a subset of
+    ("mean", "spread", "crps", "pit", "rank"); the others are None in the result.  into: an earlier FieldScores; this call's sums and histograms are
+    added onto ITS sums and hist (in place).
+    fused: True — the decoder's first layer plus the two launches of sea_decode_member_verify (include/sea_hip.h; bf16, up to 128 members): neither the
+    members' decoded fields nor a prediction matrix are written; False — Decode.forward plus the formulas as fp64 torch ops with every cell a sensor
+    (the composed path: fp32, more than 128 members, comparison; it holds the members' fields several times over).  fused=None takes the fused launches
+    in bf16 up to 128 members from 4096 decoder rows (B * members * n_patches) on, and the composed path everywhere else — the measured rule
+    (tools/field_verify_bench.py, profiles/field_verify_bench.txt; P = 64 patches, n_inp 1628, cylinder and multiphase decoder,
+    every column valid and the mesh's counts, maps on and off, device time per call): 64 members, one history (4096 rows) 0.62 - 1.01 ms fused
+    against 6.3 - 6.7 ms composed; 64 members, four histories (16384 rows) 1.78 - 3.20 against 23.5 - 25.1 ms; 128 members, one history (8192
+    rows) 1.33 - 2.20 against 8.8 - 9.7 ms; 128 members, four histories (32768 rows) 3.90 - 7.03 against 34.8 - 37.8 ms; 6 launches against 170;
+    16 - 119 MB of extra memory (9 - 95 MB without maps; the members' fp32 fields alone would be 76 - 611 MB) against 1.9 - 15.2 GB.  Nothing was
+    measured below 4096 rows, so the composed path stays the default there.  (SensorVerification with every valid cell a sensor, cylinder, 64 members,
+    one history: 0.87 ms at the mesh's 90 000 cells, 2.05 ms at all 312 576.)
+    A call reads nothing back from the device and uploads nothing after the first call on a device.  `decoder` is a sea_amd Decode; no autograd graph
+    is built."""
+    _what = "FieldVerification"
+
+    def __init__(self, decoder, n_patches: int, members: int, counts=None, layout: str = "BPFC", sigma=None, unbiased: bool = True,
+                 fused: Optional[bool] = None):
+        if layout not in ("BPFC", "BPCF"):
+            raise ValueError(f"FieldVerification: layout must be 'BPFC' or 'BPCF', got {layout!r}")
+        if not isinstance(n_patches, int) or isinstance(n_patches, bool) or n_patches < 1:
+            raise ValueError(f"FieldVerification: n_patches = {n_patches!r} must be a positive integer")
+        if not isinstance(members, int) or isinstance(members, bool) or members < 1:
+            raise ValueError(f"FieldVerification: members = {members!r} must be a positive integer")
+        if fused is not None and not isinstance(fused, bool):
+            raise ValueError(f"FieldVerification: fused = {fused!r} must be None, True or False")
+        if fused and members > N.FIELD_VERIFY_MAX_N:
+            raise ValueError(f"FieldVerification: the fused launches carry up to {N.FIELD_VERIFY_MAX_N} members, got {members} (fused=False, or None)")
+        self.decoder, self.n_patches, self.members, self.counts, self.layout, self.fused = decoder, n_patches, members, counts, layout, fused
+        self.unbiased = bool(unbiased)
+        self._set_sigma(sigma, sum(len(g) for g in decoder.field_groups))
+
+    def _fused_for(self, y) -> bool:
+        """Whether a call on y runs the fused launches (sea_decode_member_verify): the class docstring's rule when fused is None."""
+        if self.fused is not None:
+            return bool(self.fused)
+        return (self.decoder._act_dtype() == torch.bfloat16 and self.members <= N.FIELD_VERIFY_MAX_N
+                and y.shape[0] * self.n_patches >= FIELD_VERIFY_FUSED_MIN_ROWS)
+
+    def __call__(self, y: torch.Tensor, obs: torch.Tensor, precision: Optional[torch.Tensor] = None, logw: Optional[torch.Tensor] = None,
+                 into: Optional[FieldScores] = None, maps=FIELD_MAPS) -> FieldScores:
+        y, tgt, prec = self._operands(y, obs, precision, gpu=False)
+        Bm, G, E = y.shape
+        P, n = self.n_patches, self.members
+        B = Bm // n
+        n_fields = sum(len(g) for g in self.decoder.field_groups)
+        maps = tuple(maps)
+        if any(k not in FIELD_MAPS for k in maps) or len(set(maps)) != len(maps):
+            raise ValueError(f"FieldVerification: maps must be distinct names among {FIELD_MAPS}, got {maps!r}")
+        if logw is not None:
+            if not torch.is_tensor(logw) or not logw.is_floating_point() or logw.numel() != Bm or logw.dim() not in (1, 2) \
+                    or (logw.dim() == 2 and logw.shape[1] != n) or logw.device != y.device:
+                raise ValueError(f"FieldVerification: logw must be None or a floating-point [{Bm}] (or [{B}, {n}]) tensor of log-weights on {y.device}, got "
+                                 f"{(tuple(logw.shape), str(logw.device)) if torch.is_tensor(logw) else type(logw).__name__}")
+            logw = logw.detach().reshape(-1).to(torch.float32).contiguous()
+        if into is not None:
+            if not isinstance(into, FieldScores) or tuple(into.sums.shape) != (B, n_fields, N.VERIFY_SUMS) or tuple(into.hist.shape) != (B, n_fields, n + 1) \
+                    or into.sums.device != y.device or into.sums.dtype != torch.float64 or into.hist.dtype != torch.int64 \
+                    or not into.sums.is_contiguous() or not into.hist.is_contiguous():
+                raise ValueError(f"FieldVerification: into must be an earlier FieldScores for {B} histories of {n} members and {n_fields} fields on {y.device}")
+        N.require_gpu(y, "FieldVerification states")
+        z = y.reshape(Bm, G, P, E // P).permute(0, 2, 1, 3)          # the re-layout of FieldLikelihood
+        r = self.decoder.member_verify(z, tgt, n, counts=self.counts, precision=prec, field_precision=self._field_precision(y.device), logw=logw,
+                                       unbiased=self.unbiased, fused=self._fused_for(y), maps=maps, into=None if into is None else dict(sums=into.sums, hist=into.hist))
+        return FieldScores(**{k: r.get(k) for k in FIELD_MAPS}, sums=r["sums"], hist=r["hist"], status=r["status"])
+
+    verify = __call__

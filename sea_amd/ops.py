@@ -1684,3 +1684,124 @@ def ensemble_verify(pred: torch.Tensor, obs: torch.Tensor, members: int, prec: O
     P.ld_obs, P.ld_pred = max(P.ld_obs, K), max(P.ld_pred, K)   # a single row: its stride is never used and may say anything
     N.check(N.lib().sea_ensemble_verify(C.byref(P), N.stream_ptr()), "sea_ensemble_verify")
     return res
+
+
+FIELD_VERIFY_MAPS = ("mean", "spread", "crps", "pit", "rank")
+
+
+def fill_decode_member_verify(groups_arr, P: N.SeaDecodeMemberVerify, groups: Sequence[Dict], obs, prec_field, prec, counts, logw, n_patches: int, members: int,
+                              C_: int, Cp: int, unbiased: bool, accumulate: bool, mean, spread, crps, pit, rank, sums, hist, status, work, ld_out: int) -> None:
+    """The argument table of sea_decode_member_verify.  groups, obs, prec_field, prec, counts as fill_decode_member_gram; logw None or f32 [B * members]
+    contiguous; mean, spread, crps, pit f32 and rank int32 [B, n_patches, n_fields_total, ld_out] contiguous or None; sums f64 [B, n_fields_total, 8], hist
+    int64 [B, n_fields_total, members + 1], status int32 [B] contiguous; work: a uint8 workspace of at least sea_decode_member_verify_ws_bytes(...) bytes."""
+    field0 = 0
+    for g, d in zip(groups_arr, groups):
+        H, W2 = d["H"], d["W2"]
+        g.H, g.W2, g.bias, g.dH, g.Z = H.data_ptr(), W2.data_ptr(), d["bias"].data_ptr(), None, None
+        g.ldh, g.ldw, g.lddh, g.ldz = H.stride(0), W2.stride(0), 0, 0
+        g.n_fields, g.field0 = W2.shape[0] // Cp, field0
+        field0 += g.n_fields
+    P.obs, P.prec_field, P.prec, P.counts, P.logw = obs.data_ptr(), N.ptr(prec_field), N.ptr(prec), N.ptr(counts), N.ptr(logw)
+    P.mean, P.spread, P.crps, P.pit, P.rank = N.ptr(mean), N.ptr(spread), N.ptr(crps), N.ptr(pit), N.ptr(rank)
+    P.sums, P.hist, P.status, P.work = sums.data_ptr(), hist.data_ptr(), status.data_ptr(), work.data_ptr()
+    P.ld_row, P.ld_field = obs.stride(0), obs.stride(1)
+    P.ld_prow, P.ld_pfield = (0, 0) if prec is None else (prec.stride(0), prec.stride(1))
+    P.ld_out, P.work_bytes = ld_out, work.numel() * work.element_size()
+    P.M, P.S, P.C, P.Cp, P.P = groups[0]["H"].shape[0], groups[0]["H"].shape[1], C_, Cp, n_patches
+    P.members, P.n_fields_total, P.unbiased, P.accumulate, P.pad_ = members, field0, int(bool(unbiased)), int(bool(accumulate)), 0
+
+
+def decode_member_verify(groups: Sequence[Dict], obs: torch.Tensor, C_: int, Cp: int, n_patches: int, members: int, prec_field: Optional[torch.Tensor] = None,
+                         prec: Optional[torch.Tensor] = None, counts: Optional[torch.Tensor] = None, logw: Optional[torch.Tensor] = None, unbiased: bool = True,
+                         accumulate: bool = False, maps: Sequence[str] = FIELD_VERIFY_MAPS, out: Optional[Dict[str, torch.Tensor]] = None,
+                         dtype: torch.dtype = torch.bfloat16) -> Dict[str, torch.Tensor]:
+    """sea_decode_member_verify: CRPS, PIT, rank, mean and spread of an ensemble at every cell of a dense observation of the decoded fields, and per
+    (history, field) the fp64 sums and the rank histogram (include/sea_hip.h states the formulas) — the members' decoded fields are never written.
+    groups, obs, prec_field, prec, counts as decode_member_gram; logw None or f32 [B * members] unnormalised log-weights; maps: the per-cell outputs to
+    produce, a subset of ("mean", "spread", "crps", "pit", "rank").  Returns a dict: the maps asked for, f32 (rank int32) [B, n_patches, n_fields, C]
+    (every element written), sums f64 [B, n_fields, 8], hist int64 [B, n_fields, members + 1], status int32 [B] — on the device; nothing is read back.
+    out: a dict of tensors to write into, by those names (a map given there is produced whether `maps` names it or not; its last dimension may be any
+    width >= C, the same for all maps); accumulate=True adds this call's sums and histograms onto out["sums"] and out["hist"], which are then required.
+    Everything is checked on the host before the launch."""
+    what = "decode_member_verify"
+    if dtype != torch.bfloat16:
+        raise ValueError(f"{what}: the fused launch is bf16 only, got {dtype}")
+    if not groups or len(groups) > N.DECODE_MSE_MAX_GROUPS:
+        raise ValueError(f"{what}: {len(groups)} groups; a launch carries 1 .. {N.DECODE_MSE_MAX_GROUPS}")
+    if Cp < 32 or Cp % 32 or not 1 <= C_ <= Cp:
+        raise ValueError(f"{what}: need Cp a multiple of 32 and 1 <= C <= Cp, got C = {C_}, Cp = {Cp}")
+    dev = groups[0]["H"].device
+    M, S = tuple(groups[0]["H"].shape) if groups[0]["H"].dim() == 2 else (0, 0)
+    if M < 1 or S < 8 or S % 8 or S > N.DECODE_MSE_MAX_S:
+        raise ValueError(f"{what}: H must be [M >= 1, S] with S a multiple of 8 up to {N.DECODE_MSE_MAX_S}, got {tuple(groups[0]['H'].shape)}")
+    n = members
+    if not isinstance(n, int) or isinstance(n, bool) or n < 1 or n > N.FIELD_VERIFY_MAX_N:
+        raise ValueError(f"{what}: members = {members!r} must be an integer in 1 .. {N.FIELD_VERIFY_MAX_N}")
+    if n_patches < 1 or M % (n_patches * n):
+        raise ValueError(f"{what}: {M} rows are not a multiple of n_patches * members = {n_patches} * {n}")
+    n_fields = 0
+    for i, d in enumerate(groups):
+        for name in ("H", "W2"):
+            t = d[name]
+            if t.dim() != 2 or t.stride(1) != 1:
+                raise ValueError(f"{what} group {i}: {name}: need a 2-D tensor with unit inner stride, got shape {tuple(t.shape)} strides {t.stride()}")
+            if t.dtype != dtype or t.device != dev or t.shape[1] != S or (name != "W2" and t.shape[0] != M):
+                raise ValueError(f"{what} group {i}: {name} must be a {dtype} [{'n_fields * Cp' if name == 'W2' else M}, {S}] tensor on {dev}, got "
+                                 f"{tuple(t.shape)} {t.dtype} on {t.device}")
+            if t.stride(0) % 8 or t.data_ptr() % 16:
+                raise ValueError(f"{what} group {i}: {name} needs a row stride that is a multiple of 8 and a 16-byte-aligned base (stride {t.stride(0)})")
+        W2, b = d["W2"], d["bias"]
+        if W2.shape[0] < Cp or W2.shape[0] % Cp:
+            raise ValueError(f"{what} group {i}: W2 has {W2.shape[0]} rows, not a multiple of Cp = {Cp}")
+        if b.dtype != torch.float32 or b.dim() != 1 or b.shape[0] != W2.shape[0] or not b.is_contiguous() or b.device != dev or b.data_ptr() % 16:
+            raise ValueError(f"{what} group {i}: bias must be a contiguous, 16-byte-aligned float32 [{W2.shape[0]}] on {dev}, got {tuple(b.shape)} {b.dtype}")
+        n_fields += W2.shape[0] // Cp
+    B = M // (n_patches * n)
+    if B > 65535:
+        raise ValueError(f"{what}: {B} histories; a launch carries up to 65535")
+    for name, t in (("obs", obs), ("prec", prec)):
+        if t is None and name == "prec":
+            continue
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or t.dim() != 3 or tuple(t.shape[:2]) != (B * n_patches, n_fields) or t.shape[2] < C_ or t.stride(2) != 1 \
+                or t.device != dev or t.stride(1) < C_ or (t.shape[0] > 1 and t.stride(0) < 0):
+            raise ValueError(f"{what}: {name} must be a float32 [{B * n_patches}, {n_fields}, >= {C_}] tensor with unit inner stride on {dev}, got "
+                             f"{(tuple(t.shape), t.dtype, t.stride(), str(t.device)) if torch.is_tensor(t) else type(t).__name__}")
+    if prec_field is not None and (not torch.is_tensor(prec_field) or prec_field.dtype != torch.float32 or tuple(prec_field.shape) != (n_fields,)
+                                   or not prec_field.is_contiguous() or prec_field.device != dev):
+        raise ValueError(f"{what}: prec_field must be None or a contiguous float32 [{n_fields}] tensor on {dev}")
+    if counts is not None and (not torch.is_tensor(counts) or counts.dtype != torch.int32 or counts.dim() != 1 or counts.shape[0] != n_patches
+                               or not counts.is_contiguous() or counts.device != dev):
+        raise ValueError(f"{what}: counts must be a contiguous int32 [{n_patches}] on {dev}")
+    if logw is not None and (not torch.is_tensor(logw) or logw.dtype != torch.float32 or tuple(logw.shape) != (B * n,) or not logw.is_contiguous() or logw.device != dev):
+        raise ValueError(f"{what}: logw must be None or a contiguous float32 [{B * n}] tensor on {dev}, got "
+                         f"{(tuple(logw.shape), logw.dtype, str(logw.device)) if torch.is_tensor(logw) else type(logw).__name__}")
+    maps = tuple(maps)
+    if any(k not in FIELD_VERIFY_MAPS for k in maps) or len(set(maps)) != len(maps):
+        raise ValueError(f"{what}: maps must be distinct names among {FIELD_VERIFY_MAPS}, got {maps!r}")
+    out = {} if out is None else out
+    fixed = {"sums": ((B, n_fields, N.VERIFY_SUMS), torch.float64), "hist": ((B, n_fields, n + 1), torch.int64), "status": ((B,), torch.int32)}
+    if not isinstance(out, dict) or any(k not in fixed and k not in FIELD_VERIFY_MAPS for k in out):
+        raise ValueError(f"{what}: out must be a dict with keys among {FIELD_VERIFY_MAPS + tuple(fixed)}")
+    widths = {t.shape[-1] for k, t in out.items() if k in FIELD_VERIFY_MAPS and torch.is_tensor(t) and t.dim() == 4}
+    if len(widths) > 1:
+        raise ValueError(f"{what}: the maps in out must share their last dimension, got {sorted(widths)}")
+    ld_out = widths.pop() if widths else C_
+    for k, t in out.items():
+        shape, dt = fixed[k] if k in fixed else ((B, n_patches, n_fields, ld_out), torch.int32 if k == "rank" else torch.float32)
+        if not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != dev or ld_out < C_:
+            raise ValueError(f"{what}: out[{k!r}] must be a contiguous {dt} {list(shape)} tensor on {dev} (maps: last dimension >= {C_})")
+    if accumulate and ("sums" not in out or "hist" not in out):
+        raise ValueError(f"{what}: accumulate=True adds onto out['sums'] and out['hist']: both are required")
+    N.require_gpu(groups[0]["H"], f"{what} hidden rows")   # every operand is on their device (checked above)
+    res = {k: out[k] if k in out else torch.empty(fixed[k][0], device=dev, dtype=fixed[k][1]) for k in fixed}
+    for k in FIELD_VERIFY_MAPS:
+        if k in out:
+            res[k] = out[k]
+        elif k in maps:
+            res[k] = torch.empty(B, n_patches, n_fields, ld_out, device=dev, dtype=torch.int32 if k == "rank" else torch.float32)
+    work = torch.empty(int(N.lib().sea_decode_member_verify_ws_bytes(B, n_patches, n_fields, n, Cp)), device=dev, dtype=torch.uint8)
+    arr, P = (N.SeaDecodeMseGroup * len(groups))(), N.SeaDecodeMemberVerify()
+    fill_decode_member_verify(arr, P, groups, obs, prec_field, prec, counts, logw, n_patches, n, C_, Cp, unbiased, accumulate, res.get("mean"), res.get("spread"),
+                              res.get("crps"), res.get("pit"), res.get("rank"), res["sums"], res["hist"], res["status"], work, ld_out)
+    N.check(N.lib().sea_decode_member_verify(arr, len(groups), C.byref(P), N.dtype_code(dtype), N.stream_ptr()), "sea_decode_member_verify")
+    return res

@@ -207,6 +207,16 @@ class MeshUnpatcher:
         return ops.unpatchify(std_fields.float(), layout, self.partitioner.padded_index_map, self._abs_scale, self._zero_shift, self.partitioner.x_coords.numel(),
                               point_slot=self.partitioner.point_slot if self.gather else None)
 
+    def unpatch_map(self, values: torch.Tensor, layout: str = "BPFC") -> torch.Tensor:
+        """A map of unit-free numbers per cell — FieldVerification's pit and rank — onto the mesh unchanged: inverse_scale_and_unpatch's launch with
+        scale 1 and shift 0.  values [T, P, F, C] (any real dtype; converted to float32) or [T, P, C, F] ("BPCF") -> float32 [T, N, F].  (crps and spread
+        are in the fields' units: unpatch_spread.)"""
+        N.require_gpu(values, "values")
+        if not hasattr(self, "_unit_scale"):
+            self._unit_scale, self._unit_shift = torch.ones_like(self._scale), torch.zeros_like(self._shift)
+        return ops.unpatchify(values.float(), layout, self.partitioner.padded_index_map, self._unit_scale, self._unit_shift, self.partitioner.x_coords.numel(),
+                              point_slot=self.partitioner.point_slot if self.gather else None)
+
 
     # ------------------------------------------------------------------ decoder + un-patchify without the padding
     def _prefix_plan(self, max_buckets: int):
@@ -313,6 +323,13 @@ class MeshProcessor:
         if self._unpatcher is None:
             raise ValueError("call patchify_and_scale first (it builds the partition)")
         return self._unpatcher.unpatch_spread(std_fields.to(self.device), layout=layout)
+
+    def unpatch_map(self, values: torch.Tensor, layout: str = "BPFC") -> torch.Tensor:
+        """A unit-free per-cell map (FieldVerification's pit or rank, [T, P, F, C] or with layout="BPCF" [T, P, C, F]) -> float32 [T, N, F], unchanged
+        (MeshUnpatcher.unpatch_map: scale 1, no shift)."""
+        if self._unpatcher is None:
+            raise ValueError("call patchify_and_scale first (it builds the partition)")
+        return self._unpatcher.unpatch_map(values.to(self.device), layout=layout)
 
     def sensor_set(self, decoder, points, fields):
         """Point sensors on the mesh (mesh point ids and field ids) as a SensorSet for `decoder`, with scale_values / scale_sigma for readings in
