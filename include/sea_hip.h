@@ -1454,6 +1454,57 @@ typedef struct {
 int64_t sea_decode_member_verify_ws_bytes(int B, int P, int n_fields_total, int members, int Cp);   /* -1 for sizes the entry point refuses */
 int sea_decode_member_verify(const SeaDecodeMseGroup* groups, int n_groups, const SeaDecodeMemberVerify* p, int dtype, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * The forecast products of an ensemble beyond mean and variance: weighted QUANTILE maps (median, a 5 % / 95 % band, the envelope) and EXCEEDANCE
+ * probability maps of the decoded fields, in ONE launch, without the members' decoded fields ever existing in memory.  Operands H, W2, bias, ldh, ldw,
+ * n_fields, field0 of SeaDecodeMseGroup and the row order exactly as in sea_decode_member_verify: row m = (b * members + j) * P + p of H is member j of
+ * history b; B = M / (P * members); F = n_fields_total.
+ *     y_j[b, p, f, c] = sum_s H[m, s] W2[(f - field0) Cp + c, s] + bias[(f - field0) Cp + c]        (fp32 accumulation from bf16 MFMAs; never stored;
+ *                       compared as the f32 values they are; the decode is sea_decode_member_verify's code: a cell has the bits of the cell it scores)
+ * w: f32 [B * members], normalised per history by the caller, as in sea_decode_member_moments; NULL: equal weights (1 each — the definitions below only
+ * see ratios of weights).  A member with w <= 0 or NaN is DEAD: it is passed over by selects, and NaN or Inf in its hidden row reaches nothing.
+ *     W       = sum of w_j over the live members, in fp64, one chain over j ascending
+ *     below_i = sum of w_j over the live j with (y_j, j) < (y_i, i)     for a live member i; fp64, accumulated over j ascending (the walk of
+ *               sea_ensemble_verify's CRPS); cum_i = below_i + w_i
+ * Weighted quantile at a level tau in [0, 1], the inverted weighted empirical distribution function:
+ *     q_tau = min { y_i : i live, cum_i >= tau * W }      both sides fp64, tau * W ONE fp64 product of the f32 level
+ *     and the largest live value when no live member qualifies (by rounding, at tau = 1).  tau = 0 gives the smallest live value.  q_tau is the decoded
+ *     value of one member bit for bit (an f32 min / max over lanes: the result does not depend on the order); the maps are non-decreasing in tau; with
+ *     equal weights this is numpy.quantile(..., method="inverted_cdf").
+ * Exceedance probability of a threshold thr[t, f] (f32 [n_thr, F], per field, in the decoder's scaled units):
+ *     e_t = (sum of w_i over the live i with y_i > thr[t, f]) / W      strict >; fp64 through a fixed xor butterfly over the lanes; stored as f32
+ * Cells: a column at or beyond counts[p] (clamped to [0, C]; NULL: C) up to ld is dead: 0 in every map — EVERY element of quant and exceed is written.
+ * A live cell where a live member's value is not finite gives NaN in all its maps and in no other cell.  A history without a live member gives 0
+ * everywhere.  A threshold that is NaN gives NaN in that map's live cells.
+ *     quant  f32 [n_levels, B * P, F, ld]: level k's map starts at quant + k * ld_map, element (bp, f, c) at (bp * F + f) * ld + c
+ *     exceed f32 [n_thr, B * P, F, ld]:    threshold t's map starts at exceed + t * ld_map
+ * One launch: a workgroup of 8 waves per (history, patch, field, chunk of 512 columns) — sea_decode_member_verify's grid and walk — decodes 32 columns
+ * at a time, stages the values in LDS as [column][member]; a wave reads out a column at a time with a member (two above 64) per lane; thread k stores
+ * column k of every map.  The O(N^2) walk for below_i runs only when n_levels > 0 (a branch uniform over the launch).  Nothing is reduced across
+ * workgroups and there are no atomics: two runs give the same bits, a history's outputs are those of a call holding it alone, and a cell's outputs
+ * depend on its own column only.
+ * Requirements: dtype SEA_BF16 (SEA_F32: SEA_EUNSUPPORTED); M >= 1; S a multiple of 8, at most 640 (above: SEA_EUNSUPPORTED), padded by masking; Cp a
+ * multiple of 32, 1 <= C <= Cp; P >= 1; members >= 1 (above 128: SEA_EUNSUPPORTED); M % (P * members) == 0; at most 65535 histories and fields;
+ * 0 <= n_levels, n_thr <= SEA_QUANTILE_MAX_LEVELS, not both 0; every level finite and in [0, 1]; quant non-NULL when n_levels > 0, thr and exceed
+ * non-NULL when n_thr > 0; ld >= C, ld_map >= B * P * F * ld; all f32 and int32 buffers 4-byte aligned; per group H, W2, bias non-NULL and 16-byte
+ * aligned, ldh, ldw multiples of 8 and >= S; the groups' field ranges cover 0 .. F-1 exactly once; 1 <= n_groups <= SEA_DECODE_MSE_MAX_GROUPS.
+ * Returns -1, with the entry point and the offending group named in sea_last_error(), otherwise; nothing touches a device before the checks pass.
+ * Notes the form "decode.member_quantiles" (a = the padded hidden width, b = the dynamic LDS bytes).
+ * (An addition to ABI version 8.  The struct is not in sea_struct_sizes(): sizeof(SeaDecodeMemberQuantiles) is 128.)
+ */
+#define SEA_QUANTILE_MAX_LEVELS 8
+typedef struct {
+    const float* w;            /* f32 [B * members], or NULL (equal weights) */
+    const int32_t* counts;     /* device int32 [P] or NULL */
+    const float* thr;          /* f32 [n_thr, F], or NULL when n_thr == 0 */
+    float* quant;              /* f32 [n_levels, B * P, F, ld] through ld_map, or NULL when n_levels == 0 */
+    float* exceed;             /* f32 [n_thr, B * P, F, ld] through ld_map, or NULL when n_thr == 0 */
+    float level[SEA_QUANTILE_MAX_LEVELS];   /* the first n_levels are read */
+    int64_t ld, ld_map;        /* floats between two rows of a map, and between two maps */
+    int32_t n_levels, n_thr, M, S, C, Cp, P, members, n_fields_total, pad_;
+} SeaDecodeMemberQuantiles;  /* 128 bytes */
+int sea_decode_member_quantiles(const SeaDecodeMseGroup* groups, int n_groups, const SeaDecodeMemberQuantiles* p, int dtype, void* stream);
+
 /* Tuning aid: register a device buffer of n_steps * 64 8-byte words that the persistent form fills with 100 MHz clock stamps of its hand-offs
  * (tools/kv_persist_timeline.py); NULL switches it off. */
 void sea_kv_debug_stamps(unsigned long long* buf);

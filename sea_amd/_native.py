@@ -348,6 +348,17 @@ class SeaDecodeMemberVerify(C.Structure):
                 ("accumulate", _i32), ("pad_", _i32)]
 
 
+QUANTILE_MAX_LEVELS = 8      # levels, and thresholds, one launch of sea_decode_member_quantiles carries
+
+
+class SeaDecodeMemberQuantiles(C.Structure):
+    # sea_decode_member_quantiles (not in ABI_STRUCTS, like its siblings; tests/test_ensemble_quantiles_cpu.py checks the size the header states)
+    _fields_ = [("w", _vp), ("counts", _vp), ("thr", _vp), ("quant", _vp), ("exceed", _vp), ("level", C.c_float * QUANTILE_MAX_LEVELS),
+                ("ld", _i64), ("ld_map", _i64),
+                ("n_levels", _i32), ("n_thr", _i32), ("M", _i32), ("S", _i32), ("C", _i32), ("Cp", _i32), ("P", _i32), ("members", _i32),
+                ("n_fields_total", _i32), ("pad_", _i32)]
+
+
 ENKF_MAX_N = 128             # members per history of sea_enkf_transform / sea_ensemble_mix
 SENSOR_TILE = 32             # sensors per W2 tile of sea_decode_sensor_sse: every (group, patch) segment of a SensorSet is padded to a multiple of it
 SENSOR_MAX_PATCHES = 65535   # observed patches one launch of sea_decode_sensor_sse carries (a grid dimension)
@@ -355,6 +366,7 @@ MEMBER_MOMENTS_CHUNK = 128   # members one workgroup of sea_decode_member_moment
 VERIFY_MAX_N = 128           # members per history of sea_ensemble_verify
 VERIFY_SUMS = 8              # fp64 sums per history of sea_ensemble_verify
 FIELD_VERIFY_MAX_N = 128     # members per history of sea_decode_member_verify
+QUANTILE_MAX_N = 128         # members per history of sea_decode_member_quantiles
 RESAMPLE_MAX_N = 4096      # members per history of sea_resample_systematic
 
 MAX_WGRAD_GROUPS = 32
@@ -488,6 +500,8 @@ def lib() -> C.CDLL:
     L.sea_decode_member_verify.restype = C.c_int
     L.sea_decode_member_verify_ws_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
     L.sea_decode_member_verify_ws_bytes.restype = _i64
+    L.sea_decode_member_quantiles.argtypes = [C.POINTER(SeaDecodeMseGroup), C.c_int, C.POINTER(SeaDecodeMemberQuantiles), C.c_int, _vp]
+    L.sea_decode_member_quantiles.restype = C.c_int
     for name in ("sea_attention_bwd", "sea_wgrad_grouped", "sea_transpose_weights", "sea_rownorm_bwd", "sea_silu_outer_bwd", "sea_ib_bwd",
                  "sea_silu_outer_bwd_dc", "sea_ib_bwd_dc"):
         getattr(L, name).restype = C.c_int
@@ -519,7 +533,7 @@ EXPORTED_SYMBOLS = (
     "sea_mse_fwd_bwd", "sea_relative_mse", "sea_adamw_flat", "sea_grad_norm_ctl", "sea_adamw_flat_ctl",
     "sea_wgrad_grouped", "sea_transpose_weights", "sea_rownorm_bwd", "sea_silu_outer_bwd", "sea_ib_bwd",
     "sea_attention_bwd", "sea_dropout_mask", "sea_run_list", "sea_run_list_steps", "sea_unpatchify", "sea_gemm_rownorm", "sea_exchange_tail", "sea_patchify", "sea_silu_outer_ib", "sea_mlp_fc1_ln_gelu", "sea_mlp_fc2_proj_norm", "sea_kv_rollout", "sea_kv_arena_words", "sea_kv_debug_stamps",
-    "sea_kv_cache_fill", "sea_kv_cache_fork", "sea_kv_cache_gather", "sea_decode_mse", "sea_decode_member_sse", "sea_decode_member_moments", "sea_decode_sensor_sse", "sea_decode_sensor_grad", "sea_resample_systematic", "sea_enkf_transform", "sea_enkf_transform_gram", "sea_decode_member_gram", "sea_ensemble_mix", "sea_ensemble_verify", "sea_ensemble_verify_ws_bytes", "sea_decode_member_verify", "sea_decode_member_verify_ws_bytes",
+    "sea_kv_cache_fill", "sea_kv_cache_fork", "sea_kv_cache_gather", "sea_decode_mse", "sea_decode_member_sse", "sea_decode_member_moments", "sea_decode_sensor_sse", "sea_decode_sensor_grad", "sea_resample_systematic", "sea_enkf_transform", "sea_enkf_transform_gram", "sea_decode_member_gram", "sea_ensemble_mix", "sea_ensemble_verify", "sea_ensemble_verify_ws_bytes", "sea_decode_member_verify", "sea_decode_member_verify_ws_bytes", "sea_decode_member_quantiles",
     "sea_gemm_fewrows", "sea_qkv_rope_fewrows", "sea_row_chain", "sea_row_chain_riders", "sea_gemm_adaln", "sea_mlp_block", "sea_adaln_qkv", "sea_splitk_finish",
     "sea_encoder_block_ws_floats", "sea_encoder_block_fwd", "sea_encoder_block_bwd",
     "sea_silu_outer_bwd_dc", "sea_silu_outer_bwd_dc_ws_floats", "sea_ib_bwd_dc",

@@ -36,6 +36,7 @@
 // wave per SIMD (DESIGN.md section 7 has the measurements).
 #include "sea_common.hpp"
 #include "verify_score.hpp"   // sea_decode_member_verify scores a cell as verify_kernel scores a sensor
+#include "quantile_select.hpp"   // sea_decode_member_quantiles reads a column out
 
 typedef short dm_s16x4 __attribute__((ext_vector_type(4)));
 
@@ -2099,5 +2100,260 @@ extern "C" int sea_decode_member_verify(const SeaDecodeMseGroup* groups, int n_g
     else member_verify_dispatch<2>(L, grid, s);
     member_verify_finish_kernel<<<dim3((unsigned)B), dim3(256), 0, s>>>(P, mv_chunks(P.Cp), L.words);
     SEA_CHECK_LAUNCH("sea_decode_member_verify");
+    return SEA_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------------------------
+// sea_decode_member_quantiles: weighted quantile maps and exceedance-probability maps of an ensemble's decoded fields (include/sea_hip.h states the
+// definitions).  ONE launch with decode_member_verify_kernel's grid — a workgroup of 8 waves per (history, patch, field, chunk of MV_CHUNK tiles) —
+// and its decode, line for line: dm_load_tile / dm_store_tile, the bias in the accumulator, the acc0 + acc1 store to V[column][member] at the
+// 129-float stride.  A cell decoded here has the bits of the cell sea_decode_member_verify scores.  Per tile:
+//   a  the waves decode their 16 members and write the value image;
+//   b  wave w reads out the columns w, w + 8, w + 16, w + 24 (qs_column_wave, quantile_select.hpp: the walk for the weight below every member only
+//      when the launch has levels; per level a select and an f32 wave-min; per threshold one fp64 butterfly); lane 0 files the column's
+//      n_levels + n_thr results in res_s; a column at or beyond the patch's valid count is passed over;
+//   c  thread k stores column k of every map — one writer per element, 128-byte segments — while the next tile of W2 goes to its LDS image.
+// Three barriers per tile.  Columns at or beyond the walked tiles are filled with 0 before the walk.  Nothing is reduced across workgroups: there is no
+// finish launch, no workspace and no atomic of any kind.
+// LDS at SP = 640: 2 x 41984 (W2 images) + 16512 (V) dynamic, 3.8 kB static (weights, live flags, results, thresholds): 104 kB, one workgroup per CU.
+struct MemberQuantLaunch {
+    SeaDecodeMseGroup g[SEA_DECODE_MSE_MAX_GROUPS];
+    SeaDecodeMemberQuantiles p;
+    int n_groups;
+};
+
+template <int SP, int V>
+__global__ __launch_bounds__(MV_NT) void decode_member_quantiles_kernel(const MemberQuantLaunch L) {
+#pragma clang fp reassociate(off)
+    constexpr int NW = MV_NW;
+    constexpr int NT = MV_NT;
+    constexpr int KS = SP / 32;
+    constexpr int PITCH = SP * 2 + DM_PAD;
+    constexpr int TILE = DM_TC * PITCH;
+    constexpr int NCH = SP * 4 / NT;
+    constexpr int VP = MV_VP;
+    static_assert(NCH * NT == DM_TC * (SP / 8), "whole chunks per thread");
+    extern __shared__ __attribute__((aligned(16))) char smem[];   // 2 tile images; the value image [32][VP]
+    float* Vs = reinterpret_cast<float*>(smem + 2 * TILE);
+    __shared__ double w_s[VF_MAX_N];
+    __shared__ int live_s[VF_MAX_N];
+    __shared__ float res_s[DM_TC][QS_MAX_OUT];
+    __shared__ float thr_s[SEA_QUANTILE_MAX_LEVELS];
+
+    const SeaDecodeMemberQuantiles& P = L.p;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), li = lane & 15, lg = lane >> 4;
+    const int S = P.S, C = P.C, Cp = P.Cp, N = P.members, F = P.n_fields_total, nl = P.n_levels, nt = P.n_thr;
+    const int bp = blockIdx.x, fg = blockIdx.y, ck = blockIdx.z;   // the field and the chunk of its tiles this workgroup reads out
+    const int b = bp / P.P, patch = bp - b * P.P;
+    const int64_t ld = P.ld;
+    const int64_t obase = ((int64_t)bp * F + fg) * ld;
+
+    int lim = C;   // valid columns of this patch: [0, lim) — uniform over the workgroup
+    if (P.counts != nullptr) {
+        const int cnt = P.counts[patch];
+        lim = cnt < 0 ? 0 : (cnt > C ? C : cnt);
+    }
+    const int tpf = (lim + DM_TC - 1) / DM_TC;   // tiles of a field that hold valid columns
+    const int tb = ck * MV_CHUNK, te = tpf < tb + MV_CHUNK ? tpf : tb + MV_CHUNK;   // this workgroup's tiles: [tb, te)
+
+    // the weights of the history: a member with w <= 0 or NaN is dead
+    int alive = 0;
+    if (tid < N) {
+        const float wv = P.w != nullptr ? P.w[(int64_t)b * N + tid] : 1.f;
+        alive = wv > 0.f ? 1 : 0;   // false for NaN
+        w_s[tid] = alive ? (double)wv : 0.0;
+        live_s[tid] = alive;
+    }
+    if (tid < nt) thr_s[tid] = P.thr[(int64_t)tid * F + fg];
+    const int n_live = __syncthreads_count(alive);
+    const bool empty = n_live == 0;
+    if (ck == 0) {   // the columns no tile walks (all of them when the history has no live member or the patch no valid column): 0
+        const int c0 = (empty || tpf == 0) ? 0 : tpf * DM_TC;
+        for (int64_t c = c0 + tid; c < ld; c += NT) {
+            const int64_t at = obase + c;
+            for (int k = 0; k < nl; ++k) P.quant[k * P.ld_map + at] = 0.f;
+            for (int t = 0; t < nt; ++t) P.exceed[t * P.ld_map + at] = 0.f;
+        }
+    }
+    if (empty || te <= tb) return;   // uniform: nothing to read out in this chunk
+    double W = 0.0;
+    for (int j = 0; j < N; ++j) W += w_s[j];   // one chain, j ascending; a dead member adds +0
+
+    const int j0 = wave * 16;
+    const bool active = j0 < N;                 // uniform over the wave
+    const int jm = j0 + li;
+    const int64_t m = ((int64_t)b * N + (jm < N ? jm : 0)) * P.P + patch;
+
+    int gsel = 0;   // the group that holds the field: the entry point has checked that exactly one does
+    for (int gi = 1; gi < L.n_groups; ++gi) gsel = (fg >= L.g[gi].field0 && fg < L.g[gi].field0 + L.g[gi].n_fields) ? gi : gsel;
+    const SeaDecodeMseGroup& G = L.g[gsel];
+    const int j = fg - G.field0;   // the field inside its group
+    const __bf16* H = static_cast<const __bf16*>(G.H);
+    const __bf16* W2 = static_cast<const __bf16*>(G.W2);
+    uint4 hf[KS];
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+        const int s = ks * 32 + 8 * lg;
+        // a row at or beyond N repeats member 0's: its values are stored to V and never read.  The k-step that straddles S loads column 0 where
+        // s >= S and selects zeros (the tile image is zero there, but 0 * NaN is not)
+        if (ks * 32 + 32 <= S) {
+            hf[ks] = *reinterpret_cast<const uint4*>(H + m * G.ldh + s);
+        } else {
+            const uint4 v = *reinterpret_cast<const uint4*>(H + m * G.ldh + (s < S ? s : 0));
+            hf[ks] = s < S ? v : make_uint4(0u, 0u, 0u, 0u);
+        }
+    }
+    const int n_tiles = te - tb, t0 = j * tpf + tb;   // this chunk's tiles among the group's
+    uint4 wr[NCH];
+    dm_load_tile<SP, NT>(wr, W2, G.ldw, S, Cp, tpf, t0, tid);
+    dm_store_tile<SP, NT>(wr, smem, tid);
+    __syncthreads();
+
+    for (int t = 0; t < n_tiles; ++t) {
+        const char* buf = smem + (t & 1) * TILE;
+        const int cb = (tb + t) * DM_TC;
+
+        // a: decode into the value image
+        if (active) {
+            f32x4 acc[2][2];
+#pragma unroll
+            for (int sub = 0; sub < 2; ++sub) {
+                const float bv = G.bias[j * Cp + cb + sub * 16 + li];
+                acc[sub][0] = f32x4{bv, bv, bv, bv};
+                acc[sub][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {
+                if (ks * 32 < S) {
+#pragma unroll
+                    for (int sub = 0; sub < 2; ++sub) {
+                        const uint4 wv = *reinterpret_cast<const uint4*>(buf + (sub * 16 + li) * PITCH + (ks * 4 + lg) * 16);
+                        mma16<__bf16>(hf[ks], wv, acc[sub][ks & 1]);
+                    }
+                }
+            }
+#pragma unroll
+            for (int sub = 0; sub < 2; ++sub) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r)   // plain C++: the first reader of an MFMA result must be an instruction the compiler sees
+                    Vs[(sub * 16 + li) * VP + j0 + 4 * lg + r] = acc[sub][0][r] + acc[sub][1][r];
+            }
+        }
+        __syncthreads();
+        if (t + 1 < n_tiles) dm_load_tile<SP, NT>(wr, W2, G.ldw, S, Cp, tpf, t0 + t + 1, tid);   // in flight behind b
+
+        // b: a column per wave at a time
+        for (int cl = wave; cl < DM_TC; cl += NW) {
+            if (cb + cl >= lim) continue;   // the same word in every lane: a dead column, stage c writes its zeros
+            qs_column_wave<V>(Vs + cl * VP, w_s, live_s, N, lane, W, P.level, nl, thr_s, nt, res_s[cl]);
+        }
+        __syncthreads();
+
+        // c: thread k stores column k of every map
+        if (tid < DM_TC) {
+            const int c = cb + tid;
+            if (c < ld) {
+                const int64_t at = obase + c;
+                const bool on = c < lim;
+                for (int k = 0; k < nl; ++k) P.quant[k * P.ld_map + at] = on ? res_s[tid][k] : 0.f;
+                for (int q = 0; q < nt; ++q) P.exceed[q * P.ld_map + at] = on ? res_s[tid][nl + q] : 0.f;
+            }
+        }
+        if (t + 1 < n_tiles) dm_store_tile<SP, NT>(wr, smem + ((t + 1) & 1) * TILE, tid);
+        __syncthreads();
+    }
+}
+
+template <int SP, int V>
+static void member_quantiles_launch(const MemberQuantLaunch& L, dim3 grid, hipStream_t s) {
+    constexpr int lds = mv_lds_bytes<SP>();
+    static bool set_on[64] = {false};   // per device: the dynamic part is 100 kB at SP = 640, above the 64 kB a kernel gets without the attribute
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = -1;
+    if (dev < 0 || !set_on[dev]) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(decode_member_quantiles_kernel<SP, V>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        if (dev >= 0) set_on[dev] = true;
+    }
+    decode_member_quantiles_kernel<SP, V><<<grid, dim3(MV_NT), lds, s>>>(L);
+    sea_note_form("decode.member_quantiles", SP, lds);
+}
+
+template <int V>
+static void member_quantiles_dispatch(const MemberQuantLaunch& L, dim3 grid, hipStream_t s) {
+    if (L.p.S <= 128) member_quantiles_launch<128, V>(L, grid, s);
+    else if (L.p.S <= 256) member_quantiles_launch<256, V>(L, grid, s);
+    else if (L.p.S <= 384) member_quantiles_launch<384, V>(L, grid, s);
+    else if (L.p.S <= 512) member_quantiles_launch<512, V>(L, grid, s);
+    else member_quantiles_launch<640, V>(L, grid, s);
+}
+
+extern "C" int sea_decode_member_quantiles(const SeaDecodeMseGroup* groups, int n_groups, const SeaDecodeMemberQuantiles* p, int dtype, void* stream) {
+    SEA_REQUIRE(groups != nullptr && p != nullptr, "sea_decode_member_quantiles: null argument table");
+    SEA_REQUIRE(n_groups >= 1 && n_groups <= SEA_DECODE_MSE_MAX_GROUPS, "sea_decode_member_quantiles: n_groups=%d outside 1..%d", n_groups, SEA_DECODE_MSE_MAX_GROUPS);
+    SEA_REQUIRE(dtype == SEA_F32 || dtype == SEA_BF16, "sea_decode_member_quantiles: bad dtype %d", dtype);
+    if (dtype != SEA_BF16) {
+        sea_set_error("sea_decode_member_quantiles: unsupported: bf16 only (the fp32 decoder composes the decode and a sort)");
+        return SEA_EUNSUPPORTED;
+    }
+    const SeaDecodeMemberQuantiles& P = *p;
+    SEA_REQUIRE(P.n_levels >= 0 && P.n_levels <= SEA_QUANTILE_MAX_LEVELS && P.n_thr >= 0 && P.n_thr <= SEA_QUANTILE_MAX_LEVELS && P.n_levels + P.n_thr >= 1,
+                "sea_decode_member_quantiles: n_levels=%d and n_thr=%d must lie in 0..%d and not both be 0", P.n_levels, P.n_thr, SEA_QUANTILE_MAX_LEVELS);
+    for (int k = 0; k < P.n_levels; ++k)
+        SEA_REQUIRE(P.level[k] >= 0.f && P.level[k] <= 1.f, "sea_decode_member_quantiles: level[%d]=%g must be finite and lie in [0, 1]", k, (double)P.level[k]);
+    SEA_REQUIRE((P.n_levels == 0 || P.quant != nullptr) && (P.n_thr == 0 || (P.thr != nullptr && P.exceed != nullptr)),
+                "sea_decode_member_quantiles: null pointer (quant is required with levels, thr and exceed with thresholds; w and counts may be NULL)");
+    SEA_REQUIRE(P.M >= 1, "sea_decode_member_quantiles: M=%d must be positive", P.M);
+    SEA_REQUIRE(P.S >= 8 && P.S % 8 == 0, "sea_decode_member_quantiles: S=%d must be a positive multiple of 8", P.S);
+    SEA_REQUIRE(P.Cp >= 32 && P.Cp % 32 == 0, "sea_decode_member_quantiles: Cp=%d must be a positive multiple of 32", P.Cp);
+    SEA_REQUIRE(P.C >= 1 && P.C <= P.Cp, "sea_decode_member_quantiles: C=%d must lie in 1..Cp=%d", P.C, P.Cp);
+    SEA_REQUIRE(P.P >= 1, "sea_decode_member_quantiles: P=%d must be positive", P.P);
+    SEA_REQUIRE(P.members >= 1, "sea_decode_member_quantiles: members=%d must be positive", P.members);
+    SEA_REQUIRE((int64_t)P.M % ((int64_t)P.P * P.members) == 0, "sea_decode_member_quantiles: M=%d is not a multiple of P * members = %d * %d", P.M, P.P, P.members);
+    SEA_REQUIRE(P.n_fields_total >= 1 && P.n_fields_total <= 65535, "sea_decode_member_quantiles: n_fields_total=%d outside 1..65535 (a grid dimension)", P.n_fields_total);
+    const int64_t BP = (int64_t)P.M / P.members;   // (history, patch) pairs
+    const int64_t B = BP / P.P;
+    SEA_REQUIRE(BP <= 0x7fffffffLL && B <= 65535, "sea_decode_member_quantiles: %lld histories; a launch carries up to 65535", (long long)B);
+    SEA_REQUIRE(P.ld >= P.C && P.ld <= 0x7fffffffLL && P.ld_map >= BP * P.n_fields_total * P.ld,
+                "sea_decode_member_quantiles: ld=%lld must cover C=%d, and ld_map=%lld a whole map of %lld floats", (long long)P.ld, P.C, (long long)P.ld_map,
+                (long long)(BP * P.n_fields_total * P.ld));
+    SEA_REQUIRE(sea_aligned4(P.w) && sea_aligned4(P.counts) && sea_aligned4(P.thr) && sea_aligned4(P.quant) && sea_aligned4(P.exceed),
+                "sea_decode_member_quantiles: misaligned pointer (f32 and int32 buffers need 4 bytes)");
+    int64_t covered = 0;
+    for (int g = 0; g < n_groups; ++g) {
+        const SeaDecodeMseGroup& G = groups[g];
+        SEA_REQUIRE(G.H != nullptr && G.W2 != nullptr && G.bias != nullptr, "sea_decode_member_quantiles: group %d: null pointer", g);
+        SEA_REQUIRE(sea_aligned16(G.H) && sea_aligned16(G.W2) && sea_aligned16(G.bias), "sea_decode_member_quantiles: group %d: pointers must be 16-byte aligned", g);
+        SEA_REQUIRE(G.ldh >= P.S && G.ldh % 8 == 0 && G.ldw >= P.S && G.ldw % 8 == 0,
+                    "sea_decode_member_quantiles: group %d: row strides ldh=%d ldw=%d must cover S=%d and be multiples of 8", g, G.ldh, G.ldw, P.S);
+        SEA_REQUIRE(G.n_fields >= 1 && G.field0 >= 0 && (int64_t)G.field0 + G.n_fields <= P.n_fields_total,
+                    "sea_decode_member_quantiles: group %d: n_fields=%d, field0=%d outside the %d fields", g, G.n_fields, G.field0, P.n_fields_total);
+        SEA_REQUIRE((int64_t)G.n_fields * P.Cp <= 0x7fffffffLL / 2, "sea_decode_member_quantiles: group %d: too many output columns", g);
+        for (int h = 0; h < g; ++h)
+            SEA_REQUIRE(G.field0 >= groups[h].field0 + groups[h].n_fields || groups[h].field0 >= G.field0 + G.n_fields,
+                        "sea_decode_member_quantiles: group %d: its fields overlap those of group %d (a cell is read out once)", g, h);
+        covered += G.n_fields;
+    }
+    SEA_REQUIRE(covered == P.n_fields_total, "sea_decode_member_quantiles: the groups cover %lld of the %d fields (every field needs exactly one group)",
+                (long long)covered, P.n_fields_total);
+    if (P.S > 640) {
+        sea_set_error("sea_decode_member_quantiles: unsupported: hidden width S=%d above 640", P.S);
+        return SEA_EUNSUPPORTED;
+    }
+    if (P.members > VF_MAX_N) {
+        sea_set_error("sea_decode_member_quantiles: unsupported: members=%d above %d", P.members, VF_MAX_N);
+        return SEA_EUNSUPPORTED;
+    }
+    SEA_REQUIRE(mv_chunks(P.Cp) <= 65535, "sea_decode_member_quantiles: Cp=%d has too many column chunks", P.Cp);
+
+    MemberQuantLaunch L;
+    memset(&L, 0, sizeof(L));
+    for (int g = 0; g < n_groups; ++g) L.g[g] = groups[g];
+    L.p = P;
+    L.n_groups = n_groups;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)BP, (unsigned)P.n_fields_total, (unsigned)mv_chunks(P.Cp));
+    if (P.members <= 64) member_quantiles_dispatch<1>(L, grid, s);
+    else member_quantiles_dispatch<2>(L, grid, s);
+    SEA_CHECK_LAUNCH("sea_decode_member_quantiles");
     return SEA_OK;
 }

@@ -52,6 +52,11 @@ Whether the ensemble is any good is read at the same sensors (SensorVerification
     verify = FieldVerification(decoder, n_patches, members=n, counts=counts, sigma=sigma_cell)
     scores = verify(y, snapshot, precision, into=scores)                       # crps, pit, rank, mean, spread maps [B, P, n_fields, n_inp]
     scores.spread_skill, scores.pooled().suggested_inflation                    # [B, n_fields] per field; pooled(): [B] over the mesh
+
+What is published as the forecast besides mean and variance (EnsembleQuantiles: sea_decode_member_quantiles, one launch, the members' fields never written):
+
+    products = EnsembleQuantiles(decoder, n_patches, members=n, levels=(0.05, 0.5, 0.95), thresholds=unpatcher.scale_thresholds([[0.5, 2.0]]), counts=counts)
+    quant, exceed = products(y, logw)                                           # [3, B, P, n_fields, n_inp] quantile maps, [1, B, P, n_fields, n_inp] P(field > threshold)
 """
 from __future__ import annotations
 
@@ -1259,3 +1264,137 @@ class FieldVerification(_FieldObserver):
         return FieldScores(**{k: r.get(k) for k in FIELD_MAPS}, sums=r["sums"], hist=r["hist"], status=r["status"])
 
     verify = __call__
+
+
+# ------------------------------------------------------------------------------------------------ quantile and exceedance maps
+QUANTILES_FUSED_MIN_ROWS = 4096   # fused=None: the fused launch from this many decoder rows (B * members * n_patches) on — the smallest measured size
+
+
+def _composed_quantiles(Y, w, levels, thr):
+    """sea_decode_member_quantiles' maps from decoded members, by a stable sort and cumulative weights in fp64 (include/sea_hip.h states the definitions):
+    Y [B, members, P, F, C] (any float dtype, compared as given; CPU or device), w None (equal weights) or [B, members] (a member with w <= 0 or NaN
+    is dead), levels a sequence of numbers in [0, 1] (rounded to float32 first, as the launch carries them), thr None or [T, F].  Returns (quant
+    [Q, B, P, F, C] in Y's dtype or None, exceed float32 [T, B, P, F, C] or None).  Nothing is read back."""
+    B, n, P, F, C_ = Y.shape
+    dev, f64 = Y.device, torch.float64
+    w64 = torch.ones(B, n, device=dev, dtype=f64) if w is None else w.detach().reshape(B, n).to(f64)
+    live = w64 > 0                                                       # false for NaN
+    w64 = torch.where(live, w64, torch.zeros((), device=dev, dtype=f64))
+    W = w64.sum(1)
+    some = (W > 0).view(1, B, 1, 1, 1)
+    lv = live.view(B, n, 1, 1, 1)
+    bad = (lv & ~torch.isfinite(Y)).any(1).unsqueeze(0)                  # [1, B, P, F, C]: a live member's value is not finite
+    quant = exceed = None
+    if len(levels):
+        x = torch.where(lv, Y, torch.full((), float("inf"), device=dev, dtype=Y.dtype))   # dead members go behind every live one
+        xs, idx = torch.sort(x, dim=1, stable=True)                      # the order (value, member index)
+        cum = w64.view(B, n, 1, 1, 1).expand(B, n, P, F, C_).gather(1, idx).cumsum(1)
+        ok_live = lv.expand(B, n, P, F, C_).gather(1, idx)
+        pos_all = torch.arange(n, device=dev).view(1, n, 1, 1, 1)
+        last = (live.sum(1) - 1).clamp_min(0).view(B, 1, 1, 1)
+        tau = torch.tensor([float(v) for v in levels], dtype=torch.float32).to(f64).tolist()   # host floats: the float32 levels, exactly
+        maps = []
+        for k in range(len(levels)):
+            tw = (tau[k] * W).view(B, 1, 1, 1, 1)
+            pos = torch.where(ok_live & (cum >= tw), pos_all, torch.full((), n, device=dev, dtype=pos_all.dtype)).amin(1)
+            pos = torch.where(pos == n, last.expand_as(pos), pos)        # nobody qualifies (rounding at tau = 1): the largest live value
+            maps.append(xs.gather(1, pos.unsqueeze(1)).squeeze(1))
+        quant = torch.stack(maps)
+        quant = torch.where(bad, torch.full((), float("nan"), device=dev, dtype=quant.dtype), quant)
+        quant = torch.where(some, quant, torch.zeros((), device=dev, dtype=quant.dtype))
+    if thr is not None:
+        t = thr.detach().to(dev)
+        over = lv.unsqueeze(0) & (Y.unsqueeze(0) > t.to(Y.dtype).view(-1, 1, 1, 1, F, 1))
+        e = torch.where(over, w64.view(1, B, n, 1, 1, 1), torch.zeros((), device=dev, dtype=f64)).sum(2) / W.clamp_min(1e-300).view(1, B, 1, 1, 1)
+        e = torch.where(bad | torch.isnan(t).view(-1, 1, 1, F, 1), torch.full((), float("nan"), device=dev, dtype=f64), e)
+        exceed = torch.where(some, e, torch.zeros((), device=dev, dtype=f64)).to(torch.float32)
+    return quant, exceed
+
+
+class EnsembleQuantiles:
+    """The forecast products of an ensemble beyond mean and variance: quantiles(y, logw=None) -> (quant, exceed).  quant float32 [Q, B, P, n_fields,
+    n_inp]: the weighted quantile maps of the members' decoded fields at `levels` (the median, a 5 % / 95 % band, with levels 0 and 1 the envelope) —
+    each value is the decoded value of one member, so it stays in the physical range and on a mode where the mean of a bimodal cell is on neither;
+    the maps are non-decreasing in the level.  exceed float32 [T, B, P, n_fields, n_inp]: the probability (the weight of the live members) that a field
+    exceeds a threshold, strictly.  A product that was not asked for is None.  include/sea_hip.h (sea_decode_member_quantiles) states the definitions:
+    the inverted weighted empirical distribution function — numpy's method="inverted_cdf" for equal weights, with the level rounded to float32.
+
+    y, logw, counts and layout mean what they mean in EnsembleFields (normalised_weights: a dead member is passed over, NaN in its states reaches
+    nothing; a history without a live member gets equal weights); invalid cells are exactly 0 in every map; a live cell where a live member's value
+    is not finite is NaN.  levels: up to 8 numbers in [0, 1], checked here.  thresholds: None, [T] (the same for every field) or [T, n_fields], T <= 8,
+    in the decoder's SCALED units (MeshUnpatcher.scale_thresholds maps physical thresholds there); numbers or a tensor.  With layout="BPCF" the maps
+    are permuted views [.., B, P, n_inp, n_fields].  Quantile maps go back to the mesh with MeshUnpatcher.inverse_scale_and_unpatch(quant[k],
+    layout="BPFC"), exceedance maps with unpatch_map(exceed[t]).
+    fused: True — the decoder's first layer plus the ONE launch of sea_decode_member_quantiles (bf16, up to 128 members): the members' decoded fields
+    are never written; False — Decode.forward plus a sort in fp64 torch ops (the composed path: fp32, more than 128 members, comparison); None —
+    Decode.member_quantiles' rule: the fused launch in bf16 up to 128 members from 4096 decoder rows (B * members * n_patches) on — every measured row
+    (tools/quantile_bench.py, profiles/ensemble_quantiles_bench.txt) — and the composed path everywhere else.  A call reads nothing back from the device and uploads nothing after the first call on a device.  `decoder` is a
+    sea_amd Decode; no autograd graph is built."""
+
+    def __init__(self, decoder, n_patches: int, members: int, levels=(0.05, 0.5, 0.95), thresholds=None, counts=None, layout: str = "BPFC",
+                 fused: Optional[bool] = None):
+        from . import ops
+
+        if layout not in ("BPFC", "BPCF"):
+            raise ValueError(f"EnsembleQuantiles: layout must be 'BPFC' or 'BPCF', got {layout!r}")
+        if not isinstance(n_patches, int) or isinstance(n_patches, bool) or n_patches < 1:
+            raise ValueError(f"EnsembleQuantiles: n_patches = {n_patches!r} must be a positive integer")
+        if not isinstance(members, int) or isinstance(members, bool) or members < 1:
+            raise ValueError(f"EnsembleQuantiles: members = {members!r} must be a positive integer")
+        if fused is not None and not isinstance(fused, bool):
+            raise ValueError(f"EnsembleQuantiles: fused = {fused!r} must be None, True or False")
+        if fused and members > N.QUANTILE_MAX_N:
+            raise ValueError(f"EnsembleQuantiles: the fused launch carries up to {N.QUANTILE_MAX_N} members, got {members} (fused=False, or None)")
+        self.levels = ops.check_quantile_levels(() if levels is None else levels, "EnsembleQuantiles")
+        n_fields = sum(len(g) for g in decoder.field_groups)
+        self._thr_src = None
+        if thresholds is not None:
+            t = thresholds.detach() if torch.is_tensor(thresholds) else torch.as_tensor(thresholds, dtype=torch.float32)
+            if t.dim() not in (1, 2) or not 1 <= t.shape[0] <= N.QUANTILE_MAX_LEVELS or (t.dim() == 2 and t.shape[1] != n_fields) or not t.is_floating_point():
+                raise ValueError(f"EnsembleQuantiles: thresholds must be None, [T] or [T, {n_fields}] numbers with 1 <= T <= {N.QUANTILE_MAX_LEVELS}, got shape "
+                                 f"{tuple(t.shape)} {t.dtype}")
+            self._thr_src = (t.view(-1, 1).expand(t.shape[0], n_fields) if t.dim() == 1 else t).to(torch.float32).contiguous()
+        if not self.levels and self._thr_src is None:
+            raise ValueError("EnsembleQuantiles: neither levels nor thresholds: there is nothing to compute")
+        self._thr = {}
+        self.decoder, self.n_patches, self.members, self.counts, self.layout, self.fused = decoder, n_patches, members, counts, layout, fused
+
+    def _thresholds_on(self, device):
+        """The thresholds f32 [T, n_fields] on the device (None without): moved there once per device."""
+        if self._thr_src is None:
+            return None
+        t = self._thr.get(device)
+        if t is None:
+            t = self._thr[device] = self._thr_src.to(device)
+        return t
+
+    def __call__(self, y: torch.Tensor, logw: Optional[torch.Tensor] = None, layout: Optional[str] = None):
+        layout = self.layout if layout is None else layout
+        if layout not in ("BPFC", "BPCF"):
+            raise ValueError(f"EnsembleQuantiles: layout must be 'BPFC' or 'BPCF', got {layout!r}")
+        P = self.n_patches
+        if not torch.is_tensor(y) or y.dim() != 3 or y.shape[-1] % P or y.shape[0] < 1:
+            raise ValueError(f"EnsembleQuantiles: y must be [B * members, n_groups, n_patches * D] with n_patches = {P}, got "
+                             f"{tuple(y.shape) if torch.is_tensor(y) else type(y).__name__}")
+        Bm, G, E = y.shape
+        if Bm % self.members:
+            raise ValueError(f"EnsembleQuantiles: the {Bm} trajectories of y are not a multiple of members = {self.members}")
+        if logw is not None:
+            if not torch.is_tensor(logw) or not logw.is_floating_point() or logw.numel() != Bm or logw.dim() not in (1, 2) \
+                    or (logw.dim() == 2 and logw.shape[1] != self.members):
+                raise ValueError(f"EnsembleQuantiles: logw must be None or a floating-point [{Bm}] (or [{Bm // self.members}, {self.members}]) tensor of log-weights, got "
+                                 f"{tuple(logw.shape) if torch.is_tensor(logw) else type(logw).__name__}")
+            if logw.device != y.device:
+                raise ValueError(f"EnsembleQuantiles: logw is on {logw.device}, y on {y.device}")
+        N.require_gpu(y, "EnsembleQuantiles states")
+        z = y.detach().reshape(Bm, G, P, E // P).permute(0, 2, 1, 3)          # the re-layout of FieldLikelihood
+        with torch.no_grad():
+            w = None if logw is None else normalised_weights(logw, self.members)
+            quant, exceed = self.decoder.member_quantiles(z, self.members, levels=self.levels, thresholds=self._thresholds_on(y.device), weights=w,
+                                                          counts=self.counts, fused=self.fused)
+        if layout == "BPCF":
+            quant = None if quant is None else quant.permute(0, 1, 2, 4, 3)
+            exceed = None if exceed is None else exceed.permute(0, 1, 2, 4, 3)
+        return quant, exceed
+
+    quantiles = __call__

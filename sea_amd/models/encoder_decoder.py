@@ -689,6 +689,86 @@ class Decode(nn.Module):
                                             prec=None if prec is None else rows(prec), counts=cnt, logw=lw, unbiased=bool(unbiased),
                                             accumulate=into is not None, maps=maps, out=into, dtype=dt)
 
+    def member_quantiles(self, z: torch.Tensor, members: int, levels=(), thresholds: Optional[torch.Tensor] = None, weights: Optional[torch.Tensor] = None,
+                         counts=None, fused: Optional[bool] = None):
+        """Quantile and exceedance-probability maps of an ensemble's decoded fields: (quant float32 [Q, B, P, n_fields, n_inp] or None, exceed float32
+        [T, B, P, n_fields, n_inp] or None), views of n_inp_p-wide buffers as member_moments returns; no autograd graph (include/sea_hip.h,
+        sea_decode_member_quantiles, states the definitions: the inverted weighted empirical distribution function; strict exceedance).  z, weights and
+        counts as in member_moments: weights None (equal) or float32 [B * members] on z's device, normalised per history; a member with weight <= 0 or
+        NaN is dead.  levels: up to 8 numbers in [0, 1]; thresholds: None or float32 [T <= 8, n_fields] on z's device, in the decoder's scaled units.
+        Invalid cells and the pad columns are exactly 0; a live cell where a live member's value is not finite is NaN in every map.
+        fused=True (bf16 compute dtype, members <= 128): the first-layer launch plus the ONE launch of sea_decode_member_quantiles — the members'
+        decoded fields are never written.  fused=False: forward() plus ensemble._composed_quantiles (a stable sort and cumulative weights in float64
+        torch ops: fp32, any member count, comparison).  fused=None: the fused launch in bf16 up to 128 members from 4096 rows (B * members * P) on —
+        every row of profiles/ensemble_quantiles_bench.txt (tools/quantile_bench.py, DESIGN.md section 7l: 0.66 - 6.9 ms against 2.6 - 16.2 ms composed at
+        4096 - 32768 rows, 13 - 112 MB of extra memory against 0.74 - 5.9 GB; thresholds only 0.20 - 0.99 ms) — and the composed path elsewhere: below
+        4096 rows, where nothing was measured, in fp32 and above 128 members."""
+        from ..ensemble import QUANTILES_FUSED_MIN_ROWS, _composed_quantiles
+
+        what = "sea_amd.Decode.member_quantiles"
+        n_fields = sum(len(g) for g in self.field_groups)
+        C, Cp = self.n_inp, self._n_inp_p
+        if not torch.is_tensor(z) or z.dim() != 4 or z.shape[2] != self.num_groups or z.shape[3] != self.embed_dim:
+            raise ValueError(f"{what}: z must be [B * members, P, {self.num_groups}, {self.embed_dim}], got {tuple(z.shape) if torch.is_tensor(z) else type(z).__name__}")
+        Bm, P = z.shape[0], z.shape[1]
+        if not isinstance(members, int) or isinstance(members, bool) or members < 1 or Bm < 1 or Bm % members:
+            raise ValueError(f"{what}: members = {members!r} must be a positive integer that divides the {Bm} rows of z")
+        B = Bm // members
+        levels = ops.check_quantile_levels(levels, what)
+        if thresholds is not None and (not torch.is_tensor(thresholds) or thresholds.dtype != torch.float32 or thresholds.dim() != 2
+                                       or not 1 <= thresholds.shape[0] <= N.QUANTILE_MAX_LEVELS or thresholds.shape[1] != n_fields or thresholds.device != z.device):
+            raise ValueError(f"{what}: thresholds must be None or a float32 [1 .. {N.QUANTILE_MAX_LEVELS}, {n_fields}] tensor on {z.device}, got "
+                             f"{(tuple(thresholds.shape), thresholds.dtype, str(thresholds.device)) if torch.is_tensor(thresholds) else type(thresholds).__name__}")
+        if not levels and thresholds is None:
+            raise ValueError(f"{what}: neither levels nor thresholds: there is nothing to compute")
+        if weights is not None:
+            if not torch.is_tensor(weights) or weights.dim() != 1 or weights.shape[0] != Bm:
+                raise ValueError(f"{what}: weights must be None or a [{Bm}] tensor (one weight per member), got "
+                                 f"{tuple(weights.shape) if torch.is_tensor(weights) else type(weights).__name__}")
+            if weights.dtype != torch.float32 or weights.device != z.device:
+                raise ValueError(f"{what}: weights must be float32 on {z.device}, got {weights.dtype} on {weights.device}")
+        dt = self._act_dtype()
+        if fused is None:
+            fused = dt == torch.bfloat16 and members <= N.QUANTILE_MAX_N and Bm * P >= QUANTILES_FUSED_MIN_ROWS
+        if fused and dt != torch.bfloat16:
+            raise ValueError(f"{what}: the fused launch is bf16 only (set_compute_dtype('bf16'), or fused=False)")
+        if fused and members > N.QUANTILE_MAX_N:
+            raise ValueError(f"{what}: the fused launch carries up to {N.QUANTILE_MAX_N} members, got {members} (fused=False, or None)")
+        cnt, _ = self._valid_counts(counts, P, z.device, allow_empty=True, what="member_quantiles")
+        N.require_gpu(z, "Decode.member_quantiles input")
+        with torch.no_grad():
+            w = None if weights is None else weights.detach().contiguous()
+            thr = None if thresholds is None else thresholds.detach().contiguous()
+            n_q, n_t = len(levels), 0 if thr is None else thr.shape[0]
+            out = {}
+            if not fused:
+                y = self.forward(z.detach()).view(B, members, P, n_fields, C)
+                q, e = _composed_quantiles(y, None if w is None else w.view(B, members), levels, thr)
+                valid = None if cnt is None else (torch.arange(C, device=z.device) < cnt[:, None]).view(1, 1, P, 1, C)
+                for name, t, k in (("quant", q, n_q), ("exceed", e, n_t)):
+                    if t is not None:
+                        buf = torch.zeros(k, B, P, n_fields, Cp, device=z.device, dtype=torch.float32)
+                        buf[..., :C] = t if valid is None else torch.where(valid, t.to(torch.float32), torch.zeros((), device=z.device))
+                        out[name] = buf
+            else:
+                M = Bm * P
+                G, D = self.num_groups, self.embed_dim
+                zf = z.detach().to(torch.float32).contiguous().view(M, G * D)
+                za = torch.empty(M, G * D, device=z.device, dtype=dt)
+                ops.convert(zf, za)
+                W1, W2 = self._weights(dt)
+                hid = [torch.empty(M, self.MLP_hidden, device=z.device, dtype=dt) for _ in range(G)]
+                ops.gemm_grouped([dict(A=za[:, g * D:(g + 1) * D], W=W1[g], Cact=hid[g], act=1) for g in range(G)], dt)
+                bias = self._shadow[3]
+                bufs = {name: torch.empty(k, B, P, n_fields, Cp, device=z.device, dtype=torch.float32) for name, k in (("quant", n_q), ("exceed", n_t)) if k}
+                out = ops.decode_member_quantiles([dict(H=hid[g], W2=W2[g], bias=bias[g]) for g in range(G)], C, Cp, P, members, levels=levels, thr=thr, w=w,
+                                                  counts=cnt, out=bufs, dtype=dt)
+            quant, exceed = out.get("quant"), out.get("exceed")
+            if Cp != C:
+                quant = None if quant is None else quant[..., :C]
+                exceed = None if exceed is None else exceed[..., :C]
+            return quant, exceed
+
     def forward_prefix(self, z: torch.Tensor, buckets) -> torch.Tensor:
         """The decoder for a consumer that only reads the first cells of a patch (MeshUnpatcher.decode_and_unpatch: a patch holds as many mesh points as its
         cell has, the rest of its n_inp columns is padding nobody reads — 71 % of the columns on the bench's wake-refined mesh).  z [B, P, n_groups,

@@ -1805,3 +1805,117 @@ def decode_member_verify(groups: Sequence[Dict], obs: torch.Tensor, C_: int, Cp:
                               res.get("crps"), res.get("pit"), res.get("rank"), res["sums"], res["hist"], res["status"], work, ld_out)
     N.check(N.lib().sea_decode_member_verify(arr, len(groups), C.byref(P), N.dtype_code(dtype), N.stream_ptr()), "sea_decode_member_verify")
     return res
+
+
+def fill_decode_member_quantiles(groups_arr, P: N.SeaDecodeMemberQuantiles, groups: Sequence[Dict], w, counts, thr, levels: Sequence[float], quant, exceed,
+                                 n_patches: int, members: int, C_: int, Cp: int, ld: int, ld_map: int) -> None:
+    """The argument table of sea_decode_member_quantiles.  groups as fill_decode_member_verify; w None or f32 [B * members] contiguous; counts None or
+    int32 [n_patches]; thr None or f32 [n_thr, n_fields_total] contiguous; levels: the host's floats; quant f32 [n_levels, B, n_patches, n_fields_total,
+    ld] and exceed f32 [n_thr, ...] contiguous, or None; ld_map: floats between two maps."""
+    field0 = 0
+    for g, d in zip(groups_arr, groups):
+        H, W2 = d["H"], d["W2"]
+        g.H, g.W2, g.bias, g.dH, g.Z = H.data_ptr(), W2.data_ptr(), d["bias"].data_ptr(), None, None
+        g.ldh, g.ldw, g.lddh, g.ldz = H.stride(0), W2.stride(0), 0, 0
+        g.n_fields, g.field0 = W2.shape[0] // Cp, field0
+        field0 += g.n_fields
+    P.w, P.counts, P.thr, P.quant, P.exceed = N.ptr(w), N.ptr(counts), N.ptr(thr), N.ptr(quant), N.ptr(exceed)
+    for k in range(N.QUANTILE_MAX_LEVELS):
+        P.level[k] = float(levels[k]) if k < len(levels) else 0.0
+    P.ld, P.ld_map = ld, ld_map
+    P.n_levels, P.n_thr = len(levels), 0 if thr is None else thr.shape[0]
+    P.M, P.S, P.C, P.Cp, P.P = groups[0]["H"].shape[0], groups[0]["H"].shape[1], C_, Cp, n_patches
+    P.members, P.n_fields_total, P.pad_ = members, field0, 0
+
+
+def decode_member_quantiles(groups: Sequence[Dict], C_: int, Cp: int, n_patches: int, members: int, levels: Sequence[float] = (),
+                            thr: Optional[torch.Tensor] = None, w: Optional[torch.Tensor] = None, counts: Optional[torch.Tensor] = None,
+                            out: Optional[Dict[str, torch.Tensor]] = None, dtype: torch.dtype = torch.bfloat16) -> Dict[str, Optional[torch.Tensor]]:
+    """sea_decode_member_quantiles: weighted quantile maps and exceedance-probability maps of an ensemble's decoded fields in one launch
+    (include/sea_hip.h states the definitions) — the members' decoded fields are never written.  groups, counts as decode_member_verify; levels: up to 8
+    floats in [0, 1]; thr None or f32 [T <= 8, n_fields] thresholds in the decoder's scaled units; w None (equal weights) or f32 [B * members], normalised
+    per history; a member with w <= 0 or NaN is dead.  Returns dict(quant=f32 [Q, B, n_patches, n_fields, C] or None, exceed=f32 [T, ...] or None):
+    every element written, nothing read back.  out: a dict with "quant" and / or "exceed" to write into (their last dimension may be any width >= C,
+    the same for both).  Everything is checked on the host before the launch."""
+    what = "decode_member_quantiles"
+    if dtype != torch.bfloat16:
+        raise ValueError(f"{what}: the fused launch is bf16 only, got {dtype}")
+    if not groups or len(groups) > N.DECODE_MSE_MAX_GROUPS:
+        raise ValueError(f"{what}: {len(groups)} groups; a launch carries 1 .. {N.DECODE_MSE_MAX_GROUPS}")
+    if Cp < 32 or Cp % 32 or not 1 <= C_ <= Cp:
+        raise ValueError(f"{what}: need Cp a multiple of 32 and 1 <= C <= Cp, got C = {C_}, Cp = {Cp}")
+    dev = groups[0]["H"].device
+    M, S = tuple(groups[0]["H"].shape) if groups[0]["H"].dim() == 2 else (0, 0)
+    if groups[0]["H"].dtype != dtype:
+        raise ValueError(f"{what}: the fused launch is bf16 only, got hidden rows in {groups[0]['H'].dtype}")
+    if M < 1 or S < 8 or S % 8 or S > N.DECODE_MSE_MAX_S:
+        raise ValueError(f"{what}: H must be [M >= 1, S] with S a multiple of 8 up to {N.DECODE_MSE_MAX_S}, got {tuple(groups[0]['H'].shape)}")
+    n = members
+    if not isinstance(n, int) or isinstance(n, bool) or n < 1 or n > N.QUANTILE_MAX_N:
+        raise ValueError(f"{what}: members = {members!r} must be an integer in 1 .. {N.QUANTILE_MAX_N}")
+    if n_patches < 1 or M % (n_patches * n):
+        raise ValueError(f"{what}: {M} rows are not a multiple of n_patches * members = {n_patches} * {n}")
+    levels = check_quantile_levels(levels, what)
+    n_fields = 0
+    for i, d in enumerate(groups):
+        for name in ("H", "W2"):
+            t = d[name]
+            if t.dim() != 2 or t.stride(1) != 1:
+                raise ValueError(f"{what} group {i}: {name}: need a 2-D tensor with unit inner stride, got shape {tuple(t.shape)} strides {t.stride()}")
+            if t.dtype != dtype or t.device != dev or t.shape[1] != S or (name != "W2" and t.shape[0] != M):
+                raise ValueError(f"{what} group {i}: {name} must be a {dtype} [{'n_fields * Cp' if name == 'W2' else M}, {S}] tensor on {dev}, got "
+                                 f"{tuple(t.shape)} {t.dtype} on {t.device}")
+            if t.stride(0) % 8 or t.data_ptr() % 16:
+                raise ValueError(f"{what} group {i}: {name} needs a row stride that is a multiple of 8 and a 16-byte-aligned base (stride {t.stride(0)})")
+        W2, b = d["W2"], d["bias"]
+        if W2.shape[0] < Cp or W2.shape[0] % Cp:
+            raise ValueError(f"{what} group {i}: W2 has {W2.shape[0]} rows, not a multiple of Cp = {Cp}")
+        if b.dtype != torch.float32 or b.dim() != 1 or b.shape[0] != W2.shape[0] or not b.is_contiguous() or b.device != dev or b.data_ptr() % 16:
+            raise ValueError(f"{what} group {i}: bias must be a contiguous, 16-byte-aligned float32 [{W2.shape[0]}] on {dev}, got {tuple(b.shape)} {b.dtype}")
+        n_fields += W2.shape[0] // Cp
+    B = M // (n_patches * n)
+    if B > 65535:
+        raise ValueError(f"{what}: {B} histories; a launch carries up to 65535")
+    if thr is not None and (not torch.is_tensor(thr) or thr.dtype != torch.float32 or thr.dim() != 2 or not 1 <= thr.shape[0] <= N.QUANTILE_MAX_LEVELS
+                            or thr.shape[1] != n_fields or not thr.is_contiguous() or thr.device != dev):
+        raise ValueError(f"{what}: thr must be None or a contiguous float32 [1 .. {N.QUANTILE_MAX_LEVELS}, {n_fields}] tensor on {dev}, got "
+                         f"{(tuple(thr.shape), thr.dtype, str(thr.device)) if torch.is_tensor(thr) else type(thr).__name__}")
+    if not levels and thr is None:
+        raise ValueError(f"{what}: neither levels nor thresholds: there is nothing to compute")
+    if w is not None and (not torch.is_tensor(w) or w.dtype != torch.float32 or tuple(w.shape) != (B * n,) or not w.is_contiguous() or w.device != dev):
+        raise ValueError(f"{what}: w must be None or a contiguous float32 [{B * n}] tensor on {dev}, got "
+                         f"{(tuple(w.shape), w.dtype, str(w.device)) if torch.is_tensor(w) else type(w).__name__}")
+    if counts is not None and (not torch.is_tensor(counts) or counts.dtype != torch.int32 or counts.dim() != 1 or counts.shape[0] != n_patches
+                               or not counts.is_contiguous() or counts.device != dev):
+        raise ValueError(f"{what}: counts must be a contiguous int32 [{n_patches}] on {dev}")
+    n_out = {"quant": len(levels), "exceed": 0 if thr is None else thr.shape[0]}
+    out = {} if out is None else out
+    if not isinstance(out, dict) or any(k not in n_out or n_out[k] == 0 for k in out):
+        raise ValueError(f"{what}: out must be a dict with 'quant' (with levels) and / or 'exceed' (with thresholds)")
+    widths = {t.shape[-1] for t in out.values() if torch.is_tensor(t) and t.dim() == 5}
+    if len(widths) > 1:
+        raise ValueError(f"{what}: the maps in out must share their last dimension, got {sorted(widths)}")
+    ld = widths.pop() if widths else C_
+    for k, t in out.items():
+        shape = (n_out[k], B, n_patches, n_fields, ld)
+        if not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev or ld < C_:
+            raise ValueError(f"{what}: out[{k!r}] must be a contiguous float32 {list(shape)} tensor on {dev} (last dimension >= {C_})")
+    N.require_gpu(groups[0]["H"], f"{what} hidden rows")   # every operand is on their device (checked above)
+    res = {k: (out[k] if k in out else torch.empty(n_out[k], B, n_patches, n_fields, ld, device=dev, dtype=torch.float32)) if n_out[k] else None for k in n_out}
+    arr, P = (N.SeaDecodeMseGroup * len(groups))(), N.SeaDecodeMemberQuantiles()
+    fill_decode_member_quantiles(arr, P, groups, w, counts, thr, levels, res["quant"], res["exceed"], n_patches, n, C_, Cp, ld, B * n_patches * n_fields * ld)
+    N.check(N.lib().sea_decode_member_quantiles(arr, len(groups), C.byref(P), N.dtype_code(dtype), N.stream_ptr()), "sea_decode_member_quantiles")
+    return res
+
+
+def check_quantile_levels(levels, what: str) -> tuple:
+    """The levels of a quantile call as a tuple of floats: at most 8, each finite and in [0, 1] — checked on the host, ValueError otherwise."""
+    try:
+        lv = tuple(float(v) for v in levels)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: levels must be a sequence of numbers in [0, 1], got {levels!r}") from None
+    if len(lv) > N.QUANTILE_MAX_LEVELS:
+        raise ValueError(f"{what}: {len(lv)} levels; a launch carries up to {N.QUANTILE_MAX_LEVELS}")
+    if any(not (0.0 <= v <= 1.0) for v in lv):   # false for NaN
+        raise ValueError(f"{what}: every level must be finite and lie in [0, 1], got {lv}")
+    return lv

@@ -217,6 +217,25 @@ class MeshUnpatcher:
         return ops.unpatchify(values.float(), layout, self.partitioner.padded_index_map, self._unit_scale, self._unit_shift, self.partitioner.x_coords.numel(),
                               point_slot=self.partitioner.point_slot if self.gather else None)
 
+    def scale_thresholds(self, thr) -> torch.Tensor:
+        """Physical thresholds -> the decoder's scaled units, for EnsembleQuantiles(thresholds=...): thr [T, F] (numbers or a tensor; [T]: the same
+        physical value for every field) -> float32 [T, F], thr * a_f + b_f with the per-field forward affine of _forward_coefficients (what
+        patchify_and_scale applies), formed in float64.  "field > threshold" keeps its sense only under an increasing map: a field whose forward slope
+        is not positive (a MinMaxScaler with a descending feature_range) is refused."""
+        scale, shift = self._forward_coefficients()
+        F = len(scale)
+        bad = [f for f in range(F) if not scale[f] > 0.0]
+        if bad:
+            raise ValueError(f"scale_thresholds: the forward scaling of fields {bad} is not increasing (slopes {[scale[f] for f in bad]}): 'above the threshold' "
+                             "would turn into 'below' in scaled units")
+        t = thr.detach() if torch.is_tensor(thr) else torch.as_tensor(thr, dtype=torch.float64)
+        if t.dim() == 1:
+            t = t.view(-1, 1).expand(t.shape[0], F)
+        if t.dim() != 2 or t.shape[1] != F or t.shape[0] < 1:
+            raise ValueError(f"scale_thresholds: thr must be [T] or [T, {F}] (one column per field), got shape {tuple(t.shape)}")
+        a = torch.tensor(scale, dtype=torch.float64, device=t.device)
+        b = torch.tensor(shift, dtype=torch.float64, device=t.device)
+        return (t.to(torch.float64) * a + b).to(torch.float32).contiguous()
 
     # ------------------------------------------------------------------ decoder + un-patchify without the padding
     def _prefix_plan(self, max_buckets: int):
@@ -330,6 +349,13 @@ class MeshProcessor:
         if self._unpatcher is None:
             raise ValueError("call patchify_and_scale first (it builds the partition)")
         return self._unpatcher.unpatch_map(values.to(self.device), layout=layout)
+
+    def scale_thresholds(self, thr) -> torch.Tensor:
+        """Physical thresholds [T, F] (or [T]) -> float32 [T, F] in the decoder's scaled units, for EnsembleQuantiles(thresholds=...)
+        (MeshUnpatcher.scale_thresholds: the per-field forward affine; a decreasing scaling is refused)."""
+        if self._unpatcher is None:
+            raise ValueError("call patchify_and_scale first (it builds the partition)")
+        return self._unpatcher.scale_thresholds(thr)
 
     def sensor_set(self, decoder, points, fields):
         """Point sensors on the mesh (mesh point ids and field ids) as a SensorSet for `decoder`, with scale_values / scale_sigma for readings in
