@@ -776,6 +776,17 @@ typedef struct {
     float bias_scale;
     SeaGemmNormGroup down;
     SeaQkvGroup proj[SEA_CHAIN_MAX_PROJ];
+    /* optional condition memo of the launch's RIDER TILES (sea_row_chain_riders; read from group 0 only; tile_stamps NULL: none, every tile computes).  A rider tile's
+     * 128 x 128 outputs are functions of tile_cond[m] of its rows, the weights and hidden rows that are themselves functions of both.  Tile t (numbered as the riders'
+     * tiles are, over ALL the rider groups) owns the stamp set tile_stamps[t]: a tile whose live rows all carry the stamp {bits of tile_cond[m], *tile_epoch} exits and
+     * touches nothing else; any other computes as without a memo and then stores its stamps.  The caller keeps the stamps (zeroed once), the riders' outputs AND their
+     * A operands between launches, and changes *tile_epoch (never to 0) whenever a weight of these modules changes.  tile_count: hits / misses, one count per tile,
+     * where SEA_TUNE=memo_count=1. */
+    uint32_t* tile_stamps;        /* u32 [tile_sets][128][2] */
+    const float* tile_cond;       /* f32 [riders' M] */
+    const uint32_t* tile_epoch;   /* u32 [1], device memory */
+    int32_t* tile_count;          /* i32 [2] (hits, misses) or NULL */
+    int32_t tile_sets, pad_;      /* stamp sets behind tile_stamps: at least the riders' tile count */
 } SeaRowChain;
 
 /* params: n_groups <= SEA_CHAIN_MAX_GROUPS problems of one (D, E) (e.g. the F fields), one grid row each; common: rotary table, heads, positions of the projections
@@ -787,7 +798,8 @@ int sea_row_chain(const SeaRowChain* params, int n_groups, const SeaQkvCommon* c
  *            MLP and the final norm read, models/base_blocks.py:339,344), cut into 128 x 128 tiles numbered group by group; THIS launch runs tiles
  *            [tile0, tile0 + n_tiles) — the caller spreads a GEMM over several chain launches;
  *   ib       NULL, or the information-bottleneck MLP whose rows ib->X[0][m, :] are STORED as sea_silu_outer_ib stores them (models/temporal.py:111-116).
- * Results are complete when the launch is; nothing in the same launch may read them. */
+ * Results are complete when the launch is; nothing in the same launch may read them.  params[0].tile_stamps != NULL: the rider tiles' condition memo (SeaRowChain:
+ * the pointers travel in group 0, so sea_run_list's SEA_OP_CHAIN entry and a captured graph carry them as they carry every other field). */
 struct SeaIbParams_;
 int sea_row_chain_riders(const SeaRowChain* params, int n_groups, const SeaQkvCommon* common, const SeaGemmGroup* riders, int n_riders, int tile0, int n_tiles,
                          const struct SeaIbParams_* ib, float eps, int dtype, void* stream);

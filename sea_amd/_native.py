@@ -152,7 +152,8 @@ class SeaRowChain(C.Structure):
     _fields_ = [("att", _vp * XTAIL_MAX_SEG), ("Wp", _vp * XTAIL_MAX_SEG), ("a2", _vp), ("W2", _vp), ("b2", _vp), ("Xin", _vp), ("X", _vp), ("Xact", _vp),
                 ("n_seg", _i32), ("ldatt", _i32), ("ldwp", _i32), ("lda2", _i32), ("ldw2", _i32), ("ldxin", _i32), ("ldx", _i32), ("ldxact", _i32),
                 ("M", _i32), ("D", _i32), ("E", _i32), ("has_down", _i32), ("n_proj", _i32), ("bias_scale", _f32),
-                ("down", SeaGemmNormGroup), ("proj", SeaQkvGroup * CHAIN_MAX_PROJ)]
+                ("down", SeaGemmNormGroup), ("proj", SeaQkvGroup * CHAIN_MAX_PROJ),
+                ("tile_stamps", _vp), ("tile_cond", _vp), ("tile_epoch", _vp), ("tile_count", _vp), ("tile_sets", _i32), ("pad_", _i32)]   # the rider tiles' condition memo (group 0; NULL: none)
 
 
 MAX_ADALN_GROUPS = 16

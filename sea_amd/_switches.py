@@ -17,7 +17,8 @@
                                            fold_ib_gen=1         ... folded at long launches too    mlp1 / mlpnorm / mlp2=0|1   the fused MLP halves off / forced
                                            mlpblock=0            the field MLP as two launches      projnorm=0            the last proj and the final norm as two launches
                                            splitk=0              no split-K form of skinny GEMMs with a long contraction
-                                           cond_memo=0           the one-launch front recomputes its condition-only work at every forward
+                                           cond_memo=0           the one-launch front recomputes its condition-only work at every forward (and the rider tiles theirs)
+                                           rider_memo=0          the chain launches' rider tiles recompute at every forward; the front's memo stays
                                            graph_lanes=0         a captured graph replays its lanes in record order (engine.forward_graphed)
                                            enc=composed|fused    spatial encoder training: every EncoderBlock composed from the generic launches (default, measured
                                                                    faster) or as the fused sea_encoder_block_fwd / _bwd (bf16, width 32 or 64; other shapes always compose)
@@ -29,7 +30,7 @@
                                          is fixed by the first call of the process, long before the forcing test starts —: gemm_tile (64 | 128), gemm256 (0 | 1),
                                          gemm_ws (0 off, 2 also short launches), gemm_norm_rows (16 | 64), attn_split4 (0 | 1), attn_paired, attnb_mode (attention
                                          backward: 1 XCD-local order, 2 paired causal tiles, 3 both, 0 neither), chain_rows, kv_persist, kv_pre, sse_rows, wgrad_tile
-                                         (64 | 128 | 256), wgrad_stage, memo_count (1: the condition memo's workgroups count hits / misses into Plan.memo_count).  Every other key (gemm_skinny, gemm_dma_*, gemm_n_major, gemm_norm_dma, attn_row, wgrad_target,
+                                         (64 | 128 | 256), wgrad_stage, memo_count (1: the condition memo's workgroups count hits / misses into Plan.memo_count, the chain launches' rider tiles into Plan.memo_tile_count).  Every other key (gemm_skinny, gemm_dma_*, gemm_n_major, gemm_norm_dma, attn_row, wgrad_target,
                                          wgrad_xcd, normbwd_*, ...) is a measurement aid read once per process: set it before the first launch; no test may force
                                          one (tests/test_tune_keys_cpu.py).  Which kernel a launch took: ops.last_form() (sea_last_form, include/sea_hip.h).
   SEA_EXTRA_FLAGS "..."                  extra hipcc flags for `python -m sea_amd.build` (A/B builds)

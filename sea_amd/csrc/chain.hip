@@ -222,9 +222,45 @@ __global__ __launch_bounds__(256) void row_chain_kernel(const ChainLaunch L) {
             G.lda = R.lda; G.ldw = R.ldw; G.ldcact = R.ldcact; G.M = R.M; G.N = R.N; G.K = R.K;
             const int t = tile - R.tile_start;
             const int tiles_n = (R.N + 127) / 128;
+            const int tm = t / tiles_n, tn = t % tiles_n;
+            // The condition memo of the rider tiles (group 0's tile_stamps != NULL): what a tile writes is a function of the conditions of its 128 rows and the
+            // weights, and its output stays in the caller's buffer between launches.  When every live row's stamp {condition bits, weight epoch} in the tile's OWN
+            // set (the column tiles of a row panel do not share one: a late tile would read what an early tile of the same launch wrote) equals what it sees, the
+            // workgroup exits; any other computes as without a memo and stamps its rows behind the tile.  One wave decides, through LDS and a barrier.
+            uint32_t* tst = L.p[0].tile_stamps;   // (a kernel argument: uniform)
+            uint32_t t_c[2] = {0u, 0u}, t_e = 0u;
+            int t_row[2] = {-1, -1};              // wave 0, lane l: rows l and 64 + l of the tile (-1 behind the last row of a partial panel)
+            if (tst != nullptr) {
+                tst += (int64_t)tile * 256;
+                int ok = 1;
+                if (wave == 0) {
+                    t_e = *L.p[0].tile_epoch;
+#pragma unroll
+                    for (int i = 0; i < 2; ++i) {
+                        const int m = tm * 128 + i * 64 + lane;
+                        if (m < R.M) {
+                            t_row[i] = i * 64 + lane;
+                            t_c[i] = __float_as_uint(L.p[0].tile_cond[m]);
+                            const uint2 st = reinterpret_cast<const uint2*>(tst)[t_row[i]];
+                            ok &= (st.x == t_c[i] && st.y == t_e) ? 1 : 0;
+                        }
+                    }
+                }
+                const int all_ok = __all(ok);
+                if (tid == 0) *reinterpret_cast<int*>(smem) = all_ok;
+                __syncthreads();
+                const bool t_hit = __builtin_amdgcn_readfirstlane(*reinterpret_cast<const int*>(smem)) != 0;
+                if (L.p[0].tile_count != nullptr && tid == 0) atomicAdd(L.p[0].tile_count + (t_hit ? 0 : 1), 1);
+                if (t_hit) return;
+                __syncthreads();   // every wave has read the verdict: the ring's first stage goes over that word
+            }
             // the LDS-DMA ring main loop (4 stages of A | W K-tiles in flight): a rider workgroup is ALONE on its CU (the launch's LDS request is the chain's), so
             // nothing else hides its memory latency — the single-buffered form took 15 us per tile here, generated operand included (round 4, measured)
-            gemm_tile_body<T, 128, 128, true, true, false>(G, t / tiles_n, t % tiles_n, smem, 0);
+            gemm_tile_body<T, 128, 128, true, true, false>(G, tm, tn, smem, 0);
+            // (no launch reads a stamp it writes: the next launch that runs this tile sees them, and the tile's rows are complete when this launch is)
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+                if (tst != nullptr && t_row[i] >= 0) reinterpret_cast<uint2*>(tst)[t_row[i]] = make_uint2(t_c[i], t_e);
         } else if (x < L.rider_n + L.ib_wgs) {
             const int row0 = (x - L.rider_n) * 64 + wave * 16;   // a wave per row, 16 rows per wave
             for (int i = 0; i < 16; ++i) {
@@ -746,6 +782,17 @@ static int row_chain_launch(const SeaRowChain* params, int n_groups, const SeaQk
         (void)once;                                                                                             \
         row_chain_kernel<DD, EE, MM><<<grid, dim3(256), (L.rider_n > 0 ? max_ : own_), s>>>(L);                 \
     } while (0)
+    // ---- the rider tiles' condition memo (group 0 carries it; without rider tiles in this launch nothing reads it)
+    if (L.p[0].tile_stamps != nullptr && L.rider_n > 0) {
+        const SeaRowChain& P0 = L.p[0];
+        SEA_REQUIRE(P0.tile_cond && P0.tile_epoch && P0.tile_sets >= rider_total && ((uintptr_t)P0.tile_stamps & 7) == 0 && ((uintptr_t)P0.tile_cond & 3) == 0 &&
+                        ((uintptr_t)P0.tile_epoch & 3) == 0 && ((uintptr_t)P0.tile_count & 3) == 0,
+                    "sea_row_chain_riders: tile memo: null / misaligned pointer, or %d stamp sets for %d tiles", P0.tile_sets, rider_total);
+        for (int i = 1; i < n_riders; ++i) SEA_REQUIRE(riders[i].M == riders[0].M, "sea_row_chain_riders: tile memo: the rider groups share their rows (one condition per row)");
+        if (sea_tune("memo_count", 0) == 0) L.p[0].tile_count = nullptr;   // (read at every call: a test switches it on for one plan)
+    } else {
+        L.p[0].tile_stamps = nullptr;
+    }
     if (D == 128) { if (mi == 1) LAUNCH_CH(128, 256, 1); else LAUNCH_CH(128, 256, 2); }
     else { if (mi == 1) LAUNCH_CH(64, 128, 1); else LAUNCH_CH(64, 128, 2); }
 #undef LAUNCH_CH

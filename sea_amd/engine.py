@@ -276,8 +276,9 @@ class _Riders:
     grouped GEMM handed out to the `hosts` chain launches that may carry riders (the one behind the self-attention and the tails of the fields that are not
     last: their results are read by the MLP)."""
 
-    def __init__(self, arr, tiles: int, hosts: int, caps: Optional[Tuple[int, ...]]):
+    def __init__(self, arr, tiles: int, hosts: int, caps: Optional[Tuple[int, ...]], memo: Optional[dict] = None):
         self.arr, self.tiles, self.done = arr, tiles, 0
+        self.memo = memo                      # forms.rider_memo: the tiles' condition memo (ops.fill_row_chain's tile_memo), one stamp set per tile of the rider GEMM
         self.hosts_total = self.hosts_left = hosts
         self.caps, self.host_no = caps, 0     # PlanForms.rider_caps: tiles for the first, second, third host instead of equal shares
 
@@ -344,6 +345,7 @@ class Plan:
         self._riders: Optional[_Riders] = None          # rider work of the chain launches (forms.riders)
         self._front = None                              # rider plans: (cond_mlp.2 operands of the front modules, row riders of the one-launch front), see _cond_mods
         self.memo_count: Optional[torch.Tensor] = None  # forms.cond_memo: int32 [2], hits / misses of the condition memo's workgroups (SEA_TUNE=memo_count=1)
+        self.memo_tile_count: Optional[torch.Tensor] = None   # forms.rider_memo: int32 [2], hits / misses of the chain launches' rider tiles (SEA_TUNE=memo_count=1)
         self._build()
         self._find_hoisted()
         self._clist = None          # (SeaLaunchRec array, [(rec index, field, args list, args index)]) for sea_run_list
@@ -538,9 +540,14 @@ class Plan:
         tensor: the residual rows of the first layer are read from it, strided)."""
         for s in range(0, len(groups), N.CHAIN_MAX_GROUPS):
             chunk = groups[s:s + N.CHAIN_MAX_GROUPS]
-            arr = self._array(N.SeaRowChain, chunk, ops.fill_row_chain)
-            common = self._qkv_common(rope, hd)
             rd = self._riders.take() if s == 0 and self._riders is not None else None
+            memo = self._riders.memo if rd is not None and rd[3] > 0 else None   # the tiles' condition memo travels in group 0 (forms.rider_memo)
+            if memo is not None:
+                chunk = [dict(chunk[0], tile_memo=memo)] + chunk[1:]
+            arr = self._array(N.SeaRowChain, chunk, ops.fill_row_chain)
+            if memo is not None:
+                self._c_patches.append((arr[0], "tile_cond"))   # the condition pointer, patched at every bind as the front's row riders' is
+            common = self._qkv_common(rope, hd)
             if rd is None:
                 self._cur.append(self._rec(N.lib().sea_row_chain, [arr, len(chunk), C.byref(common), 1e-5, self.code], name, (arr, common)))
             else:
@@ -634,7 +641,15 @@ class Plan:
                 self._gemm([dict(A=hids[pre_], W=P.act(pre_ + "cond_mlp.2.weight"), bias=P.f32_vec(pre_ + "cond_mlp.2.bias"), Cact=mods[pre_]) for pre_, _ in front], "adaln.cond_gemm.front")
             arr = self._array(N.SeaGemmGroup, [dict(A=hids[pre_], W=P.act(pre_ + "cond_mlp.2.weight"), bias=P.f32_vec(pre_ + "cond_mlp.2.bias"),
                                                     Cact=mods[pre_]) for pre_, _ in later], ops.fill_gemm_group)
-            self._riders = _Riders(arr, sum(((M + 127) // 128) * ((2 * d + 127) // 128) for _, d in later), F, fm.rider_caps)
+            tiles = sum(((M + 127) // 128) * ((2 * d + 127) // 128) for _, d in later)
+            memo = None
+            if fm.cond_memo and fm.rider_memo:
+                # the rider tiles' condition memo: a stamp set per TILE, zeroed once (epoch 0 matches nothing).  A hit leaves the tile's
+                # modulation where the last miss stored it and a miss of SOME rows re-reads the hidden rows of all 128: mods[pre_] and hids[pre_] of the later
+                # modules are buffers of their own (_buf above), written by the rider tiles / the front's row riders only, and live as long as the plan
+                self.memo_tile_count = self._buf(2, dtype=torch.int32, zero=True)
+                memo = dict(stamps=self._buf(tiles, 128, 2, dtype=torch.int32, zero=True), epoch=P.memo_epoch, count=self.memo_tile_count)
+            self._riders = _Riders(arr, tiles, F, fm.rider_caps, memo)
             self._keep.append(arr)
             return mods
 

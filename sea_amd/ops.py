@@ -389,9 +389,17 @@ def row_chain_supported(dtype: torch.dtype, D: int, E: int, n_seg: int, hd: int)
 
 
 def fill_row_chain(P: N.SeaRowChain, W2, Xin, X, att: Sequence[torch.Tensor] = (), Wp: Sequence[torch.Tensor] = (), a2=None, b2=None, bias_scale: float = 1.0, Xact=None,
-                   down: Optional[Dict] = None, proj: Sequence[Dict] = (), ldxin: Optional[int] = None) -> None:
+                   down: Optional[Dict] = None, proj: Sequence[Dict] = (), ldxin: Optional[int] = None, tile_memo: Optional[Dict] = None) -> None:
     """One group of sea_row_chain.  Form A: a2 act [M, E], W2 act [E, E]; form B: att / Wp lists (n_seg act [M, D] / [D, D]), W2 act [E, D].  Xin f32 [M, E] (row
-    stride ldxin when given: the caller's strided tensor), X f32 [M, E]; down: dict(W [D, E], bias, gamma, beta, mod, Yact, Y32); proj: dicts(W [N, D], bias, col0, Q / K / Vt / V)."""
+    stride ldxin when given: the caller's strided tensor), X f32 [M, E]; down: dict(W [D, E], bias, gamma, beta, mod, Yact, Y32); proj: dicts(W [N, D], bias, col0, Q / K / Vt / V).
+    tile_memo (group 0 of a launch with riders): dict(stamps int32 [tiles, 128, 2] zeroed once, one set per rider tile; cond f32 [M] or None: patched in later; epoch
+    int32 [1]; count int32 [2] or None) — the rider tiles' condition memo, buffers the caller keeps between launches (None: no memo, the pointers stay NULL)."""
+    if tile_memo is not None:
+        st = tile_memo["stamps"]
+        if st.dtype != torch.int32 or st.dim() != 3 or tuple(st.shape[1:]) != (128, 2) or not st.is_contiguous():
+            raise ValueError(f"row_chain tile memo: stamps {tuple(st.shape)} {st.dtype}: int32 [tiles, 128, 2], one set per rider tile")
+        P.tile_stamps, P.tile_sets = st.data_ptr(), st.shape[0]
+        P.tile_cond, P.tile_epoch, P.tile_count = N.ptr(tile_memo.get("cond")), tile_memo["epoch"].data_ptr(), N.ptr(tile_memo.get("count"))
     for s_, a in enumerate(att):
         P.att[s_] = a.data_ptr()
         P.Wp[s_] = Wp[s_].data_ptr()

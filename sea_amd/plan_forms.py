@@ -40,7 +40,10 @@ class PlanForms:
     riders: bool
     # SEA_PLAN=rider_caps, a tuning aid: "a:b:c" = tiles for the first, second, third host.  Measured at cfg2 (tools/chain_probe.py replay): 128:128:128 tiles
     # under the three hosts 0.2153 ms per step, 192:96:96 0.2178, 256:64:64 0.2201, 384:0:0 0.2233, 0:192:192 0.2250, no riders 0.2214 — equal shares (a rider
-    # tile, alone on its CU beside 127-192 chain workgroups, takes ~9 us; the hosts last 24 / 16 / 12 us).  None: equal shares
+    # tile, alone on its CU beside 127-192 chain workgroups, takes ~9 us; the hosts last 24 / 16 / 12 us).  None: equal shares.  These figures say that the
+    # tiles are ON the hosts' critical path (190 chain workgroups + 128 tiles on 256 CUs: the first host's tiles run in two rounds behind its chain workgroups,
+    # and moving tiles between hosts moves the step by up to 10 us).  With the tiles' condition memo (rider_memo below) the split matters on MISS steps only:
+    # a tile that hits loads its stamps and leaves
     rider_caps: Optional[Tuple[int, ...]]
     # cond_mlp.0 + SiLU evaluated inside the GEMM of cond_mlp.2 (generated A operand): no hidden matrix, no silu launch.  Inference plans
     # only (the weight gradient of cond_mlp.2 reads the hidden matrix).  The operand is recomputed by every column tile of a row panel (4x at
@@ -113,6 +116,11 @@ class PlanForms:
     # Where front_chain and riders; SEA_PLAN=cond_memo=0 switches it off (the reference form of tests/test_cond_memo_gpu.py).  Not part of a PlanForms'
     # equality: it changes no launch, only optional pointers of one.
     cond_memo: bool = field(default=False, compare=False)
+    # ... taken down to the RIDER TILES of the chain launches: every 128 x 128 tile of cond_mlp.2 of AdaLN_2 and of the final norm keeps a
+    # stamp set of its own and exits when the conditions of its rows and the weight epoch are those it stamped; the modulation and hidden-row buffers of these
+    # modules persist between forwards.  In force only together with cond_memo (SEA_PLAN=cond_memo=0 switches off both); SEA_PLAN=rider_memo=0 leaves the tiles'
+    # pointers NULL and keeps the front memo (the A/B lever).  Like cond_memo it changes no launch and is not part of a PlanForms' equality.
+    rider_memo: bool = field(default=False, compare=False)
 
     @property
     def one_launch_front(self) -> bool:
@@ -184,4 +192,4 @@ def resolve_forms(model, B: int, T: int, mode: str, dt: torch.dtype, kind: str =
         mlp_fc1=mlp_fc1, mlp_norm_in=mlp_norm_in, mlp_block=mlp_block, mlp_fc2_proj=mlp_fc2_proj,
         down_norm=(fuse_norm if inference else kind == TRAINING and sw("norm", "1") != "0") and D <= 256 and D % 16 == 0,
         proj_norm=fuse_norm and Eo <= 256 and Eo % 16 == 0 and Eo == E and sw("projnorm", "1") != "0", splitk=sw("splitk", "1") != "0",
-        cond_memo=front_chain and riders and sw("cond_memo", "1") != "0")
+        cond_memo=front_chain and riders and sw("cond_memo", "1") != "0", rider_memo=front_chain and riders and sw("rider_memo", "1") != "0")

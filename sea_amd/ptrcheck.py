@@ -179,6 +179,12 @@ def _extents(st, esz: int) -> Iterable[Tuple[str, int, int]]:
         yield "X", st.X, ((st.M - 1) * st.ldx + st.E) * f32
         if st.Xact:
             yield "Xact", st.Xact, ((st.M - 1) * st.ldxact + st.E) * esz
+        if st.tile_stamps:   # the rider tiles' condition memo: a {condition bits, epoch} pair per row and tile, the conditions of the riders' rows (= this group's), the epoch word
+            yield "tile_stamps", st.tile_stamps, st.tile_sets * 128 * 8
+            yield "tile_cond", st.tile_cond, st.M * f32
+            yield "tile_epoch", st.tile_epoch, 4
+            if st.tile_count:
+                yield "tile_count", st.tile_count, 8
     elif isinstance(st, N.SeaMlpGroup):
         if st.A:
             yield "A", st.A, ((st.M - 1) * st.lda + st.E) * esz
