@@ -1257,6 +1257,55 @@ typedef struct {
 int sea_decode_sensor_grad(const SeaDecodeMseGroup* groups, int n_groups, const SeaDecodeSensorGrad* p, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * The DENSE-snapshot score with a per-cell precision map and per-field precisions, per member and field, WITH its gradient to the hidden rows, in one
+ * launch for all field groups (plus the finish launch of sea_decode_member_sse): what a particle filter's weights, nudging of members and the pull of
+ * a single trajectory towards a GAPPY snapshot need (a PIV frame with masked regions, a field known on some cells only).  It replaces Decode.forward
+ * under autograd, the weighted reductions over its [M, n_fields * Cp] output and the backward through an output gradient of that size; neither the
+ * decoded fields nor the residual ever exist in memory.  Group operands H, W2, bias, ldh, ldw, n_fields, field0 as in sea_decode_mse; dH and lddh are
+ * OUTPUT; Z and ldz are nullable and read, as in sea_decode_mse.  Rows as in sea_decode_member_sse: row m belongs to member m / P and patch m % P, and
+ * the `members` consecutive members of one history share one observation: trow(m) = ((m / P) / members) * P + m % P.  Per group, j < n_fields, c < C,
+ * f = field0 + j:
+ *     Y[m, j, c]      = sum_s H[m, s] W2[j Cp + c, s] + bias[j Cp + c]                                      (fp32 accumulation)
+ *     pw              = prec == NULL ? 1 : prec[trow(m), f, c];      fw = field_prec == NULL ? 1 : field_prec[f]
+ *     w               = valid(m, c) && pw > 0 && fw > 0 ? fw * pw : 0                   (selects: NaN, a negative value, Inf * 0 give 0)
+ *     d               = w > 0 ? Y[m, j, c] - obs[trow(m), f, c] : 0                     (a select: NaN / Inf in obs is neutral without weight)
+ *     wsse[m / P, f]  = sum over the member's P rows and c of (w d) d                   (f32 [M / P, n_fields_total], every element written)
+ *     r               = act(w d)                                                       (rounded ONCE between the two products, as sea_decode_mse rounds its residual)
+ *     dH[m, s]        = 2 grad_scale * sum_{j, c} r[m, j, c] W2[j Cp + c, s]   [* gelu_erf'(Z[m, s]) when Z != NULL]          (written in the act dtype)
+ * valid(m, c) and the clamping of counts are exactly those of sea_decode_mse (c < C when counts == NULL, else c < counts[m % P], clamped to [0, C]).
+ * obs element (r, f, c) is at obs + r ld_row + f ld_field + c; prec, when given, is an f32 map with the SAME strides; only c < C is ever read of
+ * either.  field_prec: device f32 [n_fields_total] or NULL.  A row without a weighted cell gets dH = 0 exactly.
+ * dH is all-or-nothing: with dH == NULL in EVERY group the launch is score-only (the second product is compiled out; Z, lddh, ldz are not read) and
+ * wsse has the bits of the gradient launch; NULL in some groups but not all is refused.
+ * work: f32 workspace of work_cap >= M * n_fields_total floats, private to the call: the main kernel writes the per-row, per-field sums there when the
+ * tile walk crosses a field boundary (the four lanes that hold a row's columns folded first, as sea_decode_member_sse does), the finish launch adds
+ * the P rows of a member.  One writer per dH and wsse element, no atomics: two runs give the same bits, and a member's dH rows and wsse row do not
+ * depend on `members`, on the number of histories or on the 64-row tile the member falls into.
+ * Requirements: dtype SEA_BF16 (SEA_F32 returns SEA_EUNSUPPORTED); M >= 1; S a multiple of 8, at most 640 (above: SEA_EUNSUPPORTED), padded by
+ * masking; Cp a multiple of 32, 1 <= C <= Cp; P >= 1, members >= 1, M % (P * members) == 0; ld_row, ld_field multiples of 4; obs, prec 16-byte,
+ * field_prec, counts, wsse, work 4-byte aligned; per group H, W2, bias non-NULL and 16-byte aligned, ldh, ldw multiples of 8 and >= S; with dH: dH
+ * (and Z, when given) 16-byte aligned, lddh even and >= S, ldz >= S; the groups' field ranges cover 0 .. n_fields_total-1 exactly once;
+ * grad_scale finite; 1 <= n_groups <= SEA_DECODE_MSE_MAX_GROUPS.
+ * Returns -1, with the entry point and the offending group named in sea_last_error(), otherwise; nothing touches a device before the checks pass.
+ * One kernel form ("field_grad.rows64" in sea_last_form; a = 1 with the gradient, 0 score-only): 64 rows per workgroup, 4 waves of 16 rows, SP / 8
+ * fragment registers and, with the gradient, SP / 4 fp32 dH accumulators per lane; every SP in {128, 256, 384, 512, 640} compiles without scratch
+ * (DESIGN.md section 7m has the register table), so S up to 640 is served as by sea_decode_mse.
+ * (An addition to ABI version 8.  sea_struct_sizes() keeps its 33 entries, SeaKvFork last: sizeof(SeaDecodeFieldGrad) is 104.)
+ */
+typedef struct {
+    const float* obs;          /* f32, rows of the observation: [M / (P * members) * P, n_fields_total, >= C] through ld_row, ld_field */
+    const float* prec;         /* f32 map with obs's strides, or NULL (1) */
+    const float* field_prec;   /* f32 [n_fields_total], or NULL (1) */
+    const int32_t* counts;     /* device int32 [P] or NULL */
+    float* wsse;               /* f32 [M / P, n_fields_total] (output) */
+    float* work;               /* f32 [work_cap] workspace, >= M * n_fields_total */
+    int64_t ld_row, ld_field, work_cap;
+    int32_t M, S, C, Cp, P, members, n_fields_total;
+    float grad_scale;          /* dH = 2 grad_scale * (...) */
+} SeaDecodeFieldGrad;        /* 104 bytes */
+int sea_decode_field_grad(const SeaDecodeMseGroup* groups, int n_groups, const SeaDecodeFieldGrad* p, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Systematic resampling of an ensemble, gated by the effective sample size, in one launch: log-weights in, the int32 device index that
  * sea_kv_cache_gather (RolloutSession.resample / select) takes out.  G histories with n members each, one workgroup per history, all sums in fp64.
  * Per history g (member j is element g n + j):

@@ -314,6 +314,13 @@ class SeaDecodeSensorGrad(C.Structure):
     _fields_ = SeaDecodeSensorSse._fields_ + [("grad_scale", _f32), ("pad_", _i32)]
 
 
+class SeaDecodeFieldGrad(C.Structure):
+    # sea_decode_field_grad, 104 bytes (not in ABI_STRUCTS, like its siblings; tests/test_field_grad_cpu.py checks the layout through the library's argument checks)
+    _fields_ = [("obs", _vp), ("prec", _vp), ("field_prec", _vp), ("counts", _vp), ("wsse", _vp), ("work", _vp),
+                ("ld_row", _i64), ("ld_field", _i64), ("work_cap", _i64),
+                ("M", _i32), ("S", _i32), ("C", _i32), ("Cp", _i32), ("P", _i32), ("members", _i32), ("n_fields_total", _i32), ("grad_scale", _f32)]
+
+
 class SeaEnkfTransform(C.Structure):
     # sea_enkf_transform (not in ABI_STRUCTS, like its siblings; tests/test_enkf_cpu.py checks the layout through the library's argument checks)
     _fields_ = [("pred", _vp), ("obs", _vp), ("prec", _vp), ("taper", _vp), ("D", _vp), ("status", _vp),
@@ -481,6 +488,8 @@ def lib() -> C.CDLL:
     L.sea_decode_sensor_sse.restype = C.c_int
     L.sea_decode_sensor_grad.argtypes = [C.POINTER(SeaDecodeMseGroup), C.c_int, C.POINTER(SeaDecodeSensorGrad), C.c_int, _vp]
     L.sea_decode_sensor_grad.restype = C.c_int
+    L.sea_decode_field_grad.argtypes = [C.POINTER(SeaDecodeMseGroup), C.c_int, C.POINTER(SeaDecodeFieldGrad), C.c_int, _vp]
+    L.sea_decode_field_grad.restype = C.c_int
     L.sea_decode_member_moments.argtypes = [C.POINTER(SeaDecodeMseGroup), C.c_int, C.POINTER(SeaDecodeMemberMoments), C.c_int, _vp]
     L.sea_decode_member_moments.restype = C.c_int
     L.sea_resample_systematic.argtypes = [_vp, _vp, C.c_float, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]
@@ -534,7 +543,7 @@ EXPORTED_SYMBOLS = (
     "sea_mse_fwd_bwd", "sea_relative_mse", "sea_adamw_flat", "sea_grad_norm_ctl", "sea_adamw_flat_ctl",
     "sea_wgrad_grouped", "sea_transpose_weights", "sea_rownorm_bwd", "sea_silu_outer_bwd", "sea_ib_bwd",
     "sea_attention_bwd", "sea_dropout_mask", "sea_run_list", "sea_run_list_steps", "sea_unpatchify", "sea_gemm_rownorm", "sea_exchange_tail", "sea_patchify", "sea_silu_outer_ib", "sea_mlp_fc1_ln_gelu", "sea_mlp_fc2_proj_norm", "sea_kv_rollout", "sea_kv_arena_words", "sea_kv_debug_stamps",
-    "sea_kv_cache_fill", "sea_kv_cache_fork", "sea_kv_cache_gather", "sea_decode_mse", "sea_decode_member_sse", "sea_decode_member_moments", "sea_decode_sensor_sse", "sea_decode_sensor_grad", "sea_resample_systematic", "sea_enkf_transform", "sea_enkf_transform_gram", "sea_decode_member_gram", "sea_ensemble_mix", "sea_ensemble_verify", "sea_ensemble_verify_ws_bytes", "sea_decode_member_verify", "sea_decode_member_verify_ws_bytes", "sea_decode_member_quantiles",
+    "sea_kv_cache_fill", "sea_kv_cache_fork", "sea_kv_cache_gather", "sea_decode_mse", "sea_decode_member_sse", "sea_decode_member_moments", "sea_decode_sensor_sse", "sea_decode_sensor_grad", "sea_decode_field_grad", "sea_resample_systematic", "sea_enkf_transform", "sea_enkf_transform_gram", "sea_decode_member_gram", "sea_ensemble_mix", "sea_ensemble_verify", "sea_ensemble_verify_ws_bytes", "sea_decode_member_verify", "sea_decode_member_verify_ws_bytes", "sea_decode_member_quantiles",
     "sea_gemm_fewrows", "sea_qkv_rope_fewrows", "sea_row_chain", "sea_row_chain_riders", "sea_gemm_adaln", "sea_mlp_block", "sea_adaln_qkv", "sea_splitk_finish",
     "sea_encoder_block_ws_floats", "sea_encoder_block_fwd", "sea_encoder_block_bwd",
     "sea_silu_outer_bwd_dc", "sea_silu_outer_bwd_dc_ws_floats", "sea_ib_bwd_dc",

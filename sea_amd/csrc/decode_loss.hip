@@ -1376,6 +1376,303 @@ extern "C" int sea_decode_sensor_grad(const SeaDecodeMseGroup* groups, int n_gro
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------------------------
+// sea_decode_field_grad: the DENSE-snapshot score with a per-cell precision map and per-field precisions, per member and field, WITH its gradient to the
+// hidden rows — decode_mse_kernel (both MFMA stages over the same LDS image of W2, the [rows, 32 columns] tile of decoded values in accumulator registers
+// between them) with the epilogue of the ensemble tools between the stages: the weight w = field_prec * prec applied by selects, the member -> observation
+// row map of decode_member_sse_kernel, and per-row, per-field weighted sums in place of one scalar.  The workgroup (64 rows, 4 waves of 16), the H
+// fragments, the SP masking, the two LDS images with the pitch of 2 SP + 32 bytes, both read forms, the prefetch of tile t + 1 around the MFMAs of tile t
+// and the one barrier per tile are decode_mse_kernel's.  Per tile and wave:
+//   before   the lane requests the observation AND the precision of its 2 x 4 columns (one float4 each per sub-tile, where the row has a valid column
+//            there), and reads the field's precision (uniform),
+//   stage 1  decode_mse_kernel's,
+//   between  w = valid && pw > 0 && fw > 0 ? fw pw : 0;  d = w > 0 ? y - obs : 0  (selects: NaN, a negative value or Inf * 0 give no weight, and a cell
+//            without weight is neutral whatever obs holds);  the lane's field sum += (w d) d in fp32;  r = bf16(w d), rounded ONCE: the A fragment of
+//   stage 2  decode_mse_kernel's, into the wave's [16, SP] fp32 slice of dH.
+// When the tile walk crosses a field boundary the lane's sum is folded over the four lanes that hold the row's columns (two butterfly steps, as
+// decode_member_sse_kernel) and lane group 0 writes work[m, field0 + j]; member_sse_finish_kernel then adds the P rows of a member.  GRAD = false is the
+// score-only form (no dH accumulators, no stage 2): the same stage 1 and the same epilogue arithmetic in the same order, so the score has the bits of
+// the gradient launch.  One writer per dH and work element, no atomics: two runs give the same bits; a row of an MFMA result depends on its own operand
+// row only, so a member's dH rows and wsse row do not depend on `members`, on the number of histories or on the 64-row tile the member falls into.
+struct FieldGradLaunch {
+    SeaDecodeMseGroup g[SEA_DECODE_MSE_MAX_GROUPS];
+    SeaDecodeFieldGrad p;
+};
+
+template <int SP, bool GRAD>
+__global__ __launch_bounds__(256) void decode_field_grad_kernel(const FieldGradLaunch L) {
+#pragma clang fp reassociate(off)   // the lane's sum runs over its columns in the stated order, in both forms
+    constexpr int KS = SP / 32;
+    constexpr int ST = GRAD ? SP / 16 : 1;
+    constexpr int PITCH = SP * 2 + DM_PAD;
+    constexpr int TILE = DM_TC * PITCH;
+    constexpr int NCH = DM_TC * (SP / 8) / 256;
+    static_assert(NCH * 256 == DM_TC * (SP / 8), "whole chunks per thread");
+    extern __shared__ __attribute__((aligned(16))) char smem[];   // 2 tile images
+
+    const SeaDecodeMseGroup& G = L.g[blockIdx.y];
+    const SeaDecodeFieldGrad& P = L.p;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, lg = lane >> 4;
+    const int M = P.M, S = P.S, C = P.C, Cp = P.Cp;
+    const int row0 = blockIdx.x * DM_ROWS + wave * 16;
+    const int m = row0 + li;   // the row this lane holds in the H fragments, in the stage-1 result and in the residual fragment
+    const __bf16* H = static_cast<const __bf16*>(G.H);
+    const __bf16* W2 = static_cast<const __bf16*>(G.W2);
+
+    // valid columns of this lane's row: [0, lim); its row of the observation: the `members` consecutive members of a history share one
+    int lim = 0;
+    int64_t tr = 0;
+    if (m < M) {
+        const int mem = m / P.P, patch = m - mem * P.P;
+        lim = C;
+        if (P.counts != nullptr) {
+            const int cnt = P.counts[patch];
+            lim = cnt < 0 ? 0 : (cnt > C ? C : cnt);
+        }
+        tr = (int64_t)(mem / P.members) * P.P + patch;
+    }
+
+    uint4 hf[KS];
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+        const int s = ks * 32 + 8 * lg;
+        hf[ks] = make_uint4(0u, 0u, 0u, 0u);   // (not a ternary over two lvalues: that selects between ADDRESSES and puts the zero into scratch)
+        if (m < M && s < S) hf[ks] = *reinterpret_cast<const uint4*>(H + (int64_t)m * G.ldh + s);
+    }
+    f32x4 dh[ST];
+#pragma unroll
+    for (int st = 0; st < ST; ++st) dh[st] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    const int tpf = (C + DM_TC - 1) / DM_TC;   // tiles of a field that hold real columns
+    const int n_tiles = G.n_fields * tpf;
+    uint4 wr[NCH];
+    dm_load_tile<SP>(wr, W2, G.ldw, S, Cp, tpf, 0, tid);
+    dm_store_tile<SP>(wr, smem, tid);
+    __syncthreads();
+
+    float fsum = 0.f;
+    const float* orow = P.obs + tr * P.ld_row;
+    const float* prow = P.prec != nullptr ? P.prec + tr * P.ld_row : nullptr;
+    float* wrow = P.work + (int64_t)(m < M ? m : 0) * P.n_fields_total + G.field0;
+    typedef dm_s16x4 __attribute__((address_space(3))) * lds_p;
+    int j = 0, tj = 0;   // field of tile t and the tile's index inside it
+    for (int t = 0; t < n_tiles; ++t) {
+        const char* buf = smem + (t & 1) * TILE;
+        if (t + 1 < n_tiles) dm_load_tile<SP>(wr, W2, G.ldw, S, Cp, tpf, t + 1, tid);
+        const int cb = tj * DM_TC;
+
+        // observation and precision of this lane's 2 x 4 columns (requested now, used after stage 1); a slot that is not read holds obs 0, precision 0
+        float ob[2][4], pw[2][4];
+        const int64_t foff = (int64_t)(G.field0 + j) * P.ld_field;
+        const float fw = P.field_prec != nullptr ? P.field_prec[G.field0 + j] : 1.f;
+#pragma unroll
+        for (int sub = 0; sub < 2; ++sub) {
+            const int c = cb + sub * 16 + 4 * lg;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                ob[sub][r] = 0.f;
+                pw[sub][r] = 0.f;
+            }
+            if (c < lim) {
+                if (c + 4 <= C) {
+                    const float4 v = *reinterpret_cast<const float4*>(orow + foff + c);
+                    ob[sub][0] = v.x; ob[sub][1] = v.y; ob[sub][2] = v.z; ob[sub][3] = v.w;
+                    float4 q = make_float4(1.f, 1.f, 1.f, 1.f);
+                    if (prow != nullptr) q = *reinterpret_cast<const float4*>(prow + foff + c);
+                    pw[sub][0] = q.x; pw[sub][1] = q.y; pw[sub][2] = q.z; pw[sub][3] = q.w;
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        if (c + r < C) {
+                            ob[sub][r] = orow[foff + c + r];
+                            pw[sub][r] = prow != nullptr ? prow[foff + c + r] : 1.f;
+                        }
+                }
+            }
+        }
+
+        // stage 1
+        f32x4 acc[2][2];
+#pragma unroll
+        for (int sub = 0; sub < 2; ++sub) {
+            const float4 b = *reinterpret_cast<const float4*>(G.bias + j * Cp + cb + sub * 16 + 4 * lg);
+            acc[sub][0] = f32x4{b.x, b.y, b.z, b.w};
+            acc[sub][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+            if (ks * 32 < S) {
+#pragma unroll
+                for (int sub = 0; sub < 2; ++sub) {
+                    const uint4 a = *reinterpret_cast<const uint4*>(buf + (sub * 16 + li) * PITCH + (ks * 4 + lg) * 16);
+                    mma16<__bf16>(a, hf[ks], acc[sub][ks & 1]);
+                }
+            }
+        }
+
+        // weight and residual by selects, the field's weighted square sum, the weighted residual rounded once
+        bf16x8 dfr;
+#pragma unroll
+        for (int sub = 0; sub < 2; ++sub) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int c = cb + sub * 16 + 4 * lg + r;
+                const float p = pw[sub][r];
+                const float w = (c < lim && p > 0.f && fw > 0.f) ? mul1(fw, p) : 0.f;
+                const float y = acc[sub][0][r] + acc[sub][1][r];
+                const float d = w > 0.f ? y - ob[sub][r] : 0.f;
+                const float wd = mul1(w, d);
+                fsum = fma1(wd, d, fsum);
+                dfr[sub * 4 + r] = (__bf16)wd;
+            }
+        }
+
+        if (GRAD) {   // stage 2
+            const uint4 da = __builtin_bit_cast(uint4, dfr);
+            const char* tb = buf + (4 * lg + (li >> 2)) * PITCH + (4 * (li & 3)) * 2;
+#pragma unroll
+            for (int st = 0; st < ST; ++st) {
+                if (st * 16 < S) {
+                    const dm_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(tb + st * 32));
+                    const dm_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(tb + st * 32 + 16 * PITCH));
+                    const uint2 l2 = __builtin_bit_cast(uint2, lo), h2 = __builtin_bit_cast(uint2, hi);
+                    mma16<__bf16>(da, make_uint4(l2.x, l2.y, h2.x, h2.y), dh[st]);
+                }
+            }
+        }
+
+        if (++tj == tpf) {   // the field is complete (uniform over the workgroup): fold the row's four lanes, one writer
+            float v = fsum;
+            v += __shfl_xor(v, 16);
+            v += __shfl_xor(v, 32);
+            if (lg == 0 && m < M) wrow[j] = v;
+            fsum = 0.f;
+            tj = 0;
+            ++j;
+        }
+
+        if (t + 1 < n_tiles) dm_store_tile<SP>(wr, smem + ((t + 1) & 1) * TILE, tid);
+        __syncthreads();
+    }
+
+    if (GRAD) {   // dH: register r of tile st is row 4 g + r of the wave, column 16 st + (lane & 15)
+        const float scale = 2.0f * P.grad_scale;
+        __bf16* dH = static_cast<__bf16*>(G.dH);
+        const __bf16* Z = static_cast<const __bf16*>(G.Z);
+#pragma unroll
+        for (int st = 0; st < ST; ++st) {
+            const int s = st * 16 + li;
+            if (s < S) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int mr = row0 + 4 * lg + r;
+                    if (mr < M) {
+                        float v = dh[st][r] * scale;
+                        if (Z != nullptr) v *= gelu_grad_for<__bf16>((float)Z[(int64_t)mr * G.ldz + s]);
+                        dH[(int64_t)mr * G.lddh + s] = (__bf16)v;
+                    }
+                }
+            }
+        }
+    }
+}
+
+template <int SP, bool GRAD>
+static void field_grad_launch(const FieldGradLaunch& L, dim3 grid, hipStream_t s) {
+    constexpr int lds = 2 * DM_TC * (SP * 2 + DM_PAD);
+    static bool set_on[64] = {false};   // per device: SP = 640 needs 84 kB, above the 64 kB a kernel gets without the attribute
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = -1;
+    if (dev < 0 || !set_on[dev]) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(decode_field_grad_kernel<SP, GRAD>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        if (dev >= 0) set_on[dev] = true;
+    }
+    decode_field_grad_kernel<SP, GRAD><<<grid, dim3(256), lds, s>>>(L);
+}
+
+template <bool GRAD>
+static void field_grad_dispatch(const FieldGradLaunch& L, dim3 grid, hipStream_t s) {
+    const int S = L.p.S;
+    if (S <= 128) field_grad_launch<128, GRAD>(L, grid, s);
+    else if (S <= 256) field_grad_launch<256, GRAD>(L, grid, s);
+    else if (S <= 384) field_grad_launch<384, GRAD>(L, grid, s);
+    else if (S <= 512) field_grad_launch<512, GRAD>(L, grid, s);
+    else field_grad_launch<640, GRAD>(L, grid, s);
+}
+
+extern "C" int sea_decode_field_grad(const SeaDecodeMseGroup* groups, int n_groups, const SeaDecodeFieldGrad* p, int dtype, void* stream) {
+    SEA_REQUIRE(groups != nullptr && p != nullptr, "sea_decode_field_grad: null argument table");
+    SEA_REQUIRE(n_groups >= 1 && n_groups <= SEA_DECODE_MSE_MAX_GROUPS, "sea_decode_field_grad: n_groups=%d outside 1..%d", n_groups, SEA_DECODE_MSE_MAX_GROUPS);
+    SEA_REQUIRE(dtype == SEA_F32 || dtype == SEA_BF16, "sea_decode_field_grad: bad dtype %d", dtype);
+    if (dtype != SEA_BF16) {
+        sea_set_error("sea_decode_field_grad: unsupported: bf16 only (the fp32 decoder composes sea_gemm_grouped and reductions under autograd)");
+        return SEA_EUNSUPPORTED;
+    }
+    const SeaDecodeFieldGrad& P = *p;
+    SEA_REQUIRE(P.obs != nullptr && P.wsse != nullptr && P.work != nullptr, "sea_decode_field_grad: null obs, wsse or work pointer");
+    SEA_REQUIRE(P.M >= 1, "sea_decode_field_grad: M=%d must be positive", P.M);
+    SEA_REQUIRE(P.S >= 8 && P.S % 8 == 0, "sea_decode_field_grad: S=%d must be a positive multiple of 8", P.S);
+    SEA_REQUIRE(P.Cp >= 32 && P.Cp % 32 == 0, "sea_decode_field_grad: Cp=%d must be a positive multiple of 32", P.Cp);
+    SEA_REQUIRE(P.C >= 1 && P.C <= P.Cp, "sea_decode_field_grad: C=%d must lie in 1..Cp=%d", P.C, P.Cp);
+    SEA_REQUIRE(P.P >= 1 && P.members >= 1, "sea_decode_field_grad: P=%d and members=%d must be positive", P.P, P.members);
+    SEA_REQUIRE((int64_t)P.M % ((int64_t)P.P * P.members) == 0, "sea_decode_field_grad: M=%d is not a multiple of P * members = %d * %d", P.M, P.P, P.members);
+    SEA_REQUIRE(P.n_fields_total >= 1, "sea_decode_field_grad: n_fields_total=%d must be positive", P.n_fields_total);
+    SEA_REQUIRE(P.work_cap >= (int64_t)P.M * P.n_fields_total, "sea_decode_field_grad: workspace of %lld floats is too small: %lld needed (M * n_fields_total)",
+                (long long)P.work_cap, (long long)((int64_t)P.M * P.n_fields_total));
+    SEA_REQUIRE(P.ld_row >= 0 && P.ld_row % 4 == 0 && P.ld_field >= 0 && P.ld_field % 4 == 0,
+                "sea_decode_field_grad: obs strides ld_row=%lld, ld_field=%lld must be multiples of 4", (long long)P.ld_row, (long long)P.ld_field);
+    SEA_REQUIRE(sea_aligned16(P.obs) && sea_aligned16(P.prec), "sea_decode_field_grad: obs and prec must be 16-byte aligned");
+    SEA_REQUIRE(sea_aligned4(P.field_prec) && sea_aligned4(P.counts) && sea_aligned4(P.wsse) && sea_aligned4(P.work),
+                "sea_decode_field_grad: misaligned field_prec, counts, wsse or work pointer");
+    uint32_t gs_bits;
+    memcpy(&gs_bits, &P.grad_scale, sizeof(gs_bits));
+    SEA_REQUIRE((gs_bits & 0x7f800000u) != 0x7f800000u, "sea_decode_field_grad: grad_scale must be finite");   // the exponent field itself: no floating-point compare to reason about
+    int64_t covered = 0;
+    int with_dh = 0;
+    for (int g = 0; g < n_groups; ++g) with_dh += groups[g].dH != nullptr ? 1 : 0;
+    for (int g = 0; g < n_groups; ++g) {
+        const SeaDecodeMseGroup& G = groups[g];
+        SEA_REQUIRE(G.H != nullptr && G.W2 != nullptr && G.bias != nullptr, "sea_decode_field_grad: group %d: null pointer (H, W2 or bias)", g);
+        SEA_REQUIRE(with_dh == 0 || G.dH != nullptr, "sea_decode_field_grad: group %d: dH is NULL but %d other groups carry one (all groups, or none for the score alone)", g, with_dh);
+        SEA_REQUIRE(sea_aligned16(G.H) && sea_aligned16(G.W2) && sea_aligned16(G.bias) && sea_aligned16(G.dH), "sea_decode_field_grad: group %d: pointers must be 16-byte aligned", g);
+        SEA_REQUIRE(G.ldh >= P.S && G.ldh % 8 == 0 && G.ldw >= P.S && G.ldw % 8 == 0,
+                    "sea_decode_field_grad: group %d: row strides ldh=%d ldw=%d must cover S=%d and be multiples of 8", g, G.ldh, G.ldw, P.S);
+        if (with_dh != 0) {
+            SEA_REQUIRE(sea_aligned16(G.Z), "sea_decode_field_grad: group %d: Z must be 16-byte aligned", g);
+            SEA_REQUIRE(G.lddh >= P.S && G.lddh % 2 == 0 && (G.Z == nullptr || G.ldz >= P.S),
+                        "sea_decode_field_grad: group %d: row strides lddh=%d ldz=%d must cover S=%d (lddh even)", g, G.lddh, G.ldz, P.S);
+        }
+        SEA_REQUIRE(G.n_fields >= 1 && G.field0 >= 0 && (int64_t)G.field0 + G.n_fields <= P.n_fields_total,
+                    "sea_decode_field_grad: group %d: n_fields=%d, field0=%d outside the %d fields", g, G.n_fields, G.field0, P.n_fields_total);
+        SEA_REQUIRE((int64_t)G.n_fields * P.Cp <= 0x7fffffffLL / 2, "sea_decode_field_grad: group %d: too many output columns", g);
+        for (int h = 0; h < g; ++h)
+            SEA_REQUIRE(G.field0 >= groups[h].field0 + groups[h].n_fields || groups[h].field0 >= G.field0 + G.n_fields,
+                        "sea_decode_field_grad: group %d: its fields overlap those of group %d (every output element has one writer)", g, h);
+        covered += G.n_fields;
+    }
+    SEA_REQUIRE(covered == P.n_fields_total, "sea_decode_field_grad: the groups cover %lld of the %d fields (every field needs exactly one group)", (long long)covered, P.n_fields_total);
+    if (P.S > 640) {
+        sea_set_error("sea_decode_field_grad: unsupported: hidden width S=%d above 640", P.S);
+        return SEA_EUNSUPPORTED;
+    }
+    const int64_t row_blocks = ((int64_t)P.M + DM_ROWS - 1) / DM_ROWS;
+    const int64_t n_out = (int64_t)(P.M / P.P) * P.n_fields_total;
+    SEA_REQUIRE(row_blocks <= 0x7fffffffLL && (n_out + 3) / 4 <= 0x7fffffffLL, "sea_decode_field_grad: too many rows");
+
+    FieldGradLaunch L;
+    memset(&L, 0, sizeof(L));
+    for (int g = 0; g < n_groups; ++g) L.g[g] = groups[g];
+    L.p = P;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)row_blocks, (unsigned)n_groups);
+    if (with_dh != 0) field_grad_dispatch<true>(L, grid, s);
+    else field_grad_dispatch<false>(L, grid, s);
+    sea_note_form("field_grad.rows64", with_dh != 0 ? 1 : 0, 0);
+    member_sse_finish_kernel<<<dim3((unsigned)((n_out + 3) / 4)), dim3(256), 0, s>>>(P.work, P.wsse, n_out, P.P, P.n_fields_total);
+    SEA_CHECK_LAUNCH("sea_decode_field_grad");
+    return SEA_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------------------------
 // sea_decode_member_gram: what the ensemble Kalman analysis needs from a DENSE observation of the decoded fields — per (history, patch) the N x N Gram
 // matrix of the members' weighted decoded anomalies and its product with the innovation (include/sea_hip.h states the formulas).  The walk is
 // decode_member_moments_kernel's: one workgroup of 8 waves serves one (history, patch), wave w decodes the members 16 w .. 16 w + 15 tile by tile (32

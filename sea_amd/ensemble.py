@@ -17,6 +17,14 @@ index itself (the identity where a history was not resampled) and in the returne
 ensemble: the weighted mean and the centred variance of the members' decoded fields (Decode.member_moments; fused: sea_decode_member_moments, the
 members' fields are never written), from the log-weights as they are — normalised with tensor ops, nothing read back.
 
+A GAPPY snapshot — a frame with masked regions, a field known on some cells only — comes with a precision map in obs's shape (0: missing cell,
+neutral by a select whatever obs holds there), and the same object also moves states towards it (Decode.field_loss: sea_decode_field_grad, one
+fused launch for the score and its gradient; members = 1 pulls single trajectories, which neither FieldKalman nor the encoder can):
+
+    logw = like(y, obs, precision)                                # [B * n]: -0.5 * sum_f wsse_f, sigma as a per-field precision
+    logw, dlogw_dy = like.score_and_grad(y, obs, precision)       # ... and the gradient of every member's own log-weight, in y's layout
+    y = ens.step(c_next, state=like.nudge(y, obs, precision, rate=0.25))   # one gradient step towards the frame as the corrected state
+
 Sparse observations — K point sensors, each reading one field at one cell of one patch, with a precision per reading (0: missing) — take the place of
 the dense snapshot through SensorSet and SensorLikelihood:
 
@@ -84,7 +92,11 @@ class FieldLikelihood:
     error of field f over its patches and valid cells (Decode.member_sse); sigma: None (1), a positive number, or n_fields positive numbers (a
     sequence or tensor) — applied with tensor ops on the [B * members, n_fields] result.  counts: valid cells per patch (None: all), as in
     Decode.mse_loss.  fused: None (Decode.member_sse's measured rule), True (the fused launch at any size; bf16 only) or False (the composed path).
-    `decoder` is a sea_amd Decode; no autograd graph is built."""
+    `decoder` is a sea_amd Decode; no autograd graph is built.
+    like(y, obs, precision) takes a precision map for a gappy snapshot — float32 in obs's shape and layout on y's device, >= 0, 0 marking a missing
+    cell — and scores through Decode.field_loss (its measured fused=None rule): logw = -0.5 * sum_f wsse_f with sigma as field_precision = 1 / sigma_f^2.
+    score_and_grad(y, obs, precision) adds the gradient of every member's own log-weight with respect to its state, and nudge(y, obs, precision,
+    rate) takes one gradient step along it; members = 1 is legal (single trajectories pulled towards a gappy frame)."""
 
     def __init__(self, decoder, n_patches: int, members: int, counts=None, layout: str = "BPFC", sigma=None, fused: Optional[bool] = None):
         if layout not in ("BPFC", "BPCF"):
@@ -117,23 +129,90 @@ class FieldLikelihood:
             self._scale = scale
         return self._scale
 
-    def __call__(self, y: torch.Tensor, obs: torch.Tensor, layout: Optional[str] = None) -> torch.Tensor:
+    def _field_prec(self, device):
+        """1 / sigma_f^2 as an f32 [n_fields] tensor on the device (None without sigma): the field_precision of Decode.field_loss, from the same numbers
+        as _field_scale, built once per device with tensor ops."""
+        if self._scale_host is None:
+            return None
+        cur = getattr(self, "_fprec", None)
+        if cur is None or cur.device != device:
+            cur = self._fprec = (self._field_scale(device) * -2.0).contiguous()
+        return cur
+
+    def _operands(self, y, obs, precision, layout):
+        """Checked (Bm, G, E, z view, obs and precision in "BPFC" order)."""
+        if isinstance(precision, str) and layout is None:   # the call's third positional argument used to be the layout
+            precision, layout = None, precision
         layout = self.layout if layout is None else layout
         if layout not in ("BPFC", "BPCF"):
             raise ValueError(f"FieldLikelihood: layout must be 'BPFC' or 'BPCF', got {layout!r}")
         P = self.n_patches
-        if y.dim() != 3 or y.shape[-1] % P or y.shape[0] < 1:
-            raise ValueError(f"FieldLikelihood: y must be [B * members, n_groups, n_patches * D] with n_patches = {P}, got {tuple(y.shape)}")
+        if not torch.is_tensor(y) or y.dim() != 3 or y.shape[-1] % P or y.shape[0] < 1:
+            raise ValueError(f"FieldLikelihood: y must be [B * members, n_groups, n_patches * D] with n_patches = {P}, got "
+                             f"{tuple(y.shape) if torch.is_tensor(y) else type(y).__name__}")
         Bm, G, E = y.shape
         if Bm % self.members:
             raise ValueError(f"FieldLikelihood: the {Bm} trajectories of y are not a multiple of members = {self.members}")
         B = Bm // self.members
-        if obs.dim() != 4 or tuple(obs.shape[:2]) != (B, P):
-            raise ValueError(f"FieldLikelihood: the observation must be [{B}, {P}, ...] in layout {layout} (one per history), got {tuple(obs.shape)}")
+        if not torch.is_tensor(obs) or obs.dim() != 4 or tuple(obs.shape[:2]) != (B, P):
+            raise ValueError(f"FieldLikelihood: the observation must be [{B}, {P}, ...] in layout {layout} (one per history), got "
+                             f"{tuple(obs.shape) if torch.is_tensor(obs) else type(obs).__name__}")
+        if precision is not None:
+            if not torch.is_tensor(precision) or tuple(precision.shape) != tuple(obs.shape):
+                raise ValueError(f"FieldLikelihood: precision must be None or a map of obs's shape {tuple(obs.shape)}, got "
+                                 f"{tuple(precision.shape) if torch.is_tensor(precision) else type(precision).__name__}")
+            if precision.dtype != torch.float32:
+                raise ValueError(f"FieldLikelihood: precision must be float32, got {precision.dtype}")
+            if precision.device.type == "cpu" and (not bool(torch.isfinite(precision).all()) or not bool((precision >= 0).all())):
+                raise ValueError("FieldLikelihood: precision must be finite and >= 0")
+            if precision.device != y.device:
+                raise ValueError(f"FieldLikelihood: precision is on {precision.device}, the states on {y.device}")
+        perm = (lambda t: t) if layout == "BPFC" else (lambda t: t.permute(0, 1, 3, 2))
         z = y.reshape(Bm, G, P, E // P).permute(0, 2, 1, 3)          # the re-layout of inverse_transform_processed_data, one snapshot per member
-        tgt = obs if layout == "BPFC" else obs.permute(0, 1, 3, 2)
-        sse = self.decoder.member_sse(z, tgt, counts=self.counts, members=self.members, fused=self.fused)
-        return (sse * self._field_scale(sse.device)).sum(1)
+        return Bm, G, E, z, perm(obs), None if precision is None else perm(precision)
+
+    def __call__(self, y: torch.Tensor, obs: torch.Tensor, precision: Optional[torch.Tensor] = None, layout: Optional[str] = None) -> torch.Tensor:
+        """Log-weights [B * members].  precision: None — the squared error over the valid cells (Decode.member_sse) — or a float32 map of obs's shape
+        on y's device, >= 0, 0 marking a missing cell (neutral by a select, NaN in obs there included): logw = -0.5 * sum_f wsse_f with sigma entering
+        as field_precision = 1 / sigma_f^2 (Decode.field_loss, score-only)."""
+        Bm, G, E, z, tgt, prec = self._operands(y, obs, precision, layout)
+        if prec is None:
+            sse = self.decoder.member_sse(z, tgt, counts=self.counts, members=self.members, fused=self.fused)
+            return (sse * self._field_scale(sse.device)).sum(1)
+        with torch.no_grad():
+            wsse = self.decoder.field_loss(z.detach(), tgt.detach(), members=self.members, counts=self.counts, precision=prec.detach(),
+                                           field_precision=self._field_prec(y.device), fused=self.fused)
+            return -0.5 * wsse.sum(1)
+
+    def score_and_grad(self, y: torch.Tensor, obs: torch.Tensor, precision: Optional[torch.Tensor] = None, layout: Optional[str] = None):
+        """(logw [Bm], dlogw_dy [Bm, n_groups, P * D] fp32): the log-weights logw = -0.5 * sum_f wsse_f (sigma as field_precision = 1 / sigma_f^2; with
+        a precision map the bits of __call__ on the same path) and the gradient of every member's OWN log-weight with respect to its state, in y's
+        layout (the inverse of the re-layout __call__ applies) — Decode.field_loss's one pass.  precision as in __call__; None: every valid cell with
+        weight 1.  members = 1 is the pull of single trajectories towards a gappy frame.  The graph is local to the call (y is detached); nothing is
+        read back."""
+        Bm, G, E, z, tgt, prec = self._operands(y, obs, precision, layout)
+        dec = self.decoder
+        pf = self._field_prec(y.device)
+        tgt, prec = tgt.detach(), None if prec is None else prec.detach()
+        with torch.enable_grad():
+            zz = z.detach().to(torch.float32).contiguous().requires_grad_(True)
+            wsse = dec.field_loss(zz, tgt, members=self.members, counts=self.counts, precision=prec, field_precision=pf, fused=self.fused)
+            (dz,) = torch.autograd.grad(wsse.sum(), zz)
+            wsse = wsse.detach()
+        return -0.5 * wsse.sum(1), (-0.5 * dz.to(torch.float32)).permute(0, 2, 1, 3).reshape(Bm, G, E)
+
+    def nudge(self, y: torch.Tensor, obs: torch.Tensor, precision: Optional[torch.Tensor] = None, rate=1.0, layout: Optional[str] = None) -> torch.Tensor:
+        """y + rate * dlogw_dy, in y's dtype: one gradient step on every member's log-likelihood of the snapshot — a corrected state for
+        RolloutSession.step(c, state=...).  rate: a number, or a float32 [Bm] tensor on y's device (one step length per member)."""
+        if torch.is_tensor(rate):
+            if not torch.is_tensor(y) or rate.dim() != 1 or rate.shape[0] != y.shape[0] or rate.dtype != torch.float32 or rate.device != y.device:
+                raise ValueError(f"FieldLikelihood.nudge: a rate tensor must be float32 [{y.shape[0] if torch.is_tensor(y) else 'Bm'}] on the states' device, got "
+                                 f"{tuple(rate.shape)} {rate.dtype} on {rate.device}")
+            rate = rate.detach().view(-1, 1, 1)
+        elif isinstance(rate, bool) or not isinstance(rate, (int, float)) or not math.isfinite(rate):
+            raise ValueError(f"FieldLikelihood.nudge: rate must be a finite number or a float32 [Bm] tensor, got {rate!r}")
+        _, grad = self.score_and_grad(y, obs, precision, layout=layout)
+        return (y.detach().to(torch.float32) + rate * grad).to(y.dtype)
 
 
 def normalised_weights(logw: torch.Tensor, members: int) -> torch.Tensor:

@@ -436,6 +436,140 @@ class Decode(nn.Module):
                 dz.index_copy_(1, T["patches"], self._input_grad(dpre, dt).view(Q, Bm, G, D).permute(1, 0, 2, 3))
             return wsse, pred, dz
 
+    def field_loss(self, z: torch.Tensor, obs: torch.Tensor, members: int = 1, counts=None, precision: Optional[torch.Tensor] = None,
+                   field_precision: Optional[torch.Tensor] = None, fused: Optional[bool] = None) -> torch.Tensor:
+        """The DENSE-snapshot score with a precision map, per member and field, WITH a gradient to z: wsse fp32 [B * members, n_fields],
+        wsse[bm, f] = sum over the member's patches and cells of w (y - obs)^2, as a differentiable tensor — gradient flows to z only (the decoder is a
+        frozen observation operator: a parameter that requires grad is refused; obs, precision and field_precision must not require grad).
+        z [B * members, P, n_groups, embed_dim] in fork() order (row b * members + j is member j of history b); obs float32 [B, P, n_fields, C >= n_inp]
+        on z's device, one snapshot per history; members >= 1 (members = 1: one trajectory per snapshot); counts as in mse_loss (all-zero counts are
+        accepted); precision: None or a float32 map of obs's shape, 0 marks a missing cell; field_precision: None or float32 [n_fields] on z's
+        device.  The weight of a cell is w = valid && precision > 0 && field_precision > 0 ? field_precision * precision : 0, by selects: a cell
+        without weight is neutral whatever obs and precision hold there, NaN included, and a patch without a weighted cell gets a gradient of
+        exactly 0 (include/sea_hip.h, sea_decode_field_grad, states the formulas).
+        Upstream gradients.  wsse[bm, f] depends on z[bm, :, g, :] alone, g the group of field f, and forward and backward are ONE pass, as in
+        mse_loss and sensor_loss: the gradient of sum_f wsse[bm, f] is saved at forward and the backward scales it per member AND group.  An upstream
+        gradient may therefore differ between members and between field groups, but must be the same for the fields of one group — a per-field factor
+        inside a group cannot be folded into one saved gradient and belongs into field_precision; where the upstream does differ inside a group the
+        gradient of that member's group slice is NaN (a select on the device, nothing is read back), never a silently wrong number.
+        bf16 compute dtype, fused: the first-layer launch with the pre-activation kept, ONE fused launch (sea_decode_field_grad: score and
+        pre-activation gradient; the weighted residual is rounded to bf16 once between the two products; neither the decoded fields nor their gradient
+        are written) and its finish launch, the data-gradient launch against W1^T.  Under torch.no_grad(), or when z does not require grad, the
+        score-only form of the same launch runs: the same bits, no second product.  fp32, or fused=False: forward() under autograd plus torch ops with
+        the same selects (the composed path; it holds the [B * members, P, n_fields, n_inp] fields and their gradient).
+        fused=None, read from profiles/field_grad_bench.txt (tools/field_grad_bench.py; cylinder and multiphase decoders, 64 members
+        x 64 patches, n_inp 1628, one and four histories; every column valid, the mesh's counts, a 30 %-missing map with and without counts): the fused
+        launch is the default exactly where it is ahead in every measured row —
+          the score alone (no_grad, or z without grad): in bf16 from 4096 rows (B * members * P) on: 0.20 - 0.27 ms against 0.24 - 0.29 ms composed at 4096
+          rows, 0.23 - 0.41 against 0.82 - 0.88 ms at 16384 (8 - 43 MB of extra memory against 307 - 1231 MB);
+          with the gradient: in bf16 from 4096 rows on up to hidden width 512 (cylinder: 0.43 - 0.46 ms against 0.52 - 0.65 ms at 4096 rows, 0.67 - 0.71
+          against 1.94 - 1.98 ms at 16384), and from 16384 rows on above it (multiphase: 0.87 - 0.91 against 1.96 - 2.01 ms; at 4096 rows the two are level,
+          0.55 - 0.58 against 0.55 - 0.60 ms, the fused one behind in two of four rows: the composed path stays the default there; 23 - 117 MB against
+          314 - 1266 MB) —
+        and the composed path below 4096 rows, where nothing has been measured.  fused=True selects the leaner path at any size (bf16 only)."""
+        what = "sea_amd.Decode.field_loss"
+        n_fields = sum(len(g) for g in self.field_groups)
+        C = self.n_inp
+        if not torch.is_tensor(z) or z.dim() != 4 or z.shape[2] != self.num_groups or z.shape[3] != self.embed_dim:
+            raise ValueError(f"{what}: z must be [B * members, P, {self.num_groups}, {self.embed_dim}], got {tuple(z.shape) if torch.is_tensor(z) else type(z).__name__}")
+        Bm, P = z.shape[0], z.shape[1]
+        if not isinstance(members, int) or isinstance(members, bool) or members < 1 or Bm < 1 or Bm % members:
+            raise ValueError(f"{what}: members = {members!r} must be a positive integer that divides the {Bm} rows of z")
+        B = Bm // members
+        for name, t in (("obs", obs), ("precision", precision)):
+            if t is None and name == "precision":
+                continue
+            if not torch.is_tensor(t) or t.dim() != 4 or tuple(t.shape[:3]) != (B, P, n_fields) or t.shape[3] < C:
+                raise ValueError(f"{what}: {name} must be [{B}, {P}, {n_fields}, >= {C}] (one per history of {members} members), got "
+                                 f"{tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
+            if t.dtype != torch.float32 or t.device != z.device:
+                raise ValueError(f"{what}: {name} must be float32 on {z.device}, got {t.dtype} on {t.device}")
+        if precision is not None and precision.shape[3] != obs.shape[3]:
+            raise ValueError(f"{what}: precision must have obs's shape {tuple(obs.shape)}, got {tuple(precision.shape)}")
+        if field_precision is not None and (not torch.is_tensor(field_precision) or field_precision.dtype != torch.float32 or tuple(field_precision.shape) != (n_fields,)
+                                            or field_precision.device != z.device):
+            raise ValueError(f"{what}: field_precision must be None or a float32 [{n_fields}] tensor on {z.device}")
+        if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (obs, precision, field_precision)):
+            raise ValueError(f"{what}: obs, precision and field_precision must not require grad (gradients flow to z only)")
+        self._require_frozen("field_loss")
+        dt = self._act_dtype()
+        if fused is None:
+            fused = self._field_loss_default(dt, Bm * P, z.requires_grad and torch.is_grad_enabled())
+        if fused and dt != torch.bfloat16:
+            raise ValueError(f"{what}: the fused launch is bf16 only (set_compute_dtype('bf16'), or fused=False)")
+        cnt, _ = self._valid_counts(counts, P, z.device, allow_empty=True, what="field_loss")
+        N.require_gpu(z, "Decode.field_loss input")
+        obs = obs.detach()
+        prec = None if precision is None else precision.detach()
+        pf = None if field_precision is None else field_precision.detach().contiguous()
+        want_grad = z.requires_grad and torch.is_grad_enabled()
+        if fused:
+            if want_grad:
+                return _DecodeFieldFn.apply(z, self, obs, prec, pf, cnt, members)
+            return self._field_grad_fused(z, obs, prec, pf, cnt, members, False)[0]
+        zero = torch.zeros((), device=z.device)
+        y = (_DecodeFn.apply(z, self) if want_grad else self.forward(z.detach())).view(B, members, P, n_fields, C)
+        w = torch.ones(B, P, n_fields, C, device=z.device, dtype=torch.float32)
+        live = torch.ones(B, P, n_fields, C, device=z.device, dtype=torch.bool)
+        if pf is not None:
+            w, live = w * pf.view(1, 1, n_fields, 1), live & (pf > 0).view(1, 1, n_fields, 1)
+        if prec is not None:
+            w, live = w * prec[..., :C], live & (prec[..., :C] > 0)
+        if cnt is not None:
+            live = live & (torch.arange(C, device=z.device) < cnt[:, None]).view(1, P, 1, C)
+        w = torch.where(live, w, zero)                                            # NaN, negative values and Inf * 0 give no weight
+        live = (w > 0).unsqueeze(1)
+        d = torch.where(live, y - obs[..., :C].unsqueeze(1), zero)
+        return (w.unsqueeze(1) * d * d).sum(dim=(2, 4)).view(Bm, n_fields)
+
+    def _field_loss_default(self, dt: torch.dtype, rows: int, want_grad: bool) -> bool:
+        """field_loss's fused=None rule, read from profiles/field_grad_bench.txt (tools/field_grad_bench.py): the fused launch is the
+        default exactly where it is ahead in every measured row, and the composed path where it is not or where nothing was measured (below 4096 rows)."""
+        if dt != torch.bfloat16 or rows < 4096:
+            return False
+        return not (want_grad and self.MLP_hidden > 512 and rows < 16384)
+
+    def _field_grad_fused(self, z: torch.Tensor, obs: torch.Tensor, prec: Optional[torch.Tensor], pf: Optional[torch.Tensor], cnt, members: int, want_grad: bool):
+        """The fused bf16 launches of field_loss on checked arguments, without autograd: (wsse [Bm, n_fields], dz f32 [Bm, P, G, D] or None)."""
+        dt = torch.bfloat16
+        with torch.no_grad():
+            Bm, P, G, D = z.shape
+            B, M, C = Bm // members, Bm * P, self.n_inp
+            n_fields = sum(len(g) for g in self.field_groups)
+
+            def rows(t):   # [B * P, n_fields, width]: a view where unit inner stride, strides that are multiples of 4 and a 16-byte base allow it, else None
+                t3 = t.reshape(B * P, n_fields, t.shape[3])
+                ok = t3.stride(2) == 1 and t3.stride(0) % 4 == 0 and t3.stride(1) % 4 == 0 and t3.stride(0) >= 0 and t3.stride(1) >= C and t3.data_ptr() % 16 == 0
+                return t3 if ok else None
+
+            def padded(t):   # one row-aligned copy of the first C columns (an odd cell width, or the reference's [.., C, n_fields] layout seen through a permute)
+                out = torch.zeros(B * P, n_fields, (C + 3) // 4 * 4, device=t.device, dtype=torch.float32)
+                out[..., :C] = t.reshape(B * P, n_fields, t.shape[3])[..., :C]
+                return out
+
+            o3 = rows(obs)
+            p3 = None if prec is None else rows(prec)
+            if o3 is None or (prec is not None and (p3 is None or p3.stride() != o3.stride())):   # the map is addressed through the observation's strides
+                o3, p3 = padded(obs), None if prec is None else padded(prec)
+            _, W2 = self._weights(dt)
+            if want_grad:
+                hid, pre = self._first_layer(z, dt)
+                bias = self._shadow[3]
+                dpre = [torch.empty(M, self.MLP_hidden, device=z.device, dtype=dt) for _ in range(G)]
+                groups = [dict(H=hid[g], W2=W2[g], bias=bias[g], dH=dpre[g], Z=pre[g]) for g in range(G)]
+            else:
+                zf = z.detach().to(torch.float32).contiguous().view(M, G * D)
+                za = torch.empty(M, G * D, device=z.device, dtype=dt)
+                ops.convert(zf, za)
+                W1, _ = self._weights(dt)
+                hid = [torch.empty(M, self.MLP_hidden, device=z.device, dtype=dt) for _ in range(G)]
+                ops.gemm_grouped([dict(A=za[:, g * D:(g + 1) * D], W=W1[g], Cact=hid[g], act=1) for g in range(G)], dt)
+                bias = self._shadow[3]
+                groups = [dict(H=hid[g], W2=W2[g], bias=bias[g]) for g in range(G)]
+            wsse = ops.decode_field_grad(groups, o3, C, self._n_inp_p, P, members=members, prec=p3, field_prec=pf, counts=cnt, dtype=dt)
+            dz = self._input_grad(dpre, dt).view(Bm, P, G, D) if want_grad else None
+            return wsse, dz
+
     def member_moments(self, z: torch.Tensor, members: int, weights: Optional[torch.Tensor] = None, counts=None, unbiased: bool = False,
                        fused: Optional[bool] = None):
         """The forecast of an ensemble: (mean, var) of the decoded fields over the `members` members of every history, each fp32 [B, P, n_fields, n_inp]
@@ -910,6 +1044,35 @@ class _DecodeSensorFn(torch.autograd.Function):
     def backward(ctx, g, *unused):
         (dz,) = ctx.saved_tensors
         return (dz * g.view(-1, 1, 1, 1)).to(dz.dtype), None, None, None, None, None, None
+
+
+class _DecodeFieldFn(torch.autograd.Function):
+    """Decode.field_loss on the fused path (Decode._field_grad_fused): first layer (pre-activation kept), sea_decode_field_grad (score and
+    pre-activation gradient in one launch), data-gradient launch against W1^T.  Forward and backward are one pass, as in _DecodeMseFn: wsse[bm, f]
+    depends on z[bm, :, g, :] only (g the group of field f), so the backward scales the stored dz per member and group; an upstream gradient that
+    differs between the fields of one group cannot be represented by the one stored dz and turns that slice into NaN (a select, nothing read back)."""
+
+    @staticmethod
+    def forward(ctx, z, dec, obs, prec, pf, cnt, members):
+        wsse, dz = dec._field_grad_fused(z, obs, prec, pf, cnt, members, ctx.needs_input_grad[0])
+        if dz is not None:
+            ctx.save_for_backward(dz.to(z.dtype))
+        ctx.groups = [len(g) for g in dec.field_groups]
+        return wsse
+
+    @staticmethod
+    def backward(ctx, g):
+        (dz,) = ctx.saved_tensors
+        if g.stride(1) == 0:   # an expanded upstream (wsse.sum(), c[bm] * wsse.sum(1)): the same for every field by construction
+            return (dz * g[:, 0].view(-1, 1, 1, 1)).to(dz.dtype), None, None, None, None, None, None
+        cols, off = [], 0
+        for n in ctx.groups:
+            first = g[:, off]
+            same = (g[:, off:off + n] == first.unsqueeze(1)).all(dim=1)
+            cols.append(torch.where(same, first, torch.full_like(first, float("nan"))))
+            off += n
+        factor = torch.stack(cols, dim=1).view(dz.shape[0], 1, len(cols), 1)          # [Bm, 1, G, 1]
+        return (dz * factor).to(dz.dtype), None, None, None, None, None, None
 
 
 def _round_up(x: int, m: int) -> int:

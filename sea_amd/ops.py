@@ -1277,6 +1277,109 @@ def decode_sensor_grad(groups: Sequence[Dict], obs: torch.Tensor, live: torch.Te
     return wsse, pred
 
 
+def fill_decode_field_grad(groups_arr, P: N.SeaDecodeFieldGrad, groups: Sequence[Dict], obs, prec, field_prec, counts, n_patches: int, members: int, C_: int, Cp: int,
+                           wsse, work, grad_scale: float) -> None:
+    """The argument table of sea_decode_field_grad.  groups: dicts H act [M, S], W2 act [n_fields * Cp, S], bias f32 [n_fields * Cp], and either in EVERY
+    group or in none dH act [M, S] (output) with an optional Z act [M, S]; group g's fields follow those of the groups before it.  obs: f32
+    [M / members, n_fields_total, >= C] with unit inner stride; prec: None or an f32 map with obs's strides."""
+    field0 = 0
+    for g, d in zip(groups_arr, groups):
+        H, W2, dH, Z = d["H"], d["W2"], d.get("dH"), d.get("Z")
+        g.H, g.W2, g.bias, g.dH, g.Z = H.data_ptr(), W2.data_ptr(), d["bias"].data_ptr(), N.ptr(dH), N.ptr(Z)
+        g.ldh, g.ldw, g.lddh, g.ldz = H.stride(0), W2.stride(0), (dH.stride(0) if dH is not None else 0), (Z.stride(0) if Z is not None else 0)
+        g.n_fields, g.field0 = W2.shape[0] // Cp, field0
+        field0 += g.n_fields
+    P.obs, P.prec, P.field_prec, P.counts, P.wsse, P.work = obs.data_ptr(), N.ptr(prec), N.ptr(field_prec), N.ptr(counts), wsse.data_ptr(), work.data_ptr()
+    P.ld_row, P.ld_field, P.work_cap = obs.stride(0), obs.stride(1), work.numel()
+    P.M, P.S, P.C, P.Cp, P.P = groups[0]["H"].shape[0], groups[0]["H"].shape[1], C_, Cp, n_patches
+    P.members, P.n_fields_total, P.grad_scale = members, field0, grad_scale
+
+
+def decode_field_grad(groups: Sequence[Dict], obs: torch.Tensor, C_: int, Cp: int, n_patches: int, members: int = 1, prec: Optional[torch.Tensor] = None,
+                      field_prec: Optional[torch.Tensor] = None, counts: Optional[torch.Tensor] = None, grad_scale: float = 1.0,
+                      work: Optional[torch.Tensor] = None, dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
+    """sea_decode_field_grad: the weighted squared error of the decoder's second layer against a dense observation per member and field, f32
+    [M / n_patches, n_fields_total], with the weight w = field_prec * prec applied by selects (a cell without positive weight is neutral whatever obs
+    and prec hold there) — and, when the groups carry dH, its gradient to the hidden rows in the same launch: every group's dH act [M, S] is written IN
+    PLACE with 2 grad_scale * (w d rounded to bf16) W2 [* gelu'(Z) where the group carries a Z].  Without a dH in any group the launch is score-only and
+    returns the same bits; dH in some groups only is refused.  groups as fill_decode_field_grad; rows and obs as decode_member_sse; prec: None or a
+    float32 map of obs's shape AND strides; field_prec: None or a contiguous float32 [n_fields_total]; counts: device int32 [n_patches] or None; work:
+    None (allocated here) or a contiguous float32 workspace of at least M * n_fields_total elements.  Everything is checked on the host before the launch."""
+    what = "decode_field_grad"
+    if dtype != torch.bfloat16:
+        raise ValueError(f"{what}: the fused launch is bf16 only, got {dtype}")
+    if not groups or len(groups) > N.DECODE_MSE_MAX_GROUPS:
+        raise ValueError(f"{what}: {len(groups)} groups; a launch carries 1 .. {N.DECODE_MSE_MAX_GROUPS}")
+    if Cp < 32 or Cp % 32 or not 1 <= C_ <= Cp:
+        raise ValueError(f"{what}: need Cp a multiple of 32 and 1 <= C <= Cp, got C = {C_}, Cp = {Cp}")
+    if isinstance(grad_scale, bool) or not isinstance(grad_scale, (int, float)) or not math.isfinite(grad_scale):
+        raise ValueError(f"{what}: grad_scale = {grad_scale!r} must be a finite number")
+    if not torch.is_tensor(obs):
+        raise ValueError(f"{what}: obs must be a tensor, got {type(obs).__name__}")
+    dev = obs.device
+    H0 = groups[0].get("H")
+    M, S = tuple(H0.shape) if torch.is_tensor(H0) and H0.dim() == 2 else (0, 0)
+    if M < 1 or S < 8 or S % 8 or S > N.DECODE_MSE_MAX_S:
+        raise ValueError(f"{what}: H must be [M >= 1, S] with S a multiple of 8 up to {N.DECODE_MSE_MAX_S}, got {tuple(H0.shape) if torch.is_tensor(H0) else H0!r}")
+    if not isinstance(n_patches, int) or not isinstance(members, int) or n_patches < 1 or members < 1:
+        raise ValueError(f"{what}: n_patches = {n_patches!r} and members = {members!r} must be positive integers")
+    if M % (n_patches * members):
+        raise ValueError(f"{what}: {M} rows are not a multiple of n_patches * members = {n_patches} * {members}")
+    with_dh = sum(d.get("dH") is not None for d in groups)
+    if with_dh not in (0, len(groups)):
+        raise ValueError(f"{what}: {with_dh} of the {len(groups)} groups carry a dH: all of them, or none for the score alone")
+    n_fields = 0
+    for i, d in enumerate(groups):
+        for name in ("H", "W2", "dH", "Z"):
+            t = d.get(name)
+            if t is None and (name == "Z" or (name == "dH" and with_dh == 0)):
+                continue
+            if name == "Z" and with_dh == 0:
+                raise ValueError(f"{what} group {i}: a Z without a dH (the score alone reads no pre-activation)")
+            if t is None or t.dim() != 2 or t.stride(1) != 1:
+                raise ValueError(f"{what} group {i}: {name}: need a 2-D tensor with unit inner stride, got "
+                                 f"{'None' if t is None else f'shape {tuple(t.shape)} strides {t.stride()}'}")
+            if t.dtype != dtype or t.device != dev or t.shape[1] != S or (name != "W2" and t.shape[0] != M):
+                raise ValueError(f"{what} group {i}: {name} must be a {dtype} [{'n_fields * Cp' if name == 'W2' else M}, {S}] tensor on {dev}, got "
+                                 f"{tuple(t.shape)} {t.dtype} on {t.device}")
+            if t.stride(0) % 8 or t.stride(0) < S or t.data_ptr() % 16:
+                raise ValueError(f"{what} group {i}: {name} needs a row stride that is a multiple of 8 and covers S = {S}, and a 16-byte-aligned base (stride {t.stride(0)})")
+        W2, b = d["W2"], d["bias"]
+        if W2.shape[0] < Cp or W2.shape[0] % Cp:
+            raise ValueError(f"{what} group {i}: W2 has {W2.shape[0]} rows, not a multiple of Cp = {Cp}")
+        if b.dtype != torch.float32 or b.dim() != 1 or b.shape[0] != W2.shape[0] or not b.is_contiguous() or b.device != dev or b.data_ptr() % 16:
+            raise ValueError(f"{what} group {i}: bias must be a contiguous, 16-byte-aligned float32 [{W2.shape[0]}] on {dev}, got {tuple(b.shape)} {b.dtype}")
+        n_fields += W2.shape[0] // Cp
+    rows = M // members
+    if obs.dtype != torch.float32 or obs.dim() != 3 or obs.shape[0] != rows or obs.shape[1] != n_fields or obs.shape[2] < C_:
+        raise ValueError(f"{what}: obs must be float32 [{rows}, {n_fields}, >= {C_}], got {tuple(obs.shape)} {obs.dtype}")
+    if obs.stride(2) != 1 or obs.stride(0) % 4 or obs.stride(1) % 4 or obs.stride(0) < 0 or obs.stride(1) < 0 or obs.data_ptr() % 16:
+        raise ValueError(f"{what}: obs needs unit inner stride, row and field strides that are multiples of 4 and a 16-byte-aligned base, got strides "
+                         f"{obs.stride()} (pad the cell width to a multiple of 4: patchify_and_scale(..., c_out=))")
+    if prec is not None:
+        if not torch.is_tensor(prec) or prec.dtype != torch.float32 or prec.device != dev or tuple(prec.shape) != tuple(obs.shape):
+            raise ValueError(f"{what}: prec must be None or a float32 map of obs's shape {tuple(obs.shape)} on {dev}, got "
+                             f"{(tuple(prec.shape), prec.dtype, prec.device) if torch.is_tensor(prec) else type(prec).__name__}")
+        if prec.stride() != obs.stride() or prec.data_ptr() % 16:
+            raise ValueError(f"{what}: prec needs obs's strides {obs.stride()} and a 16-byte-aligned base, got strides {prec.stride()}")
+    if field_prec is not None and (not torch.is_tensor(field_prec) or field_prec.dtype != torch.float32 or tuple(field_prec.shape) != (n_fields,)
+                                   or not field_prec.is_contiguous() or field_prec.device != dev):
+        raise ValueError(f"{what}: field_prec must be None or a contiguous float32 [{n_fields}] on {dev}")
+    if counts is not None and (counts.dtype != torch.int32 or counts.dim() != 1 or counts.shape[0] != n_patches or not counts.is_contiguous() or counts.device != dev):
+        raise ValueError(f"{what}: counts must be a contiguous int32 [{n_patches}] on {dev}, got {tuple(counts.shape)} {counts.dtype} on {counts.device}")
+    if work is not None and (not torch.is_tensor(work) or work.dtype != torch.float32 or work.device != dev or not work.is_contiguous() or work.numel() < M * n_fields):
+        raise ValueError(f"{what}: work must be None or a contiguous float32 workspace of at least M * n_fields_total = {M * n_fields} elements on {dev}, got "
+                         f"{(work.numel(), work.dtype, work.device) if torch.is_tensor(work) else type(work).__name__}")
+    N.require_gpu(obs, f"{what} obs")   # every operand is on the observation's device (checked above)
+    wsse = torch.empty(M // n_patches, n_fields, device=dev, dtype=torch.float32)
+    if work is None:
+        work = torch.empty(M * n_fields, device=dev, dtype=torch.float32)
+    arr, P = (N.SeaDecodeMseGroup * len(groups))(), N.SeaDecodeFieldGrad()
+    fill_decode_field_grad(arr, P, groups, obs, prec, field_prec, counts, n_patches, members, C_, Cp, wsse, work, float(grad_scale))
+    N.check(N.lib().sea_decode_field_grad(arr, len(groups), C.byref(P), N.dtype_code(dtype), N.stream_ptr()), "sea_decode_field_grad")
+    return wsse
+
+
 def fill_decode_member_moments(groups_arr, P: N.SeaDecodeMemberMoments, groups: Sequence[Dict], weights, var_scale, counts, n_patches: int, members: int, C_: int,
                                Cp: int, mean, var, work) -> None:
     """The argument table of sea_decode_member_moments.  groups: dicts H act [M, S], W2 act [n_fields * Cp, S], bias f32 [n_fields * Cp]; group g's fields
