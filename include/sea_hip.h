@@ -1516,6 +1516,58 @@ int64_t sea_decode_member_verify_ws_bytes(int B, int P, int n_fields_total, int 
 int sea_decode_member_verify(const SeaDecodeMseGroup* groups, int n_groups, const SeaDecodeMemberVerify* p, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * The CRPS of the decoded fields as a LOSS: per (history, field) the sum of the cells' CRPS, WITH its gradient to the hidden rows, in two launches,
+ * without the members' decoded fields or their gradient ever existing in memory.  Operands, rows, groups, counts, prec_field, prec, logw, unbiased,
+ * the decode, the cells' weights, the history's weights w_m, status[b] and c exactly as in sea_decode_member_verify; the groups also carry dH (the
+ * output, act [M, >= S] through lddh) and optionally Z (the pre-activation, through ldz).  For one live, good cell with member values x_m (the f32
+ * decoded values), reading y, q = sum_m w_m^2, c = unbiased ? 1 - q : 1 and below_m the weight of the members below m under the order (value, member
+ * index):
+ *     crps  = sum_m w_m |x_m - y|  -  (1 / c) sum_m w_m (x_m - y) (2 below_m + w_m - 1)                  (sea_ensemble_verify's, the same device code)
+ *     G[m]  = d crps / d x_m = w_m (sign(x_m - y) - (2 below_m + w_m - 1) / c)       sign(0) = 0;  c <= 0: the second term is 0      (fp64)
+ * away from ties the derivative, at ties the subgradient that the order selects.  G = 0 exactly, by selects (whatever obs holds, NaN included),
+ * for a dead member (logw = -inf), a dead cell (no weight), a bad cell (a non-finite live member value, reading or weight: counted in sums[.., 6])
+ * and a history that is not scored (status -1).  With fw = field_weight (NULL: 1; a value that is not positive counts as 0):
+ *     sums[b, f, 0..7]   sea_decode_member_verify's eight fp64 sums, with that launch's BITS for the same operands                  (f64 [B, F, 8])
+ *     loss[b, f]         float(fw[f] * sums[b, f, 1])                                                                                (f32 [B, F])
+ *     dH[m, s]           sum over the fields j of the group and their cells c of (g0 + g1) * W2[j Cp + c, s]  [* gelu_erf'(Z[m, s])]  with
+ *                        g = float(fw[f] G[m, j, c]) (formed in fp64), g0 = bf16(g) — g rounded to bf16 ONCE, the A operand of the second product as
+ *                        sea_decode_mse rounds its residual — and g1 = bf16(g - g0), what that rounding left, as a second A operand against the same
+ *                        W2 tile (g1 = 0 wherever g is a bf16 value: the result is then the one-term product's, bit for bit; elsewhere the operand
+ *                        carries 16 bits, so that a row with ONE live cell is not 2^-8 off); fp32 accumulation, the g0 product first; rounded once
+ *                        to the act dtype.  Every element of dH [M, S] is written.
+ *     status[b]          the number of live members, or -1                                                                           (int32 [B])
+ * Launch 1 has sea_decode_member_verify's grid — a workgroup per (history, patch, field, chunk of 512 columns) — and its walk; the scoring lanes
+ * place G in LDS as two [member][32 columns] bf16 fragments (g0, g1) and the wave that decoded members 16 w .. 16 w + 15 multiplies it against the same LDS
+ * image of the W2 tile into its [16, S] fp32 slice of dH, which goes to the workgroup's private partial in `work`.  Launch 2 adds a row's partials
+ * in ascending (field, chunk) order and the sums in ascending (patch, chunk) order.  No floating-point atomics, one writer per element: two runs
+ * give the same bits, and a history's outputs are those of a call holding it alone.
+ * Requirements: those of sea_decode_member_verify (without maps, hist and accumulate), and per group dH non-NULL, dH and Z 16-byte aligned, lddh and
+ * ldz >= S; loss and field_weight 4-byte aligned; work_bytes >= sea_decode_member_crps_grad_ws_bytes(B, P, F, members, Cp, S), which is
+ * B P F ceil(Cp / 512) (64 + 4 members S) bytes.  members above 64 at S above 384 returns SEA_EUNSUPPORTED with a message (the dH slice and the
+ * two-member fp64 walk do not fit the register file without scratch), as do SEA_F32, S above 640 and members above 128.  Returns -1, with the entry
+ * point and the offending group named in sea_last_error(), for anything else; nothing touches a device before the checks pass.
+ * Notes the form "decode.member_crps_grad.w8" (8 waves; members above 64, or S up to 384) or "decode.member_crps_grad.w4" (4 waves: members up to
+ * 64 at S above 384) with a = the padded hidden width, b = the dynamic LDS bytes.
+ * (An addition to ABI version 8.  The struct is not in sea_struct_sizes(): sizeof(SeaDecodeMemberCrpsGrad) is 152.)
+ */
+typedef struct {
+    const float* obs;          /* f32, rows of the observation: [B * P, F, >= C] through ld_row, ld_field */
+    const float* prec_field;   /* f32 [F], or NULL (1) */
+    const float* prec;         /* f32 map in obs's layout through ld_prow, ld_pfield, or NULL (1) */
+    const float* field_weight; /* f32 [F], or NULL (1) */
+    const int32_t* counts;     /* device int32 [P] or NULL */
+    const float* logw;         /* NULL (equal weights) or f32 [B N], unnormalised */
+    float* loss;               /* f32 [B, F] */
+    double* sums;              /* f64 [B, F, 8] */
+    int32_t* status;           /* int32 [B] */
+    void* work;                /* work_bytes bytes */
+    int64_t ld_row, ld_field, ld_prow, ld_pfield, work_bytes;
+    int32_t M, S, C, Cp, P, members, n_fields_total, unbiased;
+} SeaDecodeMemberCrpsGrad;   /* 152 bytes */
+int64_t sea_decode_member_crps_grad_ws_bytes(int B, int P, int n_fields_total, int members, int Cp, int S);   /* -1 for sizes the entry point refuses */
+int sea_decode_member_crps_grad(const SeaDecodeMseGroup* groups, int n_groups, const SeaDecodeMemberCrpsGrad* p, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * The forecast products of an ensemble beyond mean and variance: weighted QUANTILE maps (median, a 5 % / 95 % band, the envelope) and EXCEEDANCE
  * probability maps of the decoded fields, in ONE launch, without the members' decoded fields ever existing in memory.  Operands H, W2, bias, ldh, ldw,
  * n_fields, field0 of SeaDecodeMseGroup and the row order exactly as in sea_decode_member_verify: row m = (b * members + j) * P + p of H is member j of

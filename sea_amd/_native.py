@@ -356,6 +356,14 @@ class SeaDecodeMemberVerify(C.Structure):
                 ("accumulate", _i32), ("pad_", _i32)]
 
 
+class SeaDecodeMemberCrpsGrad(C.Structure):
+    # sea_decode_member_crps_grad, 152 bytes (not in ABI_STRUCTS, like its siblings; tests/test_crps_loss_cpu.py checks the layout and the library's argument checks)
+    _fields_ = [("obs", _vp), ("prec_field", _vp), ("prec", _vp), ("field_weight", _vp), ("counts", _vp), ("logw", _vp), ("loss", _vp), ("sums", _vp),
+                ("status", _vp), ("work", _vp),
+                ("ld_row", _i64), ("ld_field", _i64), ("ld_prow", _i64), ("ld_pfield", _i64), ("work_bytes", _i64),
+                ("M", _i32), ("S", _i32), ("C", _i32), ("Cp", _i32), ("P", _i32), ("members", _i32), ("n_fields_total", _i32), ("unbiased", _i32)]
+
+
 QUANTILE_MAX_LEVELS = 8      # levels, and thresholds, one launch of sea_decode_member_quantiles carries
 
 
@@ -374,6 +382,8 @@ MEMBER_MOMENTS_CHUNK = 128   # members one workgroup of sea_decode_member_moment
 VERIFY_MAX_N = 128           # members per history of sea_ensemble_verify
 VERIFY_SUMS = 8              # fp64 sums per history of sea_ensemble_verify
 FIELD_VERIFY_MAX_N = 128     # members per history of sea_decode_member_verify
+CRPS_GRAD_W8_MAX_S = 384     # sea_decode_member_crps_grad: above 64 members the hidden width it carries (beyond: SEA_EUNSUPPORTED, the composed path)
+SEA_EUNSUPPORTED = -3
 QUANTILE_MAX_N = 128         # members per history of sea_decode_member_quantiles
 RESAMPLE_MAX_N = 4096      # members per history of sea_resample_systematic
 
@@ -510,6 +520,10 @@ def lib() -> C.CDLL:
     L.sea_decode_member_verify.restype = C.c_int
     L.sea_decode_member_verify_ws_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
     L.sea_decode_member_verify_ws_bytes.restype = _i64
+    L.sea_decode_member_crps_grad.argtypes = [C.POINTER(SeaDecodeMseGroup), C.c_int, C.POINTER(SeaDecodeMemberCrpsGrad), C.c_int, _vp]
+    L.sea_decode_member_crps_grad.restype = C.c_int
+    L.sea_decode_member_crps_grad_ws_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.sea_decode_member_crps_grad_ws_bytes.restype = _i64
     L.sea_decode_member_quantiles.argtypes = [C.POINTER(SeaDecodeMseGroup), C.c_int, C.POINTER(SeaDecodeMemberQuantiles), C.c_int, _vp]
     L.sea_decode_member_quantiles.restype = C.c_int
     for name in ("sea_attention_bwd", "sea_wgrad_grouped", "sea_transpose_weights", "sea_rownorm_bwd", "sea_silu_outer_bwd", "sea_ib_bwd",
@@ -544,6 +558,7 @@ EXPORTED_SYMBOLS = (
     "sea_wgrad_grouped", "sea_transpose_weights", "sea_rownorm_bwd", "sea_silu_outer_bwd", "sea_ib_bwd",
     "sea_attention_bwd", "sea_dropout_mask", "sea_run_list", "sea_run_list_steps", "sea_unpatchify", "sea_gemm_rownorm", "sea_exchange_tail", "sea_patchify", "sea_silu_outer_ib", "sea_mlp_fc1_ln_gelu", "sea_mlp_fc2_proj_norm", "sea_kv_rollout", "sea_kv_arena_words", "sea_kv_debug_stamps",
     "sea_kv_cache_fill", "sea_kv_cache_fork", "sea_kv_cache_gather", "sea_decode_mse", "sea_decode_member_sse", "sea_decode_member_moments", "sea_decode_sensor_sse", "sea_decode_sensor_grad", "sea_decode_field_grad", "sea_resample_systematic", "sea_enkf_transform", "sea_enkf_transform_gram", "sea_decode_member_gram", "sea_ensemble_mix", "sea_ensemble_verify", "sea_ensemble_verify_ws_bytes", "sea_decode_member_verify", "sea_decode_member_verify_ws_bytes", "sea_decode_member_quantiles",
+    "sea_decode_member_crps_grad", "sea_decode_member_crps_grad_ws_bytes",
     "sea_gemm_fewrows", "sea_qkv_rope_fewrows", "sea_row_chain", "sea_row_chain_riders", "sea_gemm_adaln", "sea_mlp_block", "sea_adaln_qkv", "sea_splitk_finish",
     "sea_encoder_block_ws_floats", "sea_encoder_block_fwd", "sea_encoder_block_bwd",
     "sea_silu_outer_bwd_dc", "sea_silu_outer_bwd_dc_ws_floats", "sea_ib_bwd_dc",

@@ -2654,3 +2654,431 @@ extern "C" int sea_decode_member_quantiles(const SeaDecodeMseGroup* groups, int 
     SEA_CHECK_LAUNCH("sea_decode_member_quantiles");
     return SEA_OK;
 }
+
+// ------------------------------------------------------------------------------------------------------------------------------------------------
+// sea_decode_member_crps_grad: the CRPS of the decoded fields per (history, field) WITH its gradient to the hidden rows (include/sea_hip.h states
+// the formulas) — decode_member_verify_kernel crossed with stage 2 of decode_mse_kernel.  Launch 1 keeps member_verify's grid, a workgroup per
+// (history, patch, field, chunk of MV_CHUNK tiles), and its decode, weights, walk and sums line for line (no maps, no histogram): the fp64 sums
+// have that launch's bits.  Per tile, between scoring and the next tile:
+//   b  the scoring lanes form G = fw w (sign(x - y) - (2 below + w - 1) / c) in fp64 from what vf_score_wave_ex hands back (0 by selects for a
+//      dead member, a dead or bad cell), round it to f32 and then to bf16 ONCE — the leading term, LDS image Gs[member][32 columns] — and round what
+//      that rounding left (exact in f32) to bf16 too: the trailing term, image Gt, 0 wherever fw G is a bf16 value.  One bf16 term alone errs by up to
+//      2^-8 relative, which a row with a single live cell shows undiminished; with both the operand carries 16 bits;
+//   c  the wave that decoded the members 16 w .. 16 w + 15 reads its rows of Gs and Gt as A fragments (k-slot (g, j) = column 4 g + j or 16 + 4 g + j - 4)
+//      and multiplies them, the leading term first, against the SAME LDS image of the W2 tile, read column-wise (ds_read_b64_tr_b16), into its [16, SP] fp32 slice of dH —
+//      decode_mse_kernel's stage 2 and accumulator layout — while thread k finishes column k and the next tile goes to the other image.
+// No barrier is added: Gs and Gt are written between the barriers around b and read between those around c.  After the last tile the slice goes to the
+// workgroup's private fp32 partial [members, S] in `work`; a workgroup with nothing to score (an unscored history, a chunk without a valid column)
+// writes its zero sums only.  Launch 2 (member_crps_finish_kernel): block b < B adds history b's sums in ascending (patch, chunk) order —
+// member_verify_finish_kernel's order — and writes loss[b, f] = float(fw[f] * sums[b, f, 1]); block B + m adds the partials of row m per group in
+// ascending (field, chunk) order, passing over the workgroups that wrote none by the same uniform tests, applies gelu'(Z) where Z is given, rounds
+// once and writes dH: one writer per element, no floating-point atomics, two runs give the same bits, and nothing of a history depends on another.
+// NW is the number of waves: 8 as member_verify (2 waves per SIMD: 256 registers each), or 4 where members <= 64 and the dH slice needs the whole file.
+struct MemberCrpsLaunch {
+    SeaDecodeMseGroup g[SEA_DECODE_MSE_MAX_GROUPS];
+    SeaDecodeMemberCrpsGrad p;
+    int n_groups;
+    int chunks;
+};
+
+constexpr int MC_GP = 36;   // bf16 per member row of the G image (32 columns and 8 bytes of pad: a row is 72 bytes, 8-byte aligned)
+
+__host__ __device__ static inline int64_t mc_sum_bytes(int64_t BP, int Q, int F) { return BP * Q * F * VF_SUMS * 8; }
+
+template <int SP>
+constexpr int mc_lds_bytes() { return 2 * DM_TC * (SP * 2 + DM_PAD) + DM_TC * MV_VP * 4 + 2 * VF_MAX_N * MC_GP * 2; }
+
+template <int SP, int V, int NW>
+__global__ __launch_bounds__(64 * NW) void decode_member_crps_grad_kernel(const MemberCrpsLaunch L) {
+#pragma clang fp reassociate(off)
+    constexpr int NT = 64 * NW;
+    constexpr int KS = SP / 32;
+    constexpr int ST = SP / 16;
+    constexpr int PITCH = SP * 2 + DM_PAD;
+    constexpr int TILE = DM_TC * PITCH;
+    constexpr int NCH = SP * 4 / NT;
+    constexpr int VP = MV_VP;
+    static_assert(NCH * NT == DM_TC * (SP / 8), "whole chunks per thread");
+    static_assert(16 * NW >= 64 * V || NW == 8, "the waves decode every member");
+    extern __shared__ __attribute__((aligned(16))) char smem[];   // 2 tile images; the value image [32][VP]; the two G images [128][MC_GP] (leading and trailing bf16 term)
+    float* Vs = reinterpret_cast<float*>(smem + 2 * TILE);
+    __bf16* Gs = reinterpret_cast<__bf16*>(smem + 2 * TILE + DM_TC * VP * 4);
+    __bf16* Gt = Gs + VF_MAX_N * MC_GP;
+    __shared__ double lw_s[VF_MAX_N], w_s[VF_MAX_N];
+    __shared__ int live_s[VF_MAX_N];
+    __shared__ VfReading r_s[DM_TC];
+    __shared__ double term_s[VF_SUMS][DM_TC];
+    __shared__ float y_s[DM_TC], pv_s[DM_TC];
+
+    const SeaDecodeMemberCrpsGrad& P = L.p;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), li = lane & 15, lg = lane >> 4;
+    const int S = P.S, C = P.C, Cp = P.Cp, N = P.members, F = P.n_fields_total;
+    const int bp = blockIdx.x, fg = blockIdx.y, ck = blockIdx.z, Q = gridDim.z;
+    const int b = bp / P.P, patch = bp - b * P.P;
+    const int64_t slot = ((int64_t)bp * Q + ck) * F + fg;   // this workgroup's place in both parts of the workspace
+    double* const wsum = reinterpret_cast<double*>(P.work) + slot * VF_SUMS;
+    float* const wpart = reinterpret_cast<float*>(static_cast<char*>(P.work) + mc_sum_bytes(gridDim.x, Q, F)) + slot * N * S;
+
+    int lim = C;   // valid columns of this patch: [0, lim) — uniform over the workgroup
+    if (P.counts != nullptr) {
+        const int cnt = P.counts[patch];
+        lim = cnt < 0 ? 0 : (cnt > C ? C : cnt);
+    }
+    const int tpf = (lim + DM_TC - 1) / DM_TC;
+    const int tb = ck * MV_CHUNK, te = tpf < tb + MV_CHUNK ? tpf : tb + MV_CHUNK;
+
+    // the weights of the history (decode_member_verify_kernel's, line for line)
+    int invalid = 0, alive = 0;
+    if (tid < N) {
+        const float lw = P.logw != nullptr ? P.logw[(int64_t)b * N + tid] : 0.f;
+        invalid = (lw != lw || lw == INFINITY) ? 1 : 0;
+        alive = (!invalid && lw != -INFINITY) ? 1 : 0;
+        lw_s[tid] = (double)lw;
+        live_s[tid] = alive;
+    }
+    const int n_live = __syncthreads_count(alive);
+    invalid = __syncthreads_or(invalid);
+    const bool unscored = invalid || n_live == 0;
+    if (patch == 0 && fg == 0 && ck == 0 && tid == 0) P.status[b] = unscored ? -1 : n_live;
+    if (unscored || te <= tb) {   // uniform: nothing to score in this chunk; the finish launch passes its partial over
+        if (tid < VF_SUMS) wsum[tid] = 0.0;
+        return;
+    }
+    double mx = -INFINITY;
+    for (int j = 0; j < N; ++j) mx = lw_s[j] > mx ? lw_s[j] : mx;
+    if (tid < N) w_s[tid] = alive ? exp(lw_s[tid] - mx) : 0.0;
+    __syncthreads();
+    double W = 0.0;
+    for (int j = 0; j < N; ++j) W += w_s[j];
+    const double my_w = tid < N ? w_s[tid] / W : 0.0;
+    __syncthreads();
+    if (tid < N) w_s[tid] = my_w;
+    __syncthreads();
+    double q = 0.0;
+    for (int j = 0; j < N; ++j) q = fma(w_s[j], w_s[j], q);
+    const double cq = P.unbiased ? 1.0 - q : 1.0;
+    float fwv = P.field_weight != nullptr ? P.field_weight[fg] : 1.f;
+    fwv = fwv > 0.f ? fwv : 0.f;   // false for NaN
+    const double fwd = (double)fwv;
+
+    const int j0 = wave * 16;
+    const bool active = j0 < N;
+    const int jm = j0 + li;
+    const int64_t m = ((int64_t)b * N + (jm < N ? jm : 0)) * P.P + patch;
+    double acc_sum = 0.0;
+
+    int gsel = 0;
+    for (int gi = 1; gi < L.n_groups; ++gi) gsel = (fg >= L.g[gi].field0 && fg < L.g[gi].field0 + L.g[gi].n_fields) ? gi : gsel;
+    const SeaDecodeMseGroup& G = L.g[gsel];
+    const int j = fg - G.field0;
+    const __bf16* H = static_cast<const __bf16*>(G.H);
+    const __bf16* W2 = static_cast<const __bf16*>(G.W2);
+    uint4 hf[KS];
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+        const int s = ks * 32 + 8 * lg;
+        if (ks * 32 + 32 <= S) {
+            hf[ks] = *reinterpret_cast<const uint4*>(H + m * G.ldh + s);
+        } else {
+            const uint4 v = *reinterpret_cast<const uint4*>(H + m * G.ldh + (s < S ? s : 0));
+            hf[ks] = s < S ? v : make_uint4(0u, 0u, 0u, 0u);
+        }
+    }
+    f32x4 dh[ST];
+#pragma unroll
+    for (int st = 0; st < ST; ++st) dh[st] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    const int n_tiles = te - tb, t0 = j * tpf + tb;
+    uint4 wr[NCH];
+    dm_load_tile<SP, NT>(wr, W2, G.ldw, S, Cp, tpf, t0, tid);
+    dm_store_tile<SP, NT>(wr, smem, tid);
+    __syncthreads();
+
+    typedef dm_s16x4 __attribute__((address_space(3))) * lds_p;
+    for (int t = 0; t < n_tiles; ++t) {
+        const char* buf = smem + (t & 1) * TILE;
+        const int cb = (tb + t) * DM_TC;
+
+        // a: the columns' weights and readings; decode into the value image
+        if (tid < DM_TC) {
+            const int c = cb + tid;
+            float w = 0.f;
+            if (c < lim) {
+                const float pf = P.prec_field != nullptr ? P.prec_field[fg] : 1.f;
+                const float pm = P.prec != nullptr ? P.prec[(int64_t)bp * P.ld_prow + (int64_t)fg * P.ld_pfield + c] : 1.f;
+                w = mul1(pf > 0.f ? pf : 0.f, pm > 0.f ? pm : 0.f);
+            }
+            const bool on = w > 0.f;
+            pv_s[tid] = on ? w : 0.f;
+            y_s[tid] = on ? P.obs[(int64_t)bp * P.ld_row + (int64_t)fg * P.ld_field + c] : 0.f;
+        }
+        if (active) {
+            f32x4 acc[2][2];
+#pragma unroll
+            for (int sub = 0; sub < 2; ++sub) {
+                const float bv = G.bias[j * Cp + cb + sub * 16 + li];
+                acc[sub][0] = f32x4{bv, bv, bv, bv};
+                acc[sub][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {
+                if (ks * 32 < S) {
+#pragma unroll
+                    for (int sub = 0; sub < 2; ++sub) {
+                        const uint4 wv = *reinterpret_cast<const uint4*>(buf + (sub * 16 + li) * PITCH + (ks * 4 + lg) * 16);
+                        mma16<__bf16>(hf[ks], wv, acc[sub][ks & 1]);
+                    }
+                }
+            }
+#pragma unroll
+            for (int sub = 0; sub < 2; ++sub) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) Vs[(sub * 16 + li) * VP + j0 + 4 * lg + r] = acc[sub][0][r] + acc[sub][1][r];
+            }
+        }
+        __syncthreads();
+        if (t + 1 < n_tiles) dm_load_tile<SP, NT>(wr, W2, G.ldw, S, Cp, tpf, t0 + t + 1, tid);
+
+        // b: a column per wave at a time; the lane's members' G goes to the G image (every member row below 64 V is written, the dead ones as 0)
+        for (int cl = wave; cl < DM_TC; cl += NW) {
+            const float pv = pv_s[cl];
+            if (!(pv > 0.f)) {
+                if (lane == 0) r_s[cl].state = 1;
+#pragma unroll
+                for (int v = 0; v < V; ++v) Gs[(lane + 64 * v) * MC_GP + cl] = Gt[(lane + 64 * v) * MC_GP + cl] = (__bf16)0.f;
+                continue;
+            }
+            float x[V];
+            double w[V], below[V];
+            bool lv[V];
+            const float yf = y_s[cl];
+            const VfReading r = vf_score_wave_ex<V>(Vs + cl * VP, w_s, live_s, N, lane, yf, pv, x, w, below, lv);
+            if (lane == 0) r_s[cl] = r;
+#pragma unroll
+            for (int v = 0; v < V; ++v) {
+                const double g = r.state == 0 ? fwd * vf_crps_grad(x[v], w[v], below[v], lv[v], yf, cq) : 0.0;
+                const float gf = (float)g;
+                const __bf16 g0 = (__bf16)gf;                       // the leading term: gf rounded to bf16 once
+                Gs[(lane + 64 * v) * MC_GP + cl] = g0;
+                Gt[(lane + 64 * v) * MC_GP + cl] = (__bf16)(gf - (float)g0);   // what that rounding left (exact in f32), rounded to bf16: 0 where gf is a bf16 value
+            }
+        }
+        __syncthreads();
+
+        // c: thread k finishes column k; the waves' second product against the same tile image
+        if (tid < DM_TC) {
+            double tm[VF_SUMS];
+            const VfReading r = r_s[tid];
+            (void)vf_finish_reading(r, y_s[tid], pv_s[tid], cq, tm);
+#pragma unroll
+            for (int i = 0; i < VF_SUMS; ++i) term_s[i][tid] = tm[i];
+        }
+        if (active) {
+            const uint2 glo = *reinterpret_cast<const uint2*>(Gs + (j0 + li) * MC_GP + 4 * lg);
+            const uint2 ghi = *reinterpret_cast<const uint2*>(Gs + (j0 + li) * MC_GP + 16 + 4 * lg);
+            const uint4 da = make_uint4(glo.x, glo.y, ghi.x, ghi.y);
+            const uint2 tlo = *reinterpret_cast<const uint2*>(Gt + (j0 + li) * MC_GP + 4 * lg);
+            const uint2 thi = *reinterpret_cast<const uint2*>(Gt + (j0 + li) * MC_GP + 16 + 4 * lg);
+            const uint4 dt = make_uint4(tlo.x, tlo.y, thi.x, thi.y);
+            const char* tbp = buf + (4 * lg + (li >> 2)) * PITCH + (4 * (li & 3)) * 2;
+#pragma unroll
+            for (int st = 0; st < ST; ++st) {
+                if (st * 16 < S) {
+                    const dm_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(tbp + st * 32));
+                    const dm_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(tbp + st * 32 + 16 * PITCH));
+                    const uint2 l2 = __builtin_bit_cast(uint2, lo), h2 = __builtin_bit_cast(uint2, hi);
+                    const uint4 wt = make_uint4(l2.x, l2.y, h2.x, h2.y);
+                    mma16<__bf16>(da, wt, dh[st]);
+                    mma16<__bf16>(dt, wt, dh[st]);   // the trailing term against the same operand: a fixed order, the leading term first
+                }
+            }
+        }
+        if (t + 1 < n_tiles) dm_store_tile<SP, NT>(wr, smem + ((t + 1) & 1) * TILE, tid);
+        __syncthreads();
+
+        // d: the field's sums, columns ascending
+        if (tid < VF_SUMS)
+            for (int k = 0; k < DM_TC; ++k) acc_sum += term_s[tid][k];
+    }
+    if (tid < VF_SUMS) wsum[tid] = acc_sum;
+    if (active) {   // register r of tile st is member j0 + 4 g + r, hidden column 16 st + (lane & 15)
+#pragma unroll
+        for (int st = 0; st < ST; ++st) {
+            const int s = st * 16 + li;
+            if (s < S) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int mem = j0 + 4 * lg + r;
+                    if (mem < N) wpart[(int64_t)mem * S + s] = dh[st][r];
+                }
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void member_crps_finish_kernel(const MemberCrpsLaunch L, const int B) {
+#pragma clang fp reassociate(off)
+    const SeaDecodeMemberCrpsGrad& p = L.p;
+    const int tid = threadIdx.x, N = p.members, F = p.n_fields_total, Q = L.chunks, S = p.S;
+    if ((int)blockIdx.x < B) {   // the sums of history b, (patch, chunk) ascending — member_verify_finish_kernel's order — and the loss
+        const int b = blockIdx.x, Pn = p.P * Q;
+        const double* base = reinterpret_cast<const double*>(p.work) + (int64_t)b * Pn * F * VF_SUMS;
+        for (int e = tid; e < F * VF_SUMS; e += 256) {
+            const int f = e / VF_SUMS, i = e - f * VF_SUMS;
+            double acc = 0.0;
+#pragma unroll 8
+            for (int pt = 0; pt < Pn; ++pt) acc += base[((int64_t)pt * F + f) * VF_SUMS + i];
+            p.sums[((int64_t)b * F + f) * VF_SUMS + i] = acc;
+            if (i == 1) {
+                float fw = p.field_weight != nullptr ? p.field_weight[f] : 1.f;
+                fw = fw > 0.f ? fw : 0.f;
+                p.loss[(int64_t)b * F + f] = (float)((double)fw * acc);
+            }
+        }
+        return;
+    }
+    const int64_t m = (int64_t)blockIdx.x - B;   // row (b N + i) P + patch
+    const int patch = (int)(m % p.P);
+    const int64_t bm = m / p.P;
+    const int i = (int)(bm % N), b = (int)(bm / N);
+    const int64_t bp = (int64_t)b * p.P + patch;
+    int lim = p.C;
+    if (p.counts != nullptr) {
+        const int cnt = p.counts[patch];
+        lim = cnt < 0 ? 0 : (cnt > p.C ? p.C : cnt);
+    }
+    const int tpf = (lim + DM_TC - 1) / DM_TC;
+    const int qn = p.status[b] < 0 ? 0 : (tpf + MV_CHUNK - 1) / MV_CHUNK;   // the chunks that wrote a partial: [0, qn)
+    const float* part = reinterpret_cast<const float*>(static_cast<const char*>(p.work) + mc_sum_bytes((int64_t)B * p.P, Q, F));
+    for (int gi = 0; gi < L.n_groups; ++gi) {
+        const SeaDecodeMseGroup& G = L.g[gi];
+        __bf16* dH = static_cast<__bf16*>(G.dH);
+        const __bf16* Z = static_cast<const __bf16*>(G.Z);
+        for (int s = tid; s < S; s += 256) {
+            float acc = 0.f;
+            for (int jf = 0; jf < G.n_fields; ++jf)
+                for (int ck = 0; ck < qn; ++ck) acc += part[((((int64_t)bp * Q + ck) * F + G.field0 + jf) * N + i) * S + s];   // (field, chunk) ascending
+            if (Z != nullptr) acc *= gelu_grad_for<__bf16>((float)Z[m * G.ldz + s]);
+            dH[m * G.lddh + s] = (__bf16)acc;
+        }
+    }
+}
+
+template <int SP, int V, int NW>
+static void member_crps_launch(const MemberCrpsLaunch& L, dim3 grid, hipStream_t s) {
+    constexpr int lds = mc_lds_bytes<SP>();
+    static bool set_on[64] = {false};   // per device: the dynamic part is above the 64 kB a kernel gets without the attribute from SP = 384 on
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = -1;
+    if (dev < 0 || !set_on[dev]) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(decode_member_crps_grad_kernel<SP, V, NW>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        if (dev >= 0) set_on[dev] = true;
+    }
+    decode_member_crps_grad_kernel<SP, V, NW><<<grid, dim3(64 * NW), lds, s>>>(L);
+    sea_note_form(NW == 8 ? "decode.member_crps_grad.w8" : "decode.member_crps_grad.w4", SP, lds);
+}
+
+// The forms that compile without scratch (DESIGN.md section 7n has the register table): 8 waves up to SP = 384, 4 waves (members <= 64) above it;
+// members above 64 beyond MC_W8_MAX_SP_V2 are refused.
+constexpr int MC_W8_MAX_SP_V2 = 384;
+
+static bool member_crps_supported(int S, int members) { return members <= 64 || S <= MC_W8_MAX_SP_V2; }
+
+extern "C" int64_t sea_decode_member_crps_grad_ws_bytes(int B, int P, int n_fields_total, int members, int Cp, int S) {
+    if (B < 1 || B > 65535 || P < 1 || n_fields_total < 1 || members < 1 || members > VF_MAX_N || Cp < 32 || Cp % 32 || S < 8 || S % 8 || S > 640) return -1;
+    if (!member_crps_supported(S, members)) return -1;
+    return (int64_t)B * P * mv_chunks(Cp) * n_fields_total * (VF_SUMS * 8 + (int64_t)members * S * 4);
+}
+
+extern "C" int sea_decode_member_crps_grad(const SeaDecodeMseGroup* groups, int n_groups, const SeaDecodeMemberCrpsGrad* p, int dtype, void* stream) {
+    SEA_REQUIRE(groups != nullptr && p != nullptr, "sea_decode_member_crps_grad: null argument table");
+    SEA_REQUIRE(n_groups >= 1 && n_groups <= SEA_DECODE_MSE_MAX_GROUPS, "sea_decode_member_crps_grad: n_groups=%d outside 1..%d", n_groups, SEA_DECODE_MSE_MAX_GROUPS);
+    SEA_REQUIRE(dtype == SEA_F32 || dtype == SEA_BF16, "sea_decode_member_crps_grad: bad dtype %d", dtype);
+    if (dtype != SEA_BF16) {
+        sea_set_error("sea_decode_member_crps_grad: unsupported: bf16 only (the fp32 decoder composes the decode and the formulas under autograd)");
+        return SEA_EUNSUPPORTED;
+    }
+    const SeaDecodeMemberCrpsGrad& P = *p;
+    SEA_REQUIRE(P.obs != nullptr && P.loss != nullptr && P.sums != nullptr && P.status != nullptr && P.work != nullptr,
+                "sea_decode_member_crps_grad: null pointer (obs, loss, sums, status and work are required; prec_field, prec, field_weight, counts and logw may be NULL)");
+    SEA_REQUIRE(P.M >= 1, "sea_decode_member_crps_grad: M=%d must be positive", P.M);
+    SEA_REQUIRE(P.S >= 8 && P.S % 8 == 0, "sea_decode_member_crps_grad: S=%d must be a positive multiple of 8", P.S);
+    SEA_REQUIRE(P.Cp >= 32 && P.Cp % 32 == 0, "sea_decode_member_crps_grad: Cp=%d must be a positive multiple of 32", P.Cp);
+    SEA_REQUIRE(P.C >= 1 && P.C <= P.Cp, "sea_decode_member_crps_grad: C=%d must lie in 1..Cp=%d", P.C, P.Cp);
+    SEA_REQUIRE(P.P >= 1, "sea_decode_member_crps_grad: P=%d must be positive", P.P);
+    SEA_REQUIRE(P.members >= 1, "sea_decode_member_crps_grad: members=%d must be positive", P.members);
+    SEA_REQUIRE((int64_t)P.M % ((int64_t)P.P * P.members) == 0, "sea_decode_member_crps_grad: M=%d is not a multiple of P * members = %d * %d", P.M, P.P, P.members);
+    SEA_REQUIRE(P.n_fields_total >= 1 && P.n_fields_total <= 65535, "sea_decode_member_crps_grad: n_fields_total=%d outside 1..65535 (a grid dimension)", P.n_fields_total);
+    SEA_REQUIRE(P.ld_field >= P.C && P.ld_row >= 0, "sea_decode_member_crps_grad: obs strides ld_row=%lld, ld_field=%lld must cover C=%d", (long long)P.ld_row,
+                (long long)P.ld_field, P.C);
+    SEA_REQUIRE(P.prec == nullptr || (P.ld_pfield >= P.C && P.ld_prow >= 0), "sea_decode_member_crps_grad: prec strides ld_prow=%lld, ld_pfield=%lld must cover C=%d",
+                (long long)P.ld_prow, (long long)P.ld_pfield, P.C);
+    SEA_REQUIRE(P.unbiased == 0 || P.unbiased == 1, "sea_decode_member_crps_grad: unbiased=%d must be 0 or 1", P.unbiased);
+    SEA_REQUIRE(sea_aligned4(P.obs) && sea_aligned4(P.prec_field) && sea_aligned4(P.prec) && sea_aligned4(P.field_weight) && sea_aligned4(P.counts) && sea_aligned4(P.logw) &&
+                    sea_aligned4(P.loss) && sea_aligned4(P.status) && (reinterpret_cast<uintptr_t>(P.sums) & 7u) == 0 && (reinterpret_cast<uintptr_t>(P.work) & 7u) == 0,
+                "sea_decode_member_crps_grad: misaligned pointer (f32 and int32 buffers need 4 bytes; sums and work 8)");
+    int64_t covered = 0;
+    for (int g = 0; g < n_groups; ++g) {
+        const SeaDecodeMseGroup& G = groups[g];
+        SEA_REQUIRE(G.H != nullptr && G.W2 != nullptr && G.bias != nullptr && G.dH != nullptr, "sea_decode_member_crps_grad: group %d: null pointer (H, W2, bias or dH)", g);
+        SEA_REQUIRE(sea_aligned16(G.H) && sea_aligned16(G.W2) && sea_aligned16(G.bias) && sea_aligned16(G.dH) && sea_aligned16(G.Z),
+                    "sea_decode_member_crps_grad: group %d: pointers must be 16-byte aligned", g);
+        SEA_REQUIRE(G.ldh >= P.S && G.ldh % 8 == 0 && G.ldw >= P.S && G.ldw % 8 == 0 && G.lddh >= P.S && (G.Z == nullptr || G.ldz >= P.S),
+                    "sea_decode_member_crps_grad: group %d: row strides ldh=%d ldw=%d lddh=%d ldz=%d must cover S=%d (ldh, ldw multiples of 8)", g, G.ldh, G.ldw, G.lddh, G.ldz, P.S);
+        SEA_REQUIRE(G.n_fields >= 1 && G.field0 >= 0 && (int64_t)G.field0 + G.n_fields <= P.n_fields_total,
+                    "sea_decode_member_crps_grad: group %d: n_fields=%d, field0=%d outside the %d fields", g, G.n_fields, G.field0, P.n_fields_total);
+        SEA_REQUIRE((int64_t)G.n_fields * P.Cp <= 0x7fffffffLL / 2, "sea_decode_member_crps_grad: group %d: too many output columns", g);
+        for (int h = 0; h < g; ++h)
+            SEA_REQUIRE(G.field0 >= groups[h].field0 + groups[h].n_fields || groups[h].field0 >= G.field0 + G.n_fields,
+                        "sea_decode_member_crps_grad: group %d: its fields overlap those of group %d (a cell is scored once)", g, h);
+        covered += G.n_fields;
+    }
+    SEA_REQUIRE(covered == P.n_fields_total, "sea_decode_member_crps_grad: the groups cover %lld of the %d fields (every field needs exactly one group)", (long long)covered,
+                P.n_fields_total);
+    if (P.S > 640) {
+        sea_set_error("sea_decode_member_crps_grad: unsupported: hidden width S=%d above 640", P.S);
+        return SEA_EUNSUPPORTED;
+    }
+    if (P.members > VF_MAX_N) {
+        sea_set_error("sea_decode_member_crps_grad: unsupported: members=%d above %d", P.members, VF_MAX_N);
+        return SEA_EUNSUPPORTED;
+    }
+    if (!member_crps_supported(P.S, P.members)) {
+        sea_set_error("sea_decode_member_crps_grad: unsupported: members=%d above 64 at hidden width S=%d above %d (the dH slice and the two-member walk do not fit the register file)",
+                      P.members, P.S, MC_W8_MAX_SP_V2);
+        return SEA_EUNSUPPORTED;
+    }
+    const int64_t BP = (int64_t)P.M / P.members;
+    const int64_t B = BP / P.P;
+    SEA_REQUIRE(BP <= 0x7fffffffLL && B <= 65535, "sea_decode_member_crps_grad: %lld histories; a launch carries up to 65535", (long long)B);
+    const int Q = mv_chunks(P.Cp);
+    SEA_REQUIRE(Q <= 65535 && B + (int64_t)P.M <= 0x7fffffffLL, "sea_decode_member_crps_grad: too many rows or column chunks");
+    const int64_t need = sea_decode_member_crps_grad_ws_bytes((int)B, P.P, P.n_fields_total, P.members, P.Cp, P.S);
+    SEA_REQUIRE(P.work_bytes >= need,
+                "sea_decode_member_crps_grad: work_bytes=%lld below the %lld that sea_decode_member_crps_grad_ws_bytes(B=%d, P=%d, n_fields_total=%d, members=%d, Cp=%d, S=%d) asks for",
+                (long long)P.work_bytes, (long long)need, (int)B, P.P, P.n_fields_total, P.members, P.Cp, P.S);
+
+    MemberCrpsLaunch L;
+    memset(&L, 0, sizeof(L));
+    for (int g = 0; g < n_groups; ++g) L.g[g] = groups[g];
+    L.p = P;
+    L.n_groups = n_groups;
+    L.chunks = Q;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)BP, (unsigned)P.n_fields_total, (unsigned)Q);
+    const int S = P.S;
+    if (P.members > 64) {
+        if (S <= 128) member_crps_launch<128, 2, 8>(L, grid, s);
+        else if (S <= 256) member_crps_launch<256, 2, 8>(L, grid, s);
+        else member_crps_launch<384, 2, 8>(L, grid, s);
+    } else {
+        if (S <= 128) member_crps_launch<128, 1, 8>(L, grid, s);
+        else if (S <= 256) member_crps_launch<256, 1, 8>(L, grid, s);
+        else if (S <= 384) member_crps_launch<384, 1, 8>(L, grid, s);
+        else if (S <= 512) member_crps_launch<512, 1, 4>(L, grid, s);
+        else member_crps_launch<640, 1, 4>(L, grid, s);
+    }
+    member_crps_finish_kernel<<<dim3((unsigned)(B + P.M)), dim3(256), 0, s>>>(L, (int)B);
+    SEA_CHECK_LAUNCH("sea_decode_member_crps_grad");
+    return SEA_OK;
+}

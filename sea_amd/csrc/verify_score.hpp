@@ -4,6 +4,7 @@
 //   vf_score_wave<V>  one wave scores one reading: lane l holds member l (and l + 64 at V = 2), walks j = 0 .. N - 1 with broadcast LDS reads and
 //                     accumulates the weight below its own member under the total order (value, member index); the lane terms are reduced by a fixed
 //                     xor butterfly (the mean first: the spread is centred on it).  Every lane returns the same sums.
+//   vf_score_wave_ex  vf_score_wave's copy that hands back the lane's value, weight, weight below and live flag; vf_crps_grad: the CRPS derivative from them.
 //   vf_finish_reading one thread finishes one reading: the selects on c, the fp32 roundings, the eight terms of the per-history sums.
 #pragma once
 #include "sea_common.hpp"
@@ -108,6 +109,100 @@ __device__ __forceinline__ VfReading vf_score_wave(const float* row, const doubl
     r.rank = rk;
     r.state = bad ? 2 : 0;
     return r;
+}
+
+// vf_score_wave's sibling for the gradient launch (sea_decode_member_crps_grad): the SAME statements in the same order, and it also hands back what the
+// lane holds of its own members — the value x, the weight w, the weight below and the live flag (a member at or beyond N: 0, 0, 0, false).  It is a
+// copy and not a wrapper so that vf_score_wave's callers keep their code, instruction for instruction.
+template <int V>
+__device__ __forceinline__ VfReading vf_score_wave_ex(const float* row, const double* w_s, const int* live_s, const int N, const int lane, const float yf, const float pv,
+                                                      float (&x)[V], double (&w)[V], double (&below)[V], bool (&lv)[V]) {
+#pragma clang fp reassociate(off)
+    const double y = (double)yf;
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+        const int i = lane + 64 * v;
+        const bool in = i < N;
+        x[v] = in ? row[i] : 0.f;
+        w[v] = in ? w_s[i] : 0.0;
+        lv[v] = in && live_s[i] != 0;
+        below[v] = 0.0;
+    }
+    // the walk, j ascending; eight members' reads are issued together, and the order test is written without short-circuits: no branch in the chain
+    int j = 0;
+    for (; j + VF_WALK <= N; j += VF_WALK) {
+        float xj[VF_WALK];
+        double wj[VF_WALK];
+#pragma unroll
+        for (int u = 0; u < VF_WALK; ++u) {
+            xj[u] = row[j + u];
+            wj[u] = w_s[j + u];
+        }
+#pragma unroll
+        for (int u = 0; u < VF_WALK; ++u)
+#pragma unroll
+            for (int v = 0; v < V; ++v) {
+                const bool lower = (xj[u] < x[v]) | ((xj[u] == x[v]) & (j + u < lane + 64 * v));
+                below[v] += lower ? wj[u] : 0.0;
+            }
+    }
+    for (; j < N; ++j) {
+        const float xj = row[j];
+        const double wj = w_s[j];
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            const bool lower = (xj < x[v]) | ((xj == x[v]) & (j < lane + 64 * v));
+            below[v] += lower ? wj : 0.0;
+        }
+    }
+    double m = 0.0;
+    int bad = (isfinite(yf) && isfinite(pv)) ? 0 : 1, rk = 0;
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+        m += lv[v] ? w[v] * (double)x[v] : 0.0;
+        bad |= (lv[v] && !isfinite(x[v])) ? 1 : 0;
+        rk += (lv[v] && x[v] < yf) ? 1 : 0;
+    }
+    const double mean = vf_wave_sum(m);
+    double var = 0.0, ab = 0.0, pr = 0.0, pt = 0.0;
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+        const double xd = (double)x[v], d = xd - y, dm = xd - mean;
+        var += lv[v] ? w[v] * dm * dm : 0.0;
+        ab += lv[v] ? w[v] * fabs(d) : 0.0;
+        pr += lv[v] ? w[v] * d * (2.0 * below[v] + w[v] - 1.0) : 0.0;
+        pt += lv[v] ? w[v] * (x[v] < yf ? 1.0 : (x[v] == yf ? 0.5 : 0.0)) : 0.0;
+    }
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) {   // six butterflies, stage by stage: their exchanges are in flight together; each sum has vf_wave_sum's order
+        const double o_var = __shfl_xor(var, m, 64), o_ab = __shfl_xor(ab, m, 64), o_pr = __shfl_xor(pr, m, 64), o_pt = __shfl_xor(pt, m, 64);
+        const int o_rk = __shfl_xor(rk, m, 64), o_bad = __shfl_xor(bad, m, 64);
+        var += o_var;
+        ab += o_ab;
+        pr += o_pr;
+        pt += o_pt;
+        rk += o_rk;
+        bad += o_bad;
+    }
+    VfReading r;
+    r.mean = mean;
+    r.var = var;
+    r.ab = ab;
+    r.pair = pr;
+    r.pit = pt;
+    r.rank = rk;
+    r.state = bad ? 2 : 0;
+    return r;
+}
+
+// The derivative of a reading's CRPS with respect to the lane's member (include/sea_hip.h, sea_decode_member_crps_grad):
+//     G = w (sign(x - y) - (2 below + w - 1) / c),   sign(0) = 0;  c <= 0: the second term is 0, as in vf_finish_reading;  a dead member: 0
+// in fp64.  At ties it is the subgradient that the walk's order (value, member index) selects.
+__device__ __forceinline__ double vf_crps_grad(const float x, const double w, const double below, const bool lv, const float yf, const double c) {
+#pragma clang fp reassociate(off)
+    const double sg = x > yf ? 1.0 : (x < yf ? -1.0 : 0.0);
+    const double pr = c > 0.0 ? (2.0 * below + w - 1.0) / c : 0.0;
+    return lv ? w * (sg - pr) : 0.0;
 }
 
 struct VfOut {

@@ -65,6 +65,12 @@ What is published as the forecast besides mean and variance (EnsembleQuantiles: 
 
     products = EnsembleQuantiles(decoder, n_patches, members=n, levels=(0.05, 0.5, 0.95), thresholds=unpatcher.scale_thresholds([[0.5, 2.0]]), counts=counts)
     quant, exceed = products(y, logw)                                           # [3, B, P, n_fields, n_inp] quantile maps, [1, B, P, n_fields, n_inp] P(field > threshold)
+
+The same CRPS TRAINS the temporal model as an ensemble generator (EnsembleCRPSLoss: Decode.member_crps_loss, sea_decode_member_crps_grad — the
+CRPS sums of FieldVerification with their gradient to the latent states, the members' fields and their gradient never written):
+
+    loss = EnsembleCRPSLoss(decoder, n_patches, members=n, counts=counts)(model(x_members, perturbed_conditions), truth_fields)
+    loss.backward()                                                             # to the parameters, and to x.grad / cond.grad of TemporalModel
 """
 from __future__ import annotations
 
@@ -1477,3 +1483,154 @@ class EnsembleQuantiles:
         return quant, exceed
 
     quantiles = __call__
+
+
+# ------------------------------------------------------------------------------------------------ CRPS of the decoded fields as a loss
+def _composed_crps(Y, obs, w, logw, members: int, unbiased: bool, field_weight=None):
+    """sea_decode_member_crps_grad's formulas (include/sea_hip.h) as fp64 torch ops on _composed_verify's conventions: Y [B * members, P, F, C] decoded
+    members (any float dtype, compared as given), obs [B, P, F, >= C], w [B, P, F, C] the cells' weights (0: dead), logw None or [B * members],
+    field_weight None or [F].  Returns (loss f32 [B, F] = fw * the sum of the live, good cells' CRPS, count f64 [B, F], G f64 [B * members, P, F, C] =
+    d sum_f loss / d Y, coded explicitly: fw w_m (sign(x_m - y) - (2 below_m + w_m - 1) / c) with below_m from a STABLE sort, which is the order
+    (value, member index) — not torch.abs's subgradient; exactly 0 for a dead member, a dead or bad cell, an unscored history).  Nothing is read back."""
+    f64 = torch.float64
+    n = members
+    Bm, P, F, C_ = Y.shape
+    B = Bm // n
+    dev = Y.device
+    zero = torch.zeros((), device=dev, dtype=f64)
+    x = Y.detach().to(f64).view(B, n, P, F, C_)
+    y = obs[..., :C_].to(f64)
+    lw = torch.zeros(B, n, device=dev, dtype=f64) if logw is None else logw.to(f64).view(B, n)
+    invalid = (torch.isnan(lw) | (lw == float("inf"))).any(1) | ~torch.isfinite(lw).any(1)            # [B]
+    lw = torch.where(invalid.unsqueeze(1), zero, lw)
+    alive = lw != float("-inf")                                                                      # [B, n]
+    e = torch.where(alive, (lw - lw.max(dim=1, keepdim=True).values).exp(), zero)
+    wm = e / e.sum(dim=1, keepdim=True)
+    c = (1.0 - (wm * wm).sum(dim=1) if unbiased else torch.ones(B, device=dev, dtype=f64)).view(B, 1, 1, 1)
+    pos = c > 0
+    c_safe = torch.where(pos, c, torch.ones_like(c))
+    p = w.to(f64)
+    al = alive.view(B, n, 1, 1, 1)
+    live = (p > 0) & ~invalid.view(B, 1, 1, 1)
+    finite = torch.isfinite(y) & torch.isfinite(p) & (torch.isfinite(x) | ~al).all(1)
+    good = live & finite                                                                             # [B, P, F, C]
+    use = good.unsqueeze(1) & al                                                                     # [B, n, P, F, C]: what enters a sum
+    xs = torch.where(use, x, zero)
+    ys = torch.where(good, y, zero)
+    wv = torch.where(use, wm.view(B, n, 1, 1, 1), zero)
+    d = xs - ys.unsqueeze(1)
+    order = torch.sort(xs, dim=1, stable=True).indices                                                # ties keep the member order
+    ws, ds = torch.gather(wv, 1, order), torch.gather(d, 1, order)
+    below_sorted = ws.cumsum(1) - ws
+    pair = (ws * ds * (2.0 * below_sorted + ws - 1.0)).sum(1)
+    crps = (wv * d.abs()).sum(1) - torch.where(pos, pair / c_safe, zero)
+    below = torch.zeros_like(below_sorted).scatter_(1, order, below_sorted)
+    G = wv * (torch.sign(d) - torch.where(pos.unsqueeze(1), (2.0 * below + wv - 1.0) / c_safe.unsqueeze(1), zero))
+    G = torch.where(use, G, zero)
+    sums1 = torch.where(good, crps, zero).sum(dim=(1, 3))                                             # [B, F]
+    count = good.to(f64).sum(dim=(1, 3))
+    if field_weight is not None:
+        fw = field_weight.to(device=dev, dtype=f64)
+        fw = torch.where(fw > 0, fw, zero)
+        sums1, G = fw.view(1, F) * sums1, G * fw.view(1, 1, 1, F, 1)
+    return sums1.to(torch.float32), count, G.view(Bm, P, F, C_)
+
+
+class _CrpsComposedFn(torch.autograd.Function):
+    """_composed_crps behind autograd: (loss [B, F], count [B, F]) from the decoded members Y; the backward multiplies the saved explicit gradient by the
+    upstream factor of its (history, field) — exact for any upstream gradient."""
+
+    @staticmethod
+    def forward(ctx, Y, obs, w, logw, members, unbiased, field_weight):
+        loss, count, G = _composed_crps(Y, obs, w, logw, members, unbiased, field_weight)
+        ctx.members = members
+        ctx.save_for_backward(G.to(Y.dtype))
+        ctx.mark_non_differentiable(count)
+        return loss, count
+
+    @staticmethod
+    def backward(ctx, g, _unused):
+        (G,) = ctx.saved_tensors
+        Bm, P, F, C_ = G.shape
+        n = ctx.members
+        gy = G.view(Bm // n, n, P, F, C_) * g.to(G.dtype).view(Bm // n, 1, 1, F, 1)
+        return gy.view(Bm, P, F, C_), None, None, None, None, None, None
+
+
+class EnsembleCRPSLoss(torch.nn.Module):
+    """The CRPS of the DECODED fields of an ensemble as a training loss: loss = EnsembleCRPSLoss(decoder, n_patches, members)(out, target_fields).
+
+    out: the temporal model's output [B * members, T, n_groups, P * D] in fork order (row b * members + j is member j of history b — members that differ
+    by perturbed conditions, noisy inputs or dropout); target_fields: float32 [B, T, P, n_fields, C] (layout "BPFC"; C >= the decoder's n_inp) or, with
+    layout="BPCF", [B, T, P, C, n_fields]: ONE truth per (b, t).  precision: None or a float32 map of target_fields' shape (0: a missing cell);
+    logw: None (equal weights) or float32 [B * members] log-weights of the members, constants.  The latent -> z re-layout of
+    inverse_transform_processed_data is applied as torch views and permutes with (b, t) as the history and j as the member, so autograd carries the
+    gradient back to the temporal model's hand-written backward; the loss itself is Decode.member_crps_loss (fused: sea_decode_member_crps_grad — neither
+    the members' decoded fields nor their gradient are written).  Returns the 0-dim tensor sum(loss) / max(sum(count), 1) — the mean CRPS per live
+    cell (the fair CRPS with unbiased=True; field_weight scales a field's share) — on the device; nothing is read back.  `decoder` is a frozen sea_amd
+    Decode (decoder.requires_grad_(False)); it is not registered as a sub-module, so the loss has no parameters."""
+
+    def __init__(self, decoder, n_patches: int, members: int, counts=None, layout: str = "BPFC", unbiased: bool = True, field_weight=None, fused=None):
+        super().__init__()
+        if layout not in ("BPFC", "BPCF"):
+            raise ValueError(f"EnsembleCRPSLoss: layout must be 'BPFC' or 'BPCF', got {layout!r}")
+        if not isinstance(n_patches, int) or isinstance(n_patches, bool) or n_patches < 1:
+            raise ValueError(f"EnsembleCRPSLoss: n_patches = {n_patches!r} must be a positive integer")
+        if not isinstance(members, int) or isinstance(members, bool) or members < 1:
+            raise ValueError(f"EnsembleCRPSLoss: members = {members!r} must be a positive integer")
+        n_fields = sum(len(g) for g in decoder.field_groups)
+        if field_weight is not None:
+            field_weight = torch.as_tensor(field_weight, dtype=torch.float32)
+            if tuple(field_weight.shape) != (n_fields,) or not bool(torch.isfinite(field_weight).all()) or bool((field_weight < 0).any()):
+                raise ValueError(f"EnsembleCRPSLoss: field_weight must be {n_fields} finite numbers >= 0, got {field_weight.tolist()}")
+        object.__setattr__(self, "decoder", decoder)
+        self.n_patches, self.members, self.counts, self.layout, self.unbiased, self.fused = n_patches, members, counts, layout, bool(unbiased), fused
+        self._fw_src, self._fw = field_weight, {}
+
+    def _field_weight_on(self, device):
+        if self._fw_src is None:
+            return None
+        t = self._fw.get(device)
+        if t is None:
+            t = self._fw[device] = self._fw_src.to(device)
+            t._sea_checked_field_weight = True   # checked on the host at construction: Decode.member_crps_loss does not read it back
+        return t
+
+    def forward(self, output: torch.Tensor, target_fields: torch.Tensor, precision: Optional[torch.Tensor] = None, logw: Optional[torch.Tensor] = None,
+                layout: Optional[str] = None) -> torch.Tensor:
+        layout = self.layout if layout is None else layout
+        if layout not in ("BPFC", "BPCF"):
+            raise ValueError(f"EnsembleCRPSLoss: layout must be 'BPFC' or 'BPCF', got {layout!r}")
+        P, n = self.n_patches, self.members
+        if not torch.is_tensor(output) or output.dim() != 4 or output.shape[-1] % P or output.shape[0] < 1:
+            raise ValueError(f"EnsembleCRPSLoss: output must be [B * members, T, n_groups, n_patches * D] with n_patches = {P}, got "
+                             f"{tuple(output.shape) if torch.is_tensor(output) else type(output).__name__}")
+        Bm, T, G, E = output.shape
+        if Bm % n:
+            raise ValueError(f"EnsembleCRPSLoss: the {Bm} trajectories of output are not a multiple of members = {n}")
+        B = Bm // n
+        for name, t in (("target_fields", target_fields), ("precision", precision)):
+            if t is None and name == "precision":
+                continue
+            if not torch.is_tensor(t) or t.dim() != 5 or tuple(t.shape[:3]) != (B, T, P):
+                raise ValueError(f"EnsembleCRPSLoss: {name} must be [{B}, {T}, {P}, ...] in layout {layout} (one truth per history and step), got "
+                                 f"{tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
+        if precision is not None and precision.shape != target_fields.shape:
+            raise ValueError(f"EnsembleCRPSLoss: precision must have target_fields' shape {tuple(target_fields.shape)}, got {tuple(precision.shape)}")
+        if logw is not None and (not torch.is_tensor(logw) or logw.dtype != torch.float32 or tuple(logw.shape) != (Bm,) or logw.device != output.device):
+            raise ValueError(f"EnsembleCRPSLoss: logw must be None or a float32 [{Bm}] tensor on {output.device}, got "
+                             f"{(tuple(logw.shape), logw.dtype, str(logw.device)) if torch.is_tensor(logw) else type(logw).__name__}")
+        D = E // P
+        # [B, n, T, G, P, D] -> [B, T, n, P, G, D]: the history is (b, t), the member j
+        z = output.reshape(B, n, T, G, P, D).permute(0, 2, 1, 4, 3, 5).reshape(B * T * n, P, G, D)
+        rel = (lambda t: t) if layout == "BPFC" else (lambda t: t.permute(0, 1, 2, 4, 3))   # noqa: E731
+        tgt = rel(target_fields)
+        tgt = tgt.reshape((B * T,) + tuple(tgt.shape[2:]))
+        prec = None
+        if precision is not None:
+            prec = rel(precision)
+            prec = prec.reshape((B * T,) + tuple(prec.shape[2:]))
+        lw = None if logw is None else logw.detach().view(B, 1, n).expand(B, T, n).reshape(-1)
+        loss, count = self.decoder.member_crps_loss(z, tgt, n, counts=self.counts, precision=prec, field_weight=self._field_weight_on(output.device), logw=lw,
+                                                    unbiased=self.unbiased, fused=self.fused)
+        return loss.sum() / count.sum().clamp_min(1.0).to(loss.dtype)

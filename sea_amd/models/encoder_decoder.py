@@ -823,6 +823,122 @@ class Decode(nn.Module):
                                             prec=None if prec is None else rows(prec), counts=cnt, logw=lw, unbiased=bool(unbiased),
                                             accumulate=into is not None, maps=maps, out=into, dtype=dt)
 
+    def _field_weight_on(self, field_weight, n_fields: int, device: torch.device, what: str):
+        """field_weight checked on the host (float32 [n_fields], finite, >= 0; cached per tensor object and version) -> a contiguous copy on `device`, or None.
+        A tensor that EnsembleCRPSLoss made from values it checked at construction carries a mark and is taken as it is: nothing is read back from the device."""
+        if field_weight is None:
+            return None
+        if not torch.is_tensor(field_weight) or field_weight.dtype != torch.float32 or tuple(field_weight.shape) != (n_fields,):
+            raise ValueError(f"{what}: field_weight must be None or a float32 [{n_fields}] tensor, got "
+                             f"{(tuple(field_weight.shape), field_weight.dtype) if torch.is_tensor(field_weight) else type(field_weight).__name__}")
+        if field_weight.requires_grad and torch.is_grad_enabled():
+            raise ValueError(f"{what}: field_weight must not require grad (gradients flow to z only)")
+        if getattr(field_weight, "_sea_checked_field_weight", False):
+            return field_weight.detach().to(device).contiguous()
+        key = (id(field_weight), field_weight._version, device)
+        cur = getattr(self, "_fw_cache", None)
+        if cur is None or cur[0] != key:
+            host = field_weight.detach().cpu()
+            if not bool(torch.isfinite(host).all()) or bool((host < 0).any()):
+                raise ValueError(f"{what}: field_weight must be finite and >= 0, got {host.tolist()}")
+            cur = (key, field_weight.detach().to(device).contiguous(), field_weight)   # the object is kept so that its id is not reused
+            self._fw_cache = cur
+        return cur[1]
+
+    def member_crps_loss(self, z: torch.Tensor, obs: torch.Tensor, members: int, counts=None, precision: Optional[torch.Tensor] = None,
+                         field_precision: Optional[torch.Tensor] = None, field_weight: Optional[torch.Tensor] = None, logw: Optional[torch.Tensor] = None,
+                         unbiased: bool = True, fused: Optional[bool] = None):
+        """The CRPS of an ensemble's DECODED fields against a dense observation as a loss: (loss, count) with loss float32 [B, n_fields],
+        loss[b, f] = field_weight[f] * sum over the patches and the live, good cells of field f of the cell's CRPS (member_verify's sums[..., 1]:
+        the fair CRPS with unbiased=True), differentiable with a gradient to z only, and count float64 [B, n_fields] the number of those cells
+        (sums[..., 0]; not differentiable).  z, obs, members, counts, precision, field_precision, logw, unbiased and their validation are
+        member_verify's (logw is a constant: no gradient reaches it); field_weight: None or float32 [n_fields], finite and >= 0.  The derivative of a
+        cell's CRPS with respect to member m's value is w_m (sign(x_m - y) - (2 below_m + w_m - 1) / c) (include/sea_hip.h,
+        sea_decode_member_crps_grad): the derivative away from ties, at ties the subgradient that the order (value, member index) selects; exactly 0
+        for a dead member, a dead or bad cell and a history that is not scored.
+        Upstream gradients.  loss[b, f] depends on the z rows of history b's members in the group g of field f alone, and forward and backward are ONE
+        pass, as in field_loss: the gradient of sum_f loss[b, f] is saved at forward and the backward scales it per HISTORY and field GROUP.  Where the
+        upstream gradient differs between the fields of one group that history's group slice is NaN (a select on the device), never a silently wrong
+        number; per-field factors belong in field_weight.  (The composed path carries per-field upstream gradients exactly.)
+        fused=True (bf16; members <= 64, or <= 128 at MLP_hidden <= 384): the first-layer launch with the pre-activation kept, the TWO launches of
+        sea_decode_member_crps_grad (member_verify's grid and walk; the scoring lanes hand the derivative to a second MFMA product against the same
+        LDS image of the W2 tile; neither the members' decoded fields nor their gradient are written) and the data-gradient launch against W1^T.
+        Under torch.no_grad(), or when z does not require grad, it is member_verify without maps: the same loss bits.  fused=False: forward() under
+        autograd plus the formulas as float64 torch ops with the gradient coded explicitly in the (value, index) tie order (the composed path: fp32,
+        any member count; it holds the [B * members, P, n_fields, n_inp] fields and their gradient).
+        fused=None, read from profiles/crps_loss_bench.txt (tools/crps_loss_bench.py; cylinder and multiphase decoders, 64 patches,
+        n_inp 1628, the mesh's counts, loss + backward): the fused launches in bf16, where the fused form carries the shape, up to 64 members from 4096
+        rows (B * members * P) on, and up to 8 members from 16384 rows on — the smallest measured sizes of the two regimes; the fused path is ahead in
+        every measured row of both: 64 members x 1 and 4 histories 1.13 - 3.48 ms against 6.0 - 22.9 ms composed (112 - 584 MB of extra
+        memory against 1.9 - 7.8 GB); 4 and 8 members x 64 and 256 histories 23.9 - 104.7 ms against 104.9 - 457.3 ms (0.46 - 4.7 GB against
+        8.6 - 65.5 GB).  Member counts between 8 and 64 were not measured: the rule INTERPOLATES between the two regimes there (both ends are ahead by
+        4x or more).  The composed path serves elsewhere: below those row counts and above 64 members, where nothing was measured (the bench's
+        128-member shapes have hidden widths the fused form refuses), in fp32, and for any shape the fused form refuses (MLP_hidden above 640
+        included) — such a shape raises only under fused=True."""
+        from ..ensemble import _CrpsComposedFn, _field_cell_weights
+
+        what = "sea_amd.Decode.member_crps_loss"
+        n_fields = sum(len(g) for g in self.field_groups)
+        C, Cp = self.n_inp, self._n_inp_p
+        if not torch.is_tensor(z) or z.dim() != 4 or z.shape[2] != self.num_groups or z.shape[3] != self.embed_dim:
+            raise ValueError(f"{what}: z must be [B * members, P, {self.num_groups}, {self.embed_dim}], got {tuple(z.shape) if torch.is_tensor(z) else type(z).__name__}")
+        Bm, P = z.shape[0], z.shape[1]
+        if not isinstance(members, int) or isinstance(members, bool) or members < 1 or Bm < 1 or Bm % members:
+            raise ValueError(f"{what}: members = {members!r} must be a positive integer that divides the {Bm} rows of z")
+        B = Bm // members
+        for name, t in (("obs", obs), ("precision", precision)):
+            if t is None and name == "precision":
+                continue
+            if not torch.is_tensor(t) or t.dim() != 4 or tuple(t.shape[:3]) != (B, P, n_fields) or t.shape[3] < C:
+                raise ValueError(f"{what}: {name} must be [{B}, {P}, {n_fields}, >= {C}] (one per history of {members} members), got "
+                                 f"{tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
+            if t.dtype != torch.float32 or t.device != z.device:
+                raise ValueError(f"{what}: {name} must be float32 on {z.device}, got {t.dtype} on {t.device}")
+        if precision is not None and precision.shape[3] != obs.shape[3]:
+            raise ValueError(f"{what}: precision must have obs's shape {tuple(obs.shape)}, got {tuple(precision.shape)}")
+        if field_precision is not None and (not torch.is_tensor(field_precision) or field_precision.dtype != torch.float32 or tuple(field_precision.shape) != (n_fields,)
+                                            or field_precision.device != z.device):
+            raise ValueError(f"{what}: field_precision must be None or a float32 [{n_fields}] tensor on {z.device}")
+        if logw is not None and (not torch.is_tensor(logw) or logw.dtype != torch.float32 or tuple(logw.shape) != (Bm,) or logw.device != z.device):
+            raise ValueError(f"{what}: logw must be None or a float32 [{Bm}] tensor on {z.device}")
+        if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (obs, precision, field_precision, logw)):
+            raise ValueError(f"{what}: obs, precision, field_precision and logw must not require grad (gradients flow to z only)")
+        fw = self._field_weight_on(field_weight, n_fields, z.device, what)
+        self._require_frozen("member_crps_loss")
+        dt = self._act_dtype()
+        carried = ops.decode_member_crps_grad_supported(self.MLP_hidden, members)
+        if fused is None:
+            # profiles/crps_loss_bench.txt (DESIGN.md section 7n): the fused launches are ahead in every measured row of both regimes — 64 members at 4096 and
+            # 16384 rows, 4 and 8 members at 16384 - 131072 rows; above 64 members no shape the bench has is carried, below 4096 rows (below 16384 at up to 8
+            # members) nothing was measured; a shape the fused form refuses takes the composed path
+            fused = dt == torch.bfloat16 and carried and members <= 64 and Bm * P >= (CRPS_LOSS_FUSED_MIN_ROWS if members > 8 else CRPS_LOSS_FUSED_MIN_ROWS_SMALL)
+        if fused and dt != torch.bfloat16:
+            raise ValueError(f"{what}: the fused launches are bf16 only (set_compute_dtype('bf16'), or fused=False)")
+        if fused and not carried:
+            raise ValueError(f"{what}: the fused launches carry up to 64 members, or up to {N.FIELD_VERIFY_MAX_N} at MLP_hidden <= {N.CRPS_GRAD_W8_MAX_S}; got "
+                             f"{members} members at MLP_hidden = {self.MLP_hidden} (fused=False, or None, take the composed path)")
+        cnt, _ = self._valid_counts(counts, P, z.device, allow_empty=True, what="member_crps_loss")
+        N.require_gpu(z, "Decode.member_crps_loss input")
+        want_grad = z.requires_grad and torch.is_grad_enabled()
+        obs = obs.detach()
+        prec = None if precision is None else precision.detach()
+        pf = None if field_precision is None else field_precision.detach().contiguous()
+        lw = None if logw is None else logw.detach().contiguous()
+        if not fused:
+            y = (_DecodeFn.apply(z, self) if want_grad else self.forward(z.detach())).view(Bm, P, n_fields, C)
+            w = _field_cell_weights((B, P, n_fields, C), pf, prec, cnt, z.device)
+            return _CrpsComposedFn.apply(y, obs, w, lw, members, bool(unbiased), fw)
+        if not want_grad:
+            r = self.member_verify(z, obs, members, counts=counts, precision=prec, field_precision=pf, logw=lw, unbiased=unbiased, fused=True, maps=())
+            s1 = r["sums"][..., 1]
+            return (s1 if fw is None else fw.to(torch.float64) * s1).to(torch.float32), r["sums"][..., 0]
+
+        def rows(t):   # [B * P, n_fields, width] with unit inner stride: a view where the layout allows it, else one copy of the first C columns
+            t3 = t.reshape(B * P, n_fields, t.shape[3])
+            return t3 if t3.stride(2) == 1 and t3.stride(1) >= C and t3.stride(0) >= 0 else t3[..., :C].contiguous()
+
+        return _DecodeCrpsFn.apply(z, self, rows(obs), None if prec is None else rows(prec), pf, fw, cnt, lw, members, bool(unbiased))
+
     def member_quantiles(self, z: torch.Tensor, members: int, levels=(), thresholds: Optional[torch.Tensor] = None, weights: Optional[torch.Tensor] = None,
                          counts=None, fused: Optional[bool] = None):
         """Quantile and exceedance-probability maps of an ensemble's decoded fields: (quant float32 [Q, B, P, n_fields, n_inp] or None, exceed float32
@@ -1073,6 +1189,50 @@ class _DecodeFieldFn(torch.autograd.Function):
             off += n
         factor = torch.stack(cols, dim=1).view(dz.shape[0], 1, len(cols), 1)          # [Bm, 1, G, 1]
         return (dz * factor).to(dz.dtype), None, None, None, None, None, None
+
+
+class _DecodeCrpsFn(torch.autograd.Function):
+    """Decode.member_crps_loss on the fused path: first layer (pre-activation kept), sea_decode_member_crps_grad (the CRPS sums and the
+    pre-activation gradient in its two launches), data-gradient launch against W1^T.  Forward and backward are one pass, as in _DecodeFieldFn:
+    loss[b, f] depends on the rows of history b's members in the group of field f only, so the backward scales the stored dz per history and group; an
+    upstream gradient that differs between the fields of one group turns that slice into NaN (a select, nothing read back)."""
+
+    @staticmethod
+    def forward(ctx, z, dec, o3, p3, pf, fw, cnt, lw, members, unbiased):
+        dt = torch.bfloat16
+        with torch.no_grad():
+            Bm, P, G, D = z.shape
+            M = Bm * P
+            hid, pre = dec._first_layer(z, dt)
+            _, W2 = dec._weights(dt)
+            bias = dec._shadow[3]
+            dpre = [torch.empty(M, dec.MLP_hidden, device=z.device, dtype=dt) for _ in range(G)]
+            groups = [dict(H=hid[g], W2=W2[g], bias=bias[g], dH=dpre[g], Z=pre[g]) for g in range(G)]
+            loss, sums, _ = ops.decode_member_crps_grad(groups, o3, dec.n_inp, dec._n_inp_p, P, members, prec=p3, prec_field=pf, field_weight=fw, counts=cnt,
+                                                        logw=lw, unbiased=unbiased, dtype=dt)
+            ctx.save_for_backward(dec._input_grad(dpre, dt).view(Bm, P, G, D).to(z.dtype))
+        ctx.groups, ctx.members = [len(g) for g in dec.field_groups], members
+        count = sums[..., 0].contiguous()
+        ctx.mark_non_differentiable(count)
+        return loss, count
+
+    @staticmethod
+    def backward(ctx, g, _unused):
+        (dz,) = ctx.saved_tensors
+        Bm, P, G, D = dz.shape
+        n = ctx.members
+        cols, off = [], 0
+        for k in ctx.groups:
+            first = g[:, off]
+            same = (g[:, off:off + k] == first.unsqueeze(1)).all(dim=1)
+            cols.append(torch.where(same, first, torch.full_like(first, float("nan"))))
+            off += k
+        factor = torch.stack(cols, dim=1).view(Bm // n, 1, 1, G, 1)                       # [B, 1, 1, G, 1]
+        return (dz.view(Bm // n, n, P, G, D) * factor).view(Bm, P, G, D).to(dz.dtype), None, None, None, None, None, None, None, None, None
+
+
+CRPS_LOSS_FUSED_MIN_ROWS_SMALL = 16384   # ... and with up to 8 members, where the smallest measured size is 64 histories x 4 members x 64 patches
+CRPS_LOSS_FUSED_MIN_ROWS = 4096   # member_crps_loss, fused=None: the fused launches from this many decoder rows (B * members * n_patches) on — the smallest measured size
 
 
 def _round_up(x: int, m: int) -> int:

@@ -1918,6 +1918,115 @@ def decode_member_verify(groups: Sequence[Dict], obs: torch.Tensor, C_: int, Cp:
     return res
 
 
+def fill_decode_member_crps_grad(groups_arr, P: N.SeaDecodeMemberCrpsGrad, groups: Sequence[Dict], obs, prec_field, prec, field_weight, counts, logw, n_patches: int,
+                                members: int, C_: int, Cp: int, unbiased: bool, loss, sums, status, work) -> None:
+    """The argument table of sea_decode_member_crps_grad.  groups: dicts H act [M, S], W2 act [n_fields * Cp, S], bias f32 [n_fields * Cp], dH act [M, S]
+    (output) and an optional Z act [M, S]; obs, prec_field, prec, counts, logw as fill_decode_member_verify; field_weight None or f32 [n_fields_total]
+    contiguous; loss f32 [B, n_fields_total], sums f64 [B, n_fields_total, 8], status int32 [B] contiguous; work: a uint8 workspace of at least
+    sea_decode_member_crps_grad_ws_bytes(...) bytes."""
+    field0 = 0
+    for g, d in zip(groups_arr, groups):
+        H, W2, dH, Z = d["H"], d["W2"], d["dH"], d.get("Z")
+        g.H, g.W2, g.bias, g.dH, g.Z = H.data_ptr(), W2.data_ptr(), d["bias"].data_ptr(), dH.data_ptr(), N.ptr(Z)
+        g.ldh, g.ldw, g.lddh, g.ldz = H.stride(0), W2.stride(0), dH.stride(0), (Z.stride(0) if Z is not None else 0)
+        g.n_fields, g.field0 = W2.shape[0] // Cp, field0
+        field0 += g.n_fields
+    P.obs, P.prec_field, P.prec, P.field_weight = obs.data_ptr(), N.ptr(prec_field), N.ptr(prec), N.ptr(field_weight)
+    P.counts, P.logw = N.ptr(counts), N.ptr(logw)
+    P.loss, P.sums, P.status, P.work = loss.data_ptr(), sums.data_ptr(), status.data_ptr(), work.data_ptr()
+    P.ld_row, P.ld_field = obs.stride(0), obs.stride(1)
+    P.ld_prow, P.ld_pfield = (0, 0) if prec is None else (prec.stride(0), prec.stride(1))
+    P.work_bytes = work.numel() * work.element_size()
+    P.M, P.S, P.C, P.Cp, P.P = groups[0]["H"].shape[0], groups[0]["H"].shape[1], C_, Cp, n_patches
+    P.members, P.n_fields_total, P.unbiased = members, field0, int(bool(unbiased))
+
+
+def decode_member_crps_grad_supported(S: int, members: int) -> bool:
+    """Whether sea_decode_member_crps_grad carries this hidden width and member count (include/sea_hip.h: above 64 members the fused gradient form
+    stops at S = 384; what it refuses takes the composed path)."""
+    return 8 <= S <= N.DECODE_MSE_MAX_S and 1 <= members <= N.FIELD_VERIFY_MAX_N and (members <= 64 or S <= N.CRPS_GRAD_W8_MAX_S)
+
+
+def decode_member_crps_grad(groups: Sequence[Dict], obs: torch.Tensor, C_: int, Cp: int, n_patches: int, members: int, prec: Optional[torch.Tensor] = None,
+                            prec_field: Optional[torch.Tensor] = None, field_weight: Optional[torch.Tensor] = None, counts: Optional[torch.Tensor] = None,
+                            logw: Optional[torch.Tensor] = None, unbiased: bool = True, dtype: torch.dtype = torch.bfloat16):
+    """sea_decode_member_crps_grad: the CRPS of an ensemble's decoded fields against a dense observation, summed per (history, field), WITH its gradient
+    to the hidden rows (include/sea_hip.h states the formulas) — neither the members' decoded fields nor their gradient are written.  groups: dicts H,
+    W2, bias as decode_member_verify, plus dH act [M, S] (written IN PLACE, every element) and an optional Z act [M, S] (gelu' of it is applied); obs,
+    prec_field, prec, counts, logw as decode_member_verify; field_weight None or a contiguous f32 [n_fields].  Returns (loss f32 [B, n_fields] =
+    field_weight * sums[..., 1], sums f64 [B, n_fields, 8] with decode_member_verify's bits, status int32 [B]) on the device; nothing is read back.
+    A shape the fused form does not carry (decode_member_crps_grad_supported) raises RuntimeError from the library's SEA_EUNSUPPORTED.  Everything is
+    checked on the host before the launch."""
+    what = "decode_member_crps_grad"
+    if dtype != torch.bfloat16:
+        raise ValueError(f"{what}: the fused launch is bf16 only, got {dtype}")
+    if not groups or len(groups) > N.DECODE_MSE_MAX_GROUPS:
+        raise ValueError(f"{what}: {len(groups)} groups; a launch carries 1 .. {N.DECODE_MSE_MAX_GROUPS}")
+    if Cp < 32 or Cp % 32 or not 1 <= C_ <= Cp:
+        raise ValueError(f"{what}: need Cp a multiple of 32 and 1 <= C <= Cp, got C = {C_}, Cp = {Cp}")
+    H0 = groups[0].get("H")
+    if not torch.is_tensor(H0) or H0.dim() != 2:
+        raise ValueError(f"{what}: H must be a 2-D tensor, got {tuple(H0.shape) if torch.is_tensor(H0) else type(H0).__name__}")
+    dev = H0.device
+    M, S = tuple(H0.shape)
+    if M < 1 or S < 8 or S % 8 or S > N.DECODE_MSE_MAX_S:
+        raise ValueError(f"{what}: H must be [M >= 1, S] with S a multiple of 8 up to {N.DECODE_MSE_MAX_S}, got {tuple(H0.shape)}")
+    n = members
+    if not isinstance(n, int) or isinstance(n, bool) or n < 1 or n > N.FIELD_VERIFY_MAX_N:
+        raise ValueError(f"{what}: members = {members!r} must be an integer in 1 .. {N.FIELD_VERIFY_MAX_N}")
+    if not isinstance(n_patches, int) or n_patches < 1 or M % (n_patches * n):
+        raise ValueError(f"{what}: {M} rows are not a multiple of n_patches * members = {n_patches} * {n}")
+    n_fields = 0
+    for i, d in enumerate(groups):
+        for name in ("H", "W2", "dH", "Z"):
+            t = d.get(name)
+            if t is None and name == "Z":
+                continue
+            if not torch.is_tensor(t) or t.dim() != 2 or t.stride(1) != 1:
+                raise ValueError(f"{what} group {i}: {name}: need a 2-D tensor with unit inner stride, got "
+                                 f"{f'shape {tuple(t.shape)} strides {t.stride()}' if torch.is_tensor(t) else type(t).__name__}")
+            if t.dtype != dtype or t.device != dev or t.shape[1] != S or (name != "W2" and t.shape[0] != M):
+                raise ValueError(f"{what} group {i}: {name} must be a {dtype} [{'n_fields * Cp' if name == 'W2' else M}, {S}] tensor on {dev}, got "
+                                 f"{tuple(t.shape)} {t.dtype} on {t.device}")
+            if t.stride(0) % 8 or t.stride(0) < S or t.data_ptr() % 16:
+                raise ValueError(f"{what} group {i}: {name} needs a row stride that is a multiple of 8 and covers S = {S}, and a 16-byte-aligned base (stride {t.stride(0)})")
+        W2, b = d["W2"], d["bias"]
+        if W2.shape[0] < Cp or W2.shape[0] % Cp:
+            raise ValueError(f"{what} group {i}: W2 has {W2.shape[0]} rows, not a multiple of Cp = {Cp}")
+        if b.dtype != torch.float32 or b.dim() != 1 or b.shape[0] != W2.shape[0] or not b.is_contiguous() or b.device != dev or b.data_ptr() % 16:
+            raise ValueError(f"{what} group {i}: bias must be a contiguous, 16-byte-aligned float32 [{W2.shape[0]}] on {dev}, got {tuple(b.shape)} {b.dtype}")
+        n_fields += W2.shape[0] // Cp
+    B = M // (n_patches * n)
+    if B > 65535:
+        raise ValueError(f"{what}: {B} histories; a launch carries up to 65535")
+    for name, t in (("obs", obs), ("prec", prec)):
+        if t is None and name == "prec":
+            continue
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or t.dim() != 3 or tuple(t.shape[:2]) != (B * n_patches, n_fields) or t.shape[2] < C_ or t.stride(2) != 1 \
+                or t.device != dev or t.stride(1) < C_ or (t.shape[0] > 1 and t.stride(0) < 0):
+            raise ValueError(f"{what}: {name} must be a float32 [{B * n_patches}, {n_fields}, >= {C_}] tensor with unit inner stride on {dev}, got "
+                             f"{(tuple(t.shape), t.dtype, t.stride(), str(t.device)) if torch.is_tensor(t) else type(t).__name__}")
+    for name, t in (("prec_field", prec_field), ("field_weight", field_weight)):
+        if t is not None and (not torch.is_tensor(t) or t.dtype != torch.float32 or tuple(t.shape) != (n_fields,) or not t.is_contiguous() or t.device != dev):
+            raise ValueError(f"{what}: {name} must be None or a contiguous float32 [{n_fields}] tensor on {dev}")
+    if counts is not None and (not torch.is_tensor(counts) or counts.dtype != torch.int32 or counts.dim() != 1 or counts.shape[0] != n_patches
+                               or not counts.is_contiguous() or counts.device != dev):
+        raise ValueError(f"{what}: counts must be a contiguous int32 [{n_patches}] on {dev}")
+    if logw is not None and (not torch.is_tensor(logw) or logw.dtype != torch.float32 or tuple(logw.shape) != (B * n,) or not logw.is_contiguous() or logw.device != dev):
+        raise ValueError(f"{what}: logw must be None or a contiguous float32 [{B * n}] tensor on {dev}, got "
+                         f"{(tuple(logw.shape), logw.dtype, str(logw.device)) if torch.is_tensor(logw) else type(logw).__name__}")
+    N.require_gpu(H0, f"{what} hidden rows")   # every operand is on their device (checked above)
+    loss = torch.empty(B, n_fields, device=dev, dtype=torch.float32)
+    sums = torch.empty(B, n_fields, N.VERIFY_SUMS, device=dev, dtype=torch.float64)
+    status = torch.empty(B, device=dev, dtype=torch.int32)
+    need = int(N.lib().sea_decode_member_crps_grad_ws_bytes(B, n_patches, n_fields, n, Cp, S))
+    work = torch.empty(max(need, 8), device=dev, dtype=torch.uint8)   # (a refused shape asks for -1: the entry point below says why)
+    arr, P = (N.SeaDecodeMseGroup * len(groups))(), N.SeaDecodeMemberCrpsGrad()
+    fill_decode_member_crps_grad(arr, P, groups, obs, prec_field, prec, field_weight, counts, logw, n_patches, n, C_, Cp, unbiased, loss, sums, status, work)
+    N.check(N.lib().sea_decode_member_crps_grad(arr, len(groups), C.byref(P), N.dtype_code(dtype), N.stream_ptr()), "sea_decode_member_crps_grad")
+    return loss, sums, status
+
+
 def fill_decode_member_quantiles(groups_arr, P: N.SeaDecodeMemberQuantiles, groups: Sequence[Dict], w, counts, thr, levels: Sequence[float], quant, exceed,
                                  n_patches: int, members: int, C_: int, Cp: int, ld: int, ld_map: int) -> None:
     """The argument table of sea_decode_member_quantiles.  groups as fill_decode_member_verify; w None or f32 [B * members] contiguous; counts None or
