@@ -1568,6 +1568,26 @@ int64_t sea_decode_member_crps_grad_ws_bytes(int B, int P, int n_fields_total, i
 int sea_decode_member_crps_grad(const SeaDecodeMseGroup* groups, int n_groups, const SeaDecodeMemberCrpsGrad* p, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * sea_decode_member_crps_grad for SMALL ensembles: the same operands, the same struct, the same workspace (sea_decode_member_crps_grad_ws_bytes) and
+ * the same outputs — loss, sums, status and every dH have the BITS of sea_decode_member_crps_grad on the same operands — with several histories per
+ * workgroup in launch 1.  For 1 .. 32 members, with NP the member count rounded up to a power of two (at least 2): a workgroup serves (a group of HG
+ * histories, patch, field, chunk of 512 columns), HG = 64 / NP (16 at NP = 2 above S = 512, where the staging of 32 histories does not fit the LDS
+ * beside the 640-wide W2 tile images); slot g NP + i of 64 is member i of the group's history g.  Waves 0 - 3 decode 16 slots each; a wave scores a
+ * column of all the group's histories at once (segments of NP lanes: the walk over the lane's own segment, the butterflies stopped at the segment, the
+ * reading, its precision, c and the good / bad test per segment) and the second MFMA product runs over the slot rows.  A history that is not scored,
+ * and a history index beyond B in the last group, are dead segments by selects.  The unpacked form spends a workgroup — the W2 tile loads, the
+ * barriers, 32 wave-passes per tile — on 4 real rows of a 16-row MFMA tile and 4 of 64 scoring lanes at 4 members; this form amortises them over HG
+ * histories.  Launch 2 is sea_decode_member_crps_grad's.  Why the bits agree: an MFMA row does not depend on the other rows of its tile; the
+ * unpacked butterfly's stages beyond NP add exact +0.0 terms; every per-history chain (weights, q, the column sums) is the same chain.
+ * Requirements and messages: those of sea_decode_member_crps_grad, under this entry point's name.  SEA_EUNSUPPORTED with a message for members above 32,
+ * SEA_F32 and S above 640; every (S, NP) below that is shipped (none needs scratch).
+ * Notes the form "decode.member_crps_grad.pk<NP>" (pk2, pk4, pk8, pk16, pk32: HG = 64 / NP; "pk2h16": NP = 2 with HG = 16) with a = the padded hidden
+ * width, b = the dynamic LDS bytes.  8 waves up to S = 384, 4 waves above (the dH slice needs the register file).
+ * (An addition to ABI version 8.)
+ */
+int sea_decode_member_crps_grad_packed(const SeaDecodeMseGroup* groups, int n_groups, const SeaDecodeMemberCrpsGrad* p, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * The forecast products of an ensemble beyond mean and variance: weighted QUANTILE maps (median, a 5 % / 95 % band, the envelope) and EXCEEDANCE
  * probability maps of the decoded fields, in ONE launch, without the members' decoded fields ever existing in memory.  Operands H, W2, bias, ldh, ldw,
  * n_fields, field0 of SeaDecodeMseGroup and the row order exactly as in sea_decode_member_verify: row m = (b * members + j) * P + p of H is member j of

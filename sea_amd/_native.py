@@ -383,6 +383,7 @@ VERIFY_MAX_N = 128           # members per history of sea_ensemble_verify
 VERIFY_SUMS = 8              # fp64 sums per history of sea_ensemble_verify
 FIELD_VERIFY_MAX_N = 128     # members per history of sea_decode_member_verify
 CRPS_GRAD_W8_MAX_S = 384     # sea_decode_member_crps_grad: above 64 members the hidden width it carries (beyond: SEA_EUNSUPPORTED, the composed path)
+CRPS_PACK_MAX_N = 32         # sea_decode_member_crps_grad_packed: members per history (above: SEA_EUNSUPPORTED; sea_decode_member_crps_grad serves)
 SEA_EUNSUPPORTED = -3
 QUANTILE_MAX_N = 128         # members per history of sea_decode_member_quantiles
 RESAMPLE_MAX_N = 4096      # members per history of sea_resample_systematic
@@ -524,6 +525,8 @@ def lib() -> C.CDLL:
     L.sea_decode_member_crps_grad.restype = C.c_int
     L.sea_decode_member_crps_grad_ws_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
     L.sea_decode_member_crps_grad_ws_bytes.restype = _i64
+    L.sea_decode_member_crps_grad_packed.argtypes = [C.POINTER(SeaDecodeMseGroup), C.c_int, C.POINTER(SeaDecodeMemberCrpsGrad), C.c_int, _vp]
+    L.sea_decode_member_crps_grad_packed.restype = C.c_int
     L.sea_decode_member_quantiles.argtypes = [C.POINTER(SeaDecodeMseGroup), C.c_int, C.POINTER(SeaDecodeMemberQuantiles), C.c_int, _vp]
     L.sea_decode_member_quantiles.restype = C.c_int
     for name in ("sea_attention_bwd", "sea_wgrad_grouped", "sea_transpose_weights", "sea_rownorm_bwd", "sea_silu_outer_bwd", "sea_ib_bwd",
@@ -558,7 +561,7 @@ EXPORTED_SYMBOLS = (
     "sea_wgrad_grouped", "sea_transpose_weights", "sea_rownorm_bwd", "sea_silu_outer_bwd", "sea_ib_bwd",
     "sea_attention_bwd", "sea_dropout_mask", "sea_run_list", "sea_run_list_steps", "sea_unpatchify", "sea_gemm_rownorm", "sea_exchange_tail", "sea_patchify", "sea_silu_outer_ib", "sea_mlp_fc1_ln_gelu", "sea_mlp_fc2_proj_norm", "sea_kv_rollout", "sea_kv_arena_words", "sea_kv_debug_stamps",
     "sea_kv_cache_fill", "sea_kv_cache_fork", "sea_kv_cache_gather", "sea_decode_mse", "sea_decode_member_sse", "sea_decode_member_moments", "sea_decode_sensor_sse", "sea_decode_sensor_grad", "sea_decode_field_grad", "sea_resample_systematic", "sea_enkf_transform", "sea_enkf_transform_gram", "sea_decode_member_gram", "sea_ensemble_mix", "sea_ensemble_verify", "sea_ensemble_verify_ws_bytes", "sea_decode_member_verify", "sea_decode_member_verify_ws_bytes", "sea_decode_member_quantiles",
-    "sea_decode_member_crps_grad", "sea_decode_member_crps_grad_ws_bytes",
+    "sea_decode_member_crps_grad", "sea_decode_member_crps_grad_ws_bytes", "sea_decode_member_crps_grad_packed",
     "sea_gemm_fewrows", "sea_qkv_rope_fewrows", "sea_row_chain", "sea_row_chain_riders", "sea_gemm_adaln", "sea_mlp_block", "sea_adaln_qkv", "sea_splitk_finish",
     "sea_encoder_block_ws_floats", "sea_encoder_block_fwd", "sea_encoder_block_bwd",
     "sea_silu_outer_bwd_dc", "sea_silu_outer_bwd_dc_ws_floats", "sea_ib_bwd_dc",

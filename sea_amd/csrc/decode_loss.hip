@@ -2990,51 +2990,75 @@ extern "C" int64_t sea_decode_member_crps_grad_ws_bytes(int B, int P, int n_fiel
     return (int64_t)B * P * mv_chunks(Cp) * n_fields_total * (VF_SUMS * 8 + (int64_t)members * S * 4);
 }
 
-extern "C" int sea_decode_member_crps_grad(const SeaDecodeMseGroup* groups, int n_groups, const SeaDecodeMemberCrpsGrad* p, int dtype, void* stream) {
-    SEA_REQUIRE(groups != nullptr && p != nullptr, "sea_decode_member_crps_grad: null argument table");
-    SEA_REQUIRE(n_groups >= 1 && n_groups <= SEA_DECODE_MSE_MAX_GROUPS, "sea_decode_member_crps_grad: n_groups=%d outside 1..%d", n_groups, SEA_DECODE_MSE_MAX_GROUPS);
-    SEA_REQUIRE(dtype == SEA_F32 || dtype == SEA_BF16, "sea_decode_member_crps_grad: bad dtype %d", dtype);
+// The argument checks of sea_decode_member_crps_grad and sea_decode_member_crps_grad_packed (the same struct, the same messages under the caller's name `fn`),
+// in two parts, because each entry point names what it does not carry between them.
+static int member_crps_check_args(const char* fn, const SeaDecodeMseGroup* groups, int n_groups, const SeaDecodeMemberCrpsGrad* p, int dtype) {
+    SEA_REQUIRE(groups != nullptr && p != nullptr, "%s: null argument table", fn);
+    SEA_REQUIRE(n_groups >= 1 && n_groups <= SEA_DECODE_MSE_MAX_GROUPS, "%s: n_groups=%d outside 1..%d", fn, n_groups, SEA_DECODE_MSE_MAX_GROUPS);
+    SEA_REQUIRE(dtype == SEA_F32 || dtype == SEA_BF16, "%s: bad dtype %d", fn, dtype);
     if (dtype != SEA_BF16) {
-        sea_set_error("sea_decode_member_crps_grad: unsupported: bf16 only (the fp32 decoder composes the decode and the formulas under autograd)");
+        sea_set_error("%s: unsupported: bf16 only (the fp32 decoder composes the decode and the formulas under autograd)", fn);
         return SEA_EUNSUPPORTED;
     }
     const SeaDecodeMemberCrpsGrad& P = *p;
     SEA_REQUIRE(P.obs != nullptr && P.loss != nullptr && P.sums != nullptr && P.status != nullptr && P.work != nullptr,
-                "sea_decode_member_crps_grad: null pointer (obs, loss, sums, status and work are required; prec_field, prec, field_weight, counts and logw may be NULL)");
-    SEA_REQUIRE(P.M >= 1, "sea_decode_member_crps_grad: M=%d must be positive", P.M);
-    SEA_REQUIRE(P.S >= 8 && P.S % 8 == 0, "sea_decode_member_crps_grad: S=%d must be a positive multiple of 8", P.S);
-    SEA_REQUIRE(P.Cp >= 32 && P.Cp % 32 == 0, "sea_decode_member_crps_grad: Cp=%d must be a positive multiple of 32", P.Cp);
-    SEA_REQUIRE(P.C >= 1 && P.C <= P.Cp, "sea_decode_member_crps_grad: C=%d must lie in 1..Cp=%d", P.C, P.Cp);
-    SEA_REQUIRE(P.P >= 1, "sea_decode_member_crps_grad: P=%d must be positive", P.P);
-    SEA_REQUIRE(P.members >= 1, "sea_decode_member_crps_grad: members=%d must be positive", P.members);
-    SEA_REQUIRE((int64_t)P.M % ((int64_t)P.P * P.members) == 0, "sea_decode_member_crps_grad: M=%d is not a multiple of P * members = %d * %d", P.M, P.P, P.members);
-    SEA_REQUIRE(P.n_fields_total >= 1 && P.n_fields_total <= 65535, "sea_decode_member_crps_grad: n_fields_total=%d outside 1..65535 (a grid dimension)", P.n_fields_total);
-    SEA_REQUIRE(P.ld_field >= P.C && P.ld_row >= 0, "sea_decode_member_crps_grad: obs strides ld_row=%lld, ld_field=%lld must cover C=%d", (long long)P.ld_row,
+                "%s: null pointer (obs, loss, sums, status and work are required; prec_field, prec, field_weight, counts and logw may be NULL)", fn);
+    SEA_REQUIRE(P.M >= 1, "%s: M=%d must be positive", fn, P.M);
+    SEA_REQUIRE(P.S >= 8 && P.S % 8 == 0, "%s: S=%d must be a positive multiple of 8", fn, P.S);
+    SEA_REQUIRE(P.Cp >= 32 && P.Cp % 32 == 0, "%s: Cp=%d must be a positive multiple of 32", fn, P.Cp);
+    SEA_REQUIRE(P.C >= 1 && P.C <= P.Cp, "%s: C=%d must lie in 1..Cp=%d", fn, P.C, P.Cp);
+    SEA_REQUIRE(P.P >= 1, "%s: P=%d must be positive", fn, P.P);
+    SEA_REQUIRE(P.members >= 1, "%s: members=%d must be positive", fn, P.members);
+    SEA_REQUIRE((int64_t)P.M % ((int64_t)P.P * P.members) == 0, "%s: M=%d is not a multiple of P * members = %d * %d", fn, P.M, P.P, P.members);
+    SEA_REQUIRE(P.n_fields_total >= 1 && P.n_fields_total <= 65535, "%s: n_fields_total=%d outside 1..65535 (a grid dimension)", fn, P.n_fields_total);
+    SEA_REQUIRE(P.ld_field >= P.C && P.ld_row >= 0, "%s: obs strides ld_row=%lld, ld_field=%lld must cover C=%d", fn, (long long)P.ld_row,
                 (long long)P.ld_field, P.C);
-    SEA_REQUIRE(P.prec == nullptr || (P.ld_pfield >= P.C && P.ld_prow >= 0), "sea_decode_member_crps_grad: prec strides ld_prow=%lld, ld_pfield=%lld must cover C=%d",
+    SEA_REQUIRE(P.prec == nullptr || (P.ld_pfield >= P.C && P.ld_prow >= 0), "%s: prec strides ld_prow=%lld, ld_pfield=%lld must cover C=%d", fn,
                 (long long)P.ld_prow, (long long)P.ld_pfield, P.C);
-    SEA_REQUIRE(P.unbiased == 0 || P.unbiased == 1, "sea_decode_member_crps_grad: unbiased=%d must be 0 or 1", P.unbiased);
+    SEA_REQUIRE(P.unbiased == 0 || P.unbiased == 1, "%s: unbiased=%d must be 0 or 1", fn, P.unbiased);
     SEA_REQUIRE(sea_aligned4(P.obs) && sea_aligned4(P.prec_field) && sea_aligned4(P.prec) && sea_aligned4(P.field_weight) && sea_aligned4(P.counts) && sea_aligned4(P.logw) &&
                     sea_aligned4(P.loss) && sea_aligned4(P.status) && (reinterpret_cast<uintptr_t>(P.sums) & 7u) == 0 && (reinterpret_cast<uintptr_t>(P.work) & 7u) == 0,
-                "sea_decode_member_crps_grad: misaligned pointer (f32 and int32 buffers need 4 bytes; sums and work 8)");
+                "%s: misaligned pointer (f32 and int32 buffers need 4 bytes; sums and work 8)", fn);
     int64_t covered = 0;
     for (int g = 0; g < n_groups; ++g) {
         const SeaDecodeMseGroup& G = groups[g];
-        SEA_REQUIRE(G.H != nullptr && G.W2 != nullptr && G.bias != nullptr && G.dH != nullptr, "sea_decode_member_crps_grad: group %d: null pointer (H, W2, bias or dH)", g);
+        SEA_REQUIRE(G.H != nullptr && G.W2 != nullptr && G.bias != nullptr && G.dH != nullptr, "%s: group %d: null pointer (H, W2, bias or dH)", fn, g);
         SEA_REQUIRE(sea_aligned16(G.H) && sea_aligned16(G.W2) && sea_aligned16(G.bias) && sea_aligned16(G.dH) && sea_aligned16(G.Z),
-                    "sea_decode_member_crps_grad: group %d: pointers must be 16-byte aligned", g);
+                    "%s: group %d: pointers must be 16-byte aligned", fn, g);
         SEA_REQUIRE(G.ldh >= P.S && G.ldh % 8 == 0 && G.ldw >= P.S && G.ldw % 8 == 0 && G.lddh >= P.S && (G.Z == nullptr || G.ldz >= P.S),
-                    "sea_decode_member_crps_grad: group %d: row strides ldh=%d ldw=%d lddh=%d ldz=%d must cover S=%d (ldh, ldw multiples of 8)", g, G.ldh, G.ldw, G.lddh, G.ldz, P.S);
+                    "%s: group %d: row strides ldh=%d ldw=%d lddh=%d ldz=%d must cover S=%d (ldh, ldw multiples of 8)", fn, g, G.ldh, G.ldw, G.lddh, G.ldz, P.S);
         SEA_REQUIRE(G.n_fields >= 1 && G.field0 >= 0 && (int64_t)G.field0 + G.n_fields <= P.n_fields_total,
-                    "sea_decode_member_crps_grad: group %d: n_fields=%d, field0=%d outside the %d fields", g, G.n_fields, G.field0, P.n_fields_total);
-        SEA_REQUIRE((int64_t)G.n_fields * P.Cp <= 0x7fffffffLL / 2, "sea_decode_member_crps_grad: group %d: too many output columns", g);
+                    "%s: group %d: n_fields=%d, field0=%d outside the %d fields", fn, g, G.n_fields, G.field0, P.n_fields_total);
+        SEA_REQUIRE((int64_t)G.n_fields * P.Cp <= 0x7fffffffLL / 2, "%s: group %d: too many output columns", fn, g);
         for (int h = 0; h < g; ++h)
             SEA_REQUIRE(G.field0 >= groups[h].field0 + groups[h].n_fields || groups[h].field0 >= G.field0 + G.n_fields,
-                        "sea_decode_member_crps_grad: group %d: its fields overlap those of group %d (a cell is scored once)", g, h);
+                        "%s: group %d: its fields overlap those of group %d (a cell is scored once)", fn, g, h);
         covered += G.n_fields;
     }
-    SEA_REQUIRE(covered == P.n_fields_total, "sea_decode_member_crps_grad: the groups cover %lld of the %d fields (every field needs exactly one group)", (long long)covered,
+    SEA_REQUIRE(covered == P.n_fields_total, "%s: the groups cover %lld of the %d fields (every field needs exactly one group)", fn, (long long)covered,
                 P.n_fields_total);
+    return SEA_OK;
+}
+
+static int member_crps_check_size(const char* fn, const SeaDecodeMemberCrpsGrad& P, int64_t* B_out, int* Q_out) {
+    const int64_t BP = (int64_t)P.M / P.members;
+    const int64_t B = BP / P.P;
+    SEA_REQUIRE(BP <= 0x7fffffffLL && B <= 65535, "%s: %lld histories; a launch carries up to 65535", fn, (long long)B);
+    const int Q = mv_chunks(P.Cp);
+    SEA_REQUIRE(Q <= 65535 && B + (int64_t)P.M <= 0x7fffffffLL, "%s: too many rows or column chunks", fn);
+    const int64_t need = sea_decode_member_crps_grad_ws_bytes((int)B, P.P, P.n_fields_total, P.members, P.Cp, P.S);
+    SEA_REQUIRE(P.work_bytes >= need,
+                "%s: work_bytes=%lld below the %lld that sea_decode_member_crps_grad_ws_bytes(B=%d, P=%d, n_fields_total=%d, members=%d, Cp=%d, S=%d) asks for", fn,
+                (long long)P.work_bytes, (long long)need, (int)B, P.P, P.n_fields_total, P.members, P.Cp, P.S);
+    *B_out = B;
+    *Q_out = Q;
+    return SEA_OK;
+}
+
+extern "C" int sea_decode_member_crps_grad(const SeaDecodeMseGroup* groups, int n_groups, const SeaDecodeMemberCrpsGrad* p, int dtype, void* stream) {
+    const int rc = member_crps_check_args("sea_decode_member_crps_grad", groups, n_groups, p, dtype);
+    if (rc != SEA_OK) return rc;
+    const SeaDecodeMemberCrpsGrad& P = *p;
     if (P.S > 640) {
         sea_set_error("sea_decode_member_crps_grad: unsupported: hidden width S=%d above 640", P.S);
         return SEA_EUNSUPPORTED;
@@ -3048,15 +3072,10 @@ extern "C" int sea_decode_member_crps_grad(const SeaDecodeMseGroup* groups, int 
                       P.members, P.S, MC_W8_MAX_SP_V2);
         return SEA_EUNSUPPORTED;
     }
-    const int64_t BP = (int64_t)P.M / P.members;
-    const int64_t B = BP / P.P;
-    SEA_REQUIRE(BP <= 0x7fffffffLL && B <= 65535, "sea_decode_member_crps_grad: %lld histories; a launch carries up to 65535", (long long)B);
-    const int Q = mv_chunks(P.Cp);
-    SEA_REQUIRE(Q <= 65535 && B + (int64_t)P.M <= 0x7fffffffLL, "sea_decode_member_crps_grad: too many rows or column chunks");
-    const int64_t need = sea_decode_member_crps_grad_ws_bytes((int)B, P.P, P.n_fields_total, P.members, P.Cp, P.S);
-    SEA_REQUIRE(P.work_bytes >= need,
-                "sea_decode_member_crps_grad: work_bytes=%lld below the %lld that sea_decode_member_crps_grad_ws_bytes(B=%d, P=%d, n_fields_total=%d, members=%d, Cp=%d, S=%d) asks for",
-                (long long)P.work_bytes, (long long)need, (int)B, P.P, P.n_fields_total, P.members, P.Cp, P.S);
+    int64_t B = 0;
+    int Q = 0;
+    const int rs = member_crps_check_size("sea_decode_member_crps_grad", P, &B, &Q);
+    if (rs != SEA_OK) return rs;
 
     MemberCrpsLaunch L;
     memset(&L, 0, sizeof(L));
@@ -3065,7 +3084,7 @@ extern "C" int sea_decode_member_crps_grad(const SeaDecodeMseGroup* groups, int 
     L.n_groups = n_groups;
     L.chunks = Q;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const dim3 grid((unsigned)BP, (unsigned)P.n_fields_total, (unsigned)Q);
+    const dim3 grid((unsigned)(B * P.P), (unsigned)P.n_fields_total, (unsigned)Q);
     const int S = P.S;
     if (P.members > 64) {
         if (S <= 128) member_crps_launch<128, 2, 8>(L, grid, s);
@@ -3080,5 +3099,379 @@ extern "C" int sea_decode_member_crps_grad(const SeaDecodeMseGroup* groups, int 
     }
     member_crps_finish_kernel<<<dim3((unsigned)(B + P.M)), dim3(256), 0, s>>>(L, (int)B);
     SEA_CHECK_LAUNCH("sea_decode_member_crps_grad");
+    return SEA_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------------------------
+// sea_decode_member_crps_grad_packed: sea_decode_member_crps_grad's launch 1 for 1 .. 32 members, several HISTORIES per workgroup (include/sea_hip.h;
+// DESIGN.md section 7n).  At 4 members the unpacked form decodes 4 real rows of a 16-row MFMA tile, scores with 4 of 64 lanes and pays the tile loads,
+// the barriers and the 32 wave-passes of a tile for them.  Here a workgroup serves (a group of HG histories, patch, field, chunk): with NP the member
+// count rounded up to a power of two (at least 2), slot g NP + i of 64 is member i of the group's history g, HG = 64 / NP (less where LDS does not
+// admit it: mcp_groups).  Waves 0 - 3 decode 16 slots each with the unpacked form's MFMA sequence into Vs[column][slot]; per column a wave scores all
+// the group's histories at once (vf_score_seg_ex<NP>: segments of NP lanes), each lane forms its G with ITS history's c and rounds it to the two bf16
+// terms at its slot's row of the G images, and the segment's first lane finishes the reading (vf_finish_reading) and files its eight terms; the second
+// product multiplies the slot rows' G fragments against the same tile image; thread (g, i) adds sum i of history g, columns ascending, one chain per
+// history across the tiles.  The per-history setup (log-weights, live flags, w, q, c, status) is the unpacked kernel's statements with the same
+// j-ascending chains, run by the history's own slot threads.  A history that is not scored and a history index >= B in the last group are dead
+// segments by selects: no cell of theirs has weight, so they write zero sums and nothing else; the workgroup leaves early only when none of its
+// histories has anything to score.  Outputs go to the unpacked form's workspace slots ((b P + p) Q + ck) F + f, and member_crps_finish_kernel runs
+// unchanged as launch 2.  The bits are the unpacked form's: an MFMA row does not depend on the other rows of its tile, a segment's butterflies pair as
+// the whole wave's do (verify_score.hpp), and every chain of a history is the same chain — one writer per element, no floating-point atomics, nothing
+// of a history depends on another.
+// LDS: the term staging [32 columns][HG][8] fp64 is 64 KiB at HG = 32; beside the 640-wide tile images that is above a CU's 160 KiB, so that one
+// instantiation (SP = 640, NP = 2) runs HG = 16 (slots 0 .. 31, waves 0 and 1 decode); every other one has HG = 64 / NP.
+constexpr int MCP_VP = 65;        // floats per column of the packed value image: 64 slots and one of pad
+constexpr int MCP_STATIC = 2560;  // bound on the kernel's static LDS (the per-slot and per-segment setup arrays and the barriers' words: at most 2176 bytes)
+
+template <int SP, int HG>
+constexpr int mcp_lds_bytes() { return 2 * DM_TC * (SP * 2 + DM_PAD) + DM_TC * MCP_VP * 4 + 2 * 64 * MC_GP * 2 + HG * DM_TC * (VF_SUMS * 8 + 2 * 4); }
+
+template <int SP, int NP>
+constexpr int mcp_groups() { return (SP > 512 && NP == 2) ? 16 : 64 / NP; }
+
+template <int SP, int NP, int NW, int HG>
+__global__ __launch_bounds__(64 * NW) void decode_member_crps_pack_kernel(const MemberCrpsLaunch L, const int B) {
+#pragma clang fp reassociate(off)
+    constexpr int NT = 64 * NW;
+    constexpr int KS = SP / 32;
+    constexpr int ST = SP / 16;
+    constexpr int PITCH = SP * 2 + DM_PAD;
+    constexpr int TILE = DM_TC * PITCH;
+    constexpr int NCH = SP * 4 / NT;
+    constexpr int VP = MCP_VP;
+    constexpr int SEG = 64 / NP;
+    static_assert(NCH * NT == DM_TC * (SP / 8), "whole chunks per thread");
+    static_assert(HG >= 1 && HG <= SEG, "a group's slots fit one wave");
+    static_assert(NT >= HG * VF_SUMS, "a thread per (history, sum)");
+    static_assert(mcp_lds_bytes<SP, HG>() + MCP_STATIC <= 160 * 1024, "the tile images, the value and G images and the per-(history, column) staging fit a CU's LDS");
+    extern __shared__ __attribute__((aligned(16))) char smem[];   // 2 tile images; the value image [32][VP]; the two G images [64][MC_GP]; terms [32][HG][8]; y, pv [HG][32]
+    float* Vs = reinterpret_cast<float*>(smem + 2 * TILE);
+    __bf16* Gs = reinterpret_cast<__bf16*>(smem + 2 * TILE + DM_TC * VP * 4);
+    __bf16* Gt = Gs + 64 * MC_GP;
+    double* term_s = reinterpret_cast<double*>(smem + 2 * TILE + DM_TC * VP * 4 + 2 * 64 * MC_GP * 2);
+    float* y_s = reinterpret_cast<float*>(term_s + DM_TC * HG * VF_SUMS);
+    float* pv_s = y_s + HG * DM_TC;
+    __shared__ double lw_s[64], w_s[64], cq_s[SEG];
+    __shared__ int live_s[64], inv_s[64], ok_s[SEG];
+    static_assert(sizeof(double) * (128 + SEG) + sizeof(int) * (128 + SEG) <= MCP_STATIC, "MCP_STATIC bounds the static arrays");
+
+    const SeaDecodeMemberCrpsGrad& P = L.p;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), li = lane & 15, lg = lane >> 4;
+    const int S = P.S, C = P.C, Cp = P.Cp, N = P.members, F = P.n_fields_total;
+    const int fg = blockIdx.y, ck = blockIdx.z, Q = gridDim.z;
+    const int grp = blockIdx.x / P.P, patch = blockIdx.x - grp * P.P;
+    const int b0 = grp * HG;                              // the group's first history
+    const int nh = B - b0 < HG ? B - b0 : HG;             // its histories: [b0, b0 + nh)
+    char* const wpart0 = static_cast<char*>(P.work) + mc_sum_bytes((int64_t)B * P.P, Q, F);
+    auto ws_slot = [&](int g) { return (((int64_t)(b0 + g) * P.P + patch) * Q + ck) * F + fg; };   // history b0 + g's place in both parts of the workspace
+
+    int lim = C;   // valid columns of this patch: [0, lim) — uniform over the workgroup
+    if (P.counts != nullptr) {
+        const int cnt = P.counts[patch];
+        lim = cnt < 0 ? 0 : (cnt > C ? C : cnt);
+    }
+    const int tpf = (lim + DM_TC - 1) / DM_TC;
+    const int tb = ck * MV_CHUNK, te = tpf < tb + MV_CHUNK ? tpf : tb + MV_CHUNK;
+
+    // the weights of the group's histories: the unpacked kernel's statements, thread `tid` < 64 as member si of segment sg (its chains run over its own segment)
+    const int si = tid & (NP - 1), sg = (tid & 63) / NP, sbase = (tid & 63) - si;
+    const bool slot_t = tid < 64;
+    const bool member = slot_t && sg < nh && si < N;
+    int invalid = 0, alive = 0;
+    if (slot_t) {
+        const float lw = (member && P.logw != nullptr) ? P.logw[(int64_t)(b0 + sg) * N + si] : 0.f;
+        invalid = (member && (lw != lw || lw == INFINITY)) ? 1 : 0;
+        alive = (member && !invalid && lw != -INFINITY) ? 1 : 0;
+        lw_s[tid] = (double)lw;
+        live_s[tid] = alive;
+        inv_s[tid] = invalid;
+    }
+    __syncthreads();
+    int ok = 0;
+    if (slot_t) {
+        int n_live = 0, inv = 0;
+        for (int j = 0; j < N; ++j) {
+            n_live += live_s[sbase + j];
+            inv |= inv_s[sbase + j];
+        }
+        ok = (sg < nh && !inv && n_live > 0) ? 1 : 0;   // the history is scored
+        if (si == 0) {
+            ok_s[sg] = ok;
+            if (sg < nh && patch == 0 && fg == 0 && ck == 0) P.status[b0 + sg] = ok ? n_live : -1;
+        }
+    }
+    const int any_ok = __syncthreads_or(ok);
+    if (!any_ok || te <= tb) {   // uniform: nothing to score in this chunk for any history of the group; the finish launch passes their partials over
+        if (tid < HG * VF_SUMS && (tid >> 3) < nh) (reinterpret_cast<double*>(P.work) + ws_slot(tid >> 3) * VF_SUMS)[tid & 7] = 0.0;
+        return;
+    }
+    if (slot_t) {
+        double mx = -INFINITY;
+        for (int j = 0; j < N; ++j) mx = lw_s[sbase + j] > mx ? lw_s[sbase + j] : mx;
+        w_s[tid] = (alive && ok) ? exp(lw_s[tid] - mx) : 0.0;
+    }
+    __syncthreads();
+    double my_w = 0.0;
+    if (slot_t) {
+        double W = 0.0;
+        for (int j = 0; j < N; ++j) W += w_s[sbase + j];
+        my_w = (member && ok) ? w_s[tid] / W : 0.0;
+    }
+    __syncthreads();
+    if (slot_t) w_s[tid] = my_w;
+    __syncthreads();
+    if (slot_t) {
+        double q = 0.0;
+        for (int j = 0; j < N; ++j) q = fma(w_s[sbase + j], w_s[sbase + j], q);
+        if (si == 0) cq_s[sg] = P.unbiased ? 1.0 - q : 1.0;
+    }
+    __syncthreads();
+    float fwv = P.field_weight != nullptr ? P.field_weight[fg] : 1.f;
+    fwv = fwv > 0.f ? fwv : 0.f;   // false for NaN
+    const double fwd = (double)fwv;
+
+    // the scoring lane: member lane & (NP - 1) of segment lane / NP
+    const int lseg = lane / NP;
+    const int gs = lseg < HG ? lseg : 0;
+    const bool seg_on = lseg < HG && ok_s[gs] != 0;
+    const bool lead = lseg < HG && (lane & (NP - 1)) == 0;
+    const double cq = cq_s[lseg];
+
+    // the decoding lane: slot j0 + li
+    const int j0 = wave * 16;
+    const bool active = j0 < nh * NP;
+    const int dg = (j0 + li) / NP, di = (j0 + li) & (NP - 1);
+    const bool dvalid = dg < nh && di < N;
+    const int64_t m = ((int64_t)(b0 + (dvalid ? dg : 0)) * N + (dvalid ? di : 0)) * P.P + patch;
+    double acc_sum = 0.0;
+
+    int gsel = 0;
+    for (int gi = 1; gi < L.n_groups; ++gi) gsel = (fg >= L.g[gi].field0 && fg < L.g[gi].field0 + L.g[gi].n_fields) ? gi : gsel;
+    const SeaDecodeMseGroup& G = L.g[gsel];
+    const int j = fg - G.field0;
+    const __bf16* H = static_cast<const __bf16*>(G.H);
+    const __bf16* W2 = static_cast<const __bf16*>(G.W2);
+    uint4 hf[KS];
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+        const int s = ks * 32 + 8 * lg;
+        if (ks * 32 + 32 <= S) {
+            hf[ks] = *reinterpret_cast<const uint4*>(H + m * G.ldh + s);
+        } else {
+            const uint4 v = *reinterpret_cast<const uint4*>(H + m * G.ldh + (s < S ? s : 0));
+            hf[ks] = s < S ? v : make_uint4(0u, 0u, 0u, 0u);
+        }
+    }
+    f32x4 dh[ST];
+#pragma unroll
+    for (int st = 0; st < ST; ++st) dh[st] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    const int n_tiles = te - tb, t0 = j * tpf + tb;
+    uint4 wr[NCH];
+    dm_load_tile<SP, NT>(wr, W2, G.ldw, S, Cp, tpf, t0, tid);
+    dm_store_tile<SP, NT>(wr, smem, tid);
+    __syncthreads();
+
+    typedef dm_s16x4 __attribute__((address_space(3))) * lds_p;
+    for (int t = 0; t < n_tiles; ++t) {
+        const char* buf = smem + (t & 1) * TILE;
+        const int cb = (tb + t) * DM_TC;
+
+        // a: per (history, column) the cell's weight and reading (a history that is not scored: no weight); decode into the value image
+        for (int e = tid; e < HG * DM_TC; e += NT) {
+            const int g = e >> 5, c = cb + (e & 31);
+            const int64_t bpg = (int64_t)(b0 + g) * P.P + patch;
+            float w = 0.f;
+            if (c < lim && ok_s[g] != 0) {
+                const float pf = P.prec_field != nullptr ? P.prec_field[fg] : 1.f;
+                const float pm = P.prec != nullptr ? P.prec[bpg * P.ld_prow + (int64_t)fg * P.ld_pfield + c] : 1.f;
+                w = mul1(pf > 0.f ? pf : 0.f, pm > 0.f ? pm : 0.f);
+            }
+            const bool on = w > 0.f;
+            pv_s[e] = on ? w : 0.f;
+            y_s[e] = on ? P.obs[bpg * P.ld_row + (int64_t)fg * P.ld_field + c] : 0.f;
+        }
+        if (active) {
+            f32x4 acc[2][2];
+#pragma unroll
+            for (int sub = 0; sub < 2; ++sub) {
+                const float bv = G.bias[j * Cp + cb + sub * 16 + li];
+                acc[sub][0] = f32x4{bv, bv, bv, bv};
+                acc[sub][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {
+                if (ks * 32 < S) {
+#pragma unroll
+                    for (int sub = 0; sub < 2; ++sub) {
+                        const uint4 wv = *reinterpret_cast<const uint4*>(buf + (sub * 16 + li) * PITCH + (ks * 4 + lg) * 16);
+                        mma16<__bf16>(hf[ks], wv, acc[sub][ks & 1]);
+                    }
+                }
+            }
+#pragma unroll
+            for (int sub = 0; sub < 2; ++sub) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) Vs[(sub * 16 + li) * VP + j0 + 4 * lg + r] = acc[sub][0][r] + acc[sub][1][r];
+            }
+        }
+        __syncthreads();
+        if (t + 1 < n_tiles) dm_load_tile<SP, NT>(wr, W2, G.ldw, S, Cp, tpf, t0 + t + 1, tid);
+
+        // b: a column per wave at a time, all the group's histories at once; the lane's G goes to its slot's row of the G images (every row is written,
+        //    the dead ones as 0) and the segment's first lane finishes the reading and files its terms
+        for (int cl = wave; cl < DM_TC; cl += NW) {
+            const float pv = seg_on ? pv_s[gs * DM_TC + cl] : 0.f;
+            const float yf = seg_on ? y_s[gs * DM_TC + cl] : 0.f;
+            const bool on = pv > 0.f;
+            if (__ballot(on) == 0) {   // uniform: the cell is dead in every history
+                Gs[lane * MC_GP + cl] = Gt[lane * MC_GP + cl] = (__bf16)0.f;
+                if (lead) {
+#pragma unroll
+                    for (int i = 0; i < VF_SUMS; ++i) term_s[(cl * HG + gs) * VF_SUMS + i] = 0.0;
+                }
+                continue;
+            }
+            float x;
+            double w, below;
+            bool lv;
+            VfReading r = vf_score_seg_ex<NP>(Vs + cl * VP, w_s, live_s, N, lane, seg_on, yf, pv, x, w, below, lv);
+            r.state = on ? r.state : 1;   // a segment whose cell is dead
+            {
+                const double g = r.state == 0 ? fwd * vf_crps_grad(x, w, below, lv, yf, cq) : 0.0;
+                const float gf = (float)g;
+                const __bf16 g0 = (__bf16)gf;                       // the leading term: gf rounded to bf16 once
+                Gs[lane * MC_GP + cl] = g0;
+                Gt[lane * MC_GP + cl] = (__bf16)(gf - (float)g0);   // what that rounding left (exact in f32), rounded to bf16: 0 where gf is a bf16 value
+            }
+            double tm[VF_SUMS];
+            (void)vf_finish_reading(r, yf, pv, cq, tm);
+            if (lead) {
+#pragma unroll
+                for (int i = 0; i < VF_SUMS; ++i) term_s[(cl * HG + gs) * VF_SUMS + i] = tm[i];
+            }
+        }
+        __syncthreads();
+
+        // c: the waves' second product against the same tile image
+        if (active) {
+            const uint2 glo = *reinterpret_cast<const uint2*>(Gs + (j0 + li) * MC_GP + 4 * lg);
+            const uint2 ghi = *reinterpret_cast<const uint2*>(Gs + (j0 + li) * MC_GP + 16 + 4 * lg);
+            const uint4 da = make_uint4(glo.x, glo.y, ghi.x, ghi.y);
+            const uint2 tlo = *reinterpret_cast<const uint2*>(Gt + (j0 + li) * MC_GP + 4 * lg);
+            const uint2 thi = *reinterpret_cast<const uint2*>(Gt + (j0 + li) * MC_GP + 16 + 4 * lg);
+            const uint4 dt = make_uint4(tlo.x, tlo.y, thi.x, thi.y);
+            const char* tbp = buf + (4 * lg + (li >> 2)) * PITCH + (4 * (li & 3)) * 2;
+#pragma unroll
+            for (int st = 0; st < ST; ++st) {
+                if (st * 16 < S) {
+                    const dm_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(tbp + st * 32));
+                    const dm_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(tbp + st * 32 + 16 * PITCH));
+                    const uint2 l2 = __builtin_bit_cast(uint2, lo), h2 = __builtin_bit_cast(uint2, hi);
+                    const uint4 wt = make_uint4(l2.x, l2.y, h2.x, h2.y);
+                    mma16<__bf16>(da, wt, dh[st]);
+                    mma16<__bf16>(dt, wt, dh[st]);   // the trailing term against the same operand: a fixed order, the leading term first
+                }
+            }
+        }
+        if (t + 1 < n_tiles) dm_store_tile<SP, NT>(wr, smem + ((t + 1) & 1) * TILE, tid);
+        __syncthreads();
+
+        // d: thread (g, i): sum i of history g, columns ascending
+        if (tid < HG * VF_SUMS)
+            for (int k = 0; k < DM_TC; ++k) acc_sum += term_s[k * HG * VF_SUMS + tid];
+    }
+    if (tid < HG * VF_SUMS && (tid >> 3) < nh) (reinterpret_cast<double*>(P.work) + ws_slot(tid >> 3) * VF_SUMS)[tid & 7] = acc_sum;
+    if (active) {   // register r of tile st is slot j0 + 4 g + r, hidden column 16 st + (lane & 15); a history that is not scored writes no partial
+        float* wrow[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int slot = j0 + 4 * lg + r, g = slot / NP, i = slot & (NP - 1);
+            const bool wv = g < nh && i < N && ok_s[g < SEG ? g : 0] != 0;
+            wrow[r] = wv ? reinterpret_cast<float*>(wpart0) + (ws_slot(g) * N + i) * S : nullptr;
+        }
+#pragma unroll
+        for (int st = 0; st < ST; ++st) {
+            const int s = st * 16 + li;
+            if (s < S) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    if (wrow[r] != nullptr) wrow[r][s] = dh[st][r];
+            }
+        }
+    }
+}
+
+template <int SP, int NP, int NW>
+static void member_crps_pack_launch(const MemberCrpsLaunch& L, int B, hipStream_t s) {
+    constexpr int HG = mcp_groups<SP, NP>();
+    constexpr int lds = mcp_lds_bytes<SP, HG>();
+    static bool set_on[64] = {false};   // per device: the dynamic part is above the 64 kB a kernel gets without the attribute in most instantiations
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = -1;
+    if (dev < 0 || !set_on[dev]) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(decode_member_crps_pack_kernel<SP, NP, NW, HG>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        if (dev >= 0) set_on[dev] = true;
+    }
+    const dim3 grid((unsigned)(((B + HG - 1) / HG) * L.p.P), (unsigned)L.p.n_fields_total, (unsigned)L.chunks);
+    decode_member_crps_pack_kernel<SP, NP, NW, HG><<<grid, dim3(64 * NW), lds, s>>>(L, B);
+    // the form's name carries NP; the histories per workgroup are 64 / NP, except "pk2h16" (S above 512 at 1 or 2 members: 16)
+    sea_note_form(NP == 2 ? (HG == 32 ? "decode.member_crps_grad.pk2" : "decode.member_crps_grad.pk2h16")
+                          : NP == 4 ? "decode.member_crps_grad.pk4" : NP == 8 ? "decode.member_crps_grad.pk8" : NP == 16 ? "decode.member_crps_grad.pk16" : "decode.member_crps_grad.pk32",
+                  SP, lds);
+}
+
+template <int NP>
+static void member_crps_pack_dispatch(const MemberCrpsLaunch& L, int B, hipStream_t s) {
+    const int S = L.p.S;
+    if (S <= 128) member_crps_pack_launch<128, NP, 8>(L, B, s);
+    else if (S <= 256) member_crps_pack_launch<256, NP, 8>(L, B, s);
+    else if (S <= 384) member_crps_pack_launch<384, NP, 8>(L, B, s);
+    else if (S <= 512) member_crps_pack_launch<512, NP, 4>(L, B, s);
+    else member_crps_pack_launch<640, NP, 4>(L, B, s);
+}
+
+constexpr int MCP_MAX_N = 32;   // the packed form's member counts: 1 .. 32 (above: one history fills most of a wave; the unpacked form serves)
+
+// Every (S, NP) up to S = 640 compiles without scratch (DESIGN.md section 7n has the table), so nothing below MCP_MAX_N members is refused.
+static bool member_crps_pack_supported(int S, int members) { return members >= 1 && members <= MCP_MAX_N && S <= 640; }
+
+extern "C" int sea_decode_member_crps_grad_packed(const SeaDecodeMseGroup* groups, int n_groups, const SeaDecodeMemberCrpsGrad* p, int dtype, void* stream) {
+    const int rc = member_crps_check_args("sea_decode_member_crps_grad_packed", groups, n_groups, p, dtype);
+    if (rc != SEA_OK) return rc;
+    const SeaDecodeMemberCrpsGrad& P = *p;
+    if (P.S > 640) {
+        sea_set_error("sea_decode_member_crps_grad_packed: unsupported: hidden width S=%d above 640", P.S);
+        return SEA_EUNSUPPORTED;
+    }
+    if (P.members > MCP_MAX_N) {
+        sea_set_error("sea_decode_member_crps_grad_packed: unsupported: members=%d above %d (the packed form serves 1 .. %d members; sea_decode_member_crps_grad serves above)",
+                      P.members, MCP_MAX_N, MCP_MAX_N);
+        return SEA_EUNSUPPORTED;
+    }
+    if (!member_crps_pack_supported(P.S, P.members)) {
+        sea_set_error("sea_decode_member_crps_grad_packed: unsupported: members=%d at hidden width S=%d is not shipped", P.members, P.S);
+        return SEA_EUNSUPPORTED;
+    }
+    int64_t B = 0;
+    int Q = 0;
+    const int rs = member_crps_check_size("sea_decode_member_crps_grad_packed", P, &B, &Q);
+    if (rs != SEA_OK) return rs;
+
+    MemberCrpsLaunch L;
+    memset(&L, 0, sizeof(L));
+    for (int g = 0; g < n_groups; ++g) L.g[g] = groups[g];
+    L.p = P;
+    L.n_groups = n_groups;
+    L.chunks = Q;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int n = P.members;
+    if (n <= 2) member_crps_pack_dispatch<2>(L, (int)B, s);
+    else if (n <= 4) member_crps_pack_dispatch<4>(L, (int)B, s);
+    else if (n <= 8) member_crps_pack_dispatch<8>(L, (int)B, s);
+    else if (n <= 16) member_crps_pack_dispatch<16>(L, (int)B, s);
+    else member_crps_pack_dispatch<32>(L, (int)B, s);
+    member_crps_finish_kernel<<<dim3((unsigned)(B + P.M)), dim3(256), 0, s>>>(L, (int)B);
+    SEA_CHECK_LAUNCH("sea_decode_member_crps_grad_packed");
     return SEA_OK;
 }

@@ -1570,7 +1570,8 @@ class EnsembleCRPSLoss(torch.nn.Module):
     cell (the fair CRPS with unbiased=True; field_weight scales a field's share) — on the device; nothing is read back.  `decoder` is a frozen sea_amd
     Decode (decoder.requires_grad_(False)); it is not registered as a sub-module, so the loss has no parameters."""
 
-    def __init__(self, decoder, n_patches: int, members: int, counts=None, layout: str = "BPFC", unbiased: bool = True, field_weight=None, fused=None):
+    def __init__(self, decoder, n_patches: int, members: int, counts=None, layout: str = "BPFC", unbiased: bool = True, field_weight=None, fused=None,
+                 pack=None):
         super().__init__()
         if layout not in ("BPFC", "BPCF"):
             raise ValueError(f"EnsembleCRPSLoss: layout must be 'BPFC' or 'BPCF', got {layout!r}")
@@ -1585,6 +1586,7 @@ class EnsembleCRPSLoss(torch.nn.Module):
                 raise ValueError(f"EnsembleCRPSLoss: field_weight must be {n_fields} finite numbers >= 0, got {field_weight.tolist()}")
         object.__setattr__(self, "decoder", decoder)
         self.n_patches, self.members, self.counts, self.layout, self.unbiased, self.fused = n_patches, members, counts, layout, bool(unbiased), fused
+        self.pack = pack   # Decode.member_crps_loss's pack: None (its rule), True (the packed form, 1 .. 32 members) or False
         self._fw_src, self._fw = field_weight, {}
 
     def _field_weight_on(self, device):
@@ -1631,6 +1633,7 @@ class EnsembleCRPSLoss(torch.nn.Module):
             prec = rel(precision)
             prec = prec.reshape((B * T,) + tuple(prec.shape[2:]))
         lw = None if logw is None else logw.detach().view(B, 1, n).expand(B, T, n).reshape(-1)
+        kw = {} if self.pack is None else {"pack": self.pack}   # None: the decoder's own rule, whatever decoder this is
         loss, count = self.decoder.member_crps_loss(z, tgt, n, counts=self.counts, precision=prec, field_weight=self._field_weight_on(output.device), logw=lw,
-                                                    unbiased=self.unbiased, fused=self.fused)
+                                                    unbiased=self.unbiased, fused=self.fused, **kw)
         return loss.sum() / count.sum().clamp_min(1.0).to(loss.dtype)

@@ -847,7 +847,7 @@ class Decode(nn.Module):
 
     def member_crps_loss(self, z: torch.Tensor, obs: torch.Tensor, members: int, counts=None, precision: Optional[torch.Tensor] = None,
                          field_precision: Optional[torch.Tensor] = None, field_weight: Optional[torch.Tensor] = None, logw: Optional[torch.Tensor] = None,
-                         unbiased: bool = True, fused: Optional[bool] = None):
+                         unbiased: bool = True, fused: Optional[bool] = None, pack: Optional[bool] = None):
         """The CRPS of an ensemble's DECODED fields against a dense observation as a loss: (loss, count) with loss float32 [B, n_fields],
         loss[b, f] = field_weight[f] * sum over the patches and the live, good cells of field f of the cell's CRPS (member_verify's sums[..., 1]:
         the fair CRPS with unbiased=True), differentiable with a gradient to z only, and count float64 [B, n_fields] the number of those cells
@@ -874,7 +874,13 @@ class Decode(nn.Module):
         8.6 - 65.5 GB).  Member counts between 8 and 64 were not measured: the rule INTERPOLATES between the two regimes there (both ends are ahead by
         4x or more).  The composed path serves elsewhere: below those row counts and above 64 members, where nothing was measured (the bench's
         128-member shapes have hidden widths the fused form refuses), in fp32, and for any shape the fused form refuses (MLP_hidden above 640
-        included) — such a shape raises only under fused=True."""
+        included) — such a shape raises only under fused=True.
+        pack (the fused path with a gradient only; under no_grad the path is member_verify whatever pack says): True takes
+        sea_decode_member_crps_grad_packed — several histories per workgroup for 1 .. 32 members, every output with the bits of pack=False — and
+        raises ValueError for a shape that form refuses (above 32 members) and with fused=False; with fused=None it selects the fused launches, as
+        fused=True does.  False is the unpacked form.  None is crps_loss_pack_rule(members, rows, MLP_hidden, dtype), read from
+        profiles/crps_pack_bench.txt: the packed form at 2 .. 32 members from 4096 (history, patch) pairs on — ahead in every
+        measured row, 2.05x (32 members) to 15 - 16x (4 members) and 17 - 30x (2 members) — and the unpacked form elsewhere, tiny shapes included."""
         from ..ensemble import _CrpsComposedFn, _field_cell_weights
 
         what = "sea_amd.Decode.member_crps_loss"
@@ -907,6 +913,15 @@ class Decode(nn.Module):
         self._require_frozen("member_crps_loss")
         dt = self._act_dtype()
         carried = ops.decode_member_crps_grad_supported(self.MLP_hidden, members)
+        if pack is not None and not isinstance(pack, bool):
+            raise ValueError(f"{what}: pack must be None, True or False, got {pack!r}")
+        if pack:   # an explicit request for a form of the fused launches: a shape it refuses raises, as fused=True does
+            if fused is not None and not fused:
+                raise ValueError(f"{what}: pack=True is a form of the fused launches; fused=False takes the composed path")
+            if not ops.decode_member_crps_pack_supported(self.MLP_hidden, members):
+                raise ValueError(f"{what}: the packed form carries 1 .. {N.CRPS_PACK_MAX_N} members at MLP_hidden <= {N.DECODE_MSE_MAX_S}; got {members} members at "
+                                 f"MLP_hidden = {self.MLP_hidden} (pack=False, or None, take the unpacked form)")
+            fused = True
         if fused is None:
             # profiles/crps_loss_bench.txt: the fused launches are ahead in every measured row of both regimes — 64 members at 4096 and
             # 16384 rows, 4 and 8 members at 16384 - 131072 rows; above 64 members no shape the bench has is carried, below 4096 rows (below 16384 at up to 8
@@ -917,6 +932,8 @@ class Decode(nn.Module):
         if fused and not carried:
             raise ValueError(f"{what}: the fused launches carry up to 64 members, or up to {N.FIELD_VERIFY_MAX_N} at MLP_hidden <= {N.CRPS_GRAD_W8_MAX_S}; got "
                              f"{members} members at MLP_hidden = {self.MLP_hidden} (fused=False, or None, take the composed path)")
+        if pack is None:
+            pack = bool(fused) and crps_loss_pack_rule(members, Bm * P, self.MLP_hidden, dt)
         cnt, _ = self._valid_counts(counts, P, z.device, allow_empty=True, what="member_crps_loss")
         N.require_gpu(z, "Decode.member_crps_loss input")
         want_grad = z.requires_grad and torch.is_grad_enabled()
@@ -937,7 +954,7 @@ class Decode(nn.Module):
             t3 = t.reshape(B * P, n_fields, t.shape[3])
             return t3 if t3.stride(2) == 1 and t3.stride(1) >= C and t3.stride(0) >= 0 else t3[..., :C].contiguous()
 
-        return _DecodeCrpsFn.apply(z, self, rows(obs), None if prec is None else rows(prec), pf, fw, cnt, lw, members, bool(unbiased))
+        return _DecodeCrpsFn.apply(z, self, rows(obs), None if prec is None else rows(prec), pf, fw, cnt, lw, members, bool(unbiased), bool(pack))
 
     def member_quantiles(self, z: torch.Tensor, members: int, levels=(), thresholds: Optional[torch.Tensor] = None, weights: Optional[torch.Tensor] = None,
                          counts=None, fused: Optional[bool] = None):
@@ -1198,7 +1215,7 @@ class _DecodeCrpsFn(torch.autograd.Function):
     upstream gradient that differs between the fields of one group turns that slice into NaN (a select, nothing read back)."""
 
     @staticmethod
-    def forward(ctx, z, dec, o3, p3, pf, fw, cnt, lw, members, unbiased):
+    def forward(ctx, z, dec, o3, p3, pf, fw, cnt, lw, members, unbiased, pack=False):
         dt = torch.bfloat16
         with torch.no_grad():
             Bm, P, G, D = z.shape
@@ -1209,7 +1226,7 @@ class _DecodeCrpsFn(torch.autograd.Function):
             dpre = [torch.empty(M, dec.MLP_hidden, device=z.device, dtype=dt) for _ in range(G)]
             groups = [dict(H=hid[g], W2=W2[g], bias=bias[g], dH=dpre[g], Z=pre[g]) for g in range(G)]
             loss, sums, _ = ops.decode_member_crps_grad(groups, o3, dec.n_inp, dec._n_inp_p, P, members, prec=p3, prec_field=pf, field_weight=fw, counts=cnt,
-                                                        logw=lw, unbiased=unbiased, dtype=dt)
+                                                        logw=lw, unbiased=unbiased, dtype=dt, pack=pack)
             ctx.save_for_backward(dec._input_grad(dpre, dt).view(Bm, P, G, D).to(z.dtype))
         ctx.groups, ctx.members = [len(g) for g in dec.field_groups], members
         count = sums[..., 0].contiguous()
@@ -1228,10 +1245,26 @@ class _DecodeCrpsFn(torch.autograd.Function):
             cols.append(torch.where(same, first, torch.full_like(first, float("nan"))))
             off += k
         factor = torch.stack(cols, dim=1).view(Bm // n, 1, 1, G, 1)                       # [B, 1, 1, G, 1]
-        return (dz.view(Bm // n, n, P, G, D) * factor).view(Bm, P, G, D).to(dz.dtype), None, None, None, None, None, None, None, None, None
+        return (dz.view(Bm // n, n, P, G, D) * factor).view(Bm, P, G, D).to(dz.dtype), None, None, None, None, None, None, None, None, None, None
 
 
 CRPS_LOSS_FUSED_MIN_ROWS_SMALL = 16384   # ... and with up to 8 members, where the smallest measured size is 64 histories x 4 members x 64 patches
+CRPS_LOSS_PACK_MEMBERS = (2, 32)   # member_crps_loss, pack=None: the packed form at these member counts (the measured 2, 4, 8, 16, 32 and between them) ...
+CRPS_LOSS_PACK_MIN_PAIRS = 4096    # ... from this many (history, patch) pairs on, i.e. rows >= 4096 * members: the smallest measured size at every member count (64 histories x 64 patches)
+
+
+def crps_loss_pack_rule(members: int, rows: int, hidden: int, dtype) -> bool:
+    """Decode.member_crps_loss's pack=None: whether the fused launches take the packed form (sea_decode_member_crps_grad_packed) at this member count,
+    number of decoder rows (B * members * n_patches), MLP_hidden and compute dtype.  A pure function of its arguments, read from
+    profiles/crps_pack_bench.txt: at 2, 4, 8, 16 and 32 members x 64 histories (4 and 8 members: x 256 too) x 64 patches the
+    packed form is ahead of the unpacked one in EVERY measured row — 17 - 30x at 2 members, 15 - 16x at 4, 8.0 - 8.5x at 8, 4.0x at 16, 2.05x at 32,
+    against a run-to-run spread of up to 1.4 % — with the same bits, so it is taken at 2 .. 32 members (the counts between measured ones lie between
+    two that are both ahead) from the smallest measured size on: 4096 (history, patch) pairs, rows >= 4096 * members.  Everywhere else — tiny shapes,
+    1 member and above 32 members, fp32, widths the form does not carry — the unpacked form."""
+    return (dtype == torch.bfloat16 and isinstance(members, int) and CRPS_LOSS_PACK_MEMBERS[0] <= members <= CRPS_LOSS_PACK_MEMBERS[1]
+            and rows >= CRPS_LOSS_PACK_MIN_PAIRS * members and ops.decode_member_crps_pack_supported(hidden, members))
+
+
 CRPS_LOSS_FUSED_MIN_ROWS = 4096   # member_crps_loss, fused=None: the fused launches from this many decoder rows (B * members * n_patches) on — the smallest measured size
 
 

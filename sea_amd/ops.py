@@ -1947,16 +1947,34 @@ def decode_member_crps_grad_supported(S: int, members: int) -> bool:
     return 8 <= S <= N.DECODE_MSE_MAX_S and 1 <= members <= N.FIELD_VERIFY_MAX_N and (members <= 64 or S <= N.CRPS_GRAD_W8_MAX_S)
 
 
+def decode_member_crps_pack_supported(S: int, members: int) -> bool:
+    """Whether sea_decode_member_crps_grad_packed carries this hidden width and member count (include/sea_hip.h: 1 .. 32 members at every hidden width
+    the unpacked form carries, S up to 640; every instantiation compiles without scratch, so none is refused)."""
+    return 8 <= S <= N.DECODE_MSE_MAX_S and S % 8 == 0 and 1 <= members <= N.CRPS_PACK_MAX_N
+
+
+def decode_member_crps_pack_shape(S: int, members: int):
+    """(NP, HG) of the packed form at this shape: NP the member count rounded up to a power of two (at least 2), HG the histories one workgroup
+    serves — 64 / NP, except 16 at 1 or 2 members above S = 512 (include/sea_hip.h; DESIGN.md section 7n has the LDS table)."""
+    if not decode_member_crps_pack_supported(S, members):
+        raise ValueError(f"decode_member_crps_pack_shape: S = {S}, members = {members} is not carried by the packed form")
+    NP = 2
+    while NP < members:
+        NP *= 2
+    return NP, (16 if NP == 2 and S > 512 else 64 // NP)
+
+
 def decode_member_crps_grad(groups: Sequence[Dict], obs: torch.Tensor, C_: int, Cp: int, n_patches: int, members: int, prec: Optional[torch.Tensor] = None,
                             prec_field: Optional[torch.Tensor] = None, field_weight: Optional[torch.Tensor] = None, counts: Optional[torch.Tensor] = None,
-                            logw: Optional[torch.Tensor] = None, unbiased: bool = True, dtype: torch.dtype = torch.bfloat16):
+                            logw: Optional[torch.Tensor] = None, unbiased: bool = True, dtype: torch.dtype = torch.bfloat16, pack: bool = False):
     """sea_decode_member_crps_grad: the CRPS of an ensemble's decoded fields against a dense observation, summed per (history, field), WITH its gradient
     to the hidden rows (include/sea_hip.h states the formulas) — neither the members' decoded fields nor their gradient are written.  groups: dicts H,
     W2, bias as decode_member_verify, plus dH act [M, S] (written IN PLACE, every element) and an optional Z act [M, S] (gelu' of it is applied); obs,
     prec_field, prec, counts, logw as decode_member_verify; field_weight None or a contiguous f32 [n_fields].  Returns (loss f32 [B, n_fields] =
     field_weight * sums[..., 1], sums f64 [B, n_fields, 8] with decode_member_verify's bits, status int32 [B]) on the device; nothing is read back.
     A shape the fused form does not carry (decode_member_crps_grad_supported) raises RuntimeError from the library's SEA_EUNSUPPORTED.  Everything is
-    checked on the host before the launch."""
+    checked on the host before the launch.  pack=True: sea_decode_member_crps_grad_packed through the same argument table — several histories per
+    workgroup for 1 .. 32 members (decode_member_crps_pack_supported), every output with the bits of pack=False; a shape it refuses raises likewise."""
     what = "decode_member_crps_grad"
     if dtype != torch.bfloat16:
         raise ValueError(f"{what}: the fused launch is bf16 only, got {dtype}")
@@ -2023,7 +2041,8 @@ def decode_member_crps_grad(groups: Sequence[Dict], obs: torch.Tensor, C_: int, 
     work = torch.empty(max(need, 8), device=dev, dtype=torch.uint8)   # (a refused shape asks for -1: the entry point below says why)
     arr, P = (N.SeaDecodeMseGroup * len(groups))(), N.SeaDecodeMemberCrpsGrad()
     fill_decode_member_crps_grad(arr, P, groups, obs, prec_field, prec, field_weight, counts, logw, n_patches, n, C_, Cp, unbiased, loss, sums, status, work)
-    N.check(N.lib().sea_decode_member_crps_grad(arr, len(groups), C.byref(P), N.dtype_code(dtype), N.stream_ptr()), "sea_decode_member_crps_grad")
+    entry = "sea_decode_member_crps_grad_packed" if pack else "sea_decode_member_crps_grad"
+    N.check(getattr(N.lib(), entry)(arr, len(groups), C.byref(P), N.dtype_code(dtype), N.stream_ptr()), entry)
     return loss, sums, status
 
 
