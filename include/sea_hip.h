@@ -1638,6 +1638,100 @@ typedef struct {
 } SeaDecodeMemberQuantiles;  /* 128 bytes */
 int sea_decode_member_quantiles(const SeaDecodeMseGroup* groups, int n_groups, const SeaDecodeMemberQuantiles* p, int dtype, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Verification of EXCEEDANCE forecasts ("the probability that the field is above thr here"): the Brier score, the counts its reliability / resolution /
+ * uncertainty decomposition and the reliability diagram are read from, and the hit counts of the ROC curve — for a dense snapshot of the decoded
+ * fields (sea_decode_member_brier, two launches, the members' decoded fields never written) and for predictions at sensors that already exist
+ * (sea_ensemble_brier, two launches).  Both run the same device code per reading (sea_amd/csrc/brier_score.hpp).
+ * Members and weights: per history b, from logw exactly as in sea_ensemble_verify, in fp64: lw_j = 0 when logw is NULL; a member with lw_j = -inf is
+ * DEAD; mx = max_j lw_j; e_j = exp(lw_j - mx) (dead: 0); W = sum_j e_j over j ascending; status[b] = L (the live members), or -1 when a lw_j is NaN or
+ * +inf or none is finite: the history's maps are then 0 and it adds nothing to sums, hist and hits.
+ * Readings: a reading is LIVE, DEAD or BAD exactly as in sea_decode_member_verify (a cell: the weight w[f, c] of that entry point from counts,
+ * prec_field and prec, the same selects, a NaN counts as 0) and sea_ensemble_verify (a sensor: p = prec[b, k], NULL: 1; dead when not p > 0).  A live
+ * reading whose y, weight or a live member's value is not finite is BAD.  The precision only decides live or dead: no score is weighted by it.  obs is
+ * not read at a dead reading.
+ * Per live, good reading with members' values x_j (f32, compared as the f32 they are), reading y, and threshold thr (thr[t, f] per field for the
+ * dense form, thr[t, k] per sensor for the sensor form; f32; 1 <= n_thr <= 8):
+ *     m = #{ live j : x_j > thr }                                     strict; an integer in 0 .. L
+ *     p = (sum of e_j over the live j with x_j > thr) / W             fp64: summed first — through the fixed xor butterfly over the lanes that
+ *                                                                     sea_decode_member_quantiles uses for its exceedance maps — then divided once.
+ *                                                                     With equal weights p = m / L exactly, and the f32 prob map has the bits of that
+ *                                                                     launch's exceed map.
+ *     o = [ y > thr ]                                                 strict
+ *     A NaN threshold makes every comparison false (p = 0, m = 0, o = 0); the Python layer refuses thresholds that are not finite.
+ * Per (history, field, threshold) — per (history, threshold) for the sensor form — over the live, good readings in the order
+ * sea_decode_member_verify / sea_ensemble_verify add their sums (patches ascending, columns ascending inside a patch; sensors ascending), from the
+ * fp64 values before any rounding:
+ *     sums[.., t, 0..4] = count, sum (p - o)^2, sum p, sum o, count of BAD readings                                  (f64 [B, F, T, 5] / [B, T, 5])
+ *     hist[.., t, m]    = the number of live, good readings with m exceeding members, m = 0 .. N                     (int64 [B, F, T, N + 1] / [B, T, N + 1])
+ *     hits[.., t, m]    = the number of those readings with o = 1                                                    (int64, hist's shape)
+ * accumulate = 1 adds a call's sums, hist and hits onto the existing ones; 0 overwrites them.  status is always overwritten.
+ * Optional per-reading maps, each may be NULL; threshold t's map starts at t * ld_map:
+ *     prob  f32 [T, B, P, F, ld_out] (sensor form: [T, B, ld_out])   (float) p
+ *     brier f32, the same shape                                      (float) (p - o)^2
+ * EVERY element of a given map is written: a dead reading, the columns from C (and from counts[p]) up to ld_out and a history with status -1 give 0, a
+ * BAD reading NaN (the sensor form writes [b, k < K]).
+ * No floating-point atomics; the histograms are counted with integer adds in LDS.  Two runs give the same bits; a history's outputs are those of a call
+ * holding it alone; a reading's own outputs do not depend on the other readings.
+ *
+ * sea_decode_member_brier: operands H, W2, bias, ldh, ldw, n_fields, field0 of SeaDecodeMseGroup and obs, prec_field, prec, counts with their strides
+ * exactly as in sea_decode_member_verify; the row order and the decode are sea_decode_member_quantiles' (the same device functions: a cell has that
+ * launch's bits).  Launch 1: that launch's grid in its thresholds-only form — a workgroup of 8 waves per (history, patch, field, chunk of 512 columns),
+ * 32 columns decoded at a time and staged in LDS as [column][member], a wave per column at a time with a member (two above 64) per lane — plus
+ * sea_decode_member_verify's reads of obs, prec_field, prec and counts; thread (k, t) finishes threshold t of column k; the workgroup's fp64 partial sums
+ * (columns ascending) and its integer histograms, sized by the call's n_thr and members, go to `work`.  Launch 2: a workgroup per (history, field,
+ * threshold) adds its partials in ascending (patch, chunk) order.
+ * Requirements: as sea_decode_member_verify (dtype SEA_BF16, SEA_F32: SEA_EUNSUPPORTED; S a multiple of 8, above 640: SEA_EUNSUPPORTED; members above
+ * 128: SEA_EUNSUPPORTED; ...; at most 8191 fields: fields x thresholds is a grid dimension), and 1 <= n_thr <= 8, thr non-NULL, hits non-NULL and 8-byte aligned, ld_out >= C and ld_map >= B * P * F * ld_out when
+ * a map is given, work_bytes >= sea_decode_member_brier_ws_bytes(B, P, F, members, Cp, n_thr).  Returns -1 with the entry point named in
+ * sea_last_error() otherwise, before any device is touched.  Notes the form "decode.member_brier" (a = the padded hidden width, b = the dynamic LDS
+ * bytes).
+ * sea_ensemble_brier: pred, obs, prec and logw exactly as in sea_ensemble_verify; thr f32 [n_thr, ld_thr], a threshold per sensor.  Launch 1: a
+ * workgroup per (tile of 16 sensors, history), the tile's predictions staged as [sensor][member]; launch 2: a workgroup per (history, threshold) adds the tiles in
+ * ascending order.  Requirements as sea_ensemble_verify, and 1 <= n_thr <= 8, ld_thr >= K, ld_map >= B * ld_out when a map is given, work_bytes >=
+ * sea_ensemble_brier_ws_bytes(B, N, K, n_thr).  Notes the form "brier" (a = members per lane, 1 or 2; b = the dynamic LDS bytes).
+ * (Additions to ABI version 8.  The structs are not in sea_struct_sizes(): sizeof(SeaDecodeMemberBrier) is 200, sizeof(SeaEnsembleBrier) 176.)
+ */
+#define SEA_BRIER_SUMS 5
+typedef struct {
+    const float* obs;          /* f32, rows of the observation: [B * P, F, >= C] through ld_row, ld_field */
+    const float* prec_field;   /* f32 [F], or NULL (1) */
+    const float* prec;         /* f32 map in obs's layout through ld_prow, ld_pfield, or NULL (1) */
+    const int32_t* counts;     /* device int32 [P] or NULL */
+    const float* logw;         /* NULL (equal weights) or f32 [B N], unnormalised */
+    const float* thr;          /* f32 [n_thr, F] */
+    float* prob;               /* f32 [n_thr, B, P, F, ld_out] through ld_map, or NULL */
+    float* brier;
+    double* sums;              /* f64 [B, F, n_thr, 5] */
+    int64_t* hist;             /* int64 [B, F, n_thr, N + 1] */
+    int64_t* hits;             /* int64 [B, F, n_thr, N + 1] */
+    int32_t* status;           /* int32 [B] */
+    void* work;                /* work_bytes bytes */
+    int64_t ld_row, ld_field, ld_prow, ld_pfield, ld_out, ld_map, work_bytes;
+    int32_t M, S, C, Cp, P, members, n_fields_total, n_thr, accumulate, pad_;
+} SeaDecodeMemberBrier;      /* 200 bytes */
+int64_t sea_decode_member_brier_ws_bytes(int B, int P, int n_fields_total, int members, int Cp, int n_thr);   /* -1 for sizes the entry point refuses */
+int sea_decode_member_brier(const SeaDecodeMseGroup* groups, int n_groups, const SeaDecodeMemberBrier* p, int dtype, void* stream);
+
+typedef struct {
+    const float* pred;       /* f32 [B N, ld_pred] */
+    const float* obs;        /* f32 [B, ld_obs] */
+    const float* prec;       /* NULL (1), f32 [K] (ld_prec = 0) or f32 [B, ld_prec] */
+    const float* logw;       /* NULL (equal weights) or f32 [B N], unnormalised */
+    const float* thr;        /* f32 [n_thr, ld_thr] */
+    float* prob;             /* f32 [n_thr, B, ld_out] through ld_map, or NULL */
+    float* brier;
+    double* sums;            /* f64 [B, n_thr, 5] */
+    int64_t* hist;           /* int64 [B, n_thr, N + 1] */
+    int64_t* hits;           /* int64 [B, n_thr, N + 1] */
+    int32_t* status;         /* int32 [B] */
+    void* work;              /* work_bytes bytes */
+    int64_t ld_pred, ld_obs, ld_prec, ld_thr, ld_out, ld_map, work_bytes;
+    int32_t B, N, K, n_thr, accumulate, pad_;
+} SeaEnsembleBrier;          /* 176 bytes */
+int64_t sea_ensemble_brier_ws_bytes(int B, int N, int K, int n_thr);   /* -1 for sizes the entry point refuses */
+int sea_ensemble_brier(const SeaEnsembleBrier* p, void* stream);
+
 /* Tuning aid: register a device buffer of n_steps * 64 8-byte words that the persistent form fills with 100 MHz clock stamps of its hand-offs
  * (tools/kv_persist_timeline.py); NULL switches it off. */
 void sea_kv_debug_stamps(unsigned long long* buf);

@@ -375,6 +375,28 @@ class SeaDecodeMemberQuantiles(C.Structure):
                 ("n_fields_total", _i32), ("pad_", _i32)]
 
 
+BRIER_MAX_T = QUANTILE_MAX_LEVELS   # thresholds one launch of sea_decode_member_brier / sea_ensemble_brier carries
+BRIER_SUMS = 5               # fp64 sums per (history, field, threshold): count, sum (p - o)^2, sum p, sum o, count of bad readings
+BRIER_MAX_N = 128            # members per history of sea_decode_member_brier / sea_ensemble_brier
+
+
+class SeaDecodeMemberBrier(C.Structure):
+    # sea_decode_member_brier, 200 bytes (not in ABI_STRUCTS, like its siblings; tests/test_brier_cpu.py checks the size the header states and the argument checks)
+    _fields_ = [("obs", _vp), ("prec_field", _vp), ("prec", _vp), ("counts", _vp), ("logw", _vp), ("thr", _vp), ("prob", _vp), ("brier", _vp),
+                ("sums", _vp), ("hist", _vp), ("hits", _vp), ("status", _vp), ("work", _vp),
+                ("ld_row", _i64), ("ld_field", _i64), ("ld_prow", _i64), ("ld_pfield", _i64), ("ld_out", _i64), ("ld_map", _i64), ("work_bytes", _i64),
+                ("M", _i32), ("S", _i32), ("C", _i32), ("Cp", _i32), ("P", _i32), ("members", _i32), ("n_fields_total", _i32), ("n_thr", _i32),
+                ("accumulate", _i32), ("pad_", _i32)]
+
+
+class SeaEnsembleBrier(C.Structure):
+    # sea_ensemble_brier, 176 bytes (not in ABI_STRUCTS either)
+    _fields_ = [("pred", _vp), ("obs", _vp), ("prec", _vp), ("logw", _vp), ("thr", _vp), ("prob", _vp), ("brier", _vp), ("sums", _vp), ("hist", _vp),
+                ("hits", _vp), ("status", _vp), ("work", _vp),
+                ("ld_pred", _i64), ("ld_obs", _i64), ("ld_prec", _i64), ("ld_thr", _i64), ("ld_out", _i64), ("ld_map", _i64), ("work_bytes", _i64),
+                ("B", _i32), ("N", _i32), ("K", _i32), ("n_thr", _i32), ("accumulate", _i32), ("pad_", _i32)]
+
+
 ENKF_MAX_N = 128             # members per history of sea_enkf_transform / sea_ensemble_mix
 SENSOR_TILE = 32             # sensors per W2 tile of sea_decode_sensor_sse: every (group, patch) segment of a SensorSet is padded to a multiple of it
 SENSOR_MAX_PATCHES = 65535   # observed patches one launch of sea_decode_sensor_sse carries (a grid dimension)
@@ -529,6 +551,14 @@ def lib() -> C.CDLL:
     L.sea_decode_member_crps_grad_packed.restype = C.c_int
     L.sea_decode_member_quantiles.argtypes = [C.POINTER(SeaDecodeMseGroup), C.c_int, C.POINTER(SeaDecodeMemberQuantiles), C.c_int, _vp]
     L.sea_decode_member_quantiles.restype = C.c_int
+    L.sea_decode_member_brier.argtypes = [C.POINTER(SeaDecodeMseGroup), C.c_int, C.POINTER(SeaDecodeMemberBrier), C.c_int, _vp]
+    L.sea_decode_member_brier.restype = C.c_int
+    L.sea_decode_member_brier_ws_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.sea_decode_member_brier_ws_bytes.restype = _i64
+    L.sea_ensemble_brier.argtypes = [C.POINTER(SeaEnsembleBrier), _vp]
+    L.sea_ensemble_brier.restype = C.c_int
+    L.sea_ensemble_brier_ws_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
+    L.sea_ensemble_brier_ws_bytes.restype = _i64
     for name in ("sea_attention_bwd", "sea_wgrad_grouped", "sea_transpose_weights", "sea_rownorm_bwd", "sea_silu_outer_bwd", "sea_ib_bwd",
                  "sea_silu_outer_bwd_dc", "sea_ib_bwd_dc"):
         getattr(L, name).restype = C.c_int
@@ -562,6 +592,7 @@ EXPORTED_SYMBOLS = (
     "sea_attention_bwd", "sea_dropout_mask", "sea_run_list", "sea_run_list_steps", "sea_unpatchify", "sea_gemm_rownorm", "sea_exchange_tail", "sea_patchify", "sea_silu_outer_ib", "sea_mlp_fc1_ln_gelu", "sea_mlp_fc2_proj_norm", "sea_kv_rollout", "sea_kv_arena_words", "sea_kv_debug_stamps",
     "sea_kv_cache_fill", "sea_kv_cache_fork", "sea_kv_cache_gather", "sea_decode_mse", "sea_decode_member_sse", "sea_decode_member_moments", "sea_decode_sensor_sse", "sea_decode_sensor_grad", "sea_decode_field_grad", "sea_resample_systematic", "sea_enkf_transform", "sea_enkf_transform_gram", "sea_decode_member_gram", "sea_ensemble_mix", "sea_ensemble_verify", "sea_ensemble_verify_ws_bytes", "sea_decode_member_verify", "sea_decode_member_verify_ws_bytes", "sea_decode_member_quantiles",
     "sea_decode_member_crps_grad", "sea_decode_member_crps_grad_ws_bytes", "sea_decode_member_crps_grad_packed",
+    "sea_decode_member_brier", "sea_decode_member_brier_ws_bytes", "sea_ensemble_brier", "sea_ensemble_brier_ws_bytes",
     "sea_gemm_fewrows", "sea_qkv_rope_fewrows", "sea_row_chain", "sea_row_chain_riders", "sea_gemm_adaln", "sea_mlp_block", "sea_adaln_qkv", "sea_splitk_finish",
     "sea_encoder_block_ws_floats", "sea_encoder_block_fwd", "sea_encoder_block_bwd",
     "sea_silu_outer_bwd_dc", "sea_silu_outer_bwd_dc_ws_floats", "sea_ib_bwd_dc",

@@ -37,6 +37,7 @@
 #include "sea_common.hpp"
 #include "verify_score.hpp"   // sea_decode_member_verify scores a cell as verify_kernel scores a sensor
 #include "quantile_select.hpp"   // sea_decode_member_quantiles reads a column out
+#include "brier_score.hpp"       // sea_decode_member_brier scores a cell as brier_kernel scores a sensor
 
 typedef short dm_s16x4 __attribute__((ext_vector_type(4)));
 
@@ -2419,6 +2420,52 @@ struct MemberQuantLaunch {
     int n_groups;
 };
 
+// The decode of decode_member_quantiles_kernel and decode_member_brier_kernel, one copy for both: a cell decoded by either has the same bits.
+// mq_load_row: a lane's k-slices of its member's hidden row.  A row at or beyond N repeats member 0's: its values are stored to V and never read.  The
+// k-step that straddles S loads column 0 where s >= S and selects zeros (the tile image is zero there, but 0 * NaN is not).
+template <int SP>
+__device__ __forceinline__ void mq_load_row(uint4 (&hf)[SP / 32], const __bf16* hrow, const int S, const int lg) {
+#pragma unroll
+    for (int ks = 0; ks < SP / 32; ++ks) {
+        const int s = ks * 32 + 8 * lg;
+        if (ks * 32 + 32 <= S) {
+            hf[ks] = *reinterpret_cast<const uint4*>(hrow + s);
+        } else {
+            const uint4 v = *reinterpret_cast<const uint4*>(hrow + (s < S ? s : 0));
+            hf[ks] = s < S ? v : make_uint4(0u, 0u, 0u, 0u);
+        }
+    }
+}
+
+// mq_decode_tile: a wave's 16 members times the tile's 32 columns into the value image; bias: the tile's 32 entries; vcol: V + the wave's first member.
+template <int SP>
+__device__ __forceinline__ void mq_decode_tile(const uint4 (&hf)[SP / 32], const char* buf, const float* bias, const int S, const int li, const int lg, float* vcol) {
+    constexpr int PITCH = SP * 2 + DM_PAD;
+    f32x4 acc[2][2];
+#pragma unroll
+    for (int sub = 0; sub < 2; ++sub) {
+        const float bv = bias[sub * 16 + li];
+        acc[sub][0] = f32x4{bv, bv, bv, bv};
+        acc[sub][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+#pragma unroll
+    for (int ks = 0; ks < SP / 32; ++ks) {
+        if (ks * 32 < S) {
+#pragma unroll
+            for (int sub = 0; sub < 2; ++sub) {
+                const uint4 wv = *reinterpret_cast<const uint4*>(buf + (sub * 16 + li) * PITCH + (ks * 4 + lg) * 16);
+                mma16<__bf16>(hf[ks], wv, acc[sub][ks & 1]);
+            }
+        }
+    }
+#pragma unroll
+    for (int sub = 0; sub < 2; ++sub) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)   // plain C++: the first reader of an MFMA result must be an instruction the compiler sees
+            vcol[(sub * 16 + li) * MV_VP + 4 * lg + r] = acc[sub][0][r] + acc[sub][1][r];
+    }
+}
+
 template <int SP, int V>
 __global__ __launch_bounds__(MV_NT) void decode_member_quantiles_kernel(const MemberQuantLaunch L) {
 #pragma clang fp reassociate(off)
@@ -2488,18 +2535,7 @@ __global__ __launch_bounds__(MV_NT) void decode_member_quantiles_kernel(const Me
     const __bf16* H = static_cast<const __bf16*>(G.H);
     const __bf16* W2 = static_cast<const __bf16*>(G.W2);
     uint4 hf[KS];
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-        const int s = ks * 32 + 8 * lg;
-        // a row at or beyond N repeats member 0's: its values are stored to V and never read.  The k-step that straddles S loads column 0 where
-        // s >= S and selects zeros (the tile image is zero there, but 0 * NaN is not)
-        if (ks * 32 + 32 <= S) {
-            hf[ks] = *reinterpret_cast<const uint4*>(H + m * G.ldh + s);
-        } else {
-            const uint4 v = *reinterpret_cast<const uint4*>(H + m * G.ldh + (s < S ? s : 0));
-            hf[ks] = s < S ? v : make_uint4(0u, 0u, 0u, 0u);
-        }
-    }
+    mq_load_row<SP>(hf, H + m * G.ldh, S, lg);
     const int n_tiles = te - tb, t0 = j * tpf + tb;   // this chunk's tiles among the group's
     uint4 wr[NCH];
     dm_load_tile<SP, NT>(wr, W2, G.ldw, S, Cp, tpf, t0, tid);
@@ -2511,31 +2547,7 @@ __global__ __launch_bounds__(MV_NT) void decode_member_quantiles_kernel(const Me
         const int cb = (tb + t) * DM_TC;
 
         // a: decode into the value image
-        if (active) {
-            f32x4 acc[2][2];
-#pragma unroll
-            for (int sub = 0; sub < 2; ++sub) {
-                const float bv = G.bias[j * Cp + cb + sub * 16 + li];
-                acc[sub][0] = f32x4{bv, bv, bv, bv};
-                acc[sub][1] = f32x4{0.f, 0.f, 0.f, 0.f};
-            }
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {
-                if (ks * 32 < S) {
-#pragma unroll
-                    for (int sub = 0; sub < 2; ++sub) {
-                        const uint4 wv = *reinterpret_cast<const uint4*>(buf + (sub * 16 + li) * PITCH + (ks * 4 + lg) * 16);
-                        mma16<__bf16>(hf[ks], wv, acc[sub][ks & 1]);
-                    }
-                }
-            }
-#pragma unroll
-            for (int sub = 0; sub < 2; ++sub) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r)   // plain C++: the first reader of an MFMA result must be an instruction the compiler sees
-                    Vs[(sub * 16 + li) * VP + j0 + 4 * lg + r] = acc[sub][0][r] + acc[sub][1][r];
-            }
-        }
+        if (active) mq_decode_tile<SP>(hf, buf, G.bias + j * Cp + cb, S, li, lg, Vs + j0);
         __syncthreads();
         if (t + 1 < n_tiles) dm_load_tile<SP, NT>(wr, W2, G.ldw, S, Cp, tpf, t0 + t + 1, tid);   // in flight behind b
 
@@ -2652,6 +2664,285 @@ extern "C" int sea_decode_member_quantiles(const SeaDecodeMseGroup* groups, int 
     if (P.members <= 64) member_quantiles_dispatch<1>(L, grid, s);
     else member_quantiles_dispatch<2>(L, grid, s);
     SEA_CHECK_LAUNCH("sea_decode_member_quantiles");
+    return SEA_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------------------------
+// sea_decode_member_brier: the threshold scores of an ensemble against a DENSE observation of the decoded fields — Brier sums, the histograms of the
+// reliability diagram and the hit counts of the ROC (include/sea_hip.h states the definitions).  Launch 1 is decode_member_quantiles_kernel in its
+// thresholds-only form — its grid, mq_load_row / mq_decode_tile, the [column][member] value image — crossed with decode_member_verify_kernel's reads of
+// obs, prec_field, prec and counts and its live / dead / bad classification.  Per tile:
+//   a  threads 0 .. 31 form the columns' weights (decode_member_verify_kernel's selects) and read obs where the weight is positive; the waves decode;
+//   b  wave w scores the columns w, w + 8, w + 16, w + 24 (bs_column_wave, brier_score.hpp: per threshold one fp64 butterfly and two ballots);
+//   c  thread (k, t), k + 32 t, finishes threshold t of column k: the two maps — one writer per element, 128-byte segments —, the five terms, and the
+//      integer adds to the LDS histograms; the next tile of W2 goes to its LDS image meanwhile;
+//   d  thread (t, i) adds the tile's terms in ascending column order onto its running fp64 sum.
+// Three barriers per tile.  member_brier_finish_kernel: one workgroup per (history, field, threshold) adds its partials in ascending (patch, chunk) order.
+// LDS at SP = 640: 2 x 41984 (W2 images) + 16512 (V) dynamic, 24 kB static (weights, cells, terms, histograms at their maxima): 125 kB of the CU's 160.
+struct MemberBrierLaunch {
+    SeaDecodeMseGroup g[SEA_DECODE_MSE_MAX_GROUPS];
+    SeaDecodeMemberBrier p;
+    int n_groups;
+    int words;   // 8-byte words per (history, patch, chunk, field) of the workspace
+};
+
+template <int SP, int V>
+__global__ __launch_bounds__(MV_NT) void decode_member_brier_kernel(const MemberBrierLaunch L) {
+#pragma clang fp reassociate(off)
+    constexpr int NW = MV_NW;
+    constexpr int NT = MV_NT;
+    constexpr int KS = SP / 32;
+    constexpr int PITCH = SP * 2 + DM_PAD;
+    constexpr int TILE = DM_TC * PITCH;
+    constexpr int NCH = SP * 4 / NT;
+    constexpr int VP = MV_VP;
+    static_assert(NCH * NT == DM_TC * (SP / 8), "whole chunks per thread");
+    static_assert(DM_TC * BS_MAX_T <= NT, "a thread per (column, threshold)");
+    extern __shared__ __attribute__((aligned(16))) char smem[];   // 2 tile images; the value image [32][VP]
+    float* Vs = reinterpret_cast<float*>(smem + 2 * TILE);
+    __shared__ double lw_s[VF_MAX_N], w_s[VF_MAX_N];
+    __shared__ int live_s[VF_MAX_N];
+    __shared__ BsCell cell_s[DM_TC];
+    __shared__ double term_s[BS_MAX_T * BS_SUMS][DM_TC];
+    __shared__ int hist_s[2 * BS_MAX_T * (VF_MAX_N + 1)];   // [hist | hits][t][m] at the call's T and N
+    __shared__ float y_s[DM_TC], pv_s[DM_TC], thr_s[BS_MAX_T];
+
+    const SeaDecodeMemberBrier& P = L.p;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), li = lane & 15, lg = lane >> 4;
+    const int S = P.S, C = P.C, Cp = P.Cp, N = P.members, F = P.n_fields_total, T = P.n_thr, words = L.words;
+    const int bp = blockIdx.x, fg = blockIdx.y, ck = blockIdx.z, Q = gridDim.z;
+    const int b = bp / P.P, patch = bp - b * P.P;
+    const int64_t ld = P.ld_out;
+    const int64_t obase = ((int64_t)bp * F + fg) * ld;
+    const int nb = T * (N + 1);
+    double* const wsum = reinterpret_cast<double*>(P.work) + (((int64_t)bp * Q + ck) * F + fg) * words;
+    int32_t* const whist = reinterpret_cast<int32_t*>(wsum + T * BS_SUMS);
+
+    int lim = C;   // valid columns of this patch: [0, lim) — uniform over the workgroup
+    if (P.counts != nullptr) {
+        const int cnt = P.counts[patch];
+        lim = cnt < 0 ? 0 : (cnt > C ? C : cnt);
+    }
+    const int tpf = (lim + DM_TC - 1) / DM_TC;   // tiles of a field that hold valid columns
+    const int tb = ck * MV_CHUNK, te = tpf < tb + MV_CHUNK ? tpf : tb + MV_CHUNK;   // this workgroup's tiles: [tb, te)
+
+    for (int r = tid; r < 2 * nb; r += NT) hist_s[r] = 0;
+    if (tid < T) thr_s[tid] = P.thr[(int64_t)tid * F + fg];
+    double W;
+    const int n_live = bs_history_weights(P.logw, b, N, tid, lw_s, w_s, live_s, W);   // two barriers: hist_s and thr_s are set behind them
+    const bool unscored = n_live < 0;
+    if (patch == 0 && fg == 0 && ck == 0 && tid == 0) P.status[b] = n_live;
+    if (ck == 0 && (P.prob != nullptr || P.brier != nullptr)) {   // the columns no tile walks (all of them when the history is not scored or the patch has no valid column): 0
+        const int c0 = (unscored || tpf == 0) ? 0 : tpf * DM_TC;
+        for (int64_t c = c0 + tid; c < ld; c += NT) {
+            const int64_t at = obase + c;
+            for (int t = 0; t < T; ++t) {
+                if (P.prob != nullptr) P.prob[t * P.ld_map + at] = 0.f;
+                if (P.brier != nullptr) P.brier[t * P.ld_map + at] = 0.f;
+            }
+        }
+    }
+    if (unscored || te <= tb) {   // uniform: nothing to score in this chunk
+        for (int e = tid; e < words; e += NT) wsum[e] = 0.0;   // the sums, and the int32 bins: all bits zero
+        return;
+    }
+
+    const int j0 = wave * 16;
+    const bool active = j0 < N;                 // uniform over the wave
+    const int jm = j0 + li;
+    const int64_t m = ((int64_t)b * N + (jm < N ? jm : 0)) * P.P + patch;
+    double acc_sum = 0.0;                       // threads 0 .. 5 T - 1: the field's running sums
+
+    int gsel = 0;   // the group that holds the field: the entry point has checked that exactly one does
+    for (int gi = 1; gi < L.n_groups; ++gi) gsel = (fg >= L.g[gi].field0 && fg < L.g[gi].field0 + L.g[gi].n_fields) ? gi : gsel;
+    const SeaDecodeMseGroup& G = L.g[gsel];
+    const int j = fg - G.field0;   // the field inside its group
+    const __bf16* H = static_cast<const __bf16*>(G.H);
+    const __bf16* W2 = static_cast<const __bf16*>(G.W2);
+    uint4 hf[KS];
+    mq_load_row<SP>(hf, H + m * G.ldh, S, lg);
+    const int n_tiles = te - tb, t0 = j * tpf + tb;   // this chunk's tiles among the group's
+    uint4 wr[NCH];
+    dm_load_tile<SP, NT>(wr, W2, G.ldw, S, Cp, tpf, t0, tid);
+    dm_store_tile<SP, NT>(wr, smem, tid);
+    __syncthreads();
+
+    for (int t = 0; t < n_tiles; ++t) {
+        const char* buf = smem + (t & 1) * TILE;
+        const int cb = (tb + t) * DM_TC;
+
+        // a: the columns' weights and readings (decode_member_verify_kernel's); decode into the value image
+        if (tid < DM_TC) {
+            const int c = cb + tid;
+            float w = 0.f;
+            if (c < lim) {
+                const float pf = P.prec_field != nullptr ? P.prec_field[fg] : 1.f;
+                const float pm = P.prec != nullptr ? P.prec[(int64_t)bp * P.ld_prow + (int64_t)fg * P.ld_pfield + c] : 1.f;
+                w = mul1(pf > 0.f ? pf : 0.f, pm > 0.f ? pm : 0.f);
+            }
+            const bool on = w > 0.f;   // false for NaN
+            pv_s[tid] = on ? w : 0.f;
+            y_s[tid] = on ? P.obs[(int64_t)bp * P.ld_row + (int64_t)fg * P.ld_field + c] : 0.f;
+        }
+        if (active) mq_decode_tile<SP>(hf, buf, G.bias + j * Cp + cb, S, li, lg, Vs + j0);
+        __syncthreads();
+        if (t + 1 < n_tiles) dm_load_tile<SP, NT>(wr, W2, G.ldw, S, Cp, tpf, t0 + t + 1, tid);   // in flight behind b
+
+        // b: a column per wave at a time
+        for (int cl = wave; cl < DM_TC; cl += NW) {
+            const float pv = pv_s[cl];
+            if (!(pv > 0.f)) {   // the same word in every lane
+                if (lane == 0) cell_s[cl].state = 1;
+                continue;
+            }
+            bs_column_wave<V>(Vs + cl * VP, w_s, live_s, N, lane, W, y_s[cl], pv, thr_s, T, &cell_s[cl]);
+        }
+        __syncthreads();
+
+        // c: thread (k, q) finishes threshold q of column k
+        if (tid < DM_TC * T) {
+            const int k = tid & (DM_TC - 1), q = tid / DM_TC;
+            double tm[BS_SUMS];
+            const BsOut o = bs_finish_cell(cell_s[k], q, y_s[k], thr_s[q], tm);
+            if (o.m >= 0) {   // LDS, integers: the order does not matter; 0 <= m <= N
+                atomicAdd(&hist_s[q * (N + 1) + o.m], 1);
+                if (o.o) atomicAdd(&hist_s[nb + q * (N + 1) + o.m], 1);
+            }
+            const int c = cb + k;
+            if (c < ld) {
+                const int64_t at = q * P.ld_map + obase + c;
+                if (P.prob != nullptr) P.prob[at] = o.prob;
+                if (P.brier != nullptr) P.brier[at] = o.brier;
+            }
+#pragma unroll
+            for (int i = 0; i < BS_SUMS; ++i) term_s[q * BS_SUMS + i][k] = tm[i];
+        }
+        if (t + 1 < n_tiles) dm_store_tile<SP, NT>(wr, smem + ((t + 1) & 1) * TILE, tid);
+        __syncthreads();
+
+        // d: the field's sums, columns ascending (the next tile's terms are filed two barriers ahead)
+        if (tid < T * BS_SUMS)
+            for (int k = 0; k < DM_TC; ++k) acc_sum += term_s[tid][k];
+    }
+    if (tid < T * BS_SUMS) wsum[tid] = acc_sum;
+    for (int r = tid; r < 2 * nb; r += NT) whist[r] = hist_s[r];   // every integer add lies behind the last tile's barrier
+}
+
+__global__ __launch_bounds__(256) void member_brier_finish_kernel(const SeaDecodeMemberBrier p, const int chunks, const int words) {
+    const int b = blockIdx.x, N = p.members, F = p.n_fields_total, T = p.n_thr, Pn = p.P * chunks;   // (patch, chunk) partials per field
+    const int f = blockIdx.y / T, t = blockIdx.y - f * T;                                             // a workgroup per (history, field, threshold)
+    const double* part = reinterpret_cast<const double*>(p.work) + ((int64_t)b * Pn * F + f) * words;
+    const int64_t o = ((int64_t)b * F + f) * T + t;
+    bs_finish_threshold(part, Pn, (int64_t)F * words, T, N, t, p.sums + o * BS_SUMS, p.hist + o * (N + 1), p.hits + o * (N + 1), p.accumulate, threadIdx.x, 256);
+}
+
+template <int SP, int V>
+static void member_brier_launch(const MemberBrierLaunch& L, dim3 grid, hipStream_t s) {
+    constexpr int lds = mv_lds_bytes<SP>();
+    static bool set_on[64] = {false};   // per device: the dynamic part is 100 kB at SP = 640, above the 64 kB a kernel gets without the attribute
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = -1;
+    if (dev < 0 || !set_on[dev]) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(decode_member_brier_kernel<SP, V>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        if (dev >= 0) set_on[dev] = true;
+    }
+    decode_member_brier_kernel<SP, V><<<grid, dim3(MV_NT), lds, s>>>(L);
+    sea_note_form("decode.member_brier", SP, lds);
+}
+
+template <int V>
+static void member_brier_dispatch(const MemberBrierLaunch& L, dim3 grid, hipStream_t s) {
+    if (L.p.S <= 128) member_brier_launch<128, V>(L, grid, s);
+    else if (L.p.S <= 256) member_brier_launch<256, V>(L, grid, s);
+    else if (L.p.S <= 384) member_brier_launch<384, V>(L, grid, s);
+    else if (L.p.S <= 512) member_brier_launch<512, V>(L, grid, s);
+    else member_brier_launch<640, V>(L, grid, s);
+}
+
+extern "C" int64_t sea_decode_member_brier_ws_bytes(int B, int P, int n_fields_total, int members, int Cp, int n_thr) {
+    if (B < 1 || B > 65535 || P < 1 || n_fields_total < 1 || members < 1 || members > VF_MAX_N || Cp < 32 || Cp % 32 || n_thr < 1 || n_thr > BS_MAX_T) return -1;
+    return (int64_t)B * P * mv_chunks(Cp) * n_fields_total * bs_words(n_thr, members) * 8;
+}
+
+extern "C" int sea_decode_member_brier(const SeaDecodeMseGroup* groups, int n_groups, const SeaDecodeMemberBrier* p, int dtype, void* stream) {
+    SEA_REQUIRE(groups != nullptr && p != nullptr, "sea_decode_member_brier: null argument table");
+    SEA_REQUIRE(n_groups >= 1 && n_groups <= SEA_DECODE_MSE_MAX_GROUPS, "sea_decode_member_brier: n_groups=%d outside 1..%d", n_groups, SEA_DECODE_MSE_MAX_GROUPS);
+    SEA_REQUIRE(dtype == SEA_F32 || dtype == SEA_BF16, "sea_decode_member_brier: bad dtype %d", dtype);
+    if (dtype != SEA_BF16) {
+        sea_set_error("sea_decode_member_brier: unsupported: bf16 only (the fp32 decoder composes the decode and the formulas)");
+        return SEA_EUNSUPPORTED;
+    }
+    const SeaDecodeMemberBrier& P = *p;
+    SEA_REQUIRE(P.obs != nullptr && P.thr != nullptr && P.sums != nullptr && P.hist != nullptr && P.hits != nullptr && P.status != nullptr && P.work != nullptr,
+                "sea_decode_member_brier: null pointer (obs, thr, sums, hist, hits, status and work are required; prec_field, prec, counts, logw and the maps may be NULL)");
+    SEA_REQUIRE(P.n_thr >= 1 && P.n_thr <= BS_MAX_T, "sea_decode_member_brier: n_thr=%d outside 1..%d", P.n_thr, BS_MAX_T);
+    SEA_REQUIRE(P.M >= 1, "sea_decode_member_brier: M=%d must be positive", P.M);
+    SEA_REQUIRE(P.S >= 8 && P.S % 8 == 0, "sea_decode_member_brier: S=%d must be a positive multiple of 8", P.S);
+    SEA_REQUIRE(P.Cp >= 32 && P.Cp % 32 == 0, "sea_decode_member_brier: Cp=%d must be a positive multiple of 32", P.Cp);
+    SEA_REQUIRE(P.C >= 1 && P.C <= P.Cp, "sea_decode_member_brier: C=%d must lie in 1..Cp=%d", P.C, P.Cp);
+    SEA_REQUIRE(P.P >= 1, "sea_decode_member_brier: P=%d must be positive", P.P);
+    SEA_REQUIRE(P.members >= 1, "sea_decode_member_brier: members=%d must be positive", P.members);
+    SEA_REQUIRE((int64_t)P.M % ((int64_t)P.P * P.members) == 0, "sea_decode_member_brier: M=%d is not a multiple of P * members = %d * %d", P.M, P.P, P.members);
+    SEA_REQUIRE(P.n_fields_total >= 1 && P.n_fields_total <= 65535 / BS_MAX_T, "sea_decode_member_brier: n_fields_total=%d outside 1..%d (a grid dimension)", P.n_fields_total,
+                65535 / BS_MAX_T);
+    SEA_REQUIRE(P.ld_field >= P.C && P.ld_row >= 0, "sea_decode_member_brier: obs strides ld_row=%lld, ld_field=%lld must cover C=%d", (long long)P.ld_row,
+                (long long)P.ld_field, P.C);
+    SEA_REQUIRE(P.prec == nullptr || (P.ld_pfield >= P.C && P.ld_prow >= 0), "sea_decode_member_brier: prec strides ld_prow=%lld, ld_pfield=%lld must cover C=%d",
+                (long long)P.ld_prow, (long long)P.ld_pfield, P.C);
+    const int64_t BP = (int64_t)P.M / P.members;   // (history, patch) pairs
+    const int64_t B = BP / P.P;
+    SEA_REQUIRE(BP <= 0x7fffffffLL && B <= 65535, "sea_decode_member_brier: %lld histories; a launch carries up to 65535", (long long)B);
+    SEA_REQUIRE((P.prob == nullptr && P.brier == nullptr) || (P.ld_out >= P.C && P.ld_out <= 0x7fffffffLL && P.ld_map >= BP * P.n_fields_total * P.ld_out),
+                "sea_decode_member_brier: ld_out=%lld must cover C=%d, and ld_map=%lld a whole map", (long long)P.ld_out, P.C, (long long)P.ld_map);
+    SEA_REQUIRE(P.accumulate == 0 || P.accumulate == 1, "sea_decode_member_brier: accumulate=%d must be 0 or 1", P.accumulate);
+    SEA_REQUIRE(sea_aligned4(P.obs) && sea_aligned4(P.prec_field) && sea_aligned4(P.prec) && sea_aligned4(P.counts) && sea_aligned4(P.logw) && sea_aligned4(P.thr) &&
+                    sea_aligned4(P.prob) && sea_aligned4(P.brier) && sea_aligned4(P.status) && (reinterpret_cast<uintptr_t>(P.sums) & 7u) == 0 &&
+                    (reinterpret_cast<uintptr_t>(P.hist) & 7u) == 0 && (reinterpret_cast<uintptr_t>(P.hits) & 7u) == 0 && (reinterpret_cast<uintptr_t>(P.work) & 7u) == 0,
+                "sea_decode_member_brier: misaligned pointer (f32 and int32 buffers need 4 bytes; sums, hist, hits and work 8)");
+    int64_t covered = 0;
+    for (int g = 0; g < n_groups; ++g) {
+        const SeaDecodeMseGroup& G = groups[g];
+        SEA_REQUIRE(G.H != nullptr && G.W2 != nullptr && G.bias != nullptr, "sea_decode_member_brier: group %d: null pointer", g);
+        SEA_REQUIRE(sea_aligned16(G.H) && sea_aligned16(G.W2) && sea_aligned16(G.bias), "sea_decode_member_brier: group %d: pointers must be 16-byte aligned", g);
+        SEA_REQUIRE(G.ldh >= P.S && G.ldh % 8 == 0 && G.ldw >= P.S && G.ldw % 8 == 0,
+                    "sea_decode_member_brier: group %d: row strides ldh=%d ldw=%d must cover S=%d and be multiples of 8", g, G.ldh, G.ldw, P.S);
+        SEA_REQUIRE(G.n_fields >= 1 && G.field0 >= 0 && (int64_t)G.field0 + G.n_fields <= P.n_fields_total,
+                    "sea_decode_member_brier: group %d: n_fields=%d, field0=%d outside the %d fields", g, G.n_fields, G.field0, P.n_fields_total);
+        SEA_REQUIRE((int64_t)G.n_fields * P.Cp <= 0x7fffffffLL / 2, "sea_decode_member_brier: group %d: too many output columns", g);
+        for (int h = 0; h < g; ++h)
+            SEA_REQUIRE(G.field0 >= groups[h].field0 + groups[h].n_fields || groups[h].field0 >= G.field0 + G.n_fields,
+                        "sea_decode_member_brier: group %d: its fields overlap those of group %d (a cell is scored once)", g, h);
+        covered += G.n_fields;
+    }
+    SEA_REQUIRE(covered == P.n_fields_total, "sea_decode_member_brier: the groups cover %lld of the %d fields (every field needs exactly one group)", (long long)covered,
+                P.n_fields_total);
+    if (P.S > 640) {
+        sea_set_error("sea_decode_member_brier: unsupported: hidden width S=%d above 640", P.S);
+        return SEA_EUNSUPPORTED;
+    }
+    if (P.members > VF_MAX_N) {
+        sea_set_error("sea_decode_member_brier: unsupported: members=%d above %d", P.members, VF_MAX_N);
+        return SEA_EUNSUPPORTED;
+    }
+    SEA_REQUIRE((int64_t)P.n_fields_total * bs_words(P.n_thr, P.members) <= 0x7fffffffLL, "sea_decode_member_brier: too many fields");
+    const int64_t need = sea_decode_member_brier_ws_bytes((int)B, P.P, P.n_fields_total, P.members, P.Cp, P.n_thr);
+    SEA_REQUIRE(P.work_bytes >= need,
+                "sea_decode_member_brier: work_bytes=%lld below the %lld that sea_decode_member_brier_ws_bytes(B=%d, P=%d, n_fields_total=%d, members=%d, Cp=%d, n_thr=%d) asks for",
+                (long long)P.work_bytes, (long long)need, (int)B, P.P, P.n_fields_total, P.members, P.Cp, P.n_thr);
+    SEA_REQUIRE((int64_t)P.P * mv_chunks(P.Cp) <= 0x7fffffffLL && mv_chunks(P.Cp) <= 65535, "sea_decode_member_brier: Cp=%d has too many column chunks", P.Cp);
+
+    MemberBrierLaunch L;
+    memset(&L, 0, sizeof(L));
+    for (int g = 0; g < n_groups; ++g) L.g[g] = groups[g];
+    L.p = P;
+    L.n_groups = n_groups;
+    L.words = (int)bs_words(P.n_thr, P.members);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)BP, (unsigned)P.n_fields_total, (unsigned)mv_chunks(P.Cp));
+    if (P.members <= 64) member_brier_dispatch<1>(L, grid, s);
+    else member_brier_dispatch<2>(L, grid, s);
+    member_brier_finish_kernel<<<dim3((unsigned)B, (unsigned)(P.n_fields_total * P.n_thr)), dim3(256), 0, s>>>(P, mv_chunks(P.Cp), L.words);
+    SEA_CHECK_LAUNCH("sea_decode_member_brier");
     return SEA_OK;
 }
 

@@ -23,6 +23,34 @@ __device__ __forceinline__ float qs_wave_max(float v) {
     return v;
 }
 
+// A lane's members of one column: values, weights (0 for a dead member) and live flags; returns (in every lane) whether a live member's value is not
+// finite.  Shared with bs_column_wave (brier_score.hpp).
+template <int V>
+__device__ __forceinline__ int qs_load_column(const float* row, const double* w_s, const int* live_s, const int N, const int lane, float (&x)[V], double (&w)[V],
+                                              bool (&lv)[V]) {
+    int bad = 0;
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+        const int i = lane + 64 * v;
+        const bool in = i < N;
+        x[v] = in ? row[i] : 0.f;
+        w[v] = in ? w_s[i] : 0.0;
+        lv[v] = in && live_s[i] != 0;
+        bad |= (lv[v] && !isfinite(x[v])) ? 1 : 0;
+    }
+    return __any(bad);
+}
+
+// The weight of the live members above a threshold (strict, f32 compares), in fp64 through the fixed xor butterfly: the same bits in every lane.
+template <int V>
+__device__ __forceinline__ double qs_exceed_sum(const float (&x)[V], const double (&w)[V], const bool (&lv)[V], const float th) {
+#pragma clang fp reassociate(off)
+    double e = 0.0;
+#pragma unroll
+    for (int v = 0; v < V; ++v) e += (lv[v] && x[v] > th) ? w[v] : 0.0;
+    return vf_wave_sum(e);
+}
+
 // row: the column's member values [N] in LDS; w_s, live_s: the history's weights (0 for a dead member) and live flags [N] in LDS; W: the sum of the
 // live weights (> 0: the caller passes a history without a live member over); level: the launch's levels; thr_s: the field's thresholds in LDS.
 // Lane 0 files n_levels quantiles, then n_thr probabilities, in res.  A dead member's weight is 0: its value, NaN included, reaches nothing.
@@ -33,18 +61,9 @@ __device__ __forceinline__ void qs_column_wave(const float* row, const double* w
     float x[V];
     double w[V], below[V];
     bool lv[V];
-    int bad = 0;
 #pragma unroll
-    for (int v = 0; v < V; ++v) {
-        const int i = lane + 64 * v;
-        const bool in = i < N;
-        x[v] = in ? row[i] : 0.f;
-        w[v] = in ? w_s[i] : 0.0;
-        lv[v] = in && live_s[i] != 0;
-        below[v] = 0.0;
-        bad |= (lv[v] && !isfinite(x[v])) ? 1 : 0;
-    }
-    bad = __any(bad);   // a live member's value is not finite: NaN in every map of this cell
+    for (int v = 0; v < V; ++v) below[v] = 0.0;
+    const int bad = qs_load_column<V>(row, w_s, live_s, N, lane, x, w, lv);   // a live member's value is not finite: NaN in every map of this cell
     if (n_levels > 0) {
         // the walk of vf_score_wave, j ascending; eight members' reads are issued together, the order test has no short-circuit
         int j = 0;
@@ -89,10 +108,7 @@ __device__ __forceinline__ void qs_column_wave(const float* row, const double* w
     }
     for (int t = 0; t < n_thr; ++t) {
         const float th = thr_s[t];
-        double e = 0.0;
-#pragma unroll
-        for (int v = 0; v < V; ++v) e += (lv[v] && x[v] > th) ? w[v] : 0.0;
-        e = vf_wave_sum(e);
+        const double e = qs_exceed_sum<V>(x, w, lv, th);
         if (lane == 0) res[n_levels + t] = (bad || th != th) ? NAN : (float)(e / W);
     }
 }

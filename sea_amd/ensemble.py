@@ -66,6 +66,13 @@ What is published as the forecast besides mean and variance (EnsembleQuantiles: 
     products = EnsembleQuantiles(decoder, n_patches, members=n, levels=(0.05, 0.5, 0.95), thresholds=unpatcher.scale_thresholds([[0.5, 2.0]]), counts=counts)
     quant, exceed = products(y, logw)                                           # [3, B, P, n_fields, n_inp] quantile maps, [1, B, P, n_fields, n_inp] P(field > threshold)
 
+Whether those exceedance probabilities are any good (FieldThresholdVerification: sea_decode_member_brier, two launches, the members' fields never
+written; SensorThresholdVerification: sea_ensemble_brier on predictions that exist already):
+
+    check = FieldThresholdVerification(decoder, n_patches, members=n, thresholds=unpatcher.scale_thresholds([[0.5, 2.0]]), counts=counts)
+    scores = check(y, snapshot, precision, into=scores)                         # Brier sums, reliability histograms and ROC hit counts add up over the cycles
+    scores.brier, scores.brier_skill, scores.reliability, scores.roc_area       # [B, n_fields, T] tensors on the device; scores.reliability_curve(), scores.roc()
+
 The same CRPS TRAINS the temporal model as an ensemble generator (EnsembleCRPSLoss: Decode.member_crps_loss, sea_decode_member_crps_grad — the
 CRPS sums of FieldVerification with their gradient to the latent states, the members' fields and their gradient never written):
 
@@ -1483,6 +1490,369 @@ class EnsembleQuantiles:
         return quant, exceed
 
     quantiles = __call__
+
+
+# ------------------------------------------------------------------------------------------------ verification of exceedance forecasts
+BRIER_MAPS = ("prob", "brier")
+BRIER_FUSED_MIN_ROWS = 4096   # fused=None: the fused launches from this many decoder rows (B * members * n_patches) on — the smallest measured size
+
+
+def _check_thresholds(what: str, thresholds, n_fields: int) -> torch.Tensor:
+    """thresholds — numbers or a tensor, [T] (the same for every field) or [T, n_fields], 1 <= T <= 8, finite — as a contiguous float32 [T, n_fields]
+    tensor on the host (a tensor given on the device comes to the host once, here)."""
+    try:
+        t = thresholds.detach().cpu() if torch.is_tensor(thresholds) else torch.as_tensor(thresholds, dtype=torch.float32)
+    except (TypeError, ValueError, RuntimeError):
+        raise ValueError(f"{what}: thresholds must be [T] or [T, {n_fields}] numbers, got {thresholds!r}") from None
+    if t.dim() not in (1, 2) or not 1 <= t.shape[0] <= N.BRIER_MAX_T or (t.dim() == 2 and t.shape[1] != n_fields) or not t.is_floating_point():
+        raise ValueError(f"{what}: thresholds must be [T] or [T, {n_fields}] floating-point numbers with 1 <= T <= {N.BRIER_MAX_T}, got shape {tuple(t.shape)} {t.dtype}")
+    t = (t.view(-1, 1).expand(t.shape[0], n_fields) if t.dim() == 1 else t).to(torch.float32).contiguous()
+    if not bool(torch.isfinite(t).all()):
+        raise ValueError(f"{what}: every threshold must be finite, got {t.tolist()}")
+    return t
+
+
+@dataclasses.dataclass(frozen=True)
+class ThresholdScores:
+    """What FieldThresholdVerification and SensorThresholdVerification return, all on the states' device.  Per reading and threshold, float32
+    [T, B, P, n_fields, n_inp] (sensors: [T, B, K]) or None when not asked for: prob, the forecast probability of exceedance p, and brier_map, (p - o)^2
+    with o = [reading > threshold]; 0 at a reading without weight, NaN at a bad one.  Per (history, field, threshold) — [B, F, T, ..]; sensors: per
+    (history, threshold), [B, T, ..]: sums float64 [.., 5] (count of live good readings, sum (p - o)^2, sum p, sum o, count of bad readings), hist int64
+    [.., members + 1] (the readings by the number m of members above the threshold) and hits (those of them where the reading was above it).  status
+    int32 [B]: the live members L, or -1 (the history's log-weights are invalid: not scored).  thresholds: the float32 table the scores were made
+    with.  weighted: whether a call that went into sums was given log-weights.  sums, hist and hits add up over calls (into=).
+    The derived properties are float64 tensor expressions of shape [B, F, T] ([B, T] for sensors): nothing is read back; a field without a live good
+    reading gives NaN.  (The per-reading map is the field brier_map, so that `brier` is the score, as in every verification suite.)"""
+    prob: Optional[torch.Tensor]
+    brier_map: Optional[torch.Tensor]
+    sums: torch.Tensor
+    hist: torch.Tensor
+    hits: torch.Tensor
+    status: torch.Tensor
+    thresholds: torch.Tensor
+    weighted: bool = False
+
+    @property
+    def count(self):
+        return self.sums[..., 0]
+
+    @property
+    def brier(self):
+        """The Brier score: the mean of (p - o)^2 over the live, good readings.  Defined for weighted and unweighted ensembles."""
+        return self.sums[..., 1] / self.sums[..., 0]
+
+    @property
+    def base_rate(self):
+        """The observed frequency of exceedance, the mean of o."""
+        return self.sums[..., 3] / self.sums[..., 0]
+
+    @property
+    def mean_probability(self):
+        """The mean forecast probability: above base_rate the forecasts over-predict the event."""
+        return self.sums[..., 2] / self.sums[..., 0]
+
+    @property
+    def uncertainty(self):
+        """base_rate (1 - base_rate): the Brier score of the constant forecast p = base_rate."""
+        return self.base_rate * (1.0 - self.base_rate)
+
+    @property
+    def brier_skill(self):
+        """1 - brier / uncertainty: 1 a perfect forecast, 0 no better than the base rate."""
+        return 1.0 - self.brier / self.uncertainty
+
+    def _bins(self, what: str):
+        """(probability m / L, cells n_m, hits o_m) per bin as float64 [.., members + 1] — for equal weights only."""
+        if self.weighted:
+            raise ValueError(f"ThresholdScores.{what} is defined for equal weights only: the bins are by the NUMBER of members above the threshold, and with "
+                             "unequal weights the readings of one bin carry different forecast probabilities, so a bin has no single probability to be "
+                             "reliable against (brier, brier_skill and roc() are defined in every case)")
+        f64 = torch.float64
+        n = self.hist.shape[-1] - 1
+        L = self.status.to(f64).view((-1,) + (1,) * (self.hist.dim() - 1))
+        prob = torch.arange(n + 1, device=self.hist.device, dtype=f64) / L            # m / L; bins above L are empty
+        return prob.expand(self.hist.shape), self.hist.to(f64), self.hits.to(f64)
+
+    @property
+    def reliability(self):
+        """sum_m n_m (m / L - o_m / n_m)^2 / count over the bins m = the number of members above the threshold: 0 for a reliable forecast.  With equal
+        weights brier = reliability - resolution + uncertainty exactly (Murphy 1973), since every reading of bin m was forecast p = m / L.  Raises
+        ValueError on a result made with log-weights: the bins are by member count, and with unequal weights a bin has no single probability."""
+        prob, n_m, o_m = self._bins("reliability")
+        zero = torch.zeros((), device=n_m.device, dtype=torch.float64)
+        freq = o_m / torch.where(n_m > 0, n_m, torch.ones_like(n_m))
+        return torch.where(n_m > 0, n_m * (prob - freq) ** 2, zero).sum(-1) / self.count
+
+    @property
+    def resolution(self):
+        """sum_m n_m (o_m / n_m - base_rate)^2 / count: how far the bins' observed frequencies lie from the base rate (larger is better).  Equal weights
+        only, as reliability."""
+        _, n_m, o_m = self._bins("resolution")
+        zero = torch.zeros((), device=n_m.device, dtype=torch.float64)
+        freq = o_m / torch.where(n_m > 0, n_m, torch.ones_like(n_m))
+        return torch.where(n_m > 0, n_m * (freq - self.base_rate.unsqueeze(-1)) ** 2, zero).sum(-1) / self.count
+
+    def reliability_curve(self):
+        """The reliability diagram: (probability m / L, observed frequency o_m / n_m — NaN for an empty bin —, cells n_m), float64 [.., members + 1].
+        Equal weights only, as reliability."""
+        prob, n_m, o_m = self._bins("reliability_curve()")
+        return prob, o_m / n_m, n_m
+
+    def roc(self):
+        """The relative operating characteristic over the decision rules "warn when at least k members exceed", k = 0 .. members + 1: (hit_rate,
+        false_alarm_rate), float64 [.., members + 2], from (1, 1) at k = 0 down to (0, 0).  Defined for weighted ensembles too (the rules count members)."""
+        f64 = torch.float64
+        ev, ne = self.hits.to(f64), (self.hist - self.hits).to(f64)
+        tail = lambda t: torch.cat([t.flip(-1).cumsum(-1).flip(-1), torch.zeros_like(t[..., :1])], dim=-1)   # noqa: E731   sum over m >= k
+        return tail(ev) / ev.sum(-1, keepdim=True), tail(ne) / ne.sum(-1, keepdim=True)
+
+    @property
+    def roc_area(self):
+        """The area under roc() by the trapezoid rule: 1 a perfect discrimination, 0.5 none."""
+        hr, far = self.roc()
+        return ((far[..., :-1] - far[..., 1:]) * (hr[..., :-1] + hr[..., 1:])).sum(-1) * 0.5
+
+
+def _composed_brier(pred, obs, prec, logw, members: int, thr, out_dtype=torch.float32):
+    """sea_ensemble_brier's formulas (include/sea_hip.h) as fp64 torch ops on pred's device, for any member count and on CPU tensors: pred [B * members,
+    K] (any float dtype, compared as given), obs [B, K], prec None, [K] or [B, K], logw None or [B * members], thr [T, K] (or [T, B, K]: a table per
+    history).  Returns a dict with ops.ensemble_brier's keys: prob, brier [T, B, K] (out_dtype), sums f64 [B, T, 5], hist, hits int64 [B, T, members +
+    1], status int32 [B].  Nothing is read back."""
+    f64 = torch.float64
+    n = members
+    B, K = obs.shape
+    dev = pred.device
+    zero = torch.zeros((), device=dev, dtype=f64)
+    x = pred.view(B, n, K)
+    y = obs
+    lw = torch.zeros(B, n, device=dev, dtype=f64) if logw is None else logw.to(f64).view(B, n)
+    invalid = (torch.isnan(lw) | (lw == float("inf"))).any(1) | ~torch.isfinite(lw).any(1)            # [B]
+    lw = torch.where(invalid.unsqueeze(1), zero, lw)
+    alive = lw != float("-inf")                                                                      # [B, N]
+    e = torch.where(alive, (lw - lw.max(dim=1, keepdim=True).values).exp(), zero)
+    W = e.sum(dim=1)
+    p_ = torch.ones(B, K, device=dev, dtype=f64) if prec is None else prec.to(f64).expand(B, K)
+    live = (p_ > 0) & ~invalid.unsqueeze(1)                                                          # [B, K]
+    finite = torch.isfinite(y) & torch.isfinite(p_) & (torch.isfinite(x) | ~alive.unsqueeze(2)).all(1)
+    bad, good = (live & ~finite).unsqueeze(0), (live & finite).unsqueeze(0)                          # [1, B, K]
+    t = thr.detach().to(dev)
+    T = t.shape[0]
+    t = t.view(T, 1, K) if t.dim() == 2 else t                                                        # [T, 1 | B, K]
+    over = alive.view(1, B, n, 1) & (x.unsqueeze(0) > t.to(x.dtype).unsqueeze(2))                      # [T, B, N, K]: strict, as the values they are
+    m = over.sum(2)
+    p = torch.where(over, e.view(1, B, n, 1), zero).sum(2) / W.view(1, B, 1)
+    o = y.unsqueeze(0) > t.to(y.dtype)                                                                # [T, B, K]
+    d = p - o.to(f64)
+    br = d * d
+    hit = good & o
+    sums = torch.stack([good.expand(T, B, K).to(f64).sum(2), torch.where(good, br, zero).sum(2), torch.where(good, p, zero).sum(2), hit.to(f64).sum(2),
+                        bad.expand(T, B, K).to(f64).sum(2)], dim=2).permute(1, 0, 2).contiguous()  # [B, T, 5]
+    idx = torch.where(good, m, torch.zeros_like(m))
+    hist = torch.zeros(T, B, n + 1, device=dev, dtype=torch.int64).scatter_add_(2, idx, good.expand(T, B, K).to(torch.int64)).permute(1, 0, 2).contiguous()
+    hits = torch.zeros(T, B, n + 1, device=dev, dtype=torch.int64).scatter_add_(2, idx, hit.to(torch.int64)).permute(1, 0, 2).contiguous()
+    nan = torch.full((), float("nan"), device=dev, dtype=f64)
+    out = lambda v: torch.where(bad, nan, torch.where(good, v, zero)).to(out_dtype)   # noqa: E731
+    status = torch.where(invalid, torch.full_like(invalid, -1, dtype=torch.int64), alive.sum(1)).to(torch.int32)
+    return dict(prob=out(p), brier=out(br), sums=sums, hist=hist, hits=hits, status=status)
+
+
+def _composed_field_brier(Y, obs, w, logw, members: int, thr, maps=BRIER_MAPS, out_dtype=torch.float32):
+    """sea_decode_member_brier's outputs from decoded members, with every cell a sensor of _composed_brier and every (history, field) a history of it,
+    mirroring _composed_field_verify: Y [B * members, P, F, C] (any float dtype, compared as given), obs [B, P, F, >= C], w [B, P, F, C] the cells'
+    weights (0: dead), logw None or [B * members], thr [T, F].  Returns a dict: the maps asked for [T, B, P, F, C], sums [B, F, T, 5], hist and hits
+    [B, F, T, members + 1], status [B].  Nothing is read back."""
+    n = members
+    Bm, P, F, C_ = Y.shape
+    B = Bm // n
+    T = thr.shape[0]
+    pred = Y.reshape(B, n, P, F, C_).permute(0, 3, 1, 2, 4).reshape(B * F * n, P * C_)
+    cells = lambda t: t[..., :C_].permute(0, 2, 1, 3).reshape(B * F, P * C_)   # noqa: E731
+    lw = None if logw is None else logw.reshape(B, 1, n).expand(B, F, n).reshape(-1)
+    tk = thr.to(Y.device).view(T, 1, F, 1).expand(T, B, F, P * C_).reshape(T, B * F, P * C_)
+    r = _composed_brier(pred, cells(obs), cells(w), lw, n, tk, out_dtype=out_dtype)
+    res = {k: r[k].view(T, B, F, P, C_).permute(0, 1, 3, 2, 4).contiguous() for k in BRIER_MAPS if k in maps}
+    res.update(sums=r["sums"].view(B, F, T, N.BRIER_SUMS), hist=r["hist"].view(B, F, T, n + 1), hits=r["hits"].view(B, F, T, n + 1),
+               status=r["status"].view(B, F)[:, 0].contiguous())
+    return res
+
+
+def _check_brier_call(what: str, maps, logw, into, shape, Bm: int, n: int, device):
+    """maps, logw and into of a threshold-verification call, checked; returns (maps, logw as a contiguous float32 [Bm] or None)."""
+    maps = tuple(maps)
+    if any(k not in BRIER_MAPS for k in maps) or len(set(maps)) != len(maps):
+        raise ValueError(f"{what}: maps must be distinct names among {BRIER_MAPS}, got {maps!r}")
+    if logw is not None:
+        if not torch.is_tensor(logw) or not logw.is_floating_point() or logw.numel() != Bm or logw.dim() not in (1, 2) \
+                or (logw.dim() == 2 and logw.shape[1] != n) or logw.device != device:
+            raise ValueError(f"{what}: logw must be None or a floating-point [{Bm}] (or [{Bm // n}, {n}]) tensor of log-weights on {device}, got "
+                             f"{(tuple(logw.shape), str(logw.device)) if torch.is_tensor(logw) else type(logw).__name__}")
+        logw = logw.detach().reshape(-1).to(torch.float32).contiguous()
+    if into is not None:
+        if not isinstance(into, ThresholdScores) or tuple(into.sums.shape) != shape + (N.BRIER_SUMS,) or tuple(into.hist.shape) != shape + (n + 1,) \
+                or tuple(into.hits.shape) != shape + (n + 1,) or into.sums.device != device or into.sums.dtype != torch.float64 \
+                or into.hist.dtype != torch.int64 or into.hits.dtype != torch.int64 or not into.sums.is_contiguous() or not into.hist.is_contiguous() \
+                or not into.hits.is_contiguous():
+            raise ValueError(f"{what}: into must be an earlier ThresholdScores with sums {list(shape + (N.BRIER_SUMS,))} for {n} members on {device}")
+    return maps, logw
+
+
+class FieldThresholdVerification(_FieldObserver):
+    """Verification of EXCEEDANCE forecasts against a dense snapshot of the decoded fields — are EnsembleQuantiles' probability maps any good:
+    verify(y, obs, precision=None, logw=None, into=None, maps=()) -> ThresholdScores.  Per (history, field, threshold) the Brier score with its
+    reliability / resolution / uncertainty decomposition, the reliability diagram (is 0.8 observed 80 % of the time?) and the ROC curve, from fp64 sums
+    and integer histograms that add up over calls (into=: an earlier result whose sums, hist and hits this call's are added onto, in place); per cell,
+    when asked for (maps: a subset of ("prob", "brier")), the forecast probability and (p - o)^2 (MeshUnpatcher.unpatch_map takes them to the mesh).
+    include/sea_hip.h (sea_decode_member_brier) states the definitions; exceedance is strict, of the forecast and of the observation.
+
+    thresholds: [T] (the same for every field) or [T, n_fields], T <= 8, finite, in the decoder's SCALED units as in EnsembleQuantiles
+    (MeshUnpatcher.scale_thresholds maps physical thresholds there); checked here.  y, obs, layout, counts, precision and logw are checked exactly as
+    FieldVerification checks them; the precision only decides which cells are read (a cell with precision 0, or beyond counts, is neutral whatever obs
+    holds there): no score is weighted by it.
+    fused: True — the decoder's first layer plus the two launches of sea_decode_member_brier (bf16, up to 128 members): the thresholds-only decode of
+    sea_decode_member_quantiles plus one comparison with the observation; the members' decoded fields are never written.  False — Decode.forward plus
+    the formulas as fp64 torch ops (the composed path: fp32, more than 128 members, comparison; it holds the members' fields and a boolean and an fp64
+    temporary per threshold).  fused=None takes the fused launches in bf16 up to 128 members from 4096 decoder rows (B * members * n_patches) on and the
+    composed path everywhere else — the measured rule (tools/brier_bench.py, profiles/brier_bench.txt, DESIGN.md section 7o: every measured row, 4096 -
+    32768 rows, has the fused launches ahead); nothing was measured below 4096 rows, so the composed path stays the default there.
+    A call reads nothing back from the device and uploads nothing after the first call on a device.  `decoder` is a sea_amd Decode; no autograd graph
+    is built."""
+    _what = "FieldThresholdVerification"
+
+    def __init__(self, decoder, n_patches: int, members: int, thresholds, counts=None, layout: str = "BPFC", fused: Optional[bool] = None):
+        what = self._what
+        if layout not in ("BPFC", "BPCF"):
+            raise ValueError(f"{what}: layout must be 'BPFC' or 'BPCF', got {layout!r}")
+        if not isinstance(n_patches, int) or isinstance(n_patches, bool) or n_patches < 1:
+            raise ValueError(f"{what}: n_patches = {n_patches!r} must be a positive integer")
+        if not isinstance(members, int) or isinstance(members, bool) or members < 1:
+            raise ValueError(f"{what}: members = {members!r} must be a positive integer")
+        if fused is not None and not isinstance(fused, bool):
+            raise ValueError(f"{what}: fused = {fused!r} must be None, True or False")
+        if fused and members > N.BRIER_MAX_N:
+            raise ValueError(f"{what}: the fused launches carry up to {N.BRIER_MAX_N} members, got {members} (fused=False, or None)")
+        n_fields = sum(len(g) for g in decoder.field_groups)
+        self.thresholds = _check_thresholds(what, thresholds, n_fields)
+        self._thr = {}
+        self.decoder, self.n_patches, self.members, self.counts, self.layout, self.fused = decoder, n_patches, members, counts, layout, fused
+        self._set_sigma(None, n_fields)
+
+    def _thresholds_on(self, device):
+        """The thresholds f32 [T, n_fields] on the device: moved there once per device."""
+        t = self._thr.get(device)
+        if t is None:
+            t = self._thr[device] = self.thresholds.to(device)
+        return t
+
+    def _fused_for(self, y) -> bool:
+        """Whether a call on y runs the fused launches (sea_decode_member_brier): the class docstring's rule when fused is None."""
+        if self.fused is not None:
+            return bool(self.fused)
+        return (self.decoder._act_dtype() == torch.bfloat16 and self.members <= N.BRIER_MAX_N
+                and y.shape[0] * self.n_patches >= BRIER_FUSED_MIN_ROWS)
+
+    def __call__(self, y: torch.Tensor, obs: torch.Tensor, precision: Optional[torch.Tensor] = None, logw: Optional[torch.Tensor] = None,
+                 into: Optional[ThresholdScores] = None, maps=()) -> ThresholdScores:
+        y, tgt, prec = self._operands(y, obs, precision, gpu=False)
+        Bm, G, E = y.shape
+        P, n = self.n_patches, self.members
+        B = Bm // n
+        n_fields, T = self.thresholds.shape[1], self.thresholds.shape[0]
+        maps, logw = _check_brier_call(self._what, maps, logw, into, (B, n_fields, T), Bm, n, y.device)
+        N.require_gpu(y, f"{self._what} states")
+        thr = self._thresholds_on(y.device)
+        z = y.reshape(Bm, G, P, E // P).permute(0, 2, 1, 3)          # the re-layout of FieldLikelihood
+        r = self.decoder.member_brier(z, tgt, n, thr, counts=self.counts, precision=prec, logw=logw, fused=self._fused_for(y), maps=maps,
+                                      into=None if into is None else dict(sums=into.sums, hist=into.hist, hits=into.hits))
+        return ThresholdScores(prob=r.get("prob"), brier_map=r.get("brier"), sums=r["sums"], hist=r["hist"], hits=r["hits"], status=r["status"], thresholds=thr,
+                               weighted=logw is not None or (into is not None and into.weighted))
+
+    verify = __call__
+
+
+class SensorThresholdVerification:
+    """Verification of EXCEEDANCE forecasts against sparse sensor readings: verify(y, obs, precision=None, logw=None, into=None, maps=()) ->
+    ThresholdScores with [B, T] scores — FieldThresholdVerification's with a sensor for a cell (include/sea_hip.h, sea_ensemble_brier).
+    thresholds: [T] or [T, n_fields] in the decoder's scaled units, T <= 8, finite; a sensor takes the threshold of its field (the set's field index), so
+    the launch carries a [T, K] table.  y, obs, precision and logw exactly as in SensorVerification (precision 0 marks a missing reading; no score is
+    weighted by it).  The predictions come from Decode.sensor_sse(..., predictions=True); from_predictions(pred, obs, ...) skips the decode — the pred
+    that SensorKalman.transform returned is scored without decoding twice — and serves CPU tensors through the composed path.
+    fused: True — the two launches of sea_ensemble_brier (up to 128 members, GPU tensors); False — the same formulas as fp64 torch ops.  fused=None
+    follows SensorVerification's rule, which this form's bench confirms (tools/brier_bench.py, profiles/brier_bench.txt): the two
+    launches up to 128 members on the GPU — every measured row, 16 to 4096 sensors, has them ahead of the composed path —, the composed path above 128
+    members and on the CPU.  A call reads nothing back from the device and uploads nothing after the first call on a device."""
+
+    def __init__(self, decoder, n_patches: int, members: int, sensors: SensorSet, thresholds, fused: Optional[bool] = None):
+        what = "SensorThresholdVerification"
+        if not isinstance(members, int) or isinstance(members, bool) or members < 1:
+            raise ValueError(f"{what}: members = {members!r} must be a positive integer")
+        if fused is not None and not isinstance(fused, bool):
+            raise ValueError(f"{what}: fused = {fused!r} must be None, True or False")
+        if fused and members > N.BRIER_MAX_N:
+            raise ValueError(f"{what}: the fused launches carry up to {N.BRIER_MAX_N} members, got {members} (fused=False, or None)")
+        self._like = SensorLikelihood(decoder, n_patches, members, sensors)   # its checks
+        n_fields = sum(len(g) for g in decoder.field_groups)
+        tf = _check_thresholds(what, thresholds, n_fields)
+        self.thresholds = tf[:, torch.as_tensor(list(sensors.out_field), dtype=torch.long)].contiguous()   # [T, K] through the set's field index
+        self._thr = {}
+        self.decoder, self.n_patches, self.members, self.sensors, self.fused = decoder, n_patches, members, sensors, fused
+
+    def _thresholds_on(self, device):
+        t = self._thr.get(device)
+        if t is None:
+            t = self._thr[device] = self.thresholds.to(device)
+        return t
+
+    def _fused_for(self, device) -> bool:
+        if self.fused is not None:
+            return bool(self.fused)
+        return self.members <= N.BRIER_MAX_N and device.type == "cuda"
+
+    def _score(self, pred, obs, precision, logw, into, maps) -> ThresholdScores:
+        what = "SensorThresholdVerification"
+        n, K, T = self.members, self.sensors.K, self.thresholds.shape[0]
+        B, dev = pred.shape[0] // n, pred.device
+        _check_sensor_operands(what, obs, precision, B, K, dev)
+        maps, logw = _check_brier_call(what, maps, logw, into, (B, T), B * n, n, dev)
+        obs, prec = obs.detach(), None if precision is None else precision.detach()
+        thr = self._thresholds_on(dev)
+        with torch.no_grad():
+            if self._fused_for(dev):
+                out = None if into is None else dict(sums=into.sums, hist=into.hist, hits=into.hits)
+                r = ops.ensemble_brier(pred, obs, n, thr, prec=prec, logw=logw, accumulate=into is not None, maps=maps, out=out)
+            else:
+                r = _composed_brier(pred, obs, prec, logw, n, thr)
+                if into is not None:
+                    r["sums"], r["hist"], r["hits"] = into.sums.add_(r["sums"]), into.hist.add_(r["hist"]), into.hits.add_(r["hits"])
+        return ThresholdScores(prob=r.get("prob") if "prob" in maps else None, brier_map=r.get("brier") if "brier" in maps else None, sums=r["sums"],
+                               hist=r["hist"], hits=r["hits"], status=r["status"], thresholds=thr, weighted=logw is not None or (into is not None and into.weighted))
+
+    def from_predictions(self, pred: torch.Tensor, obs: torch.Tensor, precision: Optional[torch.Tensor] = None, logw: Optional[torch.Tensor] = None,
+                         into: Optional[ThresholdScores] = None, maps=()) -> ThresholdScores:
+        """The scores of predictions that exist already: pred float32 [B * members, K] in the sensors' given order (Decode.sensor_sse's predictions, the
+        third result of SensorKalman.transform).  CPU tensors are served by the composed path."""
+        n, K = self.members, self.sensors.K
+        if not torch.is_tensor(pred) or pred.dim() != 2 or pred.dtype != torch.float32 or pred.shape[0] < 1 or pred.shape[0] % n or pred.shape[1] != K:
+            raise ValueError(f"SensorThresholdVerification: pred must be a float32 [B * {n}, {K}] tensor, got "
+                             f"{(tuple(pred.shape), pred.dtype) if torch.is_tensor(pred) else type(pred).__name__}")
+        pred = pred.detach()
+        return self._score(pred if pred.stride(1) == 1 and pred.stride(0) >= K else pred.contiguous(), obs, precision, logw, into, maps)
+
+    def __call__(self, y: torch.Tensor, obs: torch.Tensor, precision: Optional[torch.Tensor] = None, logw: Optional[torch.Tensor] = None,
+                 into: Optional[ThresholdScores] = None, maps=()) -> ThresholdScores:
+        P, n = self.n_patches, self.members
+        if not torch.is_tensor(y) or y.dim() != 3 or y.shape[-1] % P or y.shape[0] < 1:
+            raise ValueError(f"SensorThresholdVerification: y must be [B * members, n_groups, n_patches * D] with n_patches = {P}, got "
+                             f"{tuple(y.shape) if torch.is_tensor(y) else type(y).__name__}")
+        Bm, G, E = y.shape
+        if Bm % n:
+            raise ValueError(f"SensorThresholdVerification: the {Bm} trajectories of y are not a multiple of members = {n}")
+        _check_sensor_operands("SensorThresholdVerification", obs, precision, Bm // n, self.sensors.K, y.device)
+        _check_brier_call("SensorThresholdVerification", maps, logw, into, (Bm // n, self.thresholds.shape[0]), Bm, n, y.device)
+        z = y.detach().reshape(Bm, G, P, E // P).permute(0, 2, 1, 3)          # the re-layout of SensorLikelihood
+        _, pred = self.decoder.sensor_sse(z, self.sensors, obs.detach(), precision=None if precision is None else precision.detach(), members=n, predictions=True)
+        return self._score(pred, obs, precision, logw, into, maps)
+
+    verify = __call__
 
 
 # ------------------------------------------------------------------------------------------------ CRPS of the decoded fields as a loss

@@ -823,6 +823,98 @@ class Decode(nn.Module):
                                             prec=None if prec is None else rows(prec), counts=cnt, logw=lw, unbiased=bool(unbiased),
                                             accumulate=into is not None, maps=maps, out=into, dtype=dt)
 
+    def member_brier(self, z: torch.Tensor, obs: torch.Tensor, members: int, thresholds: torch.Tensor, counts=None, precision: Optional[torch.Tensor] = None,
+                     field_precision: Optional[torch.Tensor] = None, logw: Optional[torch.Tensor] = None, fused: Optional[bool] = None, maps=(),
+                     into: Optional[dict] = None):
+        """The threshold scores of an ensemble against a DENSE observation of the decoded fields: a dict with the maps asked for — prob, brier float32
+        [T, B, P, n_fields, n_inp] — and sums float64 [B, n_fields, T, 5], hist and hits int64 [B, n_fields, T, members + 1], status int32 [B]
+        (include/sea_hip.h, sea_decode_member_brier, states the definitions); no autograd graph.  z, obs, counts, precision, field_precision and logw as
+        in member_verify (the weight of a cell only decides whether it is read); thresholds: float32 [T <= 8, n_fields] on z's device, in the decoder's
+        scaled units (a host tensor is checked for finite values; the classes of sea_amd.ensemble check theirs at construction).  into: a dict with
+        earlier "sums", "hist" and "hits" tensors that this call's are added onto in place (they are the result's).
+        fused=True (bf16 compute dtype, members <= 128): the first-layer launch plus the TWO launches of sea_decode_member_brier — the members' decoded
+        fields are never written.  fused=False: forward() plus the formulas as float64 torch ops (ensemble._composed_field_brier: fp32, any member
+        count, comparison).  fused=None: the fused launches in bf16 up to 128 members from 4096 rows (B * members * P) on — every row of
+        profiles/brier_bench.txt (tools/brier_bench.py) — and the composed path elsewhere: below 4096 rows, where nothing was
+        measured, in fp32 and above 128 members."""
+        from ..ensemble import BRIER_FUSED_MIN_ROWS, BRIER_MAPS, _composed_field_brier, _field_cell_weights
+
+        what = "sea_amd.Decode.member_brier"
+        n_fields = sum(len(g) for g in self.field_groups)
+        C, Cp = self.n_inp, self._n_inp_p
+        if not torch.is_tensor(z) or z.dim() != 4 or z.shape[2] != self.num_groups or z.shape[3] != self.embed_dim:
+            raise ValueError(f"{what}: z must be [B * members, P, {self.num_groups}, {self.embed_dim}], got {tuple(z.shape) if torch.is_tensor(z) else type(z).__name__}")
+        Bm, P = z.shape[0], z.shape[1]
+        if not isinstance(members, int) or isinstance(members, bool) or members < 1 or Bm < 1 or Bm % members:
+            raise ValueError(f"{what}: members = {members!r} must be a positive integer that divides the {Bm} rows of z")
+        B = Bm // members
+        for name, t in (("obs", obs), ("precision", precision)):
+            if t is None and name == "precision":
+                continue
+            if not torch.is_tensor(t) or t.dim() != 4 or tuple(t.shape[:3]) != (B, P, n_fields) or t.shape[3] < C:
+                raise ValueError(f"{what}: {name} must be [{B}, {P}, {n_fields}, >= {C}] (one per history of {members} members), got "
+                                 f"{tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
+            if t.dtype != torch.float32 or t.device != z.device:
+                raise ValueError(f"{what}: {name} must be float32 on {z.device}, got {t.dtype} on {t.device}")
+        if precision is not None and precision.shape[3] != obs.shape[3]:
+            raise ValueError(f"{what}: precision must have obs's shape {tuple(obs.shape)}, got {tuple(precision.shape)}")
+        if field_precision is not None and (not torch.is_tensor(field_precision) or field_precision.dtype != torch.float32 or tuple(field_precision.shape) != (n_fields,)
+                                            or field_precision.device != z.device):
+            raise ValueError(f"{what}: field_precision must be None or a float32 [{n_fields}] tensor on {z.device}")
+        if logw is not None and (not torch.is_tensor(logw) or logw.dtype != torch.float32 or tuple(logw.shape) != (Bm,) or logw.device != z.device):
+            raise ValueError(f"{what}: logw must be None or a float32 [{Bm}] tensor on {z.device}")
+        thr = thresholds.detach().contiguous() if torch.is_tensor(thresholds) else thresholds
+        ops.check_brier_thresholds(thr, n_fields, z.device, what)
+        T = thr.shape[0]
+        maps = tuple(maps)
+        if any(k not in BRIER_MAPS for k in maps) or len(set(maps)) != len(maps):
+            raise ValueError(f"{what}: maps must be distinct names among {BRIER_MAPS}, got {maps!r}")
+        shapes = (("sums", (B, n_fields, T, N.BRIER_SUMS), torch.float64), ("hist", (B, n_fields, T, members + 1), torch.int64),
+                  ("hits", (B, n_fields, T, members + 1), torch.int64))
+        if into is not None and (not isinstance(into, dict) or set(into) != {"sums", "hist", "hits"} or any(
+                not torch.is_tensor(into[k]) or tuple(into[k].shape) != sh or into[k].dtype != dt_ or into[k].device != z.device or not into[k].is_contiguous()
+                for k, sh, dt_ in shapes)):
+            raise ValueError(f"{what}: into must be a dict of contiguous sums float64 [{B}, {n_fields}, {T}, {N.BRIER_SUMS}], hist and hits int64 [{B}, {n_fields}, "
+                             f"{T}, {members + 1}] on {z.device}")
+        dt = self._act_dtype()
+        if fused is None:
+            fused = dt == torch.bfloat16 and members <= N.BRIER_MAX_N and Bm * P >= BRIER_FUSED_MIN_ROWS
+        if fused and dt != torch.bfloat16:
+            raise ValueError(f"{what}: the fused launches are bf16 only (set_compute_dtype('bf16'), or fused=False)")
+        if fused and members > N.BRIER_MAX_N:
+            raise ValueError(f"{what}: the fused launches carry up to {N.BRIER_MAX_N} members, got {members} (fused=False, or None)")
+        cnt, _ = self._valid_counts(counts, P, z.device, allow_empty=True, what="member_brier")
+        N.require_gpu(z, "Decode.member_brier input")
+        with torch.no_grad():
+            obs = obs.detach()
+            prec = None if precision is None else precision.detach()
+            pf = None if field_precision is None else field_precision.detach().contiguous()
+            lw = None if logw is None else logw.detach().contiguous()
+            if not fused:
+                y = self.forward(z.detach()).view(Bm, P, n_fields, C)
+                w = _field_cell_weights((B, P, n_fields, C), pf, prec, cnt, z.device)
+                r = _composed_field_brier(y, obs, w, lw, members, thr, maps=maps)
+                if into is not None:
+                    r["sums"], r["hist"], r["hits"] = into["sums"].add_(r["sums"]), into["hist"].add_(r["hist"]), into["hits"].add_(r["hits"])
+                return r
+
+            def rows(t):   # [B * P, n_fields, width] with unit inner stride: a view where the layout allows it, else one copy of the first C columns
+                t3 = t.reshape(B * P, n_fields, t.shape[3])
+                return t3 if t3.stride(2) == 1 and t3.stride(1) >= C and t3.stride(0) >= 0 else t3[..., :C].contiguous()
+
+            M = Bm * P
+            G, D = self.num_groups, self.embed_dim
+            zf = z.detach().to(torch.float32).contiguous().view(M, G * D)
+            za = torch.empty(M, G * D, device=z.device, dtype=dt)
+            ops.convert(zf, za)
+            W1, W2 = self._weights(dt)
+            hid = [torch.empty(M, self.MLP_hidden, device=z.device, dtype=dt) for _ in range(G)]
+            ops.gemm_grouped([dict(A=za[:, g * D:(g + 1) * D], W=W1[g], Cact=hid[g], act=1) for g in range(G)], dt)
+            bias = self._shadow[3]
+            return ops.decode_member_brier([dict(H=hid[g], W2=W2[g], bias=bias[g]) for g in range(G)], rows(obs), C, Cp, P, members, thr, prec_field=pf,
+                                           prec=None if prec is None else rows(prec), counts=cnt, logw=lw, accumulate=into is not None, maps=maps, out=into,
+                                           dtype=dt)
+
     def _field_weight_on(self, field_weight, n_fields: int, device: torch.device, what: str):
         """field_weight checked on the host (float32 [n_fields], finite, >= 0; cached per tensor object and version) -> a contiguous copy on `device`, or None.
         A tensor that EnsembleCRPSLoss made from values it checked at construction carries a mark and is taken as it is: nothing is read back from the device."""

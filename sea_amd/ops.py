@@ -2158,3 +2158,207 @@ def check_quantile_levels(levels, what: str) -> tuple:
     if any(not (0.0 <= v <= 1.0) for v in lv):   # false for NaN
         raise ValueError(f"{what}: every level must be finite and lie in [0, 1], got {lv}")
     return lv
+
+
+BRIER_MAPS = ("prob", "brier")
+
+
+def check_brier_thresholds(thr, cols: int, dev, what: str) -> None:
+    """thr of a threshold-score call: a contiguous float32 [1 .. 8, cols] tensor on `dev`; one on the host is also checked for finite values (one on the
+    device is not read back: the classes check theirs at construction)."""
+    if not torch.is_tensor(thr) or thr.dtype != torch.float32 or thr.dim() != 2 or not 1 <= thr.shape[0] <= N.BRIER_MAX_T or thr.shape[1] != cols \
+            or not thr.is_contiguous() or thr.device != dev:
+        raise ValueError(f"{what}: thr must be a contiguous float32 [1 .. {N.BRIER_MAX_T}, {cols}] tensor on {dev}, got "
+                         f"{(tuple(thr.shape), thr.dtype, str(thr.device)) if torch.is_tensor(thr) else type(thr).__name__}")
+    if thr.device.type == "cpu" and not bool(torch.isfinite(thr).all()):
+        raise ValueError(f"{what}: every threshold must be finite")
+
+
+def _brier_outputs(what: str, out, maps, accumulate: bool, fixed: Dict, map_shape, width: int, anchor: torch.Tensor):
+    """The outputs of a threshold-score call: `out`'s tensors checked against their shapes (a map's last dimension may be any width >= `width`, the same
+    for both maps), then — behind the check that `anchor`, the operand every other one was compared with, is on the GPU — the others allocated.
+    map_shape(ld) is a map's shape at last dimension ld.  Returns (the dict of outputs, ld)."""
+    dev = anchor.device
+    maps = tuple(maps)
+    if any(k not in BRIER_MAPS for k in maps) or len(set(maps)) != len(maps):
+        raise ValueError(f"{what}: maps must be distinct names among {BRIER_MAPS}, got {maps!r}")
+    out = {} if out is None else out
+    if not isinstance(out, dict) or any(k not in fixed and k not in BRIER_MAPS for k in out):
+        raise ValueError(f"{what}: out must be a dict with keys among {BRIER_MAPS + tuple(fixed)}")
+    widths = {t.shape[-1] for k, t in out.items() if k in BRIER_MAPS and torch.is_tensor(t) and t.dim() == len(map_shape(width))}
+    if len(widths) > 1:
+        raise ValueError(f"{what}: the maps in out must share their last dimension, got {sorted(widths)}")
+    ld = widths.pop() if widths else width
+    for k, t in out.items():
+        shape, dt = fixed[k] if k in fixed else (map_shape(ld), torch.float32)
+        if not torch.is_tensor(t) or tuple(t.shape) != tuple(shape) or t.dtype != dt or not t.is_contiguous() or t.device != dev or ld < width:
+            raise ValueError(f"{what}: out[{k!r}] must be a contiguous {dt} {list(shape)} tensor on {dev} (maps: last dimension >= {width})")
+    if accumulate and any(k not in out for k in ("sums", "hist", "hits")):
+        raise ValueError(f"{what}: accumulate=True adds onto out['sums'], out['hist'] and out['hits']: all three are required")
+    N.require_gpu(anchor, f"{what} operands")   # every operand is on the anchor's device (checked by the caller)
+    res = {k: out[k] if k in out else torch.empty(fixed[k][0], device=dev, dtype=fixed[k][1]) for k in fixed}
+    for k in BRIER_MAPS:
+        if k in out:
+            res[k] = out[k]
+        elif k in maps:
+            res[k] = torch.empty(map_shape(ld), device=dev, dtype=torch.float32)
+    return res, ld
+
+
+def fill_ensemble_brier(P: N.SeaEnsembleBrier, pred, obs, prec, logw, thr, members: int, accumulate: bool, prob, brier, sums, hist, hits, status, work, ld_out: int) -> None:
+    """The argument table of sea_ensemble_brier.  pred, obs, prec, logw as fill_ensemble_verify; thr f32 [T, K] contiguous; prob, brier f32 [T, B, ld_out]
+    contiguous or None; sums f64 [B, T, 5], hist, hits int64 [B, T, members + 1], status int32 [B] contiguous; work: a uint8 workspace of at least
+    sea_ensemble_brier_ws_bytes(B, members, K, T) bytes."""
+    P.pred, P.obs, P.prec, P.logw, P.thr = pred.data_ptr(), obs.data_ptr(), N.ptr(prec), N.ptr(logw), thr.data_ptr()
+    P.prob, P.brier = N.ptr(prob), N.ptr(brier)
+    P.sums, P.hist, P.hits, P.status, P.work = sums.data_ptr(), hist.data_ptr(), hits.data_ptr(), status.data_ptr(), work.data_ptr()
+    P.ld_pred, P.ld_obs, P.ld_thr = pred.stride(0), obs.stride(0), thr.stride(0)
+    P.ld_prec = 0 if prec is None or prec.dim() == 1 else prec.stride(0)
+    P.ld_out, P.ld_map = ld_out, obs.shape[0] * ld_out
+    P.work_bytes = work.numel() * work.element_size()
+    P.B, P.N, P.K, P.n_thr, P.accumulate, P.pad_ = obs.shape[0], members, obs.shape[1], thr.shape[0], int(bool(accumulate)), 0
+
+
+def ensemble_brier(pred: torch.Tensor, obs: torch.Tensor, members: int, thr: torch.Tensor, prec: Optional[torch.Tensor] = None,
+                   logw: Optional[torch.Tensor] = None, accumulate: bool = False, maps: Sequence[str] = BRIER_MAPS,
+                   out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+    """sea_ensemble_brier: the threshold scores of an ensemble at the sensors (include/sea_hip.h states the definitions).  pred, obs, prec, logw as
+    ensemble_verify; thr f32 [T <= 8, K], a threshold per sensor.  Returns a dict: the maps asked for — prob, brier f32 [T, B, K] —, sums f64 [B, T, 5],
+    hist and hits int64 [B, T, members + 1], status int32 [B]; nothing is read back.  out: a dict of tensors to write into, by those names (a map given
+    there is produced whether `maps` names it or not); accumulate=True adds this call's sums, hist and hits onto out's, which are then required."""
+    what = "ensemble_brier"
+    n = members
+    if not isinstance(n, int) or isinstance(n, bool) or n < 1 or n > N.BRIER_MAX_N:
+        raise ValueError(f"{what}: members = {members!r} must be an integer in 1 .. {N.BRIER_MAX_N}")
+    if not torch.is_tensor(obs) or obs.dim() != 2 or obs.dtype != torch.float32 or obs.shape[0] < 1 or obs.shape[1] < 1 or obs.stride(1) != 1:
+        raise ValueError(f"{what}: obs must be a float32 [B, K] tensor with unit inner stride, got {tuple(obs.shape) if torch.is_tensor(obs) else type(obs).__name__}")
+    B, K = obs.shape
+    dev = obs.device
+    if not torch.is_tensor(pred) or pred.dtype != torch.float32 or tuple(pred.shape) != (B * n, K) or pred.stride(1) != 1 or (pred.stride(0) < K and B * n > 1) \
+            or pred.device != dev:
+        raise ValueError(f"{what}: pred must be a float32 [{B * n}, {K}] tensor with unit inner stride on {dev}, got "
+                         f"{(tuple(pred.shape), pred.dtype, str(pred.device)) if torch.is_tensor(pred) else type(pred).__name__}")
+    if obs.stride(0) < K and B > 1:
+        raise ValueError(f"{what}: obs rows overlap (strides {obs.stride()})")
+    check_brier_thresholds(thr, K, dev, what)
+    if prec is not None and (not torch.is_tensor(prec) or prec.dtype != torch.float32 or tuple(prec.shape) not in ((K,), (B, K)) or prec.stride(-1) != 1
+                             or prec.device != dev or (prec.dim() == 2 and B > 1 and prec.stride(0) < K)):
+        raise ValueError(f"{what}: prec must be None or a float32 [{K}] or [{B}, {K}] tensor with unit inner stride on {dev}, got "
+                         f"{(tuple(prec.shape), prec.dtype, str(prec.device)) if torch.is_tensor(prec) else type(prec).__name__}")
+    if prec is not None and prec.device.type == "cpu" and (not bool(torch.isfinite(prec).all()) or not bool((prec >= 0).all())):
+        raise ValueError(f"{what}: prec must be finite and >= 0")
+    if prec is not None and prec.dim() == 2 and prec.stride(0) < K:   # one history whose row stride says nothing: the [K] form
+        prec = prec[0]
+    if logw is not None and (not torch.is_tensor(logw) or logw.dtype != torch.float32 or tuple(logw.shape) != (B * n,) or not logw.is_contiguous() or logw.device != dev):
+        raise ValueError(f"{what}: logw must be None or a contiguous float32 [{B * n}] tensor on {dev}, got "
+                         f"{(tuple(logw.shape), logw.dtype, str(logw.device)) if torch.is_tensor(logw) else type(logw).__name__}")
+    if B > 65535:
+        raise ValueError(f"{what}: {B} histories; a launch carries up to 65535")
+    T = thr.shape[0]
+    fixed = {"sums": ((B, T, N.BRIER_SUMS), torch.float64), "hist": ((B, T, n + 1), torch.int64), "hits": ((B, T, n + 1), torch.int64), "status": ((B,), torch.int32)}
+    res, ld = _brier_outputs(what, out, maps, accumulate, fixed, lambda ld: (T, B, ld), K, obs)
+    work = torch.empty(int(N.lib().sea_ensemble_brier_ws_bytes(B, n, K, T)), device=dev, dtype=torch.uint8)
+    P = N.SeaEnsembleBrier()
+    fill_ensemble_brier(P, pred, obs, prec, logw, thr, n, accumulate, res.get("prob"), res.get("brier"), res["sums"], res["hist"], res["hits"], res["status"], work, ld)
+    P.ld_obs, P.ld_pred = max(P.ld_obs, K), max(P.ld_pred, K)   # a single row: its stride is never used and may say anything
+    N.check(N.lib().sea_ensemble_brier(C.byref(P), N.stream_ptr()), "sea_ensemble_brier")
+    return res
+
+
+def fill_decode_member_brier(groups_arr, P: N.SeaDecodeMemberBrier, groups: Sequence[Dict], obs, prec_field, prec, counts, logw, thr, n_patches: int, members: int,
+                             C_: int, Cp: int, accumulate: bool, prob, brier, sums, hist, hits, status, work, ld_out: int) -> None:
+    """The argument table of sea_decode_member_brier.  groups, obs, prec_field, prec, counts, logw as fill_decode_member_verify; thr f32 [T, n_fields_total]
+    contiguous; prob, brier f32 [T, B, n_patches, n_fields_total, ld_out] contiguous or None; sums f64 [B, n_fields_total, T, 5], hist, hits int64
+    [B, n_fields_total, T, members + 1], status int32 [B] contiguous; work: a uint8 workspace of at least sea_decode_member_brier_ws_bytes(...) bytes."""
+    field0 = 0
+    for g, d in zip(groups_arr, groups):
+        H, W2 = d["H"], d["W2"]
+        g.H, g.W2, g.bias, g.dH, g.Z = H.data_ptr(), W2.data_ptr(), d["bias"].data_ptr(), None, None
+        g.ldh, g.ldw, g.lddh, g.ldz = H.stride(0), W2.stride(0), 0, 0
+        g.n_fields, g.field0 = W2.shape[0] // Cp, field0
+        field0 += g.n_fields
+    P.obs, P.prec_field, P.prec, P.counts, P.logw, P.thr = obs.data_ptr(), N.ptr(prec_field), N.ptr(prec), N.ptr(counts), N.ptr(logw), thr.data_ptr()
+    P.prob, P.brier = N.ptr(prob), N.ptr(brier)
+    P.sums, P.hist, P.hits, P.status, P.work = sums.data_ptr(), hist.data_ptr(), hits.data_ptr(), status.data_ptr(), work.data_ptr()
+    P.ld_row, P.ld_field = obs.stride(0), obs.stride(1)
+    P.ld_prow, P.ld_pfield = (0, 0) if prec is None else (prec.stride(0), prec.stride(1))
+    P.ld_out, P.ld_map, P.work_bytes = ld_out, obs.shape[0] * field0 * ld_out, work.numel() * work.element_size()
+    P.M, P.S, P.C, P.Cp, P.P = groups[0]["H"].shape[0], groups[0]["H"].shape[1], C_, Cp, n_patches
+    P.members, P.n_fields_total, P.n_thr, P.accumulate, P.pad_ = members, field0, thr.shape[0], int(bool(accumulate)), 0
+
+
+def decode_member_brier(groups: Sequence[Dict], obs: torch.Tensor, C_: int, Cp: int, n_patches: int, members: int, thr: torch.Tensor,
+                        prec: Optional[torch.Tensor] = None, prec_field: Optional[torch.Tensor] = None, counts: Optional[torch.Tensor] = None,
+                        logw: Optional[torch.Tensor] = None, accumulate: bool = False, maps: Sequence[str] = BRIER_MAPS,
+                        out: Optional[Dict[str, torch.Tensor]] = None, dtype: torch.dtype = torch.bfloat16) -> Dict[str, torch.Tensor]:
+    """sea_decode_member_brier: the threshold scores of an ensemble at every cell of a dense observation of the decoded fields — the Brier sums, the
+    histograms of the reliability diagram and the hit counts of the ROC (include/sea_hip.h states the definitions) — the members' decoded fields are
+    never written.  groups, obs, prec_field, prec, counts, logw as decode_member_verify; thr f32 [T <= 8, n_fields] in the decoder's scaled units; maps:
+    the per-cell outputs to produce, a subset of ("prob", "brier").  Returns a dict: the maps asked for, f32 [T, B, n_patches, n_fields, C] (every
+    element written), sums f64 [B, n_fields, T, 5], hist and hits int64 [B, n_fields, T, members + 1], status int32 [B] — on the device; nothing is read
+    back.  out: a dict of tensors to write into, by those names (a map given there is produced whether `maps` names it or not; its last dimension may be
+    any width >= C, the same for both maps); accumulate=True adds this call's sums, hist and hits onto out's, which are then required.  Everything is
+    checked on the host before the launch."""
+    what = "decode_member_brier"
+    if dtype != torch.bfloat16:
+        raise ValueError(f"{what}: the fused launch is bf16 only, got {dtype}")
+    if not groups or len(groups) > N.DECODE_MSE_MAX_GROUPS:
+        raise ValueError(f"{what}: {len(groups)} groups; a launch carries 1 .. {N.DECODE_MSE_MAX_GROUPS}")
+    if Cp < 32 or Cp % 32 or not 1 <= C_ <= Cp:
+        raise ValueError(f"{what}: need Cp a multiple of 32 and 1 <= C <= Cp, got C = {C_}, Cp = {Cp}")
+    dev = groups[0]["H"].device
+    M, S = tuple(groups[0]["H"].shape) if groups[0]["H"].dim() == 2 else (0, 0)
+    if M < 1 or S < 8 or S % 8 or S > N.DECODE_MSE_MAX_S:
+        raise ValueError(f"{what}: H must be [M >= 1, S] with S a multiple of 8 up to {N.DECODE_MSE_MAX_S}, got {tuple(groups[0]['H'].shape)}")
+    n = members
+    if not isinstance(n, int) or isinstance(n, bool) or n < 1 or n > N.BRIER_MAX_N:
+        raise ValueError(f"{what}: members = {members!r} must be an integer in 1 .. {N.BRIER_MAX_N}")
+    if n_patches < 1 or M % (n_patches * n):
+        raise ValueError(f"{what}: {M} rows are not a multiple of n_patches * members = {n_patches} * {n}")
+    n_fields = 0
+    for i, d in enumerate(groups):
+        for name in ("H", "W2"):
+            t = d[name]
+            if t.dim() != 2 or t.stride(1) != 1:
+                raise ValueError(f"{what} group {i}: {name}: need a 2-D tensor with unit inner stride, got shape {tuple(t.shape)} strides {t.stride()}")
+            if t.dtype != dtype or t.device != dev or t.shape[1] != S or (name != "W2" and t.shape[0] != M):
+                raise ValueError(f"{what} group {i}: {name} must be a {dtype} [{'n_fields * Cp' if name == 'W2' else M}, {S}] tensor on {dev}, got "
+                                 f"{tuple(t.shape)} {t.dtype} on {t.device}")
+            if t.stride(0) % 8 or t.data_ptr() % 16:
+                raise ValueError(f"{what} group {i}: {name} needs a row stride that is a multiple of 8 and a 16-byte-aligned base (stride {t.stride(0)})")
+        W2, b = d["W2"], d["bias"]
+        if W2.shape[0] < Cp or W2.shape[0] % Cp:
+            raise ValueError(f"{what} group {i}: W2 has {W2.shape[0]} rows, not a multiple of Cp = {Cp}")
+        if b.dtype != torch.float32 or b.dim() != 1 or b.shape[0] != W2.shape[0] or not b.is_contiguous() or b.device != dev or b.data_ptr() % 16:
+            raise ValueError(f"{what} group {i}: bias must be a contiguous, 16-byte-aligned float32 [{W2.shape[0]}] on {dev}, got {tuple(b.shape)} {b.dtype}")
+        n_fields += W2.shape[0] // Cp
+    B = M // (n_patches * n)
+    if B > 65535:
+        raise ValueError(f"{what}: {B} histories; a launch carries up to 65535")
+    for name, t in (("obs", obs), ("prec", prec)):
+        if t is None and name == "prec":
+            continue
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or t.dim() != 3 or tuple(t.shape[:2]) != (B * n_patches, n_fields) or t.shape[2] < C_ or t.stride(2) != 1 \
+                or t.device != dev or t.stride(1) < C_ or (t.shape[0] > 1 and t.stride(0) < 0):
+            raise ValueError(f"{what}: {name} must be a float32 [{B * n_patches}, {n_fields}, >= {C_}] tensor with unit inner stride on {dev}, got "
+                             f"{(tuple(t.shape), t.dtype, t.stride(), str(t.device)) if torch.is_tensor(t) else type(t).__name__}")
+    check_brier_thresholds(thr, n_fields, dev, what)
+    if prec_field is not None and (not torch.is_tensor(prec_field) or prec_field.dtype != torch.float32 or tuple(prec_field.shape) != (n_fields,)
+                                   or not prec_field.is_contiguous() or prec_field.device != dev):
+        raise ValueError(f"{what}: prec_field must be None or a contiguous float32 [{n_fields}] tensor on {dev}")
+    if counts is not None and (not torch.is_tensor(counts) or counts.dtype != torch.int32 or counts.dim() != 1 or counts.shape[0] != n_patches
+                               or not counts.is_contiguous() or counts.device != dev):
+        raise ValueError(f"{what}: counts must be a contiguous int32 [{n_patches}] on {dev}")
+    if logw is not None and (not torch.is_tensor(logw) or logw.dtype != torch.float32 or tuple(logw.shape) != (B * n,) or not logw.is_contiguous() or logw.device != dev):
+        raise ValueError(f"{what}: logw must be None or a contiguous float32 [{B * n}] tensor on {dev}, got "
+                         f"{(tuple(logw.shape), logw.dtype, str(logw.device)) if torch.is_tensor(logw) else type(logw).__name__}")
+    T = thr.shape[0]
+    fixed = {"sums": ((B, n_fields, T, N.BRIER_SUMS), torch.float64), "hist": ((B, n_fields, T, n + 1), torch.int64), "hits": ((B, n_fields, T, n + 1), torch.int64),
+             "status": ((B,), torch.int32)}
+    res, ld = _brier_outputs(what, out, maps, accumulate, fixed, lambda ld: (T, B, n_patches, n_fields, ld), C_, groups[0]["H"])
+    work = torch.empty(int(N.lib().sea_decode_member_brier_ws_bytes(B, n_patches, n_fields, n, Cp, T)), device=dev, dtype=torch.uint8)
+    arr, P = (N.SeaDecodeMseGroup * len(groups))(), N.SeaDecodeMemberBrier()
+    fill_decode_member_brier(arr, P, groups, obs, prec_field, prec, counts, logw, thr, n_patches, n, C_, Cp, accumulate, res.get("prob"), res.get("brier"), res["sums"],
+                             res["hist"], res["hits"], res["status"], work, ld)
+    N.check(N.lib().sea_decode_member_brier(arr, len(groups), C.byref(P), N.dtype_code(dtype), N.stream_ptr()), "sea_decode_member_brier")
+    return res
