@@ -1732,6 +1732,53 @@ typedef struct {
 int64_t sea_ensemble_brier_ws_bytes(int B, int N, int K, int n_thr);   /* -1 for sizes the entry point refuses */
 int sea_ensemble_brier(const SeaEnsembleBrier* p, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Quantile, exceedance and Brier maps of DERIVED fields — the speed |u| = sqrt(u^2 + v^2), a kinetic energy, a difference of two fields — of an
+ * ensemble, without the members' decoded components or the derived field ever existing in memory.  A quantile of |u| is not a function of the
+ * quantiles of u and v: the derived value has to be formed per member, before the read-out.  A derived field d is (op, a, b, scale_a, shift_a,
+ * scale_b, shift_b): a != b are SOURCE fields that lie in the same SeaDecodeMseGroup (they share the hidden row and land in the same lane and register
+ * of the same accumulator layout); y_a, y_b are the decoded f32 values of member j at one cell, exactly as sea_decode_member_quantiles decodes them
+ * (the same sums in the same order).  All arithmetic is f32, every operation rounded ONCE — no fused multiply-add, no reassociation:
+ *     a' = y_a * scale_a + shift_a          b' = y_b * scale_b + shift_b          (one multiply, one add each)
+ *     SEA_DERIVED_MAGNITUDE   x = sqrt(a' * a' + b' * b')       two products, one add, one CORRECTLY ROUNDED f32 root (the hardware root, one
+ *                                                                Newton step, and a choice among the result and its two neighbours by the
+ *                                                                sign of two fma residuals; arguments below 2^-96 are scaled by 2^32)
+ *     SEA_DERIVED_ENERGY      x = 0.5f * (a' * a' + b' * b')
+ *     SEA_DERIVED_DIFFERENCE  x = a' - b'
+ * scale and shift carry the mesh's inverse scaling: x is in PHYSICAL units (a magnitude of min-max-scaled components means nothing).  f32 denormals
+ * are flushed to zero, as everywhere in this library.
+ * From x_j on everything is sea_decode_member_quantiles and sea_decode_member_brier with "field" read as "derived field" — the same device code
+ * behind the value image: weights and dead members; below_i, the weighted quantile and the strict exceedance; m, p, o, sums, hist, hits, status; live,
+ * dead and bad cells; counts.  A cell where a live member's x is not finite (NaN or Inf in a source, overflow of a square) is NaN (quantiles) or BAD
+ * (Brier), as a non-finite decoded value is there.  thr is f32 [n_thr, n_derived], in the derived field's own units.
+ * p->n_fields_total stays the number of SOURCE fields (the groups cover them exactly once); every map, thr, obs, prec, prec_field, sums, hist, hits and
+ * the workspace have n_derived where the member entry points have F: quant f32 [n_levels, B * P, n_derived, ld], ld_map >= B * P * n_derived * ld;
+ * obs [B * P, n_derived, >= C]; sums f64 [B, n_derived, n_thr, 5]; work_bytes >= sea_decode_member_brier_ws_bytes(B, P, n_derived, members, Cp, n_thr).
+ * Launches: the member launches' grids with n_derived for F.  Per tile of 32 columns the W2 tiles of source a and of source b go through the SAME two
+ * LDS images (the stream a_0, b_0, a_1, b_1, ...; hidden rows loaded once); a wave decodes a's tile into 8 registers, b's tile on top, applies the op per
+ * element and stores x to the value image.  sea_decode_derived_brier is followed by sea_decode_member_brier's finish launch.  No workspace (quantiles),
+ * no floating-point atomics: two runs give the same bits, a history's outputs are those of a call holding it alone, and a derived field's outputs do not
+ * depend on the other derived fields of the call.
+ * Returns -1, with the entry point and the offending derived field named in sea_last_error(), before any device is touched, for: n_derived outside
+ * 1 .. SEA_DERIVED_MAX; an unknown op; a or b outside 0 .. n_fields_total-1; a == b; a coefficient that is not finite; and everything
+ * sea_decode_member_quantiles / sea_decode_member_brier refuse.  Returns SEA_EUNSUPPORTED (callers compose the decode and torch ops) for sources in
+ * different groups, SEA_F32, S above 640 and more than 128 members.  Notes the forms "decode.derived_quantiles" and "decode.derived_brier" (a = the
+ * padded hidden width, b = the dynamic LDS bytes).
+ * (Additions to ABI version 8.  The struct is not in sea_struct_sizes(): sizeof(SeaDerivedField) is 32.)
+ */
+#define SEA_DERIVED_MAX 8
+#define SEA_DERIVED_MAGNITUDE 0
+#define SEA_DERIVED_ENERGY 1
+#define SEA_DERIVED_DIFFERENCE 2
+typedef struct {
+    int32_t op, a, b, pad_;
+    float scale_a, shift_a, scale_b, shift_b;
+} SeaDerivedField;           /* 32 bytes */
+int sea_decode_derived_quantiles(const SeaDecodeMseGroup* groups, int n_groups, const SeaDerivedField* derived, int n_derived,
+                                 const SeaDecodeMemberQuantiles* p, int dtype, void* stream);
+int sea_decode_derived_brier(const SeaDecodeMseGroup* groups, int n_groups, const SeaDerivedField* derived, int n_derived,
+                             const SeaDecodeMemberBrier* p, int dtype, void* stream);
+
 /* Tuning aid: register a device buffer of n_steps * 64 8-byte words that the persistent form fills with 100 MHz clock stamps of its hand-offs
  * (tools/kv_persist_timeline.py); NULL switches it off. */
 void sea_kv_debug_stamps(unsigned long long* buf);

@@ -2947,6 +2947,579 @@ extern "C" int sea_decode_member_brier(const SeaDecodeMseGroup* groups, int n_gr
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------------------------
+// sea_decode_derived_quantiles / sea_decode_derived_brier: the two read-outs above for DERIVED fields — x = |(a', b')|, (a'^2 + b'^2) / 2 or a' - b'
+// of two source fields of ONE decoder group, per member and cell (include/sea_hip.h states the definitions).  The kernels are
+// decode_member_quantiles_kernel and decode_member_brier_kernel with grid.y = n_derived and stage a replaced by a two-source decode
+// (mq_decode_pair_tile): the W2 tiles of source a and of source b go through the same two LDS images — a's tile in the first, b's in the second: the
+// stream a_0, b_0, a_1, b_1, ... — the hidden rows are loaded once, a's tile is decoded into 8 registers (mq_decode_regs: mq_decode_tile's sums in
+// its order), b's tile on top of them, the op is applied per element in single-rounded f32 (mul1 / add1; dv_sqrt_rn) and x goes to V[column][member].
+// Both tiles of the next step are fetched behind stage b (two staging sets) and stored in stage c: three barriers per tile as before, LDS at
+// mv_lds_bytes<SP>().  Everything behind the value image is the member kernels' code (qs_column_wave, bs_column_wave, bs_finish_cell,
+// member_brier_finish_kernel), indexed by derived field.
+struct DerivedTable {
+    SeaDerivedField d[SEA_DERIVED_MAX];
+    int gsel[SEA_DERIVED_MAX];   // the group that holds both sources of derived field i (the entry point has resolved it)
+    int n_derived;
+};
+struct DerivedQuantLaunch {
+    SeaDecodeMseGroup g[SEA_DECODE_MSE_MAX_GROUPS];
+    SeaDecodeMemberQuantiles p;
+    DerivedTable t;
+};
+struct DerivedBrierLaunch {
+    SeaDecodeMseGroup g[SEA_DECODE_MSE_MAX_GROUPS];
+    SeaDecodeMemberBrier p;
+    DerivedTable t;
+    int words;   // 8-byte words per (history, patch, chunk, derived field) of the workspace
+};
+
+// The correctly rounded f32 square root.  The build's -ffast-math turns sqrtf (and __fsqrt_rn) into the bare v_sqrt_f32, an approximation.  So: the
+// hardware root s; one Newton step s + (x - s s) / (2 s) with the residual from ONE fma (exact this close to the root) and the quotient from
+// v_rcp_f32, so that what follows does not lean on the last bits of the hardware root; then the choice among s and its two neighbours by the sign of
+// the fma residuals x - s_down s and x - s_up s (the compiler's own IEEE lowering of llvm.sqrt.f32, written out), which is the rounded root for any
+// start within 1 ulp.  Arguments below 2^-96 are scaled by 2^32 (the root by 2^-16) so that no residual is flushed; +-0 and +inf return themselves,
+// a negative argument or NaN gives NaN.  (tests/test_derived_fields_gpu.py: equal bits with the root of float64 rounded once.)
+__device__ __forceinline__ float dv_sqrt_rn(const float x) {
+    const bool small = x < 0x1p-96f;
+    const float xs = small ? mul1(x, 0x1p+32f) : x;
+    float s = __builtin_amdgcn_sqrtf(xs);
+    s = fma1(fma1(-s, s, xs), mul1(0.5f, __builtin_amdgcn_rcpf(s)), s);
+    const float sd = __int_as_float(__float_as_int(s) - 1), su = __int_as_float(__float_as_int(s) + 1);
+    const float dd = fma1(-sd, s, xs), du = fma1(-su, s, xs);
+    s = dd <= 0.f ? sd : s;
+    s = du > 0.f ? su : s;
+    s = small ? mul1(s, 0x1p-16f) : s;
+    return (xs == 0.f || xs == __builtin_inff()) ? xs : s;
+}
+
+// One member's derived value at one cell from the two decoded source values: every operation rounded once.
+__device__ __forceinline__ float dv_value(const int op, const float ya, const float yb, const float sa, const float ha, const float sb, const float hb) {
+    const float a = add1(mul1(ya, sa), ha), b = add1(mul1(yb, sb), hb);
+    if (op == SEA_DERIVED_DIFFERENCE) return add1(a, -b);
+    const float q = add1(mul1(a, a), mul1(b, b));
+    return op == SEA_DERIVED_ENERGY ? mul1(0.5f, q) : dv_sqrt_rn(q);
+}
+
+// mq_decode_tile's decode with the 8 values left in registers: y[sub][r] is what that function stores at vcol[(sub * 16 + li) * MV_VP + 4 * lg + r].
+template <int SP>
+__device__ __forceinline__ void mq_decode_regs(const uint4 (&hf)[SP / 32], const char* buf, const float* bias, const int S, const int li, const int lg, float (&y)[2][4]) {
+    constexpr int PITCH = SP * 2 + DM_PAD;
+    f32x4 acc[2][2];
+#pragma unroll
+    for (int sub = 0; sub < 2; ++sub) {
+        const float bv = bias[sub * 16 + li];
+        acc[sub][0] = f32x4{bv, bv, bv, bv};
+        acc[sub][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+#pragma unroll
+    for (int ks = 0; ks < SP / 32; ++ks) {
+        if (ks * 32 < S) {
+#pragma unroll
+            for (int sub = 0; sub < 2; ++sub) {
+                const uint4 wv = *reinterpret_cast<const uint4*>(buf + (sub * 16 + li) * PITCH + (ks * 4 + lg) * 16);
+                mma16<__bf16>(hf[ks], wv, acc[sub][ks & 1]);
+            }
+        }
+    }
+#pragma unroll
+    for (int sub = 0; sub < 2; ++sub) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)   // plain C++: the first reader of an MFMA result must be an instruction the compiler sees
+            y[sub][r] = acc[sub][0][r] + acc[sub][1][r];
+    }
+}
+
+// mq_decode_pair_tile: a wave's 16 members times the tile's 32 columns of derived field X into the value image; bufa, bufb: the LDS images of the two
+// sources' tiles; biasa, biasb: their 32 bias entries; vcol: V + the wave's first member.
+template <int SP>
+__device__ __forceinline__ void mq_decode_pair_tile(const uint4 (&hf)[SP / 32], const char* bufa, const char* bufb, const float* biasa, const float* biasb, const int S,
+                                                    const int li, const int lg, const SeaDerivedField& X, float* vcol) {
+    float ya[2][4], yb[2][4];
+    mq_decode_regs<SP>(hf, bufa, biasa, S, li, lg, ya);
+    mq_decode_regs<SP>(hf, bufb, biasb, S, li, lg, yb);
+    const int op = X.op;
+    const float sa = X.scale_a, ha = X.shift_a, sb = X.scale_b, hb = X.shift_b;
+#pragma unroll
+    for (int sub = 0; sub < 2; ++sub) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) vcol[(sub * 16 + li) * MV_VP + 4 * lg + r] = dv_value(op, ya[sub][r], yb[sub][r], sa, ha, sb, hb);
+    }
+}
+
+template <int SP, int V>
+__global__ __launch_bounds__(MV_NT) void decode_derived_quantiles_kernel(const DerivedQuantLaunch L) {
+#pragma clang fp reassociate(off)
+    constexpr int NW = MV_NW;
+    constexpr int NT = MV_NT;
+    constexpr int KS = SP / 32;
+    constexpr int PITCH = SP * 2 + DM_PAD;
+    constexpr int TILE = DM_TC * PITCH;
+    constexpr int NCH = SP * 4 / NT;
+    constexpr int VP = MV_VP;
+    static_assert(NCH * NT == DM_TC * (SP / 8), "whole chunks per thread");
+    extern __shared__ __attribute__((aligned(16))) char smem[];   // 2 tile images (source a's, source b's); the value image [32][VP]
+    float* Vs = reinterpret_cast<float*>(smem + 2 * TILE);
+    __shared__ double w_s[VF_MAX_N];
+    __shared__ int live_s[VF_MAX_N];
+    __shared__ float res_s[DM_TC][QS_MAX_OUT];
+    __shared__ float thr_s[SEA_QUANTILE_MAX_LEVELS];
+
+    const SeaDecodeMemberQuantiles& P = L.p;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), li = lane & 15, lg = lane >> 4;
+    const int S = P.S, C = P.C, Cp = P.Cp, N = P.members, D = L.t.n_derived, nl = P.n_levels, nt = P.n_thr;
+    const int bp = blockIdx.x, dg = blockIdx.y, ck = blockIdx.z;   // the derived field and the chunk of its tiles this workgroup reads out
+    const int b = bp / P.P, patch = bp - b * P.P;
+    const int64_t ld = P.ld;
+    const int64_t obase = ((int64_t)bp * D + dg) * ld;
+
+    int lim = C;   // valid columns of this patch: [0, lim) — uniform over the workgroup
+    if (P.counts != nullptr) {
+        const int cnt = P.counts[patch];
+        lim = cnt < 0 ? 0 : (cnt > C ? C : cnt);
+    }
+    const int tpf = (lim + DM_TC - 1) / DM_TC;   // tiles of a field that hold valid columns
+    const int tb = ck * MV_CHUNK, te = tpf < tb + MV_CHUNK ? tpf : tb + MV_CHUNK;   // this workgroup's tiles: [tb, te)
+
+    // the weights of the history: a member with w <= 0 or NaN is dead
+    int alive = 0;
+    if (tid < N) {
+        const float wv = P.w != nullptr ? P.w[(int64_t)b * N + tid] : 1.f;
+        alive = wv > 0.f ? 1 : 0;   // false for NaN
+        w_s[tid] = alive ? (double)wv : 0.0;
+        live_s[tid] = alive;
+    }
+    if (tid < nt) thr_s[tid] = P.thr[(int64_t)tid * D + dg];
+    const int n_live = __syncthreads_count(alive);
+    const bool empty = n_live == 0;
+    if (ck == 0) {   // the columns no tile walks (all of them when the history has no live member or the patch no valid column): 0
+        const int c0 = (empty || tpf == 0) ? 0 : tpf * DM_TC;
+        for (int64_t c = c0 + tid; c < ld; c += NT) {
+            const int64_t at = obase + c;
+            for (int k = 0; k < nl; ++k) P.quant[k * P.ld_map + at] = 0.f;
+            for (int t = 0; t < nt; ++t) P.exceed[t * P.ld_map + at] = 0.f;
+        }
+    }
+    if (empty || te <= tb) return;   // uniform: nothing to read out in this chunk
+    double W = 0.0;
+    for (int j = 0; j < N; ++j) W += w_s[j];   // one chain, j ascending; a dead member adds +0
+
+    const int j0 = wave * 16;
+    const bool active = j0 < N;                 // uniform over the wave
+    const int jm = j0 + li;
+    const int64_t m = ((int64_t)b * N + (jm < N ? jm : 0)) * P.P + patch;
+
+    const SeaDerivedField& X = L.t.d[dg];
+    const SeaDecodeMseGroup& G = L.g[L.t.gsel[dg]];   // the group that holds both sources
+    const int ja = X.a - G.field0, jb = X.b - G.field0;   // the sources inside their group
+    const __bf16* H = static_cast<const __bf16*>(G.H);
+    const __bf16* W2 = static_cast<const __bf16*>(G.W2);
+    uint4 hf[KS];
+    mq_load_row<SP>(hf, H + m * G.ldh, S, lg);
+    const int n_tiles = te - tb, t0a = ja * tpf + tb, t0b = jb * tpf + tb;   // this chunk's tiles among the group's, per source
+    uint4 wa[NCH], wb[NCH];
+    dm_load_tile<SP, NT>(wa, W2, G.ldw, S, Cp, tpf, t0a, tid);
+    dm_load_tile<SP, NT>(wb, W2, G.ldw, S, Cp, tpf, t0b, tid);
+    dm_store_tile<SP, NT>(wa, smem, tid);
+    dm_store_tile<SP, NT>(wb, smem + TILE, tid);
+    __syncthreads();
+
+    for (int t = 0; t < n_tiles; ++t) {
+        const int cb = (tb + t) * DM_TC;
+
+        // a: decode both sources, form the derived value, into the value image
+        if (active) mq_decode_pair_tile<SP>(hf, smem, smem + TILE, G.bias + ja * Cp + cb, G.bias + jb * Cp + cb, S, li, lg, X, Vs + j0);
+        __syncthreads();
+        if (t + 1 < n_tiles) {   // in flight behind b
+            dm_load_tile<SP, NT>(wa, W2, G.ldw, S, Cp, tpf, t0a + t + 1, tid);
+            dm_load_tile<SP, NT>(wb, W2, G.ldw, S, Cp, tpf, t0b + t + 1, tid);
+        }
+
+        // b: a column per wave at a time
+        for (int cl = wave; cl < DM_TC; cl += NW) {
+            if (cb + cl >= lim) continue;   // the same word in every lane: a dead column, stage c writes its zeros
+            qs_column_wave<V>(Vs + cl * VP, w_s, live_s, N, lane, W, P.level, nl, thr_s, nt, res_s[cl]);
+        }
+        __syncthreads();
+
+        // c: thread k stores column k of every map
+        if (tid < DM_TC) {
+            const int c = cb + tid;
+            if (c < ld) {
+                const int64_t at = obase + c;
+                const bool on = c < lim;
+                for (int k = 0; k < nl; ++k) P.quant[k * P.ld_map + at] = on ? res_s[tid][k] : 0.f;
+                for (int q = 0; q < nt; ++q) P.exceed[q * P.ld_map + at] = on ? res_s[tid][nl + q] : 0.f;
+            }
+        }
+        if (t + 1 < n_tiles) {
+            dm_store_tile<SP, NT>(wa, smem, tid);
+            dm_store_tile<SP, NT>(wb, smem + TILE, tid);
+        }
+        __syncthreads();
+    }
+}
+
+template <int SP, int V>
+__global__ __launch_bounds__(MV_NT) void decode_derived_brier_kernel(const DerivedBrierLaunch L) {
+#pragma clang fp reassociate(off)
+    constexpr int NW = MV_NW;
+    constexpr int NT = MV_NT;
+    constexpr int KS = SP / 32;
+    constexpr int PITCH = SP * 2 + DM_PAD;
+    constexpr int TILE = DM_TC * PITCH;
+    constexpr int NCH = SP * 4 / NT;
+    constexpr int VP = MV_VP;
+    static_assert(NCH * NT == DM_TC * (SP / 8), "whole chunks per thread");
+    static_assert(DM_TC * BS_MAX_T <= NT, "a thread per (column, threshold)");
+    extern __shared__ __attribute__((aligned(16))) char smem[];   // 2 tile images (source a's, source b's); the value image [32][VP]
+    float* Vs = reinterpret_cast<float*>(smem + 2 * TILE);
+    __shared__ double lw_s[VF_MAX_N], w_s[VF_MAX_N];
+    __shared__ int live_s[VF_MAX_N];
+    __shared__ BsCell cell_s[DM_TC];
+    __shared__ double term_s[BS_MAX_T * BS_SUMS][DM_TC];
+    __shared__ int hist_s[2 * BS_MAX_T * (VF_MAX_N + 1)];   // [hist | hits][t][m] at the call's T and N
+    __shared__ float y_s[DM_TC], pv_s[DM_TC], thr_s[BS_MAX_T];
+
+    const SeaDecodeMemberBrier& P = L.p;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), li = lane & 15, lg = lane >> 4;
+    const int S = P.S, C = P.C, Cp = P.Cp, N = P.members, D = L.t.n_derived, T = P.n_thr, words = L.words;
+    const int bp = blockIdx.x, dg = blockIdx.y, ck = blockIdx.z, Q = gridDim.z;
+    const int b = bp / P.P, patch = bp - b * P.P;
+    const int64_t ld = P.ld_out;
+    const int64_t obase = ((int64_t)bp * D + dg) * ld;
+    const int nb = T * (N + 1);
+    double* const wsum = reinterpret_cast<double*>(P.work) + (((int64_t)bp * Q + ck) * D + dg) * words;
+    int32_t* const whist = reinterpret_cast<int32_t*>(wsum + T * BS_SUMS);
+
+    int lim = C;   // valid columns of this patch: [0, lim) — uniform over the workgroup
+    if (P.counts != nullptr) {
+        const int cnt = P.counts[patch];
+        lim = cnt < 0 ? 0 : (cnt > C ? C : cnt);
+    }
+    const int tpf = (lim + DM_TC - 1) / DM_TC;   // tiles of a field that hold valid columns
+    const int tb = ck * MV_CHUNK, te = tpf < tb + MV_CHUNK ? tpf : tb + MV_CHUNK;   // this workgroup's tiles: [tb, te)
+
+    for (int r = tid; r < 2 * nb; r += NT) hist_s[r] = 0;
+    if (tid < T) thr_s[tid] = P.thr[(int64_t)tid * D + dg];
+    double W;
+    const int n_live = bs_history_weights(P.logw, b, N, tid, lw_s, w_s, live_s, W);   // two barriers: hist_s and thr_s are set behind them
+    const bool unscored = n_live < 0;
+    if (patch == 0 && dg == 0 && ck == 0 && tid == 0) P.status[b] = n_live;
+    if (ck == 0 && (P.prob != nullptr || P.brier != nullptr)) {   // the columns no tile walks (all of them when the history is not scored or the patch has no valid column): 0
+        const int c0 = (unscored || tpf == 0) ? 0 : tpf * DM_TC;
+        for (int64_t c = c0 + tid; c < ld; c += NT) {
+            const int64_t at = obase + c;
+            for (int t = 0; t < T; ++t) {
+                if (P.prob != nullptr) P.prob[t * P.ld_map + at] = 0.f;
+                if (P.brier != nullptr) P.brier[t * P.ld_map + at] = 0.f;
+            }
+        }
+    }
+    if (unscored || te <= tb) {   // uniform: nothing to score in this chunk
+        for (int e = tid; e < words; e += NT) wsum[e] = 0.0;   // the sums, and the int32 bins: all bits zero
+        return;
+    }
+
+    const int j0 = wave * 16;
+    const bool active = j0 < N;                 // uniform over the wave
+    const int jm = j0 + li;
+    const int64_t m = ((int64_t)b * N + (jm < N ? jm : 0)) * P.P + patch;
+    double acc_sum = 0.0;                       // threads 0 .. 5 T - 1: the derived field's running sums
+
+    const SeaDerivedField& X = L.t.d[dg];
+    const SeaDecodeMseGroup& G = L.g[L.t.gsel[dg]];   // the group that holds both sources
+    const int ja = X.a - G.field0, jb = X.b - G.field0;   // the sources inside their group
+    const __bf16* H = static_cast<const __bf16*>(G.H);
+    const __bf16* W2 = static_cast<const __bf16*>(G.W2);
+    uint4 hf[KS];
+    mq_load_row<SP>(hf, H + m * G.ldh, S, lg);
+    const int n_tiles = te - tb, t0a = ja * tpf + tb, t0b = jb * tpf + tb;   // this chunk's tiles among the group's, per source
+    uint4 wa[NCH], wb[NCH];
+    dm_load_tile<SP, NT>(wa, W2, G.ldw, S, Cp, tpf, t0a, tid);
+    dm_load_tile<SP, NT>(wb, W2, G.ldw, S, Cp, tpf, t0b, tid);
+    dm_store_tile<SP, NT>(wa, smem, tid);
+    dm_store_tile<SP, NT>(wb, smem + TILE, tid);
+    __syncthreads();
+
+    for (int t = 0; t < n_tiles; ++t) {
+        const int cb = (tb + t) * DM_TC;
+
+        // a: the columns' weights and readings (decode_member_brier_kernel's, by derived field); decode both sources into the value image
+        if (tid < DM_TC) {
+            const int c = cb + tid;
+            float w = 0.f;
+            if (c < lim) {
+                const float pf = P.prec_field != nullptr ? P.prec_field[dg] : 1.f;
+                const float pm = P.prec != nullptr ? P.prec[(int64_t)bp * P.ld_prow + (int64_t)dg * P.ld_pfield + c] : 1.f;
+                w = mul1(pf > 0.f ? pf : 0.f, pm > 0.f ? pm : 0.f);
+            }
+            const bool on = w > 0.f;   // false for NaN
+            pv_s[tid] = on ? w : 0.f;
+            y_s[tid] = on ? P.obs[(int64_t)bp * P.ld_row + (int64_t)dg * P.ld_field + c] : 0.f;
+        }
+        if (active) mq_decode_pair_tile<SP>(hf, smem, smem + TILE, G.bias + ja * Cp + cb, G.bias + jb * Cp + cb, S, li, lg, X, Vs + j0);
+        __syncthreads();
+        if (t + 1 < n_tiles) {   // in flight behind b
+            dm_load_tile<SP, NT>(wa, W2, G.ldw, S, Cp, tpf, t0a + t + 1, tid);
+            dm_load_tile<SP, NT>(wb, W2, G.ldw, S, Cp, tpf, t0b + t + 1, tid);
+        }
+
+        // b: a column per wave at a time
+        for (int cl = wave; cl < DM_TC; cl += NW) {
+            const float pv = pv_s[cl];
+            if (!(pv > 0.f)) {   // the same word in every lane
+                if (lane == 0) cell_s[cl].state = 1;
+                continue;
+            }
+            bs_column_wave<V>(Vs + cl * VP, w_s, live_s, N, lane, W, y_s[cl], pv, thr_s, T, &cell_s[cl]);
+        }
+        __syncthreads();
+
+        // c: thread (k, q) finishes threshold q of column k
+        if (tid < DM_TC * T) {
+            const int k = tid & (DM_TC - 1), q = tid / DM_TC;
+            double tm[BS_SUMS];
+            const BsOut o = bs_finish_cell(cell_s[k], q, y_s[k], thr_s[q], tm);
+            if (o.m >= 0) {   // LDS, integers: the order does not matter; 0 <= m <= N
+                atomicAdd(&hist_s[q * (N + 1) + o.m], 1);
+                if (o.o) atomicAdd(&hist_s[nb + q * (N + 1) + o.m], 1);
+            }
+            const int c = cb + k;
+            if (c < ld) {
+                const int64_t at = q * P.ld_map + obase + c;
+                if (P.prob != nullptr) P.prob[at] = o.prob;
+                if (P.brier != nullptr) P.brier[at] = o.brier;
+            }
+#pragma unroll
+            for (int i = 0; i < BS_SUMS; ++i) term_s[q * BS_SUMS + i][k] = tm[i];
+        }
+        if (t + 1 < n_tiles) {
+            dm_store_tile<SP, NT>(wa, smem, tid);
+            dm_store_tile<SP, NT>(wb, smem + TILE, tid);
+        }
+        __syncthreads();
+
+        // d: the derived field's sums, columns ascending (the next tile's terms are filed two barriers ahead)
+        if (tid < T * BS_SUMS)
+            for (int k = 0; k < DM_TC; ++k) acc_sum += term_s[tid][k];
+    }
+    if (tid < T * BS_SUMS) wsum[tid] = acc_sum;
+    for (int r = tid; r < 2 * nb; r += NT) whist[r] = hist_s[r];   // every integer add lies behind the last tile's barrier
+}
+
+template <int SP, int V>
+static void derived_quantiles_launch(const DerivedQuantLaunch& L, dim3 grid, hipStream_t s) {
+    constexpr int lds = mv_lds_bytes<SP>();
+    static bool set_on[64] = {false};   // per device: the dynamic part is 100 kB at SP = 640, above the 64 kB a kernel gets without the attribute
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = -1;
+    if (dev < 0 || !set_on[dev]) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(decode_derived_quantiles_kernel<SP, V>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        if (dev >= 0) set_on[dev] = true;
+    }
+    decode_derived_quantiles_kernel<SP, V><<<grid, dim3(MV_NT), lds, s>>>(L);
+    sea_note_form("decode.derived_quantiles", SP, lds);
+}
+
+template <int V>
+static void derived_quantiles_dispatch(const DerivedQuantLaunch& L, dim3 grid, hipStream_t s) {
+    if (L.p.S <= 128) derived_quantiles_launch<128, V>(L, grid, s);
+    else if (L.p.S <= 256) derived_quantiles_launch<256, V>(L, grid, s);
+    else if (L.p.S <= 384) derived_quantiles_launch<384, V>(L, grid, s);
+    else if (L.p.S <= 512) derived_quantiles_launch<512, V>(L, grid, s);
+    else derived_quantiles_launch<640, V>(L, grid, s);
+}
+
+template <int SP, int V>
+static void derived_brier_launch(const DerivedBrierLaunch& L, dim3 grid, hipStream_t s) {
+    constexpr int lds = mv_lds_bytes<SP>();
+    static bool set_on[64] = {false};   // per device, as above
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = -1;
+    if (dev < 0 || !set_on[dev]) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(decode_derived_brier_kernel<SP, V>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        if (dev >= 0) set_on[dev] = true;
+    }
+    decode_derived_brier_kernel<SP, V><<<grid, dim3(MV_NT), lds, s>>>(L);
+    sea_note_form("decode.derived_brier", SP, lds);
+}
+
+template <int V>
+static void derived_brier_dispatch(const DerivedBrierLaunch& L, dim3 grid, hipStream_t s) {
+    if (L.p.S <= 128) derived_brier_launch<128, V>(L, grid, s);
+    else if (L.p.S <= 256) derived_brier_launch<256, V>(L, grid, s);
+    else if (L.p.S <= 384) derived_brier_launch<384, V>(L, grid, s);
+    else if (L.p.S <= 512) derived_brier_launch<512, V>(L, grid, s);
+    else derived_brier_launch<640, V>(L, grid, s);
+}
+
+// The checks the two derived entry points share, under the entry point's name `who`: the sizes, the groups (the member entry points' checks) and the
+// derived table.  SEA_OK, or SEA_EINVAL with the message set.
+static int derived_check(const char* who, const SeaDecodeMseGroup* groups, int n_groups, const SeaDerivedField* derived, int n_derived, int M, int S, int C, int Cp, int Pn,
+                         int members, int n_fields_total) {
+    SEA_REQUIRE(M >= 1, "%s: M=%d must be positive", who, M);
+    SEA_REQUIRE(S >= 8 && S % 8 == 0, "%s: S=%d must be a positive multiple of 8", who, S);
+    SEA_REQUIRE(Cp >= 32 && Cp % 32 == 0, "%s: Cp=%d must be a positive multiple of 32", who, Cp);
+    SEA_REQUIRE(C >= 1 && C <= Cp, "%s: C=%d must lie in 1..Cp=%d", who, C, Cp);
+    SEA_REQUIRE(Pn >= 1, "%s: P=%d must be positive", who, Pn);
+    SEA_REQUIRE(members >= 1, "%s: members=%d must be positive", who, members);
+    SEA_REQUIRE((int64_t)M % ((int64_t)Pn * members) == 0, "%s: M=%d is not a multiple of P * members = %d * %d", who, M, Pn, members);
+    SEA_REQUIRE(n_fields_total >= 1 && n_fields_total <= 65535, "%s: n_fields_total=%d outside 1..65535", who, n_fields_total);
+    const int64_t BP = (int64_t)M / members, B = BP / Pn;
+    SEA_REQUIRE(BP <= 0x7fffffffLL && B <= 65535, "%s: %lld histories; a launch carries up to 65535", who, (long long)B);
+    int64_t covered = 0;
+    for (int g = 0; g < n_groups; ++g) {
+        const SeaDecodeMseGroup& G = groups[g];
+        SEA_REQUIRE(G.H != nullptr && G.W2 != nullptr && G.bias != nullptr, "%s: group %d: null pointer", who, g);
+        SEA_REQUIRE(sea_aligned16(G.H) && sea_aligned16(G.W2) && sea_aligned16(G.bias), "%s: group %d: pointers must be 16-byte aligned", who, g);
+        SEA_REQUIRE(G.ldh >= S && G.ldh % 8 == 0 && G.ldw >= S && G.ldw % 8 == 0, "%s: group %d: row strides ldh=%d ldw=%d must cover S=%d and be multiples of 8", who, g,
+                    G.ldh, G.ldw, S);
+        SEA_REQUIRE(G.n_fields >= 1 && G.field0 >= 0 && (int64_t)G.field0 + G.n_fields <= n_fields_total, "%s: group %d: n_fields=%d, field0=%d outside the %d fields", who, g,
+                    G.n_fields, G.field0, n_fields_total);
+        SEA_REQUIRE((int64_t)G.n_fields * Cp <= 0x7fffffffLL / 2, "%s: group %d: too many output columns", who, g);
+        for (int h = 0; h < g; ++h)
+            SEA_REQUIRE(G.field0 >= groups[h].field0 + groups[h].n_fields || groups[h].field0 >= G.field0 + G.n_fields,
+                        "%s: group %d: its fields overlap those of group %d (a cell is decoded once)", who, g, h);
+        covered += G.n_fields;
+    }
+    SEA_REQUIRE(covered == n_fields_total, "%s: the groups cover %lld of the %d fields (every field needs exactly one group)", who, (long long)covered, n_fields_total);
+    for (int i = 0; i < n_derived; ++i) {
+        const SeaDerivedField& X = derived[i];
+        SEA_REQUIRE(X.op == SEA_DERIVED_MAGNITUDE || X.op == SEA_DERIVED_ENERGY || X.op == SEA_DERIVED_DIFFERENCE,
+                    "%s: derived field %d: unknown op %d (SEA_DERIVED_MAGNITUDE, SEA_DERIVED_ENERGY or SEA_DERIVED_DIFFERENCE)", who, i, X.op);
+        SEA_REQUIRE(X.a >= 0 && X.a < n_fields_total && X.b >= 0 && X.b < n_fields_total, "%s: derived field %d: sources a=%d, b=%d outside the %d fields", who, i, X.a, X.b,
+                    n_fields_total);
+        SEA_REQUIRE(X.a != X.b, "%s: derived field %d: a == b = %d (two different source fields are needed)", who, i, X.a);
+        SEA_REQUIRE(std::isfinite(X.scale_a) && std::isfinite(X.shift_a) && std::isfinite(X.scale_b) && std::isfinite(X.shift_b),
+                    "%s: derived field %d: a coefficient is not finite (scale_a=%g shift_a=%g scale_b=%g shift_b=%g)", who, i, (double)X.scale_a, (double)X.shift_a,
+                    (double)X.scale_b, (double)X.shift_b);
+    }
+    return SEA_OK;
+}
+
+// What the fused launches do not carry (the caller composes): SEA_OK with the table filled, or SEA_EUNSUPPORTED with the message set.
+static int derived_resolve(const char* who, const SeaDecodeMseGroup* groups, int n_groups, const SeaDerivedField* derived, int n_derived, int S, int members, DerivedTable& t) {
+    if (S > 640) {
+        sea_set_error("%s: unsupported: hidden width S=%d above 640", who, S);
+        return SEA_EUNSUPPORTED;
+    }
+    if (members > VF_MAX_N) {
+        sea_set_error("%s: unsupported: members=%d above %d", who, members, VF_MAX_N);
+        return SEA_EUNSUPPORTED;
+    }
+    memset(&t, 0, sizeof(t));
+    t.n_derived = n_derived;
+    for (int i = 0; i < n_derived; ++i) {
+        int ga = -1, gb = -1;
+        for (int g = 0; g < n_groups; ++g) {
+            if (derived[i].a >= groups[g].field0 && derived[i].a < groups[g].field0 + groups[g].n_fields) ga = g;
+            if (derived[i].b >= groups[g].field0 && derived[i].b < groups[g].field0 + groups[g].n_fields) gb = g;
+        }
+        if (ga != gb) {
+            sea_set_error("%s: unsupported: derived field %d: its sources a=%d and b=%d lie in different groups (%d and %d)", who, i, derived[i].a, derived[i].b, ga, gb);
+            return SEA_EUNSUPPORTED;
+        }
+        t.d[i] = derived[i];
+        t.gsel[i] = ga;
+    }
+    return SEA_OK;
+}
+
+extern "C" int sea_decode_derived_quantiles(const SeaDecodeMseGroup* groups, int n_groups, const SeaDerivedField* derived, int n_derived,
+                                            const SeaDecodeMemberQuantiles* p, int dtype, void* stream) {
+    const char* who = "sea_decode_derived_quantiles";
+    SEA_REQUIRE(groups != nullptr && derived != nullptr && p != nullptr, "%s: null argument table", who);
+    SEA_REQUIRE(n_groups >= 1 && n_groups <= SEA_DECODE_MSE_MAX_GROUPS, "%s: n_groups=%d outside 1..%d", who, n_groups, SEA_DECODE_MSE_MAX_GROUPS);
+    SEA_REQUIRE(n_derived >= 1 && n_derived <= SEA_DERIVED_MAX, "%s: n_derived=%d outside 1..%d", who, n_derived, SEA_DERIVED_MAX);
+    SEA_REQUIRE(dtype == SEA_F32 || dtype == SEA_BF16, "%s: bad dtype %d", who, dtype);
+    if (dtype != SEA_BF16) {
+        sea_set_error("%s: unsupported: bf16 only (the fp32 decoder composes the decode, the derived values and a sort)", who);
+        return SEA_EUNSUPPORTED;
+    }
+    const SeaDecodeMemberQuantiles& P = *p;
+    SEA_REQUIRE(P.n_levels >= 0 && P.n_levels <= SEA_QUANTILE_MAX_LEVELS && P.n_thr >= 0 && P.n_thr <= SEA_QUANTILE_MAX_LEVELS && P.n_levels + P.n_thr >= 1,
+                "%s: n_levels=%d and n_thr=%d must lie in 0..%d and not both be 0", who, P.n_levels, P.n_thr, SEA_QUANTILE_MAX_LEVELS);
+    for (int k = 0; k < P.n_levels; ++k)
+        SEA_REQUIRE(P.level[k] >= 0.f && P.level[k] <= 1.f, "%s: level[%d]=%g must be finite and lie in [0, 1]", who, k, (double)P.level[k]);
+    SEA_REQUIRE((P.n_levels == 0 || P.quant != nullptr) && (P.n_thr == 0 || (P.thr != nullptr && P.exceed != nullptr)),
+                "%s: null pointer (quant is required with levels, thr and exceed with thresholds; w and counts may be NULL)", who);
+    const int rc = derived_check(who, groups, n_groups, derived, n_derived, P.M, P.S, P.C, P.Cp, P.P, P.members, P.n_fields_total);
+    if (rc != SEA_OK) return rc;
+    const int64_t BP = (int64_t)P.M / P.members;   // (history, patch) pairs
+    SEA_REQUIRE(P.ld >= P.C && P.ld <= 0x7fffffffLL && P.ld_map >= BP * n_derived * P.ld, "%s: ld=%lld must cover C=%d, and ld_map=%lld a whole map of %lld floats", who,
+                (long long)P.ld, P.C, (long long)P.ld_map, (long long)(BP * n_derived * P.ld));
+    SEA_REQUIRE(sea_aligned4(P.w) && sea_aligned4(P.counts) && sea_aligned4(P.thr) && sea_aligned4(P.quant) && sea_aligned4(P.exceed),
+                "%s: misaligned pointer (f32 and int32 buffers need 4 bytes)", who);
+    SEA_REQUIRE(mv_chunks(P.Cp) <= 65535, "%s: Cp=%d has too many column chunks", who, P.Cp);
+
+    DerivedQuantLaunch L;
+    memset(&L, 0, sizeof(L));
+    const int ru = derived_resolve(who, groups, n_groups, derived, n_derived, P.S, P.members, L.t);
+    if (ru != SEA_OK) return ru;
+    for (int g = 0; g < n_groups; ++g) L.g[g] = groups[g];
+    L.p = P;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)BP, (unsigned)n_derived, (unsigned)mv_chunks(P.Cp));
+    if (P.members <= 64) derived_quantiles_dispatch<1>(L, grid, s);
+    else derived_quantiles_dispatch<2>(L, grid, s);
+    SEA_CHECK_LAUNCH("sea_decode_derived_quantiles");
+    return SEA_OK;
+}
+
+extern "C" int sea_decode_derived_brier(const SeaDecodeMseGroup* groups, int n_groups, const SeaDerivedField* derived, int n_derived, const SeaDecodeMemberBrier* p,
+                                        int dtype, void* stream) {
+    const char* who = "sea_decode_derived_brier";
+    SEA_REQUIRE(groups != nullptr && derived != nullptr && p != nullptr, "%s: null argument table", who);
+    SEA_REQUIRE(n_groups >= 1 && n_groups <= SEA_DECODE_MSE_MAX_GROUPS, "%s: n_groups=%d outside 1..%d", who, n_groups, SEA_DECODE_MSE_MAX_GROUPS);
+    SEA_REQUIRE(n_derived >= 1 && n_derived <= SEA_DERIVED_MAX, "%s: n_derived=%d outside 1..%d", who, n_derived, SEA_DERIVED_MAX);
+    SEA_REQUIRE(dtype == SEA_F32 || dtype == SEA_BF16, "%s: bad dtype %d", who, dtype);
+    if (dtype != SEA_BF16) {
+        sea_set_error("%s: unsupported: bf16 only (the fp32 decoder composes the decode, the derived values and the formulas)", who);
+        return SEA_EUNSUPPORTED;
+    }
+    const SeaDecodeMemberBrier& P = *p;
+    SEA_REQUIRE(P.obs != nullptr && P.thr != nullptr && P.sums != nullptr && P.hist != nullptr && P.hits != nullptr && P.status != nullptr && P.work != nullptr,
+                "%s: null pointer (obs, thr, sums, hist, hits, status and work are required; prec_field, prec, counts, logw and the maps may be NULL)", who);
+    SEA_REQUIRE(P.n_thr >= 1 && P.n_thr <= BS_MAX_T, "%s: n_thr=%d outside 1..%d", who, P.n_thr, BS_MAX_T);
+    const int rc = derived_check(who, groups, n_groups, derived, n_derived, P.M, P.S, P.C, P.Cp, P.P, P.members, P.n_fields_total);
+    if (rc != SEA_OK) return rc;
+    SEA_REQUIRE(P.ld_field >= P.C && P.ld_row >= 0, "%s: obs strides ld_row=%lld, ld_field=%lld must cover C=%d", who, (long long)P.ld_row, (long long)P.ld_field, P.C);
+    SEA_REQUIRE(P.prec == nullptr || (P.ld_pfield >= P.C && P.ld_prow >= 0), "%s: prec strides ld_prow=%lld, ld_pfield=%lld must cover C=%d", who, (long long)P.ld_prow,
+                (long long)P.ld_pfield, P.C);
+    const int64_t BP = (int64_t)P.M / P.members;   // (history, patch) pairs
+    const int64_t B = BP / P.P;
+    SEA_REQUIRE((P.prob == nullptr && P.brier == nullptr) || (P.ld_out >= P.C && P.ld_out <= 0x7fffffffLL && P.ld_map >= BP * n_derived * P.ld_out),
+                "%s: ld_out=%lld must cover C=%d, and ld_map=%lld a whole map", who, (long long)P.ld_out, P.C, (long long)P.ld_map);
+    SEA_REQUIRE(P.accumulate == 0 || P.accumulate == 1, "%s: accumulate=%d must be 0 or 1", who, P.accumulate);
+    SEA_REQUIRE(sea_aligned4(P.obs) && sea_aligned4(P.prec_field) && sea_aligned4(P.prec) && sea_aligned4(P.counts) && sea_aligned4(P.logw) && sea_aligned4(P.thr) &&
+                    sea_aligned4(P.prob) && sea_aligned4(P.brier) && sea_aligned4(P.status) && (reinterpret_cast<uintptr_t>(P.sums) & 7u) == 0 &&
+                    (reinterpret_cast<uintptr_t>(P.hist) & 7u) == 0 && (reinterpret_cast<uintptr_t>(P.hits) & 7u) == 0 && (reinterpret_cast<uintptr_t>(P.work) & 7u) == 0,
+                "%s: misaligned pointer (f32 and int32 buffers need 4 bytes; sums, hist, hits and work 8)", who);
+
+    DerivedBrierLaunch L;
+    memset(&L, 0, sizeof(L));
+    const int ru = derived_resolve(who, groups, n_groups, derived, n_derived, P.S, P.members, L.t);
+    if (ru != SEA_OK) return ru;
+    const int64_t need = sea_decode_member_brier_ws_bytes((int)B, P.P, n_derived, P.members, P.Cp, P.n_thr);
+    SEA_REQUIRE(P.work_bytes >= need, "%s: work_bytes=%lld below the %lld that sea_decode_member_brier_ws_bytes(B=%d, P=%d, n_derived=%d, members=%d, Cp=%d, n_thr=%d) asks for",
+                who, (long long)P.work_bytes, (long long)need, (int)B, P.P, n_derived, P.members, P.Cp, P.n_thr);
+    SEA_REQUIRE((int64_t)P.P * mv_chunks(P.Cp) <= 0x7fffffffLL && mv_chunks(P.Cp) <= 65535, "%s: Cp=%d has too many column chunks", who, P.Cp);
+
+    for (int g = 0; g < n_groups; ++g) L.g[g] = groups[g];
+    L.p = P;
+    L.words = (int)bs_words(P.n_thr, P.members);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)BP, (unsigned)n_derived, (unsigned)mv_chunks(P.Cp));
+    if (P.members <= 64) derived_brier_dispatch<1>(L, grid, s);
+    else derived_brier_dispatch<2>(L, grid, s);
+    SeaDecodeMemberBrier Pd = P;   // the finish launch reads its partials by derived field
+    Pd.n_fields_total = n_derived;
+    member_brier_finish_kernel<<<dim3((unsigned)B, (unsigned)(n_derived * P.n_thr)), dim3(256), 0, s>>>(Pd, mv_chunks(P.Cp), L.words);
+    SEA_CHECK_LAUNCH("sea_decode_derived_brier");
+    return SEA_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------------------------
 // sea_decode_member_crps_grad: the CRPS of the decoded fields per (history, field) WITH its gradient to the hidden rows (include/sea_hip.h states
 // the formulas) — decode_member_verify_kernel crossed with stage 2 of decode_mse_kernel.  Launch 1 keeps member_verify's grid, a workgroup per
 // (history, patch, field, chunk of MV_CHUNK tiles), and its decode, weights, walk and sums line for line (no maps, no histogram): the fp64 sums

@@ -2007,3 +2007,324 @@ class EnsembleCRPSLoss(torch.nn.Module):
         loss, count = self.decoder.member_crps_loss(z, tgt, n, counts=self.counts, precision=prec, field_weight=self._field_weight_on(output.device), logw=lw,
                                                     unbiased=self.unbiased, fused=self.fused, **kw)
         return loss.sum() / count.sum().clamp_min(1.0).to(loss.dtype)
+
+
+# ------------------------------------------------------------------------------------------------ derived fields: |u|, energy, differences
+DERIVED_OPS = ("magnitude", "energy", "difference")
+DERIVED_FUSED_MIN_ROWS = 4096   # fused=None: the fused launches from this many decoder rows (B * members * n_patches) on — the smallest measured size
+
+
+class DerivedField:
+    """A derived field of two decoded fields, formed per member and cell in float32 with every operation rounded once (include/sea_hip.h,
+    sea_decode_derived_quantiles):  a' = y_a * scale_a + shift_a,  b' = y_b * scale_b + shift_b,  then
+        "magnitude"   sqrt(a' a' + b' b')       the speed |u| of two velocity components (a correctly rounded root)
+        "energy"      0.5 (a' a' + b' b')
+        "difference"  a' - b'
+    a != b index the decoder's fields in output order; scale and shift carry the mesh's inverse scaling so that the value is in PHYSICAL units
+    (MeshUnpatcher.derived_fields builds them: a magnitude of min-max-scaled components means nothing).  Immutable; validated here, on the host."""
+    __slots__ = ("op", "a", "b", "scale_a", "shift_a", "scale_b", "shift_b", "name")
+
+    def __init__(self, op: str, a: int, b: int, scale_a: float = 1.0, shift_a: float = 0.0, scale_b: float = 1.0, shift_b: float = 0.0, name: Optional[str] = None):
+        if op not in DERIVED_OPS:
+            raise ValueError(f"DerivedField: op must be one of {DERIVED_OPS}, got {op!r}")
+        for k, v in (("a", a), ("b", b)):
+            if not isinstance(v, int) or isinstance(v, bool) or v < 0:
+                raise ValueError(f"DerivedField: {k} = {v!r} must be a field index >= 0")
+        if a == b:
+            raise ValueError(f"DerivedField: a == b = {a}: two different source fields are needed")
+        coeff = []
+        for k, v in (("scale_a", scale_a), ("shift_a", shift_a), ("scale_b", scale_b), ("shift_b", shift_b)):
+            try:
+                v = float(v)
+            except (TypeError, ValueError):
+                raise ValueError(f"DerivedField: {k} = {v!r} must be a number") from None
+            v32 = float(torch.tensor(v, dtype=torch.float32))   # the float32 the launch carries
+            if not math.isfinite(v32):
+                raise ValueError(f"DerivedField: {k} = {v!r} must be finite in float32")
+            coeff.append(v32)
+        for k, v in zip(self.__slots__, (op, a, b, *coeff, f"{op}({a},{b})" if name is None else str(name))):
+            object.__setattr__(self, k, v)
+
+    def __setattr__(self, k, v):
+        raise AttributeError("DerivedField is immutable")
+
+    def __repr__(self):
+        return (f"DerivedField({self.op!r}, {self.a}, {self.b}, scale_a={self.scale_a}, shift_a={self.shift_a}, scale_b={self.scale_b}, shift_b={self.shift_b}, "
+                f"name={self.name!r})")
+
+    def _key(self):
+        return tuple(getattr(self, k) for k in self.__slots__)
+
+    def __eq__(self, other):
+        return isinstance(other, DerivedField) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+
+def _check_derived(what: str, derived, n_fields: int) -> tuple:
+    """derived as a tuple of DerivedField whose sources lie in 0 .. n_fields - 1 (ValueError otherwise)."""
+    try:
+        derived = tuple(derived)
+    except TypeError:
+        raise ValueError(f"{what}: derived must be a sequence of DerivedField, got {type(derived).__name__}") from None
+    if not derived or any(not isinstance(d, DerivedField) for d in derived):
+        raise ValueError(f"{what}: derived must be a non-empty sequence of DerivedField, got {derived!r}")
+    for i, d in enumerate(derived):
+        if d.a >= n_fields or d.b >= n_fields:
+            raise ValueError(f"{what}: derived field {i} ({d.name}): sources a = {d.a}, b = {d.b} outside the {n_fields} fields")
+    return derived
+
+
+def _composed_derived(Y, derived):
+    """The derived fields of decoded members as separate float32 torch ops in the stated order — the composed path and the restatement's front end
+    (include/sea_hip.h, sea_decode_derived_quantiles): Y [..., F, C] (members' decoded fields [B, members, P, F, C], or an observation [B, P, F, C];
+    any float dtype, converted to float32 first; CPU or device) -> float32 [..., n_derived, C].  Every product and sum is ONE float32 torch op: nothing
+    is fused and nothing reassociated.  The root is the float64 root rounded once to float32 — the correctly rounded float32 root (a float64 root is
+    never close enough to the middle of two float32 values for the second rounding to matter); torch.sqrt on float32 tensors is NOT always that (its
+    CPU form differs from numpy's float32 root by one unit in the last place in about 0.7 % of random arguments)."""
+    y = Y.to(torch.float32)
+    out = []
+    for d in derived:
+        a = y.select(-2, d.a) * d.scale_a + d.shift_a      # python floats that are float32 values: one multiply, one add
+        b = y.select(-2, d.b) * d.scale_b + d.shift_b
+        if d.op == "difference":
+            out.append(a - b)
+            continue
+        q = a * a + b * b
+        out.append(q * 0.5 if d.op == "energy" else torch.sqrt(q.to(torch.float64)).to(torch.float32))
+    return torch.stack(out, dim=-2)
+
+
+def _derived_thresholds(what: str, thresholds, nd: int, max_t: int, finite: bool) -> torch.Tensor:
+    """thresholds — numbers or a tensor, [T] (the same for every derived field) or [T, n_derived], 1 <= T <= max_t — as a contiguous float32 [T, n_derived]
+    tensor on the host."""
+    try:
+        t = thresholds.detach().cpu() if torch.is_tensor(thresholds) else torch.as_tensor(thresholds, dtype=torch.float32)
+    except (TypeError, ValueError, RuntimeError):
+        raise ValueError(f"{what}: thresholds must be [T] or [T, {nd}] numbers, got {thresholds!r}") from None
+    if t.dim() not in (1, 2) or not 1 <= t.shape[0] <= max_t or (t.dim() == 2 and t.shape[1] != nd) or not t.is_floating_point():
+        raise ValueError(f"{what}: thresholds must be [T] or [T, {nd}] floating-point numbers (one column per derived field) with 1 <= T <= {max_t}, got shape "
+                         f"{tuple(t.shape)} {t.dtype}")
+    t = (t.view(-1, 1).expand(t.shape[0], nd) if t.dim() == 1 else t).to(torch.float32).contiguous()
+    if finite and not bool(torch.isfinite(t).all()):
+        raise ValueError(f"{what}: every threshold must be finite")
+    return t
+
+
+class _DerivedBase:
+    """What DerivedQuantiles and DerivedThresholdVerification share: the constructor's checks, the thresholds per device and the default rule."""
+    _what = "Derived"
+
+    def _init_common(self, decoder, n_patches, members, derived, counts, layout, fused, max_n: int):
+        what = self._what
+        if layout not in ("BPFC", "BPCF"):
+            raise ValueError(f"{what}: layout must be 'BPFC' or 'BPCF', got {layout!r}")
+        if not isinstance(n_patches, int) or isinstance(n_patches, bool) or n_patches < 1:
+            raise ValueError(f"{what}: n_patches = {n_patches!r} must be a positive integer")
+        if not isinstance(members, int) or isinstance(members, bool) or members < 1:
+            raise ValueError(f"{what}: members = {members!r} must be a positive integer")
+        if fused is not None and not isinstance(fused, bool):
+            raise ValueError(f"{what}: fused = {fused!r} must be None, True or False")
+        if fused and members > max_n:
+            raise ValueError(f"{what}: the fused launches carry up to {max_n} members, got {members} (fused=False, or None)")
+        self.n_fields = sum(len(g) for g in decoder.field_groups)
+        self.derived = _check_derived(what, derived, self.n_fields)
+        if fused and len(self.derived) > N.DERIVED_MAX:
+            raise ValueError(f"{what}: the fused launches carry up to {N.DERIVED_MAX} derived fields, got {len(self.derived)} (fused=False, or None)")
+        self._thr = {}
+        self.decoder, self.n_patches, self.members, self.counts, self.layout, self.fused = decoder, n_patches, members, counts, layout, fused
+
+    def _thresholds_on(self, device):
+        """The thresholds f32 [T, n_derived] on the device (None without): moved there once per device."""
+        if self._thr_src is None:
+            return None
+        t = self._thr.get(device)
+        if t is None:
+            t = self._thr[device] = self._thr_src.to(device)
+        return t
+
+    def _states(self, y):
+        """y [B * members, n_groups, n_patches * D] checked -> (z [Bm, P, G, D], Bm): the re-layout of FieldLikelihood."""
+        P, what = self.n_patches, self._what
+        if not torch.is_tensor(y) or y.dim() != 3 or y.shape[-1] % P or y.shape[0] < 1:
+            raise ValueError(f"{what}: y must be [B * members, n_groups, n_patches * D] with n_patches = {P}, got "
+                             f"{tuple(y.shape) if torch.is_tensor(y) else type(y).__name__}")
+        Bm, G, E = y.shape
+        if Bm % self.members:
+            raise ValueError(f"{what}: the {Bm} trajectories of y are not a multiple of members = {self.members}")
+        return y.detach().reshape(Bm, G, P, E // P).permute(0, 2, 1, 3), Bm
+
+    def _valid(self, P: int, C_: int, device):
+        """The valid-cell mask [1, P, 1, C] from counts (None: every cell)."""
+        if self.counts is None:
+            return None
+        cnt = torch.as_tensor(self.counts, dtype=torch.int64).to(device).clamp(0, C_)
+        return (torch.arange(C_, device=device) < cnt[:, None]).view(1, P, 1, C_)
+
+
+class DerivedQuantiles(_DerivedBase):
+    """EnsembleQuantiles for DERIVED fields — "the 5 % / 95 % band of the speed", "P(speed > 1.2 U) here": quantiles(y, logw=None) -> (quant float32
+    [Q, B, P, n_derived, n_inp], exceed float32 [T, B, P, n_derived, n_inp]).  A quantile of |u| is not a function of the quantiles of u and v: the derived
+    value is formed per member (DerivedField; include/sea_hip.h, sea_decode_derived_quantiles) and the maps are read out of those values exactly as
+    EnsembleQuantiles reads its maps out of a decoded field: each quantile is the derived value of one member, exceedance is strict.
+
+    derived: a sequence of DerivedField (MeshUnpatcher.derived_fields builds them with the mesh's inverse scaling, so the values, the quantile maps and the
+    thresholds are in PHYSICAL units); thresholds: None, [T] (the same for every derived field) or [T, n_derived], T <= 8, in the derived fields' own units.
+    y, logw, counts, layout, levels and the conventions for dead members, invalid cells (0) and non-finite values (NaN) are EnsembleQuantiles'; the maps go
+    to the mesh with MeshUnpatcher.unpatch_derived (they are in physical units already).
+    fused: True — the decoder's first layer plus the ONE launch of sea_decode_derived_quantiles (bf16, up to 128 members, up to 8 derived fields whose two
+    sources share a decoder group): neither the members' decoded fields nor the derived fields are written; raises where the launch refuses.  False —
+    Decode.forward plus _composed_derived plus _composed_quantiles (the composed path: fp32, any member count, sources in different groups).  None — the
+    fused launch where it serves, from 4096 decoder rows (B * members * n_patches) on — the measured rows (tools/derived_fields_bench.py,
+    profiles/derived_fields_bench.txt) — and the composed path everywhere else, and wherever nothing was measured.
+    from_fields(Y, logw=None) runs the composed arithmetic on members' decoded fields [B, members, P, F, n_inp] that already exist (CPU or device).
+    A call reads nothing back from the device.  `decoder` is a sea_amd Decode; no autograd graph is built."""
+    _what = "DerivedQuantiles"
+
+    def __init__(self, decoder, n_patches: int, members: int, derived, levels=(0.05, 0.5, 0.95), thresholds=None, counts=None, layout: str = "BPFC",
+                 fused: Optional[bool] = None):
+        from . import ops
+
+        self._init_common(decoder, n_patches, members, derived, counts, layout, fused, N.QUANTILE_MAX_N)
+        self.levels = ops.check_quantile_levels(() if levels is None else levels, self._what)
+        self._thr_src = None if thresholds is None else _derived_thresholds(self._what, thresholds, len(self.derived), N.QUANTILE_MAX_LEVELS, finite=False)
+        if not self.levels and self._thr_src is None:
+            raise ValueError(f"{self._what}: neither levels nor thresholds: there is nothing to compute")
+
+    def _weights(self, logw, Bm: int, device):
+        if logw is None:
+            return None
+        if not torch.is_tensor(logw) or not logw.is_floating_point() or logw.numel() != Bm or logw.dim() not in (1, 2) \
+                or (logw.dim() == 2 and logw.shape[1] != self.members):
+            raise ValueError(f"{self._what}: logw must be None or a floating-point [{Bm}] (or [{Bm // self.members}, {self.members}]) tensor of log-weights, got "
+                             f"{tuple(logw.shape) if torch.is_tensor(logw) else type(logw).__name__}")
+        if logw.device != device:
+            raise ValueError(f"{self._what}: logw is on {logw.device}, the states on {device}")
+        return normalised_weights(logw, self.members)
+
+    def _permuted(self, quant, exceed, layout):
+        layout = self.layout if layout is None else layout
+        if layout not in ("BPFC", "BPCF"):
+            raise ValueError(f"{self._what}: layout must be 'BPFC' or 'BPCF', got {layout!r}")
+        if layout == "BPCF":
+            quant = None if quant is None else quant.permute(0, 1, 2, 4, 3)
+            exceed = None if exceed is None else exceed.permute(0, 1, 2, 4, 3)
+        return quant, exceed
+
+    def from_fields(self, Y: torch.Tensor, logw: Optional[torch.Tensor] = None, layout: Optional[str] = None):
+        """The composed path on members' decoded fields Y [B, members, P, n_fields, n_inp] (scaled units, any float dtype, CPU or device)."""
+        if not torch.is_tensor(Y) or Y.dim() != 5 or Y.shape[1] != self.members or Y.shape[2] != self.n_patches or Y.shape[3] != self.n_fields:
+            raise ValueError(f"{self._what}: Y must be [B, {self.members}, {self.n_patches}, {self.n_fields}, n_inp], got "
+                             f"{tuple(Y.shape) if torch.is_tensor(Y) else type(Y).__name__}")
+        B, n, P, _, C_ = Y.shape
+        with torch.no_grad():
+            w = self._weights(logw, B * n, Y.device)
+            q, e = _composed_quantiles(_composed_derived(Y.detach(), self.derived), None if w is None else w.view(B, n), self.levels, self._thresholds_on(Y.device))
+            valid = self._valid(P, C_, Y.device)
+            if valid is not None:
+                zero = torch.zeros((), device=Y.device, dtype=torch.float32)
+                q = None if q is None else torch.where(valid.unsqueeze(0), q, zero)
+                e = None if e is None else torch.where(valid.unsqueeze(0), e, zero)
+        return self._permuted(q, e, layout)
+
+    def __call__(self, y: torch.Tensor, logw: Optional[torch.Tensor] = None, layout: Optional[str] = None):
+        self._permuted(None, None, layout)
+        z, Bm = self._states(y)
+        w = self._weights(logw, Bm, y.device)
+        N.require_gpu(y, f"{self._what} states")
+        with torch.no_grad():
+            quant, exceed = self.decoder.member_derived_quantiles(z, self.members, self.derived, levels=self.levels, thresholds=self._thresholds_on(y.device),
+                                                                  weights=w, counts=self.counts, fused=self.fused)
+        return self._permuted(quant, exceed, layout)
+
+    quantiles = __call__
+
+
+class DerivedThresholdVerification(_DerivedBase):
+    """FieldThresholdVerification for DERIVED fields — is "P(speed > 1.2 U)" any good: verify(y, obs, precision=None, logw=None, into=None, maps=()) ->
+    ThresholdScores with n_derived where that class has n_fields (include/sea_hip.h, sea_decode_derived_brier).  derived and thresholds ([T] or
+    [T, n_derived], finite, in the derived fields' own units) as in DerivedQuantiles.
+    observed="fields": obs (and precision) is the snapshot of the SOURCE fields that FieldThresholdVerification takes — [B, P, n_fields, >= n_inp] in layout
+    "BPFC", scaled units; the observed derived values are formed from it with _composed_derived's arithmetic, on the device, and a derived cell is live
+    only where both of its source cells are (precision > 0 in both).  observed="derived": obs and precision are [B, P, n_derived, >= n_inp] readings of the
+    derived quantities themselves (a PIV speed map), in their own units.  The precision only decides which cells are read.
+    fused as in DerivedQuantiles (True: the first layer plus the two launches of sea_decode_derived_brier; None: from 4096 decoder rows on where the launch
+    serves, the composed path elsewhere).  from_fields(Y, obs, ...) runs the composed arithmetic on members' decoded fields [B, members, P, F, n_inp] that
+    already exist (CPU or device).  Nothing is read back.  `decoder` is a sea_amd Decode; no autograd graph is built."""
+    _what = "DerivedThresholdVerification"
+
+    def __init__(self, decoder, n_patches: int, members: int, derived, thresholds, counts=None, layout: str = "BPFC", observed: str = "fields",
+                 fused: Optional[bool] = None):
+        if observed not in ("fields", "derived"):
+            raise ValueError(f"{self._what}: observed must be 'fields' or 'derived', got {observed!r}")
+        self._init_common(decoder, n_patches, members, derived, counts, layout, fused, N.BRIER_MAX_N)
+        self.thresholds = self._thr_src = _derived_thresholds(self._what, thresholds, len(self.derived), N.BRIER_MAX_T, finite=True)
+        self.observed = observed
+
+    def _observation(self, obs, precision, B: int, device):
+        """obs and precision checked and brought to derived readings: (obs [B, P, n_derived, W], precision [B, P, n_derived, W] or None)."""
+        what, P, nd = self._what, self.n_patches, len(self.derived)
+        width = self.n_fields if self.observed == "fields" else nd
+        if not torch.is_tensor(obs) or obs.dim() != 4 or tuple(obs.shape[:2]) != (B, P):
+            raise ValueError(f"{what}: the observation must be [{B}, {P}, ...] in layout {self.layout} (one snapshot per history), got "
+                             f"{tuple(obs.shape) if torch.is_tensor(obs) else type(obs).__name__}")
+        if obs.dtype != torch.float32 or obs.device != device:
+            raise ValueError(f"{what}: obs must be float32 on {device}, got {obs.dtype} on {obs.device}")
+        if precision is not None:
+            if not torch.is_tensor(precision) or tuple(precision.shape) != tuple(obs.shape):
+                raise ValueError(f"{what}: precision must be None or a map of obs's shape {tuple(obs.shape)}, got "
+                                 f"{tuple(precision.shape) if torch.is_tensor(precision) else type(precision).__name__}")
+            if precision.dtype != torch.float32 or precision.device != device:
+                raise ValueError(f"{what}: precision must be float32 on {device}, got {precision.dtype} on {precision.device}")
+            if precision.device.type == "cpu" and (not bool(torch.isfinite(precision).all()) or not bool((precision >= 0).all())):
+                raise ValueError(f"{what}: precision must be finite and >= 0")
+        perm = (lambda t: t) if self.layout == "BPFC" else (lambda t: t.permute(0, 1, 3, 2))
+        obs, precision = perm(obs.detach()), None if precision is None else perm(precision.detach())
+        if obs.shape[2] != width:
+            raise ValueError(f"{what}: observed={self.observed!r}: the observation must carry {width} fields in layout {self.layout}, got shape {tuple(obs.shape)}")
+        if self.observed == "derived":
+            return obs, precision
+        with torch.no_grad():
+            x = _composed_derived(obs, self.derived)
+            if precision is not None:   # live where both source cells are: the product of two 0 / 1 flags
+                on = (precision > 0).to(torch.float32)
+                precision = torch.stack([on.select(2, d.a) * on.select(2, d.b) for d in self.derived], dim=2)
+        return x, precision
+
+    def from_fields(self, Y: torch.Tensor, obs: torch.Tensor, precision: Optional[torch.Tensor] = None, logw: Optional[torch.Tensor] = None,
+                    into: Optional["ThresholdScores"] = None, maps=()) -> "ThresholdScores":
+        """The composed path on members' decoded fields Y [B, members, P, n_fields, n_inp] (scaled units, any float dtype, CPU or device)."""
+        if not torch.is_tensor(Y) or Y.dim() != 5 or Y.shape[1] != self.members or Y.shape[2] != self.n_patches or Y.shape[3] != self.n_fields:
+            raise ValueError(f"{self._what}: Y must be [B, {self.members}, {self.n_patches}, {self.n_fields}, n_inp], got "
+                             f"{tuple(Y.shape) if torch.is_tensor(Y) else type(Y).__name__}")
+        B, n, P, _, C_ = Y.shape
+        nd, T = len(self.derived), self.thresholds.shape[0]
+        x_obs, prec = self._observation(obs, precision, B, Y.device)
+        maps, logw = _check_brier_call(self._what, maps, logw, into, (B, nd, T), B * n, n, Y.device)
+        thr = self._thresholds_on(Y.device)
+        with torch.no_grad():
+            cnt = None if self.counts is None else torch.as_tensor(self.counts, dtype=torch.int64).to(Y.device)
+            w = _field_cell_weights((B, P, nd, C_), None, prec, cnt, Y.device)
+            r = _composed_field_brier(_composed_derived(Y.detach(), self.derived).view(B * n, P, nd, C_), x_obs, w, logw, n, thr, maps=maps)
+            if into is not None:
+                r["sums"], r["hist"], r["hits"] = into.sums.add_(r["sums"]), into.hist.add_(r["hist"]), into.hits.add_(r["hits"])
+        return ThresholdScores(prob=r.get("prob"), brier_map=r.get("brier"), sums=r["sums"], hist=r["hist"], hits=r["hits"], status=r["status"], thresholds=thr,
+                               weighted=logw is not None or (into is not None and into.weighted))
+
+    def __call__(self, y: torch.Tensor, obs: torch.Tensor, precision: Optional[torch.Tensor] = None, logw: Optional[torch.Tensor] = None,
+                 into: Optional["ThresholdScores"] = None, maps=()) -> "ThresholdScores":
+        z, Bm = self._states(y)
+        n = self.members
+        B = Bm // n
+        nd, T = len(self.derived), self.thresholds.shape[0]
+        x_obs, prec = self._observation(obs, precision, B, y.device)
+        maps, logw = _check_brier_call(self._what, maps, logw, into, (B, nd, T), Bm, n, y.device)
+        N.require_gpu(y, f"{self._what} states")
+        thr = self._thresholds_on(y.device)
+        r = self.decoder.member_derived_brier(z, x_obs, n, self.derived, thr, counts=self.counts, precision=prec, logw=logw, fused=self.fused, maps=maps,
+                                              into=None if into is None else dict(sums=into.sums, hist=into.hist, hits=into.hits))
+        return ThresholdScores(prob=r.get("prob"), brier_map=r.get("brier"), sums=r["sums"], hist=r["hist"], hits=r["hits"], status=r["status"], thresholds=thr,
+                               weighted=logw is not None or (into is not None and into.weighted))
+
+    verify = __call__

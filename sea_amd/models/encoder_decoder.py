@@ -1128,6 +1128,175 @@ class Decode(nn.Module):
                 exceed = None if exceed is None else exceed[..., :C]
             return quant, exceed
 
+    def _derived_call(self, what: str, z, members, derived, fused, max_n: int, min_rows: int):
+        """The checks member_derived_quantiles and member_derived_brier share.  Returns (derived as a tuple, Bm, P, B, fused resolved): fused=None takes
+        the fused launches in bf16 up to max_n members, with every derived field's sources in one decoder group, from min_rows rows on."""
+        n_fields = sum(len(g) for g in self.field_groups)
+        if not torch.is_tensor(z) or z.dim() != 4 or z.shape[2] != self.num_groups or z.shape[3] != self.embed_dim:
+            raise ValueError(f"{what}: z must be [B * members, P, {self.num_groups}, {self.embed_dim}], got {tuple(z.shape) if torch.is_tensor(z) else type(z).__name__}")
+        Bm, P = z.shape[0], z.shape[1]
+        if not isinstance(members, int) or isinstance(members, bool) or members < 1 or Bm < 1 or Bm % members:
+            raise ValueError(f"{what}: members = {members!r} must be a positive integer that divides the {Bm} rows of z")
+        try:
+            derived = tuple(derived)
+        except TypeError:
+            raise ValueError(f"{what}: derived must be a sequence of DerivedField, got {type(derived).__name__}") from None
+        if not derived or any(not all(hasattr(d, k) for k in ("op", "a", "b", "scale_a", "shift_a", "scale_b", "shift_b")) for d in derived):
+            raise ValueError(f"{what}: derived must be a non-empty sequence of DerivedField")
+        for i, d in enumerate(derived):
+            if not (0 <= d.a < n_fields and 0 <= d.b < n_fields) or d.a == d.b:
+                raise ValueError(f"{what}: derived field {i}: sources a = {d.a}, b = {d.b} must be two different fields in 0 .. {n_fields - 1}")
+        group_of = [g for g, fields in enumerate(self.field_groups) for _ in fields]   # the decoder group of every field, in output order
+        one_group = all(group_of[d.a] == group_of[d.b] for d in derived)
+        dt = self._act_dtype()
+        if fused is None:
+            fused = dt == torch.bfloat16 and members <= max_n and one_group and len(derived) <= N.DERIVED_MAX and Bm * P >= min_rows
+        if fused and dt != torch.bfloat16:
+            raise ValueError(f"{what}: the fused launches are bf16 only (set_compute_dtype('bf16'), or fused=False)")
+        if fused and members > max_n:
+            raise ValueError(f"{what}: the fused launches carry up to {max_n} members, got {members} (fused=False, or None)")
+        if fused and len(derived) > N.DERIVED_MAX:
+            raise ValueError(f"{what}: the fused launches carry up to {N.DERIVED_MAX} derived fields, got {len(derived)} (fused=False, or None)")
+        return derived, Bm, P, Bm // members, bool(fused)
+
+    def _hidden_groups(self, z: torch.Tensor, dt: torch.dtype):
+        """The first decoder layer in one grouped launch: the operand groups [dict(H, W2, bias)] of the fused decode launches."""
+        Bm, P = z.shape[0], z.shape[1]
+        M = Bm * P
+        G, D = self.num_groups, self.embed_dim
+        zf = z.detach().to(torch.float32).contiguous().view(M, G * D)
+        za = torch.empty(M, G * D, device=z.device, dtype=dt)
+        ops.convert(zf, za)
+        W1, W2 = self._weights(dt)
+        hid = [torch.empty(M, self.MLP_hidden, device=z.device, dtype=dt) for _ in range(G)]
+        ops.gemm_grouped([dict(A=za[:, g * D:(g + 1) * D], W=W1[g], Cact=hid[g], act=1) for g in range(G)], dt)
+        bias = self._shadow[3]
+        return [dict(H=hid[g], W2=W2[g], bias=bias[g]) for g in range(G)]
+
+    def member_derived_quantiles(self, z: torch.Tensor, members: int, derived, levels=(), thresholds: Optional[torch.Tensor] = None,
+                                 weights: Optional[torch.Tensor] = None, counts=None, fused: Optional[bool] = None):
+        """member_quantiles for DERIVED fields — the magnitude, the energy or the difference of two decoded fields, formed per member (include/sea_hip.h,
+        sea_decode_derived_quantiles, states the definitions; sea_amd.ensemble.DerivedField): (quant float32 [Q, B, P, n_derived, n_inp] or None, exceed
+        float32 [T, B, P, n_derived, n_inp] or None); no autograd graph.  z, levels, weights and counts as in member_quantiles; derived: a sequence of
+        DerivedField; thresholds: None or float32 [T <= 8, n_derived] on z's device, in the derived fields' own (physical) units.
+        fused=True (bf16, members <= 128, up to 8 derived fields, each with both sources in one decoder group): the first-layer launch plus the ONE
+        launch of sea_decode_derived_quantiles — neither the members' decoded fields nor the derived fields are written; it raises where the launch
+        refuses.  fused=False: forward() plus ensemble._composed_derived plus ensemble._composed_quantiles (float32 values, float64 weights: fp32, any
+        member count, sources in different groups, comparison).  fused=None: the fused launch where it serves, from 4096 rows (B * members * P) on —
+        the rows of profiles/derived_fields_bench.txt (tools/derived_fields_bench.py) — and the composed path elsewhere."""
+        from ..ensemble import DERIVED_FUSED_MIN_ROWS, _composed_derived, _composed_quantiles
+
+        what = "sea_amd.Decode.member_derived_quantiles"
+        n_fields = sum(len(g) for g in self.field_groups)
+        C, Cp = self.n_inp, self._n_inp_p
+        derived, Bm, P, B, fused = self._derived_call(what, z, members, derived, fused, N.QUANTILE_MAX_N, DERIVED_FUSED_MIN_ROWS)
+        nd = len(derived)
+        levels = ops.check_quantile_levels(levels, what)
+        if thresholds is not None and (not torch.is_tensor(thresholds) or thresholds.dtype != torch.float32 or thresholds.dim() != 2
+                                       or not 1 <= thresholds.shape[0] <= N.QUANTILE_MAX_LEVELS or thresholds.shape[1] != nd or thresholds.device != z.device):
+            raise ValueError(f"{what}: thresholds must be None or a float32 [1 .. {N.QUANTILE_MAX_LEVELS}, {nd}] tensor on {z.device}, got "
+                             f"{(tuple(thresholds.shape), thresholds.dtype, str(thresholds.device)) if torch.is_tensor(thresholds) else type(thresholds).__name__}")
+        if not levels and thresholds is None:
+            raise ValueError(f"{what}: neither levels nor thresholds: there is nothing to compute")
+        if weights is not None:
+            if not torch.is_tensor(weights) or weights.dim() != 1 or weights.shape[0] != Bm:
+                raise ValueError(f"{what}: weights must be None or a [{Bm}] tensor (one weight per member), got "
+                                 f"{tuple(weights.shape) if torch.is_tensor(weights) else type(weights).__name__}")
+            if weights.dtype != torch.float32 or weights.device != z.device:
+                raise ValueError(f"{what}: weights must be float32 on {z.device}, got {weights.dtype} on {weights.device}")
+        cnt, _ = self._valid_counts(counts, P, z.device, allow_empty=True, what="member_derived_quantiles")
+        N.require_gpu(z, "Decode.member_derived_quantiles input")
+        with torch.no_grad():
+            w = None if weights is None else weights.detach().contiguous()
+            thr = None if thresholds is None else thresholds.detach().contiguous()
+            n_q, n_t = len(levels), 0 if thr is None else thr.shape[0]
+            out = {}
+            if not fused:
+                y = self.forward(z.detach()).view(B, members, P, n_fields, C)
+                q, e = _composed_quantiles(_composed_derived(y, derived), None if w is None else w.view(B, members), levels, thr)
+                valid = None if cnt is None else (torch.arange(C, device=z.device) < cnt[:, None]).view(1, 1, P, 1, C)
+                for name, t, k in (("quant", q, n_q), ("exceed", e, n_t)):
+                    if t is not None:
+                        buf = torch.zeros(k, B, P, nd, Cp, device=z.device, dtype=torch.float32)
+                        buf[..., :C] = t if valid is None else torch.where(valid, t.to(torch.float32), torch.zeros((), device=z.device))
+                        out[name] = buf
+            else:
+                dt = self._act_dtype()
+                bufs = {name: torch.empty(k, B, P, nd, Cp, device=z.device, dtype=torch.float32) for name, k in (("quant", n_q), ("exceed", n_t)) if k}
+                out = ops.decode_derived_quantiles(self._hidden_groups(z, dt), derived, C, Cp, P, members, levels=levels, thr=thr, w=w, counts=cnt, out=bufs, dtype=dt)
+            quant, exceed = out.get("quant"), out.get("exceed")
+            if Cp != C:
+                quant = None if quant is None else quant[..., :C]
+                exceed = None if exceed is None else exceed[..., :C]
+            return quant, exceed
+
+    def member_derived_brier(self, z: torch.Tensor, obs: torch.Tensor, members: int, derived, thresholds: torch.Tensor, counts=None,
+                             precision: Optional[torch.Tensor] = None, field_precision: Optional[torch.Tensor] = None, logw: Optional[torch.Tensor] = None,
+                             fused: Optional[bool] = None, maps=(), into: Optional[dict] = None):
+        """member_brier for DERIVED fields (include/sea_hip.h, sea_decode_derived_brier; sea_amd.ensemble.DerivedField): the dict of member_brier with
+        n_derived where that has n_fields; no autograd graph.  z, counts, logw, maps and into as in member_brier; derived: a sequence of DerivedField;
+        obs and precision float32 [B, P, n_derived, >= n_inp]: readings of the DERIVED quantities (ensemble.DerivedThresholdVerification forms them from a
+        snapshot of the source fields); field_precision float32 [n_derived]; thresholds float32 [T <= 8, n_derived] on z's device, in the derived
+        fields' own units.  fused as in member_derived_quantiles: True — the first-layer launch plus the TWO launches of sea_decode_derived_brier; False —
+        forward() plus ensemble._composed_derived plus ensemble._composed_field_brier; None — the fused launches where they serve, from 4096 rows on."""
+        from ..ensemble import BRIER_MAPS, DERIVED_FUSED_MIN_ROWS, _composed_derived, _composed_field_brier, _field_cell_weights
+
+        what = "sea_amd.Decode.member_derived_brier"
+        n_fields = sum(len(g) for g in self.field_groups)
+        C, Cp = self.n_inp, self._n_inp_p
+        derived, Bm, P, B, fused = self._derived_call(what, z, members, derived, fused, N.BRIER_MAX_N, DERIVED_FUSED_MIN_ROWS)
+        nd = len(derived)
+        for name, t in (("obs", obs), ("precision", precision)):
+            if t is None and name == "precision":
+                continue
+            if not torch.is_tensor(t) or t.dim() != 4 or tuple(t.shape[:3]) != (B, P, nd) or t.shape[3] < C:
+                raise ValueError(f"{what}: {name} must be [{B}, {P}, {nd}, >= {C}] (one per history of {members} members), got "
+                                 f"{tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
+            if t.dtype != torch.float32 or t.device != z.device:
+                raise ValueError(f"{what}: {name} must be float32 on {z.device}, got {t.dtype} on {t.device}")
+        if precision is not None and precision.shape[3] != obs.shape[3]:
+            raise ValueError(f"{what}: precision must have obs's shape {tuple(obs.shape)}, got {tuple(precision.shape)}")
+        if field_precision is not None and (not torch.is_tensor(field_precision) or field_precision.dtype != torch.float32 or tuple(field_precision.shape) != (nd,)
+                                            or field_precision.device != z.device):
+            raise ValueError(f"{what}: field_precision must be None or a float32 [{nd}] tensor on {z.device}")
+        if logw is not None and (not torch.is_tensor(logw) or logw.dtype != torch.float32 or tuple(logw.shape) != (Bm,) or logw.device != z.device):
+            raise ValueError(f"{what}: logw must be None or a float32 [{Bm}] tensor on {z.device}")
+        thr = thresholds.detach().contiguous() if torch.is_tensor(thresholds) else thresholds
+        ops.check_brier_thresholds(thr, nd, z.device, what)
+        T = thr.shape[0]
+        maps = tuple(maps)
+        if any(k not in BRIER_MAPS for k in maps) or len(set(maps)) != len(maps):
+            raise ValueError(f"{what}: maps must be distinct names among {BRIER_MAPS}, got {maps!r}")
+        shapes = (("sums", (B, nd, T, N.BRIER_SUMS), torch.float64), ("hist", (B, nd, T, members + 1), torch.int64), ("hits", (B, nd, T, members + 1), torch.int64))
+        if into is not None and (not isinstance(into, dict) or set(into) != {"sums", "hist", "hits"} or any(
+                not torch.is_tensor(into[k]) or tuple(into[k].shape) != sh or into[k].dtype != dt_ or into[k].device != z.device or not into[k].is_contiguous()
+                for k, sh, dt_ in shapes)):
+            raise ValueError(f"{what}: into must be a dict of contiguous sums float64 [{B}, {nd}, {T}, {N.BRIER_SUMS}], hist and hits int64 [{B}, {nd}, {T}, "
+                             f"{members + 1}] on {z.device}")
+        cnt, _ = self._valid_counts(counts, P, z.device, allow_empty=True, what="member_derived_brier")
+        N.require_gpu(z, "Decode.member_derived_brier input")
+        with torch.no_grad():
+            obs = obs.detach()
+            prec = None if precision is None else precision.detach()
+            pf = None if field_precision is None else field_precision.detach().contiguous()
+            lw = None if logw is None else logw.detach().contiguous()
+            if not fused:
+                y = self.forward(z.detach()).view(B, members, P, n_fields, C)
+                x = _composed_derived(y, derived).view(Bm, P, nd, C)
+                w = _field_cell_weights((B, P, nd, C), pf, prec, cnt, z.device)
+                r = _composed_field_brier(x, obs, w, lw, members, thr, maps=maps)
+                if into is not None:
+                    r["sums"], r["hist"], r["hits"] = into["sums"].add_(r["sums"]), into["hist"].add_(r["hist"]), into["hits"].add_(r["hits"])
+                return r
+
+            def rows(t):   # [B * P, n_derived, width] with unit inner stride: a view where the layout allows it, else one copy of the first C columns
+                t3 = t.reshape(B * P, nd, t.shape[3])
+                return t3 if t3.stride(2) == 1 and t3.stride(1) >= C and t3.stride(0) >= 0 else t3[..., :C].contiguous()
+
+            dt = self._act_dtype()
+            return ops.decode_derived_brier(self._hidden_groups(z, dt), derived, rows(obs), C, Cp, P, members, thr, prec_field=pf,
+                                            prec=None if prec is None else rows(prec), counts=cnt, logw=lw, accumulate=into is not None, maps=maps, out=into, dtype=dt)
+
     def forward_prefix(self, z: torch.Tensor, buckets) -> torch.Tensor:
         """The decoder for a consumer that only reads the first cells of a patch (MeshUnpatcher.decode_and_unpatch: a patch holds as many mesh points as its
         cell has, the rest of its n_inp columns is padding nobody reads — 71 % of the columns on the bench's wake-refined mesh).  z [B, P, n_groups,

@@ -2362,3 +2362,152 @@ def decode_member_brier(groups: Sequence[Dict], obs: torch.Tensor, C_: int, Cp: 
                              res["hist"], res["hits"], res["status"], work, ld)
     N.check(N.lib().sea_decode_member_brier(arr, len(groups), C.byref(P), N.dtype_code(dtype), N.stream_ptr()), "sea_decode_member_brier")
     return res
+
+
+# ------------------------------------------------------------------------------------------------ derived fields (|u|, energy, difference)
+def fill_derived_table(arr, derived: Sequence) -> None:
+    """The derived-field table of sea_decode_derived_quantiles / sea_decode_derived_brier: arr a (SeaDerivedField * len(derived))(); derived: objects with
+    op ("magnitude", "energy", "difference", or the ABI's code), a, b, scale_a, shift_a, scale_b, shift_b (sea_amd.ensemble.DerivedField)."""
+    for g, d in zip(arr, derived):
+        g.op = N.DERIVED_OPS[d.op] if isinstance(d.op, str) else int(d.op)
+        g.a, g.b, g.pad_ = int(d.a), int(d.b), 0
+        g.scale_a, g.shift_a, g.scale_b, g.shift_b = float(d.scale_a), float(d.shift_a), float(d.scale_b), float(d.shift_b)
+
+
+def _check_derived_call(what: str, groups: Sequence[Dict], derived: Sequence, C_: int, Cp: int, n_patches: int, members: int, max_n: int, dtype: torch.dtype):
+    """The checks decode_derived_quantiles and decode_derived_brier share — decode_member_quantiles' checks of the groups and sizes, and the derived
+    table against the source fields.  Returns (device, M, S, n_fields, B)."""
+    if dtype != torch.bfloat16:
+        raise ValueError(f"{what}: the fused launch is bf16 only, got {dtype}")
+    if not groups or len(groups) > N.DECODE_MSE_MAX_GROUPS:
+        raise ValueError(f"{what}: {len(groups)} groups; a launch carries 1 .. {N.DECODE_MSE_MAX_GROUPS}")
+    if Cp < 32 or Cp % 32 or not 1 <= C_ <= Cp:
+        raise ValueError(f"{what}: need Cp a multiple of 32 and 1 <= C <= Cp, got C = {C_}, Cp = {Cp}")
+    dev = groups[0]["H"].device
+    M, S = tuple(groups[0]["H"].shape) if groups[0]["H"].dim() == 2 else (0, 0)
+    if M < 1 or S < 8 or S % 8 or S > N.DECODE_MSE_MAX_S:
+        raise ValueError(f"{what}: H must be [M >= 1, S] with S a multiple of 8 up to {N.DECODE_MSE_MAX_S}, got {tuple(groups[0]['H'].shape)}")
+    n = members
+    if not isinstance(n, int) or isinstance(n, bool) or n < 1 or n > max_n:
+        raise ValueError(f"{what}: members = {members!r} must be an integer in 1 .. {max_n}")
+    if n_patches < 1 or M % (n_patches * n):
+        raise ValueError(f"{what}: {M} rows are not a multiple of n_patches * members = {n_patches} * {n}")
+    n_fields = 0
+    for i, d in enumerate(groups):
+        for name in ("H", "W2"):
+            t = d[name]
+            if t.dim() != 2 or t.stride(1) != 1:
+                raise ValueError(f"{what} group {i}: {name}: need a 2-D tensor with unit inner stride, got shape {tuple(t.shape)} strides {t.stride()}")
+            if t.dtype != dtype or t.device != dev or t.shape[1] != S or (name != "W2" and t.shape[0] != M):
+                raise ValueError(f"{what} group {i}: {name} must be a {dtype} [{'n_fields * Cp' if name == 'W2' else M}, {S}] tensor on {dev}, got "
+                                 f"{tuple(t.shape)} {t.dtype} on {t.device}")
+            if t.stride(0) % 8 or t.data_ptr() % 16:
+                raise ValueError(f"{what} group {i}: {name} needs a row stride that is a multiple of 8 and a 16-byte-aligned base (stride {t.stride(0)})")
+        W2, b = d["W2"], d["bias"]
+        if W2.shape[0] < Cp or W2.shape[0] % Cp:
+            raise ValueError(f"{what} group {i}: W2 has {W2.shape[0]} rows, not a multiple of Cp = {Cp}")
+        if b.dtype != torch.float32 or b.dim() != 1 or b.shape[0] != W2.shape[0] or not b.is_contiguous() or b.device != dev or b.data_ptr() % 16:
+            raise ValueError(f"{what} group {i}: bias must be a contiguous, 16-byte-aligned float32 [{W2.shape[0]}] on {dev}, got {tuple(b.shape)} {b.dtype}")
+        n_fields += W2.shape[0] // Cp
+    B = M // (n_patches * n)
+    if B > 65535:
+        raise ValueError(f"{what}: {B} histories; a launch carries up to 65535")
+    try:
+        n_derived = len(derived)
+    except TypeError:
+        raise ValueError(f"{what}: derived must be a sequence of derived fields, got {type(derived).__name__}") from None
+    if not 1 <= n_derived <= N.DERIVED_MAX:
+        raise ValueError(f"{what}: {n_derived} derived fields; a launch carries 1 .. {N.DERIVED_MAX}")
+    for i, d in enumerate(derived):
+        if isinstance(d.op, str) and d.op not in N.DERIVED_OPS:
+            raise ValueError(f"{what}: derived field {i}: op {d.op!r} must be one of {tuple(N.DERIVED_OPS)}")
+        if not (0 <= d.a < n_fields and 0 <= d.b < n_fields) or d.a == d.b:
+            raise ValueError(f"{what}: derived field {i}: sources a = {d.a}, b = {d.b} must be two different fields in 0 .. {n_fields - 1}")
+    return dev, M, S, n_fields, B
+
+
+def decode_derived_quantiles(groups: Sequence[Dict], derived: Sequence, C_: int, Cp: int, n_patches: int, members: int, levels: Sequence[float] = (),
+                             thr: Optional[torch.Tensor] = None, w: Optional[torch.Tensor] = None, counts: Optional[torch.Tensor] = None,
+                             out: Optional[Dict[str, torch.Tensor]] = None, dtype: torch.dtype = torch.bfloat16) -> Dict[str, Optional[torch.Tensor]]:
+    """sea_decode_derived_quantiles: decode_member_quantiles for DERIVED fields — the magnitude, the energy or the difference of two source fields of one
+    decoder group, formed per member in registers (include/sea_hip.h states the definitions); neither the decoded components nor the derived field are
+    written.  groups, levels, w, counts, out as decode_member_quantiles; derived: 1 .. 8 sea_amd.ensemble.DerivedField; thr None or f32 [T <= 8, n_derived]
+    in the derived fields' own units.  Returns dict(quant=f32 [Q, B, n_patches, n_derived, C] or None, exceed=f32 [T, ...] or None).  The launch refuses
+    sources in different groups (RuntimeError, code -3): Decode.member_derived_quantiles composes there."""
+    what = "decode_derived_quantiles"
+    dev, M, S, n_fields, B = _check_derived_call(what, groups, derived, C_, Cp, n_patches, members, N.QUANTILE_MAX_N, dtype)
+    n, nd = members, len(derived)
+    levels = check_quantile_levels(levels, what)
+    if thr is not None and (not torch.is_tensor(thr) or thr.dtype != torch.float32 or thr.dim() != 2 or not 1 <= thr.shape[0] <= N.QUANTILE_MAX_LEVELS
+                            or thr.shape[1] != nd or not thr.is_contiguous() or thr.device != dev):
+        raise ValueError(f"{what}: thr must be None or a contiguous float32 [1 .. {N.QUANTILE_MAX_LEVELS}, {nd}] tensor on {dev}, got "
+                         f"{(tuple(thr.shape), thr.dtype, str(thr.device)) if torch.is_tensor(thr) else type(thr).__name__}")
+    if not levels and thr is None:
+        raise ValueError(f"{what}: neither levels nor thresholds: there is nothing to compute")
+    if w is not None and (not torch.is_tensor(w) or w.dtype != torch.float32 or tuple(w.shape) != (B * n,) or not w.is_contiguous() or w.device != dev):
+        raise ValueError(f"{what}: w must be None or a contiguous float32 [{B * n}] tensor on {dev}, got "
+                         f"{(tuple(w.shape), w.dtype, str(w.device)) if torch.is_tensor(w) else type(w).__name__}")
+    if counts is not None and (not torch.is_tensor(counts) or counts.dtype != torch.int32 or counts.dim() != 1 or counts.shape[0] != n_patches
+                               or not counts.is_contiguous() or counts.device != dev):
+        raise ValueError(f"{what}: counts must be a contiguous int32 [{n_patches}] on {dev}")
+    n_out = {"quant": len(levels), "exceed": 0 if thr is None else thr.shape[0]}
+    out = {} if out is None else out
+    if not isinstance(out, dict) or any(k not in n_out or n_out[k] == 0 for k in out):
+        raise ValueError(f"{what}: out must be a dict with 'quant' (with levels) and / or 'exceed' (with thresholds)")
+    widths = {t.shape[-1] for t in out.values() if torch.is_tensor(t) and t.dim() == 5}
+    if len(widths) > 1:
+        raise ValueError(f"{what}: the maps in out must share their last dimension, got {sorted(widths)}")
+    ld = widths.pop() if widths else C_
+    for k, t in out.items():
+        shape = (n_out[k], B, n_patches, nd, ld)
+        if not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev or ld < C_:
+            raise ValueError(f"{what}: out[{k!r}] must be a contiguous float32 {list(shape)} tensor on {dev} (last dimension >= {C_})")
+    N.require_gpu(groups[0]["H"], f"{what} hidden rows")   # every operand is on their device (checked above)
+    res = {k: (out[k] if k in out else torch.empty(n_out[k], B, n_patches, nd, ld, device=dev, dtype=torch.float32)) if n_out[k] else None for k in n_out}
+    arr, tab, P = (N.SeaDecodeMseGroup * len(groups))(), (N.SeaDerivedField * nd)(), N.SeaDecodeMemberQuantiles()
+    fill_decode_member_quantiles(arr, P, groups, w, counts, thr, levels, res["quant"], res["exceed"], n_patches, n, C_, Cp, ld, B * n_patches * nd * ld)
+    fill_derived_table(tab, derived)
+    N.check(N.lib().sea_decode_derived_quantiles(arr, len(groups), tab, nd, C.byref(P), N.dtype_code(dtype), N.stream_ptr()), "sea_decode_derived_quantiles")
+    return res
+
+
+def decode_derived_brier(groups: Sequence[Dict], derived: Sequence, obs: torch.Tensor, C_: int, Cp: int, n_patches: int, members: int, thr: torch.Tensor,
+                         prec: Optional[torch.Tensor] = None, prec_field: Optional[torch.Tensor] = None, counts: Optional[torch.Tensor] = None,
+                         logw: Optional[torch.Tensor] = None, accumulate: bool = False, maps: Sequence[str] = BRIER_MAPS,
+                         out: Optional[Dict[str, torch.Tensor]] = None, dtype: torch.dtype = torch.bfloat16) -> Dict[str, torch.Tensor]:
+    """sea_decode_derived_brier: decode_member_brier for DERIVED fields (include/sea_hip.h states the definitions).  groups, counts, logw, accumulate, maps,
+    out as decode_member_brier; derived: 1 .. 8 sea_amd.ensemble.DerivedField; obs and prec f32 [B * n_patches, n_derived, >= C] readings of the derived
+    quantities; prec_field f32 [n_derived]; thr f32 [T <= 8, n_derived] in the derived fields' own units.  Returns decode_member_brier's dict with
+    n_derived where that has n_fields."""
+    what = "decode_derived_brier"
+    dev, M, S, n_fields, B = _check_derived_call(what, groups, derived, C_, Cp, n_patches, members, N.BRIER_MAX_N, dtype)
+    n, nd = members, len(derived)
+    for name, t in (("obs", obs), ("prec", prec)):
+        if t is None and name == "prec":
+            continue
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or t.dim() != 3 or tuple(t.shape[:2]) != (B * n_patches, nd) or t.shape[2] < C_ or t.stride(2) != 1 \
+                or t.device != dev or t.stride(1) < C_ or (t.shape[0] > 1 and t.stride(0) < 0):
+            raise ValueError(f"{what}: {name} must be a float32 [{B * n_patches}, {nd}, >= {C_}] tensor with unit inner stride on {dev}, got "
+                             f"{(tuple(t.shape), t.dtype, t.stride(), str(t.device)) if torch.is_tensor(t) else type(t).__name__}")
+    check_brier_thresholds(thr, nd, dev, what)
+    if prec_field is not None and (not torch.is_tensor(prec_field) or prec_field.dtype != torch.float32 or tuple(prec_field.shape) != (nd,)
+                                   or not prec_field.is_contiguous() or prec_field.device != dev):
+        raise ValueError(f"{what}: prec_field must be None or a contiguous float32 [{nd}] tensor on {dev}")
+    if counts is not None and (not torch.is_tensor(counts) or counts.dtype != torch.int32 or counts.dim() != 1 or counts.shape[0] != n_patches
+                               or not counts.is_contiguous() or counts.device != dev):
+        raise ValueError(f"{what}: counts must be a contiguous int32 [{n_patches}] on {dev}")
+    if logw is not None and (not torch.is_tensor(logw) or logw.dtype != torch.float32 or tuple(logw.shape) != (B * n,) or not logw.is_contiguous() or logw.device != dev):
+        raise ValueError(f"{what}: logw must be None or a contiguous float32 [{B * n}] tensor on {dev}, got "
+                         f"{(tuple(logw.shape), logw.dtype, str(logw.device)) if torch.is_tensor(logw) else type(logw).__name__}")
+    T = thr.shape[0]
+    fixed = {"sums": ((B, nd, T, N.BRIER_SUMS), torch.float64), "hist": ((B, nd, T, n + 1), torch.int64), "hits": ((B, nd, T, n + 1), torch.int64),
+             "status": ((B,), torch.int32)}
+    res, ld = _brier_outputs(what, out, maps, accumulate, fixed, lambda ld: (T, B, n_patches, nd, ld), C_, groups[0]["H"])
+    work = torch.empty(int(N.lib().sea_decode_member_brier_ws_bytes(B, n_patches, nd, n, Cp, T)), device=dev, dtype=torch.uint8)
+    arr, tab, P = (N.SeaDecodeMseGroup * len(groups))(), (N.SeaDerivedField * nd)(), N.SeaDecodeMemberBrier()
+    fill_decode_member_brier(arr, P, groups, obs, prec_field, prec, counts, logw, thr, n_patches, n, C_, Cp, accumulate, res.get("prob"), res.get("brier"), res["sums"],
+                             res["hist"], res["hits"], res["status"], work, ld)
+    P.ld_map = obs.shape[0] * nd * ld   # the maps are sized by the derived fields; n_fields_total stays the number of source fields
+    fill_derived_table(tab, derived)
+    N.check(N.lib().sea_decode_derived_brier(arr, len(groups), tab, nd, C.byref(P), N.dtype_code(dtype), N.stream_ptr()), "sea_decode_derived_brier")
+    return res

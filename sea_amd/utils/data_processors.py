@@ -237,6 +237,41 @@ class MeshUnpatcher:
         b = torch.tensor(shift, dtype=torch.float64, device=t.device)
         return (t.to(torch.float64) * a + b).to(torch.float32).contiguous()
 
+    def derived_fields(self, specs) -> list:
+        """Derived fields in PHYSICAL units for sea_amd.ensemble.DerivedQuantiles / DerivedThresholdVerification: specs is a sequence of (op, a, b) or
+        (op, a, b, name) — [("magnitude", 0, 1)] is the speed of the velocity components 0 and 1 — and each DerivedField returned carries the inverse
+        affine of its two source fields (what inverse_scale_and_unpatch applies: x -> x * scale + shift), so that the decoder's scaled values are taken
+        back to the mesh's units before they are squared or subtracted.  Formed on the host from the scalers."""
+        from ..ensemble import DerivedField
+
+        F = sum(len(g) for g in self.field_groups)
+        scale, shift = [1.0] * F, [0.0] * F
+        for g, sc in zip(self.field_groups, self.scalers):
+            a, b = sc.inverse_affine()
+            for f in g:
+                scale[f], shift[f] = float(a), float(b)
+        out = []
+        for i, spec in enumerate(specs):
+            if not isinstance(spec, (tuple, list)) or len(spec) not in (3, 4):
+                raise ValueError(f"derived_fields: spec {i} must be (op, a, b) or (op, a, b, name), got {spec!r}")
+            op, a, b = spec[:3]
+            if not all(isinstance(v, int) and not isinstance(v, bool) and 0 <= v < F for v in (a, b)):
+                raise ValueError(f"derived_fields: spec {i}: sources a = {a!r}, b = {b!r} must be field indices in 0 .. {F - 1}")
+            out.append(DerivedField(op, a, b, scale_a=scale[a], shift_a=shift[a], scale_b=scale[b], shift_b=shift[b], name=spec[3] if len(spec) == 4 else None))
+        return out
+
+    def unpatch_derived(self, values: torch.Tensor, layout: str = "BPFC") -> torch.Tensor:
+        """Maps of derived fields — DerivedQuantiles' quant[k] and exceed[t], DerivedThresholdVerification's prob and brier maps — onto the mesh unchanged
+        (they are in physical units, or unit-free, already): unpatch_map with coefficient tables sized by the number of derived fields.  values
+        [T, P, n_derived, C] (any real dtype; converted to float32) or [T, P, C, n_derived] ("BPCF") -> float32 [T, N, n_derived]."""
+        N.require_gpu(values, "values")
+        if layout not in ("BPFC", "BPCF") or values.dim() != 4:
+            raise ValueError(f"unpatch_derived: values must be [T, P, n_derived, C] (layout 'BPFC') or [T, P, C, n_derived] ('BPCF'), got {tuple(values.shape)} {layout!r}")
+        nd = values.shape[2] if layout == "BPFC" else values.shape[3]
+        one, zero = torch.ones(nd, device=self._scale.device, dtype=torch.float32), torch.zeros(nd, device=self._scale.device, dtype=torch.float32)
+        return ops.unpatchify(values.float(), layout, self.partitioner.padded_index_map, one, zero, self.partitioner.x_coords.numel(),
+                              point_slot=self.partitioner.point_slot if self.gather else None)
+
     # ------------------------------------------------------------------ decoder + un-patchify without the padding
     def _prefix_plan(self, max_buckets: int):
         """Patches sorted by how many mesh points their cell holds, cut into <= max_buckets runs that minimise sum(run length x longest cell of the run) —
@@ -356,6 +391,20 @@ class MeshProcessor:
         if self._unpatcher is None:
             raise ValueError("call patchify_and_scale first (it builds the partition)")
         return self._unpatcher.scale_thresholds(thr)
+
+    def derived_fields(self, specs) -> list:
+        """[(op, a, b)] -> sea_amd.ensemble.DerivedField s carrying the inverse affine of their source fields: derived values in physical units
+        (MeshUnpatcher.derived_fields)."""
+        if self._unpatcher is None:
+            raise ValueError("call patchify_and_scale first (it builds the partition)")
+        return self._unpatcher.derived_fields(specs)
+
+    def unpatch_derived(self, values: torch.Tensor, layout: str = "BPFC") -> torch.Tensor:
+        """Maps of derived fields ([T, P, n_derived, C] or with layout="BPCF" [T, P, C, n_derived]) -> float32 [T, N, n_derived], unchanged
+        (MeshUnpatcher.unpatch_derived)."""
+        if self._unpatcher is None:
+            raise ValueError("call patchify_and_scale first (it builds the partition)")
+        return self._unpatcher.unpatch_derived(values.to(self.device), layout=layout)
 
     def sensor_set(self, decoder, points, fields):
         """Point sensors on the mesh (mesh point ids and field ids) as a SensorSet for `decoder`, with scale_values / scale_sigma for readings in
