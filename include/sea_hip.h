@@ -1779,6 +1779,37 @@ int sea_decode_derived_quantiles(const SeaDecodeMseGroup* groups, int n_groups, 
 int sea_decode_derived_brier(const SeaDecodeMseGroup* groups, int n_groups, const SeaDerivedField* derived, int n_derived,
                              const SeaDecodeMemberBrier* p, int dtype, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * sea_decode_derived_verify: sea_decode_member_verify for DERIVED fields — is the ensemble of the speed calibrated, is its spread the size of its
+ * error, what is its CRPS, is its rank histogram flat.  None of this follows from the scores of u and v: the derived value x_j of member j at a cell is
+ * formed first, exactly as sea_decode_derived_quantiles forms it (the definitions above: the same decode, the same single-rounded f32 arithmetic, the
+ * correctly rounded root), and from x_j on everything is sea_decode_member_verify with "field" read as "derived field" — the same device code behind
+ * the value image: the history's weights w_m, c and status; mean, spread, CRPS, PIT and rank per cell; the eight fp64 sums and the rank histogram per
+ * (history, derived field).  A derived cell scored from the same f32 values has the bits of a cell of sea_decode_member_verify and of a sensor of
+ * sea_ensemble_verify.
+ * p->n_fields_total stays the number of SOURCE fields (the groups cover them exactly once); every other quantity that has F in
+ * sea_decode_member_verify has n_derived here: obs and prec [B * P, n_derived, >= C] — READINGS OF THE DERIVED QUANTITY, in its own units, and their
+ * precisions — prec_field [n_derived]; mean, spread, crps, pit f32 and rank int32 [B * P, n_derived, ld_out]; sums f64 [B, n_derived, 8]; hist int64
+ * [B, n_derived, members + 1]; work_bytes >= sea_decode_member_verify_ws_bytes(B, P, n_derived, members, Cp).
+ * Cells: LIVE, DEAD and BAD exactly as in sea_decode_member_verify (the weight w[d, c] from counts, prec_field[d] and prec by selects; obs is never
+ * read at a dead cell).  A live cell where a live member's x is not finite (NaN or Inf in a source, overflow of a square) is BAD: its floats are NaN,
+ * its rank -2, sums[.., 6] counts it and nothing else is added.  accumulate, unbiased, logw, dead members and status are as in
+ * sea_decode_member_verify (status[b] = -1 for invalid log-weights or no live member: maps 0 / -1, nothing added).
+ * Launches: two.  Launch 1 has sea_decode_member_verify's grid with n_derived for F — a workgroup of 8 waves per (history, patch, derived field, chunk
+ * of 512 columns) — and per tile of 32 columns the two-source decode of the derived launches above (the W2 tiles of source a and of source b through
+ * the SAME two LDS images, the stream a_0, b_0, a_1, b_1, ...; hidden rows loaded once; a's tile into 8 registers, b's on top, the op per element, x
+ * to the value image), then sea_decode_member_verify's scoring, finish and sums; launch 2 is that entry point's finish launch.  No floating-point
+ * atomics: two runs give the same bits, a history's outputs are those of a call holding it alone, and a derived field's outputs do not depend on the
+ * other derived fields of the call.
+ * Returns -1, with the entry point and the offending derived field named in sea_last_error(), before any device is touched, for everything
+ * sea_decode_derived_brier refuses of the derived table and everything sea_decode_member_verify refuses.  Returns SEA_EUNSUPPORTED (callers compose
+ * the decode and torch ops) for sources in different groups, SEA_F32, S above 640 and more than 128 members.  Notes the form "decode.derived_verify"
+ * (a = the padded hidden width, b = the dynamic LDS bytes).
+ * (Addition to ABI version 8; SeaDecodeMemberVerify and SeaDerivedField are reused unchanged.)
+ */
+int sea_decode_derived_verify(const SeaDecodeMseGroup* groups, int n_groups, const SeaDerivedField* derived, int n_derived,
+                              const SeaDecodeMemberVerify* p, int dtype, void* stream);
+
 /* Tuning aid: register a device buffer of n_steps * 64 8-byte words that the persistent form fills with 100 MHz clock stamps of its hand-offs
  * (tools/kv_persist_timeline.py); NULL switches it off. */
 void sea_kv_debug_stamps(unsigned long long* buf);

@@ -389,7 +389,7 @@ class SeaDecodeMemberBrier(C.Structure):
                 ("accumulate", _i32), ("pad_", _i32)]
 
 
-DERIVED_MAX = 8              # derived fields one launch of sea_decode_derived_quantiles / sea_decode_derived_brier carries
+DERIVED_MAX = 8              # derived fields one launch of sea_decode_derived_quantiles / sea_decode_derived_brier / sea_decode_derived_verify carries
 DERIVED_OPS = {"magnitude": 0, "energy": 1, "difference": 2}   # SEA_DERIVED_MAGNITUDE, SEA_DERIVED_ENERGY, SEA_DERIVED_DIFFERENCE
 
 
@@ -569,6 +569,8 @@ def lib() -> C.CDLL:
     L.sea_decode_derived_quantiles.restype = C.c_int
     L.sea_decode_derived_brier.argtypes = [C.POINTER(SeaDecodeMseGroup), C.c_int, C.POINTER(SeaDerivedField), C.c_int, C.POINTER(SeaDecodeMemberBrier), C.c_int, _vp]
     L.sea_decode_derived_brier.restype = C.c_int
+    L.sea_decode_derived_verify.argtypes = [C.POINTER(SeaDecodeMseGroup), C.c_int, C.POINTER(SeaDerivedField), C.c_int, C.POINTER(SeaDecodeMemberVerify), C.c_int, _vp]
+    L.sea_decode_derived_verify.restype = C.c_int
     L.sea_ensemble_brier.argtypes = [C.POINTER(SeaEnsembleBrier), _vp]
     L.sea_ensemble_brier.restype = C.c_int
     L.sea_ensemble_brier_ws_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
@@ -607,7 +609,7 @@ EXPORTED_SYMBOLS = (
     "sea_kv_cache_fill", "sea_kv_cache_fork", "sea_kv_cache_gather", "sea_decode_mse", "sea_decode_member_sse", "sea_decode_member_moments", "sea_decode_sensor_sse", "sea_decode_sensor_grad", "sea_decode_field_grad", "sea_resample_systematic", "sea_enkf_transform", "sea_enkf_transform_gram", "sea_decode_member_gram", "sea_ensemble_mix", "sea_ensemble_verify", "sea_ensemble_verify_ws_bytes", "sea_decode_member_verify", "sea_decode_member_verify_ws_bytes", "sea_decode_member_quantiles",
     "sea_decode_member_crps_grad", "sea_decode_member_crps_grad_ws_bytes", "sea_decode_member_crps_grad_packed",
     "sea_decode_member_brier", "sea_decode_member_brier_ws_bytes", "sea_ensemble_brier", "sea_ensemble_brier_ws_bytes",
-    "sea_decode_derived_quantiles", "sea_decode_derived_brier",
+    "sea_decode_derived_quantiles", "sea_decode_derived_brier", "sea_decode_derived_verify",
     "sea_gemm_fewrows", "sea_qkv_rope_fewrows", "sea_row_chain", "sea_row_chain_riders", "sea_gemm_adaln", "sea_mlp_block", "sea_adaln_qkv", "sea_splitk_finish",
     "sea_encoder_block_ws_floats", "sea_encoder_block_fwd", "sea_encoder_block_bwd",
     "sea_silu_outer_bwd_dc", "sea_silu_outer_bwd_dc_ws_floats", "sea_ib_bwd_dc",

@@ -3520,6 +3520,268 @@ extern "C" int sea_decode_derived_brier(const SeaDecodeMseGroup* groups, int n_g
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------------------------
+// sea_decode_derived_verify: sea_decode_member_verify for DERIVED fields — per cell the mean, spread, CRPS, PIT and rank of the members' derived
+// values, per (history, derived field) the fp64 sums and the rank histogram (include/sea_hip.h states the definitions).  Launch 1 is
+// decode_member_verify_kernel with grid.y = n_derived and the decode of its stage a replaced by the two-source decode of the derived kernels above
+// (mq_decode_pair_tile; the W2 stream a_0, b_0, a_1, b_1, ... through the two LDS images, two staging sets fetched behind stage b and stored in stage
+// c, the hidden rows loaded once).  The preamble and the stages b, c, d are RESTATED from decode_member_verify_kernel line for line, indexed by
+// derived field — that kernel stays textually unchanged, and a shared body would have put its pinned bits behind a refactoring; the arithmetic
+// itself is shared: vf_score_wave and vf_finish_reading (verify_score.hpp) score a derived cell as they score a cell of the member launch and a
+// sensor of sea_ensemble_verify.  Three barriers per tile, LDS at mv_lds_bytes<SP>() plus the member kernel's static part, the member launch's
+// workspace layout [(history, patch), chunk, derived field]; member_verify_finish_kernel adds the partials, handed n_derived for F.
+struct DerivedVerifyLaunch {
+    SeaDecodeMseGroup g[SEA_DECODE_MSE_MAX_GROUPS];
+    SeaDecodeMemberVerify p;
+    DerivedTable t;
+    int words;   // 8-byte words per (history, patch, chunk, derived field) of the workspace
+};
+
+template <int SP, int V>
+__global__ __launch_bounds__(MV_NT) void decode_derived_verify_kernel(const DerivedVerifyLaunch L) {
+#pragma clang fp reassociate(off)
+    constexpr int NW = MV_NW;
+    constexpr int NT = MV_NT;
+    constexpr int KS = SP / 32;
+    constexpr int PITCH = SP * 2 + DM_PAD;
+    constexpr int TILE = DM_TC * PITCH;
+    constexpr int NCH = SP * 4 / NT;
+    constexpr int VP = MV_VP;
+    static_assert(NCH * NT == DM_TC * (SP / 8), "whole chunks per thread");
+    extern __shared__ __attribute__((aligned(16))) char smem[];   // 2 tile images (source a's, source b's); the value image [32][VP]
+    float* Vs = reinterpret_cast<float*>(smem + 2 * TILE);
+    __shared__ double lw_s[VF_MAX_N], w_s[VF_MAX_N];
+    __shared__ int live_s[VF_MAX_N];
+    __shared__ VfReading r_s[DM_TC];
+    __shared__ double term_s[VF_SUMS][DM_TC];
+    __shared__ int hist_s[VF_MAX_N + 1];
+    __shared__ float y_s[DM_TC], pv_s[DM_TC];
+
+    const SeaDecodeMemberVerify& P = L.p;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), li = lane & 15, lg = lane >> 4;
+    const int S = P.S, C = P.C, Cp = P.Cp, N = P.members, D = L.t.n_derived, words = L.words;
+    const int bp = blockIdx.x, dg = blockIdx.y, ck = blockIdx.z, Q = gridDim.z;   // the derived field and the chunk of its tiles this workgroup scores
+    const int b = bp / P.P, patch = bp - b * P.P;
+    const int64_t ld = P.ld_out;
+    const int64_t obase = ((int64_t)bp * D + dg) * ld;
+    double* const wsum = reinterpret_cast<double*>(P.work) + (((int64_t)bp * Q + ck) * D + dg) * words;
+    int32_t* const whist = reinterpret_cast<int32_t*>(wsum + VF_SUMS);
+
+    int lim = C;   // valid columns of this patch: [0, lim) — uniform over the workgroup
+    if (P.counts != nullptr) {
+        const int cnt = P.counts[patch];
+        lim = cnt < 0 ? 0 : (cnt > C ? C : cnt);
+    }
+    const int tpf = (lim + DM_TC - 1) / DM_TC;   // tiles of a field that hold valid columns
+    const int tb = ck * MV_CHUNK, te = tpf < tb + MV_CHUNK ? tpf : tb + MV_CHUNK;   // this workgroup's tiles: [tb, te)
+
+    // the weights of the history (decode_member_verify_kernel's, line for line)
+    int invalid = 0, alive = 0;
+    if (tid < N) {
+        const float lw = P.logw != nullptr ? P.logw[(int64_t)b * N + tid] : 0.f;
+        invalid = (lw != lw || lw == INFINITY) ? 1 : 0;
+        alive = (!invalid && lw != -INFINITY) ? 1 : 0;
+        lw_s[tid] = (double)lw;
+        live_s[tid] = alive;
+    }
+    for (int r = tid; r <= N; r += NT) hist_s[r] = 0;
+    const int n_live = __syncthreads_count(alive);
+    invalid = __syncthreads_or(invalid);
+    const bool unscored = invalid || n_live == 0;
+    if (patch == 0 && dg == 0 && ck == 0 && tid == 0) P.status[b] = unscored ? -1 : n_live;
+    if (ck == 0) {   // the columns no tile walks (all of them when the history is not scored or the patch has no valid column): dead
+        const int c0 = (unscored || tpf == 0) ? 0 : tpf * DM_TC;
+        for (int64_t c = c0 + tid; c < ld; c += NT) {
+            const int64_t at = obase + c;
+            if (P.mean != nullptr) P.mean[at] = 0.f;
+            if (P.spread != nullptr) P.spread[at] = 0.f;
+            if (P.crps != nullptr) P.crps[at] = 0.f;
+            if (P.pit != nullptr) P.pit[at] = 0.f;
+            if (P.rank != nullptr) P.rank[at] = -1;
+        }
+    }
+    if (unscored || te <= tb) {   // uniform: nothing to score in this chunk
+        for (int e = tid; e < words; e += NT) wsum[e] = 0.0;   // the sums, and the int32 bins: all bits zero
+        return;
+    }
+    double mx = -INFINITY;
+    for (int j = 0; j < N; ++j) mx = lw_s[j] > mx ? lw_s[j] : mx;
+    if (tid < N) w_s[tid] = alive ? exp(lw_s[tid] - mx) : 0.0;
+    __syncthreads();
+    double W = 0.0;
+    for (int j = 0; j < N; ++j) W += w_s[j];
+    const double my_w = tid < N ? w_s[tid] / W : 0.0;
+    __syncthreads();   // every thread has read the exponentials
+    if (tid < N) w_s[tid] = my_w;
+    __syncthreads();
+    double q = 0.0;
+    for (int j = 0; j < N; ++j) q = fma(w_s[j], w_s[j], q);
+    const double cq = P.unbiased ? 1.0 - q : 1.0;
+
+    const int j0 = wave * 16;
+    const bool active = j0 < N;                 // uniform over the wave
+    const int jm = j0 + li;
+    const int64_t m = ((int64_t)b * N + (jm < N ? jm : 0)) * P.P + patch;
+    double acc_sum = 0.0;                       // threads 0 .. 7: the derived field's running sums
+
+    const SeaDerivedField& X = L.t.d[dg];
+    const SeaDecodeMseGroup& G = L.g[L.t.gsel[dg]];   // the group that holds both sources
+    const int ja = X.a - G.field0, jb = X.b - G.field0;   // the sources inside their group
+    const __bf16* H = static_cast<const __bf16*>(G.H);
+    const __bf16* W2 = static_cast<const __bf16*>(G.W2);
+    uint4 hf[KS];
+    mq_load_row<SP>(hf, H + m * G.ldh, S, lg);
+    const int n_tiles = te - tb, t0a = ja * tpf + tb, t0b = jb * tpf + tb;   // this chunk's tiles among the group's, per source
+    uint4 wa[NCH], wb[NCH];
+    dm_load_tile<SP, NT>(wa, W2, G.ldw, S, Cp, tpf, t0a, tid);
+    dm_load_tile<SP, NT>(wb, W2, G.ldw, S, Cp, tpf, t0b, tid);
+    dm_store_tile<SP, NT>(wa, smem, tid);
+    dm_store_tile<SP, NT>(wb, smem + TILE, tid);
+    __syncthreads();
+
+    for (int t = 0; t < n_tiles; ++t) {
+        const int cb = (tb + t) * DM_TC;
+
+        // a: the columns' weights and readings (decode_member_verify_kernel's, by derived field); decode both sources into the value image
+        if (tid < DM_TC) {
+            const int c = cb + tid;
+            float w = 0.f;
+            if (c < lim) {
+                const float pf = P.prec_field != nullptr ? P.prec_field[dg] : 1.f;
+                const float pm = P.prec != nullptr ? P.prec[(int64_t)bp * P.ld_prow + (int64_t)dg * P.ld_pfield + c] : 1.f;
+                w = mul1(pf > 0.f ? pf : 0.f, pm > 0.f ? pm : 0.f);
+            }
+            const bool on = w > 0.f;   // false for NaN
+            pv_s[tid] = on ? w : 0.f;
+            y_s[tid] = on ? P.obs[(int64_t)bp * P.ld_row + (int64_t)dg * P.ld_field + c] : 0.f;
+        }
+        if (active) mq_decode_pair_tile<SP>(hf, smem, smem + TILE, G.bias + ja * Cp + cb, G.bias + jb * Cp + cb, S, li, lg, X, Vs + j0);
+        __syncthreads();
+        if (t + 1 < n_tiles) {   // in flight behind b
+            dm_load_tile<SP, NT>(wa, W2, G.ldw, S, Cp, tpf, t0a + t + 1, tid);
+            dm_load_tile<SP, NT>(wb, W2, G.ldw, S, Cp, tpf, t0b + t + 1, tid);
+        }
+
+        // b: a column per wave at a time
+        for (int cl = wave; cl < DM_TC; cl += NW) {
+            const float pv = pv_s[cl];
+            if (!(pv > 0.f)) {   // the same word in every lane
+                if (lane == 0) r_s[cl].state = 1;
+                continue;
+            }
+            const VfReading r = vf_score_wave<V>(Vs + cl * VP, w_s, live_s, N, lane, y_s[cl], pv);
+            if (lane == 0) r_s[cl] = r;
+        }
+        __syncthreads();
+
+        // c: thread k finishes column k
+        if (tid < DM_TC) {
+            double tm[VF_SUMS];
+            const VfReading r = r_s[tid];
+            const VfOut o = vf_finish_reading(r, y_s[tid], pv_s[tid], cq, tm);
+            if (r.state == 0) atomicAdd(&hist_s[o.rank], 1);   // LDS, integers: the order does not matter; 0 <= rank <= N
+            const int c = cb + tid;
+            if (c < ld) {
+                const int64_t at = obase + c;
+                if (P.mean != nullptr) P.mean[at] = o.mean;
+                if (P.spread != nullptr) P.spread[at] = o.spread;
+                if (P.crps != nullptr) P.crps[at] = o.crps;
+                if (P.pit != nullptr) P.pit[at] = o.pit;
+                if (P.rank != nullptr) P.rank[at] = o.rank;
+            }
+#pragma unroll
+            for (int i = 0; i < VF_SUMS; ++i) term_s[i][tid] = tm[i];
+        }
+        if (t + 1 < n_tiles) {
+            dm_store_tile<SP, NT>(wa, smem, tid);
+            dm_store_tile<SP, NT>(wb, smem + TILE, tid);
+        }
+        __syncthreads();
+
+        // d: the derived field's sums, columns ascending (the next tile's terms are filed two barriers ahead)
+        if (tid < VF_SUMS)
+            for (int k = 0; k < DM_TC; ++k) acc_sum += term_s[tid][k];
+    }
+    if (tid < VF_SUMS) wsum[tid] = acc_sum;
+    for (int r = tid; r <= N; r += NT) whist[r] = hist_s[r];   // every integer add lies behind the last tile's barrier
+}
+
+template <int SP, int V>
+static void derived_verify_launch(const DerivedVerifyLaunch& L, dim3 grid, hipStream_t s) {
+    constexpr int lds = mv_lds_bytes<SP>();
+    static bool set_on[64] = {false};   // per device, as above
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = -1;
+    if (dev < 0 || !set_on[dev]) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(decode_derived_verify_kernel<SP, V>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        if (dev >= 0) set_on[dev] = true;
+    }
+    decode_derived_verify_kernel<SP, V><<<grid, dim3(MV_NT), lds, s>>>(L);
+    sea_note_form("decode.derived_verify", SP, lds);
+}
+
+template <int V>
+static void derived_verify_dispatch(const DerivedVerifyLaunch& L, dim3 grid, hipStream_t s) {
+    if (L.p.S <= 128) derived_verify_launch<128, V>(L, grid, s);
+    else if (L.p.S <= 256) derived_verify_launch<256, V>(L, grid, s);
+    else if (L.p.S <= 384) derived_verify_launch<384, V>(L, grid, s);
+    else if (L.p.S <= 512) derived_verify_launch<512, V>(L, grid, s);
+    else derived_verify_launch<640, V>(L, grid, s);
+}
+
+extern "C" int sea_decode_derived_verify(const SeaDecodeMseGroup* groups, int n_groups, const SeaDerivedField* derived, int n_derived, const SeaDecodeMemberVerify* p,
+                                         int dtype, void* stream) {
+    const char* who = "sea_decode_derived_verify";
+    SEA_REQUIRE(groups != nullptr && derived != nullptr && p != nullptr, "%s: null argument table", who);
+    SEA_REQUIRE(n_groups >= 1 && n_groups <= SEA_DECODE_MSE_MAX_GROUPS, "%s: n_groups=%d outside 1..%d", who, n_groups, SEA_DECODE_MSE_MAX_GROUPS);
+    SEA_REQUIRE(n_derived >= 1 && n_derived <= SEA_DERIVED_MAX, "%s: n_derived=%d outside 1..%d", who, n_derived, SEA_DERIVED_MAX);
+    SEA_REQUIRE(dtype == SEA_F32 || dtype == SEA_BF16, "%s: bad dtype %d", who, dtype);
+    if (dtype != SEA_BF16) {
+        sea_set_error("%s: unsupported: bf16 only (the fp32 decoder composes the decode, the derived values and sea_ensemble_verify's formulas)", who);
+        return SEA_EUNSUPPORTED;
+    }
+    const SeaDecodeMemberVerify& P = *p;
+    SEA_REQUIRE(P.obs != nullptr && P.sums != nullptr && P.hist != nullptr && P.status != nullptr && P.work != nullptr,
+                "%s: null pointer (obs, sums, hist, status and work are required; prec_field, prec, counts, logw and the maps may be NULL)", who);
+    const int rc = derived_check(who, groups, n_groups, derived, n_derived, P.M, P.S, P.C, P.Cp, P.P, P.members, P.n_fields_total);
+    if (rc != SEA_OK) return rc;
+    SEA_REQUIRE(P.ld_field >= P.C && P.ld_row >= 0, "%s: obs strides ld_row=%lld, ld_field=%lld must cover C=%d", who, (long long)P.ld_row, (long long)P.ld_field, P.C);
+    SEA_REQUIRE(P.prec == nullptr || (P.ld_pfield >= P.C && P.ld_prow >= 0), "%s: prec strides ld_prow=%lld, ld_pfield=%lld must cover C=%d", who, (long long)P.ld_prow,
+                (long long)P.ld_pfield, P.C);
+    SEA_REQUIRE((P.mean == nullptr && P.spread == nullptr && P.crps == nullptr && P.pit == nullptr && P.rank == nullptr) || (P.ld_out >= P.C && P.ld_out <= 0x7fffffffLL),
+                "%s: ld_out=%lld must cover C=%d", who, (long long)P.ld_out, P.C);
+    SEA_REQUIRE((P.unbiased == 0 || P.unbiased == 1) && (P.accumulate == 0 || P.accumulate == 1), "%s: unbiased=%d and accumulate=%d must be 0 or 1", who, P.unbiased,
+                P.accumulate);
+    SEA_REQUIRE(sea_aligned4(P.obs) && sea_aligned4(P.prec_field) && sea_aligned4(P.prec) && sea_aligned4(P.counts) && sea_aligned4(P.logw) && sea_aligned4(P.mean) &&
+                    sea_aligned4(P.spread) && sea_aligned4(P.crps) && sea_aligned4(P.pit) && sea_aligned4(P.rank) && sea_aligned4(P.status) &&
+                    (reinterpret_cast<uintptr_t>(P.sums) & 7u) == 0 && (reinterpret_cast<uintptr_t>(P.hist) & 7u) == 0 && (reinterpret_cast<uintptr_t>(P.work) & 7u) == 0,
+                "%s: misaligned pointer (f32 and int32 buffers need 4 bytes; sums, hist and work 8)", who);
+
+    DerivedVerifyLaunch L;
+    memset(&L, 0, sizeof(L));
+    const int ru = derived_resolve(who, groups, n_groups, derived, n_derived, P.S, P.members, L.t);
+    if (ru != SEA_OK) return ru;
+    const int64_t BP = (int64_t)P.M / P.members;   // (history, patch) pairs
+    const int64_t B = BP / P.P;
+    const int64_t need = sea_decode_member_verify_ws_bytes((int)B, P.P, n_derived, P.members, P.Cp);
+    SEA_REQUIRE(P.work_bytes >= need, "%s: work_bytes=%lld below the %lld that sea_decode_member_verify_ws_bytes(B=%d, P=%d, n_derived=%d, members=%d, Cp=%d) asks for", who,
+                (long long)P.work_bytes, (long long)need, (int)B, P.P, n_derived, P.members, P.Cp);
+    SEA_REQUIRE((int64_t)P.P * mv_chunks(P.Cp) <= 0x7fffffffLL && mv_chunks(P.Cp) <= 65535, "%s: Cp=%d has too many column chunks", who, P.Cp);
+
+    for (int g = 0; g < n_groups; ++g) L.g[g] = groups[g];
+    L.p = P;
+    L.words = (int)mv_words(P.members);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)BP, (unsigned)n_derived, (unsigned)mv_chunks(P.Cp));
+    if (P.members <= 64) derived_verify_dispatch<1>(L, grid, s);
+    else derived_verify_dispatch<2>(L, grid, s);
+    SeaDecodeMemberVerify Pd = P;   // the finish launch reads its partials by derived field
+    Pd.n_fields_total = n_derived;
+    member_verify_finish_kernel<<<dim3((unsigned)B), dim3(256), 0, s>>>(Pd, mv_chunks(P.Cp), L.words);
+    SEA_CHECK_LAUNCH("sea_decode_derived_verify");
+    return SEA_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------------------------
 // sea_decode_member_crps_grad: the CRPS of the decoded fields per (history, field) WITH its gradient to the hidden rows (include/sea_hip.h states
 // the formulas) — decode_member_verify_kernel crossed with stage 2 of decode_mse_kernel.  Launch 1 keeps member_verify's grid, a workgroup per
 // (history, patch, field, chunk of MV_CHUNK tiles), and its decode, weights, walk and sums line for line (no maps, no histogram): the fp64 sums

@@ -2113,7 +2113,8 @@ def _derived_thresholds(what: str, thresholds, nd: int, max_t: int, finite: bool
 
 
 class _DerivedBase:
-    """What DerivedQuantiles and DerivedThresholdVerification share: the constructor's checks, the thresholds per device and the default rule."""
+    """What DerivedQuantiles, DerivedThresholdVerification and DerivedVerification share: the constructor's checks, the thresholds per device, the states'
+    re-layout, the valid-cell mask and (the two verifying classes, which set self.observed) the observation brought to derived readings."""
     _what = "Derived"
 
     def _init_common(self, decoder, n_patches, members, derived, counts, layout, fused, max_n: int):
@@ -2161,6 +2162,36 @@ class _DerivedBase:
             return None
         cnt = torch.as_tensor(self.counts, dtype=torch.int64).to(device).clamp(0, C_)
         return (torch.arange(C_, device=device) < cnt[:, None]).view(1, P, 1, C_)
+
+    def _observation(self, obs, precision, B: int, device):
+        """obs and precision checked and brought to derived readings: (obs [B, P, n_derived, W], precision [B, P, n_derived, W] or None)."""
+        what, P, nd = self._what, self.n_patches, len(self.derived)
+        width = self.n_fields if self.observed == "fields" else nd
+        if not torch.is_tensor(obs) or obs.dim() != 4 or tuple(obs.shape[:2]) != (B, P):
+            raise ValueError(f"{what}: the observation must be [{B}, {P}, ...] in layout {self.layout} (one snapshot per history), got "
+                             f"{tuple(obs.shape) if torch.is_tensor(obs) else type(obs).__name__}")
+        if obs.dtype != torch.float32 or obs.device != device:
+            raise ValueError(f"{what}: obs must be float32 on {device}, got {obs.dtype} on {obs.device}")
+        if precision is not None:
+            if not torch.is_tensor(precision) or tuple(precision.shape) != tuple(obs.shape):
+                raise ValueError(f"{what}: precision must be None or a map of obs's shape {tuple(obs.shape)}, got "
+                                 f"{tuple(precision.shape) if torch.is_tensor(precision) else type(precision).__name__}")
+            if precision.dtype != torch.float32 or precision.device != device:
+                raise ValueError(f"{what}: precision must be float32 on {device}, got {precision.dtype} on {precision.device}")
+            if precision.device.type == "cpu" and (not bool(torch.isfinite(precision).all()) or not bool((precision >= 0).all())):
+                raise ValueError(f"{what}: precision must be finite and >= 0")
+        perm = (lambda t: t) if self.layout == "BPFC" else (lambda t: t.permute(0, 1, 3, 2))
+        obs, precision = perm(obs.detach()), None if precision is None else perm(precision.detach())
+        if obs.shape[2] != width:
+            raise ValueError(f"{what}: observed={self.observed!r}: the observation must carry {width} fields in layout {self.layout}, got shape {tuple(obs.shape)}")
+        if self.observed == "derived":
+            return obs, precision
+        with torch.no_grad():
+            x = _composed_derived(obs, self.derived)
+            if precision is not None:   # live where both source cells are: the product of two 0 / 1 flags
+                on = (precision > 0).to(torch.float32)
+                precision = torch.stack([on.select(2, d.a) * on.select(2, d.b) for d in self.derived], dim=2)
+        return x, precision
 
 
 class DerivedQuantiles(_DerivedBase):
@@ -2262,36 +2293,6 @@ class DerivedThresholdVerification(_DerivedBase):
         self.thresholds = self._thr_src = _derived_thresholds(self._what, thresholds, len(self.derived), N.BRIER_MAX_T, finite=True)
         self.observed = observed
 
-    def _observation(self, obs, precision, B: int, device):
-        """obs and precision checked and brought to derived readings: (obs [B, P, n_derived, W], precision [B, P, n_derived, W] or None)."""
-        what, P, nd = self._what, self.n_patches, len(self.derived)
-        width = self.n_fields if self.observed == "fields" else nd
-        if not torch.is_tensor(obs) or obs.dim() != 4 or tuple(obs.shape[:2]) != (B, P):
-            raise ValueError(f"{what}: the observation must be [{B}, {P}, ...] in layout {self.layout} (one snapshot per history), got "
-                             f"{tuple(obs.shape) if torch.is_tensor(obs) else type(obs).__name__}")
-        if obs.dtype != torch.float32 or obs.device != device:
-            raise ValueError(f"{what}: obs must be float32 on {device}, got {obs.dtype} on {obs.device}")
-        if precision is not None:
-            if not torch.is_tensor(precision) or tuple(precision.shape) != tuple(obs.shape):
-                raise ValueError(f"{what}: precision must be None or a map of obs's shape {tuple(obs.shape)}, got "
-                                 f"{tuple(precision.shape) if torch.is_tensor(precision) else type(precision).__name__}")
-            if precision.dtype != torch.float32 or precision.device != device:
-                raise ValueError(f"{what}: precision must be float32 on {device}, got {precision.dtype} on {precision.device}")
-            if precision.device.type == "cpu" and (not bool(torch.isfinite(precision).all()) or not bool((precision >= 0).all())):
-                raise ValueError(f"{what}: precision must be finite and >= 0")
-        perm = (lambda t: t) if self.layout == "BPFC" else (lambda t: t.permute(0, 1, 3, 2))
-        obs, precision = perm(obs.detach()), None if precision is None else perm(precision.detach())
-        if obs.shape[2] != width:
-            raise ValueError(f"{what}: observed={self.observed!r}: the observation must carry {width} fields in layout {self.layout}, got shape {tuple(obs.shape)}")
-        if self.observed == "derived":
-            return obs, precision
-        with torch.no_grad():
-            x = _composed_derived(obs, self.derived)
-            if precision is not None:   # live where both source cells are: the product of two 0 / 1 flags
-                on = (precision > 0).to(torch.float32)
-                precision = torch.stack([on.select(2, d.a) * on.select(2, d.b) for d in self.derived], dim=2)
-        return x, precision
-
     def from_fields(self, Y: torch.Tensor, obs: torch.Tensor, precision: Optional[torch.Tensor] = None, logw: Optional[torch.Tensor] = None,
                     into: Optional["ThresholdScores"] = None, maps=()) -> "ThresholdScores":
         """The composed path on members' decoded fields Y [B, members, P, n_fields, n_inp] (scaled units, any float dtype, CPU or device)."""
@@ -2326,5 +2327,107 @@ class DerivedThresholdVerification(_DerivedBase):
                                               into=None if into is None else dict(sums=into.sums, hist=into.hist, hits=into.hits))
         return ThresholdScores(prob=r.get("prob"), brier_map=r.get("brier"), sums=r["sums"], hist=r["hist"], hits=r["hits"], status=r["status"], thresholds=thr,
                                weighted=logw is not None or (into is not None and into.weighted))
+
+    verify = __call__
+
+
+# ------------------------------------------------------------------------------------------------ derived fields: CRPS, rank and spread of the speed
+# fused=None: the fused launches from this many decoder rows (B * members * n_patches) on — the smallest measured size (None would mean "nothing
+# measured": the composed path everywhere)
+DERIVED_VERIFY_FUSED_MIN_ROWS = 4096
+
+
+def _check_verify_call(what: str, maps, logw, into, shape, Bm: int, n: int, device):
+    """maps, logw and into of a field-verification call, checked (FieldVerification's checks); returns (maps, logw as a contiguous float32 [Bm] or None)."""
+    maps = tuple(maps)
+    if any(k not in FIELD_MAPS for k in maps) or len(set(maps)) != len(maps):
+        raise ValueError(f"{what}: maps must be distinct names among {FIELD_MAPS}, got {maps!r}")
+    if logw is not None:
+        if not torch.is_tensor(logw) or not logw.is_floating_point() or logw.numel() != Bm or logw.dim() not in (1, 2) \
+                or (logw.dim() == 2 and logw.shape[1] != n) or logw.device != device:
+            raise ValueError(f"{what}: logw must be None or a floating-point [{Bm}] (or [{Bm // n}, {n}]) tensor of log-weights on {device}, got "
+                             f"{(tuple(logw.shape), str(logw.device)) if torch.is_tensor(logw) else type(logw).__name__}")
+        logw = logw.detach().reshape(-1).to(torch.float32).contiguous()
+    if into is not None:
+        if not isinstance(into, FieldScores) or tuple(into.sums.shape) != shape + (N.VERIFY_SUMS,) or tuple(into.hist.shape) != shape + (n + 1,) \
+                or into.sums.device != device or into.sums.dtype != torch.float64 or into.hist.dtype != torch.int64 \
+                or not into.sums.is_contiguous() or not into.hist.is_contiguous():
+            raise ValueError(f"{what}: into must be an earlier FieldScores for {shape[0]} histories of {n} members and {shape[1]} derived fields on {device}")
+    return maps, logw
+
+
+class DerivedVerification(_DerivedBase, _FieldObserver):
+    """FieldVerification for DERIVED fields — is the ensemble of the SPEED calibrated, is its spread the size of its error, what is its CRPS, is its rank
+    histogram flat, what inflation does it suggest: verify(y, obs, precision=None, logw=None, into=None, maps=...) -> FieldScores with n_derived where
+    FieldVerification has n_fields (include/sea_hip.h, sea_decode_derived_verify).  None of this follows from the scores of u and v: the derived value is
+    formed per member (DerivedField), before the scoring.  pooled(), rmse, spread_skill, consistency, suggested_inflation and the rest of FieldScores work
+    as they are; the maps go to the mesh with MeshUnpatcher.unpatch_derived (they are in physical units already).
+
+    derived, counts, layout, y and logw as in DerivedThresholdVerification; unbiased, maps and into as in FieldVerification.  sigma: None, a number or
+    n_derived numbers — the observation-error standard deviation in the derived field's own (physical) units, folded into a per-derived-field precision
+    1 / sigma_d^2 as FieldVerification folds its sigma; 1 / weight is the observation-error variance that `consistency` and `suggested_inflation` use.
+    observed="fields": obs (and precision) is the snapshot of the SOURCE fields that FieldVerification takes — [B, P, n_fields, >= n_inp] in layout
+    "BPFC", scaled units; the observed derived value is formed from it with _composed_derived's arithmetic, on the device; a derived cell is live only
+    where both of its source cells are (precision > 0 in both), and its weight is 1 / sigma_d^2: a source precision map has no defined image under a
+    nonlinear op, it only decides liveness.  observed="derived": obs and precision are [B, P, n_derived, >= n_inp] readings of the derived quantities
+    themselves (a PIV speed map), in their own units; the weight of a cell is precision / sigma_d^2, as in FieldVerification.
+    fused: True — the decoder's first layer plus the two launches of sea_decode_derived_verify (bf16, up to 128 members, up to 8 derived fields whose two
+    sources share a decoder group): neither the members' decoded fields nor the derived fields are written; raises where the launch refuses.  False —
+    Decode.forward plus _composed_derived plus _composed_field_verify (the composed path: fp32, any member count, sources in different groups; it holds the
+    members' fields several times over).  None — the fused launches where they serve (bf16, up to 128 members, up to 8 derived fields, both sources in one
+    decoder group) from 4096 decoder rows (B * members * n_patches, DERIVED_VERIFY_FUSED_MIN_ROWS) on, and the composed path everywhere else — the measured
+    rule (tools/derived_verify_bench.py, profiles/derived_verify_bench.txt; the speed of the cylinder decoder, P = 64 patches, n_inp
+    1628, the mesh's counts, observed="fields", maps on and off, device time per call): 64 members, one history (4096 rows) 0.43 ms fused against 2.56 ms
+    composed; 64 members, four histories (16384 rows) 0.82 against 8.8 ms; 128 members, one history (8192 rows) 0.82 against 3.45 ms; 128 members, four
+    histories (32768 rows) 1.60 against 12.8 ms; 16 launches against 177; 9 - 70 MB of extra memory against 0.7 - 5.5 GB.  Nothing was measured below
+    4096 rows, so the composed path stays the default there.
+    from_fields(Y, obs, ...) runs the composed arithmetic on members' decoded fields [B, members, P, F, n_inp] that already exist (CPU or device).
+    A call reads nothing back from the device.  `decoder` is a sea_amd Decode; no autograd graph is built."""
+    _what = "DerivedVerification"
+
+    def __init__(self, decoder, n_patches: int, members: int, derived, counts=None, layout: str = "BPFC", sigma=None, unbiased: bool = True,
+                 observed: str = "fields", fused: Optional[bool] = None):
+        if observed not in ("fields", "derived"):
+            raise ValueError(f"{self._what}: observed must be 'fields' or 'derived', got {observed!r}")
+        self._init_common(decoder, n_patches, members, derived, counts, layout, fused, N.FIELD_VERIFY_MAX_N)
+        self._thr_src = None
+        self.observed, self.unbiased = observed, bool(unbiased)
+        self._set_sigma(sigma, len(self.derived))
+
+    def _scores(self, r) -> FieldScores:
+        return FieldScores(**{k: r.get(k) for k in FIELD_MAPS}, sums=r["sums"], hist=r["hist"], status=r["status"])
+
+    def from_fields(self, Y: torch.Tensor, obs: torch.Tensor, precision: Optional[torch.Tensor] = None, logw: Optional[torch.Tensor] = None,
+                    into: Optional[FieldScores] = None, maps=FIELD_MAPS) -> FieldScores:
+        """The composed path on members' decoded fields Y [B, members, P, n_fields, n_inp] (scaled units, any float dtype, CPU or device)."""
+        if not torch.is_tensor(Y) or Y.dim() != 5 or Y.shape[1] != self.members or Y.shape[2] != self.n_patches or Y.shape[3] != self.n_fields:
+            raise ValueError(f"{self._what}: Y must be [B, {self.members}, {self.n_patches}, {self.n_fields}, n_inp], got "
+                             f"{tuple(Y.shape) if torch.is_tensor(Y) else type(Y).__name__}")
+        B, n, P, _, C_ = Y.shape
+        nd = len(self.derived)
+        x_obs, prec = self._observation(obs, precision, B, Y.device)
+        if x_obs.shape[3] < C_:
+            raise ValueError(f"{self._what}: the observation carries {x_obs.shape[3]} cells per patch, the members' fields {C_}")
+        maps, logw = _check_verify_call(self._what, maps, logw, into, (B, nd), B * n, n, Y.device)
+        with torch.no_grad():
+            cnt = None if self.counts is None else torch.as_tensor(self.counts, dtype=torch.int64).to(Y.device)
+            w = _field_cell_weights((B, P, nd, C_), self._field_precision(Y.device), prec, cnt, Y.device)
+            r = _composed_field_verify(_composed_derived(Y.detach(), self.derived).view(B * n, P, nd, C_), x_obs, w, logw, n, self.unbiased, maps=maps)
+            if into is not None:
+                r["sums"], r["hist"] = into.sums.add_(r["sums"]), into.hist.add_(r["hist"])
+        return self._scores(r)
+
+    def __call__(self, y: torch.Tensor, obs: torch.Tensor, precision: Optional[torch.Tensor] = None, logw: Optional[torch.Tensor] = None,
+                 into: Optional[FieldScores] = None, maps=FIELD_MAPS) -> FieldScores:
+        z, Bm = self._states(y)
+        n = self.members
+        B = Bm // n
+        x_obs, prec = self._observation(obs, precision, B, y.device)
+        maps, logw = _check_verify_call(self._what, maps, logw, into, (B, len(self.derived)), Bm, n, y.device)
+        N.require_gpu(y, f"{self._what} states")
+        r = self.decoder.member_derived_verify(z, x_obs, n, self.derived, counts=self.counts, precision=prec, field_precision=self._field_precision(y.device),
+                                               logw=logw, unbiased=self.unbiased, fused=self.fused, maps=maps,
+                                               into=None if into is None else dict(sums=into.sums, hist=into.hist))
+        return self._scores(r)
 
     verify = __call__

@@ -1297,6 +1297,76 @@ class Decode(nn.Module):
             return ops.decode_derived_brier(self._hidden_groups(z, dt), derived, rows(obs), C, Cp, P, members, thr, prec_field=pf,
                                             prec=None if prec is None else rows(prec), counts=cnt, logw=lw, accumulate=into is not None, maps=maps, out=into, dtype=dt)
 
+    def member_derived_verify(self, z: torch.Tensor, obs: torch.Tensor, members: int, derived, counts=None, precision: Optional[torch.Tensor] = None,
+                              field_precision: Optional[torch.Tensor] = None, logw: Optional[torch.Tensor] = None, unbiased: bool = True,
+                              fused: Optional[bool] = None, maps=("mean", "spread", "crps", "pit", "rank"), into: Optional[dict] = None):
+        """member_verify for DERIVED fields (include/sea_hip.h, sea_decode_derived_verify; sea_amd.ensemble.DerivedField): the dict of member_verify with
+        n_derived where that has n_fields; no autograd graph.  z, counts, logw, unbiased, maps and into as in member_verify; derived: a sequence of
+        DerivedField; obs and precision float32 [B, P, n_derived, >= n_inp]: readings of the DERIVED quantities, in their own units
+        (ensemble.DerivedVerification forms them from a snapshot of the source fields); field_precision float32 [n_derived]: the weight of a cell is
+        w = valid ? max(field_precision, 0) * max(precision, 0) : 0, and 1 / w is its observation-error variance.
+        fused=True (bf16, members <= 128, up to 8 derived fields, each with both sources in one decoder group): the first-layer launch plus the TWO
+        launches of sea_decode_derived_verify — neither the members' decoded fields nor the derived fields are written; it raises where the launch
+        refuses.  fused=False: forward() plus ensemble._composed_derived plus ensemble._composed_field_verify (fp32, any member count, sources in
+        different groups, comparison).  fused=None: the fused launches where they serve, from ensemble.DERIVED_VERIFY_FUSED_MIN_ROWS = 4096 rows
+        (B * members * P) on — the rows of profiles/derived_verify_bench.txt (tools/derived_verify_bench.py) — and the composed
+        path elsewhere (everywhere if that constant is None)."""
+        from ..ensemble import DERIVED_VERIFY_FUSED_MIN_ROWS, FIELD_MAPS, _composed_derived, _composed_field_verify, _field_cell_weights
+
+        what = "sea_amd.Decode.member_derived_verify"
+        n_fields = sum(len(g) for g in self.field_groups)
+        C, Cp = self.n_inp, self._n_inp_p
+        min_rows = DERIVED_VERIFY_FUSED_MIN_ROWS
+        derived, Bm, P, B, fused = self._derived_call(what, z, members, derived, False if fused is None and min_rows is None else fused, N.FIELD_VERIFY_MAX_N,
+                                                      0 if min_rows is None else min_rows)
+        nd = len(derived)
+        for name, t in (("obs", obs), ("precision", precision)):
+            if t is None and name == "precision":
+                continue
+            if not torch.is_tensor(t) or t.dim() != 4 or tuple(t.shape[:3]) != (B, P, nd) or t.shape[3] < C:
+                raise ValueError(f"{what}: {name} must be [{B}, {P}, {nd}, >= {C}] (one per history of {members} members), got "
+                                 f"{tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
+            if t.dtype != torch.float32 or t.device != z.device:
+                raise ValueError(f"{what}: {name} must be float32 on {z.device}, got {t.dtype} on {t.device}")
+        if precision is not None and precision.shape[3] != obs.shape[3]:
+            raise ValueError(f"{what}: precision must have obs's shape {tuple(obs.shape)}, got {tuple(precision.shape)}")
+        if field_precision is not None and (not torch.is_tensor(field_precision) or field_precision.dtype != torch.float32 or tuple(field_precision.shape) != (nd,)
+                                            or field_precision.device != z.device):
+            raise ValueError(f"{what}: field_precision must be None or a float32 [{nd}] tensor on {z.device}")
+        if logw is not None and (not torch.is_tensor(logw) or logw.dtype != torch.float32 or tuple(logw.shape) != (Bm,) or logw.device != z.device):
+            raise ValueError(f"{what}: logw must be None or a float32 [{Bm}] tensor on {z.device}")
+        maps = tuple(maps)
+        if any(k not in FIELD_MAPS for k in maps) or len(set(maps)) != len(maps):
+            raise ValueError(f"{what}: maps must be distinct names among {FIELD_MAPS}, got {maps!r}")
+        if into is not None and (not isinstance(into, dict) or set(into) != {"sums", "hist"} or any(
+                not torch.is_tensor(t) or tuple(t.shape) != sh or t.dtype != dt_ or t.device != z.device or not t.is_contiguous()
+                for t, sh, dt_ in ((into.get("sums"), (B, nd, N.VERIFY_SUMS), torch.float64), (into.get("hist"), (B, nd, members + 1), torch.int64)))):
+            raise ValueError(f"{what}: into must be a dict of contiguous sums float64 [{B}, {nd}, {N.VERIFY_SUMS}] and hist int64 [{B}, {nd}, {members + 1}] on {z.device}")
+        cnt, _ = self._valid_counts(counts, P, z.device, allow_empty=True, what="member_derived_verify")
+        N.require_gpu(z, "Decode.member_derived_verify input")
+        with torch.no_grad():
+            obs = obs.detach()
+            prec = None if precision is None else precision.detach()
+            pf = None if field_precision is None else field_precision.detach().contiguous()
+            lw = None if logw is None else logw.detach().contiguous()
+            if not fused:
+                y = self.forward(z.detach()).view(B, members, P, n_fields, C)
+                x = _composed_derived(y, derived).view(Bm, P, nd, C)
+                w = _field_cell_weights((B, P, nd, C), pf, prec, cnt, z.device)
+                r = _composed_field_verify(x, obs, w, lw, members, bool(unbiased), maps=maps)
+                if into is not None:
+                    r["sums"], r["hist"] = into["sums"].add_(r["sums"]), into["hist"].add_(r["hist"])
+                return r
+
+            def rows(t):   # [B * P, n_derived, width] with unit inner stride: a view where the layout allows it, else one copy of the first C columns
+                t3 = t.reshape(B * P, nd, t.shape[3])
+                return t3 if t3.stride(2) == 1 and t3.stride(1) >= C and t3.stride(0) >= 0 else t3[..., :C].contiguous()
+
+            dt = self._act_dtype()
+            return ops.decode_derived_verify(self._hidden_groups(z, dt), derived, rows(obs), C, Cp, P, members, prec_field=pf,
+                                             prec=None if prec is None else rows(prec), counts=cnt, logw=lw, unbiased=bool(unbiased),
+                                             accumulate=into is not None, maps=maps, out=into, dtype=dt)
+
     def forward_prefix(self, z: torch.Tensor, buckets) -> torch.Tensor:
         """The decoder for a consumer that only reads the first cells of a patch (MeshUnpatcher.decode_and_unpatch: a patch holds as many mesh points as its
         cell has, the rest of its n_inp columns is padding nobody reads — 71 % of the columns on the bench's wake-refined mesh).  z [B, P, n_groups,

@@ -2511,3 +2511,65 @@ def decode_derived_brier(groups: Sequence[Dict], derived: Sequence, obs: torch.T
     fill_derived_table(tab, derived)
     N.check(N.lib().sea_decode_derived_brier(arr, len(groups), tab, nd, C.byref(P), N.dtype_code(dtype), N.stream_ptr()), "sea_decode_derived_brier")
     return res
+
+
+def decode_derived_verify(groups: Sequence[Dict], derived: Sequence, obs: torch.Tensor, C_: int, Cp: int, n_patches: int, members: int,
+                          prec_field: Optional[torch.Tensor] = None, prec: Optional[torch.Tensor] = None, counts: Optional[torch.Tensor] = None,
+                          logw: Optional[torch.Tensor] = None, unbiased: bool = True, accumulate: bool = False, maps: Sequence[str] = FIELD_VERIFY_MAPS,
+                          out: Optional[Dict[str, torch.Tensor]] = None, dtype: torch.dtype = torch.bfloat16) -> Dict[str, torch.Tensor]:
+    """sea_decode_derived_verify: decode_member_verify for DERIVED fields — CRPS, PIT, rank, mean and spread of the members' derived values at every cell,
+    and per (history, derived field) the fp64 sums and the rank histogram (include/sea_hip.h states the definitions); neither the decoded components
+    nor the derived field are written.  groups, counts, logw, unbiased, accumulate, maps, out as decode_member_verify; derived: 1 .. 8
+    sea_amd.ensemble.DerivedField; obs and prec f32 [B * n_patches, n_derived, >= C] readings of the derived quantities, in their own units; prec_field
+    f32 [n_derived].  Returns decode_member_verify's dict with n_derived where that has n_fields.  The launch refuses sources in different groups
+    (RuntimeError, code -3): Decode.member_derived_verify composes there.  Everything is checked on the host before the launch."""
+    what = "decode_derived_verify"
+    dev, M, S, n_fields, B = _check_derived_call(what, groups, derived, C_, Cp, n_patches, members, N.FIELD_VERIFY_MAX_N, dtype)
+    n, nd = members, len(derived)
+    for name, t in (("obs", obs), ("prec", prec)):
+        if t is None and name == "prec":
+            continue
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or t.dim() != 3 or tuple(t.shape[:2]) != (B * n_patches, nd) or t.shape[2] < C_ or t.stride(2) != 1 \
+                or t.device != dev or t.stride(1) < C_ or (t.shape[0] > 1 and t.stride(0) < 0):
+            raise ValueError(f"{what}: {name} must be a float32 [{B * n_patches}, {nd}, >= {C_}] tensor with unit inner stride on {dev}, got "
+                             f"{(tuple(t.shape), t.dtype, t.stride(), str(t.device)) if torch.is_tensor(t) else type(t).__name__}")
+    if prec_field is not None and (not torch.is_tensor(prec_field) or prec_field.dtype != torch.float32 or tuple(prec_field.shape) != (nd,)
+                                   or not prec_field.is_contiguous() or prec_field.device != dev):
+        raise ValueError(f"{what}: prec_field must be None or a contiguous float32 [{nd}] tensor on {dev}")
+    if counts is not None and (not torch.is_tensor(counts) or counts.dtype != torch.int32 or counts.dim() != 1 or counts.shape[0] != n_patches
+                               or not counts.is_contiguous() or counts.device != dev):
+        raise ValueError(f"{what}: counts must be a contiguous int32 [{n_patches}] on {dev}")
+    if logw is not None and (not torch.is_tensor(logw) or logw.dtype != torch.float32 or tuple(logw.shape) != (B * n,) or not logw.is_contiguous() or logw.device != dev):
+        raise ValueError(f"{what}: logw must be None or a contiguous float32 [{B * n}] tensor on {dev}, got "
+                         f"{(tuple(logw.shape), logw.dtype, str(logw.device)) if torch.is_tensor(logw) else type(logw).__name__}")
+    maps = tuple(maps)
+    if any(k not in FIELD_VERIFY_MAPS for k in maps) or len(set(maps)) != len(maps):
+        raise ValueError(f"{what}: maps must be distinct names among {FIELD_VERIFY_MAPS}, got {maps!r}")
+    out = {} if out is None else out
+    fixed = {"sums": ((B, nd, N.VERIFY_SUMS), torch.float64), "hist": ((B, nd, n + 1), torch.int64), "status": ((B,), torch.int32)}
+    if not isinstance(out, dict) or any(k not in fixed and k not in FIELD_VERIFY_MAPS for k in out):
+        raise ValueError(f"{what}: out must be a dict with keys among {FIELD_VERIFY_MAPS + tuple(fixed)}")
+    widths = {t.shape[-1] for k, t in out.items() if k in FIELD_VERIFY_MAPS and torch.is_tensor(t) and t.dim() == 4}
+    if len(widths) > 1:
+        raise ValueError(f"{what}: the maps in out must share their last dimension, got {sorted(widths)}")
+    ld_out = widths.pop() if widths else C_
+    for k, t in out.items():
+        shape, dt = fixed[k] if k in fixed else ((B, n_patches, nd, ld_out), torch.int32 if k == "rank" else torch.float32)
+        if not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != dev or ld_out < C_:
+            raise ValueError(f"{what}: out[{k!r}] must be a contiguous {dt} {list(shape)} tensor on {dev} (maps: last dimension >= {C_})")
+    if accumulate and ("sums" not in out or "hist" not in out):
+        raise ValueError(f"{what}: accumulate=True adds onto out['sums'] and out['hist']: both are required")
+    N.require_gpu(groups[0]["H"], f"{what} hidden rows")   # every operand is on their device (checked above)
+    res = {k: out[k] if k in out else torch.empty(fixed[k][0], device=dev, dtype=fixed[k][1]) for k in fixed}
+    for k in FIELD_VERIFY_MAPS:
+        if k in out:
+            res[k] = out[k]
+        elif k in maps:
+            res[k] = torch.empty(B, n_patches, nd, ld_out, device=dev, dtype=torch.int32 if k == "rank" else torch.float32)
+    work = torch.empty(int(N.lib().sea_decode_member_verify_ws_bytes(B, n_patches, nd, n, Cp)), device=dev, dtype=torch.uint8)
+    arr, tab, P = (N.SeaDecodeMseGroup * len(groups))(), (N.SeaDerivedField * nd)(), N.SeaDecodeMemberVerify()
+    fill_decode_member_verify(arr, P, groups, obs, prec_field, prec, counts, logw, n_patches, n, C_, Cp, unbiased, accumulate, res.get("mean"), res.get("spread"),
+                              res.get("crps"), res.get("pit"), res.get("rank"), res["sums"], res["hist"], res["status"], work, ld_out)
+    fill_derived_table(tab, derived)   # the maps are sized by the derived fields; n_fields_total stays the number of source fields
+    N.check(N.lib().sea_decode_derived_verify(arr, len(groups), tab, nd, C.byref(P), N.dtype_code(dtype), N.stream_ptr()), "sea_decode_derived_verify")
+    return res
