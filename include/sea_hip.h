@@ -50,8 +50,11 @@ const char* sea_last_error(void);
  * sea_mlp_block ("mlp_fc1.rows32", "mlp_fc2.rows32", "mlp_block.rows32"; a = per_xcd of the XCD-local tile order, 0 in the plain order, b = workgroups launched),
  * sea_gemm_adaln ("gemm_adaln.rows64", "gemm_adaln.rows128"; a = tiles), sea_exchange_tail ("xtail.rows16"; a = row tiles per group, b = segments),
  * sea_row_chain / sea_row_chain_riders ("chain.rows16", "chain.rows32"; a = rider tiles run in this launch, b = information-bottleneck workgroups) and
- * sea_adaln_qkv ("adaln_qkv.rows32", "adaln_qkv.rows32_mod3" with the third layer; a = rider tiles, b = row-rider workgroups).  Host only.  (An addition to
- * ABI version 8; no new struct.) */
+ * sea_adaln_qkv ("adaln_qkv.rows32", "adaln_qkv.rows32_mod3" with the third layer; a = rider tiles, b = row-rider workgroups), and by the row-walking
+ * backward launches: sea_rownorm_bwd ("normbwd.wave"; a = KMAX; "normbwd.wide4", "normbwd.wide8"; a = threads per workgroup; b = workgroups per group),
+ * sea_silu_outer_bwd ("silu_bwd.wave"; a = KM, b = workgroups per group; "silu_bwd.cols"; a = column blocks, b = row splits) — both with the suffix ".ws" when
+ * the column sums go through the two-stage workspace — and sea_ib_bwd ("ib_bwd.fast"; a = 1 or 4; "ib_bwd.wave"; a = 0; b = workgroups; "ib_bwd.cols"; a = column
+ * blocks, b = row splits; "ib_bwd.linear"; a = row chunks).  Host only.  (An addition to ABI version 8; no new struct.) */
 const char* sea_last_form(int* a, int* b);
 /* sizeof of every ABI struct in declaration order (SeaGemmGroup, SeaQkvGroup, SeaQkvCommon, SeaAttnProblem,
  * SeaAttnParams, SeaNormGroup, SeaSiluGroup, SeaIbParams, ..., SeaLaunchRec, SeaGemmNormGroup, SeaExchangeTail, SeaMlpGroup, SeaMlp2Group, SeaKvNorm, SeaKvField, SeaKvPair, SeaKvLayer, SeaKvGlobal, SeaStepPatch, SeaRowChain, SeaAdalnGroup, SeaAdalnQkv, SeaSplitkGroup, SeaEncBlock, SeaKvFill, SeaKvFork last): lets a binding verify its layout.  Host only. */

@@ -864,7 +864,7 @@ extern "C" int sea_rownorm_bwd(const SeaNormBwdGroup* groups, int n_groups, int 
     L.M = M; L.d = d; L.gelu = gelu; L.accumulate = accumulate;
     const bool wide = d > 1024;  // one workgroup per row: 256 threads up to 2048 columns, 512 up to 4096, 1024 beyond (2 / 2 / 2-4 chunks of 4 columns per thread)
     int nblk = wide ? M : (M + 3) / 4;
-    static const int nblk_cap = sea_tune("normbwd_blocks", 512);  // tuning aid
+    const int nblk_cap = sea_tune("normbwd_blocks", 512);  // tuning aid; read per call (tests force the forms in one process)
     if (nblk > nblk_cap) nblk = nblk_cap;
     if (wide) {
         // all workgroups of the launch resident at once (5 per CU at the wide kernel's 90 VGPRs): a second, partial round costs more than
@@ -924,6 +924,11 @@ extern "C" int sea_rownorm_bwd(const SeaNormBwdGroup* groups, int n_groups, int 
         F.ws = ws; F.nblk = nblk; F.stride = 2 * d;
         colsum_finish_kernel<<<dim3((2 * d + 255) / 256, n_groups, 16), dim3(256), 0, s>>>(F);
     }
+    // a: KMAX of the wave-per-row kernel, or the wide kernel's threads per workgroup; b: workgroups per group
+    const int form_a = !wide ? (d <= 256 ? 1 : (d <= 512 ? 2 : 4)) : (d <= 2048 ? 256 : (d <= 4096 ? 512 : 1024));
+    if (!wide) sea_note_form(two_stage ? "normbwd.wave.ws" : "normbwd.wave", form_a, nblk);
+    else if (wide8) sea_note_form(two_stage ? "normbwd.wide8.ws" : "normbwd.wide8", form_a, nblk);
+    else sea_note_form(two_stage ? "normbwd.wide4.ws" : "normbwd.wide4", form_a, nblk);
     SEA_CHECK_LAUNCH("sea_rownorm_bwd");
     return SEA_OK;
 }
@@ -1114,7 +1119,7 @@ __global__ __launch_bounds__(256) void silu_outer_bwd_cols_kernel(const SiluCols
 // The column-block form and its column-sum finish.  dcp != nullptr: the DC kernel, its per-(column block, row) partials in dcp [ncb][M].  Returns false
 // (nothing launched) when the workspace holds less than one row split.
 static bool silu_bwd_cols(const SeaSiluBwdGroup* groups, int n_groups, const float* c, int M, int dtype, float* ws, int64_t ws_floats, int maxk, float* dcp,
-                          hipStream_t s) {
+                          hipStream_t s, int* form = nullptr) {
     SiluColsLaunch Q;
     memset(&Q, 0, sizeof(Q));
     int ncb = 0;
@@ -1151,6 +1156,10 @@ static bool silu_bwd_cols(const SeaSiluBwdGroup* groups, int n_groups, const flo
     }
     F.ws = ws; F.nblk = rs; F.stride = 2 * maxk;
     colsum_finish_kernel<<<dim3((2 * maxk + 255) / 256, n_groups, rs < 16 ? rs : 16), dim3(256), 0, s>>>(F);
+    if (form != nullptr) {   // the launch's column blocks and row splits, for sea_note_form
+        form[0] = ncb;
+        form[1] = rs;
+    }
     return true;
 }
 
@@ -1169,17 +1178,20 @@ extern "C" int sea_silu_outer_bwd(const SeaSiluBwdGroup* groups, int n_groups, c
         maxk = G.K2 > maxk ? G.K2 : maxk;
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
-    static const int cols_form = sea_tune("silubwd_cols", 1);   // tuning aid: 0 = the one-wave-per-row kernel
-    if (cols_form && ws != nullptr && silu_bwd_cols(groups, n_groups, c, M, dtype, ws, ws_floats, maxk, nullptr, s)) {
+    const int cols_form = sea_tune("silubwd_cols", 1);   // tuning aid: 0 = the one-wave-per-row kernel; read per call (tests force the forms in one process)
+    int cols_ab[2] = {0, 0};
+    if (cols_form && ws != nullptr && silu_bwd_cols(groups, n_groups, c, M, dtype, ws, ws_floats, maxk, nullptr, s, cols_ab)) {
+        sea_note_form("silu_bwd.cols", cols_ab[0], cols_ab[1]);   // a: column blocks; b: row splits
         SEA_CHECK_LAUNCH("sea_silu_outer_bwd");
         return SEA_OK;
     }
     L.c = c; L.M = M;
     int nblk = (M + 3) / 4;
     // every workgroup of the launch resident at once (about 6 per CU): measured at cfg3 (12 groups) 128 per group 76 us, 160 90 us, 256 112 us
-    static const int sb_cap = sea_tune("silubwd_blocks", 0);  // tuning aid
-    int cap = sb_cap > 0 ? sb_cap : (6 * 256 / n_groups) / 32 * 32;
+    const int sb_cap = sea_tune("silubwd_blocks", 0);  // tuning aid; read per call (tests force the forms in one process)
+    int cap = (6 * 256 / n_groups) / 32 * 32;
     cap = cap < 32 ? 32 : (cap > 256 ? 256 : cap);
+    if (sb_cap > 0) cap = sb_cap > 256 ? 256 : sb_cap;   // a forced cap may go below 32: a wave then walks several rows at few rows
     if (nblk > cap) nblk = cap;
     const bool two_stage = ws != nullptr && ws_floats >= (int64_t)n_groups * nblk * 2 * maxk && nblk > 8;
     L.ws = two_stage ? ws : nullptr;
@@ -1211,6 +1223,7 @@ extern "C" int sea_silu_outer_bwd(const SeaSiluBwdGroup* groups, int n_groups, c
         F.ws = ws; F.nblk = nblk; F.stride = 2 * maxk;
         colsum_finish_kernel<<<dim3((2 * maxk + 255) / 256, n_groups, 16), dim3(256), 0, s>>>(F);
     }
+    sea_note_form(two_stage ? "silu_bwd.wave.ws" : "silu_bwd.wave", maxk <= 256 ? 1 : (maxk <= 512 ? 2 : (maxk <= 1024 ? 4 : 8)), nblk);   // a: KM; b: workgroups per group
     SEA_CHECK_LAUNCH("sea_silu_outer_bwd");
     return SEA_OK;
 }
@@ -1283,9 +1296,13 @@ __global__ __launch_bounds__(256) void ib_bwd_kernel(const SeaIbBwdParams P) {
         const float u = xh * lw + lb;
         const float hid = act ? gelu_erf(u) : 0.f;
         float dhid = 0.f;  // lane k will hold d(hid_k)
-        for (int e0 = lane * 4; e0 < E; e0 += 256) {
+        // the trip count is the wave's, not the lane's: hid_k is read from lane k, which must be active in every trip (a lane-dependent bound left only the
+        // lanes with a column in the last, partial chunk running — E = 1028: lane 0; E = 8: lanes 0 and 1 — and they read the registers of idle lanes)
+        for (int eb = 0; eb < E; eb += 256) {
+            const int e0 = eb + lane * 4;
+            const bool in = e0 < E;
             float dib[4] = {0.f, 0.f, 0.f, 0.f};
-            for (int f = 0; f < P.n_fields; ++f) {
+            for (int f = 0; in && f < P.n_fields; ++f) {
                 float v[4];
                 load4(P.dX[f] + (int64_t)row * P.ldx + e0, v);
                 if (P.drop.thr > 0) {
@@ -1297,12 +1314,16 @@ __global__ __launch_bounds__(256) void ib_bwd_kernel(const SeaIbBwdParams P) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) dib[e] += v[e];
             }
+            if (in) {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) atomicAdd(&s_b2[e0 + e], dib[e]);
+                for (int e = 0; e < 4; ++e) atomicAdd(&s_b2[e0 + e], dib[e]);
+            }
             for (int k = 0; k < h; ++k) {
                 const float hk = __shfl(hid, k);
+                if (in) {
 #pragma unroll
-                for (int e = 0; e < 4; ++e) atomicAdd(&s_w2[(e0 + e) * h + k], dib[e] * hk);
+                    for (int e = 0; e < 4; ++e) atomicAdd(&s_w2[(e0 + e) * h + k], dib[e] * hk);
+                }
             }
         }
         // dhid_k = sum_e dib[e] W2[e][k]: every lane re-walks its columns per k (E*h is small), then a wave sum per k
@@ -1700,6 +1721,7 @@ extern "C" int sea_ib_bwd(const SeaIbBwdParams* params, void* stream) {
         for (int f = 0; f < P.n_fields; ++f) SEA_REQUIRE(P.dX[f] != nullptr, "sea_ib_bwd (linear): dX[%d] null", f);
         const int chunks = P.M >= 4096 ? 64 : (P.M + 63) / 64;
         ib_linear_bwd_kernel<<<dim3((P.E + 63) / 64, chunks), dim3(256), 0, static_cast<hipStream_t>(stream)>>>(P);
+        sea_note_form("ib_bwd.linear", chunks, 0);   // a: row chunks
         SEA_CHECK_LAUNCH("sea_ib_bwd");
         return SEA_OK;
     }
@@ -1709,7 +1731,7 @@ extern "C" int sea_ib_bwd(const SeaIbBwdParams* params, void* stream) {
     SEA_REQUIRE(P.c && P.w1 && P.b1 && P.lnw && P.lnb && P.w2 && P.dw1 && P.db1 && P.dlnw && P.dlnb && P.dw2 && P.db2, "sea_ib_bwd: null pointer");
     for (int f = 0; f < P.n_fields; ++f) SEA_REQUIRE(P.dX[f] && sea_aligned16(P.dX[f]), "sea_ib_bwd: dX[%d] null or misaligned", f);
     hipStream_t s0 = static_cast<hipStream_t>(stream);
-    static const int cols_form = sea_tune("ibbwd_cols", 1);   // tuning aid: 0 = the one-wave-per-row kernels
+    const int cols_form = sea_tune("ibbwd_cols", 1);   // tuning aid: 0 = the one-wave-per-row kernels; read per call (tests force the forms in one process)
     if (cols_form && P.h <= 8 && P.ws != nullptr && P.dhid != nullptr && P.ws_floats >= (int64_t)P.E * (1 + P.h)) {
         const int n_cb = (P.E + 255) / 256;
         int rs = (1024 + n_cb - 1) / n_cb;                       // about four workgroups per CU in all
@@ -1723,6 +1745,7 @@ extern "C" int sea_ib_bwd(const SeaIbBwdParams* params, void* stream) {
         ib_bwd_rows_kernel<<<dim3((P.M + 255) / 256), dim3(256), 0, s0>>>(P, n_cb > 1 ? 1 : 0);
         const int n = P.E * (1 + P.h);
         ib_bwd_finish_kernel<<<dim3((n + 255) / 256 < 256 ? (n + 255) / 256 : 256, rs >= 64 ? 16 : 1), dim3(256), 0, s0>>>(P, rs);
+        sea_note_form("ib_bwd.cols", n_cb, rs);   // a: column blocks; b: row splits
         SEA_CHECK_LAUNCH("sea_ib_bwd");
         return SEA_OK;
     }
@@ -1730,12 +1753,15 @@ extern "C" int sea_ib_bwd(const SeaIbBwdParams* params, void* stream) {
     SEA_REQUIRE(lds <= 160 * 1024, "sea_ib_bwd: E*(h+1) too large for LDS");
     if (lds > 65536) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(ib_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     int nblk = (P.M + 3) / 4;
-    static const int ib_cap = sea_tune("ibbwd_blocks", 256);  // tuning aid
+    const int ib_cap = sea_tune("ibbwd_blocks", 256);  // tuning aid; read per call (tests force the forms in one process)
     if (nblk > ib_cap) nblk = ib_cap;
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (P.h <= 8 && P.E <= 256) ib_bwd_fast_kernel<1><<<dim3(nblk), dim3(256), lds, s>>>(P);
     else if (P.h <= 8 && P.E <= 1024) ib_bwd_fast_kernel<4><<<dim3(nblk), dim3(256), lds, s>>>(P);
     else ib_bwd_kernel<<<dim3(nblk), dim3(256), lds, s>>>(P);
+    // a: KE of the register form (0: the generic wave-per-row kernel); b: workgroups
+    if (P.h <= 8 && P.E <= 1024) sea_note_form("ib_bwd.fast", P.E <= 256 ? 1 : 4, nblk);
+    else sea_note_form("ib_bwd.wave", 0, nblk);
     SEA_CHECK_LAUNCH("sea_ib_bwd");
     return SEA_OK;
 }
