@@ -1813,6 +1813,49 @@ int sea_decode_derived_brier(const SeaDecodeMseGroup* groups, int n_groups, cons
 int sea_decode_derived_verify(const SeaDecodeMseGroup* groups, int n_groups, const SeaDerivedField* derived, int n_derived,
                               const SeaDecodeMemberVerify* p, int dtype, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Sparse sensors that read a DERIVED quantity: sea_decode_sensor_sse and sea_decode_sensor_grad for instruments that give a speed (hot-wire, Pitot
+ * tube, cup anemometer), an energy / dynamic pressure or a difference of two values (a differential tap) at a point — mixed freely with plain
+ * sensors.  SeaDecodeSensorSse, SeaDecodeSensorGrad and the SeaDecodeMseGroup operands are reused unchanged; one table struct is added.
+ * Layout.  A READING occupies two adjacent entries of the sorted, padded list: entry 2 i gathers the W2 row of source a (wrow[2 i]), entry 2 i + 1
+ * the W2 row of source b (wrow[2 i + 1]) — same group, same observed patch, same cell.  A (group, patch) segment is padded to a multiple of 32
+ * entries as before: 16 readings per tile.  With y[bm, k] EXACTLY sea_decode_sensor_sse's (the same accumulators, the same bits), ya = y[bm, 2 i],
+ * yb = y[bm, 2 i + 1]:
+ *     op[2 i] == -1 (plain)   x = ya                       (wrow[2 i + 1] is 0 and yb is not used)
+ *     otherwise               a' = ya * scale[2 i] + shift[2 i],  b' = yb * scale[2 i + 1] + shift[2 i + 1],  x = SEA_DERIVED_* of (a', b') as defined
+ *                             above for sea_decode_derived_quantiles: the same device function, every operation rounded once, the rounded root
+ *     w          = live[2 i] != 0 and prec[b * ld_prec + 2 i] > 0 ? prec[b * ld_prec + 2 i] : 0       (prec == NULL: 1)
+ *     d          = w > 0 ? x - obs[b * ld_obs + 2 i] : 0                 (a select; obs in the units of x)
+ *     wsse[bm]   = sum over pairs of (w d) d    (fp32; the lane's pairs per tile ascending, tiles ascending, the butterfly and finish launch of
+ *                                                sea_decode_sensor_sse)
+ *     pred[bm * K_pad + 2 i] = pred[bm * K_pad + 2 i + 1] = x            (when pred != NULL)
+ * live, obs and prec at the odd entries and op at the odd entries are not read.  sea_decode_derived_sensor_grad forms, in fp32 from the same a', b', x,
+ *     ga = dx / dya:  plain 1 | difference scale_a | energy a' scale_a | magnitude x > 0 ? a' scale_a / x : 0     (a select: exactly 0 at x == 0)
+ *     gb = dx / dyb:  plain 0 | difference -scale_b | energy b' scale_b | magnitude x > 0 ? b' scale_b / x : 0
+ *     (ga, gb are NOT single-rounded like x: the magnitude quotient is a' scale_a * rcp(x) with the hardware's approximate reciprocal v_rcp_f32, about
+ *      1 ulp of f32 — far below the rounding of r to the act dtype that follows)
+ *     r[2 i] = act(w d ga),  r[2 i + 1] = act(w d gb)                    (each rounded to the act dtype ONCE)
+ * and then runs sea_decode_sensor_grad's second product unchanged: dH = 2 grad_scale * sum_k r[bm, k] W2[wrow[k]] [* gelu_erf'(Z)]; every element of
+ * dH is written, rows of empty segments are exact zeros, and wsse and pred have the bits of sea_decode_derived_sensor_sse.
+ * Tables: op int32, scale f32, shift f32, each [K_pad] on the device, non-NULL and 16-byte aligned (a lane reads them by 16-byte loads, as obs and
+ * prec).  The kernels TRUST op (-1 or a SEA_DERIVED_* code at even entries), wrow and seg: the caller range-checks them on the host before the
+ * upload (sea_amd/ensemble.py, DerivedSensorSet).  No atomics, one writer per element: two runs give the same bits, and a member's outputs do not
+ * depend on `members`, on the number of histories or on its row tile.
+ * Everything sea_decode_sensor_sse / sea_decode_sensor_grad refuse is refused here, before any device is touched, with the entry point named in
+ * sea_last_error(); so is a NULL or misaligned table pointer.  SEA_F32 and S > 640 return SEA_EUNSUPPORTED.  Forms noted:
+ * "derived_sensor_sse.rows64", "derived_sensor_grad.rows64".
+ * (Additions to ABI version 8.  The struct is not in sea_struct_sizes(): sizeof(SeaDerivedSensorTables) is 24.)
+ */
+typedef struct {
+    const int32_t* op;       /* int32 [K_pad]: -1 plain, or SEA_DERIVED_* at entry 2 i */
+    const float* scale;      /* f32 [K_pad]: scale_a at 2 i, scale_b at 2 i + 1 */
+    const float* shift;      /* f32 [K_pad]: shift_a at 2 i, shift_b at 2 i + 1 */
+} SeaDerivedSensorTables;    /* 24 bytes */
+int sea_decode_derived_sensor_sse(const SeaDecodeMseGroup* groups, int n_groups, const SeaDecodeSensorSse* p, const SeaDerivedSensorTables* tables, int dtype,
+                                  void* stream);
+int sea_decode_derived_sensor_grad(const SeaDecodeMseGroup* groups, int n_groups, const SeaDecodeSensorGrad* p, const SeaDerivedSensorTables* tables, int dtype,
+                                   void* stream);
+
 /* Tuning aid: register a device buffer of n_steps * 64 8-byte words that the persistent form fills with 100 MHz clock stamps of its hand-offs
  * (tools/kv_persist_timeline.py); NULL switches it off. */
 void sea_kv_debug_stamps(unsigned long long* buf);

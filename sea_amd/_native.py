@@ -314,6 +314,11 @@ class SeaDecodeSensorGrad(C.Structure):
     _fields_ = SeaDecodeSensorSse._fields_ + [("grad_scale", _f32), ("pad_", _i32)]
 
 
+class SeaDerivedSensorTables(C.Structure):
+    # sea_decode_derived_sensor_sse / _grad: the pair tables of a DerivedSensorSet (not in ABI_STRUCTS; tests/test_derived_sensor_cpu.py checks the size)
+    _fields_ = [("op", _vp), ("scale", _vp), ("shift", _vp)]
+
+
 class SeaDecodeFieldGrad(C.Structure):
     # sea_decode_field_grad, 104 bytes (not in ABI_STRUCTS, like its siblings; tests/test_field_grad_cpu.py checks the layout through the library's argument checks)
     _fields_ = [("obs", _vp), ("prec", _vp), ("field_prec", _vp), ("counts", _vp), ("wsse", _vp), ("work", _vp),
@@ -531,6 +536,10 @@ def lib() -> C.CDLL:
     L.sea_decode_sensor_sse.restype = C.c_int
     L.sea_decode_sensor_grad.argtypes = [C.POINTER(SeaDecodeMseGroup), C.c_int, C.POINTER(SeaDecodeSensorGrad), C.c_int, _vp]
     L.sea_decode_sensor_grad.restype = C.c_int
+    L.sea_decode_derived_sensor_sse.argtypes = [C.POINTER(SeaDecodeMseGroup), C.c_int, C.POINTER(SeaDecodeSensorSse), C.POINTER(SeaDerivedSensorTables), C.c_int, _vp]
+    L.sea_decode_derived_sensor_sse.restype = C.c_int
+    L.sea_decode_derived_sensor_grad.argtypes = [C.POINTER(SeaDecodeMseGroup), C.c_int, C.POINTER(SeaDecodeSensorGrad), C.POINTER(SeaDerivedSensorTables), C.c_int, _vp]
+    L.sea_decode_derived_sensor_grad.restype = C.c_int
     L.sea_decode_field_grad.argtypes = [C.POINTER(SeaDecodeMseGroup), C.c_int, C.POINTER(SeaDecodeFieldGrad), C.c_int, _vp]
     L.sea_decode_field_grad.restype = C.c_int
     L.sea_decode_member_moments.argtypes = [C.POINTER(SeaDecodeMseGroup), C.c_int, C.POINTER(SeaDecodeMemberMoments), C.c_int, _vp]
@@ -609,7 +618,7 @@ EXPORTED_SYMBOLS = (
     "sea_kv_cache_fill", "sea_kv_cache_fork", "sea_kv_cache_gather", "sea_decode_mse", "sea_decode_member_sse", "sea_decode_member_moments", "sea_decode_sensor_sse", "sea_decode_sensor_grad", "sea_decode_field_grad", "sea_resample_systematic", "sea_enkf_transform", "sea_enkf_transform_gram", "sea_decode_member_gram", "sea_ensemble_mix", "sea_ensemble_verify", "sea_ensemble_verify_ws_bytes", "sea_decode_member_verify", "sea_decode_member_verify_ws_bytes", "sea_decode_member_quantiles",
     "sea_decode_member_crps_grad", "sea_decode_member_crps_grad_ws_bytes", "sea_decode_member_crps_grad_packed",
     "sea_decode_member_brier", "sea_decode_member_brier_ws_bytes", "sea_ensemble_brier", "sea_ensemble_brier_ws_bytes",
-    "sea_decode_derived_quantiles", "sea_decode_derived_brier", "sea_decode_derived_verify",
+    "sea_decode_derived_quantiles", "sea_decode_derived_brier", "sea_decode_derived_verify", "sea_decode_derived_sensor_sse", "sea_decode_derived_sensor_grad",
     "sea_gemm_fewrows", "sea_qkv_rope_fewrows", "sea_row_chain", "sea_row_chain_riders", "sea_gemm_adaln", "sea_mlp_block", "sea_adaln_qkv", "sea_splitk_finish",
     "sea_encoder_block_ws_floats", "sea_encoder_block_fwd", "sea_encoder_block_bwd",
     "sea_silu_outer_bwd_dc", "sea_silu_outer_bwd_dc_ws_floats", "sea_ib_bwd_dc",

@@ -925,9 +925,26 @@ extern "C" int sea_decode_member_moments(const SeaDecodeMseGroup* groups, int n_
 // too, at pred[bm K_pad + sorted position] (pad positions included: their W2 row is row 0 — a defined value the caller drops).
 // The kernel trusts wrow (rows of W2) and seg: the host builds and range-checks them (sea_amd/ensemble.py, SensorSet).
 struct SensorSseLaunch {
+    static constexpr bool derived = false;
     SeaDecodeMseGroup g[SEA_DECODE_MSE_MAX_GROUPS];
     SeaDecodeSensorSse p;
 };
+// The same launch with the pair tables of sea_decode_derived_sensor_sse behind it (the kernels below are compiled once per launch type; everything
+// the derived form adds sits in `if constexpr (LT::derived)`, so the plain form's code is what it was).
+struct DerivedSensorSseLaunch {
+    static constexpr bool derived = true;
+    SeaDecodeMseGroup g[SEA_DECODE_MSE_MAX_GROUPS];
+    SeaDecodeSensorSse p;
+    SeaDerivedSensorTables t;
+};
+__device__ __forceinline__ float dv_value(const int op, const float ya, const float yb, const float sa, const float ha, const float sb, const float hb);   // below
+
+// A lane's 4 consecutive sorted positions are two PAIRS (2 i, 2 i + 1) = (source a, source b) of one reading: x of pair pr from the decoded values, in
+// registers.  op < 0: a plain reading, x = ya.  Both entries of y get x (pred[2 i] = pred[2 i + 1] = x).
+__device__ __forceinline__ float ds_pair_value(const int op, const float ya, const float yb, const float sa, const float ha, const float sb, const float hb) {
+    const float x = dv_value(op < 0 ? SEA_DERIVED_DIFFERENCE : op, ya, yb, sa, ha, sb, hb);
+    return op < 0 ? ya : x;
+}
 
 // dm_load_tile with gathered rows: row i of the tile is W2 row rows[i]; the 16-byte chunks of a row stay contiguous
 template <int SP, int NT = 256>
@@ -940,8 +957,8 @@ __device__ __forceinline__ void ds_load_tile_gathered(uint4 (&wr)[SP * 4 / NT], 
     }
 }
 
-template <int SP>
-__global__ __launch_bounds__(256) void decode_sensor_sse_kernel(const SensorSseLaunch L) {
+template <int SP, class LT = SensorSseLaunch>
+__global__ __launch_bounds__(256) void decode_sensor_sse_kernel(const LT L) {
 #pragma clang fp reassociate(off)   // the lane's sum runs over its sensors in the stated order
     constexpr int NT = 256;
     constexpr int KS = SP / 32;
@@ -994,6 +1011,8 @@ __global__ __launch_bounds__(256) void decode_sensor_sse_kernel(const SensorSseL
         // observation, precision and the live mask of this lane's 2 x 4 sensors (requested now, used after the products); the bias through the row table
         float ob[2][4], pw[2][4];
         f32x4 acc[2][2];
+        [[maybe_unused]] int4 dop[2];
+        [[maybe_unused]] float4 dsc[2], dsh[2];
 #pragma unroll
         for (int sub = 0; sub < 2; ++sub) {
             const int k = k0 + sub * 16 + 4 * lg;   // a multiple of 4: obs, prec and pred rows start 16-byte aligned (K_pad % 32 == 0, strides % 4 == 0)
@@ -1010,6 +1029,11 @@ __global__ __launch_bounds__(256) void decode_sensor_sse_kernel(const SensorSseL
             }
             acc[sub][0] = bv;
             acc[sub][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if constexpr (LT::derived) {   // the pair tables of this lane's two pairs, as obs and prec: one 16-byte load each
+                dop[sub] = *reinterpret_cast<const int4*>(L.t.op + k);
+                dsc[sub] = *reinterpret_cast<const float4*>(L.t.scale + k);
+                dsh[sub] = *reinterpret_cast<const float4*>(L.t.shift + k);
+            }
         }
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
@@ -1025,12 +1049,27 @@ __global__ __launch_bounds__(256) void decode_sensor_sse_kernel(const SensorSseL
 #pragma unroll
         for (int sub = 0; sub < 2; ++sub) {
             float y[4];
+            if constexpr (LT::derived) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) y[r] = acc[sub][0][r] + acc[sub][1][r];   // sea_decode_sensor_sse's y: the same accumulators, the same bits
+                const float x0 = ds_pair_value(dop[sub].x, y[0], y[1], dsc[sub].x, dsh[sub].x, dsc[sub].y, dsh[sub].y);
+                const float x1 = ds_pair_value(dop[sub].z, y[2], y[3], dsc[sub].z, dsh[sub].z, dsc[sub].w, dsh[sub].w);
+                y[0] = y[1] = x0;
+                y[2] = y[3] = x1;
+#pragma unroll
+                for (int pr = 0; pr < 2; ++pr) {   // the weight, the observation and the residual of a pair are those of its entry 2 i
+                    const float w = pw[sub][2 * pr];
+                    const float d = w > 0.f ? y[2 * pr] - ob[sub][2 * pr] : 0.f;
+                    fsum = __builtin_fmaf(w * d, d, fsum);
+                }
+            } else {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 y[r] = acc[sub][0][r] + acc[sub][1][r];
                 const float w = pw[sub][r];
                 const float d = w > 0.f ? y[r] - ob[sub][r] : 0.f;
                 fsum = __builtin_fmaf(w * d, d, fsum);
+            }
             }
             if (drow != nullptr) *reinterpret_cast<float4*>(drow + k0 + sub * 16 + 4 * lg) = make_float4(y[0], y[1], y[2], y[3]);
         }
@@ -1056,57 +1095,95 @@ __global__ __launch_bounds__(256) void sensor_sse_finish_kernel(const float* __r
     wsse[bm] = acc;
 }
 
-template <int SP>
-static void sensor_sse_launch(const SensorSseLaunch& L, dim3 grid, hipStream_t s) {
+template <int SP, class LT>
+static void sensor_sse_launch(const LT& L, dim3 grid, hipStream_t s) {
     constexpr int lds = 2 * DM_TC * (SP * 2 + DM_PAD);
-    static bool set_on[64] = {false};   // per device: SP = 640 needs 84 kB, above the 64 kB a kernel gets without the attribute
+    static bool set_on[64] = {false};   // per device (and per launch type): SP = 640 needs 84 kB, above the 64 kB a kernel gets without the attribute
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = -1;
     if (dev < 0 || !set_on[dev]) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(decode_sensor_sse_kernel<SP>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(decode_sensor_sse_kernel<SP, LT>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         if (dev >= 0) set_on[dev] = true;
     }
-    decode_sensor_sse_kernel<SP><<<grid, dim3(256), lds, s>>>(L);
+    decode_sensor_sse_kernel<SP, LT><<<grid, dim3(256), lds, s>>>(L);
 }
 
-extern "C" int sea_decode_sensor_sse(const SeaDecodeMseGroup* groups, int n_groups, const SeaDecodeSensorSse* p, int dtype, void* stream) {
-    SEA_REQUIRE(groups != nullptr && p != nullptr, "sea_decode_sensor_sse: null argument table");
-    SEA_REQUIRE(n_groups >= 1 && n_groups <= SEA_DECODE_MSE_MAX_GROUPS, "sea_decode_sensor_sse: n_groups=%d outside 1..%d", n_groups, SEA_DECODE_MSE_MAX_GROUPS);
-    SEA_REQUIRE(dtype == SEA_F32 || dtype == SEA_BF16, "sea_decode_sensor_sse: bad dtype %d", dtype);
+// The checks the four sensor entry points share, under the entry point's name `who`.  P: the fields SeaDecodeSensorGrad has in common with
+// SeaDecodeSensorSse; grad_scale: NULL for the score-only entry points; derived: the pair tables are required (t) — the plain entry points pass
+// false and NULL; composes: what the message of the unsupported fp32 form names as the caller's other path.  SEA_OK, SEA_EINVAL or SEA_EUNSUPPORTED.
+static int sensor_args_check(const char* who, const SeaDecodeMseGroup* groups, int n_groups, const SeaDecodeSensorSse& P, const float* grad_scale, bool derived,
+                             const SeaDerivedSensorTables* t, int dtype, const char* composes) {
+    const bool grad = grad_scale != nullptr;
+    SEA_REQUIRE(groups != nullptr && (!derived || t != nullptr), "%s: null argument table", who);
+    SEA_REQUIRE(n_groups >= 1 && n_groups <= SEA_DECODE_MSE_MAX_GROUPS, "%s: n_groups=%d outside 1..%d", who, n_groups, SEA_DECODE_MSE_MAX_GROUPS);
+    SEA_REQUIRE(dtype == SEA_F32 || dtype == SEA_BF16, "%s: bad dtype %d", who, dtype);
     if (dtype != SEA_BF16) {
-        sea_set_error("sea_decode_sensor_sse: unsupported: bf16 only (the fp32 decoder composes sea_gemm_grouped, a gather and reductions)");
+        sea_set_error("%s: unsupported: bf16 only (the fp32 decoder composes %s)", who, composes);
         return SEA_EUNSUPPORTED;
     }
-    const SeaDecodeSensorSse& P = *p;
     SEA_REQUIRE(P.obs != nullptr && P.live != nullptr && P.wrow != nullptr && P.seg != nullptr && P.wsse != nullptr && P.work != nullptr,
-                "sea_decode_sensor_sse: null obs, live, wrow, seg, wsse or work pointer");
-    SEA_REQUIRE(P.Bm >= 1 && P.members >= 1 && P.Bm % P.members == 0, "sea_decode_sensor_sse: Bm=%d must be a positive multiple of members=%d", P.Bm, P.members);
-    SEA_REQUIRE(P.S >= 8 && P.S % 8 == 0, "sea_decode_sensor_sse: S=%d must be a positive multiple of 8", P.S);
-    SEA_REQUIRE(P.Cp >= 32 && P.Cp % 32 == 0, "sea_decode_sensor_sse: Cp=%d must be a positive multiple of 32", P.Cp);
-    SEA_REQUIRE(P.K_pad >= 32 && P.K_pad % 32 == 0, "sea_decode_sensor_sse: K_pad=%d must be a positive multiple of 32", P.K_pad);
-    SEA_REQUIRE(P.Q >= 1 && P.Q <= 65535, "sea_decode_sensor_sse: Q=%d observed patches outside 1..65535", P.Q);
-    SEA_REQUIRE(P.ld_obs >= P.K_pad && P.ld_obs % 4 == 0, "sea_decode_sensor_sse: obs row stride ld_obs=%lld must cover K_pad=%d and be a multiple of 4", (long long)P.ld_obs, P.K_pad);
+                "%s: null obs, live, wrow, seg, wsse or work pointer", who);
+    SEA_REQUIRE(!derived || (t->op != nullptr && t->scale != nullptr && t->shift != nullptr), "%s: null op, scale or shift table", who);
+    SEA_REQUIRE(P.Bm >= 1 && P.members >= 1 && P.Bm % P.members == 0, "%s: Bm=%d must be a positive multiple of members=%d", who, P.Bm, P.members);
+    SEA_REQUIRE(P.S >= 8 && P.S % 8 == 0, "%s: S=%d must be a positive multiple of 8", who, P.S);
+    SEA_REQUIRE(P.Cp >= 32 && P.Cp % 32 == 0, "%s: Cp=%d must be a positive multiple of 32", who, P.Cp);
+    SEA_REQUIRE(P.K_pad >= 32 && P.K_pad % 32 == 0, "%s: K_pad=%d must be a positive multiple of 32", who, P.K_pad);
+    SEA_REQUIRE(P.Q >= 1 && P.Q <= 65535, "%s: Q=%d observed patches outside 1..65535", who, P.Q);
+    SEA_REQUIRE(P.ld_obs >= P.K_pad && P.ld_obs % 4 == 0, "%s: obs row stride ld_obs=%lld must cover K_pad=%d and be a multiple of 4", who, (long long)P.ld_obs, P.K_pad);
     SEA_REQUIRE(P.prec == nullptr || P.ld_prec == 0 || (P.ld_prec >= P.K_pad && P.ld_prec % 4 == 0),
-                "sea_decode_sensor_sse: prec row stride ld_prec=%lld must be 0 (one row for all histories) or cover K_pad=%d and be a multiple of 4", (long long)P.ld_prec, P.K_pad);
-    SEA_REQUIRE(sea_aligned16(P.obs) && sea_aligned16(P.prec) && sea_aligned16(P.pred), "sea_decode_sensor_sse: obs, prec and pred must be 16-byte aligned");
+                "%s: prec row stride ld_prec=%lld must be 0 (one row for all histories) or cover K_pad=%d and be a multiple of 4", who, (long long)P.ld_prec, P.K_pad);
+    SEA_REQUIRE(sea_aligned16(P.obs) && sea_aligned16(P.prec) && sea_aligned16(P.pred), "%s: obs, prec and pred must be 16-byte aligned", who);
     SEA_REQUIRE(sea_aligned4(P.live) && sea_aligned4(P.wrow) && sea_aligned4(P.seg) && sea_aligned4(P.wsse) && sea_aligned4(P.work),
-                "sea_decode_sensor_sse: misaligned live, wrow, seg, wsse or work pointer");
+                "%s: misaligned live, wrow, seg, wsse or work pointer", who);
+    SEA_REQUIRE(!derived || (sea_aligned16(t->op) && sea_aligned16(t->scale) && sea_aligned16(t->shift)), "%s: the op, scale and shift tables must be 16-byte aligned", who);
+    if (grad) {
+        uint32_t gs_bits;
+        memcpy(&gs_bits, grad_scale, sizeof(gs_bits));
+        SEA_REQUIRE((gs_bits & 0x7f800000u) != 0x7f800000u, "%s: grad_scale must be finite", who);   // the exponent field itself: no floating-point compare to reason about
+    }
     for (int g = 0; g < n_groups; ++g) {
         const SeaDecodeMseGroup& G = groups[g];
-        SEA_REQUIRE(G.H != nullptr && G.W2 != nullptr && G.bias != nullptr, "sea_decode_sensor_sse: group %d: null pointer", g);
-        SEA_REQUIRE(sea_aligned16(G.H) && sea_aligned16(G.W2) && sea_aligned16(G.bias), "sea_decode_sensor_sse: group %d: pointers must be 16-byte aligned", g);
-        SEA_REQUIRE(G.ldh >= P.S && G.ldh % 8 == 0 && G.ldw >= P.S && G.ldw % 8 == 0,
-                    "sea_decode_sensor_sse: group %d: row strides ldh=%d ldw=%d must cover S=%d and be multiples of 8", g, G.ldh, G.ldw, P.S);
-        SEA_REQUIRE(G.n_fields >= 1 && (int64_t)G.n_fields * P.Cp <= 0x7fffffffLL / 2, "sea_decode_sensor_sse: group %d: n_fields=%d", g, G.n_fields);
+        if (!grad) {
+            SEA_REQUIRE(G.H != nullptr && G.W2 != nullptr && G.bias != nullptr, "%s: group %d: null pointer", who, g);
+            SEA_REQUIRE(sea_aligned16(G.H) && sea_aligned16(G.W2) && sea_aligned16(G.bias), "%s: group %d: pointers must be 16-byte aligned", who, g);
+        } else {
+            SEA_REQUIRE(G.H != nullptr && G.W2 != nullptr && G.bias != nullptr && G.dH != nullptr, "%s: group %d: null pointer (H, W2, bias or dH)", who, g);
+            SEA_REQUIRE(sea_aligned16(G.H) && sea_aligned16(G.W2) && sea_aligned16(G.bias) && sea_aligned16(G.dH) && sea_aligned16(G.Z),
+                        "%s: group %d: pointers must be 16-byte aligned", who, g);
+        }
+        SEA_REQUIRE(G.ldh >= P.S && G.ldh % 8 == 0 && G.ldw >= P.S && G.ldw % 8 == 0, "%s: group %d: row strides ldh=%d ldw=%d must cover S=%d and be multiples of 8", who,
+                    g, G.ldh, G.ldw, P.S);
+        if (grad)
+            SEA_REQUIRE(G.lddh >= P.S && G.lddh % 8 == 0 && (G.Z == nullptr || (G.ldz >= P.S && G.ldz % 8 == 0)),
+                        "%s: group %d: row strides lddh=%d ldz=%d must cover S=%d and be multiples of 8", who, g, G.lddh, G.ldz, P.S);
+        SEA_REQUIRE(G.n_fields >= 1 && (int64_t)G.n_fields * P.Cp <= 0x7fffffffLL / 2, "%s: group %d: n_fields=%d", who, g, G.n_fields);
     }
     if (P.S > 640) {
-        sea_set_error("sea_decode_sensor_sse: unsupported: hidden width S=%d above 640", P.S);
+        sea_set_error("%s: unsupported: hidden width S=%d above 640", who, P.S);
         return SEA_EUNSUPPORTED;
     }
     const int64_t row_blocks = ((int64_t)P.Bm + DM_ROWS - 1) / DM_ROWS;
     const int64_t need = (int64_t)P.Q * n_groups * P.Bm;
-    SEA_REQUIRE(row_blocks <= 0x7fffffffLL && (int64_t)P.Q * P.Bm <= 0x7fffffffLL, "sea_decode_sensor_sse: too many rows");
-    SEA_REQUIRE(P.work_cap >= need, "sea_decode_sensor_sse: workspace of %lld floats is too small: %lld needed (Q * n_groups * Bm)", (long long)P.work_cap, (long long)need);
+    SEA_REQUIRE(row_blocks <= 0x7fffffffLL && (int64_t)P.Q * P.Bm <= 0x7fffffffLL, "%s: too many rows", who);
+    SEA_REQUIRE(P.work_cap >= need, "%s: workspace of %lld floats is too small: %lld needed (Q * n_groups * Bm)", who, (long long)P.work_cap, (long long)need);
+    return SEA_OK;
+}
+
+// The fields SeaDecodeSensorGrad has in common with SeaDecodeSensorSse, for the shared checks.
+static SeaDecodeSensorSse sensor_common(const SeaDecodeSensorGrad& P) {
+    SeaDecodeSensorSse c;
+    c.obs = P.obs; c.prec = P.prec; c.live = P.live; c.wrow = P.wrow; c.seg = P.seg; c.wsse = P.wsse; c.pred = P.pred; c.work = P.work;
+    c.ld_obs = P.ld_obs; c.ld_prec = P.ld_prec; c.work_cap = P.work_cap;
+    c.Bm = P.Bm; c.members = P.members; c.S = P.S; c.Cp = P.Cp; c.Q = P.Q; c.K_pad = P.K_pad;
+    return c;
+}
+
+extern "C" int sea_decode_sensor_sse(const SeaDecodeMseGroup* groups, int n_groups, const SeaDecodeSensorSse* p, int dtype, void* stream) {
+    SEA_REQUIRE(groups != nullptr && p != nullptr, "sea_decode_sensor_sse: null argument table");
+    const SeaDecodeSensorSse& P = *p;
+    const int rc = sensor_args_check("sea_decode_sensor_sse", groups, n_groups, P, nullptr, false, nullptr, dtype, "sea_gemm_grouped, a gather and reductions");
+    if (rc != SEA_OK) return rc;
+    const int64_t row_blocks = ((int64_t)P.Bm + DM_ROWS - 1) / DM_ROWS;
 
     SensorSseLaunch L;
     memset(&L, 0, sizeof(L));
@@ -1141,12 +1218,34 @@ extern "C" int sea_decode_sensor_sse(const SeaDecodeMseGroup* groups, int n_grou
 // own operand row only, so a member's dH rows and score do not depend on `members`, on the number of histories or on the row tile it falls into.
 // The kernel trusts wrow and seg exactly as decode_sensor_sse_kernel does.
 struct SensorGradLaunch {
+    static constexpr bool derived = false;
     SeaDecodeMseGroup g[SEA_DECODE_MSE_MAX_GROUPS];
     SeaDecodeSensorGrad p;
 };
+struct DerivedSensorGradLaunch {
+    static constexpr bool derived = true;
+    SeaDecodeMseGroup g[SEA_DECODE_MSE_MAX_GROUPS];
+    SeaDecodeSensorGrad p;
+    SeaDerivedSensorTables t;
+};
 
-template <int SP>
-__global__ __launch_bounds__(256) void decode_sensor_grad_kernel(const SensorGradLaunch L) {
+// ds_pair_value with the two partial derivatives ga = dx / dya, gb = dx / dyb, in fp32 from the same a', b' and x (include/sea_hip.h states the table;
+// single instructions, so that nothing is packed or contracted): plain 1, 0; difference sa, -sb; energy a' sa, b' sb; magnitude a' sa / x, b' sb / x
+// by a select that gives exactly 0 at x = 0.
+__device__ __forceinline__ float ds_pair_grad(const int op, const float ya, const float yb, const float sa, const float ha, const float sb, const float hb, float& ga,
+                                              float& gb) {
+    const float x = ds_pair_value(op, ya, yb, sa, ha, sb, hb);
+    const float a = add1(mul1(ya, sa), ha), b = add1(mul1(yb, sb), hb);   // dv_value's a', b': the same two instructions each, the same bits
+    const float as = mul1(a, sa), bs = mul1(b, sb);
+    const float rx = __builtin_amdgcn_rcpf(x);
+    const float ma = x > 0.f ? mul1(as, rx) : 0.f, mb = x > 0.f ? mul1(bs, rx) : 0.f;
+    ga = op < 0 ? 1.f : op == SEA_DERIVED_DIFFERENCE ? sa : op == SEA_DERIVED_ENERGY ? as : ma;
+    gb = op < 0 ? 0.f : op == SEA_DERIVED_DIFFERENCE ? -sb : op == SEA_DERIVED_ENERGY ? bs : mb;
+    return x;
+}
+
+template <int SP, class LT = SensorGradLaunch>
+__global__ __launch_bounds__(256) void decode_sensor_grad_kernel(const LT L) {
 #pragma clang fp reassociate(off)   // the lane's sum runs over its sensors in the stated order
     constexpr int NT = 256;
     constexpr int KS = SP / 32;
@@ -1212,6 +1311,8 @@ __global__ __launch_bounds__(256) void decode_sensor_grad_kernel(const SensorGra
         // stage 1, as decode_sensor_sse_kernel
         float ob[2][4], pw[2][4];
         f32x4 acc[2][2];
+        [[maybe_unused]] int4 dop[2];
+        [[maybe_unused]] float4 dsc[2], dsh[2];
 #pragma unroll
         for (int sub = 0; sub < 2; ++sub) {
             const int k = k0 + sub * 16 + 4 * lg;
@@ -1228,6 +1329,11 @@ __global__ __launch_bounds__(256) void decode_sensor_grad_kernel(const SensorGra
             }
             acc[sub][0] = bv;
             acc[sub][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if constexpr (LT::derived) {   // the pair tables of this lane's two pairs, as obs and prec: one 16-byte load each
+                dop[sub] = *reinterpret_cast<const int4*>(L.t.op + k);
+                dsc[sub] = *reinterpret_cast<const float4*>(L.t.scale + k);
+                dsh[sub] = *reinterpret_cast<const float4*>(L.t.shift + k);
+            }
         }
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
@@ -1245,6 +1351,24 @@ __global__ __launch_bounds__(256) void decode_sensor_grad_kernel(const SensorGra
 #pragma unroll
         for (int sub = 0; sub < 2; ++sub) {
             float y[4];
+            if constexpr (LT::derived) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) y[r] = acc[sub][0][r] + acc[sub][1][r];
+                float gr[4];
+                const float x0 = ds_pair_grad(dop[sub].x, y[0], y[1], dsc[sub].x, dsh[sub].x, dsc[sub].y, dsh[sub].y, gr[0], gr[1]);
+                const float x1 = ds_pair_grad(dop[sub].z, y[2], y[3], dsc[sub].z, dsh[sub].z, dsc[sub].w, dsh[sub].w, gr[2], gr[3]);
+                y[0] = y[1] = x0;
+                y[2] = y[3] = x1;
+#pragma unroll
+                for (int pr = 0; pr < 2; ++pr) {   // the score of sea_decode_derived_sensor_sse; r[2 i] = act(w d ga), r[2 i + 1] = act(w d gb)
+                    const float w = pw[sub][2 * pr];
+                    const float d = w > 0.f ? y[2 * pr] - ob[sub][2 * pr] : 0.f;
+                    const float wd = w * d;
+                    fsum = __builtin_fmaf(wd, d, fsum);
+                    dfr[sub * 4 + 2 * pr] = (__bf16)mul1(wd, gr[2 * pr]);
+                    dfr[sub * 4 + 2 * pr + 1] = (__bf16)mul1(wd, gr[2 * pr + 1]);
+                }
+            } else {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 y[r] = acc[sub][0][r] + acc[sub][1][r];
@@ -1253,6 +1377,7 @@ __global__ __launch_bounds__(256) void decode_sensor_grad_kernel(const SensorGra
                 const float wd = w * d;
                 fsum = __builtin_fmaf(wd, d, fsum);
                 dfr[sub * 4 + r] = (__bf16)wd;
+            }
             }
             if (drow != nullptr) *reinterpret_cast<float4*>(drow + k0 + sub * 16 + 4 * lg) = make_float4(y[0], y[1], y[2], y[3]);
         }
@@ -1301,63 +1426,26 @@ __global__ __launch_bounds__(256) void decode_sensor_grad_kernel(const SensorGra
     if (lg == 0 && bm < Bm) *wslot = v;
 }
 
-template <int SP>
-static void sensor_grad_launch(const SensorGradLaunch& L, dim3 grid, hipStream_t s) {
+template <int SP, class LT>
+static void sensor_grad_launch(const LT& L, dim3 grid, hipStream_t s) {
     constexpr int lds = 2 * DM_TC * (SP * 2 + DM_PAD);
-    static bool set_on[64] = {false};   // per device: SP = 640 needs 84 kB, above the 64 kB a kernel gets without the attribute
+    static bool set_on[64] = {false};   // per device (and per launch type): SP = 640 needs 84 kB, above the 64 kB a kernel gets without the attribute
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = -1;
     if (dev < 0 || !set_on[dev]) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(decode_sensor_grad_kernel<SP>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(decode_sensor_grad_kernel<SP, LT>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         if (dev >= 0) set_on[dev] = true;
     }
-    decode_sensor_grad_kernel<SP><<<grid, dim3(256), lds, s>>>(L);
+    decode_sensor_grad_kernel<SP, LT><<<grid, dim3(256), lds, s>>>(L);
 }
 
 extern "C" int sea_decode_sensor_grad(const SeaDecodeMseGroup* groups, int n_groups, const SeaDecodeSensorGrad* p, int dtype, void* stream) {
     SEA_REQUIRE(groups != nullptr && p != nullptr, "sea_decode_sensor_grad: null argument table");
-    SEA_REQUIRE(n_groups >= 1 && n_groups <= SEA_DECODE_MSE_MAX_GROUPS, "sea_decode_sensor_grad: n_groups=%d outside 1..%d", n_groups, SEA_DECODE_MSE_MAX_GROUPS);
-    SEA_REQUIRE(dtype == SEA_F32 || dtype == SEA_BF16, "sea_decode_sensor_grad: bad dtype %d", dtype);
-    if (dtype != SEA_BF16) {
-        sea_set_error("sea_decode_sensor_grad: unsupported: bf16 only (the fp32 decoder composes sea_gemm_grouped, a gather and reductions under autograd)");
-        return SEA_EUNSUPPORTED;
-    }
     const SeaDecodeSensorGrad& P = *p;
-    SEA_REQUIRE(P.obs != nullptr && P.live != nullptr && P.wrow != nullptr && P.seg != nullptr && P.wsse != nullptr && P.work != nullptr,
-                "sea_decode_sensor_grad: null obs, live, wrow, seg, wsse or work pointer");
-    SEA_REQUIRE(P.Bm >= 1 && P.members >= 1 && P.Bm % P.members == 0, "sea_decode_sensor_grad: Bm=%d must be a positive multiple of members=%d", P.Bm, P.members);
-    SEA_REQUIRE(P.S >= 8 && P.S % 8 == 0, "sea_decode_sensor_grad: S=%d must be a positive multiple of 8", P.S);
-    SEA_REQUIRE(P.Cp >= 32 && P.Cp % 32 == 0, "sea_decode_sensor_grad: Cp=%d must be a positive multiple of 32", P.Cp);
-    SEA_REQUIRE(P.K_pad >= 32 && P.K_pad % 32 == 0, "sea_decode_sensor_grad: K_pad=%d must be a positive multiple of 32", P.K_pad);
-    SEA_REQUIRE(P.Q >= 1 && P.Q <= 65535, "sea_decode_sensor_grad: Q=%d observed patches outside 1..65535", P.Q);
-    SEA_REQUIRE(P.ld_obs >= P.K_pad && P.ld_obs % 4 == 0, "sea_decode_sensor_grad: obs row stride ld_obs=%lld must cover K_pad=%d and be a multiple of 4", (long long)P.ld_obs, P.K_pad);
-    SEA_REQUIRE(P.prec == nullptr || P.ld_prec == 0 || (P.ld_prec >= P.K_pad && P.ld_prec % 4 == 0),
-                "sea_decode_sensor_grad: prec row stride ld_prec=%lld must be 0 (one row for all histories) or cover K_pad=%d and be a multiple of 4", (long long)P.ld_prec, P.K_pad);
-    SEA_REQUIRE(sea_aligned16(P.obs) && sea_aligned16(P.prec) && sea_aligned16(P.pred), "sea_decode_sensor_grad: obs, prec and pred must be 16-byte aligned");
-    SEA_REQUIRE(sea_aligned4(P.live) && sea_aligned4(P.wrow) && sea_aligned4(P.seg) && sea_aligned4(P.wsse) && sea_aligned4(P.work),
-                "sea_decode_sensor_grad: misaligned live, wrow, seg, wsse or work pointer");
-    uint32_t gs_bits;
-    memcpy(&gs_bits, &P.grad_scale, sizeof(gs_bits));
-    SEA_REQUIRE((gs_bits & 0x7f800000u) != 0x7f800000u, "sea_decode_sensor_grad: grad_scale must be finite");   // the exponent field itself: no floating-point compare to reason about
-    for (int g = 0; g < n_groups; ++g) {
-        const SeaDecodeMseGroup& G = groups[g];
-        SEA_REQUIRE(G.H != nullptr && G.W2 != nullptr && G.bias != nullptr && G.dH != nullptr, "sea_decode_sensor_grad: group %d: null pointer (H, W2, bias or dH)", g);
-        SEA_REQUIRE(sea_aligned16(G.H) && sea_aligned16(G.W2) && sea_aligned16(G.bias) && sea_aligned16(G.dH) && sea_aligned16(G.Z),
-                    "sea_decode_sensor_grad: group %d: pointers must be 16-byte aligned", g);
-        SEA_REQUIRE(G.ldh >= P.S && G.ldh % 8 == 0 && G.ldw >= P.S && G.ldw % 8 == 0,
-                    "sea_decode_sensor_grad: group %d: row strides ldh=%d ldw=%d must cover S=%d and be multiples of 8", g, G.ldh, G.ldw, P.S);
-        SEA_REQUIRE(G.lddh >= P.S && G.lddh % 8 == 0 && (G.Z == nullptr || (G.ldz >= P.S && G.ldz % 8 == 0)),
-                    "sea_decode_sensor_grad: group %d: row strides lddh=%d ldz=%d must cover S=%d and be multiples of 8", g, G.lddh, G.ldz, P.S);
-        SEA_REQUIRE(G.n_fields >= 1 && (int64_t)G.n_fields * P.Cp <= 0x7fffffffLL / 2, "sea_decode_sensor_grad: group %d: n_fields=%d", g, G.n_fields);
-    }
-    if (P.S > 640) {
-        sea_set_error("sea_decode_sensor_grad: unsupported: hidden width S=%d above 640", P.S);
-        return SEA_EUNSUPPORTED;
-    }
+    const int rc = sensor_args_check("sea_decode_sensor_grad", groups, n_groups, sensor_common(P), &P.grad_scale, false, nullptr, dtype,
+                                     "sea_gemm_grouped, a gather and reductions under autograd");
+    if (rc != SEA_OK) return rc;
     const int64_t row_blocks = ((int64_t)P.Bm + DM_ROWS - 1) / DM_ROWS;
-    const int64_t need = (int64_t)P.Q * n_groups * P.Bm;
-    SEA_REQUIRE(row_blocks <= 0x7fffffffLL && (int64_t)P.Q * P.Bm <= 0x7fffffffLL, "sea_decode_sensor_grad: too many rows");
-    SEA_REQUIRE(P.work_cap >= need, "sea_decode_sensor_grad: workspace of %lld floats is too small: %lld needed (Q * n_groups * Bm)", (long long)P.work_cap, (long long)need);
 
     SensorGradLaunch L;
     memset(&L, 0, sizeof(L));
@@ -1373,6 +1461,68 @@ extern "C" int sea_decode_sensor_grad(const SeaDecodeMseGroup* groups, int n_gro
     sea_note_form("sensor_grad.rows64", 0, 0);
     sensor_sse_finish_kernel<<<dim3((unsigned)((P.Bm + 255) / 256)), dim3(256), 0, s>>>(P.work, P.wsse, P.Bm, (int)((int64_t)P.Q * n_groups));
     SEA_CHECK_LAUNCH("sea_decode_sensor_grad");
+    return SEA_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------------------------
+// sea_decode_derived_sensor_sse / sea_decode_derived_sensor_grad: sensors that read a DERIVED quantity — a speed, an energy, a difference of the two
+// source values at one cell — scored (and differentiated) by the two kernels above compiled for the launch types with the pair tables.  A reading is
+// two adjacent entries of the sorted, padded list: entry 2 i gathers the W2 row of source a, entry 2 i + 1 that of source b (same group, patch, cell).  A
+// lane holds sorted positions 16 sub + 4 lg + r, r = 0 .. 3: two whole pairs, so the gathered tile load, both LDS images, the MFMA stage, the grid, the
+// workspace and the finish launch are untouched and only the epilogue differs — in registers, no shuffles, no extra LDS (four tile images at SP = 640
+// would need 168 kB).  op, scale, shift come per entry from device tables by 16-byte loads, as obs and prec do: a per-lane index into a by-value table
+// in the kernel arguments would put that table into scratch.  x = dv_value(...) is the device function of the derived launches below; op == -1 at
+// entry 2 i marks a plain reading (x = ya).  The weight, the observation and the residual of a pair are those of entry 2 i; pred gets x at both entries.
+extern "C" int sea_decode_derived_sensor_sse(const SeaDecodeMseGroup* groups, int n_groups, const SeaDecodeSensorSse* p, const SeaDerivedSensorTables* tables, int dtype,
+                                             void* stream) {
+    const char* who = "sea_decode_derived_sensor_sse";
+    SEA_REQUIRE(p != nullptr, "%s: null argument table", who);
+    const SeaDecodeSensorSse& P = *p;
+    const int rc = sensor_args_check(who, groups, n_groups, P, nullptr, true, tables, dtype, "sea_gemm_grouped, a gather and the derived values in torch ops");
+    if (rc != SEA_OK) return rc;
+
+    DerivedSensorSseLaunch L;
+    memset(&L, 0, sizeof(L));
+    for (int g = 0; g < n_groups; ++g) L.g[g] = groups[g];
+    L.p = P;
+    L.t = *tables;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)(((int64_t)P.Bm + DM_ROWS - 1) / DM_ROWS), (unsigned)P.Q, (unsigned)n_groups);
+    if (P.S <= 128) sensor_sse_launch<128>(L, grid, s);
+    else if (P.S <= 256) sensor_sse_launch<256>(L, grid, s);
+    else if (P.S <= 384) sensor_sse_launch<384>(L, grid, s);
+    else if (P.S <= 512) sensor_sse_launch<512>(L, grid, s);
+    else sensor_sse_launch<640>(L, grid, s);
+    sea_note_form("derived_sensor_sse.rows64", 0, 0);
+    sensor_sse_finish_kernel<<<dim3((unsigned)((P.Bm + 255) / 256)), dim3(256), 0, s>>>(P.work, P.wsse, P.Bm, (int)((int64_t)P.Q * n_groups));
+    SEA_CHECK_LAUNCH(who);
+    return SEA_OK;
+}
+
+extern "C" int sea_decode_derived_sensor_grad(const SeaDecodeMseGroup* groups, int n_groups, const SeaDecodeSensorGrad* p, const SeaDerivedSensorTables* tables, int dtype,
+                                              void* stream) {
+    const char* who = "sea_decode_derived_sensor_grad";
+    SEA_REQUIRE(p != nullptr, "%s: null argument table", who);
+    const SeaDecodeSensorGrad& P = *p;
+    const int rc = sensor_args_check(who, groups, n_groups, sensor_common(P), &P.grad_scale, true, tables, dtype,
+                                     "sea_gemm_grouped, a gather and the derived values in torch ops under autograd");
+    if (rc != SEA_OK) return rc;
+
+    DerivedSensorGradLaunch L;
+    memset(&L, 0, sizeof(L));
+    for (int g = 0; g < n_groups; ++g) L.g[g] = groups[g];
+    L.p = P;
+    L.t = *tables;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)(((int64_t)P.Bm + DM_ROWS - 1) / DM_ROWS), (unsigned)P.Q, (unsigned)n_groups);
+    if (P.S <= 128) sensor_grad_launch<128>(L, grid, s);
+    else if (P.S <= 256) sensor_grad_launch<256>(L, grid, s);
+    else if (P.S <= 384) sensor_grad_launch<384>(L, grid, s);
+    else if (P.S <= 512) sensor_grad_launch<512>(L, grid, s);
+    else sensor_grad_launch<640>(L, grid, s);
+    sea_note_form("derived_sensor_grad.rows64", 0, 0);
+    sensor_sse_finish_kernel<<<dim3((unsigned)((P.Bm + 255) / 256)), dim3(256), 0, s>>>(P.work, P.wsse, P.Bm, (int)((int64_t)P.Q * n_groups));
+    SEA_CHECK_LAUNCH(who);
     return SEA_OK;
 }
 

@@ -440,6 +440,12 @@ class SensorSet:
         if self.K_pad < T or self.K_pad >= 2 ** 31 or sum(live) != K:
             raise ValueError(f"{what}: internal error: K_pad = {self.K_pad}, {sum(live)} live entries for {K} sensors")
         self.perm, self.wrow, self.live, self.seg, self.inv = perm, wrow, live, seg, inv
+        self._finish_init(what, decoder, affine, points)
+
+    def _finish_init(self, what: str, decoder, affine, points) -> None:
+        """The end of the constructor, shared with DerivedSensorSet: the affine and the mesh points (one per sensor), the per-device caches, and the
+        upload of the tables when the decoder sits on a GPU."""
+        K = self.K
         self._dev = {}
         if affine is not None and (len(affine) != 2 or len(affine[0]) != K or len(affine[1]) != K):
             raise ValueError(f"{what}: affine must be a pair of {K} scales and {K} shifts (one per sensor)")
@@ -525,6 +531,9 @@ class SensorLikelihood:
             self._prec_host = None
         else:
             s = torch.as_tensor(sigma, dtype=torch.float64).detach().cpu()   # a tensor given on the device comes to the host once, here
+            if isinstance(sensors, DerivedSensorSet) and s.dim() == 1 and s.numel() != K:
+                raise ValueError(f"SensorLikelihood: with a DerivedSensorSet sigma must be None, a number or {K} numbers (one per reading: a derived reading has "
+                                 f"no field of its own), got shape {tuple(s.shape)}")
             if s.dim() > 1 or (s.dim() == 1 and s.numel() not in (n_fields, K)):
                 raise ValueError(f"SensorLikelihood: sigma must be None, a number, {n_fields} numbers (one per field) or {K} numbers (one per sensor), "
                                  f"got shape {tuple(s.shape)}")
@@ -533,7 +542,7 @@ class SensorLikelihood:
             p = 1.0 / (s * s)
             if p.dim() == 0:
                 self._prec_host = [float(p)] * K
-            elif p.numel() == n_fields:
+            elif p.numel() == n_fields and not isinstance(sensors, DerivedSensorSet):
                 self._prec_host = [float(p[f]) for f in sensors.out_field]
             else:
                 self._prec_host = [float(v) for v in p]
@@ -583,11 +592,13 @@ class SensorLikelihood:
         if sp is not None:
             precision = sp if precision is None else precision * sp
         dec = self.decoder
-        fused = self.fused if self.fused is not None else dec._act_dtype() == torch.bfloat16
+        fused = self.fused if self.fused is not None else dec._act_dtype() == torch.bfloat16 and (not isinstance(self.sensors, DerivedSensorSet) or self.sensors.fusable)
         z = y.detach().reshape(Bm, G, P, E // P).permute(0, 2, 1, 3)
         if fused:
             if dec._act_dtype() != torch.bfloat16:
                 raise ValueError("SensorLikelihood: the fused launch is bf16 only (set_compute_dtype('bf16'), or fused=False)")
+            if isinstance(self.sensors, DerivedSensorSet):
+                self.sensors._require_fusable("SensorLikelihood")
             N.require_gpu(y, "SensorLikelihood.score_and_grad input")
             wsse, _, dz = dec._sensor_grad_fused(z, self.sensors, obs.detach(), None if precision is None else precision.detach(), self.members, False, True)
         else:
@@ -1791,8 +1802,11 @@ class SensorThresholdVerification:
             raise ValueError(f"{what}: the fused launches carry up to {N.BRIER_MAX_N} members, got {members} (fused=False, or None)")
         self._like = SensorLikelihood(decoder, n_patches, members, sensors)   # its checks
         n_fields = sum(len(g) for g in decoder.field_groups)
-        tf = _check_thresholds(what, thresholds, n_fields)
-        self.thresholds = tf[:, torch.as_tensor(list(sensors.out_field), dtype=torch.long)].contiguous()   # [T, K] through the set's field index
+        if isinstance(sensors, DerivedSensorSet):   # a derived reading has no field of its own: [T] (every reading) or [T, K] (one column per reading)
+            self.thresholds = _check_thresholds(what, thresholds, sensors.K)
+        else:
+            tf = _check_thresholds(what, thresholds, n_fields)
+            self.thresholds = tf[:, torch.as_tensor(list(sensors.out_field), dtype=torch.long)].contiguous()   # [T, K] through the set's field index
         self._thr = {}
         self.decoder, self.n_patches, self.members, self.sensors, self.fused = decoder, n_patches, members, sensors, fused
 
@@ -2094,6 +2108,179 @@ def _composed_derived(Y, derived):
         q = a * a + b * b
         out.append(q * 0.5 if d.op == "energy" else torch.sqrt(q.to(torch.float64)).to(torch.float32))
     return torch.stack(out, dim=-2)
+
+
+def _composed_derived_readings(ya, yb, op, sa, ha, sb, hb):
+    """_composed_derived's float32 arithmetic per READING: ya, yb float32 [..., K], the decoded values of the two sources; op int64 [K] (-1 plain, else
+    the index into DERIVED_OPS); sa, ha, sb, hb float32 [K].  One torch op per product and sum, the float64 root rounded once.  Differentiable: the root
+    is taken of 1 where the sum of squares is 0 and the value selected to 0 there, so the gradient at a zero speed is exactly 0, as on the fused path."""
+    a = ya * sa + ha
+    b = yb * sb + hb
+    q = a * a + b * b
+    pos = q > 0
+    root = torch.sqrt(torch.where(pos, q, torch.ones_like(q)).to(torch.float64)).to(torch.float32)
+    mag = torch.where(pos, root, q)          # q == 0: the root of 0 (NaN stays NaN: q > 0 is false and q itself is returned)
+    x = torch.where(op == 2, a - b, torch.where(op == 1, q * 0.5, mag))
+    return torch.where(op < 0, ya, x)
+
+
+class DerivedSensorSet(SensorSet):
+    """K >= 1 point sensors of which some read a DERIVED quantity — a speed (hot-wire, Pitot tube, cup anemometer), an energy, a difference of two
+    fields (a differential tap) — at cell cell[k] of patch patch[k].  reading[k] is a field id (a plain sensor, exactly as in SensorSet: scaled units;
+    scale_values / scale_sigma apply to it) or a DerivedField (its a, b index the decoder's fields in output order; the reading is in the PHYSICAL
+    units of the derived quantity, and scale_values / scale_sigma pass it through).  Every consumer of a SensorSet takes this set with the same calls.
+    The launch tables of sea_decode_derived_sensor_sse (include/sea_hip.h) are built here, once, and uploaded once per device.  A reading occupies TWO
+    adjacent entries of the sorted, padded list — entry 2 i the W2 row of source a, entry 2 i + 1 that of source b (a plain reading: its field, and row
+    0) — so a (group, patch) segment of n readings takes 2 n entries padded to a multiple of 32:
+      perm    int32 [K_pad]: sorted entry -> reading (both entries of a pair; pad entries point at reading 0)
+      wrow    int32 [K_pad]: the rows of the group's second-layer weights
+      live    int32 [K_pad]: 1 at the first entry of a reading's pair, 0 elsewhere
+      op      int32 [K_pad]: -1 (plain) or the op code at the first entry of a pair; scale, shift float32 [K_pad]: (scale_a, shift_a) at 2 i, (scale_b,
+              shift_b) at 2 i + 1 (1, 0 elsewhere)
+      seg, Q, patches as in SensorSet; inv int64 [K]: reading -> the sorted position of its first entry
+    A derived reading whose sources lie in different decoder groups cannot be paired inside one segment: the set accepts it, `fusable` is False, no
+    launch tables exist (K_pad is None) and only the composed path serves it (fused=True raises, fused=None takes the composed path)."""
+
+    def __init__(self, decoder, n_patches: int, patch, cell, reading, affine=None, points=None):
+        what = "DerivedSensorSet"
+        if not isinstance(n_patches, int) or isinstance(n_patches, bool) or n_patches < 1:
+            raise ValueError(f"{what}: n_patches = {n_patches!r} must be a positive integer")
+        patch, cell = _int_list(patch, "patch", what), _int_list(cell, "cell", what)
+        if torch.is_tensor(reading):
+            reading = _int_list(reading, "reading", what)
+        try:
+            reading = list(reading)
+        except TypeError:
+            raise ValueError(f"{what}: reading must be a sequence of field ids and DerivedField, got {type(reading).__name__}") from None
+        K = len(patch)
+        if len(cell) != K or len(reading) != K:
+            raise ValueError(f"{what}: patch, cell and reading must have equal lengths, got {K}, {len(cell)}, {len(reading)}")
+        groups = tuple(tuple(int(f) for f in g) for g in decoder.field_groups)
+        where, bypos = {}, []           # field id -> (group, position in the group, position in the output); output position -> (group, position in the group)
+        for g, grp in enumerate(groups):
+            for j, f in enumerate(grp):
+                where[f] = (g, j, len(bypos))
+                bypos.append((g, j))
+        C_, Cp = int(decoder.n_inp), int(decoder._n_inp_p)
+        src = []                        # per reading: (op code, group a, row a, group b, row b, out a, out b, sa, ha, sb, hb)
+        for k in range(K):
+            if not 0 <= patch[k] < n_patches:
+                raise ValueError(f"{what}: sensor {k}: patch {patch[k]} outside 0 .. {n_patches - 1}")
+            if not 0 <= cell[k] < C_:
+                raise ValueError(f"{what}: sensor {k}: cell {cell[k]} outside 0 .. n_inp - 1 = {C_ - 1}")
+            r = reading[k]
+            if isinstance(r, DerivedField):
+                if r.a >= len(bypos) or r.b >= len(bypos):
+                    raise ValueError(f"{what}: sensor {k} ({r.name}): sources a = {r.a}, b = {r.b} outside the {len(bypos)} fields")
+                (ga, ja), (gb, jb) = bypos[r.a], bypos[r.b]
+                src.append((DERIVED_OPS.index(r.op), ga, ja * Cp + cell[k], gb, jb * Cp + cell[k], r.a, r.b, r.scale_a, r.shift_a, r.scale_b, r.shift_b))
+                continue
+            if torch.is_tensor(r) and r.dim() == 0 and r.dtype != torch.bool and not r.is_floating_point() and not r.is_complex():
+                r = int(r)
+            if isinstance(r, bool) or not (isinstance(r, int) or (_np is not None and isinstance(r, _np.integer))):
+                raise ValueError(f"{what}: sensor {k}: a reading must be a field id (an integer) or a DerivedField, got {type(r).__name__}")
+            r = reading[k] = int(r)
+            if r not in where:
+                raise ValueError(f"{what}: sensor {k}: field {r} is not one of the decoder's fields {sorted(where)}")
+            g, j, pos = where[r]
+            src.append((-1, g, j * Cp + cell[k], g, 0, pos, pos, 1.0, 0.0, 1.0, 0.0))
+        self.n_patches, self.n_inp, self.Cp, self.groups, self.K = n_patches, C_, Cp, groups, K
+        self.patch, self.cell, self.reading = patch, cell, reading
+        self.field = [r if isinstance(r, int) else None for r in reading]
+        self.out_field = [s[5] if s[0] < 0 else None for s in src]    # a derived reading has no field of its own (a per-field sigma is refused)
+        self.plain = [s[0] < 0 for s in src]
+        self._src = src
+        self.fusable = all(s[1] == s[3] for s in src)
+        self.patches = sorted(set(patch))
+        G, T, Q = len(groups), N.SENSOR_TILE, len(self.patches)
+        if Q > N.SENSOR_MAX_PATCHES:
+            raise ValueError(f"{what}: {Q} observed patches; a set carries at most {N.SENSOR_MAX_PATCHES}")
+        self.Q, self.K_pad = Q, None
+        self.perm = self.wrow = self.live = self.seg = self.inv = self.op = self.scale = self.shift = None
+        if self.fusable:
+            buckets = {}
+            for k in range(K):
+                buckets.setdefault((src[k][1], patch[k]), []).append(k)
+            perm, wrow, live, op, scale, shift, seg = [], [], [], [], [], [], []
+            for g in range(G):
+                row = []
+                for p in self.patches:
+                    row.append(len(perm))
+                    ks = buckets.get((g, p), [])
+                    for k in ks:
+                        o, _, ra, _, rb, _, _, sa, ha, sb, hb = src[k]
+                        perm += [k, k]
+                        wrow += [ra, rb]
+                        live += [1, 0]
+                        op += [o, -1]
+                        scale += [sa, sb]
+                        shift += [ha, hb]
+                    pad = -(2 * len(ks)) % T
+                    perm += [0] * pad
+                    wrow += [0] * pad
+                    live += [0] * pad
+                    op += [-1] * pad
+                    scale += [1.0] * pad
+                    shift += [0.0] * pad
+                row.append(len(perm))
+                seg.append(row)
+            K_pad = len(perm)
+            inv = [0] * K
+            for s_, (k, l) in enumerate(zip(perm, live)):
+                if l:
+                    inv[k] = s_
+            # the kernels trust these: check them here
+            for g in range(G):
+                for qi in range(Q):
+                    a, b = seg[g][qi], seg[g][qi + 1]
+                    if not 0 <= a <= b <= K_pad or (b - a) % T:
+                        raise ValueError(f"{what}: internal error: segment ({g}, {qi}) = [{a}, {b}) is not a multiple of {T} inside 0 .. {K_pad}")
+                    for s_ in range(a, b):
+                        if not 0 <= wrow[s_] < len(groups[g]) * Cp or not 0 <= perm[s_] < K or not -1 <= op[s_] < len(DERIVED_OPS):
+                            raise ValueError(f"{what}: internal error: entry {s_}: W2 row {wrow[s_]}, reading {perm[s_]} or op {op[s_]} out of range")
+                        if s_ % 2 and (op[s_] != -1 or live[s_]):
+                            raise ValueError(f"{what}: internal error: entry {s_}: the second entry of a pair carries an op or is live")
+            if K_pad < T or K_pad >= 2 ** 31 or sum(live) != K or any(inv[k] % 2 for k in range(K)):
+                raise ValueError(f"{what}: internal error: K_pad = {K_pad}, {sum(live)} live entries for {K} readings")
+            self.K_pad, self.perm, self.wrow, self.live, self.seg, self.inv = K_pad, perm, wrow, live, seg, inv
+            self.op, self.scale, self.shift = op, scale, shift
+        self._finish_init(what, decoder, affine, points)   # the affine holds 1 and 0 at a derived reading
+
+    def tables(self, device):
+        """The tables on `device` (uploaded once per device): the composed path's patch, cell, out_a, out_b, cop (int64 [K]) and csa, cha, csb, chb
+        (float32 [K]) and, for a fusable set, SensorSet's perm, wrow, live, seg, patches, inv plus op (int32), scale, shift (float32), each [K_pad]."""
+        device = torch.device(device)
+        t = self._dev.get(device)
+        if t is None:
+            i32 = lambda v: torch.tensor(v, dtype=torch.int32, device=device)     # noqa: E731
+            i64 = lambda v: torch.tensor(v, dtype=torch.int64, device=device)     # noqa: E731
+            f32 = lambda v: torch.tensor(v, dtype=torch.float32, device=device)   # noqa: E731
+            col = lambda i: [s[i] for s in self._src]                             # noqa: E731
+            t = dict(patches=i64(self.patches), patch=i64(self.patch), cell=i64(self.cell), out_a=i64(col(5)), out_b=i64(col(6)), cop=i64(col(0)),
+                     csa=f32(col(7)), cha=f32(col(8)), csb=f32(col(9)), chb=f32(col(10)))
+            if self.fusable:
+                t.update(perm=i32(self.perm), wrow=i32(self.wrow), live=i32(self.live), seg=i32(self.seg), inv=i64(self.inv), op=i32(self.op),
+                         scale=f32(self.scale), shift=f32(self.shift))
+            self._dev[device] = t
+        return t
+
+    def composed_predictions(self, y: torch.Tensor) -> torch.Tensor:
+        """The readings of decoded fields y [Bm, P, n_fields, C] as float32 [Bm, K]: a gather of both source values and _composed_derived's float32
+        arithmetic (the composed path; differentiable)."""
+        T = self.tables(y.device)
+        ya = y[:, T["patch"], T["out_a"], T["cell"]].to(torch.float32)
+        yb = y[:, T["patch"], T["out_b"], T["cell"]].to(torch.float32)
+        return _composed_derived_readings(ya, yb, T["cop"], T["csa"], T["cha"], T["csb"], T["chb"])
+
+    def _require_fusable(self, what: str) -> None:
+        if not self.fusable:
+            raise ValueError(f"{what}: this DerivedSensorSet has a derived reading whose sources lie in different decoder groups: the fused launches pair "
+                             f"two rows of ONE group's weights (fused=False, or None)")
+
+    def _coeffs(self, device):
+        if self._affine is None:
+            raise ValueError("DerivedSensorSet: this set was not built from a mesh (MeshUnpatcher.derived_sensor_set): it has no field scaling")
+        return SensorSet._coeffs(self, device)
 
 
 def _derived_thresholds(what: str, thresholds, nd: int, max_t: int, finite: bool) -> torch.Tensor:

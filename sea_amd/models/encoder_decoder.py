@@ -289,8 +289,12 @@ class Decode(nn.Module):
         (K columns against every cell), and no measured size has the composed path ahead (tools/sensor_bench.py, profiles/sensor_bench.txt, DESIGN.md section 7f;
         64 members x 64 patches, 16 - 4096 sensors: one history 0.10 - 0.12 ms fused against 0.12 - 0.14 ms composed, level within the windows' spread in two
         rows; four histories 0.10 - 0.14 against 0.21 - 0.29 ms; 0.5 - 46 MB of extra memory against 84 - 348 MB).  A call with device inputs reads nothing back and
-        uploads nothing once the set's tables are on the device."""
-        from ..ensemble import SensorSet, _check_sensor_operands
+        uploads nothing once the set's tables are on the device.
+        `sensors` may be a sea_amd.ensemble.DerivedSensorSet (readings of a speed, an energy or a difference, plain sensors mixed in): obs then holds
+        the readings in their own units, the fused launch is sea_decode_derived_sensor_sse (a reading is two adjacent entries of the sorted list), the
+        composed path gathers both source values and applies the derived arithmetic in float32 torch ops, and fused=None takes the fused launch in
+        bf16 only when every derived reading has its two sources in one decoder group (fused=True raises otherwise)."""
+        from ..ensemble import DerivedSensorSet, SensorSet, _check_sensor_operands
 
         if z.dim() != 4 or z.shape[2] != self.num_groups or z.shape[3] != self.embed_dim:
             raise ValueError(f"sea_amd.Decode.sensor_sse: z must be [Bm, P, {self.num_groups}, {self.embed_dim}], got {tuple(z.shape)}")
@@ -306,10 +310,13 @@ class Decode(nn.Module):
         K = sensors.K
         _check_sensor_operands("sea_amd.Decode.sensor_sse", obs, precision, B, K, z.device)
         dt = self._act_dtype()
+        derived = isinstance(sensors, DerivedSensorSet)   # readings of derived quantities: the pair launch (sea_decode_derived_sensor_sse), or the composed path
         if fused is None:
-            fused = dt == torch.bfloat16
+            fused = dt == torch.bfloat16 and (not derived or sensors.fusable)
         if fused and dt != torch.bfloat16:
             raise ValueError("sea_amd.Decode.sensor_sse: the fused launch is bf16 only (set_compute_dtype('bf16'), or fused=False)")
+        if fused and derived:
+            sensors._require_fusable("sea_amd.Decode.sensor_sse")
         N.require_gpu(z, "Decode.sensor_sse input")
         T = sensors.tables(z.device)
         with torch.no_grad():
@@ -317,7 +324,7 @@ class Decode(nn.Module):
             prec = None if precision is None else precision.detach()
             if not fused:
                 y = self.forward(z.detach())                                              # [Bm, P, n_fields, C]
-                pred = y[:, T["patch"], T["out_field"], T["cell"]]                         # [Bm, K]
+                pred = sensors.composed_predictions(y) if derived else y[:, T["patch"], T["out_field"], T["cell"]]   # [Bm, K]
                 o = obs.unsqueeze(1).expand(B, members, K).reshape(Bm, K)
                 if prec is None:
                     d = pred - o
@@ -341,8 +348,12 @@ class Decode(nn.Module):
             bias = self._shadow[3]
             obs_s = obs.index_select(1, T["perm"])                                         # [B, K_pad]: sorted, padded (a pad entry repeats sensor 0 and is not live)
             prec_s = None if prec is None else prec.index_select(prec.dim() - 1, T["perm"])
-            out = ops.decode_sensor_sse([dict(H=hid[g], W2=W2[g], bias=bias[g]) for g in range(G)], obs_s, T["live"], T["wrow"], T["seg"], self._n_inp_p,
-                                        members=members, prec=prec_s, predictions=predictions, dtype=dt)
+            if derived:   # obs and prec through perm land on both entries of a pair (the launch reads the first); inv points at the first
+                out = ops.decode_derived_sensor_sse([dict(H=hid[g], W2=W2[g], bias=bias[g]) for g in range(G)], obs_s, T["live"], T["wrow"], T["seg"], T["op"],
+                                                    T["scale"], T["shift"], self._n_inp_p, members=members, prec=prec_s, predictions=predictions, dtype=dt)
+            else:
+                out = ops.decode_sensor_sse([dict(H=hid[g], W2=W2[g], bias=bias[g]) for g in range(G)], obs_s, T["live"], T["wrow"], T["seg"], self._n_inp_p,
+                                            members=members, prec=prec_s, predictions=predictions, dtype=dt)
             if not predictions:
                 return out
             return out[0], out[1].index_select(1, T["inv"])
@@ -365,8 +376,10 @@ class Decode(nn.Module):
         patches, 16 - 4096 sensors over 4 - 64 patches, loss + backward: one history 0.23 - 0.29 ms fused against 0.40 - 0.68 ms composed, four
         histories 0.23 - 0.33 against 0.83 - 0.97 ms, every row outside the windows' spread; 1.5 - 127 MB of extra memory against 206 - 846 MB; the
         score alone, sensor_sse, takes 0.09 - 0.12 ms).  A call with device inputs reads nothing back and uploads nothing once the set's tables
-        are on the device."""
-        from ..ensemble import SensorSet, _check_sensor_operands
+        are on the device.
+        A sea_amd.ensemble.DerivedSensorSet is taken as in sensor_sse: the fused launch is sea_decode_derived_sensor_grad (the two partial derivatives
+        of a reading weight the residuals of its two entries; exactly 0 at a zero speed), fused=None by the same rule."""
+        from ..ensemble import DerivedSensorSet, SensorSet, _check_sensor_operands
 
         what = "sea_amd.Decode.sensor_loss"
         if z.dim() != 4 or z.shape[2] != self.num_groups or z.shape[3] != self.embed_dim:
@@ -386,10 +399,13 @@ class Decode(nn.Module):
             raise ValueError(f"{what}: obs and precision must not require grad (gradients flow to z only)")
         self._require_frozen("sensor_loss")
         dt = self._act_dtype()
+        derived = isinstance(sensors, DerivedSensorSet)
         if fused is None:
-            fused = dt == torch.bfloat16
+            fused = dt == torch.bfloat16 and (not derived or sensors.fusable)
         if fused and dt != torch.bfloat16:
             raise ValueError(f"{what}: the fused launch is bf16 only (set_compute_dtype('bf16'), or fused=False)")
+        if fused and derived:
+            sensors._require_fusable(what)
         N.require_gpu(z, "Decode.sensor_loss input")
         obs = obs.detach()
         prec = None if precision is None else precision.detach()
@@ -398,7 +414,7 @@ class Decode(nn.Module):
             return (out[0], out[1]) if predictions else out
         T = sensors.tables(z.device)
         y = _DecodeFn.apply(z, self)                                                  # [Bm, P, n_fields, C]
-        pred = y[:, T["patch"], T["out_field"], T["cell"]]                             # [Bm, K]
+        pred = sensors.composed_predictions(y) if derived else y[:, T["patch"], T["out_field"], T["cell"]]   # [Bm, K]
         o = obs.unsqueeze(1).expand(B, members, K).reshape(Bm, K)
         if prec is None:
             d = pred - o
@@ -415,7 +431,12 @@ class Decode(nn.Module):
 
     def _sensor_grad_fused(self, z: torch.Tensor, sensors, obs: torch.Tensor, prec: Optional[torch.Tensor], members: int, predictions: bool, want_grad: bool):
         """The fused bf16 launches of sensor_loss on checked arguments, without autograd: (wsse [Bm], pred [Bm, K] or None, dz f32 [Bm, P, G, D] or None)."""
+        from ..ensemble import DerivedSensorSet
+
         dt = torch.bfloat16
+        derived = isinstance(sensors, DerivedSensorSet)
+        if derived:
+            sensors._require_fusable("sea_amd.Decode.sensor_loss")
         with torch.no_grad():
             Bm, P, G, D = z.shape
             T, Q = sensors.tables(z.device), sensors.Q
@@ -426,8 +447,13 @@ class Decode(nn.Module):
             dpre = [torch.empty(Q * Bm, self.MLP_hidden, device=z.device, dtype=dt) for _ in range(G)]
             obs_s = obs.index_select(1, T["perm"])                                         # [B, K_pad]: sorted, padded (a pad entry repeats sensor 0 and is not live)
             prec_s = None if prec is None else prec.index_select(prec.dim() - 1, T["perm"])
-            wsse, pred = ops.decode_sensor_grad([dict(H=hid[g], W2=W2[g], bias=bias[g], dH=dpre[g], Z=pre[g]) for g in range(G)], obs_s, T["live"], T["wrow"],
-                                                T["seg"], self._n_inp_p, members=members, prec=prec_s, predictions=predictions, dtype=dt)
+            if derived:   # the pair launch (sea_decode_derived_sensor_grad)
+                wsse, pred = ops.decode_derived_sensor_grad([dict(H=hid[g], W2=W2[g], bias=bias[g], dH=dpre[g], Z=pre[g]) for g in range(G)], obs_s, T["live"],
+                                                            T["wrow"], T["seg"], T["op"], T["scale"], T["shift"], self._n_inp_p, members=members, prec=prec_s,
+                                                            predictions=predictions, dtype=dt)
+            else:
+                wsse, pred = ops.decode_sensor_grad([dict(H=hid[g], W2=W2[g], bias=bias[g], dH=dpre[g], Z=pre[g]) for g in range(G)], obs_s, T["live"], T["wrow"],
+                                                    T["seg"], self._n_inp_p, members=members, prec=prec_s, predictions=predictions, dtype=dt)
             if pred is not None:
                 pred = pred.index_select(1, T["inv"])
             dz = None

@@ -1129,61 +1129,74 @@ def decode_sensor_sse(groups: Sequence[Dict], obs: torch.Tensor, live: torch.Ten
     decoded values f32 [Bm, K_pad] in sorted, padded order).  groups as fill_decode_sensor_sse; the tables live, wrow int32 [K_pad] and seg int32
     [n_groups, Q + 1] are a SensorSet's (built and range-checked on the host: the kernel trusts their contents); obs f32 [B, K_pad] and prec (None, f32
     [K_pad] or [B, K_pad]) in the same sorted, padded order; Bm = B * members = H rows / Q.  Everything else is checked on the host before the launch."""
+    return _sensor_sse_call("decode_sensor_sse", groups, obs, live, wrow, seg, Cp, members, prec, predictions, dtype, None)
+
+
+def _sensor_sse_call(what: str, groups, obs, live, wrow, seg, Cp: int, members: int, prec, predictions: bool, dtype, _derived):
+    """The operand checks and the launch decode_sensor_sse and decode_derived_sensor_sse share, under the caller's name `what`; _derived: None, or the
+    pair tables (op, scale, shift) of decode_derived_sensor_sse."""
     if dtype != torch.bfloat16:
-        raise ValueError(f"decode_sensor_sse: the fused launch is bf16 only, got {dtype}")
+        raise ValueError(f"{what}: the fused launch is bf16 only, got {dtype}")
     if not groups or len(groups) > N.DECODE_MSE_MAX_GROUPS:
-        raise ValueError(f"decode_sensor_sse: {len(groups)} groups; a launch carries 1 .. {N.DECODE_MSE_MAX_GROUPS}")
+        raise ValueError(f"{what}: {len(groups)} groups; a launch carries 1 .. {N.DECODE_MSE_MAX_GROUPS}")
     if Cp < 32 or Cp % 32:
-        raise ValueError(f"decode_sensor_sse: need Cp a multiple of 32, got Cp = {Cp}")
+        raise ValueError(f"{what}: need Cp a multiple of 32, got Cp = {Cp}")
     dev = obs.device
     if seg.dim() != 2 or seg.shape[0] != len(groups) or seg.shape[1] < 2 or seg.dtype != torch.int32 or not seg.is_contiguous() or seg.device != dev:
-        raise ValueError(f"decode_sensor_sse: seg must be a contiguous int32 [{len(groups)}, Q + 1 >= 2] on {dev}, got {tuple(seg.shape)} {seg.dtype} on {seg.device}")
+        raise ValueError(f"{what}: seg must be a contiguous int32 [{len(groups)}, Q + 1 >= 2] on {dev}, got {tuple(seg.shape)} {seg.dtype} on {seg.device}")
     Q = seg.shape[1] - 1
     if Q > N.SENSOR_MAX_PATCHES:
-        raise ValueError(f"decode_sensor_sse: {Q} observed patches; a launch carries 1 .. {N.SENSOR_MAX_PATCHES}")
+        raise ValueError(f"{what}: {Q} observed patches; a launch carries 1 .. {N.SENSOR_MAX_PATCHES}")
     for name, t in (("live", live), ("wrow", wrow)):
         if t.dim() != 1 or t.dtype != torch.int32 or not t.is_contiguous() or t.device != dev or t.shape[0] != live.shape[0]:
-            raise ValueError(f"decode_sensor_sse: {name} must be a contiguous int32 [K_pad] on {dev}, got {tuple(t.shape)} {t.dtype} on {t.device}")
+            raise ValueError(f"{what}: {name} must be a contiguous int32 [K_pad] on {dev}, got {tuple(t.shape)} {t.dtype} on {t.device}")
     K_pad = live.shape[0]
     if K_pad < N.SENSOR_TILE or K_pad % N.SENSOR_TILE:
-        raise ValueError(f"decode_sensor_sse: K_pad = {K_pad} must be a positive multiple of {N.SENSOR_TILE}")
+        raise ValueError(f"{what}: K_pad = {K_pad} must be a positive multiple of {N.SENSOR_TILE}")
     R, S = tuple(groups[0]["H"].shape) if groups[0]["H"].dim() == 2 else (0, 0)
     if R < 1 or R % Q or S < 8 or S % 8 or S > N.DECODE_MSE_MAX_S:
-        raise ValueError(f"decode_sensor_sse: H must be [Q * Bm, S] with Q = {Q} and S a multiple of 8 up to {N.DECODE_MSE_MAX_S}, got {tuple(groups[0]['H'].shape)}")
+        raise ValueError(f"{what}: H must be [Q * Bm, S] with Q = {Q} and S a multiple of 8 up to {N.DECODE_MSE_MAX_S}, got {tuple(groups[0]['H'].shape)}")
     Bm = R // Q
     if not isinstance(members, int) or members < 1 or Bm % members:
-        raise ValueError(f"decode_sensor_sse: members = {members!r} must be a positive integer that divides Bm = {Bm}")
+        raise ValueError(f"{what}: members = {members!r} must be a positive integer that divides Bm = {Bm}")
     B = Bm // members
     for i, d in enumerate(groups):
         for name in ("H", "W2"):
             t = d[name]
             if t.dim() != 2 or t.stride(1) != 1:
-                raise ValueError(f"decode_sensor_sse group {i}: {name}: need a 2-D tensor with unit inner stride, got shape {tuple(t.shape)} strides {t.stride()}")
+                raise ValueError(f"{what} group {i}: {name}: need a 2-D tensor with unit inner stride, got shape {tuple(t.shape)} strides {t.stride()}")
             if t.dtype != dtype or t.device != dev or t.shape[1] != S or (name != "W2" and t.shape[0] != R):
-                raise ValueError(f"decode_sensor_sse group {i}: {name} must be a {dtype} [{'n_fields * Cp' if name == 'W2' else R}, {S}] tensor on {dev}, got "
+                raise ValueError(f"{what} group {i}: {name} must be a {dtype} [{'n_fields * Cp' if name == 'W2' else R}, {S}] tensor on {dev}, got "
                                  f"{tuple(t.shape)} {t.dtype} on {t.device}")
             if t.stride(0) % 8 or t.data_ptr() % 16:
-                raise ValueError(f"decode_sensor_sse group {i}: {name} needs a row stride that is a multiple of 8 and a 16-byte-aligned base (stride {t.stride(0)})")
+                raise ValueError(f"{what} group {i}: {name} needs a row stride that is a multiple of 8 and a 16-byte-aligned base (stride {t.stride(0)})")
         W2, b = d["W2"], d["bias"]
         if W2.shape[0] < Cp or W2.shape[0] % Cp:
-            raise ValueError(f"decode_sensor_sse group {i}: W2 has {W2.shape[0]} rows, not a multiple of Cp = {Cp}")
+            raise ValueError(f"{what} group {i}: W2 has {W2.shape[0]} rows, not a multiple of Cp = {Cp}")
         if b.dtype != torch.float32 or b.dim() != 1 or b.shape[0] != W2.shape[0] or not b.is_contiguous() or b.device != dev or b.data_ptr() % 16:
-            raise ValueError(f"decode_sensor_sse group {i}: bias must be a contiguous, 16-byte-aligned float32 [{W2.shape[0]}] on {dev}, got {tuple(b.shape)} {b.dtype}")
+            raise ValueError(f"{what} group {i}: bias must be a contiguous, 16-byte-aligned float32 [{W2.shape[0]}] on {dev}, got {tuple(b.shape)} {b.dtype}")
     if obs.dtype != torch.float32 or obs.dim() != 2 or tuple(obs.shape) != (B, K_pad) or obs.stride(1) != 1 or obs.stride(0) % 4 or obs.stride(0) < K_pad \
             or obs.data_ptr() % 16:
-        raise ValueError(f"decode_sensor_sse: obs must be a 16-byte-aligned float32 [{B}, {K_pad}] with unit inner stride and a row stride that is a multiple of 4, "
+        raise ValueError(f"{what}: obs must be a 16-byte-aligned float32 [{B}, {K_pad}] with unit inner stride and a row stride that is a multiple of 4, "
                          f"got {tuple(obs.shape)} {obs.dtype} strides {obs.stride()}")
     if prec is not None:
         if prec.dtype != torch.float32 or prec.device != dev or tuple(prec.shape) not in ((K_pad,), (B, K_pad)) or prec.stride(-1) != 1 or prec.data_ptr() % 16 \
                 or (prec.dim() == 2 and (prec.stride(0) % 4 or prec.stride(0) < K_pad)):
-            raise ValueError(f"decode_sensor_sse: prec must be None or a 16-byte-aligned float32 [{K_pad}] or [{B}, {K_pad}] on {dev} with unit inner stride, got "
+            raise ValueError(f"{what}: prec must be None or a 16-byte-aligned float32 [{K_pad}] or [{B}, {K_pad}] on {dev} with unit inner stride, got "
                              f"{tuple(prec.shape)} {prec.dtype} strides {prec.stride()} on {prec.device}")
-    N.require_gpu(obs, "decode_sensor_sse obs")   # every operand is on the observation's device (checked above)
+    if _derived is not None:
+        _derived = _check_derived_sensor_tables(what, _derived, K_pad, dev)
+    N.require_gpu(obs, f"{what} obs")   # every operand is on the observation's device (checked above)
     wsse = torch.empty(Bm, device=dev, dtype=torch.float32)
     pred = torch.empty(Bm, K_pad, device=dev, dtype=torch.float32) if predictions else None
     work = torch.empty(Q * len(groups) * Bm, device=dev, dtype=torch.float32)
     arr, P = (N.SeaDecodeMseGroup * len(groups))(), N.SeaDecodeSensorSse()
     fill_decode_sensor_sse(arr, P, groups, obs, prec, live, wrow, seg, members, Cp, wsse, pred, work)
+    if _derived is not None:
+        T = N.SeaDerivedSensorTables()
+        fill_derived_sensor_tables(T, *_derived)
+        N.check(N.lib().sea_decode_derived_sensor_sse(arr, len(groups), C.byref(P), C.byref(T), N.dtype_code(dtype), N.stream_ptr()), "sea_decode_derived_sensor_sse")
+        return (wsse, pred) if predictions else wsse
     N.check(N.lib().sea_decode_sensor_sse(arr, len(groups), C.byref(P), N.dtype_code(dtype), N.stream_ptr()), "sea_decode_sensor_sse")
     return (wsse, pred) if predictions else wsse
 
@@ -1212,7 +1225,12 @@ def decode_sensor_grad(groups: Sequence[Dict], obs: torch.Tensor, live: torch.Te
     [Q * Bm, S] is written IN PLACE with 2 grad_scale * (w d rounded to bf16) W2 [* gelu'(Z) where the group carries a Z], zeros at the rows of a
     (group, patch) pair without sensors.  Returns (wsse f32 [Bm], pred f32 [Bm, K_pad] or None).  groups as fill_decode_sensor_grad; the tables and obs /
     prec as decode_sensor_sse.  Everything is checked on the host before the launch."""
-    what = "decode_sensor_grad"
+    return _sensor_grad_call("decode_sensor_grad", groups, obs, live, wrow, seg, Cp, members, prec, predictions, grad_scale, dtype, None)
+
+
+def _sensor_grad_call(what: str, groups, obs, live, wrow, seg, Cp: int, members: int, prec, predictions: bool, grad_scale, dtype, _derived):
+    """The operand checks and the launch decode_sensor_grad and decode_derived_sensor_grad share, under the caller's name `what`; _derived as in
+    _sensor_sse_call."""
     if dtype != torch.bfloat16:
         raise ValueError(f"{what}: the fused launch is bf16 only, got {dtype}")
     if not groups or len(groups) > N.DECODE_MSE_MAX_GROUPS:
@@ -1267,14 +1285,54 @@ def decode_sensor_grad(groups: Sequence[Dict], obs: torch.Tensor, live: torch.Te
                 or (prec.dim() == 2 and (prec.stride(0) % 4 or prec.stride(0) < K_pad)):
             raise ValueError(f"{what}: prec must be None or a 16-byte-aligned float32 [{K_pad}] or [{B}, {K_pad}] on {dev} with unit inner stride, got "
                              f"{tuple(prec.shape)} {prec.dtype} strides {prec.stride()} on {prec.device}")
+    if _derived is not None:
+        _derived = _check_derived_sensor_tables(what, _derived, K_pad, dev)
     N.require_gpu(obs, f"{what} obs")   # every operand is on the observation's device (checked above)
     wsse = torch.empty(Bm, device=dev, dtype=torch.float32)
     pred = torch.empty(Bm, K_pad, device=dev, dtype=torch.float32) if predictions else None
     work = torch.empty(Q * len(groups) * Bm, device=dev, dtype=torch.float32)
     arr, P = (N.SeaDecodeMseGroup * len(groups))(), N.SeaDecodeSensorGrad()
     fill_decode_sensor_grad(arr, P, groups, obs, prec, live, wrow, seg, members, Cp, wsse, pred, work, float(grad_scale))
+    if _derived is not None:
+        T = N.SeaDerivedSensorTables()
+        fill_derived_sensor_tables(T, *_derived)
+        N.check(N.lib().sea_decode_derived_sensor_grad(arr, len(groups), C.byref(P), C.byref(T), N.dtype_code(dtype), N.stream_ptr()), "sea_decode_derived_sensor_grad")
+        return wsse, pred
     N.check(N.lib().sea_decode_sensor_grad(arr, len(groups), C.byref(P), N.dtype_code(dtype), N.stream_ptr()), "sea_decode_sensor_grad")
     return wsse, pred
+
+
+def fill_derived_sensor_tables(T: N.SeaDerivedSensorTables, op, scale, shift) -> None:
+    """The pair tables of sea_decode_derived_sensor_sse / _grad: op int32, scale and shift f32, each [K_pad] on the device."""
+    T.op, T.scale, T.shift = op.data_ptr(), scale.data_ptr(), shift.data_ptr()
+
+
+def _check_derived_sensor_tables(what: str, tables, K_pad: int, dev):
+    """(op, scale, shift) of a DerivedSensorSet: contiguous, 16-byte-aligned [K_pad] tensors on `dev` (their contents were range-checked by the set)."""
+    if not isinstance(tables, (tuple, list)) or len(tables) != 3 or any(not torch.is_tensor(t) for t in tables):
+        raise ValueError(f"{what}: the pair tables must be three tensors (op, scale, shift)")
+    for name, t, dt in zip(("op", "scale", "shift"), tables, (torch.int32, torch.float32, torch.float32)):
+        if t.dim() != 1 or t.shape[0] != K_pad or t.dtype != dt or not t.is_contiguous() or t.device != dev or t.data_ptr() % 16:
+            raise ValueError(f"{what}: {name} must be a contiguous, 16-byte-aligned {dt} [{K_pad}] on {dev}, got {tuple(t.shape)} {t.dtype} on {t.device}")
+    return tuple(tables)
+
+
+def decode_derived_sensor_sse(groups: Sequence[Dict], obs: torch.Tensor, live: torch.Tensor, wrow: torch.Tensor, seg: torch.Tensor, op: torch.Tensor,
+                              scale: torch.Tensor, shift: torch.Tensor, Cp: int, members: int = 1, prec: Optional[torch.Tensor] = None, predictions: bool = False,
+                              dtype: torch.dtype = torch.bfloat16):
+    """sea_decode_derived_sensor_sse: decode_sensor_sse for a DerivedSensorSet — a reading is the pair of sorted entries (2 i, 2 i + 1) = (source a, source
+    b); op int32, scale, shift f32 [K_pad] are the set's pair tables (op == -1 at entry 2 i: a plain reading).  obs and prec are read at the even
+    entries; pred [Bm, K_pad] holds the reading's value at both entries.  Operand checks: those of decode_sensor_sse, plus the three tables."""
+    return _sensor_sse_call("decode_derived_sensor_sse", groups, obs, live, wrow, seg, Cp, members, prec, predictions, dtype, (op, scale, shift))
+
+
+def decode_derived_sensor_grad(groups: Sequence[Dict], obs: torch.Tensor, live: torch.Tensor, wrow: torch.Tensor, seg: torch.Tensor, op: torch.Tensor,
+                               scale: torch.Tensor, shift: torch.Tensor, Cp: int, members: int = 1, prec: Optional[torch.Tensor] = None, predictions: bool = False,
+                               grad_scale: float = 1.0, dtype: torch.dtype = torch.bfloat16):
+    """sea_decode_derived_sensor_grad: decode_derived_sensor_sse's score (the same bits) and the gradient to the hidden rows, every group's dH written in
+    place as decode_sensor_grad does.  Returns (wsse, pred or None)."""
+    return _sensor_grad_call("decode_derived_sensor_grad", groups, obs, live, wrow, seg, Cp, members, prec, predictions, grad_scale, dtype, (op, scale, shift))
+
 
 
 def fill_decode_field_grad(groups_arr, P: N.SeaDecodeFieldGrad, groups: Sequence[Dict], obs, prec, field_prec, counts, n_patches: int, members: int, C_: int, Cp: int,

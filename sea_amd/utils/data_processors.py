@@ -143,6 +143,50 @@ class MeshUnpatcher:
         return SensorSet(decoder, int(P), [slot[pt] // C for pt in pts], [slot[pt] % C for pt in pts], flds,
                          affine=([scale[f] for f in flds], [shift[f] for f in flds]), points=pts)
 
+    def derived_sensor_set(self, decoder, points, readings):
+        """Point sensors on the mesh of which some read a derived quantity, as a sea_amd.ensemble.DerivedSensorSet for `decoder`: readings[k] is a
+        field id (a plain sensor at mesh point points[k], as in sensor_set: it gets the forward affine of its field, so scale_values / scale_sigma
+        take its physical readings into scaled units) or an (op, a, b) / (op, a, b, name) spec as in derived_fields — ("magnitude", 0, 1) is a speed
+        probe — which gets the inverse affine of its two sources: that reading is in the PHYSICAL units of the derived quantity, and scale_values /
+        scale_sigma leave it as it is.  The mesh points are recorded (sensor_taper)."""
+        from ..ensemble import DerivedSensorSet, _int_list
+
+        pts = _int_list(points, "points", "derived_sensor_set")
+        try:
+            readings = list(readings)
+        except TypeError:
+            raise ValueError(f"derived_sensor_set: readings must be a sequence of field ids and (op, a, b) specs, got {type(readings).__name__}") from None
+        if len(pts) != len(readings):
+            raise ValueError(f"derived_sensor_set: points and readings must have equal lengths, got {len(pts)} and {len(readings)}")
+        slot = self.partitioner.point_slot.detach().cpu().tolist()
+        P, C = self.partitioner.padded_index_map.shape
+        if int(decoder.n_inp) < C:
+            raise ValueError(f"derived_sensor_set: the decoder's cell width n_inp = {decoder.n_inp} is below the mesh's {C} slots per patch: it decodes another partition")
+        scale, shift = self._forward_coefficients()
+        rd, a_, b_ = [], [], []
+        for k, (pt, r) in enumerate(zip(pts, readings)):
+            if not 0 <= pt < len(slot):
+                raise ValueError(f"derived_sensor_set: sensor {k}: mesh point {pt} outside 0 .. {len(slot) - 1}")
+            if isinstance(r, (tuple, list)):
+                try:
+                    rd.append(self.derived_fields([r])[0])
+                except ValueError as e:
+                    raise ValueError(f"derived_sensor_set: sensor {k}: {e}") from None
+                a_.append(1.0)
+                b_.append(0.0)
+                continue
+            try:                                                        # a field id as DerivedSensorSet takes it: int, numpy integer or 0-dim integer tensor
+                r = _int_list([r], "readings", "derived_sensor_set")[0]
+            except ValueError:
+                r = None
+            if r is None or not 0 <= r < len(scale):
+                raise ValueError(f"derived_sensor_set: sensor {k}: a reading must be a field id in 0 .. {len(scale) - 1} or an (op, a, b) spec, "
+                                 f"got {readings[k]!r}") from None
+            rd.append(r)
+            a_.append(scale[r])
+            b_.append(shift[r])
+        return DerivedSensorSet(decoder, int(P), [slot[pt] // C for pt in pts], [slot[pt] % C for pt in pts], rd, affine=(a_, b_), points=pts)
+
     def sensor_taper(self, sensors, radius) -> torch.Tensor:
         """Localisation weights for SensorKalman(taper=...): float32 [P, K] on the partitioner's device, gaspari_cohn(distance, radius) between every
         patch's centroid — the mean of the partitioner's full_coords over the patch's valid slots — and every sensor's mesh point (the `points` a set
@@ -412,6 +456,13 @@ class MeshProcessor:
         if self._unpatcher is None:
             raise ValueError("call patchify_and_scale first (it builds the partition)")
         return self._unpatcher.sensor_set(decoder, points, fields)
+
+    def derived_sensor_set(self, decoder, points, readings):
+        """Point sensors on the mesh that read a field (a field id) or a derived quantity (an (op, a, b) spec) as a DerivedSensorSet for `decoder`
+        (MeshUnpatcher.derived_sensor_set)."""
+        if self._unpatcher is None:
+            raise ValueError("call patchify_and_scale first (it builds the partition)")
+        return self._unpatcher.derived_sensor_set(decoder, points, readings)
 
     def sensor_taper(self, sensors, radius) -> torch.Tensor:
         """Gaspari-Cohn localisation weights [P, K] between the patches' centroids and the sensors of a set from sensor_set (MeshUnpatcher.sensor_taper)."""

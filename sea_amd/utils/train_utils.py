@@ -89,7 +89,7 @@ class FieldSpaceLoss(torch.nn.Module):
 
 
 # ------------------------------------------------------------------------------------------------ ensembles (sea_amd/ensemble.py)
-from ..ensemble import DerivedField, DerivedQuantiles, DerivedThresholdVerification, DerivedVerification, EnsembleCRPSLoss, EnsembleFields, EnsembleQuantiles, EnsembleScores, FieldKalman, FieldLikelihood, FieldScores, FieldThresholdVerification, FieldVerification, SensorKalman, SensorLikelihood, SensorSet, SensorThresholdVerification, SensorVerification, ThresholdScores, gaspari_cohn, systematic_resample  # noqa: E402,F401  (re-exported: the particle-filter steps around a RolloutSession)
+from ..ensemble import DerivedField, DerivedQuantiles, DerivedSensorSet, DerivedThresholdVerification, DerivedVerification, EnsembleCRPSLoss, EnsembleFields, EnsembleQuantiles, EnsembleScores, FieldKalman, FieldLikelihood, FieldScores, FieldThresholdVerification, FieldVerification, SensorKalman, SensorLikelihood, SensorSet, SensorThresholdVerification, SensorVerification, ThresholdScores, gaspari_cohn, systematic_resample  # noqa: E402,F401  (re-exported: the particle-filter steps around a RolloutSession)
 
 
 # ------------------------------------------------------------------------------------------------ optimizer
