@@ -43,7 +43,10 @@ const char* sea_last_error(void);
 /* The kernel form the calling thread's last noted launch took, for tests: a static string such as "gemm.tile64" ("" before any noted launch) and
  * two small integers whose meaning depends on the launcher (a / b may be NULL).  Noted by sea_gemm_grouped ("gemm.skinny", "gemm.skinny_long",
  * "gemm.ws", "gemm.256", "gemm.tile64", "gemm.tile128"; a = 1 if the LDS-DMA ring is taken, b = its stages), sea_gemm_rownorm ("gemm_norm.rows16",
- * "gemm_norm.rows16_dma", "gemm_norm.rows64"), sea_attention_fwd ("attn.row", "attn.split4", "attn.split2", "attn.split1"; a = 1 if paired),
+ * "gemm_norm.rows16_dma", "gemm_norm.rows64"), sea_attention_fwd ("attn.row"; a = 1 for the wide-head kernel of head dims 64 / 128 / 256, 0 below;
+ * "attn.split4", "attn.split2", "attn.split1"; a = 1 if paired), the few-row launches sea_gemm_fewrows ("gemv.gemm") and sea_qkv_rope_fewrows ("gemv.qkv";
+ * both: a = MR, the rows of the instantiation — 1, 2 or 4 —, b = KC = K / 512), sea_qkv_rope_grouped ("qkv.skinny", "qkv.tile"), sea_rownorm
+ * ("rownorm.fewrows"; a = KM, the 4-column pieces per thread: 1, 4 or 8; "rownorm.ln_rows"; "rownorm.wave"),
  * sea_attention_bwd ("attn_bwd" at head dims 8 / 16 / 32 / 64 / 128 / 256, "attn_bwd.masked" at the other widths; a = the mode bits of the dQ kernel,
  * b = those of the dK / dV kernel: 1 XCD-local order, 2 paired tiles) and sea_wgrad_grouped ("wgrad.tile64", "wgrad.tile128", "wgrad.tile256"; a = the
  * largest split count over the groups, b = 1 if any group takes the plain store), and by the row-owning launches: sea_mlp_fc1_ln_gelu / sea_mlp_fc2_proj_norm /

@@ -807,7 +807,7 @@ template <typename T>
 static int launch_attention(const SeaAttnParams& P, hipStream_t s) {
     // few workgroups per CU and a long key range: split the key tiles of a query tile over two wave groups
     if (launch_attention_row<T>(P, s)) {
-        sea_note_form("attn.row", 0, 0);
+        sea_note_form("attn.row", P.hd >= 64 ? 1 : 0, 0);   // a: 1 the wide-head kernel (head dims 64 / 128 / 256)
         return 0;
     }
     const long blocks = (long)((P.Tq + 63) / 64) * P.B * P.H * P.n_problems;

@@ -634,6 +634,7 @@ extern "C" int sea_qkv_rope_grouped(const SeaQkvGroup* groups, int n_groups, con
         S.n_groups = n_groups;
         S.c = c;
         qkv_skinny_kernel<<<dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream)>>>(S);
+        sea_note_form("qkv.skinny", 0, 0);
         SEA_CHECK_LAUNCH("sea_qkv_rope_grouped");
         return SEA_OK;
     }
@@ -671,6 +672,7 @@ extern "C" int sea_qkv_rope_grouped(const SeaQkvGroup* groups, int n_groups, con
     if (dtype == SEA_BF16) LAUNCH_QKV_T(__bf16); else LAUNCH_QKV_T(float);
 #undef LAUNCH_QKV_T
 #undef LAUNCH_QKV
+    sea_note_form("qkv.tile", 0, 0);
     SEA_CHECK_LAUNCH("sea_qkv_rope_grouped");
     return SEA_OK;
 }

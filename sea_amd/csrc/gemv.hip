@@ -477,6 +477,7 @@ extern "C" int sea_gemm_fewrows(const SeaGemmGroup* groups, const SeaNormGroup* 
     } else {
         FEW_DISPATCH_KC(gemm_fewrows_kernel, 4, kc, L);
     }
+    sea_note_form("gemv.gemm", mmax == 1 ? 1 : (mmax == 2 ? 2 : 4), kc);   // a: MR; b: KC = K / 512 — the instantiation
     SEA_CHECK_LAUNCH("sea_gemm_fewrows");
     return SEA_OK;
 }
@@ -529,6 +530,7 @@ extern "C" int sea_qkv_rope_fewrows(const SeaQkvGroup* groups, const SeaNormGrou
     } else {
         FEW_DISPATCH_KC4(qkv_fewrows_kernel, 4, kc, L);
     }
+    sea_note_form("gemv.qkv", mmax == 1 ? 1 : (mmax == 2 ? 2 : 4), kc);   // a: MR; b: KC = K / 512 — the instantiation
     SEA_CHECK_LAUNCH("sea_qkv_rope_fewrows");
     return SEA_OK;
 }

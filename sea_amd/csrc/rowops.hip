@@ -401,6 +401,7 @@ extern "C" int sea_rownorm(const SeaNormGroup* groups, int n_groups, int M, int 
         } else {
             rownorm_fewrows_kernel<float, false, 8><<<gridw, blockw, 0, s>>>(L);
         }
+        sea_note_form("rownorm.fewrows", d <= 4096 ? 1 : (d <= 16384 && dtype == SEA_BF16 && x_is_act ? 4 : 8), 0);   // a: KM, the pieces per thread
         SEA_CHECK_LAUNCH("sea_rownorm");
         return SEA_OK;
     }
@@ -430,6 +431,7 @@ extern "C" int sea_rownorm(const SeaNormGroup* groups, int n_groups, int M, int 
             else if (d <= 8192) LAUNCH_LNR(1024, 1);
             else LAUNCH_LNR(1024, 2);
 #undef LAUNCH_LNR
+            sea_note_form("rownorm.ln_rows", 0, 0);
             SEA_CHECK_LAUNCH("sea_rownorm");
             return SEA_OK;
         }
@@ -449,6 +451,7 @@ extern "C" int sea_rownorm(const SeaNormGroup* groups, int n_groups, int M, int 
         LAUNCH_RN(float, false);  // f32 activations: x is float either way
     }
 #undef LAUNCH_RN
+    sea_note_form("rownorm.wave", 0, 0);
     SEA_CHECK_LAUNCH("sea_rownorm");
     return SEA_OK;
 }

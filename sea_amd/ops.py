@@ -79,7 +79,9 @@ def gemm_grouped(groups: Sequence[Dict], dtype: torch.dtype) -> None:
 
 def last_form():
     """(form, a, b) of the calling thread's last noted launch — which kernel sea_gemm_grouped / sea_gemm_rownorm / sea_attention_fwd / sea_attention_bwd /
-    sea_wgrad_grouped and the row-owning launches (MLP, sea_gemm_adaln, sea_exchange_tail, sea_row_chain, sea_adaln_qkv) took (include/sea_hip.h, sea_last_form);
+    sea_wgrad_grouped, the row-owning launches (MLP, sea_gemm_adaln, sea_exchange_tail, sea_row_chain, sea_adaln_qkv) and the few-row launches took
+    (include/sea_hip.h, sea_last_form): sea_gemm_fewrows ("gemv.gemm", MR, KC), sea_qkv_rope_fewrows ("gemv.qkv", MR, KC), sea_qkv_rope_grouped ("qkv.skinny" /
+    "qkv.tile"), sea_rownorm (("rownorm.fewrows", KM, 0) / "rownorm.ln_rows" / "rownorm.wave"), the one-row attention ("attn.row", 1 at head dims >= 64 else 0, 0);
     ("", 0, 0) before any.  For the tests that force a form."""
     a, b = C.c_int(0), C.c_int(0)
     name = N.lib().sea_last_form(C.byref(a), C.byref(b))
